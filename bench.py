@@ -12,6 +12,10 @@ the most time per forward, timed live with hipEvents on the launch stream; the p
 `cpu_baseline` (the CPU oracle = a port of the reference's CPU path, timed on a bounded sample on this box's host cores).
 With N > 1 rank 0 also re-computes the first 64 queries against the WHOLE gallery on its own GPU and requires the sharded
 result to be bit-identical, so the first real RCCL run verifies itself.
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the last timed step returned (the top-k of every query of all
+ranks) as DIR/topk_values.npy (float32) and DIR/topk_indices.npy (float64, exact below 2^53).  The inputs are seeded, so
+two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import glob
@@ -54,7 +58,26 @@ def parse():
     ap.add_argument("--model", default="efficientnet_b3a")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse)")
     ap.add_argument("--single-device", action="store_true", help="rehearsal: every rank uses cuda:0 (needs --backend gloo)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's top-k values / indices to DIR/*.npy (rank 0)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(dirname, out):
+    """(values, indices) of one step -> DIR/topk_values.npy (float32), DIR/topk_indices.npy (float64)."""
+    arrays = {"topk_values": out[0].float().cpu().numpy().astype(np.float32),
+              "topk_indices": out[1].cpu().numpy().astype(np.float64)}
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit"
+    os.makedirs(dirname, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(dirname, f"{name}.npy"), arr)
 
 
 def csrc_sha16():
@@ -176,6 +199,8 @@ def main():
     ms_per_step = dt / a.steps * 1e3
     images_per_s = a.batch * world * a.steps / dt
     assert out[1].shape == (a.batch * world, TOPK)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, out)
     if world > 1 and rank == 0:
         # self-check of the sharded path: the first 64 queries (rank 0's own embeddings) against the WHOLE gallery on this GPU
         with torch.cuda.stream(s_embed):
