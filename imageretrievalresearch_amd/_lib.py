@@ -73,6 +73,12 @@ PROTOTYPES = {
     "mi355_square_pad_normalize": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, vp]),
     "mi355_conv_input_silu": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     "mi355_resize_bilinear_u8": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp]),
+    "mi355_resize_batch_workspace_bytes": (C.c_size_t, [vp, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mi355_resize_batch_u8": (C.c_int, [vp, C.c_int64, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_size_t,
+                                        vp]),
+    "mi355_model_forward_images_workspace_bytes": (C.c_size_t, [vp, C.c_int, C.c_int, C.c_int]),
+    "mi355_model_forward_images": (C.c_int, [vp, vp, C.c_int64, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float),
+                                             C.POINTER(C.c_float), vp, C.c_int, vp, vp, vp, C.c_size_t, vp]),
     "mi355_score_boost": (C.c_int, [vp, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int, vp, vp]),
 }
 

@@ -5,6 +5,7 @@
 #include "ops.h"
 
 #include <stdlib.h>
+#include <type_traits>
 
 namespace mi355 {
 
@@ -88,14 +89,22 @@ int launch_stem(const float* x, const float* w, const float* bias, bf16_t* out, 
 // k_square_pad_normalize -> k_conv_input_silu -> k_stem, so its output is bit-identical to that chain.
 // =====================================================================================
 struct StemU8Args {
-    const unsigned char* img;   // [B][h][w][3]
+    const unsigned char* img;   // [B][h][w][3]; ragged: the packed batch
     int h, w, S, hp, vp, fill;  // S = max(h, w); hp / vp = left / top padding
     float mean[3], stdv[3];
     const float* cw;            // conv_input weights [3][3][3][3] (co, ci, ky, kx) on the device, or null
 };
+struct StemU8RaggedArgs : StemU8Args {
+    const int64_t* desc;        // [B][3] {byte offset, h, w} per image, all with max(h, w) == S
+    int b0;                     // batch index of this launch's first image
+};
 
-template <bool CONV_INPUT>
-__global__ __launch_bounds__(256) void k_stem_u8(const StemU8Args a, const float* __restrict__ w,
+// RAGGED: every image has its own h, w (one longer side S for the batch) and reads them from its descriptor - one load per
+// workgroup; the rest of the kernel is the uniform one, so both give the same bits per image.  (A derived argument struct:
+// the uniform instantiations keep their kernel-argument layout and code.)
+template <bool CONV_INPUT, bool RAGGED>
+__global__ __launch_bounds__(256) void k_stem_u8(const std::conditional_t<RAGGED, StemU8RaggedArgs, StemU8Args> a,
+                                                 const float* __restrict__ w,
                                                  const float* __restrict__ bias, bf16_t* __restrict__ out, int Ho, int Wo,
                                                  int Cout, int act) {
     // CONV_INPUT: the workgroup's 32 x 8 output pixels need conv_input + SiLU on a 65 x 17 window, which needs the
@@ -109,15 +118,21 @@ __global__ __launch_bounds__(256) void k_stem_u8(const StemU8Args a, const float
     const int lx = threadIdx.x & 31, ly = threadIdx.x >> 5;
     const int ox = blockIdx.x * 32 + lx;
     const int oy = blockIdx.y * 8 + ly;
-    const unsigned char* ib = a.img + (size_t)b * a.h * a.w * 3;
+    StemU8Args g = a;      // RAGGED: this image's first byte, size and padding in place of the batch's
+    if constexpr (RAGGED) {
+        const int64_t* d = a.desc + (size_t)(a.b0 + b) * 3;
+        g.img = a.img + d[0]; g.h = (int)d[1]; g.w = (int)d[2];
+        g.hp = (a.S - g.w) / 2; g.vp = (a.S - g.h) / 2;
+    }
+    const unsigned char* ib = RAGGED ? g.img : g.img + (size_t)b * g.h * g.w * 3;
     // the model input at (y, x, c): 0 outside the S x S square (the convolutions' zero padding), the normalised fill
     // colour in the SquarePad border, the normalised pixel inside the image - one rounding per fp32 op, as torch does
     auto pre = [&](int y, int x, int c) -> float {
-        if (y < 0 || y >= a.S || x < 0 || x >= a.S) return 0.f;
-        const int iy = y - a.vp, ix = x - a.hp;
-        int v = a.fill;
-        if (iy >= 0 && iy < a.h && ix >= 0 && ix < a.w) v = ib[((size_t)iy * a.w + ix) * 3 + c];
-        return __fdiv_rn(__fsub_rn(__fdiv_rn((float)v, 255.0f), a.mean[c]), a.stdv[c]);
+        if (y < 0 || y >= g.S || x < 0 || x >= g.S) return 0.f;
+        const int iy = y - g.vp, ix = x - g.hp;
+        int v = g.fill;
+        if (iy >= 0 && iy < g.h && ix >= 0 && ix < g.w) v = ib[((size_t)iy * g.w + ix) * 3 + c];
+        return __fdiv_rn(__fsub_rn(__fdiv_rn((float)v, 255.0f), g.mean[c]), g.stdv[c]);
     };
     float p[27];
     if (!CONV_INPUT) {
@@ -129,7 +144,7 @@ __global__ __launch_bounds__(256) void k_stem_u8(const StemU8Args a, const float
 #pragma unroll
                 for (int ci = 0; ci < 3; ++ci) p[(ky * 3 + kx) * 3 + ci] = pre(oy * 2 - 1 + ky, ox * 2 - 1 + kx, ci);
     } else {
-        if (threadIdx.x < 81) scw[threadIdx.x] = a.cw[threadIdx.x];
+        if (threadIdx.x < 81) scw[threadIdx.x] = g.cw[threadIdx.x];
         const int y0 = blockIdx.y * 16 - 2, x0 = blockIdx.x * 64 - 2;      // pre-processed window origin
         for (int i = threadIdx.x; i < PH * PW; i += 256) {
             const int r = i / PW, c = i - r * PW;
@@ -153,7 +168,7 @@ __global__ __launch_bounds__(256) void k_stem_u8(const StemU8Args a, const float
 #pragma unroll
                         for (int co = 0; co < 3; ++co) acc[co] += v * scw[((co * 3 + ci) * 3 + ky2) * 3 + kx2];
                     }
-            const bool in = y >= 0 && y < a.S && x >= 0 && x < a.S;
+            const bool in = y >= 0 && y < g.S && x >= 0 && x < g.S;
 #pragma unroll
             for (int co = 0; co < 3; ++co) Ct[i * 3 + co] = in ? silu_f(acc[co]) : 0.f;
         }
@@ -188,16 +203,24 @@ _Pragma("unroll")
 
 int launch_stem_u8(const unsigned char* img, int h, int w, int fill, const float* mean, const float* stdv,
                    const float* conv_w, const float* sw, const float* bias, bf16_t* out, int B, int Cout, int act,
-                   hipStream_t st) {
+                   hipStream_t st, const int64_t* desc, int b0) {
     MI355_REQUIRE(Cout % 8 == 0 && Cout <= 256, "stem: Cout=%d must be a multiple of 8 and <= 256", Cout);
-    StemU8Args a{};
+    StemU8RaggedArgs r{};
+    StemU8Args& a = r;
     a.img = img; a.h = h; a.w = w; a.S = h > w ? h : w; a.hp = (a.S - w) / 2; a.vp = (a.S - h) / 2; a.fill = fill;
     for (int c = 0; c < 3; ++c) { a.mean[c] = mean[c]; a.stdv[c] = stdv[c]; }
     a.cw = conv_w;
+    r.desc = desc; r.b0 = b0;
     const int Ho = (a.S + 2 - 3) / 2 + 1, Wo = Ho;
     dim3 grid(cdiv(Wo, 32), cdiv(Ho, 8), B);
-    if (conv_w) hipLaunchKernelGGL((k_stem_u8<true>), grid, dim3(256), 0, st, a, sw, bias, out, Ho, Wo, Cout, act);
-    else hipLaunchKernelGGL((k_stem_u8<false>), grid, dim3(256), 0, st, a, sw, bias, out, Ho, Wo, Cout, act);
+    if (desc) {
+        if (conv_w) hipLaunchKernelGGL((k_stem_u8<true, true>), grid, dim3(256), 0, st, r, sw, bias, out, Ho, Wo, Cout, act);
+        else hipLaunchKernelGGL((k_stem_u8<false, true>), grid, dim3(256), 0, st, r, sw, bias, out, Ho, Wo, Cout, act);
+    } else if (conv_w) {
+        hipLaunchKernelGGL((k_stem_u8<true, false>), grid, dim3(256), 0, st, a, sw, bias, out, Ho, Wo, Cout, act);
+    } else {
+        hipLaunchKernelGGL((k_stem_u8<false, false>), grid, dim3(256), 0, st, a, sw, bias, out, Ho, Wo, Cout, act);
+    }
     MI355_LAUNCH_CHECK();
     return OK;
 }

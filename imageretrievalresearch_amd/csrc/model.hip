@@ -277,7 +277,7 @@ static int exec_op(ExecCtx& cx, const Op& op) {
             if (cx.x_u8)
                 return launch_stem_u8(cx.x_u8, cx.img_h, cx.img_w, cx.fill, cx.mean, cx.stdv, cx.conv_w,
                                       (const float*)cx.w(op.w_off), (const float*)cx.w(op.b_off),
-                                      (bf16_t*)cx.slot_ptr(op.out), cx.nb, op.cout, op.act, cx.st);
+                                      (bf16_t*)cx.slot_ptr(op.out), cx.nb, op.cout, op.act, cx.st, cx.u8_desc, cx.b0);
             return launch_stem(cx.x, (const float*)cx.w(op.w_off), (const float*)cx.w(op.b_off),
                                (bf16_t*)cx.slot_ptr(op.out), cx.nb, cx.H, cx.W, op.cout, op.act, cx.st);
         case OP_GEMM: {
@@ -530,8 +530,9 @@ static int run_backbone(ExecCtx& cx, size_t op_begin = 0, size_t op_end = (size_
     return OK;
 }
 
-struct U8Source {                     // uint8 images in front of the stem (mi355_model_forward_u8)
+struct U8Source {                     // uint8 images in front of the stem (mi355_model_forward_u8 / _images)
     const unsigned char* img = nullptr;
+    const int64_t* desc = nullptr;    // ragged batch (device [B][3] {byte offset, h, w}); h = w = the common longer side
     int h = 0, w = 0, fill = 255;
     float mean[3] = {0.f, 0.f, 0.f}, stdv[3] = {1.f, 1.f, 1.f};
     const float* conv_w = nullptr;
@@ -580,7 +581,8 @@ static int forward_impl(mi355_model* m, const float* x, int B, int H, int W, flo
         ExecCtx cx{m, st, nb, H, W, x ? x + (size_t)b0 * 3 * H * W : nullptr, b0, B};
         cx.lane = nl > 1 ? lane : 0;
         if (u8) {
-            cx.x_u8 = u8->img + (size_t)b0 * u8->h * u8->w * 3;
+            cx.x_u8 = u8->desc ? u8->img : u8->img + (size_t)b0 * u8->h * u8->w * 3;   // ragged: the kernels index desc from b0
+            cx.u8_desc = u8->desc;
             cx.img_h = u8->h; cx.img_w = u8->w; cx.fill = u8->fill; cx.conv_w = u8->conv_w;
             for (int c = 0; c < 3; ++c) { cx.mean[c] = u8->mean[c]; cx.stdv[c] = u8->stdv[c]; }
         }
@@ -827,6 +829,58 @@ int mi355_model_forward_u8(mi355_model_t m, const unsigned char* images, int B, 
     for (int c = 0; c < 3; ++c) { u.mean[c] = mean[c]; u.stdv[c] = stdv[c]; }
     const int S = h > w ? h : w;
     return forward_impl(m, nullptr, B, S, S, out, pooled_out, features_only != 0, (hipStream_t)stream, &u);
+}
+
+size_t mi355_model_forward_images_workspace_bytes(const int64_t* desc_host, int B, int transform, int out_size) {
+    if (transform != 1 && transform != 2) return 0;     // "pad" needs none; anything else is refused by the forward
+    const size_t rs = resize_batch_workspace(desc_host, B, out_size, out_size, transform == 2);
+    return rs ? align_up((size_t)B * out_size * out_size * 3, 256) + rs : 0;
+}
+
+int mi355_model_forward_images(mi355_model_t m, const unsigned char* pixels, int64_t pixels_bytes, const int64_t* desc_host,
+                               const int64_t* desc_dev, int B, int transform, int out_size, int fill, const float* mean,
+                               const float* stdv, const float* conv_input_w, int features_only, float* out, float* pooled_out,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+    MI355_REQUIRE(m && mean && stdv && out, "forward_images: null pointer");
+    if (int e = check_images(pixels, pixels_bytes, desc_host, desc_dev, B, "forward_images")) return e;
+    MI355_REQUIRE(transform >= 0 && transform <= 2, "forward_images: transform %d (0 = pad, 1 = resize, 2 = pad_resize)", transform);
+    MI355_REQUIRE(fill >= 0 && fill <= 255, "forward_images: fill %d is not a byte value", fill);
+    for (int c = 0; c < 3; ++c) MI355_REQUIRE(stdv[c] != 0.f, "forward_images: std[%d] is zero", c);
+    MI355_REQUIRE(!m->def.ops.empty() && (m->def.ops[0].kind == OP_STEM || m->def.ops[0].kind == OP_PATCH_EMBED),
+                  "forward_images: %s has no stem / patch embedding to fuse the pre-processing into", m->def.arch.c_str());
+    const bool swin = m->def.ops[0].kind == OP_PATCH_EMBED;
+    MI355_REQUIRE(!swin || !conv_input_w, "forward_images: conv_input belongs to the convolutional backbones");
+    hipStream_t st = (hipStream_t)stream;
+    U8Source u{};
+    u.fill = fill; u.conv_w = conv_input_w;
+    for (int c = 0; c < 3; ++c) { u.mean[c] = mean[c]; u.stdv[c] = stdv[c]; }
+    if (transform == 0) {    // SquarePad in the stem's loads: one longer side for the whole batch (the reference's collate stacks)
+        const int S = (int)std::max(desc_host[1], desc_host[2]);
+        for (int b = 1; b < B; ++b)
+            MI355_REQUIRE(std::max(desc_host[(size_t)b * 3 + 1], desc_host[(size_t)b * 3 + 2]) == S,
+                          "forward_images: image %d has longer side %lld, image 0 has %d; \"pad\" needs one S per batch", b,
+                          (long long)std::max(desc_host[(size_t)b * 3 + 1], desc_host[(size_t)b * 3 + 2]), S);
+        MI355_REQUIRE(!swin || S == 224, "forward_images: swin needs images whose longer side is 224 (got %d)", S);
+        MI355_REQUIRE(S >= 32, "forward_images: the longer side %d is below the backbone's 32", S);
+        MI355_REQUIRE(m->packed, "forward_images: weights not packed (call mi355_model_pack after set_tensor)");
+        u.img = pixels; u.desc = desc_dev; u.h = S; u.w = S;
+        return forward_impl(m, nullptr, B, S, S, out, pooled_out, features_only != 0, st, &u);
+    }
+    MI355_REQUIRE(out_size >= 1 && out_size <= 16384, "forward_images: out_size %d outside 1..16384", out_size);
+    MI355_REQUIRE(out_size >= 32, "forward_images: out_size %d is below the backbone's 32", out_size);
+    MI355_REQUIRE(!swin || out_size == 224, "forward_images: swin needs out_size 224 (got %d)", out_size);
+    const size_t need = mi355_model_forward_images_workspace_bytes(desc_host, B, transform, out_size);
+    MI355_REQUIRE(workspace && workspace_bytes >= need, "forward_images: workspace of %zu bytes < %zu "
+                  "(mi355_model_forward_images_workspace_bytes)", workspace_bytes, need);
+    MI355_REQUIRE(m->packed, "forward_images: weights not packed (call mi355_model_pack after set_tensor)");
+    // Resize into the head of the workspace, then the uniform uint8 forward (unchanged stem / patch embedding) on it
+    unsigned char* resized = (unsigned char*)workspace;
+    const size_t rbytes = align_up((size_t)B * out_size * out_size * 3, 256);
+    if (int e = resize_batch(pixels, pixels_bytes, desc_host, desc_dev, B, out_size, out_size, transform == 2, fill, resized,
+                             resized + rbytes, workspace_bytes - rbytes, st))
+        return e;
+    u.img = resized; u.h = out_size; u.w = out_size;
+    return forward_impl(m, nullptr, B, out_size, out_size, out, pooled_out, features_only != 0, st, &u);
 }
 
 int mi355_model_enable_taps(mi355_model_t m, int enable) {

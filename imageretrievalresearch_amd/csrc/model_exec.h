@@ -100,6 +100,7 @@ struct ExecCtx {
     int img_h = 0, img_w = 0, fill = 255;
     float mean[3] = {0.f, 0.f, 0.f}, stdv[3] = {1.f, 1.f, 1.f};
     const float* conv_w = nullptr;          // optional conv_input weights (device)
+    const int64_t* u8_desc = nullptr;       // ragged batch: x_u8 is the packed batch, image b0 + b at desc {byte offset, h, w}
     int ln_pending_in = SLOT_NONE;          // a fused LayerNorm left its row statistics in SLOT_LNSTATS: the next GEMM reads this slot instead
     char* base() const { return (char*)m->arena + (size_t)lane * m->lane_bytes; }
     void* slot_ptr(int s) const { return s == SLOT_NONE ? nullptr : base() + m->slots[s].off; }

@@ -110,9 +110,21 @@ int launch_stem(const float* x, const float* w, const float* bias, bf16_t* out, 
 
 // Fused input + stem: img [B][h][w][3] uint8 -> SquarePad(fill) / ToTensor / Normalize (host mean / std) -> optional
 // conv_input (conv_w: device fp32 [3][3][3][3], null = none) + SiLU -> stem; out [B][S/2][S/2][Cout] bf16, S = max(h, w).
+// desc (device int64 [..][3] {byte offset into img, h, w}, or null): a ragged batch whose images share the longer side
+// S = max(h, w) of the arguments; image b of this launch is desc[b0 + b].
 int launch_stem_u8(const unsigned char* img, int h, int w, int fill, const float* mean, const float* stdv,
                    const float* conv_w, const float* sw, const float* bias, bf16_t* out, int B, int Cout, int act,
-                   hipStream_t st);
+                   hipStream_t st, const int64_t* desc = nullptr, int b0 = 0);
+
+// ---- ragged uint8 batches (preprocess.hip) -----------------------------------------------------------------------------
+// Argument checks of a packed batch: B >= 1, non-null pointers, every descriptor {byte offset, h, w} (host copy) in range.
+int check_images(const unsigned char* pixels, int64_t pixels_bytes, const int64_t* desc_host, const int64_t* desc_dev, int B,
+                 const char* who);
+// Pillow BILINEAR resize of every image (pad: of its SquarePad(fill) square) into out [B][out_h][out_w][3] uint8, two launches.
+size_t resize_batch_workspace(const int64_t* desc_host, int B, int out_h, int out_w, bool pad);   // 0 = bad arguments
+int resize_batch(const unsigned char* pixels, int64_t pixels_bytes, const int64_t* desc_host, const int64_t* desc_dev, int B,
+                 int out_h, int out_w, bool pad, int fill, unsigned char* out, void* workspace, size_t workspace_bytes,
+                 hipStream_t st);
 
 // Depthwise k x k (k = 3 or 5), stride 1 or 2, pad k/2.  w [k*k][C] bf16, bias fp32 [C].
 // pool_partial (optional): [B][dw_pool_blocks(...)][C] fp32 partial sums of the un-rounded output

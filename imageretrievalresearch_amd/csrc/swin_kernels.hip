@@ -9,6 +9,7 @@
 #include "model_exec.h"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace mi355 {
 
@@ -50,13 +51,21 @@ constexpr int PE_P = PE_PPT * PE_PG;   // 112 patches per block = 2 patch rows a
 // U8: the input is a batch of decoded uint8 images [B][h][w][3] and the reference's inference transform - SquarePad(fill) ->
 // ToTensor -> Normalize(mean, std), inference/inference.py:48-52 - is applied while the patch rows are loaded (same fp32
 // operation order as k_square_pad_normalize: bit-identical to that kernel followed by the fp32 form; no fp32 NCHW batch in HBM).
+// RAGGED: a packed batch of images of different sizes whose longer side is 224; image b is desc[b0 + b] = {byte offset into
+// img, h, w} and its padding follows from its own h, w (one descriptor load per workgroup, the loads are the uniform ones).
 struct PatchU8Args {
     const unsigned char* img;   // [B][h][w][3]
     int h, w, hp, vp, fill;     // hp / vp = left / top padding of the 224 x 224 square
     float mean[3], stdv[3];
 };
-template <bool U8>
-__global__ __launch_bounds__(256) void k_patch_embed(const float* __restrict__ x, const PatchU8Args u, const float* __restrict__ w,
+struct PatchU8RaggedArgs : PatchU8Args {   // a derived struct: the uniform instantiations keep their argument layout and code
+    const int64_t* desc;        // [B][3] per-image descriptors on the device
+    int b0;                     // batch index of this launch's first image
+};
+template <bool U8, bool RAGGED = false>
+__global__ __launch_bounds__(256) void k_patch_embed(const float* __restrict__ x,
+                                                     const std::conditional_t<RAGGED, PatchU8RaggedArgs, PatchU8Args> u,
+                                                     const float* __restrict__ w,
                                                      const float* __restrict__ bias, const float* __restrict__ gamma,
                                                      const float* __restrict__ beta, bf16_t* __restrict__ out, int H,
                                                      int W, int gw, int L, float eps) {
@@ -72,15 +81,21 @@ __global__ __launch_bounds__(256) void k_patch_embed(const float* __restrict__ x
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
         if (py * gw + px < L) {
             if constexpr (U8) {
-                const unsigned char* ib = u.img + (size_t)b * u.h * u.w * 3;
-                const int iy = 4 * py + dy - u.vp;
+                PatchU8Args g = u;      // RAGGED: this image's first byte, size and padding in place of the batch's
+                if constexpr (RAGGED) {
+                    const int64_t* d = u.desc + (size_t)(u.b0 + b) * 3;
+                    g.img = u.img + d[0]; g.h = (int)d[1]; g.w = (int)d[2];
+                    g.hp = (224 - g.w) / 2; g.vp = (224 - g.h) / 2;
+                }
+                const unsigned char* ib = RAGGED ? g.img : g.img + (size_t)b * g.h * g.w * 3;
+                const int iy = 4 * py + dy - g.vp;
                 float e[4];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    const int ix = 4 * px + q - u.hp;
-                    int pv = u.fill;
-                    if (iy >= 0 && iy < u.h && ix >= 0 && ix < u.w) pv = ib[((size_t)iy * u.w + ix) * 3 + ci];
-                    e[q] = __fdiv_rn(__fsub_rn(__fdiv_rn((float)pv, 255.0f), u.mean[ci]), u.stdv[ci]);
+                    const int ix = 4 * px + q - g.hp;
+                    int pv = g.fill;
+                    if (iy >= 0 && iy < g.h && ix >= 0 && ix < g.w) pv = ib[((size_t)iy * g.w + ix) * 3 + ci];
+                    e[q] = __fdiv_rn(__fsub_rn(__fdiv_rn((float)pv, 255.0f), g.mean[ci]), g.stdv[ci]);
                 }
                 v = (f32x4){e[0], e[1], e[2], e[3]};
             } else {
@@ -482,15 +497,22 @@ int swin_exec(const ModelDef& def, const Op& op, ExecCtx& cx) {
             MI355_REQUIRE(cx.H == 224 && cx.W == 224, "swin needs 224x224 input");
             const int gw = cx.W / 4, L = gw * (cx.H / 4);
             MI355_REQUIRE(2 * gw == PE_P, "patch_embed: kernel is laid out for 56 patches per row");
-            PatchU8Args u{};
+            PatchU8RaggedArgs r{};
+            PatchU8Args& u = r;
             if (cx.x_u8) {            // uint8 images: SquarePad + ToTensor + Normalize fused into the patch loads (mi355_model_forward_u8)
                 MI355_REQUIRE(!cx.conv_w, "swin: the conv_input pre-stem belongs to the convolutional backbones");
                 MI355_REQUIRE(std::max(cx.img_h, cx.img_w) == 224, "swin needs images whose longer side is 224 (got %dx%d)", cx.img_h, cx.img_w);
                 u.img = cx.x_u8; u.h = cx.img_h; u.w = cx.img_w; u.hp = (224 - cx.img_w) / 2; u.vp = (224 - cx.img_h) / 2; u.fill = cx.fill;
                 for (int c = 0; c < 3; ++c) { u.mean[c] = cx.mean[c]; u.stdv[c] = cx.stdv[c]; }
-                hipLaunchKernelGGL(k_patch_embed<true>, dim3(cdiv(L, PE_P), cx.nb), dim3(256), 0, cx.st, (const float*)nullptr, u,
-                                   (const float*)cx.w(op.w_off), (const float*)cx.w(op.b_off), (const float*)cx.w(op.w2_off),
-                                   (const float*)cx.w(op.b2_off), (bf16_t*)cx.slot_ptr(op.out), cx.H, cx.W, gw, L, op.ln_eps);
+                r.desc = cx.u8_desc; r.b0 = cx.b0;
+                if (cx.u8_desc)
+                    hipLaunchKernelGGL((k_patch_embed<true, true>), dim3(cdiv(L, PE_P), cx.nb), dim3(256), 0, cx.st, (const float*)nullptr,
+                                       r, (const float*)cx.w(op.w_off), (const float*)cx.w(op.b_off), (const float*)cx.w(op.w2_off),
+                                       (const float*)cx.w(op.b2_off), (bf16_t*)cx.slot_ptr(op.out), cx.H, cx.W, gw, L, op.ln_eps);
+                else
+                    hipLaunchKernelGGL(k_patch_embed<true>, dim3(cdiv(L, PE_P), cx.nb), dim3(256), 0, cx.st, (const float*)nullptr, u,
+                                       (const float*)cx.w(op.w_off), (const float*)cx.w(op.b_off), (const float*)cx.w(op.w2_off),
+                                       (const float*)cx.w(op.b2_off), (bf16_t*)cx.slot_ptr(op.out), cx.H, cx.W, gw, L, op.ln_eps);
             } else {
                 hipLaunchKernelGGL(k_patch_embed<false>, dim3(cdiv(L, PE_P), cx.nb), dim3(256), 0, cx.st, cx.x, u, (const float*)cx.w(op.w_off),
                                    (const float*)cx.w(op.b_off), (const float*)cx.w(op.w2_off), (const float*)cx.w(op.b2_off),

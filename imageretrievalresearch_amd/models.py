@@ -475,12 +475,7 @@ class MI355Model(nn.Module):
         self._ensure_packed(images.device)
         B, h, w, _ = images.shape
         S = max(h, w)
-        cw = None
-        if conv_input is not None:
-            conv = conv_input[0] if isinstance(conv_input, nn.Sequential) else getattr(conv_input, "conv", conv_input)
-            if not isinstance(conv, nn.Conv2d) or tuple(conv.weight.shape) != (3, 3, 3, 3) or conv.bias is not None:
-                raise MI355Error("conv_input must be Sequential(Conv2d(3, 3, 3, 1, 1, bias=False), SiLU)")
-            cw = conv.weight.detach().to(images.device, torch.float32).contiguous()
+        cw = _conv_input_weight(conv_input, images.device)
         D = self.num_features
         if features and self.family == "swin":
             out = torch.empty((B, D), dtype=torch.float32, device=images.device)      # timm's swin forward_features is pooled
@@ -494,6 +489,61 @@ class MI355Model(nn.Module):
                 check(lib().mi355_model_forward_u8(self._handle, images.data_ptr(), B, h, w, int(fill), m3, s3,
                                                    cw.data_ptr() if cw is not None else None, int(features),
                                                    out.data_ptr(), None, stream_ptr(images.device)))
+        return out if features else self._custom_head(out)
+
+    def forward_images(self, images, transform: str = "pad", size: int = 224, mean=None, std=None, fill: int = 255,
+                       conv_input: "nn.Module | None" = None, features: bool = False) -> torch.Tensor:
+        """``forward_uint8`` for a RAGGED batch: ``images`` is a list of uint8 (H, W, 3) device tensors of any sizes (or a
+        ``preprocess.pack_images`` pair), as a dataset yields them.  ``transform``:
+
+        * ``"pad"`` - the inference transform of inference/inference.py:48-52: SquarePad(fill) -> ToTensor -> Normalize.
+          All images share the longer side S (what the reference's collate stacks; 224 for Swin).  Fused into the stem /
+          patch embedding, which reads each image's size from a descriptor: bit-identical per image to
+          ``forward(preprocess.square_pad_normalize(images))`` at the same B.
+        * ``"resize"`` - the train / notebook transform of train/train.py:48-50: Resize((size, size)) (Pillow BILINEAR,
+          bit-exact) -> ToTensor, no normalisation: the resize runs for the whole batch in two launches
+          (``preprocess.resize_batch``), then the uniform uint8 forward.
+        * ``"pad_resize"`` - SquarePad(fill) then Resize((size, size)) -> Normalize.
+
+        ``mean`` / ``std`` default to the reference transform of each mode: ImageNet statistics for ``"pad"`` and
+        ``"pad_resize"`` (inference/inference.py:50-52), 0 / 1 for ``"resize"`` (train/train.py:48 does not normalise).
+        ``conv_input``, ``features`` and a user-assigned head behave as in ``forward_uint8``."""
+        from . import preprocess
+        self._refuse_training()
+        modes = {"pad": 0, "resize": 1, "pad_resize": 2}
+        if transform not in modes:
+            raise MI355Error(f"forward_images: transform {transform!r} is not one of {sorted(modes)}")
+        if self.family == "swin" and conv_input is not None:
+            raise MI355Error("forward_images: conv_input belongs to the convolutional backbones")
+        if mean is None:
+            mean = (0.0, 0.0, 0.0) if transform == "resize" else preprocess.IMAGENET_MEAN
+        if std is None:
+            std = (1.0, 1.0, 1.0) if transform == "resize" else preprocess.IMAGENET_STD
+        pixels, desc, desc_dev = preprocess.ragged_batch(images)
+        dev = pixels.device
+        self._ensure_packed(dev)
+        B = desc.shape[0]
+        if transform == "pad":
+            S = int(max(desc[0, 1], desc[0, 2]))
+        else:
+            S = int(size)
+        cw = _conv_input_weight(conv_input, dev)
+        D = self.num_features
+        if features and self.family == "swin":
+            out = torch.empty((B, D), dtype=torch.float32, device=dev)
+        elif features:
+            out = torch.empty((B, D, (S + 31) // 32, (S + 31) // 32), dtype=torch.float32, device=dev)
+        else:
+            out = torch.empty((B, self.num_classes if self.num_classes > 0 else D), dtype=torch.float32, device=dev)
+        L = lib()
+        ws = L.mi355_model_forward_images_workspace_bytes(desc.data_ptr(), B, modes[transform], S)
+        work = torch.empty((ws,), dtype=torch.uint8, device=dev) if ws else None
+        m3, s3 = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
+        with torch.cuda.device(dev):
+            check(L.mi355_model_forward_images(self._handle, pixels.data_ptr(), pixels.numel(), desc.data_ptr(), desc_dev.data_ptr(),
+                                               B, modes[transform], S, int(fill), m3, s3,
+                                               cw.data_ptr() if cw is not None else None, int(features), out.data_ptr(), None,
+                                               work.data_ptr() if work is not None else None, ws, stream_ptr(dev)))
         return out if features else self._custom_head(out)
 
     def embed(self, x: torch.Tensor):
@@ -518,6 +568,16 @@ class MI355Model(nn.Module):
                 lib().mi355_model_destroy(h)
             except Exception:
                 pass
+
+
+def _conv_input_weight(conv_input, device):
+    """The (3, 3, 3, 3) fp32 device weight of a ``Sequential(Conv2d(3, 3, 3, 1, 1, bias=False), SiLU)`` pre-stem, or None."""
+    if conv_input is None:
+        return None
+    conv = conv_input[0] if isinstance(conv_input, nn.Sequential) else getattr(conv_input, "conv", conv_input)
+    if not isinstance(conv, nn.Conv2d) or tuple(conv.weight.shape) != (3, 3, 3, 3) or conv.bias is not None:
+        raise MI355Error("conv_input must be Sequential(Conv2d(3, 3, 3, 1, 1, bias=False), SiLU)")
+    return conv.weight.detach().to(device, torch.float32).contiguous()
 
 
 def create_model(model_name: str, pretrained: bool = False, num_classes: int = 1000, seed: int = 0, **kwargs):

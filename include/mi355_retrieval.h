@@ -189,6 +189,41 @@ int mi355_model_forward_u8(mi355_model_t m, const unsigned char* images, int B, 
                            const float* mean, const float* stdv, const float* conv_input_w, int features_only,
                            float* out, float* pooled_out, void* stream);
 
+/* Ragged batches of decoded images: the images of a batch may all have different sizes.  They are packed in
+ * one device buffer `pixels` of pixels_bytes bytes and described by desc[B][3] int64 = {byte offset of the image in pixels,
+ * h, w}, each image uint8 RGB HWC.  The descriptors come twice with the same content: desc_host (HOST) is what the library
+ * checks and plans with, desc_dev (DEVICE) is what the kernels read; the caller keeps desc_dev alive until the work has run.
+ * Checked before any HIP call: non-null pointers, B >= 1, 1 <= h, w <= 16384, every image inside pixels_bytes.
+ *
+ * mi355_resize_batch_u8: transforms.Resize((out_h, out_w)) of train/train.py:48 on every image, bit-exact with Pillow as
+ * mi355_resize_bilinear_u8 (same tables, same integer MACs) -> out [B][out_h][out_w][3] uint8, in two launches for the
+ * whole batch.  pad != 0: SquarePad(fill) (utils/square_pad.py:20-36) first - each image is resampled as its own virtual
+ * S x S square, S = max(h, w), whose border reads `fill`.  workspace: mi355_resize_batch_workspace_bytes(...) device bytes
+ * (the per-call plan and the horizontal-pass rows).  Tables for sizes a device sees for the first time are uploaded with one
+ * copy and one stream synchronise per call; nothing else synchronises. */
+size_t mi355_resize_batch_workspace_bytes(const int64_t* desc_host, int B, int out_h, int out_w, int pad);
+int mi355_resize_batch_u8(const unsigned char* pixels, int64_t pixels_bytes, const int64_t* desc_host, const int64_t* desc_dev,
+                          int B, int out_h, int out_w, int pad, int fill, unsigned char* out, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
+/* mi355_model_forward_u8 for a ragged batch.  transform:
+ *   0 "pad"         SquarePad(fill) -> ToTensor -> Normalize, inference/inference.py:48-52: every image must have the same
+ *                   longer side S (224 for swin); the pre-processing is fused into the stem / patch embedding, which reads
+ *                   each image's descriptor.  Bit-identical per image to mi355_square_pad_normalize + mi355_model_forward
+ *                   at the same B.  out_size and the workspace are not used.
+ *   1 "resize"      Resize((out_size, out_size)) (train/train.py:48) with mi355_resize_batch_u8 into the workspace, then
+ *                   mi355_model_forward_u8 on that uniform batch.
+ *   2 "pad_resize"  SquarePad(fill) then Resize, likewise.
+ * mean / stdv: HOST float[3]; conv_input_w: as mi355_model_forward_u8 (conv backbones only); out / pooled_out as
+ * mi355_model_forward (features_only = 0) or _features (1) at S x S, S = the common longer side or out_size.  Also checked
+ * before any HIP call: fill in 0..255, nonzero std, out_size in 1..16384 (and >= 32; 224 for swin) for transforms 1 and 2,
+ * the workspace size. */
+size_t mi355_model_forward_images_workspace_bytes(const int64_t* desc_host, int B, int transform, int out_size);
+int mi355_model_forward_images(mi355_model_t m, const unsigned char* pixels, int64_t pixels_bytes, const int64_t* desc_host,
+                               const int64_t* desc_dev, int B, int transform, int out_size, int fill, const float* mean,
+                               const float* stdv, const float* conv_input_w, int features_only, float* out, float* pooled_out,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
 /* Debug/parity tap: copy the bf16 NHWC activation the executor produced for layer `tap_name`
  * (e.g. "stem", "blocks.1.0") during the LAST forward into out as fp32 NCHW.  Taps are recorded
  * only after mi355_model_enable_taps(m, 1). */
