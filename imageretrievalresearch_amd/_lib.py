@@ -31,6 +31,11 @@ PROTOTYPES = {
     "mi355_gallery_prepare": (C.c_int, [vp, C.c_int64, C.c_int, vp, C.c_size_t, vp]),
     "mi355_rank_topk_prepared": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_int64, vp, vp, vp,
                                            C.c_size_t, vp]),
+    "mi355_gallery_f16_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
+    "mi355_gallery_to_f16": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, C.c_float, vp, C.c_size_t, vp]),
+    "mi355_rank_f16_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int, C.c_int]),
+    "mi355_rank_topk_f16": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_int64, vp, vp, vp,
+                                      C.c_size_t, vp]),
     "mi355_cosine_scores": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_float, vp, vp,
                                       C.c_size_t, vp]),
     "mi355_topk_rows": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int, C.c_int64, vp, vp, vp, C.c_size_t, vp]),

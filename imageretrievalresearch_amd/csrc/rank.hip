@@ -10,7 +10,7 @@
 //   * MI355_RANK_EXACT_F32=1, gallery rows not 16-byte aligned, or Q <= 4 (GEMV): v_mfma_f32_32x32x2_f32 / fmaf, bit-for-bit
 //     an fp32 fmaf chain (2.7x the matrix-pipe time).
 // Either way an index can only differ from the CPU oracle where two scores are closer than fp32 summation noise.
-#include "common.h"
+#include "rank_common.h"
 #include "../../include/mi355_retrieval.h"
 
 #include <limits.h>
@@ -18,10 +18,6 @@
 #include <math.h>
 
 namespace mi355 {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef long long i64;
 
 // =====================================================================================
 // row norms
@@ -35,18 +31,7 @@ __global__ __launch_bounds__(256) void k_row_norm(const float* __restrict__ in, 
     const i64 row = (i64)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
     const float* x = in + row * dim;
-    float ss = 0.f;
-    if (vec) {
-        const f32x4* x4 = reinterpret_cast<const f32x4*>(x);
-        for (int i = lane; i < dim / 4; i += 64) {
-            f32x4 v = x4[i];
-            ss += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
-        }
-    } else {
-        for (int i = lane; i < dim; i += 64) ss += x[i] * x[i];
-    }
-    ss = wave_sum(ss);
-    const float r = 1.0f / fmaxf(sqrtf(ss), eps);
+    const float r = row_inv_norm(x, dim, eps, vec, lane);
     if (inv != nullptr && lane == 0) inv[row] = r;
     if (WRITE_ROWS) {
         float* y = out + row * dim;
@@ -64,8 +49,6 @@ __global__ __launch_bounds__(256) void k_row_norm(const float* __restrict__ in, 
     }
 }
 
-static inline int vec_ok(const void* p, int dim) { return (dim % 4 == 0) && (((uintptr_t)p & 15) == 0); }
-
 // =====================================================================================
 // top-k selection
 // =====================================================================================
@@ -76,23 +59,6 @@ __device__ __forceinline__ bool better(float a, i64 ia, float b, i64 ib) {
     const bool an = a != a, bn = b != b;
     if (an || bn) return (an && !bn) || (an && bn && ia < ib);
     return (a > b) || (a == b && ia < ib);
-}
-
-constexpr float NEG_INF = -INFINITY;
-constexpr i64 IDX_PAD = LLONG_MAX;
-
-constexpr int IDX32_PAD = INT_MAX;   // missing candidate in the fused per-tile lists (local int32 indices)
-
-// Order-preserving map float -> uint32 for the fused selection: larger key = better score.  NaN maps to the largest key
-// (torch.topk's order), -0 to the key of +0 (they compare equal as floats), every real score to a key > 0.
-__device__ __forceinline__ unsigned score_key(float x) {
-    const unsigned u = __float_as_uint(x + 0.0f);                  // -0 -> +0
-    if ((u & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;       // NaN
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key_score(unsigned key) {
-    if (key == 0xffffffffu) return __uint_as_float(0x7fc00000u);   // canonical NaN
-    return __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key);
 }
 
 // =====================================================================================
@@ -148,11 +114,6 @@ __global__ __launch_bounds__(256) void k_split_queries(const float* __restrict__
     o[0] = h; o[64] = m; o[128] = l;
 }
 
-__device__ __forceinline__ void glds16(const bf16_t* gsrc, bf16_t* lds_dst) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                     (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
-}
-
 // =====================================================================================
 // cosine GEMM:  S[q][g] = sum_d Qn[q][d] * Gal[g][d] * (ginv ? ginv[g] : 1)
 // =====================================================================================
@@ -161,134 +122,8 @@ __device__ __forceinline__ void glds16(const bf16_t* gsrc, bf16_t* lds_dst) {
 // [rows][BK + 4] floats (the 4-float pad makes ds_read_b128 of 16 distinct rows bank-conflict free).
 // Per lane a float4 at k = 8t + 4*(lane>>5) feeds four 32x32x2 k-steps; A and B use the same k
 // permutation, which only reorders the (exact) fma chain.
-constexpr int RK_BN = 128;
 
-// Launch order of the GEMM tiles (speed only, every result is the same for any order): the grid is one-dimensional and the
-// query blocks of ONE gallery tile get the linear ids L, L + 8, L + 16, ...  The dispatcher deals workgroups round-robin
-// over the 8 XCDs, so those workgroups share an L2 and start in the same round: the gallery tile comes from HBM once and
-// the other query blocks hit it in L2.  (With a (tile, query block) grid, x fastest, all tiles of query block 0 filled the
-// machine before query block 1 started: PMC showed every gallery row fetched from HBM once per query block.)
-__device__ __forceinline__ void rank_tile_of(int L, int ntiles, int ny, int& tx, int& ty) {
-    const int full = (ntiles >> 3) << 3;
-    if (L < full * ny) {
-        const int g = L / (8 * ny), r = L - g * 8 * ny;
-        tx = g * 8 + (r & 7);
-        ty = r >> 3;
-    } else {
-        const int r = L - full * ny, rem = ntiles - full;
-        ty = r / rem;
-        tx = full + r - ty * rem;
-    }
-}
 
-// Epilogue shared by the exact-fp32 and the split-bf16 loops (same accumulator layout: the C/D map of the 32x32 MFMAs does
-// not depend on the input type): FK = 0 writes the score slab, FK > 0 selects per-tile candidates.  Called after a
-// __syncthreads() that retired every read of the staging buffers (smem is reused).
-template <int MT, int FK>
-__device__ __forceinline__ void cos_gemm_epilogue(f32x16 (&acc)[MT][2], float* smem, const float* __restrict__ ginv,
-                                                  float* __restrict__ S, int Q, i64 G, int k, float* __restrict__ cand_val,
-                                                  int* __restrict__ cand_idx, int x0, int ntx, i64 n0, int m0) {
-    constexpr int BM = 64 * MT;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1, lr = lane & 31;
-    if constexpr (FK > 0) {
-        // (the loop's last __syncthreads() retired every read of the staging buffers)
-        // 64 query rows at a time, so that the transposed tile (64 x 132 floats = 33.8 KB) fits inside the staging
-        // buffers: a bigger LDS request would cost the third resident workgroup per CU and with it a round of tiles
-        constexpr int CLD = RK_BN + 4;                 // 132 floats: a thread per row reads float4s conflict-free
-        float* Ct = smem;                              // [64][CLD]
-        const i64 ncol = (G - n0 < RK_BN) ? G - n0 : RK_BN;     // valid columns of this tile
-#pragma unroll 1
-        for (int h = 0; h < BM / 64; ++h) {
-            if ((wm * MT * 32) / 64 == h) {            // this wave's rows belong to pass h
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const i64 col = n0 + wn * 64 + j * 32 + lr;
-                    const float gs = (ginv && col < G) ? ginv[col] : 1.0f;
-#pragma unroll
-                    for (int i = 0; i < MT; ++i)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) {
-                            const int row = (wm * MT * 32) % 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                            Ct[row * CLD + wn * 64 + j * 32 + lr] = acc[i][j][r] * gs;
-                        }
-                }
-            }
-            __syncthreads();
-            // Selection: FOUR threads per query row, each scans 32 columns in ascending order into a sorted FK-list held as
-            // order-preserving integer keys (NaN = largest, -0 = +0); the insertion is branch-free (a divergent insertion
-            // sort cost 10 % of the tile: some lane of the wave inserts at almost every column) and skipped by a wave vote
-            // when no lane beats its FK-th entry.  The row's four lists are merged through shuffles in column order, so
-            // ties keep resolving to the lower index.
-            {
-                const int lrow = tid >> 2, part = tid & 3;
-                unsigned kv[FK];
-                int ki[FK];
-#pragma unroll
-                for (int i = 0; i < FK; ++i) { kv[i] = 0u; ki[i] = IDX32_PAD; }      // key 0 = below every real score (-inf is 0x007fffff)
-                auto insert = [&](unsigned key, int id) {
-                    bool g[FK];
-#pragma unroll
-                    for (int i = 0; i < FK; ++i) g[i] = key > kv[i];          // strict: an equal score keeps the earlier (lower) index
-#pragma unroll
-                    for (int i = FK - 1; i > 0; --i) {
-                        kv[i] = g[i] ? (g[i - 1] ? kv[i - 1] : key) : kv[i];
-                        ki[i] = g[i] ? (g[i - 1] ? ki[i - 1] : id) : ki[i];
-                    }
-                    kv[0] = g[0] ? key : kv[0];
-                    ki[0] = g[0] ? id : ki[0];
-                };
-                const float* rowp = Ct + lrow * CLD + part * 32;
-#pragma unroll 2
-                for (int c4i = 0; c4i < 8; ++c4i) {
-                    const f32x4 v4 = *reinterpret_cast<const f32x4*>(rowp + c4i * 4);
-                    const float vv[4] = {v4.x, v4.y, v4.z, v4.w};
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int c = part * 32 + c4i * 4 + e;
-                        unsigned key = score_key(vv[e]);
-                        if (c >= ncol) key = 0u;
-                        if (__any(key > kv[FK - 1])) insert(key, (int)n0 + c);      // n0 + c < 2^31 (checked on the host)
-                    }
-                }
-                // merge parts 1..3 into part 0 (lanes 4r .. 4r+3 of one wave)
-#pragma unroll
-                for (int src = 1; src < 4; ++src) {
-#pragma unroll
-                    for (int i = 0; i < FK; ++i) {
-                        const unsigned ok = (unsigned)__shfl(kv[i], (lane & ~3) + src, 64);
-                        const int oi = __shfl(ki[i], (lane & ~3) + src, 64);
-                        if (part == 0) insert(ok, oi);
-                    }
-                }
-                const int qrow = m0 + h * 64 + lrow;
-                if (part == 0 && qrow < Q) {
-                    const size_t o = ((size_t)qrow * ntx + (size_t)(n0 / RK_BN)) * k;
-#pragma unroll
-                    for (int i = 0; i < FK; ++i)
-                        if (i < k) { cand_val[o + i] = ki[i] == IDX32_PAD ? NEG_INF : key_score(kv[i]); cand_idx[o + i] = ki[i]; }
-                }
-            }
-            __syncthreads();
-        }
-        return;
-    }
-    // epilogue: C[row = query][col = gallery]; lane: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const i64 col = n0 + wn * 64 + j * 32 + lr;
-        if (col >= G) continue;
-        const float gs = ginv ? ginv[col] : 1.0f;
-#pragma unroll
-        for (int i = 0; i < MT; ++i) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = m0 + wm * MT * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                if (row < Q) S[(i64)row * G + col] = acc[i][j][r] * gs;
-            }
-        }
-    }
-}
 
 // FK = 0: write the score slab S.  FK = 1/2/4/8 (fused selection, k <= FK): the score tile never leaves the CU - it is
 // transposed through LDS (the staging buffers are free after the K loop), each of the tile's query rows is scanned by one
@@ -1041,8 +876,6 @@ __global__ void k_distinct_topn(const i64* __restrict__ idx, const float* __rest
 // =====================================================================================
 // host drivers
 // =====================================================================================
-constexpr int SMALL_K = 8;
-constexpr int LARGE_K = 1024;
 constexpr i64 SMALL_CHUNK = 8192;
 
 struct TopkPlan {
@@ -1053,7 +886,7 @@ struct TopkPlan {
 
 static i64 level1_chunks(i64 G, int k) { return k <= SMALL_K ? cdiv(G, SMALL_CHUNK) : cdiv(G, BT_N); }
 
-static size_t topk_ws_bytes(i64 Q, i64 G, int k) {
+size_t topk_ws_bytes(i64 Q, i64 G, int k) {
     const i64 per_row = level1_chunks(G, k) * k;
     // two ping-pong buffers of (val f32 + idx i64)
     return 2 * align_up((size_t)Q * per_row * (sizeof(float) + sizeof(i64)), 256) + 256;
@@ -1075,9 +908,8 @@ static void dispatch_small(const float* v, const i64* ix, const int* ix32, i64 r
 
 // Select top-k of each row of vals[Q][rowlen] (implicit or explicit indices) into out_val/out_idx [Q][k].
 // idxs32 (with idxs == nullptr): int32 local candidate indices of the fused GEMM epilogue, k <= SMALL_K only.
-static int topk_select(const float* vals, const i64* idxs, i64 Q, i64 rowlen, i64 in_stride, int k, i64 idx_offset,
-                       float* out_val, i64* out_idx, void* ws, size_t ws_bytes, hipStream_t st,
-                       const int* idxs32 = nullptr) {
+int topk_select(const float* vals, const i64* idxs, i64 Q, i64 rowlen, i64 in_stride, int k, i64 idx_offset,
+                float* out_val, i64* out_idx, void* ws, size_t ws_bytes, hipStream_t st, const int* idxs32) {
     MI355_REQUIRE(k >= 1 && k <= LARGE_K, "top-k: k=%d outside [1,%d]", k, LARGE_K);
     MI355_REQUIRE(k <= rowlen, "top-k: k=%d exceeds row length %lld", k, (long long)rowlen);
     MI355_REQUIRE(!idxs32 || k <= SMALL_K, "top-k: int32 candidate lists need k <= %d", SMALL_K);
@@ -1122,9 +954,9 @@ static int topk_select(const float* vals, const i64* idxs, i64 Q, i64 rowlen, i6
     return OK;
 }
 
-static bool fused_select(i64 Q, i64 G, int k) { return k >= 1 && k <= SMALL_K && Q > 4 && G < ((i64)1 << 31) - RK_BN; }
+bool fused_select(i64 Q, i64 G, int k) { return k >= 1 && k <= SMALL_K && Q > 4 && G < ((i64)1 << 31) - RK_BN; }
 
-static i64 query_block(i64 Q, i64 G, int k) {
+i64 query_block(i64 Q, i64 G, int k) {
     if (fused_select(Q, G, k)) {
         // no score slab: candidates are cdiv(G,128) * k * 8 B per query; keep them <= 32 MiB per block of queries (a second
         // block costs one more pass over the gallery, which a GEMM of >= 1000 queries hides)
@@ -1171,7 +1003,7 @@ static RankWs carve(void* ws, i64 Q, i64 G, int D, int k, bool need_ginv, bool n
 }
 
 // resident workgroups per CU x CUs of the current device for one kernel instantiation (cached per device by the caller)
-static int kernel_slots(const void* fn, size_t lds, int* cache, int* slots_out) {
+int kernel_slots(const void* fn, size_t lds, int* cache, int* slots_out) {
     int dev = 0;
     MI355_CHECK_HIP(hipGetDevice(&dev));
     MI355_REQUIRE(dev >= 0 && dev < MI355_MAX_DEVICES, "rank: device ordinal %d out of range", dev);
@@ -1213,7 +1045,7 @@ static size_t split_lds(bool fk) {
 // (0.15 ms of 0.83 at Q=256 x 100k on the fp32 loop).  Whole rounds go out as 128-row tiles, the remainder as a second
 // launch of 64-row tiles (same column tiles, same k order: every score is bit-identical), which halves the tiles' length
 // and doubles their number.  Returns the number of column tiles of the main launch.
-static int whole_round_tiles(int ntx, int ny, int slots) {
+int whole_round_tiles(int ntx, int ny, int slots) {
     if ((long)ntx * ny > slots && ((long)ntx * ny) % slots != 0) return (int)(((long)ntx * ny / slots) * slots / ny);
     return ntx;
 }

@@ -1,0 +1,207 @@
+// Shared between the rank kernels (rank.hip: fp32 rows, bf16 planes; rank_f16.hip: fp16 rows): the launch order of the
+// cosine GEMM's tiles, its epilogue (score slab or fused per-tile top-k) and the host side of the top-k selection that
+// merges what the epilogue leaves.  gfx950 only.
+#pragma once
+#include "common.h"
+
+#include <limits.h>
+#include <math.h>
+
+namespace mi355 {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef long long i64;
+
+constexpr float NEG_INF = -INFINITY;
+constexpr i64 IDX_PAD = LLONG_MAX;
+
+constexpr int IDX32_PAD = INT_MAX;   // missing candidate in the fused per-tile lists (local int32 indices)
+
+// Order-preserving map float -> uint32 for the fused selection: larger key = better score.  NaN maps to the largest key
+// (torch.topk's order), -0 to the key of +0 (they compare equal as floats), every real score to a key > 0.
+__device__ __forceinline__ unsigned score_key(float x) {
+    const unsigned u = __float_as_uint(x + 0.0f);                  // -0 -> +0
+    if ((u & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;       // NaN
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float key_score(unsigned key) {
+    if (key == 0xffffffffu) return __uint_as_float(0x7fc00000u);   // canonical NaN
+    return __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key);
+}
+
+constexpr int RK_BN = 128;
+
+// 16 bytes per lane from global memory straight into LDS (lane-linear destination; no register is written)
+__device__ __forceinline__ void glds16(const bf16_t* gsrc, bf16_t* lds_dst) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
+                                     (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
+}
+
+// Launch order of the GEMM tiles (speed only, every result is the same for any order): the grid is one-dimensional and the
+// query blocks of ONE gallery tile get the linear ids L, L + 8, L + 16, ...  The dispatcher deals workgroups round-robin
+// over the 8 XCDs, so those workgroups share an L2 and start in the same round: the gallery tile comes from HBM once and
+// the other query blocks hit it in L2.  (With a (tile, query block) grid, x fastest, all tiles of query block 0 filled the
+// machine before query block 1 started: PMC showed every gallery row fetched from HBM once per query block.)
+__device__ __forceinline__ void rank_tile_of(int L, int ntiles, int ny, int& tx, int& ty) {
+    const int full = (ntiles >> 3) << 3;
+    if (L < full * ny) {
+        const int g = L / (8 * ny), r = L - g * 8 * ny;
+        tx = g * 8 + (r & 7);
+        ty = r >> 3;
+    } else {
+        const int r = L - full * ny, rem = ntiles - full;
+        ty = r / rem;
+        tx = full + r - ty * rem;
+    }
+}
+
+// Epilogue shared by the exact-fp32 and the split-bf16 loops (same accumulator layout: the C/D map of the 32x32 MFMAs does
+// not depend on the input type): FK = 0 writes the score slab, FK > 0 selects per-tile candidates.  Called after a
+// __syncthreads() that retired every read of the staging buffers (smem is reused).
+template <int MT, int FK>
+__device__ __forceinline__ void cos_gemm_epilogue(f32x16 (&acc)[MT][2], float* smem, const float* __restrict__ ginv,
+                                                  float* __restrict__ S, int Q, i64 G, int k, float* __restrict__ cand_val,
+                                                  int* __restrict__ cand_idx, int x0, int ntx, i64 n0, int m0) {
+    constexpr int BM = 64 * MT;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1, lr = lane & 31;
+    if constexpr (FK > 0) {
+        // (the loop's last __syncthreads() retired every read of the staging buffers)
+        // 64 query rows at a time, so that the transposed tile (64 x 132 floats = 33.8 KB) fits inside the staging
+        // buffers: a bigger LDS request would cost the third resident workgroup per CU and with it a round of tiles
+        constexpr int CLD = RK_BN + 4;                 // 132 floats: a thread per row reads float4s conflict-free
+        float* Ct = smem;                              // [64][CLD]
+        const i64 ncol = (G - n0 < RK_BN) ? G - n0 : RK_BN;     // valid columns of this tile
+#pragma unroll 1
+        for (int h = 0; h < BM / 64; ++h) {
+            if ((wm * MT * 32) / 64 == h) {            // this wave's rows belong to pass h
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const i64 col = n0 + wn * 64 + j * 32 + lr;
+                    const float gs = (ginv && col < G) ? ginv[col] : 1.0f;
+#pragma unroll
+                    for (int i = 0; i < MT; ++i)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            const int row = (wm * MT * 32) % 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                            Ct[row * CLD + wn * 64 + j * 32 + lr] = acc[i][j][r] * gs;
+                        }
+                }
+            }
+            __syncthreads();
+            // Selection: FOUR threads per query row, each scans 32 columns in ascending order into a sorted FK-list held as
+            // order-preserving integer keys (NaN = largest, -0 = +0); the insertion is branch-free (a divergent insertion
+            // sort cost 10 % of the tile: some lane of the wave inserts at almost every column) and skipped by a wave vote
+            // when no lane beats its FK-th entry.  The row's four lists are merged through shuffles in column order, so
+            // ties keep resolving to the lower index.
+            {
+                const int lrow = tid >> 2, part = tid & 3;
+                unsigned kv[FK];
+                int ki[FK];
+#pragma unroll
+                for (int i = 0; i < FK; ++i) { kv[i] = 0u; ki[i] = IDX32_PAD; }      // key 0 = below every real score (-inf is 0x007fffff)
+                auto insert = [&](unsigned key, int id) {
+                    bool g[FK];
+#pragma unroll
+                    for (int i = 0; i < FK; ++i) g[i] = key > kv[i];          // strict: an equal score keeps the earlier (lower) index
+#pragma unroll
+                    for (int i = FK - 1; i > 0; --i) {
+                        kv[i] = g[i] ? (g[i - 1] ? kv[i - 1] : key) : kv[i];
+                        ki[i] = g[i] ? (g[i - 1] ? ki[i - 1] : id) : ki[i];
+                    }
+                    kv[0] = g[0] ? key : kv[0];
+                    ki[0] = g[0] ? id : ki[0];
+                };
+                const float* rowp = Ct + lrow * CLD + part * 32;
+#pragma unroll 2
+                for (int c4i = 0; c4i < 8; ++c4i) {
+                    const f32x4 v4 = *reinterpret_cast<const f32x4*>(rowp + c4i * 4);
+                    const float vv[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int c = part * 32 + c4i * 4 + e;
+                        unsigned key = score_key(vv[e]);
+                        if (c >= ncol) key = 0u;
+                        if (__any(key > kv[FK - 1])) insert(key, (int)n0 + c);      // n0 + c < 2^31 (checked on the host)
+                    }
+                }
+                // merge parts 1..3 into part 0 (lanes 4r .. 4r+3 of one wave)
+#pragma unroll
+                for (int src = 1; src < 4; ++src) {
+#pragma unroll
+                    for (int i = 0; i < FK; ++i) {
+                        const unsigned ok = (unsigned)__shfl(kv[i], (lane & ~3) + src, 64);
+                        const int oi = __shfl(ki[i], (lane & ~3) + src, 64);
+                        if (part == 0) insert(ok, oi);
+                    }
+                }
+                const int qrow = m0 + h * 64 + lrow;
+                if (part == 0 && qrow < Q) {
+                    const size_t o = ((size_t)qrow * ntx + (size_t)(n0 / RK_BN)) * k;
+#pragma unroll
+                    for (int i = 0; i < FK; ++i)
+                        if (i < k) { cand_val[o + i] = ki[i] == IDX32_PAD ? NEG_INF : key_score(kv[i]); cand_idx[o + i] = ki[i]; }
+                }
+            }
+            __syncthreads();
+        }
+        return;
+    }
+    // epilogue: C[row = query][col = gallery]; lane: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const i64 col = n0 + wn * 64 + j * 32 + lr;
+        if (col >= G) continue;
+        const float gs = ginv ? ginv[col] : 1.0f;
+#pragma unroll
+        for (int i = 0; i < MT; ++i) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = m0 + wm * MT * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                if (row < Q) S[(i64)row * G + col] = acc[i][j][r] * gs;
+            }
+        }
+    }
+}
+
+// Row norm of an fp32 row: one wave, float4 loads when vec (dim % 4 == 0 and 16-B aligned rows).  The lane-strided
+// summation order is part of the result: every row normalisation of the library (mi355_l2_normalize_rows, the queries
+// of every search, the fp16 gallery conversion) goes through this one function, so they give the same bits.
+__device__ __forceinline__ float row_inv_norm(const float* __restrict__ x, int dim, float eps, int vec, int lane) {
+    float ss = 0.f;
+    if (vec) {
+        const f32x4* x4 = reinterpret_cast<const f32x4*>(x);
+        for (int i = lane; i < dim / 4; i += 64) {
+            f32x4 v = x4[i];
+            ss += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+        }
+    } else {
+        for (int i = lane; i < dim; i += 64) ss += x[i] * x[i];
+    }
+    ss = wave_sum(ss);
+    return 1.0f / fmaxf(sqrtf(ss), eps);
+}
+
+static inline int vec_ok(const void* p, int dim) { return (dim % 4 == 0) && (((uintptr_t)p & 15) == 0); }
+
+// ---- host side of the selection (rank.hip)
+constexpr int SMALL_K = 8;          // k <= SMALL_K: per-thread sorted lists; the fused GEMM epilogue selects up to this k
+constexpr int LARGE_K = 1024;       // largest k of any search
+
+// Scratch of topk_select for Q rows of rowlen candidates.
+size_t topk_ws_bytes(i64 Q, i64 G, int k);
+// Top-k of each row of vals[Q][rowlen] (implicit indices j + idx_offset, explicit int64 idxs, or the fused epilogue's int32
+// local indices idxs32 with IDX32_PAD = missing) into out_val / out_idx [Q][k].
+int topk_select(const float* vals, const i64* idxs, i64 Q, i64 rowlen, i64 in_stride, int k, i64 idx_offset, float* out_val,
+                i64* out_idx, void* ws, size_t ws_bytes, hipStream_t st, const int* idxs32 = nullptr);
+// Whether a (Q, G, k) search selects inside the GEMM epilogue (k <= SMALL_K, Q > 4), and how many queries one GEMM call
+// takes so that the candidate lists / the score slab stay bounded.
+bool fused_select(i64 Q, i64 G, int k);
+i64 query_block(i64 Q, i64 G, int k);
+// Resident workgroups per CU x CUs of the current device for one kernel (sets its dynamic LDS limit; cached per device).
+int kernel_slots(const void* fn, size_t lds, int* cache, int* slots_out);
+// Column tiles of a GEMM's main launch of whole rounds (the rest go to a tail launch of 64-row tiles).
+int whole_round_tiles(int ntx, int ny, int slots);
+
+}  // namespace mi355

@@ -1,0 +1,448 @@
+// Half-precision resident gallery: fp16 rows and the cosine / top-k search over them.  gfx950 only.
+//
+// Numerical contract (include/mi355_retrieval.h):
+//   * stored row = fp16_rne(l2_normalize_rows(x, eps)) - the same fp32 row mi355_l2_normalize_rows writes (one shared norm,
+//     row_inv_norm), rounded once to nearest-even; it is not renormalised after rounding.  Rows are padded with zeros to a
+//     stride of a multiple of 64 elements (128 B), so that every load of the search is a whole 128-byte row segment.
+//   * score = qn . float(row), qn the query normalised as mi355_rank_topk normalises it.  The GEMM (Q > 4) carries qn as two
+//     fp16 planes, hi = fp16(qn) and lo = fp16((qn - hi) * 2^11) (22 significant bits), multiplies each with the stored row
+//     on v_mfma_f32_32x32x16_f16 into its own fp32 accumulator (every fp16 x fp16 product is exact in fp32) and returns
+//     acc_hi + acc_lo * 2^-11.  The GEMV (Q <= 4) uses the fp32 qn directly.  Either way |score - qn . row| stays ~1e-7.
+//   * order, ties, NaN: the selection of mi355_rank_topk (rank_common.h), so the same rule as cosine_topk / torch.topk.
+#include "rank_common.h"
+#include "../../include/mi355_retrieval.h"
+
+namespace mi355 {
+
+typedef _Float16 f16;
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+constexpr int F16_KSTEP = 64;                 // k-step of the GEMM: one 128-byte segment of a stored row
+static inline int f16_ld(int dim) { return (dim + F16_KSTEP - 1) / F16_KSTEP * F16_KSTEP; }
+
+// The fp32 row value x * r, then its rounding to fp16: two roundings, as l2_normalize_rows(x).half() does them.  (With
+// -ffp-contract=fast, hipcc fuses the pair into v_fma_mixlo_f16, ONE rounding of the exact product, which differs in the
+// last bit now and then; `#pragma clang fp contract(off)` does not stop that backend fold.  The empty asm only pins the
+// fp32 product in a register - it emits no instruction.)
+__device__ __forceinline__ f16 scaled_f16(float x, float r) {
+    float p = x * r;
+    asm volatile("" : "+v"(p));
+    return (f16)p;
+}
+
+// =====================================================================================
+// fp32 rows -> normalised fp16 rows, padded to ld elements with zeros.  One wave per row; the norm is row_inv_norm (the
+// one mi355_l2_normalize_rows uses, with the same vec rule), so the stored row is bit for bit l2_normalize_rows(x).half().
+// =====================================================================================
+__global__ __launch_bounds__(256) void k_rows_to_f16(const float* __restrict__ in, f16* __restrict__ out, i64 rows, int dim,
+                                                     int ld, float eps, int normalize, int vec) {
+    const int lane = threadIdx.x & 63;
+    const i64 row = (i64)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float* x = in + row * dim;
+    const float r = normalize ? row_inv_norm(x, dim, eps, vec, lane) : 1.0f;
+    f16* y = out + row * ld;
+    if (vec) {
+        const f32x4* x4 = reinterpret_cast<const f32x4*>(x);
+        for (int i = lane; i < ld / 4; i += 64) {
+            f16x4 h = {(f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f};
+            if (i < dim / 4) {
+                const f32x4 v = x4[i];
+                h = (f16x4){scaled_f16(v.x, r), scaled_f16(v.y, r), scaled_f16(v.z, r), scaled_f16(v.w, r)};
+            }
+            reinterpret_cast<f16x4*>(y)[i] = h;
+        }
+    } else {
+        for (int i = lane; i < ld; i += 64) y[i] = i < dim ? scaled_f16(x[i], r) : (f16)0.f;
+    }
+}
+
+// =====================================================================================
+// Normalised queries -> the two fp16 planes in MFMA-fragment order: Qs[row block of 32][k sub-step of 16][plane hi, lo]
+// [lane][8 f16], lane = row + 32 * (k half), as k_split_queries lays out its bf16 planes.  A GEMM k-step of 64 is then
+// 8 KB per row block, eight 1 KB pieces that LDS-DMA moves as they are.  Rows >= Q and k >= D are zero.
+// =====================================================================================
+constexpr float F16_LO_SCALE = 2048.0f;       // 2^11: the lo plane (|qn - hi| <= 2^-11 |qn|) stays in fp16's normal range
+constexpr float F16_LO_UNSCALE = 1.0f / 2048.0f;
+
+__global__ __launch_bounds__(256) void k_split_queries_f16(const float* __restrict__ Qn, f16* __restrict__ Qs, int Q, int D,
+                                                           int n_sub, int n_frag) {
+    const int f = blockIdx.x * 4 + (threadIdx.x >> 6);   // fragment = (row block, k sub-step)
+    if (f >= n_frag) return;
+    const int lane = threadIdx.x & 63;
+    const int rb = f / n_sub, s = f % n_sub;
+    const int row = rb * 32 + (lane & 31), k0 = s * 16 + (lane >> 5) * 8;
+    f16x8 hi, lo;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const float x = (row < Q && k0 + e < D) ? Qn[(i64)row * D + k0 + e] : 0.f;
+        const f16 h = (f16)x;
+        hi[e] = h;
+        lo[e] = (f16)((x - (float)h) * F16_LO_SCALE);   // x - h is exact in fp32, the scale by 2^11 too
+    }
+    f16x8* o = reinterpret_cast<f16x8*>(Qs + (size_t)f * 2 * 512) + lane;
+    o[0] = hi;
+    o[64] = lo;
+}
+
+// =====================================================================================
+// cosine GEMM over fp16 rows: S / per-tile candidates as k_cos_gemm_split (same block and wave tiling, same launch order,
+// same epilogue, rank_common.h).  Block = 4 waves as 2(M) x 2(N), block tile (64 * MT) queries x 128 gallery rows,
+// k-step 64 (four 32x32x16 sub-steps).
+//   A (query planes): 8 * MT pieces of 1 KB per k-step by LDS-DMA from L2, one k-step ahead (ring of 2).
+//   B (gallery): the tile's 128 rows x 128 B per k-step by LDS-DMA from HBM, two k-steps ahead (ring of 3).  A piece is 8
+//     rows; the 16-byte chunk c of row r lands at position c ^ ((r >> 1) & 7) (applied to the per-lane SOURCE address, the
+//     DMA writes lane-linear): row r sits in half (r & 1) of a 256-byte bank row, so the ds_read_b128 of any 16 distinct
+//     rows of a lane group hit 16 distinct 16-byte slots.  Rows past G re-read row G - 1 (the epilogue drops them).
+// No load in the loop has a register destination: ONE counted vmcnt(4) per k-step (this iteration's four B pieces, issued
+// last, stay in flight) and one LDS-only barrier.  Per wave and k-step: 8 * MT + 8 ds_read_b128 and 16 * MT MFMAs.
+// LDS: 2 x 32 KB (A) + 3 x 16 KB (B) = 112 KB at MT = 2, 2 x 16 + 48 = 80 KB at MT = 1 (two workgroups per CU).
+// =====================================================================================
+template <int MT, int FK>
+__global__ __launch_bounds__(256) void k_cos_gemm_f16(const f16* __restrict__ Qs, const f16* __restrict__ Gal,
+                                                      float* __restrict__ S, int Q, i64 G, int ld, int k,
+                                                      float* __restrict__ cand_val, int* __restrict__ cand_idx, int x0, int ntx,
+                                                      int xtiles, int ny) {
+    constexpr int BM = 64 * MT;
+    constexpr int A_PIECES = (BM / 32) * 8;           // 1 KB pieces per stage: 4 sub-steps x 2 planes per row block
+    constexpr int A_STAGE = A_PIECES * 512;           // f16 elements per stage
+    constexpr int B_STAGE = RK_BN * F16_KSTEP;        // f16 elements per stage (16 KB)
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    f16* As = reinterpret_cast<f16*>(smem);           // [2][BM/32][4][2][512]
+    f16* Bs = As + 2 * A_STAGE;                       // [3][128][64], chunks swizzled
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1, lr = lane & 31;
+    int bx, by;
+    rank_tile_of((int)blockIdx.x, xtiles, ny, bx, by);
+    const i64 n0 = (i64)(bx + x0) * RK_BN;
+    const int m0 = by * BM;
+    const int swave = __builtin_amdgcn_readfirstlane(wave);
+    const int n_steps = ld / F16_KSTEP, n_sub = ld / 16;
+
+    // B: wave w moves pieces 4w .. 4w + 3; lane -> row 8 * piece + lane / 8, LDS position lane % 8
+    const f16* b_src[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int r = (swave * 4 + i) * 8 + (lane >> 3);
+        const int c = (lane & 7) ^ ((r >> 1) & 7);
+        const i64 g = n0 + r < G ? n0 + r : G - 1;
+        b_src[i] = Gal + g * ld + c * 8;
+    }
+    // (k-steps past the end re-read the last one: the data is never used, the count of pieces in flight stays uniform)
+    auto dma_b = [&](int stage, int t) {
+        const int tt = t < n_steps ? t : n_steps - 1;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            glds16(reinterpret_cast<const bf16_t*>(b_src[i] + tt * F16_KSTEP),
+                   reinterpret_cast<bf16_t*>(Bs + stage * B_STAGE + (swave * 4 + i) * 512));
+    };
+    // A: piece p = (row block p / 8, sub-step (p % 8) / 2, plane p % 2) of k-step t sits at
+    // Qs + ((m0/32 + p/8) * n_sub + 4t) * 1024 + (p % 8) * 512; wave w moves pieces w, w + 4, ...
+    const f16* a_src[A_PIECES / 4];
+#pragma unroll
+    for (int i = 0; i < A_PIECES / 4; ++i) {
+        const int p = swave + 4 * i;
+        a_src[i] = Qs + ((size_t)(m0 / 32 + p / 8) * n_sub) * 1024 + (p % 8) * 512 + lane * 8;
+    }
+    auto dma_a = [&](int buf, int t) {
+#pragma unroll
+        for (int i = 0; i < A_PIECES / 4; ++i)
+            glds16(reinterpret_cast<const bf16_t*>(a_src[i] + (size_t)t * 4 * 1024),
+                   reinterpret_cast<bf16_t*>(As + buf * A_STAGE + (swave + 4 * i) * 512));
+    };
+
+    f32x16 acc[MT][2], acc_lo[MT][2];
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) { acc[i][j][e] = 0.f; acc_lo[i][j][e] = 0.f; }
+
+    // B fragment reads: row r = wn * 64 + j * 32 + lr, chunk 2s + (lane >> 5) of sub-step s at its swizzled position
+    int b_off[2][4];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int r = wn * 64 + j * 32 + lr;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) b_off[j][s] = r * F16_KSTEP + (((2 * s + (lane >> 5)) ^ ((r >> 1) & 7)) << 3);
+    }
+    auto compute = [&](int abuf, int bstage) {
+        const f16* a = As + abuf * A_STAGE + (wm * MT) * 8 * 512 + lane * 8;
+        const f16* b = Bs + bstage * B_STAGE;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            f16x8 bf[2], ah[MT], al[MT];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) bf[j] = *reinterpret_cast<const f16x8*>(b + b_off[j][s]);
+#pragma unroll
+            for (int i = 0; i < MT; ++i) {
+                ah[i] = *reinterpret_cast<const f16x8*>(a + (i * 8 + s * 2) * 512);
+                al[i] = *reinterpret_cast<const f16x8*>(a + (i * 8 + s * 2 + 1) * 512);
+            }
+#pragma unroll
+            for (int i = 0; i < MT; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    acc_lo[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bf[j], acc_lo[i][j], 0, 0, 0);
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bf[j], acc[i][j], 0, 0, 0);
+                }
+        }
+    };
+
+    dma_a(0, 0);
+    dma_b(0, 0);
+    dma_b(1, 1);
+    __syncthreads();                   // drains vmcnt: everything has landed
+
+    int bs_cur = 0, bs_far = 2;        // B stage of k-step t / of k-step t + 2
+    for (int t = 0; t < n_steps; ++t) {
+        if (t + 1 < n_steps) dma_a((t & 1) ^ 1, t + 1);   // everybody left this buffer at the previous barrier
+        __builtin_amdgcn_sched_barrier(0);                // (the count below needs the A pieces issued BEFORE the B pieces)
+        dma_b(bs_far, t + 2);
+        __builtin_amdgcn_sched_barrier(0);
+        compute(t & 1, bs_cur);
+        asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); // A(t+1) and B(t+1) have landed; the four B(t+2) pieces stay in flight
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        bs_cur = bs_cur == 2 ? 0 : bs_cur + 1;
+        bs_far = bs_far == 2 ? 0 : bs_far + 1;
+    }
+    __syncthreads();                   // the last look-ahead pieces have landed before the epilogue reuses the LDS
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[i][j][e] = __builtin_fmaf(acc_lo[i][j][e], F16_LO_UNSCALE, acc[i][j][e]);
+    cos_gemm_epilogue<MT, FK>(acc, smem, nullptr, S, Q, G, k, cand_val, cand_idx, x0, ntx, n0, m0);
+}
+
+// =====================================================================================
+// Few queries (Q <= 4, the one-query-at-a-time serving shape): a GEMV bound by streaming the gallery once (2 * ld bytes
+// per row).  One wave per row, 16 bytes per lane per load, up to four loads in flight per lane; the fp32 queries sit in
+// LDS, padded with zeros to ld.
+// =====================================================================================
+template <int NQ>
+__global__ __launch_bounds__(256) void k_cos_gemv_f16(const float* __restrict__ Qn, const f16* __restrict__ Gal,
+                                                      float* __restrict__ S, i64 G, int D, int ld) {
+    extern __shared__ __attribute__((aligned(16))) float qs[];   // [NQ][ld]
+    for (int i = threadIdx.x; i < NQ * ld; i += 256) {
+        const int q = i / ld, e = i - q * ld;
+        qs[i] = e < D ? Qn[(i64)q * D + e] : 0.f;
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int nch = ld / 8;                                      // 16-byte chunks per row
+    const i64 wave_id = (i64)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const i64 nwaves = (i64)gridDim.x * 4;
+    for (i64 g = wave_id; g < G; g += nwaves) {
+        const f16x8* row = reinterpret_cast<const f16x8*>(Gal + g * ld);
+        float acc[NQ];
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) acc[q] = 0.f;
+        for (int c0 = 0; c0 < nch; c0 += 4 * 64) {
+            f16x8 h[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int c = c0 + u * 64 + lane;
+                h[u] = c < nch ? row[c] : (f16x8){};
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int c = c0 + u * 64 + lane;
+                if (c < nch) {
+#pragma unroll
+                    for (int q = 0; q < NQ; ++q) {
+                        const f32x4 u0 = *reinterpret_cast<const f32x4*>(&qs[q * ld + c * 8]);
+                        const f32x4 u1 = *reinterpret_cast<const f32x4*>(&qs[q * ld + c * 8 + 4]);
+                        acc[q] += (float)h[u][0] * u0.x + (float)h[u][1] * u0.y + (float)h[u][2] * u0.z + (float)h[u][3] * u0.w +
+                                  (float)h[u][4] * u1.x + (float)h[u][5] * u1.y + (float)h[u][6] * u1.z + (float)h[u][7] * u1.w;
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const float t = wave_sum(acc[q]);
+            if (lane == 0) S[(i64)q * G + g] = t;
+        }
+    }
+}
+
+// =====================================================================================
+// host drivers
+// =====================================================================================
+constexpr size_t F16_GEMV_LDS = 64 * 1024;
+
+static size_t f16_planes_bytes(i64 Q, int ld) { return (size_t)cdiv(Q, 128) * 4 * (ld / 16) * 2 * 1024; }
+static bool f16_gemv(i64 Q, int ld) { return Q <= 4 && (size_t)Q * ld * sizeof(float) <= F16_GEMV_LDS; }
+
+struct F16Ws {
+    float* qn; f16* qs; float* S; float* cand_val; int* cand_idx; void* topk; size_t topk_bytes; size_t total;
+};
+static F16Ws carve_f16(void* ws, i64 Q, i64 G, int D, int k) {
+    F16Ws r{};
+    const bool fused = fused_select(Q, G, k);
+    const i64 qb = query_block(Q, G, k);
+    const i64 ntiles = cdiv(G, RK_BN);
+    size_t off = 0;
+    char* base = ws ? (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255) : nullptr;
+    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align_up(bytes, 256); return p; };
+    r.qn = (float*)take((size_t)Q * D * sizeof(float));
+    r.qs = (f16*)take(f16_gemv(Q, f16_ld(D)) ? 0 : f16_planes_bytes(qb, f16_ld(D)));
+    if (fused) {
+        const size_t ncand = (size_t)qb * ntiles * k;
+        r.cand_val = (float*)take(ncand * sizeof(float));
+        r.cand_idx = (int*)take(ncand * sizeof(int));
+        r.topk_bytes = topk_ws_bytes(qb, ntiles * k, k);
+    } else {
+        r.S = (float*)take((size_t)qb * G * sizeof(float));
+        r.topk_bytes = topk_ws_bytes(qb, G, k);
+    }
+    r.topk = take(r.topk_bytes);
+    r.total = off + 256;
+    return r;
+}
+
+template <int MT>
+static size_t f16_lds(bool fk) {
+    const size_t stage = (size_t)2 * (64 * MT / 32) * 8 * 1024 + (size_t)3 * RK_BN * F16_KSTEP * 2;   // A ring of 2, B ring of 3
+    const size_t tile = fk ? (size_t)64 * (RK_BN + 4) * sizeof(float) : 0;
+    return stage > tile ? stage : tile;
+}
+template <int MT, int FK>
+static int f16_slots(size_t lds, int* slots_out) {
+    static int slots[MI355_MAX_DEVICES] = {0};
+    return kernel_slots((const void*)k_cos_gemm_f16<MT, FK>, lds, slots, slots_out);
+}
+
+// Whole rounds of 128-query tiles in one launch, the remaining column tiles as 64-query tiles (every score is the same:
+// same column tiles, same k order), as launch_split does.
+template <int MT, int FK>
+static int launch_f16(const f16* qs, const f16* gal, float* S, int Q, i64 G, int ld, int k, float* cand_val, int* cand_idx,
+                      hipStream_t st) {
+    constexpr int BM = 64 * MT;
+    const size_t lds = f16_lds<MT>(FK > 0);
+    int slots = 0;
+    if (int e = f16_slots<MT, FK>(lds, &slots)) return e;
+    const int ntx = cdiv(G, RK_BN), ny = cdiv(Q, BM);
+    const int xm = MT == 2 ? whole_round_tiles(ntx, ny, slots) : ntx;
+    if (xm > 0) {
+        hipLaunchKernelGGL((k_cos_gemm_f16<MT, FK>), dim3((unsigned)xm * (unsigned)ny), dim3(256), lds, st, qs, gal, S, Q, G, ld,
+                           k, cand_val, cand_idx, 0, ntx, xm, ny);
+        MI355_LAUNCH_CHECK();
+    }
+    if (xm < ntx) {
+        const size_t lds1 = f16_lds<1>(FK > 0);
+        int slots1 = 0;
+        if (int e = f16_slots<1, FK>(lds1, &slots1)) return e;
+        hipLaunchKernelGGL((k_cos_gemm_f16<1, FK>), dim3((unsigned)(ntx - xm) * (unsigned)cdiv(Q, 64)), dim3(256), lds1, st, qs,
+                           gal, S, Q, G, ld, k, cand_val, cand_idx, xm, ntx, ntx - xm, (int)cdiv(Q, 64));
+        MI355_LAUNCH_CHECK();
+    }
+    return OK;
+}
+template <int MT>
+static int launch_f16_fk(const f16* qs, const f16* gal, float* S, int Q, i64 G, int ld, int k, float* cand_val, int* cand_idx,
+                         hipStream_t st) {
+    if (!cand_val) return launch_f16<MT, 0>(qs, gal, S, Q, G, ld, 0, nullptr, nullptr, st);
+    if (k <= 1) return launch_f16<MT, 1>(qs, gal, S, Q, G, ld, k, cand_val, cand_idx, st);
+    if (k <= 2) return launch_f16<MT, 2>(qs, gal, S, Q, G, ld, k, cand_val, cand_idx, st);
+    if (k <= 4) return launch_f16<MT, 4>(qs, gal, S, Q, G, ld, k, cand_val, cand_idx, st);
+    return launch_f16<MT, 8>(qs, gal, S, Q, G, ld, k, cand_val, cand_idx, st);
+}
+
+}  // namespace mi355
+
+using namespace mi355;
+
+extern "C" {
+
+size_t mi355_gallery_f16_bytes(int64_t G, int dim) {
+    if (G < 0 || dim < 1) return 0;
+    return (size_t)G * f16_ld(dim) * sizeof(f16);
+}
+
+int mi355_gallery_to_f16(const float* rows, int64_t G, int dim, int rows_are_normalized, float eps, void* out, size_t out_bytes,
+                         void* stream) {
+    MI355_REQUIRE(rows && out, "gallery_to_f16: null pointer");
+    MI355_REQUIRE(G >= 0 && dim >= 1, "gallery_to_f16: bad shape G=%lld dim=%d", (long long)G, dim);
+    MI355_REQUIRE(((uintptr_t)out & 15) == 0, "gallery_to_f16: output buffer must be 16-byte aligned");
+    MI355_REQUIRE(out_bytes >= mi355_gallery_f16_bytes(G, dim), "gallery_to_f16: output buffer %zu < %zu bytes", out_bytes,
+                  mi355_gallery_f16_bytes(G, dim));
+    if (G == 0) return OK;
+    hipLaunchKernelGGL(k_rows_to_f16, dim3((unsigned)cdiv(G, 4)), dim3(256), 0, (hipStream_t)stream, rows, (f16*)out, (i64)G, dim,
+                       f16_ld(dim), eps, rows_are_normalized ? 0 : 1, vec_ok(rows, dim));
+    MI355_LAUNCH_CHECK();
+    return OK;
+}
+
+size_t mi355_rank_f16_workspace_bytes(int64_t Q, int64_t G, int dim, int k) {
+    if (Q < 1 || G < 1 || dim < 1 || k < 1 || k > LARGE_K) return 0;
+    return carve_f16(nullptr, Q, G, dim, k).total;
+}
+
+int mi355_rank_topk_f16(const float* queries, int64_t Q, const void* gallery_f16, int64_t G, int dim, int k, float eps,
+                        int64_t idx_offset, float* out_val, int64_t* out_idx, void* workspace, size_t workspace_bytes,
+                        void* stream) {
+    MI355_REQUIRE(queries && gallery_f16 && out_val && out_idx, "rank_topk_f16: null pointer");
+    MI355_REQUIRE(Q >= 0 && G >= 1 && dim >= 1, "rank_topk_f16: bad shape Q=%lld G=%lld dim=%d", (long long)Q, (long long)G, dim);
+    MI355_REQUIRE(k >= 1 && k <= LARGE_K && k <= G, "rank_topk_f16: k=%d outside [1, %lld]", k,
+                  (long long)(G < LARGE_K ? G : LARGE_K));
+    MI355_REQUIRE(((uintptr_t)gallery_f16 & 15) == 0, "rank_topk_f16: gallery buffer must be 16-byte aligned");
+    MI355_REQUIRE(Q <= INT_MAX && G <= ((int64_t)1 << 40), "rank_topk_f16: shape too large Q=%lld G=%lld", (long long)Q,
+                  (long long)G);
+    if (Q == 0) return OK;
+    const F16Ws w = carve_f16(workspace, Q, G, dim, k);
+    MI355_REQUIRE(workspace && workspace_bytes >= w.total, "rank_topk_f16: workspace %zu < %zu bytes", workspace_bytes, w.total);
+    hipStream_t st = (hipStream_t)stream;
+    const f16* gal = (const f16*)gallery_f16;
+    const int ld = f16_ld(dim);
+    {
+        RoctxRange range("rank/normalize");
+        if (int e = mi355_l2_normalize_rows(queries, w.qn, Q, dim, eps, stream)) return e;   // as mi355_rank_topk normalises
+    }
+    if (f16_gemv(Q, ld)) {
+        {
+            RoctxRange range("rank/cosine gemv (fp16 gallery)");
+            const size_t lds = (size_t)Q * ld * sizeof(float);
+            const unsigned blocks = (unsigned)(cdiv(G, 4) < 4096 ? cdiv(G, 4) : 4096);
+#define GEMV_F16(NQ) hipLaunchKernelGGL((k_cos_gemv_f16<NQ>), dim3(blocks), dim3(256), lds, st, w.qn, gal, w.S, (i64)G, dim, ld)
+            if (Q == 1) GEMV_F16(1); else if (Q == 2) GEMV_F16(2); else if (Q == 3) GEMV_F16(3); else GEMV_F16(4);
+#undef GEMV_F16
+            MI355_LAUNCH_CHECK();
+        }
+        RoctxRange range("rank/top-k");
+        return topk_select(w.S, nullptr, Q, G, G, k, idx_offset, out_val, (i64*)out_idx, w.topk, w.topk_bytes, st);
+    }
+    const i64 qb = query_block(Q, G, k);
+    const bool fused = fused_select(Q, G, k);
+    const i64 ntiles = cdiv(G, RK_BN);
+    const int n_sub = ld / 16;
+    for (i64 q0 = 0; q0 < Q; q0 += qb) {
+        const i64 qn = (Q - q0 < qb) ? Q - q0 : qb;
+        {
+            RoctxRange range(fused ? "rank/cosine gemm (fp16 gallery) + per-tile top-k" : "rank/cosine gemm (fp16 gallery)");
+            const int n_frag = cdiv(qn, 128) * 4 * n_sub;
+            hipLaunchKernelGGL(k_split_queries_f16, dim3((unsigned)cdiv(n_frag, 4)), dim3(256), 0, st, w.qn + q0 * dim, w.qs,
+                               (int)qn, dim, n_sub, n_frag);
+            MI355_LAUNCH_CHECK();
+            const int e = qn > 64 ? launch_f16_fk<2>(w.qs, gal, w.S, (int)qn, G, ld, k, w.cand_val, w.cand_idx, st)
+                                  : launch_f16_fk<1>(w.qs, gal, w.S, (int)qn, G, ld, k, w.cand_val, w.cand_idx, st);
+            if (e) return e;
+        }
+        RoctxRange range(fused ? "rank/merge candidates" : "rank/top-k");
+        const int e = fused ? topk_select(w.cand_val, nullptr, qn, ntiles * k, ntiles * k, k, idx_offset, out_val + q0 * k,
+                                          (i64*)out_idx + q0 * k, w.topk, w.topk_bytes, st, w.cand_idx)
+                            : topk_select(w.S, nullptr, qn, G, G, k, idx_offset, out_val + q0 * k, (i64*)out_idx + q0 * k, w.topk,
+                                          w.topk_bytes, st);
+        if (e) return e;
+    }
+    return OK;
+}
+
+}  // extern "C"

@@ -394,21 +394,59 @@ def cos_sim_score_booster(score: torch.Tensor, eps: float, alpha: float, mode: s
     return _score_boost(score, eps, alpha, 0.0, 1 if mode == "for_pos" else 2)
 
 
-class Gallery:
-    """Resident gallery: rows are L2-normalised once when added and stay in HBM as fp32 (SURVEY §8e:
-    the gallery is *born* on the GPU that embedded it).  ``search`` is then one fused call per query
-    batch instead of the reference's per-query cosine + topk pair."""
+def _gallery_f16_bytes(rows: int, dim: int) -> int:
+    return int(lib().mi355_gallery_f16_bytes(rows, dim))
 
-    def __init__(self, dim: int, device, capacity: int = 0, eps: float = _EPS):
-        self.dim, self.device, self.eps = int(dim), torch.device(device), eps
+
+def _f16_stride(dim: int) -> int:
+    """Row stride (elements) of an fp16 gallery buffer: ``dim`` rounded up to a multiple of 64 (128 B), padded with zeros."""
+    return (int(dim) + 63) // 64 * 64
+
+
+def _cosine_topk_f16(queries: torch.Tensor, gallery_f16: torch.Tensor, rows: int, dim: int, k: int, eps: float = _EPS,
+                    idx_offset: int = 0):
+    """Top-k of ``queries`` against the first ``rows`` rows of an fp16 gallery buffer (``mi355_gallery_to_f16`` layout:
+    ``(capacity, _f16_stride(dim))`` fp16, normalised rows, zero padding).  score = qn . float(row) with fp32
+    accumulation; order, ties and NaN as ``cosine_topk``."""
+    q = _f32c(queries, "queries")
+    Q = q.shape[0]
+    vals = torch.empty((Q, k), dtype=torch.float32, device=q.device)
+    idx = torch.empty((Q, k), dtype=torch.int64, device=q.device)
+    if Q == 0:
+        return vals, idx
+    ws = _ws.get(q.device, lib().mi355_rank_f16_workspace_bytes(Q, rows, dim, k))
+    with torch.cuda.device(q.device):
+        check(lib().mi355_rank_topk_f16(q.data_ptr(), Q, gallery_f16.data_ptr(), rows, dim, k, eps, int(idx_offset),
+                                        vals.data_ptr(), idx.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr(q.device)))
+    return vals, idx
+
+
+class Gallery:
+    """Resident gallery: rows are L2-normalised once when added and stay in HBM (the gallery is *born* on the
+    GPU that embedded it).  ``search`` is then one fused call per query batch instead of the reference's per-query cosine +
+    topk pair.
+
+    ``dtype=torch.float32`` (default) keeps the normalised rows as fp32.  ``dtype=torch.float16`` keeps
+    ``fp16(l2_normalize_rows(x))`` - bit for bit ``l2_normalize_rows(x).half()``, not renormalised after rounding - in a
+    buffer whose rows are padded with zeros to a multiple of 64 elements: half the bytes of fp32 rows.  Its search scores
+    ``qn . float(row)`` (``qn`` normalised as in ``cosine_topk``) with fp32 accumulation, |error| ~1e-7, and orders results as
+    ``cosine_topk`` does (descending, ties to the lower index, NaN first)."""
+
+    def __init__(self, dim: int, device, capacity: int = 0, eps: float = _EPS, dtype: torch.dtype = torch.float32):
+        if dtype not in (torch.float32, torch.float16):
+            raise MI355Error(f"Gallery dtype must be torch.float32 or torch.float16, got {dtype}")
+        self.dim, self.device, self.eps, self.dtype = int(dim), torch.device(device), eps, dtype
+        if dtype == torch.float16 and self.dim < 1:
+            raise MI355Error(f"an fp16 Gallery needs dim >= 1, got {dim}")
         self.rows = 0
-        self._buf = torch.empty((max(capacity, 0), self.dim), dtype=torch.float32, device=self.device)
+        self._ld = _f16_stride(self.dim) if dtype == torch.float16 else self.dim
+        self._buf = torch.empty((max(capacity, 0), self._ld), dtype=dtype, device=self.device)
         self.labels = None
 
     def _reserve(self, n):
         if n > self._buf.shape[0]:
             cap = max(n, int(self._buf.shape[0] * 1.5) + 1024)
-            nb = torch.empty((cap, self.dim), dtype=torch.float32, device=self.device)
+            nb = torch.empty((cap, self._ld), dtype=self.dtype, device=self.device)
             nb[: self.rows].copy_(self._buf[: self.rows])
             self._buf = nb
 
@@ -418,7 +456,12 @@ class Gallery:
             raise MI355Error(f"gallery rows must be (n,{self.dim}), got {tuple(e.shape)}")
         n = e.shape[0]
         self._reserve(self.rows + n)
-        if n:
+        if n and self.dtype == torch.float16:
+            out = self._buf[self.rows: self.rows + n]
+            with torch.cuda.device(e.device):
+                check(lib().mi355_gallery_to_f16(e.data_ptr(), n, self.dim, 0, self.eps, out.data_ptr(),
+                                                 _gallery_f16_bytes(n, self.dim), stream_ptr(e.device)))
+        elif n:
             l2_normalize_rows(e, self.eps, out=self._buf[self.rows: self.rows + n])
         if labels is not None:
             lab = labels.to(self.device, torch.int64)
@@ -428,19 +471,36 @@ class Gallery:
 
     @property
     def data(self) -> torch.Tensor:
+        """The (rows, dim) normalised rows (a view; for fp16 without the row padding)."""
+        if self.dtype == torch.float16:
+            return self._buf[: self.rows, : self.dim]
         return self._buf[: self.rows]
+
+    @property
+    def nbytes(self) -> int:
+        """Resident footprint in bytes: the row buffer at its current capacity, plus the bf16 planes of ``prepare()``."""
+        p = getattr(self, "_prepared", None)
+        return self._buf.numel() * self._buf.element_size() + (p.planes.numel() if p is not None else 0)
 
     def __len__(self):
         return self.rows
 
     def prepare(self):
         """Split the resident rows once into the GEMM's bf16 planes (PreparedGallery, +6 B per element): searches with k <= 8
-        and more than 4 queries then run without touching the fp32 rows.  Call again after ``add``."""
+        and more than 4 queries then run without touching the fp32 rows.  Call again after ``add``.  fp32 galleries only."""
+        if self.dtype != torch.float32:
+            raise MI355Error("prepare() makes bf16 planes of fp32 rows; an fp16 gallery is searched as it is")
         self._prepared = PreparedGallery(self.data) if self.rows else None
         self._prepared_rows = self.rows
         return self
 
     def search(self, queries: torch.Tensor, k: int, idx_offset: int = 0):
+        if self.dtype == torch.float16:
+            q = _f32c(queries, "queries")
+            _check_qg(q, self.data)
+            if k > self.rows or k < 1:
+                raise MI355Error(f"selected index k out of range: k={k}, gallery rows={self.rows}")
+            return _cosine_topk_f16(q, self._buf, self.rows, self.dim, k, self.eps, idx_offset)
         p = getattr(self, "_prepared", None)
         if p is not None and self._prepared_rows == self.rows and PreparedGallery.supports(queries.shape[0], k):
             return p.search(queries, k, self.eps, idx_offset)

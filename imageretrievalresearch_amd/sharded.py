@@ -41,6 +41,11 @@ class _HipOps:
         return _rank.PreparedGallery(gallery_normalized) if gallery_normalized.shape[0] else None
 
     @staticmethod
+    def gallery_f16(local_rows):
+        return _rank.Gallery(local_rows.shape[1], local_rows.device, capacity=local_rows.shape[0],
+                             dtype=torch.float16).add(local_rows)
+
+    @staticmethod
     def pack(vals, idx, Q, k, device):
         return _rank.pack_candidates(vals, idx, Q, k, device)
 
@@ -55,7 +60,7 @@ class _HipOps:
 
 class ShardedGallery:
     def __init__(self, local_rows: torch.Tensor, group=None, ops=None, labels: torch.Tensor | None = None,
-                 prepared: bool = False):
+                 prepared: bool = False, dtype: torch.dtype = torch.float32):
         self.ops = ops or _HipOps
         self.group = group
         dist = torch.distributed
@@ -65,7 +70,16 @@ class ShardedGallery:
             raise MI355Error(f"local gallery shard must be (rows, dim), got {tuple(local_rows.shape)}")
         self.dim = local_rows.shape[1]
         self.device = local_rows.device
-        self.local = self.ops.normalize(local_rows.float().contiguous()) if local_rows.shape[0] else local_rows.float()
+        if dtype not in (torch.float32, torch.float16):
+            raise MI355Error(f"ShardedGallery dtype must be torch.float32 or torch.float16, got {dtype}")
+        if dtype == torch.float16 and prepared:
+            raise MI355Error("prepared=True makes bf16 planes of fp32 rows; it does not combine with dtype=torch.float16")
+        # dtype=torch.float16: the shard is kept as an fp16 Gallery (half the bytes) and searched with its kernel
+        self.gallery_f16 = self.ops.gallery_f16(local_rows.float().contiguous()) if dtype == torch.float16 else None
+        if self.gallery_f16 is not None:
+            self.local = self.gallery_f16.data
+        else:
+            self.local = self.ops.normalize(local_rows.float().contiguous()) if local_rows.shape[0] else local_rows.float()
         self.labels = labels
         # prepared=True: the shard is also kept as the cosine GEMM's bf16 planes (+6 B per element; same results bit for bit)
         self.prepared = self.ops.prepare(self.local) if (prepared and hasattr(self.ops, "prepare")) else None
@@ -90,6 +104,8 @@ class ShardedGallery:
         return self.offsets[self.rank]
 
     def _local_topk(self, queries, k):
+        if self.gallery_f16 is not None:
+            return self.gallery_f16.search(queries, k)
         if self.prepared is not None:
             return self.ops.local_topk(queries, self.local, k, 0, prepared=self.prepared)
         return self.ops.local_topk(queries, self.local, k, 0)

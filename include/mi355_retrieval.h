@@ -80,6 +80,25 @@ int mi355_rank_topk_prepared(const float* queries, int64_t Q, const void* galler
                              int64_t idx_offset, float* out_val, int64_t* out_idx, void* workspace, size_t workspace_bytes,
                              void* stream);
 
+/* Half-precision resident gallery (fp16 rows: half the bytes of fp32 rows, a third of the bf16 planes).
+ * Stored row: fp16_rne(l2_normalize_rows(x, eps)), bit for bit the fp32 row mi355_l2_normalize_rows writes for the same x,
+ * rounded once to nearest-even (not renormalised after rounding); rows_are_normalized != 0 rounds x as it is.  Row r starts
+ * at element r * ld, ld = dim rounded up to a multiple of 64 (128 B); elements dim .. ld-1 are zero.  The buffer is
+ * appendable: converting n rows to out + r * ld * 2 bytes writes rows r .. r+n-1.  out must be 16-byte aligned.
+ * mi355_gallery_f16_bytes(G, dim) = G * ld * 2. */
+size_t mi355_gallery_f16_bytes(int64_t G, int dim);
+int mi355_gallery_to_f16(const float* rows, int64_t G, int dim, int rows_are_normalized, float eps, void* out, size_t out_bytes,
+                         void* stream);
+/* Cosine + top-k against an fp16 gallery (16-byte aligned, layout above).  score = qn . float(row), qn the query normalised as
+ * mi355_rank_topk normalises it, fp32 accumulation; the query is carried as two fp16 planes hi = fp16(qn),
+ * lo = fp16((qn - hi) * 2^11) with one accumulator each (Q > 4), or as fp32 (Q <= 4): |score - qn . row| ~1e-7, far inside
+ * 1e-5.  Order, ties and NaN as mi355_rank_topk; any k in [1, min(1024, G)], any dim >= 1, Q >= 0 (Q = 0 does nothing).
+ * workspace: mi355_rank_f16_workspace_bytes(Q, G, dim, k). */
+size_t mi355_rank_f16_workspace_bytes(int64_t Q, int64_t G, int dim, int k);
+int mi355_rank_topk_f16(const float* queries, int64_t Q, const void* gallery_f16, int64_t G, int dim, int k, float eps,
+                        int64_t idx_offset, float* out_val, int64_t* out_idx, void* workspace, size_t workspace_bytes,
+                        void* stream);
+
 int mi355_cosine_scores(const float* queries, int64_t Q, const float* gallery, int64_t G, int dim,
                         int gallery_is_normalized, float eps, float* out, void* workspace,
                         size_t workspace_bytes, void* stream);
