@@ -16,6 +16,18 @@ c_f32p = C.POINTER(C.c_float)
 c_i64p = C.POINTER(C.c_int64)
 vp = C.c_void_p
 
+
+class GemmExArgs(C.Structure):
+    """mi355_gemm_ex_args (include/mi355_retrieval.h), the operand block of the developer entry mi355_gemm_bf16_ex."""
+    _fields_ = [("A", vp), ("lda", C.c_int), ("W", vp), ("ldw", C.c_int), ("bias", vp),
+                ("res", vp), ("ldr", C.c_int), ("res_n", C.c_int),
+                ("gate", vp), ("gate_ld", C.c_int), ("rows_per_img", C.c_int), ("a_relu6", C.c_int),
+                ("out", vp), ("ldo", C.c_int), ("out_f32", C.c_int),
+                ("M", C.c_int), ("N", C.c_int), ("K", C.c_int), ("act", C.c_int),
+                ("M_sel", C.c_int64), ("splitk_ws", vp), ("splitk_ws_bytes", C.c_size_t),
+                ("ln_stats", vp), ("ln_colsum", vp)]
+
+
 # name -> (restype, argtypes); must list every symbol include/mi355_retrieval.h declares
 # (tests/test_abi.py cross-checks this table against the header).
 PROTOTYPES = {
@@ -75,6 +87,8 @@ PROTOTYPES = {
     "mi355_model_block_stamps": (C.c_int, [vp, C.POINTER(C.c_double), C.c_int]),
     "mi355_pool_linear": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp]),
     "mi355_gemm_bf16": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "mi355_gemm_bf16_ex": (C.c_int, [vp, C.POINTER(C.c_int), vp]),
+    "mi355_window_attention": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "mi355_square_pad_normalize": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, vp]),
     "mi355_conv_input_silu": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     "mi355_resize_bilinear_u8": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp]),

@@ -9,6 +9,7 @@
 // Block = 4 waves, tile 128 (pixels) x BN = 16*NT (channels), BK = 32, double-buffered LDS with
 // register-staged prefetch (issue tile t+1 loads, compute tile t, write tile t+1, one barrier).
 #include "ops.h"
+#include "../../include/mi355_retrieval.h"
 
 #include <stdlib.h>
 
@@ -870,13 +871,13 @@ static int launch_proj_cfg(const GemmArgs& a, hipStream_t st) {
 }
 
 // -1 = shape not covered
-static int try_launch_proj(const GemmArgs& a, hipStream_t st) {
+static int try_launch_proj(const GemmArgs& a, hipStream_t st, int* nt_out) {
     // measured (EfficientNet-B3a B=256): 112x112 / 56x56 projections 0.111 -> 0.087, 0.135 -> 0.108, 0.082 -> 0.058, 0.105 -> 0.096 ms;
     // the 28x28 ones (M = 200k rows, K = 192 / 288: one workgroup per CU) lose 0.030 -> 0.039, 0.044 -> 0.057: large M only
     if (a.out_f32 || a.M < (1 << 19) || a.N % 8 || a.ldo % 8 || a.N > 64 || a.K > 288 || a.lda != a.K) return -1;
     if (a.gate && (a.rows_per_img % 16 != 0 || a.gate_ld % 4 != 0)) return -1;
     const int kst = (a.K + 31) / 32, nt = (a.N + 15) / 16;
-#define PROJ_CASE(NTV, KSTV) if (nt == NTV && kst == KSTV) return launch_proj_cfg<NTV, KSTV>(a, st)
+#define PROJ_CASE(NTV, KSTV) if (nt == NTV && kst == KSTV) { *nt_out = NTV; return launch_proj_cfg<NTV, KSTV>(a, st); }
     PROJ_CASE(2, 1); PROJ_CASE(2, 2); PROJ_CASE(2, 5); PROJ_CASE(2, 6); PROJ_CASE(3, 6); PROJ_CASE(3, 9); PROJ_CASE(2, 9);
     PROJ_CASE(4, 8); PROJ_CASE(3, 5);        // rexnet_150: 246->58 @56x56 (+ residual), 144->41 @56x56
 #undef PROJ_CASE
@@ -888,10 +889,11 @@ static int try_launch_proj(const GemmArgs& a, hipStream_t st) {
 // K is ONE k-step: 24->144 @112x112 0.375 -> 0.284 ms, 32->192 @56x56 0.129 -> 0.107 ms (once the bias moved from 48
 // registers per lane to LDS; RexNet's 32->192 @112x112: 0.52 -> 0.40 ms).  The tiled kernel wins on 48->288 (two k-steps:
 // 0.052 vs 0.078 ms) and on every gated projection (re-measured after the epilogue fixes: 0.10 vs 0.12 ms on 192->32).
-static int try_launch_stream(const GemmArgs& a, hipStream_t st) {
+static int try_launch_stream(const GemmArgs& a, hipStream_t st, int* nt_out) {
     if (a.out_f32 || a.M < 4096 || a.N % 8 || a.ldo % 8 || a.gate || a.a_relu6) return -1;
     const int kst = (a.K + 31) / 32;
     const int nt = (a.N + 15) / 16;
+    *nt_out = nt;
     if (kst == 1 && nt == 9) return launch_stream_cfg<9, 1>(a, st);
     if (kst == 1 && nt == 12) return launch_stream_cfg<12, 1>(a, st);
     return -1;
@@ -1174,7 +1176,11 @@ int launch_head_gap(const bf16_t* A, int lda, const bf16_t* W, int ldw, const fl
     return OK;
 }
 
-int launch_gemm_bf16(const GemmArgs& a, hipStream_t st) {
+// Which branch ran goes to *path (MI355_GEMM_PATH_* | NT << 8, include/mi355_retrieval.h) when path is not null: the op-level tests
+// assert it, so that no case silently falls through to another kernel.
+int launch_gemm_bf16(const GemmArgs& a, hipStream_t st, int* path) {
+    auto ran = [&](int p, int e) { if (path && e == OK) *path = p; return e; };
+    if (path) *path = 0;
     MI355_REQUIRE(a.M >= 1 && a.N >= 1 && a.K >= 1, "gemm: bad shape M=%d N=%d K=%d", a.M, a.N, a.K);
     MI355_REQUIRE(a.K % 8 == 0 && a.lda % 8 == 0 && a.ldw % 32 == 0, "gemm: K=%d lda=%d ldw=%d alignment", a.K, a.lda,
                   a.ldw);
@@ -1187,13 +1193,13 @@ int launch_gemm_bf16(const GemmArgs& a, hipStream_t st) {
         //  microbatch / lane chunk of a big batch must give the same bits as the unchunked forward)
         const int nch = gemm_splitk_chunks(a.M_sel > 0 ? a.M_sel : a.M, a.rows_per_img > 0 ? a.rows_per_img : a.M, a.N, a.K);
         if (nch >= 2 && gemm_splitk_bytes(a.M, a.N, a.K) <= a.splitk_ws_bytes && (!a.gate || a.gate_ld % 4 == 0))
-            return launch_splitk(a, nch, st);
+            return ran(MI355_GEMM_PATH_SPLITK, launch_splitk(a, nch, st));
     }
     // Opt-in (MI355_GEMM_WIDE=1): the persistent 256-wide tile kernel (gemm_wide.hip), bit-identical to k_gemm_big on the same shape.
     // Off by default: on Swin's linears it reaches 0.7 - 1.0x of k_gemm_big (profiles/r03_gemm_wide_ab.txt) - both are bound by the
     // ~27 B/clk a CU takes in through LDS-DMA / stores (tools/dma_probe.hip), and the lock-step 8-wave tile exposes its epilogue.
     const int use_wide = getenv("MI355_GEMM_WIDE") ? atoi(getenv("MI355_GEMM_WIDE")) : 0;   // (read per call: tools / tests A/B it in one process)
-    if (use_wide && gemm_wide_supported(a)) return launch_gemm_wide(a, st);
+    if (use_wide && gemm_wide_supported(a)) return ran(MI355_GEMM_PATH_WIDE, launch_gemm_wide(a, st));
     // Measured on MI355X (profiles/r01_effnet_per_op_*.txt): the 64-row / BK=64 variants lose to 128 x BN x 32
     // on every EfficientNet layer (each wave re-reads the whole W tile from LDS, so halving the rows per wave
     // makes the block LDS-bound); they stay instantiated for tiny-M problems (classifier, M = batch).
@@ -1210,7 +1216,8 @@ int launch_gemm_bf16(const GemmArgs& a, hipStream_t st) {
     if (a.zeros && a.K >= short_min_k && a.K < 128 && a.N >= 2 * a.K && a.N >= 96 && a.M >= 32768 && ((uintptr_t)a.A % 16 == 0) &&
         a.lda % 8 == 0 && !a.gate && !a.a_relu6 && !a.ln_stats) {
         const bool ktail32 = (a.K % 32 != 0) || (a.ldw % 32 != 0);
-        return ktail32 ? launch_big<false, true, 32>(a, st) : launch_big<false, false, 32>(a, st);
+        return ktail32 ? ran(MI355_GEMM_PATH_BIG32_KTAIL, launch_big<false, true, 32>(a, st))
+                       : ran(MI355_GEMM_PATH_BIG32, launch_big<false, false, 32>(a, st));
     }
     if (a.zeros && a.K >= 128 && a.N >= 64 && a.M >= 1024 && ((uintptr_t)a.A % 16 == 0) && a.lda % 8 == 0 &&
         (!a.gate || a.gate_ld >= a.K)) {
@@ -1219,32 +1226,38 @@ int launch_gemm_bf16(const GemmArgs& a, hipStream_t st) {
         //  N = 77..96 and 167..280 win: rexnet_200 GEMM time 3.96 -> 3.79 ms, efficientnet_b3a 2.35 -> 2.31 ms)
         const bool fits = a.N <= BG_BN ? a.N >= 72 : (long)a.N * 16 >= (long)cdiv(a.N, BG_BN) * BG_BN * 10;
         const bool ktail = (a.K % 64 != 0) || (a.ldw % 64 != 0);
-        if ((a.gate || a.a_relu6) && fits) return ktail ? launch_big<true, true>(a, st) : launch_big<true, false>(a, st);
+        if ((a.gate || a.a_relu6) && fits)
+            return ktail ? ran(MI355_GEMM_PATH_BIG_GATED_KTAIL, launch_big<true, true>(a, st))
+                         : ran(MI355_GEMM_PATH_BIG_GATED, launch_big<true, false>(a, st));
         if (!a.gate && !a.a_relu6 && a.N >= 96) {
             // short K, outputs at least as wide as the inputs: four small-ring workgroups per CU (see k_gemm_big)
             static const int short_k = getenv("MI355_GEMM_SHORT_K") ? atoi(getenv("MI355_GEMM_SHORT_K")) : 128;
-            if (!ktail && a.K <= short_k && a.N >= a.K && a.M >= 32768) return launch_big<false, false, 32>(a, st);
-            return ktail ? launch_big<false, true>(a, st) : launch_big<false, false>(a, st);
+            if (!ktail && a.K <= short_k && a.N >= a.K && a.M >= 32768) return ran(MI355_GEMM_PATH_BIG32, launch_big<false, false, 32>(a, st));
+            return ktail ? ran(MI355_GEMM_PATH_BIG_KTAIL, launch_big<false, true>(a, st)) : ran(MI355_GEMM_PATH_BIG, launch_big<false, false>(a, st));
         }
     }
     // small-K layers are pure streaming (one or two K tiles): narrower tiles keep 4+ waves per SIMD resident
     static const int use_stream = getenv("MI355_GEMM_STREAM") ? atoi(getenv("MI355_GEMM_STREAM")) : 1;
     if (use_stream) {
-        const int e = try_launch_stream(a, st);
-        if (e >= 0) return e;
+        int nt = 0;
+        const int e = try_launch_stream(a, st, &nt);
+        if (e >= 0) return ran(MI355_GEMM_PATH_STREAM | nt << 8, e);
     }
     static const int use_proj = getenv("MI355_GEMM_PROJ") ? atoi(getenv("MI355_GEMM_PROJ")) : 1;
     if (use_proj) {
-        const int e = try_launch_proj(a, st);
-        if (e >= 0) return e;
+        int nt = 0;
+        const int e = try_launch_proj(a, st, &nt);
+        if (e >= 0) return ran(MI355_GEMM_PATH_PROJ | nt << 8, e);
     }
     // (measured, tools/gemm_sweep.py: N=192,K=32 runs 172 us as one 192-wide tile, 133 us as three 64-wide tiles;
     //  N=144,K=24 is best as one 144-wide tile)
     const int small_cap = a.N % 64 == 0 ? 4 : 9;
     const int nt = pick_nt(a.N, a.K <= 64 ? small_cap : 12);
-    if (a.M <= 64) return a.K >= 64 ? launch_nt<1, 64>(a, nt, st) : launch_nt<1, 32>(a, nt, st);
+    if (a.M <= 64)
+        return a.K >= 64 ? ran(MI355_GEMM_PATH_TILE_M64_BK64 | nt << 8, launch_nt<1, 64>(a, nt, st))
+                         : ran(MI355_GEMM_PATH_TILE_M64_BK32 | nt << 8, launch_nt<1, 32>(a, nt, st));
     // (64-row tiles for the late layers with few 128-row tiles were measured: no change, so they are not used)
-    return launch_nt<2, 32>(a, nt, st);
+    return ran(MI355_GEMM_PATH_TILE | nt << 8, launch_nt<2, 32>(a, nt, st));
 }
 
 }  // namespace mi355

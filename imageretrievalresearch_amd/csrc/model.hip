@@ -1093,13 +1093,9 @@ int mi355_model_block_stamps(mi355_model_t m, double* out, int max_ops) {
     return n;
 }
 
-int mi355_gemm_bf16(const void* A, const void* W, const float* bias, void* out, int M, int N, int K, int ldw, int act,
-                    void* stream) {
-    MI355_REQUIRE(A && W && bias && out, "gemm_bf16: null pointer");
-    GemmArgs a{};
-    a.A = (const bf16_t*)A; a.lda = K; a.W = (const bf16_t*)W; a.ldw = ldw; a.bias = bias;
-    a.out = out; a.ldo = N; a.out_f32 = 0; a.M = M; a.N = N; a.K = K; a.act = act; a.rows_per_img = 1; a.res_n = N;
-    static void* zero_page[MI355_MAX_DEVICES] = {nullptr};   // a 256-byte zero page per device for the DMA kernel's out-of-range chunks
+// a 256-byte zero page per device: the source of the DMA kernels' out-of-range chunks (GemmArgs::zeros)
+static int gemm_zero_page(const bf16_t** zeros) {
+    static void* zero_page[MI355_MAX_DEVICES] = {nullptr};
     int dev = 0;
     MI355_CHECK_HIP(hipGetDevice(&dev));
     MI355_REQUIRE(dev >= 0 && dev < MI355_MAX_DEVICES, "gemm_bf16: device ordinal %d out of range", dev);
@@ -1107,8 +1103,56 @@ int mi355_gemm_bf16(const void* A, const void* W, const float* bias, void* out, 
         MI355_CHECK_HIP(hipMalloc(&zero_page[dev], 256));
         MI355_CHECK_HIP(hipMemset(zero_page[dev], 0, 256));
     }
-    a.zeros = (const bf16_t*)zero_page[dev];
+    *zeros = (const bf16_t*)zero_page[dev];
+    return OK;
+}
+
+int mi355_gemm_bf16(const void* A, const void* W, const float* bias, void* out, int M, int N, int K, int ldw, int act,
+                    void* stream) {
+    MI355_REQUIRE(A && W && bias && out, "gemm_bf16: null pointer");
+    GemmArgs a{};
+    a.A = (const bf16_t*)A; a.lda = K; a.W = (const bf16_t*)W; a.ldw = ldw; a.bias = bias;
+    a.out = out; a.ldo = N; a.out_f32 = 0; a.M = M; a.N = N; a.K = K; a.act = act; a.rows_per_img = 1; a.res_n = N;
+    if (int e = gemm_zero_page(&a.zeros)) return e;
     return launch_gemm_bf16(a, (hipStream_t)stream);
+}
+
+int mi355_gemm_bf16_ex(const mi355_gemm_ex_args* x, int* path, void* stream) {
+    if (path) *path = 0;
+    MI355_REQUIRE(x, "gemm_bf16_ex: null argument block");
+    MI355_REQUIRE(x->A && x->W && x->bias && x->out, "gemm_bf16_ex: null pointer");
+    MI355_REQUIRE(x->M >= 1 && x->N >= 1 && x->K >= 1, "gemm_bf16_ex: bad shape M=%d N=%d K=%d", x->M, x->N, x->K);
+    MI355_REQUIRE(x->K % 8 == 0 && x->lda >= x->K && x->lda % 8 == 0, "gemm_bf16_ex: K=%d lda=%d: K and lda multiples of 8, lda >= K",
+                  x->K, x->lda);
+    MI355_REQUIRE(x->ldw >= x->K && x->ldw % 32 == 0, "gemm_bf16_ex: ldw=%d must be a multiple of 32 and >= K=%d", x->ldw, x->K);
+    MI355_REQUIRE(x->ldo >= x->N, "gemm_bf16_ex: ldo=%d < N=%d", x->ldo, x->N);
+    MI355_REQUIRE(x->out_f32 || (x->N % 8 == 0 && x->ldo % 8 == 0), "gemm_bf16_ex: bf16 output needs N, ldo multiples of 8 (N=%d ldo=%d)",
+                  x->N, x->ldo);
+    MI355_REQUIRE(x->act >= ACT_NONE && x->act <= ACT_SIGMOID, "gemm_bf16_ex: unknown activation %d", x->act);
+    MI355_REQUIRE(!x->res || (x->res_n >= 1 && x->res_n <= x->N && x->ldr >= x->res_n && x->ldr % 4 == 0),
+                  "gemm_bf16_ex: residual needs 1 <= res_n <= N and ldr >= res_n, a multiple of 4 (res_n=%d ldr=%d)", x->res_n, x->ldr);
+    MI355_REQUIRE(!x->gate || (x->gate_ld >= x->K && x->gate_ld % 4 == 0 && x->rows_per_img >= 1),
+                  "gemm_bf16_ex: gate needs gate_ld >= K, a multiple of 4, and rows_per_img >= 1 (gate_ld=%d rows_per_img=%d)",
+                  x->gate_ld, x->rows_per_img);
+    MI355_REQUIRE(x->rows_per_img >= 0, "gemm_bf16_ex: bad rows_per_img %d", x->rows_per_img);
+    MI355_REQUIRE(x->M_sel >= 0 && x->M_sel < (1ll << 31), "gemm_bf16_ex: bad M_sel %lld", (long long)x->M_sel);
+    MI355_REQUIRE(!x->splitk_ws == !x->splitk_ws_bytes, "gemm_bf16_ex: split-K workspace and its size go together");
+    MI355_REQUIRE(!x->ln_stats == !x->ln_colsum, "gemm_bf16_ex: ln_stats and ln_colsum go together");
+    for (const void* p : {x->A, x->W, (const void*)x->bias, x->res, (const void*)x->gate, (const void*)x->out, (const void*)x->splitk_ws,
+                          (const void*)x->ln_stats, (const void*)x->ln_colsum})
+        MI355_REQUIRE((uintptr_t)p % 16 == 0, "gemm_bf16_ex: pointers must be 16-byte aligned");
+    GemmArgs a{};
+    a.A = (const bf16_t*)x->A; a.lda = x->lda; a.W = (const bf16_t*)x->W; a.ldw = x->ldw; a.bias = x->bias;
+    a.res = (const bf16_t*)x->res; a.ldr = x->res ? x->ldr : 0; a.res_n = x->res ? x->res_n : x->N;
+    a.gate = x->gate; a.gate_ld = x->gate ? x->gate_ld : 0; a.rows_per_img = x->rows_per_img;
+    a.a_relu6 = x->a_relu6 ? 1 : 0;
+    a.out = x->out; a.ldo = x->ldo; a.out_f32 = x->out_f32 ? 1 : 0;
+    a.M = x->M; a.N = x->N; a.K = x->K; a.act = x->act;
+    a.M_sel = (long)x->M_sel;
+    a.splitk_ws = (float*)x->splitk_ws; a.splitk_ws_bytes = x->splitk_ws_bytes;
+    a.ln_stats = x->ln_stats; a.ln_colsum = x->ln_colsum;
+    if (int e = gemm_zero_page(&a.zeros)) return e;
+    return launch_gemm_bf16(a, (hipStream_t)stream, path);
 }
 
 int mi355_pool_linear(const float* fm, int B, int C, int HW, const float* weight, const float* bias, int N, float* out,

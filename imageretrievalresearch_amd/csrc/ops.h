@@ -28,7 +28,7 @@ struct GemmArgs {
     const float* ln_stats;   // [M][2] = (mean, rstd) of every A row, or null
     const float* ln_colsum;  // [ceil16(N)] column sums of the (gamma-folded) weights
 };
-int launch_gemm_bf16(const GemmArgs& a, hipStream_t st);
+int launch_gemm_bf16(const GemmArgs& a, hipStream_t st, int* path = nullptr);   // path: MI355_GEMM_PATH_* of the branch that ran
 // persistent wide-tile kernel for the compute-bound linears (gemm_wide.hip); launch_gemm_bf16 routes the shapes it supports there
 bool gemm_wide_supported(const GemmArgs& a);
 int launch_gemm_wide(const GemmArgs& a, hipStream_t st);

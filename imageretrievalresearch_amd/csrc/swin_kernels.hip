@@ -7,8 +7,10 @@
 // the softmax reduction is in-lane + two xor-shuffles, and the probabilities are already in B-operand layout for
 // O^T = V^T P^T (k permuted the same way on the V^T side).  Only V goes through LDS (transposed, 4.6 KB / wave).
 #include "model_exec.h"
+#include "../../include/mi355_retrieval.h"
 
 #include <algorithm>
+#include <vector>
 #include <type_traits>
 
 namespace mi355 {
@@ -442,6 +444,33 @@ __global__ __launch_bounds__(256) void k_win_attn(const bf16_t* __restrict__ qkv
 // =====================================================================================
 static inline uint16_t f2bf_h(float f) { return f2bf_host(f); }
 
+// relative_position_bias_table [(2*7-1)^2][heads] -> the dense [heads][49][64] bias k_win_attn reads (key dim padded to 64 with
+// zeros).  Shared by the model pack and mi355_window_attention, so the op-level test covers the packing too.
+static void swin_dense_rel_bias(const float* table, int heads, float* dense) {
+    constexpr int ws = 7;
+    for (int hh = 0; hh < heads; ++hh)
+        for (int i = 0; i < WA_N; ++i)
+            for (int j = 0; j < 64; ++j) {
+                float v = 0.f;
+                if (j < WA_N) {
+                    // relative_position_index[i][j] (timm WindowAttention.__init__)
+                    const int dy = i / ws - j / ws + ws - 1, dx = i % ws - j % ws + ws - 1;
+                    v = table[(size_t)(dy * (2 * ws - 1) + dx) * heads + hh];
+                }
+                dense[((size_t)hh * WA_N + i) * 64 + j] = v;
+            }
+}
+
+static int launch_win_attn(const bf16_t* qkv, const float* bias_dense, bf16_t* out, long B, int res, int C, int heads, int shift,
+                           hipStream_t st) {
+    const long ntasks = B * (res / 7) * (res / 7) * heads;
+    MI355_REQUIRE(ntasks >= 1 && ntasks / 4 < (1l << 31), "win_attn: grid of %ld tasks too large", ntasks);
+    hipLaunchKernelGGL(k_win_attn, dim3((unsigned)cdiv(ntasks, 4)), dim3(256), 0, st, qkv, bias_dense, out, res, C, heads, shift, ntasks,
+                       0.17677669529663687f /* 32^-0.5 */);
+    MI355_LAUNCH_CHECK();
+    return OK;
+}
+
 int swin_pack(Packer& pk, Op& op) {
     auto put_vec = [&](const std::string& name, int n, size_t& off) -> int {
         const TensorSpec* t = pk.get(name);
@@ -474,15 +503,7 @@ int swin_pack(Packer& pk, Op& op) {
             const int ws = op.window, nh = op.heads, N = ws * ws;
             MI355_REQUIRE(ws == 7 && t->numel() == (int64_t)(2 * ws - 1) * (2 * ws - 1) * nh, "pack: %s shape", op.aux_name.c_str());
             op.aux_off = pk.alloc((size_t)nh * N * 64 * 4);
-            float* Bd = (float*)(pk.blob.data() + op.aux_off);
-            for (int hh = 0; hh < nh; ++hh)
-                for (int i = 0; i < N; ++i)
-                    for (int j = 0; j < N; ++j) {
-                        // relative_position_index[i][j] (timm WindowAttention.__init__)
-                        const int dy = i / ws - j / ws + ws - 1, dx = i % ws - j % ws + ws - 1;
-                        const int idx = dy * (2 * ws - 1) + dx;
-                        Bd[((size_t)hh * N + i) * 64 + j] = t->data[(size_t)idx * nh + hh];
-                    }
+            swin_dense_rel_bias(t->data.data(), nh, (float*)(pk.blob.data() + op.aux_off));
             return OK;
         }
         default:
@@ -539,15 +560,9 @@ int swin_exec(const ModelDef& def, const Op& op, ExecCtx& cx) {
                                    (bf16_t*)cx.slot_ptr(op.out), rows, op.cout, op.tokens_h, op.tokens_h, op.ln_eps, cx.st);
         }
         case OP_WINATTN: {
-            const int res = op.tokens_h, nW = (res / 7) * (res / 7);
-            const long ntasks = (long)cx.nb * nW * op.heads;
-            const int C = op.cout;
-            MI355_REQUIRE(C == op.heads * 32, "win_attn: head_dim must be 32");
-            hipLaunchKernelGGL(k_win_attn, dim3((unsigned)cdiv(ntasks, 4)), dim3(256), 0, cx.st, (const bf16_t*)cx.slot_ptr(op.in),
-                               (const float*)cx.w(op.aux_off), (bf16_t*)cx.slot_ptr(op.out), res, C, op.heads, op.shift, ntasks,
-                               0.17677669529663687f /* 32^-0.5 */);
-            MI355_LAUNCH_CHECK();
-            return OK;
+            MI355_REQUIRE(op.cout == op.heads * 32, "win_attn: head_dim must be 32");
+            return launch_win_attn((const bf16_t*)cx.slot_ptr(op.in), (const float*)cx.w(op.aux_off), (bf16_t*)cx.slot_ptr(op.out),
+                                   cx.nb, op.tokens_h, op.cout, op.heads, op.shift, cx.st);
         }
         case OP_TOKEN_MEAN: {
             MI355_REQUIRE(op.cin == 1024, "token_mean: width %d unsupported", op.cin);
@@ -565,3 +580,33 @@ int swin_exec(const ModelDef& def, const Op& op, ExecCtx& cx) {
 }
 
 }  // namespace mi355
+
+extern "C" int mi355_window_attention(const void* qkv, const float* bias_table, void* out, int B, int res, int C, int heads, int shift,
+                                      void* stream) {
+    using namespace mi355;
+    MI355_REQUIRE(qkv && bias_table && out, "window_attention: null pointer");
+    MI355_REQUIRE(B >= 1 && res >= 7 && res % 7 == 0 && res <= 7 * 1024, "window_attention: bad shape B=%d res=%d (res a multiple of 7)", B,
+                  res);
+    MI355_REQUIRE(heads >= 1 && heads <= 1024 && C == 32 * heads, "window_attention: C=%d must be 32 * heads (heads=%d)", C, heads);
+    MI355_REQUIRE(shift == 0 || (shift == 3 && res > 7), "window_attention: shift %d (0, or 3 when res > 7)", shift);
+    MI355_REQUIRE((size_t)B * res * res * 3 * C < ((size_t)1 << 40), "window_attention: tensor too large");
+    MI355_REQUIRE((uintptr_t)qkv % 16 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)bias_table % 4 == 0,
+                  "window_attention: qkv and out must be 16-byte aligned");
+    const hipStream_t st = (hipStream_t)stream;
+    const size_t ntab = (size_t)13 * 13 * heads, ndense = (size_t)heads * WA_N * 64;
+    std::vector<float> tab(ntab), dense(ndense);
+    MI355_CHECK_HIP(hipMemcpyAsync(tab.data(), bias_table, ntab * 4, hipMemcpyDeviceToHost, st));
+    MI355_CHECK_HIP(hipStreamSynchronize(st));
+    swin_dense_rel_bias(tab.data(), heads, dense.data());
+    void* d = nullptr;
+    MI355_CHECK_HIP(hipMalloc(&d, ndense * 4));
+    int e = hipMemcpyAsync(d, dense.data(), ndense * 4, hipMemcpyHostToDevice, st) == hipSuccess ? OK : ERR_HIP;
+    if (e) set_error("window_attention: bias upload failed");
+    else e = launch_win_attn((const bf16_t*)qkv, (const float*)d, (bf16_t*)out, B, res, C, heads, shift, st);
+    if (hipStreamSynchronize(st) != hipSuccess && !e) {
+        set_error("window_attention: stream synchronisation failed");
+        e = ERR_HIP;
+    }
+    MI355_CHECK_HIP(hipFree(d));
+    return e;
+}

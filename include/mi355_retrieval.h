@@ -304,6 +304,58 @@ int mi355_pool_linear(const float* fm, int B, int C, int HW, const float* weight
 int mi355_gemm_bf16(const void* A, const void* W, const float* bias, void* out, int M, int N, int K, int ldw, int act,
                     void* stream);
 
+/* Developer entry: the same GEMM with every operand the model executor uses (tests reach each dispatch branch through it).
+ *   out[m][n] = act( sum_k A'[m][k] W[n][k] + bias[n] ) (+ res[m][n] for n < res_n), one rounding (bf16 out) or none (fp32 out)
+ *   A'[m][k]  = bf16( a_relu6 ? relu6(A[m][k] * g) : A[m][k] * g ),  g = gate[m / rows_per_img][k]  (A' = A when gate is NULL
+ *               and a_relu6 is 0; relu6(A) when gate is NULL and a_relu6 is 1)
+ *   ln_stats [M][2] (mean, rstd) + ln_colsum [ceil16(N)]: LayerNorm-folded epilogue, acc -> rstd (acc - mean colsum) before the bias
+ *   splitk_ws (splitk_ws_bytes): fp32 scratch that enables the split-K path; M_sel: the rows that decide split-K (0: M)
+ * W is bf16 [ceil16(N)][ldw], bias fp32 [ceil16(N)], all pointers 16-byte aligned device pointers; res / gate / ln / workspace
+ * may be NULL.  path (host, may be NULL) receives the branch that ran: MI355_GEMM_PATH_* in the low byte, and for the kernels
+ * templated on the tile width the number of 16-column sub-tiles (MI355_GEMM_PATH_NT).  Every argument is checked before any HIP
+ * call.  The environment variables the dispatcher reads (MI355_GEMM_WIDE, ...) apply as in the model. */
+typedef struct mi355_gemm_ex_args {
+    const void* A; int lda;
+    const void* W; int ldw;
+    const float* bias;
+    const void* res; int ldr; int res_n;
+    const float* gate; int gate_ld; int rows_per_img; int a_relu6;
+    void* out; int ldo; int out_f32;
+    int M, N, K, act;
+    int64_t M_sel;
+    void* splitk_ws; size_t splitk_ws_bytes;
+    const float* ln_stats; const float* ln_colsum;
+} mi355_gemm_ex_args;
+
+enum {
+    MI355_GEMM_PATH_TILE_M64_BK32 = 1,    /* k_gemm_bf16<1, NT, 32>: M <= 64, K < 64 */
+    MI355_GEMM_PATH_TILE_M64_BK64 = 2,    /* k_gemm_bf16<1, NT, 64>: M <= 64, K >= 64 */
+    MI355_GEMM_PATH_TILE = 3,             /* k_gemm_bf16<2, NT, 32> */
+    MI355_GEMM_PATH_BIG = 4,              /* k_gemm_big<false, false, 64> */
+    MI355_GEMM_PATH_BIG_KTAIL = 5,        /* k_gemm_big<false, true, 64> */
+    MI355_GEMM_PATH_BIG32 = 6,            /* k_gemm_big<false, false, 32> */
+    MI355_GEMM_PATH_BIG32_KTAIL = 7,      /* k_gemm_big<false, true, 32> */
+    MI355_GEMM_PATH_BIG_GATED = 8,        /* k_gemm_big<true, false, 64> */
+    MI355_GEMM_PATH_BIG_GATED_KTAIL = 9,  /* k_gemm_big<true, true, 64> */
+    MI355_GEMM_PATH_STREAM = 10,          /* k_gemm_stream<NT, 1> */
+    MI355_GEMM_PATH_PROJ = 11,            /* k_proj_lds<NT, KST> */
+    MI355_GEMM_PATH_SPLITK = 12,          /* k_gemm_splitk + k_splitk_reduce */
+    MI355_GEMM_PATH_WIDE = 13             /* k_gemm_wide<MI> (MI355_GEMM_WIDE=1) */
+};
+#define MI355_GEMM_PATH_KIND(p) ((p) & 0xff)
+#define MI355_GEMM_PATH_NT(p) (((p) >> 8) & 0xff)
+
+int mi355_gemm_bf16_ex(const mi355_gemm_ex_args* args, int* path, void* stream);
+
+/* Developer entry: one Swin window-attention layer (window 7, head_dim 32) through the model's kernel.
+ *   qkv [B][res*res][3C] bf16 (channel = which * C + head * 32 + d, tokens in image order), out [B][res*res][C] bf16,
+ *   bias_table [169][heads] fp32 (timm relative_position_bias_table), packed to the kernel's dense layout by the model's
+ *   packing routine; shift 0 or 3 (cyclic shift + -100 mask of timm's shifted windows, res > 7).
+ *   out = softmax(q k^T 32^-0.5 + bias + mask) v per (image, window, head).  res a multiple of 7, C == 32 * heads.
+ * Every argument is checked before any HIP call.  Synchronises the stream (the packed bias is a per-call scratch buffer). */
+int mi355_window_attention(const void* qkv, const float* bias_table, void* out, int B, int res, int C, int heads, int shift,
+                           void* stream);
+
 /* Inference pre-processing: SquarePad(fill) -> ToTensor -> Normalize, utils/square_pad.py:20-36 +
  * inference/inference.py:48-52.  img: uint8 RGB, HWC (h, w, 3) on the device; mean/std: HOST float[3];
  * out: fp32 (3, S, S) with S = max(h, w), i.e. one image slot of the model's NCHW input batch. */
