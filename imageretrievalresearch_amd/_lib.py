@@ -28,6 +28,13 @@ class GemmExArgs(C.Structure):
                 ("ln_stats", vp), ("ln_colsum", vp)]
 
 
+class RankFilter(C.Structure):
+    """mi355_rank_filter (include/mi355_retrieval.h): the eligibility filter of mi355_rank_topk_filtered / _f16_filtered."""
+    _fields_ = [("query_labels", vp), ("gallery_labels", vp), ("label_mode", C.c_int), ("exclude", vp)]
+
+
+LABEL_ANY, LABEL_SAME, LABEL_DIFFERENT = 0, 1, 2
+
 # name -> (restype, argtypes); must list every symbol include/mi355_retrieval.h declares
 # (tests/test_abi.py cross-checks this table against the header).
 PROTOTYPES = {
@@ -48,6 +55,13 @@ PROTOTYPES = {
     "mi355_rank_f16_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int, C.c_int]),
     "mi355_rank_topk_f16": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_int64, vp, vp, vp,
                                       C.c_size_t, vp]),
+    "mi355_rank_topk_filtered": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int64,
+                                           C.POINTER(RankFilter), vp, vp, vp, C.c_size_t, vp]),
+    "mi355_rank_topk_f16_filtered": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_int64,
+                                               C.POINTER(RankFilter), vp, vp, vp, C.c_size_t, vp]),
+    "mi355_rank_last_path": (C.c_int, []),
+    "mi355_clear_pads": (C.c_int, [vp, vp, C.c_int64, C.c_int64, C.c_int64, vp]),
+    "mi355_retrieval_metrics": (C.c_int, [vp, C.c_int64, C.c_int, vp, vp, C.c_int64, vp, vp, vp]),
     "mi355_cosine_scores": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_float, vp, vp,
                                       C.c_size_t, vp]),
     "mi355_topk_rows": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int, C.c_int64, vp, vp, vp, C.c_size_t, vp]),

@@ -135,120 +135,18 @@ __global__ __launch_bounds__(256) void k_cos_gemm(const float* __restrict__ Qn, 
                                                   const float* __restrict__ ginv, float* __restrict__ S,
                                                   int Q, i64 G, int D, int k, float* __restrict__ cand_val,
                                                   int* __restrict__ cand_idx, int x0, int ntx, int xtiles, int ny) {
-    // x0 / ntx: this launch covers the column tiles [x0, x0 + xtiles) of ntx for ny query blocks (the host splits a call into a main launch
-    // of whole rounds and a tail launch of smaller tiles)
-    constexpr int BM = 64 * MT;
-    constexpr int RK_LD = RK_BK + 4;      // +4 floats: ds_read_b128 of 16 distinct rows is bank-conflict free (36 and 20)
-    constexpr int CPR = RK_BK / 4;        // float4 columns per row of a K-tile
-    constexpr int RPP = 256 / CPR;        // rows covered by one pass of the 256 threads
-    constexpr int A_LOADS = BM / RPP;     // float4 loads per thread per K-tile for A
-    constexpr int B_LOADS = RK_BN / RPP;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* As = smem;                          // [2][BM][RK_LD]
-    float* Bs = smem + 2 * BM * RK_LD;         // [2][RK_BN][RK_LD]
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    int bx, by;
-    rank_tile_of((int)blockIdx.x, xtiles, ny, bx, by);
-    const i64 n0 = (i64)(bx + x0) * RK_BN;
-    const int m0 = by * BM;
-
-    const int c4 = tid % CPR;  // float4 column within the K-tile
-    const int r0 = tid / CPR;
-
-    f32x16 acc[MT][2];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-    f32x4 ra[A_LOADS], rb[B_LOADS];
-
-    auto load_tile = [&](int k0) {
-        const int k = k0 + c4 * 4;
-#pragma unroll
-        for (int i = 0; i < A_LOADS; ++i) {
-            const int row = m0 + r0 + RPP * i;
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (row < Q) {
-                const float* p = Qn + (i64)row * D + k;
-                if (VEC) {
-                    if (k + 3 < D) v = *reinterpret_cast<const f32x4*>(p);
-                } else {
-                    if (k + 0 < D) v.x = p[0];
-                    if (k + 1 < D) v.y = p[1];
-                    if (k + 2 < D) v.z = p[2];
-                    if (k + 3 < D) v.w = p[3];
-                }
-            }
-            ra[i] = v;
-        }
-#pragma unroll
-        for (int i = 0; i < B_LOADS; ++i) {
-            const i64 row = n0 + r0 + RPP * i;
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (row < G) {
-                const float* p = Gal + row * D + k;
-                if (VEC) {
-                    if (k + 3 < D) v = *reinterpret_cast<const f32x4*>(p);
-                } else {
-                    if (k + 0 < D) v.x = p[0];
-                    if (k + 1 < D) v.y = p[1];
-                    if (k + 2 < D) v.z = p[2];
-                    if (k + 3 < D) v.w = p[3];
-                }
-            }
-            rb[i] = v;
-        }
-    };
-    auto store_tile = [&](int buf) {
-        float* a = As + buf * BM * RK_LD;
-        float* b = Bs + buf * RK_BN * RK_LD;
-#pragma unroll
-        for (int i = 0; i < A_LOADS; ++i)
-            *reinterpret_cast<f32x4*>(a + (r0 + RPP * i) * RK_LD + c4 * 4) = ra[i];
-#pragma unroll
-        for (int i = 0; i < B_LOADS; ++i)
-            *reinterpret_cast<f32x4*>(b + (r0 + RPP * i) * RK_LD + c4 * 4) = rb[i];
-    };
-
-    const int nt = (D + RK_BK - 1) / RK_BK;
-    load_tile(0);
-    store_tile(0);
-    __syncthreads();
-
-    const int lr = lane & 31;
-    const int lk = (lane >> 5) * 4;
-    for (int t = 0; t < nt; ++t) {
-        const int buf = t & 1;
-        if (t + 1 < nt) load_tile((t + 1) * RK_BK);
-        const float* a = As + buf * BM * RK_LD + (wm * MT * 32 + lr) * RK_LD + lk;
-        const float* b = Bs + buf * RK_BN * RK_LD + (wn * 64 + lr) * RK_LD + lk;
-#pragma unroll
-        for (int t8 = 0; t8 < RK_BK / 8; ++t8) {
-            f32x4 af[MT], bfr[2];
-#pragma unroll
-            for (int i = 0; i < MT; ++i) af[i] = *reinterpret_cast<const f32x4*>(a + i * 32 * RK_LD + t8 * 8);
-#pragma unroll
-            for (int j = 0; j < 2; ++j) bfr[j] = *reinterpret_cast<const f32x4*>(b + j * 32 * RK_LD + t8 * 8);
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int i = 0; i < MT; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i][e], bfr[j][e], acc[i][j], 0, 0, 0);
-        }
-        if (t + 1 < nt) store_tile(buf ^ 1);
-        __syncthreads();
-    }
-
-    cos_gemm_epilogue<MT, FK>(acc, smem, ginv, S, Q, G, k, cand_val, cand_idx, x0, ntx, n0, m0);
+    constexpr bool FILT = false;
+    const RankFilter flt{};
+#include "rank_gemm_f32.inc"
+}
+template <int MT, int RK_BK, bool VEC, int FK>
+__global__ __launch_bounds__(256) void k_cos_gemm_filt(const float* __restrict__ Qn, const float* __restrict__ Gal,
+                                                       const float* __restrict__ ginv, int Q, i64 G, int D, int k,
+                                                       float* __restrict__ cand_val, int* __restrict__ cand_idx, int x0,
+                                                       int ntx, int xtiles, int ny, RankFilter flt) {
+    constexpr bool FILT = true;
+    float* const S = nullptr;
+#include "rank_gemm_f32.inc"
 }
 
 // =====================================================================================
@@ -273,160 +171,19 @@ __global__ __launch_bounds__(256, 3) void k_cos_gemm_split(const bf16_t* __restr
                                                            i64 G, int D, int k, float* __restrict__ cand_val,
                                                            int* __restrict__ cand_idx, int x0, int ntx, int n_steps,
                                                            const float* __restrict__ zeros, int xtiles, int ny) {
-    constexpr int BM = 64 * MT;
-    constexpr int BK = 16;
-    constexpr int A_STAGE = (BM / 32) * 3 * 512;      // bf16 elements per stage
-    constexpr int A_PIECES = (BM / 32) * 3;           // 1 KB pieces per stage
-    constexpr int B_STAGE = RK_BN * BK;               // floats per stage (8 KB)
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    bf16_t* As = reinterpret_cast<bf16_t*>(smem);                       // [A_RING][BM/32][3][512]
-    // A ring: 2 stages at MT = 2 (the pieces come from L2 one k-step ahead; a third stage would cost the third workgroup per
-    // CU), 3 stages at MT = 1 (two k-steps ahead: the 64-row tiles are the tail launch and the small-Q shapes, few
-    // workgroups per CU with nothing else to hide a piece's latency behind)
-    constexpr int A_RING = MT == 1 ? 3 : 2;
-    float* Bs = smem + (A_RING * A_STAGE * 2) / 4;                      // [3][128][16], chunks swizzled
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    int bx, by;
-    rank_tile_of((int)blockIdx.x, xtiles, ny, bx, by);
-    const i64 n0 = (i64)(bx + x0) * RK_BN;
-    const int m0 = by * BM;
-    // the wave index as a scalar: piece selection becomes scalar branches (a per-lane branch around a load makes hipcc
-    // drain vmcnt)
-    const int swave = __builtin_amdgcn_readfirstlane(wave);
-
-    // B: wave w moves pieces 2w and 2w + 1 (rows 32w .. 32w + 31); lane -> row 16 * piece + lane / 4, position lane % 4
-    const float* b_row[2];
-    int b_k[2];
-    bool b_ok[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int r = (swave * 2 + i) * 16 + (lane >> 2);
-        const int c = (lane & 3) ^ ((r >> 2) & 3);
-        b_ok[i] = n0 + r < G;
-        b_row[i] = Gal + (b_ok[i] ? (n0 + r) * D : 0);
-        b_k[i] = c * 4;
-    }
-    auto dma_b = [&](int stage, int k0) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const bool ok = b_ok[i] && k0 + b_k[i] < D;                // D % 4 == 0: a chunk is inside or outside
-            glds16(reinterpret_cast<const bf16_t*>(ok ? b_row[i] + k0 + b_k[i] : zeros),
-                   reinterpret_cast<bf16_t*>(Bs + stage * B_STAGE + (swave * 2 + i) * 256));
-        }
-    };
-    // A: piece (row block rbl, plane p) of k-step t sits at Qs + (((m0/32 + rbl) * n_steps + t) * 3 + p) * 512.
-    // 12 (MT = 2) or 6 (MT = 1) pieces per stage: wave w moves pieces w, w + 4, w + 8 / pieces w and (w < 2) w + 4.
-    const bf16_t* a_src = Qs + (size_t)(m0 / 32) * n_steps * 3 * 512 + lane * 8;
-    const bf16_t* a_piece[(A_PIECES + 3) / 4];
-#pragma unroll
-    for (int i = 0; i < (A_PIECES + 3) / 4; ++i) {
-        const int piece = (swave + 4 * i) % A_PIECES;
-        a_piece[i] = a_src + ((size_t)((piece / 3) * n_steps) * 3 + piece % 3) * 512;
-    }
-    auto dma_a = [&](int buf, int t) {
-#pragma unroll
-        for (int i = 0; i < (A_PIECES + 3) / 4; ++i) {
-            const int piece = swave + 4 * i;
-            if (A_PIECES % 4 == 0 || i < A_PIECES / 4 || swave < A_PIECES % 4)
-                glds16(a_piece[i] + (size_t)t * 3 * 512, As + buf * A_STAGE + piece * 512);
-        }
-    };
-
-    f32x16 acc[MT][2];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-    const int lr = lane & 31;
-    // B fragment reads: row r = wn * 64 + j * 32 + lr, chunks 2 * (lane >> 5) and + 1 at their swizzled positions
-    int b_off[2][2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int r = wn * 64 + j * 32 + lr, sw = (r >> 2) & 3, c0 = (lane >> 5) * 2;
-        b_off[j][0] = r * BK + ((c0 ^ sw) << 2);
-        b_off[j][1] = r * BK + (((c0 + 1) ^ sw) << 2);
-    }
-    auto compute = [&](int abuf, int bstage) {
-        const bf16_t* a = As + abuf * A_STAGE + (wm * MT * 3) * 512 + lane * 8;
-        const float* b = Bs + bstage * B_STAGE;
-        bf16x8 af[MT][3];
-        u32x4 bh[2], bm[2], bl[2];
-        f32x4 v0[2], v1[2];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            v0[j] = *reinterpret_cast<const f32x4*>(b + b_off[j][0]);
-            v1[j] = *reinterpret_cast<const f32x4*>(b + b_off[j][1]);
-        }
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int p = 0; p < 3; ++p) af[i][p] = *reinterpret_cast<const bf16x8*>(a + (i * 3 + p) * 512);
-        split3(v0[0], v1[0], bh[0], bm[0], bl[0]);
-        // Per fragment j: six products for each of the MT row blocks, smallest terms first (the order is the same for every
-        // (query, gallery row) pair wherever its tile lies).  The split of fragment 1 is issued in the gaps of fragment 0's
-        // MFMAs (an MFMA holds the vector issue for 8 of its 32 cycles): sched_group_barrier pins "1 MFMA, 4 VALU" groups.
-        auto products = [&](int j) {
-            const bf16x8 gh = *reinterpret_cast<const bf16x8*>(&bh[j]);
-            const bf16x8 gm = *reinterpret_cast<const bf16x8*>(&bm[j]);
-            const bf16x8 gl = *reinterpret_cast<const bf16x8*>(&bl[j]);
-#pragma unroll
-            for (int i = 0; i < MT; ++i) {
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][2], gh, acc[i][j], 0, 0, 0);   // l * h'
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], gl, acc[i][j], 0, 0, 0);   // h * l'
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][1], gm, acc[i][j], 0, 0, 0);   // m * m'
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][1], gh, acc[i][j], 0, 0, 0);   // m * h'
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], gm, acc[i][j], 0, 0, 0);   // h * m'
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], gh, acc[i][j], 0, 0, 0);   // h * h'
-            }
-        };
-        split3(v0[1], v1[1], bh[1], bm[1], bl[1]);
-        products(0);
-#pragma unroll
-        for (int g = 0; g < 6 * MT; ++g) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // one MFMA
-            __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);   // four VALU (of fragment 1's split)
-        }
-        products(1);
-    };
-
-    dma_a(0, 0);
-    if (A_RING == 3 && n_steps > 1) dma_a(1, 1);
-    dma_b(0, 0);
-    dma_b(1, BK);                      // (zeros past D)
-    __syncthreads();                   // drains vmcnt: everything has landed
-
-    int bs_cur = 0, bs_far = 2;        // B stage of k-step t / of k-step t + 2 (and, at A_RING == 3, the A stages)
-    for (int t = 0; t < n_steps; ++t) {
-        if constexpr (A_RING == 2) {
-            if (t + 1 < n_steps) dma_a((t & 1) ^ 1, t + 1);  // everybody left these buffers at the previous barrier
-        } else {
-            if (t + 2 < n_steps) dma_a(bs_far, t + 2);
-        }
-        __builtin_amdgcn_sched_barrier(0);                   // (the counts below need the A pieces issued BEFORE the B pieces)
-        dma_b(bs_far, (t + 2) * BK);
-        __builtin_amdgcn_sched_barrier(0);
-        compute(A_RING == 2 ? (t & 1) : bs_cur, bs_cur);
-        if constexpr (A_RING == 2) {
-            asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); // A(t+1) and B(t+1) have landed; B(t+2) stays in flight
-        } else {
-            // A(t+2) (two pieces from waves 0 and 1, one from waves 2 and 3; none at the end) and B(t+2) stay in flight
-            if (t + 2 >= n_steps) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-            else if (swave < A_PIECES % 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        bs_cur = bs_cur == 2 ? 0 : bs_cur + 1;
-        bs_far = bs_far == 2 ? 0 : bs_far + 1;
-    }
-    __syncthreads();                   // the last look-ahead pieces (zeros) have landed before the epilogue reuses the LDS
-    cos_gemm_epilogue<MT, FK>(acc, smem, ginv, S, Q, G, k, cand_val, cand_idx, x0, ntx, n0, m0);
+    constexpr bool FILT = false;
+    const RankFilter flt{};
+#include "rank_gemm_split.inc"
+}
+template <int MT, int FK>
+__global__ __launch_bounds__(256, 3) void k_cos_gemm_split_filt(const bf16_t* __restrict__ Qs, const float* __restrict__ Gal,
+                                                                const float* __restrict__ ginv, int Q, i64 G, int D, int k,
+                                                                float* __restrict__ cand_val, int* __restrict__ cand_idx,
+                                                                int x0, int ntx, int n_steps, const float* __restrict__ zeros,
+                                                                int xtiles, int ny, RankFilter flt) {
+    constexpr bool FILT = true;
+    float* const S = nullptr;
+#include "rank_gemm_split.inc"
 }
 
 // =====================================================================================
@@ -618,65 +375,18 @@ __global__ __launch_bounds__(256) void k_topk_small(const float* __restrict__ va
                                                     const int* __restrict__ idxs32,
                                                     i64 rowlen, i64 in_stride, i64 chunk_len, int k,
                                                     i64 idx_offset, float* __restrict__ ov, i64* __restrict__ oi) {
-    const int tid = threadIdx.x;
-    const i64 q = blockIdx.y;
-    const i64 c0 = (i64)blockIdx.x * chunk_len;
-    const i64 c1 = min(rowlen, c0 + chunk_len);
-    const float* v = vals + q * in_stride;
-    const i64* ix = idxs ? idxs + q * in_stride : nullptr;
-    const int* ix32 = idxs32 ? idxs32 + q * in_stride : nullptr;
-
-    float lv[K];
-    i64 li[K];
-#pragma unroll
-    for (int i = 0; i < K; ++i) { lv[i] = NEG_INF; li[i] = IDX_PAD; }
-
-    for (i64 j = c0 + tid; j < c1; j += 256) {
-        const float x = v[j];
-        i64 id;
-        if (ix32) { const int t = ix32[j]; id = t == IDX32_PAD ? IDX_PAD : (i64)t + idx_offset; }
-        else id = ix ? ix[j] : j + idx_offset;
-        if (id != IDX_PAD && better(x, id, lv[K - 1], li[K - 1])) {
-            lv[K - 1] = x; li[K - 1] = id;
-#pragma unroll
-            for (int i = K - 1; i > 0; --i) {
-                if (better(lv[i], li[i], lv[i - 1], li[i - 1])) {
-                    float tv = lv[i]; lv[i] = lv[i - 1]; lv[i - 1] = tv;
-                    i64 ti = li[i]; li[i] = li[i - 1]; li[i - 1] = ti;
-                }
-            }
-        }
-    }
-
-    __shared__ float sv[4];
-    __shared__ i64 si[4];
-    const int lane = tid & 63, wave = tid >> 6;
-    float* o_v = ov + (q * gridDim.x + blockIdx.x) * k;
-    i64* o_i = oi + (q * gridDim.x + blockIdx.x) * k;
-    for (int r = 0; r < k; ++r) {
-        float bv = lv[0];
-        i64 bi = li[0];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov2 = __shfl_xor(bv, o, 64);
-            const i64 oi2 = __shfl_xor(bi, o, 64);
-            if (better(ov2, oi2, bv, bi)) { bv = ov2; bi = oi2; }
-        }
-        if (lane == 0) { sv[wave] = bv; si[wave] = bi; }
-        __syncthreads();
-        bv = sv[0]; bi = si[0];
-#pragma unroll
-        for (int w = 1; w < 4; ++w)
-            if (better(sv[w], si[w], bv, bi)) { bv = sv[w]; bi = si[w]; }
-        if (tid == 0) { o_v[r] = bv; o_i[r] = bi; }
-        // the owner pops its head (indices are unique among real entries; pads never win a real slot)
-        if (li[0] == bi && bi != IDX_PAD) {      // (by index only: a NaN score does not compare equal to itself)
-#pragma unroll
-            for (int i = 0; i < K - 1; ++i) { lv[i] = lv[i + 1]; li[i] = li[i + 1]; }
-            lv[K - 1] = NEG_INF; li[K - 1] = IDX_PAD;
-        }
-        __syncthreads();
-    }
+    constexpr bool FILT = false;
+    const RankFilter flt{};
+#include "rank_topk_small.inc"
+}
+template <int K>
+__global__ __launch_bounds__(256) void k_topk_small_filt(const float* __restrict__ vals, i64 rowlen, i64 in_stride,
+                                                         i64 chunk_len, int k, i64 idx_offset, float* __restrict__ ov,
+                                                         i64* __restrict__ oi, RankFilter flt) {
+    constexpr bool FILT = true;
+    const i64* const idxs = nullptr;
+    const int* const idxs32 = nullptr;
+#include "rank_topk_small.inc"
 }
 
 // ---- any k <= 1024: bitonic sort of a 2048-element chunk in LDS, keep the first k.
@@ -684,41 +394,22 @@ constexpr int BT_N = 2048;
 __global__ __launch_bounds__(256) void k_topk_bitonic(const float* __restrict__ vals, const i64* __restrict__ idxs,
                                                       i64 rowlen, i64 in_stride, int k, i64 idx_offset,
                                                       float* __restrict__ ov, i64* __restrict__ oi) {
-    __shared__ float sv[BT_N];
-    __shared__ i64 si[BT_N];
-    const int tid = threadIdx.x;
-    const i64 q = blockIdx.y;
-    const i64 c0 = (i64)blockIdx.x * BT_N;
-    const float* v = vals + q * in_stride;
-    const i64* ix = idxs ? idxs + q * in_stride : nullptr;
-    for (int j = tid; j < BT_N; j += 256) {
-        const i64 g = c0 + j;
-        if (g < rowlen) {
-            sv[j] = v[g];
-            si[j] = ix ? ix[g] : g + idx_offset;
-        } else {
-            sv[j] = NEG_INF;
-            si[j] = IDX_PAD;
-        }
-    }
-    __syncthreads();
-    for (int size = 2; size <= BT_N; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = tid; t < BT_N / 2; t += 256) {
-                const int lo = 2 * t - (t & (stride - 1));
-                const int hi = lo + stride;
-                const bool desc = ((lo & size) == 0);  // first half of each size-block sorted descending
-                const float a = sv[lo], b = sv[hi];
-                const i64 ia = si[lo], ib = si[hi];
-                const bool swap = desc ? better(b, ib, a, ia) : better(a, ia, b, ib);
-                if (swap) { sv[lo] = b; sv[hi] = a; si[lo] = ib; si[hi] = ia; }
-            }
-            __syncthreads();
-        }
-    }
-    float* o_v = ov + (q * gridDim.x + blockIdx.x) * k;
-    i64* o_i = oi + (q * gridDim.x + blockIdx.x) * k;
-    for (int j = tid; j < k; j += 256) { o_v[j] = sv[j]; o_i[j] = si[j]; }
+    constexpr bool FILT = false;
+    const RankFilter flt{};
+#include "rank_topk_bitonic.inc"
+}
+__global__ __launch_bounds__(256) void k_topk_bitonic_filt(const float* __restrict__ vals, i64 rowlen, i64 in_stride, int k,
+                                                           i64 idx_offset, float* __restrict__ ov, i64* __restrict__ oi,
+                                                           RankFilter flt) {
+    constexpr bool FILT = true;
+    const i64* const idxs = nullptr;
+#include "rank_topk_bitonic.inc"
+}
+
+// Indices outside [lo, hi) -> (-inf, -1): the pads a filtered search leaves when fewer than k rows are eligible
+__global__ __launch_bounds__(256) void k_clear_pads(float* __restrict__ v, i64* __restrict__ ix, i64 n, i64 lo, i64 hi) {
+    const i64 t = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (t < n && (ix[t] < lo || ix[t] >= hi)) { v[t] = NEG_INF; ix[t] = -1; }
 }
 
 // =====================================================================================
@@ -873,6 +564,42 @@ __global__ void k_distinct_topn(const i64* __restrict__ idx, const float* __rest
     }
 }
 
+// Relevance metrics of one ranked list per wave (mi355_retrieval_metrics): rank i is relevant when its row has the query's
+// class.  The running count of relevant ranks comes from a ballot per 64 ranks; the MAP@R terms are summed per lane in rank
+// order and then across the wave in a fixed tree, so the result is a fixed function of the inputs.
+__global__ __launch_bounds__(256) void k_retrieval_metrics(const i64* __restrict__ idx, i64 Q, int k, const i64* __restrict__ qcls,
+                                                           const i64* __restrict__ gcls, i64 G, const i64* __restrict__ R,
+                                                           double* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const i64 q = (i64)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (q >= Q) return;
+    const i64 c = qcls[q], Rq = R[q];
+    int first = k, run = 0, hits = 0;
+    double ap = 0.0;
+    for (int i0 = 0; i0 < k; i0 += 64) {
+        const int i = i0 + lane;
+        bool rel = false;
+        if (i < k) {
+            const i64 g = idx[q * k + i];
+            rel = g >= 0 && g < G && gcls[g] == c;
+        }
+        const unsigned long long m = __ballot(rel);
+        if (first == k && m) first = i0 + __ffsll((long long)m) - 1;
+        const int cum = run + __popcll(m & ((1ull << lane) - 1)) + (rel ? 1 : 0);     // relevant ranks 0 .. i
+        if (rel && i < Rq) ap += (double)cum / (double)(i + 1);
+        hits += __popcll(__ballot(rel && i < Rq));
+        run += __popcll(m);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ap += __shfl_xor(ap, o, 64);
+    if (lane == 0) {
+        double* o = out + q * 3;
+        o[0] = first;
+        o[1] = Rq > 0 ? (double)hits / (double)Rq : 0.0;
+        o[2] = Rq > 0 ? ap / (double)Rq : 0.0;
+    }
+}
+
 // =====================================================================================
 // host drivers
 // =====================================================================================
@@ -892,24 +619,54 @@ size_t topk_ws_bytes(i64 Q, i64 G, int k) {
     return 2 * align_up((size_t)Q * per_row * (sizeof(float) + sizeof(i64)), 256) + 256;
 }
 
+// filt (first level of a filtered search, implicit indices): k_topk_small_filt
 template <int K>
 static void launch_small(const float* v, const i64* ix, const int* ix32, i64 rowlen, i64 in_stride, i64 chunk_len, int k,
-                         i64 off, float* ov, i64* oi, i64 nchunk, i64 Q, hipStream_t st) {
-    hipLaunchKernelGGL((k_topk_small<K>), dim3((unsigned)nchunk, (unsigned)Q), dim3(256), 0, st, v, ix, ix32, rowlen,
-                       in_stride, chunk_len, k, off, ov, oi);
+                         i64 off, float* ov, i64* oi, i64 nchunk, i64 Q, hipStream_t st, const RankFilter* filt) {
+    if (filt)
+        hipLaunchKernelGGL((k_topk_small_filt<K>), dim3((unsigned)nchunk, (unsigned)Q), dim3(256), 0, st, v, rowlen, in_stride,
+                           chunk_len, k, off, ov, oi, *filt);
+    else
+        hipLaunchKernelGGL((k_topk_small<K>), dim3((unsigned)nchunk, (unsigned)Q), dim3(256), 0, st, v, ix, ix32, rowlen,
+                           in_stride, chunk_len, k, off, ov, oi);
 }
 static void dispatch_small(const float* v, const i64* ix, const int* ix32, i64 rowlen, i64 in_stride, i64 chunk_len, int k,
-                           i64 off, float* ov, i64* oi, i64 nchunk, i64 Q, hipStream_t st) {
-    if (k <= 1) launch_small<1>(v, ix, ix32, rowlen, in_stride, chunk_len, k, off, ov, oi, nchunk, Q, st);
-    else if (k <= 2) launch_small<2>(v, ix, ix32, rowlen, in_stride, chunk_len, k, off, ov, oi, nchunk, Q, st);
-    else if (k <= 4) launch_small<4>(v, ix, ix32, rowlen, in_stride, chunk_len, k, off, ov, oi, nchunk, Q, st);
-    else launch_small<8>(v, ix, ix32, rowlen, in_stride, chunk_len, k, off, ov, oi, nchunk, Q, st);
+                           i64 off, float* ov, i64* oi, i64 nchunk, i64 Q, hipStream_t st, const RankFilter* filt) {
+    if (k <= 1) launch_small<1>(v, ix, ix32, rowlen, in_stride, chunk_len, k, off, ov, oi, nchunk, Q, st, filt);
+    else if (k <= 2) launch_small<2>(v, ix, ix32, rowlen, in_stride, chunk_len, k, off, ov, oi, nchunk, Q, st, filt);
+    else if (k <= 4) launch_small<4>(v, ix, ix32, rowlen, in_stride, chunk_len, k, off, ov, oi, nchunk, Q, st, filt);
+    else launch_small<8>(v, ix, ix32, rowlen, in_stride, chunk_len, k, off, ov, oi, nchunk, Q, st, filt);
+}
+
+static thread_local int g_rank_path = 0;
+void set_rank_path(int path) { g_rank_path = path; }
+
+RankFilter filter_from(const RankFilter& f, i64 q0) {
+    RankFilter r = f;
+    if (r.qlab) r.qlab += q0;
+    if (r.excl) r.excl += q0;
+    return r;
+}
+
+int make_filter(const mi355_rank_filter* f, i64 idx_offset, const char* who, RankFilter* out) {
+    MI355_REQUIRE(f, "%s: null filter (use the unfiltered entry)", who);
+    MI355_REQUIRE(f->label_mode == MI355_LABEL_ANY || f->label_mode == MI355_LABEL_SAME || f->label_mode == MI355_LABEL_DIFFERENT,
+                  "%s: unknown label_mode %d", who, f->label_mode);
+    MI355_REQUIRE(f->label_mode == MI355_LABEL_ANY || (f->query_labels && f->gallery_labels),
+                  "%s: label_mode %d needs query_labels and gallery_labels (null pointer)", who, f->label_mode);
+    out->qlab = f->label_mode != MI355_LABEL_ANY ? (const i64*)f->query_labels : nullptr;
+    out->glab = f->label_mode != MI355_LABEL_ANY ? (const i64*)f->gallery_labels : nullptr;
+    out->excl = (const i64*)f->exclude;
+    out->idx_offset = idx_offset;
+    out->mode = f->label_mode;
+    return OK;
 }
 
 // Select top-k of each row of vals[Q][rowlen] (implicit or explicit indices) into out_val/out_idx [Q][k].
 // idxs32 (with idxs == nullptr): int32 local candidate indices of the fused GEMM epilogue, k <= SMALL_K only.
 int topk_select(const float* vals, const i64* idxs, i64 Q, i64 rowlen, i64 in_stride, int k, i64 idx_offset,
-                float* out_val, i64* out_idx, void* ws, size_t ws_bytes, hipStream_t st, const int* idxs32) {
+                float* out_val, i64* out_idx, void* ws, size_t ws_bytes, hipStream_t st, const int* idxs32,
+                const RankFilter* filt) {
     MI355_REQUIRE(k >= 1 && k <= LARGE_K, "top-k: k=%d outside [1,%d]", k, LARGE_K);
     MI355_REQUIRE(k <= rowlen, "top-k: k=%d exceeds row length %lld", k, (long long)rowlen);
     MI355_REQUIRE(!idxs32 || k <= SMALL_K, "top-k: int32 candidate lists need k <= %d", SMALL_K);
@@ -934,6 +691,11 @@ int topk_select(const float* vals, const i64* idxs, i64 Q, i64 rowlen, i64 in_st
         i64 len = rowlen, stride = in_stride;
         i64 off = idx_offset;
         int cur = 0;
+        // the filter applies where candidates carry implicit indices (the first level over a score slab); the fused
+        // epilogue applied it already, later levels carry its pads
+        RankFilter fs{};
+        if (filt) fs = filter_from(*filt, qs);
+        const RankFilter* f1 = (filt && !ix && !ix32) ? &fs : nullptr;
         while (true) {
             const bool small = (k <= SMALL_K);
             const i64 chunk = small ? SMALL_CHUNK : BT_N;
@@ -941,15 +703,22 @@ int topk_select(const float* vals, const i64* idxs, i64 Q, i64 rowlen, i64 in_st
             const bool last = (nchunk == 1);
             float* ovp = last ? out_val + qs * k : cv[cur];
             i64* oip = last ? out_idx + qs * k : ci[cur];
-            if (small) dispatch_small(v, ix, ix32, len, stride, chunk, k, off, ovp, oip, nchunk, qn, st);
+            if (small) dispatch_small(v, ix, ix32, len, stride, chunk, k, off, ovp, oip, nchunk, qn, st, f1);
+            else if (f1) hipLaunchKernelGGL(k_topk_bitonic_filt, dim3((unsigned)nchunk, (unsigned)qn), dim3(256), 0, st, v, len,
+                                            stride, k, off, ovp, oip, *f1);
             else hipLaunchKernelGGL(k_topk_bitonic, dim3((unsigned)nchunk, (unsigned)qn), dim3(256), 0, st, v, ix,
                                     len, stride, k, off, ovp, oip);
             MI355_LAUNCH_CHECK();
             if (last) break;
-            v = cv[cur]; ix = ci[cur]; ix32 = nullptr;
+            v = cv[cur]; ix = ci[cur]; ix32 = nullptr; f1 = nullptr;
             len = nchunk * k; stride = len; off = 0;
             cur ^= 1;
         }
+    }
+    if (filt) {
+        hipLaunchKernelGGL(k_clear_pads, dim3((unsigned)cdiv(Q * k, 256)), dim3(256), 0, st, out_val, out_idx, Q * k, (i64)LLONG_MIN,
+                           IDX_PAD);
+        MI355_LAUNCH_CHECK();
     }
     return OK;
 }
@@ -1017,27 +786,43 @@ int kernel_slots(const void* fn, size_t lds, int* cache, int* slots_out) {
     *slots_out = cache[dev];
     return OK;
 }
-template <int MT, int BK, bool VEC, int FK>
+template <int MT, int BK, bool VEC, int FK, bool FILT = false>
 static int gemm_slots(size_t lds, int* slots_out) {
     static int slots[MI355_MAX_DEVICES] = {0};
-    return kernel_slots((const void*)k_cos_gemm<MT, BK, VEC, FK>, lds, slots, slots_out);
+    if constexpr (FILT) return kernel_slots((const void*)k_cos_gemm_filt<MT, BK, VEC, FK>, lds, slots, slots_out);
+    else return kernel_slots((const void*)k_cos_gemm<MT, BK, VEC, FK>, lds, slots, slots_out);
 }
-template <int MT, int FK>
+template <int MT, int FK, bool FILT = false>
 static int split_slots(size_t lds, int* slots_out) {
     static int slots[MI355_MAX_DEVICES] = {0};
-    return kernel_slots((const void*)k_cos_gemm_split<MT, FK>, lds, slots, slots_out);
+    if constexpr (FILT) return kernel_slots((const void*)k_cos_gemm_split_filt<MT, FK>, lds, slots, slots_out);
+    else return kernel_slots((const void*)k_cos_gemm_split<MT, FK>, lds, slots, slots_out);
 }
+
+// filt: the filtered epilogue keeps the tile's gallery labels behind the score tile (inside the staging buffers in every case,
+// static_asserts below, so the filtered kernels request the LDS of the unfiltered ones)
+constexpr size_t EPI_TILE_BYTES = (size_t)64 * (RK_BN + 4) * sizeof(float);
+template <int MT, int BK>
+constexpr size_t gemm_stage_bytes() { return (size_t)2 * (64 * MT + RK_BN) * (BK + 4) * sizeof(float); }
+template <int MT>
+constexpr size_t split_stage_bytes() {   // A ring of 2 (3 at MT = 1), B ring of 3
+    return (size_t)(MT == 1 ? 3 : 2) * (64 * MT / 32) * 3 * 1024 + (size_t)3 * RK_BN * 16 * sizeof(float);
+}
+static_assert(gemm_stage_bytes<2, 16>() >= EPI_TILE_BYTES + FILT_LABELS_BYTES && gemm_stage_bytes<1, 32>() >= EPI_TILE_BYTES + FILT_LABELS_BYTES,
+              "filtered epilogue would grow the exact-fp32 GEMM's LDS");
+static_assert(split_stage_bytes<2>() >= EPI_TILE_BYTES + FILT_LABELS_BYTES && split_stage_bytes<1>() >= EPI_TILE_BYTES + FILT_LABELS_BYTES,
+              "filtered epilogue would grow the split GEMM's LDS");
 
 template <int MT, int BK>
 static size_t gemm_lds(bool fk) {
-    const size_t stage = (size_t)2 * (64 * MT + RK_BN) * (BK + 4) * sizeof(float);
-    const size_t tile = fk ? (size_t)64 * (RK_BN + 4) * sizeof(float) : 0;   // fused selection: 64 rows of the score tile at a time
+    const size_t stage = gemm_stage_bytes<MT, BK>();
+    const size_t tile = fk ? EPI_TILE_BYTES : 0;   // fused selection: 64 rows of the score tile at a time
     return stage > tile ? stage : tile;
 }
 template <int MT>
 static size_t split_lds(bool fk) {
-    const size_t stage = (size_t)(MT == 1 ? 3 : 2) * (64 * MT / 32) * 3 * 1024 + (size_t)3 * RK_BN * 16 * sizeof(float);   // A ring of 2 (3 at MT = 1), B ring of 3
-    const size_t tile = fk ? (size_t)64 * (RK_BN + 4) * sizeof(float) : 0;
+    const size_t stage = split_stage_bytes<MT>();
+    const size_t tile = fk ? EPI_TILE_BYTES : 0;
     return stage > tile ? stage : tile;
 }
 
@@ -1050,53 +835,70 @@ int whole_round_tiles(int ntx, int ny, int slots) {
     return ntx;
 }
 
-template <int MT, int BK, bool VEC, int FK>
+template <int MT, int BK, bool VEC, int FK, bool FILT = false>
 static int launch_gemm(const float* qn, const float* gal, const float* ginv, float* S, int Q, i64 G, int D, int k,
-                       float* cand_val, int* cand_idx, hipStream_t st) {
+                       float* cand_val, int* cand_idx, hipStream_t st, const RankFilter* filt = nullptr) {
     constexpr int BM = 64 * MT;
     const size_t lds = gemm_lds<MT, BK>(FK > 0);
     int slots = 0;
-    if (int e = gemm_slots<MT, BK, VEC, FK>(lds, &slots)) return e;
+    if (int e = gemm_slots<MT, BK, VEC, FK, FILT>(lds, &slots)) return e;
     const int ntx = cdiv(G, RK_BN), ny = cdiv(Q, BM);
     const int xm = MT == 2 ? whole_round_tiles(ntx, ny, slots) : ntx;
     if (xm > 0) {
-        hipLaunchKernelGGL((k_cos_gemm<MT, BK, VEC, FK>), dim3((unsigned)xm * (unsigned)ny), dim3(256), lds, st, qn, gal, ginv, S,
-                           Q, G, D, k, cand_val, cand_idx, 0, ntx, xm, ny);
+        if constexpr (FILT)
+            hipLaunchKernelGGL((k_cos_gemm_filt<MT, BK, VEC, FK>), dim3((unsigned)xm * (unsigned)ny), dim3(256), lds, st, qn, gal,
+                               ginv, Q, G, D, k, cand_val, cand_idx, 0, ntx, xm, ny, *filt);
+        else
+            hipLaunchKernelGGL((k_cos_gemm<MT, BK, VEC, FK>), dim3((unsigned)xm * (unsigned)ny), dim3(256), lds, st, qn, gal, ginv, S,
+                               Q, G, D, k, cand_val, cand_idx, 0, ntx, xm, ny);
         MI355_LAUNCH_CHECK();
     }
     if (xm < ntx) {
         const size_t lds1 = gemm_lds<1, 32>(FK > 0);
         int slots1 = 0;
-        if (int e = gemm_slots<1, 32, VEC, FK>(lds1, &slots1)) return e;
-        hipLaunchKernelGGL((k_cos_gemm<1, 32, VEC, FK>), dim3((unsigned)(ntx - xm) * (unsigned)cdiv(Q, 64)), dim3(256), lds1, st,
-                           qn, gal, ginv, S, Q, G, D, k, cand_val, cand_idx, xm, ntx, ntx - xm, (int)cdiv(Q, 64));
+        if (int e = gemm_slots<1, 32, VEC, FK, FILT>(lds1, &slots1)) return e;
+        if constexpr (FILT)
+            hipLaunchKernelGGL((k_cos_gemm_filt<1, 32, VEC, FK>), dim3((unsigned)(ntx - xm) * (unsigned)cdiv(Q, 64)), dim3(256), lds1,
+                               st, qn, gal, ginv, Q, G, D, k, cand_val, cand_idx, xm, ntx, ntx - xm, (int)cdiv(Q, 64), *filt);
+        else
+            hipLaunchKernelGGL((k_cos_gemm<1, 32, VEC, FK>), dim3((unsigned)(ntx - xm) * (unsigned)cdiv(Q, 64)), dim3(256), lds1, st,
+                               qn, gal, ginv, S, Q, G, D, k, cand_val, cand_idx, xm, ntx, ntx - xm, (int)cdiv(Q, 64));
         MI355_LAUNCH_CHECK();
     }
     return OK;
 }
 
 // split-bf16 loop: qs = the split planes of these Q queries (k_split_queries, whole 128-row tiles)
-template <int MT, int FK>
+template <int MT, int FK, bool FILT = false>
 static int launch_split(const bf16_t* qs, const float* gal, const float* ginv, float* S, int Q, i64 G, int D, int k,
-                        float* cand_val, int* cand_idx, hipStream_t st) {
+                        float* cand_val, int* cand_idx, hipStream_t st, const RankFilter* filt = nullptr) {
     constexpr int BM = 64 * MT;
     const size_t lds = split_lds<MT>(FK > 0);
     int slots = 0;
-    if (int e = split_slots<MT, FK>(lds, &slots)) return e;
+    if (int e = split_slots<MT, FK, FILT>(lds, &slots)) return e;
     const int ntx = cdiv(G, RK_BN), ny = cdiv(Q, BM), n_steps = cdiv(D, 16);
     const float* zeros = reinterpret_cast<const float*>(qs + (size_t)cdiv(Q, 128) * 4 * n_steps * 3 * 512);
     const int xm = MT == 2 ? whole_round_tiles(ntx, ny, slots) : ntx;
     if (xm > 0) {
-        hipLaunchKernelGGL((k_cos_gemm_split<MT, FK>), dim3((unsigned)xm * (unsigned)ny), dim3(256), lds, st, qs, gal, ginv,
-                           S, Q, G, D, k, cand_val, cand_idx, 0, ntx, n_steps, zeros, xm, ny);
+        if constexpr (FILT)
+            hipLaunchKernelGGL((k_cos_gemm_split_filt<MT, FK>), dim3((unsigned)xm * (unsigned)ny), dim3(256), lds, st, qs, gal, ginv,
+                               Q, G, D, k, cand_val, cand_idx, 0, ntx, n_steps, zeros, xm, ny, *filt);
+        else
+            hipLaunchKernelGGL((k_cos_gemm_split<MT, FK>), dim3((unsigned)xm * (unsigned)ny), dim3(256), lds, st, qs, gal, ginv,
+                               S, Q, G, D, k, cand_val, cand_idx, 0, ntx, n_steps, zeros, xm, ny);
         MI355_LAUNCH_CHECK();
     }
     if (xm < ntx) {
         const size_t lds1 = split_lds<1>(FK > 0);
         int slots1 = 0;
-        if (int e = split_slots<1, FK>(lds1, &slots1)) return e;
-        hipLaunchKernelGGL((k_cos_gemm_split<1, FK>), dim3((unsigned)(ntx - xm) * (unsigned)cdiv(Q, 64)), dim3(256), lds1,
-                           st, qs, gal, ginv, S, Q, G, D, k, cand_val, cand_idx, xm, ntx, n_steps, zeros, ntx - xm, (int)cdiv(Q, 64));
+        if (int e = split_slots<1, FK, FILT>(lds1, &slots1)) return e;
+        if constexpr (FILT)
+            hipLaunchKernelGGL((k_cos_gemm_split_filt<1, FK>), dim3((unsigned)(ntx - xm) * (unsigned)cdiv(Q, 64)), dim3(256), lds1,
+                               st, qs, gal, ginv, Q, G, D, k, cand_val, cand_idx, xm, ntx, n_steps, zeros, ntx - xm, (int)cdiv(Q, 64),
+                               *filt);
+        else
+            hipLaunchKernelGGL((k_cos_gemm_split<1, FK>), dim3((unsigned)(ntx - xm) * (unsigned)cdiv(Q, 64)), dim3(256), lds1,
+                               st, qs, gal, ginv, S, Q, G, D, k, cand_val, cand_idx, xm, ntx, n_steps, zeros, ntx - xm, (int)cdiv(Q, 64));
         MI355_LAUNCH_CHECK();
     }
     return OK;
@@ -1104,8 +906,14 @@ static int launch_split(const bf16_t* qs, const float* gal, const float* ginv, f
 
 template <int MT, int BK, bool VEC>
 static int launch_gemm_fk(const float* qn, const float* gal, const float* ginv, float* S, int Q, i64 G, int D, int k,
-                          float* cand_val, int* cand_idx, hipStream_t st) {
+                          float* cand_val, int* cand_idx, hipStream_t st, const RankFilter* filt = nullptr) {
     if (!cand_val) return launch_gemm<MT, BK, VEC, 0>(qn, gal, ginv, S, Q, G, D, 0, nullptr, nullptr, st);
+    if (filt) {
+        if (k <= 1) return launch_gemm<MT, BK, VEC, 1, true>(qn, gal, ginv, S, Q, G, D, k, cand_val, cand_idx, st, filt);
+        if (k <= 2) return launch_gemm<MT, BK, VEC, 2, true>(qn, gal, ginv, S, Q, G, D, k, cand_val, cand_idx, st, filt);
+        if (k <= 4) return launch_gemm<MT, BK, VEC, 4, true>(qn, gal, ginv, S, Q, G, D, k, cand_val, cand_idx, st, filt);
+        return launch_gemm<MT, BK, VEC, 8, true>(qn, gal, ginv, S, Q, G, D, k, cand_val, cand_idx, st, filt);
+    }
     if (k <= 1) return launch_gemm<MT, BK, VEC, 1>(qn, gal, ginv, S, Q, G, D, k, cand_val, cand_idx, st);
     if (k <= 2) return launch_gemm<MT, BK, VEC, 2>(qn, gal, ginv, S, Q, G, D, k, cand_val, cand_idx, st);
     if (k <= 4) return launch_gemm<MT, BK, VEC, 4>(qn, gal, ginv, S, Q, G, D, k, cand_val, cand_idx, st);
@@ -1113,8 +921,14 @@ static int launch_gemm_fk(const float* qn, const float* gal, const float* ginv, 
 }
 template <int MT>
 static int launch_split_fk(const bf16_t* qs, const float* gal, const float* ginv, float* S, int Q, i64 G, int D, int k,
-                           float* cand_val, int* cand_idx, hipStream_t st) {
+                           float* cand_val, int* cand_idx, hipStream_t st, const RankFilter* filt = nullptr) {
     if (!cand_val) return launch_split<MT, 0>(qs, gal, ginv, S, Q, G, D, 0, nullptr, nullptr, st);
+    if (filt) {
+        if (k <= 1) return launch_split<MT, 1, true>(qs, gal, ginv, S, Q, G, D, k, cand_val, cand_idx, st, filt);
+        if (k <= 2) return launch_split<MT, 2, true>(qs, gal, ginv, S, Q, G, D, k, cand_val, cand_idx, st, filt);
+        if (k <= 4) return launch_split<MT, 4, true>(qs, gal, ginv, S, Q, G, D, k, cand_val, cand_idx, st, filt);
+        return launch_split<MT, 8, true>(qs, gal, ginv, S, Q, G, D, k, cand_val, cand_idx, st, filt);
+    }
     if (k <= 1) return launch_split<MT, 1>(qs, gal, ginv, S, Q, G, D, k, cand_val, cand_idx, st);
     if (k <= 2) return launch_split<MT, 2>(qs, gal, ginv, S, Q, G, D, k, cand_val, cand_idx, st);
     if (k <= 4) return launch_split<MT, 4>(qs, gal, ginv, S, Q, G, D, k, cand_val, cand_idx, st);
@@ -1173,11 +987,15 @@ static bool rank_exact_f32() {
 
 // S != nullptr: score slab.  cand_val / cand_idx != nullptr: fused per-tile top-k lists [Q][cdiv(G,128)][k] (Q > 4 only).
 // qs: scratch for the split planes of these Q queries (split_queries_bytes(Q, D)); may be null for Q <= 4.
+// filt (fused selection only; a score slab is unfiltered): the filter of these Q queries.
 static int cos_gemm(const float* qn, bf16_t* qs, const float* gal, const float* ginv, float* S, i64 Q, i64 G, int D,
-                    hipStream_t st, int k = 0, float* cand_val = nullptr, int* cand_idx = nullptr) {
+                    hipStream_t st, int k = 0, float* cand_val = nullptr, int* cand_idx = nullptr,
+                    const RankFilter* filt = nullptr) {
     const bool vec = vec_ok(qn, D) && vec_ok(gal, D);
     const int q = (int)Q;
+    const int fused_bit = cand_val ? MI355_RANK_PATH_FUSED : 0;
     if (!cand_val && Q <= 4 && (size_t)Q * D * sizeof(float) <= 60 * 1024) {
+        set_rank_path(MI355_RANK_PATH_GEMV);
         const size_t lds = (size_t)Q * D * sizeof(float);
         const unsigned blocks = (unsigned)(cdiv(G, 4) < 4096 ? cdiv(G, 4) : 4096);
 #define GEMV_LAUNCH(NQ) hipLaunchKernelGGL((k_cos_gemv<NQ>), dim3(blocks), dim3(256), lds, st, qn, gal, ginv, S, G, D, (int)vec)
@@ -1190,18 +1008,20 @@ static int cos_gemm(const float* qn, bf16_t* qs, const float* gal, const float* 
         const int n_steps = cdiv(D, 16), n_frag = cdiv(q, 128) * 4 * n_steps;
         hipLaunchKernelGGL(k_split_queries, dim3((unsigned)cdiv(n_frag, 4)), dim3(256), 0, st, qn, qs, q, D, n_steps, n_frag);
         MI355_LAUNCH_CHECK();
-        if (Q > 64) return launch_split_fk<2>(qs, gal, ginv, S, q, G, D, k, cand_val, cand_idx, st);
-        return launch_split_fk<1>(qs, gal, ginv, S, q, G, D, k, cand_val, cand_idx, st);
+        set_rank_path(MI355_RANK_PATH_SPLIT | fused_bit);
+        if (Q > 64) return launch_split_fk<2>(qs, gal, ginv, S, q, G, D, k, cand_val, cand_idx, st, filt);
+        return launch_split_fk<1>(qs, gal, ginv, S, q, G, D, k, cand_val, cand_idx, st, filt);
     }
+    set_rank_path(MI355_RANK_PATH_EXACT_F32 | fused_bit);
     // Exact-fp32 loop.  Tile choice, measured on MI355X (tools/bench_rank.py, D = 1536): it plateaus at 95-110 TFLOP/s
     // for every tile shape, so what differs is the partial last round of tiles.  128-query tiles with BK = 16 keep two
     // workgroups on a CU (41 KB of staging, 68 KB with the fused selection's score tile): a lone workgroup in the last
     // round runs at full speed, which halves the wave-quantisation loss (Q = 256, G = 100k: 0.83 ms, against 0.95 ms
     // with 256 x 128 tiles, one per CU).
-    if (Q > 64) return vec ? launch_gemm_fk<2, 16, true>(qn, gal, ginv, S, q, G, D, k, cand_val, cand_idx, st)
-                           : launch_gemm_fk<2, 16, false>(qn, gal, ginv, S, q, G, D, k, cand_val, cand_idx, st);
-    return vec ? launch_gemm_fk<1, 32, true>(qn, gal, ginv, S, q, G, D, k, cand_val, cand_idx, st)
-               : launch_gemm_fk<1, 32, false>(qn, gal, ginv, S, q, G, D, k, cand_val, cand_idx, st);
+    if (Q > 64) return vec ? launch_gemm_fk<2, 16, true>(qn, gal, ginv, S, q, G, D, k, cand_val, cand_idx, st, filt)
+                           : launch_gemm_fk<2, 16, false>(qn, gal, ginv, S, q, G, D, k, cand_val, cand_idx, st, filt);
+    return vec ? launch_gemm_fk<1, 32, true>(qn, gal, ginv, S, q, G, D, k, cand_val, cand_idx, st, filt)
+               : launch_gemm_fk<1, 32, false>(qn, gal, ginv, S, q, G, D, k, cand_val, cand_idx, st, filt);
 }
 
 static int check_rank_args(const float* queries, i64 Q, const float* gallery, i64 G, int dim) {
@@ -1261,13 +1081,12 @@ int mi355_cosine_scores(const float* queries, int64_t Q, const float* gallery, i
     return OK;
 }
 
-int mi355_rank_topk(const float* queries, int64_t Q, const float* gallery, int64_t G, int dim,
-                    int gallery_is_normalized, int k, float eps, int64_t idx_offset, float* out_val,
-                    int64_t* out_idx, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int e = check_rank_args(queries, Q, gallery, G, dim)) return e;
-    MI355_REQUIRE(out_val && out_idx, "rank_topk: null output");
-    MI355_REQUIRE(k >= 1 && k <= LARGE_K, "rank_topk: k=%d outside [1,%d]", k, LARGE_K);
-    MI355_REQUIRE(k <= G, "rank_topk: k=%d exceeds gallery rows %lld", k, (long long)G);
+}  // extern "C"
+
+// mi355_rank_topk and, with filt, mi355_rank_topk_filtered (arguments checked by the caller)
+static int rank_topk(const float* queries, int64_t Q, const float* gallery, int64_t G, int dim, int gallery_is_normalized, int k,
+                     float eps, int64_t idx_offset, float* out_val, int64_t* out_idx, void* workspace, size_t workspace_bytes,
+                     void* stream, const RankFilter* filt) {
     hipStream_t st = (hipStream_t)stream;
     RankWs w = carve(workspace, Q, G, dim, k, !gallery_is_normalized);
     MI355_REQUIRE(workspace && workspace_bytes >= w.total, "rank_topk: workspace %zu < %zu bytes", workspace_bytes,
@@ -1290,23 +1109,76 @@ int mi355_rank_topk(const float* queries, int64_t Q, const float* gallery, int64
     const i64 ntiles = cdiv(G, RK_BN);
     for (i64 qs = 0; qs < Q; qs += qb) {
         const i64 qn = (Q - qs < qb) ? Q - qs : qb;
+        RankFilter fb{};
+        if (filt) fb = filter_from(*filt, qs);
+        const RankFilter* f = filt ? &fb : nullptr;
         if (fused) {
             // per-tile top-k straight from the GEMM's accumulators, then a merge of qn x ntiles x k candidates
             {
                 RoctxRange range("rank/cosine gemm + per-tile top-k");
-                if (int e = cos_gemm(w.qn + qs * dim, w.qs, gallery, ginv, nullptr, qn, G, dim, st, k, w.cand_val, w.cand_idx)) return e;
+                if (int e = cos_gemm(w.qn + qs * dim, w.qs, gallery, ginv, nullptr, qn, G, dim, st, k, w.cand_val, w.cand_idx, f)) return e;
             }
             RoctxRange range("rank/merge candidates");
             if (int e = topk_select(w.cand_val, nullptr, qn, ntiles * k, ntiles * k, k, idx_offset, out_val + qs * k,
-                                    (i64*)out_idx + qs * k, w.topk, w.topk_bytes, st, w.cand_idx))
+                                    (i64*)out_idx + qs * k, w.topk, w.topk_bytes, st, w.cand_idx, f))
                 return e;
             continue;
         }
         if (int e = cos_gemm(w.qn + qs * dim, w.qs, gallery, ginv, w.S, qn, G, dim, st)) return e;
+        if (k > SMALL_K) set_rank_path(g_rank_path | MI355_RANK_PATH_BITONIC);
         if (int e = topk_select(w.S, nullptr, qn, G, G, k, idx_offset, out_val + qs * k, (i64*)out_idx + qs * k,
-                                w.topk, w.topk_bytes, st))
+                                w.topk, w.topk_bytes, st, nullptr, f))
             return e;
     }
+    return OK;
+}
+
+extern "C" {
+
+int mi355_rank_topk(const float* queries, int64_t Q, const float* gallery, int64_t G, int dim,
+                    int gallery_is_normalized, int k, float eps, int64_t idx_offset, float* out_val,
+                    int64_t* out_idx, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int e = check_rank_args(queries, Q, gallery, G, dim)) return e;
+    MI355_REQUIRE(out_val && out_idx, "rank_topk: null output");
+    MI355_REQUIRE(k >= 1 && k <= LARGE_K, "rank_topk: k=%d outside [1,%d]", k, LARGE_K);
+    MI355_REQUIRE(k <= G, "rank_topk: k=%d exceeds gallery rows %lld", k, (long long)G);
+    return rank_topk(queries, Q, gallery, G, dim, gallery_is_normalized, k, eps, idx_offset, out_val, out_idx, workspace,
+                     workspace_bytes, stream, nullptr);
+}
+
+int mi355_rank_topk_filtered(const float* queries, int64_t Q, const float* gallery, int64_t G, int dim,
+                             int gallery_is_normalized, int k, float eps, int64_t idx_offset, const mi355_rank_filter* filter,
+                             float* out_val, int64_t* out_idx, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int e = check_rank_args(queries, Q, gallery, G, dim)) return e;
+    MI355_REQUIRE(out_val && out_idx, "rank_topk_filtered: null output");
+    MI355_REQUIRE(k >= 1 && k <= LARGE_K, "rank_topk_filtered: k=%d outside [1,%d]", k, LARGE_K);
+    MI355_REQUIRE(k <= G, "rank_topk_filtered: k=%d exceeds gallery rows %lld", k, (long long)G);
+    RankFilter f{};
+    if (int e = make_filter(filter, idx_offset, "rank_topk_filtered", &f)) return e;
+    return rank_topk(queries, Q, gallery, G, dim, gallery_is_normalized, k, eps, idx_offset, out_val, out_idx, workspace,
+                     workspace_bytes, stream, &f);
+}
+
+int mi355_rank_last_path(void) { return g_rank_path; }
+
+int mi355_clear_pads(float* val, int64_t* idx, int64_t n, int64_t lo, int64_t hi, void* stream) {
+    MI355_REQUIRE(val && idx, "clear_pads: null pointer");
+    MI355_REQUIRE(n >= 0, "clear_pads: n=%lld < 0", (long long)n);
+    if (n == 0) return OK;
+    hipLaunchKernelGGL(k_clear_pads, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, val, (i64*)idx, (i64)n,
+                       (i64)lo, (i64)hi);
+    MI355_LAUNCH_CHECK();
+    return OK;
+}
+
+int mi355_retrieval_metrics(const int64_t* idx, int64_t Q, int k, const int64_t* query_cls, const int64_t* gallery_cls,
+                            int64_t G, const int64_t* R, double* per_query, void* stream) {
+    MI355_REQUIRE(idx && query_cls && gallery_cls && R && per_query, "retrieval_metrics: null pointer");
+    MI355_REQUIRE(Q >= 1 && G >= 1, "retrieval_metrics: bad shape Q=%lld G=%lld", (long long)Q, (long long)G);
+    MI355_REQUIRE(k >= 1 && k <= LARGE_K, "retrieval_metrics: k=%d outside [1,%d]", k, LARGE_K);
+    hipLaunchKernelGGL(k_retrieval_metrics, dim3((unsigned)cdiv(Q, 4)), dim3(256), 0, (hipStream_t)stream, (const i64*)idx, (i64)Q,
+                       k, (const i64*)query_cls, (const i64*)gallery_cls, (i64)G, (const i64*)R, per_query);
+    MI355_LAUNCH_CHECK();
     return OK;
 }
 
@@ -1360,6 +1232,7 @@ int mi355_rank_topk_prepared(const float* queries, int64_t Q, const void* galler
             const int n_frag = cdiv(qn, 128) * 4 * n_steps;
             hipLaunchKernelGGL(k_split_queries, dim3((unsigned)cdiv(n_frag, 4)), dim3(256), 0, st, w.qn + qs * dim, w.qs, (int)qn, dim, n_steps, n_frag);
             MI355_LAUNCH_CHECK();
+            set_rank_path(MI355_RANK_PATH_PREPARED | MI355_RANK_PATH_FUSED);
             const int e = qn > 64 ? launch_pre_fk<2>(w.qs, (const bf16_t*)gallery_planes, (int)qn, G, dim, k, w.cand_val, w.cand_idx, st)
                                   : launch_pre_fk<1>(w.qs, (const bf16_t*)gallery_planes, (int)qn, G, dim, k, w.cand_val, w.cand_idx, st);
             if (e) return e;

@@ -3,6 +3,7 @@
 // merges what the epilogue leaves.  gfx950 only.
 #pragma once
 #include "common.h"
+#include "../../include/mi355_retrieval.h"
 
 #include <limits.h>
 #include <math.h>
@@ -32,6 +33,29 @@ __device__ __forceinline__ float key_score(unsigned key) {
 
 constexpr int RK_BN = 128;
 
+// Eligibility filter of the filtered searches (mi355_rank_filter): row j of a search with idx_offset is left out for query q
+// when exclude[q] == j + idx_offset, or when the label mode rejects gallery_labels[j] against query_labels[q].  qlab / excl
+// point at the first query of the call they are handed to (the host shifts them per query block).
+struct RankFilter {
+    const i64* qlab;      // [Q]; null in MI355_LABEL_ANY
+    const i64* glab;      // [G]; null in MI355_LABEL_ANY
+    const i64* excl;      // [Q] global row indices (< 0: none), or null
+    i64 idx_offset;
+    int mode;             // MI355_LABEL_*
+};
+// The query's side of the filter: its label and the LOCAL row it excludes (-1: none; a row of another shard never matches)
+__device__ __forceinline__ void query_filter(const RankFilter& f, i64 q, i64& lab, i64& ex) {
+    lab = f.mode != MI355_LABEL_ANY ? f.qlab[q] : 0;
+    const i64 e = f.excl ? f.excl[q] : -1;
+    ex = e >= 0 ? e - f.idx_offset : -1;
+}
+__device__ __forceinline__ bool eligible(int mode, i64 qlab, i64 glab, i64 ex, i64 j) {
+    const bool lab_ok = mode == MI355_LABEL_ANY || ((glab == qlab) == (mode == MI355_LABEL_SAME));
+    return lab_ok && j != ex;
+}
+constexpr int FILT_LABELS_LD = RK_BN + RK_BN / 32;   // the tile's gallery labels in LDS: one i64 of padding per 32
+constexpr size_t FILT_LABELS_BYTES = FILT_LABELS_LD * sizeof(i64);
+
 // 16 bytes per lane from global memory straight into LDS (lane-linear destination; no register is written)
 __device__ __forceinline__ void glds16(const bf16_t* gsrc, bf16_t* lds_dst) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
@@ -59,10 +83,15 @@ __device__ __forceinline__ void rank_tile_of(int L, int ntiles, int ny, int& tx,
 // Epilogue shared by the exact-fp32 and the split-bf16 loops (same accumulator layout: the C/D map of the 32x32 MFMAs does
 // not depend on the input type): FK = 0 writes the score slab, FK > 0 selects per-tile candidates.  Called after a
 // __syncthreads() that retired every read of the staging buffers (smem is reused).
-template <int MT, int FK>
+// FILT (FK > 0 only): columns the filter rejects enter the selection as key 0, i.e. never.  The tile's 128 gallery labels are
+// read once per workgroup into LDS behind the transposed tile (64 x 132 floats + 1 KB stays inside every loop's staging
+// buffers, so the LDS request and the resident workgroups per CU are those of the unfiltered kernel).
+template <int MT, int FK, bool FILT = false>
 __device__ __forceinline__ void cos_gemm_epilogue(f32x16 (&acc)[MT][2], float* smem, const float* __restrict__ ginv,
                                                   float* __restrict__ S, int Q, i64 G, int k, float* __restrict__ cand_val,
-                                                  int* __restrict__ cand_idx, int x0, int ntx, i64 n0, int m0) {
+                                                  int* __restrict__ cand_idx, int x0, int ntx, i64 n0, int m0,
+                                                  const RankFilter& flt = RankFilter{}) {
+    static_assert(!FILT || FK > 0, "the filter applies to the fused selection");
     constexpr int BM = 64 * MT;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1, lr = lane & 31;
@@ -73,6 +102,10 @@ __device__ __forceinline__ void cos_gemm_epilogue(f32x16 (&acc)[MT][2], float* s
         constexpr int CLD = RK_BN + 4;                 // 132 floats: a thread per row reads float4s conflict-free
         float* Ct = smem;                              // [64][CLD]
         const i64 ncol = (G - n0 < RK_BN) ? G - n0 : RK_BN;     // valid columns of this tile
+        i64* glab = reinterpret_cast<i64*>(smem + 64 * CLD);    // FILT: [4][33], label of column c at c + c / 32
+        if constexpr (FILT) {
+            if (tid < RK_BN) glab[tid + (tid >> 5)] = (flt.mode != MI355_LABEL_ANY && tid < ncol) ? flt.glab[n0 + tid] : 0;
+        }
 #pragma unroll 1
         for (int h = 0; h < BM / 64; ++h) {
             if ((wm * MT * 32) / 64 == h) {            // this wave's rows belong to pass h
@@ -114,6 +147,10 @@ __device__ __forceinline__ void cos_gemm_epilogue(f32x16 (&acc)[MT][2], float* s
                     ki[0] = g[0] ? id : ki[0];
                 };
                 const float* rowp = Ct + lrow * CLD + part * 32;
+                i64 fq_lab = 0, fq_ex = -1;
+                if constexpr (FILT) {
+                    if (m0 + h * 64 + lrow < Q) query_filter(flt, m0 + h * 64 + lrow, fq_lab, fq_ex);
+                }
 #pragma unroll 2
                 for (int c4i = 0; c4i < 8; ++c4i) {
                     const f32x4 v4 = *reinterpret_cast<const f32x4*>(rowp + c4i * 4);
@@ -123,6 +160,9 @@ __device__ __forceinline__ void cos_gemm_epilogue(f32x16 (&acc)[MT][2], float* s
                         const int c = part * 32 + c4i * 4 + e;
                         unsigned key = score_key(vv[e]);
                         if (c >= ncol) key = 0u;
+                        if constexpr (FILT) {
+                            if (!eligible(flt.mode, fq_lab, glab[c + part], fq_ex, n0 + c)) key = 0u;
+                        }
                         if (__any(key > kv[FK - 1])) insert(key, (int)n0 + c);      // n0 + c < 2^31 (checked on the host)
                     }
                 }
@@ -193,8 +233,17 @@ constexpr int LARGE_K = 1024;       // largest k of any search
 size_t topk_ws_bytes(i64 Q, i64 G, int k);
 // Top-k of each row of vals[Q][rowlen] (implicit indices j + idx_offset, explicit int64 idxs, or the fused epilogue's int32
 // local indices idxs32 with IDX32_PAD = missing) into out_val / out_idx [Q][k].
+// filt (filtered searches): with implicit indices the first level reads an ineligible candidate as a pad; either way the
+// pads left in the output (fewer than k eligible rows) become (-inf, -1).
 int topk_select(const float* vals, const i64* idxs, i64 Q, i64 rowlen, i64 in_stride, int k, i64 idx_offset, float* out_val,
-                i64* out_idx, void* ws, size_t ws_bytes, hipStream_t st, const int* idxs32 = nullptr);
+                i64* out_idx, void* ws, size_t ws_bytes, hipStream_t st, const int* idxs32 = nullptr,
+                const RankFilter* filt = nullptr);
+// The filter of the query block starting at query q0
+RankFilter filter_from(const RankFilter& f, i64 q0);
+// Checks a mi355_rank_filter and turns it into a RankFilter for a search with idx_offset
+int make_filter(const mi355_rank_filter* f, i64 idx_offset, const char* who, RankFilter* out);
+// Which branch the calling thread's last search took (mi355_rank_last_path)
+void set_rank_path(int path);
 // Whether a (Q, G, k) search selects inside the GEMM epilogue (k <= SMALL_K, Q > 4), and how many queries one GEMM call
 // takes so that the candidate lists / the score slab stay bounded.
 bool fused_select(i64 Q, i64 G, int k);

@@ -104,121 +104,17 @@ __global__ __launch_bounds__(256) void k_cos_gemm_f16(const f16* __restrict__ Qs
                                                       float* __restrict__ S, int Q, i64 G, int ld, int k,
                                                       float* __restrict__ cand_val, int* __restrict__ cand_idx, int x0, int ntx,
                                                       int xtiles, int ny) {
-    constexpr int BM = 64 * MT;
-    constexpr int A_PIECES = (BM / 32) * 8;           // 1 KB pieces per stage: 4 sub-steps x 2 planes per row block
-    constexpr int A_STAGE = A_PIECES * 512;           // f16 elements per stage
-    constexpr int B_STAGE = RK_BN * F16_KSTEP;        // f16 elements per stage (16 KB)
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    f16* As = reinterpret_cast<f16*>(smem);           // [2][BM/32][4][2][512]
-    f16* Bs = As + 2 * A_STAGE;                       // [3][128][64], chunks swizzled
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1, lr = lane & 31;
-    int bx, by;
-    rank_tile_of((int)blockIdx.x, xtiles, ny, bx, by);
-    const i64 n0 = (i64)(bx + x0) * RK_BN;
-    const int m0 = by * BM;
-    const int swave = __builtin_amdgcn_readfirstlane(wave);
-    const int n_steps = ld / F16_KSTEP, n_sub = ld / 16;
-
-    // B: wave w moves pieces 4w .. 4w + 3; lane -> row 8 * piece + lane / 8, LDS position lane % 8
-    const f16* b_src[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int r = (swave * 4 + i) * 8 + (lane >> 3);
-        const int c = (lane & 7) ^ ((r >> 1) & 7);
-        const i64 g = n0 + r < G ? n0 + r : G - 1;
-        b_src[i] = Gal + g * ld + c * 8;
-    }
-    // (k-steps past the end re-read the last one: the data is never used, the count of pieces in flight stays uniform)
-    auto dma_b = [&](int stage, int t) {
-        const int tt = t < n_steps ? t : n_steps - 1;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            glds16(reinterpret_cast<const bf16_t*>(b_src[i] + tt * F16_KSTEP),
-                   reinterpret_cast<bf16_t*>(Bs + stage * B_STAGE + (swave * 4 + i) * 512));
-    };
-    // A: piece p = (row block p / 8, sub-step (p % 8) / 2, plane p % 2) of k-step t sits at
-    // Qs + ((m0/32 + p/8) * n_sub + 4t) * 1024 + (p % 8) * 512; wave w moves pieces w, w + 4, ...
-    const f16* a_src[A_PIECES / 4];
-#pragma unroll
-    for (int i = 0; i < A_PIECES / 4; ++i) {
-        const int p = swave + 4 * i;
-        a_src[i] = Qs + ((size_t)(m0 / 32 + p / 8) * n_sub) * 1024 + (p % 8) * 512 + lane * 8;
-    }
-    auto dma_a = [&](int buf, int t) {
-#pragma unroll
-        for (int i = 0; i < A_PIECES / 4; ++i)
-            glds16(reinterpret_cast<const bf16_t*>(a_src[i] + (size_t)t * 4 * 1024),
-                   reinterpret_cast<bf16_t*>(As + buf * A_STAGE + (swave + 4 * i) * 512));
-    };
-
-    f32x16 acc[MT][2], acc_lo[MT][2];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) { acc[i][j][e] = 0.f; acc_lo[i][j][e] = 0.f; }
-
-    // B fragment reads: row r = wn * 64 + j * 32 + lr, chunk 2s + (lane >> 5) of sub-step s at its swizzled position
-    int b_off[2][4];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int r = wn * 64 + j * 32 + lr;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) b_off[j][s] = r * F16_KSTEP + (((2 * s + (lane >> 5)) ^ ((r >> 1) & 7)) << 3);
-    }
-    auto compute = [&](int abuf, int bstage) {
-        const f16* a = As + abuf * A_STAGE + (wm * MT) * 8 * 512 + lane * 8;
-        const f16* b = Bs + bstage * B_STAGE;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            f16x8 bf[2], ah[MT], al[MT];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) bf[j] = *reinterpret_cast<const f16x8*>(b + b_off[j][s]);
-#pragma unroll
-            for (int i = 0; i < MT; ++i) {
-                ah[i] = *reinterpret_cast<const f16x8*>(a + (i * 8 + s * 2) * 512);
-                al[i] = *reinterpret_cast<const f16x8*>(a + (i * 8 + s * 2 + 1) * 512);
-            }
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    acc_lo[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bf[j], acc_lo[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bf[j], acc[i][j], 0, 0, 0);
-                }
-        }
-    };
-
-    dma_a(0, 0);
-    dma_b(0, 0);
-    dma_b(1, 1);
-    __syncthreads();                   // drains vmcnt: everything has landed
-
-    int bs_cur = 0, bs_far = 2;        // B stage of k-step t / of k-step t + 2
-    for (int t = 0; t < n_steps; ++t) {
-        if (t + 1 < n_steps) dma_a((t & 1) ^ 1, t + 1);   // everybody left this buffer at the previous barrier
-        __builtin_amdgcn_sched_barrier(0);                // (the count below needs the A pieces issued BEFORE the B pieces)
-        dma_b(bs_far, t + 2);
-        __builtin_amdgcn_sched_barrier(0);
-        compute(t & 1, bs_cur);
-        asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); // A(t+1) and B(t+1) have landed; the four B(t+2) pieces stay in flight
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        bs_cur = bs_cur == 2 ? 0 : bs_cur + 1;
-        bs_far = bs_far == 2 ? 0 : bs_far + 1;
-    }
-    __syncthreads();                   // the last look-ahead pieces have landed before the epilogue reuses the LDS
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = __builtin_fmaf(acc_lo[i][j][e], F16_LO_UNSCALE, acc[i][j][e]);
-    cos_gemm_epilogue<MT, FK>(acc, smem, nullptr, S, Q, G, k, cand_val, cand_idx, x0, ntx, n0, m0);
+    constexpr bool FILT = false;
+    const RankFilter flt{};
+#include "rank_gemm_f16.inc"
+}
+template <int MT, int FK>
+__global__ __launch_bounds__(256) void k_cos_gemm_f16_filt(const f16* __restrict__ Qs, const f16* __restrict__ Gal, int Q, i64 G,
+                                                           int ld, int k, float* __restrict__ cand_val, int* __restrict__ cand_idx,
+                                                           int x0, int ntx, int xtiles, int ny, RankFilter flt) {
+    constexpr bool FILT = true;
+    float* const S = nullptr;
+#include "rank_gemm_f16.inc"
 }
 
 // =====================================================================================
@@ -309,47 +205,66 @@ static F16Ws carve_f16(void* ws, i64 Q, i64 G, int D, int k) {
 }
 
 template <int MT>
+constexpr size_t f16_stage_bytes() { return (size_t)2 * (64 * MT / 32) * 8 * 1024 + (size_t)3 * RK_BN * F16_KSTEP * 2; }   // A ring of 2, B ring of 3
+// the filtered epilogue's score tile + gallery labels stay inside the staging buffers: same LDS request as unfiltered
+static_assert(f16_stage_bytes<1>() >= (size_t)64 * (RK_BN + 4) * sizeof(float) + FILT_LABELS_BYTES, "filtered epilogue grows the LDS");
+template <int MT>
 static size_t f16_lds(bool fk) {
-    const size_t stage = (size_t)2 * (64 * MT / 32) * 8 * 1024 + (size_t)3 * RK_BN * F16_KSTEP * 2;   // A ring of 2, B ring of 3
+    const size_t stage = f16_stage_bytes<MT>();
     const size_t tile = fk ? (size_t)64 * (RK_BN + 4) * sizeof(float) : 0;
     return stage > tile ? stage : tile;
 }
-template <int MT, int FK>
+template <int MT, int FK, bool FILT = false>
 static int f16_slots(size_t lds, int* slots_out) {
     static int slots[MI355_MAX_DEVICES] = {0};
-    return kernel_slots((const void*)k_cos_gemm_f16<MT, FK>, lds, slots, slots_out);
+    if constexpr (FILT) return kernel_slots((const void*)k_cos_gemm_f16_filt<MT, FK>, lds, slots, slots_out);
+    else return kernel_slots((const void*)k_cos_gemm_f16<MT, FK>, lds, slots, slots_out);
 }
 
 // Whole rounds of 128-query tiles in one launch, the remaining column tiles as 64-query tiles (every score is the same:
 // same column tiles, same k order), as launch_split does.
-template <int MT, int FK>
+template <int MT, int FK, bool FILT = false>
 static int launch_f16(const f16* qs, const f16* gal, float* S, int Q, i64 G, int ld, int k, float* cand_val, int* cand_idx,
-                      hipStream_t st) {
+                      hipStream_t st, const RankFilter* filt = nullptr) {
     constexpr int BM = 64 * MT;
     const size_t lds = f16_lds<MT>(FK > 0);
     int slots = 0;
-    if (int e = f16_slots<MT, FK>(lds, &slots)) return e;
+    if (int e = f16_slots<MT, FK, FILT>(lds, &slots)) return e;
     const int ntx = cdiv(G, RK_BN), ny = cdiv(Q, BM);
     const int xm = MT == 2 ? whole_round_tiles(ntx, ny, slots) : ntx;
     if (xm > 0) {
-        hipLaunchKernelGGL((k_cos_gemm_f16<MT, FK>), dim3((unsigned)xm * (unsigned)ny), dim3(256), lds, st, qs, gal, S, Q, G, ld,
-                           k, cand_val, cand_idx, 0, ntx, xm, ny);
+        if constexpr (FILT)
+            hipLaunchKernelGGL((k_cos_gemm_f16_filt<MT, FK>), dim3((unsigned)xm * (unsigned)ny), dim3(256), lds, st, qs, gal, Q, G, ld,
+                               k, cand_val, cand_idx, 0, ntx, xm, ny, *filt);
+        else
+            hipLaunchKernelGGL((k_cos_gemm_f16<MT, FK>), dim3((unsigned)xm * (unsigned)ny), dim3(256), lds, st, qs, gal, S, Q, G, ld,
+                               k, cand_val, cand_idx, 0, ntx, xm, ny);
         MI355_LAUNCH_CHECK();
     }
     if (xm < ntx) {
         const size_t lds1 = f16_lds<1>(FK > 0);
         int slots1 = 0;
-        if (int e = f16_slots<1, FK>(lds1, &slots1)) return e;
-        hipLaunchKernelGGL((k_cos_gemm_f16<1, FK>), dim3((unsigned)(ntx - xm) * (unsigned)cdiv(Q, 64)), dim3(256), lds1, st, qs,
-                           gal, S, Q, G, ld, k, cand_val, cand_idx, xm, ntx, ntx - xm, (int)cdiv(Q, 64));
+        if (int e = f16_slots<1, FK, FILT>(lds1, &slots1)) return e;
+        if constexpr (FILT)
+            hipLaunchKernelGGL((k_cos_gemm_f16_filt<1, FK>), dim3((unsigned)(ntx - xm) * (unsigned)cdiv(Q, 64)), dim3(256), lds1, st,
+                               qs, gal, Q, G, ld, k, cand_val, cand_idx, xm, ntx, ntx - xm, (int)cdiv(Q, 64), *filt);
+        else
+            hipLaunchKernelGGL((k_cos_gemm_f16<1, FK>), dim3((unsigned)(ntx - xm) * (unsigned)cdiv(Q, 64)), dim3(256), lds1, st, qs,
+                               gal, S, Q, G, ld, k, cand_val, cand_idx, xm, ntx, ntx - xm, (int)cdiv(Q, 64));
         MI355_LAUNCH_CHECK();
     }
     return OK;
 }
 template <int MT>
 static int launch_f16_fk(const f16* qs, const f16* gal, float* S, int Q, i64 G, int ld, int k, float* cand_val, int* cand_idx,
-                         hipStream_t st) {
+                         hipStream_t st, const RankFilter* filt = nullptr) {
     if (!cand_val) return launch_f16<MT, 0>(qs, gal, S, Q, G, ld, 0, nullptr, nullptr, st);
+    if (filt) {
+        if (k <= 1) return launch_f16<MT, 1, true>(qs, gal, S, Q, G, ld, k, cand_val, cand_idx, st, filt);
+        if (k <= 2) return launch_f16<MT, 2, true>(qs, gal, S, Q, G, ld, k, cand_val, cand_idx, st, filt);
+        if (k <= 4) return launch_f16<MT, 4, true>(qs, gal, S, Q, G, ld, k, cand_val, cand_idx, st, filt);
+        return launch_f16<MT, 8, true>(qs, gal, S, Q, G, ld, k, cand_val, cand_idx, st, filt);
+    }
     if (k <= 1) return launch_f16<MT, 1>(qs, gal, S, Q, G, ld, k, cand_val, cand_idx, st);
     if (k <= 2) return launch_f16<MT, 2>(qs, gal, S, Q, G, ld, k, cand_val, cand_idx, st);
     if (k <= 4) return launch_f16<MT, 4>(qs, gal, S, Q, G, ld, k, cand_val, cand_idx, st);
@@ -386,19 +301,26 @@ size_t mi355_rank_f16_workspace_bytes(int64_t Q, int64_t G, int dim, int k) {
     return carve_f16(nullptr, Q, G, dim, k).total;
 }
 
-int mi355_rank_topk_f16(const float* queries, int64_t Q, const void* gallery_f16, int64_t G, int dim, int k, float eps,
-                        int64_t idx_offset, float* out_val, int64_t* out_idx, void* workspace, size_t workspace_bytes,
-                        void* stream) {
-    MI355_REQUIRE(queries && gallery_f16 && out_val && out_idx, "rank_topk_f16: null pointer");
-    MI355_REQUIRE(Q >= 0 && G >= 1 && dim >= 1, "rank_topk_f16: bad shape Q=%lld G=%lld dim=%d", (long long)Q, (long long)G, dim);
-    MI355_REQUIRE(k >= 1 && k <= LARGE_K && k <= G, "rank_topk_f16: k=%d outside [1, %lld]", k,
+}  // extern "C"
+
+// mi355_rank_topk_f16 and, with filt, mi355_rank_topk_f16_filtered: checks its arguments under the name who
+static int rank_topk_f16(const float* queries, int64_t Q, const void* gallery_f16, int64_t G, int dim, int k, float eps,
+                         int64_t idx_offset, float* out_val, int64_t* out_idx, void* workspace, size_t workspace_bytes,
+                         void* stream, const mi355_rank_filter* filter, const char* who) {
+    MI355_REQUIRE(queries && gallery_f16 && out_val && out_idx, "%s: null pointer", who);
+    MI355_REQUIRE(Q >= 0 && G >= 1 && dim >= 1, "%s: bad shape Q=%lld G=%lld dim=%d", who, (long long)Q, (long long)G, dim);
+    MI355_REQUIRE(k >= 1 && k <= LARGE_K && k <= G, "%s: k=%d outside [1, %lld]", who, k,
                   (long long)(G < LARGE_K ? G : LARGE_K));
-    MI355_REQUIRE(((uintptr_t)gallery_f16 & 15) == 0, "rank_topk_f16: gallery buffer must be 16-byte aligned");
-    MI355_REQUIRE(Q <= INT_MAX && G <= ((int64_t)1 << 40), "rank_topk_f16: shape too large Q=%lld G=%lld", (long long)Q,
+    MI355_REQUIRE(((uintptr_t)gallery_f16 & 15) == 0, "%s: gallery buffer must be 16-byte aligned", who);
+    MI355_REQUIRE(Q <= INT_MAX && G <= ((int64_t)1 << 40), "%s: shape too large Q=%lld G=%lld", who, (long long)Q,
                   (long long)G);
+    RankFilter fall{};
+    if (filter)
+        if (int e = make_filter(filter, idx_offset, who, &fall)) return e;
+    const RankFilter* filt = filter ? &fall : nullptr;
     if (Q == 0) return OK;
     const F16Ws w = carve_f16(workspace, Q, G, dim, k);
-    MI355_REQUIRE(workspace && workspace_bytes >= w.total, "rank_topk_f16: workspace %zu < %zu bytes", workspace_bytes, w.total);
+    MI355_REQUIRE(workspace && workspace_bytes >= w.total, "%s: workspace %zu < %zu bytes", who, workspace_bytes, w.total);
     hipStream_t st = (hipStream_t)stream;
     const f16* gal = (const f16*)gallery_f16;
     const int ld = f16_ld(dim);
@@ -416,33 +338,55 @@ int mi355_rank_topk_f16(const float* queries, int64_t Q, const void* gallery_f16
 #undef GEMV_F16
             MI355_LAUNCH_CHECK();
         }
+        set_rank_path(MI355_RANK_PATH_F16_GEMV | (k > SMALL_K ? MI355_RANK_PATH_BITONIC : 0));
         RoctxRange range("rank/top-k");
-        return topk_select(w.S, nullptr, Q, G, G, k, idx_offset, out_val, (i64*)out_idx, w.topk, w.topk_bytes, st);
+        return topk_select(w.S, nullptr, Q, G, G, k, idx_offset, out_val, (i64*)out_idx, w.topk, w.topk_bytes, st, nullptr, filt);
     }
     const i64 qb = query_block(Q, G, k);
     const bool fused = fused_select(Q, G, k);
     const i64 ntiles = cdiv(G, RK_BN);
     const int n_sub = ld / 16;
+    set_rank_path(MI355_RANK_PATH_F16_GEMM | (fused ? MI355_RANK_PATH_FUSED : k > SMALL_K ? MI355_RANK_PATH_BITONIC : 0));
     for (i64 q0 = 0; q0 < Q; q0 += qb) {
         const i64 qn = (Q - q0 < qb) ? Q - q0 : qb;
+        RankFilter fb{};
+        if (filt) fb = filter_from(*filt, q0);
+        const RankFilter* f = filt ? &fb : nullptr;
         {
             RoctxRange range(fused ? "rank/cosine gemm (fp16 gallery) + per-tile top-k" : "rank/cosine gemm (fp16 gallery)");
             const int n_frag = cdiv(qn, 128) * 4 * n_sub;
             hipLaunchKernelGGL(k_split_queries_f16, dim3((unsigned)cdiv(n_frag, 4)), dim3(256), 0, st, w.qn + q0 * dim, w.qs,
                                (int)qn, dim, n_sub, n_frag);
             MI355_LAUNCH_CHECK();
-            const int e = qn > 64 ? launch_f16_fk<2>(w.qs, gal, w.S, (int)qn, G, ld, k, w.cand_val, w.cand_idx, st)
-                                  : launch_f16_fk<1>(w.qs, gal, w.S, (int)qn, G, ld, k, w.cand_val, w.cand_idx, st);
+            const int e = qn > 64 ? launch_f16_fk<2>(w.qs, gal, w.S, (int)qn, G, ld, k, w.cand_val, w.cand_idx, st, f)
+                                  : launch_f16_fk<1>(w.qs, gal, w.S, (int)qn, G, ld, k, w.cand_val, w.cand_idx, st, f);
             if (e) return e;
         }
         RoctxRange range(fused ? "rank/merge candidates" : "rank/top-k");
         const int e = fused ? topk_select(w.cand_val, nullptr, qn, ntiles * k, ntiles * k, k, idx_offset, out_val + q0 * k,
-                                          (i64*)out_idx + q0 * k, w.topk, w.topk_bytes, st, w.cand_idx)
+                                          (i64*)out_idx + q0 * k, w.topk, w.topk_bytes, st, w.cand_idx, f)
                             : topk_select(w.S, nullptr, qn, G, G, k, idx_offset, out_val + q0 * k, (i64*)out_idx + q0 * k, w.topk,
-                                          w.topk_bytes, st);
+                                          w.topk_bytes, st, nullptr, f);
         if (e) return e;
     }
     return OK;
+}
+
+extern "C" {
+
+int mi355_rank_topk_f16(const float* queries, int64_t Q, const void* gallery_f16, int64_t G, int dim, int k, float eps,
+                        int64_t idx_offset, float* out_val, int64_t* out_idx, void* workspace, size_t workspace_bytes,
+                        void* stream) {
+    return rank_topk_f16(queries, Q, gallery_f16, G, dim, k, eps, idx_offset, out_val, out_idx, workspace, workspace_bytes, stream,
+                         nullptr, "rank_topk_f16");
+}
+
+int mi355_rank_topk_f16_filtered(const float* queries, int64_t Q, const void* gallery_f16, int64_t G, int dim, int k, float eps,
+                                 int64_t idx_offset, const mi355_rank_filter* filter, float* out_val, int64_t* out_idx,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+    MI355_REQUIRE(filter, "rank_topk_f16_filtered: null filter (use the unfiltered entry)");
+    return rank_topk_f16(queries, Q, gallery_f16, G, dim, k, eps, idx_offset, out_val, out_idx, workspace, workspace_bytes, stream,
+                         filter, "rank_topk_f16_filtered");
 }
 
 }  // extern "C"

@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import torch
 
-from ._lib import MI355Error, check, lib, require_cuda, stream_ptr
+from ._lib import LABEL_ANY, LABEL_DIFFERENT, LABEL_SAME, MI355Error, RankFilter, check, lib, require_cuda, stream_ptr
 
 _EPS = 1e-6
 
@@ -99,18 +99,66 @@ def cosine_scores(queries: torch.Tensor, gallery: torch.Tensor, eps: float = _EP
     return out
 
 
+_LABEL_MODES = {None: LABEL_ANY, "same": LABEL_SAME, "different": LABEL_DIFFERENT}
+
+
+def _int64_on(t, name: str, n: int, device) -> torch.Tensor:
+    if not torch.is_tensor(t):
+        raise MI355Error(f"{name} must be a tensor")
+    require_cuda(t, name)
+    if t.device != torch.device(device):
+        raise MI355Error(f"{name} is on {t.device} but the search runs on {device}")
+    if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+        raise MI355Error(f"{name} must hold integers, got {t.dtype}")
+    if t.dim() != 1 or t.shape[0] != n:
+        raise MI355Error(f"{name} must have shape ({n},), got {tuple(t.shape)}")
+    return t.to(torch.int64).contiguous()
+
+
+def _rank_filter(Q: int, G: int, device, query_labels, gallery_labels, label_filter, exclude):
+    """The mi355_rank_filter of a filtered search, and the int64 tensors it points at (kept alive by the caller), or
+    None when no filter argument is given (the unfiltered search runs, exactly as before)."""
+    if label_filter not in _LABEL_MODES:
+        raise MI355Error(f'label_filter must be None, "same" or "different", got {label_filter!r}')
+    if label_filter is None and exclude is None:
+        return None
+    keep = []
+    f = RankFilter()
+    f.label_mode = _LABEL_MODES[label_filter]
+    if label_filter is not None:
+        if query_labels is None or gallery_labels is None:
+            raise MI355Error(f'label_filter="{label_filter}" needs query_labels and gallery labels')
+        ql = _int64_on(query_labels, "query_labels", Q, device)
+        gl = _int64_on(gallery_labels, "gallery_labels", G, device)
+        keep += [ql, gl]
+        f.query_labels, f.gallery_labels = ql.data_ptr(), gl.data_ptr()
+    if exclude is not None:
+        ex = _int64_on(exclude, "exclude", Q, device)
+        keep.append(ex)
+        f.exclude = ex.data_ptr()
+    return f, keep
+
+
 def cosine_topk(queries: torch.Tensor, gallery: torch.Tensor, k: int, eps: float = _EPS,
-                gallery_is_normalized: bool = False, idx_offset: int = 0):
+                gallery_is_normalized: bool = False, idx_offset: int = 0, query_labels: torch.Tensor | None = None,
+                gallery_labels: torch.Tensor | None = None, label_filter: str | None = None,
+                exclude: torch.Tensor | None = None):
     """All-pairs cosine + top-k: the loop of train/train.py:249-251 as one call.
 
     Returns (values (Q,k) fp32, indices (Q,k) int64), sorted by descending score; equal scores are
-    ordered by ascending gallery index.  Raises like ``torch.topk`` when k exceeds the gallery size."""
+    ordered by ascending gallery index.  Raises like ``torch.topk`` when k exceeds the gallery size.
+
+    Filtered search: ``label_filter="same"`` / ``"different"`` keeps the gallery rows whose label equals / differs from the
+    query's (``query_labels`` (Q,), ``gallery_labels`` (G,)); ``exclude`` (Q,) int64 leaves out row ``exclude[q]`` (a global
+    index, compared with ``row + idx_offset``; negative = none).  Scores and order are those of the unfiltered search on the
+    eligible rows; slots beyond the eligible rows hold (-inf, -1)."""
     q, g = _f32c(queries, "queries"), _f32c(gallery, "gallery")
     _check_qg(q, g)
     Q, D = q.shape
     G = g.shape[0]
     if k > G or k < 1:
         raise MI355Error(f"selected index k out of range: k={k}, gallery rows={G}")
+    filt = _rank_filter(Q, G, q.device, query_labels, gallery_labels, label_filter, exclude)
     vals = torch.empty((Q, k), dtype=torch.float32, device=q.device)
     idx = torch.empty((Q, k), dtype=torch.int64, device=q.device)
     if Q == 0:
@@ -118,9 +166,14 @@ def cosine_topk(queries: torch.Tensor, gallery: torch.Tensor, k: int, eps: float
     nbytes = lib().mi355_rank_workspace_bytes(Q, G, D, k)
     ws = _ws.get(q.device, nbytes)
     with torch.cuda.device(q.device):
-        check(lib().mi355_rank_topk(q.data_ptr(), Q, g.data_ptr(), G, D, int(gallery_is_normalized), k, eps,
-                                    int(idx_offset), vals.data_ptr(), idx.data_ptr(), ws.data_ptr(), ws.numel(),
-                                    stream_ptr(q.device)))
+        if filt is None:
+            check(lib().mi355_rank_topk(q.data_ptr(), Q, g.data_ptr(), G, D, int(gallery_is_normalized), k, eps,
+                                        int(idx_offset), vals.data_ptr(), idx.data_ptr(), ws.data_ptr(), ws.numel(),
+                                        stream_ptr(q.device)))
+        else:
+            check(lib().mi355_rank_topk_filtered(q.data_ptr(), Q, g.data_ptr(), G, D, int(gallery_is_normalized), k, eps,
+                                                 int(idx_offset), filt[0], vals.data_ptr(), idx.data_ptr(), ws.data_ptr(),
+                                                 ws.numel(), stream_ptr(q.device)))
     return vals, idx
 
 
@@ -404,7 +457,7 @@ def _f16_stride(dim: int) -> int:
 
 
 def _cosine_topk_f16(queries: torch.Tensor, gallery_f16: torch.Tensor, rows: int, dim: int, k: int, eps: float = _EPS,
-                    idx_offset: int = 0):
+                    idx_offset: int = 0, filt=None):
     """Top-k of ``queries`` against the first ``rows`` rows of an fp16 gallery buffer (``mi355_gallery_to_f16`` layout:
     ``(capacity, _f16_stride(dim))`` fp16, normalised rows, zero padding).  score = qn . float(row) with fp32
     accumulation; order, ties and NaN as ``cosine_topk``."""
@@ -416,8 +469,13 @@ def _cosine_topk_f16(queries: torch.Tensor, gallery_f16: torch.Tensor, rows: int
         return vals, idx
     ws = _ws.get(q.device, lib().mi355_rank_f16_workspace_bytes(Q, rows, dim, k))
     with torch.cuda.device(q.device):
-        check(lib().mi355_rank_topk_f16(q.data_ptr(), Q, gallery_f16.data_ptr(), rows, dim, k, eps, int(idx_offset),
-                                        vals.data_ptr(), idx.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr(q.device)))
+        if filt is None:
+            check(lib().mi355_rank_topk_f16(q.data_ptr(), Q, gallery_f16.data_ptr(), rows, dim, k, eps, int(idx_offset),
+                                            vals.data_ptr(), idx.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr(q.device)))
+        else:
+            check(lib().mi355_rank_topk_f16_filtered(q.data_ptr(), Q, gallery_f16.data_ptr(), rows, dim, k, eps, int(idx_offset),
+                                                     filt[0], vals.data_ptr(), idx.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                     stream_ptr(q.device)))
     return vals, idx
 
 
@@ -494,17 +552,110 @@ class Gallery:
         self._prepared_rows = self.rows
         return self
 
-    def search(self, queries: torch.Tensor, k: int, idx_offset: int = 0):
+    def search(self, queries: torch.Tensor, k: int, idx_offset: int = 0, *, query_labels: torch.Tensor | None = None,
+               label_filter: str | None = None, exclude: torch.Tensor | None = None):
+        """Top-k of ``queries`` against the resident rows.  ``label_filter`` ("same" / "different") compares the gallery's
+        labels (``add(..., labels)``) with ``query_labels``; ``exclude`` leaves out one global row per query (see
+        ``cosine_topk``).  A filtered search on a prepared gallery runs on its fp32 rows (same results)."""
+        filtered = label_filter is not None or exclude is not None
+        if label_filter is not None and self.labels is None:
+            raise MI355Error(f'label_filter="{label_filter}" needs gallery labels: add(embeddings, labels)')
+        if self.labels is not None and label_filter is not None and self.labels.shape[0] != self.rows:
+            raise MI355Error(f"the gallery holds {self.labels.shape[0]} labels for {self.rows} rows")
         if self.dtype == torch.float16:
             q = _f32c(queries, "queries")
             _check_qg(q, self.data)
             if k > self.rows or k < 1:
                 raise MI355Error(f"selected index k out of range: k={k}, gallery rows={self.rows}")
-            return _cosine_topk_f16(q, self._buf, self.rows, self.dim, k, self.eps, idx_offset)
+            filt = _rank_filter(q.shape[0], self.rows, q.device, query_labels, self.labels, label_filter, exclude)
+            return _cosine_topk_f16(q, self._buf, self.rows, self.dim, k, self.eps, idx_offset, filt)
         p = getattr(self, "_prepared", None)
-        if p is not None and self._prepared_rows == self.rows and PreparedGallery.supports(queries.shape[0], k):
+        if (not filtered and p is not None and self._prepared_rows == self.rows
+                and PreparedGallery.supports(queries.shape[0], k)):
             return p.search(queries, k, self.eps, idx_offset)
-        return cosine_topk(queries, self.data, k, self.eps, gallery_is_normalized=True, idx_offset=idx_offset)
+        if not filtered:
+            return cosine_topk(queries, self.data, k, self.eps, gallery_is_normalized=True, idx_offset=idx_offset)
+        return cosine_topk(queries, self.data, k, self.eps, gallery_is_normalized=True, idx_offset=idx_offset,
+                           query_labels=query_labels, gallery_labels=self.labels, label_filter=label_filter, exclude=exclude)
+
+
+def clear_pads(vals: torch.Tensor, idx: torch.Tensor, lo: int, hi: int):
+    """In place: entries whose index lies outside [lo, hi) become (-inf, -1)."""
+    require_cuda(idx, "idx")
+    if vals.dtype != torch.float32 or idx.dtype != torch.int64 or not vals.is_contiguous() or not idx.is_contiguous():
+        raise MI355Error("clear_pads expects contiguous fp32 values and int64 indices")
+    if vals.numel():
+        with torch.cuda.device(idx.device):
+            check(lib().mi355_clear_pads(vals.data_ptr(), idx.data_ptr(), idx.numel(), int(lo), int(hi), stream_ptr(idx.device)))
+    return vals, idx
+
+
+_MAX_R = 1024
+
+
+def retrieval_accuracy(queries: torch.Tensor, query_labels: torch.Tensor, gallery: torch.Tensor | None = None,
+                       gallery_labels: torch.Tensor | None = None, ks=(1, 2, 4, 8), eps: float = _EPS):
+    """Leave-one-out / cross-source retrieval accuracy of labelled embeddings, as defined by Musgrave et al. 2020 ("A Metric
+    Learning Reality Check") and pytorch-metric-learning's AccuracyCalculator.
+
+    ``gallery=None``: the queries are their own gallery and every query's own row is excluded (one ``cosine_topk`` with
+    ``exclude=arange(Q)``).  Otherwise ``gallery`` (G, D) with ``gallery_labels`` (G,).  R_q = the number of gallery rows
+    with the query's label (its own row not counted); queries with R_q = 0 are left out of every mean (``num_lone``).  One
+    search with k = max(max(ks), max R_q) (at most 1024) ranks every query; the per-query metrics run in one HIP kernel
+    (``mi355_retrieval_metrics``).  Returns device tensors (float64) ``precision_at_1``, ``recall_at_k`` {K: ...},
+    ``r_precision``, ``map_at_r``, and ints ``num_queries``, ``num_lone``.  The one host sync reads max R_q."""
+    q = _f32c(queries, "queries")
+    if q.dim() != 2:
+        raise MI355Error(f"queries must be (Q, D), got {tuple(q.shape)}")
+    Q = q.shape[0]
+    ql = _int64_on(query_labels, "query_labels", Q, q.device)
+    same_source = gallery is None
+    if same_source:
+        if gallery_labels is not None:
+            raise MI355Error("gallery_labels given without a gallery (same-source evaluation uses query_labels)")
+        g, gl = q, ql
+    else:
+        g = _f32c(gallery, "gallery")
+        _check_qg(q, g)
+        if gallery_labels is None:
+            raise MI355Error("a gallery needs gallery_labels")
+        gl = _int64_on(gallery_labels, "gallery_labels", g.shape[0], q.device)
+    G = g.shape[0]
+    ks = sorted({int(K) for K in ks})
+    if not ks or ks[0] < 1 or ks[-1] > _MAX_R:
+        raise MI355Error(f"ks must be ranks in [1, {_MAX_R}], got {ks}")
+    if Q == 0 or G == 0 or (same_source and G < 2):
+        raise MI355Error(f"retrieval_accuracy needs queries and at least one other gallery row (Q={Q}, G={G})")
+    # class sizes in the gallery -> R_q
+    if same_source:
+        _, inv, counts = torch.unique(ql, return_inverse=True, return_counts=True)
+        R = counts[inv] - 1
+    else:
+        uniq, inv = torch.unique(torch.cat([gl, ql]), return_inverse=True)
+        R = torch.bincount(inv[:G], minlength=uniq.numel())[inv[G:]]
+    r_max = int(R.max().item())                                # the one host sync
+    if r_max > _MAX_R:
+        lab = int(ql[int(R.argmax().item())].item())
+        raise MI355Error(f"class {lab} has {r_max} relevant gallery rows; retrieval_accuracy ranks at most {_MAX_R}")
+    k = min(max(ks[-1], r_max), G)        # k = G ranks every row, so recall@K for K > G is exact as well
+    exclude = torch.arange(Q, dtype=torch.int64, device=q.device) if same_source else None
+    _, idx = cosine_topk(q, g, k, eps, exclude=exclude)
+    per = torch.empty((Q, 3), dtype=torch.float64, device=q.device)
+    Rc = R.contiguous()
+    with torch.cuda.device(q.device):
+        check(lib().mi355_retrieval_metrics(idx.data_ptr(), Q, k, ql.data_ptr(), gl.data_ptr(), G, Rc.data_ptr(),
+                                            per.data_ptr(), stream_ptr(q.device)))
+    valid = (Rc > 0).to(torch.float64)
+    n = valid.sum()
+    first = per[:, 0]
+
+    def mean(x):
+        return (x * valid).sum() / n
+
+    return {"precision_at_1": mean((first == 0).to(torch.float64)),
+            "recall_at_k": {K: mean((first < K).to(torch.float64)) for K in ks},
+            "r_precision": mean(per[:, 1]), "map_at_r": mean(per[:, 2]),
+            "num_queries": Q, "num_lone": (Rc <= 0).sum(), "per_query": per, "R": Rc, "indices": idx}
 
 
 def retrieval_metrics(queries, positives, query_cls, gallery_cls=None, k: int = 3):

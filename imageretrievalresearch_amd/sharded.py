@@ -31,10 +31,16 @@ class _HipOps:
     collective plumbing under gloo without a GPU; the product path is always this one.)"""
 
     @staticmethod
-    def local_topk(queries, gallery_normalized, k, idx_offset, prepared=None):
-        if prepared is not None and _rank.PreparedGallery.supports(queries.shape[0], k):
+    def local_topk(queries, gallery_normalized, k, idx_offset, prepared=None, **filt):
+        # filt (filtered searches only): query_labels, gallery_labels, label_filter, exclude - the prepared planes have no
+        # filtered search, the fp32 rows give the same results
+        if not filt and prepared is not None and _rank.PreparedGallery.supports(queries.shape[0], k):
             return prepared.search(queries, k, idx_offset=idx_offset)
-        return _rank.cosine_topk(queries, gallery_normalized, k, gallery_is_normalized=True, idx_offset=idx_offset)
+        return _rank.cosine_topk(queries, gallery_normalized, k, gallery_is_normalized=True, idx_offset=idx_offset, **filt)
+
+    @staticmethod
+    def clear_pads(vals, idx, lo, hi):
+        return _rank.clear_pads(vals, idx, lo, hi)
 
     @staticmethod
     def prepare(gallery_normalized):
@@ -81,6 +87,8 @@ class ShardedGallery:
         else:
             self.local = self.ops.normalize(local_rows.float().contiguous()) if local_rows.shape[0] else local_rows.float()
         self.labels = labels
+        if self.gallery_f16 is not None and labels is not None:
+            self.gallery_f16.labels = labels.to(self.device, torch.int64)
         # prepared=True: the shard is also kept as the cosine GEMM's bf16 planes (+6 B per element; same results bit for bit)
         self.prepared = self.ops.prepare(self.local) if (prepared and hasattr(self.ops, "prepare")) else None
         if self.world > 1:
@@ -118,14 +126,76 @@ class ShardedGallery:
         v, i = self._local_topk(queries, kk) if kk > 0 else (None, None)
         return self.ops.pack(v, i, Q, k, self.device)
 
-    def search(self, queries_local: torch.Tensor, k: int):
+    def _filtered_search(self, q, k, query_labels, label_filter, exclude):
+        """Filtered search: every shard searches with its own labels and its offset as idx_offset (so ``exclude`` compares
+        global rows) and packs GLOBAL indices; the merge then adds zero offsets, and slots that no shard filled become
+        (-inf, -1)."""
+        if label_filter is not None and self.labels is None:
+            raise MI355Error(f'label_filter="{label_filter}" needs the shard labels: ShardedGallery(..., labels=)')
+        if self.total_rows >= 2 ** 31 - 128:
+            raise MI355Error("a filtered sharded search carries global int32 indices: the gallery must have fewer than 2^31 rows")
+        Ql = q.shape[0]
+        n_local = self.local.shape[0]
+        if self.labels is not None and label_filter is not None and self.labels.shape[0] != n_local:
+            raise MI355Error(f"the shard holds {self.labels.shape[0]} labels for {n_local} rows")
+        # per-query side of the filter: (Ql, 2) int64 [label, exclude], all-gathered with ONE collective
+        side = torch.full((Ql, 2), -1, dtype=torch.int64, device=self.device)
+        if label_filter is not None:
+            if query_labels is None:
+                raise MI355Error(f'label_filter="{label_filter}" needs query_labels')
+            side[:, 0] = _rank._int64_on(query_labels, "query_labels", Ql, self.device)
+        if exclude is not None:
+            side[:, 1] = _rank._int64_on(exclude, "exclude", Ql, self.device)
+        dist = torch.distributed
+        if self.world > 1:
+            allq = torch.empty((self.world * Ql, self.dim), dtype=torch.float32, device=self.device)
+            dist.all_gather_into_tensor(allq, q, group=self.group)
+            alls = torch.empty((self.world * Ql, 2), dtype=torch.int64, device=self.device)
+            dist.all_gather_into_tensor(alls, side, group=self.group)
+        else:
+            allq, alls = q, side
+        Q = allq.shape[0]
+        filt = {"label_filter": label_filter}
+        if label_filter is not None:
+            filt.update(query_labels=alls[:, 0].contiguous(), gallery_labels=self.labels)
+        if exclude is not None:
+            filt["exclude"] = alls[:, 1].contiguous()
+        kk = min(k, n_local)
+        if kk > 0:
+            if self.gallery_f16 is not None:
+                v, i = self.gallery_f16.search(allq, kk, self.offset, query_labels=filt.get("query_labels"),
+                                               label_filter=label_filter, exclude=filt.get("exclude"))
+            else:
+                v, i = self.ops.local_topk(allq, self.local, kk, self.offset, **filt)
+        else:
+            v = i = None
+        packed = self.ops.pack(v, i, Q, k, self.device)
+        if self.world > 1:
+            allp = torch.empty((self.world * Q, k, 2), dtype=torch.int32, device=self.device)
+            dist.all_gather_into_tensor(allp, packed, group=self.group)
+        else:
+            allp = packed
+        zeros = torch.zeros(self.world, dtype=torch.int64, device=self.device)
+        vals, idx = self.ops.merge_packed(allp.view(self.world, Q, k, 2), zeros, k)
+        return self.ops.clear_pads(vals, idx, 0, self.total_rows)
+
+    def search(self, queries_local: torch.Tensor, k: int, *, query_labels: torch.Tensor | None = None,
+               label_filter: str | None = None, exclude: torch.Tensor | None = None):
         """Top-k of every rank's queries against the WHOLE gallery.
 
         ``queries_local``: this rank's (Q_local, D) queries (same Q_local on every rank).
-        Returns (values, global indices) for ALL world*Q_local queries, rank-major, on every rank."""
+        Returns (values, global indices) for ALL world*Q_local queries, rank-major, on every rank.
+
+        Filtered search (see ``cosine_topk``): ``label_filter`` "same" / "different" compares the shards' labels with this
+        rank's ``query_labels`` (Q_local,); ``exclude`` (Q_local,) holds GLOBAL row indices.  Slots no shard could fill are
+        (-inf, -1)."""
         if k < 1 or k > self.total_rows:
             raise MI355Error(f"selected index k out of range: k={k}, gallery rows={self.total_rows}")
+        if label_filter not in (None, "same", "different"):
+            raise MI355Error(f'label_filter must be None, "same" or "different", got {label_filter!r}')
         q = queries_local.float().contiguous()
+        if label_filter is not None or exclude is not None:
+            return self._filtered_search(q, k, query_labels, label_filter, exclude)
         if self.world == 1:
             return self._local_topk(q, k)
         dist = torch.distributed

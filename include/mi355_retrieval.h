@@ -99,6 +99,56 @@ int mi355_rank_topk_f16(const float* queries, int64_t Q, const void* gallery_f16
                         int64_t idx_offset, float* out_val, int64_t* out_idx, void* workspace, size_t workspace_bytes,
                         void* stream);
 
+/* Filtered search: the top-k of the rows that are ELIGIBLE for each query.  Row j (global index j + idx_offset) is eligible
+ * for query q when
+ *   - exclude is NULL, exclude[q] < 0, or exclude[q] != j + idx_offset (leave-one-out: the query's own row), and
+ *   - label_mode is MI355_LABEL_ANY (labels unused, may be NULL), MI355_LABEL_SAME and gallery_labels[j] == query_labels[q],
+ *     or MI355_LABEL_DIFFERENT and gallery_labels[j] != query_labels[q].
+ * query_labels / exclude [Q], gallery_labels [G]: device int64.  Scores are bit for bit those of the unfiltered search, the
+ * order is its order (descending, ties to the lower index, NaN first); an ineligible row never appears, NaN or not.  With
+ * fewer than k eligible rows the remaining slots are (-inf, -1); k <= G is the only size rule.  Workspace: that of the
+ * unfiltered twin (mi355_rank_workspace_bytes / mi355_rank_f16_workspace_bytes).  A prepared gallery has no filtered
+ * search: filter with mi355_rank_topk_filtered on its fp32 rows (same results). */
+enum { MI355_LABEL_ANY = 0, MI355_LABEL_SAME = 1, MI355_LABEL_DIFFERENT = 2 };
+typedef struct mi355_rank_filter {
+    const int64_t* query_labels;
+    const int64_t* gallery_labels;
+    int label_mode;
+    const int64_t* exclude;
+} mi355_rank_filter;
+int mi355_rank_topk_filtered(const float* queries, int64_t Q, const float* gallery, int64_t G, int dim,
+                             int gallery_is_normalized, int k, float eps, int64_t idx_offset, const mi355_rank_filter* filter,
+                             float* out_val, int64_t* out_idx, void* workspace, size_t workspace_bytes, void* stream);
+int mi355_rank_topk_f16_filtered(const float* queries, int64_t Q, const void* gallery_f16, int64_t G, int dim, int k, float eps,
+                                 int64_t idx_offset, const mi355_rank_filter* filter, float* out_val, int64_t* out_idx,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+/* The branch the calling thread's last mi355_rank_topk* call took: MI355_RANK_PATH_* of the score stage, | FUSED when the
+ * selection ran in the GEMM epilogue, | BITONIC when a score slab was selected with k > 8 (else the small-k selection). */
+enum {
+    MI355_RANK_PATH_GEMV = 1,           /* k_cos_gemv: Q <= 4 */
+    MI355_RANK_PATH_SPLIT = 2,          /* k_cos_gemm_split: the bf16 three-way split */
+    MI355_RANK_PATH_EXACT_F32 = 3,      /* k_cos_gemm: MI355_RANK_EXACT_F32=1, or unaligned rows */
+    MI355_RANK_PATH_PREPARED = 4,       /* k_cos_gemm_pre */
+    MI355_RANK_PATH_F16_GEMM = 5,       /* k_cos_gemm_f16 */
+    MI355_RANK_PATH_F16_GEMV = 6,       /* k_cos_gemv_f16 */
+    MI355_RANK_PATH_FUSED = 0x100,
+    MI355_RANK_PATH_BITONIC = 0x200
+};
+int mi355_rank_last_path(void);
+
+/* Indices outside [lo, hi) become (-inf, -1) in val / idx [n] (the sharded filtered search: slots no shard filled). */
+int mi355_clear_pads(float* val, int64_t* idx, int64_t n, int64_t lo, int64_t hi, void* stream);
+
+/* Retrieval accuracy of ranked lists (Musgrave et al. 2020, "A Metric Learning Reality Check"): idx [Q][k] ranked gallery rows
+ * (indices outside [0, G) are misses), query_cls [Q], gallery_cls [G], R [Q] the number of relevant gallery rows of each
+ * query (R <= k; ranks past k count as misses).  One wave per query writes per_query[Q][3] float64:
+ *   [0] the first rank (0-based) holding a row of the query's class, k if none (precision@1: [0] == 0; recall@K: [0] < K),
+ *   [1] R-precision  (1/R) sum_{i<R} rel(i),
+ *   [2] MAP@R        (1/R) sum_{i<R} rel(i) * P(i),  P(i) = (1/(i+1)) sum_{j<=i} rel(j);
+ * queries with R <= 0 get [k, 0, 0]. */
+int mi355_retrieval_metrics(const int64_t* idx, int64_t Q, int k, const int64_t* query_cls, const int64_t* gallery_cls,
+                            int64_t G, const int64_t* R, double* per_query, void* stream);
+
 int mi355_cosine_scores(const float* queries, int64_t Q, const float* gallery, int64_t G, int dim,
                         int gallery_is_normalized, float eps, float* out, void* workspace,
                         size_t workspace_bytes, void* stream);
