@@ -17,7 +17,7 @@ void roctx_push(const char* label);
 void roctx_pop();
 struct RoctxRange {
     bool on;
-    explicit RoctxRange(const char* label) : on(roctx_active()) { if (on) roctx_push(label); }
+    explicit RoctxRange(const char* label) : on(label && roctx_active()) { if (on) roctx_push(label); }   // null: no range
     ~RoctxRange() { if (on) roctx_pop(); }
 };
 enum { OK = 0, ERR_ARG = 1, ERR_HIP = 2, ERR_STATE = 3, ERR_UNSUPPORTED = 4 };

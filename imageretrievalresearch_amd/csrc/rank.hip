@@ -741,12 +741,18 @@ i64 query_block(i64 Q, i64 G, int k) {
     return qb < Q ? qb : Q;
 }
 
-struct RankWs {
-    float* qn; bf16_t* qs; float* ginv; float* S; float* cand_val; int* cand_idx; void* topk; size_t topk_bytes; size_t total;
-};
-// split query planes (k_split_queries): whole 128-row tiles, 16-deep k steps, three planes
+// split planes of rows (k_split_queries): whole 128-row tiles, 16-deep k steps, three planes, then the zero page
 static size_t split_queries_bytes(i64 Q, int D) { return (size_t)cdiv(Q, 128) * 4 * cdiv(D, 16) * 3 * 1024 + 256; }
-static RankWs carve(void* ws, i64 Q, i64 G, int D, int k, bool need_ginv, bool need_S = true) {
+// rows [0, n) of x -> their split planes (k_split_queries)
+static int split_rows(const float* x, i64 n, int D, bf16_t* planes, hipStream_t st) {
+    const int n_steps = cdiv(D, 16);
+    const i64 n_frag = (i64)cdiv(n, 128) * 4 * n_steps;
+    hipLaunchKernelGGL(k_split_queries, dim3((unsigned)cdiv(n_frag, 4)), dim3(256), 0, st, x, planes, (int)n, D, n_steps, (int)n_frag);
+    MI355_LAUNCH_CHECK();
+    return OK;
+}
+
+RankWs carve(void* ws, i64 Q, i64 G, int D, int k, size_t (*planes_bytes)(i64, int), bool need_ginv, bool need_S) {
     RankWs r{};
     const bool fused = need_S && fused_select(Q, G, k);
     const i64 qb = query_block(Q, G, need_S ? k : 0);
@@ -755,7 +761,7 @@ static RankWs carve(void* ws, i64 Q, i64 G, int D, int k, bool need_ginv, bool n
     auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align_up(bytes, 256); return p; };
     r.qn = (float*)take((size_t)Q * D * sizeof(float));
     const i64 q_split = need_S ? qb : (Q < 256 * 64 ? Q : 256 * 64);      // queries of one cos_gemm call
-    r.qs = (bf16_t*)take(split_queries_bytes(q_split, D));   // (also for Q <= 4: rows too long for the GEMV's LDS copy take the GEMM)
+    r.qs = take(planes_bytes ? planes_bytes(q_split, D) : 0);
     r.ginv = (float*)take(need_ginv ? (size_t)G * sizeof(float) : 0);
     if (fused) {
         const size_t ncand = (size_t)qb * cdiv(G, RK_BN) * k;
@@ -786,197 +792,81 @@ int kernel_slots(const void* fn, size_t lds, int* cache, int* slots_out) {
     *slots_out = cache[dev];
     return OK;
 }
-template <int MT, int BK, bool VEC, int FK, bool FILT = false>
-static int gemm_slots(size_t lds, int* slots_out) {
-    static int slots[MI355_MAX_DEVICES] = {0};
-    if constexpr (FILT) return kernel_slots((const void*)k_cos_gemm_filt<MT, BK, VEC, FK>, lds, slots, slots_out);
-    else return kernel_slots((const void*)k_cos_gemm<MT, BK, VEC, FK>, lds, slots, slots_out);
-}
-template <int MT, int FK, bool FILT = false>
-static int split_slots(size_t lds, int* slots_out) {
-    static int slots[MI355_MAX_DEVICES] = {0};
-    if constexpr (FILT) return kernel_slots((const void*)k_cos_gemm_split_filt<MT, FK>, lds, slots, slots_out);
-    else return kernel_slots((const void*)k_cos_gemm_split<MT, FK>, lds, slots, slots_out);
-}
 
-// filt: the filtered epilogue keeps the tile's gallery labels behind the score tile (inside the staging buffers in every case,
-// static_asserts below, so the filtered kernels request the LDS of the unfiltered ones)
-constexpr size_t EPI_TILE_BYTES = (size_t)64 * (RK_BN + 4) * sizeof(float);
-template <int MT, int BK>
-constexpr size_t gemm_stage_bytes() { return (size_t)2 * (64 * MT + RK_BN) * (BK + 4) * sizeof(float); }
-template <int MT>
-constexpr size_t split_stage_bytes() {   // A ring of 2 (3 at MT = 1), B ring of 3
-    return (size_t)(MT == 1 ? 3 : 2) * (64 * MT / 32) * 3 * 1024 + (size_t)3 * RK_BN * 16 * sizeof(float);
-}
-static_assert(gemm_stage_bytes<2, 16>() >= EPI_TILE_BYTES + FILT_LABELS_BYTES && gemm_stage_bytes<1, 32>() >= EPI_TILE_BYTES + FILT_LABELS_BYTES,
-              "filtered epilogue would grow the exact-fp32 GEMM's LDS");
-static_assert(split_stage_bytes<2>() >= EPI_TILE_BYTES + FILT_LABELS_BYTES && split_stage_bytes<1>() >= EPI_TILE_BYTES + FILT_LABELS_BYTES,
-              "filtered epilogue would grow the split GEMM's LDS");
-
-template <int MT, int BK>
-static size_t gemm_lds(bool fk) {
-    const size_t stage = gemm_stage_bytes<MT, BK>();
-    const size_t tile = fk ? EPI_TILE_BYTES : 0;   // fused selection: 64 rows of the score tile at a time
-    return stage > tile ? stage : tile;
-}
-template <int MT>
-static size_t split_lds(bool fk) {
-    const size_t stage = split_stage_bytes<MT>();
-    const size_t tile = fk ? EPI_TILE_BYTES : 0;
-    return stage > tile ? stage : tile;
-}
-
-// Wave quantisation: 1564 tiles on 768 slots run as 2.04 rounds and the 28 tiles of the third round cost a whole round
-// (0.15 ms of 0.83 at Q=256 x 100k on the fp32 loop).  Whole rounds go out as 128-row tiles, the remainder as a second
-// launch of 64-row tiles (same column tiles, same k order: every score is bit-identical), which halves the tiles' length
-// and doubles their number.  Returns the number of column tiles of the main launch.
 int whole_round_tiles(int ntx, int ny, int slots) {
     if ((long)ntx * ny > slots && ((long)ntx * ny) % slots != 0) return (int)(((long)ntx * ny / slots) * slots / ny);
     return ntx;
 }
 
-template <int MT, int BK, bool VEC, int FK, bool FILT = false>
-static int launch_gemm(const float* qn, const float* gal, const float* ginv, float* S, int Q, i64 G, int D, int k,
-                       float* cand_val, int* cand_idx, hipStream_t st, const RankFilter* filt = nullptr) {
-    constexpr int BM = 64 * MT;
-    const size_t lds = gemm_lds<MT, BK>(FK > 0);
-    int slots = 0;
-    if (int e = gemm_slots<MT, BK, VEC, FK, FILT>(lds, &slots)) return e;
-    const int ntx = cdiv(G, RK_BN), ny = cdiv(Q, BM);
-    const int xm = MT == 2 ? whole_round_tiles(ntx, ny, slots) : ntx;
-    if (xm > 0) {
-        if constexpr (FILT)
-            hipLaunchKernelGGL((k_cos_gemm_filt<MT, BK, VEC, FK>), dim3((unsigned)xm * (unsigned)ny), dim3(256), lds, st, qn, gal,
-                               ginv, Q, G, D, k, cand_val, cand_idx, 0, ntx, xm, ny, *filt);
-        else
-            hipLaunchKernelGGL((k_cos_gemm<MT, BK, VEC, FK>), dim3((unsigned)xm * (unsigned)ny), dim3(256), lds, st, qn, gal, ginv, S,
-                               Q, G, D, k, cand_val, cand_idx, 0, ntx, xm, ny);
-        MI355_LAUNCH_CHECK();
+// ---- the tiled GEMM families of this file (launch_tiles, rank_common.h)
+// Exact fp32 loop (qry: the normalised fp32 rows).  Tile choice, measured on MI355X (tools/bench_rank.py, D = 1536): it
+// plateaus at 95-110 TFLOP/s for every tile shape, so what differs is the partial last round of tiles.  128-query tiles with
+// BK = 16 keep two workgroups on a CU (41 KB of staging, 68 KB with the fused selection's score tile): a lone workgroup in
+// the last round runs at full speed, which halves the wave-quantisation loss (Q = 256, G = 100k: 0.83 ms, against 0.95 ms
+// with 256 x 128 tiles, one per CU).  64-query tiles use BK = 32.
+template <bool VEC>
+struct F32Gemm {
+    static constexpr bool SLAB = true, FILTERED = true;
+    template <int MT> static constexpr int BK = MT == 2 ? 16 : 32;
+    template <int MT> static constexpr size_t stage_bytes() { return (size_t)2 * (64 * MT + RK_BN) * (BK<MT> + 4) * sizeof(float); }
+    template <int MT, int FK, bool FILT> static const void* kernel() {
+        if constexpr (FILT) return (const void*)k_cos_gemm_filt<MT, BK<MT>, VEC, FK>;
+        else return (const void*)k_cos_gemm<MT, BK<MT>, VEC, FK>;
     }
-    if (xm < ntx) {
-        const size_t lds1 = gemm_lds<1, 32>(FK > 0);
-        int slots1 = 0;
-        if (int e = gemm_slots<1, 32, VEC, FK, FILT>(lds1, &slots1)) return e;
+    template <int MT, int FK, bool FILT>
+    static void launch(dim3 grid, size_t lds, hipStream_t st, const TileArgs& a, int x0, int ntx, int xtiles, int ny) {
+        const float* qn = (const float*)a.qry;
+        const float* gal = (const float*)a.gal;
         if constexpr (FILT)
-            hipLaunchKernelGGL((k_cos_gemm_filt<1, 32, VEC, FK>), dim3((unsigned)(ntx - xm) * (unsigned)cdiv(Q, 64)), dim3(256), lds1,
-                               st, qn, gal, ginv, Q, G, D, k, cand_val, cand_idx, xm, ntx, ntx - xm, (int)cdiv(Q, 64), *filt);
+            hipLaunchKernelGGL((k_cos_gemm_filt<MT, BK<MT>, VEC, FK>), grid, dim3(256), lds, st, qn, gal, a.ginv, a.Q, a.G, a.D, a.k,
+                               a.cand_val, a.cand_idx, x0, ntx, xtiles, ny, *a.filt);
         else
-            hipLaunchKernelGGL((k_cos_gemm<1, 32, VEC, FK>), dim3((unsigned)(ntx - xm) * (unsigned)cdiv(Q, 64)), dim3(256), lds1, st,
-                               qn, gal, ginv, S, Q, G, D, k, cand_val, cand_idx, xm, ntx, ntx - xm, (int)cdiv(Q, 64));
-        MI355_LAUNCH_CHECK();
+            hipLaunchKernelGGL((k_cos_gemm<MT, BK<MT>, VEC, FK>), grid, dim3(256), lds, st, qn, gal, a.ginv, a.S, a.Q, a.G, a.D, a.k,
+                               a.cand_val, a.cand_idx, x0, ntx, xtiles, ny);
     }
-    return OK;
-}
+};
 
-// split-bf16 loop: qs = the split planes of these Q queries (k_split_queries, whole 128-row tiles)
-template <int MT, int FK, bool FILT = false>
-static int launch_split(const bf16_t* qs, const float* gal, const float* ginv, float* S, int Q, i64 G, int D, int k,
-                        float* cand_val, int* cand_idx, hipStream_t st, const RankFilter* filt = nullptr) {
-    constexpr int BM = 64 * MT;
-    const size_t lds = split_lds<MT>(FK > 0);
-    int slots = 0;
-    if (int e = split_slots<MT, FK, FILT>(lds, &slots)) return e;
-    const int ntx = cdiv(G, RK_BN), ny = cdiv(Q, BM), n_steps = cdiv(D, 16);
-    const float* zeros = reinterpret_cast<const float*>(qs + (size_t)cdiv(Q, 128) * 4 * n_steps * 3 * 512);
-    const int xm = MT == 2 ? whole_round_tiles(ntx, ny, slots) : ntx;
-    if (xm > 0) {
+// Split-bf16 loop (qry: the split planes of the queries, split_rows; gal: fp32 rows with D % 4 == 0)
+struct SplitGemm {
+    static constexpr bool SLAB = true, FILTERED = true;
+    template <int MT> static constexpr size_t stage_bytes() {   // A ring of 2 (3 at MT = 1), B ring of 3
+        return (size_t)(MT == 1 ? 3 : 2) * (64 * MT / 32) * 3 * 1024 + (size_t)3 * RK_BN * 16 * sizeof(float);
+    }
+    template <int MT, int FK, bool FILT> static const void* kernel() {
+        if constexpr (FILT) return (const void*)k_cos_gemm_split_filt<MT, FK>;
+        else return (const void*)k_cos_gemm_split<MT, FK>;
+    }
+    template <int MT, int FK, bool FILT>
+    static void launch(dim3 grid, size_t lds, hipStream_t st, const TileArgs& a, int x0, int ntx, int xtiles, int ny) {
+        const bf16_t* qs = (const bf16_t*)a.qry;
+        const float* gal = (const float*)a.gal;
+        const int n_steps = cdiv(a.D, 16);
+        const float* zeros = reinterpret_cast<const float*>(qs + (size_t)cdiv(a.Q, 128) * 4 * n_steps * 3 * 512);
         if constexpr (FILT)
-            hipLaunchKernelGGL((k_cos_gemm_split_filt<MT, FK>), dim3((unsigned)xm * (unsigned)ny), dim3(256), lds, st, qs, gal, ginv,
-                               Q, G, D, k, cand_val, cand_idx, 0, ntx, n_steps, zeros, xm, ny, *filt);
+            hipLaunchKernelGGL((k_cos_gemm_split_filt<MT, FK>), grid, dim3(256), lds, st, qs, gal, a.ginv, a.Q, a.G, a.D, a.k,
+                               a.cand_val, a.cand_idx, x0, ntx, n_steps, zeros, xtiles, ny, *a.filt);
         else
-            hipLaunchKernelGGL((k_cos_gemm_split<MT, FK>), dim3((unsigned)xm * (unsigned)ny), dim3(256), lds, st, qs, gal, ginv,
-                               S, Q, G, D, k, cand_val, cand_idx, 0, ntx, n_steps, zeros, xm, ny);
-        MI355_LAUNCH_CHECK();
+            hipLaunchKernelGGL((k_cos_gemm_split<MT, FK>), grid, dim3(256), lds, st, qs, gal, a.ginv, a.S, a.Q, a.G, a.D, a.k,
+                               a.cand_val, a.cand_idx, x0, ntx, n_steps, zeros, xtiles, ny);
     }
-    if (xm < ntx) {
-        const size_t lds1 = split_lds<1>(FK > 0);
-        int slots1 = 0;
-        if (int e = split_slots<1, FK, FILT>(lds1, &slots1)) return e;
-        if constexpr (FILT)
-            hipLaunchKernelGGL((k_cos_gemm_split_filt<1, FK>), dim3((unsigned)(ntx - xm) * (unsigned)cdiv(Q, 64)), dim3(256), lds1,
-                               st, qs, gal, ginv, Q, G, D, k, cand_val, cand_idx, xm, ntx, n_steps, zeros, ntx - xm, (int)cdiv(Q, 64),
-                               *filt);
-        else
-            hipLaunchKernelGGL((k_cos_gemm_split<1, FK>), dim3((unsigned)(ntx - xm) * (unsigned)cdiv(Q, 64)), dim3(256), lds1,
-                               st, qs, gal, ginv, S, Q, G, D, k, cand_val, cand_idx, xm, ntx, n_steps, zeros, ntx - xm, (int)cdiv(Q, 64));
-        MI355_LAUNCH_CHECK();
-    }
-    return OK;
-}
+};
 
-template <int MT, int BK, bool VEC>
-static int launch_gemm_fk(const float* qn, const float* gal, const float* ginv, float* S, int Q, i64 G, int D, int k,
-                          float* cand_val, int* cand_idx, hipStream_t st, const RankFilter* filt = nullptr) {
-    if (!cand_val) return launch_gemm<MT, BK, VEC, 0>(qn, gal, ginv, S, Q, G, D, 0, nullptr, nullptr, st);
-    if (filt) {
-        if (k <= 1) return launch_gemm<MT, BK, VEC, 1, true>(qn, gal, ginv, S, Q, G, D, k, cand_val, cand_idx, st, filt);
-        if (k <= 2) return launch_gemm<MT, BK, VEC, 2, true>(qn, gal, ginv, S, Q, G, D, k, cand_val, cand_idx, st, filt);
-        if (k <= 4) return launch_gemm<MT, BK, VEC, 4, true>(qn, gal, ginv, S, Q, G, D, k, cand_val, cand_idx, st, filt);
-        return launch_gemm<MT, BK, VEC, 8, true>(qn, gal, ginv, S, Q, G, D, k, cand_val, cand_idx, st, filt);
+// Prepared gallery (qry: the split planes of the queries; gal: the gallery's planes): fused selection only, unfiltered
+struct PreparedGemm {
+    static constexpr bool SLAB = false, FILTERED = false;
+    template <int MT> static constexpr size_t stage_bytes() {   // A ring of 2 (3 at MT = 1), B ring of 3
+        return (size_t)(MT == 1 ? 3 : 2) * (64 * MT / 32) * 3 * 1024 + (size_t)3 * (RK_BN / 32) * 3 * 1024;
     }
-    if (k <= 1) return launch_gemm<MT, BK, VEC, 1>(qn, gal, ginv, S, Q, G, D, k, cand_val, cand_idx, st);
-    if (k <= 2) return launch_gemm<MT, BK, VEC, 2>(qn, gal, ginv, S, Q, G, D, k, cand_val, cand_idx, st);
-    if (k <= 4) return launch_gemm<MT, BK, VEC, 4>(qn, gal, ginv, S, Q, G, D, k, cand_val, cand_idx, st);
-    return launch_gemm<MT, BK, VEC, 8>(qn, gal, ginv, S, Q, G, D, k, cand_val, cand_idx, st);
-}
-template <int MT>
-static int launch_split_fk(const bf16_t* qs, const float* gal, const float* ginv, float* S, int Q, i64 G, int D, int k,
-                           float* cand_val, int* cand_idx, hipStream_t st, const RankFilter* filt = nullptr) {
-    if (!cand_val) return launch_split<MT, 0>(qs, gal, ginv, S, Q, G, D, 0, nullptr, nullptr, st);
-    if (filt) {
-        if (k <= 1) return launch_split<MT, 1, true>(qs, gal, ginv, S, Q, G, D, k, cand_val, cand_idx, st, filt);
-        if (k <= 2) return launch_split<MT, 2, true>(qs, gal, ginv, S, Q, G, D, k, cand_val, cand_idx, st, filt);
-        if (k <= 4) return launch_split<MT, 4, true>(qs, gal, ginv, S, Q, G, D, k, cand_val, cand_idx, st, filt);
-        return launch_split<MT, 8, true>(qs, gal, ginv, S, Q, G, D, k, cand_val, cand_idx, st, filt);
+    template <int MT, int FK, bool FILT> static const void* kernel() {
+        static_assert(!FILT && FK > 0, "the prepared gallery has fused unfiltered kernels only");
+        return (const void*)k_cos_gemm_pre<MT, FK>;
     }
-    if (k <= 1) return launch_split<MT, 1>(qs, gal, ginv, S, Q, G, D, k, cand_val, cand_idx, st);
-    if (k <= 2) return launch_split<MT, 2>(qs, gal, ginv, S, Q, G, D, k, cand_val, cand_idx, st);
-    if (k <= 4) return launch_split<MT, 4>(qs, gal, ginv, S, Q, G, D, k, cand_val, cand_idx, st);
-    return launch_split<MT, 8>(qs, gal, ginv, S, Q, G, D, k, cand_val, cand_idx, st);
-}
-
-template <int MT>
-static size_t pre_lds(bool fk) {
-    const size_t stage = (size_t)(MT == 1 ? 3 : 2) * (64 * MT / 32) * 3 * 1024 + (size_t)3 * (RK_BN / 32) * 3 * 1024;   // A ring of 2 (3 at MT = 1), B ring of 3
-    const size_t tile = fk ? (size_t)64 * (RK_BN + 4) * sizeof(float) : 0;
-    return stage > tile ? stage : tile;
-}
-template <int MT, int FK>
-static int pre_slots(size_t lds, int* slots_out) {
-    static int slots[MI355_MAX_DEVICES] = {0};
-    return kernel_slots((const void*)k_cos_gemm_pre<MT, FK>, lds, slots, slots_out);
-}
-// prepared gallery: qs = the split planes of these Q queries, gs = the gallery's planes (whole 128-row tiles)
-template <int MT, int FK>
-static int launch_pre(const bf16_t* qs, const bf16_t* gs, int Q, i64 G, int D, int k, float* cand_val, int* cand_idx, hipStream_t st) {
-    constexpr int BM = 64 * MT;
-    const size_t lds = pre_lds<MT>(FK > 0);
-    int slots = 0;
-    if (int e = pre_slots<MT, FK>(lds, &slots)) return e;
-    const int ntx = cdiv(G, RK_BN), ny = cdiv(Q, BM), n_steps = cdiv(D, 16);
-    const int xm = MT == 2 ? whole_round_tiles(ntx, ny, slots) : ntx;
-    if (xm > 0) {
-        hipLaunchKernelGGL((k_cos_gemm_pre<MT, FK>), dim3((unsigned)xm * (unsigned)ny), dim3(256), lds, st, qs, gs, (float*)nullptr, Q, G, k,
-                           cand_val, cand_idx, 0, ntx, n_steps, xm, ny);
-        MI355_LAUNCH_CHECK();
+    template <int MT, int FK, bool FILT>
+    static void launch(dim3 grid, size_t lds, hipStream_t st, const TileArgs& a, int x0, int ntx, int xtiles, int ny) {
+        hipLaunchKernelGGL((k_cos_gemm_pre<MT, FK>), grid, dim3(256), lds, st, (const bf16_t*)a.qry, (const bf16_t*)a.gal, a.S, a.Q,
+                           a.G, a.k, a.cand_val, a.cand_idx, x0, ntx, cdiv(a.D, 16), xtiles, ny);
     }
-    if (xm < ntx) {
-        const size_t lds1 = pre_lds<1>(FK > 0);
-        int slots1 = 0;
-        if (int e = pre_slots<1, FK>(lds1, &slots1)) return e;
-        hipLaunchKernelGGL((k_cos_gemm_pre<1, FK>), dim3((unsigned)(ntx - xm) * (unsigned)cdiv(Q, 64)), dim3(256), lds1, st, qs, gs,
-                           (float*)nullptr, Q, G, k, cand_val, cand_idx, xm, ntx, n_steps, ntx - xm, (int)cdiv(Q, 64));
-        MI355_LAUNCH_CHECK();
-    }
-    return OK;
-}
-template <int MT>
-static int launch_pre_fk(const bf16_t* qs, const bf16_t* gs, int Q, i64 G, int D, int k, float* cand_val, int* cand_idx, hipStream_t st) {
-    if (k <= 1) return launch_pre<MT, 1>(qs, gs, Q, G, D, k, cand_val, cand_idx, st);
-    if (k <= 2) return launch_pre<MT, 2>(qs, gs, Q, G, D, k, cand_val, cand_idx, st);
-    if (k <= 4) return launch_pre<MT, 4>(qs, gs, Q, G, D, k, cand_val, cand_idx, st);
-    return launch_pre<MT, 8>(qs, gs, Q, G, D, k, cand_val, cand_idx, st);
-}
+};
 
 // MI355_RANK_EXACT_F32=1 keeps the GEMM on v_mfma_f32_32x32x2_f32 (a bit-for-bit fmaf chain, 2.7x the matrix-pipe time);
 // the default is the three-way bf16 split with six products (fp32-equivalent, see split3).
@@ -992,7 +882,6 @@ static int cos_gemm(const float* qn, bf16_t* qs, const float* gal, const float* 
                     hipStream_t st, int k = 0, float* cand_val = nullptr, int* cand_idx = nullptr,
                     const RankFilter* filt = nullptr) {
     const bool vec = vec_ok(qn, D) && vec_ok(gal, D);
-    const int q = (int)Q;
     const int fused_bit = cand_val ? MI355_RANK_PATH_FUSED : 0;
     if (!cand_val && Q <= 4 && (size_t)Q * D * sizeof(float) <= 60 * 1024) {
         set_rank_path(MI355_RANK_PATH_GEMV);
@@ -1004,24 +893,30 @@ static int cos_gemm(const float* qn, bf16_t* qs, const float* gal, const float* 
         MI355_LAUNCH_CHECK();
         return OK;
     }
+    TileArgs a{qn, gal, ginv, S, (int)Q, G, D, k, cand_val, cand_idx, filt};
     if (qs && vec_ok(gal, D) && !rank_exact_f32()) {
-        const int n_steps = cdiv(D, 16), n_frag = cdiv(q, 128) * 4 * n_steps;
-        hipLaunchKernelGGL(k_split_queries, dim3((unsigned)cdiv(n_frag, 4)), dim3(256), 0, st, qn, qs, q, D, n_steps, n_frag);
-        MI355_LAUNCH_CHECK();
+        if (int e = split_rows(qn, Q, D, qs, st)) return e;
         set_rank_path(MI355_RANK_PATH_SPLIT | fused_bit);
-        if (Q > 64) return launch_split_fk<2>(qs, gal, ginv, S, q, G, D, k, cand_val, cand_idx, st, filt);
-        return launch_split_fk<1>(qs, gal, ginv, S, q, G, D, k, cand_val, cand_idx, st, filt);
+        a.qry = qs;
+        return cos_gemm_tiles<SplitGemm>(a, st);
     }
     set_rank_path(MI355_RANK_PATH_EXACT_F32 | fused_bit);
-    // Exact-fp32 loop.  Tile choice, measured on MI355X (tools/bench_rank.py, D = 1536): it plateaus at 95-110 TFLOP/s
-    // for every tile shape, so what differs is the partial last round of tiles.  128-query tiles with BK = 16 keep two
-    // workgroups on a CU (41 KB of staging, 68 KB with the fused selection's score tile): a lone workgroup in the last
-    // round runs at full speed, which halves the wave-quantisation loss (Q = 256, G = 100k: 0.83 ms, against 0.95 ms
-    // with 256 x 128 tiles, one per CU).
-    if (Q > 64) return vec ? launch_gemm_fk<2, 16, true>(qn, gal, ginv, S, q, G, D, k, cand_val, cand_idx, st, filt)
-                           : launch_gemm_fk<2, 16, false>(qn, gal, ginv, S, q, G, D, k, cand_val, cand_idx, st, filt);
-    return vec ? launch_gemm_fk<1, 32, true>(qn, gal, ginv, S, q, G, D, k, cand_val, cand_idx, st, filt)
-               : launch_gemm_fk<1, 32, false>(qn, gal, ginv, S, q, G, D, k, cand_val, cand_idx, st, filt);
+    return vec ? cos_gemm_tiles<F32Gemm<true>>(a, st) : cos_gemm_tiles<F32Gemm<false>>(a, st);
+}
+
+int normalize_search(const float* queries, i64 Q, const float* gallery, i64 G, int dim, float eps, const RankWs& w,
+                     hipStream_t st) {
+    const int vq = vec_ok(queries, dim) && vec_ok(w.qn, dim);
+    RoctxRange range("rank/normalize");
+    hipLaunchKernelGGL((k_row_norm<true>), dim3((unsigned)cdiv(Q, 4)), dim3(256), 0, st, queries, w.qn, (float*)nullptr, (i64)Q,
+                       dim, eps, vq);
+    MI355_LAUNCH_CHECK();
+    if (gallery) {
+        hipLaunchKernelGGL((k_row_norm<false>), dim3((unsigned)cdiv(G, 4)), dim3(256), 0, st, gallery, (float*)nullptr, w.ginv,
+                           (i64)G, dim, eps, vec_ok(gallery, dim));
+        MI355_LAUNCH_CHECK();
+    }
+    return OK;
 }
 
 static int check_rank_args(const float* queries, i64 Q, const float* gallery, i64 G, int dim) {
@@ -1030,6 +925,31 @@ static int check_rank_args(const float* queries, i64 Q, const float* gallery, i6
     MI355_REQUIRE(G >= 1, "rank: G=%lld must be >= 1", (long long)G);
     MI355_REQUIRE(dim >= 1, "rank: dim=%d must be >= 1", dim);
     return OK;
+}
+// mi355_rank_topk and mi355_rank_topk_filtered, under the name who
+static int check_topk_args(const float* queries, i64 Q, const float* gallery, i64 G, int dim, int k, const float* out_val,
+                           const int64_t* out_idx, const char* who) {
+    if (int e = check_rank_args(queries, Q, gallery, G, dim)) return e;
+    MI355_REQUIRE(out_val && out_idx, "%s: null output", who);
+    MI355_REQUIRE(k >= 1 && k <= LARGE_K, "%s: k=%d outside [1,%d]", who, k, LARGE_K);
+    MI355_REQUIRE(k <= G, "%s: k=%d exceeds gallery rows %lld", who, k, (long long)G);
+    return OK;
+}
+
+// mi355_rank_topk and, with filt, mi355_rank_topk_filtered (arguments checked by the caller)
+static int rank_topk(const float* queries, i64 Q, const float* gallery, i64 G, int dim, int gallery_is_normalized, int k, float eps,
+                     i64 idx_offset, float* out_val, i64* out_idx, void* workspace, size_t workspace_bytes, hipStream_t st,
+                     const RankFilter* filt) {
+    const RankWs w = carve(workspace, Q, G, dim, k, split_queries_bytes, !gallery_is_normalized);
+    MI355_REQUIRE(workspace && workspace_bytes >= w.total, "rank_topk: workspace %zu < %zu bytes", workspace_bytes,
+                  w.total);
+    const float* ginv = gallery_is_normalized ? nullptr : w.ginv;
+    return search_blocks(queries, ginv ? gallery : nullptr, Q, G, dim, k, eps, idx_offset, filt, out_val, out_idx, w, st, nullptr,
+                         [&](i64 q0, i64 qn, const RankFilter* f) -> int {
+                             RoctxRange range(w.cand_val ? "rank/cosine gemm + per-tile top-k" : nullptr);
+                             return cos_gemm(w.qn + q0 * dim, (bf16_t*)w.qs, gallery, ginv, w.S, qn, G, dim, st, k, w.cand_val,
+                                             w.cand_idx, f);
+                         });
 }
 
 }  // namespace mi355
@@ -1052,7 +972,7 @@ int mi355_l2_normalize_rows(const float* in, float* out, int64_t rows, int dim, 
 size_t mi355_rank_workspace_bytes(int64_t Q, int64_t G, int dim, int k) {
     if (Q < 1 || G < 1) return 0;
     if (dim <= 0) return topk_ws_bytes(Q, G, k < 1 ? 1 : k) + 256;
-    return carve(nullptr, Q, G, dim, k, true).total;
+    return carve(nullptr, Q, G, dim, k, split_queries_bytes, true).total;
 }
 
 int mi355_cosine_scores(const float* queries, int64_t Q, const float* gallery, int64_t G, int dim,
@@ -1061,7 +981,7 @@ int mi355_cosine_scores(const float* queries, int64_t Q, const float* gallery, i
     if (int e = check_rank_args(queries, Q, gallery, G, dim)) return e;
     MI355_REQUIRE(out, "cosine_scores: null output");
     hipStream_t st = (hipStream_t)stream;
-    RankWs w = carve(workspace, Q, G, dim, 0, !gallery_is_normalized, false);
+    RankWs w = carve(workspace, Q, G, dim, 0, split_queries_bytes, !gallery_is_normalized, false);
     MI355_REQUIRE(workspace && workspace_bytes >= w.total, "cosine_scores: workspace %zu < %zu bytes",
                   workspace_bytes, w.total);
     const int vq = vec_ok(queries, dim) && vec_ok(w.qn, dim);
@@ -1076,87 +996,27 @@ int mi355_cosine_scores(const float* queries, int64_t Q, const float* gallery, i
     const float* ginv = gallery_is_normalized ? nullptr : w.ginv;
     for (i64 qs = 0; qs < Q; qs += 256 * 64) {  // grid.y stays small
         const i64 qn = (Q - qs < 256 * 64) ? Q - qs : 256 * 64;
-        if (int e = cos_gemm(w.qn + qs * dim, w.qs, gallery, ginv, out + qs * G, qn, G, dim, st)) return e;
+        if (int e = cos_gemm(w.qn + qs * dim, (bf16_t*)w.qs, gallery, ginv, out + qs * G, qn, G, dim, st)) return e;
     }
     return OK;
 }
-
-}  // extern "C"
-
-// mi355_rank_topk and, with filt, mi355_rank_topk_filtered (arguments checked by the caller)
-static int rank_topk(const float* queries, int64_t Q, const float* gallery, int64_t G, int dim, int gallery_is_normalized, int k,
-                     float eps, int64_t idx_offset, float* out_val, int64_t* out_idx, void* workspace, size_t workspace_bytes,
-                     void* stream, const RankFilter* filt) {
-    hipStream_t st = (hipStream_t)stream;
-    RankWs w = carve(workspace, Q, G, dim, k, !gallery_is_normalized);
-    MI355_REQUIRE(workspace && workspace_bytes >= w.total, "rank_topk: workspace %zu < %zu bytes", workspace_bytes,
-                  w.total);
-    const int vq = vec_ok(queries, dim) && vec_ok(w.qn, dim);
-    {
-        RoctxRange range("rank/normalize");
-        hipLaunchKernelGGL((k_row_norm<true>), dim3((unsigned)cdiv(Q, 4)), dim3(256), 0, st, queries, w.qn,
-                           (float*)nullptr, (i64)Q, dim, eps, vq);
-        MI355_LAUNCH_CHECK();
-        if (!gallery_is_normalized) {
-            hipLaunchKernelGGL((k_row_norm<false>), dim3((unsigned)cdiv(G, 4)), dim3(256), 0, st, gallery,
-                               (float*)nullptr, w.ginv, (i64)G, dim, eps, vec_ok(gallery, dim));
-            MI355_LAUNCH_CHECK();
-        }
-    }
-    const float* ginv = gallery_is_normalized ? nullptr : w.ginv;
-    const i64 qb = query_block(Q, G, k);
-    const bool fused = fused_select(Q, G, k);
-    const i64 ntiles = cdiv(G, RK_BN);
-    for (i64 qs = 0; qs < Q; qs += qb) {
-        const i64 qn = (Q - qs < qb) ? Q - qs : qb;
-        RankFilter fb{};
-        if (filt) fb = filter_from(*filt, qs);
-        const RankFilter* f = filt ? &fb : nullptr;
-        if (fused) {
-            // per-tile top-k straight from the GEMM's accumulators, then a merge of qn x ntiles x k candidates
-            {
-                RoctxRange range("rank/cosine gemm + per-tile top-k");
-                if (int e = cos_gemm(w.qn + qs * dim, w.qs, gallery, ginv, nullptr, qn, G, dim, st, k, w.cand_val, w.cand_idx, f)) return e;
-            }
-            RoctxRange range("rank/merge candidates");
-            if (int e = topk_select(w.cand_val, nullptr, qn, ntiles * k, ntiles * k, k, idx_offset, out_val + qs * k,
-                                    (i64*)out_idx + qs * k, w.topk, w.topk_bytes, st, w.cand_idx, f))
-                return e;
-            continue;
-        }
-        if (int e = cos_gemm(w.qn + qs * dim, w.qs, gallery, ginv, w.S, qn, G, dim, st)) return e;
-        if (k > SMALL_K) set_rank_path(g_rank_path | MI355_RANK_PATH_BITONIC);
-        if (int e = topk_select(w.S, nullptr, qn, G, G, k, idx_offset, out_val + qs * k, (i64*)out_idx + qs * k,
-                                w.topk, w.topk_bytes, st, nullptr, f))
-            return e;
-    }
-    return OK;
-}
-
-extern "C" {
 
 int mi355_rank_topk(const float* queries, int64_t Q, const float* gallery, int64_t G, int dim,
                     int gallery_is_normalized, int k, float eps, int64_t idx_offset, float* out_val,
                     int64_t* out_idx, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int e = check_rank_args(queries, Q, gallery, G, dim)) return e;
-    MI355_REQUIRE(out_val && out_idx, "rank_topk: null output");
-    MI355_REQUIRE(k >= 1 && k <= LARGE_K, "rank_topk: k=%d outside [1,%d]", k, LARGE_K);
-    MI355_REQUIRE(k <= G, "rank_topk: k=%d exceeds gallery rows %lld", k, (long long)G);
-    return rank_topk(queries, Q, gallery, G, dim, gallery_is_normalized, k, eps, idx_offset, out_val, out_idx, workspace,
-                     workspace_bytes, stream, nullptr);
+    if (int e = check_topk_args(queries, Q, gallery, G, dim, k, out_val, out_idx, "rank_topk")) return e;
+    return rank_topk(queries, Q, gallery, G, dim, gallery_is_normalized, k, eps, idx_offset, out_val, (i64*)out_idx, workspace,
+                     workspace_bytes, (hipStream_t)stream, nullptr);
 }
 
 int mi355_rank_topk_filtered(const float* queries, int64_t Q, const float* gallery, int64_t G, int dim,
                              int gallery_is_normalized, int k, float eps, int64_t idx_offset, const mi355_rank_filter* filter,
                              float* out_val, int64_t* out_idx, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int e = check_rank_args(queries, Q, gallery, G, dim)) return e;
-    MI355_REQUIRE(out_val && out_idx, "rank_topk_filtered: null output");
-    MI355_REQUIRE(k >= 1 && k <= LARGE_K, "rank_topk_filtered: k=%d outside [1,%d]", k, LARGE_K);
-    MI355_REQUIRE(k <= G, "rank_topk_filtered: k=%d exceeds gallery rows %lld", k, (long long)G);
+    if (int e = check_topk_args(queries, Q, gallery, G, dim, k, out_val, out_idx, "rank_topk_filtered")) return e;
     RankFilter f{};
     if (int e = make_filter(filter, idx_offset, "rank_topk_filtered", &f)) return e;
-    return rank_topk(queries, Q, gallery, G, dim, gallery_is_normalized, k, eps, idx_offset, out_val, out_idx, workspace,
-                     workspace_bytes, stream, &f);
+    return rank_topk(queries, Q, gallery, G, dim, gallery_is_normalized, k, eps, idx_offset, out_val, (i64*)out_idx, workspace,
+                     workspace_bytes, (hipStream_t)stream, &f);
 }
 
 int mi355_rank_last_path(void) { return g_rank_path; }
@@ -1194,13 +1054,8 @@ int mi355_gallery_prepare(const float* gallery_normalized, int64_t G, int dim, v
     MI355_REQUIRE(G >= 1 && dim >= 1 && G < ((int64_t)1 << 31) - RK_BN, "gallery_prepare: bad shape G=%lld dim=%d", (long long)G, dim);
     MI355_REQUIRE(planes_bytes >= mi355_gallery_planes_bytes(G, dim), "gallery_prepare: planes buffer %zu < %zu bytes", planes_bytes,
                   mi355_gallery_planes_bytes(G, dim));
-    const int n_steps = cdiv(dim, 16);
-    const i64 n_frag = (i64)cdiv(G, 128) * 4 * n_steps;
-    MI355_REQUIRE(n_frag < ((i64)1 << 31), "gallery_prepare: gallery too large for one call");
-    hipLaunchKernelGGL(k_split_queries, dim3((unsigned)cdiv(n_frag, 4)), dim3(256), 0, (hipStream_t)stream, gallery_normalized,
-                       (bf16_t*)planes, (int)G, dim, n_steps, (int)n_frag);
-    MI355_LAUNCH_CHECK();
-    return OK;
+    MI355_REQUIRE((i64)cdiv(G, 128) * 4 * cdiv(dim, 16) < ((i64)1 << 31), "gallery_prepare: gallery too large for one call");
+    return split_rows(gallery_normalized, G, dim, (bf16_t*)planes, (hipStream_t)stream);
 }
 
 // mi355_rank_topk against a prepared gallery (rows normalised when the planes were made): k <= 8, Q > 4 (the fused selection's
@@ -1214,35 +1069,16 @@ int mi355_rank_topk_prepared(const float* queries, int64_t Q, const void* galler
     MI355_REQUIRE(k >= 1 && k <= G, "rank_topk_prepared: k=%d outside [1, %lld]", k, (long long)G);
     MI355_REQUIRE(fused_select(Q, G, k), "rank_topk_prepared: needs k <= %d and more than 4 queries (got k=%d, Q=%lld)", SMALL_K, k, (long long)Q);
     hipStream_t st = (hipStream_t)stream;
-    RankWs w = carve(workspace, Q, G, dim, k, false);
+    const RankWs w = carve(workspace, Q, G, dim, k, split_queries_bytes, false);
     MI355_REQUIRE(workspace && workspace_bytes >= w.total, "rank_topk_prepared: workspace %zu < %zu bytes", workspace_bytes, w.total);
-    const int vq = vec_ok(queries, dim) && vec_ok(w.qn, dim);
-    {
-        RoctxRange range("rank/normalize");
-        hipLaunchKernelGGL((k_row_norm<true>), dim3((unsigned)cdiv(Q, 4)), dim3(256), 0, st, queries, w.qn, (float*)nullptr, (i64)Q, dim, eps, vq);
-        MI355_LAUNCH_CHECK();
-    }
-    const i64 qb = query_block(Q, G, k);
-    const i64 ntiles = cdiv(G, RK_BN);
-    const int n_steps = cdiv(dim, 16);
-    for (i64 qs = 0; qs < Q; qs += qb) {
-        const i64 qn = (Q - qs < qb) ? Q - qs : qb;
-        {
-            RoctxRange range("rank/cosine gemm (prepared gallery) + per-tile top-k");
-            const int n_frag = cdiv(qn, 128) * 4 * n_steps;
-            hipLaunchKernelGGL(k_split_queries, dim3((unsigned)cdiv(n_frag, 4)), dim3(256), 0, st, w.qn + qs * dim, w.qs, (int)qn, dim, n_steps, n_frag);
-            MI355_LAUNCH_CHECK();
-            set_rank_path(MI355_RANK_PATH_PREPARED | MI355_RANK_PATH_FUSED);
-            const int e = qn > 64 ? launch_pre_fk<2>(w.qs, (const bf16_t*)gallery_planes, (int)qn, G, dim, k, w.cand_val, w.cand_idx, st)
-                                  : launch_pre_fk<1>(w.qs, (const bf16_t*)gallery_planes, (int)qn, G, dim, k, w.cand_val, w.cand_idx, st);
-            if (e) return e;
-        }
-        RoctxRange range("rank/merge candidates");
-        if (int e = topk_select(w.cand_val, nullptr, qn, ntiles * k, ntiles * k, k, idx_offset, out_val + qs * k,
-                                (i64*)out_idx + qs * k, w.topk, w.topk_bytes, st, w.cand_idx))
-            return e;
-    }
-    return OK;
+    return search_blocks(queries, nullptr, Q, G, dim, k, eps, idx_offset, nullptr, out_val, (i64*)out_idx, w, st, nullptr,
+                         [&](i64 q0, i64 qn, const RankFilter*) -> int {
+                             RoctxRange range("rank/cosine gemm (prepared gallery) + per-tile top-k");
+                             if (int e = split_rows(w.qn + q0 * dim, qn, dim, (bf16_t*)w.qs, st)) return e;
+                             set_rank_path(MI355_RANK_PATH_PREPARED | MI355_RANK_PATH_FUSED);
+                             return cos_gemm_tiles<PreparedGemm>({w.qs, gallery_planes, nullptr, nullptr, (int)qn, G, dim, k, w.cand_val,
+                                                                  w.cand_idx, nullptr}, st);
+                         });
 }
 
 int mi355_topk_rows(const float* scores, int64_t Q, int64_t G, int k, int64_t idx_offset, float* out_val,

@@ -1,6 +1,7 @@
 // Shared between the rank kernels (rank.hip: fp32 rows, bf16 planes; rank_f16.hip: fp16 rows): the launch order of the
-// cosine GEMM's tiles, its epilogue (score slab or fused per-tile top-k) and the host side of the top-k selection that
-// merges what the epilogue leaves.  gfx950 only.
+// cosine GEMM's tiles, its epilogue (score slab or fused per-tile top-k), the host side of the top-k selection that
+// merges what the epilogue leaves, the one launcher of every tiled GEMM and the query-block loop of every search.
+// gfx950 only.
 #pragma once
 #include "common.h"
 #include "../../include/mi355_retrieval.h"
@@ -252,5 +253,126 @@ i64 query_block(i64 Q, i64 G, int k);
 int kernel_slots(const void* fn, size_t lds, int* cache, int* slots_out);
 // Column tiles of a GEMM's main launch of whole rounds (the rest go to a tail launch of 64-row tiles).
 int whole_round_tiles(int ntx, int ny, int slots);
+
+// ---- host side of the tiled cosine GEMMs: exact fp32, split bf16 (rank.hip: F32Gemm, SplitGemm, PreparedGemm) and fp16
+// (rank_f16.hip: F16Gemm).  A family F supplies only what differs between them:
+//   F::SLAB, F::FILTERED             whether it has score-slab (FK = 0) / filtered kernels
+//   F::stage_bytes<MT>()             the LDS of its staging buffers
+//   F::kernel<MT, FK, FILT>()        its kernel
+//   F::launch<MT, FK, FILT>(...)     one launch of that kernel over column tiles [x0, x0 + xtiles) x ny query tiles
+
+// One GEMM call over Q queries: the fused per-tile lists (cand_val / cand_idx [Q][cdiv(G, 128)][k]) or, with cand_val null,
+// the score slab S [Q][G] (unfiltered: topk_select filters it).
+struct TileArgs {
+    const void* qry;            // the queries as the family reads them: fp32 rows, bf16 split planes or fp16 planes
+    const void* gal;            // the gallery: fp32 rows, bf16 planes (prepared) or fp16 rows
+    const float* ginv;          // 1 / |gallery row| (fp32 rows), or null
+    float* S;
+    int Q;
+    i64 G;
+    int D;                      // dim (fp16 rows: their padded length ld)
+    int k;
+    float* cand_val;
+    int* cand_idx;
+    const RankFilter* filt;     // the queries' filter (fused selection), or null
+};
+
+constexpr size_t EPI_TILE_BYTES = (size_t)64 * (RK_BN + 4) * sizeof(float);   // the fused selection's transposed score tile
+
+template <class F, int MT, int FK, bool FILT>
+int tile_slots(size_t lds, int* slots_out) {
+    static int slots[MI355_MAX_DEVICES] = {0};   // per instantiation: hipFuncSetAttribute once per device
+    return kernel_slots((const void*)F::template kernel<MT, FK, FILT>(), lds, slots, slots_out);
+}
+
+// Column tiles [x0, ntx) of a GEMM call.  LDS: the staging buffers, or the fused selection's score tile (64 rows at a time)
+// if that is larger; the filtered epilogue keeps the tile's gallery labels behind the score tile, inside the staging
+// buffers, so the filtered kernels request the LDS of the unfiltered ones.
+// Wave quantisation: 1564 tiles on 768 slots run as 2.04 rounds and the 28 tiles of the third round cost a whole round
+// (0.15 ms of 0.83 at Q=256 x 100k on the fp32 loop).  At MT = 2 whole rounds go out as 128-row tiles and the remaining
+// column tiles as a second launch of 64-row tiles (same column tiles, same k order: every score is bit-identical), which
+// halves the tiles' length and doubles their number.
+template <class F, int MT, int FK, bool FILT>
+int launch_tiles(const TileArgs& a, hipStream_t st, int x0 = 0) {
+    constexpr size_t stage = F::template stage_bytes<MT>();
+    static_assert(!FILT || stage >= EPI_TILE_BYTES + FILT_LABELS_BYTES, "the filtered epilogue would grow the GEMM's LDS");
+    constexpr size_t lds = FK > 0 && EPI_TILE_BYTES > stage ? EPI_TILE_BYTES : stage;
+    int slots = 0;
+    if (int e = tile_slots<F, MT, FK, FILT>(lds, &slots)) return e;
+    const int ntx = cdiv(a.G, RK_BN), ny = cdiv(a.Q, 64 * MT);
+    const int x1 = MT == 2 ? whole_round_tiles(ntx, ny, slots) : ntx;
+    if (x1 > x0) {
+        F::template launch<MT, FK, FILT>(dim3((unsigned)(x1 - x0) * (unsigned)ny), lds, st, a, x0, ntx, x1 - x0, ny);
+        MI355_LAUNCH_CHECK();
+    }
+    if constexpr (MT == 2) {
+        if (x1 < ntx) return launch_tiles<F, 1, FK, FILT>(a, st, x1);
+    }
+    return OK;
+}
+
+// The fused selection keeps FK >= k candidates per (query, column tile)
+template <class F, int MT, bool FILT>
+int launch_fk(const TileArgs& a, hipStream_t st) {
+    if (a.k <= 1) return launch_tiles<F, MT, 1, FILT>(a, st);
+    if (a.k <= 2) return launch_tiles<F, MT, 2, FILT>(a, st);
+    if (a.k <= 4) return launch_tiles<F, MT, 4, FILT>(a, st);
+    return launch_tiles<F, MT, 8, FILT>(a, st);
+}
+template <class F, int MT>
+int launch_mt(const TileArgs& a, hipStream_t st) {
+    if constexpr (F::SLAB) {
+        if (!a.cand_val) {
+            TileArgs s = a;
+            s.k = 0;
+            return launch_tiles<F, MT, 0, false>(s, st);
+        }
+    }
+    if constexpr (F::FILTERED) {
+        if (a.filt) return launch_fk<F, MT, true>(a, st);
+    }
+    return launch_fk<F, MT, false>(a, st);
+}
+// A GEMM call of family F: 128-query tiles above 64 queries, 64-query tiles otherwise
+template <class F>
+int cos_gemm_tiles(const TileArgs& a, hipStream_t st) {
+    return a.Q > 64 ? launch_mt<F, 2>(a, st) : launch_mt<F, 1>(a, st);
+}
+
+// ---- one top-k search (mi355_rank_topk[_filtered], mi355_rank_topk_prepared, mi355_rank_topk_f16[_filtered])
+// Scratch of a search, carved from the caller's workspace (ws null: sizes only, total = the bytes it needs).
+struct RankWs {
+    float* qn; void* qs; float* ginv; float* S; float* cand_val; int* cand_idx; void* topk; size_t topk_bytes; size_t total;
+};
+// qs: planes_bytes(queries of one GEMM call, D) bytes for the queries' planes (null: none); need_S = false: no selection
+// (mi355_cosine_scores, k = 0)
+RankWs carve(void* ws, i64 Q, i64 G, int D, int k, size_t (*planes_bytes)(i64, int), bool need_ginv, bool need_S = true);
+// "rank/normalize": the queries into w.qn and, with a gallery, 1 / |row| of its rows into w.ginv
+int normalize_search(const float* queries, i64 Q, const float* gallery, i64 G, int dim, float eps, const RankWs& w,
+                     hipStream_t st);
+
+// Normalises the queries, then per block of query_block(Q, G, k) queries: score(q0, qn, f) writes the fused per-tile lists
+// (fused_select) or the score slab of queries [q0, q0 + qn) (f: their filter, or null), and topk_select merges them into
+// rows [q0, q0 + qn) of out_val / out_idx.  slab_range: roctx range around the top-k of a slab (null: none).
+template <class Score>
+int search_blocks(const float* queries, const float* gallery_to_norm, i64 Q, i64 G, int dim, int k, float eps, i64 idx_offset,
+                  const RankFilter* filt, float* out_val, i64* out_idx, const RankWs& w, hipStream_t st, const char* slab_range,
+                  Score&& score) {
+    if (int e = normalize_search(queries, Q, gallery_to_norm, G, dim, eps, w, st)) return e;
+    const bool fused = fused_select(Q, G, k);
+    const i64 qb = query_block(Q, G, k), rowlen = fused ? cdiv(G, RK_BN) * (i64)k : G;
+    for (i64 q0 = 0; q0 < Q; q0 += qb) {
+        const i64 qn = (Q - q0 < qb) ? Q - q0 : qb;
+        const RankFilter fb = filt ? filter_from(*filt, q0) : RankFilter{};
+        const RankFilter* f = filt ? &fb : nullptr;
+        if (int e = score(q0, qn, f)) return e;
+        if (!fused && k > SMALL_K) set_rank_path(mi355_rank_last_path() | MI355_RANK_PATH_BITONIC);
+        RoctxRange range(fused ? "rank/merge candidates" : slab_range);
+        if (int e = topk_select(fused ? w.cand_val : w.S, nullptr, qn, rowlen, rowlen, k, idx_offset, out_val + q0 * k,
+                                out_idx + q0 * k, w.topk, w.topk_bytes, st, w.cand_idx, f))
+            return e;
+    }
+    return OK;
+}
 
 }  // namespace mi355

@@ -174,102 +174,31 @@ __global__ __launch_bounds__(256) void k_cos_gemv_f16(const float* __restrict__ 
 // =====================================================================================
 constexpr size_t F16_GEMV_LDS = 64 * 1024;
 
-static size_t f16_planes_bytes(i64 Q, int ld) { return (size_t)cdiv(Q, 128) * 4 * (ld / 16) * 2 * 1024; }
+static size_t f16_planes_bytes(i64 Q, int D) { return (size_t)cdiv(Q, 128) * 4 * (f16_ld(D) / 16) * 2 * 1024; }
 static bool f16_gemv(i64 Q, int ld) { return Q <= 4 && (size_t)Q * ld * sizeof(float) <= F16_GEMV_LDS; }
 
-struct F16Ws {
-    float* qn; f16* qs; float* S; float* cand_val; int* cand_idx; void* topk; size_t topk_bytes; size_t total;
+// The tiled GEMM over fp16 rows (launch_tiles, rank_common.h); qry: the queries' fp16 planes, gal: the rows, D: their length ld
+struct F16Gemm {
+    static constexpr bool SLAB = true, FILTERED = true;
+    template <int MT> static constexpr size_t stage_bytes() {   // A ring of 2, B ring of 3
+        return (size_t)2 * (64 * MT / 32) * 8 * 1024 + (size_t)3 * RK_BN * F16_KSTEP * 2;
+    }
+    template <int MT, int FK, bool FILT> static const void* kernel() {
+        if constexpr (FILT) return (const void*)k_cos_gemm_f16_filt<MT, FK>;
+        else return (const void*)k_cos_gemm_f16<MT, FK>;
+    }
+    template <int MT, int FK, bool FILT>
+    static void launch(dim3 grid, size_t lds, hipStream_t st, const TileArgs& a, int x0, int ntx, int xtiles, int ny) {
+        const f16* qs = (const f16*)a.qry;
+        const f16* gal = (const f16*)a.gal;
+        if constexpr (FILT)
+            hipLaunchKernelGGL((k_cos_gemm_f16_filt<MT, FK>), grid, dim3(256), lds, st, qs, gal, a.Q, a.G, a.D, a.k, a.cand_val,
+                               a.cand_idx, x0, ntx, xtiles, ny, *a.filt);
+        else
+            hipLaunchKernelGGL((k_cos_gemm_f16<MT, FK>), grid, dim3(256), lds, st, qs, gal, a.S, a.Q, a.G, a.D, a.k, a.cand_val,
+                               a.cand_idx, x0, ntx, xtiles, ny);
+    }
 };
-static F16Ws carve_f16(void* ws, i64 Q, i64 G, int D, int k) {
-    F16Ws r{};
-    const bool fused = fused_select(Q, G, k);
-    const i64 qb = query_block(Q, G, k);
-    const i64 ntiles = cdiv(G, RK_BN);
-    size_t off = 0;
-    char* base = ws ? (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255) : nullptr;
-    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align_up(bytes, 256); return p; };
-    r.qn = (float*)take((size_t)Q * D * sizeof(float));
-    r.qs = (f16*)take(f16_gemv(Q, f16_ld(D)) ? 0 : f16_planes_bytes(qb, f16_ld(D)));
-    if (fused) {
-        const size_t ncand = (size_t)qb * ntiles * k;
-        r.cand_val = (float*)take(ncand * sizeof(float));
-        r.cand_idx = (int*)take(ncand * sizeof(int));
-        r.topk_bytes = topk_ws_bytes(qb, ntiles * k, k);
-    } else {
-        r.S = (float*)take((size_t)qb * G * sizeof(float));
-        r.topk_bytes = topk_ws_bytes(qb, G, k);
-    }
-    r.topk = take(r.topk_bytes);
-    r.total = off + 256;
-    return r;
-}
-
-template <int MT>
-constexpr size_t f16_stage_bytes() { return (size_t)2 * (64 * MT / 32) * 8 * 1024 + (size_t)3 * RK_BN * F16_KSTEP * 2; }   // A ring of 2, B ring of 3
-// the filtered epilogue's score tile + gallery labels stay inside the staging buffers: same LDS request as unfiltered
-static_assert(f16_stage_bytes<1>() >= (size_t)64 * (RK_BN + 4) * sizeof(float) + FILT_LABELS_BYTES, "filtered epilogue grows the LDS");
-template <int MT>
-static size_t f16_lds(bool fk) {
-    const size_t stage = f16_stage_bytes<MT>();
-    const size_t tile = fk ? (size_t)64 * (RK_BN + 4) * sizeof(float) : 0;
-    return stage > tile ? stage : tile;
-}
-template <int MT, int FK, bool FILT = false>
-static int f16_slots(size_t lds, int* slots_out) {
-    static int slots[MI355_MAX_DEVICES] = {0};
-    if constexpr (FILT) return kernel_slots((const void*)k_cos_gemm_f16_filt<MT, FK>, lds, slots, slots_out);
-    else return kernel_slots((const void*)k_cos_gemm_f16<MT, FK>, lds, slots, slots_out);
-}
-
-// Whole rounds of 128-query tiles in one launch, the remaining column tiles as 64-query tiles (every score is the same:
-// same column tiles, same k order), as launch_split does.
-template <int MT, int FK, bool FILT = false>
-static int launch_f16(const f16* qs, const f16* gal, float* S, int Q, i64 G, int ld, int k, float* cand_val, int* cand_idx,
-                      hipStream_t st, const RankFilter* filt = nullptr) {
-    constexpr int BM = 64 * MT;
-    const size_t lds = f16_lds<MT>(FK > 0);
-    int slots = 0;
-    if (int e = f16_slots<MT, FK, FILT>(lds, &slots)) return e;
-    const int ntx = cdiv(G, RK_BN), ny = cdiv(Q, BM);
-    const int xm = MT == 2 ? whole_round_tiles(ntx, ny, slots) : ntx;
-    if (xm > 0) {
-        if constexpr (FILT)
-            hipLaunchKernelGGL((k_cos_gemm_f16_filt<MT, FK>), dim3((unsigned)xm * (unsigned)ny), dim3(256), lds, st, qs, gal, Q, G, ld,
-                               k, cand_val, cand_idx, 0, ntx, xm, ny, *filt);
-        else
-            hipLaunchKernelGGL((k_cos_gemm_f16<MT, FK>), dim3((unsigned)xm * (unsigned)ny), dim3(256), lds, st, qs, gal, S, Q, G, ld,
-                               k, cand_val, cand_idx, 0, ntx, xm, ny);
-        MI355_LAUNCH_CHECK();
-    }
-    if (xm < ntx) {
-        const size_t lds1 = f16_lds<1>(FK > 0);
-        int slots1 = 0;
-        if (int e = f16_slots<1, FK, FILT>(lds1, &slots1)) return e;
-        if constexpr (FILT)
-            hipLaunchKernelGGL((k_cos_gemm_f16_filt<1, FK>), dim3((unsigned)(ntx - xm) * (unsigned)cdiv(Q, 64)), dim3(256), lds1, st,
-                               qs, gal, Q, G, ld, k, cand_val, cand_idx, xm, ntx, ntx - xm, (int)cdiv(Q, 64), *filt);
-        else
-            hipLaunchKernelGGL((k_cos_gemm_f16<1, FK>), dim3((unsigned)(ntx - xm) * (unsigned)cdiv(Q, 64)), dim3(256), lds1, st, qs,
-                               gal, S, Q, G, ld, k, cand_val, cand_idx, xm, ntx, ntx - xm, (int)cdiv(Q, 64));
-        MI355_LAUNCH_CHECK();
-    }
-    return OK;
-}
-template <int MT>
-static int launch_f16_fk(const f16* qs, const f16* gal, float* S, int Q, i64 G, int ld, int k, float* cand_val, int* cand_idx,
-                         hipStream_t st, const RankFilter* filt = nullptr) {
-    if (!cand_val) return launch_f16<MT, 0>(qs, gal, S, Q, G, ld, 0, nullptr, nullptr, st);
-    if (filt) {
-        if (k <= 1) return launch_f16<MT, 1, true>(qs, gal, S, Q, G, ld, k, cand_val, cand_idx, st, filt);
-        if (k <= 2) return launch_f16<MT, 2, true>(qs, gal, S, Q, G, ld, k, cand_val, cand_idx, st, filt);
-        if (k <= 4) return launch_f16<MT, 4, true>(qs, gal, S, Q, G, ld, k, cand_val, cand_idx, st, filt);
-        return launch_f16<MT, 8, true>(qs, gal, S, Q, G, ld, k, cand_val, cand_idx, st, filt);
-    }
-    if (k <= 1) return launch_f16<MT, 1>(qs, gal, S, Q, G, ld, k, cand_val, cand_idx, st);
-    if (k <= 2) return launch_f16<MT, 2>(qs, gal, S, Q, G, ld, k, cand_val, cand_idx, st);
-    if (k <= 4) return launch_f16<MT, 4>(qs, gal, S, Q, G, ld, k, cand_val, cand_idx, st);
-    return launch_f16<MT, 8>(qs, gal, S, Q, G, ld, k, cand_val, cand_idx, st);
-}
 
 }  // namespace mi355
 
@@ -298,7 +227,7 @@ int mi355_gallery_to_f16(const float* rows, int64_t G, int dim, int rows_are_nor
 
 size_t mi355_rank_f16_workspace_bytes(int64_t Q, int64_t G, int dim, int k) {
     if (Q < 1 || G < 1 || dim < 1 || k < 1 || k > LARGE_K) return 0;
-    return carve_f16(nullptr, Q, G, dim, k).total;
+    return carve(nullptr, Q, G, dim, k, f16_gemv(Q, f16_ld(dim)) ? nullptr : f16_planes_bytes, false).total;
 }
 
 }  // extern "C"
@@ -317,59 +246,35 @@ static int rank_topk_f16(const float* queries, int64_t Q, const void* gallery_f1
     RankFilter fall{};
     if (filter)
         if (int e = make_filter(filter, idx_offset, who, &fall)) return e;
-    const RankFilter* filt = filter ? &fall : nullptr;
     if (Q == 0) return OK;
-    const F16Ws w = carve_f16(workspace, Q, G, dim, k);
+    const int ld = f16_ld(dim);
+    const bool gemv = f16_gemv(Q, ld);   // (Q <= 4: a single query block)
+    const RankWs w = carve(workspace, Q, G, dim, k, gemv ? nullptr : f16_planes_bytes, false);
     MI355_REQUIRE(workspace && workspace_bytes >= w.total, "%s: workspace %zu < %zu bytes", who, workspace_bytes, w.total);
     hipStream_t st = (hipStream_t)stream;
     const f16* gal = (const f16*)gallery_f16;
-    const int ld = f16_ld(dim);
-    {
-        RoctxRange range("rank/normalize");
-        if (int e = mi355_l2_normalize_rows(queries, w.qn, Q, dim, eps, stream)) return e;   // as mi355_rank_topk normalises
-    }
-    if (f16_gemv(Q, ld)) {
-        {
-            RoctxRange range("rank/cosine gemv (fp16 gallery)");
-            const size_t lds = (size_t)Q * ld * sizeof(float);
-            const unsigned blocks = (unsigned)(cdiv(G, 4) < 4096 ? cdiv(G, 4) : 4096);
+    return search_blocks(
+        queries, nullptr, Q, G, dim, k, eps, idx_offset, filter ? &fall : nullptr, out_val, (i64*)out_idx, w, st, "rank/top-k",
+        [&](i64 q0, i64 qn, const RankFilter* f) -> int {
+            if (gemv) {
+                RoctxRange range("rank/cosine gemv (fp16 gallery)");
+                const size_t lds = (size_t)qn * ld * sizeof(float);
+                const unsigned blocks = (unsigned)(cdiv(G, 4) < 4096 ? cdiv(G, 4) : 4096);
 #define GEMV_F16(NQ) hipLaunchKernelGGL((k_cos_gemv_f16<NQ>), dim3(blocks), dim3(256), lds, st, w.qn, gal, w.S, (i64)G, dim, ld)
-            if (Q == 1) GEMV_F16(1); else if (Q == 2) GEMV_F16(2); else if (Q == 3) GEMV_F16(3); else GEMV_F16(4);
+                if (qn == 1) GEMV_F16(1); else if (qn == 2) GEMV_F16(2); else if (qn == 3) GEMV_F16(3); else GEMV_F16(4);
 #undef GEMV_F16
-            MI355_LAUNCH_CHECK();
-        }
-        set_rank_path(MI355_RANK_PATH_F16_GEMV | (k > SMALL_K ? MI355_RANK_PATH_BITONIC : 0));
-        RoctxRange range("rank/top-k");
-        return topk_select(w.S, nullptr, Q, G, G, k, idx_offset, out_val, (i64*)out_idx, w.topk, w.topk_bytes, st, nullptr, filt);
-    }
-    const i64 qb = query_block(Q, G, k);
-    const bool fused = fused_select(Q, G, k);
-    const i64 ntiles = cdiv(G, RK_BN);
-    const int n_sub = ld / 16;
-    set_rank_path(MI355_RANK_PATH_F16_GEMM | (fused ? MI355_RANK_PATH_FUSED : k > SMALL_K ? MI355_RANK_PATH_BITONIC : 0));
-    for (i64 q0 = 0; q0 < Q; q0 += qb) {
-        const i64 qn = (Q - q0 < qb) ? Q - q0 : qb;
-        RankFilter fb{};
-        if (filt) fb = filter_from(*filt, q0);
-        const RankFilter* f = filt ? &fb : nullptr;
-        {
-            RoctxRange range(fused ? "rank/cosine gemm (fp16 gallery) + per-tile top-k" : "rank/cosine gemm (fp16 gallery)");
-            const int n_frag = cdiv(qn, 128) * 4 * n_sub;
-            hipLaunchKernelGGL(k_split_queries_f16, dim3((unsigned)cdiv(n_frag, 4)), dim3(256), 0, st, w.qn + q0 * dim, w.qs,
+                MI355_LAUNCH_CHECK();
+                set_rank_path(MI355_RANK_PATH_F16_GEMV);
+                return OK;
+            }
+            RoctxRange range(w.cand_val ? "rank/cosine gemm (fp16 gallery) + per-tile top-k" : "rank/cosine gemm (fp16 gallery)");
+            set_rank_path(MI355_RANK_PATH_F16_GEMM | (w.cand_val ? MI355_RANK_PATH_FUSED : 0));
+            const int n_sub = ld / 16, n_frag = cdiv(qn, 128) * 4 * n_sub;
+            hipLaunchKernelGGL(k_split_queries_f16, dim3((unsigned)cdiv(n_frag, 4)), dim3(256), 0, st, w.qn + q0 * dim, (f16*)w.qs,
                                (int)qn, dim, n_sub, n_frag);
             MI355_LAUNCH_CHECK();
-            const int e = qn > 64 ? launch_f16_fk<2>(w.qs, gal, w.S, (int)qn, G, ld, k, w.cand_val, w.cand_idx, st, f)
-                                  : launch_f16_fk<1>(w.qs, gal, w.S, (int)qn, G, ld, k, w.cand_val, w.cand_idx, st, f);
-            if (e) return e;
-        }
-        RoctxRange range(fused ? "rank/merge candidates" : "rank/top-k");
-        const int e = fused ? topk_select(w.cand_val, nullptr, qn, ntiles * k, ntiles * k, k, idx_offset, out_val + q0 * k,
-                                          (i64*)out_idx + q0 * k, w.topk, w.topk_bytes, st, w.cand_idx, f)
-                            : topk_select(w.S, nullptr, qn, G, G, k, idx_offset, out_val + q0 * k, (i64*)out_idx + q0 * k, w.topk,
-                                          w.topk_bytes, st, nullptr, f);
-        if (e) return e;
-    }
-    return OK;
+            return cos_gemm_tiles<F16Gemm>({w.qs, gal, nullptr, w.S, (int)qn, G, ld, k, w.cand_val, w.cand_idx, f}, st);
+        });
 }
 
 extern "C" {

@@ -573,8 +573,6 @@ class Gallery:
         if (not filtered and p is not None and self._prepared_rows == self.rows
                 and PreparedGallery.supports(queries.shape[0], k)):
             return p.search(queries, k, self.eps, idx_offset)
-        if not filtered:
-            return cosine_topk(queries, self.data, k, self.eps, gallery_is_normalized=True, idx_offset=idx_offset)
         return cosine_topk(queries, self.data, k, self.eps, gallery_is_normalized=True, idx_offset=idx_offset,
                            query_labels=query_labels, gallery_labels=self.labels, label_filter=label_filter, exclude=exclude)
 

@@ -114,9 +114,8 @@ class ShardedGallery:
     def _local_topk(self, queries, k):
         if self.gallery_f16 is not None:
             return self.gallery_f16.search(queries, k)
-        if self.prepared is not None:
-            return self.ops.local_topk(queries, self.local, k, 0, prepared=self.prepared)
-        return self.ops.local_topk(queries, self.local, k, 0)
+        planes = {} if self.prepared is None else {"prepared": self.prepared}   # (an injected ops may take no prepared=)
+        return self.ops.local_topk(queries, self.local, k, 0, **planes)
 
     def _local_candidates(self, queries, k):
         """(Q, k, 2) int32: [..., 0] = the f32 score's bits, [..., 1] = LOCAL row index; a short (or empty) shard pads to

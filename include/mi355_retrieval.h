@@ -69,6 +69,10 @@ int mi355_rank_topk(const float* queries, int64_t Q, const float* gallery, int64
                     void* stream);
 
 /* Scores only: out[Q][G] fp32 cosine matrix (same kernel as above without the selection). */
+int mi355_cosine_scores(const float* queries, int64_t Q, const float* gallery, int64_t G, int dim,
+                        int gallery_is_normalized, float eps, float* out, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
 /* Prepared gallery for RESIDENT galleries (the reference re-reads and re-normalises its gallery for every query,
  * train/train.py:250; here it is normalised once when rows are added, and - optionally - split once into the three bf16 planes
  * the cosine GEMM multiplies, stored in the GEMM's fragment order: 6 B per element, mi355_gallery_planes_bytes(G, dim) bytes).
@@ -148,10 +152,6 @@ int mi355_clear_pads(float* val, int64_t* idx, int64_t n, int64_t lo, int64_t hi
  * queries with R <= 0 get [k, 0, 0]. */
 int mi355_retrieval_metrics(const int64_t* idx, int64_t Q, int k, const int64_t* query_cls, const int64_t* gallery_cls,
                             int64_t G, const int64_t* R, double* per_query, void* stream);
-
-int mi355_cosine_scores(const float* queries, int64_t Q, const float* gallery, int64_t G, int dim,
-                        int gallery_is_normalized, float eps, float* out, void* workspace,
-                        size_t workspace_bytes, void* stream);
 
 /* Row-wise top-k of an explicit score matrix scores[Q][G] (torch.topk, train/train.py:251).
  * workspace: mi355_rank_workspace_bytes(Q, G, 0, k). */
