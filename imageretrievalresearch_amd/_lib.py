@@ -61,6 +61,14 @@ PROTOTYPES = {
                                                C.POINTER(RankFilter), vp, vp, vp, C.c_size_t, vp]),
     "mi355_rank_last_path": (C.c_int, []),
     "mi355_clear_pads": (C.c_int, [vp, vp, C.c_int64, C.c_int64, C.c_int64, vp]),
+    "mi355_roc_pairs_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int]),
+    "mi355_roc_pairs_hist": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_float, vp, vp, vp, C.c_int64,
+                                       C.POINTER(C.c_double), vp, C.c_int, vp, vp, C.c_size_t, vp]),
+    "mi355_roc_pairs_f16_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int]),
+    "mi355_roc_pairs_hist_f16": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_float, vp, vp, vp, C.c_int64,
+                                           C.POINTER(C.c_double), vp, C.c_int, vp, vp, C.c_size_t, vp]),
+    "mi355_roc_scores_hist": (C.c_int, [vp, C.c_int, C.c_int64, vp, C.POINTER(C.c_double), vp, C.c_int, vp, vp]),
+    "mi355_roc_finalize": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp]),
     "mi355_retrieval_metrics": (C.c_int, [vp, C.c_int64, C.c_int, vp, vp, C.c_int64, vp, vp, vp]),
     "mi355_cosine_scores": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_float, vp, vp,
                                       C.c_size_t, vp]),

@@ -148,6 +148,19 @@ __global__ __launch_bounds__(256) void k_cos_gemm_filt(const float* __restrict__
     float* const S = nullptr;
 #include "rank_gemm_f32.inc"
 }
+// The histogram twin (mi355_roc_pairs_hist): the same body, the histogram epilogue (its overload takes RocArgs as `flt`)
+template <int MT, int RK_BK, bool VEC>
+__global__ __launch_bounds__(256) void k_cos_gemm_roc(const float* __restrict__ Qn, const float* __restrict__ Gal,
+                                                      const float* __restrict__ ginv, int Q, i64 G, int D, int x0, int ntx,
+                                                      int xtiles, int ny, RocArgs flt) {
+    constexpr int FK = FK_ROC;
+    constexpr bool FILT = false;
+    float* const S = nullptr;
+    const int k = 0;
+    float* const cand_val = nullptr;
+    int* const cand_idx = nullptr;
+#include "rank_gemm_f32.inc"
+}
 
 // =====================================================================================
 // The same GEMM on the bf16 matrix pipe (three-way split, six products; see split3 above).  Same block / wave tiling and
@@ -183,6 +196,19 @@ __global__ __launch_bounds__(256, 3) void k_cos_gemm_split_filt(const bf16_t* __
                                                                 int xtiles, int ny, RankFilter flt) {
     constexpr bool FILT = true;
     float* const S = nullptr;
+#include "rank_gemm_split.inc"
+}
+template <int MT>
+__global__ __launch_bounds__(256, 3) void k_cos_gemm_split_roc(const bf16_t* __restrict__ Qs, const float* __restrict__ Gal,
+                                                               const float* __restrict__ ginv, int Q, i64 G, int D, int x0,
+                                                               int ntx, int n_steps, const float* __restrict__ zeros, int xtiles,
+                                                               int ny, RocArgs flt) {
+    constexpr int FK = FK_ROC;
+    constexpr bool FILT = false;
+    float* const S = nullptr;
+    const int k = 0;
+    float* const cand_val = nullptr;
+    int* const cand_idx = nullptr;
 #include "rank_gemm_split.inc"
 }
 
@@ -806,18 +832,22 @@ int whole_round_tiles(int ntx, int ny, int slots) {
 // with 256 x 128 tiles, one per CU).  64-query tiles use BK = 32.
 template <bool VEC>
 struct F32Gemm {
-    static constexpr bool SLAB = true, FILTERED = true;
+    static constexpr bool SLAB = true, FILTERED = true, ROC = true;
     template <int MT> static constexpr int BK = MT == 2 ? 16 : 32;
     template <int MT> static constexpr size_t stage_bytes() { return (size_t)2 * (64 * MT + RK_BN) * (BK<MT> + 4) * sizeof(float); }
     template <int MT, int FK, bool FILT> static const void* kernel() {
-        if constexpr (FILT) return (const void*)k_cos_gemm_filt<MT, BK<MT>, VEC, FK>;
+        if constexpr (FK == FK_ROC) return (const void*)k_cos_gemm_roc<MT, BK<MT>, VEC>;
+        else if constexpr (FILT) return (const void*)k_cos_gemm_filt<MT, BK<MT>, VEC, FK>;
         else return (const void*)k_cos_gemm<MT, BK<MT>, VEC, FK>;
     }
     template <int MT, int FK, bool FILT>
     static void launch(dim3 grid, size_t lds, hipStream_t st, const TileArgs& a, int x0, int ntx, int xtiles, int ny) {
         const float* qn = (const float*)a.qry;
         const float* gal = (const float*)a.gal;
-        if constexpr (FILT)
+        if constexpr (FK == FK_ROC)
+            hipLaunchKernelGGL((k_cos_gemm_roc<MT, BK<MT>, VEC>), grid, dim3(256), lds, st, qn, gal, a.ginv, a.Q, a.G, a.D, x0, ntx,
+                               xtiles, ny, *a.roc);
+        else if constexpr (FILT)
             hipLaunchKernelGGL((k_cos_gemm_filt<MT, BK<MT>, VEC, FK>), grid, dim3(256), lds, st, qn, gal, a.ginv, a.Q, a.G, a.D, a.k,
                                a.cand_val, a.cand_idx, x0, ntx, xtiles, ny, *a.filt);
         else
@@ -828,12 +858,13 @@ struct F32Gemm {
 
 // Split-bf16 loop (qry: the split planes of the queries, split_rows; gal: fp32 rows with D % 4 == 0)
 struct SplitGemm {
-    static constexpr bool SLAB = true, FILTERED = true;
+    static constexpr bool SLAB = true, FILTERED = true, ROC = true;
     template <int MT> static constexpr size_t stage_bytes() {   // A ring of 2 (3 at MT = 1), B ring of 3
         return (size_t)(MT == 1 ? 3 : 2) * (64 * MT / 32) * 3 * 1024 + (size_t)3 * RK_BN * 16 * sizeof(float);
     }
     template <int MT, int FK, bool FILT> static const void* kernel() {
-        if constexpr (FILT) return (const void*)k_cos_gemm_split_filt<MT, FK>;
+        if constexpr (FK == FK_ROC) return (const void*)k_cos_gemm_split_roc<MT>;
+        else if constexpr (FILT) return (const void*)k_cos_gemm_split_filt<MT, FK>;
         else return (const void*)k_cos_gemm_split<MT, FK>;
     }
     template <int MT, int FK, bool FILT>
@@ -842,7 +873,10 @@ struct SplitGemm {
         const float* gal = (const float*)a.gal;
         const int n_steps = cdiv(a.D, 16);
         const float* zeros = reinterpret_cast<const float*>(qs + (size_t)cdiv(a.Q, 128) * 4 * n_steps * 3 * 512);
-        if constexpr (FILT)
+        if constexpr (FK == FK_ROC)
+            hipLaunchKernelGGL((k_cos_gemm_split_roc<MT>), grid, dim3(256), lds, st, qs, gal, a.ginv, a.Q, a.G, a.D, x0, ntx, n_steps,
+                               zeros, xtiles, ny, *a.roc);
+        else if constexpr (FILT)
             hipLaunchKernelGGL((k_cos_gemm_split_filt<MT, FK>), grid, dim3(256), lds, st, qs, gal, a.ginv, a.Q, a.G, a.D, a.k,
                                a.cand_val, a.cand_idx, x0, ntx, n_steps, zeros, xtiles, ny, *a.filt);
         else
@@ -853,7 +887,7 @@ struct SplitGemm {
 
 // Prepared gallery (qry: the split planes of the queries; gal: the gallery's planes): fused selection only, unfiltered
 struct PreparedGemm {
-    static constexpr bool SLAB = false, FILTERED = false;
+    static constexpr bool SLAB = false, FILTERED = false, ROC = false;
     template <int MT> static constexpr size_t stage_bytes() {   // A ring of 2 (3 at MT = 1), B ring of 3
         return (size_t)(MT == 1 ? 3 : 2) * (64 * MT / 32) * 3 * 1024 + (size_t)3 * (RK_BN / 32) * 3 * 1024;
     }
@@ -878,12 +912,13 @@ static bool rank_exact_f32() {
 // S != nullptr: score slab.  cand_val / cand_idx != nullptr: fused per-tile top-k lists [Q][cdiv(G,128)][k] (Q > 4 only).
 // qs: scratch for the split planes of these Q queries (split_queries_bytes(Q, D)); may be null for Q <= 4.
 // filt (fused selection only; a score slab is unfiltered): the filter of these Q queries.
+// roc (S null): the histogram of these Q queries; always on the tiles (the GEMV's bits differ), any Q.
 static int cos_gemm(const float* qn, bf16_t* qs, const float* gal, const float* ginv, float* S, i64 Q, i64 G, int D,
                     hipStream_t st, int k = 0, float* cand_val = nullptr, int* cand_idx = nullptr,
-                    const RankFilter* filt = nullptr) {
+                    const RankFilter* filt = nullptr, const RocArgs* roc = nullptr) {
     const bool vec = vec_ok(qn, D) && vec_ok(gal, D);
     const int fused_bit = cand_val ? MI355_RANK_PATH_FUSED : 0;
-    if (!cand_val && Q <= 4 && (size_t)Q * D * sizeof(float) <= 60 * 1024) {
+    if (!cand_val && !roc && Q <= 4 && (size_t)Q * D * sizeof(float) <= 60 * 1024) {
         set_rank_path(MI355_RANK_PATH_GEMV);
         const size_t lds = (size_t)Q * D * sizeof(float);
         const unsigned blocks = (unsigned)(cdiv(G, 4) < 4096 ? cdiv(G, 4) : 4096);
@@ -893,7 +928,7 @@ static int cos_gemm(const float* qn, bf16_t* qs, const float* gal, const float* 
         MI355_LAUNCH_CHECK();
         return OK;
     }
-    TileArgs a{qn, gal, ginv, S, (int)Q, G, D, k, cand_val, cand_idx, filt};
+    TileArgs a{qn, gal, ginv, S, (int)Q, G, D, k, cand_val, cand_idx, filt, roc};
     if (qs && vec_ok(gal, D) && !rank_exact_f32()) {
         if (int e = split_rows(qn, Q, D, qs, st)) return e;
         set_rank_path(MI355_RANK_PATH_SPLIT | fused_bit);
@@ -1020,6 +1055,43 @@ int mi355_rank_topk_filtered(const float* queries, int64_t Q, const float* galle
 }
 
 int mi355_rank_last_path(void) { return g_rank_path; }
+
+size_t mi355_roc_pairs_workspace_bytes(int64_t Q, int64_t G, int dim) {
+    if (Q < 1 || G < 1 || dim < 1) return 0;
+    // the normalised queries, the split planes of one GEMM call (roc_query_block <= 256 * 64 queries), 1 / |row| of the
+    // gallery rows: no slab, no candidates
+    return carve(nullptr, Q, G, dim, 0, split_queries_bytes, true, false).total;
+}
+
+int mi355_roc_pairs_hist(const float* queries, int64_t Q, const float* gallery, int64_t G, int dim, int gallery_is_normalized,
+                         float eps, const int64_t* query_labels, const int64_t* gallery_labels, const int64_t* exclude,
+                         int64_t idx_offset, const double* thresholds, const double* thresholds_dev, int T, int64_t* hist,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "roc_pairs_hist";
+    RocArgs roc{};
+    if (int e = roc_check_thresholds(thresholds, T, who, &roc)) return e;
+    if (int e = roc_check_pairs(query_labels, gallery_labels, exclude, idx_offset, thresholds_dev, hist, who, &roc)) return e;
+    MI355_REQUIRE(queries && gallery, "%s: null queries/gallery pointer", who);
+    MI355_REQUIRE(Q >= 1 && G >= 1 && dim >= 1, "%s: bad shape Q=%lld G=%lld dim=%d", who, (long long)Q, (long long)G, dim);
+    MI355_REQUIRE(Q <= INT_MAX && G < ((int64_t)1 << 31) - RK_BN, "%s: shape too large Q=%lld G=%lld", who, (long long)Q,
+                  (long long)G);
+    const i64 qb = roc_query_block(Q, G);
+    const RankWs w = carve(workspace, Q, G, dim, 0, split_queries_bytes, !gallery_is_normalized, false);
+    const size_t need = mi355_roc_pairs_workspace_bytes(Q, G, dim);
+    MI355_REQUIRE(workspace && workspace_bytes >= need, "%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
+    hipStream_t st = (hipStream_t)stream;
+    MI355_CHECK_HIP(hipMemsetAsync(hist, 0, (size_t)2 * (T + 1) * sizeof(int64_t), st));
+    const float* ginv = gallery_is_normalized ? nullptr : w.ginv;
+    if (int e = normalize_search(queries, Q, ginv ? gallery : nullptr, G, dim, eps, w, st)) return e;
+    for (i64 q0 = 0; q0 < Q; q0 += qb) {
+        const i64 qn = (Q - q0 < qb) ? Q - q0 : qb;
+        const RocArgs rb = roc_from(roc, q0);
+        RoctxRange range("roc/cosine gemm + histogram");
+        if (int e = cos_gemm(w.qn + q0 * dim, (bf16_t*)w.qs, gallery, ginv, nullptr, qn, G, dim, st, 0, nullptr, nullptr, nullptr, &rb))
+            return e;
+    }
+    return OK;
+}
 
 int mi355_clear_pads(float* val, int64_t* idx, int64_t n, int64_t lo, int64_t hi, void* stream) {
     MI355_REQUIRE(val && idx, "clear_pads: null pointer");

@@ -206,6 +206,114 @@ __device__ __forceinline__ void cos_gemm_epilogue(f32x16 (&acc)[MT][2], float* s
     }
 }
 
+// ---- verification ROC (mi355_roc_pairs_hist[_f16]): the third epilogue mode bins every (query, gallery row) score of the
+// tile by (genuine / impostor, threshold) into a per-workgroup histogram; the score slab never exists.
+// Bin b of a score s = the number of thresholds t with s >= t (0 .. T), compared in fp32 against the fp32 CEILING of each
+// float64 t (the smallest float f with (double)f >= t), which is exactly the float64 comparison for every fp32 score.
+// A NaN score lands in bin 0 (below every threshold).
+constexpr int ROC_MAX_T = MI355_ROC_MAX_THRESHOLDS;
+constexpr int ROC_SUB_T = 1024;                         // T <= this: one sub-histogram per wave (less LDS-atomic contention)
+constexpr int ROC_BIN_WORDS = ROC_MAX_T + 4;            // = 4 * (ROC_SUB_T + 1): either layout fits
+constexpr int FK_ROC = -1;                              // the histogram mode in the launcher's FK slot
+
+__host__ __device__ __forceinline__ float roc_ceil_f32(double t) {
+    float f = (float)t;                                 // round to nearest
+    if ((double)f < t) f = nextafterf(f, INFINITY);
+    return f;
+}
+
+struct RocArgs {
+    const i64* qlab;            // [Q] labels of the queries of this call (the host shifts them per query block)
+    const i64* glab;            // [G] labels of the gallery rows
+    const i64* excl;            // [Q] global row indices (< 0: none), or null: pair (q, j) is not counted if excl[q] == j + idx_offset
+    i64 idx_offset;
+    const double* thr;          // [T] the thresholds, ascending, finite
+    unsigned long long* hist;   // [2][T + 1]: genuine / impostor pairs per bin (accumulated)
+    int T;
+    int top;                    // largest power of two <= T (binary search)
+    int uniform;                // 1: guess the bin as 1 + (s - ceil(thr[0])) * scale, then fix it with compares
+    float scale;
+};
+
+// The bin of score s against the ascending table tab[T] in LDS (fp32 ceilings; float64 thresholds for float64 scores)
+template <class V>
+__device__ __forceinline__ int roc_bin(V s, const V* tab, const RocArgs& a) {
+    if (a.uniform) {
+        if (!(s >= tab[0])) return 0;                   // NaN or below the grid
+        const V x = (s - tab[0]) * (V)a.scale;
+        int g = x < (V)(a.T - 1) ? (int)x + 1 : a.T;
+        while (g < a.T && s >= tab[g]) ++g;             // (a uniform grid: at most a step or two either way)
+        while (s < tab[g - 1]) --g;
+        return g;
+    }
+    int b = 0;                                          // count of tab[] <= s; NaN compares false
+    for (int step = a.top; step > 0; step >>= 1)
+        if (b + step <= a.T && tab[b + step - 1] <= s) b += step;
+    return b;
+}
+
+// LDS of the histogram epilogue: threshold table, bins, the tile's gallery labels, its query labels and excluded rows
+constexpr size_t ROC_EPI_BYTES = (size_t)ROC_MAX_T * sizeof(float) + (size_t)ROC_BIN_WORDS * sizeof(unsigned) +
+                                 (size_t)3 * RK_BN * sizeof(i64);
+
+// The histogram epilogue: the overload of cos_gemm_epilogue that a kernel twin selects by passing RocArgs where the others pass
+// a RankFilter (the rank_gemm_*.inc bodies end with the same call either way).  Scores are acc * ginv[col] as in the other
+// modes, so every pair gets the bits of mi355_cosine_scores on the same loop.  Counts go into LDS as ONE u32 per bin
+// holding both classes (genuine adds 1 << 16, impostor 1: a tile has at most 128 x 128 = 16384 pairs, the halves cannot
+// carry), then to roc.hist with one 64-bit atomic per non-zero (bin, class), one lane per bin.  Called after a
+// __syncthreads() that retired every read of the staging buffers.
+template <int MT, int FK, bool FILT>
+__device__ __forceinline__ void cos_gemm_epilogue(f32x16 (&acc)[MT][2], float* smem, const float* __restrict__ ginv, float*, int Q,
+                                                  i64 G, int, float*, int*, int, int, i64 n0, int m0, const RocArgs& roc) {
+    static_assert(FK == FK_ROC && !FILT, "the histogram twins pass FK = FK_ROC, FILT = false");
+    constexpr int BM = 64 * MT;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1, lr = lane & 31;
+    const int T = roc.T, nb = T + 1;
+    const bool sub = T <= ROC_SUB_T;
+    float* tab = smem;                                                       // [T]
+    unsigned* bins = reinterpret_cast<unsigned*>(smem + ROC_MAX_T);          // [sub ? 4 : 1][T + 1]
+    i64* glab = reinterpret_cast<i64*>(bins + ROC_BIN_WORDS);                // [128]
+    i64* qlab = glab + RK_BN;                                                // [BM]
+    i64* qex = qlab + RK_BN;                                                 // [BM] LOCAL excluded row, -1: none
+    for (int i = tid; i < T; i += 256) tab[i] = roc_ceil_f32(roc.thr[i]);
+    for (int i = tid; i < (sub ? 4 * nb : nb); i += 256) bins[i] = 0u;
+    if (tid < RK_BN) glab[tid] = n0 + tid < G ? roc.glab[n0 + tid] : 0;
+    if (tid < BM) {
+        const bool ok = m0 + tid < Q;
+        const i64 e = ok && roc.excl ? roc.excl[m0 + tid] : -1;
+        qlab[tid] = ok ? roc.qlab[m0 + tid] : 0;
+        qex[tid] = e >= 0 ? e - roc.idx_offset : -1;
+    }
+    __syncthreads();
+    unsigned* mine = bins + (sub ? wave * nb : 0);
+    // C[row = query][col = gallery]; lane: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int c = wn * 64 + j * 32 + lr;
+        const i64 col = n0 + c;
+        if (col < G) {
+            const float gs = ginv ? ginv[col] : 1.0f;
+            const i64 gl = glab[c];
+#pragma unroll
+            for (int i = 0; i < MT; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int row = wm * MT * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                    if (m0 + row < Q && col != qex[row])
+                        atomicAdd(&mine[roc_bin(acc[i][j][r] * gs, tab, roc)], qlab[row] == gl ? 0x10000u : 1u);
+                }
+        }
+    }
+    __syncthreads();
+    for (int b = tid; b < nb; b += 256) {
+        unsigned u = bins[b];
+        if (sub) u += bins[nb + b] + bins[2 * nb + b] + bins[3 * nb + b];
+        if (u >> 16) atomicAdd(&roc.hist[b], (unsigned long long)(u >> 16));
+        if (u & 0xffffu) atomicAdd(&roc.hist[nb + b], (unsigned long long)(u & 0xffffu));
+    }
+}
+
 // Row norm of an fp32 row: one wave, float4 loads when vec (dim % 4 == 0 and 16-B aligned rows).  The lane-strided
 // summation order is part of the result: every row normalisation of the library (mi355_l2_normalize_rows, the queries
 // of every search, the fp16 gallery conversion) goes through this one function, so they give the same bits.
@@ -256,7 +364,7 @@ int whole_round_tiles(int ntx, int ny, int slots);
 
 // ---- host side of the tiled cosine GEMMs: exact fp32, split bf16 (rank.hip: F32Gemm, SplitGemm, PreparedGemm) and fp16
 // (rank_f16.hip: F16Gemm).  A family F supplies only what differs between them:
-//   F::SLAB, F::FILTERED             whether it has score-slab (FK = 0) / filtered kernels
+//   F::SLAB, F::FILTERED, F::ROC     whether it has score-slab (FK = 0) / filtered / histogram (FK = FK_ROC) kernels
 //   F::stage_bytes<MT>()             the LDS of its staging buffers
 //   F::kernel<MT, FK, FILT>()        its kernel
 //   F::launch<MT, FK, FILT>(...)     one launch of that kernel over column tiles [x0, x0 + xtiles) x ny query tiles
@@ -275,6 +383,7 @@ struct TileArgs {
     float* cand_val;
     int* cand_idx;
     const RankFilter* filt;     // the queries' filter (fused selection), or null
+    const RocArgs* roc;         // the histogram mode (the queries' labels / exclude of this call), or null
 };
 
 constexpr size_t EPI_TILE_BYTES = (size_t)64 * (RK_BN + 4) * sizeof(float);   // the fused selection's transposed score tile
@@ -296,7 +405,8 @@ template <class F, int MT, int FK, bool FILT>
 int launch_tiles(const TileArgs& a, hipStream_t st, int x0 = 0) {
     constexpr size_t stage = F::template stage_bytes<MT>();
     static_assert(!FILT || stage >= EPI_TILE_BYTES + FILT_LABELS_BYTES, "the filtered epilogue would grow the GEMM's LDS");
-    constexpr size_t lds = FK > 0 && EPI_TILE_BYTES > stage ? EPI_TILE_BYTES : stage;
+    constexpr size_t lds = FK == FK_ROC ? (ROC_EPI_BYTES > stage ? ROC_EPI_BYTES : stage)
+                                        : FK > 0 && EPI_TILE_BYTES > stage ? EPI_TILE_BYTES : stage;
     int slots = 0;
     if (int e = tile_slots<F, MT, FK, FILT>(lds, &slots)) return e;
     const int ntx = cdiv(a.G, RK_BN), ny = cdiv(a.Q, 64 * MT);
@@ -321,6 +431,9 @@ int launch_fk(const TileArgs& a, hipStream_t st) {
 }
 template <class F, int MT>
 int launch_mt(const TileArgs& a, hipStream_t st) {
+    if constexpr (F::ROC) {
+        if (a.roc) return launch_tiles<F, MT, FK_ROC, false>(a, st);
+    }
     if constexpr (F::SLAB) {
         if (!a.cand_val) {
             TileArgs s = a;
@@ -333,11 +446,22 @@ int launch_mt(const TileArgs& a, hipStream_t st) {
     }
     return launch_fk<F, MT, false>(a, st);
 }
-// A GEMM call of family F: 128-query tiles above 64 queries, 64-query tiles otherwise
+// A GEMM call of family F: 128-query tiles above 64 queries, 64-query tiles otherwise.  a.roc: the histogram mode.
 template <class F>
 int cos_gemm_tiles(const TileArgs& a, hipStream_t st) {
     return a.Q > 64 ? launch_mt<F, 2>(a, st) : launch_mt<F, 1>(a, st);
 }
+
+// ---- host side of the ROC entries (roc.cpp)
+// Checks T thresholds (host float64: count, finite, ascending) and fills the binning plan of a (null: checks only)
+int roc_check_thresholds(const double* thr, int T, const char* who, RocArgs* a);
+// Checks the label / exclude pointers and hist of mi355_roc_pairs_hist[_f16] and fills them into a
+int roc_check_pairs(const int64_t* query_labels, const int64_t* gallery_labels, const int64_t* exclude, int64_t idx_offset,
+                    const double* thresholds_dev, int64_t* hist, const char* who, RocArgs* a);
+// The block of queries [q0, ...) of a
+RocArgs roc_from(const RocArgs& a, i64 q0);
+// Queries per GEMM call of a histogram (no slab, no candidates: only the grid size bounds it)
+i64 roc_query_block(i64 Q, i64 G);
 
 // ---- one top-k search (mi355_rank_topk[_filtered], mi355_rank_topk_prepared, mi355_rank_topk_f16[_filtered])
 // Scratch of a search, carved from the caller's workspace (ws null: sizes only, total = the bytes it needs).

@@ -116,6 +116,18 @@ __global__ __launch_bounds__(256) void k_cos_gemm_f16_filt(const f16* __restrict
     float* const S = nullptr;
 #include "rank_gemm_f16.inc"
 }
+// The histogram twin (mi355_roc_pairs_hist_f16): the same body, the histogram epilogue (its overload takes RocArgs as `flt`)
+template <int MT>
+__global__ __launch_bounds__(256) void k_cos_gemm_f16_roc(const f16* __restrict__ Qs, const f16* __restrict__ Gal, int Q, i64 G,
+                                                          int ld, int x0, int ntx, int xtiles, int ny, RocArgs flt) {
+    constexpr int FK = FK_ROC;
+    constexpr bool FILT = false;
+    float* const S = nullptr;
+    const int k = 0;
+    float* const cand_val = nullptr;
+    int* const cand_idx = nullptr;
+#include "rank_gemm_f16.inc"
+}
 
 // =====================================================================================
 // Few queries (Q <= 4, the one-query-at-a-time serving shape): a GEMV bound by streaming the gallery once (2 * ld bytes
@@ -179,19 +191,22 @@ static bool f16_gemv(i64 Q, int ld) { return Q <= 4 && (size_t)Q * ld * sizeof(f
 
 // The tiled GEMM over fp16 rows (launch_tiles, rank_common.h); qry: the queries' fp16 planes, gal: the rows, D: their length ld
 struct F16Gemm {
-    static constexpr bool SLAB = true, FILTERED = true;
+    static constexpr bool SLAB = true, FILTERED = true, ROC = true;
     template <int MT> static constexpr size_t stage_bytes() {   // A ring of 2, B ring of 3
         return (size_t)2 * (64 * MT / 32) * 8 * 1024 + (size_t)3 * RK_BN * F16_KSTEP * 2;
     }
     template <int MT, int FK, bool FILT> static const void* kernel() {
-        if constexpr (FILT) return (const void*)k_cos_gemm_f16_filt<MT, FK>;
+        if constexpr (FK == FK_ROC) return (const void*)k_cos_gemm_f16_roc<MT>;
+        else if constexpr (FILT) return (const void*)k_cos_gemm_f16_filt<MT, FK>;
         else return (const void*)k_cos_gemm_f16<MT, FK>;
     }
     template <int MT, int FK, bool FILT>
     static void launch(dim3 grid, size_t lds, hipStream_t st, const TileArgs& a, int x0, int ntx, int xtiles, int ny) {
         const f16* qs = (const f16*)a.qry;
         const f16* gal = (const f16*)a.gal;
-        if constexpr (FILT)
+        if constexpr (FK == FK_ROC)
+            hipLaunchKernelGGL((k_cos_gemm_f16_roc<MT>), grid, dim3(256), lds, st, qs, gal, a.Q, a.G, a.D, x0, ntx, xtiles, ny, *a.roc);
+        else if constexpr (FILT)
             hipLaunchKernelGGL((k_cos_gemm_f16_filt<MT, FK>), grid, dim3(256), lds, st, qs, gal, a.Q, a.G, a.D, a.k, a.cand_val,
                                a.cand_idx, x0, ntx, xtiles, ny, *a.filt);
         else
@@ -273,7 +288,7 @@ static int rank_topk_f16(const float* queries, int64_t Q, const void* gallery_f1
             hipLaunchKernelGGL(k_split_queries_f16, dim3((unsigned)cdiv(n_frag, 4)), dim3(256), 0, st, w.qn + q0 * dim, (f16*)w.qs,
                                (int)qn, dim, n_sub, n_frag);
             MI355_LAUNCH_CHECK();
-            return cos_gemm_tiles<F16Gemm>({w.qs, gal, nullptr, w.S, (int)qn, G, ld, k, w.cand_val, w.cand_idx, f}, st);
+            return cos_gemm_tiles<F16Gemm>({w.qs, gal, nullptr, w.S, (int)qn, G, ld, k, w.cand_val, w.cand_idx, f, nullptr}, st);
         });
 }
 
@@ -292,6 +307,48 @@ int mi355_rank_topk_f16_filtered(const float* queries, int64_t Q, const void* ga
     MI355_REQUIRE(filter, "rank_topk_f16_filtered: null filter (use the unfiltered entry)");
     return rank_topk_f16(queries, Q, gallery_f16, G, dim, k, eps, idx_offset, out_val, out_idx, workspace, workspace_bytes, stream,
                          filter, "rank_topk_f16_filtered");
+}
+
+size_t mi355_roc_pairs_f16_workspace_bytes(int64_t Q, int64_t G, int dim) {
+    if (Q < 1 || G < 1 || dim < 1) return 0;
+    return carve(nullptr, Q, G, dim, 0, f16_planes_bytes, false, false).total;   // normalised queries + one call's planes
+}
+
+int mi355_roc_pairs_hist_f16(const float* queries, int64_t Q, const void* gallery_f16, int64_t G, int dim, float eps,
+                             const int64_t* query_labels, const int64_t* gallery_labels, const int64_t* exclude, int64_t idx_offset,
+                             const double* thresholds, const double* thresholds_dev, int T, int64_t* hist, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+    const char* who = "roc_pairs_hist_f16";
+    RocArgs roc{};
+    if (int e = roc_check_thresholds(thresholds, T, who, &roc)) return e;
+    if (int e = roc_check_pairs(query_labels, gallery_labels, exclude, idx_offset, thresholds_dev, hist, who, &roc)) return e;
+    MI355_REQUIRE(queries && gallery_f16, "%s: null queries/gallery pointer", who);
+    MI355_REQUIRE(Q >= 1 && G >= 1 && dim >= 1, "%s: bad shape Q=%lld G=%lld dim=%d", who, (long long)Q, (long long)G, dim);
+    MI355_REQUIRE(((uintptr_t)gallery_f16 & 15) == 0, "%s: gallery buffer must be 16-byte aligned", who);
+    MI355_REQUIRE(Q <= INT_MAX && G < ((int64_t)1 << 31) - RK_BN, "%s: shape too large Q=%lld G=%lld", who, (long long)Q,
+                  (long long)G);
+    const size_t need = mi355_roc_pairs_f16_workspace_bytes(Q, G, dim);
+    MI355_REQUIRE(workspace && workspace_bytes >= need, "%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
+    const RankWs w = carve(workspace, Q, G, dim, 0, f16_planes_bytes, false, false);
+    hipStream_t st = (hipStream_t)stream;
+    MI355_CHECK_HIP(hipMemsetAsync(hist, 0, (size_t)2 * (T + 1) * sizeof(int64_t), st));
+    if (int e = normalize_search(queries, Q, nullptr, G, dim, eps, w, st)) return e;
+    const int ld = f16_ld(dim), n_sub = ld / 16;
+    const i64 qb = roc_query_block(Q, G);
+    for (i64 q0 = 0; q0 < Q; q0 += qb) {
+        const i64 qn = (Q - q0 < qb) ? Q - q0 : qb;
+        const RocArgs rb = roc_from(roc, q0);
+        RoctxRange range("roc/cosine gemm (fp16 gallery) + histogram");
+        set_rank_path(MI355_RANK_PATH_F16_GEMM);
+        const int n_frag = cdiv(qn, 128) * 4 * n_sub;
+        hipLaunchKernelGGL(k_split_queries_f16, dim3((unsigned)cdiv(n_frag, 4)), dim3(256), 0, st, w.qn + q0 * dim, (f16*)w.qs,
+                           (int)qn, dim, n_sub, n_frag);
+        MI355_LAUNCH_CHECK();
+        if (int e = cos_gemm_tiles<F16Gemm>({w.qs, gallery_f16, nullptr, nullptr, (int)qn, G, ld, 0, nullptr, nullptr, nullptr, &rb},
+                                            st))
+            return e;
+    }
+    return OK;
 }
 
 }  // extern "C"

@@ -8,9 +8,13 @@ routes the arithmetic to libmi355_retrieval:
 * ``cosine_topk(Q, G, k)`` .................... the whole per-query loop train/train.py:249-255 as one call
 * ``ContrastiveLoss(margin)(fm1, fm2, label, mean)`` ... utils/contrastive_loss.py:6-61
 * ``hit_counts`` / ``distinct_class_topn`` .... train/train.py:252-255 ; notebook raw :240-251
+* ``roc_curve`` / ``verification_roc`` ........ utils/roc_curve_from_scratch.py (given pair scores / every labelled pair)
 """
 from __future__ import annotations
 
+import ctypes
+
+import numpy as np
 import torch
 
 from ._lib import LABEL_ANY, LABEL_DIFFERENT, LABEL_SAME, MI355Error, RankFilter, check, lib, require_cuda, stream_ptr
@@ -576,6 +580,33 @@ class Gallery:
         return cosine_topk(queries, self.data, k, self.eps, gallery_is_normalized=True, idx_offset=idx_offset,
                            query_labels=query_labels, gallery_labels=self.labels, label_filter=label_filter, exclude=exclude)
 
+    def _roc_labels(self):
+        if self.labels is None:
+            raise MI355Error("verification_roc needs gallery labels: add(embeddings, labels)")
+        if self.labels.shape[0] != self.rows:
+            raise MI355Error(f"the gallery holds {self.labels.shape[0]} labels for {self.rows} rows")
+
+    def _roc_hist(self, queries, query_labels, thr, exclude=None, idx_offset: int = 0):
+        """The pair histogram of ``queries`` against the resident rows and their labels (ShardedGallery's local step)."""
+        self._roc_labels()
+        q = _f32c(queries, "queries")
+        _check_qg(q, self.data)
+        ql = _int64_on(query_labels, "query_labels", q.shape[0], q.device)
+        ex = None if exclude is None else _int64_on(exclude, "exclude", q.shape[0], q.device)
+        if self.dtype == torch.float16:
+            return _roc_pairs_hist(q, ql, self._buf, self.rows, self.labels, ex, idx_offset, thr, self.eps, f16_dim=self.dim)
+        return _roc_pairs_hist(q, ql, self.data, self.rows, self.labels, ex, idx_offset, thr, self.eps, gallery_is_normalized=True)
+
+    def verification_roc(self, queries: torch.Tensor, query_labels: torch.Tensor, thresholds=None,
+                         exclude: torch.Tensor | None = None):
+        """``verification_roc`` of ``queries`` against the resident rows and the labels given to ``add``.  Each pair's score
+        has the bits of this gallery's own search (fp32 rows: ``cosine_scores`` of its normalised rows; fp16 rows: the
+        f16-MFMA kernel)."""
+        self._roc_labels()
+        require_cuda(queries, "queries")
+        thr = _roc_thresholds(thresholds, self.device)
+        return _roc_finalize(self._roc_hist(queries, query_labels, thr, exclude), thr)
+
 
 def clear_pads(vals: torch.Tensor, idx: torch.Tensor, lo: int, hi: int):
     """In place: entries whose index lies outside [lo, hi) become (-inf, -1)."""
@@ -666,3 +697,139 @@ def retrieval_metrics(queries, positives, query_cls, gallery_cls=None, k: int = 
     n = queries.shape[0]
     return {"top1": counts[0].item() / n, "top3": counts[1].item() / n,
             "scores": None if pos is None else pos.mean().item(), "topk_vals": vals, "topk_inds": idx}
+
+
+# ---- verification ROC (utils/roc_curve_from_scratch.py)
+_ROC_MAX_T = 4096
+
+
+def _roc_thresholds(thresholds, device):
+    """(host float64 tensor, the same values on ``device``): the reference's grid ``arange(0, 105, 5) / 100`` by default."""
+    if thresholds is None:
+        host = torch.from_numpy(np.array(list(range(0, 105, 5))) / 100)
+    elif torch.is_tensor(thresholds):
+        host = thresholds.detach().to("cpu", torch.float64)
+    else:
+        host = torch.from_numpy(np.array(thresholds, dtype=np.float64))
+    if host.dim() != 1 or not 1 <= host.shape[0] <= _ROC_MAX_T:
+        raise MI355Error(f"thresholds must be a 1-D sequence of 1..{_ROC_MAX_T} values, got shape {tuple(host.shape)}")
+    if not bool(torch.isfinite(host).all()):
+        raise MI355Error("thresholds must be finite")
+    if host.shape[0] > 1 and bool((host[1:] < host[:-1]).any()):
+        raise MI355Error("thresholds must be ascending")
+    host = host.contiguous()
+    if torch.device(device).type != "cuda":       # (an injected CPU backend of ShardedGallery)
+        return host, host.clone()
+    return host, host.pin_memory().to(device, non_blocking=True)
+
+
+def _dptr(host: torch.Tensor):
+    return ctypes.cast(host.data_ptr(), ctypes.POINTER(ctypes.c_double))
+
+
+def _roc_finalize(hist: torch.Tensor, thr):
+    """hist (2, T + 1) int64 -> the result dict of ``roc_curve`` / ``verification_roc`` (one launch: mi355_roc_finalize)."""
+    host, dev = thr
+    T = host.shape[0]
+    counts = torch.empty((4, T), dtype=torch.int64, device=hist.device)
+    totals = torch.empty(2, dtype=torch.int64, device=hist.device)
+    rates = torch.empty((2, T), dtype=torch.float64, device=hist.device)
+    auc = torch.empty((), dtype=torch.float64, device=hist.device)
+    with torch.cuda.device(hist.device):
+        check(lib().mi355_roc_finalize(hist.data_ptr(), T, counts.data_ptr(), totals.data_ptr(), rates.data_ptr(), auc.data_ptr(),
+                                       stream_ptr(hist.device)))
+    return {"thresholds": dev, "tp": counts[0], "fp": counts[1], "fn": counts[2], "tn": counts[3], "tpr": rates[0],
+            "fpr": rates[1], "auc": auc, "num_genuine": totals[0], "num_impostor": totals[1]}
+
+
+def roc_curve(scores: torch.Tensor, actual: torch.Tensor, thresholds=None):
+    """``roc_curve`` of utils/roc_curve_from_scratch.py on given pair scores, without the plot.
+
+    ``scores`` (n,) fp32 or fp64 and ``actual`` (n,) (1 = genuine, 0 = impostor; any other value is counted in neither class,
+    as the reference's if/elif chain does) on the GPU.  A pair is predicted positive at t iff ``score >= t`` in float64
+    (pandas' comparison; exact for fp32 scores too).  ``thresholds``: ascending, finite, 1..4096 values (default: the
+    reference's 21 points 0, 0.05, .., 1).  Returns device tensors: ``thresholds`` (T,) float64, ``tp``, ``fp``, ``fn``, ``tn``
+    (T,) int64, ``tpr``, ``fpr`` (T,) float64 (NaN where a class is empty), ``auc`` = |trapezoid(tpr, fpr)| unrounded (the
+    reference prints it rounded to 4 digits), ``num_genuine``, ``num_impostor``."""
+    for t, name in ((scores, "scores"), (actual, "actual")):
+        if not torch.is_tensor(t):
+            raise MI355Error(f"{name} must be a tensor")
+        require_cuda(t, name)
+    if scores.dtype not in (torch.float32, torch.float64):
+        raise MI355Error(f"scores must be float32 or float64, got {scores.dtype}")
+    if scores.dim() != 1 or actual.dim() != 1 or actual.shape[0] != scores.shape[0]:
+        raise MI355Error(f"scores and actual must be 1-D of the same length, got {tuple(scores.shape)} and {tuple(actual.shape)}")
+    if actual.device != scores.device:
+        raise MI355Error(f"actual is on {actual.device} but scores on {scores.device}")
+    s = scores.contiguous()
+    if actual.dtype == torch.bool:
+        code = actual.contiguous().view(torch.int8)
+    elif actual.dtype == torch.int8:
+        code = actual.contiguous()
+    else:                                       # 1 -> genuine, 0 -> impostor, everything else (2, 0.5, NaN, 257, ..) -> -1
+        code = torch.where(actual == 1, 1, torch.where(actual == 0, 0, -1)).to(torch.int8)
+    thr = _roc_thresholds(thresholds, s.device)
+    T = thr[0].shape[0]
+    hist = torch.empty((2, T + 1), dtype=torch.int64, device=s.device)
+    with torch.cuda.device(s.device):
+        check(lib().mi355_roc_scores_hist(s.data_ptr(), int(s.dtype == torch.float64), s.shape[0], code.data_ptr(), _dptr(thr[0]),
+                                          thr[1].data_ptr(), T, hist.data_ptr(), stream_ptr(s.device)))
+    return _roc_finalize(hist, thr)
+
+
+def _roc_pairs_hist(q: torch.Tensor, ql: torch.Tensor, gallery: torch.Tensor, G: int, gl: torch.Tensor, exclude, idx_offset: int,
+                    thr, eps: float = _EPS, gallery_is_normalized: bool = False, f16_dim: int | None = None) -> torch.Tensor:
+    """The (2, T + 1) int64 pair histogram of queries ``q`` (Q, D) against ``G`` gallery rows: fp32 rows ``gallery`` (G, D), or
+    with ``f16_dim`` an fp16 gallery buffer (mi355_gallery_to_f16 layout).  Arguments checked by the caller."""
+    host, dev = thr
+    T = host.shape[0]
+    Q, D = q.shape
+    if Q == 0 or G == 0:
+        return torch.zeros((2, T + 1), dtype=torch.int64, device=q.device)
+    hist = torch.empty((2, T + 1), dtype=torch.int64, device=q.device)        # (zeroed by the call)
+    ex = exclude.data_ptr() if exclude is not None else None
+    with torch.cuda.device(q.device):
+        if f16_dim is None:
+            ws = _ws.get(q.device, lib().mi355_roc_pairs_workspace_bytes(Q, G, D))
+            check(lib().mi355_roc_pairs_hist(q.data_ptr(), Q, gallery.data_ptr(), G, D, int(gallery_is_normalized), eps,
+                                             ql.data_ptr(), gl.data_ptr(), ex, int(idx_offset), _dptr(host), dev.data_ptr(), T,
+                                             hist.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr(q.device)))
+        else:
+            ws = _ws.get(q.device, lib().mi355_roc_pairs_f16_workspace_bytes(Q, G, f16_dim))
+            check(lib().mi355_roc_pairs_hist_f16(q.data_ptr(), Q, gallery.data_ptr(), G, f16_dim, eps, ql.data_ptr(), gl.data_ptr(),
+                                                 ex, int(idx_offset), _dptr(host), dev.data_ptr(), T, hist.data_ptr(), ws.data_ptr(),
+                                                 ws.numel(), stream_ptr(q.device)))
+    return hist
+
+
+def verification_roc(queries: torch.Tensor, query_labels: torch.Tensor, gallery: torch.Tensor | None = None,
+                     gallery_labels: torch.Tensor | None = None, thresholds=None, eps: float = _EPS,
+                     exclude: torch.Tensor | None = None, idx_offset: int = 0):
+    """Verification ROC over EVERY labelled (query, gallery row) pair: genuine iff the labels are equal, impostor otherwise.
+
+    Each pair's score has the bits ``cosine_scores(queries, gallery)`` gives it (the same GEMM path; Q <= 4 as well), and is
+    binned inside the GEMM's epilogue: no (Q, G) score matrix is made.  ``gallery=None``: the queries are their own gallery
+    and every ordered pair (i, j), i != j, counts once.  ``exclude`` (Q,) leaves out the pair (q, exclude[q] - idx_offset) (a
+    global row, as in ``cosine_topk``; negative = none).  Thresholds and the result as ``roc_curve``; counts are exact
+    integers, the same every run."""
+    q = _f32c(queries, "queries")
+    if q.dim() != 2:
+        raise MI355Error(f"queries must be (Q, D), got {tuple(q.shape)}")
+    Q = q.shape[0]
+    ql = _int64_on(query_labels, "query_labels", Q, q.device)
+    if gallery is None:
+        if gallery_labels is not None:
+            raise MI355Error("gallery_labels given without a gallery (same-source evaluation uses query_labels)")
+        if exclude is not None or idx_offset:
+            raise MI355Error("same-source evaluation (gallery=None) excludes each query's own row itself: no exclude / idx_offset")
+        g, gl = q, ql
+        ex = torch.arange(Q, dtype=torch.int64, device=q.device)
+    else:
+        g = _f32c(gallery, "gallery")
+        _check_qg(q, g)
+        if gallery_labels is None:
+            raise MI355Error("a gallery needs gallery_labels")
+        gl = _int64_on(gallery_labels, "gallery_labels", g.shape[0], q.device)
+        ex = None if exclude is None else _int64_on(exclude, "exclude", Q, q.device)
+    thr = _roc_thresholds(thresholds, q.device)
+    return _roc_finalize(_roc_pairs_hist(q, ql, g, g.shape[0], gl, ex, idx_offset, thr, eps), thr)

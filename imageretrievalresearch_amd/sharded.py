@@ -39,6 +39,21 @@ class _HipOps:
         return _rank.cosine_topk(queries, gallery_normalized, k, gallery_is_normalized=True, idx_offset=idx_offset, **filt)
 
     @staticmethod
+    def roc_hist(queries, query_labels, gallery_normalized, gallery_labels, exclude, idx_offset, thr, gallery_f16=None):
+        """The (2, T + 1) int64 pair histogram of ``queries`` against this shard (rows [idx_offset, ...) of the gallery)."""
+        if gallery_f16 is not None:
+            return gallery_f16._roc_hist(queries, query_labels, thr, exclude, idx_offset)
+        ql = _rank._int64_on(query_labels, "query_labels", queries.shape[0], queries.device)
+        gl = _rank._int64_on(gallery_labels, "gallery_labels", gallery_normalized.shape[0], queries.device)
+        ex = None if exclude is None else _rank._int64_on(exclude, "exclude", queries.shape[0], queries.device)
+        return _rank._roc_pairs_hist(queries, ql, gallery_normalized, gallery_normalized.shape[0], gl, ex, idx_offset, thr,
+                                     gallery_is_normalized=True)
+
+    @staticmethod
+    def roc_finalize(hist, thr):
+        return _rank._roc_finalize(hist, thr)
+
+    @staticmethod
     def clear_pads(vals, idx, lo, hi):
         return _rank.clear_pads(vals, idx, lo, hi)
 
@@ -208,6 +223,44 @@ class ShardedGallery:
         # unpacking, the shard offsets and the merge of world * k candidates per query: one library call
         # (mi355_merge_packed_topk), no torch elementwise kernels on the rank stream
         return self.ops.merge_packed(allp.view(self.world, Q, k, 2), self._offsets_dev, k)
+
+    def verification_roc(self, queries_local: torch.Tensor, query_labels_local: torch.Tensor, thresholds=None,
+                         exclude: torch.Tensor | None = None):
+        """``verification_roc`` of every rank's queries against the WHOLE gallery (the shard labels given to the constructor).
+
+        ``queries_local`` (Q_local, D) and ``query_labels_local`` (Q_local,) of this rank (same Q_local on every rank);
+        ``exclude`` (Q_local,) GLOBAL row indices (negative = none).  The queries, labels and exclude are all-gathered as
+        ``search`` does, each rank counts its shard's pairs, and ONE all_reduce(SUM) of the int64 histogram gives every rank
+        the same result, bit for bit that of one gallery holding every row."""
+        if self.labels is None:
+            raise MI355Error("verification_roc needs the shard labels: ShardedGallery(..., labels=)")
+        n_local = self.local.shape[0]
+        if self.labels.shape[0] != n_local:
+            raise MI355Error(f"the shard holds {self.labels.shape[0]} labels for {n_local} rows")
+        q = queries_local.float().contiguous()
+        Ql = q.shape[0]
+        side = torch.full((Ql, 2), -1, dtype=torch.int64, device=self.device)
+        for col, t, name in ((0, query_labels_local, "query_labels"), (1, exclude, "exclude")):
+            if t is None:
+                continue
+            if not torch.is_tensor(t) or t.dtype.is_floating_point or t.dim() != 1 or t.shape[0] != Ql:
+                raise MI355Error(f"{name} must be an integer tensor of shape ({Ql},)")
+            side[:, col] = t.to(self.device, torch.int64)
+        thr = _rank._roc_thresholds(thresholds, self.device)
+        dist = torch.distributed
+        if self.world > 1:
+            allq = torch.empty((self.world * Ql, self.dim), dtype=torch.float32, device=self.device)
+            dist.all_gather_into_tensor(allq, q, group=self.group)
+            alls = torch.empty((self.world * Ql, 2), dtype=torch.int64, device=self.device)
+            dist.all_gather_into_tensor(alls, side, group=self.group)
+        else:
+            allq, alls = q, side
+        ex = alls[:, 1].contiguous() if exclude is not None else None
+        hist = self.ops.roc_hist(allq, alls[:, 0].contiguous(), self.local, self.labels, ex, self.offset, thr,
+                                 gallery_f16=self.gallery_f16)
+        if self.world > 1:
+            dist.all_reduce(hist, op=dist.ReduceOp.SUM, group=self.group)
+        return self.ops.roc_finalize(hist, thr)
 
     def my_slice(self, Q_local: int) -> slice:
         """Rows of ``search``'s result that belong to this rank's own queries."""

@@ -140,6 +140,41 @@ enum {
 };
 int mi355_rank_last_path(void);
 
+/* Verification ROC (utils/roc_curve_from_scratch.py): genuine / impostor pairs counted per threshold, without a score slab.
+ * thresholds: HOST float64 [T], 1 <= T <= MI355_ROC_MAX_THRESHOLDS, finite, ascending (equal neighbours allowed); checked
+ * before any HIP call.  thresholds_dev: the same T values on the device (the kernels read them from there).
+ * A pair is predicted positive at t iff score >= t compared in float64: an fp32 score is compared in fp32 with the smallest
+ * float f such that (double)f >= t, which is that comparison exactly; a NaN score is never >= t.
+ * hist [2][T + 1] int64 (zeroed by the call, then filled): hist[0][b] genuine / hist[1][b] impostor pairs whose score is >= exactly
+ * b of the thresholds.  Counts are integers: the same every run.
+ *
+ * mi355_roc_pairs_hist: every (query q, gallery row j) pair, scored with the bits mi355_cosine_scores gives that pair on the
+ * same path (split bf16, or MI355_RANK_EXACT_F32=1 / unaligned rows: exact fp32; always the tiled GEMM, also for Q <= 4),
+ * genuine iff query_labels[q] == gallery_labels[j]; a pair with exclude[q] == j + idx_offset is not counted (exclude may be
+ * NULL; exclude[q] < 0: none).  query_labels / exclude [Q], gallery_labels [G]: device int64.
+ * workspace: mi355_roc_pairs_workspace_bytes(Q, G, dim) (normalised queries, split planes, 1 / |row|; no Q x G term).
+ * mi355_roc_pairs_hist_f16: the same against an fp16 gallery (mi355_gallery_to_f16 layout), scored with the bits of
+ * mi355_rank_topk_f16's tiled kernel.  workspace: mi355_roc_pairs_f16_workspace_bytes(Q, G, dim). */
+#define MI355_ROC_MAX_THRESHOLDS 4096
+size_t mi355_roc_pairs_workspace_bytes(int64_t Q, int64_t G, int dim);
+int mi355_roc_pairs_hist(const float* queries, int64_t Q, const float* gallery, int64_t G, int dim, int gallery_is_normalized,
+                         float eps, const int64_t* query_labels, const int64_t* gallery_labels, const int64_t* exclude,
+                         int64_t idx_offset, const double* thresholds, const double* thresholds_dev, int T, int64_t* hist,
+                         void* workspace, size_t workspace_bytes, void* stream);
+size_t mi355_roc_pairs_f16_workspace_bytes(int64_t Q, int64_t G, int dim);
+int mi355_roc_pairs_hist_f16(const float* queries, int64_t Q, const void* gallery_f16, int64_t G, int dim, float eps,
+                             const int64_t* query_labels, const int64_t* gallery_labels, const int64_t* exclude, int64_t idx_offset,
+                             const double* thresholds, const double* thresholds_dev, int T, int64_t* hist, void* workspace,
+                             size_t workspace_bytes, void* stream);
+/* The same histogram over n given pair scores (fp32, or float64 with scores_f64 = 1: compared in float64 with thresholds_dev)
+ * and int8 class codes actual [n]: 1 genuine, 0 impostor, any other value counted in neither class. */
+int mi355_roc_scores_hist(const void* scores, int scores_f64, int64_t n, const int8_t* actual, const double* thresholds,
+                          const double* thresholds_dev, int T, int64_t* hist, void* stream);
+/* One launch: hist [2][T + 1] -> counts [4][T] int64 (tp, fp, fn, tn; tp[i] = genuine pairs with score >= t_i),
+ * totals [2] int64 (genuine, impostor pairs), rates [2][T] float64 (tpr = tp / (tp + fn), fpr = fp / (fp + tn); NaN where
+ * the denominator is 0), auc [1] float64 = |trapezoid of tpr over fpr| in threshold order (numpy.trapz(tpr, fpr), unrounded). */
+int mi355_roc_finalize(const int64_t* hist, int T, int64_t* counts, int64_t* totals, double* rates, double* auc, void* stream);
+
 /* Indices outside [lo, hi) become (-inf, -1) in val / idx [n] (the sharded filtered search: slots no shard filled). */
 int mi355_clear_pads(float* val, int64_t* idx, int64_t n, int64_t lo, int64_t hi, void* stream);
 
