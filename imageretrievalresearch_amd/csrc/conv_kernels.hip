@@ -26,32 +26,71 @@ __device__ __forceinline__ u32x4 pack8(const float* f) {
 }
 
 // =====================================================================================
-// stem: 3x3 stride 2 pad 1, 3 -> Cout, NCHW fp32 in, NHWC bf16 out.  One thread = one output pixel,
-// the 27-tap patch lives in registers; the weights [27][Cout] are read at wave-uniform addresses, i.e. as scalar
-// loads feeding SGPR operands of packed FMAs (a broadcast-read LDS copy was LDS-issue-bound: 0.222 -> 0.196 ms).
+// stem: 3x3 stride 2 pad 1, 3 -> Cout, NCHW fp32 in, NHWC bf16 out.  A workgroup owns 16 x 16 output pixels, one per thread;
+// the arithmetic is per pixel as before: the 27-tap patch in registers, bias then taps t = 0..26 ascending, the weights
+// [27][Cout] read at wave-uniform addresses, i.e. as scalar loads feeding SGPR operands of packed FMAs (a broadcast-read LDS
+// copy of the weights was LDS-issue-bound: 0.222 -> 0.196 ms).  The memory side goes through LDS:
+//  - in:  the workgroup's input band (33 rows x 3 planes, columns 32 * bx - 4 .. 32 * bx + 31) is staged with coalesced
+//         16-byte loads (4-byte loads when W % 4 != 0), zeros outside the image = the conv's padding; the taps are LDS reads.
+//         (Per-thread gathers were 4-byte reads at a stride of 2 pixels over 3 planes.)
+//  - out: each wave writes its 64 pixels x Cout channels into a private LDS strip, then stores the strip as whole contiguous
+//         lines of 16 bytes per lane (one pixel per lane spread every store instruction over 64 x 2 * Cout bytes).
 // =====================================================================================
+constexpr int STEM_TW = 16, STEM_TH = 16;                         // output tile
+constexpr int STEM_IR = 2 * STEM_TH + 1, STEM_IC = 2 * STEM_TW + 4;   // staged input rows / columns (4 before the first tap)
+
+static size_t stem_lds_bytes(int Cout) {
+    return (size_t)3 * STEM_IR * STEM_IC * sizeof(float) + (size_t)4 * 64 * Cout * sizeof(bf16_t);
+}
+
 __global__ __launch_bounds__(256) void k_stem(const float* __restrict__ x, const float* __restrict__ w,
                                               const float* __restrict__ bias, bf16_t* __restrict__ out, int H, int W,
                                               int Ho, int Wo, int Cout, int act) {
+    extern __shared__ __attribute__((aligned(16))) float stem_sm[];
+    float* xin = stem_sm;                                                   // [3][STEM_IR][STEM_IC]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    bf16_t* strip = reinterpret_cast<bf16_t*>(stem_sm + 3 * STEM_IR * STEM_IC) + (size_t)wave * 64 * Cout;
     const int b = blockIdx.z;
-    const int ox = blockIdx.x * 32 + (threadIdx.x & 31);
-    const int oy = blockIdx.y * 8 + (threadIdx.x >> 5);
-    if (ox >= Wo || oy >= Ho) return;
-    float p[27];
+    const int ox0 = blockIdx.x * STEM_TW, oy0 = blockIdx.y * STEM_TH;
+    const int ix0 = 2 * ox0 - 4, iy0 = 2 * oy0 - 1;                       // input origin of the staged band
     const float* xb = x + (size_t)b * 3 * H * W;
+    if ((W & 3) == 0) {
+        // ix0 and W are multiples of 4: each 16-byte group lies wholly inside or wholly outside the image
+        // all of a thread's loads are issued before the first LDS write: one HBM latency per workgroup, not four
+        constexpr int G = STEM_IC / 4, NV = (3 * STEM_IR * G + 255) / 256;
+        f32x4 v[NV];
 #pragma unroll
-    for (int ky = 0; ky < 3; ++ky) {
-        const int iy = oy * 2 - 1 + ky;
+        for (int j = 0; j < NV; ++j) {
+            const int i = tid + 256 * j;
+            const int row = i / G, g = i - row * G;                         // row = ci * STEM_IR + r
+            const int ci = row / STEM_IR, iy = iy0 + row - ci * STEM_IR, ix = ix0 + g * 4;
+            v[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            if (i < 3 * STEM_IR * G && iy >= 0 && iy < H && ix >= 0 && ix < W)
+                v[j] = *reinterpret_cast<const f32x4*>(xb + ((size_t)ci * H + iy) * W + ix);
+        }
 #pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-            const int ix = ox * 2 - 1 + kx;
-            const bool ok = (iy >= 0 && iy < H && ix >= 0 && ix < W);
-#pragma unroll
-            for (int ci = 0; ci < 3; ++ci)
-                p[(ky * 3 + kx) * 3 + ci] = ok ? xb[((size_t)ci * H + iy) * W + ix] : 0.f;
+        for (int j = 0; j < NV; ++j)
+            if (tid + 256 * j < 3 * STEM_IR * G) *reinterpret_cast<f32x4*>(&xin[(tid + 256 * j) * 4]) = v[j];
+    } else {
+        for (int i = tid; i < 3 * STEM_IR * STEM_IC; i += 256) {
+            const int row = i / STEM_IC, c = i - row * STEM_IC;
+            const int ci = row / STEM_IR, iy = iy0 + row - ci * STEM_IR, ix = ix0 + c;
+            xin[i] = (iy >= 0 && iy < H && ix >= 0 && ix < W) ? xb[((size_t)ci * H + iy) * W + ix] : 0.f;
         }
     }
-    bf16_t* o = out + (((size_t)b * Ho + oy) * Wo + ox) * Cout;
+    __syncthreads();
+    // pixel of this thread: wave w holds tile rows 4w .. 4w + 3, 16 pixels each (pixels past Wo / Ho are computed on the zero
+    // padding and never stored)
+    const int lx = tid & (STEM_TW - 1), ly = tid / STEM_TW;
+    float p[27];
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx)
+#pragma unroll
+            for (int ci = 0; ci < 3; ++ci)
+                p[(ky * 3 + kx) * 3 + ci] = xin[(ci * STEM_IR + 2 * ly + ky) * STEM_IC + 2 * lx + 3 + kx];
+    bf16_t* o = strip + (size_t)lane * Cout;
     for (int c0 = 0; c0 < Cout; c0 += 8) {
         float acc[8];
 #pragma unroll
@@ -70,14 +109,31 @@ _Pragma("unroll")
         })
         *reinterpret_cast<u32x4*>(o + c0) = pack8(acc);
     }
+    // (same wave wrote and reads its strip: LDS ops complete in order, no barrier needed)
+    // the strip is 4 tile rows of 16 pixels x Cout channels; a tile row is contiguous in NHWC for its nx valid pixels
+    const int cpp = Cout / 8;                                               // 16-byte chunks per pixel
+    const int cpr = STEM_TW * cpp;                                          // ... per tile row
+    const int nx = min(STEM_TW, Wo - ox0);
+    for (int id = lane; id < 4 * cpr; id += 64) {
+        const int r = id / cpr, c = id - r * cpr;
+        const int oy = oy0 + wave * 4 + r;
+        if (oy < Ho && c < nx * cpp)
+            *reinterpret_cast<u32x4*>(out + (((size_t)b * Ho + oy) * Wo + ox0) * Cout + (size_t)c * 8) =
+                *reinterpret_cast<const u32x4*>(strip + (size_t)id * 8);
+    }
 }
 
 int launch_stem(const float* x, const float* w, const float* bias, bf16_t* out, int B, int H, int W, int Cout, int act,
                 hipStream_t st) {
     MI355_REQUIRE(Cout % 8 == 0 && Cout <= 256, "stem: Cout=%d must be a multiple of 8 and <= 256", Cout);
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-    dim3 grid(cdiv(Wo, 32), cdiv(Ho, 8), B);
-    hipLaunchKernelGGL(k_stem, grid, dim3(256), 0, st, x, w, bias, out, H, W, Ho, Wo, Cout, act);
+    const size_t lds = stem_lds_bytes(Cout);
+    static bool attr_done[MI355_MAX_DEVICES] = {};
+    if (lds > 65536 && first_time_on_this_device(attr_done))
+        MI355_CHECK_HIP(hipFuncSetAttribute((const void*)k_stem, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                            (int)stem_lds_bytes(256)));
+    dim3 grid(cdiv(Wo, STEM_TW), cdiv(Ho, STEM_TH), B);
+    hipLaunchKernelGGL(k_stem, grid, dim3(256), lds, st, x, w, bias, out, H, W, Ho, Wo, Cout, act);
     MI355_LAUNCH_CHECK();
     return OK;
 }

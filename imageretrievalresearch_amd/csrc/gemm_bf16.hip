@@ -1079,85 +1079,123 @@ static int launch_nt(const GemmArgs& a, int nt, hipStream_t st) {
 
 // =====================================================================================
 // Head 1x1 conv + bias + activation + GLOBAL AVERAGE POOL in one kernel (get_fm, train/train.py:84-103, is the
-// epilogue of conv_head / features.16 whenever the caller wants the pooled embedding): one workgroup = one image x 128 output
-// channels, so a tile never spans two images and the pooled value of a channel is complete inside the workgroup.  The head
-// tensor (B x 49 x 1536 bf16: 38.5 MB written and re-read at B = 256) and the k_gap launch (25 us) disappear.
+// epilogue of conv_head / features.16 whenever the caller wants the pooled embedding): the pooled value of a channel is
+// complete inside one wave, so a tile never spans two images.  The head tensor (B x 49 x 1536 bf16: 38.5 MB written and
+// re-read at B = 256) and the k_gap launch (25 us) disappear.
+// One workgroup = 128 output channels x 4 images, one image per wave.  The workgroup's weight tile [128][K] is staged in LDS
+// once and shared by the four waves (one image x 128 channels per workgroup re-read the whole 1.2 MB weight matrix from L2
+// for every image: ~0.9 GB of L2 -> CU traffic, 93 us); each wave streams its image's 64-row A fragments from L2 two k-steps
+// ahead and runs 32 MFMAs per k-step from the LDS weights.
 // Same arithmetic as the two-kernel path, bit for bit: fp32 MFMA accumulation over ascending k-steps from zero, bias added
 // last, activation, ONE bf16 rounding per element, then the sequential fp32 sum over the pixels in ascending order and one
-// multiply by 1 / HW (k_gap's order).  Operands come straight from L2 into MFMA fragments (K <= 512, HW <= 64: 12 k-steps).
+// multiply by 1 / HW (k_gap's order).  The pooling runs 16 pixels at a time through a wave-private LDS strip, every lane
+// carrying the running sums of two channels in registers (the old kernel summed 49 pixels serially in half the threads
+// after a full-tile barrier).
 // =====================================================================================
-template <int ACT>
+constexpr int HG_NT = 128;               // output channels per workgroup
+constexpr int HG_SLD = HG_NT + 8;        // pooling strip row stride (bf16)
+
+static int head_gap_wld(int K) { return ((K + 31) & ~31) + 8; }     // LDS weight row stride (bf16), padded against conflicts
+static size_t head_gap_lds_bytes(int K) {
+    return (size_t)HG_NT * head_gap_wld(K) * sizeof(bf16_t) + (size_t)4 * 16 * HG_SLD * sizeof(bf16_t);
+}
+
+template <int ACT, int KSMAX>
 __global__ __launch_bounds__(256) void k_head_gap(const bf16_t* __restrict__ A, int lda, const bf16_t* __restrict__ W, int ldw,
                                                   const float* __restrict__ bias, float* __restrict__ pooled,
-                                                  bf16_t* __restrict__ pooled_bf16, int ldp, int HW, int N, int K) {
-    constexpr int TLD = 132;
-    __shared__ __attribute__((aligned(16))) float T[64 * TLD];
+                                                  bf16_t* __restrict__ pooled_bf16, int ldp, int B, int HW, int N, int K) {
+    extern __shared__ __attribute__((aligned(16))) bf16_t hg_sm[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int fr = lane & 15, fq = lane >> 4;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int b = blockIdx.y, n0 = blockIdx.x * 128;
+    const int n0 = blockIdx.x * HG_NT;
     const int Npad = (N + 15) & ~15;
-    const bf16_t* Ab = A + (size_t)b * HW * lda;
-    const bf16_t* arow[2];
-    const bf16_t* wrow[4];
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi) arow[mi] = Ab + (size_t)min(wm * 32 + mi * 16 + fr, HW - 1) * lda;   // rows past the image: clamped, never summed
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) wrow[ni] = W + (size_t)min(n0 + wn * 64 + ni * 16 + fr, Npad - 1) * ldw;
-    f32x4 acc[4][2];
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi) acc[ni][mi] = (f32x4){0.f, 0.f, 0.f, 0.f};
     const int nks = (K + 31) >> 5;
-    u32x4 af[2][2], wf[2][4];
-    // k >= lda (the weight matrix is zero there): re-read the row's last 16 bytes instead of running past it
-    auto load = [&](int s, int ks) {
-        const int ka = min(ks * 32 + fq * 8, lda - 8), kw = ks * 32 + fq * 8;
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi) af[s][mi] = *reinterpret_cast<const u32x4*>(arow[mi] + ka);
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) wf[s][ni] = *reinterpret_cast<const u32x4*>(wrow[ni] + kw);
-    };
-    load(0, 0);
-    for (int ks = 0; ks < nks; ks += 2) {
-        if (ks + 1 < nks) load(1, ks + 1);
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-                acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<bf16x8*>(&wf[0][ni]), *reinterpret_cast<bf16x8*>(&af[0][mi]), acc[ni][mi], 0, 0, 0);
-        if (ks + 1 < nks) {
-            if (ks + 2 < nks) load(0, ks + 2);
-#pragma unroll
-            for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-                for (int mi = 0; mi < 2; ++mi)
-                    acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<bf16x8*>(&wf[1][ni]), *reinterpret_cast<bf16x8*>(&af[1][mi]), acc[ni][mi], 0, 0, 0);
-        }
-    }
-    // bias + activation + the bf16 rounding the head tensor would have had, into the LDS tile [pixel][channel]
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) {
-        const int nl = wn * 64 + ni * 16 + fq * 4;
-        f32x4 bb = {0.f, 0.f, 0.f, 0.f};
-        if (n0 + nl < Npad) bb = *reinterpret_cast<const f32x4*>(bias + n0 + nl);
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi) {
-            const int ml = wm * 32 + mi * 16 + fr;
-            f32x4 v;
-            v.x = bf2f(f2bf(act_c<ACT>(acc[ni][mi].x + bb.x))); v.y = bf2f(f2bf(act_c<ACT>(acc[ni][mi].y + bb.y)));
-            v.z = bf2f(f2bf(act_c<ACT>(acc[ni][mi].z + bb.z))); v.w = bf2f(f2bf(act_c<ACT>(acc[ni][mi].w + bb.w)));
-            *reinterpret_cast<f32x4*>(&T[ml * TLD + nl]) = v;
+    const int WLD = nks * 32 + 8;
+    bf16_t* Ws = hg_sm;                                                   // [HG_NT][WLD]
+    bf16_t* strip = hg_sm + HG_NT * WLD + wave * 16 * HG_SLD;            // [16][HG_SLD], this wave's
+    // weight tile: 16-byte loads, rows past N clamped (their outputs are never pooled), k < nks * 32 <= ldw
+    {
+        const int cpr = nks * 4;                                          // 16-byte chunks per row
+        for (int i = tid; i < HG_NT * cpr; i += 256) {
+            const int r = i / cpr, c = i - r * cpr;
+            *reinterpret_cast<u32x4*>(&Ws[r * WLD + c * 8]) =
+                *reinterpret_cast<const u32x4*>(W + (size_t)min(n0 + r, Npad - 1) * ldw + c * 8);
         }
     }
     __syncthreads();
-    if (tid < 128 && n0 + tid < N) {
-        float s = 0.f;
-        for (int i = 0; i < HW; ++i) s += T[i * TLD + tid];
-        s *= 1.0f / (float)HW;
-        pooled[(size_t)b * ldp + n0 + tid] = s;
-        if (pooled_bf16) pooled_bf16[(size_t)b * ldp + n0 + tid] = f2bf(s);
+    const int b = blockIdx.y * 4 + wave;
+    if (b >= B) return;                                                   // no workgroup barrier after this point
+    const bf16_t* Ab = A + (size_t)b * HW * lda;
+    const bf16_t* arow[4];
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi) arow[mi] = Ab + (size_t)min(mi * 16 + fr, HW - 1) * lda;   // rows past the image: clamped, never summed
+    f32x4 acc[8][4];
+#pragma unroll
+    for (int ni = 0; ni < 8; ++ni)
+#pragma unroll
+        for (int mi = 0; mi < 4; ++mi) acc[ni][mi] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    u32x4 af[3][4];
+    // k >= lda (the weight matrix is zero there): re-read the row's last 16 bytes instead of running past it
+    auto load = [&](int s, int ks) {
+        const int ka = min(ks * 32 + fq * 8, lda - 8);
+#pragma unroll
+        for (int mi = 0; mi < 4; ++mi) af[s][mi] = *reinterpret_cast<const u32x4*>(arow[mi] + ka);
+    };
+    load(0, 0);
+    if (nks > 1) load(1, 1);
+#pragma unroll
+    for (int ks = 0; ks < KSMAX; ++ks) {
+        if (ks < nks) {
+            if (ks + 2 < nks) load((ks + 2) % 3, ks + 2);
+#pragma unroll
+            for (int ni = 0; ni < 8; ++ni) {
+                const u32x4 wf = *reinterpret_cast<const u32x4*>(&Ws[(ni * 16 + fr) * WLD + ks * 32 + fq * 8]);
+#pragma unroll
+                for (int mi = 0; mi < 4; ++mi)
+                    acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8*>(&wf),
+                                                                          *reinterpret_cast<const bf16x8*>(&af[ks % 3][mi]),
+                                                                          acc[ni][mi], 0, 0, 0);
+            }
+        }
+    }
+    // acc[ni][mi]: pixel mi * 16 + fr, channels ni * 16 + fq * 4 + 0..3.  Per 16-pixel chunk: bias + activation + the bf16
+    // rounding the head tensor would have had, into the strip [pixel][channel]; then lane l adds the chunk's pixels in
+    // ascending order onto the running sums of channels 2l, 2l + 1.
+    f32x4 bb[8];
+#pragma unroll
+    for (int ni = 0; ni < 8; ++ni) {
+        const int n = n0 + ni * 16 + fq * 4;
+        bb[ni] = n < Npad ? *reinterpret_cast<const f32x4*>(bias + n) : (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+    float s0 = 0.f, s1 = 0.f;
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi) {
+        if (mi * 16 >= HW) break;
+#pragma unroll
+        for (int ni = 0; ni < 8; ++ni) {
+            const f32x4 a = acc[ni][mi];
+            u32x2 o;
+            o.x = pack2bf(act_c<ACT>(a.x + bb[ni].x), act_c<ACT>(a.y + bb[ni].y));
+            o.y = pack2bf(act_c<ACT>(a.z + bb[ni].z), act_c<ACT>(a.w + bb[ni].w));
+            *reinterpret_cast<u32x2*>(&strip[fr * HG_SLD + ni * 16 + fq * 4]) = o;
+        }
+        // (same wave wrote and reads its strip: LDS ops complete in order, no barrier needed)
+        const int np = min(16, HW - mi * 16);
+        for (int i = 0; i < np; ++i) {
+            const unsigned v = *reinterpret_cast<const unsigned*>(&strip[i * HG_SLD + 2 * lane]);
+            s0 += __uint_as_float(v << 16);
+            s1 += __uint_as_float(v & 0xffff0000u);
+        }
+    }
+    const int n = n0 + 2 * lane;
+    if (n < N) {
+        s0 *= 1.0f / (float)HW;
+        s1 *= 1.0f / (float)HW;
+        *reinterpret_cast<float2*>(&pooled[(size_t)b * ldp + n]) = make_float2(s0, s1);
+        if (pooled_bf16) {
+            pooled_bf16[(size_t)b * ldp + n] = f2bf(s0);
+            pooled_bf16[(size_t)b * ldp + n + 1] = f2bf(s1);
+        }
     }
 }
 
@@ -1166,14 +1204,29 @@ bool head_gap_supported(int HW, int N, int K, int lda, int ldw, int act) {
            (act == ACT_SILU || act == ACT_NONE);
 }
 
+template <int ACT, int KSMAX>
+static int launch_head_gap_cfg(const bf16_t* A, int lda, const bf16_t* W, int ldw, const float* bias, float* pooled,
+                               bf16_t* pooled_bf16, int ldp, int B, int HW, int N, int K, hipStream_t st) {
+    static bool attr_done[MI355_MAX_DEVICES] = {};
+    if (first_time_on_this_device(attr_done))
+        MI355_CHECK_HIP(hipFuncSetAttribute((const void*)k_head_gap<ACT, KSMAX>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                            (int)head_gap_lds_bytes(KSMAX * 32)));
+    const dim3 grid((unsigned)cdiv(N, HG_NT), (unsigned)cdiv(B, 4));
+    hipLaunchKernelGGL((k_head_gap<ACT, KSMAX>), grid, dim3(256), head_gap_lds_bytes(K), st, A, lda, W, ldw, bias, pooled,
+                       pooled_bf16, ldp, B, HW, N, K);
+    MI355_LAUNCH_CHECK();
+    return OK;
+}
+
 int launch_head_gap(const bf16_t* A, int lda, const bf16_t* W, int ldw, const float* bias, float* pooled, bf16_t* pooled_bf16,
                     int ldp, int B, int HW, int N, int K, int act, hipStream_t st) {
     MI355_REQUIRE(head_gap_supported(HW, N, K, lda, ldw, act), "head_gap: unsupported shape HW=%d N=%d K=%d", HW, N, K);
-    const dim3 grid((unsigned)cdiv(N, 128), (unsigned)B);
-    if (act == ACT_SILU) hipLaunchKernelGGL(k_head_gap<ACT_SILU>, grid, dim3(256), 0, st, A, lda, W, ldw, bias, pooled, pooled_bf16, ldp, HW, N, K);
-    else hipLaunchKernelGGL(k_head_gap<ACT_NONE>, grid, dim3(256), 0, st, A, lda, W, ldw, bias, pooled, pooled_bf16, ldp, HW, N, K);
-    MI355_LAUNCH_CHECK();
-    return OK;
+    const bool small_k = K <= 12 * 32;
+    if (act == ACT_SILU)
+        return small_k ? launch_head_gap_cfg<ACT_SILU, 12>(A, lda, W, ldw, bias, pooled, pooled_bf16, ldp, B, HW, N, K, st)
+                       : launch_head_gap_cfg<ACT_SILU, 16>(A, lda, W, ldw, bias, pooled, pooled_bf16, ldp, B, HW, N, K, st);
+    return small_k ? launch_head_gap_cfg<ACT_NONE, 12>(A, lda, W, ldw, bias, pooled, pooled_bf16, ldp, B, HW, N, K, st)
+                   : launch_head_gap_cfg<ACT_NONE, 16>(A, lda, W, ldw, bias, pooled, pooled_bf16, ldp, B, HW, N, K, st);
 }
 
 // Which branch ran goes to *path (MI355_GEMM_PATH_* | NT << 8, include/mi355_retrieval.h) when path is not null: the op-level tests
