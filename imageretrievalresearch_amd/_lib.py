@@ -61,6 +61,13 @@ PROTOTYPES = {
                                                C.POINTER(RankFilter), vp, vp, vp, C.c_size_t, vp]),
     "mi355_rank_last_path": (C.c_int, []),
     "mi355_clear_pads": (C.c_int, [vp, vp, C.c_int64, C.c_int64, C.c_int64, vp]),
+    "mi355_range_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int]),
+    "mi355_cosine_range": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_double, C.c_int64,
+                                     C.POINTER(RankFilter), vp, C.c_int64, C.POINTER(C.c_int64), vp, C.c_size_t, vp]),
+    "mi355_range_f16_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int]),
+    "mi355_cosine_range_f16": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_float, C.c_double, C.c_int64,
+                                         C.POINTER(RankFilter), vp, C.c_int64, C.POINTER(C.c_int64), vp, C.c_size_t, vp]),
+    "mi355_range_compact": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp, C.c_size_t, vp, vp, vp, vp]),
     "mi355_roc_pairs_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int]),
     "mi355_roc_pairs_hist": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_float, vp, vp, vp, C.c_int64,
                                        C.POINTER(C.c_double), vp, C.c_int, vp, vp, C.c_size_t, vp]),

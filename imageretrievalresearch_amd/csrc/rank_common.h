@@ -314,6 +314,131 @@ __device__ __forceinline__ void cos_gemm_epilogue(f32x16 (&acc)[MT][2], float* s
     }
 }
 
+// ---- cosine range search (mi355_cosine_range[_f16]): the fourth epilogue mode keeps every (query, gallery row) pair whose score
+// is >= the threshold (float64 comparison: fp32 score >= roc_ceil_f32(t); NaN never), filtered as the top-k search filters.
+// Per (query row, column tile) the hits are a bit mask in LDS; one 64-bit atomic per workgroup reserves the tile's hits in a
+// candidate buffer, where each row's hits land in ascending column order, and (start, count) of each (query, tile) goes to
+// a table that the compaction (range.hip) walks in tile order: the output never depends on the order of the atomics.
+constexpr int FK_RANGE = -2;                            // the range mode in the launcher's FK slot
+
+struct RangeArgs {
+    RankFilter f;               // the filter of this call's queries (mode ANY and excl null: none)
+    float thr;                  // roc_ceil_f32(threshold)
+    unsigned long long* cursor; // hits of this GEMM call so far (zeroed by the host before it)
+    unsigned long long* raw;    // [cap] hits {local column | score bits << 32}, chunks in reservation order
+    i64 cap;                    // entries raw holds: a tile whose chunk would pass it writes nothing (the counts stay exact)
+    i64* tstart;                // [Q][ntx] first raw entry of (query, column tile)
+    int* tcount;                // [Q][ntx] its hits
+};
+
+// LDS of the range epilogue: hit masks [BM][4] u32, row counts / prefixes [BM], the workgroup's base, then the tile's gallery
+// labels [128], its query labels and LOCAL excluded rows [BM] (inside the staging buffers of every loop: static_assert in
+// launch_tiles)
+constexpr size_t RANGE_EPI_BYTES = (size_t)128 * 4 * sizeof(unsigned) + (size_t)128 * sizeof(int) + 2 * sizeof(i64) +
+                                   (size_t)(RK_BN + 2 * 128) * sizeof(i64);
+
+// The range epilogue: the overload of cos_gemm_epilogue that a kernel twin selects by passing RangeArgs (see the histogram
+// epilogue).  Scores are acc * ginv[col] as in the other modes: every hit has the bits of mi355_cosine_scores on the same loop.
+// Called after a __syncthreads() that retired every read of the staging buffers.
+template <int MT, int FK, bool FILT>
+__device__ __forceinline__ void cos_gemm_epilogue(f32x16 (&acc)[MT][2], float* smem, const float* __restrict__ ginv, float*, int Q,
+                                                  i64 G, int, float*, int*, int, int ntx, i64 n0, int m0, const RangeArgs& rg) {
+    static_assert(FK == FK_RANGE && !FILT, "the range twins pass FK = FK_RANGE, FILT = false");
+    constexpr int BM = 64 * MT;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1, lr = lane & 31;
+    unsigned* mask = reinterpret_cast<unsigned*>(smem);                      // [BM][4]: bit c % 32 of word c / 32 = column c
+    int* rpre = reinterpret_cast<int*>(mask + 128 * 4);                      // [BM] hits of row, then their exclusive prefix
+    unsigned long long* sbase = reinterpret_cast<unsigned long long*>(rpre + 128);   // [0] the reservation, [1] the total
+    i64* glab = reinterpret_cast<i64*>(sbase + 2);                           // [128]
+    i64* qlab = glab + RK_BN;                                                // [BM]
+    i64* qex = qlab + 128;                                                   // [BM] LOCAL excluded row, -1: none
+    const bool filt = rg.f.mode != MI355_LABEL_ANY || rg.f.excl;
+    if (filt) {
+        if (tid < RK_BN) glab[tid] = rg.f.mode != MI355_LABEL_ANY && n0 + tid < G ? rg.f.glab[n0 + tid] : 0;
+        if (tid < BM) {
+            i64 l = 0, e = -1;
+            if (m0 + tid < Q) query_filter(rg.f, m0 + tid, l, e);
+            qlab[tid] = l;
+            qex[tid] = e;
+        }
+        __syncthreads();
+    }
+    // 1. the hit masks: in the MFMA layout lanes 0-31 hold 32 consecutive columns of one row, lanes 32-63 those of row + 4,
+    //    so one ballot is two whole mask words; each (row, word) belongs to exactly one wave
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int c = wn * 64 + j * 32 + lr;
+        const i64 col = n0 + c;
+        const float gs = (ginv && col < G) ? ginv[col] : 1.0f;
+        const i64 gl = filt ? glab[c] : 0;
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = wm * MT * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                bool hit = col < G && m0 + row < Q && acc[i][j][r] * gs >= rg.thr;
+                if (filt) hit = hit && eligible(rg.f.mode, qlab[row], gl, qex[row], col);
+                const unsigned long long b = __ballot(hit);
+                if (lane == 0) {
+                    mask[row * 4 + wn * 2 + j] = (unsigned)b;
+                    mask[(row + 4) * 4 + wn * 2 + j] = (unsigned)(b >> 32);
+                }
+            }
+    }
+    __syncthreads();
+    // 2. per row: its hits, their exclusive prefix over the tile's rows (a scan per wave, waves 0 and 1), ONE reservation
+    int cnt = 0, incl = 0;
+    if (tid < BM) {
+        cnt = __popc(mask[tid * 4]) + __popc(mask[tid * 4 + 1]) + __popc(mask[tid * 4 + 2]) + __popc(mask[tid * 4 + 3]);
+        incl = cnt;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int v = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += v;
+        }
+        if (tid == 63) sbase[1] = (unsigned long long)incl;                  // wave 0's total
+    }
+    __syncthreads();
+    if (tid < BM) {
+        if (tid >= 64) incl += (int)sbase[1];
+        rpre[tid] = incl - cnt;
+        if (tid == BM - 1) sbase[0] = incl > 0 ? atomicAdd(rg.cursor, (unsigned long long)incl) : 0ull;
+    }
+    __syncthreads();
+    const unsigned long long base = sbase[0];
+    const int tile = (int)(n0 / RK_BN);
+    if (tid < BM && m0 + tid < Q) {
+        const size_t t = (size_t)(m0 + tid) * ntx + tile;
+        rg.tstart[t] = (i64)base + rpre[tid];
+        rg.tcount[t] = cnt;
+    }
+    const int total = rpre[BM - 1] + __popc(mask[(BM - 1) * 4]) + __popc(mask[(BM - 1) * 4 + 1]) + __popc(mask[(BM - 1) * 4 + 2]) +
+                      __popc(mask[(BM - 1) * 4 + 3]);
+    if (total == 0 || (i64)base + total > rg.cap) return;                   // nothing to write, or past the buffer: counts only
+    // 3. every hit from its accumulator to base + row prefix + the popcount of the row's bits before it
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int c = wn * 64 + j * 32 + lr, w = wn * 2 + j;
+        const i64 col = n0 + c;
+        const float gs = (ginv && col < G) ? ginv[col] : 1.0f;
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = wm * MT * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                const unsigned* m = mask + row * 4;
+                if ((m[w] >> lr) & 1u) {
+                    int before = __popc(m[w] & ((1u << lr) - 1u));
+                    for (int u = 0; u < w; ++u) before += __popc(m[u]);
+                    const float s = acc[i][j][r] * gs;
+                    rg.raw[base + rpre[row] + before] = (unsigned long long)(unsigned)col |
+                                                        ((unsigned long long)__float_as_uint(s) << 32);
+                }
+            }
+    }
+}
+
 // Row norm of an fp32 row: one wave, float4 loads when vec (dim % 4 == 0 and 16-B aligned rows).  The lane-strided
 // summation order is part of the result: every row normalisation of the library (mi355_l2_normalize_rows, the queries
 // of every search, the fp16 gallery conversion) goes through this one function, so they give the same bits.
@@ -365,6 +490,7 @@ int whole_round_tiles(int ntx, int ny, int slots);
 // ---- host side of the tiled cosine GEMMs: exact fp32, split bf16 (rank.hip: F32Gemm, SplitGemm, PreparedGemm) and fp16
 // (rank_f16.hip: F16Gemm).  A family F supplies only what differs between them:
 //   F::SLAB, F::FILTERED, F::ROC     whether it has score-slab (FK = 0) / filtered / histogram (FK = FK_ROC) kernels
+//   F::RANGE                         whether it has range (FK = FK_RANGE) kernels
 //   F::stage_bytes<MT>()             the LDS of its staging buffers
 //   F::kernel<MT, FK, FILT>()        its kernel
 //   F::launch<MT, FK, FILT>(...)     one launch of that kernel over column tiles [x0, x0 + xtiles) x ny query tiles
@@ -384,6 +510,7 @@ struct TileArgs {
     int* cand_idx;
     const RankFilter* filt;     // the queries' filter (fused selection), or null
     const RocArgs* roc;         // the histogram mode (the queries' labels / exclude of this call), or null
+    const RangeArgs* rng;       // the range mode (the queries' filter, candidates and table of this call), or null
 };
 
 constexpr size_t EPI_TILE_BYTES = (size_t)64 * (RK_BN + 4) * sizeof(float);   // the fused selection's transposed score tile
@@ -405,6 +532,7 @@ template <class F, int MT, int FK, bool FILT>
 int launch_tiles(const TileArgs& a, hipStream_t st, int x0 = 0) {
     constexpr size_t stage = F::template stage_bytes<MT>();
     static_assert(!FILT || stage >= EPI_TILE_BYTES + FILT_LABELS_BYTES, "the filtered epilogue would grow the GEMM's LDS");
+    static_assert(FK != FK_RANGE || stage >= RANGE_EPI_BYTES, "the range epilogue would grow the GEMM's LDS");
     constexpr size_t lds = FK == FK_ROC ? (ROC_EPI_BYTES > stage ? ROC_EPI_BYTES : stage)
                                         : FK > 0 && EPI_TILE_BYTES > stage ? EPI_TILE_BYTES : stage;
     int slots = 0;
@@ -434,6 +562,9 @@ int launch_mt(const TileArgs& a, hipStream_t st) {
     if constexpr (F::ROC) {
         if (a.roc) return launch_tiles<F, MT, FK_ROC, false>(a, st);
     }
+    if constexpr (F::RANGE) {
+        if (a.rng) return launch_tiles<F, MT, FK_RANGE, false>(a, st);
+    }
     if constexpr (F::SLAB) {
         if (!a.cand_val) {
             TileArgs s = a;
@@ -446,7 +577,8 @@ int launch_mt(const TileArgs& a, hipStream_t st) {
     }
     return launch_fk<F, MT, false>(a, st);
 }
-// A GEMM call of family F: 128-query tiles above 64 queries, 64-query tiles otherwise.  a.roc: the histogram mode.
+// A GEMM call of family F: 128-query tiles above 64 queries, 64-query tiles otherwise.  a.roc: the histogram mode, a.rng: the
+// range mode.
 template <class F>
 int cos_gemm_tiles(const TileArgs& a, hipStream_t st) {
     return a.Q > 64 ? launch_mt<F, 2>(a, st) : launch_mt<F, 1>(a, st);
@@ -496,6 +628,60 @@ int search_blocks(const float* queries, const float* gallery_to_norm, i64 Q, i64
                                 out_idx + q0 * k, w.topk, w.topk_bytes, st, w.cand_idx, f))
             return e;
     }
+    return OK;
+}
+
+// ---- host side of the range search (range.hip)
+// Workspace of mi355_cosine_range[_f16]: the CSR offsets [Q + 1] first (mi355_range_compact finds them there), the call's
+// hit cursor, the search's own scratch (carve: normalised queries, planes of one GEMM call, 1 / |row|), then the
+// (query, tile) table and the row counts of one query block.  ws null: sizes only.
+struct RangeWs {
+    i64* offsets; unsigned long long* cursor; RankWs w; i64* tstart; int* tcount; i64* rowcnt; size_t total;
+};
+RangeWs range_carve(void* ws, i64 Q, i64 G, int D, size_t (*planes_bytes)(i64, int), bool need_ginv);
+// Queries per GEMM call of a range search: the (query, tile) table of one call stays around 100 MB
+i64 range_query_block(i64 Q, i64 G);
+// The checks every range search shares (before any HIP call); fills *f from filter (null: no filter)
+int range_check(const void* queries, i64 Q, const void* gallery, i64 G, int dim, double threshold,
+                const mi355_rank_filter* filter, i64 idx_offset, void* candidates, i64 capacity, const int64_t* nnz,
+                const char* who, RankFilter* f);
+// Q = 0 or G = 0: all-zero offsets, no hit
+int range_empty(const RangeWs& w, i64 Q, int64_t* nnz, hipStream_t st);
+// The compaction of one query block [q0, q0 + qn) whose hits begin at CSR position off: row counts, offsets, then every
+// (query, tile) chunk of raw copied in tile order to canon[offsets[q] ...]
+int range_compact_block(const RangeWs& w, i64 q0, i64 qn, i64 G, i64 off, const unsigned long long* raw,
+                        unsigned long long* canon, hipStream_t st);
+
+// The query-block loop of a range search.  candidates: [2][capacity] entries, raw hits of one GEMM call (in reservation
+// order) then the canonical CSR payload of the whole call.  Per block: zero the cursor, score(q0, qn, args) runs the range
+// pass, the block's hit count is read back (the one host sync), and while everything so far fits the block is compacted.
+// Once a block does not fit, the rest only count (cap 0): *nnz is the exact total either way, and a call with
+// capacity >= *nnz fits.
+template <class Score>
+int range_blocks(i64 Q, i64 G, const RankFilter& filt, double threshold, void* candidates, i64 capacity, int64_t* nnz,
+                 const RangeWs& w, hipStream_t st, Score&& score) {
+    unsigned long long* raw = (unsigned long long*)candidates;
+    unsigned long long* canon = raw ? raw + capacity : nullptr;
+    MI355_CHECK_HIP(hipMemsetAsync(w.offsets, 0, sizeof(i64), st));
+    const i64 qb = range_query_block(Q, G);
+    i64 off = 0;
+    bool fits = true;
+    for (i64 q0 = 0; q0 < Q; q0 += qb) {
+        const i64 qn = (Q - q0 < qb) ? Q - q0 : qb;
+        MI355_CHECK_HIP(hipMemsetAsync(w.cursor, 0, sizeof(unsigned long long), st));
+        const RangeArgs a{filter_from(filt, q0), roc_ceil_f32(threshold), w.cursor, raw, fits ? capacity : 0, w.tstart, w.tcount};
+        if (int e = score(q0, qn, a)) return e;
+        unsigned long long n = 0;
+        MI355_CHECK_HIP(hipMemcpyAsync(&n, w.cursor, sizeof(n), hipMemcpyDeviceToHost, st));
+        MI355_CHECK_HIP(hipStreamSynchronize(st));
+        fits = fits && off + (i64)n <= capacity;
+        if (fits) {
+            RoctxRange range("range/compact");
+            if (int e = range_compact_block(w, q0, qn, G, off, raw, canon, st)) return e;
+        }
+        off += (i64)n;
+    }
+    *nnz = off;
     return OK;
 }
 

@@ -128,6 +128,18 @@ __global__ __launch_bounds__(256) void k_cos_gemm_f16_roc(const f16* __restrict_
     int* const cand_idx = nullptr;
 #include "rank_gemm_f16.inc"
 }
+// The range twin (mi355_cosine_range_f16): the same body, the range epilogue (its overload takes RangeArgs as `flt`)
+template <int MT>
+__global__ __launch_bounds__(256) void k_cos_gemm_f16_range(const f16* __restrict__ Qs, const f16* __restrict__ Gal, int Q, i64 G,
+                                                            int ld, int x0, int ntx, int xtiles, int ny, RangeArgs flt) {
+    constexpr int FK = FK_RANGE;
+    constexpr bool FILT = false;
+    float* const S = nullptr;
+    const int k = 0;
+    float* const cand_val = nullptr;
+    int* const cand_idx = nullptr;
+#include "rank_gemm_f16.inc"
+}
 
 // =====================================================================================
 // Few queries (Q <= 4, the one-query-at-a-time serving shape): a GEMV bound by streaming the gallery once (2 * ld bytes
@@ -191,12 +203,13 @@ static bool f16_gemv(i64 Q, int ld) { return Q <= 4 && (size_t)Q * ld * sizeof(f
 
 // The tiled GEMM over fp16 rows (launch_tiles, rank_common.h); qry: the queries' fp16 planes, gal: the rows, D: their length ld
 struct F16Gemm {
-    static constexpr bool SLAB = true, FILTERED = true, ROC = true;
+    static constexpr bool SLAB = true, FILTERED = true, ROC = true, RANGE = true;
     template <int MT> static constexpr size_t stage_bytes() {   // A ring of 2, B ring of 3
         return (size_t)2 * (64 * MT / 32) * 8 * 1024 + (size_t)3 * RK_BN * F16_KSTEP * 2;
     }
     template <int MT, int FK, bool FILT> static const void* kernel() {
         if constexpr (FK == FK_ROC) return (const void*)k_cos_gemm_f16_roc<MT>;
+        else if constexpr (FK == FK_RANGE) return (const void*)k_cos_gemm_f16_range<MT>;
         else if constexpr (FILT) return (const void*)k_cos_gemm_f16_filt<MT, FK>;
         else return (const void*)k_cos_gemm_f16<MT, FK>;
     }
@@ -206,6 +219,8 @@ struct F16Gemm {
         const f16* gal = (const f16*)a.gal;
         if constexpr (FK == FK_ROC)
             hipLaunchKernelGGL((k_cos_gemm_f16_roc<MT>), grid, dim3(256), lds, st, qs, gal, a.Q, a.G, a.D, x0, ntx, xtiles, ny, *a.roc);
+        else if constexpr (FK == FK_RANGE)
+            hipLaunchKernelGGL((k_cos_gemm_f16_range<MT>), grid, dim3(256), lds, st, qs, gal, a.Q, a.G, a.D, x0, ntx, xtiles, ny, *a.rng);
         else if constexpr (FILT)
             hipLaunchKernelGGL((k_cos_gemm_f16_filt<MT, FK>), grid, dim3(256), lds, st, qs, gal, a.Q, a.G, a.D, a.k, a.cand_val,
                                a.cand_idx, x0, ntx, xtiles, ny, *a.filt);
@@ -349,6 +364,37 @@ int mi355_roc_pairs_hist_f16(const float* queries, int64_t Q, const void* galler
             return e;
     }
     return OK;
+}
+
+size_t mi355_range_f16_workspace_bytes(int64_t Q, int64_t G, int dim) {
+    if (Q < 0 || G < 0 || dim < 1) return 0;
+    return range_carve(nullptr, Q, G, dim, f16_planes_bytes, false).total;   // normalised queries + one call's planes + table
+}
+
+int mi355_cosine_range_f16(const float* queries, int64_t Q, const void* gallery_f16, int64_t G, int dim, float eps, double threshold,
+                           int64_t idx_offset, const mi355_rank_filter* filter, void* candidates, int64_t capacity, int64_t* nnz,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "cosine_range_f16";
+    RankFilter f{};
+    if (int e = range_check(queries, Q, gallery_f16, G, dim, threshold, filter, idx_offset, candidates, capacity, nnz, who, &f))
+        return e;
+    MI355_REQUIRE(((uintptr_t)gallery_f16 & 15) == 0, "%s: gallery buffer must be 16-byte aligned", who);
+    const RangeWs w = range_carve(workspace, Q, G, dim, f16_planes_bytes, false);
+    MI355_REQUIRE(workspace && workspace_bytes >= w.total, "%s: workspace %zu < %zu bytes", who, workspace_bytes, w.total);
+    hipStream_t st = (hipStream_t)stream;
+    if (Q == 0 || G == 0) return range_empty(w, Q, nnz, st);
+    if (int e = normalize_search(queries, Q, nullptr, G, dim, eps, w.w, st)) return e;
+    const int ld = f16_ld(dim), n_sub = ld / 16;
+    return range_blocks(Q, G, f, threshold, candidates, capacity, nnz, w, st, [&](i64 q0, i64 qn, const RangeArgs& a) -> int {
+        RoctxRange range("range/cosine gemm (fp16 gallery) + hits");
+        set_rank_path(MI355_RANK_PATH_F16_GEMM);
+        const int n_frag = cdiv(qn, 128) * 4 * n_sub;
+        hipLaunchKernelGGL(k_split_queries_f16, dim3((unsigned)cdiv(n_frag, 4)), dim3(256), 0, st, w.w.qn + q0 * dim, (f16*)w.w.qs,
+                           (int)qn, dim, n_sub, n_frag);
+        MI355_LAUNCH_CHECK();
+        TileArgs t{w.w.qs, gallery_f16, nullptr, nullptr, (int)qn, G, ld, 0, nullptr, nullptr, nullptr, nullptr, &a};
+        return cos_gemm_tiles<F16Gemm>(t, st);
+    });
 }
 
 }  // extern "C"

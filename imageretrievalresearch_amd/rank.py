@@ -9,10 +9,12 @@ routes the arithmetic to libmi355_retrieval:
 * ``ContrastiveLoss(margin)(fm1, fm2, label, mean)`` ... utils/contrastive_loss.py:6-61
 * ``hit_counts`` / ``distinct_class_topn`` .... train/train.py:252-255 ; notebook raw :240-251
 * ``roc_curve`` / ``verification_roc`` ........ utils/roc_curve_from_scratch.py (given pair scores / every labelled pair)
+* ``cosine_range`` ............................ the pairs a verification threshold accepts (``score >= threshold``)
 """
 from __future__ import annotations
 
 import ctypes
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -580,6 +582,26 @@ class Gallery:
         return cosine_topk(queries, self.data, k, self.eps, gallery_is_normalized=True, idx_offset=idx_offset,
                            query_labels=query_labels, gallery_labels=self.labels, label_filter=label_filter, exclude=exclude)
 
+    def range_search(self, queries: torch.Tensor, threshold: float, *, query_labels: torch.Tensor | None = None,
+                     label_filter: str | None = None, exclude: torch.Tensor | None = None, max_results: int | None = None,
+                     idx_offset: int = 0) -> RangeResult:
+        """``cosine_range`` of ``queries`` against the resident rows: every row whose score is >= ``threshold``, with the
+        scores of this gallery's own kernel (fp32 rows: ``cosine_scores`` of the normalised rows, a prepared gallery
+        included; fp16 rows: the f16-MFMA kernel).  ``label_filter`` uses the labels given to ``add``."""
+        if label_filter is not None and self.labels is None:
+            raise MI355Error(f'label_filter="{label_filter}" needs gallery labels: add(embeddings, labels)')
+        if self.labels is not None and label_filter is not None and self.labels.shape[0] != self.rows:
+            raise MI355Error(f"the gallery holds {self.labels.shape[0]} labels for {self.rows} rows")
+        if self.dtype != torch.float16:
+            return cosine_range(queries, self.data, threshold, eps=self.eps, gallery_is_normalized=True, idx_offset=idx_offset,
+                                query_labels=query_labels, gallery_labels=self.labels, label_filter=label_filter,
+                                exclude=exclude, max_results=max_results)
+        q = _f32c(queries, "queries")
+        _check_qg(q, self.data)
+        t = _range_threshold(threshold)
+        filt = _rank_filter(q.shape[0], self.rows, q.device, query_labels, self.labels, label_filter, exclude)
+        return _range(q, self._buf, self.rows, t, idx_offset, filt, max_results, self.eps, f16_dim=self.dim)
+
     def _roc_labels(self):
         if self.labels is None:
             raise MI355Error("verification_roc needs gallery labels: add(embeddings, labels)")
@@ -833,3 +855,95 @@ def verification_roc(queries: torch.Tensor, query_labels: torch.Tensor, gallery:
         ex = None if exclude is None else _int64_on(exclude, "exclude", Q, q.device)
     thr = _roc_thresholds(thresholds, q.device)
     return _roc_finalize(_roc_pairs_hist(q, ql, g, g.shape[0], gl, ex, idx_offset, thr, eps), thr)
+
+
+# ---- cosine range search: every gallery row at or above a threshold
+class RangeResult(NamedTuple):
+    """CSR result of ``cosine_range``: the hits of query q are ``indices[offsets[q]:offsets[q + 1]]`` (global rows, ascending)
+    with their ``scores``."""
+    offsets: torch.Tensor          # (Q + 1,) int64
+    indices: torch.Tensor          # (nnz,) int64
+    scores: torch.Tensor           # (nnz,) fp32
+
+
+_cand = _Workspace()               # the search's candidate buffers ([2][capacity] 8-byte entries), grown to the largest need
+_MIN_CAPACITY = 1 << 16
+
+
+def _range_threshold(threshold) -> float:
+    t = float(threshold)
+    if not np.isfinite(t):
+        raise MI355Error(f"threshold must be finite, got {threshold!r}")
+    return t
+
+
+def _range_empty(Q: int, device) -> RangeResult:
+    return RangeResult(torch.zeros(Q + 1, dtype=torch.int64, device=device), torch.empty(0, dtype=torch.int64, device=device),
+                       torch.empty(0, dtype=torch.float32, device=device))
+
+
+def _range(q: torch.Tensor, gallery: torch.Tensor, G: int, threshold: float, idx_offset: int, filt, max_results, eps: float,
+           gallery_is_normalized: bool = False, f16_dim: int | None = None) -> RangeResult:
+    """The range search of queries ``q`` (Q, D) against ``G`` rows: fp32 rows ``gallery`` (G, D), or with ``f16_dim`` an fp16
+    gallery buffer (mi355_gallery_to_f16 layout).  Arguments checked by the caller.  One search into the cached candidate
+    buffer; if its hits do not fit, ONE more search with exactly that capacity; then the compaction into exact-size outputs."""
+    Q, D = q.shape
+    if max_results is not None and int(max_results) < 0:
+        raise MI355Error(f"max_results must be >= 0 or None, got {max_results}")
+    if Q == 0 or G == 0:
+        return _range_empty(Q, q.device)
+    L = lib()
+    dim = D if f16_dim is None else f16_dim
+    ws = _ws.get(q.device, L.mi355_range_workspace_bytes(Q, G, dim) if f16_dim is None else L.mi355_range_f16_workspace_bytes(Q, G, dim))
+    fp = ctypes.byref(filt[0]) if filt is not None else None
+    nnz = ctypes.c_int64(0)
+
+    def search(cand):
+        cap = cand.numel() // 16
+        with torch.cuda.device(q.device):
+            if f16_dim is None:
+                check(L.mi355_cosine_range(q.data_ptr(), Q, gallery.data_ptr(), G, D, int(gallery_is_normalized), eps, threshold,
+                                           int(idx_offset), fp, cand.data_ptr(), cap, ctypes.byref(nnz), ws.data_ptr(), ws.numel(),
+                                           stream_ptr(q.device)))
+            else:
+                check(L.mi355_cosine_range_f16(q.data_ptr(), Q, gallery.data_ptr(), G, f16_dim, eps, threshold, int(idx_offset), fp,
+                                               cand.data_ptr(), cap, ctypes.byref(nnz), ws.data_ptr(), ws.numel(),
+                                               stream_ptr(q.device)))
+        return cap, int(nnz.value)
+
+    cand = _cand.get(q.device, 16 * _MIN_CAPACITY)
+    cap, n = search(cand)
+    if max_results is not None and n > int(max_results):
+        raise MI355Error(f"the range search has {n} hits, more than max_results={int(max_results)}")
+    if n > cap:                                    # the exact count is known: one more search that fits
+        cand = _cand.get(q.device, 16 * n)
+        cap, n2 = search(cand)
+        if n2 != n:
+            raise MI355Error(f"the range search counted {n} hits, then {n2}")
+    offsets = torch.empty(Q + 1, dtype=torch.int64, device=q.device)
+    indices = torch.empty(n, dtype=torch.int64, device=q.device)
+    scores = torch.empty(n, dtype=torch.float32, device=q.device)
+    with torch.cuda.device(q.device):
+        check(L.mi355_range_compact(cand.data_ptr(), cap, Q, n, int(idx_offset), ws.data_ptr(), ws.numel(), offsets.data_ptr(),
+                                    indices.data_ptr() if n else None, scores.data_ptr() if n else None, stream_ptr(q.device)))
+    return RangeResult(offsets, indices, scores)
+
+
+def cosine_range(queries: torch.Tensor, gallery: torch.Tensor, threshold: float, *, eps: float = _EPS,
+                 gallery_is_normalized: bool = False, idx_offset: int = 0, query_labels: torch.Tensor | None = None,
+                 gallery_labels: torch.Tensor | None = None, label_filter: str | None = None,
+                 exclude: torch.Tensor | None = None, max_results: int | None = None) -> RangeResult:
+    """Every (query, gallery row) pair whose cosine score is ``>= threshold``, as a CSR ``RangeResult(offsets, indices,
+    scores)``.
+
+    The comparison is the float64 ``score >= threshold`` of the reference's verification decision (an fp32 score against the
+    smallest float not below ``threshold``; a NaN score never qualifies).  Each score has the bits ``cosine_scores`` gives
+    the pair on the same path (any Q: the tiled GEMM), and no (Q, G) score matrix is made.  Within a query the rows ascend;
+    the result is the same bit for bit on every run.  Filters as in ``cosine_topk`` (``label_filter``, ``exclude``,
+    ``idx_offset``).  ``max_results``: raise ``MI355Error`` if there are more hits, before any output is allocated.  One host
+    sync per query block (its hit count), as ``torch.nonzero``."""
+    q, g = _f32c(queries, "queries"), _f32c(gallery, "gallery")
+    _check_qg(q, g)
+    t = _range_threshold(threshold)
+    filt = _rank_filter(q.shape[0], g.shape[0], q.device, query_labels, gallery_labels, label_filter, exclude)
+    return _range(q, g, g.shape[0], t, idx_offset, filt, max_results, eps, gallery_is_normalized=gallery_is_normalized)

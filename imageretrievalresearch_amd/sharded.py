@@ -50,6 +50,15 @@ class _HipOps:
                                      gallery_is_normalized=True)
 
     @staticmethod
+    def local_range(queries, gallery_normalized, threshold, idx_offset, gallery_f16=None, **filt):
+        """``cosine_range`` of ``queries`` against this shard (rows [idx_offset, ...) of the gallery): a ``RangeResult`` with
+        GLOBAL indices.  filt: query_labels, gallery_labels, label_filter, exclude."""
+        if gallery_f16 is not None:
+            filt.pop("gallery_labels", None)
+            return gallery_f16.range_search(queries, threshold, idx_offset=idx_offset, **filt)
+        return _rank.cosine_range(queries, gallery_normalized, threshold, gallery_is_normalized=True, idx_offset=idx_offset, **filt)
+
+    @staticmethod
     def roc_finalize(hist, thr):
         return _rank._roc_finalize(hist, thr)
 
@@ -223,6 +232,89 @@ class ShardedGallery:
         # unpacking, the shard offsets and the merge of world * k candidates per query: one library call
         # (mi355_merge_packed_topk), no torch elementwise kernels on the rank stream
         return self.ops.merge_packed(allp.view(self.world, Q, k, 2), self._offsets_dev, k)
+
+    def range_search(self, queries_local: torch.Tensor, threshold: float, *, query_labels: torch.Tensor | None = None,
+                     label_filter: str | None = None, exclude: torch.Tensor | None = None, max_results: int | None = None):
+        """``cosine_range`` of every rank's queries against the WHOLE gallery: a ``RangeResult`` for all world*Q_local
+        queries, rank-major, the same on every rank and bit for bit that of one gallery holding every row.
+
+        The queries and their filter side (``query_labels`` / ``exclude`` (Q_local,), GLOBAL rows) are all-gathered as in
+        ``search``; each rank searches its shard with its offset as idx_offset; the per-query hit counts are all-gathered,
+        then the payloads padded to the largest shard's hit count.  A query's hits are its shards' hits in rank order (shard
+        offsets ascend with rank: already ascending rows, no merge).  ``max_results`` applies to the whole result."""
+        if label_filter not in (None, "same", "different"):
+            raise MI355Error(f'label_filter must be None, "same" or "different", got {label_filter!r}')
+        if label_filter is not None and self.labels is None:
+            raise MI355Error(f'label_filter="{label_filter}" needs the shard labels: ShardedGallery(..., labels=)')
+        n_local = self.local.shape[0]
+        if self.labels is not None and label_filter is not None and self.labels.shape[0] != n_local:
+            raise MI355Error(f"the shard holds {self.labels.shape[0]} labels for {n_local} rows")
+        if max_results is not None and int(max_results) < 0:
+            raise MI355Error(f"max_results must be >= 0 or None, got {max_results}")
+        threshold = _rank._range_threshold(threshold)
+        q = queries_local.float().contiguous()
+        Ql = q.shape[0]
+        if label_filter is not None and query_labels is None:
+            raise MI355Error(f'label_filter="{label_filter}" needs query_labels')
+        side = torch.full((Ql, 2), -1, dtype=torch.int64, device=self.device)
+        for col, t, name in ((0, query_labels if label_filter is not None else None, "query_labels"), (1, exclude, "exclude")):
+            if t is None:
+                continue
+            if not torch.is_tensor(t) or t.dtype.is_floating_point or t.dtype == torch.bool or t.dim() != 1 or t.shape[0] != Ql:
+                raise MI355Error(f"{name} must be an integer tensor of shape ({Ql},)")
+            side[:, col] = t.to(self.device, torch.int64)
+        dist = torch.distributed
+        if self.world > 1:
+            allq = torch.empty((self.world * Ql, self.dim), dtype=torch.float32, device=self.device)
+            dist.all_gather_into_tensor(allq, q, group=self.group)
+            alls = torch.empty((self.world * Ql, 2), dtype=torch.int64, device=self.device)
+            dist.all_gather_into_tensor(alls, side, group=self.group)
+        else:
+            allq, alls = q, side
+        Q = allq.shape[0]
+        filt = {"label_filter": label_filter}
+        if label_filter is not None:
+            filt.update(query_labels=alls[:, 0].contiguous(), gallery_labels=self.labels)
+        if exclude is not None:
+            filt["exclude"] = alls[:, 1].contiguous()
+        if n_local:
+            local = self.ops.local_range(allq, self.local, threshold, self.offset, gallery_f16=self.gallery_f16, **filt)
+        else:
+            local = _rank.RangeResult(torch.zeros(Q + 1, dtype=torch.int64, device=self.device),
+                                      torch.empty(0, dtype=torch.int64, device=self.device),
+                                      torch.empty(0, dtype=torch.float32, device=self.device))
+        counts = local.offsets[1:] - local.offsets[:-1]                                   # (Q,) hits per query in this shard
+        if self.world == 1:
+            if max_results is not None and local.indices.shape[0] > int(max_results):
+                raise MI355Error(f"the range search has {local.indices.shape[0]} hits, more than max_results={int(max_results)}")
+            return local
+        allc = torch.empty(self.world * Q, dtype=torch.int64, device=self.device)
+        dist.all_gather_into_tensor(allc, counts.contiguous(), group=self.group)
+        allc = allc.view(self.world, Q)
+        shard_nnz = allc.sum(1).cpu().tolist()                                             # the one host sync of the exchange
+        total = sum(shard_nnz)
+        if max_results is not None and total > int(max_results):
+            raise MI355Error(f"the range search has {total} hits, more than max_results={int(max_results)}")
+        pad = max(max(shard_nnz), 1)                                                       # (no empty collective)
+        # payload: (pad, 2) int64 [global row, score bits]
+        payload = torch.zeros((pad, 2), dtype=torch.int64, device=self.device)
+        n = local.indices.shape[0]
+        payload[:n, 0] = local.indices
+        payload[:n, 1] = local.scores.view(torch.int32).to(torch.int64)
+        allp = torch.empty((self.world * pad, 2), dtype=torch.int64, device=self.device)
+        dist.all_gather_into_tensor(allp, payload, group=self.group)
+        # segment (q, r) = shard r's hits of query q, taken in q-major, r-minor order
+        seg_len = allc.t().reshape(-1)                                                     # (Q * world,)
+        starts = torch.zeros((self.world, Q), dtype=torch.int64, device=self.device)
+        starts[:, 1:] = allc[:, :-1].cumsum(1)
+        src0 = (starts + torch.arange(self.world, dtype=torch.int64, device=self.device)[:, None] * pad).t().reshape(-1)
+        dst0 = seg_len.cumsum(0) - seg_len
+        pos = torch.arange(total, dtype=torch.int64, device=self.device)
+        src = (torch.repeat_interleave(src0 - dst0, seg_len, output_size=total) + pos) if total else pos
+        offsets = torch.zeros(Q + 1, dtype=torch.int64, device=self.device)
+        offsets[1:] = allc.sum(0).cumsum(0)
+        out = allp[src]
+        return _rank.RangeResult(offsets, out[:, 0].contiguous(), out[:, 1].to(torch.int32).view(torch.float32).contiguous())
 
     def verification_roc(self, queries_local: torch.Tensor, query_labels_local: torch.Tensor, thresholds=None,
                          exclude: torch.Tensor | None = None):

@@ -175,6 +175,32 @@ int mi355_roc_scores_hist(const void* scores, int scores_f64, int64_t n, const i
  * the denominator is 0), auc [1] float64 = |trapezoid of tpr over fpr| in threshold order (numpy.trapz(tpr, fpr), unrounded). */
 int mi355_roc_finalize(const int64_t* hist, int T, int64_t* counts, int64_t* totals, double* rates, double* auc, void* stream);
 
+/* Cosine range search: every (query q, gallery row j) pair whose score is >= threshold, as a CSR result.
+ * Row j (global index j + idx_offset) is a hit iff its score >= threshold compared in float64 (an fp32 score is compared with
+ * the smallest float f such that (double)f >= threshold, as in the ROC entries), a NaN score never; filter (may be NULL) as in
+ * mi355_rank_topk_filtered.  Scores have the bits mi355_cosine_scores gives the pair on the same path (split bf16, or
+ * MI355_RANK_EXACT_F32=1 / unaligned rows: exact fp32; always the tiled GEMM, also for Q <= 4); _f16: the bits of
+ * mi355_rank_topk_f16's tiled kernel (fp16 gallery, mi355_gallery_to_f16 layout, 16-byte aligned).
+ * Two steps:
+ *   mi355_cosine_range[_f16] runs the search: candidates [2][capacity] 8-byte entries (16 * capacity bytes, 8-byte aligned)
+ *     hold the hits; *nnz (host) = the exact number of hits.  If *nnz > capacity the candidates are incomplete: search again
+ *     with capacity >= *nnz (that call fits).  One host sync per query block (its hit count).  Q >= 0, G >= 0 (Q = 0 or G = 0:
+ *     no hit), dim >= 1, threshold finite; every argument is checked before any HIP call.
+ *     workspace: mi355_range_workspace_bytes / mi355_range_f16_workspace_bytes(Q, G, dim) (no Q x G term).
+ *   mi355_range_compact (after a search with *nnz <= capacity, same candidates, workspace and Q): offsets [Q + 1] int64,
+ *     indices [nnz] int64 (global rows: pass the search's idx_offset), scores [nnz] fp32.  The hits of query q are
+ *     [offsets[q], offsets[q + 1]), rows ascending; the result is the same bit for bit on every run and every query split. */
+size_t mi355_range_workspace_bytes(int64_t Q, int64_t G, int dim);
+int mi355_cosine_range(const float* queries, int64_t Q, const float* gallery, int64_t G, int dim, int gallery_is_normalized,
+                       float eps, double threshold, int64_t idx_offset, const mi355_rank_filter* filter, void* candidates,
+                       int64_t capacity, int64_t* nnz, void* workspace, size_t workspace_bytes, void* stream);
+size_t mi355_range_f16_workspace_bytes(int64_t Q, int64_t G, int dim);
+int mi355_cosine_range_f16(const float* queries, int64_t Q, const void* gallery_f16, int64_t G, int dim, float eps, double threshold,
+                           int64_t idx_offset, const mi355_rank_filter* filter, void* candidates, int64_t capacity, int64_t* nnz,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int mi355_range_compact(const void* candidates, int64_t capacity, int64_t Q, int64_t nnz, int64_t idx_offset, const void* workspace,
+                        size_t workspace_bytes, int64_t* offsets, int64_t* indices, float* scores, void* stream);
+
 /* Indices outside [lo, hi) become (-inf, -1) in val / idx [n] (the sharded filtered search: slots no shard filled). */
 int mi355_clear_pads(float* val, int64_t* idx, int64_t n, int64_t lo, int64_t hi, void* stream);
 
