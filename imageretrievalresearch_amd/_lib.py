@@ -28,6 +28,18 @@ class GemmExArgs(C.Structure):
                 ("ln_stats", vp), ("ln_colsum", vp)]
 
 
+class DwconvExArgs(C.Structure):
+    """mi355_dwconv_ex_args (include/mi355_retrieval.h), the operand block of the developer entry mi355_dwconv_se_ex."""
+    _fields_ = [("in_", vp), ("w", vp), ("bias", vp), ("out", vp),
+                ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int), ("k", C.c_int), ("stride", C.c_int),
+                ("act", C.c_int), ("choice", C.c_int),
+                ("se_w1", vp), ("se_b1", vp), ("se_w2t", vp), ("se_b2", vp), ("rd", C.c_int), ("act1", C.c_int),
+                ("gate", vp), ("squeeze", vp)]
+
+
+DW_CHOICE_AUTO, DW_CHOICE_DIRECT, DW_CHOICE_TILED, DW_CHOICE_MFMA = 0, 1, 2, 3
+
+
 class RankFilter(C.Structure):
     """mi355_rank_filter (include/mi355_retrieval.h): the eligibility filter of mi355_rank_topk_filtered / _f16_filtered."""
     _fields_ = [("query_labels", vp), ("gallery_labels", vp), ("label_mode", C.c_int), ("exclude", vp)]
@@ -117,6 +129,7 @@ PROTOTYPES = {
     "mi355_pool_linear": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp]),
     "mi355_gemm_bf16": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "mi355_gemm_bf16_ex": (C.c_int, [vp, C.POINTER(C.c_int), vp]),
+    "mi355_dwconv_se_ex": (C.c_int, [vp, C.POINTER(C.c_int), vp]),
     "mi355_window_attention": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "mi355_square_pad_normalize": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, vp]),
     "mi355_conv_input_silu": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),

@@ -3,6 +3,7 @@
 // Activations are NHWC bf16 (channels multiple of 8 -> every access is a 16-byte vector of 8 channels);
 // all arithmetic is fp32 on the VALU: these layers are byte-bound, not FLOP-bound.
 #include "ops.h"
+#include "../../include/mi355_retrieval.h"
 
 #include <stdlib.h>
 #include <type_traits>
@@ -733,26 +734,47 @@ static void launch_dw3_lds(const bf16_t* in, const bf16_t* w, const float* bias,
                        nb, H, W, act, magic, tpw);
 }
 
-int launch_dwconv(const bf16_t* in, const bf16_t* w, const float* bias, bf16_t* out, float* pool_partial, int B, int H,
-                  int W, int C, int k, int stride, int act, int* pool_nblk, hipStream_t st) {
+bool dw_tiled_supported(int H, int W, int C, int k, int stride) {
+    int TH, CGC, PX;
+    size_t lds;
+    return dw_tiled_plan(H, W, C, k, stride, &TH, &CGC, &PX, &lds);
+}
+
+bool dw3_lds_supported(int H, int W, int C, int k, int stride) {
+    return k == 3 && stride == 1 && C <= 48 && W % 2 == 0 && W >= 4 && (long)H * W * C * 2 < (1L << 30);
+}
+
+void dw_env_choice(bool* try_tiled, bool* try_mfma) {
+    // measured slower than the direct kernel on every EfficientNet layer (0.27 -> 0.32 ms at 56x56 C192): opt-in only
+    static const int use_tiled = getenv("MI355_DW_TILED") ? atoi(getenv("MI355_DW_TILED")) : 0;
+    // MI355_DW_MFMA=0 keeps the direct kernel for the narrow 3x3 stride-1 layers
+    static const int use_mfma = getenv("MI355_DW_MFMA") ? atoi(getenv("MI355_DW_MFMA")) : 1;
+    *try_tiled = use_tiled != 0;
+    *try_mfma = use_mfma != 0;
+}
+
+int launch_dwconv_sel(const bf16_t* in, const bf16_t* w, const float* bias, bf16_t* out, float* pool_partial, int B, int H,
+                      int W, int C, int k, int stride, int act, bool try_tiled, bool try_mfma, int* pool_nblk, int* path,
+                      hipStream_t st) {
     MI355_REQUIRE(C % 8 == 0, "dwconv: C=%d must be a multiple of 8", C);
     MI355_REQUIRE((k == 3 || k == 5) && (stride == 1 || stride == 2), "dwconv: unsupported k=%d stride=%d", k, stride);
     const int pad = k / 2;
     const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
-    // measured slower than the direct kernel on every EfficientNet layer (0.27 -> 0.32 ms at 56x56 C192): opt-in only
-    static const int use_tiled = getenv("MI355_DW_TILED") ? atoi(getenv("MI355_DW_TILED")) : 0;
+    auto ran = [path](int p, int e) {
+        if (path && e == OK) *path = p;
+        return e;
+    };
     int TH, CGC, PX;
     size_t lds;
-    if (use_tiled && dw_tiled_plan(H, W, C, k, stride, &TH, &CGC, &PX, &lds)) {
-        if (k == 3) return PX == 7 ? launch_dw_tiled<3, 7>(in, w, bias, out, pool_partial, B, H, W, C, TH, CGC, lds, act, pool_nblk, st)
-                                   : launch_dw_tiled<3, 4>(in, w, bias, out, pool_partial, B, H, W, C, TH, CGC, lds, act, pool_nblk, st);
-        return PX == 7 ? launch_dw_tiled<5, 7>(in, w, bias, out, pool_partial, B, H, W, C, TH, CGC, lds, act, pool_nblk, st)
-                       : launch_dw_tiled<5, 4>(in, w, bias, out, pool_partial, B, H, W, C, TH, CGC, lds, act, pool_nblk, st);
+    if (try_tiled && dw_tiled_plan(H, W, C, k, stride, &TH, &CGC, &PX, &lds)) {
+        const int p = MI355_DW_PATH(MI355_DW_PATH_TILED, k, 1, PX, 0);
+        if (k == 3) return ran(p, PX == 7 ? launch_dw_tiled<3, 7>(in, w, bias, out, pool_partial, B, H, W, C, TH, CGC, lds, act, pool_nblk, st)
+                                          : launch_dw_tiled<3, 4>(in, w, bias, out, pool_partial, B, H, W, C, TH, CGC, lds, act, pool_nblk, st));
+        return ran(p, PX == 7 ? launch_dw_tiled<5, 7>(in, w, bias, out, pool_partial, B, H, W, C, TH, CGC, lds, act, pool_nblk, st)
+                              : launch_dw_tiled<5, 4>(in, w, bias, out, pool_partial, B, H, W, C, TH, CGC, lds, act, pool_nblk, st));
     }
-    // narrow 3x3 stride-1 layers (C <= 48): matrix-pipe kernel with wave-private LDS staging (C40 @112x112: 0.218 -> 0.126 ms);
-    // MI355_DW_MFMA=0 keeps the direct kernel
-    static const int use_mfma = getenv("MI355_DW_MFMA") ? atoi(getenv("MI355_DW_MFMA")) : 1;
-    if (use_mfma && k == 3 && stride == 1 && C <= 48 && W % 2 == 0 && W >= 4 && (long)H * W * C * 2 < (1L << 30)) {
+    // narrow 3x3 stride-1 layers (C <= 48): matrix-pipe kernel with wave-private LDS staging (C40 @112x112: 0.218 -> 0.126 ms)
+    if (try_mfma && dw3_lds_supported(H, W, C, k, stride)) {
         const int ntiles = cdiv((long)H * W, 32);
         int nb = std::min(std::min(dw_pool_blocks(Ho, Wo, C), 14), ntiles);      // <= the squeeze-partial slot the planner sized
         const int tpw = cdiv(ntiles, nb);
@@ -768,7 +790,7 @@ int launch_dwconv(const bf16_t* in, const bf16_t* w, const float* bias, bf16_t* 
             default: launch_dw3_lds<6>(in, w, bias, out, pool_partial, B, nb, H, W, act, magic, tpw, st); break;   // (rexnet_150's C48 @112x112)
         }
         MI355_LAUNCH_CHECK();
-        return OK;
+        return ran(MI355_DW_PATH(MI355_DW_PATH_LDS3, 3, 1, C / 8, 0), OK);
     }
     if (pool_nblk) *pool_nblk = dw_pool_blocks(Ho, Wo, C);
     const int nblk = dw_pool_blocks(Ho, Wo, C);
@@ -781,7 +803,14 @@ int launch_dwconv(const bf16_t* in, const bf16_t* w, const float* bias, bf16_t* 
     else DW_LAUNCH(5, 2);
 #undef DW_LAUNCH
     MI355_LAUNCH_CHECK();
-    return OK;
+    return ran(MI355_DW_PATH(MI355_DW_PATH_DIRECT, k, stride, DW_PX, 0), OK);
+}
+
+int launch_dwconv(const bf16_t* in, const bf16_t* w, const float* bias, bf16_t* out, float* pool_partial, int B, int H,
+                  int W, int C, int k, int stride, int act, int* pool_nblk, hipStream_t st) {
+    bool try_tiled, try_mfma;
+    dw_env_choice(&try_tiled, &try_mfma);
+    return launch_dwconv_sel(in, w, bias, out, pool_partial, B, H, W, C, k, stride, act, try_tiled, try_mfma, pool_nblk, nullptr, st);
 }
 
 // =====================================================================================
@@ -791,8 +820,6 @@ int launch_dwconv(const bf16_t* in, const bf16_t* w, const float* bias, bf16_t* 
 // All fp32; summation orders are fixed.
 // =====================================================================================
 constexpr int SE_THREADS = 1024;
-constexpr int SE_MAX_C = 4096;
-constexpr int SE_MAX_RD = 512;
 __global__ __launch_bounds__(SE_THREADS) void k_se(const float* __restrict__ pool_partial, int nblk, float inv_hw,
                                                    const float* __restrict__ w1, const float* __restrict__ b1,
                                                    const float* __restrict__ w2t, const float* __restrict__ b2,
@@ -918,13 +945,15 @@ __global__ __launch_bounds__(SE_THREADS) void k_se_small(const float* __restrict
 }
 
 int launch_se(const float* pool_partial, int nblk, float inv_hw, const float* w1, const float* b1, const float* w2t,
-              const float* b2, float* gate, int B, int C, int rd, int act1, hipStream_t st) {
+              const float* b2, float* gate, int B, int C, int rd, int act1, hipStream_t st, int* path) {
     MI355_REQUIRE(C <= SE_MAX_C && rd <= SE_MAX_RD, "se: C=%d rd=%d exceed limits", C, rd);
-    if (rd <= 16 && C <= SE_THREADS)
+    const bool small = rd <= 16 && C <= SE_THREADS;
+    if (small)
         hipLaunchKernelGGL(k_se_small, dim3(B), dim3(SE_THREADS), 0, st, pool_partial, nblk, inv_hw, w1, b1, w2t, b2, gate, C, rd, act1);
     else
         hipLaunchKernelGGL(k_se, dim3(B), dim3(SE_THREADS), 0, st, pool_partial, nblk, inv_hw, w1, b1, w2t, b2, gate, C, rd, act1);
     MI355_LAUNCH_CHECK();
+    if (path) *path = small ? MI355_DW_PATH_SE_SMALL : MI355_DW_PATH_SE_FULL;
     return OK;
 }
 

@@ -1155,6 +1155,73 @@ int mi355_gemm_bf16_ex(const mi355_gemm_ex_args* x, int* path, void* stream) {
     return launch_gemm_bf16(a, (hipStream_t)stream, path);
 }
 
+int mi355_dwconv_se_ex(const mi355_dwconv_ex_args* x, int* path, void* stream) {
+    if (path) *path = 0;
+    MI355_REQUIRE(x, "dwconv_se_ex: null argument block");
+    MI355_REQUIRE(x->in && x->w && x->bias && x->out, "dwconv_se_ex: null pointer");
+    MI355_REQUIRE(x->B >= 1 && x->H >= 1 && x->W >= 1 && x->H <= 16384 && x->W <= 16384 && x->C >= 8,
+                  "dwconv_se_ex: bad shape B=%d H=%d W=%d C=%d", x->B, x->H, x->W, x->C);
+    MI355_REQUIRE(x->C % 8 == 0, "dwconv_se_ex: C=%d must be a multiple of 8", x->C);
+    MI355_REQUIRE((size_t)x->B * x->H * x->W * x->C < ((size_t)1 << 36), "dwconv_se_ex: tensor too large");
+    MI355_REQUIRE((x->k == 3 || x->k == 5) && (x->stride == 1 || x->stride == 2), "dwconv_se_ex: unsupported k=%d stride=%d",
+                  x->k, x->stride);
+    MI355_REQUIRE(x->act >= ACT_NONE && x->act <= ACT_SIGMOID, "dwconv_se_ex: unknown activation %d", x->act);
+    MI355_REQUIRE(x->choice >= MI355_DW_CHOICE_AUTO && x->choice <= MI355_DW_CHOICE_MFMA, "dwconv_se_ex: unknown choice %d",
+                  x->choice);
+    MI355_REQUIRE(x->choice != MI355_DW_CHOICE_TILED || dw_tiled_supported(x->H, x->W, x->C, x->k, x->stride),
+                  "dwconv_se_ex: choice tiled does not take H=%d W=%d C=%d k=%d stride=%d", x->H, x->W, x->C, x->k, x->stride);
+    MI355_REQUIRE(x->choice != MI355_DW_CHOICE_MFMA || dw3_lds_supported(x->H, x->W, x->C, x->k, x->stride),
+                  "dwconv_se_ex: choice mfma does not take H=%d W=%d C=%d k=%d stride=%d", x->H, x->W, x->C, x->k, x->stride);
+    const bool se = x->se_w1 != nullptr;
+    MI355_REQUIRE(!x->se_b1 == !se && !x->se_w2t == !se && !x->se_b2 == !se && !x->gate == !se,
+                  "dwconv_se_ex: the SE weights, biases and gate go together");
+    MI355_REQUIRE(!se || (x->rd >= 1 && x->rd <= SE_MAX_RD && x->C <= SE_MAX_C),
+                  "dwconv_se_ex: SE needs 1 <= rd <= %d and C <= %d (rd=%d C=%d)", SE_MAX_RD, SE_MAX_C, x->rd, x->C);
+    MI355_REQUIRE(!se || (x->act1 >= ACT_NONE && x->act1 <= ACT_SIGMOID), "dwconv_se_ex: unknown SE activation %d", x->act1);
+    for (const void* p : {x->in, x->w, (const void*)x->bias, (const void*)x->out})
+        MI355_REQUIRE((uintptr_t)p % 16 == 0, "dwconv_se_ex: in, w, bias and out must be 16-byte aligned");
+    for (const void* p : {(const void*)x->se_w1, (const void*)x->se_b1, (const void*)x->se_w2t, (const void*)x->se_b2,
+                          (const void*)x->gate, (const void*)x->squeeze})
+        MI355_REQUIRE((uintptr_t)p % 4 == 0, "dwconv_se_ex: SE and squeeze pointers must be 4-byte aligned");
+    const int Ho = (x->H - 1) / x->stride + 1, Wo = (x->W - 1) / x->stride + 1;
+    bool try_tiled = x->choice == MI355_DW_CHOICE_TILED, try_mfma = x->choice == MI355_DW_CHOICE_MFMA;
+    if (x->choice == MI355_DW_CHOICE_AUTO) dw_env_choice(&try_tiled, &try_mfma);
+    // squeeze partials: at most dw_pool_blocks(...) per image (direct / matrix-pipe kernels) or one per row band (<= H)
+    const size_t nblk_max = (size_t)std::max(dw_pool_blocks(Ho, Wo, x->C), x->H);
+    float* partial = nullptr;
+    MI355_CHECK_HIP(hipMalloc(&partial, nblk_max * x->B * x->C * sizeof(float)));
+    const hipStream_t st = (hipStream_t)stream;
+    int nblk = 0, dw_path = 0, se_path = 0;
+    int e = launch_dwconv_sel((const bf16_t*)x->in, (const bf16_t*)x->w, x->bias, (bf16_t*)x->out, partial, x->B, x->H, x->W,
+                              x->C, x->k, x->stride, x->act, try_tiled, try_mfma, &nblk, &dw_path, st);
+    if (e == OK && se)
+        e = launch_se(partial, nblk, 1.0f / (float)(Ho * Wo), x->se_w1, x->se_b1, x->se_w2t, x->se_b2, x->gate, x->B, x->C, x->rd,
+                      x->act1, st, &se_path);
+    hipError_t he = hipStreamSynchronize(st);
+    std::vector<float> part, sq;
+    if (e == OK && he == hipSuccess && x->squeeze) {
+        // k_se's squeeze: the partials of one (image, channel) added in partial order, then one multiply
+        const size_t n = (size_t)x->B * nblk * x->C;
+        part.resize(n);
+        sq.resize((size_t)x->B * x->C);
+        he = hipMemcpy(part.data(), partial, n * sizeof(float), hipMemcpyDeviceToHost);
+        const float inv_hw = 1.0f / (float)(Ho * Wo);
+        for (int b = 0; b < x->B; ++b)
+            for (int c = 0; c < x->C; ++c) {
+                float a = 0.f;
+                for (int k = 0; k < nblk; ++k) a += part[((size_t)b * nblk + k) * x->C + c];
+                sq[(size_t)b * x->C + c] = a * inv_hw;
+            }
+        if (he == hipSuccess) he = hipMemcpy(x->squeeze, sq.data(), sq.size() * sizeof(float), hipMemcpyHostToDevice);
+    }
+    const hipError_t freed = hipFree(partial);
+    if (e != OK) return e;
+    MI355_CHECK_HIP(he);
+    MI355_CHECK_HIP(freed);
+    if (path) *path = dw_path | se_path << 24;
+    return OK;
+}
+
 int mi355_pool_linear(const float* fm, int B, int C, int HW, const float* weight, const float* bias, int N, float* out,
                       float* pooled_out, void* stream) {
     MI355_REQUIRE(fm && (out || pooled_out), "pool_linear: null pointer");

@@ -131,13 +131,25 @@ int resize_batch(const unsigned char* pixels, int64_t pixels_bytes, const int64_
 // (the SE squeeze), reduced in a fixed order.
 int dw_pool_blocks(int Ho, int Wo, int C);
 // pool_nblk (out): squeeze partials per image this launch produced (pool_partial is [B][nblk][C]).
+// The kernel is chosen as launch_dwconv_sel(try_tiled, try_mfma) with the process-wide MI355_DW_TILED / MI355_DW_MFMA choice.
 int launch_dwconv(const bf16_t* in, const bf16_t* w, const float* bias, bf16_t* out, float* pool_partial, int B,
                   int H, int W, int C, int k, int stride, int act, int* pool_nblk, hipStream_t st);
+// The same dispatch with the choice explicit: the row-band LDS kernel when try_tiled and the shape has a plan
+// (dw_tiled_supported), else the 3x3 matrix-pipe kernel when try_mfma and dw3_lds_supported, else the direct kernel.
+// path (may be null): MI355_DW_PATH(...) of the kernel that ran (include/mi355_retrieval.h).
+int launch_dwconv_sel(const bf16_t* in, const bf16_t* w, const float* bias, bf16_t* out, float* pool_partial, int B,
+                      int H, int W, int C, int k, int stride, int act, bool try_tiled, bool try_mfma, int* pool_nblk,
+                      int* path, hipStream_t st);
+void dw_env_choice(bool* try_tiled, bool* try_mfma);   // MI355_DW_TILED (default 0) / MI355_DW_MFMA (default 1), read once
+bool dw_tiled_supported(int H, int W, int C, int k, int stride);
+bool dw3_lds_supported(int H, int W, int C, int k, int stride);
 
+constexpr int SE_MAX_C = 4096, SE_MAX_RD = 512;   // launch_se's limits (LDS arrays of the SE kernels)
 // Squeeze-excite gate: s = (sum over nblk partials) / hw ; r = act1(W1 s + b1) ; gate = sigmoid(W2 r + b2).
 // W1 [rd][C] fp32, W2T [rd][C] fp32 (transposed).  gate out [B][C] fp32.
+// path (may be null): MI355_DW_PATH_SE_SMALL (k_se_small: rd <= 16, C <= 1024) or MI355_DW_PATH_SE_FULL (k_se).
 int launch_se(const float* pool_partial, int nblk, float inv_hw, const float* w1, const float* b1, const float* w2,
-              const float* b2, float* gate, int B, int C, int rd, int act1, hipStream_t st);
+              const float* b2, float* gate, int B, int C, int rd, int act1, hipStream_t st, int* path = nullptr);
 
 // Global average pool of NHWC bf16 -> pooled fp32 [B][C] (+ optional bf16 copy for the classifier GEMM).
 int launch_gap(const bf16_t* in, float* pooled, bf16_t* pooled_bf16, int B, int HW, int C, hipStream_t st);

@@ -458,6 +458,49 @@ enum {
 
 int mi355_gemm_bf16_ex(const mi355_gemm_ex_args* args, int* path, void* stream);
 
+/* Developer entry: one depthwise conv of the convolutional backbones with its SE squeeze partials, then (when SE weights are
+ * given) the SE gate on those partials, through the model's launchers.
+ *   out[b][oy][ox][c] = bf16( act( sum_{ky,kx} in[b][oy*stride - k/2 + ky][ox*stride - k/2 + kx][c] w[ky*k + kx][c] + bias[c] ) )
+ *                       (zero padding), Ho = (H - 1) / stride + 1, Wo likewise
+ *   s[b][c] = (sum over oy, ox of the un-rounded activated output) / (Ho * Wo)
+ *   gate[b][c] = sigmoid( sum_j se_w2t[j][c] act1( sum_c' se_w1[j][c'] s[b][c'] + se_b1[j] ) + se_b2[c] )
+ * in [B][H][W][C] bf16 NHWC, w [k*k][C] bf16 (pack_dw's layout), bias [C] fp32, out [B][Ho][Wo][C] bf16: 16-byte aligned
+ * device pointers, C a multiple of 8.  SE (optional, all five pointers or none): se_w1 / se_w2t [rd][C] fp32 holding bf16
+ * values, se_b1 [rd] / se_b2 [C] fp32, gate [B][C] fp32.  k 3 or 5, stride 1 or 2, act / act1 as for mi355_gemm_bf16.
+ * choice: MI355_DW_CHOICE_AUTO takes the model's decision (MI355_DW_TILED / MI355_DW_MFMA, read once per process); DIRECT,
+ * TILED and MFMA force one kernel and are rejected for shapes that kernel does not take.  path (host, may be NULL) receives
+ * MI355_DW_PATH(kind, k, stride, arg, se) of the kernels that ran.  Every argument is checked before any HIP call.
+ * squeeze (optional, device [B][C] fp32) receives s computed ON THE HOST from the depthwise kernel's squeeze partials (copied
+ * back, summed in the SE kernels' fixed order, times 1 / (Ho * Wo)); it is not read back from k_se / k_se_small, so it checks
+ * the partials, and the gate checks what the SE kernels make of them.  Synchronises the stream (the squeeze partials are a per-call scratch buffer). */
+typedef struct mi355_dwconv_ex_args {
+    const void* in; const void* w; const float* bias; void* out;
+    int B, H, W, C, k, stride, act, choice;
+    const float* se_w1; const float* se_b1; const float* se_w2t; const float* se_b2;
+    int rd, act1;
+    float* gate;
+    float* squeeze;
+} mi355_dwconv_ex_args;
+
+enum { MI355_DW_CHOICE_AUTO = 0, MI355_DW_CHOICE_DIRECT = 1, MI355_DW_CHOICE_TILED = 2, MI355_DW_CHOICE_MFMA = 3 };
+
+enum {
+    MI355_DW_PATH_DIRECT = 1,       /* k_dwconv<KS, S>, arg = pixels per thread (DW_PX) */
+    MI355_DW_PATH_LDS3 = 2,         /* k_dw3_lds<NU>: 3x3 stride 1, C <= 48, even W; arg = NU = C / 8 */
+    MI355_DW_PATH_TILED = 3,        /* k_dw_tiled<KS, PX>: stride 1 (opt-in MI355_DW_TILED); arg = PX */
+    /* SE kernel, in MI355_DW_PATH_SE(p); 0 when no SE ran */
+    MI355_DW_PATH_SE_SMALL = 1,     /* k_se_small: rd <= 16, C <= 1024 */
+    MI355_DW_PATH_SE_FULL = 2       /* k_se */
+};
+#define MI355_DW_PATH(kind, ks, s, arg, se) ((kind) | (ks) << 8 | (s) << 12 | (arg) << 16 | (se) << 24)
+#define MI355_DW_PATH_KIND(p) ((p) & 0xff)
+#define MI355_DW_PATH_KS(p) (((p) >> 8) & 0xf)
+#define MI355_DW_PATH_S(p) (((p) >> 12) & 0xf)
+#define MI355_DW_PATH_ARG(p) (((p) >> 16) & 0xff)
+#define MI355_DW_PATH_SE(p) (((p) >> 24) & 0xff)
+
+int mi355_dwconv_se_ex(const mi355_dwconv_ex_args* args, int* path, void* stream);
+
 /* Developer entry: one Swin window-attention layer (window 7, head_dim 32) through the model's kernel.
  *   qkv [B][res*res][3C] bf16 (channel = which * C + head * 32 + d, tokens in image order), out [B][res*res][C] bf16,
  *   bias_table [169][heads] fp32 (timm relative_position_bias_table), packed to the kernel's dense layout by the model's

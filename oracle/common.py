@@ -30,9 +30,16 @@ class Rounder:
         return x.to(torch.bfloat16).to(torch.float32) if self.sim else x
 
 
+def bn_scale(bn: dict, eps: float) -> torch.Tensor:
+    """g / sqrt(v + eps) in fp32 with a correctly rounded square root, as the packer's sqrtf.  (torch.sqrt of an fp32
+    tensor on CPU can be one ulp off; the float64 root rounded to fp32 is the correctly rounded fp32 root.)"""
+    v = bn["running_var"] + eps
+    return bn["weight"] / torch.sqrt(v.double()).to(v.dtype)
+
+
 def fold_bn(w: torch.Tensor, bn: dict, eps: float):
     """conv weight (O, ...) + eval-mode BN -> (w * g/sqrt(v+eps), b - m*g/sqrt(v+eps))."""
-    scale = bn["weight"] / torch.sqrt(bn["running_var"] + eps)
+    scale = bn_scale(bn, eps)
     shape = [-1] + [1] * (w.dim() - 1)
     return w * scale.reshape(shape), bn["bias"] - bn["running_mean"] * scale
 

@@ -18,7 +18,7 @@ from math import ceil
 import torch
 import torch.nn.functional as F
 
-from .common import Rounder, SeededInit, bn_of, fold_bn, make_divisible
+from .common import Rounder, SeededInit, bn_of, bn_scale, fold_bn, make_divisible
 
 BN_EPS = 1e-5
 
@@ -102,7 +102,7 @@ def forward_features(sd, x, width_mult, sim_bf16=False, taps=None):
             bn = bn_of(sd, f"{p}.se.bn")
             if sim_bf16:
                 # the HIP path folds the SE BN into fc1 and stores both FC matrices rounded to bf16 (fp32 math)
-                scale = bn["weight"] / torch.sqrt(bn["running_var"] + BN_EPS)
+                scale = bn_scale(bn, BN_EPS)
                 w1 = rb(sd[f"{p}.se.fc1.weight"] * scale.reshape(-1, 1, 1, 1))
                 b1 = sd[f"{p}.se.fc1.bias"] * scale + (bn["bias"] - bn["running_mean"] * scale)
                 r = F.relu(F.conv2d(s, w1, b1))

@@ -1,4 +1,4 @@
-"""The developer entries mi355_window_attention and mi355_gemm_bf16_ex, the parts that need no GPU: the C-ABI symbols and
+"""The developer entries mi355_window_attention, mi355_gemm_bf16_ex and mi355_dwconv_se_ex, the parts that need no GPU: the C-ABI symbols and
 every argument check (rejected before any HIP call, with a message)."""
 import ctypes
 
@@ -7,7 +7,7 @@ import pytest
 from helpers import header_symbols
 from imageretrievalresearch_amd import _lib
 
-NEW = ["mi355_window_attention", "mi355_gemm_bf16_ex"]
+NEW = ["mi355_window_attention", "mi355_gemm_bf16_ex", "mi355_dwconv_se_ex"]
 P = 1 << 20          # a 16-byte aligned stand-in pointer: nothing is dereferenced when a check fails
 
 
@@ -101,3 +101,72 @@ def test_ex_args_layout_matches_the_header():
     G = _lib.GemmExArgs
     assert ctypes.sizeof(G) == 152
     assert (G.out.offset, G.M_sel.offset, G.ln_colsum.offset) == (80, 112, 144)
+
+
+def _dw_ok():
+    """A valid operand block (B = 3, 14x14, C = 40, 3x3 stride 1, SE rd = 10) with stand-in pointers."""
+    return dict(in_=P, w=P, bias=P, out=P, B=3, H=14, W=14, C=40, k=3, stride=1, act=1, choice=0,
+                se_w1=P, se_b1=P, se_w2t=P, se_b2=P, rd=10, act1=1, gate=P)
+
+
+_NO_SE = dict(se_w1=None, se_b1=None, se_w2t=None, se_b2=None, gate=None, rd=0)
+
+
+@pytest.mark.parametrize("change,msg", [
+    (dict(in_=None), b"null"),
+    (dict(w=None), b"null"),
+    (dict(bias=None), b"null"),
+    (dict(out=None), b"null"),
+    (dict(B=0), b"bad shape"),
+    (dict(H=0), b"bad shape"),
+    (dict(W=-1), b"bad shape"),
+    (dict(W=20000), b"bad shape"),
+    (dict(C=0), b"bad shape"),
+    (dict(C=36), b"multiple of 8"),
+    (dict(B=4096, H=4096, W=4096, C=64), b"too large"),
+    (dict(k=7), b"unsupported k"),
+    (dict(k=1), b"unsupported k"),
+    (dict(stride=3), b"unsupported k"),
+    (dict(act=6), b"activation"),
+    (dict(act=-1), b"activation"),
+    (dict(choice=4), b"choice"),
+    (dict(choice=-1), b"choice"),
+    (dict(choice=2, stride=2), b"tiled does not take"),        # the row-band kernel is stride 1 only
+    (dict(choice=2, W=12), b"tiled does not take"),            # and W >= 14
+    (dict(choice=3, k=5), b"mfma does not take"),              # the matrix-pipe kernel is 3x3 stride 1 ...
+    (dict(choice=3, W=13), b"mfma does not take"),             # ... even W ...
+    (dict(choice=3, C=56), b"mfma does not take"),             # ... C <= 48
+    (dict(choice=3, W=2), b"mfma does not take"),
+    (dict(se_w1=None), b"go together"),
+    (dict(se_b2=None), b"go together"),
+    (dict(gate=None), b"go together"),
+    (dict(_NO_SE, gate=P), b"go together"),
+    (dict(rd=0), b"rd"),
+    (dict(rd=513), b"rd"),
+    (dict(C=4104), b"C <="),
+    (dict(act1=7), b"SE activation"),
+    (dict(in_=P + 8), b"16-byte aligned"),
+    (dict(bias=P + 4), b"16-byte aligned"),
+    (dict(out=P + 2), b"16-byte aligned"),
+    (dict(gate=P + 2), b"4-byte aligned"),
+    (dict(squeeze=P + 1), b"4-byte aligned"),
+])
+def test_dwconv_se_ex_argument_errors(change, msg):
+    a = _dw_ok()
+    a.update(change)
+    x = _lib.DwconvExArgs(**a)
+    path = ctypes.c_int(-1)
+    assert _lib.lib().mi355_dwconv_se_ex(ctypes.byref(x), ctypes.byref(path), None) != 0
+    assert msg in _err(), _err()
+    assert path.value == 0                                # a rejected call reports no kernel
+
+
+def test_dwconv_se_ex_null_block():
+    assert _lib.lib().mi355_dwconv_se_ex(None, None, None) != 0
+    assert b"null" in _err()
+
+
+def test_dwconv_ex_args_layout_matches_the_header():
+    D = _lib.DwconvExArgs
+    assert ctypes.sizeof(D) == 120
+    assert (D.B.offset, D.choice.offset, D.se_w1.offset, D.rd.offset, D.gate.offset, D.squeeze.offset) == (32, 60, 64, 96, 104, 112)
