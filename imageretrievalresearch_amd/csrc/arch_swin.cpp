@@ -1,12 +1,16 @@
-// swin_base_patch4_window7_224 (timm 0.4.12 swin_transformer.py): tensor table in state-dict order + plan.
+// Swin transformers (timm swin_transformer.py): tensor table in state-dict order + plan.
+//   swin_base_patch4_window7_224 (timm 0.4.12) and swin_s3_base_224 (timm 0.6.x, same key layout; per-stage windows).
 // Replaces timm.create_model(...) at train/train_vit_triplet.py:354 (with model.head = Identity() at :357).
 // Tokens are [B][L][C] bf16; the residual stream is updated in place by the proj / fc2 GEMM epilogues.
 #include "model.h"
 
+#include <algorithm>
+
 namespace mi355 {
 
-int build_swin_base(ModelDef& m) {
-    const int embed = 128, depths[4] = {2, 2, 18, 2}, heads[4] = {4, 8, 16, 32}, ws = 7, grid0 = 56;
+// window[s] is the configured window of stage s; timm uses ws = min(res, window[s]) and no shift where res <= window[s].
+static int build_swin(ModelDef& m, int embed, const int depths[4], const int heads[4], const int window[4]) {
+    const int grid0 = 56;
     m.feat_dim = m.feat_dim_pad = embed * 8;
     m.pools_in_features = true;
     m.final_slot = SLOT_X0;
@@ -21,10 +25,10 @@ int build_swin_base(ModelDef& m) {
         m.ops.push_back(op);
     }
     for (int s = 0; s < 4; ++s) {
-        const int dim = embed << s, res = grid0 >> s, nh = heads[s];
+        const int dim = embed << s, res = grid0 >> s, nh = heads[s], ws = std::min(res, window[s]);
         for (int b = 0; b < depths[s]; ++b) {
             const std::string p = "layers." + std::to_string(s) + ".blocks." + std::to_string(b);
-            const int shift = (b % 2 == 0 || res <= ws) ? 0 : ws / 2;
+            const int shift = (b % 2 == 0 || res <= window[s]) ? 0 : ws / 2;
             const int nW = (res / ws) * (res / ws);
             if (shift > 0) m.add(p + ".attn_mask", {nW, ws * ws, ws * ws}, 1);
             m.add_ln(p + ".norm1", dim);
@@ -90,6 +94,16 @@ int build_swin_base(ModelDef& m) {
         m.classifier = c;
     }
     return OK;
+}
+
+int build_swin_base(ModelDef& m) {
+    const int depths[4] = {2, 2, 18, 2}, heads[4] = {4, 8, 16, 32}, window[4] = {7, 7, 7, 7};
+    return build_swin(m, 128, depths, heads, window);
+}
+
+int build_swin_s3_base(ModelDef& m) {
+    const int depths[4] = {2, 2, 30, 2}, heads[4] = {3, 6, 12, 24}, window[4] = {7, 7, 14, 7};
+    return build_swin(m, 96, depths, heads, window);
 }
 
 }  // namespace mi355

@@ -107,6 +107,7 @@ static inline int pad8(int c) { return (c + 7) & ~7; }
 // architecture builders (arch_*.cpp); return 0 or set_error + nonzero
 int build_efficientnet_b3(ModelDef& m);
 int build_rexnet(ModelDef& m, double width_mult);
-int build_swin_base(ModelDef& m);
+int build_swin_base(ModelDef& m);      // swin_base_patch4_window7_224
+int build_swin_s3_base(ModelDef& m);   // swin_s3_base_224
 
 }  // namespace mi355

@@ -681,9 +681,10 @@ int mi355_model_create(const char* name, int num_classes, mi355_model_t* out) {
     else if (n == "rexnet_150") e = build_rexnet(m->def, 1.5);
     else if (n == "rexnet_200") e = build_rexnet(m->def, 2.0);
     else if (n == "swin_base_patch4_window7_224") e = build_swin_base(m->def);
+    else if (n == "swin_s3_base_224") e = build_swin_s3_base(m->def);
     else {
         // same wording as the reference's guard (train/train.py:400)
-        set_error("Unknown model name '%s'. Known: efficientnet_b3a, rexnet_100/130/150/200, swin_base_patch4_window7_224", name);
+        set_error("Unknown model name '%s'. Known: efficientnet_b3a, rexnet_100/130/150/200, swin_base_patch4_window7_224, swin_s3_base_224", name);
         e = ERR_ARG;
     }
     if (e) { delete m; return e; }
@@ -1054,7 +1055,7 @@ int mi355_model_traffic_kinds(mi355_model_t m, int B, int H, int W, double* byte
                 if (op.kind == OP_PATCH_EMBED) bytes_by_kind[kd] += (double)B * (3.0 * H * W * 4 + t * op.cout_real * 2);
                 else if (op.kind == OP_TOKEN_MEAN) bytes_by_kind[kd] += B * t * op.cin_real * 2;
                 else bytes_by_kind[kd] += B * t * (op.cin_real + op.cout_real) * 2;
-                if (op.kind == OP_WINATTN) macs_by_kind[kd] += B * t * 49.0 * op.cout_real * 2;   // QK^T + PV
+                if (op.kind == OP_WINATTN) macs_by_kind[kd] += B * t * (double)(op.window * op.window) * op.cout_real * 2;   // QK^T + PV
                 if (op.kind == OP_PATCH_EMBED) macs_by_kind[kd] += B * t * 48.0 * op.cout_real;
                 break;
             }

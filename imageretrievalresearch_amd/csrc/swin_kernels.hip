@@ -64,6 +64,45 @@ struct PatchU8RaggedArgs : PatchU8Args {   // a derived struct: the uniform inst
     const int64_t* desc;        // [B][3] per-image descriptors on the device
     int b0;                     // batch index of this launch's first image
 };
+// k_patch_embed96's staging: the 2 patch rows of block (blockIdx.x, image b) -> xin[patch][ci*16 + dy*4 + dx], as in k_patch_embed
+// (which keeps its own copy of these lines, so that its code does not move)
+template <bool U8, bool RAGGED>
+__device__ __forceinline__ void pe_stage(const float* __restrict__ x, const std::conditional_t<RAGGED, PatchU8RaggedArgs, PatchU8Args>& u,
+                                         float (*xin)[48], int b, int p0, int H, int W, int gw, int L) {
+    const int py0 = p0 / gw;
+    // 2 patch rows x 3 channels x 4 dy image rows of gw float4s each
+    for (int i = threadIdx.x; i < 2 * 12 * gw; i += 256) {
+        const int r = i / gw, px = i - r * gw;             // r = pyl*12 + ci*4 + dy
+        const int pyl = r / 12, cd = r - pyl * 12, ci = cd >> 2, dy = cd & 3;
+        const int py = py0 + pyl;
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (py * gw + px < L) {
+            if constexpr (U8) {
+                PatchU8Args g = u;      // RAGGED: this image's first byte, size and padding in place of the batch's
+                if constexpr (RAGGED) {
+                    const int64_t* d = u.desc + (size_t)(u.b0 + b) * 3;
+                    g.img = u.img + d[0]; g.h = (int)d[1]; g.w = (int)d[2];
+                    g.hp = (224 - g.w) / 2; g.vp = (224 - g.h) / 2;
+                }
+                const unsigned char* ib = RAGGED ? g.img : g.img + (size_t)b * g.h * g.w * 3;
+                const int iy = 4 * py + dy - g.vp;
+                float e[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int ix = 4 * px + q - g.hp;
+                    int pv = g.fill;
+                    if (iy >= 0 && iy < g.h && ix >= 0 && ix < g.w) pv = ib[((size_t)iy * g.w + ix) * 3 + ci];
+                    e[q] = __fdiv_rn(__fsub_rn(__fdiv_rn((float)pv, 255.0f), g.mean[ci]), g.stdv[ci]);
+                }
+                v = (f32x4){e[0], e[1], e[2], e[3]};
+            } else {
+                v = *reinterpret_cast<const f32x4*>(x + (((size_t)b * 3 + ci) * H + 4 * py + dy) * W + 4 * px);
+            }
+        }
+        *reinterpret_cast<f32x4*>(&xin[pyl * gw + px][ci * 16 + dy * 4]) = v;
+    }
+}
+
 template <bool U8, bool RAGGED = false>
 __global__ __launch_bounds__(256) void k_patch_embed(const float* __restrict__ x,
                                                      const std::conditional_t<RAGGED, PatchU8RaggedArgs, PatchU8Args> u,
@@ -158,6 +197,71 @@ __global__ __launch_bounds__(256) void k_patch_embed(const float* __restrict__ x
     }
 }
 
+// The same for embed width 96 (swin_s3_base_224): thread = (channel group of 6, patch group), LayerNorm(96) over the 16
+// channel groups.  (A kernel of its own: the 128-wide one keeps its code.)
+template <bool U8, bool RAGGED = false>
+__global__ __launch_bounds__(256) void k_patch_embed96(const float* __restrict__ x,
+                                                       const std::conditional_t<RAGGED, PatchU8RaggedArgs, PatchU8Args> u,
+                                                       const float* __restrict__ w,
+                                                       const float* __restrict__ bias, const float* __restrict__ gamma,
+                                                       const float* __restrict__ beta, bf16_t* __restrict__ out, int H,
+                                                       int W, int gw, int L, float eps) {
+    constexpr int CO = 96, CPT = CO / 16;
+    __shared__ __attribute__((aligned(16))) float xin[PE_P][48];
+    const int b = blockIdx.y;
+    const int p0 = blockIdx.x * PE_P;
+    pe_stage<U8, RAGGED>(x, u, xin, b, p0, H, W, gw, L);
+    __syncthreads();
+    const int pg = threadIdx.x >> 4, cg = threadIdx.x & 15;
+    float acc[PE_PPT][CPT];
+#pragma unroll
+    for (int p = 0; p < PE_PPT; ++p)
+#pragma unroll
+        for (int j = 0; j < CPT; ++j) acc[p][j] = bias[cg * CPT + j];
+#pragma unroll 2
+    for (int k4 = 0; k4 < 48; k4 += 4) {
+        f32x4 xv[PE_PPT];
+#pragma unroll
+        for (int p = 0; p < PE_PPT; ++p) xv[p] = *reinterpret_cast<const f32x4*>(&xin[pg * PE_PPT + p][k4]);
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+            float wv[CPT];
+#pragma unroll
+            for (int j = 0; j < CPT; j += 2) {
+                const float2 t = *reinterpret_cast<const float2*>(w + (k4 + kk) * CO + cg * CPT + j);
+                wv[j] = t.x; wv[j + 1] = t.y;
+            }
+#pragma unroll
+            for (int p = 0; p < PE_PPT; ++p) {
+                const float v = xv[p][kk];
+#pragma unroll
+                for (int j = 0; j < CPT; ++j) acc[p][j] += v * wv[j];
+            }
+        }
+    }
+    float g[CPT], be[CPT];
+#pragma unroll
+    for (int j = 0; j < CPT; ++j) { g[j] = gamma[cg * CPT + j]; be[j] = beta[cg * CPT + j]; }
+#pragma unroll
+    for (int p = 0; p < PE_PPT; ++p) {
+        float s = 0.f;
+#pragma unroll
+        for (int j = 0; j < CPT; ++j) s += acc[p][j];
+        const float mean = group_sum<16>(s) * (1.0f / CO);
+        float q = 0.f;
+#pragma unroll
+        for (int j = 0; j < CPT; ++j) { acc[p][j] -= mean; q += acc[p][j] * acc[p][j]; }
+        const float rstd = rsqrtf(group_sum<16>(q) * (1.0f / CO) + eps);
+        const int pp = p0 + pg * PE_PPT + p;
+        if (pp < L) {
+            unsigned* o = reinterpret_cast<unsigned*>(out + ((size_t)b * L + pp) * CO + cg * CPT);
+#pragma unroll
+            for (int j = 0; j < CPT; j += 2)
+                o[j / 2] = pack2bf(acc[p][j] * rstd * g[j] + be[j], acc[p][j + 1] * rstd * g[j + 1] + be[j + 1]);
+        }
+    }
+}
+
 // =====================================================================================
 // LayerNorm over the channel dim of [rows][C] bf16.  LPR lanes per row, VPL 16-byte vectors per lane:
 // C = LPR * VPL * 8.  MERGE: the input row is the 2x2 patch-merge concat [x(2y,2x), x(2y+1,2x), x(2y,2x+1),
@@ -230,6 +334,11 @@ static int launch_ln(const bf16_t* in, const float* g, const float* b, bf16_t* o
     hipLaunchKernelGGL((k_layernorm<LPR, VPL, MERGE, STATS>), dim3((unsigned)cdiv(rows, 256 / LPR)), dim3(256), 0, st, in, g, b, \
                        out, rows, gh, gw, eps)
     switch (C) {
+        case 96: LN_CASE(4, 3); break;      // (96 .. 1536 with three vectors per lane: swin_s3_base_224's widths)
+        case 192: LN_CASE(8, 3); break;
+        case 384: LN_CASE(16, 3); break;
+        case 768: LN_CASE(32, 3); break;
+        case 1536: LN_CASE(64, 3); break;
         case 128: LN_CASE(16, 1); break;
         case 256: LN_CASE(32, 1); break;
         case 512: LN_CASE(64, 1); break;
@@ -284,6 +393,63 @@ __global__ __launch_bounds__(256) void k_ln_token_mean(const bf16_t* __restrict_
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < 8; ++j) part[wave][(lane + i * 64) * 8 + j] = acc[i][j];
+    __syncthreads();
+    for (int c = threadIdx.x; c < C; c += 256) {
+        const float m = (part[0][c] + part[1][c] + part[2][c] + part[3][c]) / (float)L;
+        pooled[(size_t)b * C + c] = m;
+        pooled_bf16[(size_t)b * C + c] = f2bf(m);
+    }
+}
+
+// The same for C = 768 (swin_s3_base_224): a lane holds vectors lane and lane + 64 (the second only for lane < 32).
+// (A kernel of its own: the 1024-wide one keeps its code.)
+__global__ __launch_bounds__(256) void k_ln_token_mean768(const bf16_t* __restrict__ in, const float* __restrict__ gamma,
+                                                          const float* __restrict__ beta, float* __restrict__ pooled,
+                                                          bf16_t* __restrict__ pooled_bf16, int L, float eps) {
+    constexpr int C = 768, NV = C / 8;
+    __shared__ float part[4][C];
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float acc[2][8];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[i][j] = 0.f;
+    for (int t = wave; t < L; t += 4) {
+        const bf16_t* src = in + ((size_t)b * L + t) * C;
+        float v[2][8];
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int vec = lane + i * 64;
+            if (vec < NV) sw_unpack8(*reinterpret_cast<const u32x4*>(src + vec * 8), v[i]);
+            else
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[i][j] = 0.f;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) s += v[i][j];
+        }
+        const float mean = group_sum<64>(s) * (1.0f / C);
+        float q = 0.f;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+            if (lane + i * 64 < NV)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) { v[i][j] -= mean; q += v[i][j] * v[i][j]; }
+        const float rstd = rsqrtf(group_sum<64>(q) * (1.0f / C) + eps);
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+            if (lane + i * 64 < NV)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const int c = (lane + i * 64) * 8 + j;
+                    acc[i][j] += v[i][j] * rstd * gamma[c] + beta[c];
+                }
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+        if (lane + i * 64 < NV)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) part[wave][(lane + i * 64) * 8 + j] = acc[i][j];
     __syncthreads();
     for (int c = threadIdx.x; c < C; c += 256) {
         const float m = (part[0][c] + part[1][c] + part[2][c] + part[3][c]) / (float)L;
@@ -440,6 +606,141 @@ __global__ __launch_bounds__(256) void k_win_attn(const bf16_t* __restrict__ qkv
 }
 
 // =====================================================================================
+// 14x14 window attention (swin_s3_base_224's 14x14 stage: one window per image, no shift, no mask).
+// qkv / out as above; table [heads][27*27] fp32 (the head-major copy of timm's relative_position_bias_table).
+// One workgroup of 4 waves per (image, window, head): 196 tokens padded to 208 = 13 tiles of 16.  K ([key][d]), V^T
+// ([d][key]) and the head's 729-entry bias table are staged in LDS once (31 KB), behind
+// one barrier that every wave reaches.  Wave w then takes query strips w, w+4, ...: S^T = K Q^T for all 13 key tiles
+// (as in k_win_attn: keys on the MFMA rows, a lane holds 52 keys of one query), the bias is read from the table at
+// (qy-ky+13)*27 + (qx-kx+13), padded keys are -inf, and the whole row is in registers, so the softmax is the exact
+// two-pass form.  P (rounded to bf16) x V runs in 7 k-steps of 32 keys; the 14th key tile is zero on both sides.
+// =====================================================================================
+constexpr int WB_WS = 14, WB_N = 196, WB_T = 13;   // window side, tokens per window, 16-key tiles
+constexpr int WB_KS = 7;                            // 32-key k-steps of P V
+constexpr int WB_VLD = WB_KS * 32 + 8;              // Vt row stride (keys) in bf16
+constexpr int WB_TAB = 27 * 27;                     // (2*14-1)^2 relative positions
+
+__global__ __launch_bounds__(256) void k_win_attn14(const bf16_t* __restrict__ qkv, const float* __restrict__ table,
+                                                    bf16_t* __restrict__ out, int res, int C, int heads, float scale) {
+    __shared__ __attribute__((aligned(16))) bf16_t Ks[WB_T * 16 * 32];
+    __shared__ __attribute__((aligned(16))) bf16_t Vt[32 * WB_VLD];
+    __shared__ float tab[WB_TAB];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long task = blockIdx.x;
+    const int nwx = res / WB_WS, nW = nwx * nwx;
+    const int h = (int)(task % heads);
+    const long bw = task / heads;
+    const int win = (int)(bw % nW);
+    const long b = bw / nW;
+    const int wy = win / nwx, wx = win - wy * nwx;
+    const int L = res * res, C3 = 3 * C;
+    const bf16_t* base = qkv + (size_t)b * L * C3 + h * 32;
+    auto token_of = [&](int i) {
+        const int iy = i / WB_WS, ix = i - iy * WB_WS;
+        return (wy * WB_WS + iy) * res + wx * WB_WS + ix;
+    };
+
+    // ---- stage: K rows and V^T columns (keys >= 196 zero) and the head's table
+    for (int c = threadIdx.x; c < WB_T * 16 * 4; c += 256) {
+        const int key = c >> 2, dp = (c & 3) * 8;
+        u32x4 kv = {0u, 0u, 0u, 0u}, vv = {0u, 0u, 0u, 0u};
+        if (key < WB_N) {
+            const bf16_t* r = base + (size_t)token_of(key) * C3 + dp;
+            kv = *reinterpret_cast<const u32x4*>(r + C);
+            vv = *reinterpret_cast<const u32x4*>(r + 2 * C);
+        }
+        *reinterpret_cast<u32x4*>(&Ks[key * 32 + dp]) = kv;
+        const bf16_t* e = reinterpret_cast<const bf16_t*>(&vv);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) Vt[(dp + j) * WB_VLD + key] = e[j];
+    }
+    for (int i = threadIdx.x; i < 32 * 16; i += 256) Vt[(i >> 4) * WB_VLD + WB_T * 16 + (i & 15)] = f2bf(0.f);   // keys 208..223
+    for (int i = threadIdx.x; i < WB_TAB; i += 256) tab[i] = table[(size_t)h * WB_TAB + i];
+    __syncthreads();
+
+    const int fr = lane & 15, fq = lane >> 4;
+#pragma unroll 1
+    for (int u = wave; u < WB_T; u += 4) {
+        const int qi = u * 16 + fr;
+        const int qc = qi < WB_N ? qi : WB_N - 1;     // clamp padded queries to a valid row (result discarded)
+        const int qtok = token_of(qc);
+        const u32x4 qv = *reinterpret_cast<const u32x4*>(base + (size_t)qtok * C3 + fq * 8);
+        const bf16x8 qf = *reinterpret_cast<const bf16x8*>(&qv);
+        const int qy = qc / WB_WS, qb = (qy + 13) * 27 + (qc - qy * WB_WS) + 13;
+        // kz == 0, but not provably so: it keeps the K fragment reads and the bias offsets (104 values that do not depend on the
+        // strip) inside this loop; hoisted out of it they stay live across it and spill (measured: 161 spilled VGPRs)
+        const int kz = __builtin_amdgcn_readfirstlane(u) - u;
+        float v[WB_T][4];   // [key tile t][r]: query 16u + fr, key 16t + 4fq + r
+        float mx = -INFINITY;
+#pragma unroll
+        for (int t = 0; t < WB_T; ++t) {
+            const bf16x8 kf = *reinterpret_cast<const bf16x8*>(&Ks[(t * 16 + fr + kz) * 32 + fq * 8]);
+            const f32x4 s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf, (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+            const int k0 = t * 16 + fq * 4 + kz;
+            const float sv[4] = {s.x, s.y, s.z, s.w};
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                // key k0 + r at (ky, kx) = (k / 14, k % 14): table row (qy-ky+13)*27 + (qx-kx+13) = qb - (k + 13 ky);
+                // padded keys are -inf and read key 195's row (inside the table).  (k * 4682) >> 16 == k / 14 for k < 196.
+                const int k = t == WB_T - 1 ? min(k0 + r, WB_N - 1) : k0 + r, ky = (k * 4682) >> 16;
+                float x = sv[r] * scale + tab[qb - k - 13 * ky];
+                if (t == WB_T - 1 && k0 + r >= WB_N) x = -INFINITY;
+                v[t][r] = x;
+                mx = fmaxf(mx, x);
+            }
+        }
+        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        float sum = 0.f;
+#pragma unroll
+        for (int t = 0; t < WB_T; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                v[t][r] = __builtin_amdgcn_exp2f((v[t][r] - mx) * 1.4426950408889634f);
+                sum += v[t][r];
+            }
+        sum += __shfl_xor(sum, 16, 64);
+        sum += __shfl_xor(sum, 32, 64);
+        const float inv = __builtin_amdgcn_rcpf(sum);
+
+        // O^T = V^T P^T, k permuted as in k_win_attn: element j of lane group fq in k-step ks is key 16*(2ks + (j>>2)) + 4fq + (j&3)
+        f32x4 o[2] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+        for (int ks = 0; ks < WB_KS; ++ks) {
+            u32x4 pk;
+            pk.x = pack2bf(v[2 * ks][0] * inv, v[2 * ks][1] * inv);
+            pk.y = pack2bf(v[2 * ks][2] * inv, v[2 * ks][3] * inv);
+            if (2 * ks + 1 < WB_T) {
+                pk.z = pack2bf(v[2 * ks + 1][0] * inv, v[2 * ks + 1][1] * inv);
+                pk.w = pack2bf(v[2 * ks + 1][2] * inv, v[2 * ks + 1][3] * inv);
+            } else {
+                pk.z = 0u; pk.w = 0u;
+            }
+            const bf16x8 pf = *reinterpret_cast<bf16x8*>(&pk);
+#pragma unroll
+            for (int vt = 0; vt < 2; ++vt) {
+                const bf16_t* vr = Vt + (vt * 16 + fr) * WB_VLD + 32 * ks + 4 * fq;
+                u32x4 a;
+                const u32x2 lo = *reinterpret_cast<const u32x2*>(vr);
+                const u32x2 hi = *reinterpret_cast<const u32x2*>(vr + 16);
+                a.x = lo.x; a.y = lo.y; a.z = hi.x; a.w = hi.y;
+                o[vt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<bf16x8*>(&a), pf, o[vt], 0, 0, 0);
+            }
+        }
+        if (qi < WB_N) {
+            bf16_t* orow = out + ((size_t)b * L + qtok) * C + h * 32 + fq * 4;
+#pragma unroll
+            for (int vt = 0; vt < 2; ++vt) {
+                u32x2 w;
+                w.x = pack2bf(o[vt].x, o[vt].y);
+                w.y = pack2bf(o[vt].z, o[vt].w);
+                *reinterpret_cast<u32x2*>(orow + vt * 16) = w;
+            }
+        }
+    }
+}
+
+// =====================================================================================
 // packing + execution hooks used by model.hip
 // =====================================================================================
 static inline uint16_t f2bf_h(float f) { return f2bf_host(f); }
@@ -459,6 +760,22 @@ static void swin_dense_rel_bias(const float* table, int heads, float* dense) {
                 }
                 dense[((size_t)hh * WA_N + i) * 64 + j] = v;
             }
+}
+
+// relative_position_bias_table [(2*14-1)^2][heads] -> the head-major [heads][729] copy k_win_attn14 stages per head.  Shared by the
+// model pack and mi355_window_attention_ws.
+static void swin_headmajor_rel_bias(const float* table, int heads, float* out) {
+    for (int hh = 0; hh < heads; ++hh)
+        for (int i = 0; i < WB_TAB; ++i) out[(size_t)hh * WB_TAB + i] = table[(size_t)i * heads + hh];
+}
+
+static int launch_win_attn14(const bf16_t* qkv, const float* table, bf16_t* out, long B, int res, int C, int heads, hipStream_t st) {
+    const long ntasks = B * (res / WB_WS) * (res / WB_WS) * heads;
+    MI355_REQUIRE(ntasks >= 1 && ntasks < (1l << 31), "win_attn14: grid of %ld tasks too large", ntasks);
+    hipLaunchKernelGGL(k_win_attn14, dim3((unsigned)ntasks), dim3(256), 0, st, qkv, table, out, res, C, heads,
+                       0.17677669529663687f /* 32^-0.5 */);
+    MI355_LAUNCH_CHECK();
+    return OK;
 }
 
 static int launch_win_attn(const bf16_t* qkv, const float* bias_dense, bf16_t* out, long B, int res, int C, int heads, int shift,
@@ -484,14 +801,15 @@ int swin_pack(Packer& pk, Op& op) {
         case OP_PATCH_EMBED: {
             const TensorSpec* w = pk.get(op.w_name);
             if (!w) return ERR_STATE;
-            MI355_REQUIRE(w->numel() == 128 * 48, "pack: %s shape", op.w_name.c_str());
-            op.w_off = pk.alloc((size_t)48 * 128 * 4);
+            const int co_n = op.cout;   // 128 (swin_base) or 96 (swin_s3_base): [48][co_n]
+            MI355_REQUIRE((co_n == 128 || co_n == 96) && w->numel() == co_n * 48, "pack: %s shape", op.w_name.c_str());
+            op.w_off = pk.alloc((size_t)48 * co_n * 4);
             float* W = (float*)(pk.blob.data() + op.w_off);
-            for (int co = 0; co < 128; ++co)
-                for (int k = 0; k < 48; ++k) W[(size_t)k * 128 + co] = bf_round_host(w->data[(size_t)co * 48 + k]);
-            if (int e = put_vec(op.bias_name, 128, op.b_off)) return e;
-            if (int e = put_vec(op.w2_name, 128, op.w2_off)) return e;
-            return put_vec(op.bias2_name, 128, op.b2_off);
+            for (int co = 0; co < co_n; ++co)
+                for (int k = 0; k < 48; ++k) W[(size_t)k * co_n + co] = bf_round_host(w->data[(size_t)co * 48 + k]);
+            if (int e = put_vec(op.bias_name, co_n, op.b_off)) return e;
+            if (int e = put_vec(op.w2_name, co_n, op.w2_off)) return e;
+            return put_vec(op.bias2_name, co_n, op.b2_off);
         }
         case OP_LAYERNORM: case OP_PATCH_MERGE_LN: case OP_TOKEN_MEAN: {
             if (int e = put_vec(op.w_name, op.cout, op.w_off)) return e;
@@ -501,6 +819,12 @@ int swin_pack(Packer& pk, Op& op) {
             const TensorSpec* t = pk.get(op.aux_name);
             if (!t) return ERR_STATE;
             const int ws = op.window, nh = op.heads, N = ws * ws;
+            if (ws == WB_WS) {   // 14x14 windows: the head-major table, indexed in the kernel (a dense bias would be 2 MB a block)
+                MI355_REQUIRE(t->numel() == (int64_t)WB_TAB * nh, "pack: %s shape", op.aux_name.c_str());
+                op.aux_off = pk.alloc((size_t)nh * WB_TAB * 4);
+                swin_headmajor_rel_bias(t->data.data(), nh, (float*)(pk.blob.data() + op.aux_off));
+                return OK;
+            }
             MI355_REQUIRE(ws == 7 && t->numel() == (int64_t)(2 * ws - 1) * (2 * ws - 1) * nh, "pack: %s shape", op.aux_name.c_str());
             op.aux_off = pk.alloc((size_t)nh * N * 64 * 4);
             swin_dense_rel_bias(t->data.data(), nh, (float*)(pk.blob.data() + op.aux_off));
@@ -518,26 +842,36 @@ int swin_exec(const ModelDef& def, const Op& op, ExecCtx& cx) {
             MI355_REQUIRE(cx.H == 224 && cx.W == 224, "swin needs 224x224 input");
             const int gw = cx.W / 4, L = gw * (cx.H / 4);
             MI355_REQUIRE(2 * gw == PE_P, "patch_embed: kernel is laid out for 56 patches per row");
+            MI355_REQUIRE(op.cout == 128 || op.cout == 96, "patch_embed: width %d unsupported", op.cout);
             PatchU8RaggedArgs r{};
             PatchU8Args& u = r;
+            const dim3 grid(cdiv(L, PE_P), cx.nb);
+            const float *w = (const float*)cx.w(op.w_off), *bias = (const float*)cx.w(op.b_off), *g = (const float*)cx.w(op.w2_off),
+                        *be = (const float*)cx.w(op.b2_off);
+            bf16_t* out = (bf16_t*)cx.slot_ptr(op.out);
+            const bool w96 = op.cout == 96;
             if (cx.x_u8) {            // uint8 images: SquarePad + ToTensor + Normalize fused into the patch loads (mi355_model_forward_u8)
                 MI355_REQUIRE(!cx.conv_w, "swin: the conv_input pre-stem belongs to the convolutional backbones");
                 MI355_REQUIRE(std::max(cx.img_h, cx.img_w) == 224, "swin needs images whose longer side is 224 (got %dx%d)", cx.img_h, cx.img_w);
                 u.img = cx.x_u8; u.h = cx.img_h; u.w = cx.img_w; u.hp = (224 - cx.img_w) / 2; u.vp = (224 - cx.img_h) / 2; u.fill = cx.fill;
                 for (int c = 0; c < 3; ++c) { u.mean[c] = cx.mean[c]; u.stdv[c] = cx.stdv[c]; }
                 r.desc = cx.u8_desc; r.b0 = cx.b0;
-                if (cx.u8_desc)
-                    hipLaunchKernelGGL((k_patch_embed<true, true>), dim3(cdiv(L, PE_P), cx.nb), dim3(256), 0, cx.st, (const float*)nullptr,
-                                       r, (const float*)cx.w(op.w_off), (const float*)cx.w(op.b_off), (const float*)cx.w(op.w2_off),
-                                       (const float*)cx.w(op.b2_off), (bf16_t*)cx.slot_ptr(op.out), cx.H, cx.W, gw, L, op.ln_eps);
+                if (cx.u8_desc && w96)
+                    hipLaunchKernelGGL((k_patch_embed96<true, true>), grid, dim3(256), 0, cx.st, (const float*)nullptr, r, w, bias, g, be, out,
+                                       cx.H, cx.W, gw, L, op.ln_eps);
+                else if (cx.u8_desc)
+                    hipLaunchKernelGGL((k_patch_embed<true, true>), grid, dim3(256), 0, cx.st, (const float*)nullptr, r, w, bias, g, be, out,
+                                       cx.H, cx.W, gw, L, op.ln_eps);
+                else if (w96)
+                    hipLaunchKernelGGL(k_patch_embed96<true>, grid, dim3(256), 0, cx.st, (const float*)nullptr, u, w, bias, g, be, out, cx.H,
+                                       cx.W, gw, L, op.ln_eps);
                 else
-                    hipLaunchKernelGGL(k_patch_embed<true>, dim3(cdiv(L, PE_P), cx.nb), dim3(256), 0, cx.st, (const float*)nullptr, u,
-                                       (const float*)cx.w(op.w_off), (const float*)cx.w(op.b_off), (const float*)cx.w(op.w2_off),
-                                       (const float*)cx.w(op.b2_off), (bf16_t*)cx.slot_ptr(op.out), cx.H, cx.W, gw, L, op.ln_eps);
+                    hipLaunchKernelGGL(k_patch_embed<true>, grid, dim3(256), 0, cx.st, (const float*)nullptr, u, w, bias, g, be, out, cx.H,
+                                       cx.W, gw, L, op.ln_eps);
+            } else if (w96) {
+                hipLaunchKernelGGL(k_patch_embed96<false>, grid, dim3(256), 0, cx.st, cx.x, u, w, bias, g, be, out, cx.H, cx.W, gw, L, op.ln_eps);
             } else {
-                hipLaunchKernelGGL(k_patch_embed<false>, dim3(cdiv(L, PE_P), cx.nb), dim3(256), 0, cx.st, cx.x, u, (const float*)cx.w(op.w_off),
-                                   (const float*)cx.w(op.b_off), (const float*)cx.w(op.w2_off), (const float*)cx.w(op.b2_off),
-                                   (bf16_t*)cx.slot_ptr(op.out), cx.H, cx.W, gw, L, op.ln_eps);
+                hipLaunchKernelGGL(k_patch_embed<false>, grid, dim3(256), 0, cx.st, cx.x, u, w, bias, g, be, out, cx.H, cx.W, gw, L, op.ln_eps);
             }
             MI355_LAUNCH_CHECK();
             return OK;
@@ -546,7 +880,9 @@ int swin_exec(const ModelDef& def, const Op& op, ExecCtx& cx) {
             const long rows = (long)cx.nb * op.tokens_h * op.tokens_h;
             // Folded into the next GEMM (norm1 -> qkv, norm2 -> fc1) when that GEMM takes the DMA-tiled kernel, whose epilogue
             // knows how (M >= 1024 rows; smaller problems keep the separate kernel and the unfolded weights)
-            if (op.fuse_next && cx.m->fuse_ln && rows >= 1024 && cx.m->slots[SLOT_LNSTATS].bytes >= (size_t)rows * 8) {
+            // (and only where that epilogue exists: K >= 128 and a multiple of 64, so swin_s3's width-96 stage keeps the separate kernel)
+            if (op.fuse_next && cx.m->fuse_ln && rows >= 1024 && op.cout >= 128 && op.cout % 64 == 0 &&
+                cx.m->slots[SLOT_LNSTATS].bytes >= (size_t)rows * 8) {
                 cx.ln_pending_in = op.in;
                 return launch_ln<false, true>((const bf16_t*)cx.slot_ptr(op.in), nullptr, nullptr, (bf16_t*)cx.slot_ptr(SLOT_LNSTATS),
                                               rows, op.cout, 0, 0, op.ln_eps, cx.st);
@@ -561,15 +897,25 @@ int swin_exec(const ModelDef& def, const Op& op, ExecCtx& cx) {
         }
         case OP_WINATTN: {
             MI355_REQUIRE(op.cout == op.heads * 32, "win_attn: head_dim must be 32");
+            if (op.window == WB_WS) {
+                MI355_REQUIRE(op.shift == 0 && op.tokens_h % WB_WS == 0, "win_attn14: res %d shift %d unsupported", op.tokens_h, op.shift);
+                return launch_win_attn14((const bf16_t*)cx.slot_ptr(op.in), (const float*)cx.w(op.aux_off), (bf16_t*)cx.slot_ptr(op.out),
+                                         cx.nb, op.tokens_h, op.cout, op.heads, cx.st);
+            }
             return launch_win_attn((const bf16_t*)cx.slot_ptr(op.in), (const float*)cx.w(op.aux_off), (bf16_t*)cx.slot_ptr(op.out),
                                    cx.nb, op.tokens_h, op.cout, op.heads, op.shift, cx.st);
         }
         case OP_TOKEN_MEAN: {
-            MI355_REQUIRE(op.cin == 1024, "token_mean: width %d unsupported", op.cin);
+            MI355_REQUIRE(op.cin == 1024 || op.cin == 768, "token_mean: width %d unsupported", op.cin);
             const int L = op.tokens_h * op.tokens_h;
-            hipLaunchKernelGGL(k_ln_token_mean, dim3(cx.nb), dim3(256), 0, cx.st, (const bf16_t*)cx.slot_ptr(op.in),
-                               (const float*)cx.w(op.w_off), (const float*)cx.w(op.b_off), (float*)cx.slot_ptr(SLOT_POOLED),
-                               (bf16_t*)cx.slot_ptr(SLOT_POOLED_BF16), L, op.ln_eps);
+            const bf16_t* in = (const bf16_t*)cx.slot_ptr(op.in);
+            const float *g = (const float*)cx.w(op.w_off), *be = (const float*)cx.w(op.b_off);
+            float* pooled = (float*)cx.slot_ptr(SLOT_POOLED);
+            bf16_t* pooled_bf16 = (bf16_t*)cx.slot_ptr(SLOT_POOLED_BF16);
+            if (op.cin == 768)
+                hipLaunchKernelGGL(k_ln_token_mean768, dim3(cx.nb), dim3(256), 0, cx.st, in, g, be, pooled, pooled_bf16, L, op.ln_eps);
+            else
+                hipLaunchKernelGGL(k_ln_token_mean, dim3(cx.nb), dim3(256), 0, cx.st, in, g, be, pooled, pooled_bf16, L, op.ln_eps);
             MI355_LAUNCH_CHECK();
             return OK;
         }
@@ -605,6 +951,39 @@ extern "C" int mi355_window_attention(const void* qkv, const float* bias_table, 
     else e = launch_win_attn((const bf16_t*)qkv, (const float*)d, (bf16_t*)out, B, res, C, heads, shift, st);
     if (hipStreamSynchronize(st) != hipSuccess && !e) {
         set_error("window_attention: stream synchronisation failed");
+        e = ERR_HIP;
+    }
+    MI355_CHECK_HIP(hipFree(d));
+    return e;
+}
+
+extern "C" int mi355_window_attention_ws(const void* qkv, const float* bias_table, void* out, int B, int res, int C, int heads, int window,
+                                         int shift, void* stream) {
+    using namespace mi355;
+    MI355_REQUIRE(window == 7 || window == WB_WS, "window_attention_ws: window %d (7 or 14)", window);
+    if (window == 7) return mi355_window_attention(qkv, bias_table, out, B, res, C, heads, shift, stream);
+    MI355_REQUIRE(qkv && bias_table && out, "window_attention_ws: null pointer");
+    MI355_REQUIRE(B >= 1 && res >= WB_WS && res % WB_WS == 0 && res <= WB_WS * 512,
+                  "window_attention_ws: bad shape B=%d res=%d (res a multiple of 14)", B, res);
+    MI355_REQUIRE(heads >= 1 && heads <= 1024 && C == 32 * heads, "window_attention_ws: C=%d must be 32 * heads (heads=%d)", C, heads);
+    MI355_REQUIRE(shift == 0, "window_attention_ws: shift %d (14x14 windows take shift 0 only)", shift);
+    MI355_REQUIRE((size_t)B * res * res * 3 * C < ((size_t)1 << 40), "window_attention_ws: tensor too large");
+    MI355_REQUIRE((size_t)B * (res / WB_WS) * (res / WB_WS) * heads < ((size_t)1 << 31), "window_attention_ws: grid too large");
+    MI355_REQUIRE((uintptr_t)qkv % 16 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)bias_table % 4 == 0,
+                  "window_attention_ws: qkv and out must be 16-byte aligned");
+    const hipStream_t st = (hipStream_t)stream;
+    const size_t ntab = (size_t)WB_TAB * heads;
+    std::vector<float> tab(ntab), hm(ntab);
+    MI355_CHECK_HIP(hipMemcpyAsync(tab.data(), bias_table, ntab * 4, hipMemcpyDeviceToHost, st));
+    MI355_CHECK_HIP(hipStreamSynchronize(st));
+    swin_headmajor_rel_bias(tab.data(), heads, hm.data());
+    void* d = nullptr;
+    MI355_CHECK_HIP(hipMalloc(&d, ntab * 4));
+    int e = hipMemcpyAsync(d, hm.data(), ntab * 4, hipMemcpyHostToDevice, st) == hipSuccess ? OK : ERR_HIP;
+    if (e) set_error("window_attention_ws: bias upload failed");
+    else e = launch_win_attn14((const bf16_t*)qkv, (const float*)d, (bf16_t*)out, B, res, C, heads, st);
+    if (hipStreamSynchronize(st) != hipSuccess && !e) {
+        set_error("window_attention_ws: stream synchronisation failed");
         e = ERR_HIP;
     }
     MI355_CHECK_HIP(hipFree(d));

@@ -1,8 +1,9 @@
 """timm-shaped model objects backed by libmi355_retrieval.
 
-``create_model(name, pretrained=False, num_classes=1000)`` mirrors ``timm.create_model`` for the four
+``create_model(name, pretrained=False, num_classes=1000)`` mirrors ``timm.create_model`` for the
 backbones the reference uses (inference/inference.py:102,110,133,146 ; train/train.py:396 ;
-train/train_vit_triplet.py:354).  The returned ``nn.Module`` exposes the timm 0.4.12 surface the
+train/train_vit_triplet.py:354): efficientnet_b3a, rexnet_100/130/150/200, swin_base_patch4_window7_224 and
+swin_s3_base_224 (the default of train_vit_triplet.py / train_vit_crossentropy.py; timm 0.6.x state-dict layout).  The returned ``nn.Module`` exposes the timm 0.4.12 surface the
 reference touches:
 
 * ``model(x)`` / ``model.forward_features(x)``; ``.eval() .train() .to() .parameters()``
@@ -32,7 +33,7 @@ from ._lib import MI355Error, check, lib, require_cuda, stream_ptr
 _FAMILY = {
     "efficientnet_b3a": "efficientnet", "efficientnet_b3": "efficientnet",
     "rexnet_100": "rexnet", "rexnet_130": "rexnet", "rexnet_150": "rexnet", "rexnet_200": "rexnet",
-    "swin_base_patch4_window7_224": "swin",
+    "swin_base_patch4_window7_224": "swin", "swin_s3_base_224": "swin",
 }
 _HEAD_PATH = {"efficientnet": "classifier", "rexnet": "head.fc", "swin": "head"}
 
@@ -130,7 +131,7 @@ def pool_linear(fm: torch.Tensor, fc: "nn.Module | None" = None) -> torch.Tensor
 
 def _swin_relative_position_index(ws: int) -> torch.Tensor:
     """timm WindowAttention's ``relative_position_index`` buffer (kept only for state-dict fidelity: the HIP path
-    bakes the dense bias at pack time)."""
+    derives the index itself - a dense bias baked at pack time for 7x7 windows, the table indexed in the kernel for 14x14)."""
     c = torch.stack(torch.meshgrid([torch.arange(ws), torch.arange(ws)], indexing="ij")).flatten(1)
     rel = (c[:, :, None] - c[:, None, :]).permute(1, 2, 0).contiguous()
     rel[:, :, 0] += ws - 1

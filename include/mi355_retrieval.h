@@ -510,6 +510,15 @@ int mi355_dwconv_se_ex(const mi355_dwconv_ex_args* args, int* path, void* stream
 int mi355_window_attention(const void* qkv, const float* bias_table, void* out, int B, int res, int C, int heads, int shift,
                            void* stream);
 
+/* Developer entry: one Swin window-attention layer with the window side as an argument (head_dim 32).
+ *   window 7: exactly mi355_window_attention (same kernel, same checks, same bits).
+ *   window 14: the 14x14-window kernel of swin_s3_base_224's 14x14 stage.  qkv / out as above, bias_table [729][heads] fp32
+ *   (timm relative_position_bias_table, (2*14-1)^2 rows), copied to the kernel's head-major layout by the model's packing
+ *   routine; res a multiple of 14, shift 0 only (no mask).
+ * Every argument is checked before any HIP call.  Synchronises the stream (the packed bias is a per-call scratch buffer). */
+int mi355_window_attention_ws(const void* qkv, const float* bias_table, void* out, int B, int res, int C, int heads, int window,
+                              int shift, void* stream);
+
 /* Inference pre-processing: SquarePad(fill) -> ToTensor -> Normalize, utils/square_pad.py:20-36 +
  * inference/inference.py:48-52.  img: uint8 RGB, HWC (h, w, 3) on the device; mean/std: HOST float[3];
  * out: fp32 (3, S, S) with S = max(h, w), i.e. one image slot of the model's NCHW input batch. */

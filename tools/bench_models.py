@@ -7,7 +7,8 @@ from imageretrievalresearch_amd import synth
 
 dev = "cuda:0"
 out = {}
-for name, B in (("efficientnet_b3a", 256), ("rexnet_150", 256), ("rexnet_200", 256), ("swin_base_patch4_window7_224", 128)):
+for name, B in (("efficientnet_b3a", 256), ("rexnet_150", 256), ("rexnet_200", 256), ("swin_base_patch4_window7_224", 128),
+                ("swin_s3_base_224", 128)):
     model = M.create_model(name, num_classes=0).to(dev).eval()
     x = M.synth_fill(B * 3 * 224 * 224, 1, synth.UNIFORM, dev).view(B, 3, 224, 224)
     for _ in range(5):
