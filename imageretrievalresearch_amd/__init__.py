@@ -12,12 +12,12 @@ from . import models  # noqa: F401
 from .preprocess import pack_images, resize_batch  # noqa: F401
 from .rank import (ContrastiveLoss, CosineEmbeddingLoss, CosineSimilarity, Gallery, PreparedGallery, cos_sim_score_booster,  # noqa: F401
                    cos_sim_score_with_threshold, cosine_range, cosine_scores, cosine_topk,
-                   distinct_class_topn, hit_counts, l2_normalize_rows, merge_topk, pair_cosine,
+                   distinct_class_topn, expand_queries, hit_counts, l2_normalize_rows, merge_topk, pair_cosine,
                    retrieval_accuracy, retrieval_metrics, roc_curve, synth_fill, topk, validation_metrics,
                    verification_roc)
 
 __all__ = ["create_model", "list_models", "load_checkpoint", "strip_lightning_prefix", "ContrastiveLoss", "CosineEmbeddingLoss", "validation_metrics", "CosineSimilarity", "Gallery", "PreparedGallery", "cosine_scores",
-           "cosine_range", "cosine_topk", "pair_cosine", "topk", "merge_topk", "hit_counts", "distinct_class_topn",
+           "cosine_range", "cosine_topk", "expand_queries", "pair_cosine", "topk", "merge_topk", "hit_counts", "distinct_class_topn",
            "retrieval_metrics", "retrieval_accuracy", "roc_curve", "verification_roc", "cos_sim_score_with_threshold", "cos_sim_score_booster", "l2_normalize_rows", "synth_fill", "ShardedGallery", "MI355Error",
            "pack_images", "resize_batch"]
 

@@ -46,6 +46,7 @@ class RankFilter(C.Structure):
 
 
 LABEL_ANY, LABEL_SAME, LABEL_DIFFERENT = 0, 1, 2
+DTYPE_F32, DTYPE_F16 = 0, 1
 
 # name -> (restype, argtypes); must list every symbol include/mi355_retrieval.h declares
 # (tests/test_abi.py cross-checks this table against the header).
@@ -72,6 +73,10 @@ PROTOTYPES = {
     "mi355_rank_topk_f16_filtered": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_int64,
                                                C.POINTER(RankFilter), vp, vp, vp, C.c_size_t, vp]),
     "mi355_rank_last_path": (C.c_int, []),
+    "mi355_expand_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
+    "mi355_expand_rows": (C.c_int, [vp, C.c_int, C.c_int64, C.c_int, vp, C.c_int, C.c_int64, C.c_int64, C.c_int, vp, vp,
+                                    C.c_int64, C.c_int, C.c_int64, C.c_float, C.c_float, vp, C.c_int, C.c_int64, vp,
+                                    C.c_size_t, vp]),
     "mi355_clear_pads": (C.c_int, [vp, vp, C.c_int64, C.c_int64, C.c_int64, vp]),
     "mi355_range_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int]),
     "mi355_cosine_range": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_double, C.c_int64,

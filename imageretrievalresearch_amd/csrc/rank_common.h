@@ -457,6 +457,17 @@ __device__ __forceinline__ float row_inv_norm(const float* __restrict__ x, int d
     return 1.0f / fmaxf(sqrtf(ss), eps);
 }
 
+// The fp32 row value x * r, then its rounding to fp16: two roundings, as l2_normalize_rows(x).half() does them (the fp16
+// gallery conversion, rank_f16.hip, and the fp16 rows of the expansion, expand.hip).  (With
+// -ffp-contract=fast, hipcc fuses the pair into v_fma_mixlo_f16, ONE rounding of the exact product, which differs in the
+// last bit now and then; `#pragma clang fp contract(off)` does not stop that backend fold.  The empty asm only pins the
+// fp32 product in a register - it emits no instruction.)
+__device__ __forceinline__ _Float16 scaled_f16(float x, float r) {
+    float p = x * r;
+    asm volatile("" : "+v"(p));
+    return (_Float16)p;
+}
+
 static inline int vec_ok(const void* p, int dim) { return (dim % 4 == 0) && (((uintptr_t)p & 15) == 0); }
 
 // ---- host side of the selection (rank.hip)

@@ -21,16 +21,6 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 constexpr int F16_KSTEP = 64;                 // k-step of the GEMM: one 128-byte segment of a stored row
 static inline int f16_ld(int dim) { return (dim + F16_KSTEP - 1) / F16_KSTEP * F16_KSTEP; }
 
-// The fp32 row value x * r, then its rounding to fp16: two roundings, as l2_normalize_rows(x).half() does them.  (With
-// -ffp-contract=fast, hipcc fuses the pair into v_fma_mixlo_f16, ONE rounding of the exact product, which differs in the
-// last bit now and then; `#pragma clang fp contract(off)` does not stop that backend fold.  The empty asm only pins the
-// fp32 product in a register - it emits no instruction.)
-__device__ __forceinline__ f16 scaled_f16(float x, float r) {
-    float p = x * r;
-    asm volatile("" : "+v"(p));
-    return (f16)p;
-}
-
 // =====================================================================================
 // fp32 rows -> normalised fp16 rows, padded to ld elements with zeros.  One wave per row; the norm is row_inv_norm (the
 // one mi355_l2_normalize_rows uses, with the same vec rule), so the stored row is bit for bit l2_normalize_rows(x).half().

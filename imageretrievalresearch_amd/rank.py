@@ -10,6 +10,7 @@ routes the arithmetic to libmi355_retrieval:
 * ``hit_counts`` / ``distinct_class_topn`` .... train/train.py:252-255 ; notebook raw :240-251
 * ``roc_curve`` / ``verification_roc`` ........ utils/roc_curve_from_scratch.py (given pair scores / every labelled pair)
 * ``cosine_range`` ............................ the pairs a verification threshold accepts (``score >= threshold``)
+* ``expand_queries`` / ``Gallery.augmented`` .. alpha query expansion and database-side augmentation (not in the reference)
 """
 from __future__ import annotations
 
@@ -19,7 +20,8 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
-from ._lib import LABEL_ANY, LABEL_DIFFERENT, LABEL_SAME, MI355Error, RankFilter, check, lib, require_cuda, stream_ptr
+from ._lib import (DTYPE_F16, DTYPE_F32, LABEL_ANY, LABEL_DIFFERENT, LABEL_SAME, MI355Error, RankFilter, check, lib,
+                   require_cuda, stream_ptr)
 
 _EPS = 1e-6
 
@@ -485,6 +487,78 @@ def _cosine_topk_f16(queries: torch.Tensor, gallery_f16: torch.Tensor, rows: int
     return vals, idx
 
 
+# ---- alpha query expansion (alpha-QE) and database-side augmentation (DBA): Radenovic, Tolias and Chum, TPAMI 2018
+def _qe_args(n, alpha):
+    """(n, alpha) checked: n an integer >= 1, alpha a finite float >= 0."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or int(n) < 1:
+        raise MI355Error(f"query expansion needs n >= 1 neighbours, got {n!r}")
+    try:
+        a = float(alpha)
+    except (TypeError, ValueError):
+        raise MI355Error(f"alpha must be a finite float >= 0, got {alpha!r}") from None
+    if not np.isfinite(a) or a < 0:
+        raise MI355Error(f"alpha must be a finite float >= 0, got {alpha!r}")
+    return int(n), a
+
+
+def _qe_pair(qe):
+    if not isinstance(qe, (tuple, list)) or len(qe) != 2:
+        raise MI355Error(f"qe must be a pair (n, alpha), got {qe!r}")
+    return _qe_args(*qe)
+
+
+_DTYPES = {torch.float32: DTYPE_F32, torch.float16: DTYPE_F16}
+
+
+def _expand_rows(base: torch.Tensor, normalize_base: bool, gallery: torch.Tensor, gallery_dtype, G: int, dim: int,
+                 vals: torch.Tensor, idx: torch.Tensor, alpha: float, eps: float, idx_offset: int = 0,
+                 out: torch.Tensor | None = None) -> torch.Tensor:
+    """One ``mi355_expand_rows`` launch: row r of ``out`` = normalised (base_r + sum_j w_j * gallery[idx[r, j] - idx_offset]).
+    base (R, >= dim) rows (fp32, or the gallery's dtype), gallery (>= G, ld) rows, vals / idx (R, n) of a search; out: (R, dim)
+    fp32 (allocated when None) or rows of an fp16 gallery buffer.  Arguments checked by the caller and the library."""
+    R, n = vals.shape
+    if out is None:
+        out = torch.empty((R, dim), dtype=torch.float32, device=base.device)
+    if R == 0:
+        return out
+    vals = vals.contiguous()
+    idx = idx.to(torch.int64).contiguous()
+    out_dt = _DTYPES[out.dtype]
+    ws = _ws.get(base.device, max(int(lib().mi355_expand_workspace_bytes(R, dim, out_dt)), 1))
+    with torch.cuda.device(base.device):
+        check(lib().mi355_expand_rows(base.data_ptr(), _DTYPES[base.dtype], base.stride(0), int(bool(normalize_base)),
+                                      gallery.data_ptr(), _DTYPES[gallery_dtype], int(G), gallery.stride(0), int(dim),
+                                      vals.data_ptr(), idx.data_ptr(), R, n, int(idx_offset), float(alpha), float(eps),
+                                      out.data_ptr(), out_dt, out.stride(0), ws.data_ptr(), ws.numel(),
+                                      stream_ptr(base.device)))
+    return out
+
+
+def expand_queries(queries: torch.Tensor, gallery: torch.Tensor, n: int, alpha: float = 3.0, *,
+                   gallery_is_normalized: bool = False, eps: float = _EPS, idx_offset: int = 0,
+                   query_labels: torch.Tensor | None = None, gallery_labels: torch.Tensor | None = None,
+                   label_filter: str | None = None, exclude: torch.Tensor | None = None) -> torch.Tensor:
+    """Alpha query expansion (Radenovic, Tolias and Chum, TPAMI 2018; alpha = 0 is the average QE of Chum et al. 2007).
+
+    Round 1 is ``cosine_topk(queries, gallery, n, ...)`` with the filter arguments as given (slots it leaves empty are
+    (-inf, -1)).  Query q then becomes ``l2_normalize_rows(qn + sum_j w_j * row(i_j))``: qn = ``l2_normalize_rows(q)`` (same
+    bits), row(i) the gallery's normalised row (``gallery_is_normalized=False`` normalises the gallery once for this), w_j =
+    v_j ** alpha for a slot with v_j > 0 and a real row; every other slot is skipped (a NaN row behind it never enters the
+    sum).  The sum is fp32 in rank order, the normalisation that of ``l2_normalize_rows`` bit for bit; every row depends
+    only on its own query and neighbours (no atomics).  One HIP launch (``mi355_expand_rows``).  Returns (Q, D) fp32."""
+    n, alpha = _qe_args(n, alpha)
+    q, g = _f32c(queries, "queries"), _f32c(gallery, "gallery")
+    _check_qg(q, g)
+    Q, D = q.shape
+    if Q == 0:
+        return torch.empty((0, D), dtype=torch.float32, device=q.device)
+    vals, idx = cosine_topk(q, g, n, eps, gallery_is_normalized=gallery_is_normalized, idx_offset=idx_offset,
+                            query_labels=query_labels, gallery_labels=gallery_labels, label_filter=label_filter,
+                            exclude=exclude)
+    rows = g if gallery_is_normalized else l2_normalize_rows(g, eps)
+    return _expand_rows(q, True, rows, torch.float32, rows.shape[0], D, vals, idx, alpha, eps, idx_offset)
+
+
 class Gallery:
     """Resident gallery: rows are L2-normalised once when added and stay in HBM (the gallery is *born* on the
     GPU that embedded it).  ``search`` is then one fused call per query batch instead of the reference's per-query cosine +
@@ -559,10 +633,17 @@ class Gallery:
         return self
 
     def search(self, queries: torch.Tensor, k: int, idx_offset: int = 0, *, query_labels: torch.Tensor | None = None,
-               label_filter: str | None = None, exclude: torch.Tensor | None = None):
+               label_filter: str | None = None, exclude: torch.Tensor | None = None, qe=None):
         """Top-k of ``queries`` against the resident rows.  ``label_filter`` ("same" / "different") compares the gallery's
         labels (``add(..., labels)``) with ``query_labels``; ``exclude`` leaves out one global row per query (see
-        ``cosine_topk``).  A filtered search on a prepared gallery runs on its fp32 rows (same results)."""
+        ``cosine_topk``).  A filtered search on a prepared gallery runs on its fp32 rows (same results).
+
+        ``qe=(n, alpha)``: alpha query expansion - exactly ``search(expand_queries(queries, n, alpha, ...), k, ...)``, the same
+        filter arguments in both rounds (so a leave-one-out search never expands a query with its own row)."""
+        if qe is not None:
+            n, alpha = _qe_pair(qe)
+            filt = dict(query_labels=query_labels, label_filter=label_filter, exclude=exclude)
+            return self.search(self.expand_queries(queries, n, alpha, idx_offset, **filt), k, idx_offset, **filt)
         filtered = label_filter is not None or exclude is not None
         if label_filter is not None and self.labels is None:
             raise MI355Error(f'label_filter="{label_filter}" needs gallery labels: add(embeddings, labels)')
@@ -581,6 +662,50 @@ class Gallery:
             return p.search(queries, k, self.eps, idx_offset)
         return cosine_topk(queries, self.data, k, self.eps, gallery_is_normalized=True, idx_offset=idx_offset,
                            query_labels=query_labels, gallery_labels=self.labels, label_filter=label_filter, exclude=exclude)
+
+    def expand_queries(self, queries: torch.Tensor, n: int, alpha: float = 3.0, idx_offset: int = 0, *,
+                       query_labels: torch.Tensor | None = None, label_filter: str | None = None,
+                       exclude: torch.Tensor | None = None) -> torch.Tensor:
+        """Alpha query expansion against the resident rows: ``search(queries, n, ...)`` (whichever path ``search`` takes,
+        filters as given), then each query becomes ``l2_normalize_rows(qn + sum_j v_j^alpha * row(i_j))`` over its used slots
+        (score > 0, a real row), summed in fp32 in rank order (fp16 rows widened exactly) by one HIP launch
+        (``mi355_expand_rows``).  Returns (Q, dim) fp32."""
+        n, alpha = _qe_args(n, alpha)
+        q = _f32c(queries, "queries")
+        _check_qg(q, self.data)
+        if q.shape[0] == 0:
+            return torch.empty((0, self.dim), dtype=torch.float32, device=q.device)
+        vals, idx = self.search(q, n, idx_offset, query_labels=query_labels, label_filter=label_filter, exclude=exclude)
+        return _expand_rows(q, True, self._buf, self.dtype, self.rows, self.dim, vals, idx, alpha, self.eps, idx_offset)
+
+    def augmented(self, n: int, alpha: float = 3.0, block: int = 256) -> "Gallery":
+        """Database-side augmentation: a NEW gallery (same dtype, dim, eps and labels; unprepared) whose row r is
+        ``l2_normalize_rows(row_r + sum_j v_j^alpha * row(i_j))`` over the top-n of row r against this gallery with row r
+        itself left out (``exclude=arange``), every sum taken from the ORIGINAL rows; fp16 rows are stored as ``add`` would
+        store that fp32 row.  The self-join runs ``block`` rows at a time through this gallery's own search (fp32 rows:
+        ``cosine_topk``; fp16: the f16 kernel), each block followed by one expansion launch.  This gallery is not changed."""
+        n, alpha = _qe_args(n, alpha)
+        G = self.rows
+        out = Gallery(self.dim, self.device, capacity=G, eps=self.eps, dtype=self.dtype)
+        out.labels = None if self.labels is None else self.labels.clone()
+        if G == 0:
+            return out
+        if n > G:
+            raise MI355Error(f"selected index k out of range: k={n}, gallery rows={G}")
+        block = max(int(block), 1)
+        for q0 in range(0, G, block):
+            qn = min(block, G - q0)
+            ex = torch.arange(q0, q0 + qn, dtype=torch.int64, device=self.device)
+            rows = self._buf[q0: q0 + qn]
+            if self.dtype == torch.float16:
+                filt = _rank_filter(qn, G, self.device, None, None, None, ex)
+                vals, idx = _cosine_topk_f16(rows[:, : self.dim].float(), self._buf, G, self.dim, n, self.eps, 0, filt)
+            else:
+                vals, idx = cosine_topk(rows, self.data, n, self.eps, gallery_is_normalized=True, exclude=ex)
+            _expand_rows(rows, False, self._buf, self.dtype, G, self.dim, vals, idx, alpha, self.eps, 0,
+                         out=out._buf[q0: q0 + qn])
+        out.rows = G
+        return out
 
     def range_search(self, queries: torch.Tensor, threshold: float, *, query_labels: torch.Tensor | None = None,
                      label_filter: str | None = None, exclude: torch.Tensor | None = None, max_results: int | None = None,
@@ -645,7 +770,8 @@ _MAX_R = 1024
 
 
 def retrieval_accuracy(queries: torch.Tensor, query_labels: torch.Tensor, gallery: torch.Tensor | None = None,
-                       gallery_labels: torch.Tensor | None = None, ks=(1, 2, 4, 8), eps: float = _EPS):
+                       gallery_labels: torch.Tensor | None = None, ks=(1, 2, 4, 8), eps: float = _EPS,
+                       query_expansion=None):
     """Leave-one-out / cross-source retrieval accuracy of labelled embeddings, as defined by Musgrave et al. 2020 ("A Metric
     Learning Reality Check") and pytorch-metric-learning's AccuracyCalculator.
 
@@ -654,7 +780,10 @@ def retrieval_accuracy(queries: torch.Tensor, query_labels: torch.Tensor, galler
     with the query's label (its own row not counted); queries with R_q = 0 are left out of every mean (``num_lone``).  One
     search with k = max(max(ks), max R_q) (at most 1024) ranks every query; the per-query metrics run in one HIP kernel
     (``mi355_retrieval_metrics``).  Returns device tensors (float64) ``precision_at_1``, ``recall_at_k`` {K: ...},
-    ``r_precision``, ``map_at_r``, and ints ``num_queries``, ``num_lone``.  The one host sync reads max R_q."""
+    ``r_precision``, ``map_at_r``, and ints ``num_queries``, ``num_lone``.  The one host sync reads max R_q.
+
+    ``query_expansion=(n, alpha)``: the queries are first replaced by ``expand_queries(queries, gallery, n, alpha)`` with the
+    same exclusion (same-source: a query is never expanded with its own row), then ranked as above."""
     q = _f32c(queries, "queries")
     if q.dim() != 2:
         raise MI355Error(f"queries must be (Q, D), got {tuple(q.shape)}")
@@ -690,6 +819,9 @@ def retrieval_accuracy(queries: torch.Tensor, query_labels: torch.Tensor, galler
         raise MI355Error(f"class {lab} has {r_max} relevant gallery rows; retrieval_accuracy ranks at most {_MAX_R}")
     k = min(max(ks[-1], r_max), G)        # k = G ranks every row, so recall@K for K > G is exact as well
     exclude = torch.arange(Q, dtype=torch.int64, device=q.device) if same_source else None
+    if query_expansion is not None:
+        n_qe, alpha = _qe_pair(query_expansion)
+        q = expand_queries(q, g, n_qe, alpha, eps=eps, exclude=exclude)
     _, idx = cosine_topk(q, g, k, eps, exclude=exclude)
     per = torch.empty((Q, 3), dtype=torch.float64, device=q.device)
     Rc = R.contiguous()

@@ -87,6 +87,25 @@ class _HipOps:
     def normalize(rows):
         return _rank.l2_normalize_rows(rows)
 
+    @staticmethod
+    def qe_slab(idx, lo, local_rows):
+        """(Q, n, D) fp32: row (q, j) = this shard's row idx[q, j] - lo widened exactly to fp32 where the shard owns it, +0.0
+        elsewhere (the slab every rank contributes to the exchange of alpha query expansion)."""
+        Q, n = idx.shape
+        rows = local_rows.shape[0]
+        slab = torch.zeros((Q, n, local_rows.shape[1]), dtype=torch.float32, device=idx.device)
+        loc = idx - lo
+        own = (loc >= 0) & (loc < rows)
+        if rows:
+            slab[own] = local_rows[loc[own]].float()
+        return slab
+
+    @staticmethod
+    def expand(base, slab, vals, idx, alpha, eps):
+        """mi355_expand_rows of ``base`` (Q, D) raw queries over the exchanged slab as a (Q * n, D) fp32 gallery."""
+        Q, n, D = slab.shape
+        return _rank._expand_rows(base.contiguous(), True, slab.view(Q * n, D), torch.float32, Q * n, D, vals, idx, alpha, eps)
+
 
 class ShardedGallery:
     def __init__(self, local_rows: torch.Tensor, group=None, ops=None, labels: torch.Tensor | None = None,
@@ -202,8 +221,25 @@ class ShardedGallery:
         vals, idx = self.ops.merge_packed(allp.view(self.world, Q, k, 2), zeros, k)
         return self.ops.clear_pads(vals, idx, 0, self.total_rows)
 
+    def _expand_queries(self, q, n, alpha, query_labels, label_filter, exclude):
+        """Alpha query expansion of this rank's queries against the WHOLE gallery, bit for bit that of one ``Gallery`` holding
+        every row: round 1 is ``search(q, n)`` (merged global lists, the same on every rank); each rank writes the neighbour
+        rows it owns into a (Q, n, D) fp32 slab that is +0.0 elsewhere, and ONE all_reduce(SUM) of the slab viewed as int32
+        combines them exactly (one rank contributes each row's bits, -0.0 included); then every rank expands its own
+        queries over its part of the slab (mi355_expand_rows, the exchanged rows as an fp32 gallery of Q * n rows)."""
+        vals, idx = self.search(q, n, query_labels=query_labels, label_filter=label_filter, exclude=exclude)
+        Q = idx.shape[0]
+        slab = self.ops.qe_slab(idx, self.offset, self.local)
+        if self.world > 1:
+            torch.distributed.all_reduce(slab.view(torch.int32), op=torch.distributed.ReduceOp.SUM, group=self.group)
+        Ql = q.shape[0]
+        mine = slice(self.rank * Ql, (self.rank + 1) * Ql)
+        pos = torch.arange(Ql * n, dtype=torch.int64, device=self.device).view(Ql, n)
+        local_idx = torch.where(idx[mine] >= 0, pos, torch.full_like(pos, -1))
+        return self.ops.expand(q, slab[mine].contiguous(), vals[mine].contiguous(), local_idx, alpha, _rank._EPS) if Q else q
+
     def search(self, queries_local: torch.Tensor, k: int, *, query_labels: torch.Tensor | None = None,
-               label_filter: str | None = None, exclude: torch.Tensor | None = None):
+               label_filter: str | None = None, exclude: torch.Tensor | None = None, qe=None):
         """Top-k of every rank's queries against the WHOLE gallery.
 
         ``queries_local``: this rank's (Q_local, D) queries (same Q_local on every rank).
@@ -211,11 +247,21 @@ class ShardedGallery:
 
         Filtered search (see ``cosine_topk``): ``label_filter`` "same" / "different" compares the shards' labels with this
         rank's ``query_labels`` (Q_local,); ``exclude`` (Q_local,) holds GLOBAL row indices.  Slots no shard could fill are
-        (-inf, -1)."""
+        (-inf, -1).
+
+        ``qe=(n, alpha)``: alpha query expansion (``Gallery.search``'s ``qe``), the same filter arguments in both rounds; bit for
+        bit the result of one ``Gallery`` holding every row.  (Database-side augmentation has no sharded form.)"""
         if k < 1 or k > self.total_rows:
             raise MI355Error(f"selected index k out of range: k={k}, gallery rows={self.total_rows}")
         if label_filter not in (None, "same", "different"):
             raise MI355Error(f'label_filter must be None, "same" or "different", got {label_filter!r}')
+        if qe is not None:
+            n, alpha = _rank._qe_pair(qe)
+            if n > self.total_rows:
+                raise MI355Error(f"selected index k out of range: k={n}, gallery rows={self.total_rows}")
+            filt = dict(query_labels=query_labels, label_filter=label_filter, exclude=exclude)
+            q2 = self._expand_queries(queries_local.float().contiguous(), n, alpha, **filt)
+            return self.search(q2, k, **filt)
         q = queries_local.float().contiguous()
         if label_filter is not None or exclude is not None:
             return self._filtered_search(q, k, query_labels, label_filter, exclude)

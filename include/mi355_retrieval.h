@@ -201,6 +201,27 @@ int mi355_cosine_range_f16(const float* queries, int64_t Q, const void* gallery_
 int mi355_range_compact(const void* candidates, int64_t capacity, int64_t Q, int64_t nnz, int64_t idx_offset, const void* workspace,
                         size_t workspace_bytes, int64_t* offsets, int64_t* indices, float* scores, void* stream);
 
+/* Query expansion / database-side augmentation (alpha-QE, DBA; Radenovic, Tolias and Chum, TPAMI 2018): one output row per
+ * row r of the neighbour lists vals / idx [R][n] (device fp32 / int64, the output of a search, rank order):
+ *   w_j = v_j ^ alpha for a USED slot: v_j > 0 and l_j = idx[r][j] - idx_offset in [0, gallery_rows); every other slot
+ *         (pads (-inf, -1), scores <= 0 or NaN, rows outside the gallery) is skipped and its row never read.  alpha 0, 1, 2, 3
+ *         give 1, v, v * v, (v * v) * v; other alpha powf(v, alpha).  alpha finite and >= 0.
+ *   x   = base_r + sum_j w_j * gallery[l_j], fp32 per element, j = 0 .. n-1 in order, each w_j * row rounded before its add
+ *         (no fma); fp16 rows are widened exactly.  base_r: base row r as it is, or with normalize_base (fp32 base only)
+ *         l2_normalize_rows(base_r) with the bits of mi355_l2_normalize_rows.
+ *   out = l2_normalize_rows(x, eps) bit for bit (MI355_DTYPE_F32), or fp16 of it as mi355_gallery_to_f16 stores it
+ *         (MI355_DTYPE_F16, elements dim .. out_ld-1 zeroed).  No atomics: each row depends only on its own base, list and
+ *         weights.
+ * Rows are base_ld / gallery_ld / out_ld elements apart (>= dim); when dim % 4 == 0, out is 16-byte aligned and out_ld % 4 == 0.
+ * workspace: mi355_expand_workspace_bytes(R, dim, out_dtype) (fp16 output: R * dim fp32 sums; fp32 output: none, may be
+ * NULL).  Every argument is checked before any HIP call; R = 0 does nothing. */
+enum { MI355_DTYPE_F32 = 0, MI355_DTYPE_F16 = 1 };
+size_t mi355_expand_workspace_bytes(int64_t R, int dim, int out_dtype);
+int mi355_expand_rows(const void* base, int base_dtype, int64_t base_ld, int normalize_base, const void* gallery,
+                      int gallery_dtype, int64_t gallery_rows, int64_t gallery_ld, int dim, const float* vals,
+                      const int64_t* idx, int64_t R, int n, int64_t idx_offset, float alpha, float eps, void* out,
+                      int out_dtype, int64_t out_ld, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Indices outside [lo, hi) become (-inf, -1) in val / idx [n] (the sharded filtered search: slots no shard filled). */
 int mi355_clear_pads(float* val, int64_t* idx, int64_t n, int64_t lo, int64_t hi, void* stream);
 
