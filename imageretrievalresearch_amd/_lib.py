@@ -77,6 +77,12 @@ PROTOTYPES = {
     "mi355_expand_rows": (C.c_int, [vp, C.c_int, C.c_int64, C.c_int, vp, C.c_int, C.c_int64, C.c_int64, C.c_int, vp, vp,
                                     C.c_int64, C.c_int, C.c_int64, C.c_float, C.c_float, vp, C.c_int, C.c_int64, vp,
                                     C.c_size_t, vp]),
+    "mi355_moments_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
+    "mi355_embedding_moments": (C.c_int, [vp, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp,
+                                          C.c_size_t, vp]),
+    "mi355_whiten_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int]),
+    "mi355_whiten_rows": (C.c_int, [vp, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_float, vp, vp, C.c_int, C.c_int, vp,
+                                    C.c_int, C.c_int64, vp, C.c_size_t, vp]),
     "mi355_clear_pads": (C.c_int, [vp, vp, C.c_int64, C.c_int64, C.c_int64, vp]),
     "mi355_range_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int]),
     "mi355_cosine_range": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_double, C.c_int64,

@@ -169,35 +169,8 @@ __global__ __launch_bounds__(256, 4) void k_expand_rows(ExpandArgs a) {
         }
     }
     // the norm of x as l2_normalize_rows takes it (each lane reads back only its own units), then scale and store
-    const float r = row_inv_norm(x, dim, a.eps, VEC ? 1 : 0, lane);
-    if constexpr (!OF16) {
-        if constexpr (VEC) {
-            f32x4* x4 = reinterpret_cast<f32x4*>(x);
-            for (int i = lane; i < nu; i += 64) {
-                f32x4 v = x4[i];
-                v.x *= r; v.y *= r; v.z *= r; v.w *= r;
-                x4[i] = v;
-            }
-        } else {
-            for (int i = lane; i < dim; i += 64) x[i] = x[i] * r;
-        }
-    } else {
-        f16* y = static_cast<f16*>(a.out) + row * a.out_ld;
-        const int ld = (int)a.out_ld;
-        if constexpr (VEC) {
-            const f32x4* x4 = reinterpret_cast<const f32x4*>(x);
-            for (int i = lane; i < ld / 4; i += 64) {
-                f16x4 h = {(f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f};
-                if (i < nu) {
-                    const f32x4 v = x4[i];
-                    h = (f16x4){scaled_f16(v.x, r), scaled_f16(v.y, r), scaled_f16(v.z, r), scaled_f16(v.w, r)};
-                }
-                reinterpret_cast<f16x4*>(y)[i] = h;
-            }
-        } else {
-            for (int i = lane; i < ld; i += 64) y[i] = i < dim ? scaled_f16(x[i], r) : (f16)0.f;
-        }
-    }
+    f16* y = OF16 ? static_cast<f16*>(a.out) + row * a.out_ld : nullptr;
+    normalize_row_store<VEC, OF16>(x, y, dim, (int)a.out_ld, a.eps, lane);
 }
 
 template <bool VEC, class TG>

@@ -468,6 +468,43 @@ __device__ __forceinline__ _Float16 scaled_f16(float x, float r) {
     return (_Float16)p;
 }
 
+// The last step of every kernel that makes normalised rows from fp32 sums (the expansion, expand.hip; the whitening
+// transform, whiten.hip): one wave takes the norm of the fp32 row x[dim] as l2_normalize_rows does (VEC: dim % 4 == 0, rows
+// 16-byte aligned), then scales x in place (fp32 output: x IS the output row) or stores fp16(x * r) into y[ld] with elements
+// dim .. ld-1 zeroed (the mi355_gallery_to_f16 row).
+typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
+template <bool VEC, bool OF16>
+__device__ __forceinline__ void normalize_row_store(float* x, _Float16* y, int dim, int ld, float eps, int lane) {
+    const int nu = VEC ? dim / 4 : dim;
+    const float r = row_inv_norm(x, dim, eps, VEC ? 1 : 0, lane);
+    if constexpr (!OF16) {
+        if constexpr (VEC) {
+            f32x4* x4 = reinterpret_cast<f32x4*>(x);
+            for (int i = lane; i < nu; i += 64) {
+                f32x4 v = x4[i];
+                v.x *= r; v.y *= r; v.z *= r; v.w *= r;
+                x4[i] = v;
+            }
+        } else {
+            for (int i = lane; i < dim; i += 64) x[i] = x[i] * r;
+        }
+    } else {
+        if constexpr (VEC) {
+            const f32x4* x4 = reinterpret_cast<const f32x4*>(x);
+            for (int i = lane; i < ld / 4; i += 64) {
+                f16x4_t h = {(_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f};
+                if (i < nu) {
+                    const f32x4 v = x4[i];
+                    h = (f16x4_t){scaled_f16(v.x, r), scaled_f16(v.y, r), scaled_f16(v.z, r), scaled_f16(v.w, r)};
+                }
+                reinterpret_cast<f16x4_t*>(y)[i] = h;
+            }
+        } else {
+            for (int i = lane; i < ld; i += 64) y[i] = i < dim ? scaled_f16(x[i], r) : (_Float16)0.f;
+        }
+    }
+}
+
 static inline int vec_ok(const void* p, int dim) { return (dim % 4 == 0) && (((uintptr_t)p & 15) == 0); }
 
 // ---- host side of the selection (rank.hip)

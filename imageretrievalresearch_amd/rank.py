@@ -11,6 +11,7 @@ routes the arithmetic to libmi355_retrieval:
 * ``roc_curve`` / ``verification_roc`` ........ utils/roc_curve_from_scratch.py (given pair scores / every labelled pair)
 * ``cosine_range`` ............................ the pairs a verification threshold accepts (``score >= threshold``)
 * ``expand_queries`` / ``Gallery.augmented`` .. alpha query expansion and database-side augmentation (not in the reference)
+* ``Gallery.moments`` / ``Gallery.whitened`` .. PCA whitening of a resident gallery (whitening.py; not in the reference)
 """
 from __future__ import annotations
 
@@ -705,6 +706,27 @@ class Gallery:
             _expand_rows(rows, False, self._buf, self.dtype, G, self.dim, vals, idx, alpha, self.eps, 0,
                          out=out._buf[q0: q0 + qn])
         out.rows = G
+        return out
+
+    def moments(self):
+        """``embedding_moments`` of the resident normalised rows (fp32 or fp16, read where they lie): the input of a PCA
+        whitening fit (``Whitening.fit(gallery)``)."""
+        from .whitening import embedding_moments
+        return embedding_moments(self)
+
+    def whitened(self, w, dtype: torch.dtype | None = None) -> "Gallery":
+        """A NEW gallery of ``w.dim_out`` columns (same eps and labels, unprepared; ``dtype`` as this one unless given) whose
+        row r is the whitening ``w`` of resident row r - the rows are normalised already, so they go into the projection as
+        they are - written straight into the new buffer by one ``mi355_whiten_rows`` launch (fp16: rounded as ``add`` would
+        store that fp32 row).  Query side: ``whitened.search(w.transform(q), k)``.  This gallery is not changed."""
+        if self.dim != w.dim_in:
+            raise MI355Error(f"the whitening takes {w.dim_in} columns but the gallery has {self.dim}")
+        out = Gallery(w.dim_out, self.device, capacity=self.rows, eps=self.eps, dtype=self.dtype if dtype is None else dtype)
+        out.labels = None if self.labels is None else self.labels.clone()
+        if self.rows:
+            ld = int(self._buf.stride(0)) if self._buf.shape[0] > 1 else self._ld
+            w._apply(self._buf, _DTYPES[self.dtype], self.rows, ld, False, out._buf[: self.rows], True)
+        out.rows = self.rows
         return out
 
     def range_search(self, queries: torch.Tensor, threshold: float, *, query_labels: torch.Tensor | None = None,

@@ -101,6 +101,13 @@ class _HipOps:
         return slab
 
     @staticmethod
+    def moments(local_rows, gallery_f16=None):
+        """(sum (D,), outer (D, D)) float64 device tensors of this shard's normalised rows (mi355_embedding_moments)."""
+        from .whitening import embedding_moments
+        m = embedding_moments(gallery_f16 if gallery_f16 is not None else local_rows)
+        return m.sum, m.outer
+
+    @staticmethod
     def expand(base, slab, vals, idx, alpha, eps):
         """mi355_expand_rows of ``base`` (Q, D) raw queries over the exchanged slab as a (Q * n, D) fp32 gallery."""
         Q, n, D = slab.shape
@@ -399,6 +406,49 @@ class ShardedGallery:
         if self.world > 1:
             dist.all_reduce(hist, op=dist.ReduceOp.SUM, group=self.group)
         return self.ops.roc_finalize(hist, thr)
+
+    def fit_whitening(self, dim_out: int | None = None, *, power: float = 0.5, ridge: float = 1e-5):
+        """``Whitening`` fitted on the WHOLE gallery.  Moment sums are additive: each rank takes the float64 moments of its
+        shard (an empty shard contributes zeros), ONE all_gather of the packed ``[n, sum, outer]`` vector (1 + D + D^2 float64
+        per rank) brings them to every rank, they are added in rank order and ``Whitening.from_moments`` runs on every rank:
+        all ranks hold the same bits.  world_size == 1 makes no collective call."""
+        from .whitening import Whitening
+        D = self.dim
+        n_local = self.local.shape[0]
+        packed = torch.zeros(1 + D + D * D, dtype=torch.float64, device=self.device)
+        if n_local:
+            s, o = self.ops.moments(self.local, gallery_f16=self.gallery_f16)
+            packed[0] = float(n_local)
+            packed[1: 1 + D] = s.to(self.device, torch.float64)
+            packed[1 + D:] = o.to(self.device, torch.float64).reshape(-1)
+        if self.world > 1:
+            flat = torch.empty(self.world * packed.numel(), dtype=torch.float64, device=self.device)    # rank-major concat
+            torch.distributed.all_gather_into_tensor(flat, packed, group=self.group)
+            allm = flat.view(self.world, packed.numel())
+            total = allm[0].clone()
+            for r in range(1, self.world):                        # rank order: the same sum on every rank
+                total += allm[r]
+        else:
+            total = packed
+        total = total.cpu()
+        return Whitening.from_moments(int(total[0].item()), total[1: 1 + D].clone(), total[1 + D:].reshape(D, D).clone(), dim_out,
+                                      power=power, ridge=ridge, normalize_input=True, device=self.device)
+
+    def whitened(self, w) -> "ShardedGallery":
+        """A new ``ShardedGallery`` (same group, labels and dtype; prepared as this one) over the whitening ``w`` of this
+        rank's rows (``Gallery.whitened`` of the shard)."""
+        if self.dim != w.dim_in:
+            raise MI355Error(f"the whitening takes {w.dim_in} columns but the gallery has {self.dim}")
+        if self.gallery_f16 is not None:
+            rows = self.gallery_f16.whitened(w, dtype=torch.float32).data
+            dtype = torch.float16
+        else:
+            rows = torch.empty((self.local.shape[0], w.dim_out), dtype=torch.float32, device=self.device)
+            src = self.local.contiguous()
+            w._apply(src, _rank._DTYPES[torch.float32], src.shape[0], self.dim, False, rows, True)
+            dtype = torch.float32
+        return ShardedGallery(rows, group=self.group, ops=self.ops, labels=self.labels, prepared=self.prepared is not None,
+                              dtype=dtype)
 
     def my_slice(self, Q_local: int) -> slice:
         """Rows of ``search``'s result that belong to this rank's own queries."""

@@ -222,6 +222,38 @@ int mi355_expand_rows(const void* base, int base_dtype, int64_t base_ld, int nor
                       const int64_t* idx, int64_t R, int n, int64_t idx_offset, float alpha, float eps, void* out,
                       int out_dtype, int64_t out_ld, void* workspace, size_t workspace_bytes, void* stream);
 
+/* PCA whitening, the fit's hot path: first and second raw moments of embedding rows in float64.
+ *   sum[i]      = sum_r x[r][i]                 (device double [dim])
+ *   outer[i][j] = sum_r x[r][i] * x[r][j]       (device double [dim][dim], row-major)
+ * x[r] = row r (fp32, or fp16 in the mi355_gallery_to_f16 layout; rows ld >= dim elements apart) or, with normalize_rows (fp32
+ * rows only), l2_normalize_rows(row, eps) with the bits of mi355_l2_normalize_rows.  Elements are widened to float64 (exact),
+ * their products are exact in float64, the sums are float64 (v_mfma_f64_16x16x4_f64): the only rounding is the accumulation.
+ * Only tiles on or above the diagonal are computed and every element is written together with its mirror: outer is exactly
+ * symmetric.  accumulate != 0 adds to what sum / outer hold (a streaming fit), otherwise they are overwritten.
+ * Determinism: the rows are split over workgroups by a rule of (R, dim) alone, the partial tiles are added from the workspace in
+ * split order and there are no floating-point atomics - the same call sequence gives the same bits on every run.
+ * Any 1 <= dim <= 16384, any R >= 0 (R = 0: nothing with accumulate, zeros without; rows may then be NULL).  NaN / Inf propagate.
+ * workspace: mi355_moments_workspace_bytes(R, dim) (0 for R = 0), 16-byte aligned.  Every argument is checked before any HIP call. */
+size_t mi355_moments_workspace_bytes(int64_t R, int dim);
+int mi355_embedding_moments(const void* rows, int rows_dtype, int64_t R, int64_t ld, int dim, int normalize_rows, float eps,
+                            int accumulate, double* sum, double* outer, void* workspace, size_t workspace_bytes, void* stream);
+
+/* PCA whitening, the transform: normalise -> project -> bias -> normalise in one launch.
+ *   x'   = row r of x as it is (fp32, or fp16 gallery rows widened exactly), or with normalize_input (fp32 only)
+ *          l2_normalize_rows(x_r, eps) with the bits of mi355_l2_normalize_rows
+ *   y[j] = bias[j] + sum_i matrix[j][i] * x'[i]: an fp32 fmaf chain that starts from bias[j] and takes i in one fixed order
+ *          (per 8 inputs: 0, 4, 1, 5, 2, 6, 3, 7; v_mfma_f32_32x32x2_f32) that depends neither on R nor on the row's position
+ *   out  = y (normalize_output = 0, MI355_DTYPE_F32), l2_normalize_rows(y, eps) bit for bit (MI355_DTYPE_F32), or fp16 of that
+ *          as mi355_gallery_to_f16 stores it, elements dim_out .. out_ld-1 zeroed (MI355_DTYPE_F16; needs normalize_output).
+ * matrix [dim_out][dim_in] and bias [dim_out] are device fp32, 1 <= dim_out <= dim_in.  A row's output depends only on that
+ * row, the matrix and the bias.  Rows are x_ld / out_ld elements apart; with normalize_output and dim_out % 4 == 0, out is
+ * 16-byte aligned and out_ld % 4 == 0.  workspace: mi355_whiten_workspace_bytes(R, dim_in, dim_out, out_dtype) (fp16 output:
+ * R * dim_out fp32; fp32 output: none, may be NULL).  Every argument is checked before any HIP call; R = 0 does nothing. */
+size_t mi355_whiten_workspace_bytes(int64_t R, int dim_in, int dim_out, int out_dtype);
+int mi355_whiten_rows(const void* x, int x_dtype, int64_t R, int64_t x_ld, int dim_in, int normalize_input, float eps,
+                      const float* matrix, const float* bias, int dim_out, int normalize_output, void* out, int out_dtype,
+                      int64_t out_ld, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Indices outside [lo, hi) become (-inf, -1) in val / idx [n] (the sharded filtered search: slots no shard filled). */
 int mi355_clear_pads(float* val, int64_t* idx, int64_t n, int64_t lo, int64_t hi, void* stream);
 
