@@ -12,6 +12,11 @@ routes the arithmetic to libmi355_retrieval:
 * ``cosine_range`` ............................ the pairs a verification threshold accepts (``score >= threshold``)
 * ``expand_queries`` / ``Gallery.augmented`` .. alpha query expansion and database-side augmentation (not in the reference)
 * ``Gallery.moments`` / ``Gallery.whitened`` .. PCA whitening of a resident gallery (whitening.py; not in the reference)
+
+The gallery side of every search is one ``_Rows`` (buffer, dtype, rows, dim, row stride, normalised or not, optional bf16
+planes): a tensor argument, a ``PreparedGallery``, a ``Gallery`` and a ``ShardedGallery`` shard all become one.  Top-k, range
+and ROC histogram are one function each (``_topk``, ``_range``, ``_roc_hist``) that checks the arguments once and picks the
+fp32 or fp16 C entry from ``_ENTRIES``; the public functions and methods are wrappers that add their own labels.
 """
 from __future__ import annotations
 
@@ -82,12 +87,62 @@ def l2_normalize_rows(x: torch.Tensor, eps: float = _EPS, out: torch.Tensor | No
 
 
 def _check_qg(q, g):
-    if q.dim() != 2 or g.dim() != 2:
+    """Queries against a gallery, a tensor or the ``_Rows`` of a call: both 2-D, the same dim, the same device."""
+    if len(q.shape) != 2 or len(g.shape) != 2:
         raise MI355Error(f"expected (Q,D) queries and (G,D) gallery, got {tuple(q.shape)} and {tuple(g.shape)}")
     if q.shape[1] != g.shape[1]:
         raise MI355Error(f"embedding dims differ: {q.shape[1]} vs {g.shape[1]}")
     if q.device != g.device:
         raise MI355Error(f"queries on {q.device} but gallery on {g.device}")
+
+
+def _row_stride(t: torch.Tensor) -> int:
+    """Elements from one row of a 2-D buffer to the next (a single row has no stride of its own: its width)."""
+    return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
+
+
+class _Rows:
+    """The gallery side of a call: the first ``rows`` rows and ``dim`` columns of ``buf`` - fp32 rows, ``normalized`` or not, or
+    an fp16 gallery buffer (``mi355_gallery_to_f16`` layout: normalised rows, zero padding) - ``ld`` elements apart.
+    ``planes``: the bf16 planes of the same rows (``PreparedGallery``); without ``buf`` they serve the searches they cover."""
+
+    def __init__(self, buf, rows: int, dim: int, normalized: bool, planes: torch.Tensor | None = None):
+        self.buf, self.rows, self.dim, self.normalized, self.planes = buf, int(rows), int(dim), bool(normalized), planes
+        self.shape = (self.rows, self.dim)
+        self.dtype = torch.float32 if buf is None else buf.dtype
+        self.device = planes.device if buf is None else buf.device
+        self.ld = self.dim if buf is None else _row_stride(buf)
+
+    @classmethod
+    def of(cls, gallery, normalized: bool = False) -> "_Rows":
+        """``gallery`` if it is resident rows already, else the fp32 rows of a (G, D) device tensor (no copy if it is one)."""
+        if isinstance(gallery, cls):
+            return gallery
+        g = _f32c(gallery, "gallery")
+        if g.dim() != 2:
+            raise MI355Error(f"expected a (G,D) gallery, got {tuple(g.shape)}")
+        return cls(g, g.shape[0], g.shape[1], normalized)
+
+    @property
+    def data(self) -> torch.Tensor:
+        """The (rows, dim) view of the buffer (fp16: without the row padding)."""
+        return self.buf[: self.rows, : self.dim]
+
+    def c_args(self):
+        """The gallery arguments every search entry takes after (queries, Q): fp16 rows are normalised by their layout."""
+        norm = () if self.dtype == torch.float16 else (int(self.normalized),)
+        return (self.buf.data_ptr(), self.rows, self.dim) + norm
+
+
+# per row dtype, each C entry beside the function that sizes its workspace
+_ENTRIES = {
+    torch.float32: {"topk": ("mi355_rank_topk", "mi355_rank_topk_filtered", "mi355_rank_workspace_bytes"),
+                    "range": ("mi355_cosine_range", "mi355_range_workspace_bytes"),
+                    "roc": ("mi355_roc_pairs_hist", "mi355_roc_pairs_workspace_bytes")},
+    torch.float16: {"topk": ("mi355_rank_topk_f16", "mi355_rank_topk_f16_filtered", "mi355_rank_f16_workspace_bytes"),
+                    "range": ("mi355_cosine_range_f16", "mi355_range_f16_workspace_bytes"),
+                    "roc": ("mi355_roc_pairs_hist_f16", "mi355_roc_pairs_f16_workspace_bytes")},
+}
 
 
 def cosine_scores(queries: torch.Tensor, gallery: torch.Tensor, eps: float = _EPS,
@@ -122,6 +177,16 @@ def _int64_on(t, name: str, n: int, device) -> torch.Tensor:
     if t.dim() != 1 or t.shape[0] != n:
         raise MI355Error(f"{name} must have shape ({n},), got {tuple(t.shape)}")
     return t.to(torch.int64).contiguous()
+
+
+def _need_labels(labels, rows: int, what: str, source: str) -> torch.Tensor:
+    """The labels of ``rows`` resident rows for an operation that cannot do without them (``what``; ``source`` says where
+    they come from): the one check behind ``Gallery`` and ``ShardedGallery``."""
+    if labels is None:
+        raise MI355Error(f"{what} needs {source}")
+    if labels.shape[0] != rows:
+        raise MI355Error(f"{what}: {labels.shape[0]} labels for {rows} rows ({source})")
+    return labels
 
 
 def _rank_filter(Q: int, G: int, device, query_labels, gallery_labels, label_filter, exclude):
@@ -161,10 +226,18 @@ def cosine_topk(queries: torch.Tensor, gallery: torch.Tensor, k: int, eps: float
     query's (``query_labels`` (Q,), ``gallery_labels`` (G,)); ``exclude`` (Q,) int64 leaves out row ``exclude[q]`` (a global
     index, compared with ``row + idx_offset``; negative = none).  Scores and order are those of the unfiltered search on the
     eligible rows; slots beyond the eligible rows hold (-inf, -1)."""
-    q, g = _f32c(queries, "queries"), _f32c(gallery, "gallery")
-    _check_qg(q, g)
-    Q, D = q.shape
-    G = g.shape[0]
+    return _topk(queries, _Rows.of(gallery, gallery_is_normalized), k, eps, idx_offset, query_labels, gallery_labels,
+                 label_filter, exclude)
+
+
+def _topk(queries: torch.Tensor, rows: _Rows, k: int, eps: float = _EPS, idx_offset: int = 0, query_labels=None,
+          gallery_labels=None, label_filter=None, exclude=None):
+    """Top-k of ``queries`` against ``rows``, the one search behind ``cosine_topk``, ``PreparedGallery`` and ``Gallery``: an
+    unfiltered search that the planes cover (``PreparedGallery.supports``) runs on them, every other one on the fp32 or fp16
+    rows (fp16: score = qn . float(row) with fp32 accumulation; order, ties and NaN as ``cosine_topk``)."""
+    q = _f32c(queries, "queries")
+    _check_qg(q, rows)
+    Q, G = q.shape[0], rows.rows
     if k > G or k < 1:
         raise MI355Error(f"selected index k out of range: k={k}, gallery rows={G}")
     filt = _rank_filter(Q, G, q.device, query_labels, gallery_labels, label_filter, exclude)
@@ -172,17 +245,20 @@ def cosine_topk(queries: torch.Tensor, gallery: torch.Tensor, k: int, eps: float
     idx = torch.empty((Q, k), dtype=torch.int64, device=q.device)
     if Q == 0:
         return vals, idx
-    nbytes = lib().mi355_rank_workspace_bytes(Q, G, D, k)
-    ws = _ws.get(q.device, nbytes)
+    on_planes = filt is None and rows.planes is not None and PreparedGallery.supports(Q, k)
+    if not on_planes and rows.buf is None:
+        raise MI355Error(f"prepared search needs k <= 8 and more than 4 queries (got k={k}, Q={Q}): use cosine_topk on the rows")
+    L = lib()
+    plain, filtered, ws_bytes = _ENTRIES[torch.float32 if on_planes else rows.dtype]["topk"]
+    ws = _ws.get(q.device, getattr(L, ws_bytes)(Q, G, rows.dim, k))
+    out = (vals.data_ptr(), idx.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr(q.device))
     with torch.cuda.device(q.device):
-        if filt is None:
-            check(lib().mi355_rank_topk(q.data_ptr(), Q, g.data_ptr(), G, D, int(gallery_is_normalized), k, eps,
-                                        int(idx_offset), vals.data_ptr(), idx.data_ptr(), ws.data_ptr(), ws.numel(),
-                                        stream_ptr(q.device)))
+        if on_planes:
+            check(L.mi355_rank_topk_prepared(q.data_ptr(), Q, rows.planes.data_ptr(), G, rows.dim, k, eps, int(idx_offset), *out))
+        elif filt is None:
+            check(getattr(L, plain)(q.data_ptr(), Q, *rows.c_args(), k, eps, int(idx_offset), *out))
         else:
-            check(lib().mi355_rank_topk_filtered(q.data_ptr(), Q, g.data_ptr(), G, D, int(gallery_is_normalized), k, eps,
-                                                 int(idx_offset), filt[0], vals.data_ptr(), idx.data_ptr(), ws.data_ptr(),
-                                                 ws.numel(), stream_ptr(q.device)))
+            check(getattr(L, filtered)(q.data_ptr(), Q, *rows.c_args(), k, eps, int(idx_offset), filt[0], *out))
     return vals, idx
 
 
@@ -208,23 +284,9 @@ class PreparedGallery:
         return Q > 4 and 1 <= k <= 8
 
     def search(self, queries: torch.Tensor, k: int, eps: float = _EPS, idx_offset: int = 0):
-        """``cosine_topk(queries, rows, k, gallery_is_normalized=True)`` - same values and indices, bit for bit."""
-        q = _f32c(queries, "queries")
-        if q.dim() != 2 or q.shape[1] != self.dim:
-            raise MI355Error(f"queries must be (Q,{self.dim}), got {tuple(q.shape)}")
-        Q = q.shape[0]
-        if k > self.rows or k < 1:
-            raise MI355Error(f"selected index k out of range: k={k}, gallery rows={self.rows}")
-        if not self.supports(Q, k):
-            raise MI355Error(f"prepared search needs k <= 8 and more than 4 queries (got k={k}, Q={Q}): use cosine_topk on the rows")
-        vals = torch.empty((Q, k), dtype=torch.float32, device=q.device)
-        idx = torch.empty((Q, k), dtype=torch.int64, device=q.device)
-        ws = _ws.get(q.device, lib().mi355_rank_workspace_bytes(Q, self.rows, self.dim, k))
-        with torch.cuda.device(q.device):
-            check(lib().mi355_rank_topk_prepared(q.data_ptr(), Q, self.planes.data_ptr(), self.rows, self.dim, k, eps,
-                                                 int(idx_offset), vals.data_ptr(), idx.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                 stream_ptr(q.device)))
-        return vals, idx
+        """``cosine_topk(queries, rows, k, gallery_is_normalized=True)`` - same values, indices and argument checks, bit for
+        bit - for the shapes ``supports`` covers; any other non-empty query batch raises (the planes alone cannot serve it)."""
+        return _topk(queries, _Rows(None, self.rows, self.dim, True, self.planes), k, eps, idx_offset)
 
 
 def topk(scores: torch.Tensor, k: int, idx_offset: int = 0):
@@ -465,29 +527,6 @@ def _f16_stride(dim: int) -> int:
     return (int(dim) + 63) // 64 * 64
 
 
-def _cosine_topk_f16(queries: torch.Tensor, gallery_f16: torch.Tensor, rows: int, dim: int, k: int, eps: float = _EPS,
-                    idx_offset: int = 0, filt=None):
-    """Top-k of ``queries`` against the first ``rows`` rows of an fp16 gallery buffer (``mi355_gallery_to_f16`` layout:
-    ``(capacity, _f16_stride(dim))`` fp16, normalised rows, zero padding).  score = qn . float(row) with fp32
-    accumulation; order, ties and NaN as ``cosine_topk``."""
-    q = _f32c(queries, "queries")
-    Q = q.shape[0]
-    vals = torch.empty((Q, k), dtype=torch.float32, device=q.device)
-    idx = torch.empty((Q, k), dtype=torch.int64, device=q.device)
-    if Q == 0:
-        return vals, idx
-    ws = _ws.get(q.device, lib().mi355_rank_f16_workspace_bytes(Q, rows, dim, k))
-    with torch.cuda.device(q.device):
-        if filt is None:
-            check(lib().mi355_rank_topk_f16(q.data_ptr(), Q, gallery_f16.data_ptr(), rows, dim, k, eps, int(idx_offset),
-                                            vals.data_ptr(), idx.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr(q.device)))
-        else:
-            check(lib().mi355_rank_topk_f16_filtered(q.data_ptr(), Q, gallery_f16.data_ptr(), rows, dim, k, eps, int(idx_offset),
-                                                     filt[0], vals.data_ptr(), idx.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                     stream_ptr(q.device)))
-    return vals, idx
-
-
 # ---- alpha query expansion (alpha-QE) and database-side augmentation (DBA): Radenovic, Tolias and Chum, TPAMI 2018
 def _qe_args(n, alpha):
     """(n, alpha) checked: n an integer >= 1, alpha a finite float >= 0."""
@@ -548,16 +587,14 @@ def expand_queries(queries: torch.Tensor, gallery: torch.Tensor, n: int, alpha: 
     sum).  The sum is fp32 in rank order, the normalisation that of ``l2_normalize_rows`` bit for bit; every row depends
     only on its own query and neighbours (no atomics).  One HIP launch (``mi355_expand_rows``).  Returns (Q, D) fp32."""
     n, alpha = _qe_args(n, alpha)
-    q, g = _f32c(queries, "queries"), _f32c(gallery, "gallery")
-    _check_qg(q, g)
+    q, rows = _f32c(queries, "queries"), _Rows.of(gallery, gallery_is_normalized)
+    _check_qg(q, rows)
     Q, D = q.shape
     if Q == 0:
         return torch.empty((0, D), dtype=torch.float32, device=q.device)
-    vals, idx = cosine_topk(q, g, n, eps, gallery_is_normalized=gallery_is_normalized, idx_offset=idx_offset,
-                            query_labels=query_labels, gallery_labels=gallery_labels, label_filter=label_filter,
-                            exclude=exclude)
-    rows = g if gallery_is_normalized else l2_normalize_rows(g, eps)
-    return _expand_rows(q, True, rows, torch.float32, rows.shape[0], D, vals, idx, alpha, eps, idx_offset)
+    vals, idx = _topk(q, rows, n, eps, idx_offset, query_labels, gallery_labels, label_filter, exclude)
+    g = rows.buf if gallery_is_normalized else l2_normalize_rows(rows.buf, eps)
+    return _expand_rows(q, True, g, torch.float32, g.shape[0], D, vals, idx, alpha, eps, idx_offset)
 
 
 class Gallery:
@@ -581,6 +618,7 @@ class Gallery:
         self._ld = _f16_stride(self.dim) if dtype == torch.float16 else self.dim
         self._buf = torch.empty((max(capacity, 0), self._ld), dtype=dtype, device=self.device)
         self.labels = None
+        self._prepared, self._prepared_rows = None, 0
 
     def _reserve(self, n):
         if n > self._buf.shape[0]:
@@ -611,14 +649,20 @@ class Gallery:
     @property
     def data(self) -> torch.Tensor:
         """The (rows, dim) normalised rows (a view; for fp16 without the row padding)."""
-        if self.dtype == torch.float16:
-            return self._buf[: self.rows, : self.dim]
-        return self._buf[: self.rows]
+        return self._resident().data
+
+    def _resident(self) -> _Rows:
+        """The rows as the gallery side of a call, with the planes of ``prepare()`` while no row was added since."""
+        fresh = self._prepared is not None and self._prepared_rows == self.rows
+        return _Rows(self._buf, self.rows, self.dim, True, self._prepared.planes if fresh else None)
+
+    def _labels_for(self, what: str) -> torch.Tensor:
+        return _need_labels(self.labels, self.rows, what, "gallery labels: add(embeddings, labels)")
 
     @property
     def nbytes(self) -> int:
         """Resident footprint in bytes: the row buffer at its current capacity, plus the bf16 planes of ``prepare()``."""
-        p = getattr(self, "_prepared", None)
+        p = self._prepared
         return self._buf.numel() * self._buf.element_size() + (p.planes.numel() if p is not None else 0)
 
     def __len__(self):
@@ -645,24 +689,8 @@ class Gallery:
             n, alpha = _qe_pair(qe)
             filt = dict(query_labels=query_labels, label_filter=label_filter, exclude=exclude)
             return self.search(self.expand_queries(queries, n, alpha, idx_offset, **filt), k, idx_offset, **filt)
-        filtered = label_filter is not None or exclude is not None
-        if label_filter is not None and self.labels is None:
-            raise MI355Error(f'label_filter="{label_filter}" needs gallery labels: add(embeddings, labels)')
-        if self.labels is not None and label_filter is not None and self.labels.shape[0] != self.rows:
-            raise MI355Error(f"the gallery holds {self.labels.shape[0]} labels for {self.rows} rows")
-        if self.dtype == torch.float16:
-            q = _f32c(queries, "queries")
-            _check_qg(q, self.data)
-            if k > self.rows or k < 1:
-                raise MI355Error(f"selected index k out of range: k={k}, gallery rows={self.rows}")
-            filt = _rank_filter(q.shape[0], self.rows, q.device, query_labels, self.labels, label_filter, exclude)
-            return _cosine_topk_f16(q, self._buf, self.rows, self.dim, k, self.eps, idx_offset, filt)
-        p = getattr(self, "_prepared", None)
-        if (not filtered and p is not None and self._prepared_rows == self.rows
-                and PreparedGallery.supports(queries.shape[0], k)):
-            return p.search(queries, k, self.eps, idx_offset)
-        return cosine_topk(queries, self.data, k, self.eps, gallery_is_normalized=True, idx_offset=idx_offset,
-                           query_labels=query_labels, gallery_labels=self.labels, label_filter=label_filter, exclude=exclude)
+        gl = None if label_filter is None else self._labels_for(f'label_filter="{label_filter}"')
+        return _topk(queries, self._resident(), k, self.eps, idx_offset, query_labels, gl, label_filter, exclude)
 
     def expand_queries(self, queries: torch.Tensor, n: int, alpha: float = 3.0, idx_offset: int = 0, *,
                        query_labels: torch.Tensor | None = None, label_filter: str | None = None,
@@ -673,7 +701,7 @@ class Gallery:
         (``mi355_expand_rows``).  Returns (Q, dim) fp32."""
         n, alpha = _qe_args(n, alpha)
         q = _f32c(queries, "queries")
-        _check_qg(q, self.data)
+        _check_qg(q, self._resident())
         if q.shape[0] == 0:
             return torch.empty((0, self.dim), dtype=torch.float32, device=q.device)
         vals, idx = self.search(q, n, idx_offset, query_labels=query_labels, label_filter=label_filter, exclude=exclude)
@@ -683,8 +711,8 @@ class Gallery:
         """Database-side augmentation: a NEW gallery (same dtype, dim, eps and labels; unprepared) whose row r is
         ``l2_normalize_rows(row_r + sum_j v_j^alpha * row(i_j))`` over the top-n of row r against this gallery with row r
         itself left out (``exclude=arange``), every sum taken from the ORIGINAL rows; fp16 rows are stored as ``add`` would
-        store that fp32 row.  The self-join runs ``block`` rows at a time through this gallery's own search (fp32 rows:
-        ``cosine_topk``; fp16: the f16 kernel), each block followed by one expansion launch.  This gallery is not changed."""
+        store that fp32 row.  The self-join runs ``block`` rows at a time through ``search``, each block followed by one
+        expansion launch.  This gallery is not changed."""
         n, alpha = _qe_args(n, alpha)
         G = self.rows
         out = Gallery(self.dim, self.device, capacity=G, eps=self.eps, dtype=self.dtype)
@@ -697,13 +725,8 @@ class Gallery:
         for q0 in range(0, G, block):
             qn = min(block, G - q0)
             ex = torch.arange(q0, q0 + qn, dtype=torch.int64, device=self.device)
-            rows = self._buf[q0: q0 + qn]
-            if self.dtype == torch.float16:
-                filt = _rank_filter(qn, G, self.device, None, None, None, ex)
-                vals, idx = _cosine_topk_f16(rows[:, : self.dim].float(), self._buf, G, self.dim, n, self.eps, 0, filt)
-            else:
-                vals, idx = cosine_topk(rows, self.data, n, self.eps, gallery_is_normalized=True, exclude=ex)
-            _expand_rows(rows, False, self._buf, self.dtype, G, self.dim, vals, idx, alpha, self.eps, 0,
+            vals, idx = self.search(self.data[q0: q0 + qn], n, exclude=ex)
+            _expand_rows(self._buf[q0: q0 + qn], False, self._buf, self.dtype, G, self.dim, vals, idx, alpha, self.eps, 0,
                          out=out._buf[q0: q0 + qn])
         out.rows = G
         return out
@@ -723,9 +746,7 @@ class Gallery:
             raise MI355Error(f"the whitening takes {w.dim_in} columns but the gallery has {self.dim}")
         out = Gallery(w.dim_out, self.device, capacity=self.rows, eps=self.eps, dtype=self.dtype if dtype is None else dtype)
         out.labels = None if self.labels is None else self.labels.clone()
-        if self.rows:
-            ld = int(self._buf.stride(0)) if self._buf.shape[0] > 1 else self._ld
-            w._apply(self._buf, _DTYPES[self.dtype], self.rows, ld, False, out._buf[: self.rows], True)
+        w._apply(self._resident(), False, out._buf[: self.rows], True)
         out.rows = self.rows
         return out
 
@@ -735,46 +756,19 @@ class Gallery:
         """``cosine_range`` of ``queries`` against the resident rows: every row whose score is >= ``threshold``, with the
         scores of this gallery's own kernel (fp32 rows: ``cosine_scores`` of the normalised rows, a prepared gallery
         included; fp16 rows: the f16-MFMA kernel).  ``label_filter`` uses the labels given to ``add``."""
-        if label_filter is not None and self.labels is None:
-            raise MI355Error(f'label_filter="{label_filter}" needs gallery labels: add(embeddings, labels)')
-        if self.labels is not None and label_filter is not None and self.labels.shape[0] != self.rows:
-            raise MI355Error(f"the gallery holds {self.labels.shape[0]} labels for {self.rows} rows")
-        if self.dtype != torch.float16:
-            return cosine_range(queries, self.data, threshold, eps=self.eps, gallery_is_normalized=True, idx_offset=idx_offset,
-                                query_labels=query_labels, gallery_labels=self.labels, label_filter=label_filter,
-                                exclude=exclude, max_results=max_results)
-        q = _f32c(queries, "queries")
-        _check_qg(q, self.data)
-        t = _range_threshold(threshold)
-        filt = _rank_filter(q.shape[0], self.rows, q.device, query_labels, self.labels, label_filter, exclude)
-        return _range(q, self._buf, self.rows, t, idx_offset, filt, max_results, self.eps, f16_dim=self.dim)
-
-    def _roc_labels(self):
-        if self.labels is None:
-            raise MI355Error("verification_roc needs gallery labels: add(embeddings, labels)")
-        if self.labels.shape[0] != self.rows:
-            raise MI355Error(f"the gallery holds {self.labels.shape[0]} labels for {self.rows} rows")
-
-    def _roc_hist(self, queries, query_labels, thr, exclude=None, idx_offset: int = 0):
-        """The pair histogram of ``queries`` against the resident rows and their labels (ShardedGallery's local step)."""
-        self._roc_labels()
-        q = _f32c(queries, "queries")
-        _check_qg(q, self.data)
-        ql = _int64_on(query_labels, "query_labels", q.shape[0], q.device)
-        ex = None if exclude is None else _int64_on(exclude, "exclude", q.shape[0], q.device)
-        if self.dtype == torch.float16:
-            return _roc_pairs_hist(q, ql, self._buf, self.rows, self.labels, ex, idx_offset, thr, self.eps, f16_dim=self.dim)
-        return _roc_pairs_hist(q, ql, self.data, self.rows, self.labels, ex, idx_offset, thr, self.eps, gallery_is_normalized=True)
+        gl = None if label_filter is None else self._labels_for(f'label_filter="{label_filter}"')
+        return _range(queries, self._resident(), threshold, self.eps, idx_offset, query_labels, gl, label_filter, exclude,
+                      max_results)
 
     def verification_roc(self, queries: torch.Tensor, query_labels: torch.Tensor, thresholds=None,
                          exclude: torch.Tensor | None = None):
         """``verification_roc`` of ``queries`` against the resident rows and the labels given to ``add``.  Each pair's score
         has the bits of this gallery's own search (fp32 rows: ``cosine_scores`` of its normalised rows; fp16 rows: the
         f16-MFMA kernel)."""
-        self._roc_labels()
+        gl = self._labels_for("verification_roc")
         require_cuda(queries, "queries")
         thr = _roc_thresholds(thresholds, self.device)
-        return _roc_finalize(self._roc_hist(queries, query_labels, thr, exclude), thr)
+        return _roc_finalize(_roc_hist(queries, query_labels, self._resident(), gl, exclude, 0, thr, self.eps), thr)
 
 
 def clear_pads(vals: torch.Tensor, idx: torch.Tensor, lo: int, hi: int):
@@ -953,28 +947,28 @@ def roc_curve(scores: torch.Tensor, actual: torch.Tensor, thresholds=None):
     return _roc_finalize(hist, thr)
 
 
-def _roc_pairs_hist(q: torch.Tensor, ql: torch.Tensor, gallery: torch.Tensor, G: int, gl: torch.Tensor, exclude, idx_offset: int,
-                    thr, eps: float = _EPS, gallery_is_normalized: bool = False, f16_dim: int | None = None) -> torch.Tensor:
-    """The (2, T + 1) int64 pair histogram of queries ``q`` (Q, D) against ``G`` gallery rows: fp32 rows ``gallery`` (G, D), or
-    with ``f16_dim`` an fp16 gallery buffer (mi355_gallery_to_f16 layout).  Arguments checked by the caller."""
+def _roc_hist(queries: torch.Tensor, query_labels, rows: _Rows, gallery_labels, exclude, idx_offset: int, thr,
+              eps: float = _EPS) -> torch.Tensor:
+    """The (2, T + 1) int64 pair histogram of ``queries`` and their labels against ``rows`` and theirs (row j is global row
+    ``j + idx_offset`` for ``exclude``): the one entry behind ``verification_roc``, ``Gallery`` and ``ShardedGallery``."""
+    q = _f32c(queries, "queries")
+    _check_qg(q, rows)
+    Q, G = q.shape[0], rows.rows
+    ql = _int64_on(query_labels, "query_labels", Q, q.device)
+    gl = _int64_on(gallery_labels, "gallery_labels", G, q.device)
+    ex = None if exclude is None else _int64_on(exclude, "exclude", Q, q.device)
     host, dev = thr
     T = host.shape[0]
-    Q, D = q.shape
     if Q == 0 or G == 0:
         return torch.zeros((2, T + 1), dtype=torch.int64, device=q.device)
     hist = torch.empty((2, T + 1), dtype=torch.int64, device=q.device)        # (zeroed by the call)
-    ex = exclude.data_ptr() if exclude is not None else None
+    L = lib()
+    entry, ws_bytes = _ENTRIES[rows.dtype]["roc"]
+    ws = _ws.get(q.device, getattr(L, ws_bytes)(Q, G, rows.dim))
     with torch.cuda.device(q.device):
-        if f16_dim is None:
-            ws = _ws.get(q.device, lib().mi355_roc_pairs_workspace_bytes(Q, G, D))
-            check(lib().mi355_roc_pairs_hist(q.data_ptr(), Q, gallery.data_ptr(), G, D, int(gallery_is_normalized), eps,
-                                             ql.data_ptr(), gl.data_ptr(), ex, int(idx_offset), _dptr(host), dev.data_ptr(), T,
-                                             hist.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr(q.device)))
-        else:
-            ws = _ws.get(q.device, lib().mi355_roc_pairs_f16_workspace_bytes(Q, G, f16_dim))
-            check(lib().mi355_roc_pairs_hist_f16(q.data_ptr(), Q, gallery.data_ptr(), G, f16_dim, eps, ql.data_ptr(), gl.data_ptr(),
-                                                 ex, int(idx_offset), _dptr(host), dev.data_ptr(), T, hist.data_ptr(), ws.data_ptr(),
-                                                 ws.numel(), stream_ptr(q.device)))
+        check(getattr(L, entry)(q.data_ptr(), Q, *rows.c_args(), eps, ql.data_ptr(), gl.data_ptr(), ex.data_ptr() if ex is not None else None,
+                                int(idx_offset), _dptr(host), dev.data_ptr(), T, hist.data_ptr(), ws.data_ptr(), ws.numel(),
+                                stream_ptr(q.device)))
     return hist
 
 
@@ -991,24 +985,17 @@ def verification_roc(queries: torch.Tensor, query_labels: torch.Tensor, gallery:
     q = _f32c(queries, "queries")
     if q.dim() != 2:
         raise MI355Error(f"queries must be (Q, D), got {tuple(q.shape)}")
-    Q = q.shape[0]
-    ql = _int64_on(query_labels, "query_labels", Q, q.device)
     if gallery is None:
         if gallery_labels is not None:
             raise MI355Error("gallery_labels given without a gallery (same-source evaluation uses query_labels)")
         if exclude is not None or idx_offset:
             raise MI355Error("same-source evaluation (gallery=None) excludes each query's own row itself: no exclude / idx_offset")
-        g, gl = q, ql
-        ex = torch.arange(Q, dtype=torch.int64, device=q.device)
-    else:
-        g = _f32c(gallery, "gallery")
-        _check_qg(q, g)
-        if gallery_labels is None:
-            raise MI355Error("a gallery needs gallery_labels")
-        gl = _int64_on(gallery_labels, "gallery_labels", g.shape[0], q.device)
-        ex = None if exclude is None else _int64_on(exclude, "exclude", Q, q.device)
+        gallery, gallery_labels = q, query_labels
+        exclude = torch.arange(q.shape[0], dtype=torch.int64, device=q.device)
+    elif gallery_labels is None:
+        raise MI355Error("a gallery needs gallery_labels")
     thr = _roc_thresholds(thresholds, q.device)
-    return _roc_finalize(_roc_pairs_hist(q, ql, g, g.shape[0], gl, ex, idx_offset, thr, eps), thr)
+    return _roc_finalize(_roc_hist(q, query_labels, _Rows.of(gallery), gallery_labels, exclude, idx_offset, thr, eps), thr)
 
 
 # ---- cosine range search: every gallery row at or above a threshold
@@ -1036,33 +1023,31 @@ def _range_empty(Q: int, device) -> RangeResult:
                        torch.empty(0, dtype=torch.float32, device=device))
 
 
-def _range(q: torch.Tensor, gallery: torch.Tensor, G: int, threshold: float, idx_offset: int, filt, max_results, eps: float,
-           gallery_is_normalized: bool = False, f16_dim: int | None = None) -> RangeResult:
-    """The range search of queries ``q`` (Q, D) against ``G`` rows: fp32 rows ``gallery`` (G, D), or with ``f16_dim`` an fp16
-    gallery buffer (mi355_gallery_to_f16 layout).  Arguments checked by the caller.  One search into the cached candidate
-    buffer; if its hits do not fit, ONE more search with exactly that capacity; then the compaction into exact-size outputs."""
-    Q, D = q.shape
+def _range(queries: torch.Tensor, rows: _Rows, threshold: float, eps: float = _EPS, idx_offset: int = 0, query_labels=None,
+           gallery_labels=None, label_filter=None, exclude=None, max_results: int | None = None) -> RangeResult:
+    """The range search of ``queries`` against ``rows``, the one entry behind ``cosine_range``, ``Gallery`` and
+    ``ShardedGallery`` (the planes of a prepared gallery are not used).  One search into the cached candidate buffer; if its
+    hits do not fit, ONE more search with exactly that capacity; then the compaction into exact-size outputs."""
+    q = _f32c(queries, "queries")
+    _check_qg(q, rows)
+    threshold = _range_threshold(threshold)
+    Q, G = q.shape[0], rows.rows
+    filt = _rank_filter(Q, G, q.device, query_labels, gallery_labels, label_filter, exclude)
     if max_results is not None and int(max_results) < 0:
         raise MI355Error(f"max_results must be >= 0 or None, got {max_results}")
     if Q == 0 or G == 0:
         return _range_empty(Q, q.device)
     L = lib()
-    dim = D if f16_dim is None else f16_dim
-    ws = _ws.get(q.device, L.mi355_range_workspace_bytes(Q, G, dim) if f16_dim is None else L.mi355_range_f16_workspace_bytes(Q, G, dim))
+    entry, ws_bytes = _ENTRIES[rows.dtype]["range"]
+    ws = _ws.get(q.device, getattr(L, ws_bytes)(Q, G, rows.dim))
     fp = ctypes.byref(filt[0]) if filt is not None else None
     nnz = ctypes.c_int64(0)
 
     def search(cand):
         cap = cand.numel() // 16
         with torch.cuda.device(q.device):
-            if f16_dim is None:
-                check(L.mi355_cosine_range(q.data_ptr(), Q, gallery.data_ptr(), G, D, int(gallery_is_normalized), eps, threshold,
-                                           int(idx_offset), fp, cand.data_ptr(), cap, ctypes.byref(nnz), ws.data_ptr(), ws.numel(),
-                                           stream_ptr(q.device)))
-            else:
-                check(L.mi355_cosine_range_f16(q.data_ptr(), Q, gallery.data_ptr(), G, f16_dim, eps, threshold, int(idx_offset), fp,
-                                               cand.data_ptr(), cap, ctypes.byref(nnz), ws.data_ptr(), ws.numel(),
-                                               stream_ptr(q.device)))
+            check(getattr(L, entry)(q.data_ptr(), Q, *rows.c_args(), eps, threshold, int(idx_offset), fp, cand.data_ptr(), cap,
+                                    ctypes.byref(nnz), ws.data_ptr(), ws.numel(), stream_ptr(q.device)))
         return cap, int(nnz.value)
 
     cand = _cand.get(q.device, 16 * _MIN_CAPACITY)
@@ -1096,8 +1081,5 @@ def cosine_range(queries: torch.Tensor, gallery: torch.Tensor, threshold: float,
     the result is the same bit for bit on every run.  Filters as in ``cosine_topk`` (``label_filter``, ``exclude``,
     ``idx_offset``).  ``max_results``: raise ``MI355Error`` if there are more hits, before any output is allocated.  One host
     sync per query block (its hit count), as ``torch.nonzero``."""
-    q, g = _f32c(queries, "queries"), _f32c(gallery, "gallery")
-    _check_qg(q, g)
-    t = _range_threshold(threshold)
-    filt = _rank_filter(q.shape[0], g.shape[0], q.device, query_labels, gallery_labels, label_filter, exclude)
-    return _range(q, g, g.shape[0], t, idx_offset, filt, max_results, eps, gallery_is_normalized=gallery_is_normalized)
+    return _range(queries, _Rows.of(gallery, gallery_is_normalized), threshold, eps, idx_offset, query_labels, gallery_labels,
+                  label_filter, exclude, max_results)

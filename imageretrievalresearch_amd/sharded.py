@@ -16,6 +16,15 @@ the one place the hot path has a real exchange step:
      bit for bit.
 
 world_size == 1 never touches torch.distributed.
+
+Each rank holds ONE ``self.shard``.  Under the default backend (``_HipOps``) it is the ``rank._Rows`` that ``_HipOps.shard``
+builds once: the normalised rows as fp32 or fp16, with the bf16 planes when ``prepared=True``; ``rank``'s one function per
+operation picks the kernel from it.  ``self.local`` is its (rows, dim) view, ``self.labels`` the shard's labels (owned here,
+handed to each operation).  The backend interface is ``normalize``, ``local_topk(queries, shard, k, idx_offset, **filter)``,
+``pack``, ``merge_packed``, ``clear_pads``, ``roc_hist``, ``roc_finalize``, ``local_range``, ``qe_slab``, ``expand`` and
+``moments``; a test may inject a CPU backend that implements the ones it drives.  A backend without ``shard`` keeps what its
+``normalize`` returns as the shard, fp32 only.  The filtered search, the range search and the verification ROC share one
+query exchange (``_exchange_queries``), the plain and the filtered search one candidate exchange (``_exchange_candidates``).
 """
 from __future__ import annotations
 
@@ -26,37 +35,36 @@ from ._lib import MI355Error
 
 
 
+_SHARD_LABELS = "the shard labels: ShardedGallery(..., labels=)"
+
+
 class _HipOps:
-    """Default compute backend: the HIP library.  (Tests inject a CPU backend to exercise the
-    collective plumbing under gloo without a GPU; the product path is always this one.)"""
+    """Default compute backend: the HIP library.  ``shard`` builds the resident shard once; every method that takes it in
+    the place of the normalised gallery rows also takes a bare normalised fp32 (rows, dim) tensor there.  (Tests inject a
+    CPU backend to exercise the collective plumbing under gloo without a GPU; the product path is always this one.)"""
 
     @staticmethod
-    def local_topk(queries, gallery_normalized, k, idx_offset, prepared=None, **filt):
-        # filt (filtered searches only): query_labels, gallery_labels, label_filter, exclude - the prepared planes have no
-        # filtered search, the fp32 rows give the same results
-        if not filt and prepared is not None and _rank.PreparedGallery.supports(queries.shape[0], k):
-            return prepared.search(queries, k, idx_offset=idx_offset)
-        return _rank.cosine_topk(queries, gallery_normalized, k, gallery_is_normalized=True, idx_offset=idx_offset, **filt)
+    def shard(local_rows, dtype, prepared):
+        """The shard as ``rank._Rows``: the normalised rows as fp32 or fp16 (half the bytes, searched with the f16 kernel), and
+        with ``prepared`` also the cosine GEMM's bf16 planes (+6 B per element; same results bit for bit)."""
+        g = _rank.Gallery(local_rows.shape[1], local_rows.device, capacity=local_rows.shape[0], dtype=dtype).add(local_rows)
+        return (g.prepare() if prepared else g)._resident()
 
     @staticmethod
-    def roc_hist(queries, query_labels, gallery_normalized, gallery_labels, exclude, idx_offset, thr, gallery_f16=None):
+    def local_topk(queries, shard, k, idx_offset, **filt):
+        # filt (filtered searches only): query_labels, gallery_labels, label_filter, exclude
+        return _rank._topk(queries, _rank._Rows.of(shard, True), k, idx_offset=idx_offset, **filt)
+
+    @staticmethod
+    def roc_hist(queries, query_labels, shard, gallery_labels, exclude, idx_offset, thr):
         """The (2, T + 1) int64 pair histogram of ``queries`` against this shard (rows [idx_offset, ...) of the gallery)."""
-        if gallery_f16 is not None:
-            return gallery_f16._roc_hist(queries, query_labels, thr, exclude, idx_offset)
-        ql = _rank._int64_on(query_labels, "query_labels", queries.shape[0], queries.device)
-        gl = _rank._int64_on(gallery_labels, "gallery_labels", gallery_normalized.shape[0], queries.device)
-        ex = None if exclude is None else _rank._int64_on(exclude, "exclude", queries.shape[0], queries.device)
-        return _rank._roc_pairs_hist(queries, ql, gallery_normalized, gallery_normalized.shape[0], gl, ex, idx_offset, thr,
-                                     gallery_is_normalized=True)
+        return _rank._roc_hist(queries, query_labels, _rank._Rows.of(shard, True), gallery_labels, exclude, idx_offset, thr)
 
     @staticmethod
-    def local_range(queries, gallery_normalized, threshold, idx_offset, gallery_f16=None, **filt):
+    def local_range(queries, shard, threshold, idx_offset, **filt):
         """``cosine_range`` of ``queries`` against this shard (rows [idx_offset, ...) of the gallery): a ``RangeResult`` with
         GLOBAL indices.  filt: query_labels, gallery_labels, label_filter, exclude."""
-        if gallery_f16 is not None:
-            filt.pop("gallery_labels", None)
-            return gallery_f16.range_search(queries, threshold, idx_offset=idx_offset, **filt)
-        return _rank.cosine_range(queries, gallery_normalized, threshold, gallery_is_normalized=True, idx_offset=idx_offset, **filt)
+        return _rank._range(queries, _rank._Rows.of(shard, True), threshold, idx_offset=idx_offset, **filt)
 
     @staticmethod
     def roc_finalize(hist, thr):
@@ -65,15 +73,6 @@ class _HipOps:
     @staticmethod
     def clear_pads(vals, idx, lo, hi):
         return _rank.clear_pads(vals, idx, lo, hi)
-
-    @staticmethod
-    def prepare(gallery_normalized):
-        return _rank.PreparedGallery(gallery_normalized) if gallery_normalized.shape[0] else None
-
-    @staticmethod
-    def gallery_f16(local_rows):
-        return _rank.Gallery(local_rows.shape[1], local_rows.device, capacity=local_rows.shape[0],
-                             dtype=torch.float16).add(local_rows)
 
     @staticmethod
     def pack(vals, idx, Q, k, device):
@@ -101,10 +100,10 @@ class _HipOps:
         return slab
 
     @staticmethod
-    def moments(local_rows, gallery_f16=None):
+    def moments(shard):
         """(sum (D,), outer (D, D)) float64 device tensors of this shard's normalised rows (mi355_embedding_moments)."""
         from .whitening import embedding_moments
-        m = embedding_moments(gallery_f16 if gallery_f16 is not None else local_rows)
+        m = embedding_moments(shard)
         return m.sum, m.outer
 
     @staticmethod
@@ -130,17 +129,16 @@ class ShardedGallery:
             raise MI355Error(f"ShardedGallery dtype must be torch.float32 or torch.float16, got {dtype}")
         if dtype == torch.float16 and prepared:
             raise MI355Error("prepared=True makes bf16 planes of fp32 rows; it does not combine with dtype=torch.float16")
-        # dtype=torch.float16: the shard is kept as an fp16 Gallery (half the bytes) and searched with its kernel
-        self.gallery_f16 = self.ops.gallery_f16(local_rows.float().contiguous()) if dtype == torch.float16 else None
-        if self.gallery_f16 is not None:
-            self.local = self.gallery_f16.data
-        else:
-            self.local = self.ops.normalize(local_rows.float().contiguous()) if local_rows.shape[0] else local_rows.float()
-        self.labels = labels
-        if self.gallery_f16 is not None and labels is not None:
-            self.gallery_f16.labels = labels.to(self.device, torch.int64)
-        # prepared=True: the shard is also kept as the cosine GEMM's bf16 planes (+6 B per element; same results bit for bit)
-        self.prepared = self.ops.prepare(self.local) if (prepared and hasattr(self.ops, "prepare")) else None
+        rows = local_rows.float().contiguous()
+        make = getattr(self.ops, "shard", None)
+        if make is not None:
+            self.shard = make(rows, dtype, prepared)
+            self.local = self.shard.data
+        elif dtype != torch.float32:
+            raise MI355Error(f"dtype={dtype} needs a backend that builds the shard (ops.shard)")
+        else:                                   # an injected backend: its normalised fp32 rows are the shard (no planes)
+            self.shard = self.local = self.ops.normalize(rows) if rows.shape[0] else rows
+        self.labels = None if labels is None else labels.to(self.device, torch.int64)
         if self.world > 1:
             n = torch.tensor([local_rows.shape[0]], dtype=torch.int64, device=self.device)
             allc = torch.empty(self.world, dtype=torch.int64, device=self.device)
@@ -161,72 +159,61 @@ class ShardedGallery:
     def offset(self) -> int:
         return self.offsets[self.rank]
 
-    def _local_topk(self, queries, k):
-        if self.gallery_f16 is not None:
-            return self.gallery_f16.search(queries, k)
-        planes = {} if self.prepared is None else {"prepared": self.prepared}   # (an injected ops may take no prepared=)
-        return self.ops.local_topk(queries, self.local, k, 0, **planes)
+    @property
+    def prepared(self):
+        """The shard's bf16 planes, or None."""
+        return getattr(self.shard, "planes", None)
 
-    def _local_candidates(self, queries, k):
-        """(Q, k, 2) int32: [..., 0] = the f32 score's bits, [..., 1] = LOCAL row index; a short (or empty) shard pads to
-        exactly k slots with {-inf, -1} (one library kernel: mi355_pack_candidates)."""
-        Q = queries.shape[0]
-        kk = min(k, self.local.shape[0])
-        v, i = self._local_topk(queries, kk) if kk > 0 else (None, None)
-        return self.ops.pack(v, i, Q, k, self.device)
-
-    def _filtered_search(self, q, k, query_labels, label_filter, exclude):
-        """Filtered search: every shard searches with its own labels and its offset as idx_offset (so ``exclude`` compares
-        global rows) and packs GLOBAL indices; the merge then adds zero offsets, and slots that no shard filled become
-        (-inf, -1)."""
-        if label_filter is not None and self.labels is None:
-            raise MI355Error(f'label_filter="{label_filter}" needs the shard labels: ShardedGallery(..., labels=)')
-        if self.total_rows >= 2 ** 31 - 128:
-            raise MI355Error("a filtered sharded search carries global int32 indices: the gallery must have fewer than 2^31 rows")
-        Ql = q.shape[0]
-        n_local = self.local.shape[0]
-        if self.labels is not None and label_filter is not None and self.labels.shape[0] != n_local:
-            raise MI355Error(f"the shard holds {self.labels.shape[0]} labels for {n_local} rows")
-        # per-query side of the filter: (Ql, 2) int64 [label, exclude], all-gathered with ONE collective
-        side = torch.full((Ql, 2), -1, dtype=torch.int64, device=self.device)
+    def _check_filter(self, label_filter, query_labels):
+        if label_filter not in (None, "same", "different"):
+            raise MI355Error(f'label_filter must be None, "same" or "different", got {label_filter!r}')
         if label_filter is not None:
+            _rank._need_labels(self.labels, self.local.shape[0], f'label_filter="{label_filter}"', _SHARD_LABELS)
             if query_labels is None:
                 raise MI355Error(f'label_filter="{label_filter}" needs query_labels')
-            side[:, 0] = _rank._int64_on(query_labels, "query_labels", Ql, self.device)
-        if exclude is not None:
-            side[:, 1] = _rank._int64_on(exclude, "exclude", Ql, self.device)
-        dist = torch.distributed
+
+    def _exchange_queries(self, queries_local, query_labels=None, exclude=None, side: bool = True):
+        """The ONE query exchange: (all world*Q_local queries rank-major, their labels or None, their exclude rows or None), the
+        same on every rank.  The per-query side of a filter travels as one (Q_local, 2) int64 [label, exclude] tensor, -1 where
+        not given: one all-gather for the queries and one for the side (``side=False``, the plain search: none for the side);
+        no collective at world_size == 1."""
+        q = queries_local.float().contiguous()
+        Ql = q.shape[0]
+        if side:
+            alls = torch.full((Ql, 2), -1, dtype=torch.int64, device=self.device)
+            for col, t, name in ((0, query_labels, "query_labels"), (1, exclude, "exclude")):
+                if t is None:
+                    continue
+                if (not torch.is_tensor(t) or t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool
+                        or t.dim() != 1 or t.shape[0] != Ql):
+                    raise MI355Error(f"{name} must be an integer tensor of shape ({Ql},)")
+                if t.device != self.device:
+                    raise MI355Error(f"{name} is on {t.device} but the shard on {self.device}")
+                alls[:, col] = t
+        allq = q
         if self.world > 1:
+            dist = torch.distributed
             allq = torch.empty((self.world * Ql, self.dim), dtype=torch.float32, device=self.device)
             dist.all_gather_into_tensor(allq, q, group=self.group)
-            alls = torch.empty((self.world * Ql, 2), dtype=torch.int64, device=self.device)
-            dist.all_gather_into_tensor(alls, side, group=self.group)
-        else:
-            allq, alls = q, side
+            if side:
+                mine, alls = alls, torch.empty((self.world * Ql, 2), dtype=torch.int64, device=self.device)
+                dist.all_gather_into_tensor(alls, mine, group=self.group)
+        return (allq, alls[:, 0].contiguous() if side and query_labels is not None else None,
+                alls[:, 1].contiguous() if side and exclude is not None else None)
+
+    def _exchange_candidates(self, allq, k, idx_offset, shard_offsets, **filt):
+        """The ONE candidate exchange: this shard's top-k of ``allq`` packed as (Q, k, 2) int32 {f32 score bits, row index +
+        idx_offset} (a short or empty shard pads to exactly k slots with {-inf, -1}: mi355_pack_candidates), one all-gather of
+        it (rank-major), then ``shard_offsets`` added and world * k candidates merged per query in one library call
+        (mi355_merge_packed_topk: no torch elementwise kernels on the rank stream)."""
         Q = allq.shape[0]
-        filt = {"label_filter": label_filter}
-        if label_filter is not None:
-            filt.update(query_labels=alls[:, 0].contiguous(), gallery_labels=self.labels)
-        if exclude is not None:
-            filt["exclude"] = alls[:, 1].contiguous()
-        kk = min(k, n_local)
-        if kk > 0:
-            if self.gallery_f16 is not None:
-                v, i = self.gallery_f16.search(allq, kk, self.offset, query_labels=filt.get("query_labels"),
-                                               label_filter=label_filter, exclude=filt.get("exclude"))
-            else:
-                v, i = self.ops.local_topk(allq, self.local, kk, self.offset, **filt)
-        else:
-            v = i = None
-        packed = self.ops.pack(v, i, Q, k, self.device)
+        kk = min(k, self.local.shape[0])
+        v, i = self.ops.local_topk(allq, self.shard, kk, idx_offset, **filt) if kk > 0 else (None, None)
+        allp = self.ops.pack(v, i, Q, k, self.device)
         if self.world > 1:
-            allp = torch.empty((self.world * Q, k, 2), dtype=torch.int32, device=self.device)
-            dist.all_gather_into_tensor(allp, packed, group=self.group)
-        else:
-            allp = packed
-        zeros = torch.zeros(self.world, dtype=torch.int64, device=self.device)
-        vals, idx = self.ops.merge_packed(allp.view(self.world, Q, k, 2), zeros, k)
-        return self.ops.clear_pads(vals, idx, 0, self.total_rows)
+            packed, allp = allp, torch.empty((self.world * Q, k, 2), dtype=torch.int32, device=self.device)
+            torch.distributed.all_gather_into_tensor(allp, packed, group=self.group)
+        return self.ops.merge_packed(allp.view(self.world, Q, k, 2), shard_offsets, k)
 
     def _expand_queries(self, q, n, alpha, query_labels, label_filter, exclude):
         """Alpha query expansion of this rank's queries against the WHOLE gallery, bit for bit that of one ``Gallery`` holding
@@ -253,15 +240,15 @@ class ShardedGallery:
         Returns (values, global indices) for ALL world*Q_local queries, rank-major, on every rank.
 
         Filtered search (see ``cosine_topk``): ``label_filter`` "same" / "different" compares the shards' labels with this
-        rank's ``query_labels`` (Q_local,); ``exclude`` (Q_local,) holds GLOBAL row indices.  Slots no shard could fill are
-        (-inf, -1).
+        rank's ``query_labels`` (Q_local,); ``exclude`` (Q_local,) holds GLOBAL row indices.  Every shard searches with its
+        own labels and its offset as idx_offset (so ``exclude`` compares global rows) and packs GLOBAL indices; the merge then
+        adds zero offsets, and slots that no shard filled become (-inf, -1).
 
         ``qe=(n, alpha)``: alpha query expansion (``Gallery.search``'s ``qe``), the same filter arguments in both rounds; bit for
         bit the result of one ``Gallery`` holding every row.  (Database-side augmentation has no sharded form.)"""
         if k < 1 or k > self.total_rows:
             raise MI355Error(f"selected index k out of range: k={k}, gallery rows={self.total_rows}")
-        if label_filter not in (None, "same", "different"):
-            raise MI355Error(f'label_filter must be None, "same" or "different", got {label_filter!r}')
+        self._check_filter(label_filter, query_labels)
         if qe is not None:
             n, alpha = _rank._qe_pair(qe)
             if n > self.total_rows:
@@ -269,22 +256,18 @@ class ShardedGallery:
             filt = dict(query_labels=query_labels, label_filter=label_filter, exclude=exclude)
             q2 = self._expand_queries(queries_local.float().contiguous(), n, alpha, **filt)
             return self.search(q2, k, **filt)
-        q = queries_local.float().contiguous()
-        if label_filter is not None or exclude is not None:
-            return self._filtered_search(q, k, query_labels, label_filter, exclude)
-        if self.world == 1:
-            return self._local_topk(q, k)
-        dist = torch.distributed
-        Ql = q.shape[0]
-        allq = torch.empty((self.world * Ql, self.dim), dtype=torch.float32, device=self.device)
-        dist.all_gather_into_tensor(allq, q, group=self.group)
-        packed = self._local_candidates(allq, k)
-        Q = allq.shape[0]
-        allp = torch.empty((self.world * Q, k, 2), dtype=torch.int32, device=self.device)   # rank-major concat
-        dist.all_gather_into_tensor(allp, packed, group=self.group)                             # the ONE candidate exchange
-        # unpacking, the shard offsets and the merge of world * k candidates per query: one library call
-        # (mi355_merge_packed_topk), no torch elementwise kernels on the rank stream
-        return self.ops.merge_packed(allp.view(self.world, Q, k, 2), self._offsets_dev, k)
+        if label_filter is None and exclude is None:
+            if self.world == 1:
+                return self.ops.local_topk(queries_local.float().contiguous(), self.shard, k, 0)
+            allq, _, _ = self._exchange_queries(queries_local, side=False)
+            return self._exchange_candidates(allq, k, 0, self._offsets_dev)          # LOCAL indices + the shard offsets
+        if self.total_rows >= 2 ** 31 - 128:
+            raise MI355Error("a filtered sharded search carries global int32 indices: the gallery must have fewer than 2^31 rows")
+        allq, ql, ex = self._exchange_queries(queries_local, query_labels if label_filter is not None else None, exclude)
+        zeros = torch.zeros(self.world, dtype=torch.int64, device=self.device)
+        vals, idx = self._exchange_candidates(allq, k, self.offset, zeros, query_labels=ql, gallery_labels=self.labels,
+                                              label_filter=label_filter, exclude=ex)
+        return self.ops.clear_pads(vals, idx, 0, self.total_rows)
 
     def range_search(self, queries_local: torch.Tensor, threshold: float, *, query_labels: torch.Tensor | None = None,
                      label_filter: str | None = None, exclude: torch.Tensor | None = None, max_results: int | None = None):
@@ -295,47 +278,18 @@ class ShardedGallery:
         ``search``; each rank searches its shard with its offset as idx_offset; the per-query hit counts are all-gathered,
         then the payloads padded to the largest shard's hit count.  A query's hits are its shards' hits in rank order (shard
         offsets ascend with rank: already ascending rows, no merge).  ``max_results`` applies to the whole result."""
-        if label_filter not in (None, "same", "different"):
-            raise MI355Error(f'label_filter must be None, "same" or "different", got {label_filter!r}')
-        if label_filter is not None and self.labels is None:
-            raise MI355Error(f'label_filter="{label_filter}" needs the shard labels: ShardedGallery(..., labels=)')
-        n_local = self.local.shape[0]
-        if self.labels is not None and label_filter is not None and self.labels.shape[0] != n_local:
-            raise MI355Error(f"the shard holds {self.labels.shape[0]} labels for {n_local} rows")
+        self._check_filter(label_filter, query_labels)
         if max_results is not None and int(max_results) < 0:
             raise MI355Error(f"max_results must be >= 0 or None, got {max_results}")
         threshold = _rank._range_threshold(threshold)
-        q = queries_local.float().contiguous()
-        Ql = q.shape[0]
-        if label_filter is not None and query_labels is None:
-            raise MI355Error(f'label_filter="{label_filter}" needs query_labels')
-        side = torch.full((Ql, 2), -1, dtype=torch.int64, device=self.device)
-        for col, t, name in ((0, query_labels if label_filter is not None else None, "query_labels"), (1, exclude, "exclude")):
-            if t is None:
-                continue
-            if not torch.is_tensor(t) or t.dtype.is_floating_point or t.dtype == torch.bool or t.dim() != 1 or t.shape[0] != Ql:
-                raise MI355Error(f"{name} must be an integer tensor of shape ({Ql},)")
-            side[:, col] = t.to(self.device, torch.int64)
-        dist = torch.distributed
-        if self.world > 1:
-            allq = torch.empty((self.world * Ql, self.dim), dtype=torch.float32, device=self.device)
-            dist.all_gather_into_tensor(allq, q, group=self.group)
-            alls = torch.empty((self.world * Ql, 2), dtype=torch.int64, device=self.device)
-            dist.all_gather_into_tensor(alls, side, group=self.group)
-        else:
-            allq, alls = q, side
+        allq, ql, ex = self._exchange_queries(queries_local, query_labels if label_filter is not None else None, exclude)
         Q = allq.shape[0]
-        filt = {"label_filter": label_filter}
-        if label_filter is not None:
-            filt.update(query_labels=alls[:, 0].contiguous(), gallery_labels=self.labels)
-        if exclude is not None:
-            filt["exclude"] = alls[:, 1].contiguous()
-        if n_local:
-            local = self.ops.local_range(allq, self.local, threshold, self.offset, gallery_f16=self.gallery_f16, **filt)
+        dist = torch.distributed
+        if self.local.shape[0]:
+            local = self.ops.local_range(allq, self.shard, threshold, self.offset, query_labels=ql, gallery_labels=self.labels,
+                                         label_filter=label_filter, exclude=ex)
         else:
-            local = _rank.RangeResult(torch.zeros(Q + 1, dtype=torch.int64, device=self.device),
-                                      torch.empty(0, dtype=torch.int64, device=self.device),
-                                      torch.empty(0, dtype=torch.float32, device=self.device))
+            local = _rank._range_empty(Q, self.device)
         counts = local.offsets[1:] - local.offsets[:-1]                                   # (Q,) hits per query in this shard
         if self.world == 1:
             if max_results is not None and local.indices.shape[0] > int(max_results):
@@ -377,34 +331,12 @@ class ShardedGallery:
         ``exclude`` (Q_local,) GLOBAL row indices (negative = none).  The queries, labels and exclude are all-gathered as
         ``search`` does, each rank counts its shard's pairs, and ONE all_reduce(SUM) of the int64 histogram gives every rank
         the same result, bit for bit that of one gallery holding every row."""
-        if self.labels is None:
-            raise MI355Error("verification_roc needs the shard labels: ShardedGallery(..., labels=)")
-        n_local = self.local.shape[0]
-        if self.labels.shape[0] != n_local:
-            raise MI355Error(f"the shard holds {self.labels.shape[0]} labels for {n_local} rows")
-        q = queries_local.float().contiguous()
-        Ql = q.shape[0]
-        side = torch.full((Ql, 2), -1, dtype=torch.int64, device=self.device)
-        for col, t, name in ((0, query_labels_local, "query_labels"), (1, exclude, "exclude")):
-            if t is None:
-                continue
-            if not torch.is_tensor(t) or t.dtype.is_floating_point or t.dim() != 1 or t.shape[0] != Ql:
-                raise MI355Error(f"{name} must be an integer tensor of shape ({Ql},)")
-            side[:, col] = t.to(self.device, torch.int64)
+        gl = _rank._need_labels(self.labels, self.local.shape[0], "verification_roc", _SHARD_LABELS)
+        allq, ql, ex = self._exchange_queries(queries_local, query_labels_local, exclude)
         thr = _rank._roc_thresholds(thresholds, self.device)
-        dist = torch.distributed
+        hist = self.ops.roc_hist(allq, ql, self.shard, gl, ex, self.offset, thr)
         if self.world > 1:
-            allq = torch.empty((self.world * Ql, self.dim), dtype=torch.float32, device=self.device)
-            dist.all_gather_into_tensor(allq, q, group=self.group)
-            alls = torch.empty((self.world * Ql, 2), dtype=torch.int64, device=self.device)
-            dist.all_gather_into_tensor(alls, side, group=self.group)
-        else:
-            allq, alls = q, side
-        ex = alls[:, 1].contiguous() if exclude is not None else None
-        hist = self.ops.roc_hist(allq, alls[:, 0].contiguous(), self.local, self.labels, ex, self.offset, thr,
-                                 gallery_f16=self.gallery_f16)
-        if self.world > 1:
-            dist.all_reduce(hist, op=dist.ReduceOp.SUM, group=self.group)
+            torch.distributed.all_reduce(hist, op=torch.distributed.ReduceOp.SUM, group=self.group)
         return self.ops.roc_finalize(hist, thr)
 
     def fit_whitening(self, dim_out: int | None = None, *, power: float = 0.5, ridge: float = 1e-5):
@@ -417,7 +349,7 @@ class ShardedGallery:
         n_local = self.local.shape[0]
         packed = torch.zeros(1 + D + D * D, dtype=torch.float64, device=self.device)
         if n_local:
-            s, o = self.ops.moments(self.local, gallery_f16=self.gallery_f16)
+            s, o = self.ops.moments(self.shard)
             packed[0] = float(n_local)
             packed[1: 1 + D] = s.to(self.device, torch.float64)
             packed[1 + D:] = o.to(self.device, torch.float64).reshape(-1)
@@ -436,19 +368,14 @@ class ShardedGallery:
 
     def whitened(self, w) -> "ShardedGallery":
         """A new ``ShardedGallery`` (same group, labels and dtype; prepared as this one) over the whitening ``w`` of this
-        rank's rows (``Gallery.whitened`` of the shard)."""
+        rank's rows, fp32 or fp16 read where they lie (one ``mi355_whiten_rows`` launch)."""
         if self.dim != w.dim_in:
             raise MI355Error(f"the whitening takes {w.dim_in} columns but the gallery has {self.dim}")
-        if self.gallery_f16 is not None:
-            rows = self.gallery_f16.whitened(w, dtype=torch.float32).data
-            dtype = torch.float16
-        else:
-            rows = torch.empty((self.local.shape[0], w.dim_out), dtype=torch.float32, device=self.device)
-            src = self.local.contiguous()
-            w._apply(src, _rank._DTYPES[torch.float32], src.shape[0], self.dim, False, rows, True)
-            dtype = torch.float32
+        src = _rank._Rows.of(self.shard, True)
+        rows = torch.empty((src.rows, w.dim_out), dtype=torch.float32, device=self.device)
+        w._apply(src, False, rows, True)
         return ShardedGallery(rows, group=self.group, ops=self.ops, labels=self.labels, prepared=self.prepared is not None,
-                              dtype=dtype)
+                              dtype=src.dtype)
 
     def my_slice(self, Q_local: int) -> slice:
         """Rows of ``search``'s result that belong to this rank's own queries."""

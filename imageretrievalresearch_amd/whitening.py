@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import rank as _rank
-from ._lib import DTYPE_F16, DTYPE_F32, MI355Error, check, lib, require_cuda, stream_ptr
+from ._lib import MI355Error, check, lib, require_cuda, stream_ptr
 
 _EPS = _rank._EPS
 
@@ -27,9 +27,9 @@ class Moments(NamedTuple):
     outer: torch.Tensor       # (D, D) float64, sum_r x[r] x[r]^T, exactly symmetric
 
 
-def _strided_rows(t: torch.Tensor, name: str):
-    """An fp32 (R, D) device tensor as (tensor, ld): rows with unit element stride are used where they lie (ld = row stride
-    >= D), anything else is made contiguous."""
+def _strided_rows(t: torch.Tensor, name: str) -> torch.Tensor:
+    """An fp32 (R, D) device tensor whose rows a kernel can read: rows with unit element stride are used where they lie (row
+    stride >= D), anything else is made contiguous."""
     if not torch.is_tensor(t):
         raise MI355Error(f"{name} must be a tensor or a Gallery, got {type(t).__name__}")
     require_cuda(t, name)
@@ -41,29 +41,30 @@ def _strided_rows(t: torch.Tensor, name: str):
         t = t.float()
     R, D = t.shape
     if R > 1 and D >= 1 and (t.stride(1) == 1 or D == 1) and t.stride(0) >= D:
-        return t, int(t.stride(0))
-    t = t.contiguous()
-    return t, max(int(D), 1)
+        return t
+    return t.contiguous()
 
 
-def _source(rows, name: str):
-    """(buffer, dtype code, R, ld, dim, device) of a tensor or a Gallery (its resident normalised rows, no copy)."""
+def _source(rows, name: str) -> "_rank._Rows":
+    """The rows a moments call reads, where they lie: the resident rows of a Gallery (or of a shard), or a tensor's."""
     if isinstance(rows, _rank.Gallery):
-        buf = rows._buf
-        require_cuda(buf, name)
-        return buf, _rank._DTYPES[rows.dtype], int(rows.rows), int(buf.stride(0)) if buf.shape[0] > 1 else rows._ld, rows.dim, buf.device
-    t, ld = _strided_rows(rows, name)
-    return t, DTYPE_F32, int(t.shape[0]), ld, int(t.shape[1]), t.device
+        rows = rows._resident()
+    if isinstance(rows, _rank._Rows):
+        require_cuda(rows.buf, name)
+        return rows
+    t = _strided_rows(rows, name)
+    return _rank._Rows(t, t.shape[0], t.shape[1], False)
 
 
-def _moments_into(buf, dtype_code, R, ld, dim, normalize, eps, accumulate, s, o):
+def _moments_into(src, normalize, eps, accumulate, s, o):
+    R, dim = src.shape
     if dim < 1:
         raise MI355Error(f"embedding_moments needs dim >= 1, got {dim}")
-    ws = _rank._ws.get(buf.device, max(int(lib().mi355_moments_workspace_bytes(R, dim)), 1))
-    with torch.cuda.device(buf.device):
-        check(lib().mi355_embedding_moments(buf.data_ptr() if R else None, dtype_code, R, ld, dim, int(bool(normalize)), float(eps),
-                                            int(bool(accumulate)), s.data_ptr(), o.data_ptr(), ws.data_ptr(), ws.numel(),
-                                            stream_ptr(buf.device)))
+    ws = _rank._ws.get(src.device, max(int(lib().mi355_moments_workspace_bytes(R, dim)), 1))
+    with torch.cuda.device(src.device):
+        check(lib().mi355_embedding_moments(src.buf.data_ptr() if R else None, _rank._DTYPES[src.dtype], R, src.ld, dim,
+                                            int(bool(normalize)), float(eps), int(bool(accumulate)), s.data_ptr(), o.data_ptr(),
+                                            ws.data_ptr(), ws.numel(), stream_ptr(src.device)))
 
 
 def embedding_moments(rows, *, normalize: bool = False, eps: float = _EPS, out: Moments | None = None) -> Moments:
@@ -71,8 +72,9 @@ def embedding_moments(rows, *, normalize: bool = False, eps: float = _EPS, out: 
     normalised rows, fp32 or fp16).  ``normalize=True`` (fp32 tensors) takes ``l2_normalize_rows(rows, eps)`` - same bits -
     without writing it.  Elements are widened to float64, products and sums are float64 (f64 MFMA); the result is the same
     bits on every run.  ``out=`` (a ``Moments`` of the same D on the same device) is added to: a streaming fit."""
-    buf, code, R, ld, dim, device = _source(rows, "rows")
-    if normalize and code != DTYPE_F32:
+    src = _source(rows, "rows")
+    (R, dim), device = src.shape, src.device
+    if normalize and src.dtype != torch.float32:
         raise MI355Error("normalize=True needs fp32 rows (a Gallery's rows are normalised already)")
     if out is None:
         s = torch.empty((dim,), dtype=torch.float64, device=device)
@@ -84,7 +86,7 @@ def embedding_moments(rows, *, normalize: bool = False, eps: float = _EPS, out: 
             if (not torch.is_tensor(t) or t.dtype != torch.float64 or tuple(t.shape) != shape or t.device != device
                     or not t.is_contiguous()):
                 raise MI355Error(f"out.{nm} must be a contiguous float64 {shape} tensor on {device}")
-    _moments_into(buf, code, R, ld, dim, normalize, eps, out is not None, s, o)
+    _moments_into(src, normalize, eps, out is not None, s, o)
     return Moments(int(n0) + R, s, o)
 
 
@@ -122,7 +124,7 @@ class Whitening:
         if isinstance(rows, _rank.Gallery):
             m = embedding_moments(rows)
         else:
-            t, _ = _strided_rows(rows, "rows")
+            t = _strided_rows(rows, "rows")
             block = max(int(block), 1)
             m = None
             for r0 in range(0, max(t.shape[0], 1), block):
@@ -224,28 +226,30 @@ class Whitening:
         return self
 
     # ---- transform
-    def _apply(self, buf, code, R, ld, normalize_input, out, normalize_output):
-        """One mi355_whiten_rows launch of R rows of ``buf`` into the rows of ``out`` ((R, >= dim_out) fp32 or fp16 gallery rows)."""
+    def _apply(self, src, normalize_input, out, normalize_output):
+        """One mi355_whiten_rows launch of the rows ``src`` (``rank._Rows``, fp32 or fp16) into the rows of ``out`` ((R, >= dim_out)
+        fp32 or fp16 gallery rows)."""
         if self.matrix is None:
             raise MI355Error("this Whitening is not fitted")
         if self.matrix.device != out.device:
             raise MI355Error(f"the whitening lives on {self.matrix.device} but the rows on {out.device}: call .to(device)")
+        R = src.rows
         if R == 0:
             return out
         out_dt = _rank._DTYPES[out.dtype]
         ws = _rank._ws.get(out.device, max(int(lib().mi355_whiten_workspace_bytes(R, self.dim_in, self.dim_out, out_dt)), 1))
-        out_ld = int(out.stride(0)) if out.shape[0] > 1 else int(out.shape[1])
         with torch.cuda.device(out.device):
-            check(lib().mi355_whiten_rows(buf.data_ptr(), code, R, ld, self.dim_in, int(bool(normalize_input)), float(self.eps),
-                                          self.matrix.data_ptr(), self.bias.data_ptr(), self.dim_out, int(bool(normalize_output)),
-                                          out.data_ptr(), out_dt, out_ld, ws.data_ptr(), ws.numel(), stream_ptr(out.device)))
+            check(lib().mi355_whiten_rows(src.buf.data_ptr(), _rank._DTYPES[src.dtype], R, src.ld, self.dim_in,
+                                          int(bool(normalize_input)), float(self.eps), self.matrix.data_ptr(), self.bias.data_ptr(),
+                                          self.dim_out, int(bool(normalize_output)), out.data_ptr(), out_dt, _rank._row_stride(out),
+                                          ws.data_ptr(), ws.numel(), stream_ptr(out.device)))
         return out
 
     def transform(self, x: torch.Tensor, *, normalize_output: bool = True, out: torch.Tensor | None = None) -> torch.Tensor:
         """(R, dim_in) fp32 device rows -> (R, dim_out) fp32: ``l2_normalize_rows(matrix @ x' + bias)`` with x' =
         ``l2_normalize_rows(x)`` when the fit has ``normalize_input`` (both bit for bit the library's normalisation), fp32
         products and accumulation in a fixed order: a row's result does not depend on the batch it is in.  One HIP launch."""
-        t, ld = _strided_rows(x, "x")
+        t = _strided_rows(x, "x")
         if t.shape[1] != self.dim_in:
             raise MI355Error(f"x must be (R, {self.dim_in}), got {tuple(t.shape)}")
         R = int(t.shape[0])
@@ -254,4 +258,4 @@ class Whitening:
         elif (not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (R, self.dim_out)
               or out.device != t.device or not out.is_contiguous()):
             raise MI355Error(f"out must be a contiguous fp32 ({R}, {self.dim_out}) tensor on {t.device}")
-        return self._apply(t, DTYPE_F32, R, ld, self.normalize_input, out, normalize_output)
+        return self._apply(_rank._Rows(t, R, self.dim_in, False), self.normalize_input, out, normalize_output)

@@ -124,3 +124,24 @@ def test_unfiltered_sharded_search_keeps_the_four_argument_local_topk():
     assert calls == [(4, 0)] and v.shape == (6, 4) and i.shape == (6, 4)
     with pytest.raises(MI355Error, match="label_filter must be"):
         gal.search(q, 4, label_filter="other")
+
+
+def test_prepared_search_shares_the_argument_checks_of_cosine_topk(monkeypatch):
+    """PreparedGallery.search runs the checks every search entry runs: queries on another device than the planes are refused
+    (the planes' pointer is never handed to a kernel of another GPU), and an empty query batch gives empty (0, k) results.
+    The object is built without its constructor and the is-it-on-a-GPU check is switched off, so no device is needed; neither
+    case reaches a library call."""
+    monkeypatch.setattr(R, "require_cuda", lambda t, name: None)
+    p = object.__new__(R.PreparedGallery)
+    p.rows, p.dim, p.planes = 100, 8, torch.empty(16, dtype=torch.uint8, device="meta")
+    with pytest.raises(MI355Error, match="queries on cpu but gallery on meta"):
+        p.search(torch.zeros(6, 8), 3)
+    with pytest.raises(MI355Error, match="embedding dims differ"):
+        p.search(torch.zeros(6, 9, device="meta"), 3)
+    p.planes = torch.empty(16, dtype=torch.uint8)
+    v, i = p.search(torch.zeros(0, 8), 3)
+    assert v.shape == (0, 3) and v.dtype == torch.float32 and i.shape == (0, 3) and i.dtype == torch.int64
+    with pytest.raises(MI355Error, match="out of range"):
+        p.search(torch.zeros(0, 8), 101)
+    with pytest.raises(MI355Error, match="more than 4 queries"):
+        p.search(torch.zeros(2, 8), 3)                   # the planes alone cannot serve Q <= 4
