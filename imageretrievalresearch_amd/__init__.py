@@ -15,12 +15,13 @@ from .rank import (ContrastiveLoss, CosineEmbeddingLoss, CosineSimilarity, Galle
                    distinct_class_topn, expand_queries, hit_counts, l2_normalize_rows, merge_topk, pair_cosine,
                    retrieval_accuracy, retrieval_metrics, roc_curve, synth_fill, topk, validation_metrics,
                    verification_roc)
+from .rerank import RerankIndex, k_reciprocal_rerank  # noqa: F401
 from .whitening import Moments, Whitening, embedding_moments  # noqa: F401
 
 __all__ = ["Whitening", "Moments", "embedding_moments","create_model", "list_models", "load_checkpoint", "strip_lightning_prefix", "ContrastiveLoss", "CosineEmbeddingLoss", "validation_metrics", "CosineSimilarity", "Gallery", "PreparedGallery", "cosine_scores",
            "cosine_range", "cosine_topk", "expand_queries", "pair_cosine", "topk", "merge_topk", "hit_counts", "distinct_class_topn",
            "retrieval_metrics", "retrieval_accuracy", "roc_curve", "verification_roc", "cos_sim_score_with_threshold", "cos_sim_score_booster", "l2_normalize_rows", "synth_fill", "ShardedGallery", "MI355Error",
-           "pack_images", "resize_batch"]
+           "pack_images", "resize_batch", "RerankIndex", "k_reciprocal_rerank"]
 
 
 def __getattr__(name):  # lazy: models/sharded import torch.nn / torch.distributed

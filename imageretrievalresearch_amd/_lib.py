@@ -77,6 +77,13 @@ PROTOTYPES = {
     "mi355_expand_rows": (C.c_int, [vp, C.c_int, C.c_int64, C.c_int, vp, C.c_int, C.c_int64, C.c_int64, C.c_int, vp, vp,
                                     C.c_int64, C.c_int, C.c_int64, C.c_float, C.c_float, vp, C.c_int, C.c_int64, vp,
                                     C.c_size_t, vp]),
+    "mi355_kr_sets": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int, vp, C.c_int64, vp, vp, C.c_int64, vp]),
+    "mi355_kr_weights": (C.c_int, [vp, C.c_int, C.c_int64, C.c_int64, vp, C.c_int, C.c_int64, C.c_int64, C.c_int, vp, vp,
+                                   C.c_int64, vp, vp]),
+    "mi355_kr_local_qe": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, vp, vp, vp, C.c_int64, vp, vp, vp, C.c_int64, C.c_int64,
+                                    vp, vp, vp, C.c_int64, vp]),
+    "mi355_kr_score": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int64, vp, vp, vp, C.c_int64, C.c_int64, vp, vp, C.c_int,
+                                 C.c_float, vp, vp]),
     "mi355_moments_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "mi355_embedding_moments": (C.c_int, [vp, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp,
                                           C.c_size_t, vp]),

@@ -12,6 +12,7 @@ routes the arithmetic to libmi355_retrieval:
 * ``cosine_range`` ............................ the pairs a verification threshold accepts (``score >= threshold``)
 * ``expand_queries`` / ``Gallery.augmented`` .. alpha query expansion and database-side augmentation (not in the reference)
 * ``Gallery.moments`` / ``Gallery.whitened`` .. PCA whitening of a resident gallery (whitening.py; not in the reference)
+* ``Gallery.rerank`` / ``Gallery.rerank_index`` k-reciprocal re-ranking on the gallery's kNN graph (rerank.py; not in the reference)
 
 The gallery side of every search is one ``_Rows`` (buffer, dtype, rows, dim, row stride, normalised or not, optional bf16
 planes): a tensor argument, a ``PreparedGallery``, a ``Gallery`` and a ``ShardedGallery`` shard all become one.  Top-k, range
@@ -619,6 +620,7 @@ class Gallery:
         self._buf = torch.empty((max(capacity, 0), self._ld), dtype=dtype, device=self.device)
         self.labels = None
         self._prepared, self._prepared_rows = None, 0
+        self._knn, self._rerank = {}, {}                         # per k1 / (k1, k2); dropped by add
 
     def _reserve(self, n):
         if n > self._buf.shape[0]:
@@ -644,6 +646,7 @@ class Gallery:
             lab = labels.to(self.device, torch.int64)
             self.labels = lab if self.labels is None else torch.cat([self.labels, lab])
         self.rows += n
+        self._knn, self._rerank = {}, {}
         return self
 
     @property
@@ -730,6 +733,35 @@ class Gallery:
                          out=out._buf[q0: q0 + qn])
         out.rows = G
         return out
+
+    def knn_graph(self, k1: int, block: int = 256):
+        """The kNN graph of the resident rows: (vals (rows, k1) fp32, idx (rows, k1) int64), the top-k1 OTHER rows of every row
+        and their scores, as ``search(row, k1, exclude=row)`` orders them (a prepared gallery: on its fp32 rows).  The
+        self-join runs ``block`` rows per search, as ``augmented`` does.  1 <= k1 <= 32, k1 < rows.  Cached per k1 until ``add``."""
+        from . import rerank as _rr
+        k1, _ = _rr.graph_params(self.rows, k1)
+        if k1 not in self._knn:
+            self._knn[k1] = _rr.knn_graph(self, k1, block)
+        return self._knn[k1]
+
+    def rerank_index(self, k1: int = 20, k2: int = 6):
+        """The ``RerankIndex`` of the resident rows for (k1, k2): the kNN graph, tau and the sparse rows V and V' of every
+        gallery row (``nbytes`` tells its size).  Cached until ``add``."""
+        from . import rerank as _rr
+        key = _rr.graph_params(self.rows, k1, k2)
+        if key not in self._rerank:
+            self._rerank[key] = _rr.RerankIndex(self, *key)
+        return self._rerank[key]
+
+    def rerank(self, queries: torch.Tensor, k: int, *, k1: int = 20, k2: int = 6, lam: float = 0.3,
+               shortlist: int | None = None, exclude: torch.Tensor | None = None, idx_offset: int = 0):
+        """k-reciprocal re-ranking (Zhong et al., CVPR 2017; gallery-graph variant, see rerank.py): ``search(queries, shortlist)``
+        re-scored as s* = 1 - ((1 - lam) dJ + lam (1 - s)), dJ the Jaccard distance of the sparse k-reciprocal vectors of the
+        query and the row; returns the top-k of the shortlist by descending s* as (values (Q, k) fp32, indices (Q, k) int64),
+        ties to the earlier shortlist position, pads (-inf, -1) last.  ``shortlist``: k <= shortlist <= min(rows, 1024), default
+        min(rows, max(k, 100)); ``exclude`` / ``idx_offset`` as in ``search``.  ``lam=1`` is the plain search order."""
+        from . import rerank as _rr
+        return _rr.rerank(self, queries, k, k1=k1, k2=k2, lam=lam, shortlist=shortlist, exclude=exclude, idx_offset=idx_offset)
 
     def moments(self):
         """``embedding_moments`` of the resident normalised rows (fp32 or fp16, read where they lie): the input of a PCA

@@ -222,6 +222,45 @@ int mi355_expand_rows(const void* base, int base_dtype, int64_t base_ld, int nor
                       const int64_t* idx, int64_t R, int n, int64_t idx_offset, float alpha, float eps, void* out,
                       int out_dtype, int64_t out_ld, void* workspace, size_t workspace_bytes, void* stream);
 
+/* k-reciprocal re-ranking (Zhong, Zheng, Cao and Li, CVPR 2017), gallery-graph variant: the neighbourhoods of gallery rows are
+ * taken inside the gallery, queries are attached to that graph, d(a, b) = 1 - cos(a, b), and only a shortlist is re-scored.
+ * Inputs are the lists of the library's own search: graph [G][k1] int64 = the top-k1 OTHER rows nn(g) of every gallery row
+ * (a search with exclude = g), tau [G] = the k1-th of their scores.  1 <= k1 <= MI355_KR_MAX_K1, h = (k1 + 1) / 2, nn_h = the
+ * first h of nn.  Sparse rows are CSR: offsets [rows + 1] int64, cols int32 ascending, vals fp32.  No atomics; every sum has
+ * a fixed order that depends on its own row only.  Every argument is checked before any HIP call, every index a kernel reads
+ * is range-checked before it is used (a bad one is skipped), and zero rows do nothing.
+ *
+ * mi355_kr_sets: the expanded reciprocal set R*(r) of each of R rows with neighbour lists `lists` [R][k1] int64.
+ *   gallery rows (list_vals = tau = NULL, R = G, lists = graph): R(g) = {g} + {j in nn(g) : g in nn(j)};
+ *   query rows (list_vals [R][k1] their fp32 scores):            R(q) = {j in nn(q) : list_vals[q][j] >= tau[j]} (may be empty);
+ *   R_h(c) = {c} + {j in nn_h(c) : c in nn_h(j)};   R*(r) = R(r) + every R_h(c), c in R(r), with 3 |R_h(c) & R(r)| > 2 |R_h(c)|
+ *   (candidates and intersections always against the unexpanded R(r)).  At most (k1 + 1) (h + 1) columns per row.
+ *   Two calls: cols = NULL counts and leaves the finished offsets [R + 1]; the caller reads offsets[R], allocates, and calls
+ *   again with cols [cols_capacity] and those offsets to fill (a row that does not fit is not written).
+ * mi355_kr_weights: vals[p] = exp(-d(r, j)) / sum over row r's columns, j = cols[p], d = 1 - s, s the fp32 dot product of row r of
+ *   `rows` and row j of `gallery` (fp32 or fp16 rows, widened exactly, rows_ld / gallery_ld elements apart; both normalised by
+ *   the caller).  For gallery rows pass the gallery as `rows`.  dim <= 8192.
+ * mi355_kr_local_qe: out row r = (1 / k2) (own row r + gallery rows lists[r][0 .. k2 - 2]), a sparse merge summed in that order
+ *   (gallery rows: own = gallery, i.e. the first k2 of [g, nn(g) ...]); 1 <= k2 <= k1 + 1; k2 = 1 copies the own rows bit for bit.
+ *   Two calls as mi355_kr_sets: out_cols = out_vals = NULL counts into out_offsets, the second call fills.
+ * mi355_kr_score: for query q and slot p of its shortlist (shortlist_vals / shortlist_idx [Q][K], a search's output, LOCAL rows):
+ *   m = sum_c min(V'(q)[c], V'(g)[c]), dJ = 1 - m / (2 - m), out[q][p] = 1 - ((1 - lam) dJ + lam (1 - shortlist_vals[q][p])); a
+ *   slot whose row is outside [0, G) gets -inf.  out [Q][K] fp32, 1 <= K <= 1024, 0 <= lam <= 1. */
+#define MI355_KR_MAX_K1 32
+int mi355_kr_sets(const int64_t* lists, const float* list_vals, const float* tau, int64_t R, int k1, const int64_t* graph,
+                  int64_t G, int64_t* offsets, int32_t* cols, int64_t cols_capacity, void* stream);
+int mi355_kr_weights(const void* rows, int rows_dtype, int64_t rows_ld, int64_t R, const void* gallery, int gallery_dtype,
+                     int64_t G, int64_t gallery_ld, int dim, const int64_t* offsets, const int32_t* cols, int64_t nnz,
+                     float* vals, void* stream);
+int mi355_kr_local_qe(const int64_t* lists, int64_t R, int k1, int k2, const int64_t* own_offsets, const int32_t* own_cols,
+                      const float* own_vals, int64_t own_nnz, const int64_t* gallery_offsets, const int32_t* gallery_cols,
+                      const float* gallery_vals, int64_t gallery_nnz, int64_t G, int64_t* out_offsets, int32_t* out_cols,
+                      float* out_vals, int64_t out_capacity, void* stream);
+int mi355_kr_score(const int64_t* query_offsets, const int32_t* query_cols, const float* query_vals, int64_t query_nnz, int64_t Q,
+                   const int64_t* gallery_offsets, const int32_t* gallery_cols, const float* gallery_vals, int64_t gallery_nnz,
+                   int64_t G, const float* shortlist_vals, const int64_t* shortlist_idx, int K, float lam, float* out,
+                   void* stream);
+
 /* PCA whitening, the fit's hot path: first and second raw moments of embedding rows in float64.
  *   sum[i]      = sum_r x[r][i]                 (device double [dim])
  *   outer[i][j] = sum_r x[r][i] * x[r][j]       (device double [dim][dim], row-major)
