@@ -788,6 +788,65 @@ static int launch_win_attn(const bf16_t* qkv, const float* bias_dense, bf16_t* o
     return OK;
 }
 
+// patch_embed.proj.weight [co_n][3][4][4] -> the [48][co_n] fp32 matrix k_patch_embed* read (k = ci*16 + dy*4 + dx), values rounded
+// to bf16.  Shared by the model pack and mi355_swin_patch_embed.
+static void swin_patch_weight(const float* w, int co_n, float* W) {
+    for (int co = 0; co < co_n; ++co)
+        for (int k = 0; k < 48; ++k) W[(size_t)k * co_n + co] = bf_round_host(w[(size_t)co * 48 + k]);
+}
+
+// The uint8 operand block of k_patch_embed*: the SquarePad offsets of an h x w image in the 224 x 224 square (ragged batches take
+// them per image from desc, in the kernel).  Shared by swin_exec and mi355_swin_patch_embed.
+static PatchU8RaggedArgs patch_u8_args(const unsigned char* img, int h, int w, int fill, const float* mean, const float* stdv,
+                                       const int64_t* desc, int b0) {
+    PatchU8RaggedArgs r{};
+    r.img = img; r.h = h; r.w = w; r.hp = (224 - w) / 2; r.vp = (224 - h) / 2; r.fill = fill;
+    for (int c = 0; c < 3; ++c) { r.mean[c] = mean[c]; r.stdv[c] = stdv[c]; }
+    r.desc = desc; r.b0 = b0;
+    return r;
+}
+
+// x: fp32 [nb][3][H][W], or NULL with r.img the uint8 batch (ragged when r.desc is set); out [nb][(H/4)*(W/4)][embed] bf16
+static int launch_patch_embed(const float* x, const PatchU8RaggedArgs& r, int embed, const float* w, const float* bias, const float* g,
+                              const float* be, bf16_t* out, int nb, int H, int W, float eps, hipStream_t st) {
+    const int gw = W / 4, L = gw * (H / 4);
+    MI355_REQUIRE(2 * gw == PE_P, "patch_embed: kernel is laid out for 56 patches per row");
+    MI355_REQUIRE(embed == 128 || embed == 96, "patch_embed: width %d unsupported", embed);
+    const PatchU8Args& u = r;
+    const dim3 grid(cdiv(L, PE_P), nb);
+    const bool w96 = embed == 96;
+    if (!x) {            // uint8 images: SquarePad + ToTensor + Normalize fused into the patch loads (mi355_model_forward_u8)
+        if (r.desc && w96)
+            hipLaunchKernelGGL((k_patch_embed96<true, true>), grid, dim3(256), 0, st, (const float*)nullptr, r, w, bias, g, be, out, H, W,
+                               gw, L, eps);
+        else if (r.desc)
+            hipLaunchKernelGGL((k_patch_embed<true, true>), grid, dim3(256), 0, st, (const float*)nullptr, r, w, bias, g, be, out, H, W,
+                               gw, L, eps);
+        else if (w96)
+            hipLaunchKernelGGL(k_patch_embed96<true>, grid, dim3(256), 0, st, (const float*)nullptr, u, w, bias, g, be, out, H, W, gw, L,
+                               eps);
+        else
+            hipLaunchKernelGGL(k_patch_embed<true>, grid, dim3(256), 0, st, (const float*)nullptr, u, w, bias, g, be, out, H, W, gw, L, eps);
+    } else if (w96) {
+        hipLaunchKernelGGL(k_patch_embed96<false>, grid, dim3(256), 0, st, x, u, w, bias, g, be, out, H, W, gw, L, eps);
+    } else {
+        hipLaunchKernelGGL(k_patch_embed<false>, grid, dim3(256), 0, st, x, u, w, bias, g, be, out, H, W, gw, L, eps);
+    }
+    MI355_LAUNCH_CHECK();
+    return OK;
+}
+
+static int launch_ln_token_mean(const bf16_t* in, const float* g, const float* be, float* pooled, bf16_t* pooled_bf16, int nb, int L,
+                                int C, float eps, hipStream_t st) {
+    MI355_REQUIRE(C == 1024 || C == 768, "token_mean: width %d unsupported", C);
+    if (C == 768)
+        hipLaunchKernelGGL(k_ln_token_mean768, dim3(nb), dim3(256), 0, st, in, g, be, pooled, pooled_bf16, L, eps);
+    else
+        hipLaunchKernelGGL(k_ln_token_mean, dim3(nb), dim3(256), 0, st, in, g, be, pooled, pooled_bf16, L, eps);
+    MI355_LAUNCH_CHECK();
+    return OK;
+}
+
 int swin_pack(Packer& pk, Op& op) {
     auto put_vec = [&](const std::string& name, int n, size_t& off) -> int {
         const TensorSpec* t = pk.get(name);
@@ -804,9 +863,7 @@ int swin_pack(Packer& pk, Op& op) {
             const int co_n = op.cout;   // 128 (swin_base) or 96 (swin_s3_base): [48][co_n]
             MI355_REQUIRE((co_n == 128 || co_n == 96) && w->numel() == co_n * 48, "pack: %s shape", op.w_name.c_str());
             op.w_off = pk.alloc((size_t)48 * co_n * 4);
-            float* W = (float*)(pk.blob.data() + op.w_off);
-            for (int co = 0; co < co_n; ++co)
-                for (int k = 0; k < 48; ++k) W[(size_t)k * co_n + co] = bf_round_host(w->data[(size_t)co * 48 + k]);
+            swin_patch_weight(w->data.data(), co_n, (float*)(pk.blob.data() + op.w_off));
             if (int e = put_vec(op.bias_name, co_n, op.b_off)) return e;
             if (int e = put_vec(op.w2_name, co_n, op.w2_off)) return e;
             return put_vec(op.bias2_name, co_n, op.b2_off);
@@ -840,41 +897,16 @@ int swin_exec(const ModelDef& def, const Op& op, ExecCtx& cx) {
     switch (op.kind) {
         case OP_PATCH_EMBED: {
             MI355_REQUIRE(cx.H == 224 && cx.W == 224, "swin needs 224x224 input");
-            const int gw = cx.W / 4, L = gw * (cx.H / 4);
-            MI355_REQUIRE(2 * gw == PE_P, "patch_embed: kernel is laid out for 56 patches per row");
-            MI355_REQUIRE(op.cout == 128 || op.cout == 96, "patch_embed: width %d unsupported", op.cout);
-            PatchU8RaggedArgs r{};
-            PatchU8Args& u = r;
-            const dim3 grid(cdiv(L, PE_P), cx.nb);
             const float *w = (const float*)cx.w(op.w_off), *bias = (const float*)cx.w(op.b_off), *g = (const float*)cx.w(op.w2_off),
                         *be = (const float*)cx.w(op.b2_off);
             bf16_t* out = (bf16_t*)cx.slot_ptr(op.out);
-            const bool w96 = op.cout == 96;
+            PatchU8RaggedArgs r{};
             if (cx.x_u8) {            // uint8 images: SquarePad + ToTensor + Normalize fused into the patch loads (mi355_model_forward_u8)
                 MI355_REQUIRE(!cx.conv_w, "swin: the conv_input pre-stem belongs to the convolutional backbones");
                 MI355_REQUIRE(std::max(cx.img_h, cx.img_w) == 224, "swin needs images whose longer side is 224 (got %dx%d)", cx.img_h, cx.img_w);
-                u.img = cx.x_u8; u.h = cx.img_h; u.w = cx.img_w; u.hp = (224 - cx.img_w) / 2; u.vp = (224 - cx.img_h) / 2; u.fill = cx.fill;
-                for (int c = 0; c < 3; ++c) { u.mean[c] = cx.mean[c]; u.stdv[c] = cx.stdv[c]; }
-                r.desc = cx.u8_desc; r.b0 = cx.b0;
-                if (cx.u8_desc && w96)
-                    hipLaunchKernelGGL((k_patch_embed96<true, true>), grid, dim3(256), 0, cx.st, (const float*)nullptr, r, w, bias, g, be, out,
-                                       cx.H, cx.W, gw, L, op.ln_eps);
-                else if (cx.u8_desc)
-                    hipLaunchKernelGGL((k_patch_embed<true, true>), grid, dim3(256), 0, cx.st, (const float*)nullptr, r, w, bias, g, be, out,
-                                       cx.H, cx.W, gw, L, op.ln_eps);
-                else if (w96)
-                    hipLaunchKernelGGL(k_patch_embed96<true>, grid, dim3(256), 0, cx.st, (const float*)nullptr, u, w, bias, g, be, out, cx.H,
-                                       cx.W, gw, L, op.ln_eps);
-                else
-                    hipLaunchKernelGGL(k_patch_embed<true>, grid, dim3(256), 0, cx.st, (const float*)nullptr, u, w, bias, g, be, out, cx.H,
-                                       cx.W, gw, L, op.ln_eps);
-            } else if (w96) {
-                hipLaunchKernelGGL(k_patch_embed96<false>, grid, dim3(256), 0, cx.st, cx.x, u, w, bias, g, be, out, cx.H, cx.W, gw, L, op.ln_eps);
-            } else {
-                hipLaunchKernelGGL(k_patch_embed<false>, grid, dim3(256), 0, cx.st, cx.x, u, w, bias, g, be, out, cx.H, cx.W, gw, L, op.ln_eps);
+                r = patch_u8_args(cx.x_u8, cx.img_h, cx.img_w, cx.fill, cx.mean, cx.stdv, cx.u8_desc, cx.b0);
             }
-            MI355_LAUNCH_CHECK();
-            return OK;
+            return launch_patch_embed(cx.x_u8 ? nullptr : cx.x, r, op.cout, w, bias, g, be, out, cx.nb, cx.H, cx.W, op.ln_eps, cx.st);
         }
         case OP_LAYERNORM: {
             const long rows = (long)cx.nb * op.tokens_h * op.tokens_h;
@@ -906,18 +938,9 @@ int swin_exec(const ModelDef& def, const Op& op, ExecCtx& cx) {
                                    cx.nb, op.tokens_h, op.cout, op.heads, op.shift, cx.st);
         }
         case OP_TOKEN_MEAN: {
-            MI355_REQUIRE(op.cin == 1024 || op.cin == 768, "token_mean: width %d unsupported", op.cin);
-            const int L = op.tokens_h * op.tokens_h;
-            const bf16_t* in = (const bf16_t*)cx.slot_ptr(op.in);
-            const float *g = (const float*)cx.w(op.w_off), *be = (const float*)cx.w(op.b_off);
-            float* pooled = (float*)cx.slot_ptr(SLOT_POOLED);
-            bf16_t* pooled_bf16 = (bf16_t*)cx.slot_ptr(SLOT_POOLED_BF16);
-            if (op.cin == 768)
-                hipLaunchKernelGGL(k_ln_token_mean768, dim3(cx.nb), dim3(256), 0, cx.st, in, g, be, pooled, pooled_bf16, L, op.ln_eps);
-            else
-                hipLaunchKernelGGL(k_ln_token_mean, dim3(cx.nb), dim3(256), 0, cx.st, in, g, be, pooled, pooled_bf16, L, op.ln_eps);
-            MI355_LAUNCH_CHECK();
-            return OK;
+            return launch_ln_token_mean((const bf16_t*)cx.slot_ptr(op.in), (const float*)cx.w(op.w_off), (const float*)cx.w(op.b_off),
+                                        (float*)cx.slot_ptr(SLOT_POOLED), (bf16_t*)cx.slot_ptr(SLOT_POOLED_BF16), cx.nb,
+                                        op.tokens_h * op.tokens_h, op.cin, op.ln_eps, cx.st);
         }
         default:
             set_error("exec: unknown op kind %d", (int)op.kind);
@@ -988,4 +1011,92 @@ extern "C" int mi355_window_attention_ws(const void* qkv, const float* bias_tabl
     }
     MI355_CHECK_HIP(hipFree(d));
     return e;
+}
+
+extern "C" int mi355_swin_layernorm(const void* in, const float* gamma, const float* beta, void* out, int64_t rows, int C, int merge, int gh,
+                                    int gw, int stats, float eps, void* stream) {
+    using namespace mi355;
+    MI355_REQUIRE(in && out && (stats || (gamma && beta)), "swin_layernorm: null pointer");
+    MI355_REQUIRE((merge == 0 || merge == 1) && (stats == 0 || stats == 1), "swin_layernorm: merge and stats are 0 or 1");
+    MI355_REQUIRE(!(merge && stats), "swin_layernorm: merge with stats is not instantiated");
+    bool width_ok = false;
+    for (int c : {96, 192, 384, 768, 1536, 128, 256, 512, 1024, 2048}) width_ok |= c == C;
+    MI355_REQUIRE(width_ok, "swin_layernorm: unsupported width %d", C);
+    MI355_REQUIRE(rows >= 1 && rows < ((int64_t)1 << 31), "swin_layernorm: bad shape rows=%lld", (long long)rows);
+    if (merge) {
+        MI355_REQUIRE(gh >= 1 && gw >= 1 && gh <= 16384 && gw <= 16384, "swin_layernorm: bad shape gh=%d gw=%d", gh, gw);
+        MI355_REQUIRE(rows % ((int64_t)gh * gw) == 0, "swin_layernorm: rows=%lld must be a multiple of gh * gw = %d", (long long)rows,
+                      gh * gw);
+    }
+    MI355_REQUIRE(eps > 0.f && eps < 1.f, "swin_layernorm: eps %g out of range", (double)eps);
+    MI355_REQUIRE((uintptr_t)in % 16 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)gamma % 16 == 0 && (uintptr_t)beta % 16 == 0,
+                  "swin_layernorm: pointers must be 16-byte aligned");
+    const hipStream_t st = (hipStream_t)stream;
+    const bf16_t* i = (const bf16_t*)in;
+    bf16_t* o = (bf16_t*)out;
+    if (stats) return launch_ln<false, true>(i, nullptr, nullptr, o, rows, C, 0, 0, eps, st);
+    if (merge) return launch_ln<true>(i, gamma, beta, o, rows, C, gh, gw, eps, st);
+    return launch_ln<false>(i, gamma, beta, o, rows, C, 0, 0, eps, st);
+}
+
+extern "C" int mi355_swin_patch_embed(const float* x, const unsigned char* images, const int64_t* desc_dev, int b0, int B, int H, int h, int w,
+                                      int fill, const float* mean, const float* stdv, const float* weight, const float* bias,
+                                      const float* gamma, const float* beta, int embed, float eps, void* out, void* stream) {
+    using namespace mi355;
+    MI355_REQUIRE(!x != !images, "swin_patch_embed: exactly one of x and images");
+    MI355_REQUIRE(weight && bias && gamma && beta && out, "swin_patch_embed: null pointer");
+    MI355_REQUIRE(embed == 128 || embed == 96, "swin_patch_embed: embed %d (128 or 96)", embed);
+    MI355_REQUIRE(B >= 1 && B <= 65535, "swin_patch_embed: bad shape B=%d", B);
+    MI355_REQUIRE(eps > 0.f && eps < 1.f, "swin_patch_embed: eps %g out of range", (double)eps);
+    if (x) {
+        MI355_REQUIRE(!desc_dev, "swin_patch_embed: desc_dev goes with images");
+        MI355_REQUIRE(H >= 4 && H <= 224 && H % 4 == 0, "swin_patch_embed: H=%d must be a multiple of 4 in [4, 224]", H);
+    } else {
+        MI355_REQUIRE(H == 224, "swin_patch_embed: uint8 images fill the 224 x 224 square (H=%d)", H);
+        MI355_REQUIRE(mean && stdv, "swin_patch_embed: null pointer (mean, stdv)");
+        MI355_REQUIRE(fill >= 0 && fill <= 255, "swin_patch_embed: fill %d out of range", fill);
+        if (desc_dev) MI355_REQUIRE(b0 >= 0, "swin_patch_embed: b0=%d is negative", b0);
+        else MI355_REQUIRE(h >= 1 && w >= 1 && std::max(h, w) == 224, "swin_patch_embed: longer side must be 224 (got %dx%d)", h, w);
+    }
+    MI355_REQUIRE((uintptr_t)x % 16 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)bias % 16 == 0 && (uintptr_t)gamma % 16 == 0 &&
+                      (uintptr_t)beta % 16 == 0 && (uintptr_t)weight % 4 == 0 && (uintptr_t)desc_dev % 8 == 0,
+                  "swin_patch_embed: x, bias, gamma, beta and out must be 16-byte aligned (weight 4, desc_dev 8)");
+    const hipStream_t st = (hipStream_t)stream;
+    std::vector<float> wt((size_t)embed * 48), packed((size_t)embed * 48);
+    std::vector<int64_t> desc(images && desc_dev ? (size_t)B * 3 : 0);
+    MI355_CHECK_HIP(hipMemcpyAsync(wt.data(), weight, wt.size() * 4, hipMemcpyDeviceToHost, st));
+    if (!desc.empty()) MI355_CHECK_HIP(hipMemcpyAsync(desc.data(), desc_dev + (size_t)b0 * 3, desc.size() * 8, hipMemcpyDeviceToHost, st));
+    MI355_CHECK_HIP(hipStreamSynchronize(st));
+    for (size_t b = 0; b < desc.size() / 3; ++b)    // the ragged sizes live on the device: the same rule, after the copy
+        MI355_REQUIRE(desc[3 * b] >= 0 && desc[3 * b + 1] >= 1 && desc[3 * b + 2] >= 1 && std::max(desc[3 * b + 1], desc[3 * b + 2]) == 224,
+                      "swin_patch_embed: longer side must be 224 (image %d is %lldx%lld)", b0 + (int)b, (long long)desc[3 * b + 1],
+                      (long long)desc[3 * b + 2]);
+    swin_patch_weight(wt.data(), embed, packed.data());
+    PatchU8RaggedArgs r{};
+    if (images) r = patch_u8_args(images, h, w, fill, mean, stdv, desc_dev, b0);
+    void* d = nullptr;
+    MI355_CHECK_HIP(hipMalloc(&d, packed.size() * 4));
+    int e = hipMemcpyAsync(d, packed.data(), packed.size() * 4, hipMemcpyHostToDevice, st) == hipSuccess ? OK : ERR_HIP;
+    if (e) set_error("swin_patch_embed: weight upload failed");
+    else e = launch_patch_embed(x, r, embed, (const float*)d, bias, gamma, beta, (bf16_t*)out, B, H, 224, eps, st);
+    if (hipStreamSynchronize(st) != hipSuccess && !e) {
+        set_error("swin_patch_embed: stream synchronisation failed");
+        e = ERR_HIP;
+    }
+    MI355_CHECK_HIP(hipFree(d));
+    return e;
+}
+
+extern "C" int mi355_swin_ln_token_mean(const void* in, const float* gamma, const float* beta, float* pooled, void* pooled_bf16, int B, int L,
+                                        int C, float eps, void* stream) {
+    using namespace mi355;
+    MI355_REQUIRE(in && gamma && beta && pooled && pooled_bf16, "swin_ln_token_mean: null pointer");
+    MI355_REQUIRE(C == 1024 || C == 768, "swin_ln_token_mean: unsupported width %d (1024 or 768)", C);
+    MI355_REQUIRE(B >= 1 && L >= 1, "swin_ln_token_mean: bad shape B=%d L=%d", B, L);
+    MI355_REQUIRE((size_t)B * L * C < ((size_t)1 << 40), "swin_ln_token_mean: tensor too large");
+    MI355_REQUIRE(eps > 0.f && eps < 1.f, "swin_ln_token_mean: eps %g out of range", (double)eps);
+    MI355_REQUIRE((uintptr_t)in % 16 == 0 && (uintptr_t)gamma % 4 == 0 && (uintptr_t)beta % 4 == 0 && (uintptr_t)pooled % 4 == 0 &&
+                      (uintptr_t)pooled_bf16 % 2 == 0,
+                  "swin_ln_token_mean: in must be 16-byte aligned (gamma, beta, pooled 4, pooled_bf16 2)");
+    return launch_ln_token_mean((const bf16_t*)in, gamma, beta, pooled, (bf16_t*)pooled_bf16, B, L, C, eps, (hipStream_t)stream);
 }

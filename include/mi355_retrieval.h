@@ -611,6 +611,35 @@ int mi355_window_attention(const void* qkv, const float* bias_table, void* out, 
 int mi355_window_attention_ws(const void* qkv, const float* bias_table, void* out, int B, int res, int C, int heads, int window,
                               int shift, void* stream);
 
+/* Developer entry: one Swin LayerNorm over the channel dim through the model's launcher (k_layernorm, eps inside the square root).
+ *   merge 0: in [rows][C] bf16.  merge 1: in [rows / (gh*gw)][2*gh][2*gw][C/4] bf16, and row (b, oy, ox) is timm's PatchMerging
+ *            concat [x(2oy, 2ox), x(2oy+1, 2ox), x(2oy, 2ox+1), x(2oy+1, 2ox+1)], gathered on load; rows a multiple of gh*gw.
+ *   stats 0: out [rows][C] bf16 = (x - mean) rstd gamma + beta.  stats 1: out [rows][2] fp32 (mean, rstd), what the
+ *            LayerNorm-folded GEMM epilogue reads as ln_stats; gamma and beta may be NULL.  merge with stats is rejected.
+ *   C is one of 96, 192, 384, 768, 1536, 128, 256, 512, 1024, 2048; gamma, beta fp32 [C]; all pointers 16-byte aligned.
+ * Every argument is checked before any HIP call.  Does not synchronise. */
+int mi355_swin_layernorm(const void* in, const float* gamma, const float* beta, void* out, int64_t rows, int C, int merge, int gh, int gw,
+                         int stats, float eps, void* stream);
+
+/* Developer entry: Swin's patch embedding (4x4 stride-4 conv 3 -> embed, bias, LayerNorm(embed)) through the model's kernels.
+ * Exactly one of x and images is non-null:
+ *   x      fp32 [B][3][H][224], H a multiple of 4 in [4, 224] (the width stays 224: the kernel is laid out for 56 patches a row);
+ *   images uint8 [B][h][w][3] with max(h, w) == 224 and H == 224: SquarePad(fill) -> /255 -> (v - mean) / stdv applied on load
+ *          (mean, stdv HOST float[3]); with desc_dev (device int64 [..][3] = {byte offset into images, h, w}) a ragged packed
+ *          batch whose image b is desc_dev[b0 + b] (h, w unused; every descriptor's longer side must be 224).
+ *   weight fp32 [embed][3][4][4] on the device (timm patch_embed.proj.weight), packed by the model's routine (bf16-rounded,
+ *          transposed); bias, gamma, beta fp32 [embed]; embed 128 or 96; out [B][(H/4)*56][embed] bf16.
+ * Every argument is checked before any HIP call.  Synchronises the stream (the packed weight is a per-call scratch buffer). */
+int mi355_swin_patch_embed(const float* x, const unsigned char* images, const int64_t* desc_dev, int b0, int B, int H, int h, int w,
+                           int fill, const float* mean, const float* stdv, const float* weight, const float* bias, const float* gamma,
+                           const float* beta, int embed, float eps, void* out, void* stream);
+
+/* Developer entry: Swin's final LayerNorm(C) + mean over the L tokens of each image through the model's kernels.
+ *   in [B][L][C] bf16, gamma / beta fp32 [C], pooled [B][C] fp32, pooled_bf16 [B][C] bf16 (the same values rounded once).
+ *   C is 1024 or 768, L >= 1.  Every argument is checked before any HIP call.  Does not synchronise. */
+int mi355_swin_ln_token_mean(const void* in, const float* gamma, const float* beta, float* pooled, void* pooled_bf16, int B, int L, int C,
+                             float eps, void* stream);
+
 /* Inference pre-processing: SquarePad(fill) -> ToTensor -> Normalize, utils/square_pad.py:20-36 +
  * inference/inference.py:48-52.  img: uint8 RGB, HWC (h, w, 3) on the device; mean/std: HOST float[3];
  * out: fp32 (3, S, S) with S = max(h, w), i.e. one image slot of the model's NCHW input batch. */
