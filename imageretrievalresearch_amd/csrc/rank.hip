@@ -557,7 +557,7 @@ __global__ __launch_bounds__(256) void k_pack_candidates(const float* __restrict
     reinterpret_cast<int2*>(packed)[t] = o;
 }
 
-constexpr i64 PACKED_PAD_IDX = (i64)1 << 62;    // "no candidate": sorts behind every real index at equal (-inf) score
+constexpr i64 PACKED_PAD_IDX = NO_CAND_IDX;     // "no candidate" (the selection skips it): a slot no shard filled
 __global__ __launch_bounds__(256) void k_unpack_candidates(const int* __restrict__ packed, const i64* __restrict__ offsets,
                                                            int world, i64 Q, int k, float* __restrict__ cv, i64* __restrict__ ci) {
     const i64 t = (i64)blockIdx.x * 256 + threadIdx.x;      // output slot: query q, candidate (r, j) = r * k + j

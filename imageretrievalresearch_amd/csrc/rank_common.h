@@ -17,6 +17,10 @@ typedef long long i64;
 
 constexpr float NEG_INF = -INFINITY;
 constexpr i64 IDX_PAD = LLONG_MAX;
+// Explicit candidate indices (mi355_merge_topk, the unpacked lists of mi355_merge_packed_topk) at or above this are "no
+// candidate": IDX_PAD itself and the shard pad 1 << 62.  Such an entry's value is ignored and it never takes a slot; the
+// slots that no candidate fills come out as (-inf, IDX_PAD).
+constexpr i64 NO_CAND_IDX = (i64)1 << 62;
 
 constexpr int IDX32_PAD = INT_MAX;   // missing candidate in the fused per-tile lists (local int32 indices)
 

@@ -14,6 +14,7 @@
         if (g < rowlen) {
             sv[j] = v[g];
             si[j] = ix ? ix[g] : g + idx_offset;
+            if (si[j] >= NO_CAND_IDX) { sv[j] = NEG_INF; si[j] = IDX_PAD; }      // explicit "no candidate": whatever its value
             if constexpr (FILT) {
                 if (!eligible(flt.mode, fq_lab, flt.mode != MI355_LABEL_ANY ? flt.glab[g] : 0, fq_ex, g)) {
                     sv[j] = NEG_INF;

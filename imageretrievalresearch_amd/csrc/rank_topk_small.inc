@@ -23,7 +23,7 @@
         if constexpr (FILT) {
             if (!eligible(flt.mode, fq_lab, flt.mode != MI355_LABEL_ANY ? flt.glab[j] : 0, fq_ex, j)) id = IDX_PAD;
         }
-        if (id != IDX_PAD && better(x, id, lv[K - 1], li[K - 1])) {
+        if (id < NO_CAND_IDX && better(x, id, lv[K - 1], li[K - 1])) {      // (IDX_PAD and the shard pad: no candidate)
             lv[K - 1] = x; li[K - 1] = id;
 #pragma unroll
             for (int i = K - 1; i > 0; --i) {

@@ -313,7 +313,11 @@ int mi355_topk_rows(const float* scores, int64_t Q, int64_t G, int k, int64_t id
                     void* stream);
 
 /* Merge per-shard candidates: cand_val/cand_idx [Q][ncand] (ncand = shards*k, any
- * order) -> global top-k with the same ordering rule.  Used after the RCCL all-gather. */
+ * order) -> global top-k with the same ordering rule.  Used after the RCCL all-gather.
+ * The indices of a row's candidates are distinct.  An index >= 2^62 marks "no candidate" (INT64_MAX, what the selection
+ * itself leaves in an empty slot, and the shard pad 1 << 62): its value is ignored, it never takes a slot while a
+ * candidate is left, and with fewer than k candidates the remaining slots are (-inf, INT64_MAX).  A candidate whose value is
+ * -inf is a candidate and comes before every empty slot.  Values come out with the bits they went in with. */
 int mi355_merge_topk(const float* cand_val, const int64_t* cand_idx, int64_t Q, int ncand, int k,
                      float* out_val, int64_t* out_idx, void* workspace, size_t workspace_bytes,
                      void* stream);
@@ -324,7 +328,9 @@ int mi355_merge_topk(const float* cand_val, const int64_t* cand_idx, int64_t Q, 
 int mi355_pack_candidates(const float* val, const int64_t* idx, int64_t Q, int kk, int k, int32_t* packed, void* stream);
 /* Merge of the all-gathered lists packed[world][Q][k][2]: adds shard_offsets[r] (device int64[world]) to rank r's local
  * indices and selects the k best of the world * k candidates of every query (higher score, then lower global index):
- * (Q, k) values + int64 global indices, identical to ranking against the unsharded gallery. */
+ * (Q, k) values + int64 global indices, identical to ranking against the unsharded gallery.  A slot with a negative local
+ * index is no candidate; when the shards hold fewer than k candidates for a query the remaining slots are (-inf, INT64_MAX),
+ * as in mi355_merge_topk (mi355_clear_pads over [0, total rows) turns them into the (-inf, -1) of a filtered search). */
 size_t mi355_merge_packed_workspace_bytes(int64_t Q, int world, int k);
 int mi355_merge_packed_topk(const int32_t* packed, const int64_t* shard_offsets, int world, int64_t Q, int k,
                             float* out_val, int64_t* out_idx, void* workspace, size_t workspace_bytes, void* stream);
