@@ -10,10 +10,10 @@ from . import synth  # noqa: F401
 from ._lib import MI355Error, lib, LIB_PATH  # noqa: F401
 from . import models  # noqa: F401
 from .preprocess import pack_images, resize_batch  # noqa: F401
-from .rank import (ContrastiveLoss, CosineEmbeddingLoss, CosineSimilarity, Gallery, PreparedGallery, cos_sim_score_booster,  # noqa: F401
-                   cos_sim_score_with_threshold, cosine_range, cosine_scores, cosine_topk,
+from .rank import (ContrastiveLoss, CosineEmbeddingLoss, CosineSimilarity, Gallery, PositiveRanks, PreparedGallery,  # noqa: F401
+                   cos_sim_score_booster, cos_sim_score_with_threshold, cosine_range, cosine_scores, cosine_topk,
                    distinct_class_topn, expand_queries, hit_counts, l2_normalize_rows, merge_topk, pair_cosine,
-                   retrieval_accuracy, retrieval_metrics, roc_curve, synth_fill, topk, validation_metrics,
+                   positive_ranks, ranking_metrics, retrieval_accuracy, retrieval_metrics, roc_curve, synth_fill, topk, validation_metrics,
                    verification_roc)
 from .rerank import RerankIndex, k_reciprocal_rerank  # noqa: F401
 from .whitening import Moments, Whitening, embedding_moments  # noqa: F401
@@ -21,7 +21,7 @@ from .whitening import Moments, Whitening, embedding_moments  # noqa: F401
 __all__ = ["Whitening", "Moments", "embedding_moments","create_model", "list_models", "load_checkpoint", "strip_lightning_prefix", "ContrastiveLoss", "CosineEmbeddingLoss", "validation_metrics", "CosineSimilarity", "Gallery", "PreparedGallery", "cosine_scores",
            "cosine_range", "cosine_topk", "expand_queries", "pair_cosine", "topk", "merge_topk", "hit_counts", "distinct_class_topn",
            "retrieval_metrics", "retrieval_accuracy", "roc_curve", "verification_roc", "cos_sim_score_with_threshold", "cos_sim_score_booster", "l2_normalize_rows", "synth_fill", "ShardedGallery", "MI355Error",
-           "pack_images", "resize_batch", "RerankIndex", "k_reciprocal_rerank"]
+           "pack_images", "resize_batch", "RerankIndex", "k_reciprocal_rerank", "PositiveRanks", "positive_ranks", "ranking_metrics"]
 
 
 def __getattr__(name):  # lazy: models/sharded import torch.nn / torch.distributed

@@ -98,6 +98,18 @@ PROTOTYPES = {
     "mi355_cosine_range_f16": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_float, C.c_double, C.c_int64,
                                          C.POINTER(RankFilter), vp, C.c_int64, C.POINTER(C.c_int64), vp, C.c_size_t, vp]),
     "mi355_range_compact": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp, C.c_size_t, vp, vp, vp, vp]),
+    "mi355_positives_range": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_int64,
+                                        C.POINTER(RankFilter), vp, C.c_int64, C.POINTER(C.c_int64), vp, C.c_size_t, vp]),
+    "mi355_positives_range_f16": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_float, C.c_int64,
+                                            C.POINTER(RankFilter), vp, C.c_int64, C.POINTER(C.c_int64), vp, C.c_size_t, vp]),
+    "mi355_rank_positives_keys": (C.c_int, [vp, vp, C.c_int64, C.c_int64, vp, vp]),
+    "mi355_rank_positives_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int]),
+    "mi355_rank_positives": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_float, vp, vp, vp, C.c_int64, vp,
+                                       C.POINTER(C.c_int64), vp, C.c_int64, vp, C.c_int64, vp, C.c_size_t, vp]),
+    "mi355_rank_positives_f16_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int]),
+    "mi355_rank_positives_f16": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_float, vp, vp, vp, C.c_int64, vp,
+                                           C.POINTER(C.c_int64), vp, C.c_int64, vp, C.c_int64, vp, C.c_size_t, vp]),
+    "mi355_rank_positives_finalize": (C.c_int, [vp, vp, C.c_int64, C.c_int64, vp, vp, vp, vp]),
     "mi355_roc_pairs_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int]),
     "mi355_roc_pairs_hist": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_float, vp, vp, vp, C.c_int64,
                                        C.POINTER(C.c_double), vp, C.c_int, vp, vp, C.c_size_t, vp]),

@@ -175,6 +175,20 @@ __global__ __launch_bounds__(256) void k_cos_gemm_range(const float* __restrict_
 #include "rank_gemm_f32.inc"
 }
 
+// The ranks twin (mi355_rank_positives): the same body, the ranks epilogue (its overload takes RanksArgs as `flt`)
+template <int MT, int RK_BK, bool VEC>
+__global__ __launch_bounds__(256) void k_cos_gemm_ranks(const float* __restrict__ Qn, const float* __restrict__ Gal,
+                                                        const float* __restrict__ ginv, int Q, i64 G, int D, int x0, int ntx,
+                                                        int xtiles, int ny, RanksArgs flt) {
+    constexpr int FK = FK_RANKS;
+    constexpr bool FILT = false;
+    float* const S = nullptr;
+    const int k = 0;
+    float* const cand_val = nullptr;
+    int* const cand_idx = nullptr;
+#include "rank_gemm_f32.inc"
+}
+
 // =====================================================================================
 // The same GEMM on the bf16 matrix pipe (three-way split, six products; see split3 above).  Same block / wave tiling and
 // the same epilogue as k_cos_gemm; BK = 16 (one 32x32x16 k-step per K-tile).  Needs 16-byte aligned gallery rows
@@ -230,6 +244,20 @@ __global__ __launch_bounds__(256, 3) void k_cos_gemm_split_range(const bf16_t* _
                                                                  int ntx, int n_steps, const float* __restrict__ zeros, int xtiles,
                                                                  int ny, RangeArgs flt) {
     constexpr int FK = FK_RANGE;
+    constexpr bool FILT = false;
+    float* const S = nullptr;
+    const int k = 0;
+    float* const cand_val = nullptr;
+    int* const cand_idx = nullptr;
+#include "rank_gemm_split.inc"
+}
+
+template <int MT>
+__global__ __launch_bounds__(256, 3) void k_cos_gemm_split_ranks(const bf16_t* __restrict__ Qs, const float* __restrict__ Gal,
+                                                                 const float* __restrict__ ginv, int Q, i64 G, int D, int x0,
+                                                                 int ntx, int n_steps, const float* __restrict__ zeros, int xtiles,
+                                                                 int ny, RanksArgs flt) {
+    constexpr int FK = FK_RANKS;
     constexpr bool FILT = false;
     float* const S = nullptr;
     const int k = 0;
@@ -858,12 +886,13 @@ int whole_round_tiles(int ntx, int ny, int slots) {
 // with 256 x 128 tiles, one per CU).  64-query tiles use BK = 32.
 template <bool VEC>
 struct F32Gemm {
-    static constexpr bool SLAB = true, FILTERED = true, ROC = true, RANGE = true;
+    static constexpr bool SLAB = true, FILTERED = true, ROC = true, RANGE = true, RANKS = true;
     template <int MT> static constexpr int BK = MT == 2 ? 16 : 32;
     template <int MT> static constexpr size_t stage_bytes() { return (size_t)2 * (64 * MT + RK_BN) * (BK<MT> + 4) * sizeof(float); }
     template <int MT, int FK, bool FILT> static const void* kernel() {
         if constexpr (FK == FK_ROC) return (const void*)k_cos_gemm_roc<MT, BK<MT>, VEC>;
         else if constexpr (FK == FK_RANGE) return (const void*)k_cos_gemm_range<MT, BK<MT>, VEC>;
+        else if constexpr (FK == FK_RANKS) return (const void*)k_cos_gemm_ranks<MT, BK<MT>, VEC>;
         else if constexpr (FILT) return (const void*)k_cos_gemm_filt<MT, BK<MT>, VEC, FK>;
         else return (const void*)k_cos_gemm<MT, BK<MT>, VEC, FK>;
     }
@@ -877,6 +906,9 @@ struct F32Gemm {
         else if constexpr (FK == FK_RANGE)
             hipLaunchKernelGGL((k_cos_gemm_range<MT, BK<MT>, VEC>), grid, dim3(256), lds, st, qn, gal, a.ginv, a.Q, a.G, a.D, x0, ntx,
                                xtiles, ny, *a.rng);
+        else if constexpr (FK == FK_RANKS)
+            hipLaunchKernelGGL((k_cos_gemm_ranks<MT, BK<MT>, VEC>), grid, dim3(256), lds, st, qn, gal, a.ginv, a.Q, a.G, a.D, x0, ntx,
+                               xtiles, ny, *a.rnk);
         else if constexpr (FILT)
             hipLaunchKernelGGL((k_cos_gemm_filt<MT, BK<MT>, VEC, FK>), grid, dim3(256), lds, st, qn, gal, a.ginv, a.Q, a.G, a.D, a.k,
                                a.cand_val, a.cand_idx, x0, ntx, xtiles, ny, *a.filt);
@@ -888,13 +920,14 @@ struct F32Gemm {
 
 // Split-bf16 loop (qry: the split planes of the queries, split_rows; gal: fp32 rows with D % 4 == 0)
 struct SplitGemm {
-    static constexpr bool SLAB = true, FILTERED = true, ROC = true, RANGE = true;
+    static constexpr bool SLAB = true, FILTERED = true, ROC = true, RANGE = true, RANKS = true;
     template <int MT> static constexpr size_t stage_bytes() {   // A ring of 2 (3 at MT = 1), B ring of 3
         return (size_t)(MT == 1 ? 3 : 2) * (64 * MT / 32) * 3 * 1024 + (size_t)3 * RK_BN * 16 * sizeof(float);
     }
     template <int MT, int FK, bool FILT> static const void* kernel() {
         if constexpr (FK == FK_ROC) return (const void*)k_cos_gemm_split_roc<MT>;
         else if constexpr (FK == FK_RANGE) return (const void*)k_cos_gemm_split_range<MT>;
+        else if constexpr (FK == FK_RANKS) return (const void*)k_cos_gemm_split_ranks<MT>;
         else if constexpr (FILT) return (const void*)k_cos_gemm_split_filt<MT, FK>;
         else return (const void*)k_cos_gemm_split<MT, FK>;
     }
@@ -910,6 +943,9 @@ struct SplitGemm {
         else if constexpr (FK == FK_RANGE)
             hipLaunchKernelGGL((k_cos_gemm_split_range<MT>), grid, dim3(256), lds, st, qs, gal, a.ginv, a.Q, a.G, a.D, x0, ntx, n_steps,
                                zeros, xtiles, ny, *a.rng);
+        else if constexpr (FK == FK_RANKS)
+            hipLaunchKernelGGL((k_cos_gemm_split_ranks<MT>), grid, dim3(256), lds, st, qs, gal, a.ginv, a.Q, a.G, a.D, x0, ntx, n_steps,
+                               zeros, xtiles, ny, *a.rnk);
         else if constexpr (FILT)
             hipLaunchKernelGGL((k_cos_gemm_split_filt<MT, FK>), grid, dim3(256), lds, st, qs, gal, a.ginv, a.Q, a.G, a.D, a.k,
                                a.cand_val, a.cand_idx, x0, ntx, n_steps, zeros, xtiles, ny, *a.filt);
@@ -921,7 +957,7 @@ struct SplitGemm {
 
 // Prepared gallery (qry: the split planes of the queries; gal: the gallery's planes): fused selection only, unfiltered
 struct PreparedGemm {
-    static constexpr bool SLAB = false, FILTERED = false, ROC = false, RANGE = false;
+    static constexpr bool SLAB = false, FILTERED = false, ROC = false, RANGE = false, RANKS = false;
     template <int MT> static constexpr size_t stage_bytes() {   // A ring of 2 (3 at MT = 1), B ring of 3
         return (size_t)(MT == 1 ? 3 : 2) * (64 * MT / 32) * 3 * 1024 + (size_t)3 * (RK_BN / 32) * 3 * 1024;
     }
@@ -947,13 +983,14 @@ static bool rank_exact_f32() {
 // qs: scratch for the split planes of these Q queries (split_queries_bytes(Q, D)); may be null for Q <= 4.
 // filt (fused selection only; a score slab is unfiltered): the filter of these Q queries.
 // roc (S null): the histogram of these Q queries; always on the tiles (the GEMV's bits differ), any Q.  rng (S null): the
-// range pass of these Q queries, on the tiles as well.
+// range pass of these Q queries, on the tiles as well; rnk (S null): their counting pass for the ranks, likewise.
 static int cos_gemm(const float* qn, bf16_t* qs, const float* gal, const float* ginv, float* S, i64 Q, i64 G, int D,
                     hipStream_t st, int k = 0, float* cand_val = nullptr, int* cand_idx = nullptr,
-                    const RankFilter* filt = nullptr, const RocArgs* roc = nullptr, const RangeArgs* rng = nullptr) {
+                    const RankFilter* filt = nullptr, const RocArgs* roc = nullptr, const RangeArgs* rng = nullptr,
+                    const RanksArgs* rnk = nullptr) {
     const bool vec = vec_ok(qn, D) && vec_ok(gal, D);
     const int fused_bit = cand_val ? MI355_RANK_PATH_FUSED : 0;
-    if (!cand_val && !roc && !rng && Q <= 4 && (size_t)Q * D * sizeof(float) <= 60 * 1024) {
+    if (!cand_val && !roc && !rng && !rnk && Q <= 4 && (size_t)Q * D * sizeof(float) <= 60 * 1024) {
         set_rank_path(MI355_RANK_PATH_GEMV);
         const size_t lds = (size_t)Q * D * sizeof(float);
         const unsigned blocks = (unsigned)(cdiv(G, 4) < 4096 ? cdiv(G, 4) : 4096);
@@ -963,7 +1000,7 @@ static int cos_gemm(const float* qn, bf16_t* qs, const float* gal, const float* 
         MI355_LAUNCH_CHECK();
         return OK;
     }
-    TileArgs a{qn, gal, ginv, S, (int)Q, G, D, k, cand_val, cand_idx, filt, roc, rng};
+    TileArgs a{qn, gal, ginv, S, (int)Q, G, D, k, cand_val, cand_idx, filt, roc, rng, rnk};
     if (qs && vec_ok(gal, D) && !rank_exact_f32()) {
         if (int e = split_rows(qn, Q, D, qs, st)) return e;
         set_rank_path(MI355_RANK_PATH_SPLIT | fused_bit);
@@ -1133,10 +1170,13 @@ size_t mi355_range_workspace_bytes(int64_t Q, int64_t G, int dim) {
     return range_carve(nullptr, Q, G, dim, split_queries_bytes, true).total;
 }
 
-int mi355_cosine_range(const float* queries, int64_t Q, const float* gallery, int64_t G, int dim, int gallery_is_normalized,
-                       float eps, double threshold, int64_t idx_offset, const mi355_rank_filter* filter, void* candidates,
-                       int64_t capacity, int64_t* nnz, void* workspace, size_t workspace_bytes, void* stream) {
-    const char* who = "cosine_range";
+}  // extern "C"
+
+// mi355_cosine_range and, with keep_all, mi355_positives_range, under the name who
+static int cosine_range(const float* queries, int64_t Q, const float* gallery, int64_t G, int dim, int gallery_is_normalized,
+                        float eps, double threshold, int64_t idx_offset, const mi355_rank_filter* filter, void* candidates,
+                        int64_t capacity, int64_t* nnz, void* workspace, size_t workspace_bytes, void* stream, bool keep_all,
+                        const char* who) {
     RankFilter f{};
     if (int e = range_check(queries, Q, gallery, G, dim, threshold, filter, idx_offset, candidates, capacity, nnz, who, &f)) return e;
     const RangeWs w = range_carve(workspace, Q, G, dim, split_queries_bytes, !gallery_is_normalized);
@@ -1146,10 +1186,59 @@ int mi355_cosine_range(const float* queries, int64_t Q, const float* gallery, in
     const float* ginv = gallery_is_normalized ? nullptr : w.w.ginv;
     if (int e = normalize_search(queries, Q, ginv ? gallery : nullptr, G, dim, eps, w.w, st)) return e;
     return range_blocks(Q, G, f, threshold, candidates, capacity, nnz, w, st, [&](i64 q0, i64 qn, const RangeArgs& a) -> int {
-        RoctxRange range("range/cosine gemm + hits");
+        RoctxRange range(keep_all ? "ranks/positives" : "range/cosine gemm + hits");
         return cos_gemm(w.w.qn + q0 * dim, (bf16_t*)w.w.qs, gallery, ginv, nullptr, qn, G, dim, st, 0, nullptr, nullptr, nullptr,
                         nullptr, &a);
-    });
+    }, keep_all);
+}
+
+extern "C" {
+
+int mi355_cosine_range(const float* queries, int64_t Q, const float* gallery, int64_t G, int dim, int gallery_is_normalized,
+                       float eps, double threshold, int64_t idx_offset, const mi355_rank_filter* filter, void* candidates,
+                       int64_t capacity, int64_t* nnz, void* workspace, size_t workspace_bytes, void* stream) {
+    return cosine_range(queries, Q, gallery, G, dim, gallery_is_normalized, eps, threshold, idx_offset, filter, candidates, capacity,
+                        nnz, workspace, workspace_bytes, stream, false, "cosine_range");
+}
+
+int mi355_positives_range(const float* queries, int64_t Q, const float* gallery, int64_t G, int dim, int gallery_is_normalized,
+                          float eps, int64_t idx_offset, const mi355_rank_filter* filter, void* candidates, int64_t capacity,
+                          int64_t* nnz, void* workspace, size_t workspace_bytes, void* stream) {
+    MI355_REQUIRE(filter && filter->label_mode == MI355_LABEL_SAME, "positives_range: needs a filter with MI355_LABEL_SAME");
+    return cosine_range(queries, Q, gallery, G, dim, gallery_is_normalized, eps, 0.0, idx_offset, filter, candidates, capacity, nnz,
+                        workspace, workspace_bytes, stream, true, "positives_range");
+}
+
+size_t mi355_rank_positives_workspace_bytes(int64_t Q, int64_t G, int dim) { return mi355_roc_pairs_workspace_bytes(Q, G, dim); }
+
+int mi355_rank_positives(const float* queries, int64_t Q, const float* gallery, int64_t G, int dim, int gallery_is_normalized,
+                         float eps, const int64_t* query_labels, const int64_t* gallery_labels, const int64_t* exclude,
+                         int64_t idx_offset, const int64_t* offsets, const int64_t* offsets_host, const uint64_t* pos_keys,
+                         int64_t nnz, uint32_t* before, int64_t query_block, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+    const char* who = "rank_positives";
+    RanksArgs rk{};
+    if (int e = ranks_check(queries, Q, gallery, G, dim, query_labels, gallery_labels, exclude, idx_offset, offsets, offsets_host,
+                            pos_keys, nnz, before, query_block, who, &rk))
+        return e;
+    const i64 qb = ranks_query_block(Q, G, query_block);
+    const RankWs w = carve(workspace, Q, G, dim, 0, split_queries_bytes, !gallery_is_normalized, false);
+    const size_t need = mi355_rank_positives_workspace_bytes(Q, G, dim);
+    MI355_REQUIRE(workspace && workspace_bytes >= need, "%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
+    hipStream_t st = (hipStream_t)stream;
+    if (nnz == 0) return OK;                                    // no query has a positive: nothing to count
+    MI355_CHECK_HIP(hipMemsetAsync(before, 0, (size_t)nnz * sizeof(uint32_t), st));
+    const float* ginv = gallery_is_normalized ? nullptr : w.ginv;
+    if (int e = normalize_search(queries, Q, ginv ? gallery : nullptr, G, dim, eps, w, st)) return e;
+    for (i64 q0 = 0; q0 < Q; q0 += qb) {
+        const i64 qn = (Q - q0 < qb) ? Q - q0 : qb;
+        const RanksArgs rb = ranks_from(rk, q0);
+        RoctxRange range("ranks/count");
+        if (int e = cos_gemm(w.qn + q0 * dim, (bf16_t*)w.qs, gallery, ginv, nullptr, qn, G, dim, st, 0, nullptr, nullptr, nullptr,
+                             nullptr, nullptr, &rb))
+            return e;
+    }
+    return OK;
 }
 
 int mi355_clear_pads(float* val, int64_t* idx, int64_t n, int64_t lo, int64_t hi, void* stream) {

@@ -333,6 +333,7 @@ struct RangeArgs {
     i64 cap;                    // entries raw holds: a tile whose chunk would pass it writes nothing (the counts stay exact)
     i64* tstart;                // [Q][ntx] first raw entry of (query, column tile)
     int* tcount;                // [Q][ntx] its hits
+    int keep_all;               // 1: every eligible pair is a hit whatever its score, NaN included (mi355_positives_range)
 };
 
 // LDS of the range epilogue: hit masks [BM][4] u32, row counts / prefixes [BM], the workgroup's base, then the tile's gallery
@@ -381,7 +382,7 @@ __device__ __forceinline__ void cos_gemm_epilogue(f32x16 (&acc)[MT][2], float* s
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int row = wm * MT * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                bool hit = col < G && m0 + row < Q && acc[i][j][r] * gs >= rg.thr;
+                bool hit = col < G && m0 + row < Q && (rg.keep_all || acc[i][j][r] * gs >= rg.thr);
                 if (filt) hit = hit && eligible(rg.f.mode, qlab[row], gl, qex[row], col);
                 const unsigned long long b = __ballot(hit);
                 if (lane == 0) {
@@ -440,6 +441,94 @@ __device__ __forceinline__ void cos_gemm_epilogue(f32x16 (&acc)[MT][2], float* s
                                                         ((unsigned long long)__float_as_uint(s) << 32);
                 }
             }
+    }
+}
+
+// ---- full-gallery ranks (mi355_rank_positives[_f16]): the fifth epilogue mode counts, per query, every eligible row that is
+// NOT a positive (label differs) into one bin: the number b of the query's positives that rank before it.  The order is the
+// top-k search's, as one 64-bit composite per (score, row): higher score_key first, on equal keys the lower row.  The query's
+// positives are given as their composites in descending order (keys, CSR over the queries); bin b = R_q (the row beats no
+// positive) is never needed and never written.  Counts are integers: the result does not depend on the order of the atomics.
+constexpr int FK_RANKS = -3;                            // the ranks mode in the launcher's FK slot
+
+__host__ __device__ __forceinline__ unsigned long long rank_composite(unsigned key, unsigned local_row) {
+    return ((unsigned long long)key << 32) | (unsigned)~local_row;
+}
+
+struct RanksArgs {
+    const i64* qlab;            // [Q] labels of the queries of this call (the host shifts them per query block)
+    const i64* glab;            // [G] labels of the gallery rows
+    const i64* excl;            // [Q] global row indices (< 0: none), or null
+    i64 idx_offset;
+    const i64* offsets;         // [Q + 1] of this call's queries: positions in keys / before (absolute, not per block)
+    const unsigned long long* keys;   // [nnz] composites of each query's positives, descending
+    unsigned* before;           // [nnz] before[offsets[q] + b] += 1 per negative that exactly b positives of q beat
+};
+
+// LDS of the ranks epilogue: the tile's gallery labels [128], its query labels, LOCAL excluded rows and CSR starts [BM] (i64),
+// each query's weakest positive composite [BM] and its R_q [BM] (inside the staging buffers of every loop: static_assert in
+// launch_tiles)
+constexpr size_t RANKS_EPI_BYTES = (size_t)(RK_BN + 3 * 128) * sizeof(i64) + (size_t)128 * sizeof(unsigned long long) +
+                                   (size_t)128 * sizeof(int);
+
+// The ranks epilogue: the overload of cos_gemm_epilogue that a kernel twin selects by passing RanksArgs (see the histogram
+// epilogue).  Scores are acc * ginv[col] as in the other modes: every negative is compared with the bits of
+// mi355_cosine_scores on the same loop, the bits the positives' composites were made from.  For a trained model most
+// negatives lose against the query's weakest positive and are done after one 64-bit compare; the others binary-search the
+// query's composites in global memory (an L2-resident segment) and add one to their bin.  Called after a __syncthreads()
+// that retired every read of the staging buffers.
+template <int MT, int FK, bool FILT>
+__device__ __forceinline__ void cos_gemm_epilogue(f32x16 (&acc)[MT][2], float* smem, const float* __restrict__ ginv, float*, int Q,
+                                                  i64 G, int, float*, int*, int, int, i64 n0, int m0, const RanksArgs& rk) {
+    static_assert(FK == FK_RANKS && !FILT, "the ranks twins pass FK = FK_RANKS, FILT = false");
+    constexpr int BM = 64 * MT;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1, lr = lane & 31;
+    i64* glab = reinterpret_cast<i64*>(smem);                                // [128]
+    i64* qlab = glab + RK_BN;                                                // [BM]
+    i64* qex = qlab + 128;                                                   // [BM] LOCAL excluded row, -1: none
+    i64* qstart = qex + 128;                                                 // [BM] first position of the query's segment
+    unsigned long long* qweak = reinterpret_cast<unsigned long long*>(qstart + 128);   // [BM] its last (weakest) composite
+    int* qR = reinterpret_cast<int*>(qweak + 128);                           // [BM] its length R_q (< 2^31: G is)
+    if (tid < RK_BN) glab[tid] = n0 + tid < G ? rk.glab[n0 + tid] : 0;
+    if (tid < BM) {
+        const bool ok = m0 + tid < Q;
+        const i64 e = ok && rk.excl ? rk.excl[m0 + tid] : -1;
+        const i64 s0 = ok ? rk.offsets[m0 + tid] : 0, s1 = ok ? rk.offsets[m0 + tid + 1] : 0;
+        qlab[tid] = ok ? rk.qlab[m0 + tid] : 0;
+        qex[tid] = e >= 0 ? e - rk.idx_offset : -1;
+        qstart[tid] = s0;
+        qR[tid] = (int)(s1 - s0);
+        qweak[tid] = s1 > s0 ? rk.keys[s1 - 1] : 0ull;
+    }
+    __syncthreads();
+    // C[row = query][col = gallery]; lane: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int c = wn * 64 + j * 32 + lr;
+        const i64 col = n0 + c;
+        if (col < G) {
+            const float gs = ginv ? ginv[col] : 1.0f;
+            const i64 gl = glab[c];
+#pragma unroll
+            for (int i = 0; i < MT; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int row = wm * MT * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                    if (m0 + row >= Q || col == qex[row] || qlab[row] == gl) continue;      // not eligible, or a positive
+                    const int R = qR[row];
+                    const unsigned long long K = rank_composite(score_key(acc[i][j][r] * gs), (unsigned)col);
+                    if (R == 0 || K < qweak[row]) continue;                  // beats no positive: bin R_q, never needed
+                    // b = the positives that beat K = the first position whose composite is below K (the last one is)
+                    const unsigned long long* seg = rk.keys + qstart[row];
+                    int lo = 0, hi = R - 1;
+                    while (lo < hi) {
+                        const int mid = (lo + hi) >> 1;
+                        if (seg[mid] > K) lo = mid + 1; else hi = mid;
+                    }
+                    atomicAdd(&rk.before[qstart[row] + lo], 1u);
+                }
+        }
     }
 }
 
@@ -543,6 +632,7 @@ int whole_round_tiles(int ntx, int ny, int slots);
 // (rank_f16.hip: F16Gemm).  A family F supplies only what differs between them:
 //   F::SLAB, F::FILTERED, F::ROC     whether it has score-slab (FK = 0) / filtered / histogram (FK = FK_ROC) kernels
 //   F::RANGE                         whether it has range (FK = FK_RANGE) kernels
+//   F::RANKS                         whether it has ranks (FK = FK_RANKS) kernels
 //   F::stage_bytes<MT>()             the LDS of its staging buffers
 //   F::kernel<MT, FK, FILT>()        its kernel
 //   F::launch<MT, FK, FILT>(...)     one launch of that kernel over column tiles [x0, x0 + xtiles) x ny query tiles
@@ -563,6 +653,7 @@ struct TileArgs {
     const RankFilter* filt;     // the queries' filter (fused selection), or null
     const RocArgs* roc;         // the histogram mode (the queries' labels / exclude of this call), or null
     const RangeArgs* rng;       // the range mode (the queries' filter, candidates and table of this call), or null
+    const RanksArgs* rnk;       // the ranks mode (the queries' labels / exclude / positives of this call), or null
 };
 
 constexpr size_t EPI_TILE_BYTES = (size_t)64 * (RK_BN + 4) * sizeof(float);   // the fused selection's transposed score tile
@@ -585,6 +676,7 @@ int launch_tiles(const TileArgs& a, hipStream_t st, int x0 = 0) {
     constexpr size_t stage = F::template stage_bytes<MT>();
     static_assert(!FILT || stage >= EPI_TILE_BYTES + FILT_LABELS_BYTES, "the filtered epilogue would grow the GEMM's LDS");
     static_assert(FK != FK_RANGE || stage >= RANGE_EPI_BYTES, "the range epilogue would grow the GEMM's LDS");
+    static_assert(FK != FK_RANKS || stage >= RANKS_EPI_BYTES, "the ranks epilogue would grow the GEMM's LDS");
     constexpr size_t lds = FK == FK_ROC ? (ROC_EPI_BYTES > stage ? ROC_EPI_BYTES : stage)
                                         : FK > 0 && EPI_TILE_BYTES > stage ? EPI_TILE_BYTES : stage;
     int slots = 0;
@@ -617,6 +709,9 @@ int launch_mt(const TileArgs& a, hipStream_t st) {
     if constexpr (F::RANGE) {
         if (a.rng) return launch_tiles<F, MT, FK_RANGE, false>(a, st);
     }
+    if constexpr (F::RANKS) {
+        if (a.rnk) return launch_tiles<F, MT, FK_RANKS, false>(a, st);
+    }
     if constexpr (F::SLAB) {
         if (!a.cand_val) {
             TileArgs s = a;
@@ -630,7 +725,7 @@ int launch_mt(const TileArgs& a, hipStream_t st) {
     return launch_fk<F, MT, false>(a, st);
 }
 // A GEMM call of family F: 128-query tiles above 64 queries, 64-query tiles otherwise.  a.roc: the histogram mode, a.rng: the
-// range mode.
+// range mode, a.rnk: the ranks mode.
 template <class F>
 int cos_gemm_tiles(const TileArgs& a, hipStream_t st) {
     return a.Q > 64 ? launch_mt<F, 2>(a, st) : launch_mt<F, 1>(a, st);
@@ -709,9 +804,10 @@ int range_compact_block(const RangeWs& w, i64 q0, i64 qn, i64 G, i64 off, const 
 // pass, the block's hit count is read back (the one host sync), and while everything so far fits the block is compacted.
 // Once a block does not fit, the rest only count (cap 0): *nnz is the exact total either way, and a call with
 // capacity >= *nnz fits.
+// keep_all: every eligible pair is a hit (the threshold is not looked at).
 template <class Score>
 int range_blocks(i64 Q, i64 G, const RankFilter& filt, double threshold, void* candidates, i64 capacity, int64_t* nnz,
-                 const RangeWs& w, hipStream_t st, Score&& score) {
+                 const RangeWs& w, hipStream_t st, Score&& score, bool keep_all = false) {
     unsigned long long* raw = (unsigned long long*)candidates;
     unsigned long long* canon = raw ? raw + capacity : nullptr;
     MI355_CHECK_HIP(hipMemsetAsync(w.offsets, 0, sizeof(i64), st));
@@ -721,7 +817,8 @@ int range_blocks(i64 Q, i64 G, const RankFilter& filt, double threshold, void* c
     for (i64 q0 = 0; q0 < Q; q0 += qb) {
         const i64 qn = (Q - q0 < qb) ? Q - q0 : qb;
         MI355_CHECK_HIP(hipMemsetAsync(w.cursor, 0, sizeof(unsigned long long), st));
-        const RangeArgs a{filter_from(filt, q0), roc_ceil_f32(threshold), w.cursor, raw, fits ? capacity : 0, w.tstart, w.tcount};
+        const RangeArgs a{filter_from(filt, q0), roc_ceil_f32(threshold), w.cursor, raw, fits ? capacity : 0, w.tstart, w.tcount,
+                          keep_all ? 1 : 0};
         if (int e = score(q0, qn, a)) return e;
         unsigned long long n = 0;
         MI355_CHECK_HIP(hipMemcpyAsync(&n, w.cursor, sizeof(n), hipMemcpyDeviceToHost, st));
@@ -736,5 +833,16 @@ int range_blocks(i64 Q, i64 G, const RankFilter& filt, double threshold, void* c
     *nnz = off;
     return OK;
 }
+
+// ---- host side of the full-gallery ranks (ranks.hip)
+// The checks mi355_rank_positives[_f16] share (before any HIP call); fills *a
+int ranks_check(const void* queries, i64 Q, const void* gallery, i64 G, int dim, const int64_t* query_labels,
+                const int64_t* gallery_labels, const int64_t* exclude, i64 idx_offset, const int64_t* offsets,
+                const int64_t* offsets_host, const void* pos_keys, i64 nnz, const void* before, i64 query_block, const char* who,
+                RanksArgs* a);
+// The block of queries [q0, ...) of a
+RanksArgs ranks_from(const RanksArgs& a, i64 q0);
+// Queries per GEMM call of the counting pass: roc_query_block, or the caller's smaller query_block (> 0)
+i64 ranks_query_block(i64 Q, i64 G, i64 query_block);
 
 }  // namespace mi355

@@ -131,6 +131,19 @@ __global__ __launch_bounds__(256) void k_cos_gemm_f16_range(const f16* __restric
 #include "rank_gemm_f16.inc"
 }
 
+// The ranks twin (mi355_rank_positives_f16): the same body, the ranks epilogue (its overload takes RanksArgs as `flt`)
+template <int MT>
+__global__ __launch_bounds__(256) void k_cos_gemm_f16_ranks(const f16* __restrict__ Qs, const f16* __restrict__ Gal, int Q, i64 G,
+                                                            int ld, int x0, int ntx, int xtiles, int ny, RanksArgs flt) {
+    constexpr int FK = FK_RANKS;
+    constexpr bool FILT = false;
+    float* const S = nullptr;
+    const int k = 0;
+    float* const cand_val = nullptr;
+    int* const cand_idx = nullptr;
+#include "rank_gemm_f16.inc"
+}
+
 // =====================================================================================
 // Few queries (Q <= 4, the one-query-at-a-time serving shape): a GEMV bound by streaming the gallery once (2 * ld bytes
 // per row).  One wave per row, 16 bytes per lane per load, up to four loads in flight per lane; the fp32 queries sit in
@@ -193,13 +206,14 @@ static bool f16_gemv(i64 Q, int ld) { return Q <= 4 && (size_t)Q * ld * sizeof(f
 
 // The tiled GEMM over fp16 rows (launch_tiles, rank_common.h); qry: the queries' fp16 planes, gal: the rows, D: their length ld
 struct F16Gemm {
-    static constexpr bool SLAB = true, FILTERED = true, ROC = true, RANGE = true;
+    static constexpr bool SLAB = true, FILTERED = true, ROC = true, RANGE = true, RANKS = true;
     template <int MT> static constexpr size_t stage_bytes() {   // A ring of 2, B ring of 3
         return (size_t)2 * (64 * MT / 32) * 8 * 1024 + (size_t)3 * RK_BN * F16_KSTEP * 2;
     }
     template <int MT, int FK, bool FILT> static const void* kernel() {
         if constexpr (FK == FK_ROC) return (const void*)k_cos_gemm_f16_roc<MT>;
         else if constexpr (FK == FK_RANGE) return (const void*)k_cos_gemm_f16_range<MT>;
+        else if constexpr (FK == FK_RANKS) return (const void*)k_cos_gemm_f16_ranks<MT>;
         else if constexpr (FILT) return (const void*)k_cos_gemm_f16_filt<MT, FK>;
         else return (const void*)k_cos_gemm_f16<MT, FK>;
     }
@@ -211,6 +225,8 @@ struct F16Gemm {
             hipLaunchKernelGGL((k_cos_gemm_f16_roc<MT>), grid, dim3(256), lds, st, qs, gal, a.Q, a.G, a.D, x0, ntx, xtiles, ny, *a.roc);
         else if constexpr (FK == FK_RANGE)
             hipLaunchKernelGGL((k_cos_gemm_f16_range<MT>), grid, dim3(256), lds, st, qs, gal, a.Q, a.G, a.D, x0, ntx, xtiles, ny, *a.rng);
+        else if constexpr (FK == FK_RANKS)
+            hipLaunchKernelGGL((k_cos_gemm_f16_ranks<MT>), grid, dim3(256), lds, st, qs, gal, a.Q, a.G, a.D, x0, ntx, xtiles, ny, *a.rnk);
         else if constexpr (FILT)
             hipLaunchKernelGGL((k_cos_gemm_f16_filt<MT, FK>), grid, dim3(256), lds, st, qs, gal, a.Q, a.G, a.D, a.k, a.cand_val,
                                a.cand_idx, x0, ntx, xtiles, ny, *a.filt);
@@ -361,10 +377,12 @@ size_t mi355_range_f16_workspace_bytes(int64_t Q, int64_t G, int dim) {
     return range_carve(nullptr, Q, G, dim, f16_planes_bytes, false).total;   // normalised queries + one call's planes + table
 }
 
-int mi355_cosine_range_f16(const float* queries, int64_t Q, const void* gallery_f16, int64_t G, int dim, float eps, double threshold,
-                           int64_t idx_offset, const mi355_rank_filter* filter, void* candidates, int64_t capacity, int64_t* nnz,
-                           void* workspace, size_t workspace_bytes, void* stream) {
-    const char* who = "cosine_range_f16";
+}  // extern "C"
+
+// mi355_cosine_range_f16 and, with keep_all, mi355_positives_range_f16, under the name who
+static int cosine_range_f16(const float* queries, int64_t Q, const void* gallery_f16, int64_t G, int dim, float eps, double threshold,
+                            int64_t idx_offset, const mi355_rank_filter* filter, void* candidates, int64_t capacity, int64_t* nnz,
+                            void* workspace, size_t workspace_bytes, void* stream, bool keep_all, const char* who) {
     RankFilter f{};
     if (int e = range_check(queries, Q, gallery_f16, G, dim, threshold, filter, idx_offset, candidates, capacity, nnz, who, &f))
         return e;
@@ -376,7 +394,7 @@ int mi355_cosine_range_f16(const float* queries, int64_t Q, const void* gallery_
     if (int e = normalize_search(queries, Q, nullptr, G, dim, eps, w.w, st)) return e;
     const int ld = f16_ld(dim), n_sub = ld / 16;
     return range_blocks(Q, G, f, threshold, candidates, capacity, nnz, w, st, [&](i64 q0, i64 qn, const RangeArgs& a) -> int {
-        RoctxRange range("range/cosine gemm (fp16 gallery) + hits");
+        RoctxRange range(keep_all ? "ranks/positives" : "range/cosine gemm (fp16 gallery) + hits");
         set_rank_path(MI355_RANK_PATH_F16_GEMM);
         const int n_frag = cdiv(qn, 128) * 4 * n_sub;
         hipLaunchKernelGGL(k_split_queries_f16, dim3((unsigned)cdiv(n_frag, 4)), dim3(256), 0, st, w.w.qn + q0 * dim, (f16*)w.w.qs,
@@ -384,7 +402,62 @@ int mi355_cosine_range_f16(const float* queries, int64_t Q, const void* gallery_
         MI355_LAUNCH_CHECK();
         TileArgs t{w.w.qs, gallery_f16, nullptr, nullptr, (int)qn, G, ld, 0, nullptr, nullptr, nullptr, nullptr, &a};
         return cos_gemm_tiles<F16Gemm>(t, st);
-    });
+    }, keep_all);
+}
+
+extern "C" {
+
+int mi355_cosine_range_f16(const float* queries, int64_t Q, const void* gallery_f16, int64_t G, int dim, float eps, double threshold,
+                           int64_t idx_offset, const mi355_rank_filter* filter, void* candidates, int64_t capacity, int64_t* nnz,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+    return cosine_range_f16(queries, Q, gallery_f16, G, dim, eps, threshold, idx_offset, filter, candidates, capacity, nnz, workspace,
+                            workspace_bytes, stream, false, "cosine_range_f16");
+}
+
+int mi355_positives_range_f16(const float* queries, int64_t Q, const void* gallery_f16, int64_t G, int dim, float eps,
+                              int64_t idx_offset, const mi355_rank_filter* filter, void* candidates, int64_t capacity, int64_t* nnz,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+    MI355_REQUIRE(filter && filter->label_mode == MI355_LABEL_SAME, "positives_range_f16: needs a filter with MI355_LABEL_SAME");
+    return cosine_range_f16(queries, Q, gallery_f16, G, dim, eps, 0.0, idx_offset, filter, candidates, capacity, nnz, workspace,
+                            workspace_bytes, stream, true, "positives_range_f16");
+}
+
+size_t mi355_rank_positives_f16_workspace_bytes(int64_t Q, int64_t G, int dim) {
+    return mi355_roc_pairs_f16_workspace_bytes(Q, G, dim);
+}
+
+int mi355_rank_positives_f16(const float* queries, int64_t Q, const void* gallery_f16, int64_t G, int dim, float eps,
+                             const int64_t* query_labels, const int64_t* gallery_labels, const int64_t* exclude, int64_t idx_offset,
+                             const int64_t* offsets, const int64_t* offsets_host, const uint64_t* pos_keys, int64_t nnz,
+                             uint32_t* before, int64_t query_block, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "rank_positives_f16";
+    RanksArgs rk{};
+    if (int e = ranks_check(queries, Q, gallery_f16, G, dim, query_labels, gallery_labels, exclude, idx_offset, offsets, offsets_host,
+                            pos_keys, nnz, before, query_block, who, &rk))
+        return e;
+    MI355_REQUIRE(((uintptr_t)gallery_f16 & 15) == 0, "%s: gallery buffer must be 16-byte aligned", who);
+    const size_t need = mi355_rank_positives_f16_workspace_bytes(Q, G, dim);
+    MI355_REQUIRE(workspace && workspace_bytes >= need, "%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
+    const RankWs w = carve(workspace, Q, G, dim, 0, f16_planes_bytes, false, false);
+    hipStream_t st = (hipStream_t)stream;
+    if (nnz == 0) return OK;                                    // no query has a positive: nothing to count
+    MI355_CHECK_HIP(hipMemsetAsync(before, 0, (size_t)nnz * sizeof(uint32_t), st));
+    if (int e = normalize_search(queries, Q, nullptr, G, dim, eps, w, st)) return e;
+    const int ld = f16_ld(dim), n_sub = ld / 16;
+    const i64 qb = ranks_query_block(Q, G, query_block);
+    for (i64 q0 = 0; q0 < Q; q0 += qb) {
+        const i64 qn = (Q - q0 < qb) ? Q - q0 : qb;
+        const RanksArgs rb = ranks_from(rk, q0);
+        RoctxRange range("ranks/count");
+        set_rank_path(MI355_RANK_PATH_F16_GEMM);
+        const int n_frag = cdiv(qn, 128) * 4 * n_sub;
+        hipLaunchKernelGGL(k_split_queries_f16, dim3((unsigned)cdiv(n_frag, 4)), dim3(256), 0, st, w.qn + q0 * dim, (f16*)w.qs,
+                           (int)qn, dim, n_sub, n_frag);
+        MI355_LAUNCH_CHECK();
+        TileArgs t{w.qs, gallery_f16, nullptr, nullptr, (int)qn, G, ld, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &rb};
+        if (int e = cos_gemm_tiles<F16Gemm>(t, st)) return e;
+    }
+    return OK;
 }
 
 }  // extern "C"

@@ -10,6 +10,7 @@ routes the arithmetic to libmi355_retrieval:
 * ``hit_counts`` / ``distinct_class_topn`` .... train/train.py:252-255 ; notebook raw :240-251
 * ``roc_curve`` / ``verification_roc`` ........ utils/roc_curve_from_scratch.py (given pair scores / every labelled pair)
 * ``cosine_range`` ............................ the pairs a verification threshold accepts (``score >= threshold``)
+* ``positive_ranks`` / ``ranking_metrics`` .... full-gallery rank of every positive, mAP and CMC (not in the reference)
 * ``expand_queries`` / ``Gallery.augmented`` .. alpha query expansion and database-side augmentation (not in the reference)
 * ``Gallery.moments`` / ``Gallery.whitened`` .. PCA whitening of a resident gallery (whitening.py; not in the reference)
 * ``Gallery.rerank`` / ``Gallery.rerank_index`` k-reciprocal re-ranking on the gallery's kNN graph (rerank.py; not in the reference)
@@ -139,9 +140,13 @@ class _Rows:
 _ENTRIES = {
     torch.float32: {"topk": ("mi355_rank_topk", "mi355_rank_topk_filtered", "mi355_rank_workspace_bytes"),
                     "range": ("mi355_cosine_range", "mi355_range_workspace_bytes"),
+                    "positives": ("mi355_positives_range", "mi355_range_workspace_bytes"),
+                    "ranks": ("mi355_rank_positives", "mi355_rank_positives_workspace_bytes"),
                     "roc": ("mi355_roc_pairs_hist", "mi355_roc_pairs_workspace_bytes")},
     torch.float16: {"topk": ("mi355_rank_topk_f16", "mi355_rank_topk_f16_filtered", "mi355_rank_f16_workspace_bytes"),
                     "range": ("mi355_cosine_range_f16", "mi355_range_f16_workspace_bytes"),
+                    "positives": ("mi355_positives_range_f16", "mi355_range_f16_workspace_bytes"),
+                    "ranks": ("mi355_rank_positives_f16", "mi355_rank_positives_f16_workspace_bytes"),
                     "roc": ("mi355_roc_pairs_hist_f16", "mi355_roc_pairs_f16_workspace_bytes")},
 }
 
@@ -803,6 +808,17 @@ class Gallery:
         return _roc_finalize(_roc_hist(queries, query_labels, self._resident(), gl, exclude, 0, thr, self.eps), thr)
 
 
+    def ranking_metrics(self, queries: torch.Tensor, query_labels: torch.Tensor, *, exclude: torch.Tensor | None = None,
+                        ranks=(1, 5, 10, 20)):
+        """``ranking_metrics`` of ``queries`` against the resident rows and the labels given to ``add``: full-gallery mAP and
+        CMC, every score with the bits of this gallery's own search (fp32 or fp16 rows; the planes of ``prepare()`` are not
+        used).  ``exclude`` (Q,) leaves out one global row per query (negative: none)."""
+        gl = self._labels_for("ranking_metrics")
+        rows = self._resident()
+        _ranking_args(queries, query_labels, rows, gl)
+        return _ranking_metrics(queries, query_labels, rows, gl, exclude, 0, _cmc_ranks(ranks), self.eps)
+
+
 def clear_pads(vals: torch.Tensor, idx: torch.Tensor, lo: int, hi: int):
     """In place: entries whose index lies outside [lo, hi) become (-inf, -1)."""
     require_cuda(idx, "idx")
@@ -827,7 +843,7 @@ def retrieval_accuracy(queries: torch.Tensor, query_labels: torch.Tensor, galler
     ``exclude=arange(Q)``).  Otherwise ``gallery`` (G, D) with ``gallery_labels`` (G,).  R_q = the number of gallery rows
     with the query's label (its own row not counted); queries with R_q = 0 are left out of every mean (``num_lone``).  One
     search with k = max(max(ks), max R_q) (at most 1024) ranks every query; the per-query metrics run in one HIP kernel
-    (``mi355_retrieval_metrics``).  Returns device tensors (float64) ``precision_at_1``, ``recall_at_k`` {K: ...},
+    (``mi355_retrieval_metrics``); classes above 1024 rows: ``ranking_metrics`` ranks every positive.  Returns device tensors (float64) ``precision_at_1``, ``recall_at_k`` {K: ...},
     ``r_precision``, ``map_at_r``, and ints ``num_queries``, ``num_lone``.  The one host sync reads max R_q.
 
     ``query_expansion=(n, alpha)``: the queries are first replaced by ``expand_queries(queries, gallery, n, alpha)`` with the
@@ -1056,10 +1072,13 @@ def _range_empty(Q: int, device) -> RangeResult:
 
 
 def _range(queries: torch.Tensor, rows: _Rows, threshold: float, eps: float = _EPS, idx_offset: int = 0, query_labels=None,
-           gallery_labels=None, label_filter=None, exclude=None, max_results: int | None = None) -> RangeResult:
+           gallery_labels=None, label_filter=None, exclude=None, max_results: int | None = None,
+           keep_all: bool = False) -> RangeResult:
     """The range search of ``queries`` against ``rows``, the one entry behind ``cosine_range``, ``Gallery`` and
     ``ShardedGallery`` (the planes of a prepared gallery are not used).  One search into the cached candidate buffer; if its
-    hits do not fit, ONE more search with exactly that capacity; then the compaction into exact-size outputs."""
+    hits do not fit, ONE more search with exactly that capacity; then the compaction into exact-size outputs.
+    ``keep_all`` (``positive_ranks`` only, with ``label_filter="same"``): no threshold, every row the filter keeps is a hit,
+    a NaN score included."""
     q = _f32c(queries, "queries")
     _check_qg(q, rows)
     threshold = _range_threshold(threshold)
@@ -1070,15 +1089,16 @@ def _range(queries: torch.Tensor, rows: _Rows, threshold: float, eps: float = _E
     if Q == 0 or G == 0:
         return _range_empty(Q, q.device)
     L = lib()
-    entry, ws_bytes = _ENTRIES[rows.dtype]["range"]
+    entry, ws_bytes = _ENTRIES[rows.dtype]["positives" if keep_all else "range"]
     ws = _ws.get(q.device, getattr(L, ws_bytes)(Q, G, rows.dim))
     fp = ctypes.byref(filt[0]) if filt is not None else None
     nnz = ctypes.c_int64(0)
+    thr = () if keep_all else (threshold,)
 
     def search(cand):
         cap = cand.numel() // 16
         with torch.cuda.device(q.device):
-            check(getattr(L, entry)(q.data_ptr(), Q, *rows.c_args(), eps, threshold, int(idx_offset), fp, cand.data_ptr(), cap,
+            check(getattr(L, entry)(q.data_ptr(), Q, *rows.c_args(), eps, *thr, int(idx_offset), fp, cand.data_ptr(), cap,
                                     ctypes.byref(nnz), ws.data_ptr(), ws.numel(), stream_ptr(q.device)))
         return cap, int(nnz.value)
 
@@ -1115,3 +1135,197 @@ def cosine_range(queries: torch.Tensor, gallery: torch.Tensor, threshold: float,
     sync per query block (its hit count), as ``torch.nonzero``."""
     return _range(queries, _Rows.of(gallery, gallery_is_normalized), threshold, eps, idx_offset, query_labels, gallery_labels,
                   label_filter, exclude, max_results)
+
+
+# ---- full-gallery ranks of every positive: mean average precision and the CMC curve (Zheng et al., ICCV 2015)
+class PositiveRanks(NamedTuple):
+    """CSR result of ``positive_ranks``: the positives of query q are ``indices[offsets[q]:offsets[q + 1]]`` (global rows) in
+    rank order, with their ``scores`` and their 1-based ``ranks`` among the query's eligible rows."""
+    offsets: torch.Tensor          # (Q + 1,) int64
+    indices: torch.Tensor          # (nnz,) int64
+    scores: torch.Tensor           # (nnz,) fp32
+    ranks: torch.Tensor            # (nnz,) int64
+
+
+_MAX_G_RANKS = (1 << 31) - 128
+_SIGN64 = -(1 << 63)
+
+
+def _cmc_ranks(ranks):
+    """The CMC ranks as a sorted list of distinct positive ints."""
+    try:
+        rs = list(ranks)
+    except TypeError:
+        raise MI355Error(f"ranks must be a sequence of positive integers, got {ranks!r}") from None
+    if not rs or any(isinstance(r, bool) or not isinstance(r, (int, np.integer)) or int(r) < 1 for r in rs):
+        raise MI355Error(f"ranks must be a non-empty sequence of positive integers, got {ranks!r}")
+    return sorted({int(r) for r in rs})
+
+
+def _ranking_args(queries, query_labels, gallery, gallery_labels):
+    """The shape and device checks of ``positive_ranks`` / ``ranking_metrics``, before anything is asked of a device.
+    ``gallery``: None (same-source), a (G, D) tensor or the ``_Rows`` of a resident gallery."""
+    for t, name in ((queries, "queries"), (query_labels, "query_labels")):
+        if not torch.is_tensor(t):
+            raise MI355Error(f"{name} must be a tensor")
+    if queries.dim() != 2:
+        raise MI355Error(f"queries must be (Q, D), got {tuple(queries.shape)}")
+    Q = queries.shape[0]
+    if gallery is None:
+        if gallery_labels is not None:
+            raise MI355Error("gallery_labels given without a gallery (same-source evaluation uses query_labels)")
+        G = Q
+    else:
+        if gallery_labels is None:
+            raise MI355Error("a gallery needs gallery_labels")
+        if not torch.is_tensor(gallery_labels):
+            raise MI355Error("gallery_labels must be a tensor")
+        _check_qg(queries, gallery)
+        G = gallery.shape[0]
+        if gallery_labels.dim() != 1 or gallery_labels.shape[0] != G:
+            raise MI355Error(f"gallery_labels must have shape ({G},), got {tuple(gallery_labels.shape)}")
+    if query_labels.dim() != 1 or query_labels.shape[0] != Q:
+        raise MI355Error(f"query_labels must have shape ({Q},), got {tuple(query_labels.shape)}")
+    if Q == 0 or G == 0 or (gallery is None and G < 2):
+        raise MI355Error(f"ranking needs queries and at least one other gallery row (Q={Q}, G={G})")
+    if G >= _MAX_G_RANKS:
+        raise MI355Error(f"ranking counts in 32 bits: G={G} must be below {_MAX_G_RANKS}")
+
+
+def _ranks_positives(q, ql, rows: _Rows, gl, ex, idx_offset, eps):
+    """``ranks/positives``: (offsets, keys, indices, scores) of every query's positives in rank order.  The range pass without
+    a threshold under ``label_filter="same"`` yields them with the bits of the GEMM; their composites
+    (``mi355_rank_positives_keys``) are put into rank order per query by two stable ``torch.sort`` calls (composite descending
+    as UNSIGNED 64-bit - the sign bit flipped for the signed sort - then query)."""
+    pos = _range(q, rows, 0.0, eps, idx_offset, ql, gl, "same", ex, keep_all=True)
+    n, dev = pos.indices.shape[0], q.device
+    keys = torch.empty(n, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().mi355_rank_positives_keys(pos.indices.data_ptr() if n else None, pos.scores.data_ptr() if n else None, n,
+                                              int(idx_offset), keys.data_ptr() if n else None, stream_ptr(dev)))
+    seg = torch.repeat_interleave(torch.arange(q.shape[0], device=dev), pos.offsets[1:] - pos.offsets[:-1], output_size=n)
+    o1 = torch.sort(torch.bitwise_xor(keys, _SIGN64), descending=True, stable=True).indices
+    perm = o1[torch.sort(seg[o1], stable=True).indices]
+    return pos.offsets, keys[perm].contiguous(), pos.indices[perm].contiguous(), pos.scores[perm].contiguous()
+
+
+def _ranks_count(q, ql, rows: _Rows, gl, ex, idx_offset, eps, offsets, keys, block=None) -> torch.Tensor:
+    """``ranks/count``: before (nnz,) int32, the eligible non-positive rows of each query per bin of positives that beat them
+    (``mi355_rank_positives``, the GEMM with the counting epilogue).  The offsets are checked on the host first (one sync)."""
+    Q, n, dev = q.shape[0], keys.shape[0], q.device
+    before = torch.empty(n, dtype=torch.int32, device=dev)                    # (zeroed by the call)
+    off_host = offsets.cpu()
+    L = lib()
+    entry, ws_bytes = _ENTRIES[rows.dtype]["ranks"]
+    ws = _ws.get(dev, getattr(L, ws_bytes)(Q, rows.rows, rows.dim))
+    with torch.cuda.device(dev):
+        check(getattr(L, entry)(q.data_ptr(), Q, *rows.c_args(), eps, ql.data_ptr(), gl.data_ptr(),
+                                ex.data_ptr() if ex is not None else None, int(idx_offset), offsets.data_ptr(),
+                                ctypes.cast(off_host.data_ptr(), ctypes.POINTER(ctypes.c_int64)), keys.data_ptr() if n else None, n,
+                                before.data_ptr() if n else None, 0 if block is None else int(block), ws.data_ptr(), ws.numel(),
+                                stream_ptr(dev)))
+    return before
+
+
+def _ranks_finalize(offsets, before):
+    """``ranks/finalize``: (ranks (nnz,) int64, AP (Q,) float64, first rank (Q,) int64) in one launch."""
+    Q, n, dev = offsets.shape[0] - 1, before.shape[0], offsets.device
+    ranks = torch.empty(n, dtype=torch.int64, device=dev)
+    ap = torch.empty(Q, dtype=torch.float64, device=dev)
+    first = torch.empty(Q, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().mi355_rank_positives_finalize(offsets.data_ptr(), before.data_ptr() if n else None, Q, n,
+                                                  ranks.data_ptr() if n else None, ap.data_ptr(), first.data_ptr(), stream_ptr(dev)))
+    return ranks, ap, first
+
+
+def _positive_ranks(queries: torch.Tensor, query_labels, rows: _Rows, gallery_labels, exclude=None, idx_offset: int = 0,
+                    eps: float = _EPS, block: int | None = None):
+    """(``PositiveRanks``, AP (Q,) float64, first rank (Q,) int64) of ``queries`` against ``rows`` (arguments checked by
+    ``_ranking_args``): the one entry behind ``positive_ranks``, ``ranking_metrics`` and ``Gallery.ranking_metrics``, in the
+    three phases above.  ``block``: queries per GEMM call of the counting pass (for tests; the result does not depend on it).
+    Host syncs: the hit count of the range pass and the offsets."""
+    q = _f32c(queries, "queries")
+    Q, G, dev = q.shape[0], rows.rows, q.device
+    ql = _int64_on(query_labels, "query_labels", Q, dev)
+    gl = _int64_on(gallery_labels, "gallery_labels", G, dev)
+    ex = None if exclude is None else _int64_on(exclude, "exclude", Q, dev)
+    if block is not None and int(block) < 1:
+        raise MI355Error(f"block must be >= 1, got {block}")
+    offsets, keys, indices, scores = _ranks_positives(q, ql, rows, gl, ex, idx_offset, eps)
+    before = _ranks_count(q, ql, rows, gl, ex, idx_offset, eps, offsets, keys, block)
+    ranks, ap, first = _ranks_finalize(offsets, before)
+    return PositiveRanks(offsets, indices, scores, ranks), ap, first
+
+
+def _same_source(queries, exclude, idx_offset):
+    if exclude is not None or idx_offset:
+        raise MI355Error("same-source evaluation (gallery=None) excludes each query's own row itself: no exclude / idx_offset")
+    return torch.arange(queries.shape[0], dtype=torch.int64, device=queries.device)
+
+
+def positive_ranks(queries: torch.Tensor, query_labels: torch.Tensor, gallery: torch.Tensor | None = None,
+                   gallery_labels: torch.Tensor | None = None, *, eps: float = _EPS, exclude: torch.Tensor | None = None,
+                   idx_offset: int = 0, gallery_is_normalized: bool = False) -> PositiveRanks:
+    """The rank of every positive of every query in the WHOLE gallery, as a CSR ``PositiveRanks(offsets, indices, scores,
+    ranks)`` with each query's positives in rank order.
+
+    Eligible rows of query q: every gallery row except ``exclude[q]`` (a global row, compared with ``row + idx_offset``;
+    negative = none); ``gallery=None``: the queries are their own gallery and each query's own row is excluded (its
+    duplicates are not).  Positives: eligible rows with the query's label.  The order is ``cosine_topk``'s: descending score,
+    NaN first, -0 equal to +0, equal scores to the lower row; every score has the bits ``cosine_scores`` gives the pair on the
+    same path (the tiled GEMM for any Q).  ``ranks`` (int64, 1-based) counts the eligible rows up to and including the
+    positive.  Neither a (Q, G) score matrix nor a sorted gallery is made: each negative is counted inside the GEMM's epilogue
+    into the bin of the positives that beat it.  Integer counts: the same every run."""
+    _ranking_args(queries, query_labels, gallery, gallery_labels)
+    if gallery is None:
+        exclude = _same_source(queries, exclude, idx_offset)
+    q = _f32c(queries, "queries")
+    if gallery is None:
+        gallery, gallery_labels = q, query_labels
+    return _positive_ranks(q, query_labels, _Rows.of(gallery, gallery_is_normalized), gallery_labels, exclude, idx_offset, eps)[0]
+
+
+def _ranking_metrics(queries, query_labels, rows: _Rows, gallery_labels, exclude, idx_offset, ranks, eps):
+    pr, ap, first = _positive_ranks(queries, query_labels, rows, gallery_labels, exclude, idx_offset, eps)
+    R = pr.offsets[1:] - pr.offsets[:-1]
+    valid = (R > 0).to(torch.float64)
+    n = valid.sum()
+
+    def mean(x):
+        return (x.to(torch.float64) * valid).sum() / n
+
+    return {"map": mean(ap), "cmc": {r: mean((first <= r) & (R > 0)) for r in ranks}, "mean_first_rank": mean(first),
+            "per_query_ap": ap, "first_rank": first, "R": R, "num_queries": int(R.shape[0]), "num_lone": (R <= 0).sum(),
+            "positive_ranks": pr}
+
+
+def ranking_metrics(queries: torch.Tensor, query_labels: torch.Tensor, gallery: torch.Tensor | None = None,
+                    gallery_labels: torch.Tensor | None = None, *, ranks=(1, 5, 10, 20), eps: float = _EPS,
+                    query_expansion=None):
+    """Full-gallery mean average precision and the CMC curve of labelled embeddings (the protocol of Zheng et al., ICCV
+    2015, that Zhong et al. 2017 report): every positive of every query is ranked among ALL eligible gallery rows
+    (``positive_ranks``), whatever the class sizes - ``retrieval_accuracy`` stops at classes of 1024.
+
+    ``gallery=None``: the queries are their own gallery, each query's own row excluded; otherwise ``gallery`` (G, D) with
+    ``gallery_labels`` (G,).  With the positives p_0, p_1, .. of query q in rank order and R_q their number:
+    AP_q = (sum_i (i + 1) / rank(p_i)) / R_q in float64, the terms added in that order; first_rank_q = rank(p_0); CMC(r) = the
+    share of queries with first_rank_q <= r.  Queries with R_q = 0 are left out of every mean and counted in ``num_lone``
+    (their ``per_query_ap`` and ``first_rank`` are 0).  Ties, NaN and -0 as ``positive_ranks``.  Returns device tensors
+    ``map``, ``cmc`` {r: ...}, ``mean_first_rank`` (float64), ``per_query_ap`` (Q,) float64, ``first_rank`` (Q,) int64, ``R``
+    (Q,) int64, ``num_lone``, the int ``num_queries`` and the ``positive_ranks`` themselves.
+
+    ``query_expansion=(n, alpha)``: the queries are first replaced by ``expand_queries(queries, gallery, n, alpha)`` with the
+    same exclusion (same-source: a query is never expanded with its own row), then ranked as above."""
+    _ranking_args(queries, query_labels, gallery, gallery_labels)
+    ranks = _cmc_ranks(ranks)
+    q = _f32c(queries, "queries")
+    exclude = None
+    if gallery is None:
+        exclude = _same_source(q, None, 0)
+        gallery, gallery_labels = q, query_labels
+    g = _f32c(gallery, "gallery")
+    if query_expansion is not None:
+        n_qe, alpha = _qe_pair(query_expansion)
+        q = expand_queries(q, g, n_qe, alpha, eps=eps, exclude=exclude)
+    return _ranking_metrics(q, query_labels, _Rows.of(g), gallery_labels, exclude, 0, ranks, eps)

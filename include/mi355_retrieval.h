@@ -201,6 +201,50 @@ int mi355_cosine_range_f16(const float* queries, int64_t Q, const void* gallery_
 int mi355_range_compact(const void* candidates, int64_t capacity, int64_t Q, int64_t nnz, int64_t idx_offset, const void* workspace,
                         size_t workspace_bytes, int64_t* offsets, int64_t* indices, float* scores, void* stream);
 
+/* Full-gallery ranks: the 1-based rank of every POSITIVE of every query among the query's eligible rows, without a score slab
+ * or a sort of the gallery.  Eligible for query q: every gallery row but exclude[q] - idx_offset (exclude may be NULL;
+ * exclude[q] < 0: none); positive: an eligible row with gallery_labels[j] == query_labels[q].  The order is the top-k search's:
+ * higher score first with NaN above every number and -0 equal to +0, on equal scores the lower row; as one 64-bit composite
+ * per (score, row), (order-preserving key of the score << 32) | ~(uint32_t)local row, larger = ranked earlier.  Scores have the
+ * bits mi355_cosine_scores gives the pair on the same path (_f16: mi355_rank_topk_f16's tiled kernel), as in the range entries.
+ * Four steps:
+ *   mi355_positives_range[_f16]: mi355_cosine_range[_f16] without a threshold: every row the filter keeps is a hit whatever its
+ *     score, NaN included.  filter: MI355_LABEL_SAME (required) and the exclusion.  Candidates, *nnz, workspace
+ *     (mi355_range[_f16]_workspace_bytes) and mi355_range_compact as there: offsets [Q + 1], the positives' rows and scores.
+ *   mi355_rank_positives_keys: the composites keys [nnz] of (indices, scores) [nnz] (global rows: pass the search's idx_offset).
+ *     The caller sorts each query's segment descending (pos_keys below).
+ *   mi355_rank_positives[_f16]: the counting pass, the cosine GEMM again with an epilogue that adds every eligible NON-positive
+ *     row of query q to before[offsets[q] + b], b = the number of q's positives ranked before that row, unless b = R_q (such a
+ *     row changes no rank and is not counted).  before [nnz] uint32 (zeroed by the call).  offsets [Q + 1] int64 and pos_keys
+ *     [nnz] on the device; offsets_host (may be NULL): the same offsets on the host, checked before any HIP call (start at 0,
+ *     monotone, at most G per query, end at nnz).  query_block: queries per GEMM call (0: as many as the grid allows; the result
+ *     does not depend on it).  Q >= 1, 1 <= G < 2^31 - 128, dim >= 1.  Counts are integers: the same every run.
+ *     workspace: mi355_rank_positives[_f16]_workspace_bytes(Q, G, dim) (normalised queries, planes of one call, 1 / |row|).
+ *   mi355_rank_positives_finalize (one launch, one wave per query): ranks [nnz] int64, rank of the i-th positive of q (in
+ *     pos_keys order) = i + 1 + before[offsets[q]] + .. + before[offsets[q] + i]; ap [Q] float64 = (sum_i (i + 1) / rank_i) / R_q,
+ *     the terms added in the order i = 0, 1, ..; first_rank [Q] int64 = rank_0.  A query without positives: ap 0, first_rank 0. */
+int mi355_positives_range(const float* queries, int64_t Q, const float* gallery, int64_t G, int dim, int gallery_is_normalized,
+                          float eps, int64_t idx_offset, const mi355_rank_filter* filter, void* candidates, int64_t capacity,
+                          int64_t* nnz, void* workspace, size_t workspace_bytes, void* stream);
+int mi355_positives_range_f16(const float* queries, int64_t Q, const void* gallery_f16, int64_t G, int dim, float eps,
+                              int64_t idx_offset, const mi355_rank_filter* filter, void* candidates, int64_t capacity, int64_t* nnz,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int mi355_rank_positives_keys(const int64_t* indices, const float* scores, int64_t nnz, int64_t idx_offset, uint64_t* keys,
+                              void* stream);
+size_t mi355_rank_positives_workspace_bytes(int64_t Q, int64_t G, int dim);
+int mi355_rank_positives(const float* queries, int64_t Q, const float* gallery, int64_t G, int dim, int gallery_is_normalized,
+                         float eps, const int64_t* query_labels, const int64_t* gallery_labels, const int64_t* exclude,
+                         int64_t idx_offset, const int64_t* offsets, const int64_t* offsets_host, const uint64_t* pos_keys,
+                         int64_t nnz, uint32_t* before, int64_t query_block, void* workspace, size_t workspace_bytes,
+                         void* stream);
+size_t mi355_rank_positives_f16_workspace_bytes(int64_t Q, int64_t G, int dim);
+int mi355_rank_positives_f16(const float* queries, int64_t Q, const void* gallery_f16, int64_t G, int dim, float eps,
+                             const int64_t* query_labels, const int64_t* gallery_labels, const int64_t* exclude, int64_t idx_offset,
+                             const int64_t* offsets, const int64_t* offsets_host, const uint64_t* pos_keys, int64_t nnz,
+                             uint32_t* before, int64_t query_block, void* workspace, size_t workspace_bytes, void* stream);
+int mi355_rank_positives_finalize(const int64_t* offsets, const uint32_t* before, int64_t Q, int64_t nnz, int64_t* ranks, double* ap,
+                                  int64_t* first_rank, void* stream);
+
 /* Query expansion / database-side augmentation (alpha-QE, DBA; Radenovic, Tolias and Chum, TPAMI 2018): one output row per
  * row r of the neighbour lists vals / idx [R][n] (device fp32 / int64, the output of a search, rank order):
  *   w_j = v_j ^ alpha for a USED slot: v_j > 0 and l_j = idx[r][j] - idx_offset in [0, gallery_rows); every other slot
