@@ -1,6 +1,6 @@
 // Cosine range search (mi355_cosine_range*): the host side shared by the fp32 and fp16 entries (workspace, checks) and the
-// compaction that turns the range pass's hits (rank_common.h: cos_gemm_epilogue with RangeArgs; kernel twins in rank.hip /
-// rank_f16.hip) into a CSR result whose order does not depend on the order of the GEMM's atomics.  gfx950 only.
+// compaction that turns the range pass's hits (rank_common.h: the RangeArgs epilogue; driver cosine_range in
+// rank.hip) into a CSR result whose order does not depend on the order of the GEMM's atomics.  gfx950 only.
 #include "rank_common.h"
 #include "../../include/mi355_retrieval.h"
 

@@ -130,63 +130,137 @@ __global__ __launch_bounds__(256) void k_split_queries(const float* __restrict__
 // thread in ascending column order into a sorted FK-list, and k (score, local int32 index) candidates per (query, column
 // tile) go to cand_val / cand_idx [Q][n_tiles][k]; the existing multi-level selection then merges Q x n_tiles x k
 // candidates instead of reading Q x G scores (train/train.py:250-251 semantics, same tie rule).
+template <int MT, int RK_BK, bool VEC, class Epi>
+__device__ __forceinline__ void cos_gemm_f32_tile(const float* __restrict__ Qn, const float* __restrict__ Gal,
+                                                  const float* __restrict__ ginv, int Q, i64 G, int D, int x0, int ntx,
+                                                  int xtiles, int ny, const Epi& epi) {
+    // x0 / ntx: this launch covers the column tiles [x0, x0 + xtiles) of ntx for ny query blocks (the host splits a call into a main launch
+    // of whole rounds and a tail launch of smaller tiles)
+    constexpr int BM = 64 * MT;
+    constexpr int RK_LD = RK_BK + 4;      // +4 floats: ds_read_b128 of 16 distinct rows is bank-conflict free (36 and 20)
+    constexpr int CPR = RK_BK / 4;        // float4 columns per row of a K-tile
+    constexpr int RPP = 256 / CPR;        // rows covered by one pass of the 256 threads
+    constexpr int A_LOADS = BM / RPP;     // float4 loads per thread per K-tile for A
+    constexpr int B_LOADS = RK_BN / RPP;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* As = smem;                          // [2][BM][RK_LD]
+    float* Bs = smem + 2 * BM * RK_LD;         // [2][RK_BN][RK_LD]
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    int bx, by;
+    rank_tile_of((int)blockIdx.x, xtiles, ny, bx, by);
+    const i64 n0 = (i64)(bx + x0) * RK_BN;
+    const int m0 = by * BM;
+
+    const int c4 = tid % CPR;  // float4 column within the K-tile
+    const int r0 = tid / CPR;
+
+    f32x16 acc[MT][2];
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+
+    f32x4 ra[A_LOADS], rb[B_LOADS];
+
+    auto load_tile = [&](int k0) {
+        const int k = k0 + c4 * 4;
+#pragma unroll
+        for (int i = 0; i < A_LOADS; ++i) {
+            const int row = m0 + r0 + RPP * i;
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
+            if (row < Q) {
+                const float* p = Qn + (i64)row * D + k;
+                if (VEC) {
+                    if (k + 3 < D) v = *reinterpret_cast<const f32x4*>(p);
+                } else {
+                    if (k + 0 < D) v.x = p[0];
+                    if (k + 1 < D) v.y = p[1];
+                    if (k + 2 < D) v.z = p[2];
+                    if (k + 3 < D) v.w = p[3];
+                }
+            }
+            ra[i] = v;
+        }
+#pragma unroll
+        for (int i = 0; i < B_LOADS; ++i) {
+            const i64 row = n0 + r0 + RPP * i;
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
+            if (row < G) {
+                const float* p = Gal + row * D + k;
+                if (VEC) {
+                    if (k + 3 < D) v = *reinterpret_cast<const f32x4*>(p);
+                } else {
+                    if (k + 0 < D) v.x = p[0];
+                    if (k + 1 < D) v.y = p[1];
+                    if (k + 2 < D) v.z = p[2];
+                    if (k + 3 < D) v.w = p[3];
+                }
+            }
+            rb[i] = v;
+        }
+    };
+    auto store_tile = [&](int buf) {
+        float* a = As + buf * BM * RK_LD;
+        float* b = Bs + buf * RK_BN * RK_LD;
+#pragma unroll
+        for (int i = 0; i < A_LOADS; ++i)
+            *reinterpret_cast<f32x4*>(a + (r0 + RPP * i) * RK_LD + c4 * 4) = ra[i];
+#pragma unroll
+        for (int i = 0; i < B_LOADS; ++i)
+            *reinterpret_cast<f32x4*>(b + (r0 + RPP * i) * RK_LD + c4 * 4) = rb[i];
+    };
+
+    const int nt = (D + RK_BK - 1) / RK_BK;
+    load_tile(0);
+    store_tile(0);
+    __syncthreads();
+
+    const int lr = lane & 31;
+    const int lk = (lane >> 5) * 4;
+    for (int t = 0; t < nt; ++t) {
+        const int buf = t & 1;
+        if (t + 1 < nt) load_tile((t + 1) * RK_BK);
+        const float* a = As + buf * BM * RK_LD + (wm * MT * 32 + lr) * RK_LD + lk;
+        const float* b = Bs + buf * RK_BN * RK_LD + (wn * 64 + lr) * RK_LD + lk;
+#pragma unroll
+        for (int t8 = 0; t8 < RK_BK / 8; ++t8) {
+            f32x4 af[MT], bfr[2];
+#pragma unroll
+            for (int i = 0; i < MT; ++i) af[i] = *reinterpret_cast<const f32x4*>(a + i * 32 * RK_LD + t8 * 8);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) bfr[j] = *reinterpret_cast<const f32x4*>(b + j * 32 * RK_LD + t8 * 8);
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int i = 0; i < MT; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j)
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i][e], bfr[j][e], acc[i][j], 0, 0, 0);
+        }
+        if (t + 1 < nt) store_tile(buf ^ 1);
+        __syncthreads();
+    }
+
+    epi.tile(acc, smem, ginv, TileCtx{Q, G, ntx, n0, m0});
+}
 template <int MT, int RK_BK, bool VEC, int FK>
 __global__ __launch_bounds__(256) void k_cos_gemm(const float* __restrict__ Qn, const float* __restrict__ Gal,
-                                                  const float* __restrict__ ginv, float* __restrict__ S,
-                                                  int Q, i64 G, int D, int k, float* __restrict__ cand_val,
-                                                  int* __restrict__ cand_idx, int x0, int ntx, int xtiles, int ny) {
-    constexpr bool FILT = false;
-    const RankFilter flt{};
-#include "rank_gemm_f32.inc"
+                                                  const float* __restrict__ ginv, int Q, i64 G, int D, int x0, int ntx,
+                                                  int xtiles, int ny, PlainEpi<FK> epi) {
+    cos_gemm_f32_tile<MT, RK_BK, VEC>(Qn, Gal, ginv, Q, G, D, x0, ntx, xtiles, ny, epi);
 }
-template <int MT, int RK_BK, bool VEC, int FK>
-__global__ __launch_bounds__(256) void k_cos_gemm_filt(const float* __restrict__ Qn, const float* __restrict__ Gal,
-                                                       const float* __restrict__ ginv, int Q, i64 G, int D, int k,
-                                                       float* __restrict__ cand_val, int* __restrict__ cand_idx, int x0,
-                                                       int ntx, int xtiles, int ny, RankFilter flt) {
-    constexpr bool FILT = true;
-    float* const S = nullptr;
-#include "rank_gemm_f32.inc"
-}
-// The histogram twin (mi355_roc_pairs_hist): the same body, the histogram epilogue (its overload takes RocArgs as `flt`)
-template <int MT, int RK_BK, bool VEC>
-__global__ __launch_bounds__(256) void k_cos_gemm_roc(const float* __restrict__ Qn, const float* __restrict__ Gal,
+// Every other epilogue (filtered selection, histogram, range, ranks): the same loop
+template <int MT, int RK_BK, bool VEC, class Epi>
+__global__ __launch_bounds__(256) void k_cos_gemm_epi(const float* __restrict__ Qn, const float* __restrict__ Gal,
                                                       const float* __restrict__ ginv, int Q, i64 G, int D, int x0, int ntx,
-                                                      int xtiles, int ny, RocArgs flt) {
-    constexpr int FK = FK_ROC;
-    constexpr bool FILT = false;
-    float* const S = nullptr;
-    const int k = 0;
-    float* const cand_val = nullptr;
-    int* const cand_idx = nullptr;
-#include "rank_gemm_f32.inc"
-}
-// The range twin (mi355_cosine_range): the same body, the range epilogue (its overload takes RangeArgs as `flt`)
-template <int MT, int RK_BK, bool VEC>
-__global__ __launch_bounds__(256) void k_cos_gemm_range(const float* __restrict__ Qn, const float* __restrict__ Gal,
-                                                        const float* __restrict__ ginv, int Q, i64 G, int D, int x0, int ntx,
-                                                        int xtiles, int ny, RangeArgs flt) {
-    constexpr int FK = FK_RANGE;
-    constexpr bool FILT = false;
-    float* const S = nullptr;
-    const int k = 0;
-    float* const cand_val = nullptr;
-    int* const cand_idx = nullptr;
-#include "rank_gemm_f32.inc"
-}
-
-// The ranks twin (mi355_rank_positives): the same body, the ranks epilogue (its overload takes RanksArgs as `flt`)
-template <int MT, int RK_BK, bool VEC>
-__global__ __launch_bounds__(256) void k_cos_gemm_ranks(const float* __restrict__ Qn, const float* __restrict__ Gal,
-                                                        const float* __restrict__ ginv, int Q, i64 G, int D, int x0, int ntx,
-                                                        int xtiles, int ny, RanksArgs flt) {
-    constexpr int FK = FK_RANKS;
-    constexpr bool FILT = false;
-    float* const S = nullptr;
-    const int k = 0;
-    float* const cand_val = nullptr;
-    int* const cand_idx = nullptr;
-#include "rank_gemm_f32.inc"
+                                                      int xtiles, int ny, Epi epi) {
+    cos_gemm_f32_tile<MT, RK_BK, VEC>(Qn, Gal, ginv, Q, G, D, x0, ntx, xtiles, ny, epi);
 }
 
 // =====================================================================================
@@ -205,65 +279,179 @@ __global__ __launch_bounds__(256) void k_cos_gemm_ranks(const float* __restrict_
 // LDS-only barrier.  (With register-staged B loads hipcc drained vmcnt(0) before every store to LDS.)
 // LDS: 2 x 12 KB (A) + 3 x 8 KB (B) = 48 KB at MT = 2 -> three workgroups per CU; 3 x 6 + 24 = 42 KB at MT = 1.
 // =====================================================================================
+template <int MT, class Epi>
+__device__ __forceinline__ void cos_gemm_split_tile(const bf16_t* __restrict__ Qs, const float* __restrict__ Gal,
+                                                    const float* __restrict__ ginv, int Q, i64 G, int D, int x0, int ntx,
+                                                    int n_steps, const float* __restrict__ zeros, int xtiles, int ny,
+                                                    const Epi& epi) {
+    constexpr int BM = 64 * MT;
+    constexpr int BK = 16;
+    constexpr int A_STAGE = (BM / 32) * 3 * 512;      // bf16 elements per stage
+    constexpr int A_PIECES = (BM / 32) * 3;           // 1 KB pieces per stage
+    constexpr int B_STAGE = RK_BN * BK;               // floats per stage (8 KB)
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    bf16_t* As = reinterpret_cast<bf16_t*>(smem);                       // [A_RING][BM/32][3][512]
+    // A ring: 2 stages at MT = 2 (the pieces come from L2 one k-step ahead; a third stage would cost the third workgroup per
+    // CU), 3 stages at MT = 1 (two k-steps ahead: the 64-row tiles are the tail launch and the small-Q shapes, few
+    // workgroups per CU with nothing else to hide a piece's latency behind)
+    constexpr int A_RING = MT == 1 ? 3 : 2;
+    float* Bs = smem + (A_RING * A_STAGE * 2) / 4;                      // [3][128][16], chunks swizzled
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    int bx, by;
+    rank_tile_of((int)blockIdx.x, xtiles, ny, bx, by);
+    const i64 n0 = (i64)(bx + x0) * RK_BN;
+    const int m0 = by * BM;
+    // the wave index as a scalar: piece selection becomes scalar branches (a per-lane branch around a load makes hipcc
+    // drain vmcnt)
+    const int swave = __builtin_amdgcn_readfirstlane(wave);
+
+    // B: wave w moves pieces 2w and 2w + 1 (rows 32w .. 32w + 31); lane -> row 16 * piece + lane / 4, position lane % 4
+    const float* b_row[2];
+    int b_k[2];
+    bool b_ok[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int r = (swave * 2 + i) * 16 + (lane >> 2);
+        const int c = (lane & 3) ^ ((r >> 2) & 3);
+        b_ok[i] = n0 + r < G;
+        b_row[i] = Gal + (b_ok[i] ? (n0 + r) * D : 0);
+        b_k[i] = c * 4;
+    }
+    auto dma_b = [&](int stage, int k0) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const bool ok = b_ok[i] && k0 + b_k[i] < D;                // D % 4 == 0: a chunk is inside or outside
+            glds16(reinterpret_cast<const bf16_t*>(ok ? b_row[i] + k0 + b_k[i] : zeros),
+                   reinterpret_cast<bf16_t*>(Bs + stage * B_STAGE + (swave * 2 + i) * 256));
+        }
+    };
+    // A: piece (row block rbl, plane p) of k-step t sits at Qs + (((m0/32 + rbl) * n_steps + t) * 3 + p) * 512.
+    // 12 (MT = 2) or 6 (MT = 1) pieces per stage: wave w moves pieces w, w + 4, w + 8 / pieces w and (w < 2) w + 4.
+    const bf16_t* a_src = Qs + (size_t)(m0 / 32) * n_steps * 3 * 512 + lane * 8;
+    const bf16_t* a_piece[(A_PIECES + 3) / 4];
+#pragma unroll
+    for (int i = 0; i < (A_PIECES + 3) / 4; ++i) {
+        const int piece = (swave + 4 * i) % A_PIECES;
+        a_piece[i] = a_src + ((size_t)((piece / 3) * n_steps) * 3 + piece % 3) * 512;
+    }
+    auto dma_a = [&](int buf, int t) {
+#pragma unroll
+        for (int i = 0; i < (A_PIECES + 3) / 4; ++i) {
+            const int piece = swave + 4 * i;
+            if (A_PIECES % 4 == 0 || i < A_PIECES / 4 || swave < A_PIECES % 4)
+                glds16(a_piece[i] + (size_t)t * 3 * 512, As + buf * A_STAGE + piece * 512);
+        }
+    };
+
+    f32x16 acc[MT][2];
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+
+    const int lr = lane & 31;
+    // B fragment reads: row r = wn * 64 + j * 32 + lr, chunks 2 * (lane >> 5) and + 1 at their swizzled positions
+    int b_off[2][2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int r = wn * 64 + j * 32 + lr, sw = (r >> 2) & 3, c0 = (lane >> 5) * 2;
+        b_off[j][0] = r * BK + ((c0 ^ sw) << 2);
+        b_off[j][1] = r * BK + (((c0 + 1) ^ sw) << 2);
+    }
+    auto compute = [&](int abuf, int bstage) {
+        const bf16_t* a = As + abuf * A_STAGE + (wm * MT * 3) * 512 + lane * 8;
+        const float* b = Bs + bstage * B_STAGE;
+        bf16x8 af[MT][3];
+        u32x4 bh[2], bm[2], bl[2];
+        f32x4 v0[2], v1[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            v0[j] = *reinterpret_cast<const f32x4*>(b + b_off[j][0]);
+            v1[j] = *reinterpret_cast<const f32x4*>(b + b_off[j][1]);
+        }
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int p = 0; p < 3; ++p) af[i][p] = *reinterpret_cast<const bf16x8*>(a + (i * 3 + p) * 512);
+        split3(v0[0], v1[0], bh[0], bm[0], bl[0]);
+        // Per fragment j: six products for each of the MT row blocks, smallest terms first (the order is the same for every
+        // (query, gallery row) pair wherever its tile lies).  The split of fragment 1 is issued in the gaps of fragment 0's
+        // MFMAs (an MFMA holds the vector issue for 8 of its 32 cycles): sched_group_barrier pins "1 MFMA, 4 VALU" groups.
+        auto products = [&](int j) {
+            const bf16x8 gh = *reinterpret_cast<const bf16x8*>(&bh[j]);
+            const bf16x8 gm = *reinterpret_cast<const bf16x8*>(&bm[j]);
+            const bf16x8 gl = *reinterpret_cast<const bf16x8*>(&bl[j]);
+#pragma unroll
+            for (int i = 0; i < MT; ++i) {
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][2], gh, acc[i][j], 0, 0, 0);   // l * h'
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], gl, acc[i][j], 0, 0, 0);   // h * l'
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][1], gm, acc[i][j], 0, 0, 0);   // m * m'
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][1], gh, acc[i][j], 0, 0, 0);   // m * h'
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], gm, acc[i][j], 0, 0, 0);   // h * m'
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], gh, acc[i][j], 0, 0, 0);   // h * h'
+            }
+        };
+        split3(v0[1], v1[1], bh[1], bm[1], bl[1]);
+        products(0);
+#pragma unroll
+        for (int g = 0; g < 6 * MT; ++g) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // one MFMA
+            __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);   // four VALU (of fragment 1's split)
+        }
+        products(1);
+    };
+
+    dma_a(0, 0);
+    if (A_RING == 3 && n_steps > 1) dma_a(1, 1);
+    dma_b(0, 0);
+    dma_b(1, BK);                      // (zeros past D)
+    __syncthreads();                   // drains vmcnt: everything has landed
+
+    int bs_cur = 0, bs_far = 2;        // B stage of k-step t / of k-step t + 2 (and, at A_RING == 3, the A stages)
+    for (int t = 0; t < n_steps; ++t) {
+        if constexpr (A_RING == 2) {
+            if (t + 1 < n_steps) dma_a((t & 1) ^ 1, t + 1);  // everybody left these buffers at the previous barrier
+        } else {
+            if (t + 2 < n_steps) dma_a(bs_far, t + 2);
+        }
+        __builtin_amdgcn_sched_barrier(0);                   // (the counts below need the A pieces issued BEFORE the B pieces)
+        dma_b(bs_far, (t + 2) * BK);
+        __builtin_amdgcn_sched_barrier(0);
+        compute(A_RING == 2 ? (t & 1) : bs_cur, bs_cur);
+        if constexpr (A_RING == 2) {
+            asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); // A(t+1) and B(t+1) have landed; B(t+2) stays in flight
+        } else {
+            // A(t+2) (two pieces from waves 0 and 1, one from waves 2 and 3; none at the end) and B(t+2) stay in flight
+            if (t + 2 >= n_steps) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+            else if (swave < A_PIECES % 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        bs_cur = bs_cur == 2 ? 0 : bs_cur + 1;
+        bs_far = bs_far == 2 ? 0 : bs_far + 1;
+    }
+    __syncthreads();                   // the last look-ahead pieces (zeros) have landed before the epilogue reuses the LDS
+    epi.tile(acc, smem, ginv, TileCtx{Q, G, ntx, n0, m0});
+}
 template <int MT, int FK>
 __global__ __launch_bounds__(256, 3) void k_cos_gemm_split(const bf16_t* __restrict__ Qs, const float* __restrict__ Gal,
-                                                           const float* __restrict__ ginv, float* __restrict__ S, int Q,
-                                                           i64 G, int D, int k, float* __restrict__ cand_val,
-                                                           int* __restrict__ cand_idx, int x0, int ntx, int n_steps,
-                                                           const float* __restrict__ zeros, int xtiles, int ny) {
-    constexpr bool FILT = false;
-    const RankFilter flt{};
-#include "rank_gemm_split.inc"
+                                                           const float* __restrict__ ginv, int Q, i64 G, int D, int x0, int ntx,
+                                                           int n_steps, const float* __restrict__ zeros, int xtiles, int ny,
+                                                           PlainEpi<FK> epi) {
+    cos_gemm_split_tile<MT>(Qs, Gal, ginv, Q, G, D, x0, ntx, n_steps, zeros, xtiles, ny, epi);
 }
-template <int MT, int FK>
-__global__ __launch_bounds__(256, 3) void k_cos_gemm_split_filt(const bf16_t* __restrict__ Qs, const float* __restrict__ Gal,
-                                                                const float* __restrict__ ginv, int Q, i64 G, int D, int k,
-                                                                float* __restrict__ cand_val, int* __restrict__ cand_idx,
-                                                                int x0, int ntx, int n_steps, const float* __restrict__ zeros,
-                                                                int xtiles, int ny, RankFilter flt) {
-    constexpr bool FILT = true;
-    float* const S = nullptr;
-#include "rank_gemm_split.inc"
-}
-template <int MT>
-__global__ __launch_bounds__(256, 3) void k_cos_gemm_split_roc(const bf16_t* __restrict__ Qs, const float* __restrict__ Gal,
+template <int MT, class Epi>
+__global__ __launch_bounds__(256, 3) void k_cos_gemm_split_epi(const bf16_t* __restrict__ Qs, const float* __restrict__ Gal,
                                                                const float* __restrict__ ginv, int Q, i64 G, int D, int x0,
                                                                int ntx, int n_steps, const float* __restrict__ zeros, int xtiles,
-                                                               int ny, RocArgs flt) {
-    constexpr int FK = FK_ROC;
-    constexpr bool FILT = false;
-    float* const S = nullptr;
-    const int k = 0;
-    float* const cand_val = nullptr;
-    int* const cand_idx = nullptr;
-#include "rank_gemm_split.inc"
-}
-template <int MT>
-__global__ __launch_bounds__(256, 3) void k_cos_gemm_split_range(const bf16_t* __restrict__ Qs, const float* __restrict__ Gal,
-                                                                 const float* __restrict__ ginv, int Q, i64 G, int D, int x0,
-                                                                 int ntx, int n_steps, const float* __restrict__ zeros, int xtiles,
-                                                                 int ny, RangeArgs flt) {
-    constexpr int FK = FK_RANGE;
-    constexpr bool FILT = false;
-    float* const S = nullptr;
-    const int k = 0;
-    float* const cand_val = nullptr;
-    int* const cand_idx = nullptr;
-#include "rank_gemm_split.inc"
-}
-
-template <int MT>
-__global__ __launch_bounds__(256, 3) void k_cos_gemm_split_ranks(const bf16_t* __restrict__ Qs, const float* __restrict__ Gal,
-                                                                 const float* __restrict__ ginv, int Q, i64 G, int D, int x0,
-                                                                 int ntx, int n_steps, const float* __restrict__ zeros, int xtiles,
-                                                                 int ny, RanksArgs flt) {
-    constexpr int FK = FK_RANKS;
-    constexpr bool FILT = false;
-    float* const S = nullptr;
-    const int k = 0;
-    float* const cand_val = nullptr;
-    int* const cand_idx = nullptr;
-#include "rank_gemm_split.inc"
+                                                               int ny, Epi epi) {
+    cos_gemm_split_tile<MT>(Qs, Gal, ginv, Q, G, D, x0, ntx, n_steps, zeros, xtiles, ny, epi);
 }
 
 // =====================================================================================
@@ -277,10 +465,9 @@ __global__ __launch_bounds__(256, 3) void k_cos_gemm_split_ranks(const bf16_t* _
 // products are accumulated in the same order.  LDS: 2 x 12 KB (A) + 3 x 12 KB (B) = 60 KB at MT = 2 (two workgroups per CU).
 // =====================================================================================
 template <int MT, int FK>
-__global__ __launch_bounds__(256, 2) void k_cos_gemm_pre(const bf16_t* __restrict__ Qs, const bf16_t* __restrict__ Gs,
-                                                         float* __restrict__ S, int Q, i64 G, int k,
-                                                         float* __restrict__ cand_val, int* __restrict__ cand_idx, int x0,
-                                                         int ntx, int n_steps, int xtiles, int ny) {
+__global__ __launch_bounds__(256, 2) void k_cos_gemm_pre(const bf16_t* __restrict__ Qs, const bf16_t* __restrict__ Gs, int Q,
+                                                         i64 G, int x0, int ntx, int n_steps, int xtiles, int ny,
+                                                         SelectEpi<FK, false> epi) {
     constexpr int BM = 64 * MT;
     constexpr int A_PIECES = (BM / 32) * 3;           // 1 KB pieces per stage
     constexpr int A_STAGE = A_PIECES * 512;           // bf16 elements per stage
@@ -396,7 +583,7 @@ __global__ __launch_bounds__(256, 2) void k_cos_gemm_pre(const bf16_t* __restric
         bs_far = bs_far == 2 ? 0 : bs_far + 1;
     }
     __syncthreads();                   // the last look-ahead pieces have landed before the epilogue reuses the LDS
-    cos_gemm_epilogue<MT, FK>(acc, smem, nullptr, S, Q, G, k, cand_val, cand_idx, x0, ntx, n0, m0);
+    epi.tile(acc, smem, nullptr, TileCtx{Q, G, ntx, n0, m0});
 }
 
 // =====================================================================================
@@ -886,89 +1073,51 @@ int whole_round_tiles(int ntx, int ny, int slots) {
 // with 256 x 128 tiles, one per CU).  64-query tiles use BK = 32.
 template <bool VEC>
 struct F32Gemm {
-    static constexpr bool SLAB = true, FILTERED = true, ROC = true, RANGE = true, RANKS = true;
     template <int MT> static constexpr int BK = MT == 2 ? 16 : 32;
     template <int MT> static constexpr size_t stage_bytes() { return (size_t)2 * (64 * MT + RK_BN) * (BK<MT> + 4) * sizeof(float); }
-    template <int MT, int FK, bool FILT> static const void* kernel() {
-        if constexpr (FK == FK_ROC) return (const void*)k_cos_gemm_roc<MT, BK<MT>, VEC>;
-        else if constexpr (FK == FK_RANGE) return (const void*)k_cos_gemm_range<MT, BK<MT>, VEC>;
-        else if constexpr (FK == FK_RANKS) return (const void*)k_cos_gemm_ranks<MT, BK<MT>, VEC>;
-        else if constexpr (FILT) return (const void*)k_cos_gemm_filt<MT, BK<MT>, VEC, FK>;
-        else return (const void*)k_cos_gemm<MT, BK<MT>, VEC, FK>;
+    template <int MT, class Epi> static constexpr auto kernel() {
+        if constexpr (plain_fk<Epi> >= 0) return &k_cos_gemm<MT, BK<MT>, VEC, plain_fk<Epi>>;
+        else return &k_cos_gemm_epi<MT, BK<MT>, VEC, Epi>;
     }
-    template <int MT, int FK, bool FILT>
-    static void launch(dim3 grid, size_t lds, hipStream_t st, const TileArgs& a, int x0, int ntx, int xtiles, int ny) {
-        const float* qn = (const float*)a.qry;
-        const float* gal = (const float*)a.gal;
-        if constexpr (FK == FK_ROC)
-            hipLaunchKernelGGL((k_cos_gemm_roc<MT, BK<MT>, VEC>), grid, dim3(256), lds, st, qn, gal, a.ginv, a.Q, a.G, a.D, x0, ntx,
-                               xtiles, ny, *a.roc);
-        else if constexpr (FK == FK_RANGE)
-            hipLaunchKernelGGL((k_cos_gemm_range<MT, BK<MT>, VEC>), grid, dim3(256), lds, st, qn, gal, a.ginv, a.Q, a.G, a.D, x0, ntx,
-                               xtiles, ny, *a.rng);
-        else if constexpr (FK == FK_RANKS)
-            hipLaunchKernelGGL((k_cos_gemm_ranks<MT, BK<MT>, VEC>), grid, dim3(256), lds, st, qn, gal, a.ginv, a.Q, a.G, a.D, x0, ntx,
-                               xtiles, ny, *a.rnk);
-        else if constexpr (FILT)
-            hipLaunchKernelGGL((k_cos_gemm_filt<MT, BK<MT>, VEC, FK>), grid, dim3(256), lds, st, qn, gal, a.ginv, a.Q, a.G, a.D, a.k,
-                               a.cand_val, a.cand_idx, x0, ntx, xtiles, ny, *a.filt);
-        else
-            hipLaunchKernelGGL((k_cos_gemm<MT, BK<MT>, VEC, FK>), grid, dim3(256), lds, st, qn, gal, a.ginv, a.S, a.Q, a.G, a.D, a.k,
-                               a.cand_val, a.cand_idx, x0, ntx, xtiles, ny);
+    template <int MT, class Epi>
+    static void launch(dim3 grid, size_t lds, hipStream_t st, const TileArgs& a, const Epi& epi, int x0, int ntx, int xtiles, int ny) {
+        hipLaunchKernelGGL((kernel<MT, Epi>()), grid, dim3(256), lds, st, (const float*)a.qry, (const float*)a.gal, a.ginv, a.Q, a.G,
+                           a.D, x0, ntx, xtiles, ny, epi);
     }
 };
 
 // Split-bf16 loop (qry: the split planes of the queries, split_rows; gal: fp32 rows with D % 4 == 0)
 struct SplitGemm {
-    static constexpr bool SLAB = true, FILTERED = true, ROC = true, RANGE = true, RANKS = true;
     template <int MT> static constexpr size_t stage_bytes() {   // A ring of 2 (3 at MT = 1), B ring of 3
         return (size_t)(MT == 1 ? 3 : 2) * (64 * MT / 32) * 3 * 1024 + (size_t)3 * RK_BN * 16 * sizeof(float);
     }
-    template <int MT, int FK, bool FILT> static const void* kernel() {
-        if constexpr (FK == FK_ROC) return (const void*)k_cos_gemm_split_roc<MT>;
-        else if constexpr (FK == FK_RANGE) return (const void*)k_cos_gemm_split_range<MT>;
-        else if constexpr (FK == FK_RANKS) return (const void*)k_cos_gemm_split_ranks<MT>;
-        else if constexpr (FILT) return (const void*)k_cos_gemm_split_filt<MT, FK>;
-        else return (const void*)k_cos_gemm_split<MT, FK>;
+    template <int MT, class Epi> static constexpr auto kernel() {
+        if constexpr (plain_fk<Epi> >= 0) return &k_cos_gemm_split<MT, plain_fk<Epi>>;
+        else return &k_cos_gemm_split_epi<MT, Epi>;
     }
-    template <int MT, int FK, bool FILT>
-    static void launch(dim3 grid, size_t lds, hipStream_t st, const TileArgs& a, int x0, int ntx, int xtiles, int ny) {
+    template <int MT, class Epi>
+    static void launch(dim3 grid, size_t lds, hipStream_t st, const TileArgs& a, const Epi& epi, int x0, int ntx, int xtiles, int ny) {
         const bf16_t* qs = (const bf16_t*)a.qry;
-        const float* gal = (const float*)a.gal;
         const int n_steps = cdiv(a.D, 16);
         const float* zeros = reinterpret_cast<const float*>(qs + (size_t)cdiv(a.Q, 128) * 4 * n_steps * 3 * 512);
-        if constexpr (FK == FK_ROC)
-            hipLaunchKernelGGL((k_cos_gemm_split_roc<MT>), grid, dim3(256), lds, st, qs, gal, a.ginv, a.Q, a.G, a.D, x0, ntx, n_steps,
-                               zeros, xtiles, ny, *a.roc);
-        else if constexpr (FK == FK_RANGE)
-            hipLaunchKernelGGL((k_cos_gemm_split_range<MT>), grid, dim3(256), lds, st, qs, gal, a.ginv, a.Q, a.G, a.D, x0, ntx, n_steps,
-                               zeros, xtiles, ny, *a.rng);
-        else if constexpr (FK == FK_RANKS)
-            hipLaunchKernelGGL((k_cos_gemm_split_ranks<MT>), grid, dim3(256), lds, st, qs, gal, a.ginv, a.Q, a.G, a.D, x0, ntx, n_steps,
-                               zeros, xtiles, ny, *a.rnk);
-        else if constexpr (FILT)
-            hipLaunchKernelGGL((k_cos_gemm_split_filt<MT, FK>), grid, dim3(256), lds, st, qs, gal, a.ginv, a.Q, a.G, a.D, a.k,
-                               a.cand_val, a.cand_idx, x0, ntx, n_steps, zeros, xtiles, ny, *a.filt);
-        else
-            hipLaunchKernelGGL((k_cos_gemm_split<MT, FK>), grid, dim3(256), lds, st, qs, gal, a.ginv, a.S, a.Q, a.G, a.D, a.k,
-                               a.cand_val, a.cand_idx, x0, ntx, n_steps, zeros, xtiles, ny);
+        hipLaunchKernelGGL((kernel<MT, Epi>()), grid, dim3(256), lds, st, qs, (const float*)a.gal, a.ginv, a.Q, a.G, a.D, x0, ntx,
+                           n_steps, zeros, xtiles, ny, epi);
     }
 };
 
-// Prepared gallery (qry: the split planes of the queries; gal: the gallery's planes): fused selection only, unfiltered
+// Prepared gallery (qry: the split planes of the queries; gal: the gallery's planes): the unfiltered fused selection only
 struct PreparedGemm {
-    static constexpr bool SLAB = false, FILTERED = false, ROC = false, RANGE = false, RANKS = false;
     template <int MT> static constexpr size_t stage_bytes() {   // A ring of 2 (3 at MT = 1), B ring of 3
         return (size_t)(MT == 1 ? 3 : 2) * (64 * MT / 32) * 3 * 1024 + (size_t)3 * (RK_BN / 32) * 3 * 1024;
     }
-    template <int MT, int FK, bool FILT> static const void* kernel() {
-        static_assert(!FILT && FK > 0, "the prepared gallery has fused unfiltered kernels only");
-        return (const void*)k_cos_gemm_pre<MT, FK>;
+    template <int MT, class Epi> static constexpr auto kernel() {
+        static_assert(plain_fk<Epi> > 0, "the prepared gallery has fused unfiltered kernels only");
+        return &k_cos_gemm_pre<MT, plain_fk<Epi>>;
     }
-    template <int MT, int FK, bool FILT>
-    static void launch(dim3 grid, size_t lds, hipStream_t st, const TileArgs& a, int x0, int ntx, int xtiles, int ny) {
-        hipLaunchKernelGGL((k_cos_gemm_pre<MT, FK>), grid, dim3(256), lds, st, (const bf16_t*)a.qry, (const bf16_t*)a.gal, a.S, a.Q,
-                           a.G, a.k, a.cand_val, a.cand_idx, x0, ntx, cdiv(a.D, 16), xtiles, ny);
+    template <int MT, class Epi>
+    static void launch(dim3 grid, size_t lds, hipStream_t st, const TileArgs& a, const Epi& epi, int x0, int ntx, int xtiles, int ny) {
+        hipLaunchKernelGGL((kernel<MT, Epi>()), grid, dim3(256), lds, st, (const bf16_t*)a.qry, (const bf16_t*)a.gal, a.Q, a.G, x0,
+                           ntx, cdiv(a.D, 16), xtiles, ny, epi);
     }
 };
 
@@ -979,36 +1128,35 @@ static bool rank_exact_f32() {
     return e && e[0] && e[0] != '0';
 }
 
-// S != nullptr: score slab.  cand_val / cand_idx != nullptr: fused per-tile top-k lists [Q][cdiv(G,128)][k] (Q > 4 only).
+// One GEMM call over fp32 rows: the normalised queries qn [Q][D] against gal with epilogue epi.
 // qs: scratch for the split planes of these Q queries (split_queries_bytes(Q, D)); may be null for Q <= 4.
-// filt (fused selection only; a score slab is unfiltered): the filter of these Q queries.
-// roc (S null): the histogram of these Q queries; always on the tiles (the GEMV's bits differ), any Q.  rng (S null): the
-// range pass of these Q queries, on the tiles as well; rnk (S null): their counting pass for the ranks, likewise.
-static int cos_gemm(const float* qn, bf16_t* qs, const float* gal, const float* ginv, float* S, i64 Q, i64 G, int D,
-                    hipStream_t st, int k = 0, float* cand_val = nullptr, int* cand_idx = nullptr,
-                    const RankFilter* filt = nullptr, const RocArgs* roc = nullptr, const RangeArgs* rng = nullptr,
-                    const RanksArgs* rnk = nullptr) {
+// Only the score slab has a GEMV (Q <= 4); every other epilogue runs on the tiles for any Q (the GEMV's bits differ).
+template <class Epi>
+static int cos_gemm(const float* qn, bf16_t* qs, const float* gal, const float* ginv, i64 Q, i64 G, int D, const Epi& epi,
+                    hipStream_t st) {
     const bool vec = vec_ok(qn, D) && vec_ok(gal, D);
-    const int fused_bit = cand_val ? MI355_RANK_PATH_FUSED : 0;
-    if (!cand_val && !roc && !rng && !rnk && Q <= 4 && (size_t)Q * D * sizeof(float) <= 60 * 1024) {
-        set_rank_path(MI355_RANK_PATH_GEMV);
-        const size_t lds = (size_t)Q * D * sizeof(float);
-        const unsigned blocks = (unsigned)(cdiv(G, 4) < 4096 ? cdiv(G, 4) : 4096);
-#define GEMV_LAUNCH(NQ) hipLaunchKernelGGL((k_cos_gemv<NQ>), dim3(blocks), dim3(256), lds, st, qn, gal, ginv, S, G, D, (int)vec)
-        if (Q == 1) GEMV_LAUNCH(1); else if (Q == 2) GEMV_LAUNCH(2); else if (Q == 3) GEMV_LAUNCH(3); else GEMV_LAUNCH(4);
+    constexpr int fused_bit = is_select<Epi> ? MI355_RANK_PATH_FUSED : 0;
+    if constexpr (std::is_same_v<Epi, SlabEpi>) {
+        if (Q <= 4 && (size_t)Q * D * sizeof(float) <= 60 * 1024) {
+            set_rank_path(MI355_RANK_PATH_GEMV);
+            const size_t lds = (size_t)Q * D * sizeof(float);
+            const unsigned blocks = (unsigned)(cdiv(G, 4) < 4096 ? cdiv(G, 4) : 4096);
+#define GEMV_LAUNCH(NQ) hipLaunchKernelGGL((k_cos_gemv<NQ>), dim3(blocks), dim3(256), lds, st, qn, gal, ginv, epi.S, G, D, (int)vec)
+            if (Q == 1) GEMV_LAUNCH(1); else if (Q == 2) GEMV_LAUNCH(2); else if (Q == 3) GEMV_LAUNCH(3); else GEMV_LAUNCH(4);
 #undef GEMV_LAUNCH
-        MI355_LAUNCH_CHECK();
-        return OK;
+            MI355_LAUNCH_CHECK();
+            return OK;
+        }
     }
-    TileArgs a{qn, gal, ginv, S, (int)Q, G, D, k, cand_val, cand_idx, filt, roc, rng, rnk};
+    TileArgs a{qn, gal, ginv, (int)Q, G, D};
     if (qs && vec_ok(gal, D) && !rank_exact_f32()) {
         if (int e = split_rows(qn, Q, D, qs, st)) return e;
         set_rank_path(MI355_RANK_PATH_SPLIT | fused_bit);
         a.qry = qs;
-        return cos_gemm_tiles<SplitGemm>(a, st);
+        return cos_gemm_tiles<SplitGemm>(a, epi, st);
     }
     set_rank_path(MI355_RANK_PATH_EXACT_F32 | fused_bit);
-    return vec ? cos_gemm_tiles<F32Gemm<true>>(a, st) : cos_gemm_tiles<F32Gemm<false>>(a, st);
+    return vec ? cos_gemm_tiles<F32Gemm<true>>(a, epi, st) : cos_gemm_tiles<F32Gemm<false>>(a, epi, st);
 }
 
 int normalize_search(const float* queries, i64 Q, const float* gallery, i64 G, int dim, float eps, const RankWs& w,
@@ -1054,9 +1202,123 @@ static int rank_topk(const float* queries, i64 Q, const float* gallery, i64 G, i
     return search_blocks(queries, ginv ? gallery : nullptr, Q, G, dim, k, eps, idx_offset, filt, out_val, out_idx, w, st, nullptr,
                          [&](i64 q0, i64 qn, const RankFilter* f) -> int {
                              RoctxRange range(w.cand_val ? "rank/cosine gemm + per-tile top-k" : nullptr);
-                             return cos_gemm(w.qn + q0 * dim, (bf16_t*)w.qs, gallery, ginv, w.S, qn, G, dim, st, k, w.cand_val,
-                                             w.cand_idx, f);
+                             return with_topk_epi(w, k, f, [&](const auto& epi) {
+                                 return cos_gemm(w.qn + q0 * dim, (bf16_t*)w.qs, gallery, ginv, qn, G, dim, epi, st);
+                             });
                          });
+}
+
+// ---- the searches without a top-k, once for fp32 and fp16 rows (rank_common.h)
+static GalleryRows f32_rows(const float* gallery, int is_normalized) {
+    return {gallery, is_normalized != 0, nullptr, 0, split_queries_bytes};
+}
+static int check_rows(const GalleryRows& g, const char* who) {
+    MI355_REQUIRE(((uintptr_t)g.f16 & 15) == 0, "%s: gallery buffer must be 16-byte aligned", who);
+    return OK;
+}
+// The normalised queries qn [Q][dim] (qs: scratch of g.planes_bytes(Q, dim)) against the rows of g with epilogue epi
+template <class Epi>
+static int score_rows(const GalleryRows& g, const float* ginv, const float* qn, void* qs, i64 Q, i64 G, int dim, const Epi& epi,
+                      hipStream_t st) {
+    if (g.f16) return cos_gemm_f16(g.f16, g.ld, qn, qs, Q, G, dim, epi, st);
+    return cos_gemm(qn, (bf16_t*)qs, g.f32, ginv, Q, G, dim, epi, st);
+}
+
+int roc_pairs_hist(const float* queries, i64 Q, const GalleryRows& g, i64 G, int dim, float eps, const int64_t* query_labels,
+                   const int64_t* gallery_labels, const int64_t* exclude, i64 idx_offset, const double* thresholds,
+                   const double* thresholds_dev, int T, int64_t* hist, void* workspace, size_t workspace_bytes, size_t need,
+                   void* stream, const char* who) {
+    RocArgs roc{};
+    if (int e = roc_check_thresholds(thresholds, T, who, &roc)) return e;
+    if (int e = roc_check_pairs(query_labels, gallery_labels, exclude, idx_offset, thresholds_dev, hist, who, &roc)) return e;
+    MI355_REQUIRE(queries && g.rows(), "%s: null queries/gallery pointer", who);
+    MI355_REQUIRE(Q >= 1 && G >= 1 && dim >= 1, "%s: bad shape Q=%lld G=%lld dim=%d", who, (long long)Q, (long long)G, dim);
+    if (int e = check_rows(g, who)) return e;
+    MI355_REQUIRE(Q <= INT_MAX && G < ((int64_t)1 << 31) - RK_BN, "%s: shape too large Q=%lld G=%lld", who, (long long)Q,
+                  (long long)G);
+    MI355_REQUIRE(workspace && workspace_bytes >= need, "%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
+    const RankWs w = carve(workspace, Q, G, dim, 0, g.planes_bytes, g.f32 && !g.unit, false);
+    hipStream_t st = (hipStream_t)stream;
+    MI355_CHECK_HIP(hipMemsetAsync(hist, 0, (size_t)2 * (T + 1) * sizeof(int64_t), st));
+    const float* ginv = g.f32 && !g.unit ? w.ginv : nullptr;
+    if (int e = normalize_search(queries, Q, ginv ? g.f32 : nullptr, G, dim, eps, w, st)) return e;
+    const i64 qb = roc_query_block(Q, G);
+    for (i64 q0 = 0; q0 < Q; q0 += qb) {
+        const i64 qn = (Q - q0 < qb) ? Q - q0 : qb;
+        RoctxRange range(g.f16 ? "roc/cosine gemm (fp16 gallery) + histogram" : "roc/cosine gemm + histogram");
+        if (int e = score_rows(g, ginv, w.qn + q0 * dim, w.qs, qn, G, dim, roc_from(roc, q0), st)) return e;
+    }
+    return OK;
+}
+
+// candidates: [2][capacity] entries, raw hits of one GEMM call (in reservation order) then the canonical CSR payload of the
+// whole call.  Per query block: zero the cursor, run the range pass, read the block's hit count back (the one host sync), and
+// while everything so far fits compact the block.  Once a block does not fit, the rest only count (cap 0): *nnz is the exact
+// total either way, and a call with capacity >= *nnz fits.
+int cosine_range(const float* queries, i64 Q, const GalleryRows& g, i64 G, int dim, float eps, double threshold, i64 idx_offset,
+                 const mi355_rank_filter* filter, void* candidates, i64 capacity, int64_t* nnz, void* workspace,
+                 size_t workspace_bytes, void* stream, bool keep_all, const char* who) {
+    RankFilter f{};
+    if (int e = range_check(queries, Q, g.rows(), G, dim, threshold, filter, idx_offset, candidates, capacity, nnz, who, &f)) return e;
+    if (int e = check_rows(g, who)) return e;
+    const RangeWs w = range_carve(workspace, Q, G, dim, g.planes_bytes, g.f32 && !g.unit);
+    MI355_REQUIRE(workspace && workspace_bytes >= w.total, "%s: workspace %zu < %zu bytes", who, workspace_bytes, w.total);
+    hipStream_t st = (hipStream_t)stream;
+    if (Q == 0 || G == 0) return range_empty(w, Q, nnz, st);
+    const float* ginv = g.f32 && !g.unit ? w.w.ginv : nullptr;
+    if (int e = normalize_search(queries, Q, ginv ? g.f32 : nullptr, G, dim, eps, w.w, st)) return e;
+    unsigned long long* raw = (unsigned long long*)candidates;
+    unsigned long long* canon = raw ? raw + capacity : nullptr;
+    MI355_CHECK_HIP(hipMemsetAsync(w.offsets, 0, sizeof(i64), st));
+    const i64 qb = range_query_block(Q, G);
+    i64 off = 0;
+    bool fits = true;
+    for (i64 q0 = 0; q0 < Q; q0 += qb) {
+        const i64 qn = (Q - q0 < qb) ? Q - q0 : qb;
+        MI355_CHECK_HIP(hipMemsetAsync(w.cursor, 0, sizeof(unsigned long long), st));
+        const RangeArgs a{filter_from(f, q0), roc_ceil_f32(threshold), w.cursor, raw, fits ? capacity : 0, w.tstart, w.tcount,
+                          keep_all ? 1 : 0};
+        {
+            RoctxRange range(keep_all ? "ranks/positives" : g.f16 ? "range/cosine gemm (fp16 gallery) + hits" : "range/cosine gemm + hits");
+            if (int e = score_rows(g, ginv, w.w.qn + q0 * dim, w.w.qs, qn, G, dim, a, st)) return e;
+        }
+        unsigned long long n = 0;
+        MI355_CHECK_HIP(hipMemcpyAsync(&n, w.cursor, sizeof(n), hipMemcpyDeviceToHost, st));
+        MI355_CHECK_HIP(hipStreamSynchronize(st));
+        fits = fits && off + (i64)n <= capacity;
+        if (fits) {
+            RoctxRange range("range/compact");
+            if (int e = range_compact_block(w, q0, qn, G, off, raw, canon, st)) return e;
+        }
+        off += (i64)n;
+    }
+    *nnz = off;
+    return OK;
+}
+
+int rank_positives(const float* queries, i64 Q, const GalleryRows& g, i64 G, int dim, float eps, const int64_t* query_labels,
+                   const int64_t* gallery_labels, const int64_t* exclude, i64 idx_offset, const int64_t* offsets,
+                   const int64_t* offsets_host, const uint64_t* pos_keys, i64 nnz, uint32_t* before, i64 query_block,
+                   void* workspace, size_t workspace_bytes, size_t need, void* stream, const char* who) {
+    RanksArgs rk{};
+    if (int e = ranks_check(queries, Q, g.rows(), G, dim, query_labels, gallery_labels, exclude, idx_offset, offsets, offsets_host,
+                            pos_keys, nnz, before, query_block, who, &rk))
+        return e;
+    if (int e = check_rows(g, who)) return e;
+    MI355_REQUIRE(workspace && workspace_bytes >= need, "%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
+    const RankWs w = carve(workspace, Q, G, dim, 0, g.planes_bytes, g.f32 && !g.unit, false);
+    hipStream_t st = (hipStream_t)stream;
+    if (nnz == 0) return OK;                                    // no query has a positive: nothing to count
+    MI355_CHECK_HIP(hipMemsetAsync(before, 0, (size_t)nnz * sizeof(uint32_t), st));
+    const float* ginv = g.f32 && !g.unit ? w.ginv : nullptr;
+    if (int e = normalize_search(queries, Q, ginv ? g.f32 : nullptr, G, dim, eps, w, st)) return e;
+    const i64 qb = ranks_query_block(Q, G, query_block);
+    for (i64 q0 = 0; q0 < Q; q0 += qb) {
+        const i64 qn = (Q - q0 < qb) ? Q - q0 : qb;
+        RoctxRange range("ranks/count");
+        if (int e = score_rows(g, ginv, w.qn + q0 * dim, w.qs, qn, G, dim, ranks_from(rk, q0), st)) return e;
+    }
+    return OK;
 }
 
 }  // namespace mi355
@@ -1091,19 +1353,11 @@ int mi355_cosine_scores(const float* queries, int64_t Q, const float* gallery, i
     RankWs w = carve(workspace, Q, G, dim, 0, split_queries_bytes, !gallery_is_normalized, false);
     MI355_REQUIRE(workspace && workspace_bytes >= w.total, "cosine_scores: workspace %zu < %zu bytes",
                   workspace_bytes, w.total);
-    const int vq = vec_ok(queries, dim) && vec_ok(w.qn, dim);
-    hipLaunchKernelGGL((k_row_norm<true>), dim3((unsigned)cdiv(Q, 4)), dim3(256), 0, st, queries, w.qn,
-                       (float*)nullptr, (i64)Q, dim, eps, vq);
-    MI355_LAUNCH_CHECK();
-    if (!gallery_is_normalized) {
-        hipLaunchKernelGGL((k_row_norm<false>), dim3((unsigned)cdiv(G, 4)), dim3(256), 0, st, gallery,
-                           (float*)nullptr, w.ginv, (i64)G, dim, eps, vec_ok(gallery, dim));
-        MI355_LAUNCH_CHECK();
-    }
     const float* ginv = gallery_is_normalized ? nullptr : w.ginv;
+    if (int e = normalize_search(queries, Q, ginv ? gallery : nullptr, G, dim, eps, w, st)) return e;
     for (i64 qs = 0; qs < Q; qs += 256 * 64) {  // grid.y stays small
         const i64 qn = (Q - qs < 256 * 64) ? Q - qs : 256 * 64;
-        if (int e = cos_gemm(w.qn + qs * dim, (bf16_t*)w.qs, gallery, ginv, out + qs * G, qn, G, dim, st)) return e;
+        if (int e = cos_gemm(w.qn + qs * dim, (bf16_t*)w.qs, gallery, ginv, qn, G, dim, SlabEpi{out + qs * G}, st)) return e;
     }
     return OK;
 }
@@ -1139,30 +1393,9 @@ int mi355_roc_pairs_hist(const float* queries, int64_t Q, const float* gallery, 
                          float eps, const int64_t* query_labels, const int64_t* gallery_labels, const int64_t* exclude,
                          int64_t idx_offset, const double* thresholds, const double* thresholds_dev, int T, int64_t* hist,
                          void* workspace, size_t workspace_bytes, void* stream) {
-    const char* who = "roc_pairs_hist";
-    RocArgs roc{};
-    if (int e = roc_check_thresholds(thresholds, T, who, &roc)) return e;
-    if (int e = roc_check_pairs(query_labels, gallery_labels, exclude, idx_offset, thresholds_dev, hist, who, &roc)) return e;
-    MI355_REQUIRE(queries && gallery, "%s: null queries/gallery pointer", who);
-    MI355_REQUIRE(Q >= 1 && G >= 1 && dim >= 1, "%s: bad shape Q=%lld G=%lld dim=%d", who, (long long)Q, (long long)G, dim);
-    MI355_REQUIRE(Q <= INT_MAX && G < ((int64_t)1 << 31) - RK_BN, "%s: shape too large Q=%lld G=%lld", who, (long long)Q,
-                  (long long)G);
-    const i64 qb = roc_query_block(Q, G);
-    const RankWs w = carve(workspace, Q, G, dim, 0, split_queries_bytes, !gallery_is_normalized, false);
-    const size_t need = mi355_roc_pairs_workspace_bytes(Q, G, dim);
-    MI355_REQUIRE(workspace && workspace_bytes >= need, "%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
-    hipStream_t st = (hipStream_t)stream;
-    MI355_CHECK_HIP(hipMemsetAsync(hist, 0, (size_t)2 * (T + 1) * sizeof(int64_t), st));
-    const float* ginv = gallery_is_normalized ? nullptr : w.ginv;
-    if (int e = normalize_search(queries, Q, ginv ? gallery : nullptr, G, dim, eps, w, st)) return e;
-    for (i64 q0 = 0; q0 < Q; q0 += qb) {
-        const i64 qn = (Q - q0 < qb) ? Q - q0 : qb;
-        const RocArgs rb = roc_from(roc, q0);
-        RoctxRange range("roc/cosine gemm + histogram");
-        if (int e = cos_gemm(w.qn + q0 * dim, (bf16_t*)w.qs, gallery, ginv, nullptr, qn, G, dim, st, 0, nullptr, nullptr, nullptr, &rb))
-            return e;
-    }
-    return OK;
+    return roc_pairs_hist(queries, Q, f32_rows(gallery, gallery_is_normalized), G, dim, eps, query_labels, gallery_labels, exclude,
+                          idx_offset, thresholds, thresholds_dev, T, hist, workspace, workspace_bytes,
+                          mi355_roc_pairs_workspace_bytes(Q, G, dim), stream, "roc_pairs_hist");
 }
 
 size_t mi355_range_workspace_bytes(int64_t Q, int64_t G, int dim) {
@@ -1170,43 +1403,19 @@ size_t mi355_range_workspace_bytes(int64_t Q, int64_t G, int dim) {
     return range_carve(nullptr, Q, G, dim, split_queries_bytes, true).total;
 }
 
-}  // extern "C"
-
-// mi355_cosine_range and, with keep_all, mi355_positives_range, under the name who
-static int cosine_range(const float* queries, int64_t Q, const float* gallery, int64_t G, int dim, int gallery_is_normalized,
-                        float eps, double threshold, int64_t idx_offset, const mi355_rank_filter* filter, void* candidates,
-                        int64_t capacity, int64_t* nnz, void* workspace, size_t workspace_bytes, void* stream, bool keep_all,
-                        const char* who) {
-    RankFilter f{};
-    if (int e = range_check(queries, Q, gallery, G, dim, threshold, filter, idx_offset, candidates, capacity, nnz, who, &f)) return e;
-    const RangeWs w = range_carve(workspace, Q, G, dim, split_queries_bytes, !gallery_is_normalized);
-    MI355_REQUIRE(workspace && workspace_bytes >= w.total, "%s: workspace %zu < %zu bytes", who, workspace_bytes, w.total);
-    hipStream_t st = (hipStream_t)stream;
-    if (Q == 0 || G == 0) return range_empty(w, Q, nnz, st);
-    const float* ginv = gallery_is_normalized ? nullptr : w.w.ginv;
-    if (int e = normalize_search(queries, Q, ginv ? gallery : nullptr, G, dim, eps, w.w, st)) return e;
-    return range_blocks(Q, G, f, threshold, candidates, capacity, nnz, w, st, [&](i64 q0, i64 qn, const RangeArgs& a) -> int {
-        RoctxRange range(keep_all ? "ranks/positives" : "range/cosine gemm + hits");
-        return cos_gemm(w.w.qn + q0 * dim, (bf16_t*)w.w.qs, gallery, ginv, nullptr, qn, G, dim, st, 0, nullptr, nullptr, nullptr,
-                        nullptr, &a);
-    }, keep_all);
-}
-
-extern "C" {
-
 int mi355_cosine_range(const float* queries, int64_t Q, const float* gallery, int64_t G, int dim, int gallery_is_normalized,
                        float eps, double threshold, int64_t idx_offset, const mi355_rank_filter* filter, void* candidates,
                        int64_t capacity, int64_t* nnz, void* workspace, size_t workspace_bytes, void* stream) {
-    return cosine_range(queries, Q, gallery, G, dim, gallery_is_normalized, eps, threshold, idx_offset, filter, candidates, capacity,
-                        nnz, workspace, workspace_bytes, stream, false, "cosine_range");
+    return cosine_range(queries, Q, f32_rows(gallery, gallery_is_normalized), G, dim, eps, threshold, idx_offset, filter, candidates,
+                        capacity, nnz, workspace, workspace_bytes, stream, false, "cosine_range");
 }
 
 int mi355_positives_range(const float* queries, int64_t Q, const float* gallery, int64_t G, int dim, int gallery_is_normalized,
                           float eps, int64_t idx_offset, const mi355_rank_filter* filter, void* candidates, int64_t capacity,
                           int64_t* nnz, void* workspace, size_t workspace_bytes, void* stream) {
     MI355_REQUIRE(filter && filter->label_mode == MI355_LABEL_SAME, "positives_range: needs a filter with MI355_LABEL_SAME");
-    return cosine_range(queries, Q, gallery, G, dim, gallery_is_normalized, eps, 0.0, idx_offset, filter, candidates, capacity, nnz,
-                        workspace, workspace_bytes, stream, true, "positives_range");
+    return cosine_range(queries, Q, f32_rows(gallery, gallery_is_normalized), G, dim, eps, 0.0, idx_offset, filter, candidates,
+                        capacity, nnz, workspace, workspace_bytes, stream, true, "positives_range");
 }
 
 size_t mi355_rank_positives_workspace_bytes(int64_t Q, int64_t G, int dim) { return mi355_roc_pairs_workspace_bytes(Q, G, dim); }
@@ -1216,29 +1425,9 @@ int mi355_rank_positives(const float* queries, int64_t Q, const float* gallery, 
                          int64_t idx_offset, const int64_t* offsets, const int64_t* offsets_host, const uint64_t* pos_keys,
                          int64_t nnz, uint32_t* before, int64_t query_block, void* workspace, size_t workspace_bytes,
                          void* stream) {
-    const char* who = "rank_positives";
-    RanksArgs rk{};
-    if (int e = ranks_check(queries, Q, gallery, G, dim, query_labels, gallery_labels, exclude, idx_offset, offsets, offsets_host,
-                            pos_keys, nnz, before, query_block, who, &rk))
-        return e;
-    const i64 qb = ranks_query_block(Q, G, query_block);
-    const RankWs w = carve(workspace, Q, G, dim, 0, split_queries_bytes, !gallery_is_normalized, false);
-    const size_t need = mi355_rank_positives_workspace_bytes(Q, G, dim);
-    MI355_REQUIRE(workspace && workspace_bytes >= need, "%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
-    hipStream_t st = (hipStream_t)stream;
-    if (nnz == 0) return OK;                                    // no query has a positive: nothing to count
-    MI355_CHECK_HIP(hipMemsetAsync(before, 0, (size_t)nnz * sizeof(uint32_t), st));
-    const float* ginv = gallery_is_normalized ? nullptr : w.ginv;
-    if (int e = normalize_search(queries, Q, ginv ? gallery : nullptr, G, dim, eps, w, st)) return e;
-    for (i64 q0 = 0; q0 < Q; q0 += qb) {
-        const i64 qn = (Q - q0 < qb) ? Q - q0 : qb;
-        const RanksArgs rb = ranks_from(rk, q0);
-        RoctxRange range("ranks/count");
-        if (int e = cos_gemm(w.qn + q0 * dim, (bf16_t*)w.qs, gallery, ginv, nullptr, qn, G, dim, st, 0, nullptr, nullptr, nullptr,
-                             nullptr, nullptr, &rb))
-            return e;
-    }
-    return OK;
+    return rank_positives(queries, Q, f32_rows(gallery, gallery_is_normalized), G, dim, eps, query_labels, gallery_labels, exclude,
+                          idx_offset, offsets, offsets_host, pos_keys, nnz, before, query_block, workspace, workspace_bytes,
+                          mi355_rank_positives_workspace_bytes(Q, G, dim), stream, "rank_positives");
 }
 
 int mi355_clear_pads(float* val, int64_t* idx, int64_t n, int64_t lo, int64_t hi, void* stream) {
@@ -1296,8 +1485,9 @@ int mi355_rank_topk_prepared(const float* queries, int64_t Q, const void* galler
                              RoctxRange range("rank/cosine gemm (prepared gallery) + per-tile top-k");
                              if (int e = split_rows(w.qn + q0 * dim, qn, dim, (bf16_t*)w.qs, st)) return e;
                              set_rank_path(MI355_RANK_PATH_PREPARED | MI355_RANK_PATH_FUSED);
-                             return cos_gemm_tiles<PreparedGemm>({w.qs, gallery_planes, nullptr, nullptr, (int)qn, G, dim, k, w.cand_val,
-                                                                  w.cand_idx, nullptr}, st);
+                             return with_select_epi<false>(k, w.cand_val, w.cand_idx, RankFilter{}, [&](const auto& epi) {
+                                 return cos_gemm_tiles<PreparedGemm>({w.qs, gallery_planes, nullptr, (int)qn, G, dim}, epi, st);
+                             });
                          });
 }
 

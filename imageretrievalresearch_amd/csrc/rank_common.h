@@ -1,13 +1,14 @@
 // Shared between the rank kernels (rank.hip: fp32 rows, bf16 planes; rank_f16.hip: fp16 rows): the launch order of the
-// cosine GEMM's tiles, its epilogue (score slab or fused per-tile top-k), the host side of the top-k selection that
-// merges what the epilogue leaves, the one launcher of every tiled GEMM and the query-block loop of every search.
-// gfx950 only.
+// cosine GEMM's tiles, its epilogues (one type each: score slab, fused per-tile top-k, ROC histogram, range hits, full-gallery
+// ranks), the host side of the top-k selection that merges what the fused epilogue leaves, the one launcher of every tiled
+// GEMM and the query-block loop of every top-k search.  gfx950 only.
 #pragma once
 #include "common.h"
 #include "../../include/mi355_retrieval.h"
 
 #include <limits.h>
 #include <math.h>
+#include <type_traits>
 
 namespace mi355 {
 
@@ -85,22 +86,75 @@ __device__ __forceinline__ void rank_tile_of(int L, int ntiles, int ny, int& tx,
     }
 }
 
-// Epilogue shared by the exact-fp32 and the split-bf16 loops (same accumulator layout: the C/D map of the 32x32 MFMAs does
-// not depend on the input type): FK = 0 writes the score slab, FK > 0 selects per-tile candidates.  Called after a
-// __syncthreads() that retired every read of the staging buffers (smem is reused).
-// FILT (FK > 0 only): columns the filter rejects enter the selection as key 0, i.e. never.  The tile's 128 gallery labels are
-// read once per workgroup into LDS behind the transposed tile (64 x 132 floats + 1 KB stays inside every loop's staging
-// buffers, so the LDS request and the resident workgroups per CU are those of the unfiltered kernel).
-template <int MT, int FK, bool FILT = false>
-__device__ __forceinline__ void cos_gemm_epilogue(f32x16 (&acc)[MT][2], float* smem, const float* __restrict__ ginv,
-                                                  float* __restrict__ S, int Q, i64 G, int k, float* __restrict__ cand_val,
-                                                  int* __restrict__ cand_idx, int x0, int ntx, i64 n0, int m0,
-                                                  const RankFilter& flt = RankFilter{}) {
-    static_assert(!FILT || FK > 0, "the filter applies to the fused selection");
-    constexpr int BM = 64 * MT;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1, lr = lane & 31;
-    if constexpr (FK > 0) {
+// ---- the epilogues of the tiled cosine GEMM.  Every loop (exact fp32, split bf16, prepared planes, fp16 rows) leaves the same
+// accumulator layout (the C/D map of the 32x32 MFMAs does not depend on the input type) and ends in epi.tile(acc, smem, ginv,
+// t), after a __syncthreads() that retired every read of its staging buffers (smem is reused).  An epilogue is one type:
+//   its arguments (the members; it travels to the kernel by value),
+//   tile(): what a workgroup does with its (64 * MT) x 128 accumulators; scores are acc * ginv[col] in every epilogue,
+//   lds_bytes<STAGE>(): the dynamic LDS of a kernel whose loop stages STAGE bytes.
+// Where a workgroup's tile lies: queries [m0, m0 + 64 * MT) of Q, gallery rows [n0, n0 + 128) of G (ntx column tiles)
+struct TileCtx {
+    int Q;
+    i64 G;
+    int ntx;
+    i64 n0;
+    int m0;
+};
+
+// The score slab S [Q][G]
+struct SlabEpi {
+    float* S;
+    template <size_t STAGE> static constexpr size_t lds_bytes() { return STAGE; }
+    template <int MT>
+    __device__ __forceinline__ void tile(f32x16 (&acc)[MT][2], float*, const float* __restrict__ ginv, const TileCtx& t) const {
+        const int Q = t.Q, m0 = t.m0;
+        const i64 G = t.G, n0 = t.n0;
+        const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+        const int wm = wave >> 1, wn = wave & 1, lr = lane & 31;
+        // C[row = query][col = gallery]; lane: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const i64 col = n0 + wn * 64 + j * 32 + lr;
+            if (col >= G) continue;
+            const float gs = ginv ? ginv[col] : 1.0f;
+#pragma unroll
+            for (int i = 0; i < MT; ++i) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int row = m0 + wm * MT * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                    if (row < Q) S[(i64)row * G + col] = acc[i][j][r] * gs;
+                }
+            }
+        }
+    }
+};
+
+constexpr size_t EPI_TILE_BYTES = (size_t)64 * (RK_BN + 4) * sizeof(float);   // the fused selection's transposed score tile
+
+// The fused selection (k <= FK): the score tile never leaves the CU, k (score, local int32 index) candidates per (query,
+// column tile) go to cand_val / cand_idx [Q][ntx][k].
+// FILT: columns the filter rejects enter the selection as key 0, i.e. never.  The tile's 128 gallery labels are read once per
+// workgroup into LDS behind the transposed tile (64 x 132 floats + 1 KB stays inside every loop's staging buffers, so the
+// LDS request and the resident workgroups per CU are those of the unfiltered kernel).
+template <int FK, bool FILT>
+struct SelectEpi {
+    int k;
+    float* cand_val;
+    int* cand_idx;
+    RankFilter flt;             // FILT: the filter of this call's queries
+    // LDS: the staging buffers, or the transposed score tile (64 rows at a time) if that is larger
+    template <size_t STAGE> static constexpr size_t lds_bytes() {
+        static_assert(!FILT || STAGE >= EPI_TILE_BYTES + FILT_LABELS_BYTES, "the filtered epilogue would grow the GEMM's LDS");
+        return EPI_TILE_BYTES > STAGE ? EPI_TILE_BYTES : STAGE;
+    }
+    template <int MT>
+    __device__ __forceinline__ void tile(f32x16 (&acc)[MT][2], float* smem, const float* __restrict__ ginv, const TileCtx& t) const {
+        static_assert(FK > 0, "the fused selection keeps at least one candidate");
+        const int Q = t.Q, ntx = t.ntx, m0 = t.m0;
+        const i64 G = t.G, n0 = t.n0;
+        constexpr int BM = 64 * MT;
+        const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+        const int wm = wave >> 1, wn = wave & 1, lr = lane & 31;
         // (the loop's last __syncthreads() retired every read of the staging buffers)
         // 64 query rows at a time, so that the transposed tile (64 x 132 floats = 33.8 KB) fits inside the staging
         // buffers: a bigger LDS request would cost the third resident workgroup per CU and with it a round of tiles
@@ -191,26 +245,10 @@ __device__ __forceinline__ void cos_gemm_epilogue(f32x16 (&acc)[MT][2], float* s
             }
             __syncthreads();
         }
-        return;
     }
-    // epilogue: C[row = query][col = gallery]; lane: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const i64 col = n0 + wn * 64 + j * 32 + lr;
-        if (col >= G) continue;
-        const float gs = ginv ? ginv[col] : 1.0f;
-#pragma unroll
-        for (int i = 0; i < MT; ++i) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = m0 + wm * MT * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                if (row < Q) S[(i64)row * G + col] = acc[i][j][r] * gs;
-            }
-        }
-    }
-}
+};
 
-// ---- verification ROC (mi355_roc_pairs_hist[_f16]): the third epilogue mode bins every (query, gallery row) score of the
+// ---- verification ROC (mi355_roc_pairs_hist[_f16]): the histogram epilogue bins every (query, gallery row) score of the
 // tile by (genuine / impostor, threshold) into a per-workgroup histogram; the score slab never exists.
 // Bin b of a score s = the number of thresholds t with s >= t (0 .. T), compared in fp32 against the fp32 CEILING of each
 // float64 t (the smallest float f with (double)f >= t), which is exactly the float64 comparison for every fp32 score.
@@ -218,7 +256,9 @@ __device__ __forceinline__ void cos_gemm_epilogue(f32x16 (&acc)[MT][2], float* s
 constexpr int ROC_MAX_T = MI355_ROC_MAX_THRESHOLDS;
 constexpr int ROC_SUB_T = 1024;                         // T <= this: one sub-histogram per wave (less LDS-atomic contention)
 constexpr int ROC_BIN_WORDS = ROC_MAX_T + 4;            // = 4 * (ROC_SUB_T + 1): either layout fits
-constexpr int FK_ROC = -1;                              // the histogram mode in the launcher's FK slot
+// LDS of the histogram epilogue: threshold table, bins, the tile's gallery labels, its query labels and excluded rows
+constexpr size_t ROC_EPI_BYTES = (size_t)ROC_MAX_T * sizeof(float) + (size_t)ROC_BIN_WORDS * sizeof(unsigned) +
+                                 (size_t)3 * RK_BN * sizeof(i64);
 
 __host__ __device__ __forceinline__ float roc_ceil_f32(double t) {
     float f = (float)t;                                 // round to nearest
@@ -237,6 +277,9 @@ struct RocArgs {
     int top;                    // largest power of two <= T (binary search)
     int uniform;                // 1: guess the bin as 1 + (s - ceil(thr[0])) * scale, then fix it with compares
     float scale;
+    template <size_t STAGE> static constexpr size_t lds_bytes() { return ROC_EPI_BYTES > STAGE ? ROC_EPI_BYTES : STAGE; }
+    template <int MT>
+    __device__ __forceinline__ void tile(f32x16 (&acc)[MT][2], float* smem, const float* __restrict__ ginv, const TileCtx& t) const;
 };
 
 // The bin of score s against the ascending table tab[T] in LDS (fp32 ceilings; float64 thresholds for float64 scores)
@@ -256,20 +299,15 @@ __device__ __forceinline__ int roc_bin(V s, const V* tab, const RocArgs& a) {
     return b;
 }
 
-// LDS of the histogram epilogue: threshold table, bins, the tile's gallery labels, its query labels and excluded rows
-constexpr size_t ROC_EPI_BYTES = (size_t)ROC_MAX_T * sizeof(float) + (size_t)ROC_BIN_WORDS * sizeof(unsigned) +
-                                 (size_t)3 * RK_BN * sizeof(i64);
-
-// The histogram epilogue: the overload of cos_gemm_epilogue that a kernel twin selects by passing RocArgs where the others pass
-// a RankFilter (the rank_gemm_*.inc bodies end with the same call either way).  Scores are acc * ginv[col] as in the other
-// modes, so every pair gets the bits of mi355_cosine_scores on the same loop.  Counts go into LDS as ONE u32 per bin
-// holding both classes (genuine adds 1 << 16, impostor 1: a tile has at most 128 x 128 = 16384 pairs, the halves cannot
-// carry), then to roc.hist with one 64-bit atomic per non-zero (bin, class), one lane per bin.  Called after a
-// __syncthreads() that retired every read of the staging buffers.
-template <int MT, int FK, bool FILT>
-__device__ __forceinline__ void cos_gemm_epilogue(f32x16 (&acc)[MT][2], float* smem, const float* __restrict__ ginv, float*, int Q,
-                                                  i64 G, int, float*, int*, int, int, i64 n0, int m0, const RocArgs& roc) {
-    static_assert(FK == FK_ROC && !FILT, "the histogram twins pass FK = FK_ROC, FILT = false");
+// The histogram epilogue.  Scores are acc * ginv[col] as in the other epilogues, so every pair gets the bits of
+// mi355_cosine_scores on the same loop.  Counts go into LDS as ONE u32 per bin holding both classes (genuine adds 1 << 16,
+// impostor 1: a tile has at most 128 x 128 = 16384 pairs, the halves cannot carry), then to roc.hist with one 64-bit atomic
+// per non-zero (bin, class), one lane per bin.
+template <int MT>
+__device__ __forceinline__ void RocArgs::tile(f32x16 (&acc)[MT][2], float* smem, const float* __restrict__ ginv, const TileCtx& t) const {
+    const RocArgs& roc = *this;
+    const int Q = t.Q, m0 = t.m0;
+    const i64 G = t.G, n0 = t.n0;
     constexpr int BM = 64 * MT;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1, lr = lane & 31;
@@ -318,12 +356,15 @@ __device__ __forceinline__ void cos_gemm_epilogue(f32x16 (&acc)[MT][2], float* s
     }
 }
 
-// ---- cosine range search (mi355_cosine_range[_f16]): the fourth epilogue mode keeps every (query, gallery row) pair whose score
+// ---- cosine range search (mi355_cosine_range[_f16]): the range epilogue keeps every (query, gallery row) pair whose score
 // is >= the threshold (float64 comparison: fp32 score >= roc_ceil_f32(t); NaN never), filtered as the top-k search filters.
 // Per (query row, column tile) the hits are a bit mask in LDS; one 64-bit atomic per workgroup reserves the tile's hits in a
 // candidate buffer, where each row's hits land in ascending column order, and (start, count) of each (query, tile) goes to
 // a table that the compaction (range.hip) walks in tile order: the output never depends on the order of the atomics.
-constexpr int FK_RANGE = -2;                            // the range mode in the launcher's FK slot
+// LDS of the range epilogue: hit masks [BM][4] u32, row counts / prefixes [BM], the workgroup's base, then the tile's gallery
+// labels [128], its query labels and LOCAL excluded rows [BM]
+constexpr size_t RANGE_EPI_BYTES = (size_t)128 * 4 * sizeof(unsigned) + (size_t)128 * sizeof(int) + 2 * sizeof(i64) +
+                                   (size_t)(RK_BN + 2 * 128) * sizeof(i64);
 
 struct RangeArgs {
     RankFilter f;               // the filter of this call's queries (mode ANY and excl null: none)
@@ -334,21 +375,21 @@ struct RangeArgs {
     i64* tstart;                // [Q][ntx] first raw entry of (query, column tile)
     int* tcount;                // [Q][ntx] its hits
     int keep_all;               // 1: every eligible pair is a hit whatever its score, NaN included (mi355_positives_range)
+    template <size_t STAGE> static constexpr size_t lds_bytes() {   // inside the staging buffers of every loop
+        static_assert(STAGE >= RANGE_EPI_BYTES, "the range epilogue would grow the GEMM's LDS");
+        return STAGE;
+    }
+    template <int MT>
+    __device__ __forceinline__ void tile(f32x16 (&acc)[MT][2], float* smem, const float* __restrict__ ginv, const TileCtx& t) const;
 };
 
-// LDS of the range epilogue: hit masks [BM][4] u32, row counts / prefixes [BM], the workgroup's base, then the tile's gallery
-// labels [128], its query labels and LOCAL excluded rows [BM] (inside the staging buffers of every loop: static_assert in
-// launch_tiles)
-constexpr size_t RANGE_EPI_BYTES = (size_t)128 * 4 * sizeof(unsigned) + (size_t)128 * sizeof(int) + 2 * sizeof(i64) +
-                                   (size_t)(RK_BN + 2 * 128) * sizeof(i64);
-
-// The range epilogue: the overload of cos_gemm_epilogue that a kernel twin selects by passing RangeArgs (see the histogram
-// epilogue).  Scores are acc * ginv[col] as in the other modes: every hit has the bits of mi355_cosine_scores on the same loop.
-// Called after a __syncthreads() that retired every read of the staging buffers.
-template <int MT, int FK, bool FILT>
-__device__ __forceinline__ void cos_gemm_epilogue(f32x16 (&acc)[MT][2], float* smem, const float* __restrict__ ginv, float*, int Q,
-                                                  i64 G, int, float*, int*, int, int ntx, i64 n0, int m0, const RangeArgs& rg) {
-    static_assert(FK == FK_RANGE && !FILT, "the range twins pass FK = FK_RANGE, FILT = false");
+// The range epilogue.  Scores are acc * ginv[col] as in the other epilogues: every hit has the bits of mi355_cosine_scores on
+// the same loop.
+template <int MT>
+__device__ __forceinline__ void RangeArgs::tile(f32x16 (&acc)[MT][2], float* smem, const float* __restrict__ ginv, const TileCtx& t) const {
+    const RangeArgs& rg = *this;
+    const int Q = t.Q, ntx = t.ntx, m0 = t.m0;
+    const i64 G = t.G, n0 = t.n0;
     constexpr int BM = 64 * MT;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1, lr = lane & 31;
@@ -444,16 +485,19 @@ __device__ __forceinline__ void cos_gemm_epilogue(f32x16 (&acc)[MT][2], float* s
     }
 }
 
-// ---- full-gallery ranks (mi355_rank_positives[_f16]): the fifth epilogue mode counts, per query, every eligible row that is
+// ---- full-gallery ranks (mi355_rank_positives[_f16]): the ranks epilogue counts, per query, every eligible row that is
 // NOT a positive (label differs) into one bin: the number b of the query's positives that rank before it.  The order is the
 // top-k search's, as one 64-bit composite per (score, row): higher score_key first, on equal keys the lower row.  The query's
 // positives are given as their composites in descending order (keys, CSR over the queries); bin b = R_q (the row beats no
 // positive) is never needed and never written.  Counts are integers: the result does not depend on the order of the atomics.
-constexpr int FK_RANKS = -3;                            // the ranks mode in the launcher's FK slot
-
 __host__ __device__ __forceinline__ unsigned long long rank_composite(unsigned key, unsigned local_row) {
     return ((unsigned long long)key << 32) | (unsigned)~local_row;
 }
+
+// LDS of the ranks epilogue: the tile's gallery labels [128], its query labels, LOCAL excluded rows and CSR starts [BM] (i64),
+// each query's weakest positive composite [BM] and its R_q [BM]
+constexpr size_t RANKS_EPI_BYTES = (size_t)(RK_BN + 3 * 128) * sizeof(i64) + (size_t)128 * sizeof(unsigned long long) +
+                                   (size_t)128 * sizeof(int);
 
 struct RanksArgs {
     const i64* qlab;            // [Q] labels of the queries of this call (the host shifts them per query block)
@@ -463,24 +507,23 @@ struct RanksArgs {
     const i64* offsets;         // [Q + 1] of this call's queries: positions in keys / before (absolute, not per block)
     const unsigned long long* keys;   // [nnz] composites of each query's positives, descending
     unsigned* before;           // [nnz] before[offsets[q] + b] += 1 per negative that exactly b positives of q beat
+    template <size_t STAGE> static constexpr size_t lds_bytes() {   // inside the staging buffers of every loop
+        static_assert(STAGE >= RANKS_EPI_BYTES, "the ranks epilogue would grow the GEMM's LDS");
+        return STAGE;
+    }
+    template <int MT>
+    __device__ __forceinline__ void tile(f32x16 (&acc)[MT][2], float* smem, const float* __restrict__ ginv, const TileCtx& t) const;
 };
 
-// LDS of the ranks epilogue: the tile's gallery labels [128], its query labels, LOCAL excluded rows and CSR starts [BM] (i64),
-// each query's weakest positive composite [BM] and its R_q [BM] (inside the staging buffers of every loop: static_assert in
-// launch_tiles)
-constexpr size_t RANKS_EPI_BYTES = (size_t)(RK_BN + 3 * 128) * sizeof(i64) + (size_t)128 * sizeof(unsigned long long) +
-                                   (size_t)128 * sizeof(int);
-
-// The ranks epilogue: the overload of cos_gemm_epilogue that a kernel twin selects by passing RanksArgs (see the histogram
-// epilogue).  Scores are acc * ginv[col] as in the other modes: every negative is compared with the bits of
+// The ranks epilogue.  Scores are acc * ginv[col] as in the other epilogues: every negative is compared with the bits of
 // mi355_cosine_scores on the same loop, the bits the positives' composites were made from.  For a trained model most
 // negatives lose against the query's weakest positive and are done after one 64-bit compare; the others binary-search the
-// query's composites in global memory (an L2-resident segment) and add one to their bin.  Called after a __syncthreads()
-// that retired every read of the staging buffers.
-template <int MT, int FK, bool FILT>
-__device__ __forceinline__ void cos_gemm_epilogue(f32x16 (&acc)[MT][2], float* smem, const float* __restrict__ ginv, float*, int Q,
-                                                  i64 G, int, float*, int*, int, int, i64 n0, int m0, const RanksArgs& rk) {
-    static_assert(FK == FK_RANKS && !FILT, "the ranks twins pass FK = FK_RANKS, FILT = false");
+// query's composites in global memory (an L2-resident segment) and add one to their bin.
+template <int MT>
+__device__ __forceinline__ void RanksArgs::tile(f32x16 (&acc)[MT][2], float* smem, const float* __restrict__ ginv, const TileCtx& t) const {
+    const RanksArgs& rk = *this;
+    const int Q = t.Q, m0 = t.m0;
+    const i64 G = t.G, n0 = t.n0;
     constexpr int BM = 64 * MT;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1, lr = lane & 31;
@@ -630,105 +673,63 @@ int whole_round_tiles(int ntx, int ny, int slots);
 
 // ---- host side of the tiled cosine GEMMs: exact fp32, split bf16 (rank.hip: F32Gemm, SplitGemm, PreparedGemm) and fp16
 // (rank_f16.hip: F16Gemm).  A family F supplies only what differs between them:
-//   F::SLAB, F::FILTERED, F::ROC     whether it has score-slab (FK = 0) / filtered / histogram (FK = FK_ROC) kernels
-//   F::RANGE                         whether it has range (FK = FK_RANGE) kernels
-//   F::RANKS                         whether it has ranks (FK = FK_RANKS) kernels
 //   F::stage_bytes<MT>()             the LDS of its staging buffers
-//   F::kernel<MT, FK, FILT>()        its kernel
-//   F::launch<MT, FK, FILT>(...)     one launch of that kernel over column tiles [x0, x0 + xtiles) x ny query tiles
+//   F::kernel<MT, Epi>()             its kernel with epilogue Epi
+//   F::launch<MT, Epi>(...)          one launch of that kernel over column tiles [x0, x0 + xtiles) x ny query tiles
+// Per loop two kernels exist: k_*<MT, FK> for the unfiltered slab (FK = 0) and selection (the names profiles are keyed by), and
+// k_*_epi<MT, Epi> for every other epilogue.  Both take the epilogue as their last argument.
+template <int FK> using PlainEpi = std::conditional_t<FK == 0, SlabEpi, SelectEpi<(FK > 0 ? FK : 1), false>>;
+template <class Epi> constexpr int plain_fk = -1;              // FK of the k_*<MT, FK> kernel that runs Epi; -1: k_*_epi<MT, Epi>
+template <> inline constexpr int plain_fk<SlabEpi> = 0;
+template <int FK> constexpr int plain_fk<SelectEpi<FK, false>> = FK;
+template <class Epi> constexpr bool is_select = false;         // the fused selection (MI355_RANK_PATH_FUSED)
+template <int FK, bool FILT> constexpr bool is_select<SelectEpi<FK, FILT>> = true;
 
-// One GEMM call over Q queries: the fused per-tile lists (cand_val / cand_idx [Q][cdiv(G, 128)][k]) or, with cand_val null,
-// the score slab S [Q][G] (unfiltered: topk_select filters it).
+// What every GEMM call over Q queries shares; the epilogue object travels beside it
 struct TileArgs {
     const void* qry;            // the queries as the family reads them: fp32 rows, bf16 split planes or fp16 planes
     const void* gal;            // the gallery: fp32 rows, bf16 planes (prepared) or fp16 rows
     const float* ginv;          // 1 / |gallery row| (fp32 rows), or null
-    float* S;
     int Q;
     i64 G;
     int D;                      // dim (fp16 rows: their padded length ld)
-    int k;
-    float* cand_val;
-    int* cand_idx;
-    const RankFilter* filt;     // the queries' filter (fused selection), or null
-    const RocArgs* roc;         // the histogram mode (the queries' labels / exclude of this call), or null
-    const RangeArgs* rng;       // the range mode (the queries' filter, candidates and table of this call), or null
-    const RanksArgs* rnk;       // the ranks mode (the queries' labels / exclude / positives of this call), or null
 };
 
-constexpr size_t EPI_TILE_BYTES = (size_t)64 * (RK_BN + 4) * sizeof(float);   // the fused selection's transposed score tile
-
-template <class F, int MT, int FK, bool FILT>
-int tile_slots(size_t lds, int* slots_out) {
-    static int slots[MI355_MAX_DEVICES] = {0};   // per instantiation: hipFuncSetAttribute once per device
-    return kernel_slots((const void*)F::template kernel<MT, FK, FILT>(), lds, slots, slots_out);
-}
-
-// Column tiles [x0, ntx) of a GEMM call.  LDS: the staging buffers, or the fused selection's score tile (64 rows at a time)
-// if that is larger; the filtered epilogue keeps the tile's gallery labels behind the score tile, inside the staging
-// buffers, so the filtered kernels request the LDS of the unfiltered ones.
+// Column tiles [x0, ntx) of a GEMM call.
 // Wave quantisation: 1564 tiles on 768 slots run as 2.04 rounds and the 28 tiles of the third round cost a whole round
 // (0.15 ms of 0.83 at Q=256 x 100k on the fp32 loop).  At MT = 2 whole rounds go out as 128-row tiles and the remaining
 // column tiles as a second launch of 64-row tiles (same column tiles, same k order: every score is bit-identical), which
 // halves the tiles' length and doubles their number.
-template <class F, int MT, int FK, bool FILT>
-int launch_tiles(const TileArgs& a, hipStream_t st, int x0 = 0) {
-    constexpr size_t stage = F::template stage_bytes<MT>();
-    static_assert(!FILT || stage >= EPI_TILE_BYTES + FILT_LABELS_BYTES, "the filtered epilogue would grow the GEMM's LDS");
-    static_assert(FK != FK_RANGE || stage >= RANGE_EPI_BYTES, "the range epilogue would grow the GEMM's LDS");
-    static_assert(FK != FK_RANKS || stage >= RANKS_EPI_BYTES, "the ranks epilogue would grow the GEMM's LDS");
-    constexpr size_t lds = FK == FK_ROC ? (ROC_EPI_BYTES > stage ? ROC_EPI_BYTES : stage)
-                                        : FK > 0 && EPI_TILE_BYTES > stage ? EPI_TILE_BYTES : stage;
+template <class F, int MT, class Epi>
+int launch_tiles(const TileArgs& a, const Epi& epi, hipStream_t st, int x0 = 0) {
+    constexpr size_t lds = Epi::template lds_bytes<F::template stage_bytes<MT>()>();
+    static int cache[MI355_MAX_DEVICES] = {0};   // per instantiation: hipFuncSetAttribute once per device
     int slots = 0;
-    if (int e = tile_slots<F, MT, FK, FILT>(lds, &slots)) return e;
+    if (int e = kernel_slots((const void*)F::template kernel<MT, Epi>(), lds, cache, &slots)) return e;
     const int ntx = cdiv(a.G, RK_BN), ny = cdiv(a.Q, 64 * MT);
     const int x1 = MT == 2 ? whole_round_tiles(ntx, ny, slots) : ntx;
     if (x1 > x0) {
-        F::template launch<MT, FK, FILT>(dim3((unsigned)(x1 - x0) * (unsigned)ny), lds, st, a, x0, ntx, x1 - x0, ny);
+        F::template launch<MT, Epi>(dim3((unsigned)(x1 - x0) * (unsigned)ny), lds, st, a, epi, x0, ntx, x1 - x0, ny);
         MI355_LAUNCH_CHECK();
     }
     if constexpr (MT == 2) {
-        if (x1 < ntx) return launch_tiles<F, 1, FK, FILT>(a, st, x1);
+        if (x1 < ntx) return launch_tiles<F, 1, Epi>(a, epi, st, x1);
     }
     return OK;
 }
+// A GEMM call of family F: 128-query tiles above 64 queries, 64-query tiles otherwise
+template <class F, class Epi>
+int cos_gemm_tiles(const TileArgs& a, const Epi& epi, hipStream_t st) {
+    return a.Q > 64 ? launch_tiles<F, 2, Epi>(a, epi, st) : launch_tiles<F, 1, Epi>(a, epi, st);
+}
 
-// The fused selection keeps FK >= k candidates per (query, column tile)
-template <class F, int MT, bool FILT>
-int launch_fk(const TileArgs& a, hipStream_t st) {
-    if (a.k <= 1) return launch_tiles<F, MT, 1, FILT>(a, st);
-    if (a.k <= 2) return launch_tiles<F, MT, 2, FILT>(a, st);
-    if (a.k <= 4) return launch_tiles<F, MT, 4, FILT>(a, st);
-    return launch_tiles<F, MT, 8, FILT>(a, st);
-}
-template <class F, int MT>
-int launch_mt(const TileArgs& a, hipStream_t st) {
-    if constexpr (F::ROC) {
-        if (a.roc) return launch_tiles<F, MT, FK_ROC, false>(a, st);
-    }
-    if constexpr (F::RANGE) {
-        if (a.rng) return launch_tiles<F, MT, FK_RANGE, false>(a, st);
-    }
-    if constexpr (F::RANKS) {
-        if (a.rnk) return launch_tiles<F, MT, FK_RANKS, false>(a, st);
-    }
-    if constexpr (F::SLAB) {
-        if (!a.cand_val) {
-            TileArgs s = a;
-            s.k = 0;
-            return launch_tiles<F, MT, 0, false>(s, st);
-        }
-    }
-    if constexpr (F::FILTERED) {
-        if (a.filt) return launch_fk<F, MT, true>(a, st);
-    }
-    return launch_fk<F, MT, false>(a, st);
-}
-// A GEMM call of family F: 128-query tiles above 64 queries, 64-query tiles otherwise.  a.roc: the histogram mode, a.rng: the
-// range mode, a.rnk: the ranks mode.
-template <class F>
-int cos_gemm_tiles(const TileArgs& a, hipStream_t st) {
-    return a.Q > 64 ? launch_mt<F, 2>(a, st) : launch_mt<F, 1>(a, st);
+// fn(the fused selection's epilogue for k): it keeps FK >= k candidates per (query, column tile)
+template <bool FILT, class Fn>
+int with_select_epi(int k, float* cand_val, int* cand_idx, const RankFilter& f, Fn&& fn) {
+    if (k <= 1) return fn(SelectEpi<1, FILT>{k, cand_val, cand_idx, f});
+    if (k <= 2) return fn(SelectEpi<2, FILT>{k, cand_val, cand_idx, f});
+    if (k <= 4) return fn(SelectEpi<4, FILT>{k, cand_val, cand_idx, f});
+    return fn(SelectEpi<8, FILT>{k, cand_val, cand_idx, f});
 }
 
 // ---- host side of the ROC entries (roc.cpp)
@@ -753,6 +754,15 @@ RankWs carve(void* ws, i64 Q, i64 G, int D, int k, size_t (*planes_bytes)(i64, i
 // "rank/normalize": the queries into w.qn and, with a gallery, 1 / |row| of its rows into w.ginv
 int normalize_search(const float* queries, i64 Q, const float* gallery, i64 G, int dim, float eps, const RankWs& w,
                      hipStream_t st);
+
+// fn(the epilogue of one GEMM call of a top-k search over the scratch w): the fused per-tile lists cand_val / cand_idx
+// [Q][cdiv(G, 128)][k], filtered by f (null: unfiltered), or the score slab S [Q][G] (unfiltered: topk_select filters it)
+template <class Fn>
+int with_topk_epi(const RankWs& w, int k, const RankFilter* f, Fn&& fn) {
+    if (!w.cand_val) return fn(SlabEpi{w.S});
+    if (f) return with_select_epi<true>(k, w.cand_val, w.cand_idx, *f, fn);
+    return with_select_epi<false>(k, w.cand_val, w.cand_idx, RankFilter{}, fn);
+}
 
 // Normalises the queries, then per block of query_block(Q, G, k) queries: score(q0, qn, f) writes the fused per-tile lists
 // (fused_select) or the score slab of queries [q0, q0 + qn) (f: their filter, or null), and topk_select merges them into
@@ -799,41 +809,6 @@ int range_empty(const RangeWs& w, i64 Q, int64_t* nnz, hipStream_t st);
 int range_compact_block(const RangeWs& w, i64 q0, i64 qn, i64 G, i64 off, const unsigned long long* raw,
                         unsigned long long* canon, hipStream_t st);
 
-// The query-block loop of a range search.  candidates: [2][capacity] entries, raw hits of one GEMM call (in reservation
-// order) then the canonical CSR payload of the whole call.  Per block: zero the cursor, score(q0, qn, args) runs the range
-// pass, the block's hit count is read back (the one host sync), and while everything so far fits the block is compacted.
-// Once a block does not fit, the rest only count (cap 0): *nnz is the exact total either way, and a call with
-// capacity >= *nnz fits.
-// keep_all: every eligible pair is a hit (the threshold is not looked at).
-template <class Score>
-int range_blocks(i64 Q, i64 G, const RankFilter& filt, double threshold, void* candidates, i64 capacity, int64_t* nnz,
-                 const RangeWs& w, hipStream_t st, Score&& score, bool keep_all = false) {
-    unsigned long long* raw = (unsigned long long*)candidates;
-    unsigned long long* canon = raw ? raw + capacity : nullptr;
-    MI355_CHECK_HIP(hipMemsetAsync(w.offsets, 0, sizeof(i64), st));
-    const i64 qb = range_query_block(Q, G);
-    i64 off = 0;
-    bool fits = true;
-    for (i64 q0 = 0; q0 < Q; q0 += qb) {
-        const i64 qn = (Q - q0 < qb) ? Q - q0 : qb;
-        MI355_CHECK_HIP(hipMemsetAsync(w.cursor, 0, sizeof(unsigned long long), st));
-        const RangeArgs a{filter_from(filt, q0), roc_ceil_f32(threshold), w.cursor, raw, fits ? capacity : 0, w.tstart, w.tcount,
-                          keep_all ? 1 : 0};
-        if (int e = score(q0, qn, a)) return e;
-        unsigned long long n = 0;
-        MI355_CHECK_HIP(hipMemcpyAsync(&n, w.cursor, sizeof(n), hipMemcpyDeviceToHost, st));
-        MI355_CHECK_HIP(hipStreamSynchronize(st));
-        fits = fits && off + (i64)n <= capacity;
-        if (fits) {
-            RoctxRange range("range/compact");
-            if (int e = range_compact_block(w, q0, qn, G, off, raw, canon, st)) return e;
-        }
-        off += (i64)n;
-    }
-    *nnz = off;
-    return OK;
-}
-
 // ---- host side of the full-gallery ranks (ranks.hip)
 // The checks mi355_rank_positives[_f16] share (before any HIP call); fills *a
 int ranks_check(const void* queries, i64 Q, const void* gallery, i64 G, int dim, const int64_t* query_labels,
@@ -844,5 +819,35 @@ int ranks_check(const void* queries, i64 Q, const void* gallery, i64 G, int dim,
 RanksArgs ranks_from(const RanksArgs& a, i64 q0);
 // Queries per GEMM call of the counting pass: roc_query_block, or the caller's smaller query_block (> 0)
 i64 ranks_query_block(i64 Q, i64 G, i64 query_block);
+
+
+// ---- the searches without a top-k (ROC histogram, range, ranks) exist once for both kinds of gallery rows (rank.hip)
+// The gallery as a search reads it: fp32 rows [G][dim], or the fp16 rows of mi355_gallery_to_f16
+struct GalleryRows {
+    const float* f32;           // fp32 rows, or null
+    bool unit;                  // fp32 rows: unit length already (no 1 / |row| pass); fp16 rows always are
+    const void* f16;            // fp16 rows [G][ld], or null
+    int ld;                     // their padded length
+    size_t (*planes_bytes)(i64, int);   // bytes of the operand the GEMM reads for (queries of one call, dim)
+    const void* rows() const { return f16 ? f16 : (const void*)f32; }
+};
+// One GEMM call over fp16 rows: the normalised queries qn [Q][dim] into their fp16 planes qs, then F16Gemm with epi; sets the
+// rank path (rank_f16.hip; instantiated there for the epilogues of the three searches below)
+template <class Epi>
+int cos_gemm_f16(const void* rows, int ld, const float* qn, void* qs, i64 Q, i64 G, int dim, const Epi& epi, hipStream_t st);
+// mi355_roc_pairs_hist[_f16] under the name who; need: the entry's workspace size
+int roc_pairs_hist(const float* queries, i64 Q, const GalleryRows& g, i64 G, int dim, float eps, const int64_t* query_labels,
+                   const int64_t* gallery_labels, const int64_t* exclude, i64 idx_offset, const double* thresholds,
+                   const double* thresholds_dev, int T, int64_t* hist, void* workspace, size_t workspace_bytes, size_t need,
+                   void* stream, const char* who);
+// mi355_cosine_range[_f16] and, with keep_all (every eligible pair is a hit), mi355_positives_range[_f16]
+int cosine_range(const float* queries, i64 Q, const GalleryRows& g, i64 G, int dim, float eps, double threshold, i64 idx_offset,
+                 const mi355_rank_filter* filter, void* candidates, i64 capacity, int64_t* nnz, void* workspace,
+                 size_t workspace_bytes, void* stream, bool keep_all, const char* who);
+// mi355_rank_positives[_f16]
+int rank_positives(const float* queries, i64 Q, const GalleryRows& g, i64 G, int dim, float eps, const int64_t* query_labels,
+                   const int64_t* gallery_labels, const int64_t* exclude, i64 idx_offset, const int64_t* offsets,
+                   const int64_t* offsets_host, const uint64_t* pos_keys, i64 nnz, uint32_t* before, i64 query_block,
+                   void* workspace, size_t workspace_bytes, size_t need, void* stream, const char* who);
 
 }  // namespace mi355

@@ -89,59 +89,135 @@ __global__ __launch_bounds__(256) void k_split_queries_f16(const float* __restri
 // last, stay in flight) and one LDS-only barrier.  Per wave and k-step: 8 * MT + 8 ds_read_b128 and 16 * MT MFMAs.
 // LDS: 2 x 32 KB (A) + 3 x 16 KB (B) = 112 KB at MT = 2, 2 x 16 + 48 = 80 KB at MT = 1 (two workgroups per CU).
 // =====================================================================================
-template <int MT, int FK>
-__global__ __launch_bounds__(256) void k_cos_gemm_f16(const f16* __restrict__ Qs, const f16* __restrict__ Gal,
-                                                      float* __restrict__ S, int Q, i64 G, int ld, int k,
-                                                      float* __restrict__ cand_val, int* __restrict__ cand_idx, int x0, int ntx,
-                                                      int xtiles, int ny) {
-    constexpr bool FILT = false;
-    const RankFilter flt{};
-#include "rank_gemm_f16.inc"
-}
-template <int MT, int FK>
-__global__ __launch_bounds__(256) void k_cos_gemm_f16_filt(const f16* __restrict__ Qs, const f16* __restrict__ Gal, int Q, i64 G,
-                                                           int ld, int k, float* __restrict__ cand_val, int* __restrict__ cand_idx,
-                                                           int x0, int ntx, int xtiles, int ny, RankFilter flt) {
-    constexpr bool FILT = true;
-    float* const S = nullptr;
-#include "rank_gemm_f16.inc"
-}
-// The histogram twin (mi355_roc_pairs_hist_f16): the same body, the histogram epilogue (its overload takes RocArgs as `flt`)
-template <int MT>
-__global__ __launch_bounds__(256) void k_cos_gemm_f16_roc(const f16* __restrict__ Qs, const f16* __restrict__ Gal, int Q, i64 G,
-                                                          int ld, int x0, int ntx, int xtiles, int ny, RocArgs flt) {
-    constexpr int FK = FK_ROC;
-    constexpr bool FILT = false;
-    float* const S = nullptr;
-    const int k = 0;
-    float* const cand_val = nullptr;
-    int* const cand_idx = nullptr;
-#include "rank_gemm_f16.inc"
-}
-// The range twin (mi355_cosine_range_f16): the same body, the range epilogue (its overload takes RangeArgs as `flt`)
-template <int MT>
-__global__ __launch_bounds__(256) void k_cos_gemm_f16_range(const f16* __restrict__ Qs, const f16* __restrict__ Gal, int Q, i64 G,
-                                                            int ld, int x0, int ntx, int xtiles, int ny, RangeArgs flt) {
-    constexpr int FK = FK_RANGE;
-    constexpr bool FILT = false;
-    float* const S = nullptr;
-    const int k = 0;
-    float* const cand_val = nullptr;
-    int* const cand_idx = nullptr;
-#include "rank_gemm_f16.inc"
-}
+template <int MT, class Epi>
+__device__ __forceinline__ void cos_gemm_f16_tile(const f16* __restrict__ Qs, const f16* __restrict__ Gal, int Q, i64 G, int ld,
+                                                  int x0, int ntx, int xtiles, int ny, const Epi& epi) {
+    constexpr int BM = 64 * MT;
+    constexpr int A_PIECES = (BM / 32) * 8;           // 1 KB pieces per stage: 4 sub-steps x 2 planes per row block
+    constexpr int A_STAGE = A_PIECES * 512;           // f16 elements per stage
+    constexpr int B_STAGE = RK_BN * F16_KSTEP;        // f16 elements per stage (16 KB)
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    f16* As = reinterpret_cast<f16*>(smem);           // [2][BM/32][4][2][512]
+    f16* Bs = As + 2 * A_STAGE;                       // [3][128][64], chunks swizzled
 
-// The ranks twin (mi355_rank_positives_f16): the same body, the ranks epilogue (its overload takes RanksArgs as `flt`)
-template <int MT>
-__global__ __launch_bounds__(256) void k_cos_gemm_f16_ranks(const f16* __restrict__ Qs, const f16* __restrict__ Gal, int Q, i64 G,
-                                                            int ld, int x0, int ntx, int xtiles, int ny, RanksArgs flt) {
-    constexpr int FK = FK_RANKS;
-    constexpr bool FILT = false;
-    float* const S = nullptr;
-    const int k = 0;
-    float* const cand_val = nullptr;
-    int* const cand_idx = nullptr;
-#include "rank_gemm_f16.inc"
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1, lr = lane & 31;
+    int bx, by;
+    rank_tile_of((int)blockIdx.x, xtiles, ny, bx, by);
+    const i64 n0 = (i64)(bx + x0) * RK_BN;
+    const int m0 = by * BM;
+    const int swave = __builtin_amdgcn_readfirstlane(wave);
+    const int n_steps = ld / F16_KSTEP, n_sub = ld / 16;
+
+    // B: wave w moves pieces 4w .. 4w + 3; lane -> row 8 * piece + lane / 8, LDS position lane % 8
+    const f16* b_src[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int r = (swave * 4 + i) * 8 + (lane >> 3);
+        const int c = (lane & 7) ^ ((r >> 1) & 7);
+        const i64 g = n0 + r < G ? n0 + r : G - 1;
+        b_src[i] = Gal + g * ld + c * 8;
+    }
+    // (k-steps past the end re-read the last one: the data is never used, the count of pieces in flight stays uniform)
+    auto dma_b = [&](int stage, int t) {
+        const int tt = t < n_steps ? t : n_steps - 1;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            glds16(reinterpret_cast<const bf16_t*>(b_src[i] + tt * F16_KSTEP),
+                   reinterpret_cast<bf16_t*>(Bs + stage * B_STAGE + (swave * 4 + i) * 512));
+    };
+    // A: piece p = (row block p / 8, sub-step (p % 8) / 2, plane p % 2) of k-step t sits at
+    // Qs + ((m0/32 + p/8) * n_sub + 4t) * 1024 + (p % 8) * 512; wave w moves pieces w, w + 4, ...
+    const f16* a_src[A_PIECES / 4];
+#pragma unroll
+    for (int i = 0; i < A_PIECES / 4; ++i) {
+        const int p = swave + 4 * i;
+        a_src[i] = Qs + ((size_t)(m0 / 32 + p / 8) * n_sub) * 1024 + (p % 8) * 512 + lane * 8;
+    }
+    auto dma_a = [&](int buf, int t) {
+#pragma unroll
+        for (int i = 0; i < A_PIECES / 4; ++i)
+            glds16(reinterpret_cast<const bf16_t*>(a_src[i] + (size_t)t * 4 * 1024),
+                   reinterpret_cast<bf16_t*>(As + buf * A_STAGE + (swave + 4 * i) * 512));
+    };
+
+    f32x16 acc[MT][2], acc_lo[MT][2];
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) { acc[i][j][e] = 0.f; acc_lo[i][j][e] = 0.f; }
+
+    // B fragment reads: row r = wn * 64 + j * 32 + lr, chunk 2s + (lane >> 5) of sub-step s at its swizzled position
+    int b_off[2][4];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int r = wn * 64 + j * 32 + lr;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) b_off[j][s] = r * F16_KSTEP + (((2 * s + (lane >> 5)) ^ ((r >> 1) & 7)) << 3);
+    }
+    auto compute = [&](int abuf, int bstage) {
+        const f16* a = As + abuf * A_STAGE + (wm * MT) * 8 * 512 + lane * 8;
+        const f16* b = Bs + bstage * B_STAGE;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            f16x8 bf[2], ah[MT], al[MT];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) bf[j] = *reinterpret_cast<const f16x8*>(b + b_off[j][s]);
+#pragma unroll
+            for (int i = 0; i < MT; ++i) {
+                ah[i] = *reinterpret_cast<const f16x8*>(a + (i * 8 + s * 2) * 512);
+                al[i] = *reinterpret_cast<const f16x8*>(a + (i * 8 + s * 2 + 1) * 512);
+            }
+#pragma unroll
+            for (int i = 0; i < MT; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    acc_lo[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bf[j], acc_lo[i][j], 0, 0, 0);
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bf[j], acc[i][j], 0, 0, 0);
+                }
+        }
+    };
+
+    dma_a(0, 0);
+    dma_b(0, 0);
+    dma_b(1, 1);
+    __syncthreads();                   // drains vmcnt: everything has landed
+
+    int bs_cur = 0, bs_far = 2;        // B stage of k-step t / of k-step t + 2
+    for (int t = 0; t < n_steps; ++t) {
+        if (t + 1 < n_steps) dma_a((t & 1) ^ 1, t + 1);   // everybody left this buffer at the previous barrier
+        __builtin_amdgcn_sched_barrier(0);                // (the count below needs the A pieces issued BEFORE the B pieces)
+        dma_b(bs_far, t + 2);
+        __builtin_amdgcn_sched_barrier(0);
+        compute(t & 1, bs_cur);
+        asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); // A(t+1) and B(t+1) have landed; the four B(t+2) pieces stay in flight
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        bs_cur = bs_cur == 2 ? 0 : bs_cur + 1;
+        bs_far = bs_far == 2 ? 0 : bs_far + 1;
+    }
+    __syncthreads();                   // the last look-ahead pieces have landed before the epilogue reuses the LDS
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[i][j][e] = __builtin_fmaf(acc_lo[i][j][e], F16_LO_UNSCALE, acc[i][j][e]);
+    epi.tile(acc, smem, nullptr, TileCtx{Q, G, ntx, n0, m0});
+}
+template <int MT, int FK>
+__global__ __launch_bounds__(256) void k_cos_gemm_f16(const f16* __restrict__ Qs, const f16* __restrict__ Gal, int Q, i64 G,
+                                                      int ld, int x0, int ntx, int xtiles, int ny, PlainEpi<FK> epi) {
+    cos_gemm_f16_tile<MT>(Qs, Gal, Q, G, ld, x0, ntx, xtiles, ny, epi);
+}
+// Every other epilogue (filtered selection, histogram, range, ranks): the same loop
+template <int MT, class Epi>
+__global__ __launch_bounds__(256) void k_cos_gemm_f16_epi(const f16* __restrict__ Qs, const f16* __restrict__ Gal, int Q, i64 G,
+                                                          int ld, int x0, int ntx, int xtiles, int ny, Epi epi) {
+    cos_gemm_f16_tile<MT>(Qs, Gal, Q, G, ld, x0, ntx, xtiles, ny, epi);
 }
 
 // =====================================================================================
@@ -206,35 +282,33 @@ static bool f16_gemv(i64 Q, int ld) { return Q <= 4 && (size_t)Q * ld * sizeof(f
 
 // The tiled GEMM over fp16 rows (launch_tiles, rank_common.h); qry: the queries' fp16 planes, gal: the rows, D: their length ld
 struct F16Gemm {
-    static constexpr bool SLAB = true, FILTERED = true, ROC = true, RANGE = true, RANKS = true;
     template <int MT> static constexpr size_t stage_bytes() {   // A ring of 2, B ring of 3
         return (size_t)2 * (64 * MT / 32) * 8 * 1024 + (size_t)3 * RK_BN * F16_KSTEP * 2;
     }
-    template <int MT, int FK, bool FILT> static const void* kernel() {
-        if constexpr (FK == FK_ROC) return (const void*)k_cos_gemm_f16_roc<MT>;
-        else if constexpr (FK == FK_RANGE) return (const void*)k_cos_gemm_f16_range<MT>;
-        else if constexpr (FK == FK_RANKS) return (const void*)k_cos_gemm_f16_ranks<MT>;
-        else if constexpr (FILT) return (const void*)k_cos_gemm_f16_filt<MT, FK>;
-        else return (const void*)k_cos_gemm_f16<MT, FK>;
+    template <int MT, class Epi> static constexpr auto kernel() {
+        if constexpr (plain_fk<Epi> >= 0) return &k_cos_gemm_f16<MT, plain_fk<Epi>>;
+        else return &k_cos_gemm_f16_epi<MT, Epi>;
     }
-    template <int MT, int FK, bool FILT>
-    static void launch(dim3 grid, size_t lds, hipStream_t st, const TileArgs& a, int x0, int ntx, int xtiles, int ny) {
-        const f16* qs = (const f16*)a.qry;
-        const f16* gal = (const f16*)a.gal;
-        if constexpr (FK == FK_ROC)
-            hipLaunchKernelGGL((k_cos_gemm_f16_roc<MT>), grid, dim3(256), lds, st, qs, gal, a.Q, a.G, a.D, x0, ntx, xtiles, ny, *a.roc);
-        else if constexpr (FK == FK_RANGE)
-            hipLaunchKernelGGL((k_cos_gemm_f16_range<MT>), grid, dim3(256), lds, st, qs, gal, a.Q, a.G, a.D, x0, ntx, xtiles, ny, *a.rng);
-        else if constexpr (FK == FK_RANKS)
-            hipLaunchKernelGGL((k_cos_gemm_f16_ranks<MT>), grid, dim3(256), lds, st, qs, gal, a.Q, a.G, a.D, x0, ntx, xtiles, ny, *a.rnk);
-        else if constexpr (FILT)
-            hipLaunchKernelGGL((k_cos_gemm_f16_filt<MT, FK>), grid, dim3(256), lds, st, qs, gal, a.Q, a.G, a.D, a.k, a.cand_val,
-                               a.cand_idx, x0, ntx, xtiles, ny, *a.filt);
-        else
-            hipLaunchKernelGGL((k_cos_gemm_f16<MT, FK>), grid, dim3(256), lds, st, qs, gal, a.S, a.Q, a.G, a.D, a.k, a.cand_val,
-                               a.cand_idx, x0, ntx, xtiles, ny);
+    template <int MT, class Epi>
+    static void launch(dim3 grid, size_t lds, hipStream_t st, const TileArgs& a, const Epi& epi, int x0, int ntx, int xtiles, int ny) {
+        hipLaunchKernelGGL((kernel<MT, Epi>()), grid, dim3(256), lds, st, (const f16*)a.qry, (const f16*)a.gal, a.Q, a.G, a.D, x0, ntx,
+                           xtiles, ny, epi);
     }
 };
+
+template <class Epi>
+int cos_gemm_f16(const void* rows, int ld, const float* qn, void* qs, i64 Q, i64 G, int dim, const Epi& epi, hipStream_t st) {
+    set_rank_path(MI355_RANK_PATH_F16_GEMM | (is_select<Epi> ? MI355_RANK_PATH_FUSED : 0));
+    const int n_sub = ld / 16, n_frag = cdiv(Q, 128) * 4 * n_sub;
+    hipLaunchKernelGGL(k_split_queries_f16, dim3((unsigned)cdiv(n_frag, 4)), dim3(256), 0, st, qn, (f16*)qs, (int)Q, dim, n_sub, n_frag);
+    MI355_LAUNCH_CHECK();
+    return cos_gemm_tiles<F16Gemm>({qs, rows, nullptr, (int)Q, G, ld}, epi, st);
+}
+template int cos_gemm_f16(const void*, int, const float*, void*, i64, i64, int, const RocArgs&, hipStream_t);
+template int cos_gemm_f16(const void*, int, const float*, void*, i64, i64, int, const RangeArgs&, hipStream_t);
+template int cos_gemm_f16(const void*, int, const float*, void*, i64, i64, int, const RanksArgs&, hipStream_t);
+
+static GalleryRows f16_rows(const void* gallery_f16, int dim) { return {nullptr, true, gallery_f16, f16_ld(dim), f16_planes_bytes}; }
 
 }  // namespace mi355
 
@@ -304,12 +378,9 @@ static int rank_topk_f16(const float* queries, int64_t Q, const void* gallery_f1
                 return OK;
             }
             RoctxRange range(w.cand_val ? "rank/cosine gemm (fp16 gallery) + per-tile top-k" : "rank/cosine gemm (fp16 gallery)");
-            set_rank_path(MI355_RANK_PATH_F16_GEMM | (w.cand_val ? MI355_RANK_PATH_FUSED : 0));
-            const int n_sub = ld / 16, n_frag = cdiv(qn, 128) * 4 * n_sub;
-            hipLaunchKernelGGL(k_split_queries_f16, dim3((unsigned)cdiv(n_frag, 4)), dim3(256), 0, st, w.qn + q0 * dim, (f16*)w.qs,
-                               (int)qn, dim, n_sub, n_frag);
-            MI355_LAUNCH_CHECK();
-            return cos_gemm_tiles<F16Gemm>({w.qs, gal, nullptr, w.S, (int)qn, G, ld, k, w.cand_val, w.cand_idx, f, nullptr}, st);
+            return with_topk_epi(w, k, f, [&](const auto& epi) {
+                return cos_gemm_f16(gal, ld, w.qn + q0 * dim, w.qs, qn, G, dim, epi, st);
+            });
         });
 }
 
@@ -339,37 +410,9 @@ int mi355_roc_pairs_hist_f16(const float* queries, int64_t Q, const void* galler
                              const int64_t* query_labels, const int64_t* gallery_labels, const int64_t* exclude, int64_t idx_offset,
                              const double* thresholds, const double* thresholds_dev, int T, int64_t* hist, void* workspace,
                              size_t workspace_bytes, void* stream) {
-    const char* who = "roc_pairs_hist_f16";
-    RocArgs roc{};
-    if (int e = roc_check_thresholds(thresholds, T, who, &roc)) return e;
-    if (int e = roc_check_pairs(query_labels, gallery_labels, exclude, idx_offset, thresholds_dev, hist, who, &roc)) return e;
-    MI355_REQUIRE(queries && gallery_f16, "%s: null queries/gallery pointer", who);
-    MI355_REQUIRE(Q >= 1 && G >= 1 && dim >= 1, "%s: bad shape Q=%lld G=%lld dim=%d", who, (long long)Q, (long long)G, dim);
-    MI355_REQUIRE(((uintptr_t)gallery_f16 & 15) == 0, "%s: gallery buffer must be 16-byte aligned", who);
-    MI355_REQUIRE(Q <= INT_MAX && G < ((int64_t)1 << 31) - RK_BN, "%s: shape too large Q=%lld G=%lld", who, (long long)Q,
-                  (long long)G);
-    const size_t need = mi355_roc_pairs_f16_workspace_bytes(Q, G, dim);
-    MI355_REQUIRE(workspace && workspace_bytes >= need, "%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
-    const RankWs w = carve(workspace, Q, G, dim, 0, f16_planes_bytes, false, false);
-    hipStream_t st = (hipStream_t)stream;
-    MI355_CHECK_HIP(hipMemsetAsync(hist, 0, (size_t)2 * (T + 1) * sizeof(int64_t), st));
-    if (int e = normalize_search(queries, Q, nullptr, G, dim, eps, w, st)) return e;
-    const int ld = f16_ld(dim), n_sub = ld / 16;
-    const i64 qb = roc_query_block(Q, G);
-    for (i64 q0 = 0; q0 < Q; q0 += qb) {
-        const i64 qn = (Q - q0 < qb) ? Q - q0 : qb;
-        const RocArgs rb = roc_from(roc, q0);
-        RoctxRange range("roc/cosine gemm (fp16 gallery) + histogram");
-        set_rank_path(MI355_RANK_PATH_F16_GEMM);
-        const int n_frag = cdiv(qn, 128) * 4 * n_sub;
-        hipLaunchKernelGGL(k_split_queries_f16, dim3((unsigned)cdiv(n_frag, 4)), dim3(256), 0, st, w.qn + q0 * dim, (f16*)w.qs,
-                           (int)qn, dim, n_sub, n_frag);
-        MI355_LAUNCH_CHECK();
-        if (int e = cos_gemm_tiles<F16Gemm>({w.qs, gallery_f16, nullptr, nullptr, (int)qn, G, ld, 0, nullptr, nullptr, nullptr, &rb},
-                                            st))
-            return e;
-    }
-    return OK;
+    return roc_pairs_hist(queries, Q, f16_rows(gallery_f16, dim), G, dim, eps, query_labels, gallery_labels, exclude, idx_offset,
+                          thresholds, thresholds_dev, T, hist, workspace, workspace_bytes, mi355_roc_pairs_f16_workspace_bytes(Q, G, dim),
+                          stream, "roc_pairs_hist_f16");
 }
 
 size_t mi355_range_f16_workspace_bytes(int64_t Q, int64_t G, int dim) {
@@ -377,49 +420,19 @@ size_t mi355_range_f16_workspace_bytes(int64_t Q, int64_t G, int dim) {
     return range_carve(nullptr, Q, G, dim, f16_planes_bytes, false).total;   // normalised queries + one call's planes + table
 }
 
-}  // extern "C"
-
-// mi355_cosine_range_f16 and, with keep_all, mi355_positives_range_f16, under the name who
-static int cosine_range_f16(const float* queries, int64_t Q, const void* gallery_f16, int64_t G, int dim, float eps, double threshold,
-                            int64_t idx_offset, const mi355_rank_filter* filter, void* candidates, int64_t capacity, int64_t* nnz,
-                            void* workspace, size_t workspace_bytes, void* stream, bool keep_all, const char* who) {
-    RankFilter f{};
-    if (int e = range_check(queries, Q, gallery_f16, G, dim, threshold, filter, idx_offset, candidates, capacity, nnz, who, &f))
-        return e;
-    MI355_REQUIRE(((uintptr_t)gallery_f16 & 15) == 0, "%s: gallery buffer must be 16-byte aligned", who);
-    const RangeWs w = range_carve(workspace, Q, G, dim, f16_planes_bytes, false);
-    MI355_REQUIRE(workspace && workspace_bytes >= w.total, "%s: workspace %zu < %zu bytes", who, workspace_bytes, w.total);
-    hipStream_t st = (hipStream_t)stream;
-    if (Q == 0 || G == 0) return range_empty(w, Q, nnz, st);
-    if (int e = normalize_search(queries, Q, nullptr, G, dim, eps, w.w, st)) return e;
-    const int ld = f16_ld(dim), n_sub = ld / 16;
-    return range_blocks(Q, G, f, threshold, candidates, capacity, nnz, w, st, [&](i64 q0, i64 qn, const RangeArgs& a) -> int {
-        RoctxRange range(keep_all ? "ranks/positives" : "range/cosine gemm (fp16 gallery) + hits");
-        set_rank_path(MI355_RANK_PATH_F16_GEMM);
-        const int n_frag = cdiv(qn, 128) * 4 * n_sub;
-        hipLaunchKernelGGL(k_split_queries_f16, dim3((unsigned)cdiv(n_frag, 4)), dim3(256), 0, st, w.w.qn + q0 * dim, (f16*)w.w.qs,
-                           (int)qn, dim, n_sub, n_frag);
-        MI355_LAUNCH_CHECK();
-        TileArgs t{w.w.qs, gallery_f16, nullptr, nullptr, (int)qn, G, ld, 0, nullptr, nullptr, nullptr, nullptr, &a};
-        return cos_gemm_tiles<F16Gemm>(t, st);
-    }, keep_all);
-}
-
-extern "C" {
-
 int mi355_cosine_range_f16(const float* queries, int64_t Q, const void* gallery_f16, int64_t G, int dim, float eps, double threshold,
                            int64_t idx_offset, const mi355_rank_filter* filter, void* candidates, int64_t capacity, int64_t* nnz,
                            void* workspace, size_t workspace_bytes, void* stream) {
-    return cosine_range_f16(queries, Q, gallery_f16, G, dim, eps, threshold, idx_offset, filter, candidates, capacity, nnz, workspace,
-                            workspace_bytes, stream, false, "cosine_range_f16");
+    return cosine_range(queries, Q, f16_rows(gallery_f16, dim), G, dim, eps, threshold, idx_offset, filter, candidates, capacity, nnz,
+                        workspace, workspace_bytes, stream, false, "cosine_range_f16");
 }
 
 int mi355_positives_range_f16(const float* queries, int64_t Q, const void* gallery_f16, int64_t G, int dim, float eps,
                               int64_t idx_offset, const mi355_rank_filter* filter, void* candidates, int64_t capacity, int64_t* nnz,
                               void* workspace, size_t workspace_bytes, void* stream) {
     MI355_REQUIRE(filter && filter->label_mode == MI355_LABEL_SAME, "positives_range_f16: needs a filter with MI355_LABEL_SAME");
-    return cosine_range_f16(queries, Q, gallery_f16, G, dim, eps, 0.0, idx_offset, filter, candidates, capacity, nnz, workspace,
-                            workspace_bytes, stream, true, "positives_range_f16");
+    return cosine_range(queries, Q, f16_rows(gallery_f16, dim), G, dim, eps, 0.0, idx_offset, filter, candidates, capacity, nnz,
+                        workspace, workspace_bytes, stream, true, "positives_range_f16");
 }
 
 size_t mi355_rank_positives_f16_workspace_bytes(int64_t Q, int64_t G, int dim) {
@@ -430,34 +443,9 @@ int mi355_rank_positives_f16(const float* queries, int64_t Q, const void* galler
                              const int64_t* query_labels, const int64_t* gallery_labels, const int64_t* exclude, int64_t idx_offset,
                              const int64_t* offsets, const int64_t* offsets_host, const uint64_t* pos_keys, int64_t nnz,
                              uint32_t* before, int64_t query_block, void* workspace, size_t workspace_bytes, void* stream) {
-    const char* who = "rank_positives_f16";
-    RanksArgs rk{};
-    if (int e = ranks_check(queries, Q, gallery_f16, G, dim, query_labels, gallery_labels, exclude, idx_offset, offsets, offsets_host,
-                            pos_keys, nnz, before, query_block, who, &rk))
-        return e;
-    MI355_REQUIRE(((uintptr_t)gallery_f16 & 15) == 0, "%s: gallery buffer must be 16-byte aligned", who);
-    const size_t need = mi355_rank_positives_f16_workspace_bytes(Q, G, dim);
-    MI355_REQUIRE(workspace && workspace_bytes >= need, "%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
-    const RankWs w = carve(workspace, Q, G, dim, 0, f16_planes_bytes, false, false);
-    hipStream_t st = (hipStream_t)stream;
-    if (nnz == 0) return OK;                                    // no query has a positive: nothing to count
-    MI355_CHECK_HIP(hipMemsetAsync(before, 0, (size_t)nnz * sizeof(uint32_t), st));
-    if (int e = normalize_search(queries, Q, nullptr, G, dim, eps, w, st)) return e;
-    const int ld = f16_ld(dim), n_sub = ld / 16;
-    const i64 qb = ranks_query_block(Q, G, query_block);
-    for (i64 q0 = 0; q0 < Q; q0 += qb) {
-        const i64 qn = (Q - q0 < qb) ? Q - q0 : qb;
-        const RanksArgs rb = ranks_from(rk, q0);
-        RoctxRange range("ranks/count");
-        set_rank_path(MI355_RANK_PATH_F16_GEMM);
-        const int n_frag = cdiv(qn, 128) * 4 * n_sub;
-        hipLaunchKernelGGL(k_split_queries_f16, dim3((unsigned)cdiv(n_frag, 4)), dim3(256), 0, st, w.qn + q0 * dim, (f16*)w.qs,
-                           (int)qn, dim, n_sub, n_frag);
-        MI355_LAUNCH_CHECK();
-        TileArgs t{w.qs, gallery_f16, nullptr, nullptr, (int)qn, G, ld, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &rb};
-        if (int e = cos_gemm_tiles<F16Gemm>(t, st)) return e;
-    }
-    return OK;
+    return rank_positives(queries, Q, f16_rows(gallery_f16, dim), G, dim, eps, query_labels, gallery_labels, exclude, idx_offset,
+                          offsets, offsets_host, pos_keys, nnz, before, query_block, workspace, workspace_bytes,
+                          mi355_rank_positives_f16_workspace_bytes(Q, G, dim), stream, "rank_positives_f16");
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // Full-gallery ranks of every positive (mi355_rank_positives*): the host side shared by the fp32 and fp16 counting passes (their
-// GEMM epilogue is in rank_common.h, the kernel twins in rank.hip / rank_f16.hip), the composites of the positives and the
+// GEMM epilogue, RanksArgs, is in rank_common.h, their driver rank_positives in rank.hip), the composites of the positives and the
 // finalize launch: counts -> ranks, average precision and first rank per query.  gfx950 only.
 #include "rank_common.h"
 #include "../../include/mi355_retrieval.h"

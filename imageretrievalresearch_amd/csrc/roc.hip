@@ -1,5 +1,5 @@
-// Verification ROC (mi355_roc_*): the host side of the all-pairs histogram (its GEMM epilogue is in rank_common.h, its kernel
-// twins in rank.hip / rank_f16.hip), the histogram of given pair scores (utils/roc_curve_from_scratch.py's loop) and the one
+// Verification ROC (mi355_roc_*): the host side of the all-pairs histogram (its GEMM epilogue, RocArgs, is in rank_common.h, its
+// driver roc_pairs_hist in rank.hip), the histogram of given pair scores (utils/roc_curve_from_scratch.py's loop) and the one
 // finalize launch: histogram -> tp / fp / fn / tn, rates and the trapezoid AUC.  gfx950 only.
 #include "rank_common.h"
 #include "../../include/mi355_retrieval.h"
