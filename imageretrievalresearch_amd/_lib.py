@@ -110,6 +110,22 @@ PROTOTYPES = {
     "mi355_rank_positives_f16": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_float, vp, vp, vp, C.c_int64, vp,
                                            C.POINTER(C.c_int64), vp, C.c_int64, vp, C.c_int64, vp, C.c_size_t, vp]),
     "mi355_rank_positives_finalize": (C.c_int, [vp, vp, C.c_int64, C.c_int64, vp, vp, vp, vp]),
+    "mi355_nearest_centroid_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int]),
+    "mi355_nearest_centroid": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_int64, vp, vp, vp,
+                                         C.c_size_t, vp]),
+    "mi355_nearest_centroid_f16_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int]),
+    "mi355_nearest_centroid_f16": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_float, C.c_int64, vp, vp, vp,
+                                             C.c_size_t, vp]),
+    "mi355_cluster_members_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "mi355_cluster_members": (C.c_int, [vp, C.c_int64, C.c_int64, vp, vp, vp, C.c_size_t, vp]),
+    "mi355_centroid_update_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int]),
+    "mi355_centroid_update": (C.c_int, [vp, C.c_int64, C.c_int, vp, C.c_int64, vp, C.c_float, vp, vp, vp, vp, vp, C.c_size_t,
+                                        vp]),
+    "mi355_centroid_update_f16_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int]),
+    "mi355_centroid_update_f16": (C.c_int, [vp, C.c_int64, C.c_int, vp, C.c_int64, vp, C.c_float, vp, vp, vp, vp, vp,
+                                            C.c_size_t, vp]),
+    "mi355_contingency_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
+    "mi355_contingency": (C.c_int, [vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, C.c_size_t, vp]),
     "mi355_roc_pairs_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int]),
     "mi355_roc_pairs_hist": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_float, vp, vp, vp, C.c_int64,
                                        C.POINTER(C.c_double), vp, C.c_int, vp, vp, C.c_size_t, vp]),

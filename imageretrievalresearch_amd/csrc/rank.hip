@@ -1321,6 +1321,52 @@ int rank_positives(const float* queries, i64 Q, const GalleryRows& g, i64 G, int
     return OK;
 }
 
+// best[] -> assign (the centroid in the low word, complemented) and score (the fp32 the key was made from; -0 reads as +0)
+__global__ __launch_bounds__(256) void k_nearest_unpack(const unsigned long long* __restrict__ best, i64 G, i64* __restrict__ assign,
+                                                        float* __restrict__ score) {
+    const i64 stride = (i64)gridDim.x * 256;
+    for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < G; i += stride) {
+        const unsigned long long e = best[i];
+        assign[i] = (i64)(unsigned)~(unsigned)(e & 0xffffffffull);
+        score[i] = key_score((unsigned)(e >> 32));
+    }
+}
+
+size_t nearest_ws_bytes(i64 K, i64 G, int dim, size_t (*planes_bytes)(i64, int), bool need_ginv) {
+    return align_up((size_t)G * sizeof(unsigned long long), 256) + carve(nullptr, K, G, dim, 0, planes_bytes, need_ginv, false).total;
+}
+
+int nearest_centroid(const float* centroids, i64 K, const GalleryRows& g, i64 G, int dim, float eps, i64 query_block,
+                     int64_t* assign, float* score, void* workspace, size_t workspace_bytes, void* stream, const char* who) {
+    MI355_REQUIRE(centroids && g.rows(), "%s: null centroids/rows pointer", who);
+    MI355_REQUIRE(assign && score, "%s: null assign/score output", who);
+    MI355_REQUIRE(K >= 1 && G >= 1 && dim >= 1, "%s: bad shape K=%lld N=%lld dim=%d", who, (long long)K, (long long)G, dim);
+    if (int e = check_rows(g, who)) return e;
+    MI355_REQUIRE(K <= INT_MAX && G < ((int64_t)1 << 31) - RK_BN, "%s: shape too large K=%lld N=%lld", who, (long long)K,
+                  (long long)G);
+    MI355_REQUIRE(query_block >= 0, "%s: query_block=%lld < 0", who, (long long)query_block);
+    const size_t need = nearest_ws_bytes(K, G, dim, g.planes_bytes, g.f32 && !g.unit);
+    MI355_REQUIRE(workspace && workspace_bytes >= need, "%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
+    char* base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    unsigned long long* best = (unsigned long long*)base;
+    const RankWs w = carve(base + align_up((size_t)G * sizeof(unsigned long long), 256), K, G, dim, 0, g.planes_bytes,
+                           g.f32 && !g.unit, false);
+    hipStream_t st = (hipStream_t)stream;
+    MI355_CHECK_HIP(hipMemsetAsync(best, 0, (size_t)G * sizeof(unsigned long long), st));
+    const float* ginv = g.f32 && !g.unit ? w.ginv : nullptr;
+    if (int e = normalize_search(centroids, K, ginv ? g.f32 : nullptr, G, dim, eps, w, st)) return e;
+    const i64 qb = ranks_query_block(K, G, query_block);
+    for (i64 q0 = 0; q0 < K; q0 += qb) {
+        const i64 qn = (K - q0 < qb) ? K - q0 : qb;
+        RoctxRange range(g.f16 ? "kmeans/cosine gemm (fp16 rows) + nearest centroid" : "kmeans/cosine gemm + nearest centroid");
+        if (int e = score_rows(g, ginv, w.qn + q0 * dim, w.qs, qn, G, dim, NearestEpi{best, (int)q0}, st)) return e;
+    }
+    const unsigned blocks = (unsigned)(cdiv(G, 256) < 8192 ? cdiv(G, 256) : 8192);
+    hipLaunchKernelGGL(k_nearest_unpack, dim3(blocks), dim3(256), 0, st, (const unsigned long long*)best, G, (i64*)assign, score);
+    MI355_LAUNCH_CHECK();
+    return OK;
+}
+
 }  // namespace mi355
 
 using namespace mi355;
@@ -1428,6 +1474,18 @@ int mi355_rank_positives(const float* queries, int64_t Q, const float* gallery, 
     return rank_positives(queries, Q, f32_rows(gallery, gallery_is_normalized), G, dim, eps, query_labels, gallery_labels, exclude,
                           idx_offset, offsets, offsets_host, pos_keys, nnz, before, query_block, workspace, workspace_bytes,
                           mi355_rank_positives_workspace_bytes(Q, G, dim), stream, "rank_positives");
+}
+
+size_t mi355_nearest_centroid_workspace_bytes(int64_t K, int64_t N, int dim) {
+    if (K < 1 || N < 1 || dim < 1) return 0;
+    return nearest_ws_bytes(K, N, dim, split_queries_bytes, true);
+}
+
+int mi355_nearest_centroid(const float* centroids, int64_t K, const float* rows, int64_t N, int dim, int rows_are_normalized, float eps,
+                           int64_t query_block, int64_t* assign, float* score, void* workspace, size_t workspace_bytes,
+                           void* stream) {
+    return nearest_centroid(centroids, K, f32_rows(rows, rows_are_normalized), N, dim, eps, query_block, assign, score, workspace,
+                            workspace_bytes, stream, "nearest_centroid");
 }
 
 int mi355_clear_pads(float* val, int64_t* idx, int64_t n, int64_t lo, int64_t hi, void* stream) {

@@ -1,6 +1,6 @@
 // Shared between the rank kernels (rank.hip: fp32 rows, bf16 planes; rank_f16.hip: fp16 rows): the launch order of the
 // cosine GEMM's tiles, its epilogues (one type each: score slab, fused per-tile top-k, ROC histogram, range hits, full-gallery
-// ranks), the host side of the top-k selection that merges what the fused epilogue leaves, the one launcher of every tiled
+// ranks, nearest centroid), the host side of the top-k selection that merges what the fused epilogue leaves, the one launcher of every tiled
 // GEMM and the query-block loop of every top-k search.  gfx950 only.
 #pragma once
 #include "common.h"
@@ -575,6 +575,69 @@ __device__ __forceinline__ void RanksArgs::tile(f32x16 (&acc)[MT][2], float* sme
     }
 }
 
+// ---- nearest centroid (mi355_nearest_centroid[_f16]): the centroids are the GEMM's query rows, the resident rows its gallery
+// columns, and the nearest epilogue keeps per COLUMN the best (score, centroid) over the tile's query rows - the arg-max runs
+// down the rows, the opposite direction to SelectEpi.  "Best" is the maximum of one 64-bit key, score_key in the high word
+// and ~centroid in the low one: the higher score wins, equal scores go to the lower centroid.  A maximum does not depend on
+// the order it is taken in, so best[] has the same bits for any launch order and any split of the centroids into GEMM calls.
+__host__ __device__ __forceinline__ unsigned long long nearest_key(unsigned key, unsigned centroid) {
+    return ((unsigned long long)key << 32) | (unsigned)~centroid;
+}
+
+struct NearestEpi {
+    unsigned long long* best;   // [G] keys, zeroed by the host before the first GEMM call (every real score's key is > 0)
+    int q0;                     // centroid index of this call's first query row
+    template <size_t STAGE> static constexpr size_t lds_bytes() {   // 128 keys: inside the staging buffers of every loop
+        static_assert(STAGE >= RK_BN * sizeof(unsigned long long), "the nearest epilogue would grow the GEMM's LDS");
+        return STAGE;
+    }
+    // Scores are acc * ginv[col] as in the other epilogues: the bits of mi355_cosine_scores on the same loop.
+    template <int MT>
+    __device__ __forceinline__ void tile(f32x16 (&acc)[MT][2], float* smem, const float* __restrict__ ginv, const TileCtx& t) const {
+        const int Q = t.Q, m0 = t.m0;
+        const i64 G = t.G, n0 = t.n0;
+        const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+        const int wm = wave >> 1, wn = wave & 1, lr = lane & 31;
+        unsigned long long* colbest = reinterpret_cast<unsigned long long*>(smem);   // [128]: the upper row half's keys
+        unsigned long long mine[2];
+        // C[row = query][col = gallery]; lane: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const i64 col = n0 + wn * 64 + j * 32 + lr;
+            const float gs = (ginv && col < G) ? ginv[col] : 1.0f;
+            // 1. in registers over the lane's 16 * MT rows, ascending: a strict compare keeps the lower centroid
+            unsigned bk = 0u;
+            int brow = 0;
+#pragma unroll
+            for (int i = 0; i < MT; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int row = m0 + wm * MT * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                    const unsigned key = row < Q ? score_key(acc[i][j][r] * gs) : 0u;
+                    if (key > bk) { bk = key; brow = row; }
+                }
+            unsigned long long k64 = bk ? nearest_key(bk, (unsigned)(q0 + brow)) : 0ull;
+            // 2. the partner lane holds the column's other rows (row + 4 of every group of 8)
+            const unsigned long long o = __shfl_xor(k64, 32, 64);
+            mine[j] = o > k64 ? o : k64;
+        }
+        // 3. the two row halves of the tile (wm) through LDS, then ONE global maximum per column per workgroup
+        if (wm == 1 && lane < 32) {
+            colbest[wn * 64 + lr] = mine[0];
+            colbest[wn * 64 + 32 + lr] = mine[1];
+        }
+        __syncthreads();
+        if (wm == 0 && lane < 32) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int c = wn * 64 + j * 32 + lr;
+                const unsigned long long o = colbest[c], k64 = o > mine[j] ? o : mine[j];
+                if (n0 + c < G && k64) atomicMax(&best[n0 + c], k64);
+            }
+        }
+    }
+};
+
 // Row norm of an fp32 row: one wave, float4 loads when vec (dim % 4 == 0 and 16-B aligned rows).  The lane-strided
 // summation order is part of the result: every row normalisation of the library (mi355_l2_normalize_rows, the queries
 // of every search, the fp16 gallery conversion) goes through this one function, so they give the same bits.
@@ -849,5 +912,10 @@ int rank_positives(const float* queries, i64 Q, const GalleryRows& g, i64 G, int
                    const int64_t* gallery_labels, const int64_t* exclude, i64 idx_offset, const int64_t* offsets,
                    const int64_t* offsets_host, const uint64_t* pos_keys, i64 nnz, uint32_t* before, i64 query_block,
                    void* workspace, size_t workspace_bytes, size_t need, void* stream, const char* who);
+// mi355_nearest_centroid[_f16]: workspace = the keys best[G], then carve(K, G, dim, 0, planes, need_ginv).  need_ginv: room
+// for 1 / |row| of fp32 rows that are not normalised (the fp32 sizer always counts it: it does not know the rows).
+size_t nearest_ws_bytes(i64 K, i64 G, int dim, size_t (*planes_bytes)(i64, int), bool need_ginv);
+int nearest_centroid(const float* centroids, i64 K, const GalleryRows& g, i64 G, int dim, float eps, i64 query_block,
+                     int64_t* assign, float* score, void* workspace, size_t workspace_bytes, void* stream, const char* who);
 
 }  // namespace mi355

@@ -307,6 +307,7 @@ int cos_gemm_f16(const void* rows, int ld, const float* qn, void* qs, i64 Q, i64
 template int cos_gemm_f16(const void*, int, const float*, void*, i64, i64, int, const RocArgs&, hipStream_t);
 template int cos_gemm_f16(const void*, int, const float*, void*, i64, i64, int, const RangeArgs&, hipStream_t);
 template int cos_gemm_f16(const void*, int, const float*, void*, i64, i64, int, const RanksArgs&, hipStream_t);
+template int cos_gemm_f16(const void*, int, const float*, void*, i64, i64, int, const NearestEpi&, hipStream_t);
 
 static GalleryRows f16_rows(const void* gallery_f16, int dim) { return {nullptr, true, gallery_f16, f16_ld(dim), f16_planes_bytes}; }
 
@@ -446,6 +447,18 @@ int mi355_rank_positives_f16(const float* queries, int64_t Q, const void* galler
     return rank_positives(queries, Q, f16_rows(gallery_f16, dim), G, dim, eps, query_labels, gallery_labels, exclude, idx_offset,
                           offsets, offsets_host, pos_keys, nnz, before, query_block, workspace, workspace_bytes,
                           mi355_rank_positives_f16_workspace_bytes(Q, G, dim), stream, "rank_positives_f16");
+}
+
+size_t mi355_nearest_centroid_f16_workspace_bytes(int64_t K, int64_t N, int dim) {
+    if (K < 1 || N < 1 || dim < 1) return 0;
+    return nearest_ws_bytes(K, N, dim, f16_planes_bytes, false);
+}
+
+int mi355_nearest_centroid_f16(const float* centroids, int64_t K, const void* rows_f16, int64_t N, int dim, float eps,
+                               int64_t query_block, int64_t* assign, float* score, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+    return nearest_centroid(centroids, K, f16_rows(rows_f16, dim), N, dim, eps, query_block, assign, score, workspace,
+                            workspace_bytes, stream, "nearest_centroid_f16");
 }
 
 }  // extern "C"

@@ -14,6 +14,7 @@ routes the arithmetic to libmi355_retrieval:
 * ``expand_queries`` / ``Gallery.augmented`` .. alpha query expansion and database-side augmentation (not in the reference)
 * ``Gallery.moments`` / ``Gallery.whitened`` .. PCA whitening of a resident gallery (whitening.py; not in the reference)
 * ``Gallery.rerank`` / ``Gallery.rerank_index`` k-reciprocal re-ranking on the gallery's kNN graph (rerank.py; not in the reference)
+* ``Gallery.kmeans`` / ``Gallery.clustering_metrics`` spherical k-means, NMI / purity / F1 (cluster.py; not in the reference)
 
 The gallery side of every search is one ``_Rows`` (buffer, dtype, rows, dim, row stride, normalised or not, optional bf16
 planes): a tensor argument, a ``PreparedGallery``, a ``Gallery`` and a ``ShardedGallery`` shard all become one.  Top-k, range
@@ -817,6 +818,22 @@ class Gallery:
         rows = self._resident()
         _ranking_args(queries, query_labels, rows, gl)
         return _ranking_metrics(queries, query_labels, rows, gl, exclude, 0, _cmc_ranks(ranks), self.eps)
+
+    def kmeans(self, n_clusters: int, **kw):
+        """``spherical_kmeans`` of the resident rows (fp32 or fp16, read where they lie): a ``KMeansResult``.  Keywords as
+        there (``iters``, ``seed``, ``init``, ``block``)."""
+        from . import cluster as _cl
+        return _cl.spherical_kmeans(self, n_clusters, eps=self.eps, **kw)
+
+    def clustering_metrics(self, n_clusters: int | None = None, **kw) -> dict:
+        """Clusters the resident rows (``kmeans``; ``n_clusters`` defaults to the number of distinct labels given to ``add``)
+        and scores the clusters against those labels: ``clustering_metrics(kmeans(K).assignments, labels)`` - NMI, purity and
+        pairwise F1."""
+        from . import cluster as _cl
+        gl = self._labels_for("clustering_metrics")
+        if n_clusters is None:
+            n_clusters = int(torch.unique(gl).shape[0])
+        return _cl.clustering_metrics(self.kmeans(n_clusters, **kw).assignments, gl)
 
 
 def clear_pads(vals: torch.Tensor, idx: torch.Tensor, lo: int, hi: int):

@@ -409,6 +409,55 @@ int mi355_distinct_class_topn(const int64_t* idx, const float* val, int64_t Q, i
                               const int64_t* gallery_cls, int64_t G, int n, int64_t* out_cls, int64_t* out_idx,
                               float* out_val, void* stream);
 
+/* ------------------------------------------------------------------ spherical k-means and clustering scores
+ * Nearest centroid: assign[n] = the centroid (row of centroids [K][dim], device fp32, normalised by the call as the queries of
+ * every search are) with the highest cosine to resident row n, score[n] that cosine (device int64 [N] / fp32 [N]).  Equal
+ * scores go to the lower centroid.  The rows are the gallery side of the tiled cosine GEMM: fp32 rows [N][dim]
+ * (rows_are_normalized as in mi355_rank_topk) or the fp16 rows of mi355_gallery_to_f16; every score has the bits of
+ * mi355_cosine_scores(centroids, rows) on the same loop.  The centroids go through the GEMM mi355_roc_pairs_hist's query
+ * block at a time, or query_block (> 0, smaller) at a time; the result does not depend on it, nor on the launch order.
+ * N < 2^31 - 128.  Every argument is checked before any HIP call. */
+size_t mi355_nearest_centroid_workspace_bytes(int64_t K, int64_t N, int dim);
+int mi355_nearest_centroid(const float* centroids, int64_t K, const float* rows, int64_t N, int dim, int rows_are_normalized, float eps,
+                           int64_t query_block, int64_t* assign, float* score, void* workspace, size_t workspace_bytes,
+                           void* stream);
+size_t mi355_nearest_centroid_f16_workspace_bytes(int64_t K, int64_t N, int dim);
+int mi355_nearest_centroid_f16(const float* centroids, int64_t K, const void* rows_f16, int64_t N, int dim, float eps,
+                               int64_t query_block, int64_t* assign, float* score, void* workspace, size_t workspace_bytes,
+                               void* stream);
+
+/* The members of every cluster as CSR: assign [N] device int64 in [0, K) -> offsets [K + 1] and order [N] (device int64), the
+ * rows of cluster k at order[offsets[k] .. offsets[k + 1]) in ascending row index.  A value outside [0, K) is found on the
+ * device and reported as an argument error (the call reads one flag word back: one host sync); nothing is read or written
+ * out of bounds because of it.  K < 2^24 (one workgroup per cluster). */
+size_t mi355_cluster_members_workspace_bytes(int64_t N, int64_t K);
+int mi355_cluster_members(const int64_t* assign, int64_t N, int64_t K, int64_t* offsets, int64_t* order, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
+/* Centroid update of spherical k-means: mi355_cluster_members of assign (offsets / order come out as there), then per
+ * cluster the float64 sum of its member rows (fp32 rows [N][dim], or the fp16 rows of mi355_gallery_to_f16 widened exactly)
+ * in ascending row order - 256 members at a time, the partial sums then in segment order - and
+ * centroids[k] = fp32(sum / |sum|), one rounding.  A cluster without members, or with |sum| < eps, keeps previous[k] bit for
+ * bit.  centroids / previous [K][dim] device fp32 (they may be the same buffer), counts [K] device int64.  The same bits on
+ * every run and every device.  K < 2^24 and ceil(N / 256) + K < 2^24 (one workgroup per segment).  The two sizers return
+ * the same number: the partial sums are float64 for either kind of rows. */
+size_t mi355_centroid_update_workspace_bytes(int64_t N, int64_t K, int dim);
+int mi355_centroid_update(const float* rows, int64_t N, int dim, const int64_t* assign, int64_t K, const float* previous, float eps,
+                          float* centroids, int64_t* counts, int64_t* offsets, int64_t* order, void* workspace,
+                          size_t workspace_bytes, void* stream);
+size_t mi355_centroid_update_f16_workspace_bytes(int64_t N, int64_t K, int dim);
+int mi355_centroid_update_f16(const void* rows_f16, int64_t N, int dim, const int64_t* assign, int64_t K, const float* previous,
+                              float eps, float* centroids, int64_t* counts, int64_t* offsets, int64_t* order, void* workspace,
+                              size_t workspace_bytes, void* stream);
+
+/* Contingency table of two labelings: table[x * Kb + y] = #{i : a[i] == x and b[i] == y}, a / b [N] device int64 in [0, Ka) /
+ * [0, Kb), table [Ka][Kb] device int64 (zeroed by the call), N <= 2^40, Ka * Kb <= 2^28.  Exact integer counts (per-workgroup LDS
+ * sub-histograms up to 8192 cells, global integer atomics above).  An id out of range is an argument error found on the
+ * device (one flag word read back). */
+size_t mi355_contingency_workspace_bytes(int64_t N, int64_t Ka, int64_t Kb);
+int mi355_contingency(const int64_t* a, const int64_t* b, int64_t N, int64_t Ka, int64_t Kb, int64_t* table, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ backbone models
  * Replaces timm.create_model(name, num_classes=N) and the methods the reference calls on it
  * (inference/inference.py:102,110,133,146,199-201 ; train/train.py:194-195,288,396 ;
