@@ -103,6 +103,7 @@ static inline int make_divisible(double v, int divisor = 8, int min_value = 0, d
     return new_v;
 }
 static inline int pad8(int c) { return (c + 7) & ~7; }
+static inline int kpad32(int k) { return (k + 31) & ~31; }   // row stride of packed GEMM weights: K rounded up to 32
 
 // architecture builders (arch_*.cpp); return 0 or set_error + nonzero
 int build_efficientnet_b3(ModelDef& m);

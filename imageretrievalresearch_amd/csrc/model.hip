@@ -23,7 +23,7 @@ int pack_gemm(Packer& pk, Op& op) {
         if (!b) return ERR_STATE;
         for (int i = 0; i < N; ++i) shift[i] = b->data[i] * scale[i] + shift[i];
     }
-    const int Np = (op.cout + 15) & ~15, Kp = (op.cin + 31) & ~31;
+    const int Np = (op.cout + 15) & ~15, Kp = kpad32(op.cin);
     op.w_off = pk.alloc((size_t)Np * Kp * 2);
     op.b_off = pk.alloc((size_t)Np * 4);
     uint16_t* W = (uint16_t*)(pk.blob.data() + op.w_off);
@@ -156,65 +156,169 @@ static int pack_op(Packer& pk, Op& op) {
     }
 }
 
-// ------------------------------------------------------------------------------------ shape pass
+// ------------------------------------------------------------------------------------ launch plan
 static inline int conv_out(int h, int k, int s) { return (h + 2 * (k / 2) - k) / s + 1; }
 
-// Walk the plan for a chunk of nb images: fill slot dims and sizes.  Returns total arena bytes.
-static size_t plan_slots(mi355_model* m, int nb, int H, int W, int B_full = 0) {
-    if (B_full < nb) B_full = nb;       // the caller's whole batch decides the kernel choices that change rounding (split-K)
-    SlotState* S = m->slots;
-    for (int i = 0; i < SLOT_COUNT; ++i) S[i] = SlotState();
-    auto need = [&](int s, size_t bytes) { if (s != SLOT_NONE && bytes > S[s].bytes) S[s].bytes = bytes; };
-    for (const Op& op : m->def.ops) {
-        switch (op.kind) {
-            case OP_STEM: {
-                const int ho = conv_out(H, 3, 2), wo = conv_out(W, 3, 2);
-                S[op.out].h = ho; S[op.out].w = wo; S[op.out].c = op.cout;
-                need(op.out, (size_t)nb * ho * wo * op.cout * 2);
-                break;
-            }
-            case OP_GEMM: {
-                const int h = S[op.in].h, w = S[op.in].w;
-                S[op.out].h = h; S[op.out].w = w; S[op.out].c = op.cout;
-                if (gemm_splitk_chunks((long)B_full * h * w, h * w, op.cout, op.cin) >= 2)
-                    need(SLOT_SPLITK, gemm_splitk_bytes((long)nb * h * w, op.cout, op.cin));
-                need(op.out, (size_t)nb * h * w * op.cout * 2);
-                break;
-            }
-            case OP_DW: {
-                const int ho = conv_out(S[op.in].h, op.k, op.stride), wo = conv_out(S[op.in].w, op.k, op.stride);
-                S[op.out].h = ho; S[op.out].w = wo; S[op.out].c = op.cout;
-                need(op.out, (size_t)nb * ho * wo * op.cout * 2);
-                // squeeze partials: per 256-item block (k_dwconv) or per row band (fused kernels, <= ho bands)
-                if (op.pool) need(SLOT_POOLPART, (size_t)nb * std::max(dw_pool_blocks(ho, wo, op.cout), ho) * op.cout * 4);
-                break;
-            }
-            case OP_SE:
-                need(SLOT_GATE, (size_t)nb * op.cin * 4);
-                break;
-            default: {
-                // swin ops: sizes are declared by the builder through cin/cout/tokens_h
-                const int th = op.tokens_h;
-                if (op.out != SLOT_NONE) {
-                    S[op.out].h = th; S[op.out].w = th; S[op.out].c = op.cout;
-                    need(op.out, (size_t)nb * th * th * op.cout * 2);
-                }
-                if (op.kind == OP_LAYERNORM && op.fuse_next) need(SLOT_LNSTATS, (size_t)nb * th * th * 8);
-                break;
-            }
-        }
+// The one shape rule.  Returns the dims of what `op` writes given the dims `in` of what it reads (Step::in), and reports
+// through need(slot, bytes) the arena bytes a chunk of nb images needs for it.
+template <class Need>
+static Dims op_shape(const Op& op, Dims in, int nb, int B_full, Need&& need) {
+    Dims o = in;
+    switch (op.kind) {
+        case OP_STEM:
+            o = {conv_out(in.h, 3, 2), conv_out(in.w, 3, 2), op.cout};
+            break;
+        case OP_GEMM:
+            o.c = op.cout;
+            // the caller's whole batch decides the kernel choices that change rounding (split-K); the chunk sizes the scratch
+            if (gemm_splitk_chunks((long)B_full * in.h * in.w, in.h * in.w, op.cout, op.cin) >= 2)
+                need(SLOT_SPLITK, gemm_splitk_bytes((long)nb * in.h * in.w, op.cout, op.cin));
+            break;
+        case OP_DW:
+            o = {conv_out(in.h, op.k, op.stride), conv_out(in.w, op.k, op.stride), op.cout};
+            // squeeze partials: per 256-item block (k_dwconv) or per row band (fused kernels, <= ho bands)
+            if (op.pool) need(SLOT_POOLPART, (size_t)nb * std::max(dw_pool_blocks(o.h, o.w, op.cout), o.h) * op.cout * 4);
+            break;
+        case OP_SE:
+            need(SLOT_GATE, (size_t)nb * op.cin * 4);
+            return {1, 1, op.cin};
+        default:
+            // swin ops: sizes are declared by the builder through cin/cout/tokens_h
+            o = {op.tokens_h, op.tokens_h, op.cout};
+            if (op.kind == OP_LAYERNORM && op.fuse_next) need(SLOT_LNSTATS, (size_t)nb * op.tokens_h * op.tokens_h * 8);
+            break;
     }
+    need(op.out, (size_t)nb * o.h * o.w * o.c * 2);
+    return o;
+}
+
+// expand GEMM (-> SLOT_E) immediately followed by the depthwise conv that consumes it: which kernel runs the pair as one
+// launch (MI355_PLAN_FUSED_LATE / _SWEEP / _BAND), or MI355_PLAN_OP when the two run apart
+static int fused_pair_how(const mi355_model* m, size_t i, int h, int w, int* band_rows) {
+    if (!m->fuse || i + 1 >= m->def.ops.size()) return MI355_PLAN_OP;
+    const Op& g = m->def.ops[i];
+    const Op& d = m->def.ops[i + 1];
+    if (g.kind != OP_GEMM || d.kind != OP_DW || g.out != SLOT_E || d.in != SLOT_E) return MI355_PLAN_OP;
+    if (g.use_gate || g.res != SLOT_NONE || g.a_relu6 || !g.tap.empty()) return MI355_PLAN_OP;
+    if (fused_late_supported(h, w, g.cin, g.cout, d.k, d.stride)) return MI355_PLAN_FUSED_LATE;   // whole-image tile
+    // row-sweep kernel (MFMA depthwise, complete squeeze sums): the early-stage shape classes of sweep_mbconv.hip
+    if (m->fuse_sweep && sweep_mbconv_supported(h, w, g.cin, g.cout, d.k, d.stride, g.act, d.act)) return MI355_PLAN_SWEEP;
+    // Band variant, measured per layer on EfficientNet-B3a B=256 (fused vs expand + depthwise): 3x3 s1 C192 @56x56 307 vs
+    // 339 us (wins); 3x3 s2 C144 @112x112 780 vs 619, 5x5 s2 C192 @56x56 465 vs 276, 5x5 s1 C288 @28x28 247 vs 172 (lose:
+    // short bands recompute too much halo and leave most threads idle in the depthwise phase).
+    // RexNet-200: 3x3 s1 C324 @56x56 (7-row bands) 582 vs 661 us and 3x3 s2 C192 @112x112 714 vs 771 us (win: its 32->192
+    // expand alone costs 0.5 ms).
+    const int rows = m->fuse_band ? fused_band_rows(h, w, g.cin, g.cout, d.k, d.stride) : 0;
+    const bool measured_win = d.k == 3 && ((d.stride == 1 && rows >= 7) || (d.stride == 2 && w >= 112 && g.cout >= 192));
+    if (rows > 0 && (m->fuse_band == 1 || measured_win)) { *band_rows = rows; return MI355_PLAN_BAND; }
+    return MI355_PLAN_OP;
+}
+
+// expand GEMM -> depthwise -> SE -> gated projection on a whole-image tile: one kernel (mbconv_block.hip)
+static bool can_fuse_block(const mi355_model* m, size_t i, int h, int w, int nb) {
+    if (!m->fuse_block || nb < m->fuse_block_min_batch || i + 3 >= m->def.ops.size()) return false;
+    const Op& g = m->def.ops[i];
+    const Op& d = m->def.ops[i + 1];
+    const Op& s = m->def.ops[i + 2];
+    const Op& p = m->def.ops[i + 3];
+    if (g.kind != OP_GEMM || d.kind != OP_DW || s.kind != OP_SE || p.kind != OP_GEMM) return false;
+    if (g.out != SLOT_E || d.in != SLOT_E || d.out != SLOT_D || p.in != SLOT_D || !p.use_gate || !d.pool) return false;
+    if (g.use_gate || g.res != SLOT_NONE || g.a_relu6 || !g.tap.empty() || !d.tap.empty()) return false;
+    // (rexnet: ReLU6 behind the gate, a shortcut over the first res_channels outputs and channel counts padded to 8 are all
+    //  handled by the kernel: pad channels carry exact zeros through every phase, as in the unfused chain)
+    if (p.act != ACT_NONE || (p.res != SLOT_NONE && p.res != g.in)) return false;
+    if (p.res != SLOT_NONE && p.res_channels && ((p.res_channels + 7) & ~7) != g.cin) return false;
+    return mbconv_block_supported(h, w, g.cin, g.cout, p.cout, d.k, d.stride, s.rd, g.act, d.act);
+}
+
+// Pooled embedding wanted and the last op is the head 1x1 conv: conv + bias + act + GAP as ONE kernel (k_head_gap: the
+// head tensor never reaches HBM).  forward_features, taps and per-op profiling need the un-pooled map: two-kernel path.
+static bool can_fuse_head_gap(const mi355_model* m, size_t i, Dims in, bool pooled) {
+    const ModelDef& d = m->def;
+    if (!pooled || d.pools_in_features || !m->fuse_head_gap || m->taps || m->profile || i + 1 != d.ops.size()) return false;
+    const Op& h = d.ops[i];
+    if (h.kind != OP_GEMM || h.out != d.final_slot || h.in == SLOT_NONE || h.use_gate || h.res != SLOT_NONE || h.a_relu6 ||
+        !h.ln_w_name.empty())
+        return false;
+    return head_gap_supported(in.h * in.w, h.cout, h.cin, h.cin, kpad32(h.cin), h.act);
+}
+
+struct PlanSeed {       // run_between_taps: the caller's activation sits in `slot` in front of the first op
+    int slot = SLOT_NONE;
+    Dims dims;
+};
+
+// The launch plan of ops [first_op, last_op] for a chunk of nb images of a batch of B_full: one walk over def.ops gives every
+// op its shapes, sizes and lays out the arena slots (always for the whole op list, so a sub-range runs in the arena of a
+// forward), and decides per step which kernel runs it.  This is the ONLY place a kernel is chosen; the executor, the
+// profile and the traffic model walk the result.  `pooled`: the caller wants the pooled embedding, not the feature map.
+static Plan resolve_plan(const mi355_model* m, size_t first_op, size_t last_op, PlanSeed seed, int nb, int B_full, int H, int W,
+                         bool pooled) {
+    const std::vector<Op>& ops = m->def.ops;
+    Plan p;
+    p.op_in.resize(ops.size());
+    Dims D[SLOT_COUNT];
+    auto need = [&](int s, size_t bytes) { if (s != SLOT_NONE && bytes > p.slots[s].bytes) p.slots[s].bytes = bytes; };
+    size_t next = first_op;      // first op behind the steps resolved so far
+    int ln_in = SLOT_NONE;       // a MI355_PLAN_LN_STATS step waits for its consumer GEMM: the slot that LayerNorm read
+    for (size_t i = 0; i < ops.size(); ++i) {
+        const Op& op = ops[i];
+        if (i == first_op && seed.slot != SLOT_NONE) D[seed.slot] = seed.dims;
+        // (the SE gate is computed from the squeeze partials of the depthwise conv in front of it: SLOT_D's geometry)
+        const Dims in = op.in == SLOT_NONE ? Dims{H, W, 3} : D[op.kind == OP_SE ? SLOT_D : op.in];
+        p.op_in[i] = in;
+        // (a fused step never writes its SLOT_E; sizing it anyway keeps the arena as it was - a memory change of its own)
+        const Dims out = op_shape(op, in, nb, B_full, need);
+        if (op.out != SLOT_NONE) D[op.out] = out;
+        if (i == next && i <= last_op) {
+            Step s;
+            s.first_op = (int)i;
+            s.in = in;
+            // (the whole-block kernel is chosen by the caller's WHOLE batch, not by the chunk: it rounds differently from the unfused chain)
+            if (op.in != SLOT_NONE && can_fuse_block(m, i, in.h, in.w, B_full)) {
+                s.how = MI355_PLAN_BLOCK;
+                s.n_ops = 4;       // depthwise, SE and projection run inside the block kernel
+            } else if ((s.how = fused_pair_how(m, i, in.h, in.w, &s.band_rows)) != MI355_PLAN_OP) {
+                s.n_ops = 2;       // the depthwise op runs together with the expand
+            } else if (can_fuse_head_gap(m, i, in, pooled)) {
+                s.how = MI355_PLAN_HEAD_GAP;
+            } else if (op.kind == OP_LAYERNORM) {
+                // Folded into the next GEMM (norm1 -> qkv, norm2 -> fc1) when that GEMM takes the DMA-tiled kernel, whose epilogue
+                // knows how (M >= 1024 rows of THIS chunk; smaller problems keep the separate kernel and the unfolded weights)
+                // (and only where that epilogue exists: K >= 128 and a multiple of 64, so swin_s3's width-96 stage keeps the separate kernel).
+                // SLOT_LNSTATS holds the rows * 8 bytes: op_shape sizes it to nb * tokens^2 * 8 for every fuse_next LayerNorm, in
+                // this walk or, for a tail chunk, in the walk of the larger chunk whose slots the forward lays out.
+                const long rows = (long)nb * op.tokens_h * op.tokens_h;
+                if (op.fuse_next && m->fuse_ln && rows >= 1024 && op.cout >= 128 && op.cout % 64 == 0) {
+                    s.how = MI355_PLAN_LN_STATS;
+                    ln_in = op.in;
+                }
+            } else if (op.kind == OP_GEMM) {
+                s.res_c = op.res != SLOT_NONE ? D[op.res].c : 0;
+                s.ln_in = ln_in;
+                ln_in = SLOT_NONE;
+            }
+            next = i + s.n_ops;
+            p.steps.push_back(s);
+        }
+        if (i >= first_op && i < next) p.steps.back().out = out;   // the step's last op leaves its dims
+    }
+    p.final = D[m->def.final_slot];
     need(SLOT_POOLED, (size_t)nb * m->def.feat_dim_pad * 4);
     need(SLOT_POOLED_BF16, (size_t)nb * m->def.feat_dim_pad * 2);
     size_t off = 0;
     for (int i = 0; i < SLOT_COUNT; ++i) {
-        S[i].off = off;
-        off += align_up(S[i].bytes, 256);
+        p.slots[i].off = off;
+        off += align_up(p.slots[i].bytes, 256);
     }
-    return off + 256;
+    p.arena_bytes = off + 256;
+    return p;
 }
 
-static int ensure_arena(mi355_model* m, size_t bytes) {
+static int ensure_arena(mi355_model* m, const Plan& plan, int lanes) {
+    std::copy(plan.slots, plan.slots + SLOT_COUNT, m->slots);
+    m->lane_bytes = lanes > 1 ? align_up(plan.arena_bytes, 4096) : 0;
+    const size_t bytes = lanes > 1 ? m->lane_bytes * lanes : plan.arena_bytes;
     int dev = 0;
     MI355_CHECK_HIP(hipGetDevice(&dev));
     if (m->arena && m->arena_device != dev) {      // the model moved to another GPU: its scratch must follow
@@ -238,7 +342,7 @@ static int ensure_arena(mi355_model* m, size_t bytes) {
     return OK;
 }
 
-// ------------------------------------------------------------------------------------ execution
+// ------------------------------------------------------------------------------------ labels, traffic model
 static int prof_kind(const Op& op) {
     switch (op.kind) {
         case OP_STEM: return PK_STEM;
@@ -252,9 +356,65 @@ static int prof_kind(const Op& op) {
     }
 }
 
-static int record_tap(ExecCtx& cx, const Op& op) {
+// Label, algorithmic HBM bytes and MACs of one op at batch B, from the op and the dims it reads.  Layer-granular model
+// (SURVEY §8d): every conv/dw/1x1 layer reads its input once and writes its output once; BN/act/SE-gate/GAP are epilogues;
+// each residual adds one read of the block input.
+struct OpCost {
+    char label[128];
+    double bytes, macs;
+    double table_bytes;     // what mi355_model_profile_ops reports: `bytes`, except for the discrepancy marked below
+};
+static OpCost op_cost(const Op& op, Dims in, int B) {
+    OpCost c{};
+    switch (op.kind) {
+        case OP_STEM: {
+            const int ho = conv_out(in.h, 3, 2), wo = conv_out(in.w, 3, 2);
+            c.bytes = (double)B * (3.0 * in.h * in.w * 4 + (double)ho * wo * op.cout_real * 2);
+            c.macs = (double)B * ho * wo * op.cout_real * 27;
+            snprintf(c.label, sizeof c.label, "stem 3->%d @%dx%d", op.cout_real, ho, wo);
+            break;
+        }
+        case OP_GEMM: {
+            const double hw = (double)in.h * in.w;
+            double el = hw * (op.cin_real + op.cout_real);
+            if (op.res != SLOT_NONE) el += hw * (op.res_channels ? op.res_channels : op.cout_real);
+            c.bytes = B * el * 2;
+            c.macs = B * hw * op.cin_real * op.cout_real;
+            snprintf(c.label, sizeof c.label, "pw %d->%d @%dx%d%s%s", op.cin_real, op.cout_real, in.h, in.w,
+                     op.use_gate ? " gate" : "", op.res != SLOT_NONE ? " res" : "");
+            break;
+        }
+        case OP_DW: {
+            const int ho = conv_out(in.h, op.k, op.stride), wo = conv_out(in.w, op.k, op.stride);
+            c.bytes = (double)B * ((double)in.h * in.w + (double)ho * wo) * op.cin_real * 2;
+            c.macs = (double)B * ho * wo * op.cin_real * op.k * op.k;
+            snprintf(c.label, sizeof c.label, "dw k%d s%d C%d @%dx%d", op.k, op.stride, op.cin_real, in.h, in.w);
+            break;
+        }
+        case OP_SE:
+            c.macs = (double)B * 2.0 * op.cin_real * op.rd;
+            snprintf(c.label, sizeof c.label, "se C%d rd%d", op.cin_real, op.rd);
+            break;
+        default: {
+            const double t = (double)op.tokens_h * op.tokens_h;
+            c.bytes = c.table_bytes = B * t * (op.cin_real + op.cout_real) * 2;
+            // KNOWN DISCREPANCY: the traffic model counts the patch embedding's fp32 image and the token mean's
+            // single read; the per-op table counts both ops like every other token op.  Both values are kept as they were.
+            if (op.kind == OP_PATCH_EMBED) c.bytes = (double)B * (3.0 * in.h * in.w * 4 + t * op.cout_real * 2);
+            else if (op.kind == OP_TOKEN_MEAN) c.bytes = B * t * op.cin_real * 2;
+            if (op.kind == OP_WINATTN) c.macs = B * t * (double)(op.window * op.window) * op.cout_real * 2;   // QK^T + PV
+            if (op.kind == OP_PATCH_EMBED) c.macs = B * t * 48.0 * op.cout_real;
+            snprintf(c.label, sizeof c.label, "op%d C%d->%d t%d", (int)op.kind, op.cin_real, op.cout_real, op.tokens_h);
+            return c;
+        }
+    }
+    c.table_bytes = c.bytes;
+    return c;
+}
+
+// ------------------------------------------------------------------------------------ execution
+static int record_tap(ExecCtx& cx, const Op& op, Dims s) {
     mi355_model* m = cx.m;
-    const SlotState& s = m->slots[op.out];
     TapBuf& t = m->tapbufs[op.tap];
     const size_t per_img = (size_t)s.h * s.w * s.c * 2;
     const size_t bytes = per_img * cx.B;
@@ -269,25 +429,24 @@ static int record_tap(ExecCtx& cx, const Op& op) {
     return OK;
 }
 
-static int exec_op(ExecCtx& cx, const Op& op) {
+static int exec_op(ExecCtx& cx, const Op& op, const Step& s) {
     mi355_model* m = cx.m;
-    SlotState* S = m->slots;
     switch (op.kind) {
         case OP_STEM:
-            if (cx.x_u8)
-                return launch_stem_u8(cx.x_u8, cx.img_h, cx.img_w, cx.fill, cx.mean, cx.stdv, cx.conv_w,
+            if (const U8Source* u = cx.u8)
+                return launch_stem_u8(cx.x_u8(), u->h, u->w, u->fill, u->mean, u->stdv, u->conv_w,
                                       (const float*)cx.w(op.w_off), (const float*)cx.w(op.b_off),
-                                      (bf16_t*)cx.slot_ptr(op.out), cx.nb, op.cout, op.act, cx.st, cx.u8_desc, cx.b0);
+                                      (bf16_t*)cx.slot_ptr(op.out), cx.nb, op.cout, op.act, cx.st, u->desc, cx.b0);
             return launch_stem(cx.x, (const float*)cx.w(op.w_off), (const float*)cx.w(op.b_off),
-                               (bf16_t*)cx.slot_ptr(op.out), cx.nb, cx.H, cx.W, op.cout, op.act, cx.st);
+                               (bf16_t*)cx.slot_ptr(op.out), cx.nb, s.in.h, s.in.w, op.cout, op.act, cx.st);
         case OP_GEMM: {
-            const int hw = S[op.in].h * S[op.in].w;
+            const int hw = s.in.h * s.in.w;
             GemmArgs a{};
             a.A = (const bf16_t*)cx.slot_ptr(op.in); a.lda = op.cin;
-            a.W = (const bf16_t*)cx.w(op.w_off); a.ldw = (op.cin + 31) & ~31;
+            a.W = (const bf16_t*)cx.w(op.w_off); a.ldw = kpad32(op.cin);
             a.bias = (const float*)cx.w(op.b_off);
             a.res = op.res != SLOT_NONE ? (const bf16_t*)cx.slot_ptr(op.res) : nullptr;
-            a.ldr = op.res != SLOT_NONE ? S[op.res].c : 0;
+            a.ldr = s.res_c;
             a.res_n = op.res_channels ? op.res_channels : op.cout;
             a.gate = op.use_gate ? (const float*)cx.slot_ptr(SLOT_GATE) : nullptr;
             a.gate_ld = op.cin; a.rows_per_img = hw;
@@ -296,14 +455,13 @@ static int exec_op(ExecCtx& cx, const Op& op) {
             a.M_sel = (long)cx.B * hw;
             a.act = op.act; a.a_relu6 = op.a_relu6;
             a.zeros = (const bf16_t*)cx.w(0);
-            if (cx.ln_pending_in != SLOT_NONE) {      // the preceding LayerNorm only left (mean, rstd) per row: fold it in here
+            if (s.ln_in != SLOT_NONE) {      // the preceding LayerNorm only left (mean, rstd) per row: fold it in here
                 MI355_REQUIRE(op.w_ln_off && op.in != SLOT_NONE, "exec: GEMM after a fused LayerNorm has no folded weights");
-                a.A = (const bf16_t*)cx.slot_ptr(cx.ln_pending_in);
+                a.A = (const bf16_t*)cx.slot_ptr(s.ln_in);
                 a.W = (const bf16_t*)cx.w(op.w_ln_off);
                 a.bias = (const float*)cx.w(op.b_ln_off);
                 a.ln_stats = (const float*)cx.slot_ptr(SLOT_LNSTATS);
                 a.ln_colsum = (const float*)cx.w(op.cs_off);
-                cx.ln_pending_in = SLOT_NONE;
             }
             if (m->slots[SLOT_SPLITK].bytes) {
                 a.splitk_ws = (float*)cx.slot_ptr(SLOT_SPLITK);
@@ -314,60 +472,16 @@ static int exec_op(ExecCtx& cx, const Op& op) {
         case OP_DW:
             return launch_dwconv((const bf16_t*)cx.slot_ptr(op.in), (const bf16_t*)cx.w(op.w_off),
                                  (const float*)cx.w(op.b_off), (bf16_t*)cx.slot_ptr(op.out),
-                                 op.pool ? (float*)cx.slot_ptr(SLOT_POOLPART) : nullptr, cx.nb, S[op.in].h, S[op.in].w,
-                                 op.cin, op.k, op.stride, op.act, &m->pool_nblk, cx.st);
-        case OP_SE: {
-            // the squeeze partials were produced by the preceding depthwise conv into SLOT_D's geometry
-            const int ho = S[SLOT_D].h, wo = S[SLOT_D].w;
-            return launch_se((const float*)cx.slot_ptr(SLOT_POOLPART), m->pool_nblk,
-                             1.0f / (float)(ho * wo), (const float*)cx.w(op.w_off), (const float*)cx.w(op.b_off),
+                                 op.pool ? (float*)cx.slot_ptr(SLOT_POOLPART) : nullptr, cx.nb, s.in.h, s.in.w,
+                                 op.cin, op.k, op.stride, op.act, &cx.pool_nblk, cx.st);
+        case OP_SE:
+            return launch_se((const float*)cx.slot_ptr(SLOT_POOLPART), cx.pool_nblk,
+                             1.0f / (float)(s.in.h * s.in.w), (const float*)cx.w(op.w_off), (const float*)cx.w(op.b_off),
                              (const float*)cx.w(op.w2_off), (const float*)cx.w(op.b2_off),
                              (float*)cx.slot_ptr(SLOT_GATE), cx.nb, op.cin, op.rd, op.se_act, cx.st);
-        }
         default:
-            return swin_exec(m->def, op, cx);
+            return swin_exec(op, s, cx);
     }
-}
-
-// row-sweep kernel (MFMA depthwise, complete squeeze sums): the early-stage shape classes of sweep_mbconv.hip
-static bool use_sweep(const mi355_model* m, const Op& g, const Op& d, int h, int w) {
-    return m->fuse_sweep && sweep_mbconv_supported(h, w, g.cin, g.cout, d.k, d.stride, g.act, d.act);
-}
-
-// expand GEMM (-> SLOT_E) immediately followed by the depthwise conv that consumes it, on a whole-image tile
-static bool can_fuse(const mi355_model* m, size_t i, int h, int w) {
-    if (!m->fuse || i + 1 >= m->def.ops.size()) return false;
-    const Op& g = m->def.ops[i];
-    const Op& d = m->def.ops[i + 1];
-    if (g.kind != OP_GEMM || d.kind != OP_DW || g.out != SLOT_E || d.in != SLOT_E) return false;
-    if (g.use_gate || g.res != SLOT_NONE || g.a_relu6 || !g.tap.empty()) return false;
-    if (fused_late_supported(h, w, g.cin, g.cout, d.k, d.stride)) return true;
-    if (use_sweep(m, g, d, h, w)) return true;
-    // Band variant, measured per layer on EfficientNet-B3a B=256 (fused vs expand + depthwise): 3x3 s1 C192 @56x56 307 vs
-    // 339 us (wins); 3x3 s2 C144 @112x112 780 vs 619, 5x5 s2 C192 @56x56 465 vs 276, 5x5 s1 C288 @28x28 247 vs 172 (lose:
-    // short bands recompute too much halo and leave most threads idle in the depthwise phase).
-    // RexNet-200: 3x3 s1 C324 @56x56 (7-row bands) 582 vs 661 us and 3x3 s2 C192 @112x112 714 vs 771 us (win: its 32->192
-    // expand alone costs 0.5 ms).
-    const int rows = m->fuse_band ? fused_band_rows(h, w, g.cin, g.cout, d.k, d.stride) : 0;
-    const bool measured_win = d.k == 3 && ((d.stride == 1 && rows >= 7) || (d.stride == 2 && w >= 112 && g.cout >= 192));
-    return rows > 0 && (m->fuse_band == 1 || measured_win);
-}
-
-// expand GEMM -> depthwise -> SE -> gated projection on a whole-image tile: one kernel (mbconv_block.hip)
-static bool can_fuse_block(const mi355_model* m, size_t i, int h, int w, int nb) {
-    if (!m->fuse_block || nb < m->fuse_block_min_batch || i + 3 >= m->def.ops.size()) return false;
-    const Op& g = m->def.ops[i];
-    const Op& d = m->def.ops[i + 1];
-    const Op& s = m->def.ops[i + 2];
-    const Op& p = m->def.ops[i + 3];
-    if (g.kind != OP_GEMM || d.kind != OP_DW || s.kind != OP_SE || p.kind != OP_GEMM) return false;
-    if (g.out != SLOT_E || d.in != SLOT_E || d.out != SLOT_D || p.in != SLOT_D || !p.use_gate || !d.pool) return false;
-    if (g.use_gate || g.res != SLOT_NONE || g.a_relu6 || !g.tap.empty() || !d.tap.empty()) return false;
-    // (rexnet: ReLU6 behind the gate, a shortcut over the first res_channels outputs and channel counts padded to 8 are all
-    //  handled by the kernel: pad channels carry exact zeros through every phase, as in the unfused chain)
-    if (p.act != ACT_NONE || (p.res != SLOT_NONE && p.res != g.in)) return false;
-    if (p.res != SLOT_NONE && p.res_channels && ((p.res_channels + 7) & ~7) != g.cin) return false;
-    return mbconv_block_supported(h, w, g.cin, g.cout, p.cout, d.k, d.stride, s.rd, g.act, d.act);
 }
 
 // diagnosis buffer [ops][B][16] of cycle buckets (option "block_stamps"); *out stays null when the option is off
@@ -387,112 +501,89 @@ static int stamp_ptr(ExecCtx& cx, size_t oi, long long** out) {
     return OK;
 }
 
-static int exec_block(ExecCtx& cx, size_t oi) {
-    mi355_model* m = cx.m;
-    SlotState* S = m->slots;
-    const Op& g = m->def.ops[oi];
-    const Op& d = m->def.ops[oi + 1];
-    const Op& s = m->def.ops[oi + 2];
-    const Op& p = m->def.ops[oi + 3];
-    BlockArgs a{};
+// The operands FusedArgs, SweepArgs and BlockArgs share: block input, expand and depthwise weights, depthwise output, shapes.
+// (Ho x Wo: the depthwise output, which the block's projection keeps.)
+template <class Args>
+static Args front_half_args(const ExecCtx& cx, const Step& s) {
+    const Op& g = cx.m->def.ops[s.first_op];
+    const Op& d = cx.m->def.ops[s.first_op + 1];
+    Args a{};
     a.X = (const bf16_t*)cx.slot_ptr(g.in);
     a.We = (const bf16_t*)cx.w(g.w_off); a.be = (const float*)cx.w(g.b_off);
     a.Wd = (const bf16_t*)cx.w(d.w_off); a.bd = (const float*)cx.w(d.b_off);
+    a.D = (bf16_t*)cx.slot_ptr(d.out);
+    a.H = s.in.h; a.W = s.in.w; a.Cin = g.cin; a.Kp = kpad32(g.cin); a.mid = g.cout;
+    a.Ho = s.out.h; a.Wo = s.out.w; a.act_e = g.act; a.act_d = d.act;
+    return a;
+}
+
+static int exec_block(ExecCtx& cx, const Step& st) {
+    mi355_model* m = cx.m;
+    const Op& d = m->def.ops[st.first_op + 1];
+    const Op& s = m->def.ops[st.first_op + 2];
+    const Op& p = m->def.ops[st.first_op + 3];
+    BlockArgs a = front_half_args<BlockArgs>(cx, st);
     a.W1 = (const bf16_t*)cx.w(s.w3_off); a.b1 = (const float*)cx.w(s.b_off);
     a.W2 = (const bf16_t*)cx.w(s.w4_off); a.b2 = (const float*)cx.w(s.b2_off);
     a.Wp = (const bf16_t*)cx.w(p.w_off); a.bp = (const float*)cx.w(p.b_off);
-    a.D = (bf16_t*)cx.slot_ptr(d.out);
     a.Y = (bf16_t*)cx.slot_ptr(p.out);
-    a.H = S[g.in].h; a.W = S[g.in].w; a.Cin = g.cin; a.Kp = (g.cin + 31) & ~31; a.mid = g.cout;
-    a.Ho = S[d.out].h; a.Wo = S[d.out].w; a.Cout = p.cout; a.Kp2 = (p.cin + 31) & ~31; a.rd = s.rd;
+    a.Cout = p.cout; a.Kp2 = kpad32(p.cin); a.rd = s.rd;
     a.has_res = p.res != SLOT_NONE;
     a.res_n = p.res != SLOT_NONE ? (p.res_channels ? ((p.res_channels + 7) & ~7) : p.cout) : 0;
     a.a_relu6 = p.a_relu6;
-    a.act_e = g.act; a.act_d = d.act; a.se_act = s.se_act;
+    a.se_act = s.se_act;
     a.inv_hw = 1.0f / (float)(a.Ho * a.Wo);
     a.norot = m->block_norot;
     a.variant = m->block_variant;
-    a.stamps = nullptr;
-    { const int rc = stamp_ptr(cx, oi, &a.stamps); if (rc != OK) return rc; }
+    if (int e = stamp_ptr(cx, st.first_op, &a.stamps)) return e;
     return launch_mbconv_block(a, cx.nb, d.k, d.stride, cx.st);
 }
 
-static int exec_fused(ExecCtx& cx, const Op& g, const Op& d) {
+// expand + depthwise as one launch; leaves the squeeze partials' count for the SE op behind it
+template <class Args>
+static Args fused_pair_args(const ExecCtx& cx, const Step& s) {
+    Args a = front_half_args<Args>(cx, s);
+    a.pool = cx.m->def.ops[s.first_op + 1].pool ? (float*)cx.slot_ptr(SLOT_POOLPART) : nullptr;
+    return a;
+}
+static int exec_fused(ExecCtx& cx, const Step& s) {
     mi355_model* m = cx.m;
-    SlotState* S = m->slots;
-    FusedArgs a{};
-    a.X = (const bf16_t*)cx.slot_ptr(g.in);
-    a.We = (const bf16_t*)cx.w(g.w_off); a.be = (const float*)cx.w(g.b_off);
-    a.Wd = (const bf16_t*)cx.w(d.w_off); a.bd = (const float*)cx.w(d.b_off);
-    a.D = (bf16_t*)cx.slot_ptr(d.out);
-    a.pool = d.pool ? (float*)cx.slot_ptr(SLOT_POOLPART) : nullptr;
-    a.H = S[g.in].h; a.W = S[g.in].w; a.Cin = g.cin; a.Kp = (g.cin + 31) & ~31; a.mid = g.cout;
-    a.Ho = S[d.out].h; a.Wo = S[d.out].w; a.act_e = g.act; a.act_d = d.act;
+    const Op& d = m->def.ops[s.first_op + 1];
+    if (s.how == MI355_PLAN_SWEEP) {
+        SweepArgs a = fused_pair_args<SweepArgs>(cx, s);
+        a.csplit_override = m->sweep_csplit; a.variant = m->sweep_variant; a.debug_skip = m->sweep_skip;
+        if (int e = stamp_ptr(cx, s.first_op, &a.stamps)) return e;
+        cx.pool_nblk = 1;
+        return launch_sweep_mbconv(a, cx.nb, d.k, d.stride, cx.st);
+    }
+    FusedArgs a = fused_pair_args<FusedArgs>(cx, s);
     a.debug_skip = m->fuse_debug;
-    if (fused_late_supported(a.H, a.W, g.cin, g.cout, d.k, d.stride)) {
-        m->pool_nblk = 1;
+    if (s.how == MI355_PLAN_FUSED_LATE) {
+        cx.pool_nblk = 1;
         return launch_fused_late(a, cx.nb, d.k, d.stride, cx.st);
     }
-    if (use_sweep(m, g, d, a.H, a.W)) {
-        SweepArgs sa{};
-        sa.X = a.X; sa.We = a.We; sa.be = a.be; sa.Wd = a.Wd; sa.bd = a.bd; sa.D = a.D; sa.pool = a.pool;
-        sa.H = a.H; sa.W = a.W; sa.Cin = a.Cin; sa.Kp = a.Kp; sa.mid = a.mid; sa.Ho = a.Ho; sa.Wo = a.Wo;
-        sa.act_e = a.act_e; sa.act_d = a.act_d; sa.csplit_override = m->sweep_csplit; sa.variant = m->sweep_variant; sa.debug_skip = m->sweep_skip;
-        { const int rc = stamp_ptr(cx, (size_t)(&g - m->def.ops.data()), &sa.stamps); if (rc != OK) return rc; }
-        m->pool_nblk = 1;
-        return launch_sweep_mbconv(sa, cx.nb, d.k, d.stride, cx.st);
-    }
-    a.TH = fused_band_rows(a.H, a.W, g.cin, g.cout, d.k, d.stride);
-    m->pool_nblk = cdiv(a.Ho, a.TH);
+    a.TH = s.band_rows;
+    cx.pool_nblk = cdiv(a.Ho, a.TH);
     return launch_fused_band(a, cx.nb, d.k, d.stride, cx.st);
 }
 
-// roctx range label of one executor launch (same wording as mi355_model_profile_ops)
-static void op_range_label(const Op& op, int H, int W, int in_h, int in_w, const char* how, char* lab, size_t n) {
-    switch (op.kind) {
-        case OP_STEM: snprintf(lab, n, "embed/%sstem 3->%d @%dx%d", how, op.cout_real, conv_out(H, 3, 2), conv_out(W, 3, 2)); break;
-        case OP_GEMM: snprintf(lab, n, "embed/%spw %d->%d @%dx%d%s%s", how, op.cin_real, op.cout_real, in_h, in_w,
-                               op.use_gate ? " gate" : "", op.res != SLOT_NONE ? " res" : ""); break;
-        case OP_DW: snprintf(lab, n, "embed/%sdw k%d s%d C%d @%dx%d", how, op.k, op.stride, op.cin_real, in_h, in_w); break;
-        case OP_SE: snprintf(lab, n, "embed/%sse C%d rd%d", how, op.cin_real, op.rd); break;
-        default: snprintf(lab, n, "embed/%sop%d C%d->%d t%d", how, (int)op.kind, op.cin_real, op.cout_real, op.tokens_h); break;
-    }
+static int exec_head_gap(ExecCtx& cx, const Op& h, const Step& s) {
+    return launch_head_gap((const bf16_t*)cx.slot_ptr(h.in), h.cin, (const bf16_t*)cx.w(h.w_off), kpad32(h.cin),
+                           (const float*)cx.w(h.b_off), (float*)cx.slot_ptr(SLOT_POOLED),
+                           cx.want_logits ? (bf16_t*)cx.slot_ptr(SLOT_POOLED_BF16) : nullptr, cx.m->def.feat_dim_pad, cx.nb,
+                           s.in.h * s.in.w, h.cout, h.cin, h.act, cx.st);
 }
 
-static int run_backbone(ExecCtx& cx, size_t op_begin = 0, size_t op_end = (size_t)-1) {
+// roctx range label of one step: the per-op table's wording behind how the step runs
+static void step_range_label(const Op& op, const Step& s, char* lab, size_t n) {
+    if (s.how == MI355_PLAN_HEAD_GAP) { snprintf(lab, n, "embed/head 1x1 + global average pool"); return; }
+    snprintf(lab, n, "embed/%s%s", s.how == MI355_PLAN_BLOCK ? "block: " : (s.fused() ? "fused: " : ""), op_cost(op, s.in, 0).label);
+}
+
+static int run_backbone(ExecCtx& cx, const Plan& plan) {
     mi355_model* m = cx.m;
-    // NOTE: slot dims for DW/SE depend on walk order; plan_slots() left the LAST writer's dims in each
-    // slot, so re-derive dims incrementally while executing.
-    SlotState* S = m->slots;
-    if (op_end > m->def.ops.size()) op_end = m->def.ops.size();
-    for (size_t oi = op_begin; oi < op_end; ++oi) {
-        const Op& op = m->def.ops[oi];
-        const int op_index = (int)oi;
-        const int in_h = S[op.in == SLOT_NONE ? 0 : op.in].h, in_w = S[op.in == SLOT_NONE ? 0 : op.in].w;
-        // (the whole-block kernel is chosen by the caller's WHOLE batch, not by the chunk: it rounds differently from the unfused chain)
-        const bool block = op.in != SLOT_NONE && can_fuse_block(m, oi, in_h, in_w, cx.B);
-        const bool fused = block || can_fuse(m, oi, in_h, in_w);
-        if (fused) {   // dims of the (virtual) expand output and of the depthwise output
-            const Op& d = m->def.ops[oi + 1];
-            S[op.out].h = S[op.in].h; S[op.out].w = S[op.in].w; S[op.out].c = op.cout;
-            S[d.out].h = conv_out(S[op.in].h, d.k, d.stride); S[d.out].w = conv_out(S[op.in].w, d.k, d.stride);
-            S[d.out].c = d.cout;
-            if (block) {
-                const Op& pj = m->def.ops[oi + 3];
-                S[pj.out].h = S[d.out].h; S[pj.out].w = S[d.out].w; S[pj.out].c = pj.cout;
-            }
-        } else
-        switch (op.kind) {
-            case OP_STEM: S[op.out].h = conv_out(cx.H, 3, 2); S[op.out].w = conv_out(cx.W, 3, 2); S[op.out].c = op.cout; break;
-            case OP_GEMM: S[op.out].h = S[op.in].h; S[op.out].w = S[op.in].w; S[op.out].c = op.cout; break;
-            case OP_DW: {
-                const int ho = conv_out(S[op.in].h, op.k, op.stride), wo = conv_out(S[op.in].w, op.k, op.stride);
-                S[op.out].h = ho; S[op.out].w = wo; S[op.out].c = op.cout;
-                break;
-            }
-            case OP_SE: break;
-            default: if (op.out != SLOT_NONE) { S[op.out].h = op.tokens_h; S[op.out].w = op.tokens_h; S[op.out].c = op.cout; } break;
-        }
+    for (const Step& s : plan.steps) {
+        const Op& op = m->def.ops[s.first_op];
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (m->profile) {
             MI355_CHECK_HIP(hipEventCreate(&e0));
@@ -501,42 +592,34 @@ static int run_backbone(ExecCtx& cx, size_t op_begin = 0, size_t op_end = (size_
         }
         {
             char lab[192] = "";
-            if (roctx_active())
-                op_range_label(op, cx.H, cx.W, in_h, in_w, block ? "block: " : (fused ? "fused: " : ""), lab, sizeof lab);
+            if (roctx_active()) step_range_label(op, s, lab, sizeof lab);
             RoctxRange range(lab);
-            if (block) {
-                if (int e = exec_block(cx, oi)) return e;
-            } else if (fused) {
-                if (int e = exec_fused(cx, op, m->def.ops[oi + 1])) return e;
-            } else if (int e = exec_op(cx, op)) return e;
+            int e;
+            switch (s.how) {
+                case MI355_PLAN_BLOCK: e = exec_block(cx, s); break;
+                case MI355_PLAN_FUSED_LATE: case MI355_PLAN_SWEEP: case MI355_PLAN_BAND: e = exec_fused(cx, s); break;
+                case MI355_PLAN_HEAD_GAP: e = exec_head_gap(cx, op, s); break;
+                default: e = exec_op(cx, op, s); break;      // MI355_PLAN_OP, and MI355_PLAN_LN_STATS inside swin_exec
+            }
+            if (e) return e;
         }
         if (m->profile) {
             MI355_CHECK_HIP(hipEventRecord(e1, cx.st));
-            m->prof_events.push_back({op_index, {e0, e1}});
-            if (m->prof_fused.size() < m->def.ops.size()) m->prof_fused.resize(m->def.ops.size(), 0);
-            m->prof_fused[op_index] = fused ? 1 : 0;
+            m->prof_events.push_back({s.first_op, s.how, e0, e1});
         }
-        if (block) {
-            const Op& pj = m->def.ops[oi + 3];
-            if (m->taps && !pj.tap.empty())
-                if (int e = record_tap(cx, pj)) return e;
-            oi += 3;       // depthwise, SE and projection ran inside the block kernel
-            continue;
-        }
-        if (m->taps && !op.tap.empty())
-            if (int e = record_tap(cx, op)) return e;
-        if (fused) ++oi;   // the depthwise op was executed together with the expand
+        // a block's tap sits on its projection; an expand + depthwise pair has none (fused_pair_how)
+        const Op& t = m->def.ops[s.first_op + (s.how == MI355_PLAN_BLOCK ? 3 : 0)];
+        if (m->taps && !t.tap.empty())
+            if (int e = record_tap(cx, t, s.out)) return e;
     }
     return OK;
 }
 
-struct U8Source {                     // uint8 images in front of the stem (mi355_model_forward_u8 / _images)
-    const unsigned char* img = nullptr;
-    const int64_t* desc = nullptr;    // ragged batch (device [B][3] {byte offset, h, w}); h = w = the common longer side
-    int h = 0, w = 0, fill = 255;
-    float mean[3] = {0.f, 0.f, 0.f}, stdv[3] = {1.f, 1.f, 1.f};
-    const float* conv_w = nullptr;
-};
+// pooled rows [nb][Dp] fp32 -> the caller's [nb][D]
+static int copy_pooled_rows(float* dst, const float* pooled, int nb, int D, int Dp, hipStream_t st) {
+    MI355_CHECK_HIP(hipMemcpy2DAsync(dst, (size_t)D * 4, pooled, (size_t)Dp * 4, (size_t)D * 4, nb, hipMemcpyDeviceToDevice, st));
+    return OK;
+}
 
 static int forward_impl(mi355_model* m, const float* x, int B, int H, int W, float* out, float* pooled_out,
                         bool features_only, hipStream_t st, const U8Source* u8 = nullptr) {
@@ -558,9 +641,11 @@ static int forward_impl(mi355_model* m, const float* x, int B, int H, int W, flo
     if (nl < 1 || B < 32 * nl || m->profile || m->taps) nl = 1;
     int mb = (m->microbatch > 0 && m->microbatch < B) ? m->microbatch : B;
     if (nl > 1) mb = (B + nl - 1) / nl;
-    const size_t bytes = plan_slots(m, mb, H, W, B);
-    m->lane_bytes = nl > 1 ? align_up(bytes, 4096) : 0;
-    if (int e = ensure_arena(m, nl > 1 ? m->lane_bytes * nl : bytes)) return e;
+    // one plan per distinct chunk size: the chunk's, whose slots lay out the arena, and the shorter tail's (steps only)
+    const size_t last_op = d.ops.size() - 1;
+    const Plan plan = resolve_plan(m, 0, last_op, {}, mb, B, H, W, !features_only);
+    const Plan tail = B % mb ? resolve_plan(m, 0, last_op, {}, B % mb, B, H, W, !features_only) : Plan();
+    if (int e = ensure_arena(m, plan, nl)) return e;
     if (nl > 1) {
         if (!m->lane_fork) MI355_CHECK_HIP(hipEventCreateWithFlags(&m->lane_fork, hipEventDisableTiming));
         for (int l = 0; l < nl; ++l) {
@@ -572,82 +657,39 @@ static int forward_impl(mi355_model* m, const float* x, int B, int H, int W, flo
     hipStream_t caller_st = st;
     int lane = 0;
     const int D = d.feat_dim, Dp = d.feat_dim_pad;
+    const bool want_logits = !features_only && d.num_classes > 0;
     for (int b0 = 0; b0 < B; b0 += mb, ++lane) {
         const int nb = std::min(mb, B - b0);
+        const Plan& cp = nb == mb ? plan : tail;
         if (nl > 1) {
             st = m->lane_stream[lane];
             MI355_CHECK_HIP(hipStreamWaitEvent(st, m->lane_fork, 0));
         }
-        ExecCtx cx{m, st, nb, H, W, x ? x + (size_t)b0 * 3 * H * W : nullptr, b0, B};
+        ExecCtx cx{m, st, nb, x ? x + (size_t)b0 * 3 * H * W : nullptr, b0, B, u8};
         cx.lane = nl > 1 ? lane : 0;
-        if (u8) {
-            cx.x_u8 = u8->desc ? u8->img : u8->img + (size_t)b0 * u8->h * u8->w * 3;   // ragged: the kernels index desc from b0
-            cx.u8_desc = u8->desc;
-            cx.img_h = u8->h; cx.img_w = u8->w; cx.fill = u8->fill; cx.conv_w = u8->conv_w;
-            for (int c = 0; c < 3; ++c) { cx.mean[c] = u8->mean[c]; cx.stdv[c] = u8->stdv[c]; }
-        }
-        const bool want_logits = !features_only && d.num_classes > 0;
-        // Pooled embedding wanted and the last op is the head 1x1 conv: conv + bias + act + GAP as ONE kernel (k_head_gap: the
-        // head tensor never reaches HBM).  forward_features, taps and per-op profiling need the un-pooled map: two-kernel path.
-        bool head_fused = false, backbone_done = false;
-        if (!features_only && !d.pools_in_features && m->fuse_head_gap && !m->taps && !m->profile && !d.ops.empty()) {
-            const Op& h = d.ops.back();
-            if (h.kind == OP_GEMM && h.out == d.final_slot && h.in != SLOT_NONE && !h.use_gate && h.res == SLOT_NONE && !h.a_relu6 &&
-                h.ln_w_name.empty()) {
-                if (int e = run_backbone(cx, 0, d.ops.size() - 1)) return e;
-                const SlotState& I = m->slots[h.in];
-                const int hwi = I.h * I.w;
-                if (head_gap_supported(hwi, h.cout, h.cin, h.cin, (h.cin + 31) & ~31, h.act)) {
-                    RoctxRange range(roctx_active() ? "embed/head 1x1 + global average pool" : "");
-                    if (int e = launch_head_gap((const bf16_t*)cx.slot_ptr(h.in), h.cin, (const bf16_t*)cx.w(h.w_off), (h.cin + 31) & ~31,
-                                                (const float*)cx.w(h.b_off), (float*)cx.slot_ptr(SLOT_POOLED),
-                                                want_logits ? (bf16_t*)cx.slot_ptr(SLOT_POOLED_BF16) : nullptr, Dp, nb, hwi, h.cout, h.cin,
-                                                h.act, st))
-                        return e;
-                    head_fused = true;
-                } else if (int e = run_backbone(cx, d.ops.size() - 1)) return e;
-                backbone_done = true;
-            }
-        }
-        if (!backbone_done)
-            if (int e = run_backbone(cx)) return e;
-        const SlotState& F = m->slots[d.final_slot];
-        const int hw = F.h * F.w;
-        if (d.pools_in_features) {
-            // swin: final op wrote pooled fp32 (+bf16) into SLOT_POOLED / SLOT_POOLED_BF16
-            float* pooled = (float*)cx.slot_ptr(SLOT_POOLED);
-            if (!want_logits)
-                MI355_CHECK_HIP(hipMemcpy2DAsync(out + (size_t)b0 * D, (size_t)D * 4, pooled, (size_t)Dp * 4, (size_t)D * 4,
-                                                 nb, hipMemcpyDeviceToDevice, st));
-            if (pooled_out)
-                MI355_CHECK_HIP(hipMemcpy2DAsync(pooled_out + (size_t)b0 * D, (size_t)D * 4, pooled, (size_t)Dp * 4,
-                                                 (size_t)D * 4, nb, hipMemcpyDeviceToDevice, st));
-        } else {
-            if (features_only) {
-                if (int e = launch_nhwc_to_nchw_f32((const bf16_t*)cx.slot_ptr(d.final_slot),
-                                                    out + (size_t)b0 * D * hw, nb, hw, F.c, D, st))
+        cx.want_logits = want_logits;
+        if (int e = run_backbone(cx, cp)) return e;
+        float* pooled = (float*)cx.slot_ptr(SLOT_POOLED);   // [nb][Dp]; swin: written by the final op, with its bf16 copy
+        if (!d.pools_in_features) {
+            const int hw = cp.final.h * cp.final.w;
+            if (features_only)
+                if (int e = launch_nhwc_to_nchw_f32((const bf16_t*)cx.slot_ptr(d.final_slot), out + (size_t)b0 * D * hw, nb, hw,
+                                                    cp.final.c, D, st))
                     return e;
-            }
-            const bool need_pool = !features_only || pooled_out;
-            if (need_pool) {
-                float* pooled = (float*)cx.slot_ptr(SLOT_POOLED);   // [nb][Dp]
-                if (!head_fused)
-                    if (int e = launch_gap((const bf16_t*)cx.slot_ptr(d.final_slot), pooled,
-                                           want_logits ? (bf16_t*)cx.slot_ptr(SLOT_POOLED_BF16) : nullptr, nb, hw, F.c, st))
-                        return e;
-                if (!features_only && !want_logits)
-                    MI355_CHECK_HIP(hipMemcpy2DAsync(out + (size_t)b0 * D, (size_t)D * 4, pooled, (size_t)Dp * 4,
-                                                     (size_t)D * 4, nb, hipMemcpyDeviceToDevice, st));
-                if (pooled_out)
-                    MI355_CHECK_HIP(hipMemcpy2DAsync(pooled_out + (size_t)b0 * D, (size_t)D * 4, pooled, (size_t)Dp * 4,
-                                                     (size_t)D * 4, nb, hipMemcpyDeviceToDevice, st));
-            }
+            if ((!features_only || pooled_out) && cp.steps.back().how != MI355_PLAN_HEAD_GAP)
+                if (int e = launch_gap((const bf16_t*)cx.slot_ptr(d.final_slot), pooled,
+                                       want_logits ? (bf16_t*)cx.slot_ptr(SLOT_POOLED_BF16) : nullptr, nb, hw, cp.final.c, st))
+                    return e;
         }
+        if ((d.pools_in_features || !features_only) && !want_logits)
+            if (int e = copy_pooled_rows(out + (size_t)b0 * D, pooled, nb, D, Dp, st)) return e;
+        if (pooled_out)
+            if (int e = copy_pooled_rows(pooled_out + (size_t)b0 * D, pooled, nb, D, Dp, st)) return e;
         if (want_logits) {
             const Op& c = d.classifier;
             GemmArgs a{};
             a.A = (const bf16_t*)cx.slot_ptr(SLOT_POOLED_BF16); a.lda = Dp;
-            a.W = (const bf16_t*)cx.w(c.w_off); a.ldw = (c.cin + 31) & ~31;
+            a.W = (const bf16_t*)cx.w(c.w_off); a.ldw = kpad32(c.cin);
             a.bias = (const float*)cx.w(c.b_off);
             a.out = out + (size_t)b0 * d.num_classes; a.ldo = d.num_classes; a.out_f32 = 1;
             a.M = nb; a.N = d.num_classes; a.K = c.cin; a.act = ACT_NONE; a.rows_per_img = 1; a.res_n = a.N;
@@ -796,23 +838,15 @@ int mi355_model_run_between_taps(mi355_model_t m, const char* from_tap, const ch
     MI355_REQUIRE(src.out != SLOT_NONE && (src.cout_real ? src.cout_real : src.cout) == C,
                   "run_between_taps: tap '%s' has %d channels, got %d", from_tap, src.cout_real ? src.cout_real : src.cout, C);
     hipStream_t st = (hipStream_t)stream;
-    // size the arena as for a full forward whose maps are at least as large as the ones reached from here
-    int H = 32, W = 32;
-    for (const Op& op : ops) { (void)op; }
-    {   // input size that gives the tap this resolution: walk the strides in front of it
-        int sh = 1;
-        for (size_t i = 0; i <= i0; ++i)
-            if (ops[i].kind == OP_STEM || (ops[i].kind == OP_DW && ops[i].stride == 2)) sh *= 2;
-        H = h * sh; W = w * sh;
-    }
-    const size_t bytes = plan_slots(m, B, H, W);
-    m->lane_bytes = 0;
-    if (int e = ensure_arena(m, bytes)) return e;
-    ExecCtx cx{m, st, B, H, W, nullptr, 0, B};
-    SlotState* S = m->slots;
-    S[src.out].h = h; S[src.out].w = w; S[src.out].c = src.cout;
+    // size the arena as for a full forward whose input gives the tap this resolution: walk the strides in front of it
+    int sh = 1;
+    for (size_t i = 0; i <= i0; ++i)
+        if (ops[i].kind == OP_STEM || (ops[i].kind == OP_DW && ops[i].stride == 2)) sh *= 2;
+    const Plan plan = resolve_plan(m, i0 + 1, i1, {src.out, {h, w, src.cout}}, B, B, h * sh, w * sh, false);
+    if (int e = ensure_arena(m, plan, 1)) return e;
+    ExecCtx cx{m, st, B, nullptr, 0, B};
     if (int e = launch_nchw_f32_to_nhwc_bf16(x, (bf16_t*)cx.slot_ptr(src.out), B, h * w, C, src.cout, st)) return e;
-    return run_backbone(cx, i0 + 1, i1 + 1);
+    return run_backbone(cx, plan);
 }
 
 int mi355_model_forward_u8(mi355_model_t m, const unsigned char* images, int B, int h, int w, int fill, const float* mean,
@@ -936,20 +970,18 @@ int mi355_model_set_option(mi355_model_t m, const char* key, int64_t value) {
 
 int mi355_model_profile_read(mi355_model_t m, double* ms_by_kind, int64_t* launches_by_kind, int n) {
     MI355_REQUIRE(m && ms_by_kind && launches_by_kind && n >= PK_COUNT, "profile_read: need arrays of >= %d", PK_COUNT);
-    for (auto& pe : m->prof_events) {
-        MI355_CHECK_HIP(hipEventSynchronize(pe.second.second));
+    for (const ProfEvent& pe : m->prof_events) {
+        MI355_CHECK_HIP(hipEventSynchronize(pe.e1));
         float ms = 0.f;
-        MI355_CHECK_HIP(hipEventElapsedTime(&ms, pe.second.first, pe.second.second));
-        int kd = prof_kind(m->def.ops[pe.first]);
-        if (m->fuse && m->def.ops[pe.first].kind == OP_GEMM && m->def.ops[pe.first].out == SLOT_E &&
-            (size_t)pe.first < m->prof_fused.size() && m->prof_fused[pe.first]) kd = PK_FUSED;
+        MI355_CHECK_HIP(hipEventElapsedTime(&ms, pe.e0, pe.e1));
+        const int kd = how_is_fused(pe.how) ? PK_FUSED : prof_kind(m->def.ops[pe.op]);
         m->prof_ms[kd] += ms;
         m->prof_launches[kd] += 1;
         if (m->prof_op_ms.size() < m->def.ops.size()) { m->prof_op_ms.resize(m->def.ops.size(), 0.0); m->prof_op_n.resize(m->def.ops.size(), 0); }
-        m->prof_op_ms[pe.first] += ms;
-        m->prof_op_n[pe.first] += 1;
-        (void)hipEventDestroy(pe.second.first);
-        (void)hipEventDestroy(pe.second.second);
+        m->prof_op_ms[pe.op] += ms;
+        m->prof_op_n[pe.op] += 1;
+        (void)hipEventDestroy(pe.e0);
+        (void)hipEventDestroy(pe.e1);
     }
     m->prof_events.clear();
     for (int i = 0; i < PK_COUNT; ++i) { ms_by_kind[i] = m->prof_ms[i]; launches_by_kind[i] = m->prof_launches[i]; }
@@ -963,105 +995,52 @@ int mi355_model_profile_ops(mi355_model_t m, int B, int H, int W, int max_ops, d
     MI355_REQUIRE(m && avg_ms && bytes && kinds, "profile_ops: null argument");
     const int n = (int)m->def.ops.size();
     MI355_REQUIRE(max_ops >= n, "profile_ops: need room for %d ops", n);
-    SlotState S[SLOT_COUNT];
+    const Plan plan = resolve_plan(m, 0, n - 1, {}, B, B, H, W, false);
     for (int i = 0; i < n; ++i) {
         const Op& op = m->def.ops[i];
+        const OpCost c = op_cost(op, plan.op_in[i], B);
         avg_ms[i] = (i < (int)m->prof_op_n.size() && m->prof_op_n[i]) ? m->prof_op_ms[i] / m->prof_op_n[i] : 0.0;
         kinds[i] = prof_kind(op);
-        double by = 0;
-        char lab[128] = "";
-        switch (op.kind) {
-            case OP_STEM: {
-                const int ho = conv_out(H, 3, 2), wo = conv_out(W, 3, 2);
-                S[op.out].h = ho; S[op.out].w = wo;
-                by = (double)B * (3.0 * H * W * 4 + (double)ho * wo * op.cout_real * 2);
-                snprintf(lab, sizeof lab, "stem 3->%d @%dx%d", op.cout_real, ho, wo);
-                break;
-            }
-            case OP_GEMM: {
-                const double hw = (double)S[op.in].h * S[op.in].w;
-                S[op.out].h = S[op.in].h; S[op.out].w = S[op.in].w;
-                double el = hw * (op.cin_real + op.cout_real);
-                if (op.res != SLOT_NONE) el += hw * (op.res_channels ? op.res_channels : op.cout_real);
-                by = B * el * 2;
-                snprintf(lab, sizeof lab, "pw %d->%d @%dx%d%s%s", op.cin_real, op.cout_real, S[op.in].h, S[op.in].w,
-                         op.use_gate ? " gate" : "", op.res != SLOT_NONE ? " res" : "");
-                break;
-            }
-            case OP_DW: {
-                const int ho = conv_out(S[op.in].h, op.k, op.stride), wo = conv_out(S[op.in].w, op.k, op.stride);
-                by = (double)B * ((double)S[op.in].h * S[op.in].w + (double)ho * wo) * op.cin_real * 2;
-                snprintf(lab, sizeof lab, "dw k%d s%d C%d @%dx%d", op.k, op.stride, op.cin_real, S[op.in].h, S[op.in].w);
-                S[op.out].h = ho; S[op.out].w = wo;
-                break;
-            }
-            case OP_SE: snprintf(lab, sizeof lab, "se C%d rd%d", op.cin_real, op.rd); break;
-            default: {
-                if (op.out != SLOT_NONE) { S[op.out].h = op.tokens_h; S[op.out].w = op.tokens_h; }
-                by = (double)B * op.tokens_h * op.tokens_h * (op.cin_real + op.cout_real) * 2;
-                snprintf(lab, sizeof lab, "op%d C%d->%d t%d", (int)op.kind, op.cin_real, op.cout_real, op.tokens_h);
-                break;
-            }
-        }
-        bytes[i] = by;
-        if (labels && label_stride > 0) { strncpy(labels + (size_t)i * label_stride, lab, label_stride - 1); labels[(size_t)i * label_stride + label_stride - 1] = 0; }
+        bytes[i] = c.table_bytes;
+        if (labels && label_stride > 0) { strncpy(labels + (size_t)i * label_stride, c.label, label_stride - 1); labels[(size_t)i * label_stride + label_stride - 1] = 0; }
     }
     return n;
 }
 
-// Layer-granular algorithmic traffic: every conv/dw/1x1 layer reads its input once and
-// writes its output once; BN/act/SE-gate/GAP are epilogues; each residual adds one read of the block input.
+// Layer-granular algorithmic traffic (op_cost) by kernel family; the ops of a step the executor runs as one fused kernel
+// (expand + depthwise, whole block) count as PK_FUSED.
 int mi355_model_traffic_kinds(mi355_model_t m, int B, int H, int W, double* bytes_by_kind, double* macs_by_kind, int n) {
     MI355_REQUIRE(m && bytes_by_kind && macs_by_kind && n >= PK_COUNT, "traffic_kinds: need arrays of >= %d", PK_COUNT);
     for (int i = 0; i < PK_COUNT; ++i) { bytes_by_kind[i] = 0; macs_by_kind[i] = 0; }
-    SlotState S[SLOT_COUNT];
-    int fused_left = 0;   // > 0 while walking the two ops of a pair the executor runs as one fused kernel
-    for (size_t oi = 0; oi < m->def.ops.size(); ++oi) {
-        const Op& op = m->def.ops[oi];
-        int kd = prof_kind(op);
-        if (fused_left == 0 && op.in != SLOT_NONE && can_fuse_block(m, oi, S[op.in].h, S[op.in].w, B)) fused_left = 4;
-        if (fused_left == 0 && op.in != SLOT_NONE && can_fuse(m, oi, S[op.in].h, S[op.in].w)) fused_left = 2;
-        if (fused_left > 0) { kd = PK_FUSED; --fused_left; }
-        switch (op.kind) {
-            case OP_STEM: {
-                const int ho = conv_out(H, 3, 2), wo = conv_out(W, 3, 2);
-                S[op.out].h = ho; S[op.out].w = wo;
-                bytes_by_kind[kd] += (double)B * (3.0 * H * W * 4 + (double)ho * wo * op.cout_real * 2);
-                macs_by_kind[kd] += (double)B * ho * wo * op.cout_real * 27;
-                break;
-            }
-            case OP_GEMM: {
-                const double hw = (double)S[op.in].h * S[op.in].w;
-                S[op.out].h = S[op.in].h; S[op.out].w = S[op.in].w;
-                double el = hw * (op.cin_real + op.cout_real);
-                if (op.res != SLOT_NONE) el += hw * (op.res_channels ? op.res_channels : op.cout_real);
-                bytes_by_kind[kd] += B * el * 2;
-                macs_by_kind[kd] += B * hw * op.cin_real * op.cout_real;
-                break;
-            }
-            case OP_DW: {
-                const int ho = conv_out(S[op.in].h, op.k, op.stride), wo = conv_out(S[op.in].w, op.k, op.stride);
-                bytes_by_kind[kd] += (double)B * ((double)S[op.in].h * S[op.in].w + (double)ho * wo) * op.cin_real * 2;
-                macs_by_kind[kd] += (double)B * ho * wo * op.cin_real * op.k * op.k;
-                S[op.out].h = ho; S[op.out].w = wo;
-                break;
-            }
-            case OP_SE:
-                macs_by_kind[kd] += (double)B * 2.0 * op.cin_real * op.rd;
-                break;
-            default: {
-                if (op.out != SLOT_NONE) { S[op.out].h = op.tokens_h; S[op.out].w = op.tokens_h; }
-                const double t = (double)op.tokens_h * op.tokens_h;
-                if (op.kind == OP_PATCH_EMBED) bytes_by_kind[kd] += (double)B * (3.0 * H * W * 4 + t * op.cout_real * 2);
-                else if (op.kind == OP_TOKEN_MEAN) bytes_by_kind[kd] += B * t * op.cin_real * 2;
-                else bytes_by_kind[kd] += B * t * (op.cin_real + op.cout_real) * 2;
-                if (op.kind == OP_WINATTN) macs_by_kind[kd] += B * t * (double)(op.window * op.window) * op.cout_real * 2;   // QK^T + PV
-                if (op.kind == OP_PATCH_EMBED) macs_by_kind[kd] += B * t * 48.0 * op.cout_real;
-                break;
-            }
+    const Plan plan = resolve_plan(m, 0, m->def.ops.size() - 1, {}, B, B, H, W, false);
+    for (const Step& s : plan.steps)
+        for (int i = s.first_op; i < s.first_op + s.n_ops; ++i) {
+            const Op& op = m->def.ops[i];
+            const OpCost c = op_cost(op, plan.op_in[i], B);
+            const int kd = s.fused() ? PK_FUSED : prof_kind(op);
+            bytes_by_kind[kd] += c.bytes;
+            macs_by_kind[kd] += c.macs;
         }
-    }
     return OK;
+}
+
+static int plan_args_ok(mi355_model_t m, int B, int nb, int H, int W, int max_steps, const int* first_op, const int* n_ops,
+                        const int* how, const size_t* arena_bytes) {
+    MI355_REQUIRE(m && first_op && n_ops && how && arena_bytes && max_steps >= 0, "model_plan: null argument");
+    MI355_REQUIRE(B >= 1 && nb >= 1 && nb <= B && H >= 32 && W >= 32, "model_plan: bad shape B=%d nb=%d H=%d W=%d", B, nb, H, W);
+    return OK;
+}
+
+int mi355_model_plan(mi355_model_t m, int B, int nb, int H, int W, int pooled, int max_steps, int* first_op, int* n_ops,
+                     int* how, size_t* arena_bytes) {
+    if (int e = plan_args_ok(m, B, nb, H, W, max_steps, first_op, n_ops, how, arena_bytes)) return -e;
+    const Plan plan = resolve_plan(m, 0, m->def.ops.size() - 1, {}, nb, B, H, W, pooled != 0);
+    *arena_bytes = plan.arena_bytes;
+    const int n = (int)plan.steps.size();
+    for (int i = 0; i < n && i < max_steps; ++i) {
+        first_op[i] = plan.steps[i].first_op; n_ops[i] = plan.steps[i].n_ops; how[i] = plan.steps[i].how;
+    }
+    return n;
 }
 
 int mi355_model_traffic(mi355_model_t m, int B, int H, int W, double* act_bytes, double* weight_bytes, double* macs) {

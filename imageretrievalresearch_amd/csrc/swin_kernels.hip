@@ -893,32 +893,27 @@ int swin_pack(Packer& pk, Op& op) {
     }
 }
 
-int swin_exec(const ModelDef& def, const Op& op, ExecCtx& cx) {
+int swin_exec(const Op& op, const Step& s, ExecCtx& cx) {
     switch (op.kind) {
         case OP_PATCH_EMBED: {
-            MI355_REQUIRE(cx.H == 224 && cx.W == 224, "swin needs 224x224 input");
+            MI355_REQUIRE(s.in.h == 224 && s.in.w == 224, "swin needs 224x224 input");
             const float *w = (const float*)cx.w(op.w_off), *bias = (const float*)cx.w(op.b_off), *g = (const float*)cx.w(op.w2_off),
                         *be = (const float*)cx.w(op.b2_off);
             bf16_t* out = (bf16_t*)cx.slot_ptr(op.out);
             PatchU8RaggedArgs r{};
-            if (cx.x_u8) {            // uint8 images: SquarePad + ToTensor + Normalize fused into the patch loads (mi355_model_forward_u8)
-                MI355_REQUIRE(!cx.conv_w, "swin: the conv_input pre-stem belongs to the convolutional backbones");
-                MI355_REQUIRE(std::max(cx.img_h, cx.img_w) == 224, "swin needs images whose longer side is 224 (got %dx%d)", cx.img_h, cx.img_w);
-                r = patch_u8_args(cx.x_u8, cx.img_h, cx.img_w, cx.fill, cx.mean, cx.stdv, cx.u8_desc, cx.b0);
+            if (const U8Source* u = cx.u8) {   // uint8 images: SquarePad + ToTensor + Normalize fused into the patch loads (mi355_model_forward_u8)
+                MI355_REQUIRE(!u->conv_w, "swin: the conv_input pre-stem belongs to the convolutional backbones");
+                MI355_REQUIRE(std::max(u->h, u->w) == 224, "swin needs images whose longer side is 224 (got %dx%d)", u->h, u->w);
+                r = patch_u8_args(cx.x_u8(), u->h, u->w, u->fill, u->mean, u->stdv, u->desc, cx.b0);
             }
-            return launch_patch_embed(cx.x_u8 ? nullptr : cx.x, r, op.cout, w, bias, g, be, out, cx.nb, cx.H, cx.W, op.ln_eps, cx.st);
+            return launch_patch_embed(cx.u8 ? nullptr : cx.x, r, op.cout, w, bias, g, be, out, cx.nb, s.in.h, s.in.w, op.ln_eps, cx.st);
         }
         case OP_LAYERNORM: {
             const long rows = (long)cx.nb * op.tokens_h * op.tokens_h;
-            // Folded into the next GEMM (norm1 -> qkv, norm2 -> fc1) when that GEMM takes the DMA-tiled kernel, whose epilogue
-            // knows how (M >= 1024 rows; smaller problems keep the separate kernel and the unfolded weights)
-            // (and only where that epilogue exists: K >= 128 and a multiple of 64, so swin_s3's width-96 stage keeps the separate kernel)
-            if (op.fuse_next && cx.m->fuse_ln && rows >= 1024 && op.cout >= 128 && op.cout % 64 == 0 &&
-                cx.m->slots[SLOT_LNSTATS].bytes >= (size_t)rows * 8) {
-                cx.ln_pending_in = op.in;
+            // folded into the next GEMM (the plan decides, resolve_plan in model.hip): only the row statistics are left here
+            if (s.how == MI355_PLAN_LN_STATS)
                 return launch_ln<false, true>((const bf16_t*)cx.slot_ptr(op.in), nullptr, nullptr, (bf16_t*)cx.slot_ptr(SLOT_LNSTATS),
                                               rows, op.cout, 0, 0, op.ln_eps, cx.st);
-            }
             return launch_ln<false>((const bf16_t*)cx.slot_ptr(op.in), (const float*)cx.w(op.w_off), (const float*)cx.w(op.b_off),
                                     (bf16_t*)cx.slot_ptr(op.out), rows, op.cout, 0, 0, op.ln_eps, cx.st);
         }

@@ -364,6 +364,18 @@ class MI355Model(nn.Module):
         kinds = ["stem", "gemm", "dw", "se", "other", "attn", "ln", "fused"]
         return [(lab.raw[i * 64:(i + 1) * 64].split(b"\0")[0].decode(), kinds[kd[i]], ms[i], by[i]) for i in range(cnt)]
 
+    def plan(self, B: int, H: int = 224, W: int = 224, chunk: int = 0, pooled: bool = True):
+        """The launch plan of one chunk (``chunk`` images, 0 = all) of a forward of ``B`` images, resolved on the host:
+        ``([(first_op, n_ops, how)], arena_bytes)``; ``pooled=False`` gives the plan of ``forward_features``."""
+        n = 1024
+        fo, no, hw = (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
+        arena = C.c_size_t(0)
+        cnt = lib().mi355_model_plan(self._handle, B, chunk or B, H, W, int(pooled), n, fo, no, hw, C.byref(arena))
+        if cnt < 0:
+            check(cnt)
+        hows = ["op", "fused_late", "sweep", "band", "block", "head_gap", "ln_stats"]
+        return [(fo[i], no[i], hows[hw[i]]) for i in range(cnt)], arena.value
+
     def block_stamps(self):
         """Per-op phase cycle counts of the whole-block kernel (after ``set_option('block_stamps', 1)`` and a forward):
         list of (op_index, [16 cycle buckets]) for the ops that ran as a block (bucket list: end of k_mbconv_block)."""

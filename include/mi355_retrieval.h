@@ -587,6 +587,25 @@ int mi355_model_profile_read(mi355_model_t m, double* ms_by_kind, int64_t* launc
 int mi355_model_profile_ops(mi355_model_t m, int B, int H, int W, int max_ops, double* avg_ms, double* bytes,
                             int* kinds, char* labels, int label_stride);
 
+/* The launch plan of one chunk of a forward: which ops each launch covers and which kernel runs them, resolved from the op
+ * list, the options, the caller's whole batch B, the chunk's nb images (1 <= nb <= B) and the input size; pooled != 0 asks
+ * for the plan of mi355_model_forward (pooled embedding), 0 for that of mi355_model_forward_features.  Host-only: needs no
+ * packed weights and makes no HIP call.  Step s covers the ops [first_op[s], first_op[s] + n_ops[s]) and runs as how[s];
+ * the steps cover every op exactly once, in order.  *arena_bytes: the activation arena one chunk of nb images needs.
+ * Returns the number of steps (arrays of max_steps entries are filled as far as they reach; 1024 is always enough) or a
+ * negative error.  Developer / test tool. */
+enum {
+    MI355_PLAN_OP = 0,          /* one op, its own kernel */
+    MI355_PLAN_FUSED_LATE = 1,  /* expand + depthwise on a whole-image tile (14x14 / 7x7 maps) */
+    MI355_PLAN_SWEEP = 2,       /* expand + depthwise, row-sweep kernel */
+    MI355_PLAN_BAND = 3,        /* expand + depthwise, row-band kernel */
+    MI355_PLAN_BLOCK = 4,       /* expand, depthwise, SE and gated projection: the whole MBConv block in one kernel */
+    MI355_PLAN_HEAD_GAP = 5,    /* head 1x1 conv + global average pool */
+    MI355_PLAN_LN_STATS = 6     /* LayerNorm as a row-statistics pass; the next GEMM step applies it in its epilogue */
+};
+int mi355_model_plan(mi355_model_t m, int B, int nb, int H, int W, int pooled, int max_steps, int* first_op, int* n_ops,
+                     int* how, size_t* arena_bytes);
+
 /* Diagnosis of the whole-MBConv-block kernel (option "block_stamps" = 1): per-phase shader-cycle counts of the LAST forward,
  * averaged over its images.  out[op][16] in plan order (rows of ops that did not run as a block kernel stay 0); the 16
  * buckets are listed at the end of k_mbconv_block (csrc/mbconv_block.hip).  Synchronises the device.  Returns the number

@@ -23,8 +23,11 @@ for _ in range(5):
     model(x)
 fam = model.profile_read()
 tot = 0.0
-print(f"{'op':38s} {'kind':5s} {'ms':>8s} {'MB':>9s} {'GB/s':>8s}")
-for lab, kind, ms, by in model.profile_ops(B):
+how = {}      # op index -> how its launch ran; "^" = inside the launch of the op above
+for first, n, h in model.plan(B, pooled=False)[0]:
+    how.update({first + j: h if j == 0 else "^" for j in range(n)})
+print(f"{'op':38s} {'kind':5s} {'how':10s} {'ms':>8s} {'MB':>9s} {'GB/s':>8s}")
+for i, (lab, kind, ms, by) in enumerate(model.profile_ops(B)):
     tot += ms
-    print(f"{lab:38s} {kind:5s} {ms:8.4f} {by / 1e6:9.1f} {by / max(ms, 1e-9) / 1e6:8.0f}")
+    print(f"{lab:38s} {kind:5s} {how[i]:10s} {ms:8.4f} {by / 1e6:9.1f} {by / max(ms, 1e-9) / 1e6:8.0f}")
 print("sum of op ms per forward", tot, {k: round(v['ms'] / 5, 3) for k, v in fam.items() if v['launches']})
