@@ -37,6 +37,13 @@ class DwconvExArgs(C.Structure):
                 ("gate", vp), ("squeeze", vp)]
 
 
+class StemExArgs(C.Structure):
+    """mi355_stem_ex_args (include/mi355_retrieval.h), the operand block of the developer entry mi355_stem_ex."""
+    _fields_ = [("x", vp), ("images", vp), ("images_bytes", C.c_int64), ("desc_host", vp), ("desc_dev", vp),
+                ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("fill", C.c_int), ("mean", c_f32p), ("stdv", c_f32p),
+                ("conv_input_w", vp), ("w", vp), ("bias", vp), ("out", vp), ("Cout", C.c_int), ("act", C.c_int)]
+
+
 DW_CHOICE_AUTO, DW_CHOICE_DIRECT, DW_CHOICE_TILED, DW_CHOICE_MFMA = 0, 1, 2, 3
 
 
@@ -178,6 +185,12 @@ PROTOTYPES = {
     "mi355_gemm_bf16": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "mi355_gemm_bf16_ex": (C.c_int, [vp, C.POINTER(C.c_int), vp]),
     "mi355_dwconv_se_ex": (C.c_int, [vp, C.POINTER(C.c_int), vp]),
+    "mi355_stem_ex": (C.c_int, [vp, C.POINTER(C.c_int), vp]),
+    "mi355_head_gap_ex": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    C.POINTER(C.c_int), vp]),
+    "mi355_gap": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    "mi355_nhwc_to_nchw": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "mi355_nchw_to_nhwc": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "mi355_window_attention": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "mi355_window_attention_ws": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "mi355_swin_layernorm": (C.c_int, [vp, vp, vp, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp]),

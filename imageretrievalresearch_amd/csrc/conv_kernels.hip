@@ -125,7 +125,7 @@ _Pragma("unroll")
 }
 
 int launch_stem(const float* x, const float* w, const float* bias, bf16_t* out, int B, int H, int W, int Cout, int act,
-                hipStream_t st) {
+                hipStream_t st, int* path) {
     MI355_REQUIRE(Cout % 8 == 0 && Cout <= 256, "stem: Cout=%d must be a multiple of 8 and <= 256", Cout);
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
     const size_t lds = stem_lds_bytes(Cout);
@@ -136,6 +136,7 @@ int launch_stem(const float* x, const float* w, const float* bias, bf16_t* out, 
     dim3 grid(cdiv(Wo, STEM_TW), cdiv(Ho, STEM_TH), B);
     hipLaunchKernelGGL(k_stem, grid, dim3(256), lds, st, x, w, bias, out, H, W, Ho, Wo, Cout, act);
     MI355_LAUNCH_CHECK();
+    if (path) *path = (W & 3) == 0 ? MI355_STEM_PATH_F32_LOAD16 : MI355_STEM_PATH_F32_LOAD4;   // k_stem's staging branch
     return OK;
 }
 
@@ -260,7 +261,7 @@ _Pragma("unroll")
 
 int launch_stem_u8(const unsigned char* img, int h, int w, int fill, const float* mean, const float* stdv,
                    const float* conv_w, const float* sw, const float* bias, bf16_t* out, int B, int Cout, int act,
-                   hipStream_t st, const int64_t* desc, int b0) {
+                   hipStream_t st, const int64_t* desc, int b0, int* path) {
     MI355_REQUIRE(Cout % 8 == 0 && Cout <= 256, "stem: Cout=%d must be a multiple of 8 and <= 256", Cout);
     StemU8RaggedArgs r{};
     StemU8Args& a = r;
@@ -270,15 +271,23 @@ int launch_stem_u8(const unsigned char* img, int h, int w, int fill, const float
     r.desc = desc; r.b0 = b0;
     const int Ho = (a.S + 2 - 3) / 2 + 1, Wo = Ho;
     dim3 grid(cdiv(Wo, 32), cdiv(Ho, 8), B);
+    int ran = MI355_STEM_PATH_U8;
     if (desc) {
-        if (conv_w) hipLaunchKernelGGL((k_stem_u8<true, true>), grid, dim3(256), 0, st, r, sw, bias, out, Ho, Wo, Cout, act);
-        else hipLaunchKernelGGL((k_stem_u8<false, true>), grid, dim3(256), 0, st, r, sw, bias, out, Ho, Wo, Cout, act);
+        ran |= MI355_STEM_PATH_RAGGED;
+        if (conv_w) {
+            ran |= MI355_STEM_PATH_CONV_INPUT;
+            hipLaunchKernelGGL((k_stem_u8<true, true>), grid, dim3(256), 0, st, r, sw, bias, out, Ho, Wo, Cout, act);
+        } else {
+            hipLaunchKernelGGL((k_stem_u8<false, true>), grid, dim3(256), 0, st, r, sw, bias, out, Ho, Wo, Cout, act);
+        }
     } else if (conv_w) {
+        ran |= MI355_STEM_PATH_CONV_INPUT;
         hipLaunchKernelGGL((k_stem_u8<true, false>), grid, dim3(256), 0, st, a, sw, bias, out, Ho, Wo, Cout, act);
     } else {
         hipLaunchKernelGGL((k_stem_u8<false, false>), grid, dim3(256), 0, st, a, sw, bias, out, Ho, Wo, Cout, act);
     }
     MI355_LAUNCH_CHECK();
+    if (path) *path = ran;
     return OK;
 }
 

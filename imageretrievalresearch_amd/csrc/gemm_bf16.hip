@@ -1219,14 +1219,18 @@ static int launch_head_gap_cfg(const bf16_t* A, int lda, const bf16_t* W, int ld
 }
 
 int launch_head_gap(const bf16_t* A, int lda, const bf16_t* W, int ldw, const float* bias, float* pooled, bf16_t* pooled_bf16,
-                    int ldp, int B, int HW, int N, int K, int act, hipStream_t st) {
+                    int ldp, int B, int HW, int N, int K, int act, hipStream_t st, int* path) {
     MI355_REQUIRE(head_gap_supported(HW, N, K, lda, ldw, act), "head_gap: unsupported shape HW=%d N=%d K=%d", HW, N, K);
     const bool small_k = K <= 12 * 32;
+    int e;
     if (act == ACT_SILU)
-        return small_k ? launch_head_gap_cfg<ACT_SILU, 12>(A, lda, W, ldw, bias, pooled, pooled_bf16, ldp, B, HW, N, K, st)
-                       : launch_head_gap_cfg<ACT_SILU, 16>(A, lda, W, ldw, bias, pooled, pooled_bf16, ldp, B, HW, N, K, st);
-    return small_k ? launch_head_gap_cfg<ACT_NONE, 12>(A, lda, W, ldw, bias, pooled, pooled_bf16, ldp, B, HW, N, K, st)
-                   : launch_head_gap_cfg<ACT_NONE, 16>(A, lda, W, ldw, bias, pooled, pooled_bf16, ldp, B, HW, N, K, st);
+        e = small_k ? launch_head_gap_cfg<ACT_SILU, 12>(A, lda, W, ldw, bias, pooled, pooled_bf16, ldp, B, HW, N, K, st)
+                    : launch_head_gap_cfg<ACT_SILU, 16>(A, lda, W, ldw, bias, pooled, pooled_bf16, ldp, B, HW, N, K, st);
+    else
+        e = small_k ? launch_head_gap_cfg<ACT_NONE, 12>(A, lda, W, ldw, bias, pooled, pooled_bf16, ldp, B, HW, N, K, st)
+                    : launch_head_gap_cfg<ACT_NONE, 16>(A, lda, W, ldw, bias, pooled, pooled_bf16, ldp, B, HW, N, K, st);
+    if (path && e == OK) *path = MI355_HEAD_GAP_PATH(act, small_k ? 12 : 16);
+    return e;
 }
 
 // Which branch ran goes to *path (MI355_GEMM_PATH_* | NT << 8, include/mi355_retrieval.h) when path is not null: the op-level tests

@@ -1202,6 +1202,86 @@ int mi355_dwconv_se_ex(const mi355_dwconv_ex_args* x, int* path, void* stream) {
     return OK;
 }
 
+int mi355_stem_ex(const mi355_stem_ex_args* x, int* path, void* stream) {
+    if (path) *path = 0;
+    MI355_REQUIRE(x, "stem_ex: null argument block");
+    MI355_REQUIRE(x->w && x->bias && x->out, "stem_ex: null pointer (w, bias, out)");
+    MI355_REQUIRE(!x->x != !x->images, "stem_ex: exactly one of x (fp32 form) and images (uint8 form) is given");
+    MI355_REQUIRE(x->B >= 1 && x->B <= 65535 && x->H >= 1 && x->W >= 1 && x->H <= 16384 && x->W <= 16384,
+                  "stem_ex: bad shape B=%d H=%d W=%d", x->B, x->H, x->W);
+    MI355_REQUIRE(x->Cout >= 8 && x->Cout % 8 == 0 && x->Cout <= 256, "stem_ex: Cout=%d must be a multiple of 8 in 8..256", x->Cout);
+    MI355_REQUIRE(x->act >= ACT_NONE && x->act <= ACT_SIGMOID, "stem_ex: unknown activation %d", x->act);
+    for (const void* p : {(const void*)x->x, (const void*)x->w, (const void*)x->bias, (const void*)x->out})
+        MI355_REQUIRE((uintptr_t)p % 16 == 0, "stem_ex: x, w, bias and out must be 16-byte aligned");
+    const hipStream_t st = (hipStream_t)stream;
+    if (x->x) {
+        MI355_REQUIRE(!x->desc_host && !x->desc_dev && !x->conv_input_w,
+                      "stem_ex: descriptors and conv_input belong to the uint8 form");
+        return launch_stem(x->x, x->w, x->bias, (bf16_t*)x->out, x->B, x->H, x->W, x->Cout, x->act, st, path);
+    }
+    MI355_REQUIRE(x->mean && x->stdv, "stem_ex: null pointer (mean, stdv)");
+    MI355_REQUIRE(x->fill >= 0 && x->fill <= 255, "stem_ex: fill %d is not a byte value", x->fill);
+    for (int c = 0; c < 3; ++c) MI355_REQUIRE(x->stdv[c] != 0.f, "stem_ex: std[%d] is zero", c);
+    MI355_REQUIRE((uintptr_t)x->conv_input_w % 4 == 0, "stem_ex: conv_input_w must be 4-byte aligned");
+    MI355_REQUIRE(!x->desc_host == !x->desc_dev, "stem_ex: desc_host and desc_dev go together");
+    if (x->desc_host) {
+        if (int e = check_images(x->images, x->images_bytes, x->desc_host, x->desc_dev, x->B, "stem_ex")) return e;
+        MI355_REQUIRE(x->H == x->W, "stem_ex: a ragged batch takes H == W == S, the common longer side (H=%d W=%d)", x->H, x->W);
+        for (int b = 0; b < x->B; ++b) {
+            const long long s = (long long)std::max(x->desc_host[(size_t)b * 3 + 1], x->desc_host[(size_t)b * 3 + 2]);
+            MI355_REQUIRE(s == x->H, "stem_ex: image %d has longer side %lld, the batch's S is %d", b, s, x->H);
+        }
+    }
+    return launch_stem_u8(x->images, x->H, x->W, x->fill, x->mean, x->stdv, x->conv_input_w, x->w, x->bias, (bf16_t*)x->out, x->B,
+                          x->Cout, x->act, st, x->desc_dev, 0, path);
+}
+
+int mi355_head_gap_ex(const void* A, int lda, const void* W, int ldw, const float* bias, float* pooled, void* pooled_bf16, int ldp,
+                      int B, int HW, int N, int K, int act, int* path, void* stream) {
+    if (path) *path = 0;
+    MI355_REQUIRE(A && W && bias && pooled, "head_gap_ex: null pointer");
+    MI355_REQUIRE(B >= 1 && B <= 4 * 65535 && N >= 8, "head_gap_ex: bad shape B=%d N=%d", B, N);
+    MI355_REQUIRE(head_gap_supported(HW, N, K, lda, ldw, act) && lda >= K,
+                  "head_gap_ex: the kernel takes 1 <= HW <= 64, 32 <= K <= 512, lda a multiple of 8 and >= K, ldw a multiple of 32 "
+                  "and >= K rounded up to 32, N a multiple of 8, act none or SiLU (HW=%d N=%d K=%d lda=%d ldw=%d act=%d)",
+                  HW, N, K, lda, ldw, act);
+    MI355_REQUIRE(ldp >= N && ldp % 2 == 0, "head_gap_ex: ldp=%d must be even and >= N=%d", ldp, N);
+    for (const void* p : {A, W, (const void*)bias, (const void*)pooled, (const void*)pooled_bf16})
+        MI355_REQUIRE((uintptr_t)p % 16 == 0, "head_gap_ex: pointers must be 16-byte aligned");
+    return launch_head_gap((const bf16_t*)A, lda, (const bf16_t*)W, ldw, bias, pooled, (bf16_t*)pooled_bf16, ldp, B, HW, N, K, act,
+                           (hipStream_t)stream, path);
+}
+
+int mi355_gap(const void* in, int B, int HW, int C, float* pooled, void* pooled_bf16, void* stream) {
+    MI355_REQUIRE(in && pooled, "gap: null pointer");
+    MI355_REQUIRE(B >= 1 && HW >= 1 && C >= 8, "gap: bad shape B=%d HW=%d C=%d", B, HW, C);
+    MI355_REQUIRE(C % 8 == 0, "gap: C=%d must be a multiple of 8", C);
+    MI355_REQUIRE((long)B * (C / 8) < (1l << 31), "gap: B=%d x C=%d too large", B, C);
+    for (const void* p : {in, (const void*)pooled, (const void*)pooled_bf16})
+        MI355_REQUIRE((uintptr_t)p % 16 == 0, "gap: pointers must be 16-byte aligned");
+    return launch_gap((const bf16_t*)in, pooled, (bf16_t*)pooled_bf16, B, HW, C, (hipStream_t)stream);
+}
+
+// the layout kernels' grid is (HW / 32, C / 32, B)
+static int layout_args_ok(const char* who, const void* in, const void* out, int B, int HW, int C, int Cvalid, int in_align) {
+    MI355_REQUIRE(in && out, "%s: null pointer", who);
+    MI355_REQUIRE(B >= 1 && B <= 65535 && HW >= 1 && C >= 1 && C <= 32 * 65535, "%s: bad shape B=%d HW=%d C=%d", who, B, HW, C);
+    MI355_REQUIRE(Cvalid >= 1 && Cvalid <= C, "%s: Cvalid=%d outside 1..C=%d", who, Cvalid, C);
+    MI355_REQUIRE((uintptr_t)in % in_align == 0 && (uintptr_t)out % (6 - in_align) == 0,
+                  "%s: pointers must be aligned to their element size", who);
+    return OK;
+}
+
+int mi355_nhwc_to_nchw(const void* in, float* out, int B, int HW, int C, int Cvalid, void* stream) {
+    if (int e = layout_args_ok("nhwc_to_nchw", in, out, B, HW, C, Cvalid, 2)) return e;
+    return launch_nhwc_to_nchw_f32((const bf16_t*)in, out, B, HW, C, Cvalid, (hipStream_t)stream);
+}
+
+int mi355_nchw_to_nhwc(const float* in, void* out, int B, int HW, int C, int Cvalid, void* stream) {
+    if (int e = layout_args_ok("nchw_to_nhwc", in, out, B, HW, C, Cvalid, 4)) return e;
+    return launch_nchw_f32_to_nhwc_bf16(in, (bf16_t*)out, B, HW, Cvalid, C, (hipStream_t)stream);
+}
+
 int mi355_pool_linear(const float* fm, int B, int C, int HW, const float* weight, const float* bias, int N, float* out,
                       float* pooled_out, void* stream) {
     MI355_REQUIRE(fm && (out || pooled_out), "pool_linear: null pointer");

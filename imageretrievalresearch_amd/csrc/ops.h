@@ -105,8 +105,9 @@ int launch_mbconv_block(const BlockArgs& a, int B, int k, int stride, hipStream_
 // ---- convolution-side kernels (conv_kernels.hip) -----------------------------------------------
 // Stem: x [B][3][H][W] fp32 NCHW -> out [B][Ho][Wo][Cout] bf16, 3x3 stride 2 pad 1, + bias + act.
 // w [3*3*3][Cout] fp32 laid out (ky, kx, ci) major, bias fp32 [Cout].
+// path (may be null): MI355_STEM_PATH_* of the kernel branch that ran (include/mi355_retrieval.h).
 int launch_stem(const float* x, const float* w, const float* bias, bf16_t* out, int B, int H, int W, int Cout,
-                int act, hipStream_t st);
+                int act, hipStream_t st, int* path = nullptr);
 
 // Fused input + stem: img [B][h][w][3] uint8 -> SquarePad(fill) / ToTensor / Normalize (host mean / std) -> optional
 // conv_input (conv_w: device fp32 [3][3][3][3], null = none) + SiLU -> stem; out [B][S/2][S/2][Cout] bf16, S = max(h, w).
@@ -114,7 +115,7 @@ int launch_stem(const float* x, const float* w, const float* bias, bf16_t* out, 
 // S = max(h, w) of the arguments; image b of this launch is desc[b0 + b].
 int launch_stem_u8(const unsigned char* img, int h, int w, int fill, const float* mean, const float* stdv,
                    const float* conv_w, const float* sw, const float* bias, bf16_t* out, int B, int Cout, int act,
-                   hipStream_t st, const int64_t* desc = nullptr, int b0 = 0);
+                   hipStream_t st, const int64_t* desc = nullptr, int b0 = 0, int* path = nullptr);
 
 // ---- ragged uint8 batches (preprocess.hip) -----------------------------------------------------------------------------
 // Argument checks of a packed batch: B >= 1, non-null pointers, every descriptor {byte offset, h, w} (host copy) in range.
@@ -154,9 +155,10 @@ int launch_se(const float* pool_partial, int nblk, float inv_hw, const float* w1
 // Global average pool of NHWC bf16 -> pooled fp32 [B][C] (+ optional bf16 copy for the classifier GEMM).
 int launch_gap(const bf16_t* in, float* pooled, bf16_t* pooled_bf16, int B, int HW, int C, hipStream_t st);
 // head 1x1 conv + bias + act + global average pool in one kernel (gemm_bf16.hip); pooled / pooled_bf16: [B][ldp]
+// path (may be null): MI355_HEAD_GAP_PATH(act, KSMAX) of the instantiation that ran.
 bool head_gap_supported(int HW, int N, int K, int lda, int ldw, int act);
 int launch_head_gap(const bf16_t* A, int lda, const bf16_t* W, int ldw, const float* bias, float* pooled, bf16_t* pooled_bf16,
-                    int ldp, int B, int HW, int N, int K, int act, hipStream_t st);
+                    int ldp, int B, int HW, int N, int K, int act, hipStream_t st, int* path = nullptr);
 
 // ClassifierHead on an un-pooled NCHW fp32 map: pooled_out (optional) [B][C] fp32 = mean over HW; out (when w != null) [B][N]
 // = Linear(bf16(pooled); bf16(w) [N][C], bias [N] or null) with fp32 accumulation.

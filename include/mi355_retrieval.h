@@ -711,6 +711,69 @@ enum {
 
 int mi355_dwconv_se_ex(const mi355_dwconv_ex_args* args, int* path, void* stream);
 
+/* Developer entry: one stem call of the convolutional backbones (3x3 stride 2 pad 1, 3 -> Cout, + bias + act) through the
+ * model's launchers, in either input form.  Exactly one of x and images is non-null.
+ *   out[b][oy][ox][co] = bf16( act( bias[co] + sum_{ky,kx,ci} in[b][ci][2 oy - 1 + ky][2 ox - 1 + kx] w[(ky*3 + kx)*3 + ci][co] ) )
+ *                        (zero padding), out [B][Ho][Wo][Cout] bf16 NHWC, Ho = (H - 1) / 2 + 1, Wo likewise
+ *   w [27][Cout] fp32 in pack_stem's tap order (ky*3 + kx)*3 + ci, bias [Cout] fp32; Cout a multiple of 8, <= 256.
+ *   fp32 form  x [B][3][H][W] fp32 NCHW is `in`.
+ *   uint8 form images [B][H][W][3] uint8 (every image H x W) -> SquarePad(fill) to S x S, S = max(H, W) -> /255 ->
+ *              (v - mean) / stdv (HOST float[3]) -> optional conv_input (conv_input_w: device fp32 [3][3][3][3]) + SiLU with
+ *              no rounding in between, zero outside the S x S square -> `in` of the stem; Ho = Wo = (S - 1) / 2 + 1.
+ *              Ragged (desc_host and desc_dev non-null, the same [B][3] int64 {byte offset into images, h, w} on the host
+ *              and on the device; images_bytes = size of the packed buffer): H == W == S and every image's max(h, w) == S.
+ * Bits: the uint8 form equals mi355_square_pad_normalize (-> mi355_conv_input_silu) -> the fp32 form; ragged equals uniform
+ * per image.  path (host, may be NULL) receives what ran: MI355_STEM_PATH_F32_LOAD16 (W % 4 == 0: 16-byte staging loads) or
+ * _F32_LOAD4, or MI355_STEM_PATH_U8 | _CONV_INPUT | _RAGGED.  x, w, bias, out: 16-byte aligned; conv_input_w: 4-byte aligned.
+ * Every argument is checked before any HIP call.  Does not synchronise. */
+typedef struct mi355_stem_ex_args {
+    const float* x;
+    const unsigned char* images; int64_t images_bytes;
+    const int64_t* desc_host; const int64_t* desc_dev;
+    int B, H, W;
+    int fill; const float* mean; const float* stdv;
+    const float* conv_input_w;
+    const float* w; const float* bias; void* out;
+    int Cout, act;
+} mi355_stem_ex_args;
+
+enum {
+    MI355_STEM_PATH_F32_LOAD16 = 1,     /* k_stem, input band staged with 16-byte loads (W % 4 == 0) */
+    MI355_STEM_PATH_F32_LOAD4 = 2,      /* k_stem, input band staged with 4-byte loads */
+    MI355_STEM_PATH_U8 = 3,             /* k_stem_u8<CONV_INPUT, RAGGED> */
+    MI355_STEM_PATH_CONV_INPUT = 0x100,
+    MI355_STEM_PATH_RAGGED = 0x200
+};
+
+int mi355_stem_ex(const mi355_stem_ex_args* args, int* path, void* stream);
+
+/* Developer entry: head 1x1 conv + bias + act + global average pool in one kernel (k_head_gap) through the model's launcher.
+ *   pooled[b][n] = (1 / HW) sum_p float( bf16( act( sum_k A[b * HW + p][k] W[n][k] + bias[n] ) ) ),  p = 0 .. HW-1 in order
+ *   pooled_bf16 (optional) [B][ldp] bf16: the same values rounded once.  Bit for bit mi355_gemm_bf16_ex (bf16 out) -> mi355_gap.
+ * A [B * HW][lda] bf16, W bf16 [ceil16(N)][ldw] zero padded past K, bias fp32 [ceil16(N)], pooled fp32 [B][ldp]; all 16-byte
+ * aligned device pointers.  Rejected for shapes the kernel does not take: 1 <= HW <= 64, 32 <= K <= 512, lda a multiple of
+ * 8 and >= K, ldw a multiple of 32 and >= K rounded up to 32, N a multiple of 8, act none (0) or SiLU (1); and ldp >= N, even.
+ * path (host, may be NULL) receives MI355_HEAD_GAP_PATH(act, KSMAX) of the instantiation: KSMAX 12 (K <= 384) or 16.
+ * Every argument is checked before any HIP call.  Does not synchronise. */
+#define MI355_HEAD_GAP_PATH(act, ksmax) ((act) | (ksmax) << 8)
+#define MI355_HEAD_GAP_PATH_ACT(p) ((p) & 0xff)
+#define MI355_HEAD_GAP_PATH_KSMAX(p) (((p) >> 8) & 0xff)
+int mi355_head_gap_ex(const void* A, int lda, const void* W, int ldw, const float* bias, float* pooled, void* pooled_bf16, int ldp,
+                      int B, int HW, int N, int K, int act, int* path, void* stream);
+
+/* Developer entry: global average pool (k_gap).  in [B][HW][C] bf16 -> pooled [B][C] fp32 = (sum_p in[b][p][c]) * (1 / HW),
+ * fp32, the pixels added in ascending order; pooled_bf16 (optional) [B][C] bf16, the same values rounded once.  C a multiple
+ * of 8; 16-byte aligned device pointers.  Every argument is checked before any HIP call.  Does not synchronise. */
+int mi355_gap(const void* in, int B, int HW, int C, float* pooled, void* pooled_bf16, void* stream);
+
+/* Developer entries: the two layout kernels behind forward_features, the taps and mi355_model_run_between_taps.
+ *   mi355_nhwc_to_nchw: in [B][HW][C] bf16 -> out [B][Cvalid][HW] fp32, out[b][c][p] = float(in[b][p][c]) (exact), c < Cvalid.
+ *   mi355_nchw_to_nhwc: in [B][Cvalid][HW] fp32 -> out [B][HW][C] bf16, out[b][p][c] = bf16(in[b][c][p]) (nearest even) for
+ *                       c < Cvalid and zero for Cvalid <= c < C.
+ * 1 <= Cvalid <= C.  Every argument is checked before any HIP call.  Neither synchronises. */
+int mi355_nhwc_to_nchw(const void* in, float* out, int B, int HW, int C, int Cvalid, void* stream);
+int mi355_nchw_to_nhwc(const float* in, void* out, int B, int HW, int C, int Cvalid, void* stream);
+
 /* Developer entry: one Swin window-attention layer (window 7, head_dim 32) through the model's kernel.
  *   qkv [B][res*res][3C] bf16 (channel = which * C + head * 32 + d, tokens in image order), out [B][res*res][C] bf16,
  *   bias_table [169][heads] fp32 (timm relative_position_bias_table), packed to the kernel's dense layout by the model's
