@@ -80,6 +80,9 @@ PROTOTYPES = {
     "mi355_rank_topk_f16_filtered": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_int64,
                                                C.POINTER(RankFilter), vp, vp, vp, C.c_size_t, vp]),
     "mi355_rank_last_path": (C.c_int, []),
+    "mi355_rank_round_split": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "mi355_rank_set_round_slots": (C.c_int, [C.c_int]),
+    "mi355_rank_last_tiles": (C.c_int, [C.POINTER(C.c_int), C.c_int]),
     "mi355_expand_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
     "mi355_expand_rows": (C.c_int, [vp, C.c_int, C.c_int64, C.c_int, vp, C.c_int, C.c_int64, C.c_int64, C.c_int, vp, vp,
                                     C.c_int64, C.c_int, C.c_int64, C.c_float, C.c_float, vp, C.c_int, C.c_int64, vp,

@@ -1065,6 +1065,15 @@ int whole_round_tiles(int ntx, int ny, int slots) {
     return ntx;
 }
 
+// Test override of the slots (0: the device's own) and the last cut, per thread like the rank path
+static thread_local int g_round_slots = 0;
+static thread_local int g_last_tiles[5] = {0, 0, 0, 0, 0};
+int round_slots(int device_slots) { return g_round_slots > 0 ? g_round_slots : device_slots; }
+void set_last_tiles(int slots, int ny, int main_tiles, int tail_tiles, int tail_ny) {
+    g_last_tiles[0] = slots; g_last_tiles[1] = ny; g_last_tiles[2] = main_tiles; g_last_tiles[3] = tail_tiles;
+    g_last_tiles[4] = tail_ny;
+}
+
 // ---- the tiled GEMM families of this file (launch_tiles, rank_common.h)
 // Exact fp32 loop (qry: the normalised fp32 rows).  Tile choice, measured on MI355X (tools/bench_rank.py, D = 1536): it
 // plateaus at 95-110 TFLOP/s for every tile shape, so what differs is the partial last round of tiles.  128-query tiles with
@@ -1427,6 +1436,24 @@ int mi355_rank_topk_filtered(const float* queries, int64_t Q, const float* galle
 }
 
 int mi355_rank_last_path(void) { return g_rank_path; }
+
+int mi355_rank_round_split(int ntx, int ny, int slots) {
+    if (ntx < 0 || ny < 1 || slots < 1) return -1;
+    return whole_round_tiles(ntx, ny, slots);
+}
+
+int mi355_rank_set_round_slots(int slots) {
+    MI355_REQUIRE(slots >= 0, "rank_set_round_slots: slots=%d must be >= 0 (0: the device's own count)", slots);
+    g_round_slots = slots;
+    return OK;
+}
+
+int mi355_rank_last_tiles(int* out, int n) {
+    if (!out || n < 1) return -1;
+    const int m = n < 5 ? n : 5;
+    for (int i = 0; i < m; ++i) out[i] = g_last_tiles[i];
+    return m;
+}
 
 size_t mi355_roc_pairs_workspace_bytes(int64_t Q, int64_t G, int dim) {
     if (Q < 1 || G < 1 || dim < 1) return 0;

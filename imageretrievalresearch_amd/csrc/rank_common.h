@@ -733,6 +733,10 @@ i64 query_block(i64 Q, i64 G, int k);
 int kernel_slots(const void* fn, size_t lds, int* cache, int* slots_out);
 // Column tiles of a GEMM's main launch of whole rounds (the rest go to a tail launch of 64-row tiles).
 int whole_round_tiles(int ntx, int ny, int slots);
+// The slots a GEMM call is cut by: the device's own count, or the calling thread's test override (mi355_rank_set_round_slots)
+int round_slots(int device_slots);
+// The cut of the calling thread's last GEMM call (mi355_rank_last_tiles)
+void set_last_tiles(int slots, int ny, int main_tiles, int tail_tiles, int tail_ny);
 
 // ---- host side of the tiled cosine GEMMs: exact fp32, split bf16 (rank.hip: F32Gemm, SplitGemm, PreparedGemm) and fp16
 // (rank_f16.hip: F16Gemm).  A family F supplies only what differs between them:
@@ -764,19 +768,21 @@ struct TileArgs {
 // column tiles as a second launch of 64-row tiles (same column tiles, same k order: every score is bit-identical), which
 // halves the tiles' length and doubles their number.
 template <class F, int MT, class Epi>
-int launch_tiles(const TileArgs& a, const Epi& epi, hipStream_t st, int x0 = 0) {
+int launch_tiles(const TileArgs& a, const Epi& epi, hipStream_t st, int x0 = 0, bool tail = false) {
     constexpr size_t lds = Epi::template lds_bytes<F::template stage_bytes<MT>()>();
     static int cache[MI355_MAX_DEVICES] = {0};   // per instantiation: hipFuncSetAttribute once per device
     int slots = 0;
     if (int e = kernel_slots((const void*)F::template kernel<MT, Epi>(), lds, cache, &slots)) return e;
     const int ntx = cdiv(a.G, RK_BN), ny = cdiv(a.Q, 64 * MT);
+    if (!tail) slots = round_slots(slots);
     const int x1 = MT == 2 ? whole_round_tiles(ntx, ny, slots) : ntx;
+    if (!tail) set_last_tiles(slots, ny, x1, ntx - x1, x1 < ntx ? cdiv(a.Q, 64) : 0);
     if (x1 > x0) {
         F::template launch<MT, Epi>(dim3((unsigned)(x1 - x0) * (unsigned)ny), lds, st, a, epi, x0, ntx, x1 - x0, ny);
         MI355_LAUNCH_CHECK();
     }
     if constexpr (MT == 2) {
-        if (x1 < ntx) return launch_tiles<F, 1, Epi>(a, epi, st, x1);
+        if (x1 < ntx) return launch_tiles<F, 1, Epi>(a, epi, st, x1, true);
     }
     return OK;
 }

@@ -139,6 +139,22 @@ enum {
     MI355_RANK_PATH_BITONIC = 0x200
 };
 int mi355_rank_last_path(void);
+/* Developer entries (tests): where a tiled cosine GEMM call is cut into its two launches.  A call over ntx = ceil(G / 128)
+ * column tiles and ny = ceil(Q / 128) tiles of 128 queries (Q > 64) with more tiles than `slots` resident workgroups, and a tile
+ * count that is no multiple of slots, runs column tiles [0, x1) as 128-query tiles and [x1, ntx) as a second launch of
+ * ceil(Q / 64) tiles of 64 queries each; x1 = mi355_rank_round_split(ntx, ny, slots) (host only, no HIP call; ntx >= 0, ny >= 1,
+ * slots >= 1, else -1), and x1 == ntx is a single launch.
+ * mi355_rank_set_round_slots(slots > 0): the calling thread's searches cut their GEMM calls as if the device had that many
+ * slots; 0 restores the device's own count (CUs x resident workgroups of the kernel); negative: an error.  Only the cut moves:
+ * the kernels, their LDS and the occupancy query are the same, and by the promise above (a score depends on its two rows only)
+ * no result of any entry depends on it.  For tests of the seam between the two launches; it costs speed.
+ * mi355_rank_last_tiles(out, n): the cut of the calling thread's last tiled GEMM call, out[0 .. min(n, 5)) = {slots used, query
+ * tiles of the main launch, its column tiles, column tiles of the tail launch (0: one launch), query tiles of the tail launch (0
+ * without a tail)}; a search of several query blocks reports its last block.  Returns the number of values written, or a negative
+ * error (out NULL, n < 1).  All zero before the thread's first such call. */
+int mi355_rank_round_split(int ntx, int ny, int slots);
+int mi355_rank_set_round_slots(int slots);
+int mi355_rank_last_tiles(int* out, int n);
 
 /* Verification ROC (utils/roc_curve_from_scratch.py): genuine / impostor pairs counted per threshold, without a score slab.
  * thresholds: HOST float64 [T], 1 <= T <= MI355_ROC_MAX_THRESHOLDS, finite, ascending (equal neighbours allowed); checked

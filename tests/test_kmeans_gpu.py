@@ -71,8 +71,9 @@ def _ref_from_scores(s64):
     return a, best, best - t.max(axis=1)
 
 
-# (N, K, D): the 128-column tile edge and a ragged last tile; the 64- and 128-query tile edges and the two-launch tail;
-# dim % 4, k-step tails and the workload's width
+# (N, K, D): the 128-column tile edge and a ragged last tile; the 64- and 128-query tile edges (K = 300 is three 128-query
+# tiles, 33 x 3 tiles in ONE launch: the two-launch tail needs more tiles than resident workgroups and is reached with forced
+# slots in tests/test_rank_tiles_gpu.py); dim % 4, k-step tails and the workload's width
 SHAPES = [(1, 1, 1), (127, 2, 7), (128, 63, 64), (129, 64, 70), (4099, 65, 64), (129, 129, 7), (4099, 300, 70),
           (127, 300, 1536), (1, 300, 64), (4099, 7, 1536), (128, 1, 70), (129, 2, 1)]
 
