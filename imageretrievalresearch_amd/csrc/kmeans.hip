@@ -239,6 +239,25 @@ static int members(const int64_t* assign, i64 N, i64 K, int64_t* offsets, int64_
     return OK;
 }
 
+// mi355_cluster_members for a caller inside the library that must not wait for the host (the IVF scan, ivf.hip): the same
+// three kernels, and the range flag stays on the device (*flag, zeroed here, 1 after a value outside [0, K)) for the caller
+// to read with its own.  A value out of range belongs to no cluster: it is counted nowhere and appears nowhere in order.
+size_t members_ws_bytes(i64 N, i64 K) { return kmeans_carve(nullptr, N, K, 0).total; }
+int members_async(const int64_t* assign, i64 N, i64 K, int64_t* offsets, int64_t* order, void* workspace, hipStream_t st,
+                  const unsigned** flag) {
+    const KmeansWs w = kmeans_carve(workspace, N, K, 0);
+    RoctxRange range("kmeans/members");
+    MI355_CHECK_HIP(hipMemsetAsync(w.flag, 0, sizeof(unsigned), st));
+    hipLaunchKernelGGL(k_member_counts, dim3((unsigned)K), dim3(256), 0, st, (const i64*)assign, N, K, w.counts, w.flag);
+    MI355_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_member_offsets, dim3(1), dim3(1024), 0, st, (const i64*)w.counts, K, (i64*)offsets, w.segoff);
+    MI355_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_member_order, dim3((unsigned)K), dim3(256), 0, st, (const i64*)assign, N, (const i64*)offsets, (i64*)order);
+    MI355_LAUNCH_CHECK();
+    *flag = w.flag;
+    return OK;
+}
+
 static int centroid_update(const void* rows, bool f16rows, i64 ld, i64 N, int dim, const int64_t* assign, i64 K, const float* previous,
                            float eps, float* centroids, int64_t* counts, int64_t* offsets, int64_t* order, void* workspace,
                            size_t workspace_bytes, void* stream, const char* who) {

@@ -924,4 +924,11 @@ size_t nearest_ws_bytes(i64 K, i64 G, int dim, size_t (*planes_bytes)(i64, int),
 int nearest_centroid(const float* centroids, i64 K, const GalleryRows& g, i64 G, int dim, float eps, i64 query_block,
                      int64_t* assign, float* score, void* workspace, size_t workspace_bytes, void* stream, const char* who);
 
+// ---- mi355_cluster_members without its host sync (kmeans.hip), for the IVF scan (ivf.hip): offsets [K + 1] and order [N] of
+// assign [N]; *flag: a device word that is 1 after a value outside [0, K) (such a value is in no cluster).  workspace:
+// members_ws_bytes(N, K) bytes.  N >= 1, 1 <= K < 2^24.
+size_t members_ws_bytes(i64 N, i64 K);
+int members_async(const int64_t* assign, i64 N, i64 K, int64_t* offsets, int64_t* order, void* workspace, hipStream_t st,
+                  const unsigned** flag);
+
 }  // namespace mi355

@@ -1,0 +1,176 @@
+"""Inverted-file (IVF) search over a resident ``Gallery``: the centroids of a spherical k-means are the coarse quantiser, the
+members of every cluster are its lists, and a query is scored against the rows of the ``nprobe`` lists nearest to it only.
+
+* ``IVFIndex(gallery, centroids, assignments)`` .. the lists of given assignments (CSR from ``cluster_members``)
+* ``IVFIndex.build(gallery, nlist)`` ............. ``gallery.kmeans(nlist)``, then the constructor (``Gallery.ivf`` caches it)
+* ``index.probe(queries, nprobe)`` ............... the nearest lists: the fp32 top-k of the queries against the centroids
+* ``index.search(queries, k, nprobe)`` ........... scan of the probed lists (``mi355_ivf_scan``), ``merge_topk``, ``clear_pads``
+* ``index.recall(queries, k, nprobe)`` ........... the share of the exhaustive top-k it returns: how to choose ``nprobe``
+* ``index.update()`` ............................. after ``gallery.add``: the new rows go to their nearest list
+
+The rows are scanned where they lie in the gallery (fp32 or fp16), through the lists' ``order``; the index holds no copy of
+them.  Out of scope: ``ShardedGallery``, product quantisation, a list-ordered copy of the rows.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import cluster as _cl
+from . import rank as _rank
+from ._lib import MI355Error, check, lib, stream_ptr
+
+_MAX_K = 1024                       # largest k of any search, and the most lists a query probes
+_SLAB_BYTES = 256 << 20             # the candidate slab of one query block (12 B per slot) stays under this
+
+
+def _is_int(x) -> bool:
+    return isinstance(x, (int, np.integer)) and not isinstance(x, bool)
+
+
+class IVFIndex:
+    """The lists of a ``Gallery``: ``centroids`` (nlist, D) fp32, ``offsets`` (nlist + 1,) / ``order`` (rows,) int64 (the rows
+    of list l are ``order[offsets[l]:offsets[l + 1]]``, ascending), ``counts`` (nlist,) int64, and a reference to the gallery."""
+
+    def __init__(self, gallery, centroids: torch.Tensor, assignments: torch.Tensor):
+        if not isinstance(gallery, _rank.Gallery):
+            raise MI355Error(f"an IVF index is built over a Gallery, got {type(gallery).__name__}")
+        if gallery.rows < 1:
+            raise MI355Error("an IVF index needs a gallery with at least one row")
+        self.gallery = gallery
+        self.centroids = _cl._centroids_of(centroids, gallery._resident())
+        self.nlist = int(self.centroids.shape[0])
+        if self.nlist >= 1 << 24:
+            raise MI355Error(f"nlist={self.nlist} must be below 2^24")
+        self._set_lists(_rank._int64_on(assignments, "assignments", gallery.rows, gallery.device))
+
+    def _set_lists(self, assignments: torch.Tensor) -> None:
+        self.assignments = assignments
+        self.offsets, self.order = _cl.cluster_members(assignments, self.nlist)
+        self.counts = self.offsets[1:] - self.offsets[:-1]
+        host = self.counts.cpu().numpy()                                    # the one read of the lists' lengths
+        self._longest = np.concatenate([[0], np.cumsum(np.sort(host)[::-1])])   # [n] = the rows of the n longest lists
+        self.rows = int(assignments.shape[0])
+
+    @classmethod
+    def build(cls, gallery, nlist: int, *, iters: int = 10, seed: int = 0, init: torch.Tensor | None = None) -> "IVFIndex":
+        """``gallery.kmeans(nlist, iters=, seed=, init=)``, then the lists of its assignments."""
+        if not isinstance(gallery, _rank.Gallery):
+            raise MI355Error(f"an IVF index is built over a Gallery, got {type(gallery).__name__}")
+        r = gallery.kmeans(nlist, iters=iters, seed=seed, init=init)
+        return cls(gallery, r.centroids, r.assignments)
+
+    @property
+    def nbytes(self) -> int:
+        """The index's size in bytes: centroids, assignments, offsets, order and counts (the rows belong to the gallery)."""
+        return sum(t.numel() * t.element_size() for t in (self.centroids, self.assignments, self.offsets, self.order, self.counts))
+
+    @property
+    def stale(self) -> bool:
+        """Rows were added to the gallery since the lists were made (``update()`` brings them in)."""
+        return self.rows != self.gallery.rows
+
+    def update(self) -> "IVFIndex":
+        """After ``gallery.add``: ``assign_clusters`` of the new rows only against the unchanged centroids, then the CSR again."""
+        g = self.gallery
+        if g.rows < self.rows:
+            raise MI355Error(f"the gallery has {g.rows} rows but the index lists {self.rows}")
+        if g.rows > self.rows:
+            new = _rank._Rows(g._buf[self.rows: g.rows], g.rows - self.rows, g.dim, True)
+            a, _ = _cl.assign_clusters(new, self.centroids, eps=g.eps)
+            self._set_lists(torch.cat([self.assignments, a]))
+        return self
+
+    def _fresh(self) -> None:
+        if self.stale:
+            raise MI355Error(f"the IVF index is stale: it lists {self.rows} rows but the gallery holds {self.gallery.rows} "
+                             "(call update())")
+
+    def _check_nprobe(self, nprobe) -> int:
+        top = min(self.nlist, _MAX_K)
+        if not _is_int(nprobe) or not 1 <= nprobe <= top:
+            raise MI355Error(f"nprobe={nprobe!r} outside [1, {top}] (min(nlist, {_MAX_K}))")
+        return int(nprobe)
+
+    def probe(self, queries: torch.Tensor, nprobe: int) -> torch.Tensor:
+        """(Q, nprobe) int64: the lists nearest to every query, nearest first - exactly the indices of
+        ``cosine_topk(queries, centroids, nprobe)``.  ``1 <= nprobe <= min(nlist, 1024)``."""
+        nprobe = self._check_nprobe(nprobe)
+        return _rank.cosine_topk(queries, self.centroids, nprobe, self.gallery.eps)[1]
+
+    def _block(self, Q: int, nprobe: int, cap: int, block) -> int:
+        if block is not None:
+            if not _is_int(block) or block < 1:
+                raise MI355Error(f"block must be a positive integer, got {block!r}")
+            return int(block)
+        return max(1, min(_SLAB_BYTES // (12 * cap), ((1 << 31) - 1) // nprobe, 65535 * 16))
+
+    def _scan(self, q, probes, cap, idx_offset, filt):
+        """The candidate slab (values (n, cap) fp32, indices (n, cap) int64) of the queries ``q`` (n, D) probing ``probes``."""
+        g = self.gallery
+        n, nprobe, dev = q.shape[0], probes.shape[1], q.device
+        cand_val = torch.empty((n, cap), dtype=torch.float32, device=dev)
+        cand_idx = torch.empty((n, cap), dtype=torch.int64, device=dev)
+        L = lib()
+        ws = _rank._ws.get(dev, L.mi355_ivf_scan_workspace_bytes(n, nprobe, self.nlist, g.dim, cap))
+        with torch.cuda.device(dev):
+            check(L.mi355_ivf_scan(q.data_ptr(), n, g.dim, g.eps, g._buf.data_ptr(), _rank._DTYPES[g.dtype], g._ld, g.rows,
+                                   self.offsets.data_ptr(), self.order.data_ptr(), self.nlist, probes.data_ptr(), nprobe, cap,
+                                   int(idx_offset), None if filt is None else filt[0], cand_val.data_ptr(),
+                                   cand_idx.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr(dev)))
+        return cand_val, cand_idx
+
+    def search(self, queries: torch.Tensor, k: int, nprobe: int | None = None, *, probes: torch.Tensor | None = None,
+               query_labels: torch.Tensor | None = None, label_filter: str | None = None,
+               exclude: torch.Tensor | None = None, idx_offset: int = 0, block: int | None = None):
+        """(values (Q, k) fp32, indices (Q, k) int64): the top-k of the rows of every query's probed lists, ordered as
+        ``Gallery.search`` orders them (descending, ties to the lower index).  Exactly one of ``nprobe`` (the lists of
+        ``probe(queries, nprobe)``) and ``probes`` ((Q, n) int64 list ids, distinct within a row) is given.  A score is
+        ``qn . row`` in fp32 (fp16 rows widened exactly) and depends on its query and its row only: not on the other queries,
+        ``nprobe`` or ``block``.  Filters and ``idx_offset`` as in ``Gallery.search``; with fewer than k eligible probed rows
+        the remaining slots are (-inf, -1).  ``1 <= k <= min(1024, rows)``.  The queries go through ``block`` at a time
+        (default: what keeps the candidate slab under 256 MB); the result does not depend on it."""
+        self._fresh()
+        top = min(_MAX_K, self.rows)
+        if not _is_int(k) or not 1 <= k <= top:
+            raise MI355Error(f"selected index k out of range: k={k!r} outside [1, {top}] (min({_MAX_K}, rows))")
+        if (nprobe is None) == (probes is None):
+            raise MI355Error("give exactly one of nprobe and probes")
+        if nprobe is not None:
+            nprobe = self._check_nprobe(nprobe)
+        g = self.gallery
+        q = _rank._f32c(queries, "queries")
+        _rank._check_qg(q, g._resident())
+        Q = q.shape[0]
+        if probes is None:
+            probes = self.probe(q, nprobe) if Q else torch.empty((0, nprobe), dtype=torch.int64, device=q.device)
+        else:
+            if not torch.is_tensor(probes) or probes.dim() != 2 or probes.shape[0] != Q:
+                raise MI355Error(f"probes must be a (Q={Q}, nprobe) tensor")
+            nprobe = self._check_nprobe(int(probes.shape[1]))
+            probes = _rank._int64_on(probes.reshape(-1), "probes", Q * nprobe, q.device).view(Q, nprobe)
+        gl = None if label_filter is None else g._labels_for(f'label_filter="{label_filter}"')
+        filtered = _rank._rank_filter(Q, g.rows, q.device, query_labels, gl, label_filter, exclude) is not None
+        cap = max(int(self._longest[nprobe]), int(k))
+        blk = self._block(Q, nprobe, cap, block)
+        vals = torch.empty((Q, k), dtype=torch.float32, device=q.device)
+        idx = torch.empty((Q, k), dtype=torch.int64, device=q.device)
+        for q0 in range(0, Q, blk):
+            q1 = min(Q, q0 + blk)
+            filt = None
+            if filtered:
+                filt = _rank._rank_filter(q1 - q0, g.rows, q.device, None if query_labels is None else query_labels[q0:q1], gl,
+                                          label_filter, None if exclude is None else exclude[q0:q1])
+            cand_val, cand_idx = self._scan(q[q0:q1], probes[q0:q1].contiguous(), cap, idx_offset, filt)
+            v, i = _rank.merge_topk(cand_val, cand_idx, int(k))
+            _rank.clear_pads(v, i, int(idx_offset), int(idx_offset) + g.rows)
+            vals[q0:q1], idx[q0:q1] = v, i
+        return vals, idx
+
+    def recall(self, queries: torch.Tensor, k: int, nprobe: int):
+        """(mean, per_query (Q,) float64): the share of ``gallery.search(queries, k)``'s indices that
+        ``search(queries, k, nprobe)`` returns."""
+        got = self.search(queries, k, nprobe)[1]
+        want = self.gallery.search(queries, k)[1]
+        per = (got.unsqueeze(2) == want.unsqueeze(1)).any(dim=1).sum(dim=1).double() / float(k)
+        return (float(per.mean()) if per.numel() else 1.0), per

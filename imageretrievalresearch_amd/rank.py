@@ -627,6 +627,7 @@ class Gallery:
         self.labels = None
         self._prepared, self._prepared_rows = None, 0
         self._knn, self._rerank = {}, {}                         # per k1 / (k1, k2); dropped by add
+        self._ivf = {}                                           # per (nlist, iters, seed); dropped by add
 
     def _reserve(self, n):
         if n > self._buf.shape[0]:
@@ -653,6 +654,7 @@ class Gallery:
             self.labels = lab if self.labels is None else torch.cat([self.labels, lab])
         self.rows += n
         self._knn, self._rerank = {}, {}
+        self._ivf = {}
         return self
 
     @property
@@ -824,6 +826,17 @@ class Gallery:
         there (``iters``, ``seed``, ``init``, ``block``)."""
         from . import cluster as _cl
         return _cl.spherical_kmeans(self, n_clusters, eps=self.eps, **kw)
+
+    def ivf(self, nlist: int, **kw):
+        """The ``IVFIndex`` of the resident rows with ``nlist`` lists: ``IVFIndex.build(self, nlist, **kw)`` (``iters``,
+        ``seed``, ``init``).  Cached per (nlist, iters, seed) until ``add``; an index built from a given ``init`` is not cached."""
+        from . import ivf as _ivf
+        if kw.get("init") is not None:
+            return _ivf.IVFIndex.build(self, nlist, **kw)
+        key = (nlist, kw.get("iters", 10), kw.get("seed", 0))
+        if key not in self._ivf:
+            self._ivf[key] = _ivf.IVFIndex.build(self, nlist, **kw)
+        return self._ivf[key]
 
     def clustering_metrics(self, n_clusters: int | None = None, **kw) -> dict:
         """Clusters the resident rows (``kmeans``; ``n_clusters`` defaults to the number of distinct labels given to ``add``)

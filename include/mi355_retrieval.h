@@ -474,6 +474,40 @@ size_t mi355_contingency_workspace_bytes(int64_t N, int64_t Ka, int64_t Kb);
 int mi355_contingency(const int64_t* a, const int64_t* b, int64_t N, int64_t Ka, int64_t Kb, int64_t* table, void* workspace,
                       size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ inverted-file (IVF) search
+ * The scan of the lists a query probes.  The gallery's rows stay where they lie and are read through the lists' CSR
+ * (offsets [nlist + 1], order [G], device int64: the rows of list l are order[offsets[l] .. offsets[l + 1]), as
+ * mi355_cluster_members writes them); no list-ordered copy is made.
+ *   queries [Q][dim] device fp32, raw: normalised by the call with the bits of mi355_l2_normalize_rows(queries, eps);
+ *   rows: MI355_DTYPE_F32 normalised rows, ld floats apart (ld >= dim), or MI355_DTYPE_F16 rows in the mi355_gallery_to_f16
+ *     layout (16-byte aligned, ld a multiple of 8 halves, ld >= dim, the padding zero); G rows;
+ *   probes [Q][nprobe] device int64 list ids, those of one query distinct; 1 <= nprobe <= nlist;
+ *   cand_val [Q][cap] device fp32, cand_idx [Q][cap] device int64: cap candidate slots per query;
+ *   filter: NULL, or the eligibility rule of the filtered searches (exclude compared with row + idx_offset).
+ * For query q the rows of probes[q][0], then probes[q][1], ... fill slots 0 .. n_q - 1 in list order, each with
+ * (qn . row, order[r] + idx_offset); the slot of an ineligible row, and every slot n_q .. cap - 1, holds (-inf, 2^62), the
+ * "no candidate" of mi355_merge_topk, which selects the k best of the slab.  Every slot is written once, by one wave; there
+ * are no atomics.
+ * Arithmetic: one wave per row, fp32 accumulation, fp16 rows widened exactly.  Lane i takes the elements [4u, 4u + 4) (fp16
+ * rows: [8u, 8u + 8)) of the units u = i, i + 64, ... in ascending order, one fused multiply-add each, then the 64 partial
+ * sums go through the library's wave reduction: the order depends on dim alone.  A score therefore depends on its query row
+ * and its gallery row only - not on Q, nprobe, the list, how queries are grouped, or the query block of the caller.
+ * Work: the (query, list) pairs are grouped by list (the kernels of mi355_cluster_members over the flattened probes), each
+ * list's pairs are cut into groups of up to 4 queries held in LDS (fewer when 4 rows of dim floats pass 64 KB; one must fit)
+ * and its rows into chunks of 64; a small kernel writes the (list, group, chunk) items and their count to device memory and
+ * the scan loops over them on a fixed grid sized by the device's CUs.  Slot bases are running sums taken on the device.
+ * Nothing is read back between these steps.
+ * Errors found on the device are reported after the call from one flag word (one host sync at the end, as in
+ * mi355_cluster_members): n_q > cap for some query; a list id outside [0, nlist), an order entry outside [0, G) or offsets
+ * that do not ascend within [0, G].  Such an entry is skipped (a bad order entry's slot holds "no candidate") and nothing
+ * is read or written out of bounds because of it.  Q = 0 does nothing.  Q * nprobe < 2^31, Q * cap < 2^40, nlist < 2^24.
+ * Every argument is checked before any HIP call. */
+size_t mi355_ivf_scan_workspace_bytes(int64_t Q, int nprobe, int64_t nlist, int dim, int64_t cap);
+int mi355_ivf_scan(const float* queries, int64_t Q, int dim, float eps, const void* rows, int rows_dtype, int64_t ld, int64_t G,
+                   const int64_t* offsets, const int64_t* order, int64_t nlist, const int64_t* probes, int nprobe, int64_t cap,
+                   int64_t idx_offset, const mi355_rank_filter* filter, float* cand_val, int64_t* cand_idx, void* workspace,
+                   size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ backbone models
  * Replaces timm.create_model(name, num_classes=N) and the methods the reference calls on it
  * (inference/inference.py:102,110,133,146,199-201 ; train/train.py:194-195,288,396 ;
