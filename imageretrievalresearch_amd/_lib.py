@@ -37,6 +37,14 @@ class DwconvExArgs(C.Structure):
                 ("gate", vp), ("squeeze", vp)]
 
 
+class MbconvFrontArgs(C.Structure):
+    """mi355_mbconv_front_args (include/mi355_retrieval.h), the operand block of the developer entry mi355_mbconv_front_ex."""
+    _fields_ = [("X", vp), ("We", vp), ("be", vp), ("Wd", vp), ("bd", vp), ("D", vp), ("pool", vp),
+                ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("Cin", C.c_int), ("mid", C.c_int), ("k", C.c_int),
+                ("stride", C.c_int), ("act_e", C.c_int), ("act_d", C.c_int),
+                ("kernel", C.c_int), ("band_rows", C.c_int), ("sweep_variant", C.c_int), ("sweep_csplit", C.c_int)]
+
+
 class StemExArgs(C.Structure):
     """mi355_stem_ex_args (include/mi355_retrieval.h), the operand block of the developer entry mi355_stem_ex."""
     _fields_ = [("x", vp), ("images", vp), ("images_bytes", C.c_int64), ("desc_host", vp), ("desc_dev", vp),
@@ -191,6 +199,7 @@ PROTOTYPES = {
     "mi355_gemm_bf16": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "mi355_gemm_bf16_ex": (C.c_int, [vp, C.POINTER(C.c_int), vp]),
     "mi355_dwconv_se_ex": (C.c_int, [vp, C.POINTER(C.c_int), vp]),
+    "mi355_mbconv_front_ex": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), vp]),
     "mi355_stem_ex": (C.c_int, [vp, C.POINTER(C.c_int), vp]),
     "mi355_head_gap_ex": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.POINTER(C.c_int), vp]),

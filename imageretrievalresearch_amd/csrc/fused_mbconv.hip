@@ -15,6 +15,7 @@
 //   phase 2  thread = 8 channels x PX output pixels of one row, taps read from the LDS slab (zero padding by
 //            bounds checks), result streamed to HBM as 16-byte NHWC vectors; per-channel sums reduced through
 //            LDS in thread order.
+#include "../../include/mi355_retrieval.h"
 #include "ops.h"
 
 namespace mi355 {
@@ -284,7 +285,7 @@ _Pragma("unroll")
 // =====================================================================================
 template <int KS, int S, int KST, int PX, int MC>
 __global__ __launch_bounds__(FL_THREADS) void k_fused_band(const FusedArgs a) {
-    // MC = channels per slab (48 / 64 / 96, picked to divide the expanded width: a 64-wide slab wasted a third of both
+    // MC = channels per slab (48 / 64, picked to divide the expanded width: a 64-wide slab wasted a third of both
     // phases on mid = 144); NACT = the largest multiple of the slab's channel groups <= 512, so that a thread keeps ONE
     // channel group over all its items (its squeeze partial sums stay per channel)
     constexpr int NT = MC / 16;
@@ -510,7 +511,7 @@ _Pragma("unroll")
     }
 }
 
-static int band_slab(int mid) { return mid % 64 == 0 ? 64 : (mid % 48 == 0 ? 48 : (mid % 96 == 0 ? 96 : 64)); }
+static int band_slab(int mid) { return mid % 64 == 0 ? 64 : (mid % 48 == 0 ? 48 : 64); }
 
 static size_t band_lds_bytes(int W, int Kp, int k, int stride, int TH, int px, int mc) {
     const int pad = k / 2, IH = (TH - 1) * stride + k;
@@ -533,7 +534,7 @@ int fused_band_rows(int H, int W, int Cin, int mid, int k, int stride) {
 }
 
 template <int KS, int S, int KST, int PX, int MC>
-static int launch_fb(const FusedArgs& a, int B, hipStream_t st) {
+static int launch_fb(const FusedArgs& a, int B, hipStream_t st, int* path) {
     const size_t lds = band_lds_bytes(a.W, a.Kp, KS, S, a.TH, PX, MC);
     static bool attr_done[MI355_MAX_DEVICES] = {false};   // per device
     if (first_time_on_this_device(attr_done)) {
@@ -542,30 +543,30 @@ static int launch_fb(const FusedArgs& a, int B, hipStream_t st) {
     }
     hipLaunchKernelGGL((k_fused_band<KS, S, KST, PX, MC>), dim3(cdiv(a.Ho, a.TH), B), dim3(FL_THREADS), lds, st, a);
     MI355_LAUNCH_CHECK();
+    if (path) *path = MI355_FRONT_PATH_BAND(KS, S, KST, PX, MC, a.TH);
     return OK;
 }
 
 template <int KS, int S, int KST, int PX>
-static int launch_fb_mc(const FusedArgs& a, int B, hipStream_t st) {
-    const int mc = band_slab(a.mid);
-    if (mc == 48) return launch_fb<KS, S, KST, PX, 48>(a, B, st);
-    if (mc == 96) return launch_fb<KS, S, KST, PX, 96>(a, B, st);
-    return launch_fb<KS, S, KST, PX, 64>(a, B, st);
+static int launch_fb_mc(const FusedArgs& a, int B, hipStream_t st, int* path) {
+    if (band_slab(a.mid) == 48) return launch_fb<KS, S, KST, PX, 48>(a, B, st, path);
+    return launch_fb<KS, S, KST, PX, 64>(a, B, st, path);
 }
 
 template <int KS, int S>
-static int launch_fb_ks(const FusedArgs& a, int B, hipStream_t st) {
+static int launch_fb_ks(const FusedArgs& a, int B, hipStream_t st, int* path) {
     const bool px7 = (a.Wo % 7 == 0);
-    if (a.Kp == 32) return px7 ? launch_fb_mc<KS, S, 1, 7>(a, B, st) : launch_fb_mc<KS, S, 1, 4>(a, B, st);
-    return px7 ? launch_fb_mc<KS, S, 2, 7>(a, B, st) : launch_fb_mc<KS, S, 2, 4>(a, B, st);
+    if (a.Kp == 32) return px7 ? launch_fb_mc<KS, S, 1, 7>(a, B, st, path) : launch_fb_mc<KS, S, 1, 4>(a, B, st, path);
+    return px7 ? launch_fb_mc<KS, S, 2, 7>(a, B, st, path) : launch_fb_mc<KS, S, 2, 4>(a, B, st, path);
 }
 
-int launch_fused_band(const FusedArgs& a, int B, int k, int stride, hipStream_t st) {
+int launch_fused_band(const FusedArgs& a, int B, int k, int stride, hipStream_t st, int* path) {
+    if (path) *path = 0;
     MI355_REQUIRE(a.TH >= 1 && (a.Kp == 32 || a.Kp == 64), "fused_band: unsupported shape");
-    if (k == 3 && stride == 1) return launch_fb_ks<3, 1>(a, B, st);
-    if (k == 3 && stride == 2) return launch_fb_ks<3, 2>(a, B, st);
-    if (k == 5 && stride == 1) return launch_fb_ks<5, 1>(a, B, st);
-    return launch_fb_ks<5, 2>(a, B, st);
+    if (k == 3 && stride == 1) return launch_fb_ks<3, 1>(a, B, st, path);
+    if (k == 3 && stride == 2) return launch_fb_ks<3, 2>(a, B, st, path);
+    if (k == 5 && stride == 1) return launch_fb_ks<5, 1>(a, B, st, path);
+    return launch_fb_ks<5, 2>(a, B, st, path);
 }
 
 static size_t fused_lds_bytes(int H, int W, int Kp, int MC, int k, int stride) {
@@ -586,7 +587,7 @@ bool fused_late_supported(int H, int W, int Cin, int mid, int k, int stride) {
 }
 
 template <int KS, int S, int NIW, int PX>
-static int launch_fl(const FusedArgs& a, int B, hipStream_t st) {
+static int launch_fl(const FusedArgs& a, int B, hipStream_t st, int* path) {
     constexpr int MC = 128 * NIW;
     const size_t lds = fused_lds_bytes(a.H, a.W, a.Kp, MC, KS, S);
     static bool attr_done[MI355_MAX_DEVICES] = {false};   // per device
@@ -600,24 +601,26 @@ static int launch_fl(const FusedArgs& a, int B, hipStream_t st) {
     if (G > nchunks) G = nchunks;
     hipLaunchKernelGGL((k_fused_late<KS, S, NIW, PX>), dim3(G, B), dim3(FL_THREADS), lds, st, a);
     MI355_LAUNCH_CHECK();
+    if (path) *path = MI355_FRONT_PATH_LATE(KS, S, NIW, PX);
     return OK;
 }
 
 template <int KS, int S>
-static int launch_fl_ks(const FusedArgs& a, int B, hipStream_t st) {
+static int launch_fl_ks(const FusedArgs& a, int B, hipStream_t st, int* path) {
     const int P = a.H * a.W;
     const bool px7 = (a.Wo % 7 == 0);
-    if (P <= 64) return px7 ? launch_fl<KS, S, 4, 7>(a, B, st) : launch_fl<KS, S, 4, 4>(a, B, st);
-    if (P <= 112) return px7 ? launch_fl<KS, S, 2, 7>(a, B, st) : launch_fl<KS, S, 2, 4>(a, B, st);
-    return px7 ? launch_fl<KS, S, 1, 7>(a, B, st) : launch_fl<KS, S, 1, 4>(a, B, st);
+    if (P <= 64) return px7 ? launch_fl<KS, S, 4, 7>(a, B, st, path) : launch_fl<KS, S, 4, 4>(a, B, st, path);
+    if (P <= 112) return px7 ? launch_fl<KS, S, 2, 7>(a, B, st, path) : launch_fl<KS, S, 2, 4>(a, B, st, path);
+    return px7 ? launch_fl<KS, S, 1, 7>(a, B, st, path) : launch_fl<KS, S, 1, 4>(a, B, st, path);
 }
 
-int launch_fused_late(const FusedArgs& a, int B, int k, int stride, hipStream_t st) {
+int launch_fused_late(const FusedArgs& a, int B, int k, int stride, hipStream_t st, int* path) {
+    if (path) *path = 0;
     MI355_REQUIRE(fused_late_supported(a.H, a.W, a.Cin, a.mid, k, stride), "fused_late: unsupported shape");
-    if (k == 3 && stride == 1) return launch_fl_ks<3, 1>(a, B, st);
-    if (k == 3 && stride == 2) return launch_fl_ks<3, 2>(a, B, st);
-    if (k == 5 && stride == 1) return launch_fl_ks<5, 1>(a, B, st);
-    return launch_fl_ks<5, 2>(a, B, st);
+    if (k == 3 && stride == 1) return launch_fl_ks<3, 1>(a, B, st, path);
+    if (k == 3 && stride == 2) return launch_fl_ks<3, 2>(a, B, st, path);
+    if (k == 5 && stride == 1) return launch_fl_ks<5, 1>(a, B, st, path);
+    return launch_fl_ks<5, 2>(a, B, st, path);
 }
 
 }  // namespace mi355

@@ -192,6 +192,25 @@ static Dims op_shape(const Op& op, Dims in, int nb, int B_full, Need&& need) {
     return o;
 }
 
+// The shape-only part of fused_pair_how: which fused front-half kernel takes an expand (cin -> mid, act_e) + depthwise (k, stride,
+// act_d) pair on an h x w map under the options fuse_sweep / fuse_band (MI355_PLAN_FUSED_LATE / _SWEEP / _BAND), or
+// MI355_PLAN_OP.  The launch plan and the developer entry mi355_mbconv_front_ex both decide here.
+static int fused_pair_shape_how(int fuse_sweep, int fuse_band, int h, int w, int cin, int mid, int k, int stride, int act_e,
+                                int act_d, int* band_rows) {
+    if (fused_late_supported(h, w, cin, mid, k, stride)) return MI355_PLAN_FUSED_LATE;   // whole-image tile
+    // row-sweep kernel (MFMA depthwise, complete squeeze sums): the early-stage shape classes of sweep_mbconv.hip
+    if (fuse_sweep && sweep_mbconv_supported(h, w, cin, mid, k, stride, act_e, act_d)) return MI355_PLAN_SWEEP;
+    // Band variant, measured per layer on EfficientNet-B3a B=256 (fused vs expand + depthwise): 3x3 s1 C192 @56x56 307 vs
+    // 339 us (wins); 3x3 s2 C144 @112x112 780 vs 619, 5x5 s2 C192 @56x56 465 vs 276, 5x5 s1 C288 @28x28 247 vs 172 (lose:
+    // short bands recompute too much halo and leave most threads idle in the depthwise phase).
+    // RexNet-200: 3x3 s1 C324 @56x56 (7-row bands) 582 vs 661 us and 3x3 s2 C192 @112x112 714 vs 771 us (win: its 32->192
+    // expand alone costs 0.5 ms).
+    const int rows = fuse_band ? fused_band_rows(h, w, cin, mid, k, stride) : 0;
+    const bool measured_win = k == 3 && ((stride == 1 && rows >= 7) || (stride == 2 && w >= 112 && mid >= 192));
+    if (rows > 0 && (fuse_band == 1 || measured_win)) { *band_rows = rows; return MI355_PLAN_BAND; }
+    return MI355_PLAN_OP;
+}
+
 // expand GEMM (-> SLOT_E) immediately followed by the depthwise conv that consumes it: which kernel runs the pair as one
 // launch (MI355_PLAN_FUSED_LATE / _SWEEP / _BAND), or MI355_PLAN_OP when the two run apart
 static int fused_pair_how(const mi355_model* m, size_t i, int h, int w, int* band_rows) {
@@ -200,18 +219,7 @@ static int fused_pair_how(const mi355_model* m, size_t i, int h, int w, int* ban
     const Op& d = m->def.ops[i + 1];
     if (g.kind != OP_GEMM || d.kind != OP_DW || g.out != SLOT_E || d.in != SLOT_E) return MI355_PLAN_OP;
     if (g.use_gate || g.res != SLOT_NONE || g.a_relu6 || !g.tap.empty()) return MI355_PLAN_OP;
-    if (fused_late_supported(h, w, g.cin, g.cout, d.k, d.stride)) return MI355_PLAN_FUSED_LATE;   // whole-image tile
-    // row-sweep kernel (MFMA depthwise, complete squeeze sums): the early-stage shape classes of sweep_mbconv.hip
-    if (m->fuse_sweep && sweep_mbconv_supported(h, w, g.cin, g.cout, d.k, d.stride, g.act, d.act)) return MI355_PLAN_SWEEP;
-    // Band variant, measured per layer on EfficientNet-B3a B=256 (fused vs expand + depthwise): 3x3 s1 C192 @56x56 307 vs
-    // 339 us (wins); 3x3 s2 C144 @112x112 780 vs 619, 5x5 s2 C192 @56x56 465 vs 276, 5x5 s1 C288 @28x28 247 vs 172 (lose:
-    // short bands recompute too much halo and leave most threads idle in the depthwise phase).
-    // RexNet-200: 3x3 s1 C324 @56x56 (7-row bands) 582 vs 661 us and 3x3 s2 C192 @112x112 714 vs 771 us (win: its 32->192
-    // expand alone costs 0.5 ms).
-    const int rows = m->fuse_band ? fused_band_rows(h, w, g.cin, g.cout, d.k, d.stride) : 0;
-    const bool measured_win = d.k == 3 && ((d.stride == 1 && rows >= 7) || (d.stride == 2 && w >= 112 && g.cout >= 192));
-    if (rows > 0 && (m->fuse_band == 1 || measured_win)) { *band_rows = rows; return MI355_PLAN_BAND; }
-    return MI355_PLAN_OP;
+    return fused_pair_shape_how(m->fuse_sweep, m->fuse_band, h, w, g.cin, g.cout, d.k, d.stride, g.act, d.act, band_rows);
 }
 
 // expand GEMM -> depthwise -> SE -> gated projection on a whole-image tile: one kernel (mbconv_block.hip)
@@ -1200,6 +1208,77 @@ int mi355_dwconv_se_ex(const mi355_dwconv_ex_args* x, int* path, void* stream) {
     MI355_CHECK_HIP(freed);
     if (path) *path = dw_path | se_path << 24;
     return OK;
+}
+
+int mi355_mbconv_front_ex(const mi355_mbconv_front_args* x, int* pool_nblk, int* path, void* stream) {
+    if (path) *path = 0;
+    if (pool_nblk) *pool_nblk = 0;
+    MI355_REQUIRE(x, "mbconv_front_ex: null argument block");
+    MI355_REQUIRE(x->X && x->We && x->be && x->Wd && x->bd && x->D, "mbconv_front_ex: null pointer");
+    MI355_REQUIRE(x->B >= 1 && x->B <= 65535 && x->H >= 1 && x->W >= 1 && x->H <= 16384 && x->W <= 16384 && x->Cin >= 8 && x->mid >= 8 &&
+                      x->Cin <= 32768 && x->mid <= 32768,
+                  "mbconv_front_ex: bad shape B=%d H=%d W=%d Cin=%d mid=%d", x->B, x->H, x->W, x->Cin, x->mid);
+    MI355_REQUIRE(x->Cin % 8 == 0 && x->mid % 8 == 0, "mbconv_front_ex: Cin=%d and mid=%d must be multiples of 8", x->Cin, x->mid);
+    MI355_REQUIRE((size_t)x->B * x->H * x->W * std::max(x->Cin, x->mid) < ((size_t)1 << 36), "mbconv_front_ex: tensor too large");
+    MI355_REQUIRE((x->k == 3 || x->k == 5) && (x->stride == 1 || x->stride == 2), "mbconv_front_ex: unsupported k=%d stride=%d", x->k,
+                  x->stride);
+    MI355_REQUIRE(x->act_e >= ACT_NONE && x->act_e <= ACT_SIGMOID && x->act_d >= ACT_NONE && x->act_d <= ACT_SIGMOID,
+                  "mbconv_front_ex: unknown activation %d / %d", x->act_e, x->act_d);
+    MI355_REQUIRE(x->kernel >= MI355_FRONT_KERNEL_AUTO && x->kernel <= MI355_FRONT_KERNEL_BAND, "mbconv_front_ex: unknown kernel %d",
+                  x->kernel);
+    MI355_REQUIRE(x->band_rows >= 0 && x->sweep_variant >= 0 && x->sweep_variant <= 4 && x->sweep_csplit >= 0 && x->sweep_csplit <= 4095,
+                  "mbconv_front_ex: band_rows=%d, sweep_variant=%d (0..4) or sweep_csplit=%d (0..4095) out of range", x->band_rows,
+                  x->sweep_variant, x->sweep_csplit);
+    for (const void* p : {x->X, x->We, (const void*)x->be, x->Wd, (const void*)x->bd, (const void*)x->D, (const void*)x->pool})
+        MI355_REQUIRE((uintptr_t)p % 16 == 0, "mbconv_front_ex: pointers must be 16-byte aligned");
+    const int H = x->H, W = x->W, Cin = x->Cin, mid = x->mid, k = x->k, stride = x->stride;
+    int rows = 0, how = x->kernel;
+    if (how == MI355_FRONT_KERNEL_AUTO) {
+        const mi355_model defaults{};    // the options a fresh model has
+        how = fused_pair_shape_how(defaults.fuse_sweep, defaults.fuse_band, H, W, Cin, mid, k, stride, x->act_e, x->act_d, &rows);
+        MI355_REQUIRE(how != MI355_PLAN_OP, "mbconv_front_ex: the launch plan runs H=%d W=%d Cin=%d mid=%d k=%d stride=%d unfused", H, W,
+                      Cin, mid, k, stride);
+    }
+    static_assert(MI355_FRONT_KERNEL_LATE == MI355_PLAN_FUSED_LATE && MI355_FRONT_KERNEL_SWEEP == MI355_PLAN_SWEEP &&
+                      MI355_FRONT_KERNEL_BAND == MI355_PLAN_BAND, "the forced kinds are the plan's");
+    MI355_REQUIRE(how != MI355_FRONT_KERNEL_LATE || fused_late_supported(H, W, Cin, mid, k, stride),
+                  "mbconv_front_ex: kernel late does not take H=%d W=%d Cin=%d mid=%d k=%d stride=%d", H, W, Cin, mid, k, stride);
+    MI355_REQUIRE(how != MI355_FRONT_KERNEL_SWEEP || (sweep_mbconv_supported(H, W, Cin, mid, k, stride, x->act_e, x->act_d) && kpad32(Cin) <= 128),
+                  "mbconv_front_ex: kernel sweep does not take H=%d W=%d Cin=%d mid=%d k=%d stride=%d act %d / %d", H, W, Cin, mid, k,
+                  stride, x->act_e, x->act_d);
+    if (how == MI355_FRONT_KERNEL_BAND) {
+        const int most = fused_band_rows(H, W, Cin, mid, k, stride);
+        MI355_REQUIRE(most > 0 && kpad32(Cin) <= 64, "mbconv_front_ex: kernel band does not take H=%d W=%d Cin=%d mid=%d k=%d stride=%d", H, W,
+                      Cin, mid, k, stride);
+        MI355_REQUIRE(x->band_rows <= most, "mbconv_front_ex: band_rows=%d exceeds the %d rows that fit the LDS", x->band_rows, most);
+        rows = x->band_rows ? x->band_rows : most;
+    } else {
+        MI355_REQUIRE(x->band_rows == 0, "mbconv_front_ex: band_rows belongs to the band kernel");
+    }
+    MI355_REQUIRE(how == MI355_FRONT_KERNEL_SWEEP || (x->sweep_variant == 0 && x->sweep_csplit == 0),
+                  "mbconv_front_ex: sweep_variant and sweep_csplit belong to the sweep kernel");
+    const int Ho = conv_out(H, k, stride), Wo = conv_out(W, k, stride);
+    const hipStream_t st = (hipStream_t)stream;
+    if (how == MI355_FRONT_KERNEL_SWEEP) {
+        SweepArgs a{};
+        a.X = (const bf16_t*)x->X; a.We = (const bf16_t*)x->We; a.be = x->be; a.Wd = (const bf16_t*)x->Wd; a.bd = x->bd;
+        a.D = (bf16_t*)x->D; a.pool = x->pool;
+        a.H = H; a.W = W; a.Cin = Cin; a.Kp = kpad32(Cin); a.mid = mid; a.Ho = Ho; a.Wo = Wo; a.act_e = x->act_e; a.act_d = x->act_d;
+        a.csplit_override = x->sweep_csplit; a.variant = x->sweep_variant;
+        if (pool_nblk) *pool_nblk = 1;
+        return launch_sweep_mbconv(a, x->B, k, stride, st, path);
+    }
+    FusedArgs a{};
+    a.X = (const bf16_t*)x->X; a.We = (const bf16_t*)x->We; a.be = x->be; a.Wd = (const bf16_t*)x->Wd; a.bd = x->bd;
+    a.D = (bf16_t*)x->D; a.pool = x->pool;
+    a.H = H; a.W = W; a.Cin = Cin; a.Kp = kpad32(Cin); a.mid = mid; a.Ho = Ho; a.Wo = Wo; a.act_e = x->act_e; a.act_d = x->act_d;
+    if (how == MI355_FRONT_KERNEL_LATE) {
+        if (pool_nblk) *pool_nblk = 1;
+        return launch_fused_late(a, x->B, k, stride, st, path);
+    }
+    a.TH = rows;
+    if (pool_nblk) *pool_nblk = cdiv(Ho, rows);
+    return launch_fused_band(a, x->B, k, stride, st, path);
 }
 
 int mi355_stem_ex(const mi355_stem_ex_args* x, int* path, void* stream) {

@@ -53,9 +53,10 @@ struct FusedArgs {
     int debug_skip;       // diagnosis only: bit0 skip the expand GEMM phase, bit1 skip the depthwise phase
 };
 bool fused_late_supported(int H, int W, int Cin, int mid, int k, int stride);
-int launch_fused_late(const FusedArgs& a, int B, int k, int stride, hipStream_t st);
+// path (may be null, here and below): MI355_FRONT_PATH_* of the instantiation that ran (include/mi355_retrieval.h)
+int launch_fused_late(const FusedArgs& a, int B, int k, int stride, hipStream_t st, int* path = nullptr);
 int fused_band_rows(int H, int W, int Cin, int mid, int k, int stride);   // 0 = unsupported
-int launch_fused_band(const FusedArgs& a, int B, int k, int stride, hipStream_t st);
+int launch_fused_band(const FusedArgs& a, int B, int k, int stride, hipStream_t st, int* path = nullptr);
 
 // ---- row-sweep front half for the early stages (sweep_mbconv.hip): expand -> MFMA depthwise -> D + complete squeeze sums
 struct SweepArgs {
@@ -75,7 +76,7 @@ struct SweepArgs {
     long long* stamps;    // diagnosis only: [B][16] cycle buckets, summed over the image's workgroups (wave 0's view)
 };
 bool sweep_mbconv_supported(int H, int W, int Cin, int mid, int k, int stride, int act_e, int act_d);
-int launch_sweep_mbconv(const SweepArgs& a, int B, int k, int stride, hipStream_t st);
+int launch_sweep_mbconv(const SweepArgs& a, int B, int k, int stride, hipStream_t st, int* path = nullptr);
 
 // ---- whole MBConv block for the late stages (mbconv_block.hip): expand -> depthwise -> SE -> gated projection (+ residual)
 struct BlockArgs {

@@ -17,6 +17,7 @@
 // row buffer of <= ~55 KB: two or three workgroups share a CU and hide each other's barriers and L2 latency.
 // Stride 2: the row buffer keeps even and odd columns in separate planes, so 16 consecutive output pixels read 16
 // consecutive LDS pixels for every tap (a stride-2 walk over 48-byte pixels would be a 2-way bank conflict).
+#include "../../include/mi355_retrieval.h"
 #include "ops.h"
 
 namespace mi355 {
@@ -182,6 +183,16 @@ __global__ __launch_bounds__(NW * 64, (NW * OCC + 3) / 4) void k_sweep_mbconv(co
     for (int si = g; si < nslab; si += a.csplit) {
         const int ch0 = ((si + b) % nslab) * (16 * NS);       // first channel of this pass; tile s covers ch0 + 16 s ...
         load_x(-1);
+        // Bands shorter than the halo (HALO > NEWR: 5x5 stride 2 with one-row bands): band -1's expand does not reach rows
+        // [NEWR, HALO) of its buffer, which band 0 takes over as rows above the image.  They are zero in a workgroup's first slab
+        // only; a slab walked before left its own rows there.
+        if constexpr (HALO > NEWR) {
+            constexpr int NZ16 = (HALO - NEWR) * RP * ELD / 8;
+#pragma unroll
+            for (int s = 0; s < NS; ++s)
+                for (int id = tid; id < NZ16; id += NTHR)
+                    *reinterpret_cast<u32x4*>(&Es[s * 2 * EBUF + NEWR * RP * ELD + id * 8]) = (u32x4){0u, 0u, 0u, 0u};
+        }
         // ---- slab constants: expand weights (MFMA A fragments) + bias, depthwise taps of this lane's channel + bias
         u32x4 wf[NS][KST];
         f32x4 bb[NS], bdr[NS];
@@ -390,7 +401,9 @@ struct SwPlan { int cls; int wgs_per_cu; int nct; };
 
 // shape classes (template instances).  NCT = 1 everywhere: one 16-channel tile per slab keeps the row buffer <= 55 KB
 // (2-3 workgroups per CU); 7 waves because 49 pixel tiles (14 or 28 rows of 56 / 28 pixels) split evenly over them.
+// (the values are MI355_SWEEP_CLASS_* of include/mi355_retrieval.h: launch_sweep_mbconv reports the class through `path`)
 enum { SW_NONE = 0, SW_3_2_112, SW_3_1_56, SW_5_2_56, SW_5_1_28, SW_3_2_28, SW_3_2_56, SW_3_1_28 };
+static_assert(SW_3_2_112 == MI355_SWEEP_CLASS_3_2_112 && SW_3_2_28 == MI355_SWEEP_CLASS_3_2_28 && SW_3_1_28 == MI355_SWEEP_CLASS_3_1_28, "sweep classes");
 
 static int sw_class(int H, int W, int k, int stride) {
     if (k == 3 && stride == 2 && W == 112 && H == 112) return SW_3_2_112;
@@ -420,7 +433,7 @@ bool sweep_mbconv_supported(int H, int W, int Cin, int mid, int k, int stride, i
 }
 
 template <int KS, int S, int WI, int TH, int NW, int KST, int OCC, bool PREF, int AE, int AD, int NS = 1>
-static int launch_sw_act(SweepArgs a, int B, hipStream_t st) {
+static int launch_sw_act(SweepArgs a, int B, hipStream_t st, int* path, int cls, int variant) {
     using G = SwGeom<KS, S, WI, TH>;
     const size_t lds = G::lds_bytes(NW, NS);
     static_assert(G::lds_bytes(NW, NS) <= 160 * 1024, "sweep: the row windows do not fit the LDS");
@@ -443,26 +456,31 @@ static int launch_sw_act(SweepArgs a, int B, hipStream_t st) {
     const unsigned grid = (unsigned)(8 * cdiv(B, 8) * a.csplit);
     hipLaunchKernelGGL((k_sweep_mbconv<KS, S, WI, TH, NW, KST, OCC, PREF, AE, AD, NS>), dim3(grid), dim3(NW * 64), lds, st, a);
     MI355_LAUNCH_CHECK();
+    if (path) {
+        const int inst = AE < 0 ? MI355_FRONT_ACT_RUNTIME : (AD == ACT_SILU ? MI355_FRONT_ACT_SILU_SILU : MI355_FRONT_ACT_SILU_NONE);
+        *path = MI355_FRONT_PATH_SWEEP(KS, S, cls, KST, NS, variant, inst, a.csplit);
+    }
     return OK;
 }
 
 template <int KS, int S, int WI, int TH, int NW, int KST, int OCC, bool PREF>
-static int launch_sw(const SweepArgs& a, int B, hipStream_t st) {
-    if (a.act_e == ACT_SILU && a.act_d == ACT_SILU) return launch_sw_act<KS, S, WI, TH, NW, KST, OCC, PREF, ACT_SILU, ACT_SILU>(a, B, st);
+static int launch_sw(const SweepArgs& a, int B, hipStream_t st, int* path, int cls) {
+    if (a.act_e == ACT_SILU && a.act_d == ACT_SILU) return launch_sw_act<KS, S, WI, TH, NW, KST, OCC, PREF, ACT_SILU, ACT_SILU>(a, B, st, path, cls, 0);
     // RexNet: SiLU after the expand, nothing after the depthwise (SE + ReLU6 follow in the projection's A load)
-    if (a.act_e == ACT_SILU && a.act_d == ACT_NONE) return launch_sw_act<KS, S, WI, TH, NW, KST, OCC, PREF, ACT_SILU, ACT_NONE>(a, B, st);
-    return launch_sw_act<KS, S, WI, TH, NW, KST, OCC, PREF, -1, -1>(a, B, st);
+    if (a.act_e == ACT_SILU && a.act_d == ACT_NONE) return launch_sw_act<KS, S, WI, TH, NW, KST, OCC, PREF, ACT_SILU, ACT_NONE>(a, B, st, path, cls, 0);
+    return launch_sw_act<KS, S, WI, TH, NW, KST, OCC, PREF, -1, -1>(a, B, st, path, cls, 0);
 }
 
 // variant table {TH, NW, OCC, PREF} per class; variant 0 is the default (both K depths, any activation), the others exist only
 // for the EfficientNet-B3a instances and are kept for tuning runs (tools/tune_sweep.py)
 // (two k-steps: no cross-phase X prefetch - its 2 x MW1 x 4 extra live registers spill at the 128-VGPR budget)
 #define SW_V0(KS, S, WI, TH, NW, OCC, PREF) \
-    return k2 ? launch_sw<KS, S, WI, TH, NW, 2, OCC, false>(a, B, st) : launch_sw<KS, S, WI, TH, NW, 1, OCC, PREF>(a, B, st)
+    return k2 ? launch_sw<KS, S, WI, TH, NW, 2, OCC, false>(a, B, st, path, cls) : launch_sw<KS, S, WI, TH, NW, 1, OCC, PREF>(a, B, st, path, cls)
 #define SW_VT(KS, S, WI, TH, NW, KST, OCC, PREF) \
-    return launch_sw_act<KS, S, WI, TH, NW, KST, OCC, PREF, ACT_SILU, ACT_SILU>(a, B, st)
+    return launch_sw_act<KS, S, WI, TH, NW, KST, OCC, PREF, ACT_SILU, ACT_SILU>(a, B, st, path, cls, v)
 
-int launch_sweep_mbconv(const SweepArgs& a, int B, int k, int stride, hipStream_t st) {
+int launch_sweep_mbconv(const SweepArgs& a, int B, int k, int stride, hipStream_t st, int* path) {
+    if (path) *path = 0;
     MI355_REQUIRE(sweep_mbconv_supported(a.H, a.W, a.Cin, a.mid, k, stride, a.act_e, a.act_d) && a.Kp % 32 == 0 && a.Kp >= 32 && a.Kp <= 128,
                   "sweep_mbconv: unsupported shape %dx%d k%d s%d Cin %d", a.H, a.W, k, stride, a.Cin);
     const bool k2 = a.Kp == 64;
@@ -470,15 +488,17 @@ int launch_sweep_mbconv(const SweepArgs& a, int B, int k, int stride, hipStream_
     const int cls = sw_class(a.H, a.W, k, stride);
     if (a.act_e == ACT_SILU && a.act_d == ACT_NONE && (sw_rex_instance(cls, a.Kp / 32) || (cls == SW_3_1_56 && a.Kp == 64))) {
         // RexNet (SiLU after the expand, linear depthwise).  REX(class geometry..., k-steps, workgroups per CU, X prefetch, tiles per pass)
-#define REX(KS, S, WI, TH, NW, KST, OCC, PREF, NS) return launch_sw_act<KS, S, WI, TH, NW, KST, OCC, PREF, ACT_SILU, ACT_NONE, NS>(a, B, st)
+#define REX(KS, S, WI, TH, NW, KST, OCC, PREF, NS) return launch_sw_act<KS, S, WI, TH, NW, KST, OCC, PREF, ACT_SILU, ACT_NONE, NS>(a, B, st, path, cls, rv)
         const int kst = a.Kp / 32;
         // measured at B = 256 (rexnet_150 / rexnet_200 forward): a pair of channel tiles per pass at 56 x 56 with one workgroup per CU:
         // 41->246 0.35 -> 0.22 ms, 58->348 s2 0.35 -> 0.29, 54->324 0.46 -> 0.31, 77->462 s2 0.42 -> 0.41; the same at 28 x 28, and
         // four-row bands for the stride-2 class, are level (and four-row bands change the order of the squeeze sums): not used
+        int rv = 3;                // the variant the instance stands for (reported through path)
         if (a.variant == 3) {      // tuning: one tile per pass at 56 x 56 as well
             if (cls == SW_3_1_56) REX(3, 1, 56, 8, 8, 2, 1, true, 1);
             if (cls == SW_3_2_56) { if (kst == 2) REX(3, 2, 56, 2, 7, 2, 1, true, 1); REX(3, 2, 56, 2, 7, 3, 2, false, 1); }
         }
+        rv = 0;
         if (cls == SW_3_1_56) REX(3, 1, 56, 8, 8, 2, 1, true, 2);
         if (cls == SW_3_2_56) { if (kst == 2) REX(3, 2, 56, 2, 7, 2, 1, true, 2); REX(3, 2, 56, 2, 7, 3, 1, false, 2); }
         if (cls == SW_3_1_28) { if (kst == 3) REX(3, 1, 28, 4, 7, 3, 2, false, 1); REX(3, 1, 28, 4, 7, 4, 2, false, 1); }

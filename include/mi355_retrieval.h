@@ -761,6 +761,50 @@ enum {
 
 int mi355_dwconv_se_ex(const mi355_dwconv_ex_args* args, int* path, void* stream);
 
+/* Developer entry: the fused front half of one MBConv / RexNet block (1x1 expand -> bias + act_e -> depthwise k x k -> bias +
+ * act_d, plus the SE squeeze sums) through the model's launchers: k_fused_late and k_fused_band (csrc/fused_mbconv.hip) and
+ * k_sweep_mbconv (csrc/sweep_mbconv.hip).  The expanded tensor E never leaves the LDS.
+ *   E[b][y][x][n]  = bf16( act_e( sum_c X[b][y][x][c] We[n][c] + be[n] ) )
+ *   v[b][oy][ox][n] = act_d( sum_{ky,kx} E[b][oy*stride - k/2 + ky][ox*stride - k/2 + kx][n] Wd[ky*k + kx][n] + bd[n] )   (zero padding)
+ *   D = bf16(v), Ho = (H - 1) / stride + 1, Wo likewise;  sum over blk of pool[b][blk][n] = sum over oy, ox of the un-rounded v
+ * X [B][H][W][Cin] bf16 NHWC; We [ceil16(mid)][ceil32(Cin)] bf16 in GEMM packing, zero padded; be [ceil16(mid)] fp32; Wd [k*k][mid]
+ * bf16; bd [mid] fp32; D [B][Ho][Wo][mid] bf16; pool (may be NULL) [B][nblk][mid] fp32 with nblk = *pool_nblk: 1 for the late and
+ * sweep kernels, ceil(Ho / band rows) for the band kernel.  All 16-byte aligned device pointers; Cin and mid multiples of 8.
+ * kernel: MI355_FRONT_KERNEL_AUTO takes the decision of the model's launch plan under default options (an error when the plan
+ * would run the pair unfused); LATE, SWEEP and BAND force one kernel and are rejected for shapes that kernel does not take.
+ * band_rows (BAND): output rows per workgroup, 0 = the largest that fits the LDS (what the model uses), else 1 .. that value.
+ * sweep_variant / sweep_csplit (SWEEP): the model options of the same names (0 = default).
+ * path (host, may be NULL) receives MI355_FRONT_PATH_LATE / _BAND / _SWEEP (...) of the instantiation that ran.  Every argument is
+ * checked before any HIP call.  Does not synchronise. */
+typedef struct mi355_mbconv_front_args {
+    const void* X; const void* We; const float* be; const void* Wd; const float* bd; void* D; float* pool;
+    int B, H, W, Cin, mid, k, stride, act_e, act_d;
+    int kernel, band_rows, sweep_variant, sweep_csplit;
+} mi355_mbconv_front_args;
+
+enum { MI355_FRONT_KERNEL_AUTO = 0, MI355_FRONT_KERNEL_LATE = 1, MI355_FRONT_KERNEL_SWEEP = 2, MI355_FRONT_KERNEL_BAND = 3 };
+/* activation instance of k_sweep_mbconv: compiled for SiLU / SiLU, for SiLU / none, or reading act_e / act_d at run time */
+enum { MI355_FRONT_ACT_SILU_SILU = 1, MI355_FRONT_ACT_SILU_NONE = 2, MI355_FRONT_ACT_RUNTIME = 3 };
+/* shape classes of k_sweep_mbconv: k_stride_map */
+enum {
+    MI355_SWEEP_CLASS_3_2_112 = 1, MI355_SWEEP_CLASS_3_1_56 = 2, MI355_SWEEP_CLASS_5_2_56 = 3, MI355_SWEEP_CLASS_5_1_28 = 4,
+    MI355_SWEEP_CLASS_3_2_28 = 5, MI355_SWEEP_CLASS_3_2_56 = 6, MI355_SWEEP_CLASS_3_1_28 = 7
+};
+/* family = MI355_FRONT_KERNEL_*; late: NIW images' worth of channels per slab (slab = 128 NIW), PX pixels per depthwise thread;
+ * band: KST k-steps, PX, MC channels per slab, TH output rows per workgroup; sweep: class, KST, NS channel tiles per pass, the
+ * tuning variant that ran (0 when the request does not apply), activation instance, workgroups per image */
+#define MI355_FRONT_PATH_BASE(family, ks, s) ((family) | ((ks) == 5) << 2 | ((s) == 2) << 3)
+#define MI355_FRONT_PATH_LATE(ks, s, niw, px) (MI355_FRONT_PATH_BASE(MI355_FRONT_KERNEL_LATE, ks, s) | (niw) << 4 | (px) << 8)
+#define MI355_FRONT_PATH_BAND(ks, s, kst, px, mc, th) \
+    (MI355_FRONT_PATH_BASE(MI355_FRONT_KERNEL_BAND, ks, s) | (kst) << 4 | (px) << 8 | (mc) << 12 | (th) << 20)
+#define MI355_FRONT_PATH_SWEEP(ks, s, cls, kst, ns, variant, act, csplit) \
+    (MI355_FRONT_PATH_BASE(MI355_FRONT_KERNEL_SWEEP, ks, s) | (cls) << 4 | (kst) << 8 | (ns) << 12 | (variant) << 14 | (act) << 17 | (csplit) << 19)
+#define MI355_FRONT_PATH_FAMILY(p) ((p) & 3)
+#define MI355_FRONT_PATH_KS(p) (((p) >> 2 & 1) ? 5 : 3)
+#define MI355_FRONT_PATH_S(p) (((p) >> 3 & 1) ? 2 : 1)
+
+int mi355_mbconv_front_ex(const mi355_mbconv_front_args* args, int* pool_nblk, int* path, void* stream);
+
 /* Developer entry: one stem call of the convolutional backbones (3x3 stride 2 pad 1, 3 -> Cout, + bias + act) through the
  * model's launchers, in either input form.  Exactly one of x and images is non-null.
  *   out[b][oy][ox][co] = bf16( act( bias[co] + sum_{ky,kx,ci} in[b][ci][2 oy - 1 + ky][2 ox - 1 + kx] w[(ky*3 + kx)*3 + ci][co] ) )

@@ -1,5 +1,5 @@
-"""The developer entries mi355_window_attention, mi355_gemm_bf16_ex and mi355_dwconv_se_ex, the parts that need no GPU: the C-ABI symbols and
-every argument check (rejected before any HIP call, with a message)."""
+"""The developer entries mi355_window_attention, mi355_gemm_bf16_ex, mi355_dwconv_se_ex and mi355_mbconv_front_ex, the parts that need no
+GPU: the C-ABI symbols and every argument check (rejected before any HIP call, with a message)."""
 import ctypes
 
 import pytest
@@ -7,7 +7,7 @@ import pytest
 from helpers import header_symbols
 from imageretrievalresearch_amd import _lib
 
-NEW = ["mi355_window_attention", "mi355_gemm_bf16_ex", "mi355_dwconv_se_ex"]
+NEW = ["mi355_window_attention", "mi355_gemm_bf16_ex", "mi355_dwconv_se_ex", "mi355_mbconv_front_ex"]
 P = 1 << 20          # a 16-byte aligned stand-in pointer: nothing is dereferenced when a check fails
 
 
@@ -170,3 +170,82 @@ def test_dwconv_ex_args_layout_matches_the_header():
     D = _lib.DwconvExArgs
     assert ctypes.sizeof(D) == 120
     assert (D.B.offset, D.choice.offset, D.se_w1.offset, D.rd.offset, D.gate.offset, D.squeeze.offset) == (32, 60, 64, 96, 104, 112)
+
+
+def _front_ok():
+    """A valid operand block (B = 3, 14x14, 24 -> 144, 3x3 stride 1, SiLU / SiLU, kernel auto = late) with stand-in pointers."""
+    return dict(X=P, We=P, be=P, Wd=P, bd=P, D=P, pool=P, B=3, H=14, W=14, Cin=24, mid=144, k=3, stride=1, act_e=1, act_d=1)
+
+
+_AT56 = dict(H=56, W=56)        # a 3x3 stride-1 56x56 layer: the sweep kernel's class 3_1_56, and a band-kernel shape
+
+
+@pytest.mark.parametrize("change,msg", [
+    (dict(X=None), b"null"),
+    (dict(We=None), b"null"),
+    (dict(be=None), b"null"),
+    (dict(Wd=None), b"null"),
+    (dict(bd=None), b"null"),
+    (dict(D=None), b"null"),
+    (dict(B=0), b"bad shape"),
+    (dict(B=65536), b"bad shape"),
+    (dict(H=0), b"bad shape"),
+    (dict(W=-1), b"bad shape"),
+    (dict(W=20000), b"bad shape"),
+    (dict(Cin=0), b"bad shape"),
+    (dict(mid=0), b"bad shape"),
+    (dict(mid=40000), b"bad shape"),
+    (dict(Cin=20), b"multiples of 8"),
+    (dict(mid=148), b"multiples of 8"),
+    (dict(B=4096, H=4096, W=4096, kernel=3), b"too large"),
+    (dict(k=7), b"unsupported k"),
+    (dict(k=1), b"unsupported k"),
+    (dict(stride=3), b"unsupported k"),
+    (dict(act_e=6), b"activation"),
+    (dict(act_d=-1), b"activation"),
+    (dict(kernel=4), b"unknown kernel"),
+    (dict(kernel=-1), b"unknown kernel"),
+    (dict(band_rows=-1), b"out of range"),
+    (dict(sweep_variant=5), b"out of range"),
+    (dict(sweep_csplit=-2), b"out of range"),
+    (dict(sweep_csplit=4096), b"out of range"),
+    (dict(X=P + 8), b"16-byte aligned"),
+    (dict(be=P + 4), b"16-byte aligned"),
+    (dict(D=P + 2), b"16-byte aligned"),
+    (dict(pool=P + 4), b"16-byte aligned"),
+    (dict(H=15, W=14, k=5), b"unfused"),                              # auto: 210 pixels and 5x5: the plan fuses no such pair
+    (dict(_AT56, Cin=72, mid=432), b"unfused"),                       # auto: three k-steps with SiLU / SiLU
+    (dict(kernel=1, H=15, W=14), b"late does not take"),              # the whole-image kernel stops at 208 pixels
+    (dict(kernel=1, Cin=512, mid=3072), b"late does not take"),       # ... and at the LDS
+    (dict(kernel=2), b"sweep does not take"),                         # the sweep kernel has its map classes
+    (dict(_AT56, kernel=2, k=5), b"sweep does not take"),
+    (dict(_AT56, kernel=2, Cin=72), b"sweep does not take"),          # three k-steps: only RexNet's 3_2_56 with SiLU / none
+    (dict(_AT56, kernel=2, Cin=72, stride=2, act_d=1), b"sweep does not take"),
+    (dict(H=28, W=28, kernel=2, Cin=136, act_d=0), b"sweep does not take"),     # five k-steps
+    (dict(_AT56, kernel=3, Cin=72), b"band does not take"),           # the band kernel has one or two k-steps
+    (dict(kernel=3, H=8, W=136), b"band does not take"),              # ... and maps up to 128 wide
+    (dict(_AT56, kernel=3, Cin=32, mid=192, band_rows=10), b"exceeds"),          # nine rows of this layer fit the LDS
+    (dict(band_rows=2), b"belongs to the band kernel"),
+    (dict(_AT56, kernel=2, band_rows=2), b"belongs to the band kernel"),
+    (dict(sweep_variant=1), b"belong to the sweep kernel"),
+    (dict(_AT56, kernel=3, sweep_csplit=2), b"belong to the sweep kernel"),
+])
+def test_mbconv_front_ex_argument_errors(change, msg):
+    a = _front_ok()
+    a.update(change)
+    x = _lib.MbconvFrontArgs(**a)
+    path, nblk = ctypes.c_int(-1), ctypes.c_int(-1)
+    assert _lib.lib().mi355_mbconv_front_ex(ctypes.byref(x), ctypes.byref(nblk), ctypes.byref(path), None) != 0
+    assert msg in _err(), _err()
+    assert path.value == 0 and nblk.value == 0            # a rejected call reports no kernel
+
+
+def test_mbconv_front_ex_null_block():
+    assert _lib.lib().mi355_mbconv_front_ex(None, None, None, None) != 0
+    assert b"null" in _err()
+
+
+def test_mbconv_front_args_layout_matches_the_header():
+    F = _lib.MbconvFrontArgs
+    assert ctypes.sizeof(F) == 112
+    assert (F.pool.offset, F.B.offset, F.act_d.offset, F.kernel.offset, F.sweep_csplit.offset) == (48, 56, 88, 92, 104)
