@@ -20,13 +20,14 @@ from .whitening import Moments, Whitening, embedding_moments  # noqa: F401
 from .cluster import (KMeansResult, assign_clusters, cluster_members, clustering_metrics,  # noqa: F401
                       clustering_metrics_from_table, contingency, spherical_kmeans, update_centroids)
 from .ivf import IVFIndex  # noqa: F401
+from .quantized import Int8Gallery  # noqa: F401
 
 __all__ = ["Whitening", "Moments", "embedding_moments","create_model", "list_models", "load_checkpoint", "strip_lightning_prefix", "ContrastiveLoss", "CosineEmbeddingLoss", "validation_metrics", "CosineSimilarity", "Gallery", "PreparedGallery", "cosine_scores",
            "cosine_range", "cosine_topk", "expand_queries", "pair_cosine", "topk", "merge_topk", "hit_counts", "distinct_class_topn",
            "retrieval_metrics", "retrieval_accuracy", "roc_curve", "verification_roc", "cos_sim_score_with_threshold", "cos_sim_score_booster", "l2_normalize_rows", "synth_fill", "ShardedGallery", "MI355Error",
            "pack_images", "resize_batch", "RerankIndex", "k_reciprocal_rerank", "PositiveRanks", "positive_ranks", "ranking_metrics",
            "KMeansResult", "assign_clusters", "update_centroids", "cluster_members", "spherical_kmeans", "contingency",
-           "clustering_metrics", "clustering_metrics_from_table", "IVFIndex"]
+           "clustering_metrics", "clustering_metrics_from_table", "IVFIndex", "Int8Gallery"]
 
 
 def __getattr__(name):  # lazy: models/sharded import torch.nn / torch.distributed

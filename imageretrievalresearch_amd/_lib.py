@@ -87,6 +87,16 @@ PROTOTYPES = {
                                            C.POINTER(RankFilter), vp, vp, vp, C.c_size_t, vp]),
     "mi355_rank_topk_f16_filtered": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_int64,
                                                C.POINTER(RankFilter), vp, vp, vp, C.c_size_t, vp]),
+    "mi355_gallery_i8_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
+    "mi355_gallery_to_i8": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, C.c_float, vp, C.c_size_t, vp, vp]),
+    "mi355_rank_i8_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int, C.c_int]),
+    "mi355_rank_topk_i8": (C.c_int, [vp, C.c_int64, vp, vp, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_int64, vp, vp, vp,
+                                     C.c_size_t, vp]),
+    "mi355_rank_topk_i8_filtered": (C.c_int, [vp, C.c_int64, vp, vp, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_int64,
+                                              C.POINTER(RankFilter), vp, vp, vp, C.c_size_t, vp]),
+    "mi355_range_i8_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int]),
+    "mi355_cosine_range_i8": (C.c_int, [vp, C.c_int64, vp, vp, C.c_int64, C.c_int, C.c_float, C.c_double, C.c_int64,
+                                        C.POINTER(RankFilter), vp, C.c_int64, C.POINTER(C.c_int64), vp, C.c_size_t, vp]),
     "mi355_rank_last_path": (C.c_int, []),
     "mi355_rank_round_split": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "mi355_rank_set_round_slots": (C.c_int, [C.c_int]),

@@ -1,5 +1,5 @@
-// Shared between the rank kernels (rank.hip: fp32 rows, bf16 planes; rank_f16.hip: fp16 rows): the launch order of the
-// cosine GEMM's tiles, its epilogues (one type each: score slab, fused per-tile top-k, ROC histogram, range hits, full-gallery
+// Shared between the rank kernels (rank.hip: fp32 rows, bf16 planes; rank_f16.hip: fp16 rows; rank_i8.hip: int8 rows): the
+// launch order of the cosine GEMM's tiles, its epilogues (one type each: score slab, fused per-tile top-k, ROC histogram, range hits, full-gallery
 // ranks, nearest centroid), the host side of the top-k selection that merges what the fused epilogue leaves, the one launcher of every tiled
 // GEMM and the query-block loop of every top-k search.  gfx950 only.
 #pragma once
@@ -739,7 +739,7 @@ int round_slots(int device_slots);
 void set_last_tiles(int slots, int ny, int main_tiles, int tail_tiles, int tail_ny);
 
 // ---- host side of the tiled cosine GEMMs: exact fp32, split bf16 (rank.hip: F32Gemm, SplitGemm, PreparedGemm) and fp16
-// (rank_f16.hip: F16Gemm).  A family F supplies only what differs between them:
+// (rank_f16.hip: F16Gemm) and int8 (rank_i8.hip: I8Gemm).  A family F supplies only what differs between them:
 //   F::stage_bytes<MT>()             the LDS of its staging buffers
 //   F::kernel<MT, Epi>()             its kernel with epilogue Epi
 //   F::launch<MT, Epi>(...)          one launch of that kernel over column tiles [x0, x0 + xtiles) x ny query tiles
@@ -754,12 +754,12 @@ template <int FK, bool FILT> constexpr bool is_select<SelectEpi<FK, FILT>> = tru
 
 // What every GEMM call over Q queries shares; the epilogue object travels beside it
 struct TileArgs {
-    const void* qry;            // the queries as the family reads them: fp32 rows, bf16 split planes or fp16 planes
-    const void* gal;            // the gallery: fp32 rows, bf16 planes (prepared) or fp16 rows
-    const float* ginv;          // 1 / |gallery row| (fp32 rows), or null
+    const void* qry;            // the queries as the family reads them: fp32 rows, bf16 split planes, fp16 or int8 planes
+    const void* gal;            // the gallery: fp32 rows, bf16 planes (prepared), fp16 rows or int8 codes
+    const float* ginv;          // 1 / |gallery row| (fp32 rows), the rows' scales (int8 codes), or null
     int Q;
     i64 G;
-    int D;                      // dim (fp16 rows: their padded length ld)
+    int D;                      // dim (fp16 / int8 rows: their padded length ld)
 };
 
 // Column tiles [x0, ntx) of a GEMM call.
@@ -891,19 +891,27 @@ i64 ranks_query_block(i64 Q, i64 G, i64 query_block);
 
 
 // ---- the searches without a top-k (ROC histogram, range, ranks) exist once for both kinds of gallery rows (rank.hip)
-// The gallery as a search reads it: fp32 rows [G][dim], or the fp16 rows of mi355_gallery_to_f16
+// The gallery as a search reads it: fp32 rows [G][dim], the fp16 rows of mi355_gallery_to_f16, or the int8 codes and scales
+// of mi355_gallery_to_i8
 struct GalleryRows {
     const float* f32;           // fp32 rows, or null
-    bool unit;                  // fp32 rows: unit length already (no 1 / |row| pass); fp16 rows always are
+    bool unit;                  // fp32 rows: unit length already (no 1 / |row| pass); fp16 and int8 rows always are
     const void* f16;            // fp16 rows [G][ld], or null
-    int ld;                     // their padded length
+    int ld;                     // the padded length of fp16 / int8 rows
     size_t (*planes_bytes)(i64, int);   // bytes of the operand the GEMM reads for (queries of one call, dim)
-    const void* rows() const { return f16 ? f16 : (const void*)f32; }
+    const void* i8 = nullptr;   // int8 codes [G][ld], or null
+    const float* scales = nullptr;      // their scales [G]
+    const void* rows() const { return i8 ? i8 : f16 ? f16 : (const void*)f32; }
 };
 // One GEMM call over fp16 rows: the normalised queries qn [Q][dim] into their fp16 planes qs, then F16Gemm with epi; sets the
 // rank path (rank_f16.hip; instantiated there for the epilogues of the three searches below)
 template <class Epi>
 int cos_gemm_f16(const void* rows, int ld, const float* qn, void* qs, i64 Q, i64 G, int dim, const Epi& epi, hipStream_t st);
+// The same over int8 rows: the queries' two int8 planes and s_q into qs, then I8Gemm with epi (rank_i8.hip; instantiated there
+// for the range epilogue)
+template <class Epi>
+int cos_gemm_i8(const void* codes, const float* scales, int ld, const float* qn, void* qs, i64 Q, i64 G, int dim, const Epi& epi,
+                hipStream_t st);
 // mi355_roc_pairs_hist[_f16] under the name who; need: the entry's workspace size
 int roc_pairs_hist(const float* queries, i64 Q, const GalleryRows& g, i64 G, int dim, float eps, const int64_t* query_labels,
                    const int64_t* gallery_labels, const int64_t* exclude, i64 idx_offset, const double* thresholds,

@@ -1,0 +1,558 @@
+// 8-bit resident gallery: scalar-quantised int8 rows with one fp32 scale per row, and the cosine / top-k / range search over
+// them on v_mfma_i32_32x32x32_i8.  gfx950 only.
+//
+// Numerical contract (include/mi355_retrieval.h).  "fp32" = one IEEE rounding per named operation.
+//   * row quantiser (gallery rows and the query's hi plane): n = the fp32 row mi355_l2_normalize_rows writes for x (one shared
+//     norm, row_inv_norm, same vec rule), amax = max |n_i|.  A NaN element or a non-finite amax: scale = NaN, codes 0.
+//     amax < 1e-30: scale = 0, codes 0.  Else scale = amax / 127, inv = 127 / amax, code_i = clamp(rintf(n_i * inv), -127, 127)
+//     (round-half-even).  Codes are int8, ld = dim rounded up to a multiple of 128 bytes per row, bytes dim .. ld-1 zero; the
+//     scales are an fp32 array [G] beside them.
+//   * query planes, per call, from qn = l2_normalize_rows(q): (hi, s_q) = the row quantiser of qn, r_i = fmaf(-hi_i, s_q, qn_i),
+//     lo_i = clamp(rintf(r_i * (128 / s_q)), -127, 127) (|lo_i| <= 64; lo = 0 when s_q is 0 or NaN): about 15 bits of the query.
+//   * score: acc_hi = sum hi_i c_i, acc_lo = sum lo_i c_i, exact in int32 (dim <= 65536); t = fmaf(float(acc_lo), 2^-7,
+//     float(acc_hi)); score = (t * s_q) * s_g.  A NaN row scores NaN, a zero row 0, a NaN query NaN everywhere.
+//   * the integer sums do not depend on any summation order, so the GEMV (Q <= 4), both tile sizes of the GEMM, its two
+//     launches and every epilogue return the SAME bits for a (query, row) pair.
+//   * order, ties, NaN, pads: the selection of mi355_rank_topk (rank_common.h).
+#include "rank_common.h"
+#include "../../include/mi355_retrieval.h"
+
+#include <float.h>
+
+namespace mi355 {
+
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int I8_KSTEP = 128;                 // k-step of the GEMM: one 128-byte segment of a stored row
+constexpr int I8_MAX_DIM = 65536;             // 65536 * 127 * 127 < 2^31: the int32 sums are exact
+static inline int i8_ld(int dim) { return (dim + I8_KSTEP - 1) / I8_KSTEP * I8_KSTEP; }
+
+// ---- the row quantiser: scale and inverse scale of a row from its amax, then the code of one element
+struct I8Quant {
+    float scale, inv;
+    bool zero;                                // every code is 0 (NaN row, zero row)
+};
+__device__ __forceinline__ I8Quant i8_quant(float amax, bool has_nan) {
+    if (has_nan || !(amax <= FLT_MAX)) return {__uint_as_float(0x7fc00000u), 0.f, true};
+    if (amax < 1e-30f) return {0.f, 0.f, true};
+    return {amax / 127.0f, 127.0f / amax, false};
+}
+// clamp(rintf(x * m), -127, 127); the empty asm pins the fp32 product in a register, as scaled_f16 does
+__device__ __forceinline__ int i8_code(float x, float m) {
+    float p = x * m;
+    asm volatile("" : "+v"(p));
+    return (int)fminf(fmaxf(rintf(p), -127.0f), 127.0f);
+}
+// the fp32 row value x * r (the bits of l2_normalize_rows), pinned so that no later product is folded into it
+__device__ __forceinline__ float i8_norm_elem(float x, float r) {
+    float p = x * r;
+    asm volatile("" : "+v"(p));
+    return p;
+}
+__device__ __forceinline__ unsigned pack4_i8(int a, int b, int c, int d) {
+    return (unsigned)(a & 0xff) | ((unsigned)(b & 0xff) << 8) | ((unsigned)(c & 0xff) << 16) | ((unsigned)(d & 0xff) << 24);
+}
+
+// =====================================================================================
+// fp32 rows -> int8 codes, padded to ld bytes with zeros, and one scale per row.  One wave per row: the norm with
+// row_inv_norm, amax by wave reduction, then the codes.  Appendable: converting n rows to codes + r * ld, scales + r writes
+// rows r .. r+n-1.
+// =====================================================================================
+__global__ __launch_bounds__(256) void k_rows_to_i8(const float* __restrict__ in, signed char* __restrict__ codes,
+                                                    float* __restrict__ scales, i64 rows, int dim, int ld, float eps,
+                                                    int normalize, int vec) {
+    const int lane = threadIdx.x & 63;
+    const i64 row = (i64)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float* x = in + row * dim;
+    const float r = normalize ? row_inv_norm(x, dim, eps, vec, lane) : 1.0f;
+    float amax = 0.f;
+    bool nan = false;
+    if (vec) {
+        const f32x4* x4 = reinterpret_cast<const f32x4*>(x);
+        for (int i = lane; i < dim / 4; i += 64) {
+            const f32x4 v = x4[i];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float n = i8_norm_elem(v[e], r);
+                nan = nan || n != n;
+                amax = fmaxf(amax, fabsf(n));
+            }
+        }
+    } else {
+        for (int i = lane; i < dim; i += 64) {
+            const float n = i8_norm_elem(x[i], r);
+            nan = nan || n != n;
+            amax = fmaxf(amax, fabsf(n));
+        }
+    }
+    const I8Quant q = i8_quant(wave_max(amax), __ballot(nan) != 0ull);
+    if (lane == 0) scales[row] = q.scale;
+    signed char* y = codes + row * ld;
+    if (vec) {
+        const f32x4* x4 = reinterpret_cast<const f32x4*>(x);
+        for (int i = lane; i < ld / 4; i += 64) {
+            unsigned w = 0u;
+            if (i < dim / 4 && !q.zero) {
+                const f32x4 v = x4[i];
+                w = pack4_i8(i8_code(i8_norm_elem(v.x, r), q.inv), i8_code(i8_norm_elem(v.y, r), q.inv),
+                             i8_code(i8_norm_elem(v.z, r), q.inv), i8_code(i8_norm_elem(v.w, r), q.inv));
+            }
+            reinterpret_cast<unsigned*>(y)[i] = w;
+        }
+    } else {
+        for (int i = lane; i < ld; i += 64) y[i] = (i < dim && !q.zero) ? (signed char)i8_code(i8_norm_elem(x[i], r), q.inv) : (signed char)0;
+    }
+}
+
+// =====================================================================================
+// Normalised queries -> their two int8 planes in MFMA-fragment order and s_q per query:
+// Qs[row block of 32][k sub-step of 32][plane hi, lo][lane][16 B], lane = row + 32 * (k half): the lane's 16 bytes are the 16
+// consecutive k of its half of the sub-step.  A GEMM k-step of 128 is then 8 KB per row block, eight 1 KB pieces that LDS-DMA
+// moves as they are.  One wave per row of the rows_pad (whole 128-row tiles) rows; rows >= Q and k >= D are zero, sq 0.
+// =====================================================================================
+__global__ __launch_bounds__(256) void k_split_queries_i8(const float* __restrict__ Qn, signed char* __restrict__ Qs,
+                                                          float* __restrict__ sq, int Q, int D, int n_sub, int rows_pad,
+                                                          int vec) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows_pad) return;
+    const float* x = Qn + (i64)row * D;
+    I8Quant q = {0.f, 0.f, true};
+    if (row < Q) {
+        float amax = 0.f;
+        bool nan = false;
+        if (vec) {
+            const f32x4* x4 = reinterpret_cast<const f32x4*>(x);
+            for (int i = lane; i < D / 4; i += 64) {
+                const f32x4 v = x4[i];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    nan = nan || v[e] != v[e];
+                    amax = fmaxf(amax, fabsf(v[e]));
+                }
+            }
+        } else {
+            for (int i = lane; i < D; i += 64) {
+                const float n = x[i];
+                nan = nan || n != n;
+                amax = fmaxf(amax, fabsf(n));
+            }
+        }
+        q = i8_quant(wave_max(amax), __ballot(nan) != 0ull);
+    }
+    if (lane == 0) sq[row] = q.scale;
+    const float lo_mul = q.zero ? 0.f : 128.0f / q.scale;
+    signed char* base = Qs + (size_t)(row >> 5) * n_sub * 2048 + (row & 31) * 16;
+    for (int c = lane; c < 2 * n_sub; c += 64) {           // 16-byte chunk c: sub-step c / 2, k half c % 2
+        unsigned hi[4] = {0u, 0u, 0u, 0u}, lo[4] = {0u, 0u, 0u, 0u};
+        if (!q.zero) {
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                const int k0 = c * 16 + w * 4;
+                f32x4 v = {0.f, 0.f, 0.f, 0.f};
+                if (vec) {                                 // D % 4 == 0: a group of four lies inside the row or past it
+                    if (k0 < D) v = *reinterpret_cast<const f32x4*>(x + k0);
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = k0 + e < D ? x[k0 + e] : 0.f;
+                }
+                int h[4], l[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float n = v[e];
+                    h[e] = i8_code(n, q.inv);
+                    l[e] = i8_code(__builtin_fmaf(-(float)h[e], q.scale, n), lo_mul);
+                }
+                hi[w] = pack4_i8(h[0], h[1], h[2], h[3]);
+                lo[w] = pack4_i8(l[0], l[1], l[2], l[3]);
+            }
+        }
+        signed char* o = base + (size_t)(c >> 1) * 2048 + (c & 1) * 512;
+        *reinterpret_cast<i32x4*>(o) = (i32x4){(int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
+        *reinterpret_cast<i32x4*>(o + 1024) = (i32x4){(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3]};
+    }
+}
+
+// =====================================================================================
+// cosine GEMM over int8 rows: S / per-tile candidates as k_cos_gemm_f16 (same block and wave tiling, same launch order, same
+// DMA rings, same epilogues, rank_common.h).  Block = 4 waves as 2(M) x 2(N), block tile (64 * MT) queries x 128 gallery rows,
+// k-step 128 (four 32x32x32 sub-steps, two planes each).
+//   A (query planes): 8 * MT pieces of 1 KB per k-step by LDS-DMA from L2, one k-step ahead (ring of 2).
+//   B (gallery): the tile's 128 rows x 128 B per k-step by LDS-DMA from HBM, two k-steps ahead (ring of 3).  A piece is 8
+//     rows; the 16-byte chunk c of row r lands at position c ^ ((r >> 1) & 7) (applied to the per-lane SOURCE address, the
+//     DMA writes lane-linear) - the byte layout of the fp16 kernel, so its swizzle carries over.  Rows past G re-read row G - 1
+//     (the epilogue drops them).
+// No load in the loop has a register destination: ONE counted vmcnt(4) per k-step (this iteration's four B pieces, issued
+// last, stay in flight) and one LDS-only barrier.  Per wave and k-step: 8 * MT + 8 ds_read_b128 and 16 * MT MFMAs.
+// LDS: 2 x 32 KB (A) + 3 x 16 KB (B) = 112 KB at MT = 2, 2 x 16 + 48 = 80 KB at MT = 1 (two workgroups per CU).
+// Fragment map: a lane's A and B fragments of a sub-step are the SAME 16 consecutive k (its half of the sub-step), byte for
+// byte.  The MFMA pairs A and B bytes by (lane half, byte), and an integer sum does not depend on the k order, so whichever k
+// the hardware calls them the result is the exact dot product.
+// =====================================================================================
+template <int MT, class Epi>
+__device__ __forceinline__ void cos_gemm_i8_tile(const signed char* __restrict__ Qs, const float* __restrict__ sq,
+                                                 const signed char* __restrict__ Gal, const float* __restrict__ scales, int Q, i64 G,
+                                                 int ld, int x0, int ntx, int xtiles, int ny, const Epi& epi) {
+    constexpr int BM = 64 * MT;
+    constexpr int A_PIECES = (BM / 32) * 8;           // 1 KB pieces per stage: 4 sub-steps x 2 planes per row block
+    constexpr int A_STAGE = A_PIECES * 1024;          // bytes per stage
+    constexpr int B_STAGE = RK_BN * I8_KSTEP;         // bytes per stage (16 KB)
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    signed char* As = reinterpret_cast<signed char*>(smem);   // [2][BM/32][4][2][1024]
+    signed char* Bs = As + 2 * A_STAGE;                        // [3][128][128], chunks swizzled
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1, lr = lane & 31;
+    int bx, by;
+    rank_tile_of((int)blockIdx.x, xtiles, ny, bx, by);
+    const i64 n0 = (i64)(bx + x0) * RK_BN;
+    const int m0 = by * BM;
+    const int swave = __builtin_amdgcn_readfirstlane(wave);
+    const int n_steps = ld / I8_KSTEP, n_sub = ld / 32;
+
+    // B: wave w moves pieces 4w .. 4w + 3; lane -> row 8 * piece + lane / 8, LDS position lane % 8
+    const signed char* b_src[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int r = (swave * 4 + i) * 8 + (lane >> 3);
+        const int c = (lane & 7) ^ ((r >> 1) & 7);
+        const i64 g = n0 + r < G ? n0 + r : G - 1;
+        b_src[i] = Gal + g * ld + c * 16;
+    }
+    // (k-steps past the end re-read the last one: the data is never used, the count of pieces in flight stays uniform)
+    auto dma_b = [&](int stage, int t) {
+        const int tt = t < n_steps ? t : n_steps - 1;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            glds16(reinterpret_cast<const bf16_t*>(b_src[i] + tt * I8_KSTEP),
+                   reinterpret_cast<bf16_t*>(Bs + stage * B_STAGE + (swave * 4 + i) * 1024));
+    };
+    // A: piece p = (row block p / 8, sub-step (p % 8) / 2, plane p % 2) of k-step t sits at
+    // Qs + ((m0/32 + p/8) * n_sub + 4t) * 2048 + (p % 8) * 1024; wave w moves pieces w, w + 4, ...
+    const signed char* a_src[A_PIECES / 4];
+#pragma unroll
+    for (int i = 0; i < A_PIECES / 4; ++i) {
+        const int p = swave + 4 * i;
+        a_src[i] = Qs + ((size_t)(m0 / 32 + p / 8) * n_sub) * 2048 + (p % 8) * 1024 + lane * 16;
+    }
+    auto dma_a = [&](int buf, int t) {
+#pragma unroll
+        for (int i = 0; i < A_PIECES / 4; ++i)
+            glds16(reinterpret_cast<const bf16_t*>(a_src[i] + (size_t)t * 4 * 2048),
+                   reinterpret_cast<bf16_t*>(As + buf * A_STAGE + (swave + 4 * i) * 1024));
+    };
+
+    i32x16 acc_hi[MT][2], acc_lo[MT][2];
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) { acc_hi[i][j][e] = 0; acc_lo[i][j][e] = 0; }
+
+    // B fragment reads: row r = wn * 64 + j * 32 + lr, chunk 2s + (lane >> 5) of sub-step s at its swizzled position
+    int b_off[2][4];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int r = wn * 64 + j * 32 + lr;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) b_off[j][s] = r * I8_KSTEP + (((2 * s + (lane >> 5)) ^ ((r >> 1) & 7)) << 4);
+    }
+    auto compute = [&](int abuf, int bstage) {
+        const signed char* a = As + abuf * A_STAGE + (wm * MT) * 8 * 1024 + lane * 16;
+        const signed char* b = Bs + bstage * B_STAGE;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            i32x4 bf[2], ah[MT], al[MT];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) bf[j] = *reinterpret_cast<const i32x4*>(b + b_off[j][s]);
+#pragma unroll
+            for (int i = 0; i < MT; ++i) {
+                ah[i] = *reinterpret_cast<const i32x4*>(a + (i * 8 + s * 2) * 1024);
+                al[i] = *reinterpret_cast<const i32x4*>(a + (i * 8 + s * 2 + 1) * 1024);
+            }
+#pragma unroll
+            for (int i = 0; i < MT; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    acc_lo[i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(al[i], bf[j], acc_lo[i][j], 0, 0, 0);
+                    acc_hi[i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(ah[i], bf[j], acc_hi[i][j], 0, 0, 0);
+                }
+        }
+    };
+
+    dma_a(0, 0);
+    dma_b(0, 0);
+    dma_b(1, 1);
+    __syncthreads();                   // drains vmcnt: everything has landed
+
+    int bs_cur = 0, bs_far = 2;        // B stage of k-step t / of k-step t + 2
+    for (int t = 0; t < n_steps; ++t) {
+        if (t + 1 < n_steps) dma_a((t & 1) ^ 1, t + 1);   // everybody left this buffer at the previous barrier
+        __builtin_amdgcn_sched_barrier(0);                // (the count below needs the A pieces issued BEFORE the B pieces)
+        dma_b(bs_far, t + 2);
+        __builtin_amdgcn_sched_barrier(0);
+        compute(t & 1, bs_cur);
+        asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); // A(t+1) and B(t+1) have landed; the four B(t+2) pieces stay in flight
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        bs_cur = bs_cur == 2 ? 0 : bs_cur + 1;
+        bs_far = bs_far == 2 ? 0 : bs_far + 1;
+    }
+    __syncthreads();                   // the last look-ahead pieces have landed before the epilogue reuses the LDS
+    // the float tail: t = fmaf(float(acc_lo), 2^-7, float(acc_hi)), then t * s_q per accumulator row; the epilogue's
+    // acc * ginv[col] is the multiply by s_g.  (sq holds whole 128-row tiles: rows >= Q read 0.)
+    f32x16 acc[MT][2];
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const float s = sq[m0 + wm * MT * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)];
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+                acc[i][j][r] = __builtin_fmaf((float)acc_lo[i][j][r], 0x1p-7f, (float)acc_hi[i][j][r]) * s;
+        }
+    epi.tile(acc, smem, scales, TileCtx{Q, G, ntx, n0, m0});
+}
+template <int MT, int FK>
+__global__ __launch_bounds__(256) void k_cos_gemm_i8(const signed char* __restrict__ Qs, const float* __restrict__ sq,
+                                                     const signed char* __restrict__ Gal, const float* __restrict__ scales, int Q,
+                                                     i64 G, int ld, int x0, int ntx, int xtiles, int ny, PlainEpi<FK> epi) {
+    cos_gemm_i8_tile<MT>(Qs, sq, Gal, scales, Q, G, ld, x0, ntx, xtiles, ny, epi);
+}
+// Every other epilogue (filtered selection, range): the same loop
+template <int MT, class Epi>
+__global__ __launch_bounds__(256) void k_cos_gemm_i8_epi(const signed char* __restrict__ Qs, const float* __restrict__ sq,
+                                                         const signed char* __restrict__ Gal, const float* __restrict__ scales,
+                                                         int Q, i64 G, int ld, int x0, int ntx, int xtiles, int ny, Epi epi) {
+    cos_gemm_i8_tile<MT>(Qs, sq, Gal, scales, Q, G, ld, x0, ntx, xtiles, ny, epi);
+}
+
+// =====================================================================================
+// Few queries (Q <= 4, the one-query-at-a-time serving shape): a GEMV bound by streaming the gallery once (ld bytes per
+// row).  One wave per row, 16 bytes per lane per load, up to four loads in flight per lane; the queries' two int8 planes (the
+// ones the GEMM reads, taken out of their fragment order) sit in LDS as [NQ][hi, lo][ld].  Integer dot products, reduced over
+// the wave in integers, then the float tail of the GEMM: the same bits.
+// =====================================================================================
+template <int NQ>
+__global__ __launch_bounds__(256) void k_cos_gemv_i8(const signed char* __restrict__ Qs, const float* __restrict__ sq,
+                                                     const signed char* __restrict__ Gal, const float* __restrict__ scales,
+                                                     float* __restrict__ S, i64 G, int ld) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    i32x4* qs = reinterpret_cast<i32x4*>(smem);                  // [NQ][2][ld / 16] chunks
+    const int nch = ld / 16;                                     // 16-byte chunks per row
+    for (int i = threadIdx.x; i < NQ * 2 * nch; i += 256) {
+        const int q = i / (2 * nch), p = (i / nch) & 1, c = i % nch;
+        qs[i] = *reinterpret_cast<const i32x4*>(Qs + ((size_t)((c >> 1) * 2 + p) * 64 + (c & 1) * 32 + q) * 16);
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const i64 wave_id = (i64)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const i64 nwaves = (i64)gridDim.x * 4;
+    float s_q[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) s_q[q] = sq[q];
+    for (i64 g = wave_id; g < G; g += nwaves) {
+        const i32x4* row = reinterpret_cast<const i32x4*>(Gal + g * ld);
+        int hi[NQ], lo[NQ];
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) { hi[q] = 0; lo[q] = 0; }
+        for (int c0 = 0; c0 < nch; c0 += 4 * 64) {
+            i32x4 v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int c = c0 + u * 64 + lane;
+                v[u] = c < nch ? row[c] : (i32x4){0, 0, 0, 0};
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int c = c0 + u * 64 + lane;
+                if (c < nch) {
+#pragma unroll
+                    for (int q = 0; q < NQ; ++q) {
+                        const i32x4 h = qs[(q * 2) * nch + c], l = qs[(q * 2 + 1) * nch + c];
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            hi[q] = __builtin_amdgcn_sdot4(h[e], v[u][e], hi[q], false);
+                            lo[q] = __builtin_amdgcn_sdot4(l[e], v[u][e], lo[q], false);
+                        }
+                    }
+                }
+            }
+        }
+        const float s_g = scales[g];
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            int h = hi[q], l = lo[q];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) { h += __shfl_xor(h, o, 64); l += __shfl_xor(l, o, 64); }
+            if (lane == 0) S[(i64)q * G + g] = (__builtin_fmaf((float)l, 0x1p-7f, (float)h) * s_q[q]) * s_g;
+        }
+    }
+}
+
+// =====================================================================================
+// host drivers
+// =====================================================================================
+constexpr size_t I8_GEMV_LDS = 64 * 1024;
+
+// the planes of whole 128-row tiles, then s_q of those rows
+static size_t i8_planes_only(i64 Q, int ld) { return (size_t)cdiv(Q, 128) * 4 * (ld / 32) * 2048; }
+static size_t i8_planes_bytes(i64 Q, int D) { return i8_planes_only(Q, i8_ld(D)) + (size_t)cdiv(Q, 128) * 128 * sizeof(float); }
+static bool i8_gemv(i64 Q, int ld) { return Q <= 4 && (size_t)Q * 2 * ld <= I8_GEMV_LDS; }
+
+// The tiled GEMM over int8 rows (launch_tiles, rank_common.h); qry: the queries' planes and s_q behind them, gal: the codes,
+// ginv: the rows' scales, D: the rows' length ld
+struct I8Gemm {
+    template <int MT> static constexpr size_t stage_bytes() {   // A ring of 2, B ring of 3
+        return (size_t)2 * (64 * MT / 32) * 8 * 1024 + (size_t)3 * RK_BN * I8_KSTEP;
+    }
+    template <int MT, class Epi> static constexpr auto kernel() {
+        if constexpr (plain_fk<Epi> >= 0) return &k_cos_gemm_i8<MT, plain_fk<Epi>>;
+        else return &k_cos_gemm_i8_epi<MT, Epi>;
+    }
+    template <int MT, class Epi>
+    static void launch(dim3 grid, size_t lds, hipStream_t st, const TileArgs& a, const Epi& epi, int x0, int ntx, int xtiles, int ny) {
+        const signed char* qs = (const signed char*)a.qry;
+        const float* sq = reinterpret_cast<const float*>(qs + i8_planes_only(a.Q, a.D));
+        hipLaunchKernelGGL((kernel<MT, Epi>()), grid, dim3(256), lds, st, qs, sq, (const signed char*)a.gal, a.ginv, a.Q, a.G, a.D,
+                           x0, ntx, xtiles, ny, epi);
+    }
+};
+
+// qn [Q][dim] normalised -> planes and s_q in qs (i8_planes_bytes(Q, dim))
+static int split_queries_i8(const float* qn, void* qs, i64 Q, int dim, int ld, hipStream_t st) {
+    const int rows_pad = cdiv(Q, 128) * 128;
+    signed char* planes = (signed char*)qs;
+    hipLaunchKernelGGL(k_split_queries_i8, dim3((unsigned)cdiv(rows_pad, 4)), dim3(256), 0, st, qn, planes,
+                       reinterpret_cast<float*>(planes + i8_planes_only(Q, ld)), (int)Q, dim, ld / 32, rows_pad, vec_ok(qn, dim));
+    MI355_LAUNCH_CHECK();
+    return OK;
+}
+
+template <class Epi>
+int cos_gemm_i8(const void* codes, const float* scales, int ld, const float* qn, void* qs, i64 Q, i64 G, int dim, const Epi& epi,
+                hipStream_t st) {
+    set_rank_path(MI355_RANK_PATH_I8_GEMM | (is_select<Epi> ? MI355_RANK_PATH_FUSED : 0));
+    if (int e = split_queries_i8(qn, qs, Q, dim, ld, st)) return e;
+    return cos_gemm_tiles<I8Gemm>({qs, codes, scales, (int)Q, G, ld}, epi, st);
+}
+template int cos_gemm_i8(const void*, const float*, int, const float*, void*, i64, i64, int, const RangeArgs&, hipStream_t);
+
+static GalleryRows i8_rows(const void* codes, const float* scales, int dim) {
+    return {nullptr, true, nullptr, i8_ld(dim), i8_planes_bytes, codes, scales};
+}
+
+}  // namespace mi355
+
+using namespace mi355;
+
+extern "C" {
+
+size_t mi355_gallery_i8_bytes(int64_t G, int dim) {
+    if (G < 0 || dim < 1) return 0;
+    return (size_t)G * i8_ld(dim);
+}
+
+int mi355_gallery_to_i8(const float* rows, int64_t G, int dim, int rows_are_normalized, float eps, void* codes, size_t codes_bytes,
+                        float* scales, void* stream) {
+    MI355_REQUIRE(rows && codes && scales, "gallery_to_i8: null pointer");
+    MI355_REQUIRE(G >= 0 && dim >= 1, "gallery_to_i8: bad shape G=%lld dim=%d", (long long)G, dim);
+    MI355_REQUIRE(dim <= I8_MAX_DIM, "gallery_to_i8: dim=%d exceeds %d", dim, I8_MAX_DIM);
+    MI355_REQUIRE(((uintptr_t)codes & 15) == 0, "gallery_to_i8: output buffer must be 16-byte aligned");
+    MI355_REQUIRE(codes_bytes >= mi355_gallery_i8_bytes(G, dim), "gallery_to_i8: output buffer %zu < %zu bytes", codes_bytes,
+                  mi355_gallery_i8_bytes(G, dim));
+    if (G == 0) return OK;
+    hipLaunchKernelGGL(k_rows_to_i8, dim3((unsigned)cdiv(G, 4)), dim3(256), 0, (hipStream_t)stream, rows, (signed char*)codes, scales,
+                       (i64)G, dim, i8_ld(dim), eps, rows_are_normalized ? 0 : 1, vec_ok(rows, dim));
+    MI355_LAUNCH_CHECK();
+    return OK;
+}
+
+size_t mi355_rank_i8_workspace_bytes(int64_t Q, int64_t G, int dim, int k) {
+    if (Q < 1 || G < 1 || dim < 1 || dim > I8_MAX_DIM || k < 1 || k > LARGE_K) return 0;
+    return carve(nullptr, Q, G, dim, k, i8_planes_bytes, false).total;
+}
+
+}  // extern "C"
+
+// mi355_rank_topk_i8 and, with filt, mi355_rank_topk_i8_filtered: checks its arguments under the name who
+static int rank_topk_i8(const float* queries, int64_t Q, const void* codes, const float* scales, int64_t G, int dim, int k,
+                        float eps, int64_t idx_offset, float* out_val, int64_t* out_idx, void* workspace, size_t workspace_bytes,
+                        void* stream, const mi355_rank_filter* filter, const char* who) {
+    MI355_REQUIRE(queries && codes && scales && out_val && out_idx, "%s: null pointer", who);
+    MI355_REQUIRE(Q >= 0 && G >= 1 && dim >= 1, "%s: bad shape Q=%lld G=%lld dim=%d", who, (long long)Q, (long long)G, dim);
+    MI355_REQUIRE(dim <= I8_MAX_DIM, "%s: dim=%d exceeds %d", who, dim, I8_MAX_DIM);
+    MI355_REQUIRE(k >= 1 && k <= LARGE_K && k <= G, "%s: k=%d outside [1, %lld]", who, k,
+                  (long long)(G < LARGE_K ? G : LARGE_K));
+    MI355_REQUIRE(((uintptr_t)codes & 15) == 0, "%s: gallery buffer must be 16-byte aligned", who);
+    MI355_REQUIRE(Q <= INT_MAX && G <= ((int64_t)1 << 40), "%s: shape too large Q=%lld G=%lld", who, (long long)Q,
+                  (long long)G);
+    RankFilter fall{};
+    if (filter)
+        if (int e = make_filter(filter, idx_offset, who, &fall)) return e;
+    if (Q == 0) return OK;
+    const int ld = i8_ld(dim);
+    const bool gemv = i8_gemv(Q, ld);    // (Q <= 4: a single query block)
+    const RankWs w = carve(workspace, Q, G, dim, k, i8_planes_bytes, false);
+    MI355_REQUIRE(workspace && workspace_bytes >= w.total, "%s: workspace %zu < %zu bytes", who, workspace_bytes, w.total);
+    hipStream_t st = (hipStream_t)stream;
+    const signed char* gal = (const signed char*)codes;
+    return search_blocks(
+        queries, nullptr, Q, G, dim, k, eps, idx_offset, filter ? &fall : nullptr, out_val, (i64*)out_idx, w, st, "rank/top-k",
+        [&](i64 q0, i64 qn, const RankFilter* f) -> int {
+            if (gemv) {
+                RoctxRange range("rank/cosine gemv (int8 gallery)");
+                if (int e = split_queries_i8(w.qn, w.qs, qn, dim, ld, st)) return e;
+                const signed char* qs = (const signed char*)w.qs;
+                const float* sq = reinterpret_cast<const float*>(qs + i8_planes_only(qn, ld));
+                const size_t lds = (size_t)qn * 2 * ld;
+                const unsigned blocks = (unsigned)(cdiv(G, 4) < 4096 ? cdiv(G, 4) : 4096);
+#define GEMV_I8(NQ) hipLaunchKernelGGL((k_cos_gemv_i8<NQ>), dim3(blocks), dim3(256), lds, st, qs, sq, gal, scales, w.S, (i64)G, ld)
+                if (qn == 1) GEMV_I8(1); else if (qn == 2) GEMV_I8(2); else if (qn == 3) GEMV_I8(3); else GEMV_I8(4);
+#undef GEMV_I8
+                MI355_LAUNCH_CHECK();
+                set_rank_path(MI355_RANK_PATH_I8_GEMV);
+                return OK;
+            }
+            RoctxRange range(w.cand_val ? "rank/cosine gemm (int8 gallery) + per-tile top-k" : "rank/cosine gemm (int8 gallery)");
+            return with_topk_epi(w, k, f, [&](const auto& epi) {
+                return cos_gemm_i8(gal, scales, ld, w.qn + q0 * dim, w.qs, qn, G, dim, epi, st);
+            });
+        });
+}
+
+extern "C" {
+
+int mi355_rank_topk_i8(const float* queries, int64_t Q, const void* codes, const float* scales, int64_t G, int dim, int k, float eps,
+                       int64_t idx_offset, float* out_val, int64_t* out_idx, void* workspace, size_t workspace_bytes, void* stream) {
+    return rank_topk_i8(queries, Q, codes, scales, G, dim, k, eps, idx_offset, out_val, out_idx, workspace, workspace_bytes, stream,
+                        nullptr, "rank_topk_i8");
+}
+
+int mi355_rank_topk_i8_filtered(const float* queries, int64_t Q, const void* codes, const float* scales, int64_t G, int dim, int k,
+                                float eps, int64_t idx_offset, const mi355_rank_filter* filter, float* out_val, int64_t* out_idx,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+    MI355_REQUIRE(filter, "rank_topk_i8_filtered: null filter (use the unfiltered entry)");
+    return rank_topk_i8(queries, Q, codes, scales, G, dim, k, eps, idx_offset, out_val, out_idx, workspace, workspace_bytes, stream,
+                        filter, "rank_topk_i8_filtered");
+}
+
+size_t mi355_range_i8_workspace_bytes(int64_t Q, int64_t G, int dim) {
+    if (Q < 0 || G < 0 || dim < 1 || dim > I8_MAX_DIM) return 0;
+    return range_carve(nullptr, Q, G, dim, i8_planes_bytes, false).total;   // normalised queries + one call's planes + table
+}
+
+int mi355_cosine_range_i8(const float* queries, int64_t Q, const void* codes, const float* scales, int64_t G, int dim, float eps,
+                          double threshold, int64_t idx_offset, const mi355_rank_filter* filter, void* candidates, int64_t capacity,
+                          int64_t* nnz, void* workspace, size_t workspace_bytes, void* stream) {
+    MI355_REQUIRE(dim <= I8_MAX_DIM, "cosine_range_i8: dim=%d exceeds %d", dim, I8_MAX_DIM);
+    MI355_REQUIRE(scales || !codes, "cosine_range_i8: null queries/gallery pointer");
+    return cosine_range(queries, Q, i8_rows(codes, scales, dim), G, dim, eps, threshold, idx_offset, filter, candidates, capacity, nnz,
+                        workspace, workspace_bytes, stream, false, "cosine_range_i8");
+}
+
+}  // extern "C"

@@ -19,7 +19,8 @@ routes the arithmetic to libmi355_retrieval:
 The gallery side of every search is one ``_Rows`` (buffer, dtype, rows, dim, row stride, normalised or not, optional bf16
 planes): a tensor argument, a ``PreparedGallery``, a ``Gallery`` and a ``ShardedGallery`` shard all become one.  Top-k, range
 and ROC histogram are one function each (``_topk``, ``_range``, ``_roc_hist``) that checks the arguments once and picks the
-fp32 or fp16 C entry from ``_ENTRIES``; the public functions and methods are wrappers that add their own labels.
+fp32, fp16 or int8 C entry from ``_ENTRIES``; the public functions and methods are wrappers that add their own labels.  (int8 rows
+come from an ``Int8Gallery``, quantized.py, and have the top-k and range entries only.)
 """
 from __future__ import annotations
 
@@ -105,12 +106,15 @@ def _row_stride(t: torch.Tensor) -> int:
 
 
 class _Rows:
-    """The gallery side of a call: the first ``rows`` rows and ``dim`` columns of ``buf`` - fp32 rows, ``normalized`` or not, or
-    an fp16 gallery buffer (``mi355_gallery_to_f16`` layout: normalised rows, zero padding) - ``ld`` elements apart.
+    """The gallery side of a call: the first ``rows`` rows and ``dim`` columns of ``buf`` - fp32 rows, ``normalized`` or not, an
+    fp16 gallery buffer (``mi355_gallery_to_f16`` layout: normalised rows, zero padding) or the int8 codes of
+    ``mi355_gallery_to_i8`` with their ``scales`` - ``ld`` elements apart.
     ``planes``: the bf16 planes of the same rows (``PreparedGallery``); without ``buf`` they serve the searches they cover."""
 
-    def __init__(self, buf, rows: int, dim: int, normalized: bool, planes: torch.Tensor | None = None):
+    def __init__(self, buf, rows: int, dim: int, normalized: bool, planes: torch.Tensor | None = None,
+                 scales: torch.Tensor | None = None):
         self.buf, self.rows, self.dim, self.normalized, self.planes = buf, int(rows), int(dim), bool(normalized), planes
+        self.scales = scales
         self.shape = (self.rows, self.dim)
         self.dtype = torch.float32 if buf is None else buf.dtype
         self.device = planes.device if buf is None else buf.device
@@ -132,7 +136,10 @@ class _Rows:
         return self.buf[: self.rows, : self.dim]
 
     def c_args(self):
-        """The gallery arguments every search entry takes after (queries, Q): fp16 rows are normalised by their layout."""
+        """The gallery arguments every search entry takes after (queries, Q): fp16 and int8 rows are normalised by their
+        layout, int8 codes travel with their scales."""
+        if self.dtype == torch.int8:
+            return (self.buf.data_ptr(), self.scales.data_ptr(), self.rows, self.dim)
         norm = () if self.dtype == torch.float16 else (int(self.normalized),)
         return (self.buf.data_ptr(), self.rows, self.dim) + norm
 
@@ -149,6 +156,9 @@ _ENTRIES = {
                     "positives": ("mi355_positives_range_f16", "mi355_range_f16_workspace_bytes"),
                     "ranks": ("mi355_rank_positives_f16", "mi355_rank_positives_f16_workspace_bytes"),
                     "roc": ("mi355_roc_pairs_hist_f16", "mi355_roc_pairs_f16_workspace_bytes")},
+    # the int8 rows of an Int8Gallery (quantized.py): top-k and range search only
+    torch.int8: {"topk": ("mi355_rank_topk_i8", "mi355_rank_topk_i8_filtered", "mi355_rank_i8_workspace_bytes"),
+                 "range": ("mi355_cosine_range_i8", "mi355_range_i8_workspace_bytes")},
 }
 
 
@@ -687,6 +697,16 @@ class Gallery:
         self._prepared = PreparedGallery(self.data) if self.rows else None
         self._prepared_rows = self.rows
         return self
+
+    def quantized(self):
+        """An ``Int8Gallery`` (quantized.py) of the resident rows of an fp32 gallery: the rows are normalised already, so its
+        codes and scales are bit for bit those of ``Int8Gallery.add`` of the original embeddings.  Labels are copied."""
+        from .quantized import Int8Gallery
+        if self.dtype != torch.float32:
+            raise MI355Error("quantized() makes int8 codes of fp32 rows; quantise the embeddings with Int8Gallery.add instead")
+        out = Int8Gallery(self.dim, self.device, capacity=self.rows, eps=self.eps)
+        out._append(self.data, None if self.labels is None else self.labels.clone(), normalized=True)
+        return out
 
     def search(self, queries: torch.Tensor, k: int, idx_offset: int = 0, *, query_labels: torch.Tensor | None = None,
                label_filter: str | None = None, exclude: torch.Tensor | None = None, qe=None):

@@ -135,6 +135,8 @@ enum {
     MI355_RANK_PATH_PREPARED = 4,       /* k_cos_gemm_pre */
     MI355_RANK_PATH_F16_GEMM = 5,       /* k_cos_gemm_f16 */
     MI355_RANK_PATH_F16_GEMV = 6,       /* k_cos_gemv_f16 */
+    MI355_RANK_PATH_I8_GEMM = 7,        /* k_cos_gemm_i8 */
+    MI355_RANK_PATH_I8_GEMV = 8,        /* k_cos_gemv_i8: Q <= 4 */
     MI355_RANK_PATH_FUSED = 0x100,
     MI355_RANK_PATH_BITONIC = 0x200
 };
@@ -216,6 +218,44 @@ int mi355_cosine_range_f16(const float* queries, int64_t Q, const void* gallery_
                            void* workspace, size_t workspace_bytes, void* stream);
 int mi355_range_compact(const void* candidates, int64_t capacity, int64_t Q, int64_t nnz, int64_t idx_offset, const void* workspace,
                         size_t workspace_bytes, int64_t* offsets, int64_t* indices, float* scores, void* stream);
+
+/* 8-bit resident gallery (int8 codes and one fp32 scale per row: a quarter of the bytes of fp32 rows, half of fp16 rows).
+ * Below, "fp32" means one IEEE rounding per named operation.
+ * Row quantiser (gallery rows, and the hi plane of a query): n = the fp32 row mi355_l2_normalize_rows writes for x, bit for
+ * bit (rows_are_normalized != 0: n = x as it is); amax = max_i |n_i|.
+ *   - any n_i NaN, or amax not finite: scale = NaN, every code 0;
+ *   - else amax < 1e-30f: scale = 0, every code 0;
+ *   - else scale = amax / 127.0f, inv = 127.0f / amax (fp32 divisions), code_i = clamp(rintf(n_i * inv), -127, 127), rintf rounding
+ *     halves to even.
+ * codes: int8, row r at byte r * ld, ld = dim rounded up to a multiple of 128; bytes dim .. ld-1 are zero.  scales: fp32 [G].
+ * Both are appendable: converting n rows to codes + r * ld, scales + r writes rows r .. r+n-1.  codes must be 16-byte aligned;
+ * dim <= 65536.  mi355_gallery_i8_bytes(G, dim) = G * ld.
+ * Query planes, made per call from qn = l2_normalize_rows(q): (hi, s_q) = the row quantiser of qn; r_i = fmaf(-(float)hi_i, s_q,
+ * qn_i); lo_i = clamp(rintf(r_i * (128.0f / s_q)), -127, 127), |lo_i| <= 64 up to rounding, lo = 0 when s_q is 0 or NaN: the query
+ * keeps about 15 bits, its error is 1/256 of the gallery's.
+ * Score of query q against row g with codes c and scale s_g: acc_hi = sum_i hi_i c_i and acc_lo = sum_i lo_i c_i, exact in int32;
+ * t = fmaf((float)acc_lo, 0x1p-7f, (float)acc_hi) (the conversions round to nearest even); score = (t * s_q) * s_g, two fp32
+ * multiplies in that order.  A NaN row scores NaN (it ranks first, as in mi355_rank_topk), a zero row 0, a NaN query NaN
+ * everywhere.  The sums are integers, so EVERY path returns these bits for a (query, row) pair: the GEMV (Q <= 4), the tiled
+ * GEMM with 64- and 128-query tiles in its main and its tail launch, the fused selection and the score slab, the filtered and the
+ * unfiltered search, and the range search.  Order, ties, NaN and pads: the selection of mi355_rank_topk.
+ * The gallery argument of every entry is the pair (codes, scales).  Arguments are checked as for the _f16 entries (null, shape, k,
+ * alignment, workspace), and dim <= 65536.  workspace: mi355_rank_i8_workspace_bytes(Q, G, dim, k) (both top-k entries),
+ * mi355_range_i8_workspace_bytes(Q, G, dim); mi355_cosine_range_i8 is mi355_cosine_range_f16 over int8 rows (results read with
+ * mi355_range_compact). */
+size_t mi355_gallery_i8_bytes(int64_t G, int dim);
+int mi355_gallery_to_i8(const float* rows, int64_t G, int dim, int rows_are_normalized, float eps, void* codes, size_t codes_bytes,
+                        float* scales, void* stream);
+size_t mi355_rank_i8_workspace_bytes(int64_t Q, int64_t G, int dim, int k);
+int mi355_rank_topk_i8(const float* queries, int64_t Q, const void* codes, const float* scales, int64_t G, int dim, int k, float eps,
+                       int64_t idx_offset, float* out_val, int64_t* out_idx, void* workspace, size_t workspace_bytes, void* stream);
+int mi355_rank_topk_i8_filtered(const float* queries, int64_t Q, const void* codes, const float* scales, int64_t G, int dim, int k,
+                                float eps, int64_t idx_offset, const mi355_rank_filter* filter, float* out_val, int64_t* out_idx,
+                                void* workspace, size_t workspace_bytes, void* stream);
+size_t mi355_range_i8_workspace_bytes(int64_t Q, int64_t G, int dim);
+int mi355_cosine_range_i8(const float* queries, int64_t Q, const void* codes, const float* scales, int64_t G, int dim, float eps,
+                          double threshold, int64_t idx_offset, const mi355_rank_filter* filter, void* candidates, int64_t capacity,
+                          int64_t* nnz, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Full-gallery ranks: the 1-based rank of every POSITIVE of every query among the query's eligible rows, without a score slab
  * or a sort of the gallery.  Eligible for query q: every gallery row but exclude[q] - idx_offset (exclude may be NULL;
