@@ -45,6 +45,15 @@ class MbconvFrontArgs(C.Structure):
                 ("kernel", C.c_int), ("band_rows", C.c_int), ("sweep_variant", C.c_int), ("sweep_csplit", C.c_int)]
 
 
+class MbconvBlockArgs(C.Structure):
+    """mi355_mbconv_block_args (include/mi355_retrieval.h), the operand block of the developer entry mi355_mbconv_block_ex."""
+    _fields_ = [("X", vp), ("We", vp), ("be", vp), ("Wd", vp), ("bd", vp), ("W1", vp), ("b1", vp), ("W2", vp), ("b2", vp),
+                ("Wp", vp), ("bp", vp), ("D", vp), ("Y", vp),
+                ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("Cin", C.c_int), ("mid", C.c_int), ("Cout", C.c_int),
+                ("k", C.c_int), ("stride", C.c_int), ("rd", C.c_int), ("act_e", C.c_int), ("act_d", C.c_int),
+                ("se_act", C.c_int), ("a_relu6", C.c_int), ("has_res", C.c_int), ("res_n", C.c_int), ("norot", C.c_int)]
+
+
 class StemExArgs(C.Structure):
     """mi355_stem_ex_args (include/mi355_retrieval.h), the operand block of the developer entry mi355_stem_ex."""
     _fields_ = [("x", vp), ("images", vp), ("images_bytes", C.c_int64), ("desc_host", vp), ("desc_dev", vp),
@@ -210,6 +219,8 @@ PROTOTYPES = {
     "mi355_gemm_bf16_ex": (C.c_int, [vp, C.POINTER(C.c_int), vp]),
     "mi355_dwconv_se_ex": (C.c_int, [vp, C.POINTER(C.c_int), vp]),
     "mi355_mbconv_front_ex": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), vp]),
+    "mi355_mbconv_block_ex": (C.c_int, [vp, C.POINTER(C.c_int), vp]),
+    "mi355_mbconv_block_how": (C.c_int, [C.c_int] * 10 + [C.POINTER(C.c_int)]),
     "mi355_stem_ex": (C.c_int, [vp, C.POINTER(C.c_int), vp]),
     "mi355_head_gap_ex": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.POINTER(C.c_int), vp]),

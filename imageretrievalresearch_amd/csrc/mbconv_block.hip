@@ -27,6 +27,7 @@
 // What bounds it (tools/microbench_valu.hip): the vector issue port.  v_exp_f32 / v_rcp_f32 hold it for 8 cycles, plain
 // VALU for 4, a 16x16x32 MFMA for 8 of its 16; the two SiLUs per expanded element and the MFMA issue slots add up to
 // ~55 k cycles per 7x7 C1392 block per SIMD, the matrix pipe alone to ~40 k.
+#include "../../include/mi355_retrieval.h"
 #include "ops.h"
 
 namespace mi355 {
@@ -882,6 +883,15 @@ static int mb_pick_kcs(const BlockArgs& a) {
     return (per + q - 1) / q * q;
 }
 
+// SE FC2: slices of the hidden units per 8-channel chunk (the kernel's JS)
+static int mb_fc2_slices(int mid) {
+    const int nch = mid / 8;
+    int JS = MB_THREADS / nch;
+    if (JS > 8) JS = 8;
+    if (JS < 1) JS = 1;
+    return JS;
+}
+
 // LDS bytes for a given X row stride (elements); 0 = does not fit
 static size_t mb_lds_bytes_xld(const BlockArgs& a, int k, int xld, const MbGeom& g) {
     const int P = a.H * a.W, MT = (P + 15) / 16, pad = k / 2;
@@ -893,11 +903,7 @@ static size_t mb_lds_bytes_xld(const BlockArgs& a, int k, int xld, const MbGeom&
     const size_t fixed = xs + pl + MB_MAX_RD * 4;
     const size_t slab = (size_t)MB_WAVES * EP * 16 * 2;
     const int Pout = a.Ho * a.Wo;
-    const int nch = a.mid / 8;
-    int JS = MB_THREADS / nch;
-    if (JS > 8) JS = 8;
-    if (JS < 1) JS = 1;
-    const size_t se = (size_t)JS * a.mid * 4;
+    const size_t se = (size_t)mb_fc2_slices(a.mid) * a.mid * 4;
     const int kcs = mb_pick_kcs(a);
     if (!kcs) return 0;
     const int kc = g.wi == 7 ? 256 : 128, MTp = (Pout + 15) / 16;
@@ -949,11 +955,15 @@ bool mbconv_block_supported(int H, int W, int Cin, int mid, int Cout, int k, int
 }
 
 template <int KS, int S, int WI, int MW, int MH, int NTW, int MWP, int KST, int A_IT, int ACT_E, int ACT_D>
-static int launch_mb(BlockArgs a, int B, hipStream_t st) {
+static int launch_mb(BlockArgs a, int B, hipStream_t st, int* path, bool dry_run) {
     MbGeom g;
     mb_geom(a.H, a.W, &g);
     a.XLD = mb_pick_xld(a, KS, g);
     a.KCS = mb_pick_kcs(a);
+    if (path)
+        *path = MI355_BLOCK_PATH(KS, S, WI, KST, NTW, ACT_D, a.XLD == a.Kp + 16, WI == 7 && NTW == 2, (a.Kp2 + a.KCS - 1) / a.KCS,
+                                 mb_fc2_slices(a.mid));
+    if (dry_run) return OK;
     const size_t lds = mb_lds_bytes_xld(a, KS, a.XLD, g);
     static bool attr_done[64] = {false};     // per device: the attribute is a property of the loaded code object
     int dev = 0;
@@ -968,7 +978,7 @@ static int launch_mb(BlockArgs a, int B, hipStream_t st) {
     return OK;
 }
 
-int launch_mbconv_block(const BlockArgs& a, int B, int k, int stride, hipStream_t st) {
+int launch_mbconv_block(const BlockArgs& a, int B, int k, int stride, hipStream_t st, int* path, bool dry_run) {
     MI355_REQUIRE(mbconv_block_supported(a.H, a.W, a.Cin, a.mid, a.Cout, k, stride, a.rd, a.act_e, a.act_d), "mbconv_block: unsupported shape");
     const int Pout = a.Ho * a.Wo;
     MbGeom gg;
@@ -977,7 +987,7 @@ int launch_mbconv_block(const BlockArgs& a, int B, int k, int stride, hipStream_
     const int kst = a.Kp / 32;
 #define X(KS, S, WI, KST, NTW, AD)                                                                  \
     if (k == KS && stride == S && a.W == WI && kst == KST && ntw == NTW && a.act_d == AD)           \
-        return launch_mb<KS, S, WI, (WI == 7 ? 4 : 7), (WI == 7 ? 1 : 2), NTW, (WI == 7 ? 4 : 7), KST, (WI == 7 ? 4 : 7), ACT_SILU, AD>(a, B, st);
+        return launch_mb<KS, S, WI, (WI == 7 ? 4 : 7), (WI == 7 ? 1 : 2), NTW, (WI == 7 ? 4 : 7), KST, (WI == 7 ? 4 : 7), ACT_SILU, AD>(a, B, st, path, dry_run);
     MB_INSTANCES(X)
 #undef X
     set_error("mbconv_block: no instance for k=%d s=%d W=%d Kp=%d ntw=%d", k, stride, a.W, a.Kp, ntw);

@@ -1281,6 +1281,68 @@ int mi355_mbconv_front_ex(const mi355_mbconv_front_args* x, int* pool_nblk, int*
     return launch_fused_band(a, x->B, k, stride, st, path);
 }
 
+// the shape checks mi355_mbconv_block_ex and mi355_mbconv_block_how share (everything mbconv_block_supported takes for granted)
+static int block_shape_check(const char* who, int H, int W, int Cin, int mid, int Cout, int k, int stride, int rd, int act_e, int act_d) {
+    MI355_REQUIRE(H >= 1 && W >= 1 && H <= 16384 && W <= 16384 && Cin >= 8 && mid >= 8 && Cout >= 8 && Cin <= 32768 && mid <= 32768 &&
+                      Cout <= 32768 && rd >= 1 && rd <= 32768,
+                  "%s: bad shape H=%d W=%d Cin=%d mid=%d Cout=%d rd=%d", who, H, W, Cin, mid, Cout, rd);
+    MI355_REQUIRE(Cin % 8 == 0 && mid % 8 == 0 && Cout % 8 == 0, "%s: Cin=%d, mid=%d and Cout=%d must be multiples of 8", who, Cin, mid, Cout);
+    MI355_REQUIRE((k == 3 || k == 5) && (stride == 1 || stride == 2), "%s: unsupported k=%d stride=%d", who, k, stride);
+    MI355_REQUIRE(act_e >= ACT_NONE && act_e <= ACT_SIGMOID && act_d >= ACT_NONE && act_d <= ACT_SIGMOID, "%s: unknown activation %d / %d",
+                  who, act_e, act_d);
+    return OK;
+}
+
+// BlockArgs as exec_block fills them, from a shape
+static BlockArgs block_shape_args(int H, int W, int Cin, int mid, int Cout, int k, int stride, int rd, int act_e, int act_d) {
+    BlockArgs a{};
+    a.H = H; a.W = W; a.Cin = Cin; a.Kp = kpad32(Cin); a.mid = mid;
+    a.Ho = conv_out(H, k, stride); a.Wo = conv_out(W, k, stride); a.act_e = act_e; a.act_d = act_d;
+    a.Cout = Cout; a.Kp2 = kpad32(mid); a.rd = rd;
+    a.inv_hw = 1.0f / (float)(a.Ho * a.Wo);
+    return a;
+}
+
+int mi355_mbconv_block_how(int H, int W, int Cin, int mid, int Cout, int k, int stride, int rd, int act_e, int act_d, int* path) {
+    if (path) *path = 0;
+    if (int e = block_shape_check("mbconv_block_how", H, W, Cin, mid, Cout, k, stride, rd, act_e, act_d)) return e;
+    return launch_mbconv_block(block_shape_args(H, W, Cin, mid, Cout, k, stride, rd, act_e, act_d), 1, k, stride, nullptr, path, true);
+}
+
+int mi355_mbconv_block_ex(const mi355_mbconv_block_args* x, int* path, void* stream) {
+    if (path) *path = 0;
+    MI355_REQUIRE(x, "mbconv_block_ex: null argument block");
+    MI355_REQUIRE(x->X && x->We && x->be && x->Wd && x->bd && x->W1 && x->b1 && x->W2 && x->b2 && x->Wp && x->bp && x->D && x->Y,
+                  "mbconv_block_ex: null pointer");
+    MI355_REQUIRE(x->B >= 1 && x->B <= 65535, "mbconv_block_ex: bad shape B=%d", x->B);
+    if (int e = block_shape_check("mbconv_block_ex", x->H, x->W, x->Cin, x->mid, x->Cout, x->k, x->stride, x->rd, x->act_e, x->act_d))
+        return e;
+    MI355_REQUIRE(x->se_act >= ACT_NONE && x->se_act <= ACT_SIGMOID, "mbconv_block_ex: unknown SE activation %d", x->se_act);
+    MI355_REQUIRE((x->a_relu6 == 0 || x->a_relu6 == 1) && (x->has_res == 0 || x->has_res == 1),
+                  "mbconv_block_ex: a_relu6=%d and has_res=%d are flags (0 / 1)", x->a_relu6, x->has_res);
+    if (x->has_res) {
+        MI355_REQUIRE(x->stride == 1, "mbconv_block_ex: a residual needs stride 1");
+        MI355_REQUIRE(x->res_n >= 8 && x->res_n % 8 == 0 && x->res_n <= std::min(x->Cin, x->Cout),
+                      "mbconv_block_ex: res_n=%d must be a multiple of 8 in 8 .. min(Cin, Cout) = %d", x->res_n, std::min(x->Cin, x->Cout));
+    } else {
+        MI355_REQUIRE(x->res_n == 0, "mbconv_block_ex: res_n=%d without a residual", x->res_n);
+    }
+    MI355_REQUIRE(x->norot >= 0 && x->norot <= 15, "mbconv_block_ex: norot=%d out of range 0..15", x->norot);
+    for (const void* p : {x->X, x->We, (const void*)x->be, x->Wd, (const void*)x->bd, x->W1, (const void*)x->b1, x->W2, (const void*)x->b2,
+                          x->Wp, (const void*)x->bp, (const void*)x->D, (const void*)x->Y})
+        MI355_REQUIRE((uintptr_t)p % 16 == 0, "mbconv_block_ex: pointers must be 16-byte aligned");
+    MI355_REQUIRE(mbconv_block_supported(x->H, x->W, x->Cin, x->mid, x->Cout, x->k, x->stride, x->rd, x->act_e, x->act_d),
+                  "mbconv_block_ex: unsupported shape H=%d W=%d Cin=%d mid=%d Cout=%d k=%d stride=%d rd=%d act %d / %d", x->H, x->W, x->Cin,
+                  x->mid, x->Cout, x->k, x->stride, x->rd, x->act_e, x->act_d);
+    BlockArgs a = block_shape_args(x->H, x->W, x->Cin, x->mid, x->Cout, x->k, x->stride, x->rd, x->act_e, x->act_d);
+    a.X = (const bf16_t*)x->X; a.We = (const bf16_t*)x->We; a.be = x->be; a.Wd = (const bf16_t*)x->Wd; a.bd = x->bd;
+    a.W1 = (const bf16_t*)x->W1; a.b1 = x->b1; a.W2 = (const bf16_t*)x->W2; a.b2 = x->b2; a.Wp = (const bf16_t*)x->Wp; a.bp = x->bp;
+    a.D = (bf16_t*)x->D; a.Y = (bf16_t*)x->Y;
+    a.has_res = x->has_res; a.res_n = x->res_n; a.a_relu6 = x->a_relu6; a.se_act = x->se_act;
+    a.norot = x->norot;             // variant = 0, stamps = null: no phase is skipped, nothing is timed
+    return launch_mbconv_block(a, x->B, x->k, x->stride, (hipStream_t)stream, path);
+}
+
 int mi355_stem_ex(const mi355_stem_ex_args* x, int* path, void* stream) {
     if (path) *path = 0;
     MI355_REQUIRE(x, "stem_ex: null argument block");

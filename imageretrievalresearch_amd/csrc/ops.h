@@ -93,7 +93,9 @@ struct BlockArgs {
     int XLD;                              // LDS row stride of the X image (set by the launcher)
     int KCS;                              // k per staged super-chunk of the projection's A operand (set by the launcher)
     int norot;                            // diagnosis: bit0 slabs, bit1 SE FC1, bit2 SE FC2, bit3 projection columns NOT rotated by image
-    int variant;                          // tuning (option "block_variant"): bit0 = the round-2 14x14 geometry (two waves share a channel tile, barriers per slab)
+    int variant;                          // diagnosis only (option "block_variant"): every bit SKIPS a phase and the results are garbage -
+                                          // bit0 expand, bit1 depthwise, bit2 SE FCs, bit3 the projection's K loop, bit4 the slab loop's
+                                          // weight requests.  0 in every run that is meant to compute something.
     int has_res;
     int res_n;                            // the residual covers output channels [0, res_n) (rexnet: the block's input channels)
     int a_relu6;                          // ReLU6 between the SE gate and the projection (rexnet)
@@ -101,7 +103,9 @@ struct BlockArgs {
     float inv_hw;
 };
 bool mbconv_block_supported(int H, int W, int Cin, int mid, int Cout, int k, int stride, int rd, int act_e, int act_d);
-int launch_mbconv_block(const BlockArgs& a, int B, int k, int stride, hipStream_t st);
+// path (may be null): MI355_BLOCK_PATH(...) of the instantiation and of the launcher's run-time choices; dry_run: report the path (or
+// the "unsupported" error) from the shape fields alone, without any HIP call
+int launch_mbconv_block(const BlockArgs& a, int B, int k, int stride, hipStream_t st, int* path = nullptr, bool dry_run = false);
 
 // ---- convolution-side kernels (conv_kernels.hip) -----------------------------------------------
 // Stem: x [B][3][H][W] fp32 NCHW -> out [B][Ho][Wo][Cout] bf16, 3x3 stride 2 pad 1, + bias + act.

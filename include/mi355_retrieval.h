@@ -845,6 +845,48 @@ enum {
 
 int mi355_mbconv_front_ex(const mi355_mbconv_front_args* args, int* pool_nblk, int* path, void* stream);
 
+/* Developer entry: one whole MBConv / RexNet block of a 14-wide or 7-wide map in ONE launch of k_mbconv_block
+ * (csrc/mbconv_block.hip), through the model's launcher and with the operand layouts the model's executor passes.
+ *   E, v, D as for mi355_mbconv_front_ex (act_e must be SiLU);  s[b][n] = (1 / (Ho Wo)) sum over oy, ox of the un-rounded v
+ *   r[b][j] = se_act( sum_n W1[j][n] s[b][n] + b1[j] ),  g[b][n] = sigmoid( sum_j W2[j][n] r[b][j] + b2[n] )       (fp32)
+ *   A[b][p][n] = bf16( relu6?( D[b][p][n] g[b][n] ) )                                       (ReLU6 when a_relu6)
+ *   Y[b][p][o] = bf16( sum_n A[b][p][n] Wp[o][n] + bp[o] + (has_res && o < res_n ? X[b][p][o] : 0) )
+ * X [B][H][W][Cin] bf16 NHWC; We [ceil16(mid)][ceil32(Cin)] bf16 zero padded, be [ceil16(mid)] fp32; Wd [k*k][mid] bf16, bd [mid]
+ * fp32; W1 and W2 [rd][mid] bf16 (W2 transposed), b1 [rd], b2 [mid] fp32; Wp [ceil16(Cout)][ceil32(mid)] bf16 zero padded, bp
+ * [ceil16(Cout)] fp32; D [B][Ho Wo][mid] bf16 (the kernel's scratch: the depthwise output, readable afterwards); Y [B][Ho][Wo][Cout]
+ * bf16.  All 16-byte aligned device pointers.  Cin, mid, Cout multiples of 8; has_res needs stride 1 and res_n a multiple of 8 in
+ * 8 .. min(Cin, Cout), otherwise res_n = 0; norot 0..15: bit0 slabs, bit1 SE FC1 groups, bit2 SE FC2 chunks, bit3 projection
+ * columns are NOT rotated by image (the bits of the result do not depend on it).  Shapes the kernel does not take (the model
+ * then runs the unfused chain) are rejected.  path (host, may be NULL) receives MI355_BLOCK_PATH(...): the instantiation that
+ * ran and the launcher's run-time choices.  Every argument is checked before any HIP call.  Does not synchronise.
+ * mi355_mbconv_block_how: the same path (or the same "unsupported" error) from the shape alone; touches no device. */
+typedef struct mi355_mbconv_block_args {
+    const void* X; const void* We; const float* be; const void* Wd; const float* bd;
+    const void* W1; const float* b1; const void* W2; const float* b2; const void* Wp; const float* bp;
+    void* D; void* Y;
+    int B, H, W, Cin, mid, Cout, k, stride, rd, act_e, act_d, se_act, a_relu6, has_res, res_n, norot;
+} mi355_mbconv_block_args;
+
+/* instantiation: depthwise k (3 / 5), stride, map width WI (7 / 14), KST expand k-steps, NTW projection column tiles per wave, ACT_D
+ * depthwise activation; run time: xwide = X rows Kp + 16 apart in the LDS (0: the compact ceil8(Cin) + 8), whole = the projection
+ * stages whole super-chunks (PROJ_WHOLE; 0: double-buffered K chunks), nsc = super-chunks of the projection's K, js = SE FC2 slices */
+#define MI355_BLOCK_PATH(ks, s, wi, kst, ntw, act_d, xwide, whole, nsc, js)                                                      \
+    (((ks) == 5) | ((s) == 2) << 1 | ((wi) == 14) << 2 | (kst) << 3 | (ntw) << 7 | (act_d) << 10 | ((xwide) != 0) << 13 |      \
+     ((whole) != 0) << 14 | (nsc) << 15 | (js) << 20)
+#define MI355_BLOCK_PATH_KS(p) (((p) & 1) ? 5 : 3)
+#define MI355_BLOCK_PATH_S(p) (((p) >> 1 & 1) ? 2 : 1)
+#define MI355_BLOCK_PATH_WI(p) (((p) >> 2 & 1) ? 14 : 7)
+#define MI355_BLOCK_PATH_KST(p) (((p) >> 3) & 15)
+#define MI355_BLOCK_PATH_NTW(p) (((p) >> 7) & 7)
+#define MI355_BLOCK_PATH_ACT_D(p) (((p) >> 10) & 7)
+#define MI355_BLOCK_PATH_XWIDE(p) (((p) >> 13) & 1)
+#define MI355_BLOCK_PATH_WHOLE(p) (((p) >> 14) & 1)
+#define MI355_BLOCK_PATH_NSC(p) (((p) >> 15) & 31)
+#define MI355_BLOCK_PATH_JS(p) (((p) >> 20) & 15)
+
+int mi355_mbconv_block_ex(const mi355_mbconv_block_args* args, int* path, void* stream);
+int mi355_mbconv_block_how(int H, int W, int Cin, int mid, int Cout, int k, int stride, int rd, int act_e, int act_d, int* path);
+
 /* Developer entry: one stem call of the convolutional backbones (3x3 stride 2 pad 1, 3 -> Cout, + bias + act) through the
  * model's launchers, in either input form.  Exactly one of x and images is non-null.
  *   out[b][oy][ox][co] = bf16( act( bias[co] + sum_{ky,kx,ci} in[b][ci][2 oy - 1 + ky][2 ox - 1 + kx] w[(ky*3 + kx)*3 + ci][co] ) )

@@ -1,5 +1,6 @@
-"""The developer entries mi355_window_attention, mi355_gemm_bf16_ex, mi355_dwconv_se_ex and mi355_mbconv_front_ex, the parts that need no
-GPU: the C-ABI symbols and every argument check (rejected before any HIP call, with a message)."""
+"""The developer entries mi355_window_attention, mi355_gemm_bf16_ex, mi355_dwconv_se_ex, mi355_mbconv_front_ex and mi355_mbconv_block_ex
+(with mi355_mbconv_block_how), the parts that need no GPU: the C-ABI symbols and every argument check (rejected before any HIP call,
+with a message)."""
 import ctypes
 
 import pytest
@@ -7,7 +8,8 @@ import pytest
 from helpers import header_symbols
 from imageretrievalresearch_amd import _lib
 
-NEW = ["mi355_window_attention", "mi355_gemm_bf16_ex", "mi355_dwconv_se_ex", "mi355_mbconv_front_ex"]
+NEW = ["mi355_window_attention", "mi355_gemm_bf16_ex", "mi355_dwconv_se_ex", "mi355_mbconv_front_ex", "mi355_mbconv_block_ex",
+       "mi355_mbconv_block_how"]
 P = 1 << 20          # a 16-byte aligned stand-in pointer: nothing is dereferenced when a check fails
 
 
@@ -249,3 +251,106 @@ def test_mbconv_front_args_layout_matches_the_header():
     F = _lib.MbconvFrontArgs
     assert ctypes.sizeof(F) == 112
     assert (F.pool.offset, F.B.offset, F.act_d.offset, F.kernel.offset, F.sweep_csplit.offset) == (48, 56, 88, 92, 104)
+
+
+def _block_ok():
+    """A valid operand block (B = 3, 14x14, 96 -> 576 -> 96, 3x3 stride 1, rd 24, SiLU / SiLU, residual on every column: efficientnet_b3a's
+    first whole-block shape) with stand-in pointers."""
+    return dict(X=P, We=P, be=P, Wd=P, bd=P, W1=P, b1=P, W2=P, b2=P, Wp=P, bp=P, D=P, Y=P, B=3, H=14, W=14, Cin=96, mid=576, Cout=96, k=3,
+                stride=1, rd=24, act_e=1, act_d=1, se_act=1, a_relu6=0, has_res=1, res_n=96, norot=0)
+
+
+_NO_RES = dict(has_res=0, res_n=0)
+
+
+@pytest.mark.parametrize("change,msg", [
+    *[(dict([(p, None)]), b"null") for p in ("X", "We", "be", "Wd", "bd", "W1", "b1", "W2", "b2", "Wp", "bp", "D", "Y")],
+    (dict(B=0), b"bad shape"),
+    (dict(B=65536), b"bad shape"),
+    (dict(H=0), b"bad shape"),
+    (dict(W=-1), b"bad shape"),
+    (dict(W=20000), b"bad shape"),
+    (dict(Cin=0), b"bad shape"),
+    (dict(mid=0), b"bad shape"),
+    (dict(mid=40000), b"bad shape"),
+    (dict(Cout=0), b"bad shape"),
+    (dict(rd=0), b"bad shape"),
+    (dict(rd=-3), b"bad shape"),
+    (dict(Cin=100), b"multiples of 8"),
+    (dict(mid=580), b"multiples of 8"),
+    (dict(Cout=100), b"multiples of 8"),
+    (dict(k=7), b"unsupported k"),
+    (dict(k=1), b"unsupported k"),
+    (dict(stride=3), b"unsupported k"),
+    (dict(stride=0), b"unsupported k"),
+    (dict(act_e=6), b"activation"),
+    (dict(act_d=-1), b"activation"),
+    (dict(se_act=6), b"SE activation"),
+    (dict(se_act=-1), b"SE activation"),
+    (dict(a_relu6=2), b"flags"),
+    (dict(has_res=-1), b"flags"),
+    (dict(_NO_RES, Cin=136, mid=816, Cout=232, k=5, stride=2, rd=34, has_res=1, res_n=136), b"stride 1"),
+    (dict(res_n=0), b"res_n"),
+    (dict(res_n=100), b"res_n"),
+    (dict(res_n=104), b"res_n"),                                       # past min(Cin, Cout)
+    (dict(Cout=136, res_n=104), b"res_n"),                             # past Cin
+    (dict(res_n=-8), b"res_n"),
+    (dict(has_res=0), b"without a residual"),
+    (dict(norot=16), b"norot"),
+    (dict(norot=-1), b"norot"),
+    *[(dict([(p, P + off)]), b"16-byte aligned") for p, off in (("X", 8), ("We", 2), ("be", 4), ("Wd", 8), ("bd", 4), ("W1", 8), ("b1", 4),
+                                                                 ("W2", 2), ("b2", 8), ("Wp", 8), ("bp", 4), ("D", 2), ("Y", 8))],
+    (dict(H=15), b"unsupported shape"),                                # 210 pixels
+    (dict(H=7, W=7), b"unsupported shape"),                            # no 7x7 instance with three k-steps
+    (dict(_NO_RES, H=7, W=7, Cin=232, mid=1392, Cout=232, k=5, stride=2, rd=58), b"unsupported shape"),      # no stride 2 on 7x7
+    (dict(act_e=0), b"unsupported shape"),                             # the expand activation is SiLU
+    (dict(act_d=2), b"unsupported shape"),
+    (dict(mid=2568), b"unsupported shape"),
+    (dict(rd=193), b"unsupported shape"),
+    (dict(_NO_RES, Cout=520), b"unsupported shape"),                   # more than 8 waves x 4 column tiles
+    (dict(_NO_RES, k=5, Cin=128, mid=768), b"unsupported shape"),      # no 5x5 14x14 instance with four k-steps
+])
+def test_mbconv_block_ex_argument_errors(change, msg):
+    a = _block_ok()
+    a.update(change)
+    x = _lib.MbconvBlockArgs(**a)
+    path = ctypes.c_int(-1)
+    assert _lib.lib().mi355_mbconv_block_ex(ctypes.byref(x), ctypes.byref(path), None) != 0
+    assert msg in _err(), _err()
+    assert path.value == 0                                # a rejected call reports no kernel
+
+
+def test_mbconv_block_ex_null_block():
+    assert _lib.lib().mi355_mbconv_block_ex(None, None, None) != 0
+    assert b"null" in _err()
+
+
+@pytest.mark.parametrize("shape,msg", [
+    ((0, 14, 96, 576, 96, 3, 1, 24, 1, 1), b"bad shape"),
+    ((14, 14, 96, 576, 96, 3, 1, 0, 1, 1), b"bad shape"),
+    ((14, 14, 100, 576, 96, 3, 1, 24, 1, 1), b"multiples of 8"),
+    ((14, 14, 96, 576, 96, 4, 1, 24, 1, 1), b"unsupported k"),
+    ((14, 14, 96, 576, 96, 3, 1, 24, 7, 1), b"activation"),
+    ((14, 14, 96, 576, 96, 3, 1, 24, 1, 0), b"unsupported shape"),     # no linear-depthwise instance with three k-steps
+    ((14, 15, 96, 576, 96, 3, 1, 24, 1, 1), b"unsupported shape"),
+])
+def test_mbconv_block_how_argument_errors(shape, msg):
+    path = ctypes.c_int(-1)
+    assert _lib.lib().mi355_mbconv_block_how(*shape, ctypes.byref(path)) != 0
+    assert msg in _err(), _err()
+    assert path.value == 0
+    assert _lib.lib().mi355_mbconv_block_how(*shape, None) != 0
+
+
+def test_mbconv_block_how_reports_a_path_without_a_device():
+    path = ctypes.c_int(-1)
+    assert _lib.lib().mi355_mbconv_block_how(14, 14, 96, 576, 96, 3, 1, 24, 1, 1, ctypes.byref(path)) == 0
+    assert path.value > 0
+    assert _lib.lib().mi355_mbconv_block_how(14, 14, 96, 576, 96, 3, 1, 24, 1, 1, None) == 0
+
+
+def test_mbconv_block_args_layout_matches_the_header():
+    F = _lib.MbconvBlockArgs
+    assert ctypes.sizeof(F) == 168
+    assert (F.bp.offset, F.D.offset, F.Y.offset, F.B.offset, F.Cout.offset, F.act_e.offset, F.res_n.offset, F.norot.offset) == \
+        (80, 88, 96, 104, 124, 140, 160, 164)
