@@ -15,10 +15,18 @@
 // Because a workgroup sees every pixel of its channels, the squeeze sums are complete (no partials in HBM), the slab's
 // expand and depthwise weights are loaded once into registers and stay there for the whole sweep, and the LDS need is one
 // row buffer of <= ~55 KB: two or three workgroups share a CU and hide each other's barriers and L2 latency.
+// Slab pipeline: a workgroup walks its 3-9 slabs without a barrier or an exposed load between them.
+//   constants  the NEXT slab's weights and biases are staged in the LDS by LDS-DMA (no register) while this slab runs, and
+//              picked up with a few LDS reads at the slab switch; with the X prefetch the next slab's band -1 X fragments
+//              are requested in front of the last depthwise phase and retired by a counted wait that skips the D stores
+//   E buffers  each slab starts in the buffer its predecessor's last band did NOT read, so no barrier separates them
+//   squeeze    every slab parks its per-wave sums in its own LDS slot; one barrier and one fold per workgroup at the end
+//              (same lane fold, same wave order w = 0 .. NW-1: the sums keep their bits)
 // Stride 2: the row buffer keeps even and odd columns in separate planes, so 16 consecutive output pixels read 16
 // consecutive LDS pixels for every tap (a stride-2 walk over 48-byte pixels would be a 2-way bank conflict).
 #include "../../include/mi355_retrieval.h"
 #include "ops.h"
+#include <type_traits>
 
 namespace mi355 {
 
@@ -31,6 +39,31 @@ __device__ __forceinline__ void sw_lds_barrier() {          // orders LDS traffi
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
+}
+
+// LDS-DMA, 16 or 4 bytes per lane: lane l's bytes at gsrc land at LDS byte address lds_dst (wave-uniform, below 64 KB) + l * size.
+// No register is written, so nothing of it is live while it travels; hipcc does not see it either: the issuing wave waits for
+// it with its own s_waitcnt vmcnt, and a barrier behind that wait publishes the data to the other waves.  M0 (the destination
+// base) is written in the statement that reads it and put back.
+__device__ __forceinline__ void sw_dma16(const void* gsrc, unsigned lds_dst) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
+}
+__device__ __forceinline__ void sw_dma4(const void* gsrc, unsigned lds_dst) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
+}
+
+// s_waitcnt vmcnt(min(n, N)): n (wave-uniform) vector-memory instructions younger than the data waited for stay in flight
+template <int N>
+__device__ __forceinline__ void sw_wait_vm_leaving(int n) {
+    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    else {
+        if (n >= N) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+        else sw_wait_vm_leaving<N - 1>(n);
+    }
 }
 
 typedef __bf16 sw_bf16x2 __attribute__((ext_vector_type(2)));
@@ -80,7 +113,14 @@ struct SwGeom {
     static constexpr int WO = (WI + 2 * PAD - KS) / S + 1;
     static constexpr int ELD = 24;                            // 16 channels + 8: 16 pixels x 16 B land on distinct banks
     static constexpr int EBUF = (IH + 1) * RP * ELD;          // elements per buffer (+ one zero slack row: unused second taps)
-    static constexpr size_t lds_bytes(int nw, int ns = 1) { return (size_t)ns * 2 * EBUF * 2 + (size_t)nw * 16 * ns * 4; }
+    // staged slab constants of one channel tile: the expand weights in fragment order (1 KB per k-step), 64 B of each bias, the
+    // taps as [tap][16 channels] in whole 256-byte DMA pieces
+    static constexpr int NWD = (KS * KS * 8 + 63) / 64;
+    static constexpr int cst_bytes(int kst) { return kst * 1024 + 128 + NWD * 256; }
+    // two sets of staged constants (this slab's and the next one's) + two E buffers per tile + one [NW][16 NS] slot of squeeze partials per slab a workgroup walks
+    static constexpr size_t lds_bytes(int nw, int ns, int kst, int nwalk) {
+        return (size_t)2 * ns * cst_bytes(kst) + (size_t)ns * 2 * EBUF * 2 + (size_t)nwalk * nw * 16 * ns * 4;
+    }
     __host__ __device__ static constexpr int epx(int r, int c) {   // E pixel index of (buffer row, padded column)
         return r * RP + (S == 1 ? c : (c & 1) * EWH + (c >> 1));
     }
@@ -107,12 +147,14 @@ __global__ __launch_bounds__(NW * 64, (NW * OCC + 3) / 4) void k_sweep_mbconv(co
     constexpr int NPX2 = TH * WO, NT2 = (NPX2 + 15) / 16, MW2 = (NT2 + NW - 1) / NW;     // depthwise
     constexpr int EBUF = G::EBUF;
     extern __shared__ __attribute__((aligned(16))) unsigned char sw_smem[];
-    bf16_t* Es = reinterpret_cast<bf16_t*>(sw_smem);                                  // [NS][2][EBUF]
-    float* red = reinterpret_cast<float*>(sw_smem + (size_t)NS * 2 * EBUF * 2);       // [NW][16 NS]
+    constexpr int NWD = G::NWD, CST = G::cst_bytes(KST);
+    const unsigned char* cst = sw_smem;                                               // [2][NS][CST] staged slab constants (first: the DMA base stays below 64 KB)
+    bf16_t* Es = reinterpret_cast<bf16_t*>(sw_smem + 2 * NS * CST);                   // [NS][2][EBUF]
+    float* red = reinterpret_cast<float*>(sw_smem + 2 * NS * CST + (size_t)NS * 2 * EBUF * 2);   // [slabs walked][NW][16 NS]
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int fr = lane & 15, fq = lane >> 4, fk = fq * 8;
+    const int fr = lane & 15, fq = lane >> 4;
     // XCD-aware placement (workgroups are dealt round-robin over the 8 XCDs): the workgroups of one image are consecutive on
     // ONE XCD, so the image's X rows are fetched into one L2 once and re-read from there by the other slabs
     const int xcd = blockIdx.x & 7, seq = blockIdx.x >> 3;
@@ -130,6 +172,75 @@ __global__ __launch_bounds__(NW * 64, (NW * OCC + 3) / 4) void k_sweep_mbconv(co
     auto tick = [&](int i) {
         if (stamping) { const long long t = (long long)__builtin_readcyclecounter(); t_acc[i] += t - t_last; t_last = t; }
     };
+
+    const bf16_t* xb = a.X + (size_t)b * a.H * WI * a.Cin;
+    bf16_t* Db = a.D + (size_t)b * a.Ho * WO * a.mid;
+    const int hw1 = a.H * WI - 1;
+    const int kclamp = a.Cin - 8;
+
+    // X fragments of one band straight from global (L2) in MFMA layout; the band's new rows are contiguous in memory, so the
+    // pixel index is just first-row * WI + p.  Rows outside the image are clamped (their results are replaced by zeros);
+    // k >= Cin re-reads valid data that meets zero weight columns.
+    u32x4 xa[MW1][KST];
+    auto load_x_of = [&](int band, auto first) {
+        constexpr bool FIRST = decltype(first)::value;
+        const int pix0 = (band * NEWR - PAD + HALO) * WI;
+        int l = lane;                                         // (band -1, once per slab: its addresses do not change from slab to slab,
+        if constexpr (FIRST) asm volatile("" : "+v"(l));      //  and hipcc would keep them in registers from the first to the last)
+        const int lr = l & 15, lk = (l >> 4) * 8;
+#pragma unroll
+        for (int i = 0; i < MW1; ++i) {
+            const int pix = min(max(pix0 + (wave + NW * i) * 16 + lr, 0), hw1);
+#pragma unroll
+            for (int ks = 0; ks < KST; ++ks) {
+                u32x4 t = {0u, 0u, 0u, 0u};
+                if (!(a.debug_skip & 4)) t = *reinterpret_cast<const u32x4*>(xb + pix * a.Cin + min(ks * 32 + lk, kclamp));
+                xa[i][ks] = t;
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    };
+
+    // ---- slab constants: expand weights (MFMA A fragments) + bias, depthwise taps of this lane's channel + bias.  They are
+    // staged ONE SLAB AHEAD in the LDS by LDS-DMA: the last wave requests them (the first slab's here, in front of the LDS
+    // zero-fill; every later slab's at the top of its predecessor, into the other of two staging sets - last read
+    // at the top of the slab before that, many barriers back), waits for them in front of the last band's barrier, which every wave passes anyway, and
+    // at the slab switch each wave picks its fragments up with a handful of LDS reads.  No slab starts with
+    // an exposed L2 round trip and no register is live while the constants travel (a second register set spilled everywhere:
+    // the kernel sits at its 128-VGPR budget).  Per tile: [KST][64 lanes][16 B] We fragments - the DMA's per-lane source is
+    // the address the fragment load would have used, so the LDS image is in fragment order - then be and bd of the 16 channels,
+    // then Wd as [tap][16 channels].  Channels past mid / midp are clamped to valid memory exactly as the loads were.
+    auto ch0_of = [&](int si) { return ((si + b) % nslab) * (16 * NS); };   // first channel of pass si; tile s covers ch0 + 16 s ...
+    const unsigned cst_lds = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)sw_smem;
+    auto stage_consts = [&](int ch0, int set) {               // (one wave calls this)
+        // (the lane number through an empty asm: hipcc otherwise hoists every per-lane address below out of the band and slab loops
+        //  and keeps it in registers for the whole kernel - 15 to 20 VGPRs at a 128-VGPR budget)
+        int l = lane;
+        asm volatile("" : "+v"(l));
+        const int lr = l & 15, lk = (l >> 4) * 8;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            const int c0 = ch0 + 16 * s;
+            const unsigned dst = cst_lds + (set * NS + s) * CST;
+            const int n = min(c0 + lr, midp - 1);
+#pragma unroll
+            for (int ks = 0; ks < KST; ++ks) sw_dma16(a.We + (n * a.Kp + ks * 32 + lk), dst + ks * 1024);
+            if (l < 8) {                                      // lanes 0-3: be, four channels each; lanes 4-7: bd
+                const int q = l & 3;
+                const float* src = l < 4 ? a.be + min(c0 + q * 4, midp - 4) : a.bd + min(c0 + q * 4, a.mid - 4);
+                sw_dma16(src, dst + KST * 1024);
+            }
+#pragma unroll
+            for (int j = 0; j < NWD; ++j) {                   // lane l: tap 8 j + l / 8 (clamped: the spare lanes fill padding), channel pair l % 8
+                const int t = min(j * 8 + (l >> 3), KS * KS - 1);
+                sw_dma4(a.Wd + (t * a.mid + min(c0 + 2 * (l & 7), a.mid - 2)), dst + KST * 1024 + 128 + j * 256);
+            }
+        }
+    };
+    u32x4 wf[NS][KST];
+    f32x4 bb[NS];
+    if (wave == NW - 1) stage_consts(ch0_of(g), 0);           // (its wait: in front of the barrier behind the zero-fill)
+    if (PREF) load_x_of(-1, std::true_type{});
 
     // zero both buffers once: pad columns and the slack rows stay zero, the phases rewrite interior pixels only
     for (int id = tid; id < NS * 2 * EBUF / 8; id += NTHR) *reinterpret_cast<u32x4*>(&Es[id * 8]) = (u32x4){0u, 0u, 0u, 0u};
@@ -151,38 +262,18 @@ __global__ __launch_bounds__(NW * 64, (NW * OCC + 3) / 4) void k_sweep_mbconv(co
     }
     const int vsel = (fq >> 1) ? RP * ELD : 0;             // vertical pairs: second tap one row down
     const int hsel = (fq >> 1) ? G::HOFF * ELD : 0;        // horizontal pairs: one column right
+    if (wave == NW - 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the first slab's constants have landed
     sw_lds_barrier();
     tick(0);
 
-    const bf16_t* xb = a.X + (size_t)b * a.H * WI * a.Cin;
-    bf16_t* Db = a.D + (size_t)b * a.Ho * WO * a.mid;
-    const int hw1 = a.H * WI - 1;
-    const int kclamp = a.Cin - 8;
-
-    // X fragments of one band straight from global (L2) in MFMA layout; the band's new rows are contiguous in memory, so the
-    // pixel index is just first-row * WI + p.  Rows outside the image are clamped (their results are replaced by zeros);
-    // k >= Cin re-reads valid data that meets zero weight columns.
-    u32x4 xa[MW1][KST];
-    auto load_x = [&](int band) {
-        const int pix0 = (band * NEWR - PAD + HALO) * WI;
-#pragma unroll
-        for (int i = 0; i < MW1; ++i) {
-            const int pix = min(max(pix0 + (wave + NW * i) * 16 + fr, 0), hw1);
-#pragma unroll
-            for (int ks = 0; ks < KST; ++ks) {
-                u32x4 t = {0u, 0u, 0u, 0u};
-                if (!(a.debug_skip & 4)) t = *reinterpret_cast<const u32x4*>(xb + pix * a.Cin + min(ks * 32 + fk, kclamp));
-                xa[i][ks] = t;
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    };
-
     // slabs are walked from an image-dependent start so co-resident workgroups do not stream the same weight lines in
     // lock-step (slabs are independent: no sum changes order)
-    for (int si = g; si < nslab; si += a.csplit) {
-        const int ch0 = ((si + b) % nslab) * (16 * NS);       // first channel of this pass; tile s covers ch0 + 16 s ...
-        load_x(-1);
+    int pb = 0;               // E buffer of this slab's band -1 (band j uses buffer (pb + j + 1) & 1)
+    int kslab = 0;            // slabs this workgroup has finished
+    int nst = 0;              // D store instructions this wave has issued since the last band -1 X prefetch
+    for (int si = g; si < nslab; si += a.csplit, ++kslab) {
+        const int ch0 = ch0_of(si);
+        const bool has_next = si + a.csplit < nslab;
         // Bands shorter than the halo (HALO > NEWR: 5x5 stride 2 with one-row bands): band -1's expand does not reach rows
         // [NEWR, HALO) of its buffer, which band 0 takes over as rows above the image.  They are zero in a workgroup's first slab
         // only; a slab walked before left its own rows there.
@@ -191,29 +282,44 @@ __global__ __launch_bounds__(NW * 64, (NW * OCC + 3) / 4) void k_sweep_mbconv(co
 #pragma unroll
             for (int s = 0; s < NS; ++s)
                 for (int id = tid; id < NZ16; id += NTHR)
-                    *reinterpret_cast<u32x4*>(&Es[s * 2 * EBUF + NEWR * RP * ELD + id * 8]) = (u32x4){0u, 0u, 0u, 0u};
+                    *reinterpret_cast<u32x4*>(&Es[(s * 2 + pb) * EBUF + NEWR * RP * ELD + id * 8]) = (u32x4){0u, 0u, 0u, 0u};
         }
-        // ---- slab constants: expand weights (MFMA A fragments) + bias, depthwise taps of this lane's channel + bias
-        u32x4 wf[NS][KST];
-        f32x4 bb[NS], bdr[NS];
+        // ---- slab switch: this slab's constants out of the LDS staging area (published by the barrier of the previous slab's
+        // last band, or by the start-up barrier), and band -1's X fragments.  The X fragments are retired HERE and passed
+        // through an empty asm: hipcc then treats them as plain register values.  With PREF they were requested in front of the
+        // last band's depthwise phase: vmcnt retires in order and the only vector-memory instructions younger than they are the
+        // nst D stores of that band, so the wait leaves exactly those in flight.  Without PREF xa must not be live across a
+        // depthwise phase: the request goes out here, and its round trip (like every band's in those instances) is exposed.
+        if (!PREF) load_x_of(-1, std::true_type{});
+        f32x4 bdr[NS];
         unsigned wd_raw[NS][(NP + 1) / 2];                    // two tap pairs per register
+        int l = lane;                                         // (opaque, as in stage_consts: no LDS address survives the slab)
+        asm volatile("" : "+v"(l));
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
-            const int c0 = ch0 + 16 * s;
-            const int n = min(c0 + fr, midp - 1);
+            const unsigned char* cs = cst + ((kslab & 1) * NS + s) * CST;
 #pragma unroll
-            for (int ks = 0; ks < KST; ++ks) wf[s][ks] = *reinterpret_cast<const u32x4*>(a.We + (n * a.Kp + ks * 32 + fk));
-            bb[s] = *reinterpret_cast<const f32x4*>(a.be + min(c0 + fq * 4, midp - 4));
-            const int ch = min(c0 + fr, a.mid - 1);
+            for (int ks = 0; ks < KST; ++ks) wf[s][ks] = *reinterpret_cast<const u32x4*>(cs + ks * 1024 + l * 16);
+            bb[s] = *reinterpret_cast<const f32x4*>(cs + KST * 1024 + (l >> 4) * 16);
+            bdr[s] = *reinterpret_cast<const f32x4*>(cs + KST * 1024 + 64 + (l >> 4) * 16);
+            const unsigned short* wds = reinterpret_cast<const unsigned short*>(cs + KST * 1024 + 128) + (l & 15);
 #pragma unroll
             for (int tp = 0; tp < NP; ++tp) {
                 const int ta = TP::tap_a(tp), tb = TP::tap_b(tp) < 0 ? TP::tap_a(tp) : TP::tap_b(tp);
-                const unsigned v = a.Wd[((lane & 32) ? tb : ta) * a.mid + ch];
+                const unsigned v = wds[((l & 32) ? tb : ta) * 16];
                 if (tp & 1) wd_raw[s][tp >> 1] |= v << 16;
                 else wd_raw[s][tp >> 1] = v;
             }
-            bdr[s] = *reinterpret_cast<const f32x4*>(a.bd + min(c0 + fq * 4, a.mid - 4));
         }
+        if (PREF) sw_wait_vm_leaving<MW2 * NS>(nst);
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+        for (int i = 0; i < MW1; ++i)
+#pragma unroll
+            for (int ks = 0; ks < KST; ++ks) asm volatile("" : "+v"(xa[i][ks]));
+        // the next slab's constants go out now, into the other staging set (last read a slab ago, many barriers back); behind the
+        // wait above, which must not count them.  A workgroup's final slab requests nothing.
+        if (has_next && wave == NW - 1) stage_consts(ch0_of(si + a.csplit), (kslab + 1) & 1);
         // diagonal weight fragments of the depthwise MFMAs: lane (n = lane & 15, kg = lane >> 4) holds k = kg*8 + j -> tap
         // (kg >> 1), channel (kg & 1)*8 + j of the tile: nonzero only where that channel is the lane's own n
         auto build_dwf = [&](int s, u32x4* dwf) {
@@ -234,23 +340,6 @@ __global__ __launch_bounds__(NW * 64, (NW * OCC + 3) / 4) void k_sweep_mbconv(co
         for (int s = 0; s < NS; ++s)
 #pragma unroll
             for (int j = 0; j < 4; ++j) psum[s][j] = 0.f;
-        // retire the slab constants (and band -1's X fragments) HERE and pass them through an empty asm: hipcc then treats them
-        // as plain register values.  Left alone it put a vmcnt(0) in front of the first depthwise MFMA of every band (first use
-        // of the depthwise bias inside the loop), which also waited for the X fragments prefetched for the next band.
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-#pragma unroll
-            for (int ks = 0; ks < KST; ++ks) asm volatile("" : "+v"(wf[s][ks]));
-            asm volatile("" : "+v"(bb[s]));
-            asm volatile("" : "+v"(bdr[s]));
-#pragma unroll
-            for (int i = 0; i < (NP + 1) / 2; ++i) asm volatile("" : "+v"(wd_raw[s][i]));
-        }
-#pragma unroll
-        for (int i = 0; i < MW1; ++i)
-#pragma unroll
-            for (int ks = 0; ks < KST; ++ks) asm volatile("" : "+v"(xa[i][ks]));
         if constexpr (DWF_PER_SLAB) {
 #pragma unroll
             for (int s = 0; s < NS; ++s) build_dwf(s, dwf_s[s]);
@@ -258,12 +347,12 @@ __global__ __launch_bounds__(NW * 64, (NW * OCC + 3) / 4) void k_sweep_mbconv(co
         tick(1);
 
         for (int band = -1; band < nbands; ++band) {
-            bf16_t* Ec = Es + ((band + 1) & 1) * EBUF;         // this band's buffer of tile 0 (tile s: + s * 2 * EBUF)
+            bf16_t* Ec = Es + ((band + 1 + pb) & 1) * EBUF;    // this band's buffer of tile 0 (tile s: + s * 2 * EBUF)
             // ---- expand: rows [HALO, IH) of Ec = act(X W^T + b) for the band's new input rows, zeros outside the image
             {
                 const int iyn0 = band * NEWR - PAD + HALO;                       // first new input row
                 const int plo = max(0, -iyn0) * WI, phi = max(0, min(NEWR, a.H - iyn0)) * WI;   // valid pixels: [plo, phi)
-                if (!PREF && band >= 0) load_x(band);
+                if (!PREF && band >= 0) load_x_of(band, std::false_type{});
                 tick(3);
                 if (stamping) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); tick(4); }
 #pragma unroll
@@ -292,14 +381,23 @@ __global__ __launch_bounds__(NW * 64, (NW * OCC + 3) / 4) void k_sweep_mbconv(co
                         }
                     }
                 }
-                if (PREF && band + 1 < nbands) load_x(band + 1);
+                const bool last = band + 1 >= nbands;
+                // last band: the staged constants of the next slab must have landed before the barrier below publishes them
+                // (requested at the top of this slab, all its bands ago; the wait also covers the previous band's D stores)
+                if (last && has_next && wave == NW - 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                // the next band's X - behind the last band the next slab's band -1, in front of the last depthwise phase - from
+                // ONE request site: with a second one hipcc loads into spare registers and copies, i.e. waits, before the phase
+                if (PREF && (!last || has_next)) {
+                    load_x_of(last ? -1 : band + 1, std::false_type{});
+                    if (last) nst = 0;
+                }
             }
             tick(5);
             sw_lds_barrier();
             tick(6);
             // ---- halo: this band's last HALO rows are the next band's first rows (other buffer; nobody reads it now)
             if (band + 1 < nbands) {
-                bf16_t* En = Es + (band & 1) * EBUF;
+                bf16_t* En = Es + ((band + pb) & 1) * EBUF;
                 constexpr int NV16 = HALO * RP * ELD / 8;
 #pragma unroll
                 for (int s = 0; s < NS; ++s)
@@ -358,6 +456,7 @@ __global__ __launch_bounds__(NW * 64, (NW * OCC + 3) / 4) void k_sweep_mbconv(co
                                 *reinterpret_cast<u32x2*>(Dband + p * a.mid) = sw_pack4(acc);
                             }
                         }
+                        ++nst;      // lane 0 (p = t0 < np2, channel c0 < mid) takes both branches: exactly one store instruction per tile
                     }
                 }
             }
@@ -365,7 +464,7 @@ __global__ __launch_bounds__(NW * 64, (NW * OCC + 3) / 4) void k_sweep_mbconv(co
             tick(7);
         }
 
-        // ---- squeeze: fold the 16 pixel lanes, then the waves, both in a fixed order
+        // ---- squeeze, first half: fold the 16 pixel lanes and park the wave's sums in this slab's own slot of `red`
         if (a.pool) {
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
@@ -374,22 +473,33 @@ __global__ __launch_bounds__(NW * 64, (NW * OCC + 3) / 4) void k_sweep_mbconv(co
 #pragma unroll
                     for (int j = 0; j < 4; ++j) psum[s][j] += __shfl_xor(psum[s][j], o, 64);
                 }
-                if (fr == 0) *reinterpret_cast<f32x4*>(&red[(wave * NS + s) * 16 + fq * 4]) = (f32x4){psum[s][0], psum[s][1], psum[s][2], psum[s][3]};
-            }
-            sw_lds_barrier();
-            if (tid < 16 * NS) {
-                const int s = tid >> 4, c = tid & 15;
-                float sum = 0.f;
-#pragma unroll
-                for (int w = 0; w < NW; ++w) sum += red[(w * NS + s) * 16 + c];
-                if (ch0 + tid < a.mid) a.pool[(size_t)b * a.mid + ch0 + tid] = sum;
+                if (fr == 0) *reinterpret_cast<f32x4*>(&red[((kslab * NW + wave) * NS + s) * 16 + fq * 4]) = (f32x4){psum[s][0], psum[s][1], psum[s][2], psum[s][3]};
             }
         }
-        sw_lds_barrier();       // the next slab's band -1 rewrites the buffers (and red)
+        // NO barrier between slabs.  red: every slab has its own slot.  E buffers: the last band (nbands - 1) read buffer
+        // (pb + nbands) & 1, so the next slab starts in the OTHER one: its band -1 expand (and the HALO > NEWR zero rows) write
+        // a buffer whose last readers were the depthwise phase of band nbands - 2, and a wave gets here only through the barrier of
+        // band nbands - 1, which every wave reaches after that phase.  The next slab's first halo copy (into the buffer the last
+        // band read) comes behind ITS band -1 barrier, which every wave reaches after its own last depthwise phase.
+        pb = (pb + nbands + 1) & 1;
         tick(9);
     }
-    // buckets: 0 init | 1 slab constants (issue) | 2 halo copy | 3 X loads (issue) | 4 wait for the loads | 5 expand + act +
-    //          E writes | 6 barrier | 7 depthwise + act + D stores | 9 squeeze + barrier
+    // ---- squeeze, second half, once per workgroup: add the waves in the fixed order w = 0 .. NW-1, one thread per channel
+    if (a.pool && g < nslab) {
+        sw_lds_barrier();
+        for (int id = tid; id < kslab * 16 * NS; id += NTHR) {
+            const int k = id / (16 * NS), t = id - k * (16 * NS);
+            const int ch = ch0_of(g + k * a.csplit) + t;
+            float sum = 0.f;
+#pragma unroll
+            for (int w = 0; w < NW; ++w) sum += red[(k * NW + w) * (16 * NS) + t];
+            if (ch < a.mid) a.pool[(size_t)b * a.mid + ch] = sum;
+        }
+        tick(9);
+    }
+    // buckets: 0 init (+ the first slab's staged constants) | 1 slab switch: constants out of the LDS, wait for band -1's X |
+    //          2 halo copy | 3 X loads (issue) | 4 wait for the loads | 5 expand + act + E writes (+ X prefetch issue) | 6 barrier |
+    //          7 depthwise + act + D stores | 9 squeeze: lane fold per slab, and the one barrier + wave fold at the end
     if (stamping && tid == 0) {
 #pragma unroll
         for (int i = 0; i < 10; ++i) atomicAdd(reinterpret_cast<unsigned long long*>(a.stamps + (size_t)b * 16 + i), (unsigned long long)t_acc[i]);
@@ -435,8 +545,7 @@ bool sweep_mbconv_supported(int H, int W, int Cin, int mid, int k, int stride, i
 template <int KS, int S, int WI, int TH, int NW, int KST, int OCC, bool PREF, int AE, int AD, int NS = 1>
 static int launch_sw_act(SweepArgs a, int B, hipStream_t st, int* path, int cls, int variant) {
     using G = SwGeom<KS, S, WI, TH>;
-    const size_t lds = G::lds_bytes(NW, NS);
-    static_assert(G::lds_bytes(NW, NS) <= 160 * 1024, "sweep: the row windows do not fit the LDS");
+    static_assert(G::lds_bytes(NW, NS, KST, 1) <= 160 * 1024, "sweep: the row windows do not fit the LDS");
     static bool attr_done[MI355_MAX_DEVICES] = {false};   // per device
     if (first_time_on_this_device(attr_done)) {
         MI355_CHECK_HIP(hipFuncSetAttribute((const void*)k_sweep_mbconv<KS, S, WI, TH, NW, KST, OCC, PREF, AE, AD, NS>,
@@ -453,6 +562,10 @@ static int launch_sw_act(SweepArgs a, int B, hipStream_t st, int* path, int cls,
     if (c > nslab) c = nslab;
     a.csplit = a.csplit_override > 0 ? std::min(a.csplit_override, nslab) : c;
     a.B = B;
+    // one slot of squeeze partials per slab a workgroup walks (a few KB at the model's splits; a forced split of 1 on a wide layer
+    // is the most: 46 slabs x 8 waves x 64 B = 23 KB)
+    const size_t lds = G::lds_bytes(NW, NS, KST, cdiv(nslab, a.csplit));
+    MI355_REQUIRE(lds <= 160 * 1024, "sweep_mbconv: %d slabs per workgroup do not fit the LDS (%zu bytes)", cdiv(nslab, a.csplit), lds);
     const unsigned grid = (unsigned)(8 * cdiv(B, 8) * a.csplit);
     hipLaunchKernelGGL((k_sweep_mbconv<KS, S, WI, TH, NW, KST, OCC, PREF, AE, AD, NS>), dim3(grid), dim3(NW * 64), lds, st, a);
     MI355_LAUNCH_CHECK();
@@ -473,9 +586,12 @@ static int launch_sw(const SweepArgs& a, int B, hipStream_t st, int* path, int c
 
 // variant table {TH, NW, OCC, PREF} per class; variant 0 is the default (both K depths, any activation), the others exist only
 // for the EfficientNet-B3a instances and are kept for tuning runs (tools/tune_sweep.py)
-// (two k-steps: no cross-phase X prefetch - its 2 x MW1 x 4 extra live registers spill at the 128-VGPR budget)
-#define SW_V0(KS, S, WI, TH, NW, OCC, PREF) \
-    return k2 ? launch_sw<KS, S, WI, TH, NW, 2, OCC, false>(a, B, st, path, cls) : launch_sw<KS, S, WI, TH, NW, 1, OCC, PREF>(a, B, st, path, cls)
+// PREF2: the X prefetch of the two-k-step instance.  Its 2 x MW1 x 4 extra live registers used to spill at the 128-VGPR budget
+// everywhere; since the slab constants reach the registers through the LDS (no per-lane address survives a slab) the 28 x 28
+// stride-2 instance holds them without scratch and gains 4 % (62.2 -> 59.5 us at B = 256).  The 5x5 28 x 28 instance still spills
+// six registers with it and is 5 % slower (118.9 -> 125.2 us), the 56 / 112 two-k-step instances serve no model: all three stay off.
+#define SW_V0(KS, S, WI, TH, NW, OCC, PREF, PREF2) \
+    return k2 ? launch_sw<KS, S, WI, TH, NW, 2, OCC, PREF2>(a, B, st, path, cls) : launch_sw<KS, S, WI, TH, NW, 1, OCC, PREF>(a, B, st, path, cls)
 #define SW_VT(KS, S, WI, TH, NW, KST, OCC, PREF) \
     return launch_sw_act<KS, S, WI, TH, NW, KST, OCC, PREF, ACT_SILU, ACT_SILU>(a, B, st, path, cls, v)
 
@@ -513,31 +629,31 @@ int launch_sweep_mbconv(const SweepArgs& a, int B, int k, int stride, hipStream_
             if (v == 2) SW_VT(3, 2, 112, 2, 8, 1, 3, false);
             if (v == 3) SW_VT(3, 2, 112, 1, 7, 1, 2, true);
             if (v == 4) SW_VT(3, 2, 112, 1, 4, 1, 4, true);
-            SW_V0(3, 2, 112, 2, 8, 2, true);
+            SW_V0(3, 2, 112, 2, 8, 2, true, false);
         case SW_3_1_56:
             if (v == 1) SW_VT(3, 1, 56, 8, 7, 1, 2, true);
             if (v == 2) SW_VT(3, 1, 56, 4, 8, 1, 2, true);
             if (v == 3) SW_VT(3, 1, 56, 2, 7, 1, 2, true);
             if (v == 4) SW_VT(3, 1, 56, 2, 7, 1, 3, true);
-            SW_V0(3, 1, 56, 8, 8, 2, true);
+            SW_V0(3, 1, 56, 8, 8, 2, true, false);
         case SW_5_2_56:
             if (v == 1) SW_VT(5, 2, 56, 4, 7, 1, 2, true);
             if (v == 2) SW_VT(5, 2, 56, 2, 8, 1, 2, true);
             if (v == 3) SW_VT(5, 2, 56, 2, 7, 1, 2, false);
             if (v == 4) SW_VT(5, 2, 56, 1, 7, 1, 2, true);
-            SW_V0(5, 2, 56, 2, 7, 2, true);
+            SW_V0(5, 2, 56, 2, 7, 2, true, false);
         case SW_5_1_28:
             if (v == 1) SW_VT(5, 1, 28, 4, 7, 2, 2, true);
             if (v == 2) SW_VT(5, 1, 28, 4, 8, 2, 2, false);
             if (v == 3) SW_VT(5, 1, 28, 2, 7, 2, 2, false);
             if (v == 4) SW_VT(5, 1, 28, 4, 4, 2, 4, false);
-            SW_V0(5, 1, 28, 4, 7, 2, false);
+            SW_V0(5, 1, 28, 4, 7, 2, false, false);
         default:
             if (v == 1) SW_VT(3, 2, 28, 7, 7, 2, 2, false);
             if (v == 2) SW_VT(3, 2, 28, 4, 8, 2, 2, true);
             if (v == 3) SW_VT(3, 2, 28, 2, 7, 2, 2, true);
             if (v == 4) SW_VT(3, 2, 28, 4, 7, 2, 2, true);
-            SW_V0(3, 2, 28, 4, 7, 2, false);
+            SW_V0(3, 2, 28, 4, 7, 2, false, true);
     }
 }
 #undef SW_V0
