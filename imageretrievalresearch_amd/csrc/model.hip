@@ -1081,15 +1081,21 @@ int mi355_model_block_stamps(mi355_model_t m, double* out, int max_ops) {
     return n;
 }
 
-// a 256-byte zero page per device: the source of the DMA kernels' out-of-range chunks (GemmArgs::zeros)
-static int gemm_zero_page(const bf16_t** zeros) {
+// a 256-byte zero page per device: the source of the DMA kernels' out-of-range chunks (GemmArgs::zeros).  The one-time fill
+// is enqueued on the caller's stream and finished before the pointer is published (as preprocess.hip::get_coeffs does): a
+// memset on the null stream is not ordered before kernels on a non-blocking stream, and a later caller on ANOTHER stream must
+// never find a page whose fill is still queued.
+static int gemm_zero_page(const bf16_t** zeros, hipStream_t st) {
     static void* zero_page[MI355_MAX_DEVICES] = {nullptr};
     int dev = 0;
     MI355_CHECK_HIP(hipGetDevice(&dev));
     MI355_REQUIRE(dev >= 0 && dev < MI355_MAX_DEVICES, "gemm_bf16: device ordinal %d out of range", dev);
     if (!zero_page[dev]) {
-        MI355_CHECK_HIP(hipMalloc(&zero_page[dev], 256));
-        MI355_CHECK_HIP(hipMemset(zero_page[dev], 0, 256));
+        void* page = nullptr;
+        MI355_CHECK_HIP(hipMalloc(&page, 256));
+        MI355_CHECK_HIP(hipMemsetAsync(page, 0, 256, st));
+        MI355_CHECK_HIP(hipStreamSynchronize(st));
+        zero_page[dev] = page;
     }
     *zeros = (const bf16_t*)zero_page[dev];
     return OK;
@@ -1101,7 +1107,7 @@ int mi355_gemm_bf16(const void* A, const void* W, const float* bias, void* out, 
     GemmArgs a{};
     a.A = (const bf16_t*)A; a.lda = K; a.W = (const bf16_t*)W; a.ldw = ldw; a.bias = bias;
     a.out = out; a.ldo = N; a.out_f32 = 0; a.M = M; a.N = N; a.K = K; a.act = act; a.rows_per_img = 1; a.res_n = N;
-    if (int e = gemm_zero_page(&a.zeros)) return e;
+    if (int e = gemm_zero_page(&a.zeros, (hipStream_t)stream)) return e;
     return launch_gemm_bf16(a, (hipStream_t)stream);
 }
 
@@ -1139,7 +1145,7 @@ int mi355_gemm_bf16_ex(const mi355_gemm_ex_args* x, int* path, void* stream) {
     a.M_sel = (long)x->M_sel;
     a.splitk_ws = (float*)x->splitk_ws; a.splitk_ws_bytes = x->splitk_ws_bytes;
     a.ln_stats = x->ln_stats; a.ln_colsum = x->ln_colsum;
-    if (int e = gemm_zero_page(&a.zeros)) return e;
+    if (int e = gemm_zero_page(&a.zeros, (hipStream_t)stream)) return e;
     return launch_gemm_bf16(a, (hipStream_t)stream, path);
 }
 

@@ -49,6 +49,8 @@ class Int8Gallery:
             scales = torch.empty((cap,), dtype=torch.float32, device=self.device)
             codes[: self.rows].copy_(self._codes[: self.rows])
             scales[: self.rows].copy_(self._scales[: self.rows])
+            _rank._retire(self._codes, self.device)          # the queued copies still read the old buffers
+            _rank._retire(self._scales, self.device)
             self._codes, self._scales = codes, scales
 
     def _append(self, e: torch.Tensor, labels, normalized: bool):
@@ -61,7 +63,10 @@ class Int8Gallery:
                                                 n * self._ld, scales.data_ptr(), stream_ptr(e.device)))
         if labels is not None:
             lab = labels.to(self.device, torch.int64)
-            self.labels = lab if self.labels is None else torch.cat([self.labels, lab])
+            if self.labels is not None:
+                _rank._retire(self.labels, self.device)
+                lab = torch.cat([self.labels, lab])
+            self.labels = lab
         self.rows += n
         return self
 

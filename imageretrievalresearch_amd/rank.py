@@ -68,6 +68,14 @@ class _Workspace:
 _ws = _Workspace()
 
 
+def _retire(old: torch.Tensor | None, device) -> None:
+    """A resident buffer that was just replaced (a queued copy or ``torch.cat`` on the current stream still reads it): tell the
+    caching allocator, as ``_Workspace.get`` does, so that its block is not handed out again - on the stream that allocated
+    it, which need not be this one - before that read has run."""
+    if old is not None and old.is_cuda and old.numel():
+        old.record_stream(torch.cuda.current_stream(device))
+
+
 def synth_fill(n: int, seed: int, kind: int, device, offset: int = 0) -> torch.Tensor:
     """Device-side portable generator (bit-identical to ``synth.fill``)."""
     out = torch.empty(int(n), dtype=torch.float32, device=device)
@@ -644,6 +652,7 @@ class Gallery:
             cap = max(n, int(self._buf.shape[0] * 1.5) + 1024)
             nb = torch.empty((cap, self._ld), dtype=self.dtype, device=self.device)
             nb[: self.rows].copy_(self._buf[: self.rows])
+            _retire(self._buf, self.device)
             self._buf = nb
 
     def add(self, embeddings: torch.Tensor, labels: torch.Tensor | None = None):
@@ -661,7 +670,10 @@ class Gallery:
             l2_normalize_rows(e, self.eps, out=self._buf[self.rows: self.rows + n])
         if labels is not None:
             lab = labels.to(self.device, torch.int64)
-            self.labels = lab if self.labels is None else torch.cat([self.labels, lab])
+            if self.labels is not None:
+                _retire(self.labels, self.device)
+                lab = torch.cat([self.labels, lab])
+            self.labels = lab
         self.rows += n
         self._knn, self._rerank = {}, {}
         self._ivf = {}
