@@ -37,6 +37,9 @@ def __getattr__(name):  # lazy: models/sharded import torch.nn / torch.distribut
     if name in ("create_model", "list_models", "ConvInput", "with_conv_input"):
         from . import models
         return getattr(models, name)
+    if name == "PQGallery":
+        from .pq import PQGallery
+        return PQGallery
     if name == "ShardedGallery":
         from .sharded import ShardedGallery
         return ShardedGallery

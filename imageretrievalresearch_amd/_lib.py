@@ -166,6 +166,17 @@ PROTOTYPES = {
     "mi355_ivf_scan_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int64]),
     "mi355_ivf_scan": (C.c_int, [vp, C.c_int64, C.c_int, C.c_float, vp, C.c_int, C.c_int64, C.c_int64, vp, vp, C.c_int64, vp,
                                  C.c_int, C.c_int64, C.c_int64, C.POINTER(RankFilter), vp, vp, vp, C.c_size_t, vp]),
+    "mi355_pq_encode_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
+    "mi355_pq_encode": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, C.c_size_t, vp, C.c_size_t, vp]),
+    "mi355_pq_update_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
+    "mi355_pq_update": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp, vp, C.c_size_t, vp]),
+    "mi355_pq_search_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int]),
+    "mi355_pq_scores": (C.c_int, [vp, C.c_int64, C.c_int, C.c_float, vp, C.c_int, vp, C.c_int64, vp, vp, C.c_size_t, vp]),
+    "mi355_pq_search": (C.c_int, [vp, C.c_int64, C.c_int, C.c_float, vp, C.c_int, vp, C.c_int64, C.c_int, C.c_int64,
+                                  C.POINTER(RankFilter), vp, vp, vp, C.c_size_t, vp]),
+    "mi355_rescore_candidates_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
+    "mi355_rescore_candidates": (C.c_int, [vp, C.c_int64, C.c_int, C.c_float, vp, C.c_int, C.c_int64, C.c_int64, vp, C.c_int64,
+                                           C.c_int64, vp, vp, C.c_size_t, vp]),
     "mi355_roc_pairs_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int]),
     "mi355_roc_pairs_hist": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_float, vp, vp, vp, C.c_int64,
                                        C.POINTER(C.c_double), vp, C.c_int, vp, vp, C.c_size_t, vp]),

@@ -52,14 +52,7 @@ __global__ __launch_bounds__(256) void k_row_norm(const float* __restrict__ in, 
 // =====================================================================================
 // top-k selection
 // =====================================================================================
-// Ordering of (score, index) candidates: higher score first, ties -> lower index.  NaN orders as the LARGEST value, as in
-// torch.topk (a NaN score - e.g. from an Inf/NaN embedding - is returned with its in-range index instead of starving
-// the list and leaving pad entries behind); two NaNs tie.
-__device__ __forceinline__ bool better(float a, i64 ia, float b, i64 ib) {
-    const bool an = a != a, bn = b != b;
-    if (an || bn) return (an && !bn) || (an && bn && ia < ib);
-    return (a > b) || (a == b && ia < ib);
-}
+// (the ordering of (score, index) candidates, better(), lives in rank_common.h: the PQ scan selects with it too)
 
 // =====================================================================================
 // fp32 operands on the bf16 matrix pipe: three-way split, six products

@@ -37,6 +37,15 @@ __device__ __forceinline__ float key_score(unsigned key) {
     return __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key);
 }
 
+// Ordering of (score, index) candidates: higher score first, ties -> lower index.  NaN orders as the LARGEST value, as in
+// torch.topk (a NaN score - e.g. from an Inf/NaN embedding - is returned with its in-range index instead of starving
+// the list and leaving pad entries behind); two NaNs tie.
+__device__ __forceinline__ bool better(float a, i64 ia, float b, i64 ib) {
+    const bool an = a != a, bn = b != b;
+    if (an || bn) return (an && !bn) || (an && bn && ia < ib);
+    return (a > b) || (a == b && ia < ib);
+}
+
 constexpr int RK_BN = 128;
 
 // Eligibility filter of the filtered searches (mi355_rank_filter): row j of a search with idx_offset is left out for query q

@@ -1,5 +1,14 @@
 // Body of k_topk_small and k_topk_small_filt (rank.hip): included into both, so the unfiltered kernel compiles from exactly
 // the text it always had.  FILT (constexpr bool) and flt (RankFilter) are declared by the including kernel.
+// TOPK_SMALL_VALUE(j): the score of candidate j; the PQ scan (pq.hip) defines it as the table lookup of row j, so that its
+// scores never exist in memory.
+// TOPK_SMALL_THREADS: the threads of the including kernel's workgroup (a multiple of 64).
+#ifndef TOPK_SMALL_VALUE
+#define TOPK_SMALL_VALUE(j) v[j]
+#endif
+#ifndef TOPK_SMALL_THREADS
+#define TOPK_SMALL_THREADS 256
+#endif
     const int tid = threadIdx.x;
     const i64 q = blockIdx.y;
     const i64 c0 = (i64)blockIdx.x * chunk_len;
@@ -15,8 +24,8 @@
     i64 fq_lab = 0, fq_ex = -1;
     if constexpr (FILT) query_filter(flt, q, fq_lab, fq_ex);
 
-    for (i64 j = c0 + tid; j < c1; j += 256) {
-        const float x = v[j];
+    for (i64 j = c0 + tid; j < c1; j += TOPK_SMALL_THREADS) {
+        const float x = TOPK_SMALL_VALUE(j);
         i64 id;
         if (ix32) { const int t = ix32[j]; id = t == IDX32_PAD ? IDX_PAD : (i64)t + idx_offset; }
         else id = ix ? ix[j] : j + idx_offset;
@@ -35,8 +44,8 @@
         }
     }
 
-    __shared__ float sv[4];
-    __shared__ i64 si[4];
+    __shared__ float sv[TOPK_SMALL_THREADS / 64];
+    __shared__ i64 si[TOPK_SMALL_THREADS / 64];
     const int lane = tid & 63, wave = tid >> 6;
     float* o_v = ov + (q * gridDim.x + blockIdx.x) * k;
     i64* o_i = oi + (q * gridDim.x + blockIdx.x) * k;
@@ -53,7 +62,7 @@
         __syncthreads();
         bv = sv[0]; bi = si[0];
 #pragma unroll
-        for (int w = 1; w < 4; ++w)
+        for (int w = 1; w < TOPK_SMALL_THREADS / 64; ++w)
             if (better(sv[w], si[w], bv, bi)) { bv = sv[w]; bi = si[w]; }
         if (tid == 0) { o_v[r] = bv; o_i[r] = bi; }
         // the owner pops its head (indices are unique among real entries; pads never win a real slot)

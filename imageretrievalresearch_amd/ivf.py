@@ -9,7 +9,7 @@ members of every cluster are its lists, and a query is scored against the rows o
 * ``index.update()`` ............................. after ``gallery.add``: the new rows go to their nearest list
 
 The rows are scanned where they lie in the gallery (fp32 or fp16), through the lists' ``order``; the index holds no copy of
-them.  Out of scope: ``ShardedGallery``, product quantisation, a list-ordered copy of the rows.
+them.  Out of scope: ``ShardedGallery``, a list-ordered copy of the rows.
 """
 from __future__ import annotations
 

@@ -137,6 +137,7 @@ enum {
     MI355_RANK_PATH_F16_GEMV = 6,       /* k_cos_gemv_f16 */
     MI355_RANK_PATH_I8_GEMM = 7,        /* k_cos_gemm_i8 */
     MI355_RANK_PATH_I8_GEMV = 8,        /* k_cos_gemv_i8: Q <= 4 */
+    MI355_RANK_PATH_PQ = 9,             /* k_pq_scan / k_pq_scores: the table scan over product-quantised rows (mi355_pq_search) */
     MI355_RANK_PATH_FUSED = 0x100,
     MI355_RANK_PATH_BITONIC = 0x200
 };
@@ -547,6 +548,60 @@ int mi355_ivf_scan(const float* queries, int64_t Q, int dim, float eps, const vo
                    const int64_t* offsets, const int64_t* order, int64_t nlist, const int64_t* probes, int nprobe, int64_t cap,
                    int64_t idx_offset, const mi355_rank_filter* filter, float* cand_val, int64_t* cand_idx, void* workspace,
                    size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------ product-quantised (PQ) resident gallery
+ * A row is M bytes: its normalised fp32 row is cut into M sub-vectors of dsub = dim / M elements, and byte m names the nearest
+ * of the 256 centroids of sub-quantiser m.  At dim = 1536, M = 96 that is 96 bytes, a 64th of the fp32 row.
+ * Below, "fp32" means one IEEE rounding per named operation; no multiply is fused with an add anywhere in this block.
+ * Parameters: M % 4 == 0, 4 <= M <= 128, dim % M == 0, 1 <= dsub <= 64.  codebooks: device fp32 [M][256][dsub].  codes: uint8
+ * [G][M], row-major and appendable (encoding n rows to codes + r * M writes rows r .. r+n-1); the base is 16-byte aligned.
+ * Encode: n = the fp32 row mi355_l2_normalize_rows writes for x, bit for bit (rows_are_normalized != 0: n = x as it is).  For
+ * subspace m and centroid c: d = 0.0f, then for i ascending t = n[m*dsub+i] - cb[m][c][i]; d = d + t*t (the subtraction, the
+ * multiply and the add each rounded to fp32).  code[m] = the lowest c whose d is strictly below the d of every earlier c (c = 0
+ * to begin with).  A NaN distance never wins: a row with a NaN element gets code 0 in the subspaces the NaN touches.  This is
+ * the one place where the format departs from the other galleries' "a NaN row ranks first": a code cannot carry a NaN, so such
+ * a row scores like any row with those codes.
+ * Table (per query, made by every search): qn = the normalised query (the bits above); T[m][c]: acc = 0.0f, then for i ascending
+ * acc = acc + qn[m*dsub+i] * cb[m][c][i], the multiply rounded, then the add rounded.
+ * Score of (q, g): four accumulators a_j = 0.0f; for m ascending a_{m%4} = a_{m%4} + T[m][code[g][m]]; score = (a0 + a1) +
+ * (a2 + a3).  A NaN query scores NaN everywhere.  A score depends on its query row, its code row and the codebooks only - not on
+ * Q, G, the row's position in a chunk of the scan, k, the filter or the path (fused selection, score slab, mi355_pq_scores).
+ * Top-k: the selection of mi355_rank_topk (descending, NaN first, ties to the lower row, -0 equal to +0, the slots a filter
+ * leaves empty (-inf, -1)).  Equal code rows give equal bits, so ties are the normal case here.
+ * The scan: one workgroup per (query, chunk of 2048 rows) holds the query's table in LDS (M KB of the 160 KB).  For k <= 8 it
+ * selects inside the kernel (k candidates per (query, chunk), merged by the selection of mi355_merge_topk: MI355_RANK_PATH_PQ |
+ * FUSED); for 8 < k <= 1024 it writes the score slab of a block of queries and the selection of mi355_topk_rows follows
+ * (| BITONIC).  An ineligible row (filter) never enters the selection.  No atomics: one writer per output slot.
+ * Centroid update (training): new[m][c] = fp32(S / count), S = the float64 sum of the sub-vectors m of the normalised rows n
+ * whose code[m] is c, added ONE AT A TIME IN ASCENDING ROW ORDER (each fp32 element widened exactly; sum and division in
+ * float64, one rounding to fp32 at the end), count = their number.  The order is the rows' order alone: it does not depend on
+ * the device, its CU count or the launch geometry.  A cell without members keeps its previous centroid bit for bit.  counts:
+ * device int64 [M][256].  codebooks and codebooks_out may be the same buffer.
+ * Rescoring (mi355_rescore_candidates): out_val[q][r] = the fp32 dot mi355_ivf_scan gives query q and row cand_idx[q][r] -
+ * idx_offset of fp32 or fp16 rows (the same routine: one wave per pair, lane-strided units, fused multiply-adds, the wave
+ * reduction), for the re-ranking of a PQ shortlist against the rows it was made from.  cand_idx [Q][R] device int64 is left as
+ * it is; a negative index, one >= 2^62, or one whose row falls outside [0, G) scores -inf.
+ * Every argument is checked before any HIP call (null pointers, shape, k in [1, min(1024, G)], 16-byte alignment of the codes,
+ * codes_bytes, workspace).  R, Q or G equal to 0 does nothing.  Workspaces: the _workspace_bytes entry of the same name;
+ * mi355_pq_scores takes mi355_pq_search_workspace_bytes(Q, G, dim, M, 0) (k = 0: no selection).  The sizers return 0 for a shape
+ * the entry would reject, and for R = 0 / Q = 0. */
+size_t mi355_pq_encode_workspace_bytes(int64_t R, int dim, int rows_are_normalized);
+int mi355_pq_encode(const float* rows, int64_t R, int dim, int M, int rows_are_normalized, float eps, const float* codebooks,
+                    void* codes, size_t codes_bytes, void* workspace, size_t workspace_bytes, void* stream);
+size_t mi355_pq_update_workspace_bytes(int64_t R, int dim, int rows_are_normalized);
+int mi355_pq_update(const float* rows, int64_t R, int dim, int M, int rows_are_normalized, float eps, const void* codes,
+                    const float* codebooks, float* codebooks_out, int64_t* counts, void* workspace, size_t workspace_bytes,
+                    void* stream);
+size_t mi355_pq_search_workspace_bytes(int64_t Q, int64_t G, int dim, int M, int k);
+int mi355_pq_scores(const float* queries, int64_t Q, int dim, float eps, const float* codebooks, int M, const void* codes, int64_t G,
+                    float* scores, void* workspace, size_t workspace_bytes, void* stream);
+int mi355_pq_search(const float* queries, int64_t Q, int dim, float eps, const float* codebooks, int M, const void* codes, int64_t G,
+                    int k, int64_t idx_offset, const mi355_rank_filter* filter, float* out_val, int64_t* out_idx, void* workspace,
+                    size_t workspace_bytes, void* stream);
+size_t mi355_rescore_candidates_workspace_bytes(int64_t Q, int dim);
+int mi355_rescore_candidates(const float* queries, int64_t Q, int dim, float eps, const void* rows, int rows_dtype, int64_t ld,
+                             int64_t G, const int64_t* cand_idx, int64_t R, int64_t idx_offset, float* out_val, void* workspace,
+                             size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ backbone models
  * Replaces timm.create_model(name, num_classes=N) and the methods the reference calls on it
