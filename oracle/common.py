@@ -21,13 +21,16 @@ def make_divisible(v, divisor=8, min_value=None, round_limit=0.9):
 
 class Rounder:
     """bf16 rounding points of the HIP path.  ``sim=False`` -> identity (pure fp32 = the
-    reference's CPU semantics, autocast is a no-op without CUDA: inference/inference.py:196)."""
+    reference's CPU semantics, autocast is a no-op without CUDA: inference/inference.py:196).  The dtype of ``x`` is kept: a
+    float64 activation is rounded to bf16 at the same points and comes back as float64, so an oracle fed a float64 tensor
+    keeps its rounding points and does the arithmetic between them in float64 (tests/plan_shapes_ref.py measures the
+    fp32 oracle's own rounding-flip noise that way)."""
 
     def __init__(self, sim: bool):
         self.sim = sim
 
     def __call__(self, x: torch.Tensor) -> torch.Tensor:
-        return x.to(torch.bfloat16).to(torch.float32) if self.sim else x
+        return x.to(torch.bfloat16).to(x.dtype) if self.sim else x
 
 
 def bn_scale(bn: dict, eps: float) -> torch.Tensor:
@@ -37,11 +40,13 @@ def bn_scale(bn: dict, eps: float) -> torch.Tensor:
     return bn["weight"] / torch.sqrt(v.double()).to(v.dtype)
 
 
-def fold_bn(w: torch.Tensor, bn: dict, eps: float):
-    """conv weight (O, ...) + eval-mode BN -> (w * g/sqrt(v+eps), b - m*g/sqrt(v+eps))."""
+def fold_bn(w: torch.Tensor, bn: dict, eps: float, dtype=None):
+    """conv weight (O, ...) + eval-mode BN -> (w * g/sqrt(v+eps), b - m*g/sqrt(v+eps)).  The fold is the packer's, in fp32
+    whatever ``dtype`` says; ``dtype`` only converts the two results (exactly) for a conv on an activation of that dtype."""
     scale = bn_scale(bn, eps)
     shape = [-1] + [1] * (w.dim() - 1)
-    return w * scale.reshape(shape), bn["bias"] - bn["running_mean"] * scale
+    wf, bf = w * scale.reshape(shape), bn["bias"] - bn["running_mean"] * scale
+    return (wf, bf) if dtype is None else (wf.to(dtype), bf.to(dtype))
 
 
 def bn_of(sd, prefix):

@@ -79,18 +79,64 @@ def init_state_dict(seed: int, num_classes: int = 1000):
 
 
 def _conv_bn(x, sd, conv, bn, rb, stride=1, pad=0, groups=1, act=True):
-    w, b = fold_bn(sd[f"{conv}.weight"], bn_of(sd, bn), BN_EPS)
+    """conv + folded BN (+ SiLU) in the dtype of ``x`` (fp32, or float64 between the same bf16 rounding points)."""
+    w, b = fold_bn(sd[f"{conv}.weight"], bn_of(sd, bn), BN_EPS, x.dtype)
     y = F.conv2d(x, rb(w), b, stride=stride, padding=pad, groups=groups)
     return F.silu(y) if act else y
 
 
-def _se(x, sd, p, rb):
+def _se(x, sd, p, rb, squeeze=None):
     """SE on the fp32 (pre-rounding) activation: mean -> conv_reduce(+b) -> SiLU -> conv_expand(+b)
     -> sigmoid.  Returns the gate.  The HIP path stores the two FC matrices in bf16 (``rb`` in sim mode; every image's
     workgroup streams them from L2) and keeps biases, accumulation and the gate in fp32."""
-    s = x.mean((2, 3), keepdim=True)
-    r = F.silu(F.conv2d(s, rb(sd[f"{p}.se.conv_reduce.weight"]), sd[f"{p}.se.conv_reduce.bias"]))
-    return torch.sigmoid(F.conv2d(r, rb(sd[f"{p}.se.conv_expand.weight"]), sd[f"{p}.se.conv_expand.bias"]))
+    s = x.mean((2, 3), keepdim=True) if squeeze is None else squeeze(x)
+    t = lambda k: sd[f"{p}.se.{k}"].to(x.dtype)
+    r = F.silu(F.conv2d(s, rb(t("conv_reduce.weight")), t("conv_reduce.bias")))
+    return torch.sigmoid(F.conv2d(r, rb(t("conv_expand.weight")), t("conv_expand.bias")))
+
+
+def stem(sd, x, rb):
+    return rb(_conv_bn(x, sd, "conv_stem", "bn1", rb, stride=2, pad=1))
+
+
+def block(sd, p, b, x, rb, hooks=None):
+    """One block (``p`` = "blocks.S.B", ``b`` its dict of arch()) on the previous block's output.  ``hooks`` lets a test plant
+    a deliberate bug (tests/plan_shapes_ref.py): "dw_in" maps the depthwise conv's input, "squeeze" replaces the SE mean,
+    "gate" maps the gate."""
+    h = hooks or {}
+    k, s, mid = b["k"], b["s"], b["mid"]
+    sc = x
+    if b["type"] == "ir":
+        x = rb(_conv_bn(x, sd, f"{p}.conv_pw", f"{p}.bn1", rb))
+        dw_bn, pw, bnl = f"{p}.bn2", f"{p}.conv_pwl", f"{p}.bn3"
+    else:
+        dw_bn, pw, bnl = f"{p}.bn1", f"{p}.conv_pw", f"{p}.bn2"
+    if "dw_in" in h:
+        x = h["dw_in"](x)
+    d = _conv_bn(x, sd, f"{p}.conv_dw", dw_bn, rb, stride=s, pad=k // 2, groups=mid)
+    gate = _se(d, sd, p, rb, h.get("squeeze"))
+    if "gate" in h:
+        gate = h["gate"](gate)
+    x = rb(rb(d) * gate)
+    x = _conv_bn(x, sd, pw, bnl, rb, act=False)
+    if b["s"] == 1 and b["cin"] == b["cout"]:
+        x = x + sc
+    return rb(x)
+
+
+def head(sd, x, rb):
+    return rb(_conv_bn(x, sd, "conv_head", "bn2", rb))
+
+
+def layers(sd):
+    """[(tap name, block dict or None, f(x, rb, hooks=None))] from the stem to the head: each maps the previous entry's output."""
+    out = [("stem", None, lambda x, rb, hooks=None: stem(sd, x, rb))]
+    for si, st in enumerate(arch()["stages"]):
+        for bi, b in enumerate(st):
+            p = f"blocks.{si}.{bi}"
+            out.append((p, b, lambda x, rb, hooks=None, p=p, b=b: block(sd, p, b, x, rb, hooks)))
+    out.append(("head", None, lambda x, rb, hooks=None: head(sd, x, rb)))
+    return out
 
 
 def forward_features(sd, x, sim_bf16=False, taps=None):
@@ -101,31 +147,10 @@ def forward_features(sd, x, sim_bf16=False, taps=None):
     squeeze averages the un-rounded depthwise output, the gated tensor is re-rounded before conv_pwl.
     ``taps`` (dict) collects intermediate tensors by name for per-layer parity tests."""
     rb = Rounder(sim_bf16)
-    a = arch()
-    x = rb(_conv_bn(x, sd, "conv_stem", "bn1", rb, stride=2, pad=1))
-    if taps is not None:
-        taps["stem"] = x
-    for si, st in enumerate(a["stages"]):
-        for bi, b in enumerate(st):
-            p = f"blocks.{si}.{bi}"
-            k, s, mid = b["k"], b["s"], b["mid"]
-            sc = x
-            if b["type"] == "ir":
-                x = rb(_conv_bn(x, sd, f"{p}.conv_pw", f"{p}.bn1", rb))
-                d = _conv_bn(x, sd, f"{p}.conv_dw", f"{p}.bn2", rb, stride=s, pad=k // 2, groups=mid)
-                pw, bnl = f"{p}.conv_pwl", f"{p}.bn3"
-            else:
-                d = _conv_bn(x, sd, f"{p}.conv_dw", f"{p}.bn1", rb, stride=s, pad=k // 2, groups=mid)
-                pw, bnl = f"{p}.conv_pw", f"{p}.bn2"
-            gate = _se(d, sd, p, rb)
-            x = rb(rb(d) * gate)
-            x = _conv_bn(x, sd, pw, bnl, rb, act=False)
-            if b["s"] == 1 and b["cin"] == b["cout"]:
-                x = x + sc
-            x = rb(x)
-            if taps is not None:
-                taps[p] = x
-    x = rb(_conv_bn(x, sd, "conv_head", "bn2", rb))
+    for name, _, f in layers(sd):
+        x = f(x, rb)
+        if taps is not None and name != "head":
+            taps[name] = x
     return x
 
 

@@ -80,48 +80,80 @@ def init_state_dict(seed: int, width_mult: float, num_classes: int = 1000):
 
 
 def _cba(x, sd, p, rb, stride=1, pad=0, groups=1):
-    w, b = fold_bn(sd[f"{p}.conv.weight"], bn_of(sd, f"{p}.bn"), BN_EPS)
+    """conv + folded BN in the dtype of ``x`` (fp32, or float64 between the same bf16 rounding points)."""
+    w, b = fold_bn(sd[f"{p}.conv.weight"], bn_of(sd, f"{p}.bn"), BN_EPS, x.dtype)
     return F.conv2d(x, rb(w), b, stride=stride, padding=pad, groups=groups)
+
+
+def stem(sd, x, rb):
+    return rb(F.silu(_cba(x, sd, "stem", rb, stride=2, pad=1)))
+
+
+def block(sd, p, b, x, rb, hooks=None):
+    """One LinearBottleneck (``p`` = "features.I", ``b`` its dict of arch()) on the previous block's output.  ``hooks`` lets a
+    test plant a deliberate bug (tests/plan_shapes_ref.py): "dw_in" maps the depthwise conv's input, "squeeze" replaces the SE
+    mean, "gate" maps the gate, "residual" replaces the partial-channel shortcut f(x, sc, cin)."""
+    h = hooks or {}
+    sim, dt = rb.sim, x.dtype
+    sc = x
+    if b["e"] != 1:
+        x = rb(F.silu(_cba(x, sd, f"{p}.conv_exp", rb)))
+    if "dw_in" in h:
+        x = h["dw_in"](x)
+    d = _cba(x, sd, f"{p}.conv_dw", rb, stride=b["s"], pad=1, groups=b["dw"])   # BN, no activation
+    if b["rd"]:
+        s = d.mean((2, 3), keepdim=True) if "squeeze" not in h else h["squeeze"](d)
+        bn = bn_of(sd, f"{p}.se.bn")
+        t = lambda k: sd[f"{p}.se.{k}"]
+        if sim:
+            # the HIP path folds the SE BN into fc1 and stores both FC matrices rounded to bf16 (fp32 math)
+            scale = bn_scale(bn, BN_EPS)
+            w1 = rb(t("fc1.weight") * scale.reshape(-1, 1, 1, 1))
+            b1 = t("fc1.bias") * scale + (bn["bias"] - bn["running_mean"] * scale)
+            r = F.relu(F.conv2d(s, w1.to(dt), b1.to(dt)))
+            gate = torch.sigmoid(F.conv2d(r, rb(t("fc2.weight")).to(dt), t("fc2.bias").to(dt)))
+        else:
+            r = F.conv2d(s, t("fc1.weight").to(dt), t("fc1.bias").to(dt))
+            r = F.relu(F.batch_norm(r, bn["running_mean"].to(dt), bn["running_var"].to(dt), bn["weight"].to(dt), bn["bias"].to(dt),
+                                    False, 0.0, BN_EPS))
+            gate = torch.sigmoid(F.conv2d(r, t("fc2.weight").to(dt), t("fc2.bias").to(dt)))
+        if "gate" in h:
+            gate = h["gate"](gate)
+        x = rb(F.relu6(rb(d) * gate))
+    else:
+        x = rb(F.relu6(rb(d)))
+    x = _cba(x, sd, f"{p}.conv_pwl", rb)
+    if b["s"] == 1 and b["cin"] <= b["cout"]:
+        if "residual" in h:
+            x = h["residual"](x, sc, b["cin"])
+        else:
+            x = torch.cat([x[:, : b["cin"]] + sc, x[:, b["cin"]:]], 1)   # x[:, 0:in_chs] += shortcut
+    return rb(x)
+
+
+def head(sd, x, rb, n):
+    return rb(F.silu(_cba(x, sd, f"features.{n}", rb)))
+
+
+def layers(sd, width_mult):
+    """[(tap name, block dict or None, f(x, rb, hooks=None))] from the stem to the head: each maps the previous entry's output."""
+    blocks = arch(width_mult)["blocks"]
+    out = [("stem", None, lambda x, rb, hooks=None: stem(sd, x, rb))]
+    for i, b in enumerate(blocks):
+        p = f"features.{i}"
+        out.append((p, b, lambda x, rb, hooks=None, p=p, b=b: block(sd, p, b, x, rb, hooks)))
+    out.append(("head", None, lambda x, rb, hooks=None: head(sd, x, rb, len(blocks))))
+    return out
 
 
 def forward_features(sd, x, width_mult, sim_bf16=False, taps=None):
     """(B,3,H,W) -> un-pooled (B, pen_chs, H/32, W/32).  ``sim_bf16``: the HIP path's rounding points."""
     rb = Rounder(sim_bf16)
-    a = arch(width_mult)
-    x = rb(F.silu(_cba(x, sd, "stem", rb, stride=2, pad=1)))
-    if taps is not None:
-        taps["stem"] = x
-    for i, b in enumerate(a["blocks"]):
-        p = f"features.{i}"
-        sc = x
-        if b["e"] != 1:
-            x = rb(F.silu(_cba(x, sd, f"{p}.conv_exp", rb)))
-        d = _cba(x, sd, f"{p}.conv_dw", rb, stride=b["s"], pad=1, groups=b["dw"])   # BN, no activation
-        if b["rd"]:
-            s = d.mean((2, 3), keepdim=True)
-            bn = bn_of(sd, f"{p}.se.bn")
-            if sim_bf16:
-                # the HIP path folds the SE BN into fc1 and stores both FC matrices rounded to bf16 (fp32 math)
-                scale = bn_scale(bn, BN_EPS)
-                w1 = rb(sd[f"{p}.se.fc1.weight"] * scale.reshape(-1, 1, 1, 1))
-                b1 = sd[f"{p}.se.fc1.bias"] * scale + (bn["bias"] - bn["running_mean"] * scale)
-                r = F.relu(F.conv2d(s, w1, b1))
-                gate = torch.sigmoid(F.conv2d(r, rb(sd[f"{p}.se.fc2.weight"]), sd[f"{p}.se.fc2.bias"]))
-            else:
-                r = F.conv2d(s, sd[f"{p}.se.fc1.weight"], sd[f"{p}.se.fc1.bias"])
-                r = F.relu(F.batch_norm(r, bn["running_mean"], bn["running_var"], bn["weight"], bn["bias"], False, 0.0, BN_EPS))
-                gate = torch.sigmoid(F.conv2d(r, sd[f"{p}.se.fc2.weight"], sd[f"{p}.se.fc2.bias"]))
-            x = rb(F.relu6(rb(d) * gate))
-        else:
-            x = rb(F.relu6(rb(d)))
-        x = _cba(x, sd, f"{p}.conv_pwl", rb)
-        if b["s"] == 1 and b["cin"] <= b["cout"]:
-            x = torch.cat([x[:, : b["cin"]] + sc, x[:, b["cin"]:]], 1)   # x[:, 0:in_chs] += shortcut
-        x = rb(x)
-        if taps is not None:
-            taps[p] = x
-    n = len(a["blocks"])
-    return rb(F.silu(_cba(x, sd, f"features.{n}", rb)))
+    for name, _, f in layers(sd, width_mult):
+        x = f(x, rb)
+        if taps is not None and name != "head":
+            taps[name] = x
+    return x
 
 
 def forward(sd, x, width_mult, sim_bf16=False):

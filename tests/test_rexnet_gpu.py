@@ -16,7 +16,7 @@ TOL_TAP_SIM = 2.5e-2      # ReLU6 clipping + 16 blocks: bf16 rounding flips comp
 TOL_EMB_FP32 = 5e-2
 
 
-@pytest.mark.parametrize("name,wm", [("rexnet_150", 1.5), ("rexnet_200", 2.0)])
+@pytest.mark.parametrize("name,wm", [("rexnet_100", 1.0), ("rexnet_130", 1.3), ("rexnet_150", 1.5), ("rexnet_200", 2.0)])
 def test_rexnet_blocks_and_embedding_match_oracle(name, wm):
     sd = rexnet.init_state_dict(4, wm)
     model = M.create_model(name).to(DEV).eval()
