@@ -40,6 +40,9 @@ def __getattr__(name):  # lazy: models/sharded import torch.nn / torch.distribut
     if name == "PQGallery":
         from .pq import PQGallery
         return PQGallery
+    if name == "IVFPQIndex":
+        from .ivfpq import IVFPQIndex
+        return IVFPQIndex
     if name == "ShardedGallery":
         from .sharded import ShardedGallery
         return ShardedGallery

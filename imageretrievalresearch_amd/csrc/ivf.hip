@@ -8,7 +8,7 @@
 //   5. k_ivf_pad: the slots n_q .. cap - 1 of every query;
 //   6. k_ivf_scan: a fixed grid loops over the items; one wave per row, the group's queries in LDS.
 // Every slot is written by exactly one wave (of k_ivf_scan below n_q, of k_ivf_pad from n_q on).  gfx950 only.
-#include "rank_common.h"
+#include "ivf_lists.h"
 #include "row_dot.h"
 #include "../../include/mi355_retrieval.h"
 
@@ -17,8 +17,6 @@ namespace mi355 {
 constexpr int IVF_NQ = 4;                  // queries of one group at most (k_cos_gemv's count)
 constexpr int IVF_CHUNK = 64;              // rows of one work item: 16 per wave
 constexpr size_t IVF_LDS = 64 * 1024;      // the group's queries
-constexpr i64 IVF_MAX_WGS = ((i64)1 << 24) - 1;
-enum { IVF_FLAG_ENTRY = 0, IVF_FLAG_CAP = 1, IVF_FLAGS = 2 };
 
 // What the kernels share
 struct IvfArgs {
@@ -46,15 +44,6 @@ struct IvfArgs {
     RankFilter filt;
     bool filtered;
 };
-
-// The rows [b, e) of list l in order; false (and an empty range) when the offsets do not ascend within [0, G]
-__device__ __forceinline__ bool list_range(const i64* __restrict__ offsets, i64 l, i64 G, i64& b, i64& e) {
-    b = offsets[l];
-    e = offsets[l + 1];
-    if (b >= 0 && b <= e && e <= G) return true;
-    e = b = 0;
-    return false;
-}
 
 // base[q][j] = the rows of probes[q][0 .. j); nfill[q] = n_q.  One thread per query.
 __global__ __launch_bounds__(256) void k_ivf_bases(IvfArgs a) {

@@ -7,24 +7,16 @@
 //                   four accumulators, then the small-k selection of rank_topk_small.inc over scores that never reach memory
 //   k_pq_scores ... the same lookups, written out as a score slab (k > 8, mi355_pq_scores)
 //   k_rescore ..... one wave per (query, candidate): the row dot of the IVF scan (row_dot.h) against fp32 / fp16 rows
+// The table in LDS, the lookups of one row and the shape rules live in pq_scan.h: the IVF-PQ scan (ivfpq.hip) shares them.
 // No atomics: every output slot has one writer.  gfx950 only.
-#include "rank_common.h"
+#include "pq_scan.h"
 #include "row_dot.h"
 #include "../../include/mi355_retrieval.h"
 
 namespace mi355 {
 
-constexpr int PQ_CENTROIDS = 256;
-constexpr int PQ_MAX_M = 128;
-constexpr int PQ_MAX_DSUB = 64;
 constexpr int PQ_CHUNK = 2048;              // rows of one scan workgroup; the table load (M KB) is 1/8 of its lookups
-// Threads of a scan workgroup (a template argument NT): the LDS a table takes bounds the workgroups per CU, so a larger table is
-// shared by more waves - 16 to 24 waves per CU in every case (measured, DESIGN.md section 5: at M = 96 1024 threads are 1.4x
-// faster than 256, at M = 48 they are 1.2x slower than 256)
-static int pq_threads(int M) { return M <= 40 ? 256 : M <= 80 ? 512 : 1024; }
 constexpr int PQ_TABLE_Q = 8;               // queries of one table workgroup: codebook m is staged in LDS once for them
-constexpr i64 PQ_QBLOCK = 256;              // queries of one table / scan launch (the tables of a block: 256 * M KB)
-constexpr i64 PQ_SLAB_FLOATS = (i64)1 << 27;   // the score slab of one query block stays under 512 MB
 constexpr i64 PQ_ENC_BLOCK = 16384;         // rows normalised at a time by mi355_pq_encode
 constexpr int PQ_UPD_ROWS = 4096;           // rows one pass of k_pq_update looks at: 16 per thread
 constexpr int RESCORE_CHUNK = 64;           // candidates of one rescore workgroup: 16 per wave
@@ -145,41 +137,6 @@ __global__ __launch_bounds__(256) void k_pq_table(const float* __restrict__ qn, 
     }
 }
 
-// ---- the lookups of one row: tab [M][256] in LDS, the row's M codes read 16 bytes at a time (VEC: M % 16 == 0, so every row
-// of a 16-byte aligned base is aligned) or 4 (M % 4 == 0).  Byte m of a unit goes to accumulator m % 4 (a unit starts at a
-// multiple of 4).
-__device__ __forceinline__ void pq_lookup4(const float* t, unsigned w, float& a0, float& a1, float& a2, float& a3) {
-    a0 = __fadd_rn(a0, t[w & 255u]);
-    a1 = __fadd_rn(a1, t[PQ_CENTROIDS + ((w >> 8) & 255u)]);
-    a2 = __fadd_rn(a2, t[2 * PQ_CENTROIDS + ((w >> 16) & 255u)]);
-    a3 = __fadd_rn(a3, t[3 * PQ_CENTROIDS + (w >> 24)]);
-}
-template <bool VEC>
-__device__ __forceinline__ float pq_score(const float* tab, const unsigned char* __restrict__ codes, i64 g, int M) {
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-    if constexpr (VEC) {
-        const uint4* row = reinterpret_cast<const uint4*>(codes + g * M);
-        for (int u = 0; u < M / 16; ++u) {
-            const uint4 w = row[u];
-            const float* t = tab + u * 16 * PQ_CENTROIDS;
-            pq_lookup4(t, w.x, a0, a1, a2, a3);
-            pq_lookup4(t + 4 * PQ_CENTROIDS, w.y, a0, a1, a2, a3);
-            pq_lookup4(t + 8 * PQ_CENTROIDS, w.z, a0, a1, a2, a3);
-            pq_lookup4(t + 12 * PQ_CENTROIDS, w.w, a0, a1, a2, a3);
-        }
-    } else {
-        const unsigned* row = reinterpret_cast<const unsigned*>(codes + g * M);
-        for (int u = 0; u < M / 4; ++u) pq_lookup4(tab + u * 4 * PQ_CENTROIDS, row[u], a0, a1, a2, a3);
-    }
-    return __fadd_rn(__fadd_rn(a0, a1), __fadd_rn(a2, a3));
-}
-template <int NT>
-__device__ __forceinline__ void pq_load_table(float* tab, const float* __restrict__ T, int M) {
-    const f32x4* src = reinterpret_cast<const f32x4*>(T + (size_t)blockIdx.y * M * PQ_CENTROIDS);
-    for (int i = threadIdx.x; i < M * (PQ_CENTROIDS / 4); i += NT) reinterpret_cast<f32x4*>(tab)[i] = src[i];
-    __syncthreads();
-}
-
 // ---- scan with the selection inside (k <= K <= 8): grid (cdiv(G, PQ_CHUNK), queries).  The body is the small-k selection of
 // the score slabs; its candidate value is the row's lookups.  ov / oi [queries][chunks][k].
 template <int K, bool FILT, bool VEC, int NT>
@@ -240,16 +197,6 @@ __global__ __launch_bounds__(256) void k_rescore(RescoreArgs a) {
 }
 
 // ---- host side
-static bool pq_shape_ok(int dim, int M) {
-    return M >= 4 && M <= PQ_MAX_M && M % 4 == 0 && dim >= 1 && dim % M == 0 && dim / M <= PQ_MAX_DSUB;
-}
-static int pq_check_shape(const char* who, int dim, int M) {
-    MI355_REQUIRE(M >= 4 && M <= PQ_MAX_M && M % 4 == 0, "%s: M=%d must be a multiple of 4 in [4, %d]", who, M, PQ_MAX_M);
-    MI355_REQUIRE(dim >= 1 && dim % M == 0, "%s: dim=%d must be a positive multiple of M=%d", who, dim, M);
-    MI355_REQUIRE(dim / M <= PQ_MAX_DSUB, "%s: dsub = dim / M = %d exceeds %d", who, dim / M, PQ_MAX_DSUB);
-    return OK;
-}
-
 // Scratch of a search over Q queries (k = 0: mi355_pq_scores, no selection): the normalised queries, the tables of one query
 // block, then the block's candidate lists (k <= 8) or its score slab (k > 8) and the selection's own scratch
 struct PqWs {
@@ -333,7 +280,7 @@ static int launch_scores(dim3 grid, const float* T, const unsigned char* codes, 
     if (nt == 512) return launch_scores_nt<VEC, 512>(grid, T, codes, G, M, S, ldS, st);
     return launch_scores_nt<VEC, 1024>(grid, T, codes, G, M, S, ldS, st);
 }
-static int launch_table(const float* qn_rows, i64 qn, int dim, const float* cb, int M, float* T, hipStream_t st) {
+int launch_table(const float* qn_rows, i64 qn, int dim, const float* cb, int M, float* T, hipStream_t st) {
     static bool done[MI355_MAX_DEVICES] = {false};
     if (int e = pq_allow_lds(k_pq_table, done)) return e;         // 256 * 65 floats at dsub = 64: just above 64 KB
     const size_t lds = (size_t)PQ_CENTROIDS * ((dim / M) | 1) * sizeof(float);

@@ -3,11 +3,20 @@
 // TOPK_SMALL_VALUE(j): the score of candidate j; the PQ scan (pq.hip) defines it as the table lookup of row j, so that its
 // scores never exist in memory.
 // TOPK_SMALL_THREADS: the threads of the including kernel's workgroup (a multiple of 64).
+// TOPK_SMALL_ROW(j): the gallery row of candidate j, which its implicit index, its label and the excluded row go by; the IVF-PQ
+// scan (ivfpq.hip) visits rows in list order and defines it as the list's entry for position j (evaluated after the value).
+// TOPK_SMALL_SKIP(j): true for a position that holds no candidate (there: a list entry outside the gallery).
 #ifndef TOPK_SMALL_VALUE
 #define TOPK_SMALL_VALUE(j) v[j]
 #endif
 #ifndef TOPK_SMALL_THREADS
 #define TOPK_SMALL_THREADS 256
+#endif
+#ifndef TOPK_SMALL_ROW
+#define TOPK_SMALL_ROW(j) (j)
+#endif
+#ifndef TOPK_SMALL_SKIP
+#define TOPK_SMALL_SKIP(j) false
 #endif
     const int tid = threadIdx.x;
     const i64 q = blockIdx.y;
@@ -28,10 +37,12 @@
         const float x = TOPK_SMALL_VALUE(j);
         i64 id;
         if (ix32) { const int t = ix32[j]; id = t == IDX32_PAD ? IDX_PAD : (i64)t + idx_offset; }
-        else id = ix ? ix[j] : j + idx_offset;
+        else id = ix ? ix[j] : TOPK_SMALL_ROW(j) + idx_offset;
         if constexpr (FILT) {
-            if (!eligible(flt.mode, fq_lab, flt.mode != MI355_LABEL_ANY ? flt.glab[j] : 0, fq_ex, j)) id = IDX_PAD;
+            if (!eligible(flt.mode, fq_lab, flt.mode != MI355_LABEL_ANY ? flt.glab[TOPK_SMALL_ROW(j)] : 0, fq_ex, TOPK_SMALL_ROW(j)))
+                id = IDX_PAD;
         }
+        if (TOPK_SMALL_SKIP(j)) id = IDX_PAD;
         if (id < NO_CAND_IDX && better(x, id, lv[K - 1], li[K - 1])) {      // (IDX_PAD and the shard pad: no candidate)
             lv[K - 1] = x; li[K - 1] = id;
 #pragma unroll

@@ -11,8 +11,9 @@ D = 1536 and M = 96 a 64th of the fp32 row, so that a million rows are 96 MB and
 
 The format is approximate against the fp32 cosine, but its arithmetic is specified bit for bit in include/mi355_retrieval.h: a
 score depends on its query, its code row and the codebooks alone, and a NumPy model (tests/pq_ref.py) reproduces every bit of
-the codes, the tables, the scores, the top-k and the trained codebooks.  Out of scope: IVF lists over the codes,
-an OPQ rotation, a sharded PQ gallery, range search / query expansion over codes, training on fp16 rows.
+the codes, the tables, the scores, the top-k and the trained codebooks.  ``pq.ivf(rows, nlist)`` puts IVF lists over the codes
+(ivfpq.py).  Out of scope: residual codes, an OPQ rotation, a sharded PQ gallery, range search / query expansion over
+codes, training on fp16 rows.
 """
 from __future__ import annotations
 
@@ -31,6 +32,44 @@ _MAX_K = 1024                       # largest k of any search, and the longest s
 
 def _is_int(x) -> bool:
     return isinstance(x, (int, np.integer)) and not isinstance(x, bool)
+
+
+def _shortlist_length(pq: "PQGallery", k, refine, shortlist):
+    """(k, R) of a search over ``pq``'s rows: the checked k, and the rows the code scan returns per query - k itself, or with
+    ``refine`` the length of the shortlist it rescores.  The one set of rules behind ``PQGallery.search`` and
+    ``IVFPQIndex.search``."""
+    top = min(_MAX_K, pq.rows)
+    if not _is_int(k) or not 1 <= k <= top:
+        raise MI355Error(f"selected index k out of range: k={k!r} outside [1, {top}] (min({_MAX_K}, rows))")
+    k = int(k)
+    if refine is None:
+        if shortlist is not None:
+            raise MI355Error("shortlist is the length of the list that refine= rescores: give refine too")
+        return k, k
+    if not isinstance(refine, _rank.Gallery):
+        raise MI355Error(f"refine must be a Gallery of the same rows, got {type(refine).__name__}")
+    if refine.device != pq.device:
+        raise MI355Error(f"refine is on {refine.device} but the PQGallery lives on {pq.device}")
+    if len(refine) != pq.rows or refine.dim != pq.dim:
+        raise MI355Error(f"refine holds {len(refine)} rows of dim {refine.dim}, the PQGallery {pq.rows} of dim {pq.dim}")
+    R = min(max(10 * k, 100), top) if shortlist is None else shortlist
+    if not _is_int(R) or not k <= R <= top:
+        raise MI355Error(f"shortlist={R!r} outside [k={k}, {top}] (min({_MAX_K}, rows))")
+    return k, int(R)
+
+
+def _refined_topk(pq: "PQGallery", q: torch.Tensor, vals: torch.Tensor, idx: torch.Tensor, k: int, refine, idx_offset):
+    """The tail of a refined search: the shortlist ``idx`` (Q, R) of the queries ``q`` is scored again against ``refine``'s
+    rows (``mi355_rescore_candidates``, into ``vals``), then ``merge_topk`` and ``clear_pads``."""
+    Q, R, L, dev = idx.shape[0], idx.shape[1], lib(), pq.device
+    ws = _rank._ws.get(dev, L.mi355_rescore_candidates_workspace_bytes(Q, pq.dim))
+    with torch.cuda.device(dev):
+        check(L.mi355_rescore_candidates(q.data_ptr(), Q, pq.dim, pq.eps, refine._buf.data_ptr(), _rank._DTYPES[refine.dtype],
+                                         refine._ld, pq.rows, idx.data_ptr(), R, int(idx_offset), vals.data_ptr(),
+                                         ws.data_ptr(), ws.numel(), stream_ptr(dev)))
+    v, i = _rank.merge_topk(vals, idx, k)
+    _rank.clear_pads(v, i, int(idx_offset), int(idx_offset) + pq.rows)
+    return v, i
 
 
 class PQGallery:
@@ -237,25 +276,7 @@ class PQGallery:
         rows)``, default ``min(max(10 * k, 100), 1024, rows)``), each is scored again as ``qn . row`` against the gallery's row
         (the bits an ``IVFIndex`` scan gives the pair) and the top-k of those values is returned.  Nothing is read back."""
         self._trained("search")
-        top = min(_MAX_K, self.rows)
-        if not _is_int(k) or not 1 <= k <= top:
-            raise MI355Error(f"selected index k out of range: k={k!r} outside [1, {top}] (min({_MAX_K}, rows))")
-        k = int(k)
-        if refine is None:
-            if shortlist is not None:
-                raise MI355Error("shortlist is the length of the list that refine= rescores: give refine too")
-            R = k
-        else:
-            if not isinstance(refine, _rank.Gallery):
-                raise MI355Error(f"refine must be a Gallery of the same rows, got {type(refine).__name__}")
-            if refine.device != self.device:
-                raise MI355Error(f"refine is on {refine.device} but the PQGallery lives on {self.device}")
-            if len(refine) != self.rows or refine.dim != self.dim:
-                raise MI355Error(f"refine holds {len(refine)} rows of dim {refine.dim}, the PQGallery {self.rows} of dim {self.dim}")
-            R = min(max(10 * k, 100), top) if shortlist is None else shortlist
-            if not _is_int(R) or not k <= R <= top:
-                raise MI355Error(f"shortlist={R!r} outside [k={k}, {top}] (min({_MAX_K}, rows))")
-            R = int(R)
+        k, R = _shortlist_length(self, k, refine, shortlist)
         q = self._queries(queries, "search")
         Q = q.shape[0]
         gl = None if label_filter is None else self._labels_for(f'label_filter="{label_filter}"')
@@ -263,15 +284,7 @@ class PQGallery:
         vals, idx = self._pq_topk(q, R, idx_offset, filt)
         if refine is None or Q == 0:
             return vals[:, :k], idx[:, :k]
-        L = lib()
-        ws = _rank._ws.get(self.device, L.mi355_rescore_candidates_workspace_bytes(Q, self.dim))
-        with torch.cuda.device(self.device):
-            check(L.mi355_rescore_candidates(q.data_ptr(), Q, self.dim, self.eps, refine._buf.data_ptr(), _rank._DTYPES[refine.dtype],
-                                             refine._ld, self.rows, idx.data_ptr(), R, int(idx_offset), vals.data_ptr(),
-                                             ws.data_ptr(), ws.numel(), stream_ptr(self.device)))
-        v, i = _rank.merge_topk(vals, idx, k)
-        _rank.clear_pads(v, i, int(idx_offset), int(idx_offset) + self.rows)
-        return v, i
+        return _refined_topk(self, q, vals, idx, k, refine, idx_offset)
 
     def recall(self, queries: torch.Tensor, k: int, exact: "_rank.Gallery", **search_kwargs):
         """(mean, per_query (Q,) float64): the share of ``exact.search(queries, k)``'s indices that ``search(queries, k,
@@ -283,3 +296,9 @@ class PQGallery:
         want = exact.search(queries, k)[1]
         per = (got.unsqueeze(2) == want.unsqueeze(1)).any(dim=1).sum(dim=1).double() / float(k)
         return (float(per.mean()) if per.numel() else 1.0), per
+
+    def ivf(self, rows, nlist: int, **kw):
+        """The ``IVFPQIndex`` over these codes with ``nlist`` lists: ``IVFPQIndex.build(self, rows, nlist, **kw)`` (``iters``,
+        ``seed``, ``init``); ``rows`` is the ``Gallery`` or the fp32 tensor the codes were made from."""
+        from .ivfpq import IVFPQIndex
+        return IVFPQIndex.build(self, rows, nlist, **kw)

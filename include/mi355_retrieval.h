@@ -603,6 +603,43 @@ int mi355_rescore_candidates(const float* queries, int64_t Q, int dim, float eps
                              int64_t G, const int64_t* cand_idx, int64_t R, int64_t idx_offset, float* out_val, void* workspace,
                              size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ IVF-PQ search: the probed lists of a PQ gallery's codes
+ * The table scan of the PQ block over the rows of the lists a query probes only.  It indexes the codes a PQ gallery already
+ * holds (no residual coding): codebooks, M, dim as in the PQ block; offsets [nlist + 1], order [G] device int64 as in the IVF
+ * block; probes [Q][nprobe] device int64 list ids, those of one query distinct, 1 <= nprobe <= min(nlist, 1024).
+ * Layout: list_codes uint8 [G][M] is the list-ordered copy of the codes, list_codes[p] = codes[order[p]], base 16-byte aligned:
+ * list l is the contiguous byte range [offsets[l] * M, offsets[l + 1] * M), and the scan's 16-byte (M % 16 == 0) or 4-byte code
+ * loads are those of the exhaustive scan.
+ * Score of (q, row): exactly the PQ score above - the table T[m][c] of the normalised query, four accumulators in order m % 4,
+ * then (a0 + a1) + (a2 + a3) - bit for bit.  It depends on the query row, the code row and the codebooks only: not on the list,
+ * nprobe, Q, cap, the chunk of the scan, k, the filter or the path.  A search that probes every list therefore returns the
+ * values and indices of mi355_pq_search over the same codes, bit for bit.
+ * Selection: that of mi355_rank_topk (descending, NaN first, ties to the lower GALLERY ROW, -0 equal to +0).  The scan visits
+ * rows in list order, so the tie rule is applied on order[p] + idx_offset, never on the scan position.  The slots that the
+ * probed lists or a filter leave empty hold (-inf, -1).
+ * filter: NULL, or the eligibility rule of the filtered searches; labels are looked up by gallery row order[p], exclude is
+ * compared with order[p] + idx_offset.  Returned indices are order[p] + idx_offset.
+ * cap: an upper bound on the rows any one query probes (the host knows it from the list lengths); cap >= k.  Per block of 256
+ * queries: their tables, then per query the running sums base[0 .. nprobe] of its probed lists' lengths (n_q = base[nprobe]),
+ * then a grid of (cdiv(cap, 2048), queries) workgroups: workgroup (c, q) owns positions [2048 c, min(2048 (c + 1), n_q)) of
+ * query q's concatenated lists, finds the list of a position in base[] (held in LDS beside the table: M KB + 8 (nprobe + 1)
+ * bytes) and returns at once, with empty candidates, when 2048 c >= n_q.  For k <= 8 it selects inside the kernel (k candidates
+ * per (query, chunk), merged by the selection of mi355_merge_topk); for 8 < k <= 1024 it writes a (queries, cap) slab of
+ * (value, index) candidates with (-inf, 2^62) from n_q on and the selection of mi355_merge_topk follows; the query block
+ * shrinks so that the slab stays under 512 MB.  No atomics: one writer per output slot.  The result does not depend on the
+ * chunk length.
+ * Errors found on the device are reported after the call from one flag read-back (one host sync at the end, as in
+ * mi355_ivf_scan): n_q > cap for some query; a list id outside [0, nlist), an order entry outside [0, G) or offsets that do not
+ * ascend within [0, G].  Such an entry is skipped and nothing is read or written out of bounds because of it.
+ * Every argument is checked before any HIP call: null pointers, the PQ shape rules, 16-byte alignment of list_codes, G >= 1,
+ * 1 <= nprobe <= min(nlist, 1024), nlist < 2^24, k in [1, min(1024, cap)], Q * nprobe < 2^31, Q * cap <= 2^40, the filter, the
+ * workspace.  Q = 0 does nothing.  The sizer returns 0 for a shape the entry would reject, and for Q = 0. */
+size_t mi355_ivfpq_search_workspace_bytes(int64_t Q, int nprobe, int64_t nlist, int dim, int M, int64_t cap, int k);
+int mi355_ivfpq_search(const float* queries, int64_t Q, int dim, float eps, const float* codebooks, int M, const void* list_codes,
+                       int64_t G, const int64_t* offsets, const int64_t* order, int64_t nlist, const int64_t* probes, int nprobe,
+                       int64_t cap, int k, int64_t idx_offset, const mi355_rank_filter* filter, float* out_val, int64_t* out_idx,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ backbone models
  * Replaces timm.create_model(name, num_classes=N) and the methods the reference calls on it
  * (inference/inference.py:102,110,133,146,199-201 ; train/train.py:194-195,288,396 ;
