@@ -71,7 +71,7 @@ def _check_rows(src) -> None:
 
 
 def _check_k(n_clusters, N: int) -> int:
-    if isinstance(n_clusters, bool) or not isinstance(n_clusters, (int, np.integer)):
+    if not _rank._is_int(n_clusters):
         raise MI355Error(f"n_clusters must be an integer, got {n_clusters!r}")
     if not 1 <= n_clusters <= N:
         raise MI355Error(f"n_clusters={n_clusters} outside [1, {N}] (the number of rows)")
@@ -80,7 +80,7 @@ def _check_k(n_clusters, N: int) -> int:
 
 def _assign(src, c: torch.Tensor, block, eps: float):
     N, dev = src.rows, src.device
-    if block is not None and (isinstance(block, bool) or not isinstance(block, (int, np.integer)) or block < 1):
+    if block is not None and (not _rank._is_int(block) or block < 1):
         raise MI355Error(f"block must be a positive integer, got {block!r}")
     assign = torch.empty(N, dtype=torch.int64, device=dev)
     score = torch.empty(N, dtype=torch.float32, device=dev)
@@ -158,7 +158,7 @@ def cluster_members(assign: torch.Tensor, n_clusters: int):
     if not torch.is_tensor(assign) or assign.dim() != 1 or assign.shape[0] < 1:
         raise MI355Error("assign must be a non-empty 1-D tensor")
     a = _rank._int64_on(assign, "assign", assign.shape[0], assign.device)
-    if isinstance(n_clusters, bool) or not isinstance(n_clusters, (int, np.integer)) or n_clusters < 1:
+    if not _rank._is_int(n_clusters) or n_clusters < 1:
         raise MI355Error(f"n_clusters must be a positive integer, got {n_clusters!r}")
     N, K, dev = a.shape[0], int(n_clusters), a.device
     offsets = torch.empty(K + 1, dtype=torch.int64, device=dev)
@@ -190,7 +190,7 @@ def spherical_kmeans(rows, n_clusters: int, *, iters: int = 20, seed: int = 0, i
     require_cuda(src.buf, "rows")
     _check_rows(src)
     K = _check_k(n_clusters, src.rows)
-    if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or iters < 0:
+    if not _rank._is_int(iters) or iters < 0:
         raise MI355Error(f"iters must be a non-negative integer, got {iters!r}")
     if init is None:
         pick = torch.from_numpy(seeded_rows(src.rows, K, seed)).to(src.device)

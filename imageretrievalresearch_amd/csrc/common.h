@@ -55,6 +55,19 @@ static inline bool first_time_on_this_device(bool* flags) {
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 static inline size_t align_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
 
+// ---- host-side workspace carving: a caller's workspace may start anywhere, every piece of it starts on 256 bytes.
+static inline char* align256(const void* p) { return (char*)(((uintptr_t)p + 255) & ~(uintptr_t)255); }
+// The pieces of one workspace layout, taken in order.  `ws` null: sizing only (every piece is null).  total() is what the
+// layout asks of the caller: the pieces, each rounded up to 256 bytes, plus the 256 that aligning `ws` can cost.
+struct WsCarver {
+    char* base;
+    size_t off = 0;
+    explicit WsCarver(void* ws) : base(ws ? align256(ws) : nullptr) {}
+    char* next() const { return base ? base + off : nullptr; }         // where the next piece will start
+    char* take(size_t bytes) { char* p = next(); off += align_up(bytes, 256); return p; }
+    size_t total() const { return off + 256; }
+};
+
 // ---- bf16 <-> f32 bit helpers (device).  Plain casts so NaN stays NaN (v_cvt_pk_bf16_f32).
 typedef unsigned short bf16_t;  // storage type for bf16 tensors across the library
 

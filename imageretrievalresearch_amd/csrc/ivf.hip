@@ -212,28 +212,25 @@ struct IvfWs {
 };
 static IvfWs ivf_carve(void* ws, i64 Q, int nprobe, i64 nlist, int dim, i64 cap) {
     IvfWs r{};
-    size_t off = 0;
-    char* base = ws ? (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255) : nullptr;
-    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align_up(bytes, 256); return p; };
+    WsCarver c(ws);
     const size_t P = (size_t)Q * nprobe;
-    r.flag = (unsigned*)take(IVF_FLAGS * sizeof(unsigned));
-    r.n_work = (i64*)take(sizeof(i64));
-    r.qn = (float*)take((size_t)Q * dim * sizeof(float));
-    r.poff = (i64*)take((size_t)(nlist + 1) * sizeof(i64));
-    r.pord = (i64*)take(P * sizeof(i64));
-    r.base = (i64*)take(P * sizeof(i64));
-    r.nfill = (i64*)take((size_t)Q * sizeof(i64));
-    r.wstart = (i64*)take((size_t)(nlist + 1) * sizeof(i64));
-    r.items = (int4*)take((size_t)ivf_max_work(Q, nprobe, cap) * sizeof(int4));
-    r.members = take(members_ws_bytes((i64)P, nlist));
-    r.total = off + 256;
+    r.flag = (unsigned*)c.take(IVF_FLAGS * sizeof(unsigned));
+    r.n_work = (i64*)c.take(sizeof(i64));
+    r.qn = (float*)c.take((size_t)Q * dim * sizeof(float));
+    r.poff = (i64*)c.take((size_t)(nlist + 1) * sizeof(i64));
+    r.pord = (i64*)c.take(P * sizeof(i64));
+    r.base = (i64*)c.take(P * sizeof(i64));
+    r.nfill = (i64*)c.take((size_t)Q * sizeof(i64));
+    r.wstart = (i64*)c.take((size_t)(nlist + 1) * sizeof(i64));
+    r.items = (int4*)c.take((size_t)ivf_max_work(Q, nprobe, cap) * sizeof(int4));
+    r.members = c.take(members_ws_bytes((i64)P, nlist));
+    r.total = c.total();
     return r;
 }
 
 // What both entries check of the shape; true when it is one a scan can run
 static bool ivf_shape_ok(i64 Q, int nprobe, i64 nlist, int dim, i64 cap) {
-    return Q >= 1 && nlist >= 1 && nlist <= IVF_MAX_WGS && nprobe >= 1 && nprobe <= nlist && dim >= 1 && cap >= 1 &&
-           Q <= (((i64)1 << 31) - 1) / nprobe && cap <= ((i64)1 << 40) / Q;
+    return dim >= 1 && ivf_lists_shape_ok(Q, nprobe, nlist, cap);
 }
 
 static int ivf_grid() {                        // workgroups of the scan: eight per CU (32 waves)
@@ -325,14 +322,7 @@ int mi355_ivf_scan(const float* queries, int64_t Q, int dim, float eps, const vo
         hipLaunchKernelGGL((k_ivf_scan<false, false>), grid, dim3(256), lds, st, a);
     MI355_LAUNCH_CHECK();
 
-    unsigned flags[IVF_FLAGS] = {0, 0}, bad_probe = 0;
-    MI355_CHECK_HIP(hipMemcpyAsync(flags, w.flag, sizeof(flags), hipMemcpyDeviceToHost, st));
-    MI355_CHECK_HIP(hipMemcpyAsync(&bad_probe, members_flag, sizeof(bad_probe), hipMemcpyDeviceToHost, st));
-    MI355_CHECK_HIP(hipStreamSynchronize(st));
-    MI355_REQUIRE(!bad_probe && !flags[IVF_FLAG_ENTRY], "%s: a list id outside [0, nlist=%lld), an order entry outside [0, G=%lld) "
-                  "or offsets that do not ascend within [0, G]", who, (long long)nlist, (long long)G);
-    MI355_REQUIRE(!flags[IVF_FLAG_CAP], "%s: a query's probed lists hold more than cap=%lld rows", who, (long long)cap);
-    return OK;
+    return ivf_check_flags(w.flag, members_flag, nlist, G, cap, who, st);
 }
 
 }  // extern "C"

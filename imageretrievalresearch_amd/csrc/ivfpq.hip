@@ -192,9 +192,8 @@ __global__ __launch_bounds__(NT) void k_ivfpq_cands(IvfPqArgs a) {
 
 // ---- host side
 static bool ivfpq_shape_ok(i64 Q, int nprobe, i64 nlist, int dim, int M, i64 G, i64 cap, int k) {
-    return Q >= 1 && G >= 1 && G <= ((i64)1 << 40) && pq_shape_ok(dim, M) && nlist >= 1 && nlist <= IVF_MAX_WGS && nprobe >= 1 &&
-           nprobe <= nlist && nprobe <= IVFPQ_MAX_NPROBE && cap >= 1 && k >= 1 && k <= LARGE_K && k <= cap &&
-           Q <= (((i64)1 << 31) - 1) / nprobe && cap <= ((i64)1 << 40) / Q;
+    return G >= 1 && G <= ((i64)1 << 40) && pq_shape_ok(dim, M) && ivf_lists_shape_ok(Q, nprobe, nlist, cap) &&
+           nprobe <= IVFPQ_MAX_NPROBE && k >= 1 && k <= LARGE_K && k <= cap;
 }
 // Queries of one table / scan launch: PQ_QBLOCK, fewer when their candidate slab (k > 8: 12 bytes a slot) would pass the bound
 static i64 ivfpq_query_block(i64 Q, i64 cap, int k) {
@@ -213,21 +212,19 @@ struct IvfPqWs {
 };
 static IvfPqWs ivfpq_carve(void* ws, i64 Q, int nprobe, int dim, int M, i64 cap, int k) {
     IvfPqWs r{};
-    size_t off = 0;
-    char* base = ws ? (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255) : nullptr;
-    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align_up(bytes, 256); return p; };
+    WsCarver c(ws);
     const i64 qb = ivfpq_query_block(Q, cap, k);
     const i64 slots = k <= SMALL_K ? (i64)cdiv(cap, IVFPQ_CHUNK) * k : cap;
-    r.flag = (unsigned*)take(IVF_FLAGS * sizeof(unsigned));
-    r.qn = (float*)take((size_t)Q * dim * sizeof(float));
-    r.T = (float*)take((size_t)qb * M * PQ_CENTROIDS * sizeof(float));
-    r.base = (i64*)take((size_t)qb * (nprobe + 1) * sizeof(i64));
-    r.lbeg = (i64*)take((size_t)qb * nprobe * sizeof(i64));
-    r.cand_val = (float*)take((size_t)qb * slots * sizeof(float));
-    r.cand_idx = (i64*)take((size_t)qb * slots * sizeof(i64));
+    r.flag = (unsigned*)c.take(IVF_FLAGS * sizeof(unsigned));
+    r.qn = (float*)c.take((size_t)Q * dim * sizeof(float));
+    r.T = (float*)c.take((size_t)qb * M * PQ_CENTROIDS * sizeof(float));
+    r.base = (i64*)c.take((size_t)qb * (nprobe + 1) * sizeof(i64));
+    r.lbeg = (i64*)c.take((size_t)qb * nprobe * sizeof(i64));
+    r.cand_val = (float*)c.take((size_t)qb * slots * sizeof(float));
+    r.cand_idx = (i64*)c.take((size_t)qb * slots * sizeof(i64));
     r.topk_bytes = topk_ws_bytes(qb, slots, k);
-    r.topk = take(r.topk_bytes);
-    r.total = off + 256;
+    r.topk = c.take(r.topk_bytes);
+    r.total = c.total();
     return r;
 }
 
@@ -334,13 +331,7 @@ int mi355_ivfpq_search(const float* queries, int64_t Q, int dim, float eps, cons
                                 w.topk_bytes, st, nullptr, &fb))
             return e;
     }
-    unsigned flags[IVF_FLAGS] = {0, 0};
-    MI355_CHECK_HIP(hipMemcpyAsync(flags, w.flag, sizeof(flags), hipMemcpyDeviceToHost, st));
-    MI355_CHECK_HIP(hipStreamSynchronize(st));
-    MI355_REQUIRE(!flags[IVF_FLAG_ENTRY], "%s: a list id outside [0, nlist=%lld), an order entry outside [0, G=%lld) or offsets that "
-                  "do not ascend within [0, G]", who, (long long)nlist, (long long)G);
-    MI355_REQUIRE(!flags[IVF_FLAG_CAP], "%s: a query's probed lists hold more than cap=%lld rows", who, (long long)cap);
-    return OK;
+    return ivf_check_flags(w.flag, nullptr, nlist, G, cap, who, st);
 }
 
 }  // extern "C"

@@ -203,14 +203,12 @@ constexpr i64 KM_MAX_WGS = ((i64)1 << 24) - 1;
 // flag word, counts [K], segoff [K + 1], and (dim > 0) the partial sums [max_segments][dim]
 static KmeansWs kmeans_carve(void* ws, i64 N, i64 K, int dim) {
     KmeansWs r{};
-    size_t off = 0;
-    char* base = ws ? (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255) : nullptr;
-    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align_up(bytes, 256); return p; };
-    r.flag = (unsigned*)take(sizeof(unsigned));
-    r.counts = (i64*)take((size_t)K * sizeof(i64));
-    r.segoff = (i64*)take((size_t)(K + 1) * sizeof(i64));
-    r.partial = (double*)take(dim > 0 ? (size_t)max_segments(N, K) * dim * sizeof(double) : 0);
-    r.total = off + 256;
+    WsCarver c(ws);
+    r.flag = (unsigned*)c.take(sizeof(unsigned));
+    r.counts = (i64*)c.take((size_t)K * sizeof(i64));
+    r.segoff = (i64*)c.take((size_t)(K + 1) * sizeof(i64));
+    r.partial = (double*)c.take(dim > 0 ? (size_t)max_segments(N, K) * dim * sizeof(double) : 0);
+    r.total = c.total();
     return r;
 }
 
@@ -348,7 +346,7 @@ int mi355_contingency(const int64_t* a, const int64_t* b, int64_t N, int64_t Ka,
     const size_t need = mi355_contingency_workspace_bytes(N, Ka, Kb);
     MI355_REQUIRE(workspace && workspace_bytes >= need, "%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
     hipStream_t st = (hipStream_t)stream;
-    unsigned* flag = (unsigned*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    unsigned* flag = (unsigned*)align256(workspace);
     RoctxRange range("kmeans/contingency");
     MI355_CHECK_HIP(hipMemsetAsync(flag, 0, sizeof(unsigned), st));
     MI355_CHECK_HIP(hipMemsetAsync(table, 0, (size_t)(Ka * Kb) * sizeof(int64_t), st));

@@ -212,24 +212,22 @@ static i64 pq_query_block(i64 Q, i64 G, int k) {
 }
 static PqWs pq_carve(void* ws, i64 Q, i64 G, int dim, int M, int k) {
     PqWs r{};
-    size_t off = 0;
-    char* base = ws ? (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255) : nullptr;
-    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align_up(bytes, 256); return p; };
+    WsCarver c(ws);
     const i64 qb = pq_query_block(Q, G, k);
-    r.qn = (float*)take((size_t)Q * dim * sizeof(float));
-    r.T = (float*)take((size_t)qb * M * PQ_CENTROIDS * sizeof(float));
+    r.qn = (float*)c.take((size_t)Q * dim * sizeof(float));
+    r.T = (float*)c.take((size_t)qb * M * PQ_CENTROIDS * sizeof(float));
     if (k >= 1 && k <= SMALL_K) {
         const size_t n = (size_t)qb * cdiv(G, PQ_CHUNK) * k;
-        r.cand_val = (float*)take(n * sizeof(float));
-        r.cand_idx = (i64*)take(n * sizeof(i64));
+        r.cand_val = (float*)c.take(n * sizeof(float));
+        r.cand_idx = (i64*)c.take(n * sizeof(i64));
         r.topk_bytes = topk_ws_bytes(qb, (i64)cdiv(G, PQ_CHUNK) * k, k);
-        r.topk = take(r.topk_bytes);
+        r.topk = c.take(r.topk_bytes);
     } else if (k > SMALL_K) {
-        r.S = (float*)take((size_t)qb * G * sizeof(float));
+        r.S = (float*)c.take((size_t)qb * G * sizeof(float));
         r.topk_bytes = topk_ws_bytes(qb, G, k);
-        r.topk = take(r.topk_bytes);
+        r.topk = c.take(r.topk_bytes);
     }
-    r.total = off + 256;
+    r.total = c.total();
     return r;
 }
 
@@ -332,7 +330,7 @@ int mi355_pq_encode(const float* rows, int64_t R, int dim, int M, int rows_are_n
     if (R == 0) return OK;
     hipStream_t st = (hipStream_t)stream;
     RoctxRange range("pq/encode");
-    float* nbuf = rows_are_normalized ? nullptr : (float*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    float* nbuf = rows_are_normalized ? nullptr : (float*)align256(workspace);
     const size_t lds = (size_t)PQ_CENTROIDS * (dim / M) * sizeof(float);
     for (int64_t r0 = 0; r0 < R; r0 += PQ_ENC_BLOCK) {
         const int64_t rn = R - r0 < PQ_ENC_BLOCK ? R - r0 : PQ_ENC_BLOCK;
@@ -373,7 +371,7 @@ int mi355_pq_update(const float* rows, int64_t R, int dim, int M, int rows_are_n
     RoctxRange range("pq/update");
     const float* n = rows;
     if (!rows_are_normalized) {
-        float* nbuf = (float*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+        float* nbuf = (float*)align256(workspace);
         if (int e = mi355_l2_normalize_rows(rows, nbuf, R, dim, eps, stream)) return e;
         n = nbuf;
     }
@@ -480,7 +478,7 @@ int mi355_rescore_candidates(const float* queries, int64_t Q, int dim, float eps
     if (Q == 0 || R == 0) return OK;
     hipStream_t st = (hipStream_t)stream;
     RoctxRange range("pq/rescore candidates");
-    float* qn = (float*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    float* qn = (float*)align256(workspace);
     if (int e = mi355_l2_normalize_rows(queries, qn, Q, dim, eps, stream)) return e;
     const bool vec = ld % 4 == 0 && dim % 4 == 0 && ((uintptr_t)rows & 15) == 0;
     for (int64_t q0 = 0; q0 < Q; q0 += RESCORE_QBLOCK) {

@@ -95,21 +95,19 @@ i64 range_query_block(i64 Q, i64 G) {
 
 RangeWs range_carve(void* ws, i64 Q, i64 G, int D, size_t (*planes_bytes)(i64, int), bool need_ginv) {
     RangeWs r{};
-    size_t off = 0;
-    char* base = ws ? (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255) : nullptr;
-    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align_up(bytes, 256); return p; };
-    r.offsets = (i64*)take((size_t)(Q + 1) * sizeof(i64));
+    WsCarver c(ws);
+    r.offsets = (i64*)c.take((size_t)(Q + 1) * sizeof(i64));
     if (Q > 0 && G > 0) {
-        r.cursor = (unsigned long long*)take(sizeof(unsigned long long));
-        r.w = carve(base ? base + off : nullptr, Q, G, D, 0, planes_bytes, need_ginv, false);
-        off += r.w.total - 256;                        // (carve's base is already 256-aligned here: its slack is not needed)
+        r.cursor = (unsigned long long*)c.take(sizeof(unsigned long long));
+        r.w = carve(c.next(), Q, G, D, 0, planes_bytes, need_ginv, false);
+        c.take(r.w.total - 256);                       // (carve's base is already 256-aligned here: its slack is not needed)
         const i64 qb = range_query_block(Q, G);
         const size_t cells = (size_t)qb * cdiv(G, RK_BN);
-        r.tstart = (i64*)take(cells * sizeof(i64));
-        r.tcount = (int*)take(cells * sizeof(int));
-        r.rowcnt = (i64*)take((size_t)qb * sizeof(i64));
+        r.tstart = (i64*)c.take(cells * sizeof(i64));
+        r.tcount = (int*)c.take(cells * sizeof(int));
+        r.rowcnt = (i64*)c.take((size_t)qb * sizeof(i64));
     }
-    r.total = off + 256;
+    r.total = c.total();
     return r;
 }
 

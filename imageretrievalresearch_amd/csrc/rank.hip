@@ -935,7 +935,7 @@ int topk_select(const float* vals, const i64* idxs, i64 Q, i64 rowlen, i64 in_st
                   topk_ws_bytes(Q, rowlen, k));
     const i64 per_row_max = level1_chunks(rowlen, k) * k;
     const size_t half = align_up((size_t)Q * per_row_max * (sizeof(float) + sizeof(i64)), 256);
-    char* base = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+    char* base = align256(ws);
     float* cv[2];
     i64* ci[2];
     for (int b = 0; b < 2; ++b) {
@@ -1016,24 +1016,22 @@ RankWs carve(void* ws, i64 Q, i64 G, int D, int k, size_t (*planes_bytes)(i64, i
     RankWs r{};
     const bool fused = need_S && fused_select(Q, G, k);
     const i64 qb = query_block(Q, G, need_S ? k : 0);
-    size_t off = 0;
-    char* base = ws ? (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255) : nullptr;
-    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align_up(bytes, 256); return p; };
-    r.qn = (float*)take((size_t)Q * D * sizeof(float));
+    WsCarver c(ws);
+    r.qn = (float*)c.take((size_t)Q * D * sizeof(float));
     const i64 q_split = need_S ? qb : (Q < 256 * 64 ? Q : 256 * 64);      // queries of one cos_gemm call
-    r.qs = take(planes_bytes ? planes_bytes(q_split, D) : 0);
-    r.ginv = (float*)take(need_ginv ? (size_t)G * sizeof(float) : 0);
+    r.qs = c.take(planes_bytes ? planes_bytes(q_split, D) : 0);
+    r.ginv = (float*)c.take(need_ginv ? (size_t)G * sizeof(float) : 0);
     if (fused) {
         const size_t ncand = (size_t)qb * cdiv(G, RK_BN) * k;
-        r.cand_val = (float*)take(ncand * sizeof(float));
-        r.cand_idx = (int*)take(ncand * sizeof(int));
+        r.cand_val = (float*)c.take(ncand * sizeof(float));
+        r.cand_idx = (int*)c.take(ncand * sizeof(int));
         r.topk_bytes = topk_ws_bytes(qb, cdiv(G, RK_BN) * (i64)k, k);
     } else {
-        r.S = (float*)take(need_S ? (size_t)qb * G * sizeof(float) : 0);
+        r.S = (float*)c.take(need_S ? (size_t)qb * G * sizeof(float) : 0);
         r.topk_bytes = k > 0 ? topk_ws_bytes(qb, G, k) : 0;
     }
-    r.topk = take(r.topk_bytes);
-    r.total = off + 256;
+    r.topk = c.take(r.topk_bytes);
+    r.total = c.total();
     return r;
 }
 
@@ -1353,7 +1351,7 @@ int nearest_centroid(const float* centroids, i64 K, const GalleryRows& g, i64 G,
     MI355_REQUIRE(query_block >= 0, "%s: query_block=%lld < 0", who, (long long)query_block);
     const size_t need = nearest_ws_bytes(K, G, dim, g.planes_bytes, g.f32 && !g.unit);
     MI355_REQUIRE(workspace && workspace_bytes >= need, "%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
-    char* base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    char* base = align256(workspace);
     unsigned long long* best = (unsigned long long*)base;
     const RankWs w = carve(base + align_up((size_t)G * sizeof(unsigned long long), 256), K, G, dim, 0, g.planes_bytes,
                            g.f32 && !g.unit, false);
@@ -1620,7 +1618,7 @@ int mi355_merge_packed_topk(const int32_t* packed, const int64_t* shard_offsets,
     MI355_REQUIRE(workspace && workspace_bytes >= mi355_merge_packed_workspace_bytes(Q, world, k),
                   "merge_packed_topk: workspace %zu < %zu bytes", workspace_bytes, mi355_merge_packed_workspace_bytes(Q, world, k));
     const size_t n = (size_t)Q * world * k;
-    char* base = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    char* base = align256(workspace);
     i64* ci = (i64*)base;
     float* cv = (float*)(base + align_up(n * sizeof(i64), 256));
     char* rest = base + align_up(n * sizeof(i64), 256) + align_up(n * sizeof(float), 256);

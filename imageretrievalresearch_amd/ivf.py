@@ -9,28 +9,27 @@ members of every cluster are its lists, and a query is scored against the rows o
 * ``index.update()`` ............................. after ``gallery.add``: the new rows go to their nearest list
 
 The rows are scanned where they lie in the gallery (fp32 or fp16), through the lists' ``order``; the index holds no copy of
-them.  Out of scope: ``ShardedGallery``, a list-ordered copy of the rows.
+them.  The lists themselves, ``probe``, ``stale`` and the rules for ``nprobe`` / ``probes`` are ``_lists._ListIndex``, shared with
+``IVFPQIndex``.  Out of scope: ``ShardedGallery``, a list-ordered copy of the rows.
 """
 from __future__ import annotations
 
-import numpy as np
 import torch
 
 from . import cluster as _cl
 from . import rank as _rank
 from ._lib import MI355Error, check, lib, stream_ptr
+from ._lists import MAX_K, _ListIndex
+from .rank import _is_int
 
-_MAX_K = 1024                       # largest k of any search, and the most lists a query probes
 _SLAB_BYTES = 256 << 20             # the candidate slab of one query block (12 B per slot) stays under this
 
 
-def _is_int(x) -> bool:
-    return isinstance(x, (int, np.integer)) and not isinstance(x, bool)
-
-
-class IVFIndex:
+class IVFIndex(_ListIndex):
     """The lists of a ``Gallery``: ``centroids`` (nlist, D) fp32, ``offsets`` (nlist + 1,) / ``order`` (rows,) int64 (the rows
     of list l are ``order[offsets[l]:offsets[l + 1]]``, ascending), ``counts`` (nlist,) int64, and a reference to the gallery."""
+
+    _STORE, _NOUN, _STORE_NOUN, _HINT = "gallery", "IVF index", "gallery", "call update()"
 
     def __init__(self, gallery, centroids: torch.Tensor, assignments: torch.Tensor):
         if not isinstance(gallery, _rank.Gallery):
@@ -38,19 +37,7 @@ class IVFIndex:
         if gallery.rows < 1:
             raise MI355Error("an IVF index needs a gallery with at least one row")
         self.gallery = gallery
-        self.centroids = _cl._centroids_of(centroids, gallery._resident())
-        self.nlist = int(self.centroids.shape[0])
-        if self.nlist >= 1 << 24:
-            raise MI355Error(f"nlist={self.nlist} must be below 2^24")
-        self._set_lists(_rank._int64_on(assignments, "assignments", gallery.rows, gallery.device))
-
-    def _set_lists(self, assignments: torch.Tensor) -> None:
-        self.assignments = assignments
-        self.offsets, self.order = _cl.cluster_members(assignments, self.nlist)
-        self.counts = self.offsets[1:] - self.offsets[:-1]
-        host = self.counts.cpu().numpy()                                    # the one read of the lists' lengths
-        self._longest = np.concatenate([[0], np.cumsum(np.sort(host)[::-1])])   # [n] = the rows of the n longest lists
-        self.rows = int(assignments.shape[0])
+        self._init_lists(_cl._centroids_of(centroids, gallery._resident()), assignments)
 
     @classmethod
     def build(cls, gallery, nlist: int, *, iters: int = 10, seed: int = 0, init: torch.Tensor | None = None) -> "IVFIndex":
@@ -60,18 +47,9 @@ class IVFIndex:
         r = gallery.kmeans(nlist, iters=iters, seed=seed, init=init)
         return cls(gallery, r.centroids, r.assignments)
 
-    @property
-    def nbytes(self) -> int:
-        """The index's size in bytes: centroids, assignments, offsets, order and counts (the rows belong to the gallery)."""
-        return sum(t.numel() * t.element_size() for t in (self.centroids, self.assignments, self.offsets, self.order, self.counts))
-
-    @property
-    def stale(self) -> bool:
-        """Rows were added to the gallery since the lists were made (``update()`` brings them in)."""
-        return self.rows != self.gallery.rows
-
     def update(self) -> "IVFIndex":
-        """After ``gallery.add``: ``assign_clusters`` of the new rows only against the unchanged centroids, then the CSR again."""
+        """After ``gallery.add`` (the index is ``stale``): ``assign_clusters`` of the new rows only against the unchanged
+        centroids, then the CSR again."""
         g = self.gallery
         if g.rows < self.rows:
             raise MI355Error(f"the gallery has {g.rows} rows but the index lists {self.rows}")
@@ -81,22 +59,10 @@ class IVFIndex:
             self._set_lists(torch.cat([self.assignments, a]))
         return self
 
-    def _fresh(self) -> None:
-        if self.stale:
-            raise MI355Error(f"the IVF index is stale: it lists {self.rows} rows but the gallery holds {self.gallery.rows} "
-                             "(call update())")
-
-    def _check_nprobe(self, nprobe) -> int:
-        top = min(self.nlist, _MAX_K)
-        if not _is_int(nprobe) or not 1 <= nprobe <= top:
-            raise MI355Error(f"nprobe={nprobe!r} outside [1, {top}] (min(nlist, {_MAX_K}))")
-        return int(nprobe)
-
-    def probe(self, queries: torch.Tensor, nprobe: int) -> torch.Tensor:
-        """(Q, nprobe) int64: the lists nearest to every query, nearest first - exactly the indices of
-        ``cosine_topk(queries, centroids, nprobe)``.  ``1 <= nprobe <= min(nlist, 1024)``."""
-        nprobe = self._check_nprobe(nprobe)
-        return _rank.cosine_topk(queries, self.centroids, nprobe, self.gallery.eps)[1]
+    def _queries(self, queries: torch.Tensor) -> torch.Tensor:
+        q = _rank._f32c(queries, "queries")
+        _rank._check_qg(q, self.gallery._resident())
+        return q
 
     def _block(self, Q: int, nprobe: int, cap: int, block) -> int:
         if block is not None:
@@ -131,24 +97,11 @@ class IVFIndex:
         the remaining slots are (-inf, -1).  ``1 <= k <= min(1024, rows)``.  The queries go through ``block`` at a time
         (default: what keeps the candidate slab under 256 MB); the result does not depend on it."""
         self._fresh()
-        top = min(_MAX_K, self.rows)
+        top = min(MAX_K, self.rows)
         if not _is_int(k) or not 1 <= k <= top:
-            raise MI355Error(f"selected index k out of range: k={k!r} outside [1, {top}] (min({_MAX_K}, rows))")
-        if (nprobe is None) == (probes is None):
-            raise MI355Error("give exactly one of nprobe and probes")
-        if nprobe is not None:
-            nprobe = self._check_nprobe(nprobe)
-        g = self.gallery
-        q = _rank._f32c(queries, "queries")
-        _rank._check_qg(q, g._resident())
-        Q = q.shape[0]
-        if probes is None:
-            probes = self.probe(q, nprobe) if Q else torch.empty((0, nprobe), dtype=torch.int64, device=q.device)
-        else:
-            if not torch.is_tensor(probes) or probes.dim() != 2 or probes.shape[0] != Q:
-                raise MI355Error(f"probes must be a (Q={Q}, nprobe) tensor")
-            nprobe = self._check_nprobe(int(probes.shape[1]))
-            probes = _rank._int64_on(probes.reshape(-1), "probes", Q * nprobe, q.device).view(Q, nprobe)
+            raise MI355Error(f"selected index k out of range: k={k!r} outside [1, {top}] (min({MAX_K}, rows))")
+        q, probes = self._probes(queries, nprobe, probes)
+        g, Q, nprobe = self.gallery, q.shape[0], probes.shape[1]
         gl = None if label_filter is None else g._labels_for(f'label_filter="{label_filter}"')
         filtered = _rank._rank_filter(Q, g.rows, q.device, query_labels, gl, label_filter, exclude) is not None
         cap = max(int(self._longest[nprobe]), int(k))
@@ -171,6 +124,4 @@ class IVFIndex:
         """(mean, per_query (Q,) float64): the share of ``gallery.search(queries, k)``'s indices that
         ``search(queries, k, nprobe)`` returns."""
         got = self.search(queries, k, nprobe)[1]
-        want = self.gallery.search(queries, k)[1]
-        per = (got.unsqueeze(2) == want.unsqueeze(1)).any(dim=1).sum(dim=1).double() / float(k)
-        return (float(per.mean()) if per.numel() else 1.0), per
+        return _rank._recall(got, self.gallery.search(queries, k)[1], k)

@@ -14,20 +14,20 @@ it, not for every row of the gallery as ``PQGallery.search`` does.
 The index codes nothing itself: a score is the PQ score of the gallery's own code row, bit for bit, so a search that probes
 every list returns exactly what ``pq.search`` returns.  It keeps a list-ordered copy of the codes (``list_codes[p] =
 pq.codes[order[p]]``, M bytes per row): every list is one contiguous byte range, which is what the scan reads; ``pq.codes``
-stays the record.  Out of scope: residual codes, an OPQ rotation, an index over a sharded PQ gallery.
+stays the record.  The lists, ``probe``, ``stale`` and the rules for ``nprobe`` / ``probes`` are ``_lists._ListIndex``, shared
+with ``IVFIndex``.  Out of scope: residual codes, an OPQ rotation, an index over a sharded PQ gallery.
 """
 from __future__ import annotations
 
-import numpy as np
 import torch
 
 from . import cluster as _cl
 from . import pq as _pq
 from . import rank as _rank
 from ._lib import MI355Error, check, lib, stream_ptr
+from ._lists import _ListIndex
 
 SCAN_CHUNK = 2048                   # positions of one scan workgroup (IVFPQ_CHUNK, csrc/ivfpq.hip)
-_MAX_NPROBE = 1024                  # the most lists a query probes: their running sums sit in LDS beside the table
 
 
 def _check_pq(pq) -> None:
@@ -38,10 +38,16 @@ def _check_pq(pq) -> None:
         raise MI355Error("an IVF-PQ index needs a PQGallery with at least one row")
 
 
-class IVFPQIndex:
+class IVFPQIndex(_ListIndex):
     """The lists of a ``PQGallery``: ``centroids`` (nlist, D) fp32, ``assignments`` (rows,), ``offsets`` (nlist + 1,) / ``order``
     (rows,) int64 (the rows of list l are ``order[offsets[l]:offsets[l + 1]]``, ascending), ``counts`` (nlist,) int64,
-    ``list_codes`` (rows, M) uint8 (the codes in list order) and a reference to ``pq``."""
+    ``list_codes`` (rows, M) uint8 (the codes in list order) and a reference to ``pq``.  ``stale``: rows were added to ``pq``
+    behind the index's back (``index.add`` keeps the two together)."""
+
+    _STORE, _NOUN, _STORE_NOUN = "pq", "IVF-PQ index", "PQGallery"
+    _HINT = "add rows through index.add, or build the index again"
+    _EXTRA = ("list_codes",)
+    list_codes = None
 
     def __init__(self, pq, centroids: torch.Tensor, assignments: torch.Tensor):
         _check_pq(pq)
@@ -51,22 +57,14 @@ class IVFPQIndex:
         c = centroids
         if c.dim() != 2 or c.shape[0] < 1 or c.shape[1] != pq.dim or c.device != pq.device:
             raise MI355Error(f"centroids must be (nlist, {pq.dim}) on {pq.device}, got {tuple(c.shape)} on {c.device}")
-        self.centroids = c = _rank._f32c(c, "centroids")
-        self.nlist = int(c.shape[0])
-        if self.nlist >= 1 << 24:
-            raise MI355Error(f"nlist={self.nlist} must be below 2^24")
-        self.list_codes = None
-        self._set_lists(_rank._int64_on(assignments, "assignments", pq.rows, pq.device))
+        self._init_lists(_rank._f32c(c, "centroids"), assignments)
 
-    def _set_lists(self, assignments: torch.Tensor) -> None:
-        self.assignments = assignments
-        self.offsets, self.order = _cl.cluster_members(assignments, self.nlist)
-        self.counts = self.offsets[1:] - self.offsets[:-1]
+    def _relist(self) -> None:
         _rank._retire(self.list_codes, self.pq.device)               # a queued search may still read the old copy
         self.list_codes = self.pq.codes.index_select(0, self.order)
-        host = self.counts.cpu().numpy()                                    # the one read of the lists' lengths
-        self._longest = np.concatenate([[0], np.cumsum(np.sort(host)[::-1])])   # [n] = the rows of the n longest lists
-        self.rows = int(assignments.shape[0])
+
+    def _queries(self, queries: torch.Tensor) -> torch.Tensor:
+        return self.pq._queries(queries, "search")
 
     @staticmethod
     def _check_rows(pq, rows) -> None:
@@ -104,23 +102,6 @@ class IVFPQIndex:
         pq = _pq.PQGallery.from_gallery(gallery, M, iters=pq_iters, seed=seed)
         return cls.build(pq, gallery, nlist, iters=iters, seed=seed)
 
-    @property
-    def nbytes(self) -> int:
-        """The index's size in bytes: centroids, assignments, offsets, order, counts and the list-ordered codes (``pq``'s own
-        codes and codebooks belong to the gallery)."""
-        return sum(t.numel() * t.element_size() for t in (self.centroids, self.assignments, self.offsets, self.order, self.counts,
-                                                          self.list_codes))
-
-    @property
-    def stale(self) -> bool:
-        """Rows were added to ``pq`` behind the index's back (``index.add`` keeps the two together)."""
-        return self.rows != self.pq.rows
-
-    def _fresh(self) -> None:
-        if self.stale:
-            raise MI355Error(f"the IVF-PQ index is stale: it lists {self.rows} rows but the PQGallery holds {self.pq.rows} "
-                             "(add rows through index.add, or build the index again)")
-
     def add(self, embeddings: torch.Tensor, labels: torch.Tensor | None = None) -> "IVFPQIndex":
         """``pq.add(embeddings, labels)``, then ``assign_clusters`` of the new rows against the unchanged centroids, then the
         lists and ``list_codes`` again."""
@@ -131,18 +112,6 @@ class IVFPQIndex:
             a, _ = _cl.assign_clusters(e, self.centroids, eps=self.pq.eps)
             self._set_lists(torch.cat([self.assignments, a]))
         return self
-
-    def _check_nprobe(self, nprobe) -> int:
-        top = min(self.nlist, _MAX_NPROBE)
-        if not _pq._is_int(nprobe) or not 1 <= nprobe <= top:
-            raise MI355Error(f"nprobe={nprobe!r} outside [1, {top}] (min(nlist, {_MAX_NPROBE}))")
-        return int(nprobe)
-
-    def probe(self, queries: torch.Tensor, nprobe: int) -> torch.Tensor:
-        """(Q, nprobe) int64: the lists nearest to every query, nearest first - exactly the indices of
-        ``cosine_topk(queries, centroids, nprobe)``.  ``1 <= nprobe <= min(nlist, 1024)``."""
-        nprobe = self._check_nprobe(nprobe)
-        return _rank.cosine_topk(queries, self.centroids, nprobe, self.pq.eps)[1]
 
     def _scan(self, q, probes, cap, k, idx_offset, filt):
         pq, dev, L = self.pq, self.pq.device, lib()
@@ -172,22 +141,8 @@ class IVFPQIndex:
         self._fresh()
         pq = self.pq
         k, R = _pq._shortlist_length(pq, k, refine, shortlist)
-        if (nprobe is None) == (probes is None):
-            raise MI355Error("give exactly one of nprobe and probes")
-        if probes is None:
-            nprobe = self._check_nprobe(nprobe)
-        else:
-            if not torch.is_tensor(probes) or probes.dim() != 2:
-                raise MI355Error("probes must be a (Q, nprobe) tensor")
-            nprobe = self._check_nprobe(int(probes.shape[1]))
-        q = pq._queries(queries, "search")
-        Q = q.shape[0]
-        if probes is None:
-            probes = self.probe(q, nprobe) if Q else torch.empty((0, nprobe), dtype=torch.int64, device=q.device)
-        else:
-            if probes.shape[0] != Q:
-                raise MI355Error(f"probes must be a (Q={Q}, nprobe) tensor, got {tuple(probes.shape)}")
-            probes = _rank._int64_on(probes.reshape(-1), "probes", Q * nprobe, q.device).view(Q, nprobe)
+        q, probes = self._probes(queries, nprobe, probes)
+        Q, nprobe = q.shape[0], probes.shape[1]
         gl = None if label_filter is None else pq._labels_for(f'label_filter="{label_filter}"')
         filt = _rank._rank_filter(Q, self.rows, q.device, query_labels, gl, label_filter, exclude)
         cap = max(int(self._longest[nprobe]), R)
@@ -203,6 +158,4 @@ class IVFPQIndex:
         if exact is not None and (not isinstance(exact, _rank.Gallery) or len(exact) != self.rows):
             raise MI355Error(f"recall needs exact=None or a Gallery of the same {self.rows} rows")
         got = self.search(queries, k, nprobe, **search_kwargs)[1]
-        want = (self.pq if exact is None else exact).search(queries, k)[1]
-        per = (got.unsqueeze(2) == want.unsqueeze(1)).any(dim=1).sum(dim=1).double() / float(k)
-        return (float(per.mean()) if per.numel() else 1.0), per
+        return _rank._recall(got, (self.pq if exact is None else exact).search(queries, k)[1], k)

@@ -12,12 +12,11 @@ D = 1536 and M = 96 a 64th of the fp32 row, so that a million rows are 96 MB and
 The format is approximate against the fp32 cosine, but its arithmetic is specified bit for bit in include/mi355_retrieval.h: a
 score depends on its query, its code row and the codebooks alone, and a NumPy model (tests/pq_ref.py) reproduces every bit of
 the codes, the tables, the scores, the top-k and the trained codebooks.  ``pq.ivf(rows, nlist)`` puts IVF lists over the codes
-(ivfpq.py).  Out of scope: residual codes, an OPQ rotation, a sharded PQ gallery, range search / query expansion over
+(ivfpq.py).  Growth of the code buffer, labels and recall come from ``rank._RowStore``, as for the other galleries.  Out of scope: residual codes, an OPQ rotation, a sharded PQ gallery, range search / query expansion over
 codes, training on fp16 rows.
 """
 from __future__ import annotations
 
-import numpy as np
 import torch
 
 from . import cluster as _cl
@@ -28,10 +27,7 @@ CENTROIDS = 256                     # centroids of every sub-quantiser: a code i
 MAX_M, MAX_DSUB = 128, 64
 SCAN_CHUNK = 2048                   # rows of one scan workgroup (PQ_CHUNK, csrc/pq.hip)
 _MAX_K = 1024                       # largest k of any search, and the longest shortlist
-
-
-def _is_int(x) -> bool:
-    return isinstance(x, (int, np.integer)) and not isinstance(x, bool)
+_is_int = _rank._is_int
 
 
 def _shortlist_length(pq: "PQGallery", k, refine, shortlist):
@@ -72,7 +68,7 @@ def _refined_topk(pq: "PQGallery", q: torch.Tensor, vals: torch.Tensor, idx: tor
     return v, i
 
 
-class PQGallery:
+class PQGallery(_rank._RowStore):
     """Resident product-quantised gallery.  ``codes`` (rows, M) uint8, ``codebooks`` (M, 256, dim / M) fp32.  A search builds
     one table ``T[m][c] = qn_m . codebooks[m][c]`` per query and scores a row as the sum of its M table entries (four
     accumulators, a fixed order); order, ties, NaN queries and pads as ``cosine_topk``.  Equal code rows score equal bits, so
@@ -81,7 +77,8 @@ class PQGallery:
 
     def __init__(self, dim: int, device, M: int, codebooks: torch.Tensor | None = None, capacity: int = 0,
                  eps: float = _rank._EPS):
-        self.dim, self.device, self.M, self.eps = int(dim), torch.device(device), int(M), eps
+        super().__init__(dim, device, eps)
+        self.M = int(M)
         if self.device.type == "cuda" and self.device.index is None:       # "cuda": the index tensors on it report
             self.device = torch.device("cuda", torch.cuda.current_device())
         if not _is_int(M) or not 4 <= M <= MAX_M or M % 4:
@@ -91,10 +88,8 @@ class PQGallery:
         self.dsub = self.dim // self.M
         if self.dsub > MAX_DSUB:
             raise MI355Error(f"a PQGallery needs dim / M <= {MAX_DSUB}, got {self.dsub}")
-        self.rows = 0
         self._codes = torch.empty((max(int(capacity), 0), self.M), dtype=torch.uint8, device=self.device)
         self._codebooks = None
-        self.labels = None
         self.train_counts = None
         if codebooks is not None:
             cb = _rank._f32c(codebooks, "codebooks")
@@ -171,40 +166,17 @@ class PQGallery:
         return pq._append(gallery.data, gallery.labels, normalized=True)
 
     # ---- the resident rows
-    def _reserve(self, n):
-        if n > self._codes.shape[0]:
-            cap = max(n, int(self._codes.shape[0] * 1.5) + 1024)
-            codes = torch.empty((cap, self.M), dtype=torch.uint8, device=self.device)
-            codes[: self.rows].copy_(self._codes[: self.rows])
-            _rank._retire(self._codes, self.device)              # the queued copy still reads the old buffer
-            self._codes = codes
+    _BUFFERS = ("_codes",)
 
-    def _append(self, e: torch.Tensor, labels, normalized: bool):
-        n = e.shape[0]
-        self._reserve(self.rows + n)
-        if n:
-            self._encode(e, normalized, self._codes[self.rows: self.rows + n])
-        if labels is not None:
-            lab = labels.to(self.device, torch.int64)
-            if self.labels is not None:
-                _rank._retire(self.labels, self.device)
-                lab = torch.cat([self.labels, lab])
-            self.labels = lab
-        self.rows += n
-        return self
+    def _write(self, e: torch.Tensor, r0: int, normalized: bool) -> None:
+        self._encode(e, normalized, self._codes[r0: r0 + e.shape[0]])
 
     def add(self, embeddings: torch.Tensor, labels: torch.Tensor | None = None):
-        if self._codebooks is None:
-            raise MI355Error("add: the PQGallery has no codebooks yet (train() it, or pass codebooks=)")
-        e = _rank._f32c(embeddings, "embeddings")
-        if e.dim() != 2 or e.shape[1] != self.dim:
-            raise MI355Error(f"gallery rows must be (n,{self.dim}), got {tuple(e.shape)}")
+        self._trained("add")
+        e = self._new_rows(embeddings)
         if e.device != self.device:
             raise MI355Error(f"embeddings are on {e.device} but the gallery lives on {self.device}")
         return self._append(e, labels, normalized=False)
-
-    def __len__(self):
-        return self.rows
 
     @property
     def codes(self) -> torch.Tensor:
@@ -230,9 +202,6 @@ class PQGallery:
     def _trained(self, what: str) -> None:
         if self._codebooks is None:
             raise MI355Error(f"{what}: the PQGallery has no codebooks yet (train() it, or pass codebooks=)")
-
-    def _labels_for(self, what: str) -> torch.Tensor:
-        return _rank._need_labels(self.labels, self.rows, what, "gallery labels: add(embeddings, labels)")
 
     def _queries(self, queries: torch.Tensor, what: str) -> torch.Tensor:
         self._trained(what)
@@ -290,12 +259,7 @@ class PQGallery:
         """(mean, per_query (Q,) float64): the share of ``exact.search(queries, k)``'s indices that ``search(queries, k,
         **search_kwargs)`` returns; ``exact`` is a ``Gallery`` of the same rows (pass ``refine=exact`` to measure the refined
         search)."""
-        if not isinstance(exact, _rank.Gallery) or len(exact) != self.rows:
-            raise MI355Error(f"recall needs a Gallery of the same {self.rows} rows")
-        got = self.search(queries, k, **search_kwargs)[1]
-        want = exact.search(queries, k)[1]
-        per = (got.unsqueeze(2) == want.unsqueeze(1)).any(dim=1).sum(dim=1).double() / float(k)
-        return (float(per.mean()) if per.numel() else 1.0), per
+        return self._recall_against(exact, queries, k, **search_kwargs)
 
     def ivf(self, rows, nlist: int, **kw):
         """The ``IVFPQIndex`` over these codes with ``nlist`` lists: ``IVFPQIndex.build(self, rows, nlist, **kw)`` (``iters``,

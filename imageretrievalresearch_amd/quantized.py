@@ -3,7 +3,8 @@
 ``Int8Gallery`` is a class of its own rather than a third ``dtype=`` of ``Gallery``: it carries extra state (the scales) and
 offers part of ``Gallery``'s surface only - ``add``, ``search`` (filters included), ``range_search`` and ``recall``.  Its
 searches go through the same ``_topk`` / ``_range`` as every other gallery (rank.py), so the workspace cache, the device
-checks and the filter arguments are shared; the rows travel as a ``_Rows`` of dtype int8.
+checks and the filter arguments are shared; the rows travel as a ``_Rows`` of dtype int8.  Growth of the two buffers, labels
+and recall come from ``rank._RowStore``, the base it shares with ``Gallery`` and ``PQGallery``.
 
 The format and its arithmetic are specified bit for bit in include/mi355_retrieval.h: the integer dot products are exact, so
 a score depends on its query and its row alone - never on the number of queries, the kernel (GEMV or GEMM), its tiling or
@@ -23,7 +24,7 @@ def _stride(dim: int) -> int:
     return (dim + _SEGMENT - 1) // _SEGMENT * _SEGMENT
 
 
-class Int8Gallery:
+class Int8Gallery(_rank._RowStore):
     """Resident int8 gallery.  A row is stored as ``codes = clamp(rint(n * 127 / amax), -127, 127)`` of its L2-normalised fp32
     row ``n`` (``amax = max |n_i|``) beside ``scale = amax / 127``: ``ld + 4`` bytes per row, ``ld`` = ``dim`` rounded up to a
     multiple of 128.  A search keeps about 15 bits of each query (two int8 planes), multiplies on the int8 matrix pipe and
@@ -32,52 +33,25 @@ class Int8Gallery:
     top-k is approximate (``recall``)."""
 
     def __init__(self, dim: int, device, capacity: int = 0, eps: float = _rank._EPS):
-        self.dim, self.device, self.eps = int(dim), torch.device(device), eps
+        super().__init__(dim, device, eps)
         if not 1 <= self.dim <= _MAX_DIM:
             raise MI355Error(f"an Int8Gallery needs 1 <= dim <= {_MAX_DIM}, got {dim}")
-        self.rows = 0
         self._ld = _stride(self.dim)
         cap = max(int(capacity), 0)
         self._codes = torch.empty((cap, self._ld), dtype=torch.int8, device=self.device)
         self._scales = torch.empty((cap,), dtype=torch.float32, device=self.device)
-        self.labels = None
 
-    def _reserve(self, n):
-        if n > self._codes.shape[0]:
-            cap = max(n, int(self._codes.shape[0] * 1.5) + 1024)
-            codes = torch.empty((cap, self._ld), dtype=torch.int8, device=self.device)
-            scales = torch.empty((cap,), dtype=torch.float32, device=self.device)
-            codes[: self.rows].copy_(self._codes[: self.rows])
-            scales[: self.rows].copy_(self._scales[: self.rows])
-            _rank._retire(self._codes, self.device)          # the queued copies still read the old buffers
-            _rank._retire(self._scales, self.device)
-            self._codes, self._scales = codes, scales
+    _BUFFERS = ("_codes", "_scales")
 
-    def _append(self, e: torch.Tensor, labels, normalized: bool):
+    def _write(self, e: torch.Tensor, r0: int, normalized: bool) -> None:
         n = e.shape[0]
-        self._reserve(self.rows + n)
-        if n:
-            codes, scales = self._codes[self.rows: self.rows + n], self._scales[self.rows: self.rows + n]
-            with torch.cuda.device(e.device):
-                check(lib().mi355_gallery_to_i8(e.data_ptr(), n, self.dim, int(normalized), self.eps, codes.data_ptr(),
-                                                n * self._ld, scales.data_ptr(), stream_ptr(e.device)))
-        if labels is not None:
-            lab = labels.to(self.device, torch.int64)
-            if self.labels is not None:
-                _rank._retire(self.labels, self.device)
-                lab = torch.cat([self.labels, lab])
-            self.labels = lab
-        self.rows += n
-        return self
+        codes, scales = self._codes[r0: r0 + n], self._scales[r0: r0 + n]
+        with torch.cuda.device(e.device):
+            check(lib().mi355_gallery_to_i8(e.data_ptr(), n, self.dim, int(normalized), self.eps, codes.data_ptr(),
+                                            n * self._ld, scales.data_ptr(), stream_ptr(e.device)))
 
     def add(self, embeddings: torch.Tensor, labels: torch.Tensor | None = None):
-        e = _rank._f32c(embeddings, "embeddings")
-        if e.dim() != 2 or e.shape[1] != self.dim:
-            raise MI355Error(f"gallery rows must be (n,{self.dim}), got {tuple(e.shape)}")
-        return self._append(e, labels, normalized=False)
-
-    def __len__(self):
-        return self.rows
+        return self._append(self._new_rows(embeddings), labels, normalized=False)
 
     @property
     def codes(self) -> torch.Tensor:
@@ -101,9 +75,6 @@ class Int8Gallery:
     def _resident(self) -> _rank._Rows:
         return _rank._Rows(self._codes, self.rows, self.dim, True, None, self._scales)
 
-    def _labels_for(self, what: str) -> torch.Tensor:
-        return _rank._need_labels(self.labels, self.rows, what, "gallery labels: add(embeddings, labels)")
-
     def search(self, queries: torch.Tensor, k: int, idx_offset: int = 0, *, query_labels: torch.Tensor | None = None,
                label_filter: str | None = None, exclude: torch.Tensor | None = None):
         """Top-k of ``queries`` against the resident rows, arguments and result as ``Gallery.search`` (without ``qe``)."""
@@ -122,9 +93,4 @@ class Int8Gallery:
     def recall(self, queries: torch.Tensor, k: int, exact: "_rank.Gallery"):
         """(mean, per_query (Q,) float64): the share of ``exact.search(queries, k)``'s indices that ``search(queries, k)``
         returns; ``exact`` is a ``Gallery`` of the same rows."""
-        if not isinstance(exact, _rank.Gallery) or len(exact) != self.rows:
-            raise MI355Error(f"recall needs a Gallery of the same {self.rows} rows")
-        got = self.search(queries, k)[1]
-        want = exact.search(queries, k)[1]
-        per = (got.unsqueeze(2) == want.unsqueeze(1)).any(dim=1).sum(dim=1).double() / float(k)
-        return (float(per.mean()) if per.numel() else 1.0), per
+        return self._recall_against(exact, queries, k)

@@ -20,7 +20,8 @@ The gallery side of every search is one ``_Rows`` (buffer, dtype, rows, dim, row
 planes): a tensor argument, a ``PreparedGallery``, a ``Gallery`` and a ``ShardedGallery`` shard all become one.  Top-k, range
 and ROC histogram are one function each (``_topk``, ``_range``, ``_roc_hist``) that checks the arguments once and picks the
 fp32, fp16 or int8 C entry from ``_ENTRIES``; the public functions and methods are wrappers that add their own labels.  (int8 rows
-come from an ``Int8Gallery``, quantized.py, and have the top-k and range entries only.)
+come from an ``Int8Gallery``, quantized.py, and have the top-k and range entries only.)  ``Gallery``, ``Int8Gallery`` and
+``PQGallery`` (pq.py) grow their buffers, keep their labels and measure recall through one base, ``_RowStore``.
 """
 from __future__ import annotations
 
@@ -34,6 +35,11 @@ from ._lib import (DTYPE_F16, DTYPE_F32, LABEL_ANY, LABEL_DIFFERENT, LABEL_SAME,
                    require_cuda, stream_ptr)
 
 _EPS = 1e-6
+
+
+def _is_int(x) -> bool:
+    """An integer argument: a Python or NumPy integer, never a bool."""
+    return isinstance(x, (int, np.integer)) and not isinstance(x, bool)
 
 
 def _f32c(t: torch.Tensor, name: str) -> torch.Tensor:
@@ -555,7 +561,7 @@ def _f16_stride(dim: int) -> int:
 # ---- alpha query expansion (alpha-QE) and database-side augmentation (DBA): Radenovic, Tolias and Chum, TPAMI 2018
 def _qe_args(n, alpha):
     """(n, alpha) checked: n an integer >= 1, alpha a finite float >= 0."""
-    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or int(n) < 1:
+    if not _is_int(n) or int(n) < 1:
         raise MI355Error(f"query expansion needs n >= 1 neighbours, got {n!r}")
     try:
         a = float(alpha)
@@ -622,7 +628,77 @@ def expand_queries(queries: torch.Tensor, gallery: torch.Tensor, n: int, alpha: 
     return _expand_rows(q, True, g, torch.float32, g.shape[0], D, vals, idx, alpha, eps, idx_offset)
 
 
-class Gallery:
+def _recall(got_idx: torch.Tensor, want_idx: torch.Tensor, k: int):
+    """(mean, per_query (Q,) float64): the share of each row of ``want_idx`` (Q, k) that the same row of ``got_idx`` holds;
+    no query: (1.0, empty)."""
+    per = (got_idx.unsqueeze(2) == want_idx.unsqueeze(1)).any(dim=1).sum(dim=1).double() / float(k)
+    return (float(per.mean()) if per.numel() else 1.0), per
+
+
+class _RowStore:
+    """What ``Gallery``, ``Int8Gallery`` (quantized.py) and ``PQGallery`` (pq.py) share: ``rows`` labelled rows of ``dim``
+    columns on ``device``, resident in the buffers a class names in ``_BUFFERS`` (one row each per gallery row, all of one
+    capacity), which only grow.  A class says how a block of rows is written (``_write``); growth, labels and recall are here."""
+
+    _BUFFERS: tuple = ()
+
+    def __init__(self, dim: int, device, eps: float):
+        self.dim, self.device, self.eps = int(dim), torch.device(device), eps
+        self.rows, self.labels = 0, None
+
+    def __len__(self):
+        return self.rows
+
+    def _reserve(self, n: int) -> None:
+        """Room for ``n`` rows: past the capacity every buffer moves to one of ``max(n, 1.5 * capacity + 1024)`` rows."""
+        old_cap = getattr(self, self._BUFFERS[0]).shape[0]
+        if n > old_cap:
+            cap = max(n, int(old_cap * 1.5) + 1024)
+            for name in self._BUFFERS:
+                old = getattr(self, name)
+                new = torch.empty((cap,) + tuple(old.shape[1:]), dtype=old.dtype, device=self.device)
+                new[: self.rows].copy_(old[: self.rows])
+                _retire(old, self.device)                        # the queued copy still reads the old buffer
+                setattr(self, name, new)
+
+    def _add_labels(self, labels) -> None:
+        """The labels of a block of rows behind those held so far (int64, on the device); None leaves them as they are."""
+        if labels is not None:
+            lab = labels.to(self.device, torch.int64)
+            if self.labels is not None:
+                _retire(self.labels, self.device)
+                lab = torch.cat([self.labels, lab])
+            self.labels = lab
+
+    def _append(self, e: torch.Tensor, labels, **how):
+        """The checked (n, dim) fp32 rows ``e`` behind the resident ones: ``_write(e, first_row, **how)`` fills the buffers."""
+        n = e.shape[0]
+        self._reserve(self.rows + n)
+        if n:
+            self._write(e, self.rows, **how)
+        self._add_labels(labels)
+        self.rows += n
+        return self
+
+    def _new_rows(self, embeddings: torch.Tensor) -> torch.Tensor:
+        """The argument of ``add`` as contiguous fp32 rows on the GPU, (n, dim)."""
+        e = _f32c(embeddings, "embeddings")
+        if e.dim() != 2 or e.shape[1] != self.dim:
+            raise MI355Error(f"gallery rows must be (n,{self.dim}), got {tuple(e.shape)}")
+        return e
+
+    def _labels_for(self, what: str) -> torch.Tensor:
+        return _need_labels(self.labels, self.rows, what, "gallery labels: add(embeddings, labels)")
+
+    def _recall_against(self, exact, queries: torch.Tensor, k: int, **search_kwargs):
+        """``_recall`` of ``search(queries, k, **search_kwargs)`` against the search of ``exact``, a ``Gallery`` of the same rows."""
+        if not isinstance(exact, Gallery) or len(exact) != self.rows:
+            raise MI355Error(f"recall needs a Gallery of the same {self.rows} rows")
+        got = self.search(queries, k, **search_kwargs)[1]
+        return _recall(got, exact.search(queries, k)[1], k)
+
+
+class Gallery(_RowStore):
     """Resident gallery: rows are L2-normalised once when added and stay in HBM (the gallery is *born* on the
     GPU that embedded it).  ``search`` is then one fused call per query batch instead of the reference's per-query cosine +
     topk pair.
@@ -636,45 +712,30 @@ class Gallery:
     def __init__(self, dim: int, device, capacity: int = 0, eps: float = _EPS, dtype: torch.dtype = torch.float32):
         if dtype not in (torch.float32, torch.float16):
             raise MI355Error(f"Gallery dtype must be torch.float32 or torch.float16, got {dtype}")
-        self.dim, self.device, self.eps, self.dtype = int(dim), torch.device(device), eps, dtype
+        super().__init__(dim, device, eps)
+        self.dtype = dtype
         if dtype == torch.float16 and self.dim < 1:
             raise MI355Error(f"an fp16 Gallery needs dim >= 1, got {dim}")
-        self.rows = 0
         self._ld = _f16_stride(self.dim) if dtype == torch.float16 else self.dim
         self._buf = torch.empty((max(capacity, 0), self._ld), dtype=dtype, device=self.device)
-        self.labels = None
         self._prepared, self._prepared_rows = None, 0
         self._knn, self._rerank = {}, {}                         # per k1 / (k1, k2); dropped by add
         self._ivf = {}                                           # per (nlist, iters, seed); dropped by add
 
-    def _reserve(self, n):
-        if n > self._buf.shape[0]:
-            cap = max(n, int(self._buf.shape[0] * 1.5) + 1024)
-            nb = torch.empty((cap, self._ld), dtype=self.dtype, device=self.device)
-            nb[: self.rows].copy_(self._buf[: self.rows])
-            _retire(self._buf, self.device)
-            self._buf = nb
+    _BUFFERS = ("_buf",)
 
-    def add(self, embeddings: torch.Tensor, labels: torch.Tensor | None = None):
-        e = _f32c(embeddings, "embeddings")
-        if e.dim() != 2 or e.shape[1] != self.dim:
-            raise MI355Error(f"gallery rows must be (n,{self.dim}), got {tuple(e.shape)}")
+    def _write(self, e: torch.Tensor, r0: int) -> None:
         n = e.shape[0]
-        self._reserve(self.rows + n)
-        if n and self.dtype == torch.float16:
-            out = self._buf[self.rows: self.rows + n]
+        out = self._buf[r0: r0 + n]
+        if self.dtype == torch.float16:
             with torch.cuda.device(e.device):
                 check(lib().mi355_gallery_to_f16(e.data_ptr(), n, self.dim, 0, self.eps, out.data_ptr(),
                                                  _gallery_f16_bytes(n, self.dim), stream_ptr(e.device)))
-        elif n:
-            l2_normalize_rows(e, self.eps, out=self._buf[self.rows: self.rows + n])
-        if labels is not None:
-            lab = labels.to(self.device, torch.int64)
-            if self.labels is not None:
-                _retire(self.labels, self.device)
-                lab = torch.cat([self.labels, lab])
-            self.labels = lab
-        self.rows += n
+        else:
+            l2_normalize_rows(e, self.eps, out=out)
+
+    def add(self, embeddings: torch.Tensor, labels: torch.Tensor | None = None):
+        self._append(self._new_rows(embeddings), labels)
         self._knn, self._rerank = {}, {}
         self._ivf = {}
         return self
@@ -689,17 +750,11 @@ class Gallery:
         fresh = self._prepared is not None and self._prepared_rows == self.rows
         return _Rows(self._buf, self.rows, self.dim, True, self._prepared.planes if fresh else None)
 
-    def _labels_for(self, what: str) -> torch.Tensor:
-        return _need_labels(self.labels, self.rows, what, "gallery labels: add(embeddings, labels)")
-
     @property
     def nbytes(self) -> int:
         """Resident footprint in bytes: the row buffer at its current capacity, plus the bf16 planes of ``prepare()``."""
         p = self._prepared
         return self._buf.numel() * self._buf.element_size() + (p.planes.numel() if p is not None else 0)
-
-    def __len__(self):
-        return self.rows
 
     def prepare(self):
         """Split the resident rows once into the GEMM's bf16 planes (PreparedGallery, +6 B per element): searches with k <= 8
@@ -1219,7 +1274,7 @@ def _cmc_ranks(ranks):
         rs = list(ranks)
     except TypeError:
         raise MI355Error(f"ranks must be a sequence of positive integers, got {ranks!r}") from None
-    if not rs or any(isinstance(r, bool) or not isinstance(r, (int, np.integer)) or int(r) < 1 for r in rs):
+    if not rs or any(not _is_int(r) or int(r) < 1 for r in rs):
         raise MI355Error(f"ranks must be a non-empty sequence of positive integers, got {ranks!r}")
     return sorted({int(r) for r in rs})
 

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from ._lib import DTYPE_F16, DTYPE_F32, MI355Error, check, lib, require_cuda, stream_ptr
-from .rank import _EPS, Gallery, _check_qg, _f32c, _int64_on, l2_normalize_rows, topk
+from .rank import _EPS, Gallery, _check_qg, _f32c, _int64_on, _is_int, l2_normalize_rows, topk
 
 MAX_K1 = 32          # MI355_KR_MAX_K1
 MAX_SHORTLIST = 1024
@@ -40,7 +40,7 @@ class Csr(NamedTuple):
 
 
 def _int_in(name: str, v, lo: int, hi: int) -> int:
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+    if not _is_int(v) or not lo <= int(v) <= hi:
         raise MI355Error(f"{name} must be an integer in [{lo}, {hi}], got {v!r}")
     return int(v)
 
@@ -63,12 +63,12 @@ def rerank_params(G: int, k, k1=20, k2=6, lam=0.3, shortlist=None):
         raise MI355Error(f"lam must be a float in [0, 1], got {lam!r}") from None
     if not np.isfinite(lam) or not 0.0 <= lam <= 1.0:
         raise MI355Error(f"lam must be a finite float in [0, 1], got {lam!r}")
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or int(k) < 1:
+    if not _is_int(k) or int(k) < 1:
         raise MI355Error(f"selected index k out of range: k={k!r}, gallery rows={G}")
     k = int(k)
     top = min(G, MAX_SHORTLIST)
     K = min(G, max(k, 100)) if shortlist is None else shortlist
-    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not k <= int(K) <= top:
+    if not _is_int(K) or not k <= int(K) <= top:
         raise MI355Error(f"shortlist must be an integer with k={k} <= shortlist <= min(gallery rows, {MAX_SHORTLIST}) = {top}, "
                          f"got {K!r}")
     return k, k1, k2, lam, int(K)

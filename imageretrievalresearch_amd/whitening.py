@@ -141,7 +141,7 @@ class Whitening:
         and sorted descending, each eigenvector signed so that its component of largest magnitude (lowest index on a tie) is
         positive, scale_j = (lambda_j + ridge * lambda_0) ** -power, matrix = diag(scale[:d]) V[:, :d]^T, bias = -matrix mu;
         both rounded once to fp32.  power 0.5 whitens, 0 is the plain PCA rotation / truncation.  Needs no GPU."""
-        if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
+        if not _rank._is_int(n):
             raise MI355Error(f"n must be an integer row count, got {n!r}")
         n = int(n)
         if n < 2:
@@ -151,7 +151,7 @@ class Whitening:
             raise MI355Error(f"moments must be sum (D,) and outer (D, D), got {tuple(s.shape)} and {tuple(o.shape)}")
         D = int(s.shape[0])
         d = D if dim_out is None else dim_out
-        if isinstance(d, bool) or not isinstance(d, (int, np.integer)) or not 1 <= int(d) <= D:
+        if not _rank._is_int(d) or not 1 <= int(d) <= D:
             raise MI355Error(f"dim_out must be an integer in [1, {D}], got {dim_out!r}")
         d = int(d)
         try:

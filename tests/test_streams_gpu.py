@@ -97,14 +97,14 @@ def test_a_gallery_and_its_indexes_change_streams(dtype):
 _GROW_ROWS = 4096
 
 
-def _grow(make, read, buffers):
+def _grow(make, read, buffers, width=SC.D):
     """A gallery built on the default stream with capacity == rows grows inside ``add()`` on a side stream behind a delay;
     the default stream at once allocates and fills tensors of the old buffers' byte sizes.  Without ``record_stream`` in
     ``_reserve`` the old block is back in the default stream's pool while the copy out of it is still queued."""
     n = _GROW_ROWS
     H.cycles_per_ms()                                           # calibrated, and the fill kernel loaded, before the race starts
     torch.full((16,), 0x5A, dtype=torch.uint8, device=DEV)
-    rows, labels = SC.randn(21, 2 * n, SC.D).to(DEV), SC.randint(22, SC.NLAB, 2 * n).to(DEV).to(torch.int32)
+    rows, labels = SC.randn(21, 2 * n, width).to(DEV), SC.randint(22, SC.NLAB, 2 * n).to(DEV).to(torch.int32)
     whole = make(2 * n).add(rows, labels)
     want = H.to_host(H.clone_leaves(read(whole)))
     g = make(n).add(rows[:n], labels[:n])
@@ -132,6 +132,14 @@ def test_an_int8_gallery_grows_on_a_side_stream():
     import imageretrievalresearch_amd as M
     _grow(lambda cap: M.Int8Gallery(SC.D, DEV, capacity=cap), lambda g: (g.codes, g.scales, g.labels),
           lambda g: (g._codes, g._scales, g.labels))
+
+
+def test_a_pq_gallery_grows_on_a_side_stream():
+    import imageretrievalresearch_amd as M
+    width = 72                                                  # SC.D = 70 is no multiple of M = 4
+    codebooks = SC.randn(23, 4, 256, width // 4).to(DEV)
+    _grow(lambda cap: M.PQGallery(width, DEV, 4, codebooks=codebooks, capacity=cap), lambda g: (g.codes, g.labels),
+          lambda g: (g._codes, g.labels), width=width)
 
 
 # ---------------------------------------------------------------------------------------------- two streams at once
