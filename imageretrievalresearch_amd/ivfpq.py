@@ -15,7 +15,8 @@ The index codes nothing itself: a score is the PQ score of the gallery's own cod
 every list returns exactly what ``pq.search`` returns.  It keeps a list-ordered copy of the codes (``list_codes[p] =
 pq.codes[order[p]]``, M bytes per row): every list is one contiguous byte range, which is what the scan reads; ``pq.codes``
 stays the record.  The lists, ``probe``, ``stale`` and the rules for ``nprobe`` / ``probes`` are ``_lists._ListIndex``, shared
-with ``IVFIndex``.  Out of scope: residual codes, an OPQ rotation, an index over a sharded PQ gallery.
+with ``IVFIndex``.  Residual codes (a row's offset from its list centroid) are ``ResidualIVFPQIndex`` (ivfrpq.py).  Out of
+scope: an OPQ rotation, an index over a sharded PQ gallery.
 """
 from __future__ import annotations
 

@@ -12,8 +12,8 @@ D = 1536 and M = 96 a 64th of the fp32 row, so that a million rows are 96 MB and
 The format is approximate against the fp32 cosine, but its arithmetic is specified bit for bit in include/mi355_retrieval.h: a
 score depends on its query, its code row and the codebooks alone, and a NumPy model (tests/pq_ref.py) reproduces every bit of
 the codes, the tables, the scores, the top-k and the trained codebooks.  ``pq.ivf(rows, nlist)`` puts IVF lists over the codes
-(ivfpq.py).  Growth of the code buffer, labels and recall come from ``rank._RowStore``, as for the other galleries.  Out of scope: residual codes, an OPQ rotation, a sharded PQ gallery, range search / query expansion over
-codes, training on fp16 rows.
+(ivfpq.py).  Growth of the code buffer, labels and recall come from ``rank._RowStore``, as for the other galleries.  Codes of a row's offset from its list centroid are ``ResidualIVFPQIndex`` (ivfrpq.py).  Out of scope
+(DESIGN §7): an OPQ rotation, a sharded PQ gallery, range search / query expansion over codes, training on fp16 rows.
 """
 from __future__ import annotations
 
@@ -148,6 +148,12 @@ class PQGallery(_rank._RowStore):
             raise MI355Error(f"train: {N} rows cannot seed {CENTROIDS} centroids per sub-quantiser")
         if not isinstance(rows, _rank.Gallery):
             n = _rank.l2_normalize_rows(_rank._f32c(n, "rows"), self.eps)
+        return self._lloyd(n, iters, seed)
+
+    def _lloyd(self, n: torch.Tensor, iters: int, seed: int) -> "PQGallery":
+        """The loop of ``train`` over the (N, dim) fp32 rows ``n`` as they are (``train``: normalised rows; ivfrpq.py: residual
+        rows, which are not unit rows and must not be normalised again)."""
+        N = int(n.shape[0])
         pick = torch.from_numpy(_cl.seeded_rows(N, CENTROIDS, seed)).to(self.device)
         self._codebooks = n[pick].view(CENTROIDS, self.M, self.dsub).permute(1, 0, 2).contiguous()
         self.train_counts = None

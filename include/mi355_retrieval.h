@@ -640,6 +640,42 @@ int mi355_ivfpq_search(const float* queries, int64_t Q, int dim, float eps, cons
                        int64_t cap, int k, int64_t idx_offset, const mi355_rank_filter* filter, float* out_val, int64_t* out_idx,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ residual IVF-PQ: codes of row - centroid(list)
+ * The IVF-PQ search above over codes that describe a row's offset from the centroid of its list, so that the lists pay for
+ * accuracy as well as for time.  Bit for bit, with "fp32" as in the PQ block:
+ * Normalisation: rn = the row mi355_l2_normalize_rows writes, as everywhere.
+ * List: l = the row's list - the nearest of the unit centroids [nlist][dim] (mi355_nearest_centroid), or the caller's choice.
+ * Residual: e[i] = rn[i] - centroids[l][i], one fp32 subtraction per element (mi355_ivfpq_residuals).
+ * Codes and codebooks: the PQ contract applied unchanged to the rows e - mi355_pq_encode / mi355_pq_update with
+ * rows_are_normalized = 1, so that nothing is normalised again; training is the same Lloyd loop over residual rows.
+ * Score of (q, g): coarse(q, l_g) + s(q, g), one fp32 addition.  s is the PQ score of g's code row against the table of the
+ * normalised query - (a0 + a1) + (a2 + a3), the table built from the residual codebooks: one table per query, since q . e does
+ * not depend on the list.  coarse(q, l) = the fp32 dot of the normalised query with centroids[l] with the bits
+ * mi355_rescore_candidates gives that pair over the centroids as rows (the same routine: one wave per pair, lane-strided
+ * units, fused multiply-adds, the wave reduction).  A row lies in one list, so its score depends on the query and the row
+ * alone: not on nprobe, the order of the probes, Q, cap, k, the path or the filter.
+ * Selection, filter, cap, probes, flags, limits and argument checks: those of mi355_ivfpq_search (ties to the lower GALLERY
+ * ROW, pads (-inf, -1), a bad list id counts as an empty list - its coarse term is never read - and raises the flag).
+ * mi355_ivfpq_residual_search: mi355_ivfpq_search's arguments and centroids [nlist][dim] device fp32 (unit rows, dense).  Per
+ * query block a launch of one wave per (query, probed list) writes coarse[q][j] into the workspace; the scan stages the
+ * query's nprobe terms in LDS behind base[] (4 nprobe bytes more: 143,368 bytes at M = 128, nprobe = 1024) and adds the
+ * term of the list the position lies in to the position's lookups.  Its sizer asks for those terms on top of the plain one's
+ * bytes.
+ * mi355_ivfpq_residuals: rows [R][dim] device fp32 (raw, or rn itself with rows_are_normalized != 0), assignments [R] device
+ * int64 -> residuals [R][dim] device fp32 (may be rows itself), one vectorised pass.  R <= 2^31, dim <= 8192, nlist < 2^24.
+ * An assignment outside [0, nlist) is found on the device (its row is left unwritten) and reported as an argument error from
+ * one flag word read back (one host sync).  workspace: MI355_IVFPQ_RESIDUALS_WORKSPACE bytes (the flag).  R = 0 does nothing. */
+#define MI355_IVFPQ_RESIDUALS_WORKSPACE 512
+int mi355_ivfpq_residuals(const float* rows, int64_t R, int dim, int rows_are_normalized, float eps, const int64_t* assignments,
+                          const float* centroids, int64_t nlist, float* residuals, void* workspace, size_t workspace_bytes,
+                          void* stream);
+size_t mi355_ivfpq_residual_search_workspace_bytes(int64_t Q, int nprobe, int64_t nlist, int dim, int M, int64_t cap, int k);
+int mi355_ivfpq_residual_search(const float* queries, int64_t Q, int dim, float eps, const float* codebooks, int M,
+                                const void* list_codes, int64_t G, const int64_t* offsets, const int64_t* order, int64_t nlist,
+                                const int64_t* probes, int nprobe, int64_t cap, int k, int64_t idx_offset,
+                                const mi355_rank_filter* filter, const float* centroids, float* out_val, int64_t* out_idx,
+                                void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ backbone models
  * Replaces timm.create_model(name, num_classes=N) and the methods the reference calls on it
  * (inference/inference.py:102,110,133,146,199-201 ; train/train.py:194-195,288,396 ;
