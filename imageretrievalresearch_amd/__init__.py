@@ -46,6 +46,9 @@ def __getattr__(name):  # lazy: models/sharded import torch.nn / torch.distribut
     if name == "ResidualIVFPQIndex":
         from .ivfrpq import ResidualIVFPQIndex
         return ResidualIVFPQIndex
+    if name in ("GraphIndex", "merged_graph"):
+        from . import graph
+        return getattr(graph, name)
     if name == "ShardedGallery":
         from .sharded import ShardedGallery
         return ShardedGallery

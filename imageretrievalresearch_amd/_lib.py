@@ -186,6 +186,10 @@ PROTOTYPES = {
     "mi355_ivfpq_residual_search": (C.c_int, [vp, C.c_int64, C.c_int, C.c_float, vp, C.c_int, vp, C.c_int64, vp, vp, C.c_int64, vp,
                                               C.c_int, C.c_int64, C.c_int, C.c_int64, C.POINTER(RankFilter), vp, vp, vp, vp,
                                               C.c_size_t, vp]),
+    "mi355_graph_search_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mi355_graph_search": (C.c_int, [vp, C.c_int64, C.c_int, C.c_float, vp, C.c_int, C.c_int64, C.c_int64, vp, C.c_int, vp, C.c_int,
+                                     C.c_int, C.c_int, C.c_int, C.c_int64, C.POINTER(RankFilter), vp, vp, vp, vp, vp, C.c_size_t,
+                                     vp]),
     "mi355_roc_pairs_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int]),
     "mi355_roc_pairs_hist": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_float, vp, vp, vp, C.c_int64,
                                        C.POINTER(C.c_double), vp, C.c_int, vp, vp, C.c_size_t, vp]),

@@ -698,7 +698,25 @@ class _RowStore:
         return _recall(got, exact.search(queries, k)[1], k)
 
 
-class Gallery(_RowStore):
+class _GraphIndexed:
+    """``Gallery.graph``: the cached ``GraphIndex`` (graph.py) of a gallery's rows.  It lives in a base of ``Gallery`` because
+    the index, like the PQ classes, is exported lazily and carries its own side-stream cases (tests/test_graph_gpu.py covers
+    ``Gallery.graph``) instead of a row in the stream table, which lists what ``Gallery`` itself defines."""
+
+    def graph(self, nentry: int, degree: int = 32, **kw):
+        """The ``GraphIndex`` of the resident rows with ``nentry`` entry points: ``GraphIndex.build(self, nentry,
+        degree=degree, **kw)`` (``iters``, ``seed``, ``init``).  Cached per (nentry, degree, iters, seed) until ``add``; an index
+        built from a given ``init`` is not cached."""
+        from . import graph as _graph
+        if kw.get("init") is not None:
+            return _graph.GraphIndex.build(self, nentry, degree=degree, **kw)
+        key = (nentry, degree, kw.get("iters", 10), kw.get("seed", 0))
+        if key not in self._graph:
+            self._graph[key] = _graph.GraphIndex.build(self, nentry, degree=degree, **kw)
+        return self._graph[key]
+
+
+class Gallery(_RowStore, _GraphIndexed):
     """Resident gallery: rows are L2-normalised once when added and stay in HBM (the gallery is *born* on the
     GPU that embedded it).  ``search`` is then one fused call per query batch instead of the reference's per-query cosine +
     topk pair.
@@ -721,6 +739,7 @@ class Gallery(_RowStore):
         self._prepared, self._prepared_rows = None, 0
         self._knn, self._rerank = {}, {}                         # per k1 / (k1, k2); dropped by add
         self._ivf = {}                                           # per (nlist, iters, seed); dropped by add
+        self._graph = {}                                         # per (nentry, degree, iters, seed); dropped by add
 
     _BUFFERS = ("_buf",)
 
@@ -738,6 +757,7 @@ class Gallery(_RowStore):
         self._append(self._new_rows(embeddings), labels)
         self._knn, self._rerank = {}, {}
         self._ivf = {}
+        self._graph = {}
         return self
 
     @property

@@ -676,6 +676,43 @@ int mi355_ivfpq_residual_search(const float* queries, int64_t Q, int dim, float 
                                 const mi355_rank_filter* filter, const float* centroids, float* out_val, int64_t* out_idx,
                                 void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ graph search: a beam walk over neighbour lists
+ * A best-first search over a graph on the rows of a resident gallery.  The result is approximate against the exhaustive
+ * search, but a pure function of its inputs: every index, every score bit and both counters are specified here.
+ *   queries [Q][dim] device fp32, raw: normalised by the call with the bits of mi355_l2_normalize_rows(queries, eps);
+ *   rows: as in mi355_ivf_scan (MI355_DTYPE_F32 rows ld floats apart, or MI355_DTYPE_F16 rows 16-byte aligned with ld a
+ *     multiple of 8 halves and zero padding); G rows, G < 2^31;
+ *   graph [G][degree] device int32, dense: row r lists the neighbours of r, -1 is a pad; 2 <= degree <= 64;
+ *   seeds [Q][nseed] device int64 row ids, -1 is skipped; 1 <= nseed <= 64;
+ *   1 <= k <= ef <= 512, 1 <= max_iters, nseed + max_iters * degree <= 16384, 1 <= dim <= 4096.
+ * Score s(q, r): exactly what mi355_rescore_candidates returns for the pair (the same routine: one wave per row, lane-strided
+ * units, fused multiply-adds, the wave reduction).  It depends on the query and the row only.
+ * Beam order: that of mi355_merge_topk - NaN first, then descending score, ties (-0 equal to +0) to the lower row.
+ * Per query: visited = {}, the beam empty.
+ *   1. For each seed in order: -1 and a row already visited are skipped; every other row is marked visited, scored and put
+ *      into the beam, which keeps its best ef entries.
+ *   2. For it = 0 .. max_iters - 1: p = the first beam entry in beam order that has not been expanded; none: stop.  p is marked
+ *      expanded.  For j = 0 .. degree - 1, n = graph[p][j]: -1 and a visited n (self-loops, duplicates within a list) are
+ *      skipped; every other n is marked visited and scored.  The new beam is the best ef of the old beam and the new rows.  A
+ *      row that drops out of the beam stays visited.
+ *   3. out_val / out_idx [Q][k]: the first k beam entries that the filter (NULL, or the eligibility rule of the filtered
+ *      searches) accepts, indices + idx_offset; the remaining slots hold (-inf, -1).  The filter never changes the walk.
+ *   4. out_iters / out_visited [Q] device int32 (either may be NULL): the number of expansions, and the size of the visited set.
+ * The kernel: one workgroup of 16 waves per query; the normalised query, the beam and the visited set (an open-addressing
+ * table of the power of two at or above 2 * (nseed + max_iters * degree) slots: it cannot fill, and membership does not depend
+ * on the order of insertion) live in LDS, at the limits 153 KB of the 160.  One hop is one coalesced read of p's list, the
+ * visited filter, one wave per new row, and a merge by rank into the sorted beam.  Every loop has a bound known before it
+ * starts; no workgroup waits on another; there are no global atomics.
+ * A seed or a graph entry outside [0, G) other than -1 is never dereferenced: it raises a flag word that is read back once
+ * behind the launch (one host sync at the end, as in mi355_ivf_scan) and the call fails with a message.
+ * Every argument is checked before any HIP call.  Q = 0 does nothing.  The sizer returns 0 for a shape the entry would
+ * reject, and for Q = 0. */
+size_t mi355_graph_search_workspace_bytes(int64_t Q, int dim, int nseed, int ef, int degree, int max_iters);
+int mi355_graph_search(const float* queries, int64_t Q, int dim, float eps, const void* rows, int rows_dtype, int64_t ld, int64_t G,
+                       const int32_t* graph, int degree, const int64_t* seeds, int nseed, int k, int ef, int max_iters,
+                       int64_t idx_offset, const mi355_rank_filter* filter, float* out_val, int64_t* out_idx, int32_t* out_iters,
+                       int32_t* out_visited, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ backbone models
  * Replaces timm.create_model(name, num_classes=N) and the methods the reference calls on it
  * (inference/inference.py:102,110,133,146,199-201 ; train/train.py:194-195,288,396 ;
