@@ -243,6 +243,99 @@ def test_a_query_does_not_depend_on_its_batch_and_runs_repeat(kind):
     _same(_run(ix, x[torch.from_numpy(perm).to(DEV)], seeds[perm], 8, 64), tuple(a[perm] for a in whole), "permuted")
 
 
+# ---- the limits the header declares, the visited set's wrap, and the beam's order among equal and NaN scores
+@pytest.mark.parametrize("kind", list(DTYPES))
+def test_the_largest_launch(kind):
+    """dim 4096, ef 512 and nseed + max_iters * degree = 16384 together: the dynamic LDS the launcher declares as its maximum
+    (the query, two beams, the hop's rows and a 32768-slot visited set: 156,176 bytes)."""
+    D, R, nseed, ef, max_iters, Q, k = graph.MAX_DIM, graph.MAX_DEGREE, graph.MAX_NSEED, graph.MAX_EF, 255, 3, 64
+    assert (D, R, nseed, ef) == (4096, 64, 64, 512) and nseed + max_iters * R == graph.MAX_VISITS == 16384
+    slots = 8
+    while slots < 2 * (nseed + max_iters * R):
+        slots *= 2
+    assert slots == 32768 and 4 * D + 2 * ef * 8 + 2 * 64 * 4 + 16 + 4 * slots == 156176
+    g = M.Gallery(D, DEV, dtype=DTYPES[kind]).add(torch.from_numpy(_raw(1, G, D)).to(DEV))
+    x = torch.from_numpy(_raw(2, Q, D)).to(DEV)
+    S, adj = scores_of(g, x), messy(G, R)
+    ix = _index(g, adj)
+    seeds = _seeds(Q, nseed, G)
+    got = _run(ix, x, seeds, k, ef, max_iters)
+    _same(got, ref.search(S, adj, seeds, k, ef, max_iters), f"largest launch {kind}")
+    assert (got[2] == max_iters).all() and (got[3] > ef).all()      # the walk ran to its last hop with a full beam
+
+
+def _slot_of(row, slots):
+    """Where the visited set's probe of ``row`` begins - restated from graph.hip: the top log2(slots) bits of the 32-bit
+    product row * 2654435761."""
+    return ((int(row) * 2654435761) & 0xffffffff) >> (32 - (slots.bit_length() - 1))
+
+
+@pytest.mark.parametrize("nseed,R,max_iters,slots", [(1, 2, 1, 8), (2, 2, 3, 16), (8, 8, 3, 64)])
+def test_the_visited_set_wraps_from_its_last_slot(nseed, R, max_iters, slots):
+    """Every row a walk can meet begins its probe at the last slot of the smallest tables (the power of two at or above
+    2 * (nseed + max_iters * degree)), so every row but the first goes on to slot 0, 1, ..."""
+    table = 8
+    while table < 2 * (nseed + max_iters * R):
+        table *= 2
+    assert table == slots
+    g, x, S, _, _ = _setup("f32", 7)
+    last = [r for r in range(G) if _slot_of(r, slots) == slots - 1]
+    assert len(last) >= max(4, nseed + 1), (slots, last)
+    # row r lists the next R rows of `last` (cyclically) after its own place, or after r mod len(last) for the other rows
+    place = {r: i for i, r in enumerate(last)}
+    adj = np.array([[last[(place.get(r, r) + 1 + j) % len(last)] for j in range(R)] for r in range(G)], np.int32)
+    seeds = np.array([[last[(q + j) % len(last)] for j in range(nseed)] for q in range(3)], np.int64)
+    assert all(_slot_of(r, slots) == slots - 1 for r in adj[last].reshape(-1)) and all(_slot_of(r, slots) == slots - 1 for r in seeds.reshape(-1))
+    ix = _index(g, adj)
+    got = _run(ix, x[:3], seeds, 1, min(8, nseed + R), max_iters)
+    want = ref.search(S[:3], adj, seeds, 1, min(8, nseed + R), max_iters)
+    _same(got, want, f"wrap slots={slots}")
+    # at least three distinct rows began at the last slot, so at least two went on to slot 0: none was lost or met twice
+    assert (got[3] >= 3).all() and (got[3] >= nseed).all() and (got[3] <= min(len(last), nseed + max_iters * R)).all()
+    if slots == 8:                                                   # the seed and its two neighbours, nothing else
+        assert (got[2] == 1).all() and (got[3] == 3).all()
+    if slots == 64:                                                  # eight seeds and the one row of `last` that is left
+        assert (got[3] == len(last)).all() and len(last) == nseed + 1
+
+
+@pytest.mark.parametrize("kind", list(DTYPES))
+def test_equal_zero_and_nan_scores_keep_the_beam_order(kind):
+    """Rows r and r + 300 are copies (equal score bits), four rows (and their copies) are zero and five are one-hot (exact zeros
+    against a one-hot query), one row is NaN; a query that is a gallery row, a one-hot query and a zero query (every score 0
+    or NaN).  The rank-by-count merge gives two entries the same place unless the order is strict on what it meets."""
+    D, half = 70, G // 2
+    base = _raw(31, half, D).copy()
+    base[10:14] = 0.0
+    base[30:35] = np.eye(D, dtype=np.float32)[:5]
+    rows = np.concatenate([base, base])
+    rows[20] = np.nan                                                # (row 320 stays what row 20 was)
+    g = M.Gallery(D, DEV, dtype=DTYPES[kind]).add(torch.from_numpy(rows).to(DEV))
+    xq = np.stack([rows[5], np.eye(D, dtype=np.float32)[0], np.zeros(D, np.float32), _raw(32, 1, D)[0], rows[315]])
+    x = torch.from_numpy(xq).to(DEV)
+    Q = x.shape[0]
+    S = scores_of(g, x)
+    # what the scores hold, before the walk is looked at
+    assert np.isnan(S[:, 20]).all() and not np.isnan(np.delete(S, 20, axis=1)).any()
+    keep = [r for r in range(half) if r != 20]
+    assert (_bits(S[:, keep]) == _bits(S[:, [r + half for r in keep]])).all()
+    assert (S[1, 31:35] == 0).all() and (S[1, 10:14] == 0).all() and S[1, 30] > 0.99 and (np.delete(S[2], 20) == 0).all()
+    assert S[0, 5] > 0.99 and S[0, 305] == S[0, 5]
+    for make in (ring, messy):
+        adj = make(G, 8)
+        ix = _index(g, adj)
+        seeds = _seeds(Q, 8, G)
+        seeds[:, 1] = 20                                             # the NaN row is in every beam from the start
+        for ef in (2, 63, 64, 512):
+            k = min(ef, 64)
+            mi = ix.default_max_iters(ef, 8)
+            got = _run(ix, x, seeds, k, ef)
+            _same(got, ref.search(S, adj, seeds, k, ef, mi), f"order {kind} {make.__name__} ef={ef}")
+            assert (got[1][:, 0] == 20).all()                        # NaN first
+            for q in range(Q):
+                real = got[1][q][got[1][q] >= 0]
+                assert len(set(real.tolist())) == real.size, (kind, make.__name__, ef, q)     # no row twice
+
+
 # ---- build
 @functools.lru_cache(maxsize=None)
 def _planted():

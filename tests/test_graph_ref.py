@@ -33,6 +33,47 @@ def test_complete_graph_with_a_wide_beam_is_the_exact_topk():
     assert i4.index(3) + 1 == i4.index(8)
 
 
+def test_equal_zero_and_nan_scores_in_a_narrow_beam_keep_the_beam_order():
+    """The scores of test_graph_gpu's order test - copies r and r + 30 with equal scores, a run of exact zeros of both signs,
+    NaNs - walked over a sparse ring with beams narrower than the ties: after every merge the beam is the best ef rows seen in
+    the strict order (NaN first, descending, -0 = +0, the lower row), so no two rows ever share a place."""
+    G, Q = 60, 4
+    rng = np.random.default_rng(5)
+    half = rng.standard_normal((Q, G // 2)).astype(np.float32)
+    S = np.concatenate([half, half], axis=1)                             # rows r and r + 30 tie, for every r
+    S[:, 10:14] = 0.0
+    S[:, 40:44] = -0.0                                                   # eight zeros, four of them negative
+    S[0, 7] = S[1, [7, 37, 52]] = np.nan                                 # one NaN; three NaNs, one beside its own copy
+    S[3] = 0.0                                                           # a query that ties with everything ...
+    S[3, 20] = np.nan                                                    # ... but one NaN row
+    graph = np.stack([[(r + 1) % G, (r - 1) % G, (r + 30) % G, (r + 7) % G] for r in range(G)]).astype(np.int32)
+    seeds = np.array([[0, 31], [59, 7], [12, 42], [45, 2]])
+    for ef in (2, 5, 9, G):
+        for k in (1, min(ef, 9), ef):
+            v, i, iters, visited = ref.search(S, graph, seeds, k, ef, 200)
+            for q in range(Q):
+                got = i[q].tolist()
+                assert len(set(got)) == k and min(got) >= 0, (ef, k, q)              # no row twice, no pad
+                assert got == sorted(got, key=lambda r: ref.beam_key(S[q, r], r)), (ef, k, q)
+                assert (v[q].view(np.int32) == S[q, got].view(np.int32)).all()       # each with its own bits (the sign of a zero too)
+    # the whole graph in the beam: the exhaustive order, every rule visible
+    v, i, iters, visited = ref.search(S, graph, seeds, G, G, 200)
+    assert (visited == G).all() and (iters == G).all()
+    for q in range(Q):
+        wv, wi = ref.topk_exact(S[q], G)
+        assert (i[q] == wi).all() and (v[q].view(np.int32) == wv.view(np.int32)).all()
+    assert i[0, 0] == 7 and i[1, :3].tolist() == [7, 37, 52]             # NaN first, the lower row first among them
+    order = i[2].tolist()
+    zeros = [r for r in order if S[2, r] == 0]
+    assert zeros == [10, 11, 12, 13, 40, 41, 42, 43]                     # -0 = +0: by row alone
+    assert all(order.index(r) + 1 == order.index(r + 30) for r in range(30) if r not in range(10, 14))    # a copy follows its original
+    assert i[3].tolist() == [20] + [r for r in range(G) if r != 20]
+    # a beam of two among the eight zeros of query 3: the two lowest rows seen stay, whatever comes later
+    v, i, iters, visited = ref.search(S[3:], graph, np.array([[45, 2]]), 2, 2, 200)
+    # 2 -> 3 1 32 9 (45 drops out), 1 -> 0 31 8, 0 -> 59 30 7: nothing below row 0 is left to find
+    assert i[0].tolist() == [0, 1] and iters[0] == 3 and visited[0] == 12
+
+
 def test_one_iteration_expands_one_row():
     G = 30
     graph = np.stack([[(r + 1) % G, (r + 2) % G, (r + 7) % G] for r in range(G)]).astype(np.int32)

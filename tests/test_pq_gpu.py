@@ -19,8 +19,10 @@ NQ = 200                                                            # queries of
 CHUNK = pq.SCAN_CHUNK
 GMAX = CHUNK + 1                                                    # rows of every model; each G of a test is a prefix
 # (D, M): dsub 1, 8, 64, 1, 16, then 4 and 4; code loads of 4 bytes (M % 16 != 0) and 16; scan workgroups of 256 threads (M <= 40),
-# 512 (M <= 80) and 1024
-SHAPES = [(4, 4), (64, 8), (256, 4), (128, 128), (1536, 96), (192, 48), (176, 44)]
+# 512 (M <= 80) and 1024.  The last four: dsub 3, 24, 32 and 33 - no power of two but 32, and k_pq_encode<8>, <32>, <32> (its
+# last dsub) and <64> (its first)
+SHAPES = [(4, 4), (64, 8), (256, 4), (128, 128), (1536, 96), (192, 48), (176, 44), (12, 4), (96, 4), (128, 4), (132, 4)]
+ENCODE_REGS = {3: 8, 24: 32, 32: 32, 33: 64}                        # dsub -> DMAX of the k_pq_encode instance (pq.hip's dispatch)
 SIZES = [1, 63, 65, 1000, 2000, CHUNK - 1, CHUNK, CHUNK + 1]
 
 
@@ -78,6 +80,8 @@ def _top(m, G):
 @pytest.mark.parametrize("D,Mq", SHAPES)
 def test_encode_bit_for_bit(D, Mq):
     dsub = D // Mq
+    if dsub in ENCODE_REGS:                                          # the instance this shape is here for
+        assert min(r for r in (8, 16, 32, 64) if dsub <= r) == ENCODE_REGS[dsub]
     cb = _codebooks(D, Mq, 7 + D)
     x = _randn((1000, D), D + Mq)
     x[3] = 0.0
@@ -205,7 +209,7 @@ def _ulps(a, b):
     return np.abs(a - b).max()
 
 
-@pytest.mark.parametrize("D,Mq", [(64, 8), (256, 4), (128, 128), (1536, 96)])
+@pytest.mark.parametrize("D,Mq", [(64, 8), (256, 4), (128, 128), (1536, 96), (96, 4)])
 def test_update_against_the_float64_mean(D, Mq):
     m = _model(D, Mq)
     n = M.l2_normalize_rows(m["x"])
