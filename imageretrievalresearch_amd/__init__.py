@@ -43,6 +43,9 @@ def __getattr__(name):  # lazy: models/sharded import torch.nn / torch.distribut
     if name == "IVFPQIndex":
         from .ivfpq import IVFPQIndex
         return IVFPQIndex
+    if name == "Int8IVFIndex":
+        from .ivf_i8 import Int8IVFIndex
+        return Int8IVFIndex
     if name == "ResidualIVFPQIndex":
         from .ivfrpq import ResidualIVFPQIndex
         return ResidualIVFPQIndex

@@ -166,6 +166,9 @@ PROTOTYPES = {
     "mi355_ivf_scan_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int64]),
     "mi355_ivf_scan": (C.c_int, [vp, C.c_int64, C.c_int, C.c_float, vp, C.c_int, C.c_int64, C.c_int64, vp, vp, C.c_int64, vp,
                                  C.c_int, C.c_int64, C.c_int64, C.POINTER(RankFilter), vp, vp, vp, C.c_size_t, vp]),
+    "mi355_ivf_scan_i8_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int64]),
+    "mi355_ivf_scan_i8": (C.c_int, [vp, C.c_int64, C.c_int, C.c_float, vp, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64, vp,
+                                    C.c_int, C.c_int64, C.c_int64, C.POINTER(RankFilter), vp, vp, vp, C.c_size_t, vp]),
     "mi355_pq_encode_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
     "mi355_pq_encode": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, C.c_size_t, vp, C.c_size_t, vp]),
     "mi355_pq_update_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),

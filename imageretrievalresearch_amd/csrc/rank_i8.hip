@@ -14,45 +14,12 @@
 //   * the integer sums do not depend on any summation order, so the GEMV (Q <= 4), both tile sizes of the GEMM, its two
 //     launches and every epilogue return the SAME bits for a (query, row) pair.
 //   * order, ties, NaN, pads: the selection of mi355_rank_topk (rank_common.h).
-#include "rank_common.h"
+#include "i8_quant.h"
 #include "../../include/mi355_retrieval.h"
-
-#include <float.h>
 
 namespace mi355 {
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int I8_KSTEP = 128;                 // k-step of the GEMM: one 128-byte segment of a stored row
-constexpr int I8_MAX_DIM = 65536;             // 65536 * 127 * 127 < 2^31: the int32 sums are exact
-static inline int i8_ld(int dim) { return (dim + I8_KSTEP - 1) / I8_KSTEP * I8_KSTEP; }
-
-// ---- the row quantiser: scale and inverse scale of a row from its amax, then the code of one element
-struct I8Quant {
-    float scale, inv;
-    bool zero;                                // every code is 0 (NaN row, zero row)
-};
-__device__ __forceinline__ I8Quant i8_quant(float amax, bool has_nan) {
-    if (has_nan || !(amax <= FLT_MAX)) return {__uint_as_float(0x7fc00000u), 0.f, true};
-    if (amax < 1e-30f) return {0.f, 0.f, true};
-    return {amax / 127.0f, 127.0f / amax, false};
-}
-// clamp(rintf(x * m), -127, 127); the empty asm pins the fp32 product in a register, as scaled_f16 does
-__device__ __forceinline__ int i8_code(float x, float m) {
-    float p = x * m;
-    asm volatile("" : "+v"(p));
-    return (int)fminf(fmaxf(rintf(p), -127.0f), 127.0f);
-}
-// the fp32 row value x * r (the bits of l2_normalize_rows), pinned so that no later product is folded into it
-__device__ __forceinline__ float i8_norm_elem(float x, float r) {
-    float p = x * r;
-    asm volatile("" : "+v"(p));
-    return p;
-}
-__device__ __forceinline__ unsigned pack4_i8(int a, int b, int c, int d) {
-    return (unsigned)(a & 0xff) | ((unsigned)(b & 0xff) << 8) | ((unsigned)(c & 0xff) << 16) | ((unsigned)(d & 0xff) << 24);
-}
 
 // =====================================================================================
 // fp32 rows -> int8 codes, padded to ld bytes with zeros, and one scale per row.  One wave per row: the norm with
@@ -143,7 +110,7 @@ __global__ __launch_bounds__(256) void k_split_queries_i8(const float* __restric
         q = i8_quant(wave_max(amax), __ballot(nan) != 0ull);
     }
     if (lane == 0) sq[row] = q.scale;
-    const float lo_mul = q.zero ? 0.f : 128.0f / q.scale;
+    const float lo_mul = i8_lo_mul(q);
     signed char* base = Qs + (size_t)(row >> 5) * n_sub * 2048 + (row & 31) * 16;
     for (int c = lane; c < 2 * n_sub; c += 64) {           // 16-byte chunk c: sub-step c / 2, k half c % 2
         unsigned hi[4] = {0u, 0u, 0u, 0u}, lo[4] = {0u, 0u, 0u, 0u};
@@ -160,11 +127,7 @@ __global__ __launch_bounds__(256) void k_split_queries_i8(const float* __restric
                 }
                 int h[4], l[4];
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float n = v[e];
-                    h[e] = i8_code(n, q.inv);
-                    l[e] = i8_code(__builtin_fmaf(-(float)h[e], q.scale, n), lo_mul);
-                }
+                for (int e = 0; e < 4; ++e) i8_split_elem(v[e], q, lo_mul, h[e], l[e]);
                 hi[w] = pack4_i8(h[0], h[1], h[2], h[3]);
                 lo[w] = pack4_i8(l[0], l[1], l[2], l[3]);
             }

@@ -70,7 +70,7 @@ class IVFPQIndex(_ListIndex):
     @staticmethod
     def _check_rows(pq, rows) -> None:
         """``rows``: what ``pq``'s codes were made from - a Gallery (fp32 or fp16) or a (N, D) fp32 tensor, same device and dim,
-        N == len(pq)."""
+        N == len(pq).  ``pq``: a ``PQGallery``, or any row store with a ``_NOUN`` (``Int8IVFIndex`` checks its rows here)."""
         if isinstance(rows, _rank.Gallery):
             n, dim, dev = len(rows), rows.dim, rows.device
         elif torch.is_tensor(rows):
@@ -82,11 +82,11 @@ class IVFPQIndex(_ListIndex):
         else:
             raise MI355Error(f"rows must be a Gallery or a tensor, got {type(rows).__name__}")
         if dev != pq.device:
-            raise MI355Error(f"rows are on {dev} but the PQGallery lives on {pq.device}")
+            raise MI355Error(f"rows are on {dev} but the {pq._NOUN} lives on {pq.device}")
         if dim != pq.dim:
-            raise MI355Error(f"rows have dim {dim}, the PQGallery {pq.dim}")
+            raise MI355Error(f"rows have dim {dim}, the {pq._NOUN} {pq.dim}")
         if n != pq.rows:
-            raise MI355Error(f"rows holds {n} rows, the PQGallery {pq.rows}: the lists are made of the rows the codes were made from")
+            raise MI355Error(f"rows holds {n} rows, the {pq._NOUN} {pq.rows}: the lists are made of the rows the codes were made from")
 
     @classmethod
     def build(cls, pq, rows, nlist: int, *, iters: int = 10, seed: int = 0, init: torch.Tensor | None = None) -> "IVFPQIndex":

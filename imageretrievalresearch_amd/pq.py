@@ -30,11 +30,11 @@ _MAX_K = 1024                       # largest k of any search, and the longest s
 _is_int = _rank._is_int
 
 
-def _shortlist_length(pq: "PQGallery", k, refine, shortlist):
-    """(k, R) of a search over ``pq``'s rows: the checked k, and the rows the code scan returns per query - k itself, or with
-    ``refine`` the length of the shortlist it rescores.  The one set of rules behind ``PQGallery.search`` and
-    ``IVFPQIndex.search``."""
-    top = min(_MAX_K, pq.rows)
+def _shortlist_length(store, k, refine, shortlist):
+    """(k, R) of a search over ``store``'s rows: the checked k, and the rows the approximate scan returns per query - k itself,
+    or with ``refine`` the length of the shortlist it rescores.  ``store`` is any row store with ``rows``, ``dim``, ``device``
+    and ``_NOUN``: the one set of rules behind ``PQGallery.search``, ``Int8Gallery.search`` and the indexes over them."""
+    top = min(_MAX_K, store.rows)
     if not _is_int(k) or not 1 <= k <= top:
         raise MI355Error(f"selected index k out of range: k={k!r} outside [1, {top}] (min({_MAX_K}, rows))")
     k = int(k)
@@ -44,27 +44,28 @@ def _shortlist_length(pq: "PQGallery", k, refine, shortlist):
         return k, k
     if not isinstance(refine, _rank.Gallery):
         raise MI355Error(f"refine must be a Gallery of the same rows, got {type(refine).__name__}")
-    if refine.device != pq.device:
-        raise MI355Error(f"refine is on {refine.device} but the PQGallery lives on {pq.device}")
-    if len(refine) != pq.rows or refine.dim != pq.dim:
-        raise MI355Error(f"refine holds {len(refine)} rows of dim {refine.dim}, the PQGallery {pq.rows} of dim {pq.dim}")
+    if refine.device != store.device:
+        raise MI355Error(f"refine is on {refine.device} but the {store._NOUN} lives on {store.device}")
+    if len(refine) != store.rows or refine.dim != store.dim:
+        raise MI355Error(f"refine holds {len(refine)} rows of dim {refine.dim}, the {store._NOUN} {store.rows} of dim {store.dim}")
     R = min(max(10 * k, 100), top) if shortlist is None else shortlist
     if not _is_int(R) or not k <= R <= top:
         raise MI355Error(f"shortlist={R!r} outside [k={k}, {top}] (min({_MAX_K}, rows))")
     return k, int(R)
 
 
-def _refined_topk(pq: "PQGallery", q: torch.Tensor, vals: torch.Tensor, idx: torch.Tensor, k: int, refine, idx_offset):
-    """The tail of a refined search: the shortlist ``idx`` (Q, R) of the queries ``q`` is scored again against ``refine``'s
-    rows (``mi355_rescore_candidates``, into ``vals``), then ``merge_topk`` and ``clear_pads``."""
-    Q, R, L, dev = idx.shape[0], idx.shape[1], lib(), pq.device
-    ws = _rank._ws.get(dev, L.mi355_rescore_candidates_workspace_bytes(Q, pq.dim))
+def _refined_topk(store, q: torch.Tensor, vals: torch.Tensor, idx: torch.Tensor, k: int, refine, idx_offset):
+    """The tail of a refined search over ``store`` (``rows``, ``dim``, ``device``, ``eps``): the shortlist ``idx`` (Q, R) of the
+    queries ``q`` is scored again against ``refine``'s rows (``mi355_rescore_candidates``, into ``vals``), then ``merge_topk``
+    and ``clear_pads``."""
+    Q, R, L, dev = idx.shape[0], idx.shape[1], lib(), store.device
+    ws = _rank._ws.get(dev, L.mi355_rescore_candidates_workspace_bytes(Q, store.dim))
     with torch.cuda.device(dev):
-        check(L.mi355_rescore_candidates(q.data_ptr(), Q, pq.dim, pq.eps, refine._buf.data_ptr(), _rank._DTYPES[refine.dtype],
-                                         refine._ld, pq.rows, idx.data_ptr(), R, int(idx_offset), vals.data_ptr(),
-                                         ws.data_ptr(), ws.numel(), stream_ptr(dev)))
+        check(L.mi355_rescore_candidates(q.data_ptr(), Q, store.dim, store.eps, refine._buf.data_ptr(),
+                                         _rank._DTYPES[refine.dtype], refine._ld, store.rows, idx.data_ptr(), R, int(idx_offset),
+                                         vals.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr(dev)))
     v, i = _rank.merge_topk(vals, idx, k)
-    _rank.clear_pads(v, i, int(idx_offset), int(idx_offset) + pq.rows)
+    _rank.clear_pads(v, i, int(idx_offset), int(idx_offset) + store.rows)
     return v, i
 
 
@@ -74,6 +75,8 @@ class PQGallery(_rank._RowStore):
     accumulators, a fixed order); order, ties, NaN queries and pads as ``cosine_topk``.  Equal code rows score equal bits, so
     ties (resolved to the lower row) are common.  A row with a NaN element is encoded like any other (code 0 where the NaN
     reaches): unlike the other galleries it does not rank first."""
+
+    _NOUN = "PQGallery"
 
     def __init__(self, dim: int, device, M: int, codebooks: torch.Tensor | None = None, capacity: int = 0,
                  eps: float = _rank._EPS):

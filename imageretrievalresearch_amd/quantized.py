@@ -24,13 +24,33 @@ def _stride(dim: int) -> int:
     return (dim + _SEGMENT - 1) // _SEGMENT * _SEGMENT
 
 
-class Int8Gallery(_rank._RowStore):
+class _ListIndexed:
+    """``Int8Gallery.ivf``: the cached ``Int8IVFIndex`` (ivf_i8.py) over a gallery's codes.  It lives in a base of
+    ``Int8Gallery`` as ``rank._GraphIndexed`` does for ``Gallery.graph``: the index is exported lazily and carries its own
+    side-stream cases (tests/test_ivf_i8_gpu.py)."""
+
+    def ivf(self, rows, nlist: int, **kw):
+        """The ``Int8IVFIndex`` over these codes with ``nlist`` lists: ``Int8IVFIndex.build(self, rows, nlist, **kw)``
+        (``iters``, ``seed``, ``init``); ``rows`` is the ``Gallery`` or the fp32 tensor the codes were made from.  Cached per
+        (nlist, iters, seed) until ``add``; an index built from a given ``init`` is not cached."""
+        from .ivf_i8 import Int8IVFIndex
+        if kw.get("init") is not None:
+            return Int8IVFIndex.build(self, rows, nlist, **kw)
+        key = (nlist, kw.get("iters", 10), kw.get("seed", 0))
+        if key not in self._ivf:
+            self._ivf[key] = Int8IVFIndex.build(self, rows, nlist, **kw)
+        return self._ivf[key]
+
+
+class Int8Gallery(_rank._RowStore, _ListIndexed):
     """Resident int8 gallery.  A row is stored as ``codes = clamp(rint(n * 127 / amax), -127, 127)`` of its L2-normalised fp32
     row ``n`` (``amax = max |n_i|``) beside ``scale = amax / 127``: ``ld + 4`` bytes per row, ``ld`` = ``dim`` rounded up to a
     multiple of 128.  A search keeps about 15 bits of each query (two int8 planes), multiplies on the int8 matrix pipe and
     returns ``(acc_hi + acc_lo / 128) * s_q * s_g``; order, ties, NaN and pads as ``cosine_topk``.  The error against the
     fp32 cosine is that of the row quantisation, about 1e-3 at most and a few 1e-4 rms at the reference's widths: the
     top-k is approximate (``recall``)."""
+
+    _NOUN = "Int8Gallery"
 
     def __init__(self, dim: int, device, capacity: int = 0, eps: float = _rank._EPS):
         super().__init__(dim, device, eps)
@@ -40,6 +60,7 @@ class Int8Gallery(_rank._RowStore):
         cap = max(int(capacity), 0)
         self._codes = torch.empty((cap, self._ld), dtype=torch.int8, device=self.device)
         self._scales = torch.empty((cap,), dtype=torch.float32, device=self.device)
+        self._ivf = {}                                           # per (nlist, iters, seed); dropped by add
 
     _BUFFERS = ("_codes", "_scales")
 
@@ -51,6 +72,7 @@ class Int8Gallery(_rank._RowStore):
                                             n * self._ld, scales.data_ptr(), stream_ptr(e.device)))
 
     def add(self, embeddings: torch.Tensor, labels: torch.Tensor | None = None):
+        self._ivf = {}
         return self._append(self._new_rows(embeddings), labels, normalized=False)
 
     @property
@@ -76,10 +98,22 @@ class Int8Gallery(_rank._RowStore):
         return _rank._Rows(self._codes, self.rows, self.dim, True, None, self._scales)
 
     def search(self, queries: torch.Tensor, k: int, idx_offset: int = 0, *, query_labels: torch.Tensor | None = None,
-               label_filter: str | None = None, exclude: torch.Tensor | None = None):
-        """Top-k of ``queries`` against the resident rows, arguments and result as ``Gallery.search`` (without ``qe``)."""
+               label_filter: str | None = None, exclude: torch.Tensor | None = None, refine=None, shortlist: int | None = None):
+        """Top-k of ``queries`` against the resident rows, arguments and result as ``Gallery.search`` (without ``qe``).
+        ``refine`` / ``shortlist`` as in ``PQGallery.search``: with ``refine``, a ``Gallery`` (fp32 or fp16) of the same rows on
+        the same device, the int8 search returns ``shortlist`` rows per query (``k <= shortlist <= min(1024, rows)``, default
+        ``min(max(10 * k, 100), 1024, rows)``), each is scored again as ``qn . row`` against the gallery's row (the bits an
+        ``IVFIndex`` scan gives the pair) and the top-k of those values is returned."""
         gl = None if label_filter is None else self._labels_for(f'label_filter="{label_filter}"')
-        return _rank._topk(queries, self._resident(), k, self.eps, idx_offset, query_labels, gl, label_filter, exclude)
+        if refine is None and shortlist is None:
+            return _rank._topk(queries, self._resident(), k, self.eps, idx_offset, query_labels, gl, label_filter, exclude)
+        from . import pq as _pq
+        k, R = _pq._shortlist_length(self, k, refine, shortlist)
+        q = _rank._f32c(queries, "queries")
+        vals, idx = _rank._topk(q, self._resident(), R, self.eps, idx_offset, query_labels, gl, label_filter, exclude)
+        if q.shape[0] == 0:
+            return vals[:, :k], idx[:, :k]
+        return _pq._refined_topk(self, q, vals.contiguous(), idx.contiguous(), k, refine, idx_offset)
 
     def range_search(self, queries: torch.Tensor, threshold: float, *, query_labels: torch.Tensor | None = None,
                      label_filter: str | None = None, exclude: torch.Tensor | None = None, max_results: int | None = None,

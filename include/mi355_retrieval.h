@@ -239,7 +239,8 @@ int mi355_range_compact(const void* candidates, int64_t capacity, int64_t Q, int
  * multiplies in that order.  A NaN row scores NaN (it ranks first, as in mi355_rank_topk), a zero row 0, a NaN query NaN
  * everywhere.  The sums are integers, so EVERY path returns these bits for a (query, row) pair: the GEMV (Q <= 4), the tiled
  * GEMM with 64- and 128-query tiles in its main and its tail launch, the fused selection and the score slab, the filtered and the
- * unfiltered search, and the range search.  Order, ties, NaN and pads: the selection of mi355_rank_topk.
+ * unfiltered search, the range search, and the scan of probed lists (mi355_ivf_scan_i8, in the IVF block).  Order, ties, NaN and
+ * pads: the selection of mi355_rank_topk.
  * The gallery argument of every entry is the pair (codes, scales).  Arguments are checked as for the _f16 entries (null, shape, k,
  * alignment, workspace), and dim <= 65536.  workspace: mi355_rank_i8_workspace_bytes(Q, G, dim, k) (both top-k entries),
  * mi355_range_i8_workspace_bytes(Q, G, dim); mi355_cosine_range_i8 is mi355_cosine_range_f16 over int8 rows (results read with
@@ -548,6 +549,32 @@ int mi355_ivf_scan(const float* queries, int64_t Q, int dim, float eps, const vo
                    const int64_t* offsets, const int64_t* order, int64_t nlist, const int64_t* probes, int nprobe, int64_t cap,
                    int64_t idx_offset, const mi355_rank_filter* filter, float* cand_val, int64_t* cand_idx, void* workspace,
                    size_t workspace_bytes, void* stream);
+
+/* The same scan over the rows of an int8 gallery (mi355_ivf_scan_i8): a quarter of the bytes of fp32 rows per probed row.
+ *   codes / scales: the pair mi355_gallery_to_i8 writes - codes 16-byte aligned, rows ld bytes apart, ld a multiple of 128 and
+ *     >= dim, the bytes dim .. (dim rounded up to 128) - 1 of a row zero; scales fp32 [G]; G rows; 1 <= dim <= 65536;
+ *   queries, offsets, order, probes, cand_val, cand_idx, filter, idx_offset, cap: exactly as in mi355_ivf_scan, and so is the
+ *     slot layout: the lists fill slots 0 .. n_q - 1 in probe order, then list order; an ineligible row and every slot
+ *     n_q .. cap - 1 hold (-inf, 2^62); every slot is written once, by one wave, with no atomics.
+ * Query planes: (hi, lo, s_q) of the int8 block above, made by the call from qn = the bits of mi355_l2_normalize_rows(queries,
+ * eps) (one kernel takes the norm and splits: no normalised copy is written), kept as [Q][hi, lo][dim rounded up to 128] bytes
+ * and s_q [Q] in the workspace.
+ * Score: acc_hi, acc_lo exact in int32; t = fmaf((float)acc_lo, 0x1p-7f, (float)acc_hi); score = (t * s_q) * s_g - the bits
+ * mi355_rank_topk_i8 returns for the pair.  A NaN-scale row scores NaN, a zero row 0, a NaN query NaN everywhere.  A score
+ * depends on its query and its row only - not on Q, nprobe, the list, the group or the query block of the caller - so a scan
+ * that probes every list, merged by mi355_merge_topk, is mi355_rank_topk_i8 bit for bit.
+ * Work: the planning kernels and the loop over the (list, group, chunk) items are mi355_ivf_scan's.  One wave per row, 16 bytes
+ * of the row per lane and load, up to four loads in flight; the group's planes in LDS (2 bytes per element and query), so a
+ * group is up to 8 queries, fewer when 8 * 2 * ld' bytes pass 64 KB (ld' = dim rounded up to 128); one must fit: dim <= 32768.
+ * v_dot4_i32_i8 into int32, an integer wave reduction, lanes < n write the slots.
+ * Errors: as in mi355_ivf_scan - every argument is checked before any HIP call (Q = 0 does nothing), what is found on the
+ * device is reported after the call from the same two flag words behind one host sync, with the same messages.
+ * workspace: mi355_ivf_scan_i8_workspace_bytes(Q, nprobe, nlist, dim, cap), 0 for a shape the scan refuses. */
+size_t mi355_ivf_scan_i8_workspace_bytes(int64_t Q, int nprobe, int64_t nlist, int dim, int64_t cap);
+int mi355_ivf_scan_i8(const float* queries, int64_t Q, int dim, float eps, const void* codes, const float* scales, int64_t ld,
+                      int64_t G, const int64_t* offsets, const int64_t* order, int64_t nlist, const int64_t* probes, int nprobe,
+                      int64_t cap, int64_t idx_offset, const mi355_rank_filter* filter, float* cand_val, int64_t* cand_idx,
+                      void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ product-quantised (PQ) resident gallery
  * A row is M bytes: its normalised fp32 row is cut into M sub-vectors of dsub = dim / M elements, and byte m names the nearest
