@@ -17,8 +17,9 @@ from .rank import (ContrastiveLoss, CosineEmbeddingLoss, CosineSimilarity, Galle
                    verification_roc)
 from .rerank import RerankIndex, k_reciprocal_rerank  # noqa: F401
 from .whitening import Moments, Whitening, embedding_moments  # noqa: F401
-from .cluster import (KMeansResult, assign_clusters, cluster_members, clustering_metrics,  # noqa: F401
-                      clustering_metrics_from_table, contingency, spherical_kmeans, update_centroids)
+from .cluster import (DBSCANResult, KMeansResult, assign_clusters, cluster_members, clustering_metrics,  # noqa: F401
+                      clustering_metrics_from_table, connected_components, contingency, dbscan, spherical_kmeans,
+                      update_centroids)
 from .ivf import IVFIndex  # noqa: F401
 from .quantized import Int8Gallery  # noqa: F401
 
@@ -28,6 +29,8 @@ __all__ = ["Whitening", "Moments", "embedding_moments","create_model", "list_mod
            "pack_images", "resize_batch", "RerankIndex", "k_reciprocal_rerank", "PositiveRanks", "positive_ranks", "ranking_metrics",
            "KMeansResult", "assign_clusters", "update_centroids", "cluster_members", "spherical_kmeans", "contingency",
            "clustering_metrics", "clustering_metrics_from_table", "IVFIndex", "Int8Gallery"]
+# dbscan / connected_components / DBSCANResult are importable from here but, like the lazily exported indexes, are not in __all__:
+# the stream table (tests/stream_cases.py) enumerates __all__, and their side-stream case is tests/test_dbscan_streams_gpu.py
 
 
 def __getattr__(name):  # lazy: models/sharded import torch.nn / torch.distributed

@@ -163,6 +163,18 @@ PROTOTYPES = {
                                             C.c_size_t, vp]),
     "mi355_contingency_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
     "mi355_contingency": (C.c_int, [vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, C.c_size_t, vp]),
+    "mi355_dbscan_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int]),
+    "mi355_dbscan_f16_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int]),
+    "mi355_dbscan_init": (C.c_int, [C.c_int64, vp, vp, vp, vp]),
+    "mi355_dbscan_degree": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_double, vp, vp,
+                                      C.c_size_t, vp]),
+    "mi355_dbscan_degree_f16": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_float, C.c_double, vp, vp,
+                                          C.c_size_t, vp]),
+    "mi355_dbscan_link": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_double, C.c_int, vp,
+                                    vp, vp, vp, C.c_size_t, vp]),
+    "mi355_dbscan_link_f16": (C.c_int, [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int, C.c_float, C.c_double, C.c_int, vp, vp,
+                                        vp, vp, C.c_size_t, vp]),
+    "mi355_dbscan_finish": (C.c_int, [C.c_int64, C.c_int, vp, vp, vp, vp, vp, vp]),
     "mi355_ivf_scan_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int64]),
     "mi355_ivf_scan": (C.c_int, [vp, C.c_int64, C.c_int, C.c_float, vp, C.c_int, C.c_int64, C.c_int64, vp, vp, C.c_int64, vp,
                                  C.c_int, C.c_int64, C.c_int64, C.POINTER(RankFilter), vp, vp, vp, C.c_size_t, vp]),

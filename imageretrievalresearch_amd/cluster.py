@@ -7,6 +7,9 @@
 * ``spherical_kmeans`` .... the loop of the two, from seeded distinct rows or a given start
 * ``contingency`` ......... the table of two labelings (``mi355_contingency``)
 * ``clustering_metrics`` .. NMI, purity, pairwise precision / recall / F1 of that table (host float64)
+* ``dbscan`` .............. DBSCAN on cosine similarity without a pair list: two sweeps of the cosine GEMM (a degree epilogue, a
+                            link epilogue over a lock-free union-find: ``mi355_dbscan_*``), the same bits on every run
+* ``connected_components``  ``dbscan`` with ``min_samples=1``: the components of the threshold graph
 
 The rows are a (N, D) device tensor or a ``Gallery`` (fp32 or fp16), whose resident rows are read where they lie.  Out of
 scope here: k-means++ seeding, mini-batches, ``ShardedGallery``.
@@ -220,6 +223,111 @@ def spherical_kmeans(rows, n_clusters: int, *, iters: int = 20, seed: int = 0, i
     if not np.isfinite(objective):
         raise MI355Error(f"spherical_kmeans: the objective is not finite ({objective}); the rows or the start hold NaN / inf")
     return KMeansResult(c, assign, score, counts, members, objective, passes, converged)
+
+
+# ---- DBSCAN and threshold components: clustering without a number of clusters
+class DBSCANResult(NamedTuple):
+    labels: torch.Tensor          # (N,) int64: the cluster of every row, 0 .. n_clusters - 1 by ascending root; -1 = noise
+    core: torch.Tensor            # (N,) bool: degree >= min_samples
+    degree: torch.Tensor          # (N,) int64: rows at or above the threshold, the row itself included
+    roots: torch.Tensor           # (C,) int64: each cluster's smallest core row, ascending
+    counts: torch.Tensor          # (C,) int64: rows per cluster, border rows included
+    n_clusters: int
+    n_noise: int
+
+
+_DBSCAN = {torch.float32: ("mi355_dbscan_degree", "mi355_dbscan_link", "mi355_dbscan_workspace_bytes"),
+           torch.float16: ("mi355_dbscan_degree_f16", "mi355_dbscan_link_f16", "mi355_dbscan_f16_workspace_bytes")}
+_DBSCAN_BLOCK = 4096              # rows per GEMM call: the fp32 copy of one block of fp16 rows stays at 4096 x D
+_MAX_N_DBSCAN = (1 << 31) - 128
+
+
+def dbscan(rows, threshold: float, min_samples: int = 5, *, block: int | None = None, eps: float = _EPS) -> DBSCANResult:
+    """DBSCAN (Ester et al., KDD 1996) on cosine similarity, inside the tiled cosine GEMM: no number of clusters, and no
+    pair list - the self-join is swept twice, ``block`` rows at a time as the queries, first counting every row's hits, then
+    joining core rows in a lock-free union-find on the GPU (the hooking rule of Jaiganesh & Burtscher, HPDC 2018).
+
+    ``hit(i, j)``: the score of row i as a query against row j is ``>= threshold`` - the score bits and the comparison of
+    this gallery's own ``range_search`` of its rows (NaN never hits), row i itself included.  ``degree[i]`` counts the hits of
+    row i (itself too, as sklearn counts); row i is a core row when ``degree[i] >= min_samples``.  Core rows i, j are linked
+    when ``hit(i, j)`` or ``hit(j, i)``; the clusters are the connected components of the core rows, each named by its root,
+    its smallest core row, and numbered 0 .. C-1 by ascending root.  A non-core row joins the cluster of the core row that
+    hits it (or that it hits) with the highest score, equal scores going to the lower core row - sklearn gives such a border
+    row to whichever cluster reaches it first; here the choice depends on the rows alone.  A non-core row without such a core
+    row is noise, label -1.  With ``min_samples=1`` this is exactly ``connected_components``.
+
+    ``rows``: a ``Gallery`` (fp32 or fp16, read where it lies; a prepared one on its fp32 rows) or a (N, D) fp32 device
+    tensor, which is normalised once into a temporary (N x D fp32) and clustered as an fp32 ``Gallery`` of it would be.
+    ``block`` (default 4096) never changes the result, nor does anything else but the rows: the same bits on every run.
+    One host sync (the dense numbering).  ``clustering_metrics(result.labels, labels)`` counts the noise rows, label -1, as
+    one more cluster."""
+    src = _rows_of(rows)
+    require_cuda(src.buf, "rows")
+    t = _rank._range_threshold(threshold)
+    if not _rank._is_int(min_samples) or min_samples < 1:
+        raise MI355Error(f"min_samples must be an integer >= 1, got {min_samples!r}")
+    if block is not None and (not _rank._is_int(block) or block < 1):
+        raise MI355Error(f"block must be a positive integer, got {block!r}")
+    if src.dim < 1:
+        raise MI355Error(f"clustering needs at least one column, got {src.shape}")
+    N, D, dev = src.rows, src.dim, src.device
+    if N >= _MAX_N_DBSCAN:
+        raise MI355Error(f"dbscan: {N} rows, the limit is {_MAX_N_DBSCAN - 1}")
+    if N == 0:
+        e = torch.empty(0, dtype=torch.int64, device=dev)
+        return DBSCANResult(e, torch.empty(0, dtype=torch.bool, device=dev), e.clone(), e.clone(), e.clone(), 0, 0)
+    run = _DBSCANRun(_unit_rows(src, eps), t, int(min(min_samples, 2**31 - 1)), block, eps)
+    run.sweep(link=False)
+    run.sweep(link=True)
+    return run.finish()
+
+
+class _DBSCANRun:
+    """The state and the three phases of one ``dbscan`` call on normalised rows ``src`` (tools/dbscan_bench.py times them one
+    by one): ``sweep(False)`` counts the degrees, ``sweep(True)`` links, ``finish()`` resolves the roots and numbers them."""
+
+    def __init__(self, src, threshold: float, min_samples: int, block, eps: float):
+        N, dev = src.rows, src.device
+        self.src, self.t, self.ms, self.eps = src, threshold, min_samples, eps
+        self.block = min(_DBSCAN_BLOCK if block is None else int(block), N)
+        self.degree = torch.empty(N, dtype=torch.int32, device=dev)
+        self.parent = torch.empty(N, dtype=torch.int32, device=dev)
+        self.border = torch.empty(N, dtype=torch.int64, device=dev)
+        self.e_degree, self.e_link, ws_bytes = _DBSCAN[src.dtype]
+        self.ws = _rank._ws.get(dev, getattr(lib(), ws_bytes)(self.block, N, src.dim))
+        with torch.cuda.device(dev):
+            check(lib().mi355_dbscan_init(N, self.degree.data_ptr(), self.parent.data_ptr(), self.border.data_ptr(), stream_ptr(dev)))
+
+    def sweep(self, link: bool) -> None:
+        src, L = self.src, lib()
+        entry = getattr(L, self.e_link if link else self.e_degree)
+        state = (self.ms, self.degree.data_ptr(), self.parent.data_ptr(), self.border.data_ptr()) if link else (self.degree.data_ptr(),)
+        data = src.data
+        with torch.cuda.device(src.device):
+            for q0 in range(0, src.rows, self.block):
+                q = data[q0: q0 + self.block].float().contiguous()      # fp32 rows: the rows themselves, no copy
+                check(entry(q.data_ptr(), q0, q.shape[0], *src.c_args(), self.eps, self.t, *state, self.ws.data_ptr(),
+                            self.ws.numel(), stream_ptr(src.device)))
+
+    def finish(self) -> DBSCANResult:
+        N, dev = self.src.rows, self.src.device
+        root = torch.empty(N, dtype=torch.int64, device=dev)
+        core = torch.empty(N, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            check(lib().mi355_dbscan_finish(N, self.ms, self.degree.data_ptr(), self.parent.data_ptr(), self.border.data_ptr(),
+                                            root.data_ptr(), core.data_ptr(), stream_ptr(dev)))
+        member = root >= 0
+        roots, inverse, counts = torch.unique(root[member], sorted=True, return_inverse=True, return_counts=True)
+        labels = torch.full((N,), -1, dtype=torch.int64, device=dev)
+        labels[member] = inverse
+        return DBSCANResult(labels, core.bool(), self.degree.long(), roots, counts, int(roots.shape[0]), N - int(inverse.shape[0]))
+
+
+def connected_components(rows, threshold: float, **kw) -> DBSCANResult:
+    """The connected components of the threshold graph of ``rows`` (rows i, j joined when ``hit(i, j)`` or ``hit(j, i)``, see
+    ``dbscan``): ``dbscan(rows, threshold, min_samples=1, **kw)`` - every row is a core row, no row is noise, and a
+    component's root is its smallest row.  The de-duplication groups of ``range_search`` pairs, without the pairs."""
+    return dbscan(rows, threshold, 1, **kw)
 
 
 def _dense(t, name: str):

@@ -1371,6 +1371,37 @@ int nearest_centroid(const float* centroids, i64 K, const GalleryRows& g, i64 G,
     return OK;
 }
 
+size_t dbscan_ws_bytes(i64 rows, i64 N, int dim, size_t (*planes_bytes)(i64, int), bool need_ginv) {
+    return carve(nullptr, rows, N, dim, 0, planes_bytes, need_ginv, false).total;
+}
+
+int dbscan_sweep(const float* queries, i64 q0, i64 rows, const GalleryRows& g, i64 N, int dim, float eps, double threshold,
+                 int min_samples, int32_t* degree, int32_t* parent, uint64_t* border, bool link, void* workspace,
+                 size_t workspace_bytes, void* stream, const char* who) {
+    if (int e = dbscan_check(queries, q0, rows, g.rows(), N, dim, threshold, min_samples, degree, parent, border, link, who)) return e;
+    if (int e = check_rows(g, who)) return e;
+    const size_t need = dbscan_ws_bytes(rows, N, dim, g.planes_bytes, g.f32 && !g.unit);
+    MI355_REQUIRE(workspace && workspace_bytes >= need, "%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
+    if (rows == 0) return OK;
+    const RankWs w = carve(workspace, rows, N, dim, 0, g.planes_bytes, g.f32 && !g.unit, false);
+    hipStream_t st = (hipStream_t)stream;
+    const float* ginv = g.f32 && !g.unit ? w.ginv : nullptr;
+    if (int e = normalize_search(queries, rows, ginv ? g.f32 : nullptr, N, dim, eps, w, st)) return e;
+    const float thr = roc_ceil_f32(threshold);
+    const i64 qb = roc_query_block(rows, N);
+    for (i64 b0 = 0; b0 < rows; b0 += qb) {
+        const i64 qn = (rows - b0 < qb) ? rows - b0 : qb;
+        RoctxRange range(link ? "dbscan/cosine gemm + link" : "dbscan/cosine gemm + degree");
+        if (link) {
+            const LinkEpi epi{thr, (int)(q0 + b0), min_samples, degree, parent, (unsigned long long*)border};
+            if (int e = score_rows(g, ginv, w.qn + b0 * dim, w.qs, qn, N, dim, epi, st)) return e;
+        } else {
+            if (int e = score_rows(g, ginv, w.qn + b0 * dim, w.qs, qn, N, dim, DegreeEpi{thr, degree + q0 + b0}, st)) return e;
+        }
+    }
+    return OK;
+}
+
 }  // namespace mi355
 
 using namespace mi355;
@@ -1508,6 +1539,25 @@ int mi355_nearest_centroid(const float* centroids, int64_t K, const float* rows,
                            void* stream) {
     return nearest_centroid(centroids, K, f32_rows(rows, rows_are_normalized), N, dim, eps, query_block, assign, score, workspace,
                             workspace_bytes, stream, "nearest_centroid");
+}
+
+size_t mi355_dbscan_workspace_bytes(int64_t rows, int64_t N, int dim) {
+    if (rows < 1 || N < 1 || dim < 1) return 0;
+    return dbscan_ws_bytes(rows, N, dim, split_queries_bytes, true);
+}
+
+int mi355_dbscan_degree(const float* queries, int64_t q0, int64_t rows, const float* gallery, int64_t N, int dim,
+                        int gallery_is_normalized, float eps, double threshold, int32_t* degree, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+    return dbscan_sweep(queries, q0, rows, f32_rows(gallery, gallery_is_normalized), N, dim, eps, threshold, 1, degree, nullptr,
+                        nullptr, false, workspace, workspace_bytes, stream, "dbscan_degree");
+}
+
+int mi355_dbscan_link(const float* queries, int64_t q0, int64_t rows, const float* gallery, int64_t N, int dim,
+                      int gallery_is_normalized, float eps, double threshold, int min_samples, const int32_t* degree,
+                      int32_t* parent, uint64_t* border, void* workspace, size_t workspace_bytes, void* stream) {
+    return dbscan_sweep(queries, q0, rows, f32_rows(gallery, gallery_is_normalized), N, dim, eps, threshold, min_samples,
+                        const_cast<int32_t*>(degree), parent, border, true, workspace, workspace_bytes, stream, "dbscan_link");
 }
 
 int mi355_clear_pads(float* val, int64_t* idx, int64_t n, int64_t lo, int64_t hi, void* stream) {

@@ -647,6 +647,151 @@ struct NearestEpi {
     }
 };
 
+// ---- DBSCAN / threshold components (mi355_dbscan_degree[_f16], mi355_dbscan_link[_f16]; host side and the finishing kernel in
+// dbscan.hip): the self-join of the resident rows, a block of them as the GEMM's queries, swept twice.  A hit is the range
+// search's: fp32 score >= roc_ceil_f32(threshold), NaN never, the row itself included.  Pass 1 counts each query row's hits
+// (its degree); pass 2 joins core rows (degree >= min_samples) that hit each other in a union-find over parent[] and offers
+// every core row to the non-core rows it hits or is hit by.  No pair list exists.  Every result is a sum of integers, a
+// maximum of keys or the minimum row of a component: none depends on the order of the atomics, the query block or the tile cut.
+// LDS of either epilogue: the degree epilogue's hit masks [128][4] u32 (the link epilogue's core flags are smaller)
+constexpr size_t DBSCAN_EPI_BYTES = (size_t)128 * 4 * sizeof(unsigned);
+
+// Pass 1: degree[row] += the row's hits in this tile, ONE integer atomic per (query row with hits, column tile)
+struct DegreeEpi {
+    float thr;                  // roc_ceil_f32(threshold)
+    int* degree;                // [rows of this call]: the degrees of its queries (the host shifts it per query block)
+    template <size_t STAGE> static constexpr size_t lds_bytes() {   // inside the staging buffers of every loop
+        static_assert(STAGE >= DBSCAN_EPI_BYTES, "the degree epilogue would grow the GEMM's LDS");
+        return STAGE;
+    }
+    // Scores are acc * ginv[col] as in the other epilogues: every hit is a hit of mi355_cosine_range on the same loop.
+    template <int MT>
+    __device__ __forceinline__ void tile(f32x16 (&acc)[MT][2], float* smem, const float* __restrict__ ginv, const TileCtx& t) const {
+        const int Q = t.Q, m0 = t.m0;
+        const i64 G = t.G, n0 = t.n0;
+        constexpr int BM = 64 * MT;
+        const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+        const int wm = wave >> 1, wn = wave & 1, lr = lane & 31;
+        unsigned* mask = reinterpret_cast<unsigned*>(smem);                  // [BM][4]: bit c % 32 of word c / 32 = column c
+        // the hit masks as the range epilogue takes them: lanes 0-31 hold 32 consecutive columns of one row, lanes 32-63 those
+        // of row + 4, so one ballot is two whole mask words; each (row, word) belongs to exactly one wave
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const i64 col = n0 + wn * 64 + j * 32 + lr;
+            const float gs = (ginv && col < G) ? ginv[col] : 1.0f;
+#pragma unroll
+            for (int i = 0; i < MT; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int row = wm * MT * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                    const bool hit = col < G && m0 + row < Q && acc[i][j][r] * gs >= thr;
+                    const unsigned long long b = __ballot(hit);
+                    if (lane == 0) {
+                        mask[row * 4 + wn * 2 + j] = (unsigned)b;
+                        mask[(row + 4) * 4 + wn * 2 + j] = (unsigned)(b >> 32);
+                    }
+                }
+        }
+        __syncthreads();
+        if (tid < BM && m0 + tid < Q) {
+            const int cnt = __popc(mask[tid * 4]) + __popc(mask[tid * 4 + 1]) + __popc(mask[tid * 4 + 2]) + __popc(mask[tid * 4 + 3]);
+            if (cnt) atomicAdd(&degree[m0 + tid], cnt);
+        }
+    }
+};
+
+// The union-find of pass 2 lives in parent[N] (parent[x] == x: a root).  Other workgroups, on other XCDs, work on it during the
+// same launch: the XCDs' L2s are not coherent and a CU's L1 is never refreshed, so inside the launch parent[] is read and
+// written ONLY by agent-scope relaxed atomics (loads that bypass L1, a compare-and-swap; no plain access, no fence).
+// Invariant: parent[x] <= x, and parent[x] is x itself or a true ancestor of x - a hook writes the smaller of two roots under
+// the larger, a shortcut writes a value that an atomic load returned as the parent of x's parent.  A value read late is thus
+// still an ancestor, and the compare-and-swap validates every hook against the word itself.
+__device__ __forceinline__ int uf_load(int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// The root above x as this thread sees it, pointing every visited row at its grandparent.  The walk strictly descends
+// (parent[y] < y unless y is a root), so it ends after at most x steps whatever other threads write meanwhile.
+__device__ __forceinline__ int uf_find(int* parent, int x) {
+    int p = uf_load(parent + x);
+    while (p != x) {
+        const int gp = uf_load(parent + p);
+        // x is not a root and never becomes one again, so this store cannot undo a hook (hooks change roots only)
+        if (gp != p) __hip_atomic_store(parent + x, gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        x = p;
+        p = gp;
+    }
+    return x;
+}
+// Joins the components of a and b: the larger root goes under the smaller, so a finished component's root is its smallest row
+// in any order of the hooks.  Termination: the loop ends when both walks reach one root (nothing is written: in a dense
+// cluster that is almost every hit) or when this thread's own compare-and-swap succeeds.  A failed one returns the word's
+// value, a true ancestor below hi, and lo is below hi too: the next round's larger root is strictly smaller than this
+// round's, so a thread makes fewer than N rounds.  No thread ever waits for a value another thread has yet to write.
+__device__ __forceinline__ void uf_union(int* parent, int a, int b) {
+    for (;;) {
+        a = uf_find(parent, a);
+        b = uf_find(parent, b);
+        if (a == b) return;
+        const int hi = a > b ? a : b, lo = a > b ? b : a;
+        int seen = hi;
+        if (__hip_atomic_compare_exchange_strong(parent + hi, &seen, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+            return;
+        a = seen;
+        b = lo;
+    }
+}
+
+// Pass 2, for every hit (i, j), i != j, of query row i = q0 + local row and column j: both core -> union(i, j); exactly one
+// core -> the non-core row's border key takes the maximum with rank_composite(score_key(score), core row): the highest score
+// wins, equal scores go to the lower core row.  degree[] is complete (pass 1 ended before this launch): plain loads.
+struct LinkEpi {
+    float thr;                  // roc_ceil_f32(threshold)
+    int q0;                     // global row of this call's first query
+    int min_samples;
+    const int* degree;          // [G]
+    int* parent;                // [G], see uf_find
+    unsigned long long* border; // [G] keys, zeroed before the first call (every real score's key is > 0)
+    template <size_t STAGE> static constexpr size_t lds_bytes() {   // inside the staging buffers of every loop
+        static_assert(STAGE >= DBSCAN_EPI_BYTES, "the link epilogue would grow the GEMM's LDS");
+        return STAGE;
+    }
+    // Scores are acc * ginv[col] as in the other epilogues: hits and border keys have the bits of mi355_cosine_range.
+    template <int MT>
+    __device__ __forceinline__ void tile(f32x16 (&acc)[MT][2], float* smem, const float* __restrict__ ginv, const TileCtx& t) const {
+        const int Q = t.Q, m0 = t.m0;
+        const i64 G = t.G, n0 = t.n0;
+        constexpr int BM = 64 * MT;
+        const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+        const int wm = wave >> 1, wn = wave & 1, lr = lane & 31;
+        unsigned char* ccore = reinterpret_cast<unsigned char*>(smem);      // [128] the tile's columns: 1 = core row
+        unsigned char* qcore = ccore + RK_BN;                               // [BM] its query rows
+        if (tid < RK_BN) ccore[tid] = n0 + tid < G && degree[n0 + tid] >= min_samples;
+        if (tid >= 128 && tid - 128 < BM) qcore[tid - 128] = m0 + tid - 128 < Q && degree[q0 + m0 + tid - 128] >= min_samples;
+        __syncthreads();
+        // C[row = query][col = gallery]; lane: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int c = wn * 64 + j * 32 + lr;
+            const i64 col = n0 + c;
+            if (col < G) {
+                const float gs = ginv ? ginv[col] : 1.0f;
+                const bool cc = ccore[c];
+#pragma unroll
+                for (int i = 0; i < MT; ++i)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int row = wm * MT * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                        const float s = acc[i][j][r] * gs;
+                        const int qi = q0 + m0 + row;
+                        if (m0 + row >= Q || !(s >= thr) || qi == (int)col) continue;
+                        const bool qc = qcore[row];
+                        if (qc && cc) uf_union(parent, qi, (int)col);
+                        else if (qc) atomicMax(&border[col], rank_composite(score_key(s), (unsigned)qi));
+                        else if (cc) atomicMax(&border[qi], rank_composite(score_key(s), (unsigned)col));
+                    }
+            }
+        }
+    }
+};
+
 // Row norm of an fp32 row: one wave, float4 loads when vec (dim % 4 == 0 and 16-B aligned rows).  The lane-strided
 // summation order is part of the result: every row normalisation of the library (mi355_l2_normalize_rows, the queries
 // of every search, the fp16 gallery conversion) goes through this one function, so they give the same bits.
@@ -940,6 +1085,16 @@ int rank_positives(const float* queries, i64 Q, const GalleryRows& g, i64 G, int
 size_t nearest_ws_bytes(i64 K, i64 G, int dim, size_t (*planes_bytes)(i64, int), bool need_ginv);
 int nearest_centroid(const float* centroids, i64 K, const GalleryRows& g, i64 G, int dim, float eps, i64 query_block,
                      int64_t* assign, float* score, void* workspace, size_t workspace_bytes, void* stream, const char* who);
+
+// mi355_dbscan_degree[_f16] (link false: parent / border unused) and mi355_dbscan_link[_f16]: one sweep of queries
+// [q0, q0 + rows) of the self-join over the N rows of g.  workspace = carve(rows, N, dim, 0, planes, need_ginv)
+size_t dbscan_ws_bytes(i64 rows, i64 N, int dim, size_t (*planes_bytes)(i64, int), bool need_ginv);
+int dbscan_sweep(const float* queries, i64 q0, i64 rows, const GalleryRows& g, i64 N, int dim, float eps, double threshold,
+                 int min_samples, int32_t* degree, int32_t* parent, uint64_t* border, bool link, void* workspace,
+                 size_t workspace_bytes, void* stream, const char* who);
+// The checks both sweeps share (dbscan.hip), before any HIP call
+int dbscan_check(const void* queries, i64 q0, i64 rows, const void* gallery, i64 N, int dim, double threshold, int min_samples,
+                 const void* degree, const void* parent, const void* border, bool link, const char* who);
 
 // ---- mi355_cluster_members without its host sync (kmeans.hip), for the IVF scan (ivf.hip): offsets [K + 1] and order [N] of
 // assign [N]; *flag: a device word that is 1 after a value outside [0, K) (such a value is in no cluster).  workspace:

@@ -308,6 +308,8 @@ template int cos_gemm_f16(const void*, int, const float*, void*, i64, i64, int, 
 template int cos_gemm_f16(const void*, int, const float*, void*, i64, i64, int, const RangeArgs&, hipStream_t);
 template int cos_gemm_f16(const void*, int, const float*, void*, i64, i64, int, const RanksArgs&, hipStream_t);
 template int cos_gemm_f16(const void*, int, const float*, void*, i64, i64, int, const NearestEpi&, hipStream_t);
+template int cos_gemm_f16(const void*, int, const float*, void*, i64, i64, int, const DegreeEpi&, hipStream_t);
+template int cos_gemm_f16(const void*, int, const float*, void*, i64, i64, int, const LinkEpi&, hipStream_t);
 
 static GalleryRows f16_rows(const void* gallery_f16, int dim) { return {nullptr, true, gallery_f16, f16_ld(dim), f16_planes_bytes}; }
 
@@ -459,6 +461,24 @@ int mi355_nearest_centroid_f16(const float* centroids, int64_t K, const void* ro
                                void* stream) {
     return nearest_centroid(centroids, K, f16_rows(rows_f16, dim), N, dim, eps, query_block, assign, score, workspace,
                             workspace_bytes, stream, "nearest_centroid_f16");
+}
+
+size_t mi355_dbscan_f16_workspace_bytes(int64_t rows, int64_t N, int dim) {
+    if (rows < 1 || N < 1 || dim < 1) return 0;
+    return dbscan_ws_bytes(rows, N, dim, f16_planes_bytes, false);
+}
+
+int mi355_dbscan_degree_f16(const float* queries, int64_t q0, int64_t rows, const void* gallery_f16, int64_t N, int dim, float eps,
+                            double threshold, int32_t* degree, void* workspace, size_t workspace_bytes, void* stream) {
+    return dbscan_sweep(queries, q0, rows, f16_rows(gallery_f16, dim), N, dim, eps, threshold, 1, degree, nullptr, nullptr, false,
+                        workspace, workspace_bytes, stream, "dbscan_degree_f16");
+}
+
+int mi355_dbscan_link_f16(const float* queries, int64_t q0, int64_t rows, const void* gallery_f16, int64_t N, int dim, float eps,
+                          double threshold, int min_samples, const int32_t* degree, int32_t* parent, uint64_t* border,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+    return dbscan_sweep(queries, q0, rows, f16_rows(gallery_f16, dim), N, dim, eps, threshold, min_samples,
+                        const_cast<int32_t*>(degree), parent, border, true, workspace, workspace_bytes, stream, "dbscan_link_f16");
 }
 
 }  // extern "C"

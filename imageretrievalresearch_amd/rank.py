@@ -716,7 +716,24 @@ class _GraphIndexed:
         return self._graph[key]
 
 
-class Gallery(_RowStore, _GraphIndexed):
+class _DensityClustered:
+    """``Gallery.dbscan`` and ``Gallery.components`` (cluster.py).  They live in a base of ``Gallery`` for the reason
+    ``_GraphIndexed`` does: their side-stream case is tests/test_dbscan_streams_gpu.py, not a row of the stream table, which
+    lists what ``Gallery`` itself defines."""
+
+    def dbscan(self, threshold: float, min_samples: int = 5, **kw):
+        """``dbscan`` of the resident rows (fp32 or fp16, read where they lie): a ``DBSCANResult`` whose hits are those of
+        ``range_search(self.data.float(), threshold)``.  Keywords as there (``block``).  Not cached."""
+        from . import cluster as _cl
+        return _cl.dbscan(self, threshold, min_samples, eps=self.eps, **kw)
+
+    def components(self, threshold: float, **kw):
+        """``connected_components`` of the resident rows' threshold graph: ``dbscan(threshold, 1)``.  Not cached."""
+        from . import cluster as _cl
+        return _cl.connected_components(self, threshold, eps=self.eps, **kw)
+
+
+class Gallery(_RowStore, _GraphIndexed, _DensityClustered):
     """Resident gallery: rows are L2-normalised once when added and stay in HBM (the gallery is *born* on the
     GPU that embedded it).  ``search`` is then one fused call per query batch instead of the reference's per-query cosine +
     topk pair.

@@ -516,6 +516,42 @@ size_t mi355_contingency_workspace_bytes(int64_t N, int64_t Ka, int64_t Kb);
 int mi355_contingency(const int64_t* a, const int64_t* b, int64_t N, int64_t Ka, int64_t Kb, int64_t* table, void* workspace,
                       size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ DBSCAN and threshold components
+ * Clustering without a number of clusters, inside the tiled cosine GEMM: the self-join of N resident rows (fp32 rows [N][dim],
+ * gallery_is_normalized as in mi355_rank_topk, or the fp16 rows of mi355_gallery_to_f16) is swept twice, a block of rows at a
+ * time as the GEMM's queries; no pair list is ever made.  hit(i, j): the score of query row i against row j (the bits and the
+ * comparison of mi355_cosine_range: fp32 score >= the fp32 ceiling of threshold, NaN never, j == i included).
+ *   state (device, N entries each): degree int32, parent int32, border uint64.  mi355_dbscan_init: degree = 0, border = 0,
+ *     parent[i] = i.
+ *   mi355_dbscan_degree[_f16]: queries [rows][dim] device fp32 = rows [q0, q0 + rows) of the same data (normalised by the call
+ *     as the queries of every search are); degree[q0 + r] += the hits of query r.  Call it once per block until every row
+ *     has been a query; only then start the link sweeps.
+ *   mi355_dbscan_link[_f16]: the same sweep again.  Row i is core when degree[i] >= min_samples.  For a hit (i, j), i != j:
+ *     both core: their components are joined in parent[] (lock-free union-find, the larger root under the smaller: a finished
+ *     component's root is its smallest row); exactly one core: border[the other row] = max(border, score_key(score) << 32 |
+ *     ~core row): the highest score wins, equal scores go to the lower core row.
+ *   mi355_dbscan_finish: root[i] (device int64) = the smallest core row of row i's cluster - a core row's component, a
+ *     non-core row's chosen core row's - or -1 (noise: a non-core row no core row hit or was hit by); core[i] (device uint8).
+ * With min_samples = 1 every row is core and root[] is the connected components of the threshold graph.  Every output is the
+ * same for any block size, launch order and run.  N < 2^31 - 128.  Every argument is checked before any HIP call; the work
+ * is enqueued on the given stream and nothing synchronises. */
+size_t mi355_dbscan_workspace_bytes(int64_t rows, int64_t N, int dim);
+size_t mi355_dbscan_f16_workspace_bytes(int64_t rows, int64_t N, int dim);
+int mi355_dbscan_init(int64_t N, int32_t* degree, int32_t* parent, uint64_t* border, void* stream);
+int mi355_dbscan_degree(const float* queries, int64_t q0, int64_t rows, const float* gallery, int64_t N, int dim,
+                        int gallery_is_normalized, float eps, double threshold, int32_t* degree, void* workspace,
+                        size_t workspace_bytes, void* stream);
+int mi355_dbscan_degree_f16(const float* queries, int64_t q0, int64_t rows, const void* gallery_f16, int64_t N, int dim, float eps,
+                            double threshold, int32_t* degree, void* workspace, size_t workspace_bytes, void* stream);
+int mi355_dbscan_link(const float* queries, int64_t q0, int64_t rows, const float* gallery, int64_t N, int dim,
+                      int gallery_is_normalized, float eps, double threshold, int min_samples, const int32_t* degree,
+                      int32_t* parent, uint64_t* border, void* workspace, size_t workspace_bytes, void* stream);
+int mi355_dbscan_link_f16(const float* queries, int64_t q0, int64_t rows, const void* gallery_f16, int64_t N, int dim, float eps,
+                          double threshold, int min_samples, const int32_t* degree, int32_t* parent, uint64_t* border,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int mi355_dbscan_finish(int64_t N, int min_samples, const int32_t* degree, const int32_t* parent, const uint64_t* border,
+                        int64_t* root, uint8_t* core, void* stream);
+
 /* ------------------------------------------------------------------ inverted-file (IVF) search
  * The scan of the lists a query probes.  The gallery's rows stay where they lie and are read through the lists' CSR
  * (offsets [nlist + 1], order [G], device int64: the rows of list l are order[offsets[l] .. offsets[l + 1]), as
