@@ -7,8 +7,8 @@ sub-quantiser on what is left of a row once its cluster centre is taken away.
   (``PQGallery.train``'s loop), then every row added (``from_gallery`` is the same call)
 * ``index.add(embeddings, labels=None, assignments=None)`` normalise, ``assign_clusters`` unless given, residuals
   (``mi355_ivfpq_residuals``), encode (``mi355_pq_encode``), the lists and ``list_codes`` again
-* ``index.search(queries, k, nprobe, refine=None, ...)`` .. the rules of ``IVFPQIndex.search``; the scan is
-  ``mi355_ivfpq_residual_search``
+* ``index.search(queries, k, nprobe, refine=None, ...)`` .. ``IVFPQIndex.search`` itself; its scan call names
+  ``mi355_ivfpq_residual_search`` and takes the centroids as well
 * ``index.coarse(queries, probes)`` ...................... (Q, nprobe) fp32: the query . centroid terms of the scores
 * ``index.probe`` / ``index.recall(queries, k, nprobe, exact)`` / ``index.reconstruct()``
 * ``index.codes`` / ``list_codes`` / ``codebooks`` / ``labels`` / ``nbytes``
@@ -16,8 +16,9 @@ sub-quantiser on what is left of a row once its cluster centre is taken away.
 The score of (query, row) is ``coarse(q, list of the row) + the PQ score of the row's residual code``, specified bit for bit in
 include/mi355_retrieval.h; tests/ivfrpq_ref.py is the NumPy model.  With inner products there is still one table per query
 (``q . residual centroid`` does not depend on the list) and one scalar per (query, probed list).  The codes live in a
-``PQGallery`` of the residual codebooks (``index.pq``: growth and labels are ``rank._RowStore``'s); the lists are
-``_lists._ListIndex``.  Out of scope: an OPQ rotation, a sharded index, training on fp16 rows.
+``PQGallery`` of the residual codebooks (``index.pq``: growth and labels are ``rank._RowStore``'s); the lists, the search
+around the scan and ``recall`` are ``_lists._ListIndex``, the scan call is ``IVFPQIndex._scan``.  Out of scope: an
+OPQ rotation, a sharded index, training on fp16 rows.
 """
 from __future__ import annotations
 
@@ -66,6 +67,7 @@ class ResidualIVFPQIndex(IVFPQIndex):
 
     _NOUN, _STORE_NOUN = "residual IVF-PQ index", "code store"
     _HINT = "add rows through index.add"
+    _ENTRIES = ("mi355_ivfpq_residual_search_workspace_bytes", "mi355_ivfpq_residual_search")
 
     def __init__(self, centroids: torch.Tensor, codebooks: torch.Tensor, eps: float = _rank._EPS):
         if not torch.is_tensor(centroids) or centroids.dim() != 2 or centroids.shape[0] < 1:
@@ -175,20 +177,8 @@ class ResidualIVFPQIndex(IVFPQIndex):
             raise MI355Error(f"queries are on {queries.device} but the index lives on {pq.device}")
         return pq._queries(queries, "search")
 
-    def _scan(self, q, probes, cap, k, idx_offset, filt):
-        pq, dev, L = self.pq, self.pq.device, lib()
-        Q, nprobe = q.shape[0], probes.shape[1]
-        vals = torch.empty((Q, k), dtype=torch.float32, device=dev)
-        idx = torch.empty((Q, k), dtype=torch.int64, device=dev)
-        if Q:
-            ws = _rank._ws.get(dev, L.mi355_ivfpq_residual_search_workspace_bytes(Q, nprobe, self.nlist, pq.dim, pq.M, cap, k))
-            with torch.cuda.device(dev):
-                check(L.mi355_ivfpq_residual_search(q.data_ptr(), Q, pq.dim, pq.eps, pq._codebooks.data_ptr(), pq.M,
-                                                    self.list_codes.data_ptr(), self.rows, self.offsets.data_ptr(),
-                                                    self.order.data_ptr(), self.nlist, probes.data_ptr(), nprobe, cap, k,
-                                                    int(idx_offset), None if filt is None else filt[0], self.centroids.data_ptr(),
-                                                    vals.data_ptr(), idx.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr(dev)))
-        return vals, idx
+    def _scan_args(self):
+        return (self.centroids.data_ptr(),)
 
     def coarse(self, queries: torch.Tensor, probes: torch.Tensor) -> torch.Tensor:
         """(Q, nprobe) fp32: ``qn . centroids[probes[q, j]]``, the term a search adds to the PQ score of every row of that list
@@ -208,10 +198,7 @@ class ResidualIVFPQIndex(IVFPQIndex):
     def recall(self, queries: torch.Tensor, k: int, nprobe: int, exact, **search_kwargs):
         """(mean, per_query (Q,) float64): the share of ``exact.search(queries, k)``'s indices that ``search(queries, k,
         nprobe, **search_kwargs)`` returns; ``exact`` is a ``Gallery`` of the same rows."""
-        if not isinstance(exact, _rank.Gallery) or len(exact) != self.rows:
-            raise MI355Error(f"recall needs exact, a Gallery of the same {self.rows} rows")
-        got = self.search(queries, k, nprobe, **search_kwargs)[1]
-        return _rank._recall(got, exact.search(queries, k)[1], k)
+        return self._recall_lists(queries, k, nprobe, exact, True, **search_kwargs)
 
     def reconstruct(self) -> torch.Tensor:
         """(rows, dim) fp32: ``centroids[assignments]`` plus the centroids each row's residual codes name."""

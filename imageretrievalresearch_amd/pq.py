@@ -12,7 +12,8 @@ D = 1536 and M = 96 a 64th of the fp32 row, so that a million rows are 96 MB and
 The format is approximate against the fp32 cosine, but its arithmetic is specified bit for bit in include/mi355_retrieval.h: a
 score depends on its query, its code row and the codebooks alone, and a NumPy model (tests/pq_ref.py) reproduces every bit of
 the codes, the tables, the scores, the top-k and the trained codebooks.  ``pq.ivf(rows, nlist)`` puts IVF lists over the codes
-(ivfpq.py).  Growth of the code buffer, labels and recall come from ``rank._RowStore``, as for the other galleries.  Codes of a row's offset from its list centroid are ``ResidualIVFPQIndex`` (ivfrpq.py).  Out of scope
+(ivfpq.py).  Growth of the code buffer, labels, recall and the shortlist rules of ``refine=`` come from ``rank._RowStore``, as for
+the other galleries.  Codes of a row's offset from its list centroid are ``ResidualIVFPQIndex`` (ivfrpq.py).  Out of scope
 (DESIGN §7): an OPQ rotation, a sharded PQ gallery, range search / query expansion over codes, training on fp16 rows.
 """
 from __future__ import annotations
@@ -26,47 +27,8 @@ from ._lib import MI355Error, check, lib, stream_ptr
 CENTROIDS = 256                     # centroids of every sub-quantiser: a code is one byte
 MAX_M, MAX_DSUB = 128, 64
 SCAN_CHUNK = 2048                   # rows of one scan workgroup (PQ_CHUNK, csrc/pq.hip)
-_MAX_K = 1024                       # largest k of any search, and the longest shortlist
 _is_int = _rank._is_int
-
-
-def _shortlist_length(store, k, refine, shortlist):
-    """(k, R) of a search over ``store``'s rows: the checked k, and the rows the approximate scan returns per query - k itself,
-    or with ``refine`` the length of the shortlist it rescores.  ``store`` is any row store with ``rows``, ``dim``, ``device``
-    and ``_NOUN``: the one set of rules behind ``PQGallery.search``, ``Int8Gallery.search`` and the indexes over them."""
-    top = min(_MAX_K, store.rows)
-    if not _is_int(k) or not 1 <= k <= top:
-        raise MI355Error(f"selected index k out of range: k={k!r} outside [1, {top}] (min({_MAX_K}, rows))")
-    k = int(k)
-    if refine is None:
-        if shortlist is not None:
-            raise MI355Error("shortlist is the length of the list that refine= rescores: give refine too")
-        return k, k
-    if not isinstance(refine, _rank.Gallery):
-        raise MI355Error(f"refine must be a Gallery of the same rows, got {type(refine).__name__}")
-    if refine.device != store.device:
-        raise MI355Error(f"refine is on {refine.device} but the {store._NOUN} lives on {store.device}")
-    if len(refine) != store.rows or refine.dim != store.dim:
-        raise MI355Error(f"refine holds {len(refine)} rows of dim {refine.dim}, the {store._NOUN} {store.rows} of dim {store.dim}")
-    R = min(max(10 * k, 100), top) if shortlist is None else shortlist
-    if not _is_int(R) or not k <= R <= top:
-        raise MI355Error(f"shortlist={R!r} outside [k={k}, {top}] (min({_MAX_K}, rows))")
-    return k, int(R)
-
-
-def _refined_topk(store, q: torch.Tensor, vals: torch.Tensor, idx: torch.Tensor, k: int, refine, idx_offset):
-    """The tail of a refined search over ``store`` (``rows``, ``dim``, ``device``, ``eps``): the shortlist ``idx`` (Q, R) of the
-    queries ``q`` is scored again against ``refine``'s rows (``mi355_rescore_candidates``, into ``vals``), then ``merge_topk``
-    and ``clear_pads``."""
-    Q, R, L, dev = idx.shape[0], idx.shape[1], lib(), store.device
-    ws = _rank._ws.get(dev, L.mi355_rescore_candidates_workspace_bytes(Q, store.dim))
-    with torch.cuda.device(dev):
-        check(L.mi355_rescore_candidates(q.data_ptr(), Q, store.dim, store.eps, refine._buf.data_ptr(),
-                                         _rank._DTYPES[refine.dtype], refine._ld, store.rows, idx.data_ptr(), R, int(idx_offset),
-                                         vals.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr(dev)))
-    v, i = _rank.merge_topk(vals, idx, k)
-    _rank.clear_pads(v, i, int(idx_offset), int(idx_offset) + store.rows)
-    return v, i
+_refined_topk = _rank._RowStore._refined_topk       # (store, q, vals, idx, k, refine, idx_offset): the row store's own routine
 
 
 class PQGallery(_rank._RowStore):
@@ -254,7 +216,7 @@ class PQGallery(_rank._RowStore):
         rows)``, default ``min(max(10 * k, 100), 1024, rows)``), each is scored again as ``qn . row`` against the gallery's row
         (the bits an ``IVFIndex`` scan gives the pair) and the top-k of those values is returned.  Nothing is read back."""
         self._trained("search")
-        k, R = _shortlist_length(self, k, refine, shortlist)
+        k, R = self._shortlist_length(k, refine, shortlist)
         q = self._queries(queries, "search")
         Q = q.shape[0]
         gl = None if label_filter is None else self._labels_for(f'label_filter="{label_filter}"')
@@ -262,7 +224,7 @@ class PQGallery(_rank._RowStore):
         vals, idx = self._pq_topk(q, R, idx_offset, filt)
         if refine is None or Q == 0:
             return vals[:, :k], idx[:, :k]
-        return _refined_topk(self, q, vals, idx, k, refine, idx_offset)
+        return self._refined_topk(q, vals, idx, k, refine, idx_offset)
 
     def recall(self, queries: torch.Tensor, k: int, exact: "_rank.Gallery", **search_kwargs):
         """(mean, per_query (Q,) float64): the share of ``exact.search(queries, k)``'s indices that ``search(queries, k,

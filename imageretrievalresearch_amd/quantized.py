@@ -107,13 +107,12 @@ class Int8Gallery(_rank._RowStore, _ListIndexed):
         gl = None if label_filter is None else self._labels_for(f'label_filter="{label_filter}"')
         if refine is None and shortlist is None:
             return _rank._topk(queries, self._resident(), k, self.eps, idx_offset, query_labels, gl, label_filter, exclude)
-        from . import pq as _pq
-        k, R = _pq._shortlist_length(self, k, refine, shortlist)
+        k, R = self._shortlist_length(k, refine, shortlist)
         q = _rank._f32c(queries, "queries")
         vals, idx = _rank._topk(q, self._resident(), R, self.eps, idx_offset, query_labels, gl, label_filter, exclude)
         if q.shape[0] == 0:
             return vals[:, :k], idx[:, :k]
-        return _pq._refined_topk(self, q, vals.contiguous(), idx.contiguous(), k, refine, idx_offset)
+        return self._refined_topk(q, vals.contiguous(), idx.contiguous(), k, refine, idx_offset)
 
     def range_search(self, queries: torch.Tensor, threshold: float, *, query_labels: torch.Tensor | None = None,
                      label_filter: str | None = None, exclude: torch.Tensor | None = None, max_results: int | None = None,

@@ -21,7 +21,8 @@ planes): a tensor argument, a ``PreparedGallery``, a ``Gallery`` and a ``Sharded
 and ROC histogram are one function each (``_topk``, ``_range``, ``_roc_hist``) that checks the arguments once and picks the
 fp32, fp16 or int8 C entry from ``_ENTRIES``; the public functions and methods are wrappers that add their own labels.  (int8 rows
 come from an ``Int8Gallery``, quantized.py, and have the top-k and range entries only.)  ``Gallery``, ``Int8Gallery`` and
-``PQGallery`` (pq.py) grow their buffers, keep their labels and measure recall through one base, ``_RowStore``.
+``PQGallery`` (pq.py) grow their buffers, keep their labels, measure recall and rescore a ``refine=`` shortlist through one base,
+``_RowStore``.
 """
 from __future__ import annotations
 
@@ -635,10 +636,24 @@ def _recall(got_idx: torch.Tensor, want_idx: torch.Tensor, k: int):
     return (float(per.mean()) if per.numel() else 1.0), per
 
 
+def _filter_from(filt, q0: int):
+    """``filt`` (what ``_rank_filter`` returned for a batch of queries) for the queries from ``q0`` on, as ``filter_from`` does
+    in C: the same gallery labels and mode, the per-query arrays entered ``q0`` int64 later."""
+    if filt is None or not q0:
+        return filt
+    f, keep = filt
+    r = RankFilter(f.query_labels and f.query_labels + 8 * q0, f.gallery_labels, f.label_mode, f.exclude and f.exclude + 8 * q0)
+    return r, keep
+
+
+_MAX_K = 1024                       # the largest k of any search, and the longest shortlist
+
+
 class _RowStore:
     """What ``Gallery``, ``Int8Gallery`` (quantized.py) and ``PQGallery`` (pq.py) share: ``rows`` labelled rows of ``dim``
     columns on ``device``, resident in the buffers a class names in ``_BUFFERS`` (one row each per gallery row, all of one
-    capacity), which only grow.  A class says how a block of rows is written (``_write``); growth, labels and recall are here."""
+    capacity), which only grow.  A class says how a block of rows is written (``_write``); growth, labels, recall and the rules
+    of a shortlist that ``refine=`` rescores are here."""
 
     _BUFFERS: tuple = ()
 
@@ -696,6 +711,42 @@ class _RowStore:
             raise MI355Error(f"recall needs a Gallery of the same {self.rows} rows")
         got = self.search(queries, k, **search_kwargs)[1]
         return _recall(got, exact.search(queries, k)[1], k)
+
+    def _shortlist_length(self, k, refine, shortlist):
+        """(k, R) of a search over these rows: the checked k, and the rows the first scan returns per query - k itself, or with
+        ``refine`` the length of the shortlist it rescores.  The one set of rules behind ``PQGallery.search``,
+        ``Int8Gallery.search`` and every list index (a store that takes ``refine`` has a ``_NOUN``)."""
+        top = min(_MAX_K, self.rows)
+        if not _is_int(k) or not 1 <= k <= top:
+            raise MI355Error(f"selected index k out of range: k={k!r} outside [1, {top}] (min({_MAX_K}, rows))")
+        k = int(k)
+        if refine is None:
+            if shortlist is not None:
+                raise MI355Error("shortlist is the length of the list that refine= rescores: give refine too")
+            return k, k
+        if not isinstance(refine, Gallery):
+            raise MI355Error(f"refine must be a Gallery of the same rows, got {type(refine).__name__}")
+        if refine.device != self.device:
+            raise MI355Error(f"refine is on {refine.device} but the {self._NOUN} lives on {self.device}")
+        if len(refine) != self.rows or refine.dim != self.dim:
+            raise MI355Error(f"refine holds {len(refine)} rows of dim {refine.dim}, the {self._NOUN} {self.rows} of dim {self.dim}")
+        R = min(max(10 * k, 100), top) if shortlist is None else shortlist
+        if not _is_int(R) or not k <= R <= top:
+            raise MI355Error(f"shortlist={R!r} outside [k={k}, {top}] (min({_MAX_K}, rows))")
+        return k, int(R)
+
+    def _refined_topk(self, q: torch.Tensor, vals: torch.Tensor, idx: torch.Tensor, k: int, refine, idx_offset):
+        """The tail of a refined search: the shortlist ``idx`` (Q, R) of the queries ``q`` is scored again against ``refine``'s
+        rows (``mi355_rescore_candidates``, into ``vals``), then ``merge_topk`` and ``clear_pads``."""
+        Q, R, L, dev = idx.shape[0], idx.shape[1], lib(), self.device
+        ws = _ws.get(dev, L.mi355_rescore_candidates_workspace_bytes(Q, self.dim))
+        with torch.cuda.device(dev):
+            check(L.mi355_rescore_candidates(q.data_ptr(), Q, self.dim, self.eps, refine._buf.data_ptr(), _DTYPES[refine.dtype],
+                                             refine._ld, self.rows, idx.data_ptr(), R, int(idx_offset), vals.data_ptr(),
+                                             ws.data_ptr(), ws.numel(), stream_ptr(dev)))
+        v, i = merge_topk(vals, idx, k)
+        clear_pads(v, i, int(idx_offset), int(idx_offset) + self.rows)
+        return v, i
 
 
 class _GraphIndexed:

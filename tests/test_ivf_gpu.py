@@ -171,16 +171,21 @@ def test_filters(kind):
             kw["exclude"] = torch.from_numpy(c["exclude"]).to(DEV)
         if "label_filter" in c:
             kw.update(label_filter=c["label_filter"], query_labels=torch.from_numpy(qlab).to(DEV))
-        v, i = ix.search(q, k, probes=pt, **kw)
-        v, i = v.cpu().numpy(), i.cpu().numpy()
         wv, wi, gap = ref.topk(S, k, off)
-        local = np.where(i >= 0, i - off, 0)
-        assert (np.isfinite(np.take_along_axis(S, local, axis=1)) | (i < 0)).all(), c      # an ineligible row never appears
-        if "exclude" in c:
-            assert not (i == c["exclude"][:, None]).any()
-        # assert_topk_matches looks scores up by the returned index: hand it local indices
-        assert_topk_matches(v, np.where(i >= 0, i - off, -1), wv, np.where(wi >= 0, wi - off, -1), gap=gap, what=str(sorted(c)),
-                            scores_ref=S)
+        whole = None
+        for block in (None, 2, 4):            # one trip; five and three trips, the last ragged: every block its own queries' filter
+            tv, ti = ix.search(q, k, probes=pt, block=block, **kw)
+            v, i = tv.cpu().numpy(), ti.cpu().numpy()
+            local = np.where(i >= 0, i - off, 0)
+            assert (np.isfinite(np.take_along_axis(S, local, axis=1)) | (i < 0)).all(), (c, block)   # an ineligible row never appears
+            if "exclude" in c:
+                assert not (i == c["exclude"][:, None]).any(), (c, block)
+            # assert_topk_matches looks scores up by the returned index: hand it local indices
+            assert_topk_matches(v, np.where(i >= 0, i - off, -1), wv, np.where(wi >= 0, wi - off, -1), gap=gap,
+                                what=f"{sorted(c)} block={block}", scores_ref=S)
+            if whole is None:
+                whole = _bits(tv), _bits(ti)
+            assert (_bits(tv) == whole[0]).all() and (_bits(ti) == whole[1]).all(), (c, block)
 
 
 def _planted():

@@ -245,10 +245,10 @@ def test_filters_and_pads(D):
         kw = dict(idx_offset=off, query_labels=_dev(ql), label_filter=label_filter, exclude=_dev(ex))
         for k in (3, 9, 150):
             wv, wi = R.search(m["s"], m["offsets"], m["order"], probes, k, ok, off)
-            for Q in (1, NQ):
-                v, i = ix.search(m["q"][:Q], k, probes=_dev(probes[:Q]),
+            for Q, block in ((1, None), (NQ, None), (NQ, 7)):                     # 7: 29 trips, each with its own queries' filter
+                v, i = ix.search(m["q"][:Q], k, probes=_dev(probes[:Q]), block=block,
                                  **{n: (a[:Q] if torch.is_tensor(a) else a) for n, a in kw.items()})
-                what = f"Q={Q} k={k} {label_filter}"
+                what = f"Q={Q} block={block} k={k} {label_filter}"
                 assert (_np(i) == wi[:Q]).all(), what
                 _assert_bits(v, wv[:Q], what)
         gl = None if label_filter is None else _dev(m["lab"])
