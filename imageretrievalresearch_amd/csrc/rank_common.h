@@ -892,8 +892,8 @@ int round_slots(int device_slots);
 // The cut of the calling thread's last GEMM call (mi355_rank_last_tiles)
 void set_last_tiles(int slots, int ny, int main_tiles, int tail_tiles, int tail_ny);
 
-// ---- host side of the tiled cosine GEMMs: exact fp32, split bf16 (rank.hip: F32Gemm, SplitGemm, PreparedGemm) and fp16
-// (rank_f16.hip: F16Gemm) and int8 (rank_i8.hip: I8Gemm).  A family F supplies only what differs between them:
+// ---- host side of the tiled cosine GEMMs: exact fp32, split bf16 (rank.hip: F32Gemm, SplitGemm, PreparedGemm) and fp16 and
+// int8 rows (rows_gemm.h: RowsGemm<F16Rows>, RowsGemm<I8Rows>).  A family F supplies only what differs between them:
 //   F::stage_bytes<MT>()             the LDS of its staging buffers
 //   F::kernel<MT, Epi>()             its kernel with epilogue Epi
 //   F::launch<MT, Epi>(...)          one launch of that kernel over column tiles [x0, x0 + xtiles) x ny query tiles
@@ -1057,12 +1057,12 @@ struct GalleryRows {
     const float* scales = nullptr;      // their scales [G]
     const void* rows() const { return i8 ? i8 : f16 ? f16 : (const void*)f32; }
 };
-// One GEMM call over fp16 rows: the normalised queries qn [Q][dim] into their fp16 planes qs, then F16Gemm with epi; sets the
-// rank path (rank_f16.hip; instantiated there for the epilogues of the three searches below)
+// One GEMM call over fp16 rows: the normalised queries qn [Q][dim] into their fp16 planes qs, then RowsGemm<F16Rows> with epi;
+// sets the rank path (rank_f16.hip; instantiated there for the epilogues of the three searches below)
 template <class Epi>
 int cos_gemm_f16(const void* rows, int ld, const float* qn, void* qs, i64 Q, i64 G, int dim, const Epi& epi, hipStream_t st);
-// The same over int8 rows: the queries' two int8 planes and s_q into qs, then I8Gemm with epi (rank_i8.hip; instantiated there
-// for the range epilogue)
+// The same over int8 rows: the queries' two int8 planes and s_q into qs, then RowsGemm<I8Rows> with epi (rank_i8.hip;
+// instantiated there for the range epilogue)
 template <class Epi>
 int cos_gemm_i8(const void* codes, const float* scales, int ld, const float* qn, void* qs, i64 Q, i64 G, int dim, const Epi& epi,
                 hipStream_t st);

@@ -9,7 +9,7 @@
 //     on v_mfma_f32_32x32x16_f16 into its own fp32 accumulator (every fp16 x fp16 product is exact in fp32) and returns
 //     acc_hi + acc_lo * 2^-11.  The GEMV (Q <= 4) uses the fp32 qn directly.  Either way |score - qn . row| stays ~1e-7.
 //   * order, ties, NaN: the selection of mi355_rank_topk (rank_common.h), so the same rule as cosine_topk / torch.topk.
-#include "rank_common.h"
+#include "rows_gemm.h"
 #include "../../include/mi355_retrieval.h"
 
 namespace mi355 {
@@ -77,147 +77,33 @@ __global__ __launch_bounds__(256) void k_split_queries_f16(const float* __restri
 }
 
 // =====================================================================================
-// cosine GEMM over fp16 rows: S / per-tile candidates as k_cos_gemm_split (same block and wave tiling, same launch order,
-// same epilogue, rank_common.h).  Block = 4 waves as 2(M) x 2(N), block tile (64 * MT) queries x 128 gallery rows,
-// k-step 64 (four 32x32x16 sub-steps).
-//   A (query planes): 8 * MT pieces of 1 KB per k-step by LDS-DMA from L2, one k-step ahead (ring of 2).
-//   B (gallery): the tile's 128 rows x 128 B per k-step by LDS-DMA from HBM, two k-steps ahead (ring of 3).  A piece is 8
-//     rows; the 16-byte chunk c of row r lands at position c ^ ((r >> 1) & 7) (applied to the per-lane SOURCE address, the
-//     DMA writes lane-linear): row r sits in half (r & 1) of a 256-byte bank row, so the ds_read_b128 of any 16 distinct
-//     rows of a lane group hit 16 distinct 16-byte slots.  Rows past G re-read row G - 1 (the epilogue drops them).
-// No load in the loop has a register destination: ONE counted vmcnt(4) per k-step (this iteration's four B pieces, issued
-// last, stay in flight) and one LDS-only barrier.  Per wave and k-step: 8 * MT + 8 ds_read_b128 and 16 * MT MFMAs.
-// LDS: 2 x 32 KB (A) + 3 x 16 KB (B) = 112 KB at MT = 2, 2 x 16 + 48 = 80 KB at MT = 1 (two workgroups per CU).
+// cosine GEMM over fp16 rows: the DMA-ring loop of rows_gemm.h with 8 f16 per fragment on v_mfma_f32_32x32x16_f16 (a sub-step
+// is 16 k), fp32 accumulators, and the tail acc_hi + acc_lo * 2^-11.  The stored rows are unit length: no column scale.
 // =====================================================================================
-template <int MT, class Epi>
-__device__ __forceinline__ void cos_gemm_f16_tile(const f16* __restrict__ Qs, const f16* __restrict__ Gal, int Q, i64 G, int ld,
-                                                  int x0, int ntx, int xtiles, int ny, const Epi& epi) {
-    constexpr int BM = 64 * MT;
-    constexpr int A_PIECES = (BM / 32) * 8;           // 1 KB pieces per stage: 4 sub-steps x 2 planes per row block
-    constexpr int A_STAGE = A_PIECES * 512;           // f16 elements per stage
-    constexpr int B_STAGE = RK_BN * F16_KSTEP;        // f16 elements per stage (16 KB)
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    f16* As = reinterpret_cast<f16*>(smem);           // [2][BM/32][4][2][512]
-    f16* Bs = As + 2 * A_STAGE;                       // [3][128][64], chunks swizzled
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1, lr = lane & 31;
-    int bx, by;
-    rank_tile_of((int)blockIdx.x, xtiles, ny, bx, by);
-    const i64 n0 = (i64)(bx + x0) * RK_BN;
-    const int m0 = by * BM;
-    const int swave = __builtin_amdgcn_readfirstlane(wave);
-    const int n_steps = ld / F16_KSTEP, n_sub = ld / 16;
-
-    // B: wave w moves pieces 4w .. 4w + 3; lane -> row 8 * piece + lane / 8, LDS position lane % 8
-    const f16* b_src[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int r = (swave * 4 + i) * 8 + (lane >> 3);
-        const int c = (lane & 7) ^ ((r >> 1) & 7);
-        const i64 g = n0 + r < G ? n0 + r : G - 1;
-        b_src[i] = Gal + g * ld + c * 8;
-    }
-    // (k-steps past the end re-read the last one: the data is never used, the count of pieces in flight stays uniform)
-    auto dma_b = [&](int stage, int t) {
-        const int tt = t < n_steps ? t : n_steps - 1;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            glds16(reinterpret_cast<const bf16_t*>(b_src[i] + tt * F16_KSTEP),
-                   reinterpret_cast<bf16_t*>(Bs + stage * B_STAGE + (swave * 4 + i) * 512));
-    };
-    // A: piece p = (row block p / 8, sub-step (p % 8) / 2, plane p % 2) of k-step t sits at
-    // Qs + ((m0/32 + p/8) * n_sub + 4t) * 1024 + (p % 8) * 512; wave w moves pieces w, w + 4, ...
-    const f16* a_src[A_PIECES / 4];
-#pragma unroll
-    for (int i = 0; i < A_PIECES / 4; ++i) {
-        const int p = swave + 4 * i;
-        a_src[i] = Qs + ((size_t)(m0 / 32 + p / 8) * n_sub) * 1024 + (p % 8) * 512 + lane * 8;
-    }
-    auto dma_a = [&](int buf, int t) {
-#pragma unroll
-        for (int i = 0; i < A_PIECES / 4; ++i)
-            glds16(reinterpret_cast<const bf16_t*>(a_src[i] + (size_t)t * 4 * 1024),
-                   reinterpret_cast<bf16_t*>(As + buf * A_STAGE + (swave + 4 * i) * 512));
-    };
-
-    f32x16 acc[MT][2], acc_lo[MT][2];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
+struct F16Tile {
+    typedef f16x8 Frag;
+    typedef f32x16 Acc;
+    static __device__ __forceinline__ Acc mfma(Frag a, Frag b, Acc c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+    __device__ __forceinline__ void tail(const Acc (&hi)[2], const Acc (&lo)[2], f32x16 (&acc)[2], int, int) const {
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
-            for (int e = 0; e < 16; ++e) { acc[i][j][e] = 0.f; acc_lo[i][j][e] = 0.f; }
-
-    // B fragment reads: row r = wn * 64 + j * 32 + lr, chunk 2s + (lane >> 5) of sub-step s at its swizzled position
-    int b_off[2][4];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int r = wn * 64 + j * 32 + lr;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) b_off[j][s] = r * F16_KSTEP + (((2 * s + (lane >> 5)) ^ ((r >> 1) & 7)) << 3);
+            for (int e = 0; e < 16; ++e) acc[j][e] = __builtin_fmaf(lo[j][e], F16_LO_UNSCALE, hi[j][e]);
     }
-    auto compute = [&](int abuf, int bstage) {
-        const f16* a = As + abuf * A_STAGE + (wm * MT) * 8 * 512 + lane * 8;
-        const f16* b = Bs + bstage * B_STAGE;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            f16x8 bf[2], ah[MT], al[MT];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) bf[j] = *reinterpret_cast<const f16x8*>(b + b_off[j][s]);
-#pragma unroll
-            for (int i = 0; i < MT; ++i) {
-                ah[i] = *reinterpret_cast<const f16x8*>(a + (i * 8 + s * 2) * 512);
-                al[i] = *reinterpret_cast<const f16x8*>(a + (i * 8 + s * 2 + 1) * 512);
-            }
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    acc_lo[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bf[j], acc_lo[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bf[j], acc[i][j], 0, 0, 0);
-                }
-        }
-    };
+    __device__ __forceinline__ const float* ginv() const { return nullptr; }
+};
+static_assert(F16_KSTEP * sizeof(f16) == ROWS_KSTEP, "a k-step is one 128-byte segment of a stored row");
 
-    dma_a(0, 0);
-    dma_b(0, 0);
-    dma_b(1, 1);
-    __syncthreads();                   // drains vmcnt: everything has landed
-
-    int bs_cur = 0, bs_far = 2;        // B stage of k-step t / of k-step t + 2
-    for (int t = 0; t < n_steps; ++t) {
-        if (t + 1 < n_steps) dma_a((t & 1) ^ 1, t + 1);   // everybody left this buffer at the previous barrier
-        __builtin_amdgcn_sched_barrier(0);                // (the count below needs the A pieces issued BEFORE the B pieces)
-        dma_b(bs_far, t + 2);
-        __builtin_amdgcn_sched_barrier(0);
-        compute(t & 1, bs_cur);
-        asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); // A(t+1) and B(t+1) have landed; the four B(t+2) pieces stay in flight
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        bs_cur = bs_cur == 2 ? 0 : bs_cur + 1;
-        bs_far = bs_far == 2 ? 0 : bs_far + 1;
-    }
-    __syncthreads();                   // the last look-ahead pieces have landed before the epilogue reuses the LDS
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = __builtin_fmaf(acc_lo[i][j][e], F16_LO_UNSCALE, acc[i][j][e]);
-    epi.tile(acc, smem, nullptr, TileCtx{Q, G, ntx, n0, m0});
-}
 template <int MT, int FK>
 __global__ __launch_bounds__(256) void k_cos_gemm_f16(const f16* __restrict__ Qs, const f16* __restrict__ Gal, int Q, i64 G,
                                                       int ld, int x0, int ntx, int xtiles, int ny, PlainEpi<FK> epi) {
-    cos_gemm_f16_tile<MT>(Qs, Gal, Q, G, ld, x0, ntx, xtiles, ny, epi);
+    rows_gemm_tile<F16Tile, MT>((const char*)Qs, (const char*)Gal, F16Tile{}, Q, G, ld * (int)sizeof(f16), x0, ntx, xtiles, ny, epi);
 }
 // Every other epilogue (filtered selection, histogram, range, ranks): the same loop
 template <int MT, class Epi>
 __global__ __launch_bounds__(256) void k_cos_gemm_f16_epi(const f16* __restrict__ Qs, const f16* __restrict__ Gal, int Q, i64 G,
                                                           int ld, int x0, int ntx, int xtiles, int ny, Epi epi) {
-    cos_gemm_f16_tile<MT>(Qs, Gal, Q, G, ld, x0, ntx, xtiles, ny, epi);
+    rows_gemm_tile<F16Tile, MT>((const char*)Qs, (const char*)Gal, F16Tile{}, Q, G, ld * (int)sizeof(f16), x0, ntx, xtiles, ny, epi);
 }
 
 // =====================================================================================
@@ -280,19 +166,34 @@ constexpr size_t F16_GEMV_LDS = 64 * 1024;
 static size_t f16_planes_bytes(i64 Q, int D) { return (size_t)cdiv(Q, 128) * 4 * (f16_ld(D) / 16) * 2 * 1024; }
 static bool f16_gemv(i64 Q, int ld) { return Q <= 4 && (size_t)Q * ld * sizeof(float) <= F16_GEMV_LDS; }
 
-// The tiled GEMM over fp16 rows (launch_tiles, rank_common.h); qry: the queries' fp16 planes, gal: the rows, D: their length ld
-struct F16Gemm {
-    template <int MT> static constexpr size_t stage_bytes() {   // A ring of 2, B ring of 3
-        return (size_t)2 * (64 * MT / 32) * 8 * 1024 + (size_t)3 * RK_BN * F16_KSTEP * 2;
+// The fp16 row kind of RowsGemm and rank_topk_rows (rows_gemm.h).  TileArgs::D is ld in f16 elements; the GEMV reads the fp32
+// queries, so a search that takes it carves no planes.
+struct F16Rows {
+    static constexpr bool SCALED = false, GEMV_PLANES = false;
+    static constexpr int MAX_DIM = 0, PATH_GEMV = MI355_RANK_PATH_F16_GEMV;
+    static constexpr const char* GEMV_RANGE = "rank/cosine gemv (fp16 gallery)";
+    static constexpr const char* GEMM_RANGE = "rank/cosine gemm (fp16 gallery)";
+    static constexpr const char* SELECT_RANGE = "rank/cosine gemm (fp16 gallery) + per-tile top-k";
+    static constexpr auto ld = f16_ld;
+    static constexpr auto planes_bytes = f16_planes_bytes;
+    static constexpr auto gemv = f16_gemv;
+    template <int MT, int FK> static constexpr auto plain_kernel() { return &k_cos_gemm_f16<MT, FK>; }
+    template <int MT, class Epi> static constexpr auto epi_kernel() { return &k_cos_gemm_f16_epi<MT, Epi>; }
+    template <class K, class Epi>
+    static void launch(K kernel, dim3 grid, size_t lds, hipStream_t st, const TileArgs& a, const Epi& epi, int x0, int ntx, int xtiles,
+                       int ny) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, (const f16*)a.qry, (const f16*)a.gal, a.Q, a.G, a.D, x0, ntx, xtiles, ny, epi);
     }
-    template <int MT, class Epi> static constexpr auto kernel() {
-        if constexpr (plain_fk<Epi> >= 0) return &k_cos_gemm_f16<MT, plain_fk<Epi>>;
-        else return &k_cos_gemm_f16_epi<MT, Epi>;
+    template <int NQ>
+    static int gemv_launch(const RankWs& w, const void* rows, const float*, i64 G, int dim, int ld, unsigned blocks, hipStream_t st) {
+        hipLaunchKernelGGL((k_cos_gemv_f16<NQ>), dim3(blocks), dim3(256), (size_t)NQ * ld * sizeof(float), st, w.qn, (const f16*)rows, w.S,
+                           G, dim, ld);
+        return OK;
     }
-    template <int MT, class Epi>
-    static void launch(dim3 grid, size_t lds, hipStream_t st, const TileArgs& a, const Epi& epi, int x0, int ntx, int xtiles, int ny) {
-        hipLaunchKernelGGL((kernel<MT, Epi>()), grid, dim3(256), lds, st, (const f16*)a.qry, (const f16*)a.gal, a.Q, a.G, a.D, x0, ntx,
-                           xtiles, ny, epi);
+    template <class Epi>
+    static int cos_gemm(const void* rows, const float*, int ld, const float* qn, void* qs, i64 Q, i64 G, int dim, const Epi& epi,
+                        hipStream_t st) {
+        return cos_gemm_f16(rows, ld, qn, qs, Q, G, dim, epi, st);
     }
 };
 
@@ -302,7 +203,7 @@ int cos_gemm_f16(const void* rows, int ld, const float* qn, void* qs, i64 Q, i64
     const int n_sub = ld / 16, n_frag = cdiv(Q, 128) * 4 * n_sub;
     hipLaunchKernelGGL(k_split_queries_f16, dim3((unsigned)cdiv(n_frag, 4)), dim3(256), 0, st, qn, (f16*)qs, (int)Q, dim, n_sub, n_frag);
     MI355_LAUNCH_CHECK();
-    return cos_gemm_tiles<F16Gemm>({qs, rows, nullptr, (int)Q, G, ld}, epi, st);
+    return cos_gemm_tiles<RowsGemm<F16Rows>>({qs, rows, nullptr, (int)Q, G, ld}, epi, st);
 }
 template int cos_gemm_f16(const void*, int, const float*, void*, i64, i64, int, const RocArgs&, hipStream_t);
 template int cos_gemm_f16(const void*, int, const float*, void*, i64, i64, int, const RangeArgs&, hipStream_t);
@@ -343,65 +244,19 @@ size_t mi355_rank_f16_workspace_bytes(int64_t Q, int64_t G, int dim, int k) {
     return carve(nullptr, Q, G, dim, k, f16_gemv(Q, f16_ld(dim)) ? nullptr : f16_planes_bytes, false).total;
 }
 
-}  // extern "C"
-
-// mi355_rank_topk_f16 and, with filt, mi355_rank_topk_f16_filtered: checks its arguments under the name who
-static int rank_topk_f16(const float* queries, int64_t Q, const void* gallery_f16, int64_t G, int dim, int k, float eps,
-                         int64_t idx_offset, float* out_val, int64_t* out_idx, void* workspace, size_t workspace_bytes,
-                         void* stream, const mi355_rank_filter* filter, const char* who) {
-    MI355_REQUIRE(queries && gallery_f16 && out_val && out_idx, "%s: null pointer", who);
-    MI355_REQUIRE(Q >= 0 && G >= 1 && dim >= 1, "%s: bad shape Q=%lld G=%lld dim=%d", who, (long long)Q, (long long)G, dim);
-    MI355_REQUIRE(k >= 1 && k <= LARGE_K && k <= G, "%s: k=%d outside [1, %lld]", who, k,
-                  (long long)(G < LARGE_K ? G : LARGE_K));
-    MI355_REQUIRE(((uintptr_t)gallery_f16 & 15) == 0, "%s: gallery buffer must be 16-byte aligned", who);
-    MI355_REQUIRE(Q <= INT_MAX && G <= ((int64_t)1 << 40), "%s: shape too large Q=%lld G=%lld", who, (long long)Q,
-                  (long long)G);
-    RankFilter fall{};
-    if (filter)
-        if (int e = make_filter(filter, idx_offset, who, &fall)) return e;
-    if (Q == 0) return OK;
-    const int ld = f16_ld(dim);
-    const bool gemv = f16_gemv(Q, ld);   // (Q <= 4: a single query block)
-    const RankWs w = carve(workspace, Q, G, dim, k, gemv ? nullptr : f16_planes_bytes, false);
-    MI355_REQUIRE(workspace && workspace_bytes >= w.total, "%s: workspace %zu < %zu bytes", who, workspace_bytes, w.total);
-    hipStream_t st = (hipStream_t)stream;
-    const f16* gal = (const f16*)gallery_f16;
-    return search_blocks(
-        queries, nullptr, Q, G, dim, k, eps, idx_offset, filter ? &fall : nullptr, out_val, (i64*)out_idx, w, st, "rank/top-k",
-        [&](i64 q0, i64 qn, const RankFilter* f) -> int {
-            if (gemv) {
-                RoctxRange range("rank/cosine gemv (fp16 gallery)");
-                const size_t lds = (size_t)qn * ld * sizeof(float);
-                const unsigned blocks = (unsigned)(cdiv(G, 4) < 4096 ? cdiv(G, 4) : 4096);
-#define GEMV_F16(NQ) hipLaunchKernelGGL((k_cos_gemv_f16<NQ>), dim3(blocks), dim3(256), lds, st, w.qn, gal, w.S, (i64)G, dim, ld)
-                if (qn == 1) GEMV_F16(1); else if (qn == 2) GEMV_F16(2); else if (qn == 3) GEMV_F16(3); else GEMV_F16(4);
-#undef GEMV_F16
-                MI355_LAUNCH_CHECK();
-                set_rank_path(MI355_RANK_PATH_F16_GEMV);
-                return OK;
-            }
-            RoctxRange range(w.cand_val ? "rank/cosine gemm (fp16 gallery) + per-tile top-k" : "rank/cosine gemm (fp16 gallery)");
-            return with_topk_epi(w, k, f, [&](const auto& epi) {
-                return cos_gemm_f16(gal, ld, w.qn + q0 * dim, w.qs, qn, G, dim, epi, st);
-            });
-        });
-}
-
-extern "C" {
-
 int mi355_rank_topk_f16(const float* queries, int64_t Q, const void* gallery_f16, int64_t G, int dim, int k, float eps,
                         int64_t idx_offset, float* out_val, int64_t* out_idx, void* workspace, size_t workspace_bytes,
                         void* stream) {
-    return rank_topk_f16(queries, Q, gallery_f16, G, dim, k, eps, idx_offset, out_val, out_idx, workspace, workspace_bytes, stream,
-                         nullptr, "rank_topk_f16");
+    return rank_topk_rows<F16Rows>(queries, Q, gallery_f16, nullptr, G, dim, k, eps, idx_offset, out_val, out_idx, workspace,
+                                   workspace_bytes, stream, nullptr, "rank_topk_f16");
 }
 
 int mi355_rank_topk_f16_filtered(const float* queries, int64_t Q, const void* gallery_f16, int64_t G, int dim, int k, float eps,
                                  int64_t idx_offset, const mi355_rank_filter* filter, float* out_val, int64_t* out_idx,
                                  void* workspace, size_t workspace_bytes, void* stream) {
     MI355_REQUIRE(filter, "rank_topk_f16_filtered: null filter (use the unfiltered entry)");
-    return rank_topk_f16(queries, Q, gallery_f16, G, dim, k, eps, idx_offset, out_val, out_idx, workspace, workspace_bytes, stream,
-                         filter, "rank_topk_f16_filtered");
+    return rank_topk_rows<F16Rows>(queries, Q, gallery_f16, nullptr, G, dim, k, eps, idx_offset, out_val, out_idx, workspace,
+                                   workspace_bytes, stream, filter, "rank_topk_f16_filtered");
 }
 
 size_t mi355_roc_pairs_f16_workspace_bytes(int64_t Q, int64_t G, int dim) {

@@ -15,6 +15,7 @@
 //     launches and every epilogue return the SAME bits for a (query, row) pair.
 //   * order, ties, NaN, pads: the selection of mi355_rank_topk (rank_common.h).
 #include "i8_quant.h"
+#include "rows_gemm.h"
 #include "../../include/mi355_retrieval.h"
 
 namespace mi355 {
@@ -139,159 +140,43 @@ __global__ __launch_bounds__(256) void k_split_queries_i8(const float* __restric
 }
 
 // =====================================================================================
-// cosine GEMM over int8 rows: S / per-tile candidates as k_cos_gemm_f16 (same block and wave tiling, same launch order, same
-// DMA rings, same epilogues, rank_common.h).  Block = 4 waves as 2(M) x 2(N), block tile (64 * MT) queries x 128 gallery rows,
-// k-step 128 (four 32x32x32 sub-steps, two planes each).
-//   A (query planes): 8 * MT pieces of 1 KB per k-step by LDS-DMA from L2, one k-step ahead (ring of 2).
-//   B (gallery): the tile's 128 rows x 128 B per k-step by LDS-DMA from HBM, two k-steps ahead (ring of 3).  A piece is 8
-//     rows; the 16-byte chunk c of row r lands at position c ^ ((r >> 1) & 7) (applied to the per-lane SOURCE address, the
-//     DMA writes lane-linear) - the byte layout of the fp16 kernel, so its swizzle carries over.  Rows past G re-read row G - 1
-//     (the epilogue drops them).
-// No load in the loop has a register destination: ONE counted vmcnt(4) per k-step (this iteration's four B pieces, issued
-// last, stay in flight) and one LDS-only barrier.  Per wave and k-step: 8 * MT + 8 ds_read_b128 and 16 * MT MFMAs.
-// LDS: 2 x 32 KB (A) + 3 x 16 KB (B) = 112 KB at MT = 2, 2 x 16 + 48 = 80 KB at MT = 1 (two workgroups per CU).
+// cosine GEMM over int8 rows: the DMA-ring loop of rows_gemm.h with 16 codes per fragment on v_mfma_i32_32x32x32_i8 (a sub-step
+// is 32 k), int32 accumulators, and the float tail t = fmaf(float(acc_lo), 2^-7, float(acc_hi)), then t * s_q per accumulator
+// row; the epilogue's acc * ginv[col] is the multiply by s_g.  (sq holds whole 128-row tiles: rows >= Q read 0.)
 // Fragment map: a lane's A and B fragments of a sub-step are the SAME 16 consecutive k (its half of the sub-step), byte for
 // byte.  The MFMA pairs A and B bytes by (lane half, byte), and an integer sum does not depend on the k order, so whichever k
 // the hardware calls them the result is the exact dot product.
 // =====================================================================================
-template <int MT, class Epi>
-__device__ __forceinline__ void cos_gemm_i8_tile(const signed char* __restrict__ Qs, const float* __restrict__ sq,
-                                                 const signed char* __restrict__ Gal, const float* __restrict__ scales, int Q, i64 G,
-                                                 int ld, int x0, int ntx, int xtiles, int ny, const Epi& epi) {
-    constexpr int BM = 64 * MT;
-    constexpr int A_PIECES = (BM / 32) * 8;           // 1 KB pieces per stage: 4 sub-steps x 2 planes per row block
-    constexpr int A_STAGE = A_PIECES * 1024;          // bytes per stage
-    constexpr int B_STAGE = RK_BN * I8_KSTEP;         // bytes per stage (16 KB)
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    signed char* As = reinterpret_cast<signed char*>(smem);   // [2][BM/32][4][2][1024]
-    signed char* Bs = As + 2 * A_STAGE;                        // [3][128][128], chunks swizzled
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1, lr = lane & 31;
-    int bx, by;
-    rank_tile_of((int)blockIdx.x, xtiles, ny, bx, by);
-    const i64 n0 = (i64)(bx + x0) * RK_BN;
-    const int m0 = by * BM;
-    const int swave = __builtin_amdgcn_readfirstlane(wave);
-    const int n_steps = ld / I8_KSTEP, n_sub = ld / 32;
-
-    // B: wave w moves pieces 4w .. 4w + 3; lane -> row 8 * piece + lane / 8, LDS position lane % 8
-    const signed char* b_src[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int r = (swave * 4 + i) * 8 + (lane >> 3);
-        const int c = (lane & 7) ^ ((r >> 1) & 7);
-        const i64 g = n0 + r < G ? n0 + r : G - 1;
-        b_src[i] = Gal + g * ld + c * 16;
-    }
-    // (k-steps past the end re-read the last one: the data is never used, the count of pieces in flight stays uniform)
-    auto dma_b = [&](int stage, int t) {
-        const int tt = t < n_steps ? t : n_steps - 1;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            glds16(reinterpret_cast<const bf16_t*>(b_src[i] + tt * I8_KSTEP),
-                   reinterpret_cast<bf16_t*>(Bs + stage * B_STAGE + (swave * 4 + i) * 1024));
-    };
-    // A: piece p = (row block p / 8, sub-step (p % 8) / 2, plane p % 2) of k-step t sits at
-    // Qs + ((m0/32 + p/8) * n_sub + 4t) * 2048 + (p % 8) * 1024; wave w moves pieces w, w + 4, ...
-    const signed char* a_src[A_PIECES / 4];
-#pragma unroll
-    for (int i = 0; i < A_PIECES / 4; ++i) {
-        const int p = swave + 4 * i;
-        a_src[i] = Qs + ((size_t)(m0 / 32 + p / 8) * n_sub) * 2048 + (p % 8) * 1024 + lane * 16;
-    }
-    auto dma_a = [&](int buf, int t) {
-#pragma unroll
-        for (int i = 0; i < A_PIECES / 4; ++i)
-            glds16(reinterpret_cast<const bf16_t*>(a_src[i] + (size_t)t * 4 * 2048),
-                   reinterpret_cast<bf16_t*>(As + buf * A_STAGE + (swave + 4 * i) * 1024));
-    };
-
-    i32x16 acc_hi[MT][2], acc_lo[MT][2];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) { acc_hi[i][j][e] = 0; acc_lo[i][j][e] = 0; }
-
-    // B fragment reads: row r = wn * 64 + j * 32 + lr, chunk 2s + (lane >> 5) of sub-step s at its swizzled position
-    int b_off[2][4];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int r = wn * 64 + j * 32 + lr;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) b_off[j][s] = r * I8_KSTEP + (((2 * s + (lane >> 5)) ^ ((r >> 1) & 7)) << 4);
-    }
-    auto compute = [&](int abuf, int bstage) {
-        const signed char* a = As + abuf * A_STAGE + (wm * MT) * 8 * 1024 + lane * 16;
-        const signed char* b = Bs + bstage * B_STAGE;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            i32x4 bf[2], ah[MT], al[MT];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) bf[j] = *reinterpret_cast<const i32x4*>(b + b_off[j][s]);
-#pragma unroll
-            for (int i = 0; i < MT; ++i) {
-                ah[i] = *reinterpret_cast<const i32x4*>(a + (i * 8 + s * 2) * 1024);
-                al[i] = *reinterpret_cast<const i32x4*>(a + (i * 8 + s * 2 + 1) * 1024);
-            }
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    acc_lo[i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(al[i], bf[j], acc_lo[i][j], 0, 0, 0);
-                    acc_hi[i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(ah[i], bf[j], acc_hi[i][j], 0, 0, 0);
-                }
-        }
-    };
-
-    dma_a(0, 0);
-    dma_b(0, 0);
-    dma_b(1, 1);
-    __syncthreads();                   // drains vmcnt: everything has landed
-
-    int bs_cur = 0, bs_far = 2;        // B stage of k-step t / of k-step t + 2
-    for (int t = 0; t < n_steps; ++t) {
-        if (t + 1 < n_steps) dma_a((t & 1) ^ 1, t + 1);   // everybody left this buffer at the previous barrier
-        __builtin_amdgcn_sched_barrier(0);                // (the count below needs the A pieces issued BEFORE the B pieces)
-        dma_b(bs_far, t + 2);
-        __builtin_amdgcn_sched_barrier(0);
-        compute(t & 1, bs_cur);
-        asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); // A(t+1) and B(t+1) have landed; the four B(t+2) pieces stay in flight
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        bs_cur = bs_cur == 2 ? 0 : bs_cur + 1;
-        bs_far = bs_far == 2 ? 0 : bs_far + 1;
-    }
-    __syncthreads();                   // the last look-ahead pieces have landed before the epilogue reuses the LDS
-    // the float tail: t = fmaf(float(acc_lo), 2^-7, float(acc_hi)), then t * s_q per accumulator row; the epilogue's
-    // acc * ginv[col] is the multiply by s_g.  (sq holds whole 128-row tiles: rows >= Q read 0.)
-    f32x16 acc[MT][2];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
+struct I8Tile {
+    typedef i32x4 Frag;
+    typedef i32x16 Acc;
+    const float* __restrict__ sq;       // s_q of the call's queries
+    const float* __restrict__ scales;   // s_g of the gallery rows
+    static __device__ __forceinline__ Acc mfma(Frag a, Frag b, Acc c) { return __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, c, 0, 0, 0); }
+    __device__ __forceinline__ void tail(const Acc (&hi)[2], const Acc (&lo)[2], f32x16 (&acc)[2], int row0, int lane) const {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const float s = sq[m0 + wm * MT * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)];
+            const float s = sq[row0 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)];
 #pragma unroll
-            for (int j = 0; j < 2; ++j)
-                acc[i][j][r] = __builtin_fmaf((float)acc_lo[i][j][r], 0x1p-7f, (float)acc_hi[i][j][r]) * s;
+            for (int j = 0; j < 2; ++j) acc[j][r] = __builtin_fmaf((float)lo[j][r], 0x1p-7f, (float)hi[j][r]) * s;
         }
-    epi.tile(acc, smem, scales, TileCtx{Q, G, ntx, n0, m0});
-}
+    }
+    __device__ __forceinline__ const float* ginv() const { return scales; }
+};
+static_assert(I8_KSTEP == ROWS_KSTEP, "a k-step is one 128-byte segment of a stored row");
+
 template <int MT, int FK>
 __global__ __launch_bounds__(256) void k_cos_gemm_i8(const signed char* __restrict__ Qs, const float* __restrict__ sq,
                                                      const signed char* __restrict__ Gal, const float* __restrict__ scales, int Q,
                                                      i64 G, int ld, int x0, int ntx, int xtiles, int ny, PlainEpi<FK> epi) {
-    cos_gemm_i8_tile<MT>(Qs, sq, Gal, scales, Q, G, ld, x0, ntx, xtiles, ny, epi);
+    rows_gemm_tile<I8Tile, MT>((const char*)Qs, (const char*)Gal, I8Tile{sq, scales}, Q, G, ld, x0, ntx, xtiles, ny, epi);
 }
 // Every other epilogue (filtered selection, range): the same loop
 template <int MT, class Epi>
 __global__ __launch_bounds__(256) void k_cos_gemm_i8_epi(const signed char* __restrict__ Qs, const float* __restrict__ sq,
                                                          const signed char* __restrict__ Gal, const float* __restrict__ scales,
                                                          int Q, i64 G, int ld, int x0, int ntx, int xtiles, int ny, Epi epi) {
-    cos_gemm_i8_tile<MT>(Qs, sq, Gal, scales, Q, G, ld, x0, ntx, xtiles, ny, epi);
+    rows_gemm_tile<I8Tile, MT>((const char*)Qs, (const char*)Gal, I8Tile{sq, scales}, Q, G, ld, x0, ntx, xtiles, ny, epi);
 }
 
 // =====================================================================================
@@ -367,25 +252,6 @@ static size_t i8_planes_only(i64 Q, int ld) { return (size_t)cdiv(Q, 128) * 4 * 
 static size_t i8_planes_bytes(i64 Q, int D) { return i8_planes_only(Q, i8_ld(D)) + (size_t)cdiv(Q, 128) * 128 * sizeof(float); }
 static bool i8_gemv(i64 Q, int ld) { return Q <= 4 && (size_t)Q * 2 * ld <= I8_GEMV_LDS; }
 
-// The tiled GEMM over int8 rows (launch_tiles, rank_common.h); qry: the queries' planes and s_q behind them, gal: the codes,
-// ginv: the rows' scales, D: the rows' length ld
-struct I8Gemm {
-    template <int MT> static constexpr size_t stage_bytes() {   // A ring of 2, B ring of 3
-        return (size_t)2 * (64 * MT / 32) * 8 * 1024 + (size_t)3 * RK_BN * I8_KSTEP;
-    }
-    template <int MT, class Epi> static constexpr auto kernel() {
-        if constexpr (plain_fk<Epi> >= 0) return &k_cos_gemm_i8<MT, plain_fk<Epi>>;
-        else return &k_cos_gemm_i8_epi<MT, Epi>;
-    }
-    template <int MT, class Epi>
-    static void launch(dim3 grid, size_t lds, hipStream_t st, const TileArgs& a, const Epi& epi, int x0, int ntx, int xtiles, int ny) {
-        const signed char* qs = (const signed char*)a.qry;
-        const float* sq = reinterpret_cast<const float*>(qs + i8_planes_only(a.Q, a.D));
-        hipLaunchKernelGGL((kernel<MT, Epi>()), grid, dim3(256), lds, st, qs, sq, (const signed char*)a.gal, a.ginv, a.Q, a.G, a.D,
-                           x0, ntx, xtiles, ny, epi);
-    }
-};
-
 // qn [Q][dim] normalised -> planes and s_q in qs (i8_planes_bytes(Q, dim))
 static int split_queries_i8(const float* qn, void* qs, i64 Q, int dim, int ld, hipStream_t st) {
     const int rows_pad = cdiv(Q, 128) * 128;
@@ -396,12 +262,50 @@ static int split_queries_i8(const float* qn, void* qs, i64 Q, int dim, int ld, h
     return OK;
 }
 
+// The int8 row kind of RowsGemm and rank_topk_rows (rows_gemm.h).  TileArgs: qry = the queries' planes with s_q behind them,
+// ginv = the rows' scales, D = ld.  The GEMV reads the GEMM's planes, so every search carves them and splits the queries first.
+struct I8Rows {
+    static constexpr bool SCALED = true, GEMV_PLANES = true;
+    static constexpr int MAX_DIM = I8_MAX_DIM, PATH_GEMV = MI355_RANK_PATH_I8_GEMV;
+    static constexpr const char* GEMV_RANGE = "rank/cosine gemv (int8 gallery)";
+    static constexpr const char* GEMM_RANGE = "rank/cosine gemm (int8 gallery)";
+    static constexpr const char* SELECT_RANGE = "rank/cosine gemm (int8 gallery) + per-tile top-k";
+    static constexpr auto ld = i8_ld;
+    static constexpr auto planes_bytes = i8_planes_bytes;
+    static constexpr auto gemv = i8_gemv;
+    template <int MT, int FK> static constexpr auto plain_kernel() { return &k_cos_gemm_i8<MT, FK>; }
+    template <int MT, class Epi> static constexpr auto epi_kernel() { return &k_cos_gemm_i8_epi<MT, Epi>; }
+    template <class K, class Epi>
+    static void launch(K kernel, dim3 grid, size_t lds, hipStream_t st, const TileArgs& a, const Epi& epi, int x0, int ntx, int xtiles,
+                       int ny) {
+        const signed char* qs = (const signed char*)a.qry;
+        const float* sq = reinterpret_cast<const float*>(qs + i8_planes_only(a.Q, a.D));
+        hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, qs, sq, (const signed char*)a.gal, a.ginv, a.Q, a.G, a.D, x0, ntx, xtiles,
+                           ny, epi);
+    }
+    template <int NQ>
+    static int gemv_launch(const RankWs& w, const void* codes, const float* scales, i64 G, int dim, int ld, unsigned blocks,
+                           hipStream_t st) {
+        if (int e = split_queries_i8(w.qn, w.qs, NQ, dim, ld, st)) return e;
+        const signed char* qs = (const signed char*)w.qs;
+        const float* sq = reinterpret_cast<const float*>(qs + i8_planes_only(NQ, ld));
+        hipLaunchKernelGGL((k_cos_gemv_i8<NQ>), dim3(blocks), dim3(256), (size_t)NQ * 2 * ld, st, qs, sq, (const signed char*)codes, scales,
+                           w.S, G, ld);
+        return OK;
+    }
+    template <class Epi>
+    static int cos_gemm(const void* codes, const float* scales, int ld, const float* qn, void* qs, i64 Q, i64 G, int dim, const Epi& epi,
+                        hipStream_t st) {
+        return cos_gemm_i8(codes, scales, ld, qn, qs, Q, G, dim, epi, st);
+    }
+};
+
 template <class Epi>
 int cos_gemm_i8(const void* codes, const float* scales, int ld, const float* qn, void* qs, i64 Q, i64 G, int dim, const Epi& epi,
                 hipStream_t st) {
     set_rank_path(MI355_RANK_PATH_I8_GEMM | (is_select<Epi> ? MI355_RANK_PATH_FUSED : 0));
     if (int e = split_queries_i8(qn, qs, Q, dim, ld, st)) return e;
-    return cos_gemm_tiles<I8Gemm>({qs, codes, scales, (int)Q, G, ld}, epi, st);
+    return cos_gemm_tiles<RowsGemm<I8Rows>>({qs, codes, scales, (int)Q, G, ld}, epi, st);
 }
 template int cos_gemm_i8(const void*, const float*, int, const float*, void*, i64, i64, int, const RangeArgs&, hipStream_t);
 
@@ -440,68 +344,18 @@ size_t mi355_rank_i8_workspace_bytes(int64_t Q, int64_t G, int dim, int k) {
     return carve(nullptr, Q, G, dim, k, i8_planes_bytes, false).total;
 }
 
-}  // extern "C"
-
-// mi355_rank_topk_i8 and, with filt, mi355_rank_topk_i8_filtered: checks its arguments under the name who
-static int rank_topk_i8(const float* queries, int64_t Q, const void* codes, const float* scales, int64_t G, int dim, int k,
-                        float eps, int64_t idx_offset, float* out_val, int64_t* out_idx, void* workspace, size_t workspace_bytes,
-                        void* stream, const mi355_rank_filter* filter, const char* who) {
-    MI355_REQUIRE(queries && codes && scales && out_val && out_idx, "%s: null pointer", who);
-    MI355_REQUIRE(Q >= 0 && G >= 1 && dim >= 1, "%s: bad shape Q=%lld G=%lld dim=%d", who, (long long)Q, (long long)G, dim);
-    MI355_REQUIRE(dim <= I8_MAX_DIM, "%s: dim=%d exceeds %d", who, dim, I8_MAX_DIM);
-    MI355_REQUIRE(k >= 1 && k <= LARGE_K && k <= G, "%s: k=%d outside [1, %lld]", who, k,
-                  (long long)(G < LARGE_K ? G : LARGE_K));
-    MI355_REQUIRE(((uintptr_t)codes & 15) == 0, "%s: gallery buffer must be 16-byte aligned", who);
-    MI355_REQUIRE(Q <= INT_MAX && G <= ((int64_t)1 << 40), "%s: shape too large Q=%lld G=%lld", who, (long long)Q,
-                  (long long)G);
-    RankFilter fall{};
-    if (filter)
-        if (int e = make_filter(filter, idx_offset, who, &fall)) return e;
-    if (Q == 0) return OK;
-    const int ld = i8_ld(dim);
-    const bool gemv = i8_gemv(Q, ld);    // (Q <= 4: a single query block)
-    const RankWs w = carve(workspace, Q, G, dim, k, i8_planes_bytes, false);
-    MI355_REQUIRE(workspace && workspace_bytes >= w.total, "%s: workspace %zu < %zu bytes", who, workspace_bytes, w.total);
-    hipStream_t st = (hipStream_t)stream;
-    const signed char* gal = (const signed char*)codes;
-    return search_blocks(
-        queries, nullptr, Q, G, dim, k, eps, idx_offset, filter ? &fall : nullptr, out_val, (i64*)out_idx, w, st, "rank/top-k",
-        [&](i64 q0, i64 qn, const RankFilter* f) -> int {
-            if (gemv) {
-                RoctxRange range("rank/cosine gemv (int8 gallery)");
-                if (int e = split_queries_i8(w.qn, w.qs, qn, dim, ld, st)) return e;
-                const signed char* qs = (const signed char*)w.qs;
-                const float* sq = reinterpret_cast<const float*>(qs + i8_planes_only(qn, ld));
-                const size_t lds = (size_t)qn * 2 * ld;
-                const unsigned blocks = (unsigned)(cdiv(G, 4) < 4096 ? cdiv(G, 4) : 4096);
-#define GEMV_I8(NQ) hipLaunchKernelGGL((k_cos_gemv_i8<NQ>), dim3(blocks), dim3(256), lds, st, qs, sq, gal, scales, w.S, (i64)G, ld)
-                if (qn == 1) GEMV_I8(1); else if (qn == 2) GEMV_I8(2); else if (qn == 3) GEMV_I8(3); else GEMV_I8(4);
-#undef GEMV_I8
-                MI355_LAUNCH_CHECK();
-                set_rank_path(MI355_RANK_PATH_I8_GEMV);
-                return OK;
-            }
-            RoctxRange range(w.cand_val ? "rank/cosine gemm (int8 gallery) + per-tile top-k" : "rank/cosine gemm (int8 gallery)");
-            return with_topk_epi(w, k, f, [&](const auto& epi) {
-                return cos_gemm_i8(gal, scales, ld, w.qn + q0 * dim, w.qs, qn, G, dim, epi, st);
-            });
-        });
-}
-
-extern "C" {
-
 int mi355_rank_topk_i8(const float* queries, int64_t Q, const void* codes, const float* scales, int64_t G, int dim, int k, float eps,
                        int64_t idx_offset, float* out_val, int64_t* out_idx, void* workspace, size_t workspace_bytes, void* stream) {
-    return rank_topk_i8(queries, Q, codes, scales, G, dim, k, eps, idx_offset, out_val, out_idx, workspace, workspace_bytes, stream,
-                        nullptr, "rank_topk_i8");
+    return rank_topk_rows<I8Rows>(queries, Q, codes, scales, G, dim, k, eps, idx_offset, out_val, out_idx, workspace, workspace_bytes,
+                                  stream, nullptr, "rank_topk_i8");
 }
 
 int mi355_rank_topk_i8_filtered(const float* queries, int64_t Q, const void* codes, const float* scales, int64_t G, int dim, int k,
                                 float eps, int64_t idx_offset, const mi355_rank_filter* filter, float* out_val, int64_t* out_idx,
                                 void* workspace, size_t workspace_bytes, void* stream) {
     MI355_REQUIRE(filter, "rank_topk_i8_filtered: null filter (use the unfiltered entry)");
-    return rank_topk_i8(queries, Q, codes, scales, G, dim, k, eps, idx_offset, out_val, out_idx, workspace, workspace_bytes, stream,
-                        filter, "rank_topk_i8_filtered");
+    return rank_topk_rows<I8Rows>(queries, Q, codes, scales, G, dim, k, eps, idx_offset, out_val, out_idx, workspace, workspace_bytes,
+                                  stream, filter, "rank_topk_i8_filtered");
 }
 
 size_t mi355_range_i8_workspace_bytes(int64_t Q, int64_t G, int dim) {

@@ -68,9 +68,13 @@ def _check_topk(v, i, s, k, what):
     assert not bad.any(), f"{what}: {int(bad.sum())} index mismatches outside ties"
 
 
-@pytest.mark.parametrize("D", [1536, 70])
-@pytest.mark.parametrize("G", [1, 127, 1000, 100000])
-def test_search_against_float64_reference(D, G):
+# D = 48, 150, 200: one, three and four k-steps of the GEMM (its gallery ring is three deep: re-read, exactly full, first reuse)
+_SEARCH_SHAPES = ([(G, D) for G in (1, 127, 1000, 100000) for D in (1536, 70)] +
+                  [(G, D) for G in (127, 1000) for D in (48, 150, 200)])
+
+
+@pytest.mark.parametrize("G,D", _SEARCH_SHAPES, ids=[f"{G}-{D}" for G, D in _SEARCH_SHAPES])
+def test_search_against_float64_reference(G, D):
     gal = M.Gallery(D, DEV, dtype=F16).add(_randn((G, D), 11 + G))
     qs = _randn((2000, D), 7)
     for Q in (1, 3, 5, 256, 2000):

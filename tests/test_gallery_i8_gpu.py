@@ -86,7 +86,7 @@ def test_conversion_bit_for_bit(D):
 
 # ---- 2. every search path equals the model
 @pytest.mark.parametrize("G", [1, 127, 129, 1000, 5000])
-@pytest.mark.parametrize("D", [1, 70, 128, 200, 1536])
+@pytest.mark.parametrize("D", [1, 70, 128, 200, 300, 400, 1536])     # 1, 1, 1, 2, 3, 4, 12 k-steps: the gallery ring is 3 deep
 def test_search_equals_the_model(D, G):
     m = _model(D, G)
     for Q in (1, 3, 4, 5, 64, 65, 200):
@@ -107,21 +107,23 @@ def test_search_equals_the_model(D, G):
 # ---- 3. the seam between the two launches
 @pytest.mark.parametrize("k", [3, 150])
 def test_tail_launch_is_bit_identical(k):
-    """Q = 200 x G = 5000 is 2 x 40 tiles: 8 slots cut them into whole rounds (one launch), 12 slots leave a tail launch."""
-    m = _model(200, 5000)
-    want_v, want_i = m["gal"].search(m["q"], k)
+    """Q = 200 x G = 5000 is 2 x 40 tiles: 8 slots cut them into whole rounds (one launch), 12 slots leave a tail launch.
+    D = 200, 300, 400: two, three and four k-steps."""
     out = (ctypes.c_int * 5)()
-    try:
-        for slots, tail in ((8, False), (12, True)):
-            assert lib().mi355_rank_set_round_slots(slots) == 0
-            v, i = m["gal"].search(m["q"], k)
-            assert lib().mi355_rank_last_tiles(out, 5) == 5
-            assert out[0] == slots and (out[3] > 0) == tail, list(out)
-            assert torch.equal(v.view(torch.int32), want_v.view(torch.int32)) and torch.equal(i, want_i)
-    finally:
-        assert lib().mi355_rank_set_round_slots(0) == 0
-    _assert_bits(want_v, m["top"][0][:, :k])
-    assert (_np(want_i) == m["top"][1][:, :k]).all()
+    for D in (200, 300, 400):
+        m = _model(D, 5000)
+        want_v, want_i = m["gal"].search(m["q"], k)
+        try:
+            for slots, tail in ((8, False), (12, True)):
+                assert lib().mi355_rank_set_round_slots(slots) == 0
+                v, i = m["gal"].search(m["q"], k)
+                assert lib().mi355_rank_last_tiles(out, 5) == 5
+                assert out[0] == slots and (out[3] > 0) == tail, list(out)
+                assert torch.equal(v.view(torch.int32), want_v.view(torch.int32)) and torch.equal(i, want_i), D
+        finally:
+            assert lib().mi355_rank_set_round_slots(0) == 0
+        _assert_bits(want_v, m["top"][0][:, :k], f"D={D}")
+        assert (_np(want_i) == m["top"][1][:, :k]).all(), D
 
 
 # ---- 4. a score depends on its query and its row only
