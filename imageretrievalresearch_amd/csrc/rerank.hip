@@ -272,7 +272,8 @@ __global__ __launch_bounds__(64) void k_kr_local_qe(LocalArgs a) {
         }
     }
     const bool fill = a.out_cols != nullptr;
-    const i64 off = fill ? a.out_off[row] : 0;
+    const i64 off = fill ? a.out_off[row] : 0, end = fill ? a.out_off[row + 1] : 0;
+    const bool fits = off >= 0 && end <= a.cap;            // a row that does not fit is not written, as in k_kr_sets
     const float k2f = (float)a.k2;
     int cur = 0, n = 0;
     int head = cur < len ? cols[cur] : INT_MAX;
@@ -287,7 +288,7 @@ __global__ __launch_bounds__(64) void k_kr_local_qe(LocalArgs a) {
             const float c = mine ? hv : 0.f;
             float sum = 0.f;
             for (int s = 0; s < a.k2; ++s) sum += __shfl(c, s, 64);      // source order; an absent source adds 0
-            if (lane == 0 && off >= 0 && off + n < a.cap) {
+            if (lane == 0 && fits && off + n < end) {
                 a.out_cols[off + n] = m;
                 a.out_vals[off + n] = sum / k2f;
             }

@@ -9,22 +9,46 @@ gallery-graph variant (include/mi355_retrieval.h, mi355_kr_*), written with Pyth
     V'(g)    = mean of V over the first k2 of [g, nn(g) ...];   V'(q) = (V(q) + sum of V over the first k2 - 1 of nn(q)) / k2
     s*(q, g) = 1 - ((1 - lam) dJ + lam (1 - s(q, g))),  dJ = 1 - m / (2 - m),  m = sum_c min(V'(q)[c], V'(g)[c])
 
-Sparse rows are dicts {column: value}; ``to_csr`` flattens a list of them (ascending columns) for comparison with the kernels."""
+Sparse rows are dicts {column: value}; ``to_csr`` flattens a list of them (ascending columns) for comparison with the kernels.
+
+Lists given by hand may hold what a search never returns.  The reference skips it where the kernels do (csrc/rerank.hip):
+
+    an id outside [0, G) in a list or in the graph is no member, no candidate and no reciprocal neighbour;
+    a gallery row that lists itself gains nothing from it (it is in its own R already), and in R_h(c) the entry c counts once;
+    a repeated id in a list counts once: its FIRST occurrence decides (for a query row, that occurrence's score against tau);
+    ``weights``: a column outside [0, G) gets the weight 0 and stays out of the row's sum;
+    ``local_qe``: a source outside [0, G) is absent - the sum is still divided by k2 - and a repeated source is added once per
+    occurrence;
+    ``scores``: a slot outside [0, G), not only a negative one, is -inf."""
 from __future__ import annotations
 
 import numpy as np
 
 
+def _valid(j, G):
+    return 0 <= int(j) < G
+
+
 def recip_h(graph, c, h):
     """R_h(c) as a set."""
-    return {int(c)} | {int(j) for j in graph[c][:h] if c in graph[j][:h]}
+    G = len(graph)
+    return {int(c)} | {int(j) for j in graph[c][:h] if _valid(j, G) and c in graph[int(j)][:h]}
 
 
 def base_set(r, nn_row, graph, nv_row=None, tau=None):
     """R(r): gallery row r (nv_row None) or a query with its scores nv_row (compared as given: pass float32 arrays)."""
+    G = len(graph)
     if nv_row is None:
-        return {int(r)} | {int(j) for j in nn_row if r in graph[j]}
-    return {int(j) for t, j in enumerate(nn_row) if nv_row[t] >= tau[j]}
+        return {int(r)} | {int(j) for j in nn_row if _valid(j, G) and r in graph[int(j)]}
+    out, seen = set(), set()
+    for t, j in enumerate(nn_row):
+        j = int(j)
+        if not _valid(j, G) or j in seen:
+            continue
+        seen.add(j)
+        if nv_row[t] >= tau[j]:
+            out.add(j)
+    return out
 
 
 def expanded_set(base, graph, h):
@@ -71,11 +95,12 @@ def weights(rows, gallery, col_sets):
     """V as a list of dicts: rows (R, D) and gallery (G, D) float64 NORMALISED rows, col_sets the R*(r).  A gallery row that is in
     no set is never touched."""
     rows, gallery = np.asarray(rows, np.float64), np.asarray(gallery, np.float64)
+    G = len(gallery)
     out = []
     for r, cs in enumerate(col_sets):
-        e = {int(j): np.exp(-(1.0 - float(rows[r] @ gallery[j]))) for j in cs}
+        e = {int(j): np.exp(-(1.0 - float(rows[r] @ gallery[int(j)]))) for j in cs if _valid(j, G)}
         tot = sum(e[j] for j in sorted(e))
-        out.append({j: e[j] / tot for j in e})
+        out.append({int(j): e[int(j)] / tot if int(j) in e else 0.0 for j in cs})
     return out
 
 
@@ -85,6 +110,8 @@ def local_qe(own, gallery_V, lists, k2):
     for r, v in enumerate(own):
         acc = dict(v)
         for j in lists[r][: k2 - 1]:
+            if not _valid(j, len(gallery_V)):
+                continue
             for c, x in gallery_V[int(j)].items():
                 acc[c] = acc.get(c, 0.0) + x
         out.append({c: x / k2 for c, x in acc.items()})
@@ -92,14 +119,14 @@ def local_qe(own, gallery_V, lists, k2):
 
 
 def scores(vq2, vg2, short_vals, short_idx, lam):
-    """s* (Q, K) float64; pads (index < 0) are -inf."""
+    """s* (Q, K) float64; pads (an index outside [0, G)) are -inf."""
     short_vals = np.asarray(short_vals, np.float64)
     out = np.full(short_vals.shape, -np.inf)
     for q in range(out.shape[0]):
         a = vq2[q]
         for p in range(out.shape[1]):
             g = int(short_idx[q, p])
-            if g < 0:
+            if not _valid(g, len(vg2)):
                 continue
             b = vg2[g]
             m = sum(min(a[c], b[c]) for c in sorted(a.keys() & b.keys()))
