@@ -115,14 +115,6 @@ __global__ __launch_bounds__(256) void k_split_queries(const float* __restrict__
 // [rows][BK + 4] floats (the 4-float pad makes ds_read_b128 of 16 distinct rows bank-conflict free).
 // Per lane a float4 at k = 8t + 4*(lane>>5) feeds four 32x32x2 k-steps; A and B use the same k
 // permutation, which only reorders the (exact) fma chain.
-
-
-
-// FK = 0: write the score slab S.  FK = 1/2/4/8 (fused selection, k <= FK): the score tile never leaves the CU - it is
-// transposed through LDS (the staging buffers are free after the K loop), each of the tile's query rows is scanned by one
-// thread in ascending column order into a sorted FK-list, and k (score, local int32 index) candidates per (query, column
-// tile) go to cand_val / cand_idx [Q][n_tiles][k]; the existing multi-level selection then merges Q x n_tiles x k
-// candidates instead of reading Q x G scores (train/train.py:250-251 semantics, same tie rule).
 template <int MT, int RK_BK, bool VEC, class Epi>
 __device__ __forceinline__ void cos_gemm_f32_tile(const float* __restrict__ Qn, const float* __restrict__ Gal,
                                                   const float* __restrict__ ginv, int Q, i64 G, int D, int x0, int ntx,
@@ -258,37 +250,131 @@ __global__ __launch_bounds__(256) void k_cos_gemm_epi(const float* __restrict__ 
 
 // =====================================================================================
 // The same GEMM on the bf16 matrix pipe (three-way split, six products; see split3 above).  Same block / wave tiling and
-// the same epilogue as k_cos_gemm; BK = 16 (one 32x32x16 k-step per K-tile).  Needs 16-byte aligned gallery rows
-// (D % 4 == 0); other shapes stay on the fp32 loop.
-//   A (queries): pre-split planes in fragment order (k_split_queries), 1 KB per (row block, plane) by LDS-DMA, one
-//     k-step ahead (they come from L2);
-//   B (gallery): fp32 rows by LDS-DMA as well, TWO k-steps ahead (they come from HBM): a piece is 16 rows x 64 B, the
-//     16-byte chunk c of row r lands at position c ^ ((r >> 2) & 3) (the swizzle is applied to the per-lane SOURCE address,
-//     the DMA writes lane-linear), so that the ds_read_b128 of 8 rows hit 8 different bank groups without padding.  Each
-//     wave reads its two 32-row fragments (8 consecutive k per lane) and splits them in registers - 44 VALU instructions
-//     per fragment next to the 12 MFMAs (384 matrix-pipe cycles) that consume it.
-// No load in the loop has a register destination, so the only waits are the ones written here: ONE vmcnt(2) per k-step
-// (the counter retires in order: everything but this iteration's two B pieces - issued last - has landed) and one
-// LDS-only barrier.  (With register-staged B loads hipcc drained vmcnt(0) before every store to LDS.)
-// LDS: 2 x 12 KB (A) + 3 x 8 KB (B) = 48 KB at MT = 2 -> three workgroups per CU; 3 x 6 + 24 = 42 KB at MT = 1.
+// the same epilogues as k_cos_gemm; one 32x32x16 k-step per K-tile.  Both operands arrive by LDS-DMA, the loop is dma_ring
+// (rank_common.h): no load has a register destination, one counted wait and one LDS-only barrier per k-step.  (With
+// register-staged B loads hipcc drained the vector-memory counter before every store to LDS.)
+//   A (queries): pre-split planes in fragment order (k_split_queries), 1 KB per (row block, plane), from L2.
+//   B (gallery): from HBM, two k-steps ahead.  A B operand type says how it arrives and how a wave's 32-row fragment j
+//     becomes its planes (h, m, l):
+//       WAVE_PIECES, STAGE_BYTES   DMA pieces per wave and bytes per ring stage of a k-step
+//       init(...)                  the lane's source and LDS addresses for the tile at gallery row n0
+//       dma(Bs, stage, t, swave)   issues the wave's pieces of k-step t (past the end too: the count in flight stays uniform)
+//       read(Bs, stage, j)         the lane's Frag out of LDS;  planes(Frag) its Planes3
+//       SPLITS                     planes() is VALU work, to be interleaved with the MFMAs
 // =====================================================================================
-template <int MT, class Epi>
-__device__ __forceinline__ void cos_gemm_split_tile(const bf16_t* __restrict__ Qs, const float* __restrict__ Gal,
-                                                    const float* __restrict__ ginv, int Q, i64 G, int D, int x0, int ntx,
-                                                    int n_steps, const float* __restrict__ zeros, int xtiles, int ny,
-                                                    const Epi& epi) {
+// A ring: 2 stages at MT = 2 (one k-step ahead; a third stage would cost the split kernel its third workgroup per CU), 3
+// stages at MT = 1 (two k-steps ahead: the 64-row tiles are the tail launch and the small-Q shapes, few workgroups per CU
+// with nothing else to hide a piece's latency behind)
+template <int MT> constexpr int SPLIT_A_RING = MT == 1 ? 3 : 2;
+template <int MT> constexpr size_t SPLIT_A_BYTES = (size_t)SPLIT_A_RING<MT> * (64 * MT / 32) * 3 * 1024;
+struct Planes3 {
+    bf16x8 h, m, l;
+};
+
+// fp32 rows with 16-byte aligned rows (D % 4 == 0; other shapes stay on the fp32 loop): a piece is 16 rows x 64 B, wave w
+// moves pieces 2w and 2w + 1 (lane -> row 16 * piece + lane / 4, position lane % 4).  The 16-byte chunk c of row r lands at
+// position c ^ ((r >> 2) & 3) (the swizzle is applied to the per-lane SOURCE address, the DMA writes lane-linear), so that
+// the ds_read_b128 of 8 rows hit 8 different bank groups without padding.  Chunks past D or G come from the zero page.  A
+// fragment is 8 consecutive k per lane, split in registers: 44 VALU instructions next to the 12 MFMAs that consume it.
+// LDS: 2 x 12 KB (A) + 3 x 8 KB (B) = 48 KB at MT = 2 -> three workgroups per CU; 3 x 6 + 24 = 42 KB at MT = 1.
+struct F32RowsB {
+    static constexpr int WAVE_PIECES = 2;
+    static constexpr int STAGE_BYTES = RK_BN * 16 * sizeof(float);
+    static constexpr bool SPLITS = true;
+    struct Frag {
+        f32x4 v0, v1;
+    };
+    const float* gal;
+    const float* zeros;
+    int D;
+    const float* row[2];
+    int k[2], off[2][2];
+    bool ok[2];
+    __device__ __forceinline__ void init(i64 n0, i64 G, int, int swave, int lane, int wn) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int r = (swave * 2 + i) * 16 + (lane >> 2);
+            ok[i] = n0 + r < G;
+            row[i] = gal + (ok[i] ? (n0 + r) * D : 0);
+            k[i] = ((lane & 3) ^ ((r >> 2) & 3)) * 4;
+        }
+        // fragment reads: row r = wn * 64 + j * 32 + lane % 32, chunks 2 * (lane >> 5) and + 1 at their swizzled positions
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int r = wn * 64 + j * 32 + (lane & 31), sw = (r >> 2) & 3, c0 = (lane >> 5) * 2;
+            off[j][0] = r * 16 + ((c0 ^ sw) << 2);
+            off[j][1] = r * 16 + (((c0 + 1) ^ sw) << 2);
+        }
+    }
+    __device__ __forceinline__ void dma(char* Bs, int stage, int t, int swave) const {
+        const int k0 = t * 16;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const bool in = ok[i] && k0 + k[i] < D;                    // D % 4 == 0: a chunk is inside or outside
+            glds16(reinterpret_cast<const bf16_t*>(in ? row[i] + k0 + k[i] : zeros),
+                   reinterpret_cast<bf16_t*>(Bs + stage * STAGE_BYTES + (swave * 2 + i) * 1024));
+        }
+    }
+    __device__ __forceinline__ Frag read(const char* Bs, int stage, int j) const {
+        const float* b = reinterpret_cast<const float*>(Bs + stage * STAGE_BYTES);
+        return {*reinterpret_cast<const f32x4*>(b + off[j][0]), *reinterpret_cast<const f32x4*>(b + off[j][1])};
+    }
+    static __device__ __forceinline__ Planes3 planes(const Frag& f) {
+        u32x4 h, m, l;
+        split3(f.v0, f.v1, h, m, l);
+        return {__builtin_bit_cast(bf16x8, h), __builtin_bit_cast(bf16x8, m), __builtin_bit_cast(bf16x8, l)};
+    }
+};
+
+// A PREPARED gallery (mi355_gallery_prepare): the three bf16 planes of its normalised rows in the fragment order of
+// k_split_queries ([row block of 32][k step][h, m, l][64 lanes][8], 6 B per element instead of 4), so B arrives as ready MFMA
+// fragments like A: no split in the loop (round 2's PMC: matrix pipe 57 % busy + VALU 45 % busy, the 88 VALU instructions per
+// fragment split did not co-issue with the MFMAs).  12 pieces per k-step, wave w moves pieces w, w + 4, w + 8; k-steps past
+// the end re-read the last one.  LDS: 2 x 12 KB (A) + 3 x 12 KB (B) = 60 KB at MT = 2 (two workgroups per CU).
+struct PlanesB {
+    static constexpr int WAVE_PIECES = 3;
+    static constexpr int STAGE_BYTES = (RK_BN / 32) * 3 * 1024;
+    static constexpr bool SPLITS = false;
+    typedef Planes3 Frag;
+    const bf16_t* gs;
+    const bf16_t* piece[3];
+    int n_steps, frag0;
+    __device__ __forceinline__ void init(i64 n0, i64, int steps, int swave, int lane, int wn) {
+        n_steps = steps;
+        frag0 = (wn * 2 * 3) * 512 + lane * 8;
+        const bf16_t* src = gs + (size_t)(n0 / 32) * n_steps * 3 * 512 + lane * 8;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const int p = swave + 4 * i;
+            piece[i] = src + ((size_t)((p / 3) * n_steps) * 3 + p % 3) * 512;
+        }
+    }
+    __device__ __forceinline__ void dma(char* Bs, int stage, int t, int swave) const {
+        const int tt = t < n_steps ? t : n_steps - 1;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+            glds16(piece[i] + (size_t)tt * 3 * 512, reinterpret_cast<bf16_t*>(Bs + stage * STAGE_BYTES + (swave + 4 * i) * 1024));
+    }
+    __device__ __forceinline__ Frag read(const char* Bs, int stage, int j) const {
+        const bf16_t* b = reinterpret_cast<const bf16_t*>(Bs + stage * STAGE_BYTES) + frag0 + j * 3 * 512;
+        return {*reinterpret_cast<const bf16x8*>(b), *reinterpret_cast<const bf16x8*>(b + 512),
+                *reinterpret_cast<const bf16x8*>(b + 1024)};
+    }
+    static __device__ __forceinline__ Planes3 planes(const Frag& f) { return f; }
+};
+
+// One tile of either: scores are bit-identical between the two B operands, since the planes are the same values (split3 of
+// the same fp32 rows) and the six products below are the only ones there are.
+template <int MT, class B, class Epi>
+__device__ __forceinline__ void cos_gemm_split_tile(const bf16_t* __restrict__ Qs, B bop, const float* __restrict__ ginv, int Q,
+                                                    i64 G, int x0, int ntx, int n_steps, int xtiles, int ny, const Epi& epi) {
     constexpr int BM = 64 * MT;
-    constexpr int BK = 16;
-    constexpr int A_STAGE = (BM / 32) * 3 * 512;      // bf16 elements per stage
     constexpr int A_PIECES = (BM / 32) * 3;           // 1 KB pieces per stage
-    constexpr int B_STAGE = RK_BN * BK;               // floats per stage (8 KB)
+    constexpr int A_STAGE = A_PIECES * 512;           // bf16 elements per stage
+    constexpr int A_RING = SPLIT_A_RING<MT>;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     bf16_t* As = reinterpret_cast<bf16_t*>(smem);                       // [A_RING][BM/32][3][512]
-    // A ring: 2 stages at MT = 2 (the pieces come from L2 one k-step ahead; a third stage would cost the third workgroup per
-    // CU), 3 stages at MT = 1 (two k-steps ahead: the 64-row tiles are the tail launch and the small-Q shapes, few
-    // workgroups per CU with nothing else to hide a piece's latency behind)
-    constexpr int A_RING = MT == 1 ? 3 : 2;
-    float* Bs = smem + (A_RING * A_STAGE * 2) / 4;                      // [3][128][16], chunks swizzled
+    char* Bs = reinterpret_cast<char*>(As + A_RING * A_STAGE);          // [3][B::STAGE_BYTES]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
@@ -300,26 +386,8 @@ __device__ __forceinline__ void cos_gemm_split_tile(const bf16_t* __restrict__ Q
     // drain vmcnt)
     const int swave = __builtin_amdgcn_readfirstlane(wave);
 
-    // B: wave w moves pieces 2w and 2w + 1 (rows 32w .. 32w + 31); lane -> row 16 * piece + lane / 4, position lane % 4
-    const float* b_row[2];
-    int b_k[2];
-    bool b_ok[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int r = (swave * 2 + i) * 16 + (lane >> 2);
-        const int c = (lane & 3) ^ ((r >> 2) & 3);
-        b_ok[i] = n0 + r < G;
-        b_row[i] = Gal + (b_ok[i] ? (n0 + r) * D : 0);
-        b_k[i] = c * 4;
-    }
-    auto dma_b = [&](int stage, int k0) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const bool ok = b_ok[i] && k0 + b_k[i] < D;                // D % 4 == 0: a chunk is inside or outside
-            glds16(reinterpret_cast<const bf16_t*>(ok ? b_row[i] + k0 + b_k[i] : zeros),
-                   reinterpret_cast<bf16_t*>(Bs + stage * B_STAGE + (swave * 2 + i) * 256));
-        }
-    };
+    bop.init(n0, G, n_steps, swave, lane, wn);
+    auto dma_b = [&](int stage, int t) { bop.dma(Bs, stage, t, swave); };
     // A: piece (row block rbl, plane p) of k-step t sits at Qs + (((m0/32 + rbl) * n_steps + t) * 3 + p) * 512.
     // 12 (MT = 2) or 6 (MT = 1) pieces per stage: wave w moves pieces w, w + 4, w + 8 / pieces w and (w < 2) w + 4.
     const bf16_t* a_src = Qs + (size_t)(m0 / 32) * n_steps * 3 * 512 + lane * 8;
@@ -346,90 +414,44 @@ __device__ __forceinline__ void cos_gemm_split_tile(const bf16_t* __restrict__ Q
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 
-    const int lr = lane & 31;
-    // B fragment reads: row r = wn * 64 + j * 32 + lr, chunks 2 * (lane >> 5) and + 1 at their swizzled positions
-    int b_off[2][2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int r = wn * 64 + j * 32 + lr, sw = (r >> 2) & 3, c0 = (lane >> 5) * 2;
-        b_off[j][0] = r * BK + ((c0 ^ sw) << 2);
-        b_off[j][1] = r * BK + (((c0 + 1) ^ sw) << 2);
-    }
     auto compute = [&](int abuf, int bstage) {
         const bf16_t* a = As + abuf * A_STAGE + (wm * MT * 3) * 512 + lane * 8;
-        const float* b = Bs + bstage * B_STAGE;
         bf16x8 af[MT][3];
-        u32x4 bh[2], bm[2], bl[2];
-        f32x4 v0[2], v1[2];
+        typename B::Frag bf[2];
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            v0[j] = *reinterpret_cast<const f32x4*>(b + b_off[j][0]);
-            v1[j] = *reinterpret_cast<const f32x4*>(b + b_off[j][1]);
-        }
+        for (int j = 0; j < 2; ++j) bf[j] = bop.read(Bs, bstage, j);
 #pragma unroll
         for (int i = 0; i < MT; ++i)
 #pragma unroll
             for (int p = 0; p < 3; ++p) af[i][p] = *reinterpret_cast<const bf16x8*>(a + (i * 3 + p) * 512);
-        split3(v0[0], v1[0], bh[0], bm[0], bl[0]);
         // Per fragment j: six products for each of the MT row blocks, smallest terms first (the order is the same for every
-        // (query, gallery row) pair wherever its tile lies).  The split of fragment 1 is issued in the gaps of fragment 0's
-        // MFMAs (an MFMA holds the vector issue for 8 of its 32 cycles): sched_group_barrier pins "1 MFMA, 4 VALU" groups.
-        auto products = [&](int j) {
-            const bf16x8 gh = *reinterpret_cast<const bf16x8*>(&bh[j]);
-            const bf16x8 gm = *reinterpret_cast<const bf16x8*>(&bm[j]);
-            const bf16x8 gl = *reinterpret_cast<const bf16x8*>(&bl[j]);
+        // (query, gallery row) pair wherever its tile lies and however B arrived).
+        auto products = [&](int j, const Planes3& g) {
 #pragma unroll
             for (int i = 0; i < MT; ++i) {
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][2], gh, acc[i][j], 0, 0, 0);   // l * h'
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], gl, acc[i][j], 0, 0, 0);   // h * l'
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][1], gm, acc[i][j], 0, 0, 0);   // m * m'
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][1], gh, acc[i][j], 0, 0, 0);   // m * h'
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], gm, acc[i][j], 0, 0, 0);   // h * m'
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], gh, acc[i][j], 0, 0, 0);   // h * h'
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][2], g.h, acc[i][j], 0, 0, 0);   // l * h'
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], g.l, acc[i][j], 0, 0, 0);   // h * l'
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][1], g.m, acc[i][j], 0, 0, 0);   // m * m'
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][1], g.h, acc[i][j], 0, 0, 0);   // m * h'
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], g.m, acc[i][j], 0, 0, 0);   // h * m'
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], g.h, acc[i][j], 0, 0, 0);   // h * h'
             }
         };
-        split3(v0[1], v1[1], bh[1], bm[1], bl[1]);
-        products(0);
+        const Planes3 g0 = B::planes(bf[0]), g1 = B::planes(bf[1]);
+        products(0, g0);
+        // The split of fragment 1 is issued in the gaps of fragment 0's MFMAs (an MFMA holds the vector issue for 8 of its 32
+        // cycles): sched_group_barrier pins "1 MFMA, 4 VALU" groups.
+        if constexpr (B::SPLITS) {
 #pragma unroll
-        for (int g = 0; g < 6 * MT; ++g) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // one MFMA
-            __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);   // four VALU (of fragment 1's split)
+            for (int g = 0; g < 6 * MT; ++g) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // one MFMA
+                __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);   // four VALU (of fragment 1's split)
+            }
         }
-        products(1);
+        products(1, g1);
     };
 
-    dma_a(0, 0);
-    if (A_RING == 3 && n_steps > 1) dma_a(1, 1);
-    dma_b(0, 0);
-    dma_b(1, BK);                      // (zeros past D)
-    __syncthreads();                   // drains vmcnt: everything has landed
-
-    int bs_cur = 0, bs_far = 2;        // B stage of k-step t / of k-step t + 2 (and, at A_RING == 3, the A stages)
-    for (int t = 0; t < n_steps; ++t) {
-        if constexpr (A_RING == 2) {
-            if (t + 1 < n_steps) dma_a((t & 1) ^ 1, t + 1);  // everybody left these buffers at the previous barrier
-        } else {
-            if (t + 2 < n_steps) dma_a(bs_far, t + 2);
-        }
-        __builtin_amdgcn_sched_barrier(0);                   // (the counts below need the A pieces issued BEFORE the B pieces)
-        dma_b(bs_far, (t + 2) * BK);
-        __builtin_amdgcn_sched_barrier(0);
-        compute(A_RING == 2 ? (t & 1) : bs_cur, bs_cur);
-        if constexpr (A_RING == 2) {
-            asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); // A(t+1) and B(t+1) have landed; B(t+2) stays in flight
-        } else {
-            // A(t+2) (two pieces from waves 0 and 1, one from waves 2 and 3; none at the end) and B(t+2) stay in flight
-            if (t + 2 >= n_steps) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-            else if (swave < A_PIECES % 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        bs_cur = bs_cur == 2 ? 0 : bs_cur + 1;
-        bs_far = bs_far == 2 ? 0 : bs_far + 1;
-    }
-    __syncthreads();                   // the last look-ahead pieces (zeros) have landed before the epilogue reuses the LDS
+    dma_ring<A_RING, A_PIECES, B::WAVE_PIECES>(n_steps, swave, dma_a, dma_b, compute);
     epi.tile(acc, smem, ginv, TileCtx{Q, G, ntx, n0, m0});
 }
 template <int MT, int FK>
@@ -437,146 +459,21 @@ __global__ __launch_bounds__(256, 3) void k_cos_gemm_split(const bf16_t* __restr
                                                            const float* __restrict__ ginv, int Q, i64 G, int D, int x0, int ntx,
                                                            int n_steps, const float* __restrict__ zeros, int xtiles, int ny,
                                                            PlainEpi<FK> epi) {
-    cos_gemm_split_tile<MT>(Qs, Gal, ginv, Q, G, D, x0, ntx, n_steps, zeros, xtiles, ny, epi);
+    cos_gemm_split_tile<MT>(Qs, F32RowsB{Gal, zeros, D}, ginv, Q, G, x0, ntx, n_steps, xtiles, ny, epi);
 }
 template <int MT, class Epi>
 __global__ __launch_bounds__(256, 3) void k_cos_gemm_split_epi(const bf16_t* __restrict__ Qs, const float* __restrict__ Gal,
                                                                const float* __restrict__ ginv, int Q, i64 G, int D, int x0,
                                                                int ntx, int n_steps, const float* __restrict__ zeros, int xtiles,
                                                                int ny, Epi epi) {
-    cos_gemm_split_tile<MT>(Qs, Gal, ginv, Q, G, D, x0, ntx, n_steps, zeros, xtiles, ny, epi);
+    cos_gemm_split_tile<MT>(Qs, F32RowsB{Gal, zeros, D}, ginv, Q, G, x0, ntx, n_steps, xtiles, ny, epi);
 }
 
-// =====================================================================================
-// The same GEMM against a PREPARED gallery (mi355_gallery_prepare): the resident gallery holds, beside nothing else, the three
-// bf16 planes of its normalised rows in the fragment order of k_split_queries ([row block of 32][k step][h, m, l][64 lanes][8],
-// 6 B per element instead of 4).  Both operands then arrive by LDS-DMA as ready MFMA fragments: no split in the loop (round 2's
-// PMC: matrix pipe 57 % busy + VALU 45 % busy, the 88 VALU instructions per fragment split did not co-issue with the MFMAs).
-// Per k-step a workgroup moves 12 A pieces (one k-step ahead, from L2) and 12 B pieces (two ahead, from HBM), three + three per
-// wave; ONE counted vmcnt (the three youngest = this iteration's B pieces stay in flight) + one LDS-only barrier per k-step.
-// Scores are bit-identical to k_cos_gemm_split: the planes are the same values (split3 of the same fp32 rows) and the six
-// products are accumulated in the same order.  LDS: 2 x 12 KB (A) + 3 x 12 KB (B) = 60 KB at MT = 2 (two workgroups per CU).
-// =====================================================================================
 template <int MT, int FK>
 __global__ __launch_bounds__(256, 2) void k_cos_gemm_pre(const bf16_t* __restrict__ Qs, const bf16_t* __restrict__ Gs, int Q,
                                                          i64 G, int x0, int ntx, int n_steps, int xtiles, int ny,
                                                          SelectEpi<FK, false> epi) {
-    constexpr int BM = 64 * MT;
-    constexpr int A_PIECES = (BM / 32) * 3;           // 1 KB pieces per stage
-    constexpr int A_STAGE = A_PIECES * 512;           // bf16 elements per stage
-    constexpr int B_PIECES = (RK_BN / 32) * 3;        // 12
-    constexpr int B_STAGE = B_PIECES * 512;
-    constexpr int A_RING = MT == 1 ? 3 : 2;           // (MT = 1: the tail launch / small-Q shapes, nothing else hides a piece's latency)
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    bf16_t* As = reinterpret_cast<bf16_t*>(smem);                       // [A_RING][BM/32][3][512]
-    bf16_t* Bs = As + A_RING * A_STAGE;                                 // [3][4][3][512]
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    int bx, by;
-    rank_tile_of((int)blockIdx.x, xtiles, ny, bx, by);
-    const i64 n0 = (i64)(bx + x0) * RK_BN;
-    const int m0 = by * BM;
-    const int swave = __builtin_amdgcn_readfirstlane(wave);
-
-    // piece (row block rbl, plane p) of k-step t sits at base + (((row0/32 + rbl) * n_steps + t) * 3 + p) * 512; wave w moves
-    // pieces w, w + 4, w + 8 of a 12-piece stage (MT = 1, A: pieces w and (w < 2) w + 4)
-    const bf16_t* a_src = Qs + (size_t)(m0 / 32) * n_steps * 3 * 512 + lane * 8;
-    const bf16_t* b_src = Gs + (size_t)(n0 / 32) * n_steps * 3 * 512 + lane * 8;
-    const bf16_t* a_piece[(A_PIECES + 3) / 4];
-    const bf16_t* b_piece[3];
-#pragma unroll
-    for (int i = 0; i < (A_PIECES + 3) / 4; ++i) {
-        const int piece = (swave + 4 * i) % A_PIECES;
-        a_piece[i] = a_src + ((size_t)((piece / 3) * n_steps) * 3 + piece % 3) * 512;
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const int piece = swave + 4 * i;
-        b_piece[i] = b_src + ((size_t)((piece / 3) * n_steps) * 3 + piece % 3) * 512;
-    }
-    auto dma_a = [&](int buf, int t) {
-#pragma unroll
-        for (int i = 0; i < (A_PIECES + 3) / 4; ++i) {
-            const int piece = swave + 4 * i;
-            if (A_PIECES % 4 == 0 || i < A_PIECES / 4 || swave < A_PIECES % 4)
-                glds16(a_piece[i] + (size_t)t * 3 * 512, As + buf * A_STAGE + piece * 512);
-        }
-    };
-    // (k-steps past the end re-read the last one: the data is never used, the count of pieces in flight stays uniform)
-    auto dma_b = [&](int stage, int t) {
-        const int tt = t < n_steps ? t : n_steps - 1;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) glds16(b_piece[i] + (size_t)tt * 3 * 512, Bs + stage * B_STAGE + (swave + 4 * i) * 512);
-    };
-
-    f32x16 acc[MT][2];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-    auto compute = [&](int abuf, int bstage) {
-        const bf16_t* a = As + abuf * A_STAGE + (wm * MT * 3) * 512 + lane * 8;
-        const bf16_t* b = Bs + bstage * B_STAGE + (wn * 2 * 3) * 512 + lane * 8;
-        bf16x8 af[MT][3], bfr[2][3];
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int p = 0; p < 3; ++p) bfr[j][p] = *reinterpret_cast<const bf16x8*>(b + (j * 3 + p) * 512);
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int p = 0; p < 3; ++p) af[i][p] = *reinterpret_cast<const bf16x8*>(a + (i * 3 + p) * 512);
-        // six products per (row block, gallery fragment), smallest terms first - the order of k_cos_gemm_split
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int i = 0; i < MT; ++i) {
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][2], bfr[j][0], acc[i][j], 0, 0, 0);   // l * h'
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], bfr[j][2], acc[i][j], 0, 0, 0);   // h * l'
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][1], bfr[j][1], acc[i][j], 0, 0, 0);   // m * m'
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][1], bfr[j][0], acc[i][j], 0, 0, 0);   // m * h'
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], bfr[j][1], acc[i][j], 0, 0, 0);   // h * m'
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], bfr[j][0], acc[i][j], 0, 0, 0);   // h * h'
-            }
-    };
-
-    dma_a(0, 0);
-    if (A_RING == 3 && n_steps > 1) dma_a(1, 1);
-    dma_b(0, 0);
-    dma_b(1, 1);
-    __syncthreads();                   // drains vmcnt: everything has landed
-
-    int bs_cur = 0, bs_far = 2;        // B stage of k-step t / of k-step t + 2 (and, at A_RING == 3, the A stages)
-    for (int t = 0; t < n_steps; ++t) {
-        if constexpr (A_RING == 2) {
-            if (t + 1 < n_steps) dma_a((t & 1) ^ 1, t + 1);  // everybody left these buffers at the previous barrier
-        } else {
-            if (t + 2 < n_steps) dma_a(bs_far, t + 2);
-        }
-        __builtin_amdgcn_sched_barrier(0);                   // (the counts below need the A pieces issued BEFORE the B pieces)
-        dma_b(bs_far, t + 2);
-        __builtin_amdgcn_sched_barrier(0);
-        compute(A_RING == 2 ? (t & 1) : bs_cur, bs_cur);
-        if constexpr (A_RING == 2) {
-            asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); // A(t+1) and B(t+1) have landed; the three B(t+2) pieces stay in flight
-        } else {
-            // A(t+2) (two pieces from waves 0 and 1, one from waves 2 and 3; none at the end) and B(t+2) stay in flight
-            if (t + 2 >= n_steps) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-            else if (swave < A_PIECES % 4) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        bs_cur = bs_cur == 2 ? 0 : bs_cur + 1;
-        bs_far = bs_far == 2 ? 0 : bs_far + 1;
-    }
-    __syncthreads();                   // the last look-ahead pieces have landed before the epilogue reuses the LDS
-    epi.tile(acc, smem, nullptr, TileCtx{Q, G, ntx, n0, m0});
+    cos_gemm_split_tile<MT>(Qs, PlanesB{Gs}, nullptr, Q, G, x0, ntx, n_steps, xtiles, ny, epi);
 }
 
 // =====================================================================================
@@ -1088,9 +985,7 @@ struct F32Gemm {
 
 // Split-bf16 loop (qry: the split planes of the queries, split_rows; gal: fp32 rows with D % 4 == 0)
 struct SplitGemm {
-    template <int MT> static constexpr size_t stage_bytes() {   // A ring of 2 (3 at MT = 1), B ring of 3
-        return (size_t)(MT == 1 ? 3 : 2) * (64 * MT / 32) * 3 * 1024 + (size_t)3 * RK_BN * 16 * sizeof(float);
-    }
+    template <int MT> static constexpr size_t stage_bytes() { return SPLIT_A_BYTES<MT> + 3 * F32RowsB::STAGE_BYTES; }
     template <int MT, class Epi> static constexpr auto kernel() {
         if constexpr (plain_fk<Epi> >= 0) return &k_cos_gemm_split<MT, plain_fk<Epi>>;
         else return &k_cos_gemm_split_epi<MT, Epi>;
@@ -1107,9 +1002,7 @@ struct SplitGemm {
 
 // Prepared gallery (qry: the split planes of the queries; gal: the gallery's planes): the unfiltered fused selection only
 struct PreparedGemm {
-    template <int MT> static constexpr size_t stage_bytes() {   // A ring of 2 (3 at MT = 1), B ring of 3
-        return (size_t)(MT == 1 ? 3 : 2) * (64 * MT / 32) * 3 * 1024 + (size_t)3 * (RK_BN / 32) * 3 * 1024;
-    }
+    template <int MT> static constexpr size_t stage_bytes() { return SPLIT_A_BYTES<MT> + 3 * PlanesB::STAGE_BYTES; }
     template <int MT, class Epi> static constexpr auto kernel() {
         static_assert(plain_fk<Epi> > 0, "the prepared gallery has fused unfiltered kernels only");
         return &k_cos_gemm_pre<MT, plain_fk<Epi>>;

@@ -77,6 +77,58 @@ __device__ __forceinline__ void glds16(const bf16_t* gsrc, bf16_t* lds_dst) {
                                      (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
 }
 
+// The k loop of every LDS-DMA cosine GEMM (split bf16, prepared planes, fp16 and int8 rows).  dma_a(stage, t) and
+// dma_b(stage, t) issue this wave's pieces of k-step t into a ring stage, compute(a stage, b stage) runs a k-step's MFMAs
+// out of LDS.  The B ring of 3 runs two k-steps ahead (HBM); the A ring runs one ahead at A_RING = 2 (two buffers, t & 1)
+// and two ahead at A_RING = 3, where it shares the B ring's stage numbers.  Every wave issues B_WAVE B pieces per k-step
+// (dma_b past the end still issues them, from a harmless source) and A_PIECES / 4 A pieces, plus one if swave <
+// A_PIECES % 4.
+// No load has a register destination, so the compiler places no vmcnt wait of its own: the one written here is the loop's
+// only one.  vmcnt retires in issue order and "vmcnt(N)" waits until at most N of this wave's loads are outstanding, so N
+// is the number of pieces issued LAST that may stay in flight.  Step t needs A(t + 1) and B(t + 1) landed at its barrier:
+//   A_RING = 2: A(t + 1) is issued in this iteration.  It must come BEFORE B(t + 2) (the two sched_barriers pin that), then
+//               N = B_WAVE leaves exactly B(t + 2) in flight and covers A(t + 1) and the older B(t + 1).
+//   A_RING = 3: A(t + 2), B(t + 2) are this iteration's; N = B_WAVE + this wave's A pieces leaves both in flight and covers
+//               the older A(t + 1), B(t + 1).  With no A(t + 2) left to issue (t + 2 >= n_steps) N = B_WAVE.
+// Were the B pieces issued first, N would have to drop to 0 to cover the A pieces and the look-ahead would be lost.
+// After lgkmcnt(0) (this wave's LDS reads of step t are done) the barrier publishes step t + 1 and frees step t's stages
+// for the next iteration's DMA.  The closing __syncthreads() drains the last look-ahead pieces before smem is reused.
+template <int N>
+__device__ __forceinline__ void wait_vmcnt() {
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+template <int A_RING, int A_PIECES, int B_WAVE, class DmaA, class DmaB, class Compute>
+__device__ __forceinline__ void dma_ring(int n_steps, int swave, const DmaA& dma_a, const DmaB& dma_b, const Compute& compute) {
+    static_assert(A_RING == 2 || A_RING == 3, "the A ring is one or two k-steps ahead");
+    dma_a(0, 0);
+    if (A_RING == 3 && n_steps > 1) dma_a(1, 1);
+    dma_b(0, 0);
+    dma_b(1, 1);
+    __syncthreads();                   // drains vmcnt: everything has landed
+
+    int bs_cur = 0, bs_far = 2;        // ring stage of k-step t / of k-step t + 2
+    for (int t = 0; t < n_steps; ++t) {
+        if constexpr (A_RING == 2) {
+            if (t + 1 < n_steps) dma_a((t & 1) ^ 1, t + 1);  // everybody left this buffer at the previous barrier
+        } else {
+            if (t + 2 < n_steps) dma_a(bs_far, t + 2);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        dma_b(bs_far, t + 2);
+        __builtin_amdgcn_sched_barrier(0);
+        compute(A_RING == 2 ? (t & 1) : bs_cur, bs_cur);
+        if (A_RING == 2 || t + 2 >= n_steps) wait_vmcnt<B_WAVE>();
+        else if (swave < A_PIECES % 4) wait_vmcnt<B_WAVE + A_PIECES / 4 + 1>();
+        else wait_vmcnt<B_WAVE + A_PIECES / 4>();
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        bs_cur = bs_cur == 2 ? 0 : bs_cur + 1;
+        bs_far = bs_far == 2 ? 0 : bs_far + 1;
+    }
+    __syncthreads();
+}
+
 // Launch order of the GEMM tiles (speed only, every result is the same for any order): the grid is one-dimensional and the
 // query blocks of ONE gallery tile get the linear ids L, L + 8, L + 16, ...  The dispatcher deals workgroups round-robin
 // over the 8 XCDs, so those workgroups share an L2 and start in the same round: the gallery tile comes from HBM once and

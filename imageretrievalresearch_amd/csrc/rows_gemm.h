@@ -16,8 +16,8 @@ constexpr int ROWS_KSTEP = 128;               // bytes of a stored row per k-ste
 //     rows; the 16-byte chunk c of row r lands at position c ^ ((r >> 1) & 7) (applied to the per-lane SOURCE address, the
 //     DMA writes lane-linear): row r sits in half (r & 1) of a 256-byte bank row, so the ds_read_b128 of any 16 distinct
 //     rows of a lane group hit 16 distinct 16-byte slots.  Rows past G re-read row G - 1 (the epilogue drops them).
-// No load in the loop has a register destination: ONE counted vmcnt wait per k-step (this iteration's four B pieces, issued
-// last, stay in flight) and one LDS-only barrier.  Per wave and k-step: 8 * MT + 8 ds_read_b128 and 16 * MT MFMAs.
+// The loop is dma_ring (rank_common.h) with an A ring of 2 and four B pieces per wave: one counted wait and one LDS-only
+// barrier per k-step.  Per wave and k-step: 8 * MT + 8 ds_read_b128 and 16 * MT MFMAs.
 // LDS: 2 x 32 KB (A) + 3 x 16 KB (B) = 112 KB at MT = 2, 2 x 16 + 48 = 80 KB at MT = 1 (two workgroups per CU).
 // A Kind (an object: it may carry pointers) supplies only what the element type changes:
 //   Frag, Acc                  a lane's 16 bytes of A or B as the MFMA takes them; its 32x32 accumulator
@@ -119,26 +119,7 @@ __device__ __forceinline__ void rows_gemm_tile(const char* __restrict__ Qs, cons
         }
     };
 
-    dma_a(0, 0);
-    dma_b(0, 0);
-    dma_b(1, 1);
-    __syncthreads();                   // drains vmcnt: everything has landed
-
-    int bs_cur = 0, bs_far = 2;        // B stage of k-step t / of k-step t + 2
-    for (int t = 0; t < n_steps; ++t) {
-        if (t + 1 < n_steps) dma_a((t & 1) ^ 1, t + 1);   // everybody left this buffer at the previous barrier
-        __builtin_amdgcn_sched_barrier(0);                // (the count below needs the A pieces issued BEFORE the B pieces)
-        dma_b(bs_far, t + 2);
-        __builtin_amdgcn_sched_barrier(0);
-        compute(t & 1, bs_cur);
-        asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); // A(t+1) and B(t+1) have landed; the four B(t+2) pieces stay in flight
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        bs_cur = bs_cur == 2 ? 0 : bs_cur + 1;
-        bs_far = bs_far == 2 ? 0 : bs_far + 1;
-    }
-    __syncthreads();                   // the last look-ahead pieces have landed before the epilogue reuses the LDS
+    dma_ring<2, A_PIECES, 4>(n_steps, swave, dma_a, dma_b, compute);
     f32x16 acc[MT][2];
 #pragma unroll
     for (int i = 0; i < MT; ++i) kind.tail(acc_hi[i], acc_lo[i], acc[i], m0 + wm * MT * 32 + i * 32, lane);

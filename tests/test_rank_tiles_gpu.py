@@ -47,6 +47,18 @@ def _epilogues(fam):
 MATRIX = [(fam, c, e) for fam in FAMILIES for c in ref.CASES for e in _epilogues(fam)]
 BLOCKS = [(fam, c, e) for fam in ("split48", "exact70", "f16-70") for c in ref.BLOCK_CASES for e in ("ranks", "nearest")]
 
+# The DMA ring of the split and the prepared loop (dma_ring, csrc/rank_common.h) at every number of 16-wide k-steps the D = 48
+# of the matrix (3 steps) leaves out: D = 16, 20, 32, 64, 80 are 1, 2 (zeros past D inside the second), 2, 4 and 5 steps.  At 2 and
+# 4 steps the A ring of 3 of the 64-query kernels takes its extra prologue piece and then issues nothing in the loop, at 4 and 5
+# the B ring of 3 wraps.  Outside MATRIX: two cases and a few epilogues each, under the forced cut (both tile heights run).
+STEP_D = (16, 20, 32, 64, 80)
+STEP_EPILOGUES = {"split": ("f32", SPLIT, ["slab", "topk3", "filt2", "range"]), "prepared": ("prepared", PREP, ["topk3", "topk8"])}
+STEPS = []
+for _D in STEP_D:
+    for _name, (_kind, _path, _epis) in STEP_EPILOGUES.items():
+        FAMILIES["%s%d" % (_name, _D)], PATHS["%s%d" % (_name, _D)] = (_kind, _D, False, False), _path
+        STEPS += [("%s%d" % (_name, _D), c, e) for c in (ref.CASES[0], ref.CASES[2]) for e in _epis]
+
 
 @pytest.fixture(autouse=True)
 def _restore_the_override():
@@ -268,7 +280,7 @@ def _check_forced(monkeypatch, fam, case, epi, qblock=0):
 def test_the_lattice_premise():
     """l2_normalize_rows of the +-1 rows is the +-0.25 rows bit for bit (norm 4, 1 / 4 and x / 4 exact), and the fp16 gallery of
     either is the same fp16 rows: the raw and the unit variant of a case are the same rows to every kernel."""
-    for D in (48, 70, 100):
+    for D in (48, 70, 100) + STEP_D:
         d = ref.case_data(*ref.CASES[0], D)
         for which in "qg":
             raw, unit = d.rows(which, True), d.rows(which, False)
@@ -287,7 +299,12 @@ def test_forced_split(fam, case, epi, monkeypatch):
     _check_forced(monkeypatch, fam, case, epi)
 
 
-@pytest.mark.parametrize("fam,case,epi", BLOCKS, ids=lambda v: v if isinstance(v, str) else "s%d-q%d-g%d-b%d" % v)
+@pytest.mark.parametrize("fam,case,epi", STEPS, ids=lambda v: v if isinstance(v, str) else "s%d-q%d-g%d" % v)
+def test_forced_split_at_every_k_step_count(fam, case, epi, monkeypatch):
+    _check_forced(monkeypatch, fam, case, epi)
+
+
+@pytest.mark.parametrize("fam,case,epi", BLOCKS,ids=lambda v: v if isinstance(v, str) else "s%d-q%d-g%d-b%d" % v)
 def test_forced_split_over_several_query_blocks(fam, case, epi, monkeypatch):
     _check_forced(monkeypatch, fam, case[:3], epi, case[3])
 
