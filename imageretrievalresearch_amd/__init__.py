@@ -43,6 +43,9 @@ def __getattr__(name):  # lazy: models/sharded import torch.nn / torch.distribut
     if name == "PQGallery":
         from .pq import PQGallery
         return PQGallery
+    if name == "BinaryGallery":
+        from .binary import BinaryGallery
+        return BinaryGallery
     if name == "IVFPQIndex":
         from .ivfpq import IVFPQIndex
         return IVFPQIndex

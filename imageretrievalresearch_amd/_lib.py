@@ -192,6 +192,12 @@ PROTOTYPES = {
     "mi355_rescore_candidates_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "mi355_rescore_candidates": (C.c_int, [vp, C.c_int64, C.c_int, C.c_float, vp, C.c_int, C.c_int64, C.c_int64, vp, C.c_int64,
                                            C.c_int64, vp, vp, C.c_size_t, vp]),
+    "mi355_binary_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
+    "mi355_binary_encode": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, C.c_float, vp, vp, C.c_size_t, vp]),
+    "mi355_binary_search_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int, C.c_int]),
+    "mi355_binary_distances": (C.c_int, [vp, C.c_int64, C.c_int, C.c_float, vp, vp, C.c_int64, vp, vp, C.c_size_t, vp]),
+    "mi355_binary_search": (C.c_int, [vp, C.c_int64, C.c_int, C.c_float, vp, vp, C.c_int64, C.c_int, C.c_int64,
+                                      C.POINTER(RankFilter), vp, vp, vp, C.c_size_t, vp]),
     "mi355_ivfpq_search_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int]),
     "mi355_ivfpq_search": (C.c_int, [vp, C.c_int64, C.c_int, C.c_float, vp, C.c_int, vp, C.c_int64, vp, vp, C.c_int64, vp, C.c_int,
                                      C.c_int64, C.c_int, C.c_int64, C.POINTER(RankFilter), vp, vp, vp, C.c_size_t, vp]),

@@ -650,10 +650,10 @@ _MAX_K = 1024                       # the largest k of any search, and the longe
 
 
 class _RowStore:
-    """What ``Gallery``, ``Int8Gallery`` (quantized.py) and ``PQGallery`` (pq.py) share: ``rows`` labelled rows of ``dim``
-    columns on ``device``, resident in the buffers a class names in ``_BUFFERS`` (one row each per gallery row, all of one
-    capacity), which only grow.  A class says how a block of rows is written (``_write``); growth, labels, recall and the rules
-    of a shortlist that ``refine=`` rescores are here."""
+    """What ``Gallery``, ``Int8Gallery`` (quantized.py), ``PQGallery`` (pq.py) and ``BinaryGallery`` (binary.py) share: ``rows``
+    labelled rows of ``dim`` columns on ``device``, resident in the buffers a class names in ``_BUFFERS`` (one row each per
+    gallery row, all of one capacity), which only grow.  A class says how a block of rows is written (``_write``); growth,
+    labels, recall and the rules of a shortlist that ``refine=`` rescores are here."""
 
     _BUFFERS: tuple = ()
 

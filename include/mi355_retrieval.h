@@ -138,6 +138,7 @@ enum {
     MI355_RANK_PATH_I8_GEMM = 7,        /* k_cos_gemm_i8 */
     MI355_RANK_PATH_I8_GEMV = 8,        /* k_cos_gemv_i8: Q <= 4 */
     MI355_RANK_PATH_PQ = 9,             /* k_pq_scan / k_pq_scores: the table scan over product-quantised rows (mi355_pq_search) */
+    MI355_RANK_PATH_BINARY = 10,        /* k_bin_scan: the popcount scan over sign-bit rows (mi355_binary_search) */
     MI355_RANK_PATH_FUSED = 0x100,
     MI355_RANK_PATH_BITONIC = 0x200
 };
@@ -738,6 +739,50 @@ int mi355_ivfpq_residual_search(const float* queries, int64_t Q, int dim, float 
                                 const int64_t* probes, int nprobe, int64_t cap, int k, int64_t idx_offset,
                                 const mi355_rank_filter* filter, const float* centroids, float* out_val, int64_t* out_idx,
                                 void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------ binary (sign-bit) resident gallery
+ * A row is dim bits: bit j says whether element j of the normalised row reaches a trained centre.  At dim = 1536 that is 192
+ * bytes, twice the PQ row at M = 96 and an eighth of the int8 row.  The score of a pair is a Hamming distance - integer
+ * arithmetic and one fp32 division - so everything below is bit for bit, with no tolerance anywhere.  The format is a shortlist
+ * generator for a search that rescores (mi355_rescore_candidates): its own order is coarse.
+ * Parameters: 1 <= dim <= 65536.  W = ceil(dim / 32) words; a row is stored as ld = W rounded up to a multiple of 4 uint32
+ * words (a multiple of 16 bytes): codes [G][ld], row-major and appendable (encoding n rows to codes + r * ld writes rows
+ * r .. r+n-1); the base is 16-byte aligned.  mi355_binary_bytes(R, dim) = R * ld * 4 (0 for a shape the entries reject).
+ * center: device fp32 [dim], or NULL for zeros.  Embeddings that are pooled activations are positive in nearly every element,
+ * so their raw signs are all ones: the centre (the column mean of the normalised rows) is what makes the bits informative.
+ * Encode: n = the fp32 row mi355_l2_normalize_rows writes for x into a 16-byte aligned buffer, bit for bit
+ * (rows_are_normalized != 0: n = x as it is).  Bit j lives in word j / 32 at position j % 32 and is 1 iff n[j] >= center[j]: a
+ * comparison, no arithmetic, so no rounding; a NaN on either side gives 0.  Pad bits (j >= dim) and pad words are 0.  A gallery
+ * row cannot carry a NaN: a row with a NaN element gets 0 bits there and scores like any row with those bits - the departure
+ * from "a NaN row ranks first" that the PQ block makes too.  Queries are encoded by the same routine with the same centre.
+ * Distance h(q, g) = popcount of the xor of the two code rows, an integer in [0, dim].
+ * Score of (q, g) = float(dim - 2 h) / float(dim): both conversions exact, one IEEE fp32 division - the cosine of the two +-1
+ * vectors.  A query whose normalised row n holds a NaN (a NaN or an infinite element of x always gives one) scores NaN against
+ * every row; its row of mi355_binary_distances is -1.  A score depends on the two code rows alone - not on Q, G, k, the
+ * filter, the chunk of the scan or the path.
+ * Top-k: the selection of mi355_rank_topk (descending, NaN first, ties to the lower row, the slots a filter leaves empty
+ * (-inf, -1)), k in [1, min(1024, G)].  At most dim + 1 distinct scores exist, so ties are the normal case.  An ineligible
+ * row (filter) never enters the selection.
+ * The scan: one workgroup per (chunk of 256 rows, block of 64 queries); the chunk's rows pass through LDS into registers, one
+ * row per lane, and a query's words are wave-uniform.  It selects inside the kernel on the integer key (h, row).  For k <= 8
+ * k candidates per (query, chunk) are merged by the selection of mi355_merge_topk (MI355_RANK_PATH_BINARY | FUSED).  For
+ * 8 < k <= 1024 (| BITONIC) no score slab exists either: each chunk leaves its 8 best rows; with b the k-th best of those, a
+ * row of the top-k that a chunk did not report lies in a chunk whose 8th row is not worse than b, a query has at most k / 8
+ * such chunks, and every row of them is scored again; the selection of mi355_merge_topk over both sets is the exact top-k.
+ * No atomics: one writer per output slot.
+ * Every argument is checked before any HIP call (null pointers, shape, k, 16-byte alignment of the codes, codes_bytes,
+ * workspace).  R, Q or G equal to 0 does nothing.  G < 2^31.  Workspace of both searching entries:
+ * mi355_binary_search_workspace_bytes (k = 0: distances only; 0 for a shape the entry would reject, and for Q = 0).
+ * dist: device int32 [Q][G]. */
+size_t mi355_binary_bytes(int64_t R, int dim);
+int mi355_binary_encode(const float* rows, int64_t R, int dim, int rows_are_normalized, float eps, const float* center, void* codes,
+                        size_t codes_bytes, void* stream);
+size_t mi355_binary_search_workspace_bytes(int64_t Q, int64_t G, int dim, int k);
+int mi355_binary_distances(const float* queries, int64_t Q, int dim, float eps, const float* center, const void* codes, int64_t G,
+                           int32_t* dist, void* workspace, size_t workspace_bytes, void* stream);
+int mi355_binary_search(const float* queries, int64_t Q, int dim, float eps, const float* center, const void* codes, int64_t G, int k,
+                        int64_t idx_offset, const mi355_rank_filter* filter, float* out_val, int64_t* out_idx, void* workspace,
+                        size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ graph search: a beam walk over neighbour lists
  * A best-first search over a graph on the rows of a resident gallery.  The result is approximate against the exhaustive
