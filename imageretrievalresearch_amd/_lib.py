@@ -198,6 +198,11 @@ PROTOTYPES = {
     "mi355_binary_distances": (C.c_int, [vp, C.c_int64, C.c_int, C.c_float, vp, vp, C.c_int64, vp, vp, C.c_size_t, vp]),
     "mi355_binary_search": (C.c_int, [vp, C.c_int64, C.c_int, C.c_float, vp, vp, C.c_int64, C.c_int, C.c_int64,
                                       C.POINTER(RankFilter), vp, vp, vp, C.c_size_t, vp]),
+    "mi355_binary_asym_search_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int, C.c_int]),
+    "mi355_binary_asym_query_codes": (C.c_int, [vp, C.c_int64, C.c_int, C.c_float, vp, vp, vp, vp, vp]),
+    "mi355_binary_asym_distances": (C.c_int, [vp, C.c_int64, C.c_int, C.c_float, vp, vp, C.c_int64, vp, vp, C.c_size_t, vp]),
+    "mi355_binary_asym_search": (C.c_int, [vp, C.c_int64, C.c_int, C.c_float, vp, vp, C.c_int64, C.c_int, C.c_int64,
+                                           C.POINTER(RankFilter), vp, vp, vp, C.c_size_t, vp]),
     "mi355_ivfpq_search_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int]),
     "mi355_ivfpq_search": (C.c_int, [vp, C.c_int64, C.c_int, C.c_float, vp, C.c_int, vp, C.c_int64, vp, vp, C.c_int64, vp, C.c_int,
                                      C.c_int64, C.c_int, C.c_int64, C.POINTER(RankFilter), vp, vp, vp, C.c_size_t, vp]),

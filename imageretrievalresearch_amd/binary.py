@@ -11,6 +11,12 @@ exhaustive first stage that the PQ table scan (one query per workgroup) is not.
 * ``bg.search(queries, k, refine=None, ...)`` ....... popcount scan (``mi355_binary_search``); with ``refine`` a shortlist is
   rescored against the fp32 / fp16 rows of a ``Gallery`` (``mi355_rescore_candidates``) and merged (``merge_topk``)
 * ``bg.distances(queries)`` / ``bg.recall(...)``
+* ``asymmetric=True`` (``search``, ``distances``, ``recall``): the gallery stays bits, the query keeps 8 bits per element - int8
+  codes ``u`` of ``n - center`` - and a row's distance is the Hamming distance weighted by ``|u|``
+  (``mi355_binary_asym_search``: the bits expanded to bytes in the kernel, the sums on the i8 MFMA).  The same codes, the same
+  bytes, a finer order: over a thousand distinct scores per query where the symmetric search has 70-80 (D = 256), and refined
+  recall@10 at a shortlist of 30 up from 0.78-0.83 to 0.88-0.92 on the tests' planted mixture.  ``bg.query_codes(queries)``
+  returns the codes.
 
 **The format is a shortlist generator.**  Its own top-k is coarse (at most ``dim + 1`` distinct scores; raw recall@10 of about
 0.4 on a clustered mixture at D = 256), the refined search is what it is for.  **The centre is not optional for pooled
@@ -20,10 +26,10 @@ bits is the existing ``Whitening``: ``BinaryGallery(w.dim_out, device)`` fed wit
 and variance-balanced, so a zero centre serves them); no projection is built into the encoder.
 
 The arithmetic is integer but for one fp32 division, and is specified bit for bit in include/mi355_retrieval.h; a NumPy model
-(tests/binary_ref.py) reproduces every bit of the codes, the distances, the scores and the top-k.  Growth of the code buffer,
-labels, recall and the shortlist rules of ``refine=`` come from ``rank._RowStore``, as for the other galleries.  Out of scope
-(DESIGN section 7): an IVF index over binary codes, a sharded binary gallery, asymmetric scoring (float query against bits),
-ITQ, range search and the metric epilogues over codes.
+(tests/binary_ref.py, tests/binary_asym_ref.py) reproduces every bit of the codes, the distances, the scores and the top-k.
+Growth of the code buffer, labels, recall and the shortlist rules of ``refine=`` come from ``rank._RowStore``, as for the other
+galleries.  Out of scope: an IVF index over binary codes, a sharded binary gallery, ITQ, more than one bit per
+dimension, range search and the metric epilogues over codes.
 """
 from __future__ import annotations
 
@@ -35,6 +41,7 @@ from ._lib import MI355Error, check, lib, stream_ptr
 MAX_DIM = 65536
 SCAN_CHUNK = 256                    # rows of one scan workgroup (BIN_CHUNK, csrc/binary.hip)
 QUERY_BLOCK = 64                    # queries of one scan workgroup (BIN_QB)
+ASYM_QUERY_BLOCK = 64               # queries of one asymmetric scan workgroup (BIN_AQB): two MFMA tiles of 32
 SELECT_PASS = 32                    # queries of one pass of the in-kernel selection (BIN_QP)
 SLICE_WORDS = 48                    # words of a row a lane holds at a time (BIN_SLICE): longer rows are scanned in slices
 
@@ -160,45 +167,75 @@ class BinaryGallery(_rank._RowStore):
         return q
 
     # ---- searching
-    def distances(self, queries: torch.Tensor) -> torch.Tensor:
+    @staticmethod
+    def _asym(asymmetric, what: str) -> bool:
+        if not isinstance(asymmetric, bool):
+            raise MI355Error(f"{what}: asymmetric must be a bool, got {asymmetric!r}")
+        return asymmetric
+
+    def distances(self, queries: torch.Tensor, asymmetric: bool = False) -> torch.Tensor:
         """(Q, rows) int32: the Hamming distance of every (query, row) pair, the integers ``search`` ranks by; the row of a
-        query with a NaN is -1."""
+        query with a NaN is -1.  ``asymmetric=True``: the weighted distances ``m`` of the asymmetric search."""
+        asym = self._asym(asymmetric, "distances")
         q = self._queries(queries, "distances")
         Q, G, L = q.shape[0], self.rows, lib()
+        sizer, entry = (L.mi355_binary_asym_search_workspace_bytes, L.mi355_binary_asym_distances) if asym else \
+            (L.mi355_binary_search_workspace_bytes, L.mi355_binary_distances)
         out = torch.empty((Q, G), dtype=torch.int32, device=self.device)
         if Q and G:
-            ws = _rank._ws.get(self.device, L.mi355_binary_search_workspace_bytes(Q, G, self.dim, 0))
+            ws = _rank._ws.get(self.device, sizer(Q, G, self.dim, 0))
             with torch.cuda.device(self.device):
-                check(L.mi355_binary_distances(q.data_ptr(), Q, self.dim, self.eps, self._center_ptr(), self._codes.data_ptr(), G,
-                                               out.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr(self.device)))
+                check(entry(q.data_ptr(), Q, self.dim, self.eps, self._center_ptr(), self._codes.data_ptr(), G,
+                            out.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr(self.device)))
         return out
 
-    def _bin_topk(self, q, k, idx_offset, filt):
+    def query_codes(self, queries: torch.Tensor):
+        """(codes (Q, dim) int8, l1 (Q,) int32, nan (Q,) bool): what the asymmetric search makes of the queries - the int8 codes
+        ``u`` of ``n - center``, ``sum |u|``, and whether the query is a NaN query (``mi355_binary_asym_query_codes``)."""
+        q = self._queries(queries, "query_codes")
+        Q = q.shape[0]
+        codes = torch.empty((Q, self.dim), dtype=torch.int8, device=self.device)
+        l1 = torch.empty((Q,), dtype=torch.int32, device=self.device)
+        nan = torch.empty((Q,), dtype=torch.int32, device=self.device)
+        if Q:
+            with torch.cuda.device(self.device):
+                check(lib().mi355_binary_asym_query_codes(q.data_ptr(), Q, self.dim, self.eps, self._center_ptr(), codes.data_ptr(),
+                                                          l1.data_ptr(), nan.data_ptr(), stream_ptr(self.device)))
+        return codes, l1, nan != 0
+
+    def _bin_topk(self, q, k, idx_offset, filt, asym=False):
         Q, G, L = q.shape[0], self.rows, lib()
+        sizer, entry = (L.mi355_binary_asym_search_workspace_bytes, L.mi355_binary_asym_search) if asym else \
+            (L.mi355_binary_search_workspace_bytes, L.mi355_binary_search)
         vals = torch.empty((Q, k), dtype=torch.float32, device=self.device)
         idx = torch.empty((Q, k), dtype=torch.int64, device=self.device)
         if Q:
-            ws = _rank._ws.get(self.device, L.mi355_binary_search_workspace_bytes(Q, G, self.dim, k))
+            ws = _rank._ws.get(self.device, sizer(Q, G, self.dim, k))
             with torch.cuda.device(self.device):
-                check(L.mi355_binary_search(q.data_ptr(), Q, self.dim, self.eps, self._center_ptr(), self._codes.data_ptr(), G, k,
-                                            int(idx_offset), None if filt is None else filt[0], vals.data_ptr(), idx.data_ptr(),
-                                            ws.data_ptr(), ws.numel(), stream_ptr(self.device)))
+                check(entry(q.data_ptr(), Q, self.dim, self.eps, self._center_ptr(), self._codes.data_ptr(), G, k,
+                            int(idx_offset), None if filt is None else filt[0], vals.data_ptr(), idx.data_ptr(),
+                            ws.data_ptr(), ws.numel(), stream_ptr(self.device)))
         return vals, idx
 
     def search(self, queries: torch.Tensor, k: int, idx_offset: int = 0, *, query_labels: torch.Tensor | None = None,
-               label_filter: str | None = None, exclude: torch.Tensor | None = None, refine=None, shortlist: int | None = None):
+               label_filter: str | None = None, exclude: torch.Tensor | None = None, refine=None, shortlist: int | None = None,
+               asymmetric: bool = False):
         """(values (Q, k) fp32, indices (Q, k) int64), ``1 <= k <= min(1024, rows)``; filters and ``idx_offset`` as in
         ``Gallery.search``.  Without ``refine`` the values are the binary scores ``(dim - 2 h) / dim``.  With ``refine``, a
         ``Gallery`` (fp32 or fp16) of the same rows on the same device, the binary search returns ``shortlist`` rows per query
         (``k <= shortlist <= min(1024, rows)``, default ``min(max(10 * k, 100), 1024, rows)``), each is scored again as
         ``qn . row`` against the gallery's row (the bits an ``IVFIndex`` scan gives the pair) and the top-k of those values is
-        returned.  Nothing is read back."""
+        returned.  Nothing is read back.  ``asymmetric=True`` scores the same codes against an int8 quantisation of
+        ``n - center`` instead of the query's sign bits (``mi355_binary_asym_search``): the values are ``(L1 - 2 m) / L1`` with
+        ``m`` the Hamming distance weighted by the query's magnitudes, a finer order and a better shortlist; everything else
+        (filters, ``idx_offset``, ``refine``, ``shortlist``) is the same."""
+        asym = self._asym(asymmetric, "search")
         k, R = self._shortlist_length(k, refine, shortlist)
         q = self._queries(queries, "search")
         Q = q.shape[0]
         gl = None if label_filter is None else self._labels_for(f'label_filter="{label_filter}"')
         filt = _rank._rank_filter(Q, self.rows, self.device, query_labels, gl, label_filter, exclude)
-        vals, idx = self._bin_topk(q, R, idx_offset, filt)
+        vals, idx = self._bin_topk(q, R, idx_offset, filt, asym)
         if refine is None or Q == 0:
             return vals[:, :k], idx[:, :k]
         return self._refined_topk(q, vals, idx, k, refine, idx_offset)

@@ -20,9 +20,13 @@
 //                    not worse than b - a SATURATED chunk - and since only k candidates are not worse than b, a query has at
 //                    most k / 8 of them.  k_bin_saturated lists them in chunk order and retires their candidates,
 //                    k_bin_rescan scores every row of those chunks for that query, and the selection over both is exact.
+//   asymmetric ..... the same codes searched with int8 query codes on the i8 MFMA (k_bin_asym_queries, k_bin_asym_scan: see
+//                    the block in front of them); staging, selection pass and the k > 8 route are shared with the above.
 // No atomics: every output slot has one writer.  gfx950 only.
-#include "rank_common.h"
+#include "i8_quant.h"
 #include "../../include/mi355_retrieval.h"
+
+#include <type_traits>
 
 namespace mi355 {
 
@@ -92,16 +96,70 @@ struct BinScanArgs {
     RankFilter flt;             // FUSED && FILT: the filter of this launch's queries
 };
 
-// Words [s0, s0 + S) of the chunk's 256 rows into rows_s [256][S + 1]; a row past G or a word past ld reads as 0
-template <int S>
-__device__ __forceinline__ void bin_stage(unsigned* rows_s, const BinScanArgs& a, i64 c0, int s0) {
-    constexpr int PPR = S / 4;                                          // 16-byte pieces of a row slice
+// Words [s0, s0 + S) of the chunk's 256 rows into rows_s [256][S + 1]; a row past G or a word past ld reads as 0.  (S is a
+// constant of the popcount scan and a launch-wide value of the asymmetric one: inlined, the former compiles as before.)
+__device__ __forceinline__ void bin_stage_words(unsigned* rows_s, const BinScanArgs& a, i64 c0, int s0, const int S) {
+    const int PPR = S / 4;                                              // 16-byte pieces of a row slice
     for (int p = threadIdx.x; p < BIN_CHUNK * PPR; p += 256) {
         const int row = p / PPR, w0 = s0 + (p - row * PPR) * 4;
         uint4 v = make_uint4(0u, 0u, 0u, 0u);
         if (c0 + row < a.G && w0 < a.ld) v = *reinterpret_cast<const uint4*>(a.codes + (c0 + row) * a.ld + w0);
         unsigned* d = rows_s + row * (S + 1) + (w0 - s0);
         d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+    }
+}
+template <int S>
+__device__ __forceinline__ void bin_stage(unsigned* rows_s, const BinScanArgs& a, i64 c0, int s0) {
+    bin_stage_words(rows_s, a, c0, s0, S);
+}
+
+// The ending of one pass of the fused scans.  tile [BIN_QP][BIN_TS] holds the pass's keys (distance << 8 | row in chunk,
+// BIN_NO_KEY for an ineligible row), query qq of the pass is query q0 + qq of the launch and takes part iff q_lo <= q0 + qq <
+// q_hi.  Thread t: query t / 8 of the pass, keys part * 33 .. part * 33 + 31 of it (rows part * 32 .. + 31 of the chunk): it
+// keeps the K smallest in a branch-free sorted list, the eight lists of a query are merged by a butterfly of shuffles, and
+// part 0 writes the a.k best as (score(q)(distance), row) to the chunk's candidate slots.  No barrier inside.
+template <int K, class Score>
+__device__ __forceinline__ void bin_select_pass(const unsigned* tile, const BinScanArgs& a, int chunk, i64 c0, int q0, int q_lo, int q_hi,
+                                                const Score& score) {
+    const int tid = threadIdx.x;
+    const int qq = tid >> 3, part = tid & 7;
+    const int q = q0 + qq;
+    const bool mine_q = q >= q_lo && q < q_hi;                          // (whole groups of 8 lanes: the shuffles below stay inside one)
+    unsigned kv[K];
+#pragma unroll
+    for (int i = 0; i < K; ++i) kv[i] = BIN_NO_KEY;
+    auto insert = [&](unsigned key) {                                   // keys are distinct; BIN_NO_KEY is below nothing
+        bool g[K];
+#pragma unroll
+        for (int i = 0; i < K; ++i) g[i] = key < kv[i];
+#pragma unroll
+        for (int i = K - 1; i > 0; --i) kv[i] = g[i] ? (g[i - 1] ? kv[i - 1] : key) : kv[i];
+        kv[0] = g[0] ? key : kv[0];
+    };
+    if (mine_q) {
+        const unsigned* mine = tile + qq * BIN_TS + part * 33;
+#pragma unroll 4
+        for (int i = 0; i < 32; ++i) insert(mine[i]);
+    }
+#pragma unroll
+    for (int m = 1; m < 8; m <<= 1) {
+        unsigned other[K];
+#pragma unroll
+        for (int i = 0; i < K; ++i) other[i] = (unsigned)__shfl_xor((int)kv[i], m, 64);
+#pragma unroll
+        for (int i = 0; i < K; ++i) insert(other[i]);
+    }
+    if (part == 0 && mine_q) {
+        const size_t o = (size_t)q * a.cand_ld + (size_t)chunk * a.k;
+        const auto score_of = score(q);                                 // the query's constants, read once
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+            if (i < a.k) {
+                const bool have = kv[i] != BIN_NO_KEY;
+                a.cand_val[o + i] = have ? score_of((int)(kv[i] >> 8)) : NEG_INF;
+                a.cand_idx[o + i] = have ? c0 + (i64)(kv[i] & 255u) + a.idx_offset : IDX_PAD;
+            }
+        }
     }
 }
 
@@ -182,47 +240,240 @@ __global__ __launch_bounds__(256) void k_bin_scan(BinScanArgs a) {
         }
         if constexpr (MODE == BIN_FUSED) {
             __syncthreads();
-            // thread t: query t / 8 of the pass, keys part * 33 .. part * 33 + 31 of it (rows part * 32 .. + 31 of the chunk)
-            const int qq = tid >> 3, part = tid & 7;
-            unsigned kv[K];
-#pragma unroll
-            for (int i = 0; i < K; ++i) kv[i] = BIN_NO_KEY;
-            auto insert = [&](unsigned key) {                           // keys are distinct; BIN_NO_KEY is below nothing
-                bool g[K];
-#pragma unroll
-                for (int i = 0; i < K; ++i) g[i] = key < kv[i];
-#pragma unroll
-                for (int i = K - 1; i > 0; --i) kv[i] = g[i] ? (g[i - 1] ? kv[i - 1] : key) : kv[i];
-                kv[0] = g[0] ? key : kv[0];
-            };
-            if (qq < nq) {                                              // (whole groups of 8 lanes: the shuffles below stay inside one)
-                const unsigned* mine = tile + qq * BIN_TS + part * 33;
-#pragma unroll 4
-                for (int i = 0; i < 32; ++i) insert(mine[i]);
-            }
-#pragma unroll
-            for (int m = 1; m < 8; m <<= 1) {
-                unsigned other[K];
-#pragma unroll
-                for (int i = 0; i < K; ++i) other[i] = (unsigned)__shfl_xor((int)kv[i], m, 64);
-#pragma unroll
-                for (int i = 0; i < K; ++i) insert(other[i]);
-            }
-            if (part == 0 && qq < nq) {
-                const int q = qp + qq;
+            bin_select_pass<K>(tile, a, chunk, c0, qp, q_lo, q_hi, [&](int q) {
                 const bool qbad = a.qnan[q] != 0;
-                const size_t o = (size_t)q * a.cand_ld + (size_t)chunk * a.k;
+                const int dim = a.dim;
+                return [=](int h) { return qbad ? __uint_as_float(0x7fc00000u) : bin_score(h, dim); };
+            });
+            __syncthreads();                                            // the next pass writes the tile
+        }
+    }
+}
+
+// ---- asymmetric scoring: the gallery stays bits, the query becomes int8 codes u of r = n - center (the row quantiser of
+// i8_quant.h), and the distance is the Hamming distance weighted by |u|: m = Upos - P with P = the sum of u over the set bits of
+// the row and Upos = the sum of the positive u.  P is an int8 dot product of u with the row's bits as 0/1 bytes, so it runs on
+// v_mfma_i32_32x32x32_i8 with exact int32 sums.  score = float(L1 - 2 m) / float(L1), L1 = sum |u|.
+//   k_bin_asym_queries ... one wave per query: norm, r, amax, the codes in the order the scan's A fragments want them
+//   k_bin_asym_scan ...... one workgroup per (chunk of 256 rows, block of 64 queries); a wave takes 64 rows of the chunk as two
+//                          B tiles of 32 columns and the block's queries as one or two A tiles of 32 rows.  Per k-step of 32
+//                          dimensions a lane reads one word of each of its two rows from the LDS image, expands its 16 bits
+//                          to 16 bytes of 0 / 1 ((nibble * 0x00204081) & 0x01010101: bit i of the nibble lands in byte i) and
+//                          issues 2 x tiles MFMAs.  A lane's A and B bytes are the same 16 dimensions, byte for byte, and an
+//                          integer sum has no order (the pairing argument of rank_i8.hip).  The endings are those of k_bin_scan.
+// Queries of one asymmetric scan workgroup: two A tiles, 64 accumulator registers per lane.  Measured at 1M rows x 1536
+// (plain k = 3, Q = 256 / Q = 1): 128 queries at one wave per SIMD 1.35 / 0.29 ms, held to two waves (it spills) 1.31 / 0.24,
+// 64 queries at two waves 0.91 / 0.19, at three waves 0.85 / 0.17 - the bits are expanded twice as often, but the loop is
+// bound by the latency of its loads, and the waves hide it.
+constexpr int BIN_AQB = 64;
+constexpr int BIN_ANT = BIN_AQB / 32;
+constexpr int BIN_ASYM_WGS = 3;                // workgroups per CU the scan is compiled for: at most 170 VGPRs
+static_assert(BIN_ANT == 2, "k_bin_asym_scan has a k-loop for one live tile and one for both");
+typedef int bin_i32x16 __attribute__((ext_vector_type(16)));
+
+// The queries of an asymmetric call.  frag [tile of 32 queries][k-step][lane][16 B]: lane = query % 32 + 32 * half holds the
+// codes of dimensions step * 32 + half * 16 .. + 15; whole tiles, the rows past Q and the dimensions past dim are 0.
+struct BinAsymQueries {
+    const signed char* frag;
+    const int* upos;            // [Q up to whole tiles] the sum of the positive codes
+    const int* l1;              // the sum of |code|
+    const int* qnan;            // 1: a NaN in r, or a non-finite amax
+    int steps;                  // ceil(dim / 32)
+    // float(L1 - 2 m) / float(L1): both conversions exact (|L1 - 2 m| <= L1 < 2^23), one IEEE division
+    // (score_of(q): the query's two integers read once, then a function of m)
+    __device__ __forceinline__ auto score_of(int q) const {
+        const bool bad = qnan[q] != 0;
+        const int L = l1[q];
+        return [=](int m) {
+            if (bad) return __uint_as_float(0x7fc00000u);
+            return L == 0 ? 0.0f : __fdiv_rn((float)(L - 2 * m), (float)L);
+        };
+    }
+    __device__ __forceinline__ float score(int q, int m) const { return score_of(q)(m); }
+};
+
+// bits 0 .. 3 of nib as four bytes of 0 / 1
+__device__ __forceinline__ unsigned bin_expand4(unsigned nib) { return (nib * 0x00204081u) & 0x01010101u; }
+__device__ __forceinline__ i32x4 bin_expand16(unsigned bits) {
+    return (i32x4){(int)bin_expand4(bits & 15u), (int)bin_expand4((bits >> 4) & 15u), (int)bin_expand4((bits >> 8) & 15u),
+                   (int)bin_expand4((bits >> 12) & 15u)};
+}
+
+// P of (query q, the code row g) on the VALU: for the rescan of the saturated chunks
+__device__ __forceinline__ int bin_asym_row_sum(const BinAsymQueries& aq, int q, const unsigned* __restrict__ g) {
+    const signed char* f = aq.frag + (size_t)(q >> 5) * aq.steps * 1024 + (q & 31) * 16;
+    int p = 0;
+    for (int w = 0; w < aq.steps; ++w) {
+        const unsigned bits = g[w];
 #pragma unroll
-                for (int i = 0; i < K; ++i) {
-                    if (i < a.k) {
-                        const bool have = kv[i] != BIN_NO_KEY;
-                        const float s = qbad ? __uint_as_float(0x7fc00000u) : bin_score((int)(kv[i] >> 8), a.dim);
-                        a.cand_val[o + i] = have ? s : NEG_INF;
-                        a.cand_idx[o + i] = have ? c0 + (i64)(kv[i] & 255u) + a.idx_offset : IDX_PAD;
+        for (int h = 0; h < 2; ++h) {
+            const i32x4 u = *reinterpret_cast<const i32x4*>(f + (size_t)w * 1024 + h * 512);
+            const i32x4 b = bin_expand16(bits >> (16 * h));
+#pragma unroll
+            for (int e = 0; e < 4; ++e) p = __builtin_amdgcn_sdot4(u[e], b[e], p, false);
+        }
+    }
+    return p;
+}
+
+// wave w of workgroup b takes row b * 4 + w of the rows_pad rows; rows >= Q (the rest of the last tile) are written as zeros.
+// frag, upos null: only plain [Q][dim], l1 and qnan are written (mi355_binary_asym_query_codes); plain null otherwise.
+__global__ __launch_bounds__(256) void k_bin_asym_queries(const float* __restrict__ queries, const float* __restrict__ center, int Q,
+                                                          int rows_pad, int dim, float eps, int vec, signed char* __restrict__ frag,
+                                                          int steps, int* __restrict__ upos, int* __restrict__ l1,
+                                                          int* __restrict__ qnan, signed char* __restrict__ plain) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows_pad) return;
+    signed char* out = frag ? frag + (size_t)(row >> 5) * steps * 1024 + (row & 31) * 16 : nullptr;
+    const bool real = row < Q;
+    const float* x = queries + (i64)(real ? row : 0) * dim;
+    I8Quant q = {0.f, 0.f, true};
+    float r = 0.f;
+    if (real) {
+        r = row_inv_norm(x, dim, eps, vec, lane);
+        float amax = 0.f;
+        bool nan = false;
+        for (int i = lane; i < dim; i += 64) {
+            const float d = i8_norm_elem(x[i], r) - (center ? center[i] : 0.0f);
+            nan = nan || d != d;
+            amax = fmaxf(amax, fabsf(d));
+        }
+        q = i8_quant(wave_max(amax), __ballot(nan) != 0ull);
+    }
+    int sum_abs = 0, sum_pos = 0;
+    for (int c = lane; c < 2 * steps; c += 64) {                        // 16-byte piece c: k-step c / 2, half c % 2
+        unsigned w[4] = {0u, 0u, 0u, 0u};
+        if (!q.zero) {
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const int k = c * 16 + j;
+                int u = 0;
+                if (k < dim) u = i8_code(i8_norm_elem(x[k], r) - (center ? center[k] : 0.0f), q.inv);
+                sum_abs += u < 0 ? -u : u;
+                sum_pos += u > 0 ? u : 0;
+                w[j >> 2] |= (unsigned)(u & 0xff) << (8 * (j & 3));
+            }
+        }
+        if (out) *reinterpret_cast<i32x4*>(out + (size_t)(c >> 1) * 1024 + (c & 1) * 512) = (i32x4){(int)w[0], (int)w[1], (int)w[2], (int)w[3]};
+        if (plain && real) {
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const int k = c * 16 + j;
+                if (k < dim) plain[(i64)row * dim + k] = (signed char)((w[j >> 2] >> (8 * (j & 3))) & 0xff);
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { sum_abs += __shfl_xor(sum_abs, o, 64); sum_pos += __shfl_xor(sum_pos, o, 64); }
+    if (lane == 0) {
+        l1[row] = sum_abs;
+        qnan[row] = q.zero && q.scale != q.scale ? 1 : 0;
+        if (upos) upos[row] = sum_pos;
+    }
+}
+
+struct BinAsymScanArgs {
+    BinScanArgs s;              // codes, G, ld, Q = the queries of this launch, k, nch, the outputs and the filter; no qcodes
+    BinAsymQueries aq;          // the queries of the call
+    int aq0;                    // query q of the launch is query aq0 + q of the call
+    int S;                      // words of a row in the LDS image at a time: min(ld, BIN_SLICE)
+};
+
+// grid: query blocks (fastest) x nch chunks, one-dimensional.  The A tiles are tiles of 32 of the CALL's queries; a launch's
+// queries aq0 .. aq0 + Q - 1 may start and end inside one (aq0 need not be a multiple of 32: the query block of k > 8 over a
+// very large gallery is whatever fits the candidate lists).  The launch covers every tile it touches, a workgroup takes up to
+// BIN_ANT consecutive ones, computes all 32 rows of each and leaves out the queries of another launch (q < 0 or q >= Q below).
+template <int MODE, int K, bool FILT>
+__global__ __launch_bounds__(256, BIN_ASYM_WGS) void k_bin_asym_scan(BinAsymScanArgs b) {
+    extern __shared__ __attribute__((aligned(16))) unsigned smem[];
+    unsigned* rows_s = smem;                                            // [256][S + 1]
+    unsigned* tile = smem;                                              // the keys of a pass, once the k-loop has left the rows
+    const BinScanArgs& a = b.s;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
+    const int t_first = b.aq0 >> 5, t_end = (b.aq0 + a.Q + 31) >> 5;
+    const int nqb = (t_end - t_first + BIN_ANT - 1) / BIN_ANT;
+    const int chunk = blockIdx.x / nqb, qblk = blockIdx.x - chunk * nqb;
+    const int t0 = t_first + qblk * BIN_ANT;
+    const int nt = t_end - t0 < BIN_ANT ? t_end - t0 : BIN_ANT;         // live tiles: the same in every thread
+    const i64 c0 = (i64)chunk * BIN_CHUNK;
+    const int steps = b.aq.steps, S = b.S;
+    bin_i32x16 acc[2][BIN_ANT];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int t = 0; t < BIN_ANT; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[j][t][r] = 0;
+    const unsigned* my0 = rows_s + (wave * 64 + col) * (S + 1);
+    const unsigned* my1 = my0 + 32 * (S + 1);
+    for (int s0 = 0; s0 < steps; s0 += S) {
+        __syncthreads();                                                // every lane has left the previous slice
+        bin_stage_words(rows_s, a, c0, s0, S);
+        __syncthreads();
+        const int nw = steps - s0 < S ? steps - s0 : S;
+        const signed char* fa = b.aq.frag + ((size_t)t0 * steps + s0) * 1024 + lane * 16;
+        auto k_loop = [&](auto live_tiles) {                            // (a branch-free body per number of live tiles)
+            constexpr int NTL = decltype(live_tiles)::value;
+            for (int w = 0; w < nw; ++w) {
+                const i32x4 b0 = bin_expand16(my0[w] >> (16 * half)), b1 = bin_expand16(my1[w] >> (16 * half));
+#pragma unroll
+                for (int t = 0; t < NTL; ++t) {
+                    const i32x4 af = *reinterpret_cast<const i32x4*>(fa + ((size_t)t * steps + w) * 1024);
+                    acc[0][t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(af, b0, acc[0][t], 0, 0, 0);
+                    acc[1][t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(af, b1, acc[1][t], 0, 0, 0);
+                }
+            }
+        };
+        if (nt == 1) k_loop(std::integral_constant<int, 1>{});
+        else k_loop(std::integral_constant<int, BIN_ANT>{});
+    }
+    // accumulator register r of a lane: query (r & 3) + 8 * (r >> 2) + 4 * half of the tile, row col (+ 32) of the wave's 64
+    const int rc[2] = {wave * 64 + col, wave * 64 + 32 + col};
+    const bool live[2] = {c0 + rc[0] < a.G, c0 + rc[1] < a.G};
+    i64 glab[2] = {0, 0};
+    if constexpr (MODE == BIN_FUSED && FILT) {
+        if (a.flt.mode != MI355_LABEL_ANY) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+                if (live[j]) glab[j] = a.flt.glab[c0 + rc[j]];
+        }
+    }
+    if constexpr (MODE == BIN_FUSED) __syncthreads();                   // the tile takes the rows' place
+#pragma unroll
+    for (int t = 0; t < BIN_ANT; ++t) {
+        if (t < nt) {
+            const int qt = (t0 + t) * 32;                               // the tile's first query, of the call
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int qq = (r & 3) + 8 * (r >> 2) + 4 * half;
+                const int q = qt + qq - b.aq0;                          // of the launch
+                const bool mine_q = q >= 0 && q < a.Q;
+                const int up = b.aq.upos[qt + qq];
+                const bool qbad = b.aq.qnan[qt + qq] != 0;
+                i64 fq_lab = 0, fq_ex = -1;
+                if constexpr (MODE == BIN_FUSED && FILT) {
+                    if (mine_q) query_filter(a.flt, q, fq_lab, fq_ex);
+                }
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const int m = up - acc[j][t][r];
+                    if constexpr (MODE == BIN_DIST) {
+                        if (mine_q && live[j]) a.out[(i64)q * a.ld_out + c0 + rc[j]] = qbad ? -1 : m;
+                    } else {
+                        bool ok = live[j];
+                        if constexpr (FILT) ok = ok && eligible(a.flt.mode, fq_lab, glab[j], fq_ex, c0 + rc[j]);
+                        // m < 2^23: the key stays below BIN_NO_KEY.  A NaN query scores NaN everywhere: all tie
+                        tile[qq * BIN_TS + (rc[j] >> 5) * 33 + (rc[j] & 31)] =
+                            ok ? ((unsigned)(qbad ? 0 : m) << 8) | (unsigned)rc[j] : BIN_NO_KEY;
                     }
                 }
             }
-            __syncthreads();                                            // the next pass writes the tile
+            if constexpr (MODE == BIN_FUSED) {
+                __syncthreads();
+                bin_select_pass<K>(tile, a, chunk, c0, qt - b.aq0, 0, a.Q, [&](int q) { return b.aq.score_of(b.aq0 + q); });
+                __syncthreads();                                        // the next pass writes the tile
+            }
         }
     }
 }
@@ -284,7 +535,9 @@ struct BinRescanArgs {
     i64 idx_offset, cand_ld, tail;
     float* cand_val; i64* cand_idx;
     RankFilter flt; int filt;
+    BinAsymQueries aq; int aq0;     // ASYM: the queries' int8 codes; query q of the launch is query aq0 + q of them
 };
+template <bool ASYM>
 __global__ __launch_bounds__(256) void k_bin_rescan(BinRescanArgs a) {
     const int s = blockIdx.x, tid = threadIdx.x;
     const i64 q = blockIdx.y;
@@ -301,10 +554,15 @@ __global__ __launch_bounds__(256) void k_bin_rescan(BinRescanArgs a) {
         }
         if (ok) {
             const unsigned* g = a.codes + row * a.ld;
-            const unsigned* qw = a.qcodes + q * a.ldq;
-            int h = 0;
-            for (int w = 0; w < a.ld; ++w) h += __popc(g[w] ^ qw[w]);
-            val = a.qnan[q] ? __uint_as_float(0x7fc00000u) : bin_score(h, a.dim);
+            if constexpr (ASYM) {
+                const int qa = a.aq0 + (int)q;
+                val = a.aq.score(qa, a.aq.upos[qa] - bin_asym_row_sum(a.aq, qa, g));
+            } else {
+                const unsigned* qw = a.qcodes + q * a.ldq;
+                int h = 0;
+                for (int w = 0; w < a.ld; ++w) h += __popc(g[w] ^ qw[w]);
+                val = a.qnan[q] ? __uint_as_float(0x7fc00000u) : bin_score(h, a.dim);
+            }
             idx = row + a.idx_offset;
         }
     }
@@ -407,6 +665,82 @@ static int bin_check_search(const char* who, const void* queries, i64 Q, int dim
     return OK;
 }
 
+// ---- host side of the asymmetric search
+struct BinAsymWs {
+    signed char* frag; int* upos; int* l1; int* qnan;
+    float* cand_val; i64* cand_idx; int* satlist; int* satcount; void* topk; size_t topk_bytes;
+    size_t total;
+};
+// As bin_carve, with the queries' int8 codes (whole tiles of 32 queries) and their three integers in place of the bit codes
+static BinAsymWs bin_asym_carve(void* ws, i64 Q, i64 G, int dim, int k) {
+    BinAsymWs r{};
+    WsCarver c(ws);
+    const i64 qb = bin_query_block(Q, G, k), qpad = (Q + 31) / 32 * 32;
+    r.frag = (signed char*)c.take((size_t)qpad * bin_words(dim) * 32);
+    r.upos = (int*)c.take((size_t)qpad * sizeof(int));
+    r.l1 = (int*)c.take((size_t)qpad * sizeof(int));
+    r.qnan = (int*)c.take((size_t)qpad * sizeof(int));
+    if (k >= 1) {
+        const size_t n = (size_t)qb * bin_cand_ld(G, k);
+        r.cand_val = (float*)c.take(n * sizeof(float));
+        r.cand_idx = (i64*)c.take(n * sizeof(i64));
+        if (k > SMALL_K) {
+            r.satlist = (int*)c.take((size_t)qb * (k / SMALL_K) * sizeof(int));
+            r.satcount = (int*)c.take((size_t)qb * sizeof(int));
+        }
+        r.topk_bytes = topk_ws_bytes(qb, bin_cand_ld(G, k), k);
+        r.topk = c.take(r.topk_bytes);
+    }
+    r.total = c.total();
+    return r;
+}
+
+static int launch_asym_queries(const float* queries, i64 Q, i64 rows_pad, int dim, float eps, const float* center, signed char* frag,
+                               int* upos, int* l1, int* qnan, signed char* plain, hipStream_t st) {
+    hipLaunchKernelGGL(k_bin_asym_queries, dim3((unsigned)((rows_pad + 3) / 4)), dim3(256), 0, st, queries, center, (int)Q, (int)rows_pad,
+                       dim, eps, vec_ok(queries, dim), frag, bin_words(dim), upos, l1, qnan, plain);
+    MI355_LAUNCH_CHECK();
+    return OK;
+}
+static BinAsymQueries asym_queries(const BinAsymWs& w, int dim) { return {w.frag, w.upos, w.l1, w.qnan, bin_words(dim)}; }
+
+template <int MODE, int K, bool FILT>
+static int launch_asym_scan(const BinAsymScanArgs& b, hipStream_t st) {
+    const size_t rows_b = (size_t)BIN_CHUNK * (b.S + 1) * sizeof(unsigned), tile_b = (size_t)BIN_QP * BIN_TS * sizeof(unsigned);
+    const size_t lds = MODE == BIN_FUSED && tile_b > rows_b ? tile_b : rows_b;              // at most 50176 bytes
+    const int tiles = ((b.aq0 + b.s.Q + 31) >> 5) - (b.aq0 >> 5);
+    const unsigned grid = (unsigned)b.s.nch * (unsigned)((tiles + BIN_ANT - 1) / BIN_ANT);
+    hipLaunchKernelGGL((k_bin_asym_scan<MODE, K, FILT>), dim3(grid), dim3(256), lds, st, b);
+    MI355_LAUNCH_CHECK();
+    return OK;
+}
+template <bool FILT>
+static int dispatch_asym_fused(const BinAsymScanArgs& b, hipStream_t st) {
+    if (b.s.k <= 1) return launch_asym_scan<BIN_FUSED, 1, FILT>(b, st);
+    if (b.s.k <= 4) return launch_asym_scan<BIN_FUSED, 4, FILT>(b, st);
+    return launch_asym_scan<BIN_FUSED, 8, FILT>(b, st);
+}
+
+// The k > 8 route of both searches over one query block, after the scan has left 8 candidates per chunk (cand): the bound into
+// (ov, oi), the saturated chunks, their rescan into the tail of cand.  r comes with the queries' side filled in.
+template <bool ASYM>
+static int bin_saturated_route(BinRescanArgs r, i64 qn, i64 nch, int k, const RankFilter* f, float* ov, i64* oi, int* satlist,
+                               int* satcount, void* topk, size_t topk_bytes, hipStream_t st) {
+    // the bound: the k-th best of the chunks' candidates, into the output for now (none if there are fewer than k)
+    const i64 head = nch * SMALL_K;
+    const bool bound = head >= k;
+    if (bound)
+        if (int e = topk_select(r.cand_val, r.cand_idx, qn, head, r.cand_ld, k, 0, ov, oi, topk, topk_bytes, st, nullptr, f)) return e;
+    const int nslots = k / SMALL_K;
+    hipLaunchKernelGGL(k_bin_saturated, dim3((unsigned)qn), dim3(256), 0, st, r.cand_val, r.cand_idx, r.cand_ld, (int)nch,
+                       bound ? ov : nullptr, bound ? oi : nullptr, k, nslots, satlist, satcount);
+    MI355_LAUNCH_CHECK();
+    r.nslots = nslots; r.satlist = satlist; r.satcount = satcount; r.tail = head; r.filt = f ? 1 : 0;
+    hipLaunchKernelGGL(k_bin_rescan<ASYM>, dim3((unsigned)nslots, (unsigned)qn), dim3(256), 0, st, r);
+    MI355_LAUNCH_CHECK();
+    return OK;
+}
+
 }  // namespace mi355
 
 using namespace mi355;
@@ -494,24 +828,97 @@ int mi355_binary_search(const float* queries, int64_t Q, int dim, float eps, con
         a.cand_val = w.cand_val; a.cand_idx = w.cand_idx; a.cand_ld = cand_ld; a.flt = fb;
         if (int e = f ? dispatch_fused<true>(a, st) : dispatch_fused<false>(a, st)) return e;
         if (!fused) {
-            // the bound: the k-th best of the chunks' candidates, into the output for now (none if there are fewer than k)
-            const i64 head = nch * SMALL_K;
-            const bool bound = head >= k;
-            if (bound)
-                if (int e = topk_select(w.cand_val, w.cand_idx, qn, head, cand_ld, k, 0, ov, oi, w.topk, w.topk_bytes, st, nullptr, f))
-                    return e;
-            const int nslots = k / SMALL_K;
-            hipLaunchKernelGGL(k_bin_saturated, dim3((unsigned)qn), dim3(256), 0, st, w.cand_val, w.cand_idx, cand_ld, (int)nch,
-                               bound ? ov : nullptr, bound ? oi : nullptr, k, nslots, w.satlist, w.satcount);
-            MI355_LAUNCH_CHECK();
             BinRescanArgs r{};
-            r.codes = a.codes; r.G = G; r.ld = ld; r.qcodes = a.qcodes; r.qnan = a.qnan; r.ldq = ldq; r.dim = dim; r.nslots = nslots;
-            r.satlist = w.satlist; r.satcount = w.satcount; r.idx_offset = idx_offset; r.cand_ld = cand_ld; r.tail = head;
-            r.cand_val = w.cand_val; r.cand_idx = w.cand_idx; r.flt = fb; r.filt = f ? 1 : 0;
-            hipLaunchKernelGGL(k_bin_rescan, dim3((unsigned)nslots, (unsigned)qn), dim3(256), 0, st, r);
-            MI355_LAUNCH_CHECK();
+            r.codes = a.codes; r.G = G; r.ld = ld; r.qcodes = a.qcodes; r.qnan = a.qnan; r.ldq = ldq; r.dim = dim;
+            r.idx_offset = idx_offset; r.cand_ld = cand_ld; r.cand_val = w.cand_val; r.cand_idx = w.cand_idx; r.flt = fb;
+            if (int e = bin_saturated_route<false>(r, qn, nch, k, f, ov, oi, w.satlist, w.satcount, w.topk, w.topk_bytes, st)) return e;
         }
         // the candidates carry their indices; with a filter the slots no eligible row filled end as (-inf, -1)
+        if (int e = topk_select(w.cand_val, w.cand_idx, qn, cand_ld, cand_ld, k, 0, ov, oi, w.topk, w.topk_bytes, st, nullptr, f)) return e;
+    }
+    return OK;
+}
+
+size_t mi355_binary_asym_search_workspace_bytes(int64_t Q, int64_t G, int dim, int k) {
+    if (Q < 1 || !bin_shape_ok(Q, G, dim) || k < 0 || k > LARGE_K) return 0;
+    return bin_asym_carve(nullptr, Q, G, dim, k).total;
+}
+
+int mi355_binary_asym_query_codes(const float* queries, int64_t Q, int dim, float eps, const float* center, int8_t* codes, int32_t* l1,
+                                  int32_t* nanflag, void* stream) {
+    const char* who = "binary_asym_query_codes";
+    MI355_REQUIRE(queries && codes && l1 && nanflag, "%s: null pointer", who);
+    MI355_REQUIRE(Q >= 0 && dim >= 1, "%s: bad shape Q=%lld dim=%d", who, (long long)Q, dim);
+    MI355_REQUIRE(dim <= BIN_MAX_DIM, "%s: dim=%d exceeds %d", who, dim, BIN_MAX_DIM);
+    MI355_REQUIRE(Q <= INT_MAX, "%s: shape too large Q=%lld", who, (long long)Q);
+    if (Q == 0) return OK;
+    RoctxRange range("binary/asymmetric query codes");
+    return launch_asym_queries(queries, Q, Q, dim, eps, center, nullptr, nullptr, (int*)l1, (int*)nanflag, (signed char*)codes,
+                               (hipStream_t)stream);
+}
+
+int mi355_binary_asym_distances(const float* queries, int64_t Q, int dim, float eps, const float* center, const void* codes, int64_t G,
+                                int32_t* dist, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "binary_asym_distances";
+    if (int e = bin_check_search(who, queries, Q, dim, codes, G, dist, dist)) return e;
+    if (Q == 0 || G == 0) return OK;
+    const BinAsymWs w = bin_asym_carve(workspace, Q, G, dim, 0);
+    MI355_REQUIRE(workspace && workspace_bytes >= w.total, "%s: workspace %zu < %zu bytes", who, workspace_bytes, w.total);
+    hipStream_t st = (hipStream_t)stream;
+    RoctxRange range("binary/asymmetric distances");
+    if (int e = launch_asym_queries(queries, Q, (Q + 31) / 32 * 32, dim, eps, center, w.frag, w.upos, w.l1, w.qnan, nullptr, st)) return e;
+    const int ld = bin_ld(dim);
+    const i64 qb = bin_query_block(Q, G, 0), nch = (G + BIN_CHUNK - 1) / BIN_CHUNK;
+    for (i64 q0 = 0; q0 < Q; q0 += qb) {
+        const i64 qn = Q - q0 < qb ? Q - q0 : qb;
+        BinAsymScanArgs b{};
+        b.s.codes = (const unsigned*)codes; b.s.G = G; b.s.ld = ld; b.s.Q = (int)qn; b.s.dim = dim; b.s.nch = (int)nch;
+        b.s.out = (int*)dist + q0 * G; b.s.ld_out = G;
+        b.aq = asym_queries(w, dim); b.aq0 = (int)q0; b.S = ld < BIN_SLICE ? ld : BIN_SLICE;
+        if (int e = launch_asym_scan<BIN_DIST, 1, false>(b, st)) return e;
+    }
+    return OK;
+}
+
+int mi355_binary_asym_search(const float* queries, int64_t Q, int dim, float eps, const float* center, const void* codes, int64_t G, int k,
+                             int64_t idx_offset, const mi355_rank_filter* filter, float* out_val, int64_t* out_idx, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+    const char* who = "binary_asym_search";
+    if (int e = bin_check_search(who, queries, Q, dim, codes, G, out_val, out_idx)) return e;
+    MI355_REQUIRE(k >= 1 && k <= LARGE_K && (G == 0 || k <= G), "%s: k=%d outside [1, %lld]", who, k,
+                  (long long)(G > 0 && G < LARGE_K ? G : LARGE_K));
+    RankFilter fall{};
+    if (filter)
+        if (int e = make_filter(filter, idx_offset, who, &fall)) return e;
+    if (Q == 0 || G == 0) return OK;
+    const BinAsymWs w = bin_asym_carve(workspace, Q, G, dim, k);
+    MI355_REQUIRE(workspace && workspace_bytes >= w.total, "%s: workspace %zu < %zu bytes", who, workspace_bytes, w.total);
+    hipStream_t st = (hipStream_t)stream;
+    const bool fused = k <= SMALL_K;
+    RoctxRange range(fused ? "binary/asymmetric scan + per-chunk top-k"
+                           : "binary/asymmetric scan + per-chunk top-8 + saturated chunks + top-k");
+    if (int e = launch_asym_queries(queries, Q, (Q + 31) / 32 * 32, dim, eps, center, w.frag, w.upos, w.l1, w.qnan, nullptr, st)) return e;
+    set_rank_path(MI355_RANK_PATH_BINARY_ASYM | (fused ? MI355_RANK_PATH_FUSED : MI355_RANK_PATH_BITONIC));
+    const int ld = bin_ld(dim);
+    const i64 qb = bin_query_block(Q, G, k), nch = (G + BIN_CHUNK - 1) / BIN_CHUNK, cand_ld = bin_cand_ld(G, k);
+    for (i64 q0 = 0; q0 < Q; q0 += qb) {
+        const i64 qn = Q - q0 < qb ? Q - q0 : qb;
+        const RankFilter fb = filter ? filter_from(fall, q0) : RankFilter{};
+        const RankFilter* f = filter ? &fb : nullptr;
+        float* ov = out_val + q0 * k;
+        i64* oi = (i64*)out_idx + q0 * k;
+        BinAsymScanArgs b{};
+        b.s.codes = (const unsigned*)codes; b.s.G = G; b.s.ld = ld; b.s.Q = (int)qn; b.s.dim = dim; b.s.nch = (int)nch;
+        b.s.k = fused ? k : SMALL_K; b.s.idx_offset = idx_offset;
+        b.s.cand_val = w.cand_val; b.s.cand_idx = w.cand_idx; b.s.cand_ld = cand_ld; b.s.flt = fb;
+        b.aq = asym_queries(w, dim); b.aq0 = (int)q0; b.S = ld < BIN_SLICE ? ld : BIN_SLICE;
+        if (int e = f ? dispatch_asym_fused<true>(b, st) : dispatch_asym_fused<false>(b, st)) return e;
+        if (!fused) {
+            BinRescanArgs r{};
+            r.codes = b.s.codes; r.G = G; r.ld = ld; r.dim = dim; r.aq = b.aq; r.aq0 = b.aq0;
+            r.idx_offset = idx_offset; r.cand_ld = cand_ld; r.cand_val = w.cand_val; r.cand_idx = w.cand_idx; r.flt = fb;
+            if (int e = bin_saturated_route<true>(r, qn, nch, k, f, ov, oi, w.satlist, w.satcount, w.topk, w.topk_bytes, st)) return e;
+        }
         if (int e = topk_select(w.cand_val, w.cand_idx, qn, cand_ld, cand_ld, k, 0, ov, oi, w.topk, w.topk_bytes, st, nullptr, f)) return e;
     }
     return OK;

@@ -139,6 +139,8 @@ enum {
     MI355_RANK_PATH_I8_GEMV = 8,        /* k_cos_gemv_i8: Q <= 4 */
     MI355_RANK_PATH_PQ = 9,             /* k_pq_scan / k_pq_scores: the table scan over product-quantised rows (mi355_pq_search) */
     MI355_RANK_PATH_BINARY = 10,        /* k_bin_scan: the popcount scan over sign-bit rows (mi355_binary_search) */
+    MI355_RANK_PATH_BINARY_ASYM = 11,   /* k_bin_asym_scan: int8 query codes against sign-bit rows on the i8 MFMA
+                                           (mi355_binary_asym_search) */
     MI355_RANK_PATH_FUSED = 0x100,
     MI355_RANK_PATH_BITONIC = 0x200
 };
@@ -783,6 +785,45 @@ int mi355_binary_distances(const float* queries, int64_t Q, int dim, float eps, 
 int mi355_binary_search(const float* queries, int64_t Q, int dim, float eps, const float* center, const void* codes, int64_t G, int k,
                         int64_t idx_offset, const mi355_rank_filter* filter, float* out_val, int64_t* out_idx, void* workspace,
                         size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------ binary gallery, asymmetric search: an int8 query against
+ * the sign bits.  The symmetric search above cuts the query down to sign bits too, so every element of it counts the same,
+ * whether it lies far from the centre or right on it, and a pair can take dim + 1 score values only.  Here the gallery stays
+ * what it is - the codes of mi355_binary_encode, searchable without re-encoding - and the query keeps 8 bits per element.
+ * "fp32" = one IEEE rounding per named operation; everything after the quantiser is integer arithmetic and one fp32 division,
+ * so this block is bit for bit too.
+ * Query side, per call: n = the fp32 row mi355_l2_normalize_rows writes for the query (the same row_inv_norm and the same
+ * vec rule as the encoder).  r_j = n_j - center_j in fp32 (centre NULL: zeros).  amax = max |r_j| over j < dim.  u = the
+ * int8 row quantiser of the int8 gallery block applied to r: inv = 127 / amax, u_j = clamp(rintf(r_j * inv), -127, 127)
+ * (round-half-even).  A NaN in r, or a non-finite amax, makes a NaN query (codes 0).  amax < 1e-30 makes every code 0.
+ * L1 = sum |u_j| <= 127 * 65536 < 2^23.
+ * Distance m(q, g) = sum over j of |u_j| * [(u_j > 0 and bit_j(g) == 0) or (u_j < 0 and bit_j(g) == 1)]: a Hamming distance
+ * weighted by the query's magnitudes, an integer in [0, L1].  With s_j = 2 bit_j - 1: L1 - 2 m = sum u_j s_j.  With P = the sum
+ * of u_j over the set bits of g and Upos = the sum of the positive u_j: m = Upos - P.  Any summation order gives the same
+ * integer.
+ * Score = float(L1 - 2 m) / float(L1): both conversions exact (|L1 - 2 m| < 2^24), one IEEE fp32 division.  L1 == 0 scores
+ * 0.0f against every row.  A NaN query scores NaN against every row; its row of mi355_binary_asym_distances is -1.
+ * Order, ties, pads, filters: as mi355_binary_search - lower m first, then the lower row.  Distinct m give distinct scores
+ * (the exact quotients of two m differ by at least 2 / L1 > 2^-22 and lie in [-1, 1], where an fp32 rounding moves a value by
+ * at most 2^-25), so the order by score IS the order by m and the selection runs on the integer key (m, row).
+ * A score depends on the query row, the centre and the code row alone - not on Q, G, k, the filter, the path or the stream.
+ * The scan: one workgroup per (chunk of 256 rows, block of 64 queries).  The chunk's words pass through LDS; per 32
+ * dimensions a lane expands the bits of its rows to bytes of 0 / 1 and v_mfma_i32_32x32x32_i8 sums them against the queries'
+ * codes (P, exact in int32).  The endings and the k > 8 route are those of mi355_binary_search: MI355_RANK_PATH_BINARY_ASYM |
+ * FUSED for k <= 8, | BITONIC for 8 < k <= 1024 (8 rows per chunk, the saturated chunks scored again by the same contract).
+ * No atomics: one writer per output slot.
+ * Arguments and their checks as mi355_binary_distances / mi355_binary_search; the workspace of both is
+ * mi355_binary_asym_search_workspace_bytes (k = 0: distances only; 0 for a shape the entry would reject, and for Q = 0).
+ * mi355_binary_asym_query_codes writes what the search makes of the queries: codes int8 [Q][dim] in plain order, l1 int32 [Q],
+ * nanflag int32 [Q] (1: a NaN query); it needs no workspace.  dist: device int32 [Q][G]. */
+size_t mi355_binary_asym_search_workspace_bytes(int64_t Q, int64_t G, int dim, int k);
+int mi355_binary_asym_query_codes(const float* queries, int64_t Q, int dim, float eps, const float* center, int8_t* codes, int32_t* l1,
+                                  int32_t* nanflag, void* stream);
+int mi355_binary_asym_distances(const float* queries, int64_t Q, int dim, float eps, const float* center, const void* codes, int64_t G,
+                                int32_t* dist, void* workspace, size_t workspace_bytes, void* stream);
+int mi355_binary_asym_search(const float* queries, int64_t Q, int dim, float eps, const float* center, const void* codes, int64_t G, int k,
+                             int64_t idx_offset, const mi355_rank_filter* filter, float* out_val, int64_t* out_idx, void* workspace,
+                             size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ graph search: a beam walk over neighbour lists
  * A best-first search over a graph on the rows of a resident gallery.  The result is approximate against the exhaustive

@@ -3,7 +3,10 @@ galleries it has to be weighed against - fp16 ``Gallery``, ``Int8Gallery`` and `
 rows and queries, in the same run.  The variants run in alternation in one process, each rep timed with HIP events around
 ``--calls`` back-to-back searches; the median of the reps is reported, one JSON line per cell: the plain searches at k, the
 shortlist alone (the first stage of a refined search: k = ``--shortlist``), every ``refine=`` variant at that shortlist
-(rescored against the fp16 rows), and recall@k of each against the fp32 gallery's search.
+(rescored against the fp16 rows), and recall@k of each against the fp32 gallery's search.  The asymmetric search of the same
+binary codes (``asymmetric=True``: int8 query codes against the bits) runs in the same alternation - plain, shortlist, refined,
+recall plain and refined - with its ratios against the symmetric search and against int8 (``binary_asym_*``; above 1: the
+asymmetric search is the faster one).
 
     python tools/bench_binary.py [--rows clusters] [--G 100000,1000000] [--Q 1,256] [--k 3] [--shortlist 100] [--M 96]
                                  [--train-rows 100000] [--iters 10] [--reps 9] [--calls 5] [--out profiles/binary_bench.txt]
@@ -111,6 +114,10 @@ def main():
                         variants[name] = lambda g=g: g.search(q, k)
                         variants[f"{name}_shortlist"] = lambda g=g: g.search(q, R)
                         variants[f"{name}_refined"] = lambda g=g: g.search(q, k, refine=g16, shortlist=R)
+                    # the asymmetric search over the same codes: int8 query codes against the bits on the i8 MFMA
+                    variants["binary_asym"] = lambda: bg.search(q, k, asymmetric=True)
+                    variants["binary_asym_shortlist"] = lambda: bg.search(q, R, asymmetric=True)
+                    variants["binary_asym_refined"] = lambda: bg.search(q, k, refine=g16, shortlist=R, asymmetric=True)
                     for fn in variants.values():         # warm-up (the first calls of a process run slower)
                         for _ in range(3):
                             fn()
@@ -130,8 +137,14 @@ def main():
                     for name, ms in med.items():
                         out[f"{name}_ms"] = round(ms, 4)
                     want = g32.search(q, k)[1]
-                    for name in ("fp16",) + tuple(n for g in first for n in (g, f"{g}_refined")):
+                    for name in ("fp16",) + tuple(n for g in first for n in (g, f"{g}_refined")) + ("binary_asym", "binary_asym_refined"):
                         out[f"{name}_recall_at_{k}"] = round(M.rank._recall(variants[name]()[1], want, k)[0], 4)
+                    # each ratio: how many times faster the asymmetric search is than the other (above 1: faster)
+                    out["binary_asym_vs_binary"] = round(med["binary"] / med["binary_asym"], 3)
+                    out["binary_asym_vs_int8"] = round(med["int8"] / med["binary_asym"], 3)
+                    out["binary_asym_shortlist_vs_binary_shortlist"] = round(med["binary_shortlist"] / med["binary_asym_shortlist"], 3)
+                    out["binary_asym_refined_vs_binary_refined"] = round(med["binary_refined"] / med["binary_asym_refined"], 3)
+                    out["binary_asym_refined_vs_int8_refined"] = round(med["int8_refined"] / med["binary_asym_refined"], 3)
                     for other in ("int8", f"pq{a.M}"):
                         out[f"binary_vs_{other}"] = round(med[other] / med["binary"], 3)
                         out[f"binary_refined_vs_{other}_refined"] = round(med[f"{other}_refined"] / med["binary_refined"], 3)
