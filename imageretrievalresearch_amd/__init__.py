@@ -46,6 +46,9 @@ def __getattr__(name):  # lazy: models/sharded import torch.nn / torch.distribut
     if name == "BinaryGallery":
         from .binary import BinaryGallery
         return BinaryGallery
+    if name == "FP4Gallery":
+        from .fp4 import FP4Gallery
+        return FP4Gallery
     if name == "IVFPQIndex":
         from .ivfpq import IVFPQIndex
         return IVFPQIndex

@@ -106,6 +106,16 @@ PROTOTYPES = {
     "mi355_range_i8_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int]),
     "mi355_cosine_range_i8": (C.c_int, [vp, C.c_int64, vp, vp, C.c_int64, C.c_int, C.c_float, C.c_double, C.c_int64,
                                         C.POINTER(RankFilter), vp, C.c_int64, C.POINTER(C.c_int64), vp, C.c_size_t, vp]),
+    "mi355_gallery_fp4_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
+    "mi355_gallery_to_fp4": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, C.c_float, vp, C.c_size_t, vp, vp]),
+    "mi355_rank_fp4_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int, C.c_int]),
+    "mi355_rank_topk_fp4": (C.c_int, [vp, C.c_int64, vp, vp, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_int64, vp, vp, vp,
+                                      C.c_size_t, vp]),
+    "mi355_rank_topk_fp4_filtered": (C.c_int, [vp, C.c_int64, vp, vp, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_int64,
+                                               C.POINTER(RankFilter), vp, vp, vp, C.c_size_t, vp]),
+    "mi355_range_fp4_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int]),
+    "mi355_cosine_range_fp4": (C.c_int, [vp, C.c_int64, vp, vp, C.c_int64, C.c_int, C.c_float, C.c_double, C.c_int64,
+                                         C.POINTER(RankFilter), vp, C.c_int64, C.POINTER(C.c_int64), vp, C.c_size_t, vp]),
     "mi355_rank_last_path": (C.c_int, []),
     "mi355_rank_round_split": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "mi355_rank_set_round_slots": (C.c_int, [C.c_int]),

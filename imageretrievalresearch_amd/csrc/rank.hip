@@ -1106,7 +1106,7 @@ static GalleryRows f32_rows(const float* gallery, int is_normalized) {
     return {gallery, is_normalized != 0, nullptr, 0, split_queries_bytes};
 }
 static int check_rows(const GalleryRows& g, const char* who) {
-    MI355_REQUIRE((((uintptr_t)g.f16 | (uintptr_t)g.i8) & 15) == 0, "%s: gallery buffer must be 16-byte aligned", who);
+    MI355_REQUIRE((((uintptr_t)g.f16 | (uintptr_t)g.i8 | (uintptr_t)g.fp4) & 15) == 0, "%s: gallery buffer must be 16-byte aligned", who);
     return OK;
 }
 // The normalised queries qn [Q][dim] (qs: scratch of g.planes_bytes(Q, dim)) against the rows of g with epilogue epi
@@ -1114,8 +1114,9 @@ template <class Epi>
 static int score_rows(const GalleryRows& g, const float* ginv, const float* qn, void* qs, i64 Q, i64 G, int dim, const Epi& epi,
                       hipStream_t st) {
     if (g.f16) return cos_gemm_f16(g.f16, g.ld, qn, qs, Q, G, dim, epi, st);
-    if constexpr (std::is_same_v<Epi, RangeArgs>) {      // int8 rows: the range search only
+    if constexpr (std::is_same_v<Epi, RangeArgs>) {      // int8 and fp4 rows: the range search only
         if (g.i8) return cos_gemm_i8(g.i8, g.scales, g.ld, qn, qs, Q, G, dim, epi, st);
+        if (g.fp4) return cos_gemm_fp4(g.fp4, g.scales, g.ld, qn, qs, Q, G, dim, epi, st);
     }
     return cos_gemm(qn, (bf16_t*)qs, g.f32, ginv, Q, G, dim, epi, st);
 }
@@ -1176,7 +1177,8 @@ int cosine_range(const float* queries, i64 Q, const GalleryRows& g, i64 G, int d
                           keep_all ? 1 : 0};
         {
             RoctxRange range(keep_all ? "ranks/positives" : g.f16 ? "range/cosine gemm (fp16 gallery) + hits"
-                             : g.i8 ? "range/cosine gemm (int8 gallery) + hits" : "range/cosine gemm + hits");
+                             : g.i8 ? "range/cosine gemm (int8 gallery) + hits"
+                             : g.fp4 ? "range/cosine gemm (fp4 gallery) + hits" : "range/cosine gemm + hits");
             if (int e = score_rows(g, ginv, w.w.qn + q0 * dim, w.w.qs, qn, G, dim, a, st)) return e;
         }
         unsigned long long n = 0;

@@ -1097,17 +1097,18 @@ i64 ranks_query_block(i64 Q, i64 G, i64 query_block);
 
 
 // ---- the searches without a top-k (ROC histogram, range, ranks) exist once for both kinds of gallery rows (rank.hip)
-// The gallery as a search reads it: fp32 rows [G][dim], the fp16 rows of mi355_gallery_to_f16, or the int8 codes and scales
-// of mi355_gallery_to_i8
+// The gallery as a search reads it: fp32 rows [G][dim], the fp16 rows of mi355_gallery_to_f16, the int8 codes and scales
+// of mi355_gallery_to_i8, or the fp4 codes and multipliers of mi355_gallery_to_fp4
 struct GalleryRows {
     const float* f32;           // fp32 rows, or null
     bool unit;                  // fp32 rows: unit length already (no 1 / |row| pass); fp16 and int8 rows always are
     const void* f16;            // fp16 rows [G][ld], or null
-    int ld;                     // the padded length of fp16 / int8 rows
+    int ld;                     // the padded length of fp16 / int8 rows, the bytes of an fp4 row
     size_t (*planes_bytes)(i64, int);   // bytes of the operand the GEMM reads for (queries of one call, dim)
     const void* i8 = nullptr;   // int8 codes [G][ld], or null
-    const float* scales = nullptr;      // their scales [G]
-    const void* rows() const { return i8 ? i8 : f16 ? f16 : (const void*)f32; }
+    const float* scales = nullptr;      // their scales [G] (fp4 rows: their multipliers)
+    const void* fp4 = nullptr;  // packed e2m1 codes [G][ld] of mi355_gallery_to_fp4, or null
+    const void* rows() const { return fp4 ? fp4 : i8 ? i8 : f16 ? f16 : (const void*)f32; }
 };
 // One GEMM call over fp16 rows: the normalised queries qn [Q][dim] into their fp16 planes qs, then RowsGemm<F16Rows> with epi;
 // sets the rank path (rank_f16.hip; instantiated there for the epilogues of the three searches below)
@@ -1118,6 +1119,11 @@ int cos_gemm_f16(const void* rows, int ld, const float* qn, void* qs, i64 Q, i64
 template <class Epi>
 int cos_gemm_i8(const void* codes, const float* scales, int ld, const float* qn, void* qs, i64 Q, i64 G, int dim, const Epi& epi,
                 hipStream_t st);
+// The same over fp4 rows: the queries' two e2m1 planes and s_q into qs, then RowsGemm<Fp4Rows> with epi (rank_fp4.hip;
+// instantiated there for the range epilogue)
+template <class Epi>
+int cos_gemm_fp4(const void* codes, const float* mults, int ld, const float* qn, void* qs, i64 Q, i64 G, int dim, const Epi& epi,
+                 hipStream_t st);
 // mi355_roc_pairs_hist[_f16] under the name who; need: the entry's workspace size
 int roc_pairs_hist(const float* queries, i64 Q, const GalleryRows& g, i64 G, int dim, float eps, const int64_t* query_labels,
                    const int64_t* gallery_labels, const int64_t* exclude, i64 idx_offset, const double* thresholds,

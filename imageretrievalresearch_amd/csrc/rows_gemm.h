@@ -1,5 +1,6 @@
-// Resident rows stored as 128-byte segments (rank_f16.hip: fp16 rows, rank_i8.hip: int8 codes): the one DMA-ring loop of their
-// cosine GEMMs, its family for the tiled launcher and the one driver of their top-k searches.  gfx950 only.
+// Resident rows stored as 128-byte segments (rank_f16.hip: fp16 rows, rank_i8.hip: int8 codes, rank_fp4.hip: packed e2m1
+// codes): the one DMA-ring loop of their cosine GEMMs, its family for the tiled launcher and the one driver of their top-k
+// searches.  gfx950 only.
 #pragma once
 #include "rank_common.h"
 
@@ -143,7 +144,7 @@ struct RowsGemm {
     }
 };
 
-// mi355_rank_topk_{f16,i8} and, with filter, their _filtered entries: checks its arguments under the name who.  The row kind R
+// mi355_rank_topk_{f16,i8,fp4} and, with filter, their _filtered entries: checks its arguments under the name who.  The row kind R
 // supplies ld(dim), planes_bytes, MAX_DIM (0: no cap), SCALED (rows come with scales), gemv(Q, ld) (whether Q queries take
 // the GEMV), GEMV_PLANES (its GEMV reads the queries' planes), gemv_launch<NQ>, cos_gemm, its roctx range names and PATH_GEMV.
 template <class R>

@@ -152,8 +152,8 @@ class _Rows:
 
     def c_args(self):
         """The gallery arguments every search entry takes after (queries, Q): fp16 and int8 rows are normalised by their
-        layout, int8 codes travel with their scales."""
-        if self.dtype == torch.int8:
+        layout, int8 codes travel with their scales, packed fp4 codes (uint8) with their multipliers."""
+        if self.dtype in (torch.int8, torch.uint8):
             return (self.buf.data_ptr(), self.scales.data_ptr(), self.rows, self.dim)
         norm = () if self.dtype == torch.float16 else (int(self.normalized),)
         return (self.buf.data_ptr(), self.rows, self.dim) + norm
@@ -174,6 +174,9 @@ _ENTRIES = {
     # the int8 rows of an Int8Gallery (quantized.py): top-k and range search only
     torch.int8: {"topk": ("mi355_rank_topk_i8", "mi355_rank_topk_i8_filtered", "mi355_rank_i8_workspace_bytes"),
                  "range": ("mi355_cosine_range_i8", "mi355_range_i8_workspace_bytes")},
+    # the packed e2m1 rows of an FP4Gallery (fp4.py), two codes per uint8: the same two searches
+    torch.uint8: {"topk": ("mi355_rank_topk_fp4", "mi355_rank_topk_fp4_filtered", "mi355_rank_fp4_workspace_bytes"),
+                  "range": ("mi355_cosine_range_fp4", "mi355_range_fp4_workspace_bytes")},
 }
 
 

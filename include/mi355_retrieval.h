@@ -141,6 +141,8 @@ enum {
     MI355_RANK_PATH_BINARY = 10,        /* k_bin_scan: the popcount scan over sign-bit rows (mi355_binary_search) */
     MI355_RANK_PATH_BINARY_ASYM = 11,   /* k_bin_asym_scan: int8 query codes against sign-bit rows on the i8 MFMA
                                            (mi355_binary_asym_search) */
+    MI355_RANK_PATH_FP4_GEMM = 12,      /* k_cos_gemm_fp4 */
+    MI355_RANK_PATH_FP4_GEMV = 13,      /* k_cos_gemv_fp4: Q <= 4 */
     MI355_RANK_PATH_FUSED = 0x100,
     MI355_RANK_PATH_BITONIC = 0x200
 };
@@ -261,6 +263,57 @@ size_t mi355_range_i8_workspace_bytes(int64_t Q, int64_t G, int dim);
 int mi355_cosine_range_i8(const float* queries, int64_t Q, const void* codes, const float* scales, int64_t G, int dim, float eps,
                           double threshold, int64_t idx_offset, const mi355_rank_filter* filter, void* candidates, int64_t capacity,
                           int64_t* nnz, void* workspace, size_t workspace_bytes, void* stream);
+
+/* 4-bit resident gallery (e2m1 codes, two per byte, and one fp32 multiplier per row: half the bytes of int8 rows), searched on the
+ * block-scaled fp4 matrix instruction of gfx950.  Below, "fp32" means one IEEE rounding per named operation.
+ * e2m1: a code is 4 bits, bit 3 the sign, bits 0..2 the index m of the magnitude in {0, 0.5, 1, 1.5, 2, 3, 4, 6} (the OCP
+ * encoding).  e2m1(a) of an fp32 a rounds |a| to the nearest magnitude, a tie to the even index:
+ *     m = (|a| > 0.25) + (|a| >= 0.75) + (|a| > 1.25) + (|a| >= 1.75) + (|a| > 2.5) + (|a| >= 3.5) + (|a| > 5)
+ * (so 0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4, and every |a| >= 6 -> 6); the sign bit is set when
+ * a < 0 and m != 0: there is no negative zero, a zero is the code 0.  value(code) is the signed magnitude.
+ * Packing: dimension 2j is the low nibble of byte j of a row, dimension 2j+1 the high nibble; row r at byte r * ld, ld =
+ * ceil(dim / 2) rounded up to a multiple of 128; every nibble from dim on is 0.
+ * Row quantiser: n = the fp32 row mi355_l2_normalize_rows writes for x, bit for bit (rows_are_normalized != 0: n = x as it is);
+ * amax = max_i |n_i|.
+ *   - any n_i NaN, or amax not finite: mult = NaN, every code 0;
+ *   - else amax < 1e-30f: mult = 0, every code 0;
+ *   - else inv = 6.0f / amax (fp32 division), a_i = n_i * inv (fp32), code_i = e2m1(a_i); n2 = sum_i (2 value(code_i))^2, an
+ *     exact integer (<= 144 * dim < 2^24); mult = 1.0f / sqrtf(0.25f * (float)n2): the product is exact, the square root and the
+ *     division are fp32, correctly rounded (n2 = 0 cannot happen here; it would give mult = 0).  mult is 1 / |value(codes)|: the
+ *     decoded row value(code_i) * mult has unit length, whatever the quantiser's own scale was.
+ * mults: fp32 [G] beside the codes.  Both are appendable: converting n rows to codes + r * ld, mults + r writes rows r .. r+n-1.
+ * codes must be 16-byte aligned; dim <= 65536.  mi355_gallery_fp4_bytes(G, dim) = G * ld; a row costs ld + 4 bytes.
+ * Query planes, made per call from qn = l2_normalize_rows(q), amax_q = max_i |qn_i| (NaN / zero cases as the row quantiser: s_q =
+ * NaN or 0, both planes 0):
+ *     s_q = amax_q / 6.0f;  inv_q = 6.0f / amax_q                                 (two fp32 divisions)
+ *     hi_i = e2m1(qn_i * inv_q)                                                   (fp32 product)
+ *     r_i = fmaf(-value(hi_i), s_q, qn_i) / s_q                                   (one fused multiply-add, one fp32 division)
+ *     lo_i = e2m1(4.0f * r_i)                                                     (exact product; |r_i| <= 1 up to its two roundings:
+ *                                                                                  |value(lo_i)| <= 4)
+ * Score of query q against row g with codes c and multiplier mult_g: acc_hi = sum_i value(hi_i) value(c_i), acc_lo = sum_i
+ * value(lo_i) value(c_i).  Every product is a multiple of 0.25 of magnitude <= 36, so every partial sum in any order is a
+ * multiple of 0.25 below 36 * 65536 = 2^24 * 0.140625: exact in fp32.  t = fmaf(acc_lo, 0.25f, acc_hi); score = (t * s_q) *
+ * mult_g, two fp32 multiplies in that order.  A NaN row scores NaN (it ranks first, as in mi355_rank_topk), a zero row 0, a NaN
+ * query NaN everywhere.  The sums are exact, so EVERY path returns these bits for a (query, row) pair: the GEMV (Q <= 4, integer
+ * dot products of the codes doubled), the tiled GEMM with 64- and 128-query tiles in its main and its tail launch, the fused
+ * selection and the score slab, the filtered and the unfiltered search and the range search.  Order, ties, NaN and pads: the
+ * selection of mi355_rank_topk.
+ * The gallery argument of every entry is the pair (codes, mults).  Arguments are checked as for the _i8 entries (null, shape, k,
+ * alignment, workspace, dim <= 65536).  workspace: mi355_rank_fp4_workspace_bytes(Q, G, dim, k) (both top-k entries),
+ * mi355_range_fp4_workspace_bytes(Q, G, dim); mi355_cosine_range_fp4 is mi355_cosine_range_i8 over fp4 rows. */
+size_t mi355_gallery_fp4_bytes(int64_t G, int dim);
+int mi355_gallery_to_fp4(const float* rows, int64_t G, int dim, int rows_are_normalized, float eps, void* codes, size_t codes_bytes,
+                         float* mults, void* stream);
+size_t mi355_rank_fp4_workspace_bytes(int64_t Q, int64_t G, int dim, int k);
+int mi355_rank_topk_fp4(const float* queries, int64_t Q, const void* codes, const float* mults, int64_t G, int dim, int k, float eps,
+                        int64_t idx_offset, float* out_val, int64_t* out_idx, void* workspace, size_t workspace_bytes, void* stream);
+int mi355_rank_topk_fp4_filtered(const float* queries, int64_t Q, const void* codes, const float* mults, int64_t G, int dim, int k,
+                                 float eps, int64_t idx_offset, const mi355_rank_filter* filter, float* out_val, int64_t* out_idx,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+size_t mi355_range_fp4_workspace_bytes(int64_t Q, int64_t G, int dim);
+int mi355_cosine_range_fp4(const float* queries, int64_t Q, const void* codes, const float* mults, int64_t G, int dim, float eps,
+                           double threshold, int64_t idx_offset, const mi355_rank_filter* filter, void* candidates, int64_t capacity,
+                           int64_t* nnz, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Full-gallery ranks: the 1-based rank of every POSITIVE of every query among the query's eligible rows, without a score slab
  * or a sort of the gallery.  Eligible for query q: every gallery row but exclude[q] - idx_offset (exclude may be NULL;
