@@ -61,6 +61,9 @@ def __getattr__(name):  # lazy: models/sharded import torch.nn / torch.distribut
     if name in ("GraphIndex", "merged_graph"):
         from . import graph
         return getattr(graph, name)
+    if name in ("DiffusionIndex", "diffusion_rerank"):
+        from . import diffusion
+        return getattr(diffusion, name)
     if name == "ShardedGallery":
         from .sharded import ShardedGallery
         return ShardedGallery

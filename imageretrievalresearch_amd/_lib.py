@@ -131,6 +131,10 @@ PROTOTYPES = {
                                     vp, vp, vp, C.c_int64, vp]),
     "mi355_kr_score": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int64, vp, vp, vp, C.c_int64, C.c_int64, vp, vp, C.c_int,
                                  C.c_float, vp, vp]),
+    "mi355_diffusion_graph": (C.c_int, [vp, vp, C.c_int64, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "mi355_diffusion_source": (C.c_int, [vp, vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "mi355_diffusion_lds_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "mi355_diffusion_solve": (C.c_int, [vp, vp, C.c_int64, C.c_int, vp, vp, C.c_int64, C.c_int, C.c_float, C.c_int, vp, vp, vp]),
     "mi355_moments_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "mi355_embedding_moments": (C.c_int, [vp, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp,
                                           C.c_size_t, vp]),

@@ -787,7 +787,36 @@ class _DensityClustered:
         return _cl.connected_components(self, threshold, eps=self.eps, **kw)
 
 
-class Gallery(_RowStore, _GraphIndexed, _DensityClustered):
+class _Diffused:
+    """``Gallery.diffusion_index`` and ``Gallery.diffuse`` (diffusion.py).  They live in a base of ``Gallery`` for the reason
+    ``_GraphIndexed`` does: ``DiffusionIndex`` is exported lazily and the side-stream case is
+    tests/test_diffusion_streams_gpu.py, not a row of the stream table, which lists what ``Gallery`` itself defines."""
+
+    def diffusion_index(self, kd: int = 20, gamma: int = 3):
+        """The ``DiffusionIndex`` of the resident rows for (kd, gamma): the kNN graph and the symmetric normalised affinity rows
+        of its mutual edges (``nbytes`` tells its size).  Cached until ``add``."""
+        from . import diffusion as _df
+        key = _df.index_params(self.rows, kd, gamma)
+        if key not in self._diffusion:
+            self._diffusion[key] = _df.DiffusionIndex(self, *key)
+        return self._diffusion[key]
+
+    def diffuse(self, queries: torch.Tensor, k: int, *, kd: int = 20, kq: int = 10, alpha: float = 0.99, gamma: int = 3,
+                iters: int = 20, shortlist: int | None = None, exclude: torch.Tensor | None = None, idx_offset: int = 0,
+                stats: bool = False):
+        """Diffusion re-ranking (Iscen et al., CVPR 2017; truncated to the shortlist, see diffusion.py): ``search(queries,
+        shortlist)``, then ``(I - alpha S_L) f = y`` by at most ``iters`` conjugate-gradient iterations on the part of the
+        gallery's mutual kNN graph (``kd`` neighbours, affinity ``max(score, 0)^gamma``) inside the shortlist, ``y`` the
+        affinities of the first ``kq`` shortlist rows.  Returns the top-k of the shortlist by descending f as (values (Q, k) fp32,
+        indices (Q, k) int64), ties to the earlier shortlist position, pads (-inf, -1) last; with ``stats=True`` also the
+        iterations done per query (Q,) int32.  ``shortlist``: k <= shortlist <= min(rows, 1024), default min(rows, max(k, 200));
+        1 <= kq <= shortlist; alpha in (0, 1); gamma in [1, 8]; iters in [1, 64]; ``exclude`` / ``idx_offset`` as in ``search``."""
+        from . import diffusion as _df
+        return _df.diffuse(self, queries, k, kd=kd, kq=kq, alpha=alpha, gamma=gamma, iters=iters, shortlist=shortlist,
+                           exclude=exclude, idx_offset=idx_offset, stats=stats)
+
+
+class Gallery(_RowStore, _GraphIndexed, _DensityClustered, _Diffused):
     """Resident gallery: rows are L2-normalised once when added and stay in HBM (the gallery is *born* on the
     GPU that embedded it).  ``search`` is then one fused call per query batch instead of the reference's per-query cosine +
     topk pair.
@@ -811,6 +840,7 @@ class Gallery(_RowStore, _GraphIndexed, _DensityClustered):
         self._knn, self._rerank = {}, {}                         # per k1 / (k1, k2); dropped by add
         self._ivf = {}                                           # per (nlist, iters, seed); dropped by add
         self._graph = {}                                         # per (nentry, degree, iters, seed); dropped by add
+        self._diffusion = {}                                     # per (kd, gamma); dropped by add
 
     _BUFFERS = ("_buf",)
 
@@ -829,6 +859,7 @@ class Gallery(_RowStore, _GraphIndexed, _DensityClustered):
         self._knn, self._rerank = {}, {}
         self._ivf = {}
         self._graph = {}
+        self._diffusion = {}
         return self
 
     @property

@@ -221,17 +221,25 @@ class RerankIndex:
         return sum(t.numel() * t.element_size() for t in (self.nv, self.nn, self.tau)) + self.V.nbytes + self.V2.nbytes
 
 
-def _rerank_scores(gal: Gallery, q: torch.Tensor, k1: int, k2: int, lam: float, K: int, ex: torch.Tensor | None):
-    """The stages of ``rerank`` for checked arguments and LOCAL ``ex``: (s* (Q, K), shortlist values, shortlist rows, nv, nn).
-    The search always runs with more than 4 queries (a smaller batch is padded with copies of its last query), so that it
-    takes the same kernels - and gives the same bits - for every batch size."""
-    G, Q = gal.rows, q.shape[0]
-    index = gal.rerank_index(k1, k2)
+def _shortlist_search(gal: Gallery, q: torch.Tensor, n: int, ex: torch.Tensor | None):
+    """``gal.search(q, n, exclude=ex)`` (LOCAL ``ex``) run with more than 4 queries - a smaller batch is padded with copies of
+    its last query - so that it takes the same kernels, and gives the same bits, for every batch size.  Returns the (Q, n) values
+    and rows of the queries given."""
+    Q = q.shape[0]
     qq, exq = q, ex
     if Q < 5:
         qq = torch.cat([q, q[-1:].expand(5 - Q, -1)])
         exq = None if ex is None else torch.cat([ex, ex[-1:].expand(5 - Q)])
-    sv, si = gal.search(qq, max(K, k1), exclude=exq)
+    sv, si = gal.search(qq, n, exclude=exq)
+    return sv[:Q], si[:Q]
+
+
+def _rerank_scores(gal: Gallery, q: torch.Tensor, k1: int, k2: int, lam: float, K: int, ex: torch.Tensor | None):
+    """The stages of ``rerank`` for checked arguments and LOCAL ``ex``: (s* (Q, K), shortlist values, shortlist rows, nv, nn).
+    The search is ``_shortlist_search``: the same bits for every batch size."""
+    G, Q = gal.rows, q.shape[0]
+    index = gal.rerank_index(k1, k2)
+    sv, si = _shortlist_search(gal, q, max(K, k1), ex)
     nv, nn = sv[:Q, :k1].contiguous(), si[:Q, :k1].contiguous()
     sv, si = sv[:Q, :K].contiguous(), si[:Q, :K].contiguous()
     offsets, cols = _kr_sets(nn, index.nn, nv, index.tau)

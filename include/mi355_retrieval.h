@@ -419,6 +419,38 @@ int mi355_kr_score(const int64_t* query_offsets, const int32_t* query_cols, cons
                    int64_t G, const float* shortlist_vals, const int64_t* shortlist_idx, int K, float lam, float* out,
                    void* stream);
 
+/* Diffusion re-ranking (Iscen et al., CVPR 2017), truncated to a query's shortlist (Yang et al., AAAI 2019): conjugate gradients
+ * on the sub-graph of the gallery's kNN graph that the shortlist induces.  All arithmetic is fp32; no atomics on global memory;
+ * every sum has a fixed order that depends on its own row or query only.  Every argument is checked before any HIP call and every
+ * index a kernel reads is range-checked before it is used.
+ *
+ * mi355_diffusion_graph: the index rows of a kNN graph nn [G][kd] int64 / nv [G][kd] fp32 (the top-kd OTHER rows of every row
+ *   and their scores), 1 <= kd <= MI355_DIFFUSION_MAX_KD, kd < G, gamma an integer in [1, 8]:
+ *     a(i, t) = max(nv[i][t], 0)^gamma, by repeated multiplication left to right;
+ *     j = nn[i][t]; if i occurs in nn[j] (first at slot u): cols[i][t] = j and w(i, t) = min(a(i, t), a(j, u)); otherwise the slot
+ *     is empty, cols[i][t] = -1 and vals[i][t] = 0;
+ *     deg[i] = sum_t w(i, t) in slot order;  c_i = 1 / sqrt(deg[i]), 0 for deg[i] = 0;  vals[i][t] = w(i, t) * (c_i * c_j).
+ *   The entry of i -> j and that of j -> i hold the same bits.  Two launches; cols / vals [G][kd], deg [G].
+ * mi355_diffusion_source: y[q][p] = max(shortlist_vals[q][p], 0)^gamma for p < kq and shortlist_idx[q][p] >= 0, else 0
+ *   (shortlist_vals / shortlist_idx [Q][L], a search's output; 1 <= kq <= L <= 1024).
+ * mi355_diffusion_solve: for every query q, (I - alpha S_L) f = y[q] by conjugate gradients, S_L the entries of cols / vals whose
+ *   row and column are both in shortlist_idx[q] (LOCAL rows; a row outside [0, G) is a pad: isolated, f = -inf; a row that occurs
+ *   twice is reached at its earlier position).  f0 = 0, r0 = p0 = y, rs0 = r0 . r0; before each of at most `iters` iterations
+ *   the query stops when rs <= 2^-48 rs0 (so at once for y = 0) or when p . A p <= 0; otherwise step = rs / (p . A p),
+ *   f += step p, r -= step A p, rs' = r . r, p = r + (rs' / rs) p.  (S p)[i] is summed in slot order; a dot product per thread
+ *   in row order, then by xor shuffles in the wave, then over the waves in order: the bits of a query do not depend on the
+ *   batch.  One workgroup per query with mi355_diffusion_lds_bytes(L, kd) of LDS (0 for a shape outside 1 <= L <= 1024,
+ *   1 <= kd <= 32; at most 160 KiB).  f [Q][L]; iterations [Q] int32 (the iterations done) or NULL; 1 <= iters <= 64; alpha a
+ *   finite float in (0, 1); Q = 0 does nothing. */
+#define MI355_DIFFUSION_MAX_KD 32
+int mi355_diffusion_graph(const int64_t* nn, const float* nv, int64_t G, int kd, int gamma, int32_t* cols, float* vals, float* deg,
+                          void* stream);
+int mi355_diffusion_source(const float* shortlist_vals, const int64_t* shortlist_idx, int64_t Q, int L, int kq, int gamma, float* y,
+                           void* stream);
+size_t mi355_diffusion_lds_bytes(int L, int kd);
+int mi355_diffusion_solve(const int32_t* cols, const float* vals, int64_t G, int kd, const int64_t* shortlist_idx, const float* y,
+                          int64_t Q, int L, float alpha, int iters, float* f, int32_t* iterations, void* stream);
+
 /* PCA whitening, the fit's hot path: first and second raw moments of embedding rows in float64.
  *   sum[i]      = sum_r x[r][i]                 (device double [dim])
  *   outer[i][j] = sum_r x[r][i] * x[r][j]       (device double [dim][dim], row-major)
