@@ -847,6 +847,8 @@ struct LinkEpi {
 // Row norm of an fp32 row: one wave, float4 loads when vec (dim % 4 == 0 and 16-B aligned rows).  The lane-strided
 // summation order is part of the result: every row normalisation of the library (mi355_l2_normalize_rows, the queries
 // of every search, the fp16 gallery conversion) goes through this one function, so they give the same bits.
+// The norm of a row with a NaN element is NaN and stays NaN, so the whole row comes out NaN, as x / max(|x|, eps) does in
+// NumPy and torch (fmaxf(NaN, eps) is eps: it left such a row as x / eps around its NaN).  An Inf element: norm Inf, r = 0.
 __device__ __forceinline__ float row_inv_norm(const float* __restrict__ x, int dim, float eps, int vec, int lane) {
     float ss = 0.f;
     if (vec) {
@@ -859,7 +861,8 @@ __device__ __forceinline__ float row_inv_norm(const float* __restrict__ x, int d
         for (int i = lane; i < dim; i += 64) ss += x[i] * x[i];
     }
     ss = wave_sum(ss);
-    return 1.0f / fmaxf(sqrtf(ss), eps);
+    const float norm = sqrtf(ss);
+    return 1.0f / (norm < eps ? eps : norm);
 }
 
 // The fp32 row value x * r, then its rounding to fp16: two roundings, as l2_normalize_rows(x).half() does them (the fp16

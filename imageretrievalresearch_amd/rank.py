@@ -94,11 +94,18 @@ def synth_fill(n: int, seed: int, kind: int, device, offset: int = 0) -> torch.T
 
 
 def l2_normalize_rows(x: torch.Tensor, eps: float = _EPS, out: torch.Tensor | None = None) -> torch.Tensor:
+    """``x / max(|x|, eps)`` row by row, (rows, dim) fp32.  ``out``: where the rows go instead of a new tensor - float32,
+    contiguous, of ``x``'s shape and on its device (``out`` may be ``x`` itself); anything else raises ``MI355Error``."""
     x = _f32c(x, "x")
     if x.dim() != 2:
         raise MI355Error(f"l2_normalize_rows expects (rows, dim), got {tuple(x.shape)}")
     if out is None:
         out = torch.empty_like(x)
+    elif not torch.is_tensor(out):
+        raise MI355Error(f"l2_normalize_rows: out must be a contiguous float32 tensor, got {type(out).__name__}")
+    elif out.dtype != torch.float32 or out.shape != x.shape or out.device != x.device or not out.is_contiguous():
+        raise MI355Error(f"l2_normalize_rows: out must be a contiguous float32 {tuple(x.shape)} tensor on {x.device}, got "
+                         f"{out.dtype} {tuple(out.shape)} on {out.device}, strides {tuple(out.stride())}")
     with torch.cuda.device(x.device):
         check(lib().mi355_l2_normalize_rows(x.data_ptr(), out.data_ptr(), x.shape[0], x.shape[1], eps,
                                             stream_ptr(x.device)))

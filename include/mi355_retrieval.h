@@ -45,7 +45,8 @@ int mi355_synth_fill(float* out, int64_t n, uint64_t seed, int64_t offset, int k
  * fp32 throughout (exact-f32 MFMA); top-k sorted by descending score, ties -> lower index first; a NaN score orders as
  * the largest value (as torch.topk does), two NaNs tie. */
 
-/* out[r][:] = in[r][:] / max(||in[r]||_2, eps); in == out allowed.  rows x dim fp32 row-major. */
+/* out[r][:] = in[r][:] / max(||in[r]||_2, eps); in == out allowed.  rows x dim fp32 row-major.  A row with a NaN element comes
+ * out NaN in every element (its norm is NaN, not eps).  in and out may start at any 4-byte aligned address. */
 int mi355_l2_normalize_rows(const float* in, float* out, int64_t rows, int dim, float eps, void* stream);
 
 /* Bytes of scratch mi355_rank_topk needs for (Q, G, D, k). */
