@@ -9,6 +9,9 @@ for device memory, streams and torch.distributed only.
 from . import synth  # noqa: F401
 from ._lib import MI355Error, lib, LIB_PATH  # noqa: F401
 from . import models  # noqa: F401
+# models imports the submodule aggregate.py (model.forward_descriptors), which binds the MODULE to the package attribute
+# `aggregate`; the public name is the function, so it is bound over it here (the module: importlib.import_module(__name__ + ".aggregate"))
+from .aggregate import aggregate, rmac_regions  # noqa: F401
 from .preprocess import pack_images, resize_batch  # noqa: F401
 from .rank import (ContrastiveLoss, CosineEmbeddingLoss, CosineSimilarity, Gallery, PositiveRanks, PreparedGallery,  # noqa: F401
                    cos_sim_score_booster, cos_sim_score_with_threshold, cosine_range, cosine_scores, cosine_topk,
@@ -30,7 +33,8 @@ __all__ = ["Whitening", "Moments", "embedding_moments","create_model", "list_mod
            "KMeansResult", "assign_clusters", "update_centroids", "cluster_members", "spherical_kmeans", "contingency",
            "clustering_metrics", "clustering_metrics_from_table", "IVFIndex", "Int8Gallery"]
 # dbscan / connected_components / DBSCANResult are importable from here but, like the lazily exported indexes, are not in __all__:
-# the stream table (tests/stream_cases.py) enumerates __all__, and their side-stream case is tests/test_dbscan_streams_gpu.py
+# the stream table (tests/stream_cases.py) enumerates __all__, and their side-stream case is tests/test_dbscan_streams_gpu.py;
+# aggregate / rmac_regions (bound above) likewise: their side-stream case is tests/test_aggregate_streams_gpu.py
 
 
 def __getattr__(name):  # lazy: models/sharded import torch.nn / torch.distributed

@@ -135,6 +135,11 @@ PROTOTYPES = {
     "mi355_diffusion_source": (C.c_int, [vp, vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp, vp]),
     "mi355_diffusion_lds_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "mi355_diffusion_solve": (C.c_int, [vp, vp, C.c_int64, C.c_int, vp, vp, C.c_int64, C.c_int, C.c_float, C.c_int, vp, vp, vp]),
+    "mi355_aggregate_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
+    "mi355_aggregate_regions": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_float, vp, C.c_float,
+                                          C.c_int, C.c_int, C.c_float, vp, vp, C.c_size_t, vp]),
+    "mi355_aggregate_crow": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, C.c_size_t, vp]),
+    "mi355_aggregate_sum": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp]),
     "mi355_moments_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "mi355_embedding_moments": (C.c_int, [vp, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp,
                                           C.c_size_t, vp]),

@@ -29,6 +29,7 @@ import torch
 import torch.nn as nn
 
 from ._lib import MI355Error, check, lib, require_cuda, stream_ptr
+from .aggregate import _Descriptors
 
 _FAMILY = {
     "efficientnet_b3a": "efficientnet", "efficientnet_b3": "efficientnet",
@@ -172,7 +173,7 @@ def _new_handle(name: str, num_classes: int):
     return h
 
 
-class MI355Model(nn.Module):
+class MI355Model(nn.Module, _Descriptors):
     def __init__(self, model_name: str, num_classes: int = 1000, seed: int = 0):
         super().__init__()
         if model_name not in _FAMILY:

@@ -452,6 +452,44 @@ size_t mi355_diffusion_lds_bytes(int L, int kd);
 int mi355_diffusion_solve(const int32_t* cols, const float* vals, int64_t G, int kd, const int64_t* shortlist_idx, const float* y,
                           int64_t Q, int L, float alpha, int iters, float* f, int32_t* iterations, void* stream);
 
+/* Feature-map aggregation: how a backbone's last map becomes the descriptor (csrc/aggregate.hip).  SPoC / MAC / R-MAC (Tolias et
+ * al., ICLR 2016), GeM (Radenovic et al., TPAMI 2018) and CroW (Kalantidis et al., ECCV 2016).  fm is [B][C][H][W] fp32,
+ * contiguous, 4-byte aligned (a channel row of H*W floats need not be 16-byte aligned: the map is loaded as the flat array it is
+ * and handed to its channels through LDS).  1 <= H, W <= 64, C >= 1.  All arithmetic is fp32; every sum has a fixed order that
+ * depends on (C, H, W, the regions) alone, never on B or on where an image stands in the batch; no floating-point atomics.  Every
+ * argument is checked before any HIP call.  B = 0 does nothing.
+ *
+ * mi355_aggregate_regions: `regions` is a HOST array [R][4] of (y0, x0, h, w), h, w >= 1, inside the map, 1 <= R <= 64 (it
+ *   travels in the kernel arguments).  For image b, region r, channel c, over the region's values x:
+ *     MI355_AGG_MEAN: the sum divided by h*w;   MI355_AGG_MAX: the maximum, exact;
+ *     MI355_AGG_GEM:  t = max(x, eps_clamp), m = max t, g = m * (mean((t/m)^pc))^(1/pc) - no power of a value above 1 is ever
+ *       taken, so large activations and pc = 64 stay finite.  pc = p_channels[c] (DEVICE [C], clamped to [2^-10, 64] where it is
+ *       read) or, with p_channels NULL, the scalar p, 0 < p <= 64.  eps_clamp > 0.
+ *   Then, if normalize: v[b][r][:] /= max(|v[b][r][:]|_2, eps).  return_regions != 0: out [B][R][C] holds these vectors.  Otherwise
+ *   out [B][C] = sum_r v[b][r][:] in the order r = 0 .. R-1, divided again by max(its norm, eps) when normalize.
+ *   Two launches: one reads the map once - an image is split over workgroups by channel slab, every region of a channel is pooled
+ *   from the slab's copy in LDS - and leaves the pooled values and one partial sum of squares per (b, r, slab) in the workspace;
+ *   a small second one adds the partial sums in slab order, normalises, sums the regions and normalises again.
+ * mi355_aggregate_crow (alpha = beta = 2): X' = max(X, 0); S[h][w] = sum_c X'[c][h][w]; St = sqrt(S / sqrt(sum_hw S^2)), 0 when
+ *   that sum is 0; F[c] = sum_hw St[h][w] X'[c][h][w]; Q[c] = the share of positions with X[c] > 0; I[c] = log(sum_c' Q[c'] / Q[c])
+ *   for Q[c] > 0, else 0; out [B][C] = I * F, divided by max(its norm, eps) when normalize.  Four launches, two reads of the map.
+ * mi355_aggregate_sum: the second launch of mi355_aggregate_regions alone, for vectors a caller has transformed in between (the
+ *   R-MAC regional whitening): out [B][D] = sum_r vecs[b][r][:] (vecs [B][R][D]) in region order, normalised when normalize.
+ * mi355_aggregate_workspace_bytes(B, C, R): what either entry needs (mi355_aggregate_crow: with any R); 0 for B = 0 or a
+ *   shape outside the limits. */
+#define MI355_AGG_MEAN 0
+#define MI355_AGG_MAX 1
+#define MI355_AGG_GEM 2
+#define MI355_AGG_MAX_SIDE 64
+#define MI355_AGG_MAX_REGIONS 64
+size_t mi355_aggregate_workspace_bytes(int64_t B, int C, int R);
+int mi355_aggregate_regions(const float* fm, int64_t B, int C, int H, int W, const int32_t* regions, int R, int pool, float p,
+                            const float* p_channels, float eps_clamp, int normalize, int return_regions, float eps, float* out,
+                            void* workspace, size_t workspace_bytes, void* stream);
+int mi355_aggregate_crow(const float* fm, int64_t B, int C, int H, int W, int normalize, float eps, float* out, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int mi355_aggregate_sum(const float* vecs, int64_t B, int R, int D, int normalize, float eps, float* out, void* stream);
+
 /* PCA whitening, the fit's hot path: first and second raw moments of embedding rows in float64.
  *   sum[i]      = sum_r x[r][i]                 (device double [dim])
  *   outer[i][j] = sum_r x[r][i] * x[r][j]       (device double [dim][dim], row-major)
