@@ -490,6 +490,30 @@ int mi355_aggregate_crow(const float* fm, int64_t B, int C, int H, int W, int no
                          size_t workspace_bytes, void* stream);
 int mi355_aggregate_sum(const float* vecs, int64_t B, int R, int D, int normalize, float eps, float* out, void* stream);
 
+/* Regional MaxSim re-ranking (csrc/regional.hip): a query image of Rq regional vectors against candidate images of R regional
+ * vectors each (Razavian et al. 2016; Tolias et al., ICLR 2016, section 5; the "late interaction" of ColBERT).  Both sides are the
+ * fp16 codes of mi355_gallery_to_f16, one row per region: qcodes [Q][Rq][ld], gcodes [rows][R][ld], ld = dim rounded up to a
+ * multiple of 64 with zeros behind dim, 16-byte aligned.  1 <= Rq, R <= MI355_REGION_MAX_REGIONS, 1 <= dim <= 65536.  For query q
+ * and the row in slot p of its list:
+ *     s[i][j] = sum_d float(qcodes[q][i][d]) * float(gcodes[row][j][d])   (fp32 accumulation on v_mfma_f32_16x16x32_f16, the
+ *               k-steps in ascending d; every product of two fp16 values is exact in fp32)
+ *     m[i] = max_j s[i][j] over the R regions of the row, a[i] = the lowest j that attains it
+ *     out_scores[q][p] = sum_i w[i] * m[i], in fp32 in ascending i;  out_matches[q][p][i] = a[i]
+ *   w = weights[q] ([Q][Rq] fp32) or, with weights NULL, fp32(1) / fp32(Rq) for every i.  Rq and R are padded to the 16-row tile
+ *   inside the kernel: a pad region of the row never reaches the maximum and a pad region of the query adds nothing to the sum.
+ *   The bits of a pair depend on the query's codes, its weights and the row alone - not on Q, L, the slot, the other rows of the
+ *   list or whether idx was given.
+ * idx [Q][L] int64 LOCAL rows, 1 <= L <= 1024; a row may occur twice; a slot outside [0, rows) - the pad -1 or any other value -
+ *   is treated as a pad: no row is read, out_scores = -inf and out_matches = -1.  idx NULL: slot p is row p and L must be rows.
+ * out_scores [Q][L] fp32; out_matches [Q][L][Rq] int32 or NULL.  One workgroup per (query, slice of the list) keeps the query's
+ *   codes in mi355_region_scores_lds_bytes(Rq, dim) of LDS (0 for a shape outside the limits; at most 64 KiB): all of them where
+ *   they fit, otherwise one chunk of d at a time with the accumulators in registers.  A candidate's codes are read once.  Every
+ *   argument is checked before any HIP call; no atomics; no host sync; Q = 0 does nothing. */
+#define MI355_REGION_MAX_REGIONS 64
+size_t mi355_region_scores_lds_bytes(int Rq, int dim);
+int mi355_region_scores(const void* qcodes, int64_t Q, int Rq, const void* gcodes, int64_t rows, int R, int dim, int ld,
+                        const int64_t* idx, int64_t L, const float* weights, float* out_scores, int32_t* out_matches, void* stream);
+
 /* PCA whitening, the fit's hot path: first and second raw moments of embedding rows in float64.
  *   sum[i]      = sum_r x[r][i]                 (device double [dim])
  *   outer[i][j] = sum_r x[r][i] * x[r][j]       (device double [dim][dim], row-major)
