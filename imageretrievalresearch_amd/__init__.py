@@ -68,7 +68,10 @@ def __getattr__(name):  # lazy: models/sharded import torch.nn / torch.distribut
     if name in ("DiffusionIndex", "diffusion_rerank"):
         from . import diffusion
         return getattr(diffusion, name)
-    if name in ("RegionGallery", "maxsim"):                  # their side-stream case: tests/test_regional_streams_gpu.py
+    if name == "mmr_rerank":                                 # its side-stream case: tests/test_diversify_streams_gpu.py
+        from .diversify import mmr_rerank
+        return mmr_rerank
+    if name in ("RegionGallery", "maxsim"):                 # their side-stream case: tests/test_regional_streams_gpu.py
         from . import regional
         return getattr(regional, name)
     if name == "ShardedGallery":

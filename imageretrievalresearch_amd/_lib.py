@@ -142,6 +142,8 @@ PROTOTYPES = {
     "mi355_aggregate_sum": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp]),
     "mi355_region_scores_lds_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "mi355_region_scores": (C.c_int, [vp, C.c_int64, C.c_int, vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp, C.c_int64, vp, vp, vp, vp]),
+    "mi355_shortlist_gram": (C.c_int, [vp, C.c_int, C.c_int64, C.c_int64, C.c_int, vp, C.c_int64, C.c_int, vp, vp]),
+    "mi355_mmr_select": (C.c_int, [vp, vp, vp, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int64, vp, vp, vp, vp, vp]),
     "mi355_moments_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "mi355_embedding_moments": (C.c_int, [vp, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp,
                                           C.c_size_t, vp]),

@@ -823,7 +823,29 @@ class _Diffused:
                            exclude=exclude, idx_offset=idx_offset, stats=stats)
 
 
-class Gallery(_RowStore, _GraphIndexed, _DensityClustered, _Diffused):
+class _Diversified:
+    """``Gallery.diversify`` (diversify.py).  It lives in a base of ``Gallery`` for the reason ``_Diffused`` does: ``mmr_rerank``
+    is exported lazily and the side-stream case is tests/test_diversify_streams_gpu.py, not a row of the stream table, which lists
+    what ``Gallery`` itself defines."""
+
+    def diversify(self, queries: torch.Tensor, k: int, *, lam: float = 0.7, dedup=None, shortlist: int | None = None,
+                  exclude: torch.Tensor | None = None, idx_offset: int = 0, stats: bool = False, block: int | None = None):
+        """The k best *different* results (maximal marginal relevance, Carbonell and Goldstein 1998; see diversify.py):
+        ``search(queries, shortlist)``, the Gram matrix S of each shortlist's rows (their fp16 values on the f16 MFMA), then k
+        greedy picks: the eligible slot of greatest ``lam * score - (1 - lam) * m``, ``m`` the slot's largest S against the picks
+        so far, ties to the earlier slot.  With ``dedup=t`` a slot is ineligible once ``m >= t`` (near-duplicate suppression;
+        ``lam=1, dedup=t`` walks the plain order and keeps a row unless it is within t of a kept one).  Returns, in pick order,
+        (the picks' cosine scores (Q, k) fp32 - not monotone -, indices (Q, k) int64); when the eligible slots run out the rest is
+        (-inf, -1).  ``stats=True`` adds the MMR values at pick time (Q, k) fp32 and the picks per query (Q,) int32.
+        ``shortlist``: k <= shortlist <= min(rows, 1024), default min(rows, max(10 k, 100), 1024); lam in [0, 1]; ``block``: queries
+        whose Gram matrices are held at once (default: what fits 256 MiB; results do not depend on it); ``exclude`` / ``idx_offset``
+        as in ``search``.  ``lam=1`` without ``dedup`` is ``search(queries, shortlist)[:, :k]``."""
+        from . import diversify as _dv
+        return _dv.diversify(self, queries, k, lam=lam, dedup=dedup, shortlist=shortlist, exclude=exclude, idx_offset=idx_offset,
+                             stats=stats, block=block)
+
+
+class Gallery(_RowStore, _GraphIndexed, _DensityClustered, _Diffused, _Diversified):
     """Resident gallery: rows are L2-normalised once when added and stay in HBM (the gallery is *born* on the
     GPU that embedded it).  ``search`` is then one fused call per query batch instead of the reference's per-query cosine +
     topk pair.

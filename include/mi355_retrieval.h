@@ -514,6 +514,35 @@ size_t mi355_region_scores_lds_bytes(int Rq, int dim);
 int mi355_region_scores(const void* qcodes, int64_t Q, int Rq, const void* gcodes, int64_t rows, int R, int dim, int ld,
                         const int64_t* idx, int64_t L, const float* weights, float* out_scores, int32_t* out_matches, void* stream);
 
+/* Result diversification (csrc/diversify.hip): maximal marginal relevance (Carbonell and Goldstein, SIGIR 1998) and greedy
+ * near-duplicate suppression over a query's shortlist, in two stages.  Every argument is checked before any HIP call; no atomics;
+ * no host sync; Q = 0 does nothing.
+ *
+ * mi355_shortlist_gram: out[q][p][r] = the dot product of gallery rows idx[q][p] and idx[q][r] (idx [Q][L] int64 LOCAL rows,
+ *   1 <= L <= MI355_DIVERSIFY_MAX_SHORTLIST; out [Q][L][L] fp32).  rows / rows_dtype / ld / G as in mi355_rescore_candidates: fp32
+ *   rows (4-byte aligned, any ld >= dim) or fp16 rows (16-byte aligned, ld a multiple of 8), normalised by the caller; 1 <= dim <=
+ *   65536.  The operands are the rows' fp16 values - an fp16 row as it lies, an fp32 element rounded to fp16 (round-to-nearest-even)
+ *   on load - columns at or past dim are zero, and the sum is fp32 on v_mfma_f32_16x16x32_f16 with the k-steps in ascending column
+ *   order (every product of two fp16 values is exact in fp32).  An entry is 0 where either slot is a pad: -1, or any index outside
+ *   [0, G).  The diagonal is computed like any other entry.  An entry's bits depend on the unordered pair of rows alone - not on
+ *   L, the slot, the tile, the query or Q - and out[q] is bit-symmetric: only entries at or above the diagonal are computed, each
+ *   stored together with its mirror.  One workgroup per (query, pair of 64-slot tiles at or above the diagonal).
+ * mi355_mmr_select: greedy selection of k of the L slots of every query, entirely in fp32 without fused multiply-add.  rel / idx
+ *   [Q][L] are a search's output (idx < 0: a pad), gram [Q][L][L] that of mi355_shortlist_gram.  oml = fp32(1) - lam; m[p] = 0 and
+ *   nothing picked at the start.  For pick t = 0 .. k-1: slot p is eligible if it holds a row, is unpicked and, unless
+ *   dedup_or_nan is NaN, m[p] < dedup_or_nan; its value is v[p] = fp32(lam * rel[p]) - fp32(oml * m[p]), a NaN value counting as
+ *   -inf; the pick j is the eligible slot of greatest value, ties to the lower position; then m[p] = gram[q][j][p] wherever that
+ *   is greater than m[p].  out_val[q][t] = rel[j] (the cosine score: not monotone in t), out_idx[q][t] = idx[q][j] + idx_offset,
+ *   out_mmr[q][t] = v[j] (or NULL).  When no slot is eligible the remaining outputs are (-inf, -1, -inf); out_count[q] (or NULL)
+ *   is the number of picks.  1 <= k <= L <= MI355_DIVERSIFY_MAX_SHORTLIST; lam a finite float in [0, 1]; dedup_or_nan finite or
+ *   NaN.  lam = 1 without a threshold returns the first k slots that hold a row.  One workgroup of L threads (rounded up to
+ *   whole waves) per query: a slot's rel and m stay in registers. */
+#define MI355_DIVERSIFY_MAX_SHORTLIST 1024
+int mi355_shortlist_gram(const void* rows, int rows_dtype, int64_t ld, int64_t G, int dim, const int64_t* idx, int64_t Q, int L,
+                         float* out, void* stream);
+int mi355_mmr_select(const float* rel, const int64_t* idx, const float* gram, int64_t Q, int L, int k, float lam, float dedup_or_nan,
+                     int64_t idx_offset, float* out_val, int64_t* out_idx, float* out_mmr, int32_t* out_count, void* stream);
+
 /* PCA whitening, the fit's hot path: first and second raw moments of embedding rows in float64.
  *   sum[i]      = sum_r x[r][i]                 (device double [dim])
  *   outer[i][j] = sum_r x[r][i] * x[r][j]       (device double [dim][dim], row-major)
