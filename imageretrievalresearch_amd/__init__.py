@@ -74,6 +74,9 @@ def __getattr__(name):  # lazy: models/sharded import torch.nn / torch.distribut
     if name in ("RegionGallery", "maxsim"):                 # their side-stream case: tests/test_regional_streams_gpu.py
         from . import regional
         return getattr(regional, name)
+    if name in ("ScoreNorm", "adjusted_topk", "adjusted_scores", "neighbourhood_stats", "topn_stats"):
+        from . import scorenorm                              # their side-stream case: tests/test_scorenorm_streams_gpu.py
+        return getattr(scorenorm, name)
     if name == "ShardedGallery":
         from .sharded import ShardedGallery
         return ShardedGallery

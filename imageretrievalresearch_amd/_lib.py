@@ -69,6 +69,11 @@ class RankFilter(C.Structure):
     _fields_ = [("query_labels", vp), ("gallery_labels", vp), ("label_mode", C.c_int), ("exclude", vp)]
 
 
+class ScoreAdjust(C.Structure):
+    """mi355_score_adjust (include/mi355_retrieval.h): the four nullable coefficient vectors of the adjusted searches."""
+    _fields_ = [("aq", vp), ("bq", vp), ("ag", vp), ("bg", vp)]
+
+
 LABEL_ANY, LABEL_SAME, LABEL_DIFFERENT = 0, 1, 2
 DTYPE_F32, DTYPE_F16 = 0, 1
 
@@ -96,6 +101,17 @@ PROTOTYPES = {
                                            C.POINTER(RankFilter), vp, vp, vp, C.c_size_t, vp]),
     "mi355_rank_topk_f16_filtered": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_int64,
                                                C.POINTER(RankFilter), vp, vp, vp, C.c_size_t, vp]),
+    "mi355_rank_adjusted_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int, C.c_int]),
+    "mi355_rank_adjusted_f16_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int, C.c_int]),
+    "mi355_rank_topk_adjusted": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int64,
+                                           C.POINTER(ScoreAdjust), C.POINTER(RankFilter), C.c_int64, vp, vp, vp, C.c_size_t, vp]),
+    "mi355_rank_topk_adjusted_f16": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_int64,
+                                               C.POINTER(ScoreAdjust), C.POINTER(RankFilter), C.c_int64, vp, vp, vp, C.c_size_t, vp]),
+    "mi355_cosine_scores_adjusted": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_float, C.POINTER(ScoreAdjust),
+                                               C.c_int64, vp, vp, C.c_size_t, vp]),
+    "mi355_cosine_scores_adjusted_f16": (C.c_int, [vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_float, C.POINTER(ScoreAdjust),
+                                                   C.c_int64, vp, vp, C.c_size_t, vp]),
+    "mi355_topn_stats": (C.c_int, [vp, vp, C.c_int64, C.c_int, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp]),
     "mi355_gallery_i8_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "mi355_gallery_to_i8": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, C.c_float, vp, C.c_size_t, vp, vp]),
     "mi355_rank_i8_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int, C.c_int]),

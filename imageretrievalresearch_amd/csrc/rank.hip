@@ -1102,7 +1102,7 @@ static int rank_topk(const float* queries, i64 Q, const float* gallery, i64 G, i
 }
 
 // ---- the searches without a top-k, once for fp32 and fp16 rows (rank_common.h)
-static GalleryRows f32_rows(const float* gallery, int is_normalized) {
+GalleryRows f32_rows(const float* gallery, int is_normalized) {
     return {gallery, is_normalized != 0, nullptr, 0, split_queries_bytes};
 }
 static int check_rows(const GalleryRows& g, const char* who) {
@@ -1119,6 +1119,54 @@ static int score_rows(const GalleryRows& g, const float* ginv, const float* qn, 
         if (g.fp4) return cos_gemm_fp4(g.fp4, g.scales, g.ld, qn, qs, Q, G, dim, epi, st);
     }
     return cos_gemm(qn, (bf16_t*)qs, g.f32, ginv, Q, G, dim, epi, st);
+}
+
+// fn(the epilogue of one GEMM call of an adjusted search over the scratch w): with_topk_epi with the map in front of the
+// selection, or the adjusted slab
+template <class Fn>
+static int with_adjusted_epi(const RankWs& w, int k, const RankFilter* f, const ScoreAdjust& adj, Fn&& fn) {
+    if (!w.cand_val) return fn(AdjSlabEpi{w.S, adj});
+    if (f) return with_adjusted_select_epi<true>(k, w.cand_val, w.cand_idx, *f, adj, fn);
+    return with_adjusted_select_epi<false>(k, w.cand_val, w.cand_idx, RankFilter{}, adj, fn);
+}
+
+// The block loop is search_blocks' with the adjustment shifted beside the filter; the caller's query_block only shortens it
+int adjusted_search(const float* queries, i64 Q, const GalleryRows& g, i64 G, int dim, float eps, int k, i64 idx_offset,
+                    const ScoreAdjust& adj, const RankFilter* filt, i64 query_block_arg, float* out_val, i64* out_idx, void* workspace,
+                    size_t workspace_bytes, hipStream_t st, const char* who) {
+    const bool need_ginv = g.f32 && !g.unit;
+    const RankWs w = carve(workspace, Q, G, dim, k, g.planes_bytes, need_ginv, k > 0);
+    MI355_REQUIRE(workspace && workspace_bytes >= w.total, "%s: workspace %zu < %zu bytes", who, workspace_bytes, w.total);
+    const float* ginv = need_ginv ? w.ginv : nullptr;
+    if (int e = normalize_search(queries, Q, ginv ? g.f32 : nullptr, G, dim, eps, w, st)) return e;
+    const bool fused = fused_select(Q, G, k);
+    i64 qb = k > 0 ? query_block(Q, G, k) : (Q < 256 * 64 ? Q : 256 * 64);
+    if (query_block_arg > 0 && query_block_arg < qb) qb = query_block_arg;
+    const i64 rowlen = fused ? cdiv(G, RK_BN) * (i64)k : G;
+    for (i64 q0 = 0; q0 < Q; q0 += qb) {
+        const i64 qn = (Q - q0 < qb) ? Q - q0 : qb;
+        const ScoreAdjust ab = adjust_from(adj, q0);
+        if (k == 0) {
+            RoctxRange range("scorenorm/cosine gemm + adjusted slab");
+            if (int e = score_rows(g, ginv, w.qn + q0 * dim, w.qs, qn, G, dim, AdjSlabEpi{out_val + q0 * G, ab}, st)) return e;
+            continue;
+        }
+        const RankFilter fb = filt ? filter_from(*filt, q0) : RankFilter{};
+        const RankFilter* f = filt ? &fb : nullptr;
+        {
+            RoctxRange range(fused ? "scorenorm/cosine gemm + adjusted per-tile top-k" : "scorenorm/cosine gemm + adjusted slab");
+            if (int e = with_adjusted_epi(w, k, f, ab, [&](const auto& epi) {
+                    return score_rows(g, ginv, w.qn + q0 * dim, w.qs, qn, G, dim, epi, st);
+                }))
+                return e;
+        }
+        if (!fused && k > SMALL_K) set_rank_path(mi355_rank_last_path() | MI355_RANK_PATH_BITONIC);
+        RoctxRange range(fused ? "rank/merge candidates" : "rank/top-k");
+        if (int e = topk_select(fused ? w.cand_val : w.S, nullptr, qn, rowlen, rowlen, k, idx_offset, out_val + q0 * k, out_idx + q0 * k,
+                                w.topk, w.topk_bytes, st, w.cand_idx, f))
+            return e;
+    }
+    return OK;
 }
 
 int roc_pairs_hist(const float* queries, i64 Q, const GalleryRows& g, i64 G, int dim, float eps, const int64_t* query_labels,

@@ -162,6 +162,39 @@ struct TileCtx {
     int m0;
 };
 
+// ---- adjusted scores (mi355_rank_topk_adjusted, mi355_cosine_scores_adjusted; CSLS and cohort normalisation, scorenorm.hip):
+// the score s of pair (query q, gallery row g) becomes t = s * (aq[q] + ag[g]) - (bq[q] + bg[g]), every step rounded to fp32
+// and none fused, so t depends on s and the four coefficients alone.  A null vector counts as 0.  aq / bq point at the first
+// query of the call they are handed to (the host shifts them per query block, as it shifts the filter).
+struct NoAdjust {};
+struct ScoreAdjust {
+    const float* aq;            // [Q] or null
+    const float* bq;            // [Q] or null
+    const float* ag;            // [G] or null
+    const float* bg;            // [G] or null
+};
+__device__ __forceinline__ float adjusted_score(float s, float w, float c) {
+    float p = __fmul_rn(s, w);
+    asm volatile("" : "+v"(p));     // the rounded product in a register: -ffp-contract=fast must not fuse it into the subtraction
+    return __fsub_rn(p, c);
+}
+// aq or bq of a lane's query row in the MFMA layout: one accumulator element belongs to row urow in lanes 0-31 and to row
+// urow + 4 in lanes 32-63, urow the same in the whole wave.  Both rows are read through wave-uniform addresses, so the loads are
+// scalar and no vector register holds a coefficient across the tile (as vector loads, hoisted in front of the tile's stores,
+// they cost the 128-query kernels up to 34 VGPRs and with them a wave per SIMD); the lane then picks its own.  Rows past Q: 0.
+__device__ __forceinline__ float row_coefficient(const float* v, int urow, int Q, int upper) {
+    const float lo = (v && urow < Q) ? v[urow] : 0.0f;
+    const float hi = (v && urow + 4 < Q) ? v[urow + 4] : 0.0f;
+    return upper ? hi : lo;
+}
+// The block of queries [q0, ...) of a
+inline ScoreAdjust adjust_from(const ScoreAdjust& a, i64 q0) {
+    ScoreAdjust r = a;
+    if (r.aq) r.aq += q0;
+    if (r.bq) r.bq += q0;
+    return r;
+}
+
 // The score slab S [Q][G]
 struct SlabEpi {
     float* S;
@@ -190,6 +223,45 @@ struct SlabEpi {
     }
 };
 
+// The adjusted score slab T [Q][G]: SlabEpi with the map applied.  The gallery side's coefficients are read once per lane
+// column, the query side's once per row (32 lanes share the address; an L2 hit after the first tile).
+struct AdjSlabEpi {
+    float* S;
+    ScoreAdjust adj;
+    template <size_t STAGE> static constexpr size_t lds_bytes() { return STAGE; }
+    template <int MT>
+    __device__ __forceinline__ void tile(f32x16 (&acc)[MT][2], float*, const float* __restrict__ ginv, const TileCtx& t) const {
+        const int Q = t.Q, m0 = t.m0;
+        const i64 G = t.G, n0 = t.n0;
+        const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+        const int wm = wave >> 1, wn = wave & 1, lr = lane & 31;
+        float gs[2], ga[2], gb[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const i64 col = n0 + wn * 64 + j * 32 + lr;
+            gs[j] = (ginv && col < G) ? ginv[col] : 1.0f;
+            ga[j] = (adj.ag && col < G) ? adj.ag[col] : 0.0f;
+            gb[j] = (adj.bg && col < G) ? adj.bg[col] : 0.0f;
+        }
+        // C[row = query][col = gallery]; lane: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
+        const int urow0 = m0 + __builtin_amdgcn_readfirstlane(wm) * MT * 32;     // wave-uniform
+#pragma unroll
+        for (int i = 0; i < MT; ++i) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int urow = urow0 + i * 32 + (r & 3) + 8 * (r >> 2), row = urow + 4 * (lane >> 5);
+                const float qa = row_coefficient(adj.aq, urow, Q, lane >> 5), qb = row_coefficient(adj.bq, urow, Q, lane >> 5);
+                if (row >= Q) continue;
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const i64 col = n0 + wn * 64 + j * 32 + lr;
+                    if (col < G) S[(i64)row * G + col] = adjusted_score(acc[i][j][r] * gs[j], qa + ga[j], qb + gb[j]);
+                }
+            }
+        }
+    }
+};
+
 constexpr size_t EPI_TILE_BYTES = (size_t)64 * (RK_BN + 4) * sizeof(float);   // the fused selection's transposed score tile
 
 // The fused selection (k <= FK): the score tile never leaves the CU, k (score, local int32 index) candidates per (query,
@@ -197,12 +269,16 @@ constexpr size_t EPI_TILE_BYTES = (size_t)64 * (RK_BN + 4) * sizeof(float);   //
 // FILT: columns the filter rejects enter the selection as key 0, i.e. never.  The tile's 128 gallery labels are read once per
 // workgroup into LDS behind the transposed tile (64 x 132 floats + 1 KB stays inside every loop's staging buffers, so the
 // LDS request and the resident workgroups per CU are those of the unfiltered kernel).
-template <int FK, bool FILT>
-struct SelectEpi {
+// Adj = ScoreAdjust (mi355_rank_topk_adjusted): the tile is written as adjusted scores and the same selection runs on it; the
+// map needs no LDS of its own.  Adj = NoAdjust takes no room in the object and compiles to the unadjusted selection.
+// The two epilogue types are SelectEpi<FK, FILT> and AdjSelectEpi<FK, FILT> below (kernel names are made of the type's name).
+template <int FK, bool FILT, class Adj>
+struct SelectTile {
     int k;
     float* cand_val;
     int* cand_idx;
     RankFilter flt;             // FILT: the filter of this call's queries
+    [[no_unique_address]] Adj adj;
     // LDS: the staging buffers, or the transposed score tile (64 rows at a time) if that is larger
     template <size_t STAGE> static constexpr size_t lds_bytes() {
         static_assert(!FILT || STAGE >= EPI_TILE_BYTES + FILT_LABELS_BYTES, "the filtered epilogue would grow the GEMM's LDS");
@@ -229,16 +305,41 @@ struct SelectEpi {
 #pragma unroll 1
         for (int h = 0; h < BM / 64; ++h) {
             if ((wm * MT * 32) / 64 == h) {            // this wave's rows belong to pass h
+                if constexpr (std::is_same_v<Adj, NoAdjust>) {
 #pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const i64 col = n0 + wn * 64 + j * 32 + lr;
-                    const float gs = (ginv && col < G) ? ginv[col] : 1.0f;
+                    for (int j = 0; j < 2; ++j) {
+                        const i64 col = n0 + wn * 64 + j * 32 + lr;
+                        const float gs = (ginv && col < G) ? ginv[col] : 1.0f;
+#pragma unroll
+                        for (int i = 0; i < MT; ++i)
+#pragma unroll
+                            for (int r = 0; r < 16; ++r) {
+                                const int row = (wm * MT * 32) % 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                                Ct[row * CLD + wn * 64 + j * 32 + lr] = acc[i][j][r] * gs;
+                            }
+                    }
+                } else {
+                    // the gallery side's coefficients once per lane column, the query side's once per row (rows past Q: 0)
+                    float gs[2], ga[2], gb[2];
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+                        const i64 col = n0 + wn * 64 + j * 32 + lr;
+                        gs[j] = (ginv && col < G) ? ginv[col] : 1.0f;
+                        ga[j] = (adj.ag && col < G) ? adj.ag[col] : 0.0f;
+                        gb[j] = (adj.bg && col < G) ? adj.bg[col] : 0.0f;
+                    }
+                    const int urow0 = m0 + h * 64 + (__builtin_amdgcn_readfirstlane(wm) * MT * 32) % 64;     // wave-uniform
 #pragma unroll
                     for (int i = 0; i < MT; ++i)
 #pragma unroll
                         for (int r = 0; r < 16; ++r) {
                             const int row = (wm * MT * 32) % 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                            Ct[row * CLD + wn * 64 + j * 32 + lr] = acc[i][j][r] * gs;
+                            const int urow = urow0 + i * 32 + (r & 3) + 8 * (r >> 2);
+                            const float qa = row_coefficient(adj.aq, urow, Q, lane >> 5);
+                            const float qb = row_coefficient(adj.bq, urow, Q, lane >> 5);
+#pragma unroll
+                            for (int j = 0; j < 2; ++j)
+                                Ct[row * CLD + wn * 64 + j * 32 + lr] = adjusted_score(acc[i][j][r] * gs[j], qa + ga[j], qb + gb[j]);
                         }
                 }
             }
@@ -308,6 +409,8 @@ struct SelectEpi {
         }
     }
 };
+template <int FK, bool FILT> struct SelectEpi : SelectTile<FK, FILT, NoAdjust> {};
+template <int FK, bool FILT> struct AdjSelectEpi : SelectTile<FK, FILT, ScoreAdjust> {};
 
 // ---- verification ROC (mi355_roc_pairs_hist[_f16]): the histogram epilogue bins every (query, gallery row) score of the
 // tile by (genuine / impostor, threshold) into a per-workgroup histogram; the score slab never exists.
@@ -960,6 +1063,9 @@ template <> inline constexpr int plain_fk<SlabEpi> = 0;
 template <int FK> constexpr int plain_fk<SelectEpi<FK, false>> = FK;
 template <class Epi> constexpr bool is_select = false;         // the fused selection (MI355_RANK_PATH_FUSED)
 template <int FK, bool FILT> constexpr bool is_select<SelectEpi<FK, FILT>> = true;
+template <int FK, bool FILT> constexpr bool is_select<AdjSelectEpi<FK, FILT>> = true;
+static_assert(sizeof(SelectEpi<1, true>) == 2 * sizeof(int) + 2 * sizeof(void*) + sizeof(RankFilter),
+              "the unadjusted selection's kernel argument keeps its layout");
 
 // What every GEMM call over Q queries shares; the epilogue object travels beside it
 struct TileArgs {
@@ -1004,10 +1110,18 @@ int cos_gemm_tiles(const TileArgs& a, const Epi& epi, hipStream_t st) {
 // fn(the fused selection's epilogue for k): it keeps FK >= k candidates per (query, column tile)
 template <bool FILT, class Fn>
 int with_select_epi(int k, float* cand_val, int* cand_idx, const RankFilter& f, Fn&& fn) {
-    if (k <= 1) return fn(SelectEpi<1, FILT>{k, cand_val, cand_idx, f});
-    if (k <= 2) return fn(SelectEpi<2, FILT>{k, cand_val, cand_idx, f});
-    if (k <= 4) return fn(SelectEpi<4, FILT>{k, cand_val, cand_idx, f});
-    return fn(SelectEpi<8, FILT>{k, cand_val, cand_idx, f});
+    if (k <= 1) return fn(SelectEpi<1, FILT>{{k, cand_val, cand_idx, f, {}}});
+    if (k <= 2) return fn(SelectEpi<2, FILT>{{k, cand_val, cand_idx, f, {}}});
+    if (k <= 4) return fn(SelectEpi<4, FILT>{{k, cand_val, cand_idx, f, {}}});
+    return fn(SelectEpi<8, FILT>{{k, cand_val, cand_idx, f, {}}});
+}
+// The same with the map of adj (this call's queries) in front of the selection
+template <bool FILT, class Fn>
+int with_adjusted_select_epi(int k, float* cand_val, int* cand_idx, const RankFilter& f, const ScoreAdjust& adj, Fn&& fn) {
+    if (k <= 1) return fn(AdjSelectEpi<1, FILT>{{k, cand_val, cand_idx, f, adj}});
+    if (k <= 2) return fn(AdjSelectEpi<2, FILT>{{k, cand_val, cand_idx, f, adj}});
+    if (k <= 4) return fn(AdjSelectEpi<4, FILT>{{k, cand_val, cand_idx, f, adj}});
+    return fn(AdjSelectEpi<8, FILT>{{k, cand_val, cand_idx, f, adj}});
 }
 
 // ---- host side of the ROC entries (roc.cpp)
@@ -1141,6 +1255,18 @@ int rank_positives(const float* queries, i64 Q, const GalleryRows& g, i64 G, int
                    const int64_t* gallery_labels, const int64_t* exclude, i64 idx_offset, const int64_t* offsets,
                    const int64_t* offsets_host, const uint64_t* pos_keys, i64 nnz, uint32_t* before, i64 query_block,
                    void* workspace, size_t workspace_bytes, size_t need, void* stream, const char* who);
+// mi355_rank_topk_adjusted[_f16] (k >= 1: out_val / out_idx [Q][k]) and mi355_cosine_scores_adjusted[_f16] (k = 0: out_val is the
+// slab [Q][G], out_idx unused): the search of mi355_rank_topk_filtered over t = s * (aq + ag) - (bq + bg).  Every Q runs on the
+// tiles (no GEMV), a prepared gallery on its fp32 rows.  query_block > 0: at most that many queries per GEMM call.
+// workspace = carve(Q, G, dim, k, planes, need_ginv, k > 0).  Arguments checked by adjust_check (scorenorm.hip).
+GalleryRows f32_rows(const float* gallery, int is_normalized);
+int adjusted_search(const float* queries, i64 Q, const GalleryRows& g, i64 G, int dim, float eps, int k, i64 idx_offset,
+                    const ScoreAdjust& adj, const RankFilter* filt, i64 query_block, float* out_val, i64* out_idx, void* workspace,
+                    size_t workspace_bytes, hipStream_t st, const char* who);
+// The checks the adjusted entries share, before any HIP call; fills *adj and, with a filter, *f
+int adjust_check(const void* queries, i64 Q, const GalleryRows& g, i64 G, int dim, int k, bool topk, const mi355_score_adjust* adjust,
+                 const mi355_rank_filter* filter, i64 idx_offset, i64 query_block, const void* out_val, const void* out_idx,
+                 const char* who, ScoreAdjust* adj, RankFilter* f);
 // mi355_nearest_centroid[_f16]: workspace = the keys best[G], then carve(K, G, dim, 0, planes, need_ginv).  need_ginv: room
 // for 1 / |row| of fp32 rows that are not normalised (the fp32 sizer always counts it: it does not know the rows).
 size_t nearest_ws_bytes(i64 K, i64 G, int dim, size_t (*planes_bytes)(i64, int), bool need_ginv);

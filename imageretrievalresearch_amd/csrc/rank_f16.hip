@@ -211,6 +211,16 @@ template int cos_gemm_f16(const void*, int, const float*, void*, i64, i64, int, 
 template int cos_gemm_f16(const void*, int, const float*, void*, i64, i64, int, const NearestEpi&, hipStream_t);
 template int cos_gemm_f16(const void*, int, const float*, void*, i64, i64, int, const DegreeEpi&, hipStream_t);
 template int cos_gemm_f16(const void*, int, const float*, void*, i64, i64, int, const LinkEpi&, hipStream_t);
+// the adjusted scores (adjusted_search, rank.hip): the slab and the fused selection with the map in front of it
+template int cos_gemm_f16(const void*, int, const float*, void*, i64, i64, int, const AdjSlabEpi&, hipStream_t);
+#define ADJ_SELECT_F16(FK)                                                                                                  \
+    template int cos_gemm_f16(const void*, int, const float*, void*, i64, i64, int, const AdjSelectEpi<FK, false>&, hipStream_t); \
+    template int cos_gemm_f16(const void*, int, const float*, void*, i64, i64, int, const AdjSelectEpi<FK, true>&, hipStream_t);
+ADJ_SELECT_F16(1)
+ADJ_SELECT_F16(2)
+ADJ_SELECT_F16(4)
+ADJ_SELECT_F16(8)
+#undef ADJ_SELECT_F16
 
 static GalleryRows f16_rows(const void* gallery_f16, int dim) { return {nullptr, true, gallery_f16, f16_ld(dim), f16_planes_bytes}; }
 
@@ -257,6 +267,39 @@ int mi355_rank_topk_f16_filtered(const float* queries, int64_t Q, const void* ga
     MI355_REQUIRE(filter, "rank_topk_f16_filtered: null filter (use the unfiltered entry)");
     return rank_topk_rows<F16Rows>(queries, Q, gallery_f16, nullptr, G, dim, k, eps, idx_offset, out_val, out_idx, workspace,
                                    workspace_bytes, stream, filter, "rank_topk_f16_filtered");
+}
+
+size_t mi355_rank_adjusted_f16_workspace_bytes(int64_t Q, int64_t G, int dim, int k) {
+    if (Q < 1 || G < 1 || dim < 1 || k < 0 || k > LARGE_K) return 0;
+    return carve(nullptr, Q, G, dim, k, f16_planes_bytes, false, k > 0).total;   // (no GEMV: the planes at every Q)
+}
+
+int mi355_rank_topk_adjusted_f16(const float* queries, int64_t Q, const void* gallery_f16, int64_t G, int dim, int k, float eps,
+                                 int64_t idx_offset, const mi355_score_adjust* adjust, const mi355_rank_filter* filter,
+                                 int64_t query_block, float* out_val, int64_t* out_idx, void* workspace, size_t workspace_bytes,
+                                 void* stream) {
+    const GalleryRows g = f16_rows(gallery_f16, dim < 1 ? 1 : dim);
+    ScoreAdjust adj{};
+    RankFilter f{};
+    if (int e = adjust_check(queries, Q, g, G, dim, k, true, adjust, filter, idx_offset, query_block, out_val, out_idx,
+                             "rank_topk_adjusted_f16", &adj, &f))
+        return e;
+    if (Q == 0) return OK;
+    return adjusted_search(queries, Q, g, G, dim, eps, k, idx_offset, adj, filter ? &f : nullptr, query_block, out_val, (i64*)out_idx,
+                           workspace, workspace_bytes, (hipStream_t)stream, "rank_topk_adjusted_f16");
+}
+
+int mi355_cosine_scores_adjusted_f16(const float* queries, int64_t Q, const void* gallery_f16, int64_t G, int dim, float eps,
+                                     const mi355_score_adjust* adjust, int64_t query_block, float* out, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+    const GalleryRows g = f16_rows(gallery_f16, dim < 1 ? 1 : dim);
+    ScoreAdjust adj{};
+    if (int e = adjust_check(queries, Q, g, G, dim, 0, false, adjust, nullptr, 0, query_block, out, nullptr,
+                             "cosine_scores_adjusted_f16", &adj, nullptr))
+        return e;
+    if (Q == 0) return OK;
+    return adjusted_search(queries, Q, g, G, dim, eps, 0, 0, adj, nullptr, query_block, out, nullptr, workspace, workspace_bytes,
+                           (hipStream_t)stream, "cosine_scores_adjusted_f16");
 }
 
 size_t mi355_roc_pairs_f16_workspace_bytes(int64_t Q, int64_t G, int dim) {

@@ -845,7 +845,37 @@ class _Diversified:
                              stats=stats, block=block)
 
 
-class Gallery(_RowStore, _GraphIndexed, _DensityClustered, _Diffused, _Diversified):
+class _ScoreNormed:
+    """``Gallery.score_norm``, ``Gallery.search_normed`` and ``Gallery.neighbourhood_stats`` (scorenorm.py).  They live in a base of
+    ``Gallery`` for the reason ``_Diversified`` does: the module's names are exported lazily and the side-stream case is
+    tests/test_scorenorm_streams_gpu.py, not a row of the stream table, which lists what ``Gallery`` itself defines."""
+
+    def neighbourhood_stats(self, cohort, n: int | None = None, exclude: torch.Tensor | None = None):
+        """(mean, std, count) of each resident row's ``n`` largest cosines against ``cohort`` (a (C, D) tensor or a ``Gallery``;
+        ``n=None``: the whole cohort, at most 1024 rows): float64 sums, the population deviation.  ``exclude`` (rows,) int64 leaves
+        one cohort row out per resident row, for a cohort that contains the rows themselves."""
+        from . import scorenorm as _sn
+        return _sn.neighbourhood_stats(self.data, cohort, n, exclude=exclude, eps=self.eps)
+
+    def score_norm(self, cohort, kind: str = "csls", n: int | None = None, min_std: float = 1e-6):
+        """A ``ScoreNorm`` of this gallery (scorenorm.py): ``kind="csls"`` removes hubs (``cohort``: samples of the query domain;
+        n = 10), "znorm" / "tnorm" / "snorm" centre and scale a pair's score by each side's scores against an impostor ``cohort``
+        (``n=None``: the whole cohort; a given n: the adaptive variant).  Fit again after ``add``."""
+        from . import scorenorm as _sn
+        return _sn.ScoreNorm.fit(self, cohort, kind, n, min_std)
+
+    def search_normed(self, queries: torch.Tensor, k: int, norm, idx_offset: int = 0, *, query_labels: torch.Tensor | None = None,
+                      label_filter: str | None = None, exclude: torch.Tensor | None = None):
+        """``search`` over the scores that ``norm`` (``score_norm``) adjusts: (adjusted values (Q, k) fp32, indices (Q, k) int64),
+        descending, ties to the lower index; the filter arguments as in ``search``.  The adjustment runs inside the cosine GEMM in
+        front of the fused selection; a prepared gallery is searched on its fp32 rows (same results)."""
+        from . import scorenorm as _sn
+        if not isinstance(norm, _sn.ScoreNorm):
+            raise MI355Error(f"norm must be a ScoreNorm (Gallery.score_norm), got {type(norm).__name__}")
+        return norm.search(self, queries, k, idx_offset, query_labels=query_labels, label_filter=label_filter, exclude=exclude)
+
+
+class Gallery(_RowStore, _GraphIndexed, _DensityClustered, _Diffused, _Diversified, _ScoreNormed):
     """Resident gallery: rows are L2-normalised once when added and stay in HBM (the gallery is *born* on the
     GPU that embedded it).  ``search`` is then one fused call per query batch instead of the reference's per-query cosine +
     topk pair.

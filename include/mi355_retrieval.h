@@ -127,6 +127,52 @@ int mi355_rank_topk_filtered(const float* queries, int64_t Q, const float* galle
 int mi355_rank_topk_f16_filtered(const float* queries, int64_t Q, const void* gallery_f16, int64_t G, int dim, int k, float eps,
                                  int64_t idx_offset, const mi355_rank_filter* filter, float* out_val, int64_t* out_idx,
                                  void* workspace, size_t workspace_bytes, void* stream);
+/* Adjusted scores: CSLS (Conneau et al., ICLR 2018) and cohort normalisation (Z-, T-, S-norm) are one affine map of the score
+ * with per-query and per-gallery-row coefficients.  For query q and gallery row g, in fp32 and without fused multiply-add:
+ *   s = the pair's score as the tiled GEMM of the rows leaves it (fp32 rows: acc * 1/|row|; fp16 rows: the f16 loop's score)
+ *   w = aq[q] + ag[g],  c = bq[q] + bg[g]          (a NULL vector counts as 0.0f; at least one of aq / ag is given)
+ *   t = fp32(fp32(s * w) - c)
+ * aq / bq [Q], ag / bg [G]: device fp32.  mi355_rank_topk_adjusted is the filtered search over t (filter NULL: every row is
+ * eligible): descending t, ties to the lower index, NaN largest, (-inf, -1) beyond the eligible rows, and t is what is
+ * returned.  For k <= 8 and Q > 4 the map is applied where the fused selection writes its score tile, so no Q x G slab exists;
+ * other shapes select from the adjusted slab.  Every Q runs on the tiles (Q <= 4 has no GEMV here): t depends on the pair and
+ * the four coefficients alone, not on Q, k, the tile height, the two-launch cut or query_block (> 0: at most that many queries
+ * per GEMM call; 0: the library's rule).  mi355_cosine_scores_adjusted writes the slab t [Q][G].  A prepared gallery is searched
+ * on its fp32 rows.  Workspace: mi355_rank_adjusted[_f16]_workspace_bytes(Q, G, dim, k), k = 0 for the slab entries.
+ * Errors (before any HIP call): a null pointer, aq and ag both NULL, k outside [1, 1024], k > G, a short workspace, fp16 rows
+ * that are not 16-byte aligned. */
+typedef struct mi355_score_adjust {
+    const float* aq;
+    const float* bq;
+    const float* ag;
+    const float* bg;
+} mi355_score_adjust;
+size_t mi355_rank_adjusted_workspace_bytes(int64_t Q, int64_t G, int dim, int k);
+size_t mi355_rank_adjusted_f16_workspace_bytes(int64_t Q, int64_t G, int dim, int k);
+int mi355_rank_topk_adjusted(const float* queries, int64_t Q, const float* gallery, int64_t G, int dim, int gallery_is_normalized,
+                             int k, float eps, int64_t idx_offset, const mi355_score_adjust* adjust, const mi355_rank_filter* filter,
+                             int64_t query_block, float* out_val, int64_t* out_idx, void* workspace, size_t workspace_bytes,
+                             void* stream);
+int mi355_rank_topk_adjusted_f16(const float* queries, int64_t Q, const void* gallery_f16, int64_t G, int dim, int k, float eps,
+                                 int64_t idx_offset, const mi355_score_adjust* adjust, const mi355_rank_filter* filter,
+                                 int64_t query_block, float* out_val, int64_t* out_idx, void* workspace, size_t workspace_bytes,
+                                 void* stream);
+int mi355_cosine_scores_adjusted(const float* queries, int64_t Q, const float* gallery, int64_t G, int dim, int gallery_is_normalized,
+                                 float eps, const mi355_score_adjust* adjust, int64_t query_block, float* out, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+int mi355_cosine_scores_adjusted_f16(const float* queries, int64_t Q, const void* gallery_f16, int64_t G, int dim, float eps,
+                                     const mi355_score_adjust* adjust, int64_t query_block, float* out, void* workspace,
+                                     size_t workspace_bytes, void* stream);
+/* Statistics of a top-n result val / idx [N][n] (a search's output; idx < 0: a pad), one row each, in float64:
+ *   count[r] = the real entries (idx >= 0);  sum = their values added in slot order;  mean64 = sum / count;
+ *   std64 = sqrt(sum of (value - mean64)^2 in slot order / count)   (the population deviation)
+ * mean[r] = fp32(mean64), std[r] = fp32(std64); a row with no real entry gives mean 0 and std 0.  With a / b (both or neither):
+ * std_f = max(std64, min_std), a[r] = fp32(half / std_f), b[r] = fp32(mean64 * half / std_f): the coefficients of a cohort
+ * normalisation (half = 1 for a one-sided norm, 0.5 for each side of S-norm).  1 <= n <= 1024; half and min_std finite,
+ * min_std >= 0. */
+int mi355_topn_stats(const float* val, const int64_t* idx, int64_t N, int n, double half, double min_std, float* mean, float* std,
+                     int32_t* count, float* a, float* b, void* stream);
+
 /* The branch the calling thread's last mi355_rank_topk* call took: MI355_RANK_PATH_* of the score stage, | FUSED when the
  * selection ran in the GEMM epilogue, | BITONIC when a score slab was selected with k > 8 (else the small-k selection). */
 enum {
