@@ -5,6 +5,22 @@ import numpy as np
 
 F32 = np.float32
 
+# A row of amax = 127 * 2^e taken as it is has inv = 2^-e exactly, so n_i * inv is exact and these elements (times 2^e) are
+# exact ties of rintf: (k + 0.5) for k = 0, 1, 2, 3, 125, 126 and their negatives; then the ends, and two elements off a tie
+TIES = np.array([0.5, 1.5, 2.5, 3.5, 125.5, 126.5, -0.5, -1.5, -2.5, -3.5, -125.5, -126.5,
+                 127.0, -127.0, 126.75, 0.25, -0.25], dtype=F32)
+TIE_CODES = np.array([0, 2, 2, 4, 126, 126, 0, -2, -2, -4, -126, -126, 127, -127, 127, 0, 0], dtype=np.int8)   # half to even
+TIE_EXPONENTS = (0, -3, 6)
+
+
+def tie_rows(D):
+    """(rows float32 [3][D], codes int8 [D], scales float32 [3]): TIES repeated along a row of D >= len(TIES) elements, scaled
+    by 2^e for each e of TIE_EXPONENTS, with the codes and scales the contract gives them (the same codes for every e)."""
+    assert D >= len(TIES)
+    sel = np.arange(D) % len(TIES)
+    rows = np.stack([TIES[sel] * F32(2.0 ** e) for e in TIE_EXPONENTS]).astype(F32)
+    return rows, TIE_CODES[sel], np.array([2.0 ** e for e in TIE_EXPONENTS], dtype=F32)
+
 
 def quantize_rows(n):
     """(codes int8 [R][D], scales float32 [R]) of the float32 rows n (normalised already)."""

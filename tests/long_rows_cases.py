@@ -1,6 +1,6 @@
 """The inputs and the modelled bugs of the long-row tests (test_long_rows_gpu.py on the GPU, test_long_rows_args.py without
 one): rows so long that the row walkers take a second trip of their 4 x 64-unit loop, and dims on either side of every step
-of the IVF scan's group size.  NumPy only.
+of the IVF scan's group size (over fp32, fp16 and int8 rows).  NumPy only.
 
 The constants below are restated from the kernels they aim at: row_dot.h and k_cos_gemv_f16 walk 4 x 64 units of 8 halves
 (2048 elements) per trip, row_dot's fp32 branch 4 x 64 units of 4 floats (1024), k_cos_gemv_i8 4 x 64 units of 16 codes (4096).
@@ -27,6 +27,13 @@ IVF_LENGTHS = [64, 0, 1, 65, 70]                                     # five hand
 IVF_G, IVF_Q = sum(IVF_LENGTHS), 9
 IVF_PROBES = [3, 1, 4, 0, 2]                                         # every query probes every list in this order
 
+# IVF scan over int8 rows: a query is two int8 planes of lq = dim rounded up to 128 bytes, the group of ivf_group_i8() is
+# min(8, 64 KB / (2 * lq)) queries - 8, then both sides of 8 -> 7 ... and 2 -> 1, and the one query that fills the 64 KB alone
+I8_SEGMENT, IVF_LDS, IVF_MAXQ_I8 = 128, 64 * 1024, 8
+IVF_DIMS_I8 = [4096, 4100, 8192, 8200, 16384, 16400, 32768]
+IVF_GROUP_I8 = {4096: 8, 4100: 7, 8192: 4, 8200: 3, 16384: 2, 16400: 1, 32768: 1}
+IVF_SPLIT_I8 = {8: [8, 1], 7: [7, 2], 4: [4, 4, 1], 3: [3, 3, 3], 2: [2, 2, 2, 2, 1], 1: [1] * 9}         # of the 9 queries of one list
+
 # The GEMVs behind search(q[:Q], k): (D, Q) -> whether the LDS rule lets the GEMV run
 GEMV_G = 1000
 GEMV_F16 = {(D, Q): Q * D * 4 <= 64 * 1024 for D in (2048, 2112, 4096, 4160) for Q in (1, 2, 3, 4)}      # D = ld (a multiple of 64)
@@ -43,6 +50,16 @@ def ldq(D, kind):
 def ivf_nq(D, kind):
     """Queries of one group of the IVF scan (ivf_group): 0 when not even one fits."""
     return min(4, (64 * 1024) // (ldq(D, kind) * 4))
+
+
+def lq_i8(D):
+    """Bytes of one int8 plane of a query in LDS: dim rounded up to a 128-byte segment (i8_ld)."""
+    return (D + I8_SEGMENT - 1) // I8_SEGMENT * I8_SEGMENT
+
+
+def ivf_nq_i8(D):
+    """Queries of one group of the IVF scan over int8 rows (ivf_group_i8): 0 when not even one fits."""
+    return min(IVF_MAXQ_I8, IVF_LDS // (2 * lq_i8(D)))
 
 
 def raw(kind, seed, n, D):

@@ -67,6 +67,27 @@ def test_plane_ranges(D, kind):
     assert acc_hi < 2 ** 24                                          # float(acc_hi) is exact at these widths
 
 
+def test_exact_ties_go_to_the_even_code():
+    """The model against the codes written out by hand: half to even, never half away from zero or half up."""
+    assert R.TIES.tolist() == [0.5, 1.5, 2.5, 3.5, 125.5, 126.5, -0.5, -1.5, -2.5, -3.5, -125.5, -126.5, 127, -127, 126.75, 0.25, -0.25]
+    assert R.TIE_CODES.tolist() == [0, 2, 2, 4, 126, 126, 0, -2, -2, -4, -126, -126, 127, -127, 127, 0, 0]
+    away = np.sign(R.TIES) * np.floor(np.abs(R.TIES) + F32(0.5))     # half away from zero, and half up: both miss ties
+    assert (away.astype(np.int8) != R.TIE_CODES).sum() == 6 and (np.floor(R.TIES + F32(0.5)).astype(np.int8) != R.TIE_CODES).sum() == 6
+    for D in (17, 68, 70):
+        rows, want, scales = R.tie_rows(D)
+        assert rows.dtype == F32 and (np.abs(rows).max(axis=1) == F32(127) * scales).all()
+        assert (rows[1] * F32(8) == rows[0]).all() and (rows[2] == rows[0] * F32(64)).all()         # the scalings are exact
+        codes, s = R.quantize_rows(rows)
+        assert (codes == want[None, :]).all() and (want[:17] == R.TIE_CODES).all()
+        assert (s.view(np.int32) == scales.view(np.int32)).all() and scales.tolist() == [1.0, 0.125, 64.0]
+        assert (codes.view(np.uint8)[:, 6] == 0).all()               # -0.5 -> the byte 0x00
+    n = np.full((2, 8), 0.25, F32)
+    n[0, 5] = np.inf                                                 # a non-finite amax without a NaN element
+    n[1] = F32(1e-31) * np.array([1, -1, 0.5, 0, 1, 0.25, -0.5, 1], F32)   # a non-zero row below 1e-30
+    codes, s = R.quantize_rows(n)
+    assert not np.isnan(n).any() and (codes == 0).all() and np.isnan(s[0]) and s[1] == 0 and np.abs(n[1]).max() == F32(1e-31)
+
+
 def test_special_rows():
     n = np.zeros((5, 8), F32)
     n[1, 3] = np.nan

@@ -1,14 +1,17 @@
 """The long-row cases without a GPU (tests/long_rows_cases.py, the inputs of test_long_rows_gpu.py): the float64 reference
 leaves the tolerance to the kernels - a plain float32 dot of the same operands stays within a tenth of SCORE_TOL of it at every
 dim used - and each bug the GPU tests are there to catch moves some score of every case it applies to by more than ten times
-SCORE_TOL.  Also the restated constants: the group size of the IVF scan per dim, and which side of its LDS rule every GEMV
-case lies on."""
+SCORE_TOL.  Also the restated constants: the group size of the IVF scan per dim (over int8 rows: against the constants and the
+rule read from ivf.hip), and which side of its LDS rule every GEMV case lies on."""
+import os
+import re
+
 import numpy as np
 import pytest
 
 import ivf_ref
 import long_rows_cases as C
-from helpers import SCORE_TOL
+from helpers import ROOT, SCORE_TOL
 
 KINDS = ("f16", "f32")
 
@@ -83,6 +86,29 @@ def test_the_group_size_steps_where_the_cases_say():
     assert [len(g) for g in C.ivf_groups(2)] == [2, 2, 2, 2, 1] and [len(g) for g in C.ivf_groups(1)] == [1] * 9
     assert sum(C.IVF_LENGTHS) == 200 and 0 in C.IVF_LENGTHS and sorted(C.IVF_PROBES) == list(range(5))
     assert (np.bincount(C.ivf_assign(), minlength=5) == C.IVF_LENGTHS).all()
+
+
+def test_the_int8_group_size_is_the_rule_of_the_scan():
+    """The restated rule against the constants and the expression of ivf.hip, and every step of it against the cases."""
+    csrc = os.path.join(ROOT, "imageretrievalresearch_amd", "csrc")
+    src, quant = open(os.path.join(csrc, "ivf.hip")).read(), open(os.path.join(csrc, "i8_quant.h")).read()
+    assert int(re.search(r"constexpr int IVF_NQ_I8 = (\d+);", src).group(1)) == C.IVF_MAXQ_I8 == 8
+    lds = re.search(r"constexpr size_t IVF_LDS = (\d+) \* (\d+);", src)
+    assert int(lds.group(1)) * int(lds.group(2)) == C.IVF_LDS == 65536
+    assert int(re.search(r"constexpr int I8_KSTEP = (\d+);", quant).group(1)) == C.I8_SEGMENT == 128
+    assert "(dim + I8_KSTEP - 1) / I8_KSTEP * I8_KSTEP" in quant
+    rule = src[src.index("static int ivf_group_i8(int lq)"):src.index("static bool ivf_shape_ok")]
+    assert "const size_t fit = IVF_LDS / ((size_t)2 * lq);" in rule
+    assert "return (int)(fit < (size_t)IVF_NQ_I8 ? fit : (size_t)IVF_NQ_I8);" in rule
+    assert "const int lq = i8_ld(dim), nq = ivf_group_i8(lq);" in src and "const size_t lds = (size_t)nq * 2 * lq;" in src
+    got = {D: C.ivf_nq_i8(D) for D in C.IVF_DIMS_I8}
+    assert got == C.IVF_GROUP_I8 == {4096: 8, 4100: 7, 8192: 4, 8200: 3, 16384: 2, 16400: 1, 32768: 1}
+    assert [C.lq_i8(D) for D in C.IVF_DIMS_I8] == [4096, 4224, 8192, 8320, 16384, 16512, 32768]
+    for nq, split in C.IVF_SPLIT_I8.items():
+        assert [len(g) for g in C.ivf_groups(nq)] == split and sum(split) == C.IVF_Q == 9
+    assert sorted(C.IVF_SPLIT_I8) == sorted(set(got.values())) == [1, 2, 3, 4, 7, 8]
+    assert C.ivf_nq_i8(32768) * 2 * C.lq_i8(32768) == C.IVF_LDS and C.ivf_nq_i8(32769) == 0      # the whole 64 KB; past it
+    assert all(D > C.FIRST_TRIP["i8"] for D in C.IVF_DIMS_I8[1:]) and C.IVF_DIMS_I8[0] == C.FIRST_TRIP["i8"]
 
 
 def test_every_gemv_rule_has_a_case_on_either_side():

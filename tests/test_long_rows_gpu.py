@@ -1,6 +1,6 @@
 """Rows longer than one trip of the row walkers, on the GPU against float64 (int8: against the NumPy model, bit for bit).  The
 shapes sit on the constants of the code (tests/long_rows_cases.py restates them): the second trip of row_dot (row_dot.h: the
-IVF scan, mi355_rescore_candidates, the graph walk) and of the three GEMVs, every group size of ivf_group() with both sides of
+IVF scan, mi355_rescore_candidates, the graph walk) and of the three GEMVs, every group size of ivf_group() and ivf_group_i8() with both sides of
 each step, and both sides of each GEMV's LDS rule - the side past it being "Q <= 4, but the GEMM runs".  Each case asserts the
 condition it is there for: the reported rank path, or the group size its dim implies.  test_long_rows_args.py shows without a
 GPU that the reference keeps nine tenths of SCORE_TOL for the kernels and that a dropped, repeated or misplaced trip cannot
@@ -13,10 +13,11 @@ import torch
 
 import gallery_i8_ref as R8
 import imageretrievalresearch_amd as M
+import ivf_i8_ref as R8I
 import ivf_ref as ref
 import long_rows_cases as C
 from helpers import SCORE_TOL, assert_topk_matches
-from imageretrievalresearch_amd import _lib
+from imageretrievalresearch_amd import _lib, ivf_i8
 from imageretrievalresearch_amd import rank as _rank
 from test_gallery_f16_gpu import _check_topk
 
@@ -131,6 +132,48 @@ def test_ivf_scan_refuses_a_query_past_the_lds(kind):
     ix = M.IVFIndex(g, _dev(C.raw(kind, 3, 2, D)), _dev(a))
     with pytest.raises(M.MI355Error, match="too large"):
         ix.search(_dev(C.raw(kind, 2, 2, D)), 3, probes=_dev(np.array([[0, 1], [1, 0]], np.int64)))
+
+
+@pytest.mark.parametrize("D", C.IVF_DIMS_I8)
+def test_ivf_i8_scan_at_every_group_size(D):
+    """Int8IVFIndex over the same five lists at every step of ivf_group_i8: the candidate slab and the search against the
+    NumPy model of the int8 score restricted to the probed lists, bit for bit.  D = 32768: one query's planes are the whole
+    64 KB of LDS."""
+    nq, lq, Q = C.ivf_nq_i8(D), C.lq_i8(D), C.IVF_Q
+    assert nq == C.IVF_GROUP_I8[D] and [len(g) for g in C.ivf_groups(nq)] == C.IVF_SPLIT_I8[nq]
+    assert nq * 2 * lq <= C.IVF_LDS and (nq == C.IVF_MAXQ_I8 or (nq + 1) * 2 * lq > C.IVF_LDS)
+    assert D != 32768 or (nq, 2 * lq) == (1, C.IVF_LDS)
+    a, offsets, order = _lists()
+    xt, q = _dev(C.raw("i8", 1, C.IVF_G, D)), _dev(C.raw("i8", 2, Q, D))
+    gal = M.Int8Gallery(D, DEV).add(xt)
+    assert gal._codes.shape[1] == lq
+    ix = ivf_i8.Int8IVFIndex(gal, _dev(C.raw("i8", 3, len(C.IVF_LENGTHS), D)), _dev(a))
+    assert (ix.offsets.cpu().numpy() == offsets).all() and (ix.order.cpu().numpy() == order).all()
+    codes, s_g = R8.quantize_rows(M.l2_normalize_rows(xt).cpu().numpy())
+    assert (gal.codes.cpu().numpy() == codes).all() and (_bits(gal.scales) == s_g.view(np.int32)).all()
+    s = R8I.pair_scores(M.l2_normalize_rows(q).cpu().numpy(), codes, s_g)
+    assert np.isfinite(s).all()
+    p = np.tile(np.array(C.IVF_PROBES, np.int64), (Q, 1))            # the same lists for all: the groups are whole
+    pt = _dev(p)
+    want = ref.probed_rows(offsets, order, p[0])
+    assert want.size == C.IVF_G and sorted(want.tolist()) == list(range(C.IVF_G))
+    for cap in (C.IVF_G, C.IVF_G + 5):                               # the slab ends with the lists; five pads behind them
+        cv, ci = ix._scan(q, pt, cap, 0, None)
+        wv, wi = R8I.slab(s, offsets, order, p, cap)
+        assert (wi[:, :C.IVF_G] == want[None, :]).all() and (wi[:, C.IVF_G:] == R8I.NO_CAND).all()
+        assert (ci.cpu().numpy() == wi).all(), (D, cap)
+        assert (_bits(cv) == wv.view(np.int32)).all(), (D, cap)
+    for k in (3, 9):
+        v, i = ix.search(q, k, probes=pt)
+        wv, wi = R8I.search(s, offsets, order, p, k)
+        assert (i.cpu().numpy() == wi).all() and (_bits(v) == wv.view(np.int32)).all(), (D, k)
+        ev, ei = gal.search(q, k)                                    # every list probed: the exhaustive search's bits
+        assert _path() == I8_GEMM, (D, k, _path())
+        assert (_bits(ev) == _bits(v)).all() and (_bits(ei) == _bits(i)).all(), (D, k)
+        # a query searched alone (a group of one) gives the bits it gives inside its group
+        for j in range(Q):
+            v1, i1 = ix.search(q[j: j + 1], k, probes=pt[j: j + 1])
+            assert (_bits(v1[0]) == _bits(v[j])).all() and (_bits(i1[0]) == _bits(i[j])).all(), (D, k, j)
 
 
 # ---- c. the three GEMVs, and the GEMM just past their LDS rules
